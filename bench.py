@@ -3,7 +3,7 @@
 discriminator, three optimizer steps; experiments/new_betavaegan.py:87-193 of the
 reference) in images/s on N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 128]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 128] [--full] [--dump-outputs DIR]
 
 One process per GPU; per-GPU batch 128 (BASELINE.json configs[1] at N=1; configs[2]
 = global batch 1024 at N=8: weak scaling).  ``--gpus N`` with N > 1 STARTS the N ranks
@@ -22,6 +22,16 @@ forces eager).  Launches inside a replayed graph cannot be bracketed by events, 
 timed in an eager leg of the same K iterations right after the timed region (``roofline.launches_timed_in``).  Under
 N > 1 the iteration stays eager (the gradient exchange is launched from autograd hooks) and the line carries
 ``data_parallel``: ranks the transport connected, bytes all-reduced and time the compute stream waited per step.
+
+A plain run does only what the headline needs: set-up (including the graph capture), W warm-up steps, the K timed
+steps, the optional output dump and the line.  ``--full`` adds everything else, each leg a run of its own outside the
+timed region: the instrumented iteration that finds the dominant launch, the ``roofline`` leg, the ``regime`` probe,
+the other arithmetics (``--no-opt-in`` skips them) and the CPU baseline (``--no-cpu-baseline`` skips it).
+
+``--dump-outputs DIR`` writes what the last timed step computed, as float32 ``.npy`` files: the nine loss scalars the
+step returns (``<name>.npy``) and, for each network, a fixed seeded sample of 2^20 entries of its state after that
+step's optimizer updates (``netEG_state_sample.npy``, ``netD_state_sample.npy``; state_dict order, floating entries).
+Inputs and weights are seeded, so two builds can be compared output for output.
 
 ``--rehearse-launch``: the same launch path without a GPU -- every rank joins a gloo group,
 the world is checked with an all-reduce and rank 0 prints a line marked "rehearsal" (no
@@ -155,6 +165,24 @@ def cpu_baseline(batch, beta):
                                               f"(min {min(ts_v):.3f} s, max {max(ts_v):.3f} s)"}}
 
 
+DUMP_STATE_SAMPLE = 1 << 20        # entries of each network's state written by --dump-outputs (4 MB each)
+
+
+def dump_outputs(path, out, tr):
+    """--dump-outputs: the loss scalars of the last timed step and a seeded sample (the same indices in every run) of
+    each network's floating state_dict entries, flattened in state_dict order, after that step's optimizer updates."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        v = v.detach().cpu()
+        np.save(os.path.join(path, k + ".npy"), (v.double() if v.dtype == torch.float64 else v.float()).numpy())
+    for name, net in (("netEG", tr.netEG), ("netD", tr.netD)):
+        flat = torch.cat([t.detach().reshape(-1).float() for t in net.state_dict().values() if t.is_floating_point()])
+        idx = torch.randint(flat.numel(), (DUMP_STATE_SAMPLE,), generator=torch.Generator().manual_seed(0))
+        np.save(os.path.join(path, name + "_state_sample.npy"), flat[idx.to(flat.device)].cpu().numpy())
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -202,10 +230,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=128, help="per-GPU batch")
     ap.add_argument("--beta", type=float, default=25.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-opt-in", action="store_true", help="skip the informational legs in the other arithmetics")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline and regime legs, the other arithmetics and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-opt-in", action="store_true", help="with --full: skip the informational legs in the other arithmetics")
     ap.add_argument("--rehearse-launch", action="store_true", help="exercise the N-rank launch on CPU (gloo); no measurement")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args, sys.argv[1:]))       # nothing above touched the GPU
@@ -285,20 +318,22 @@ def main():
         wall = time.perf_counter() - t0
         return wall, [marks[i].elapsed_time(marks[i + 1]) for i in range(n)], o
 
-    # ---- untimed preparation: one instrumented (eager) iteration times every convolution launch to find the dominant
-    # one; a single-process trainer captures the iteration in a HIP graph on its third iteration of this shape
-    # (trainer.GRAPH_WARM_STEPS eager ones first) -- all of that happens here, before the W warm-up steps
+    # ---- untimed preparation: a single-process trainer captures the iteration in a HIP graph on its third iteration of
+    # this shape (trainer.GRAPH_WARM_STEPS eager ones first); under --full one instrumented (eager) iteration then times
+    # every convolution launch to find the dominant one -- all of that happens here, before the W warm-up steps
     prep_steps = GRAPH_PREP_STEPS if tr.graph else 1
     for _ in range(prep_steps):
         one_step()
     graphed = bool(tr.graph and tr._graphs)
-    ops.start_timing()                              # (an instrumented iteration is always eager)
-    one_step()
-    prep_steps += 1
-    per_key = ops.stop_timing()
-    totals = {k: sum(v) for k, v in per_key.items()}
-    dominant = max(totals, key=totals.get) if totals else None
-    conv_ms_profiled = sum(totals.values())
+    dominant = conv_ms_profiled = None
+    if args.full:
+        ops.start_timing()                          # (an instrumented iteration is always eager)
+        one_step()
+        prep_steps += 1
+        per_key = ops.stop_timing()
+        totals = {k: sum(v) for k, v in per_key.items()}
+        dominant = max(totals, key=totals.get) if totals else None
+        conv_ms_profiled = sum(totals.values())
     # The preparation above has already trained for prep_steps iterations on this one synthetic batch, and on it the
     # discriminator saturates within a few iterations (the fake path's gradients then underflow and their launches
     # run on near-zero operands, which the chip clocks higher): go back to the initial weights and optimizer state, in
@@ -312,12 +347,15 @@ def main():
     for f in flats:
         f.reset_stats()
         f.time_finish = True
-    if not graphed:
+    time_dominant_in_place = dominant is not None and not graphed
+    if time_dominant_in_place:
         ops.start_timing(only=dominant)             # eager launches: the dominant kernel is bracketed in place
     elapsed, step_ms, out = timed_steps(args.steps)
     host_ms = timed_steps.host_ms
-    dom_ms = ops.stop_timing().get(dominant, []) if not graphed else []
+    dom_ms = ops.stop_timing().get(dominant, []) if time_dominant_in_place else []
     out = {k: v.clone() for k, v in out.items()}
+    if args.dump_outputs and rank == 0:             # before any later leg moves the weights on
+        dump_outputs(args.dump_outputs, out, tr)
     comm = None
     if world > 1 or alone:
         ranks = torch.ones(1, device=dev)
@@ -335,21 +373,22 @@ def main():
                                else "eager (collectives launched from autograd hooks)"}
     for f in flats:
         f.time_finish = False
-    # what regime the last timed step ran in: mean D(x), and how much of the gradient that D sends back into the decoder
-    # through the generated batch is exactly zero (one probed -- eager -- iteration right after the timed region)
+    # what regime the last timed step ran in: mean D(x), and (--full) how much of the gradient that D sends back into the
+    # decoder through the generated batch is exactly zero (one probed -- eager -- iteration right after the timed region)
     regime = {"D_x_mean_last_timed_step": round(float(out["D_x_sum"]) / B, 6),
               "iterations_since_initial_weights": args.warmup + args.steps}
-    def _probe(name, gten):
-        regime["fake_path_gy_zero_fraction"] = round(float((gten == 0).float().mean()), 6)
-        regime["fake_path_gy_absmax"] = float(gten.abs().max())
-    tr.probe = _probe
-    one_step()
-    tr.probe = None
+    if args.full:
+        def _probe(name, gten):
+            regime["fake_path_gy_zero_fraction"] = round(float((gten == 0).float().mean()), 6)
+            regime["fake_path_gy_absmax"] = float(gten.abs().max())
+        tr.probe = _probe
+        one_step()
+        tr.probe = None
 
     # ---- launches inside a replayed graph cannot be bracketed by events: the dominant kernel's K x n launches are timed
     # in an eager leg of the same K iterations right after the timed region (same process, same kernels, same inputs)
     dom_leg = "timed region"
-    if graphed:
+    if args.full and graphed:
         ops.start_timing(only=dominant)
         timed_steps(args.steps)
         dom_ms = ops.stop_timing().get(dominant, [])
@@ -357,7 +396,7 @@ def main():
 
     # ---- informational: the same K steps in the other arithmetics (N = 1 only; NOT `value`)
     other = None
-    if world == 1 and not args.no_opt_in:
+    if world == 1 and args.full and not args.no_opt_in:
         other = {}
         try:
             for mode in ("fp32", "bf16x6", "bf16x3", "fp16x3"):
@@ -449,15 +488,16 @@ def main():
             # MFMA peak / MFMAs per fp32 multiply for the split modes): iteration level, everything else included
             "conv_path_frac_of_own_roof": round(ALG_CONV_GFLOP_PER_IMAGE * value / world / 1e3 / (
                 PEAK_BF16_MFMA_TFLOPS / MFMAS_PER_PRODUCT[arith] if arith in MFMAS_PER_PRODUCT else PEAK_FP32_MFMA_TFLOPS), 4),
-            "conv_ms_per_step_profiled": round(conv_ms_profiled, 3),
             "losses_finite": finite,
             "regime": regime,
         }
+        if args.full:
+            res["conv_ms_per_step_profiled"] = round(conv_ms_profiled, 3)
         if comm is not None:
             res["data_parallel"] = comm
         if other is not None:
             res["other_arithmetics"] = other
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(B, args.beta)
         print(json.dumps(res), flush=True)
     if world > 1 or alone:

@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/${1:-pmc_bench}
 mkdir -p $O
-CMD="python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-opt-in"
+CMD="python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-opt-in"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- $CMD > $O/stats.log 2>&1 &&
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch -- $CMD > $O/fetch.log 2>&1 &&
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/write -- $CMD > $O/write.log 2>&1 &&

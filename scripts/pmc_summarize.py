@@ -31,7 +31,7 @@ def duration_us(d, substr, grid):
 root, substr = sys.argv[1], sys.argv[2]
 wgs = int(sys.argv[3]) if len(sys.argv) > 3 else None
 grid = wgs * 512 if wgs else None          # Grid_Size in the counter CSV is in work-items (512-thread workgroups)
-out = {"kernel_substring": substr, "command": "scripts/pmc_bench.sh: rocprofv3 passes over `python3 bench.py --steps 5 --warmup 2 "
+out = {"kernel_substring": substr, "command": "scripts/pmc_bench.sh: rocprofv3 passes over `python3 bench.py --full --steps 5 --warmup 2 "
        "--no-cpu-baseline --no-opt-in` (FETCH_SIZE | WRITE_SIZE | TCC_HIT_sum TCC_MISS_sum | SQ_* GRBM_GUI_ACTIVE, one pass each, --kernel-trace only)"}
 f, nf = counters(os.path.join(root, "fetch"), substr, grid)
 w, _ = counters(os.path.join(root, "write"), substr, grid)

@@ -738,3 +738,41 @@ def test_fused_conv_bn_equals_two_pass_batchnorm(T, batch):
                 continue
             e = float((res[True][1][ph][k] - r).norm() / r.norm())
             assert e <= grad_tol, (ph, k, e, "flipped units:", flips)
+
+
+def test_bench_plain_run_and_output_dump(tmp_path):
+    """`bench.py` as every change is measured: exactly K timed steps, `ms_per_step` the wall time of one of them, and
+    under --dump-outputs the last timed step's outputs (the nine losses, a seeded 2^20-entry sample of each network's
+    state), float32, at most 64 MB.  A --full run with the same arguments adds its legs (the instrumented iteration, the
+    regime probe, the eager roofline leg) outside the timed region and times the same iterations from the same state:
+    its dump equals the plain one bit for bit."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    dumps, lines = {}, {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-opt-in"])):
+        d = tmp_path / mode
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                              "--batch", "16", "--dump-outputs", str(d)] + extra, env=env, capture_output=True, text=True,
+                             timeout=900)
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+        js = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(js) == 1, out.stdout
+        res = lines[mode] = json.loads(js[0])
+        assert res["steps"] == 3 and res["warmup"] == 1 and res["losses_finite"] and res["higher_is_better"]
+        assert res["metric"] == "celeba64_betavaegan_train_images_per_sec" and res["unit"] == "images/s"
+        assert abs(res["value"] - 16 * 1e3 / res["ms_per_step"]) <= 0.01 * res["value"]
+        names = sorted(os.listdir(d))
+        assert len(names) == 11 and "netEG_state_sample.npy" in names and "netD_state_sample.npy" in names, names
+        assert sum(os.path.getsize(d / n) for n in names) <= 64 << 20
+        dumps[mode] = {n: np.load(d / n) for n in names}
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in dumps[mode].values())
+    assert lines["plain"]["roofline"] is None and "cpu_baseline" not in lines["plain"]
+    assert "conv_ms_per_step_profiled" not in lines["plain"] and "fake_path_gy_zero_fraction" not in lines["plain"]["regime"]
+    assert lines["full"]["roofline"]["launches_timed"] > 0 and "fake_path_gy_zero_fraction" in lines["full"]["regime"]
+    assert dumps["plain"].keys() == dumps["full"].keys()
+    for n, a in dumps["plain"].items():
+        assert np.array_equal(a, dumps["full"][n]), n

@@ -139,11 +139,7 @@ __global__ __launch_bounds__(NT) void bn_apply_kernel(const float* __restrict__ 
   __shared__ float s_co[4];
   // slices in descending order: the sums pass before this one went through the channel's slices in ascending order (same
   // channel -> same XCD in both launches), so the end of the channel is what its L2 still holds
-#if defined(VG_BN_APPLY_ASCENDING)      // timing experiments: the previous order
-  const int c = blockIdx.x, k = blockIdx.y;
-#else
   const int c = blockIdx.x, k = (int)gridDim.y - 1 - (int)blockIdx.y;
-#endif
   const double count = (double)B * HW;
   if (threadIdx.x < 64) {   // wavefront 0: fixed-order reduction of the slice partials
     double s1 = 0.0, s2 = 0.0;
@@ -796,12 +792,7 @@ extern "C" int vg_bn_act_bwd(const float* gy, const float* x, const float* gamma
   }
   // one pass when a channel fits a workgroup's registers and there are channels enough to fill the chip's memory system
   const long per_channel = (long)B * HW;
-#ifdef VG_BN_TWO_PASS                  // timing experiments only (same-box A/B of the one-pass form)
-  constexpr bool one_pass = false;
-#else
-  constexpr bool one_pass = true;
-#endif
-  if (one_pass && (HW & 3) == 0 && per_channel >= 4 && per_channel <= (long)ONE_NT * 4 * 8 && C >= 128) {
+  if ((HW & 3) == 0 && per_channel >= 4 && per_channel <= (long)ONE_NT * 4 * 8 && C >= 128) {
     if (per_channel <= (long)ONE_NT * 4 * 2)
       hipLaunchKernelGGL(bn_bwd_onepass_kernel<2>, dim3(C), dim3(ONE_NT), 0, st, x, gy, gamma, beta, save_mean, save_invstd,
                          gx, dgamma, dbeta, B, C, HW, act_apply, am);

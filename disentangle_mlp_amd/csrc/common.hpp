@@ -55,6 +55,15 @@ typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 
 #define VG_PLANES_F16_FLAG 0x100      // == VG_PLANES_F16 of vaegan_hip.h
 
+// A packed filter (conv_bf16split.hip, pack kernel) is nsteps K steps of planes x 2 k-blocks x CoutP units of 16 bytes,
+// then VG_PACK_SPARE zero steps (the ring kernel's filter DMA runs up to VG_RING_SLOTS steps past the last one), then,
+// with fp16 planes, a 16-byte trailer whose first float is the inverse of the filter's power-of-two scale.
+constexpr int VG_PACK_SPARE = 6;
+// 16-byte units in front of the trailer (host side; the pack kernel writes the same expression out)
+constexpr size_t vg_pack_trailer_units(int nsteps, int planes, int CoutP) {
+  return (size_t)(nsteps + VG_PACK_SPARE) * planes * 2 * CoutP;
+}
+
 // biased fp32 exponent of an upper bound `amax` >= 0, clamped so that both 2^(14 - E) and 2^(E - 14) are normal fp32
 // numbers (amax = 0 or subnormal: the largest scale; inf / NaN: the smallest -- the data then carries the inf / NaN)
 __device__ __forceinline__ unsigned f16_bound_exp(float amax) {

@@ -30,7 +30,6 @@ namespace {
 
 enum { X_FWD = 0, X_TR = 1 };
 constexpr int XNT = 256;
-constexpr int VG_PACK_SPARE = 6;   // zero steps behind a pack (the ring kernel's DMA runs up to six steps ahead: RING_MAX_SLOTS)
 
 // 16-byte units per patch row (FWD stride 2: per column parity).  Chosen so that the patch rows a
 // 32-pixel fragment spans start on disjoint groups of 16 units (= 256 B, one LDS bank row):
@@ -372,7 +371,7 @@ int launch_x(const float* x, const bf16x8* w, const float* bias, float* y, int B
   A.ysplit = (size_t)B * Cout * A.YH * A.YW;
   if (ksplit > 1) A.y = xs.slabs;
   A.in_amax = xs.in_amax;
-  A.w_unscale = (const float*)(w + (size_t)(Cin / 16 * 25 + VG_PACK_SPARE) * 2 * C::NP * A.CoutP);      // the pack's trailer
+  A.w_unscale = (const float*)(w + vg_pack_trailer_units(Cin / 16 * 25, C::NP, A.CoutP));      // the pack's trailer
   hipLaunchKernelGGL(conv5x5_bf16split_kernel<C>, dim3((unsigned)grid), dim3(XNT), 0, st, A);
   VG_CHECK_LAUNCH();
   if (ksplit > 1) {
@@ -433,7 +432,7 @@ int dispatch_x(const float* x, const bf16x8* w, const float* bias, float* y, int
 }
 
 // packed[class][chunk][step][plane][k-block][CoutP] x 8 bf16 (+ VG_PACK_SPARE zero steps at the end: the ring
-// kernel's DMA runs three steps ahead of the MFMAs).
+// kernel's DMA runs up to VG_RING_SLOTS steps ahead of the MFMAs; + the fp16 trailer, common.hpp).
 //   transposed = 0, S = 1: w is [Cout][Cin][5][5], one class of 25 taps (kh*5 + kw); a step is one tap, its two
 //                   k-blocks are channels 0-7 / 8-15 of the chunk;
 //   transposed = 0, S = 2 (conv_ring.hip): a step is 8 channels x 2 consecutive taps -- steps 0-11 taps (2s, 2s+1)
@@ -455,6 +454,7 @@ __device__ __forceinline__ void pack_bf16split_body(float* T, const float* __res
   const bool f16 = (planes & VG_PLANES_F16_FLAG) != 0;
   planes &= 0xff;
   const float wscale = f16 ? f16_scale_of(*w_amax) : 1.f;
+  // the trailer at vg_pack_trailer_units(nsteps, planes, CoutP), written out (a call compiles to another instruction order)
   if (f16 && bx == 0 && by == 0 && tid == 0)
     *(float*)(p + (size_t)(nsteps + VG_PACK_SPARE) * planes * 2 * CoutP) = f16_unscale_of(*w_amax);
   const int co0 = bx * PK_CO, c16 = by, nchunks = Cin / 16;
@@ -609,7 +609,7 @@ extern "C" int vg_debug_set_conv_ring_tile(int variant) {
 extern "C" size_t vg_conv5x5_packed_bf16split_bytes(int Cout, int Cin, int planes) {
   if (Cout <= 0 || Cin <= 0 || Cin % 16 || !planes_ok(planes)) return 0;
   // fp16 planes: + a 16-byte trailer holding the inverse of the filter's power-of-two scale
-  return (size_t)(Cin / 16 * 25 + VG_PACK_SPARE) * 2 * (planes & 0xff) * ((Cout + 127) & ~127) * 16 +
+  return vg_pack_trailer_units(Cin / 16 * 25, planes & 0xff, (Cout + 127) & ~127) * 16 +
          ((planes & VG_PLANES_F16_FLAG) ? 16 : 0);
 }
 

@@ -34,9 +34,6 @@ constexpr int RNT = 512;          // 8 wavefronts
 #ifndef VG_RING_SLOTS
 #define VG_RING_SLOTS 3
 #endif
-#ifndef VG_RING_REGF
-#define VG_RING_REGF 0
-#endif
 // Timing experiment for the K = 32 body planned in DESIGN.md section 4.10: NO cross-body fragment prefetch -- body k reads
 // the fragments of step k itself, right behind its barrier (the filter DMA of body k then refills the slot of step k - 1,
 // one step less of run-ahead: build with -DVG_RING_SLOTS=4 to keep three).
@@ -49,8 +46,8 @@ constexpr int ring_slots(bool f16, int slotu, int patchu) {
   while (n > 3 && (n * slotu + patchu + 1) * 16 > 160 * 1024) --n;
   return n;
 }
-constexpr int RING_MAX_SLOTS = 6;      // <= VG_PACK_SPARE of conv_bf16split.hip: the run-ahead past the last step reads zeros
-static_assert(VG_RING_SLOTS >= 3 && VG_RING_SLOTS <= RING_MAX_SLOTS, "ring depth");
+// the run-ahead past the last step reads the pack's zero spare steps (conv_bf16split.hip, pack kernel)
+static_assert(VG_RING_SLOTS >= 3 && VG_RING_SLOTS <= VG_PACK_SPARE, "ring depth");
 
 // 16-byte units per patch row; same bank rules as conv_bf16split.hip (fragments of 2 rows x 16 pixels need the
 // two rows 0 (mod 16) units apart, 4 rows x 8 pixels 8 (mod 16))
@@ -168,23 +165,8 @@ __device__ __forceinline__ void ring_body(const RArgs& A, f32x4* lds, int bid, i
   constexpr int PSTEP = (MODE == R_FWD) ? S : 1;
   constexpr int RING0 = 0, PATCH0 = C::RINGU, DUMMY = C::RINGU + C::PATCHU;
 
-  // Timing experiments only (scripts/abl_ring.py builds one-off libraries with -DVG_RING_ABL=bits; results are
-  // then wrong): 1 no filter DMA, 2 no barrier, 4 no patch staging, 8 no counted vmcnt wait, 16 no pixel-fragment
-  // reads, 32 no filter-fragment reads, 64 no MFMAs.  Compile-time: a run-time switch changed the schedule.
-#ifdef VG_RING_ABL
-  constexpr int abl = VG_RING_ABL;
-#else
-  constexpr int abl = 0;
-#endif
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);       // wave-uniform: keeps the DMA's LDS base in SGPRs
-#ifndef VG_RING_STAGGER
-#define VG_RING_STAGGER 0
-#endif
-  constexpr bool STG = VG_RING_STAGGER != 0;
-  static_assert(!(STG && VG_RING_REGF), "stagger build: DMA path only");
-  const bool early = STG && wid >= 4;                             // wave-uniform: meets each barrier half a body late
-  const bool late = wid >= 4;      // wave-uniform: the second-dispatched half (timing experiments VG_RING_PLACE = 1, 2)
   const int kb = lane >> 5, l32 = lane & 31;
   const int wc = wid % C::WC, wp = wid / C::WC;
   // XCD-aware placement (conv_igemm.hip): the cout tiles of one pixel tile share an XCD
@@ -193,13 +175,9 @@ __device__ __forceinline__ void ring_body(const RArgs& A, f32x4* lds, int bid, i
     const int ntn = A.ntiles_n, npatch = A.blocks_per_cls / ntn, full = (npatch / 8) * 8 * ntn;
     if (bid < full) {
       const int xcd = bid & 7, j = bid >> 3;
-#if defined(VG_RING_PT_INTERLEAVED)            // timing experiments: the previous map (neighbouring pixel tiles on 8 XCDs)
-      pt = (j / ntn) * 8 + xcd;
-#else
       // an XCD works through a contiguous run of pixel tiles: neighbours in the image (shared halo rows, shared cache
       // lines of a row) follow each other through the same L2
       pt = xcd * (npatch / 8) + j / ntn;
-#endif
       nt = j % ntn;
     } else {
       const int t = bid - full;
@@ -317,40 +295,16 @@ __device__ __forceinline__ void ring_body(const RArgs& A, f32x4* lds, int bid, i
     const bf16x8*& dma_ptr = second ? dma_ptr2 : dma_ptr1;
 #pragma unroll
     for (int j = 0; j < NDMA; ++j) {
-#if !defined(VG_RING_DMA_VADDR)
-      // scalar-base form: SGPR-pair base + one 32-bit lane offset, M0 = the slot's LDS address.  The builtin gives every
-      // lane a 64-bit address (a v_lshl_add_u64 per instruction and twice the address registers to read): same-box A/B
-      // 151.7-152.1 against 155.9-156.4 us on the dominant layer (profiles/r04_logs/r4_saddr.log).  hipcc does not see
-      // this VMEM instruction; its own waits for the staging loads only become more conservative (completion is in order),
-      // the waits for the DMA are the counted ones of this file.
+      // scalar-base form: SGPR-pair base + one 32-bit lane offset, M0 = the slot's LDS address.  The builtin
+      // (__builtin_amdgcn_global_load_lds) gives every lane a 64-bit address (a v_lshl_add_u64 per instruction and twice
+      // the address registers to read): same-box A/B 151.7-152.1 against 155.9-156.4 us on the dominant layer
+      // (profiles/r04_logs/r4_saddr.log).  hipcc does not see this VMEM instruction; its own waits for the staging loads
+      // only become more conservative (completion is in order), the waits for the DMA are the counted ones of this file.
       const unsigned m0v = (unsigned)(size_t)(__attribute__((address_space(3))) void*)(lds + RING0 + slot * SLOTU + dma_dst[j]);
       asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(dma_src[j]), "s"(dma_ptr), "s"(m0v) : "memory", "m0");
-#else
-      __builtin_amdgcn_global_load_lds((const void*)((const char*)dma_ptr + dma_src[j]),
-                                       (__attribute__((address_space(3))) void*)(lds + RING0 + slot * SLOTU + dma_dst[j]),
-                                       16, 0, 0);
-#endif
     }
     dma_ptr += wstep;
   };
-  // Filter through registers instead (fp16 planes, -DVG_RING_REGF=1): the step's slice as NDMA plain 16-byte loads per
-  // wavefront (scalar base + lane offset, seen by the compiler: it counts their vmcnt itself), written to the ring one
-  // body later with ds_write_b128.  Body k writes step k+2 (loaded in body k-1) into slot (k+2) % 3 -- free since the
-  // barrier of body k-1: step k-1's fragments were read in body k-2 -- and loads step k+3.
-  constexpr bool REGF = (VG_RING_REGF != 0) && F16;
-  static_assert(!REGF || NSLOT == 3, "register path: three slots");
-  f32x4 freg[REGF ? NDMA : 1];
-  auto filt_load = [&](bool second = false) {
-    const bf16x8*& dma_ptr = second ? dma_ptr2 : dma_ptr1;
-#pragma unroll
-    for (int j = 0; j < NDMA; ++j) freg[j] = *(const f32x4*)((const char*)dma_ptr + dma_src[j]);
-    dma_ptr += wstep;
-  };
-  auto filt_store = [&](int slot) {
-#pragma unroll
-    for (int j = 0; j < NDMA; ++j) lds[RING0 + slot * SLOTU + dma_dst[j] + lane] = freg[j];
-  };
-
   // ---- per-lane operand bases (units)
   int base_a[FC], base_b[FP];
 #pragma unroll
@@ -418,32 +372,15 @@ __device__ __forceinline__ void ring_body(const RArgs& A, f32x4* lds, int bid, i
         if (n == pr) { pa = a; pb = sum - a; }
         ++n;
       }
-    if constexpr ((abl & 128) != 0) {
-      // timing experiment: the same FLOPs as two v_mfma_f32_16x16x32_bf16 (numerically meaningless here)
-      typedef float f32x4v __attribute__((ext_vector_type(4)));
-      f32x4v c0 = {acc[g][f][0], acc[g][f][1], acc[g][f][2], acc[g][f][3]};
-      f32x4v c1 = {acc[g][f][4], acc[g][f][5], acc[g][f][6], acc[g][f][7]};
-      c0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[buf][g][pa], bv[buf][f][pb], c0, 0, 0, 0);
-      c1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[buf][g][pa], bv[buf][f][pb], c1, 0, 0, 0);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { acc[g][f][r] = c0[r]; acc[g][f][4 + r] = c1[r]; }
-    } else {
-      acc[g][f] = mfma_split16<F16>(av[buf][g][pa], bv[buf][f][pb], acc[g][f]);
-    }
+    acc[g][f] = mfma_split16<F16>(av[buf][g][pa], bv[buf][f][pb], acc[g][f]);
   };
   // a step's MFMAs with the next step's fragment reads spread between them (one read per RS MFMAs), pinned
   constexpr int RS = (NMF / NRD) > 0 ? (NMF / NRD) : 1;
   // ---- prologue: first patch buffer, ring slots 0..2, fragments of step 0
   dma_ptr1 += (size_t)c_begin * NA * wstep;
   dma_ptr2 += (size_t)c_begin * NB2 * wstep;
-  if constexpr (REGF) {
-    filt_load(); filt_store(0);
-    filt_load(); filt_store(1);
-    filt_load();                                     // step 2 stays in registers until body 0
-  } else {
 #pragma unroll
-    for (int i = 0; i < NSLOT - (VG_RING_NOPF ? 1 : 0); ++i) dma_next(i);
-  }
+  for (int i = 0; i < NSLOT - (VG_RING_NOPF ? 1 : 0); ++i) dma_next(i);
   stage_load(c_begin * 16);
   stage_store(0);
   wait_vmcnt<0>();
@@ -476,12 +413,11 @@ __device__ __forceinline__ void ring_body(const RArgs& A, f32x4* lds, int bid, i
       const bool ld = (MODE == R_FWD) ? (s == 0 || s == 13) : (s == 0);
       const bool wr = (MODE == R_FWD) ? (s == 4 || s == 17) : (s == LW);
       const int wbuf = (MODE == R_FWD) ? (s == 4 ? BUFU : 0) : pnxt;
-      // B_k: slot (k+1)%3 and the patch writes of body k-1 are visible.  Staggered build: the second-dispatched half of
-      // the wavefronts (4-7: the SIMD partners of 0-3) meets the same barrier in the MIDDLE of its body, see below.
+      // B_k: slot (k+1)%3 and the patch writes of body k-1 are visible
 #ifdef VG_RING_STAMP
       asm volatile("s_memtime %0" : "=s"(tk_a));
 #endif
-      if (!(abl & 2) && !early) __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_s_barrier();
 #ifdef VG_RING_STAMP
       asm volatile("s_memtime %0" : "=s"(tk_b));
 #endif
@@ -490,127 +426,55 @@ __device__ __forceinline__ void ring_body(const RArgs& A, f32x4* lds, int bid, i
       const int so = nslot * SLOTU;
       // the next step's patch offset (the last body reads step 0 of the next chunk)
       const int bo = (s + 1 < NSTEP) ? patch_off(s + 1, pcur) : patch_off(0, pnxt);
-      if constexpr (STG) {
-        // Stagger (MI355X_MICROARCH.md, "Two waves per SIMD", item 9): a body is [H1: the first half of the step's
-        // MFMAs, nothing else][H2: the second half + EVERYTHING that touches memory -- filter DMA, staging loads, the
-        // next step's fragment reads, patch writes].  Wavefronts 0-3 pass the step's barrier before H1, wavefronts 4-7
-        // between H1 and H2: every memory operation of body k still falls between barriers k and k+1 for all eight
-        // (the hazard analysis of the file header holds unchanged), but the two wavefronts of a SIMD are half a body
-        // apart, so one of them has MFMAs to issue while the other drains its waits and sits at the barrier.
-        // Accumulation order per output is unchanged: results are bit-identical to the lockstep build.
-        constexpr int H1N = NMF / 2, H2N = NMF - H1N;
-        constexpr int RPM = (NRD + H2N - 1) / H2N;           // fragment reads per MFMA of H2
-#pragma unroll
-        for (int i = 0; i < H1N; ++i)
-          if (!(abl & 64)) mfma_one(cur, i, (TWO && s >= NA) ? 1 : 0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (!(abl & 2) && early) __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = H1N; i < NMF; ++i) {
-          const int j = i - H1N;
-          if (!(abl & 64)) mfma_one(cur, i, (TWO && s >= NA) ? 1 : 0);
-          if (j == 0) {
-            if (!(abl & 1)) dma_next(slot, TWO && (s + NSLOT) % NSTEP >= NA);      // step k+3 into the slot read during body k-1
-            if (ld && !(abl & 4)) {
-              if constexpr (MODE == R_FWD) stage_load(ch * 16 + (s == 0 ? 8 : 16));
-              else stage_load((ch + 1) * 16);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-          }
-#pragma unroll
-          for (int r = 0; r < RPM; ++r)
-            if (j * RPM + r < NRD && !(abl & ((j * RPM + r < FC * NP) ? 32 : 16))) read_one(nxt, j * RPM + r, so, bo);
-          __builtin_amdgcn_sched_barrier(0);
-          if (wr && !(abl & 4) && j < NQ) {
-            split_unit(j, wbuf);
-            __builtin_amdgcn_sched_barrier(0);
-          }
-        }
-        if (wr && !(abl & 4)) {
-#pragma unroll
-          for (int q = H2N; q < NQ; ++q) split_unit(q, wbuf);
-        }
-      } else {
       // Placement of the step's vector-memory instructions (filter DMA, a staging event's loads behind it) and of a
       // written unit's split: behind MFMA 0 and between the later MFMAs, the same in all eight wavefronts.  Round 4 timed
       // two other placements with per-MFMA s_memtime stamps (scripts/ring_stamps.py, profiles/r04_logs/r4_stamps*.log):
-      // the DMA half a body later in wavefronts 4-7 (VG_RING_PLACE=1), and the whole memory block in front of the MFMAs
-      // in wavefronts 4-7 / behind them in 0-3 (VG_RING_PLACE=2).  Both within 2 % of this one (154.7-157.5 us against
-      // 159.5-163 on the dominant layer): the two wavefronts of a SIMD do not interleave their MFMAs whatever the
-      // placement -- the older one wins every arbitration while it has an instruction ready and runs its twelve first --
-      // and an LDS-DMA instruction holds its in-order wavefront 70-190 cycles wherever it stands.
-#ifndef VG_RING_PLACE
-#define VG_RING_PLACE 0
-#endif
+      // the DMA half a body later in wavefronts 4-7, and the whole memory block in front of the MFMAs in wavefronts 4-7 /
+      // behind them in 0-3.  Both within 2 % of this one (154.7-157.5 us against 159.5-163 on the dominant layer): the two
+      // wavefronts of a SIMD do not interleave their MFMAs whatever the placement -- the older one wins every arbitration
+      // while it has an instruction ready and runs its twelve first -- and an LDS-DMA instruction holds its in-order
+      // wavefront 70-190 cycles wherever it stands.  (Those builds, like the other timing experiments of DESIGN.md
+      // section 4, were removed after they were measured.)
       if (VG_RING_NOPF) {          // this step's own fragments, behind the barrier
 #pragma unroll
         for (int j = 0; j < NRD; ++j) read_one(cur, j, slot * SLOTU, patch_off(s, pcur));
         __builtin_amdgcn_sched_barrier(0);
       }
-      auto mem_block = [&]() {
-        if constexpr (VG_RING_NOPF != 0) {
-          if (!(abl & 1)) dma_next(slot == 0 ? NSLOT - 1 : slot - 1, TWO && (s + NSLOT - 1) % NSTEP >= NA);
-        } else
-        if constexpr (REGF) {
-          if (!(abl & 1)) {
-            filt_store(slot == 0 ? 2 : slot - 1);                                  // step k+2 -> slot (k+2) % 3
-            filt_load(TWO && (s + NSLOT) % NSTEP >= NA);                           // step k+3
-          }
-        } else
-        if (!(abl & 1)) dma_next(slot, TWO && (s + NSLOT) % NSTEP >= NA);          // step k+NSLOT into the slot read during body k-1
-        if (ld && !(abl & 4)) {
+      auto mem_block = [&]() {     // a lambda on purpose: written out in the loop, the body is scheduled differently
+        if constexpr (VG_RING_NOPF != 0)
+          dma_next(slot == 0 ? NSLOT - 1 : slot - 1, TWO && (s + NSLOT - 1) % NSTEP >= NA);
+        else
+          dma_next(slot, TWO && (s + NSLOT) % NSTEP >= NA);        // step k+NSLOT into the slot read during body k-1
+        if (ld) {
           if constexpr (MODE == R_FWD) stage_load(ch * 16 + (s == 0 ? 8 : 16));
           else stage_load((ch + 1) * 16);
         }
-        if (VG_RING_PLACE == 2 && wr && !(abl & 4)) {
-#pragma unroll
-          for (int q = 0; q < NQ; ++q) split_unit(q, wbuf);
-        }
       };
-      if (VG_RING_PLACE == 2 && late) {
-        mem_block();
-        __builtin_amdgcn_sched_barrier(0);
-      }
 #pragma unroll
       for (int i = 0; i < NMF; ++i) {
-        if (!(abl & 64)) mfma_one(cur, i, (TWO && s >= NA) ? 1 : 0);
+        mfma_one(cur, i, (TWO && s >= NA) ? 1 : 0);
 #ifdef VG_RING_STAMP
         if (i < 12) asm volatile("s_memtime %0" : "=s"(tm[i]));
 #endif
-        if (VG_RING_PLACE < 2 && (i == 0 || i == NMF / 2)) {
-          if ((i != 0) == (VG_RING_PLACE == 1 && late)) mem_block();
+        if (i == 0 || i == NMF / 2) {
+          if (i == 0) mem_block();
           __builtin_amdgcn_sched_barrier(0);
         }
         if (!VG_RING_NOPF && i % RS == RS - 1 && i / RS < NRD) {
-          if (!(abl & ((i / RS < FC * NP) ? 32 : 16))) read_one(nxt, i / RS, so, bo);
+          read_one(nxt, i / RS, so, bo);
           __builtin_amdgcn_sched_barrier(0);
         }
         // a written unit's split (VALU) + ds_writes go between the later MFMAs
-        if (VG_RING_PLACE < 2 && wr && !(abl & 4) && i >= NMF / 2 && (i - NMF / 2) < NQ) {
+        if (wr && i >= NMF / 2 && (i - NMF / 2) < NQ) {
           split_unit(i - NMF / 2, wbuf);
           __builtin_amdgcn_sched_barrier(0);
         }
       }
 #pragma unroll
       for (int j = NMF / RS; j < NRD && !VG_RING_NOPF; ++j) read_one(nxt, j, so, bo);     // reads the MFMA count left over
-      if constexpr ((abl & 256) != 0) {
-        // timing experiment: what a v_mfma_f32_16x16x32_bf16 build would read on top -- (FC + FP) * 2 * 2 operand
-        // registers per step instead of (FC + FP) * 3: one more read per fragment row / column (results discarded)
-#pragma unroll
-        for (int j = 0; j < FC + FP; ++j) {
-          f32x4 d = (j < FC) ? lds[base_a[j] + so + TN] : lds[base_b[j - FC] + bo + 1];
-          asm volatile("" ::"v"(d));
-        }
-      }
-      if (VG_RING_PLACE < 2 && wr && !(abl & 4)) {
+      if (wr) {
 #pragma unroll
         for (int q = NMF - NMF / 2; q < NQ; ++q) split_unit(q, wbuf);
-      }
-      if (VG_RING_PLACE == 2 && !late) {
-        __builtin_amdgcn_sched_barrier(0);
-        mem_block();
-      }
       }
       // DMA(k+2) has landed (DMA(k+3), and a staging event's loads for two bodies, stay in flight);
       // this wavefront's reads of step k+1 and its patch writes are done
@@ -622,12 +486,7 @@ __device__ __forceinline__ void ring_body(const RArgs& A, f32x4* lds, int bid, i
       // bodies from the one that issued them (they follow that body's DMA; hipcc itself waits for them where the
       // registers are used)
       const bool ldw = (MODE == R_FWD) ? ((s >= 0 && s < NSLOT - 1) || (s >= 13 && s < 13 + NSLOT - 1)) : (s >= 0 && s < NSLOT - 1);
-      if constexpr (REGF) {
-        // every vector-memory instruction is the compiler's: it waits where a register is used
-      } else
-      if (abl & (8 | 4 | 1)) {                                      // ablations change what is in flight: drain or skip
-        if (!(abl & 8)) wait_vmcnt<0>();
-      } else if (ldw) wait_vmcnt<(NSLOT - 2) * NDMA + NL>(); else wait_vmcnt<(NSLOT - 2) * NDMA>();
+      if (ldw) wait_vmcnt<(NSLOT - 2) * NDMA + NL>(); else wait_vmcnt<(NSLOT - 2) * NDMA>();
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #ifdef VG_RING_STAMP
       asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tk_d), "+s"(tk_a), "+s"(tk_b), "+s"(tk_c));
@@ -815,9 +674,9 @@ int launch_ring(const float* x, const bf16x8* w, const float* bias, float* y, in
   A.in_scale = fu.in_scale; A.in_shift = fu.in_shift; A.in_act = fu.in_act;
   A.stats = (ksplit == 1) ? fu.stats : nullptr;
   A.in_amax = fu.in_amax;
-  // the pack's trailer (conv_bf16split.hip, pack kernel): behind the steps and the spare steps
-  A.w_unscale = (const float*)(w + (size_t)(Cin / 16 * 25 + RING_MAX_SLOTS) * 2 * C::NP * ((Cout + 127) & ~127));
   A.B = B; A.Cin = Cin; A.XH = XH; A.XW = XW; A.Cout = Cout; A.CoutP = (Cout + 127) & ~127;
+  // the pack's trailer (common.hpp): behind the steps and the spare steps
+  A.w_unscale = (const float*)(w + vg_pack_trailer_units(Cin / 16 * 25, C::NP, A.CoutP));
   int tsh, tsw;
   if (C::MODE == R_FWD) {
     A.YH = (XH - 1) / 2 + 1; A.YW = (XW - 1) / 2 + 1;
@@ -832,9 +691,6 @@ int launch_ring(const float* x, const bf16x8* w, const float* bias, float* y, in
   const long per_cls = (long)A.ntiles_n * A.tiles_hw * cdiv(B, C::NB);
   // transposed: two classes per workgroup when that still gives every CU a workgroup (and the XCD arithmetic holds)
   A.paired = (C::NCLS == 4 && C::F16 && per_cls * ksplit * 2 >= 256 && per_cls % 8 == 0) ? 1 : 0;
-#ifdef VG_RING_UNPAIRED      // timing experiments
-  A.paired = 0;
-#endif
   const long grid = per_cls * (A.paired ? 2 : C::NCLS) * ksplit;
   if (grid <= 0 || grid > 0x7fffffffL) return VG_ERR_BAD_ARG;
   A.blocks_per_cls = (int)per_cls;

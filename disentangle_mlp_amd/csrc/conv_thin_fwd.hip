@@ -27,12 +27,6 @@ namespace {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 
-// timing experiments only (experiments/abl_build.sh tfwd <bits>): 1 no output stores, 2 no MFMAs, 4 input rows built once,
-// 8 no statistics
-#ifndef VG_TF_ABL
-#define VG_TF_ABL 0
-#endif
-
 struct FArgs {
   const float* x;
   const float* w;
@@ -194,7 +188,7 @@ __global__ __launch_bounds__(512) void conv_thin_fwd_kernel(FArgs A) {
       if (t < rows) {                                  // uniform
 #pragma unroll
         for (int n = 0; n < S; ++n)
-          if (!(VG_TF_ABL & 4) || t == 0) build_row((S * u + 5 - S + n) % C::RS, S * t + 5 - S + n);
+          build_row((S * u + 5 - S + n) % C::RS, S * t + 5 - S + n);
         // two accumulators taken in turn: an MFMA that accumulates into the result of the one issued just before it
         // waits out that one's whole latency in compiler-inserted s_nops (one chain: 4158 SALU instructions per
         // wavefront, three quarters of the kernel's time); products in order of size, smallest plane products first
@@ -209,9 +203,7 @@ __global__ __launch_bounds__(512) void conv_thin_fwd_kernel(FArgs A) {
             for (int pa = sum; pa >= 0; --pa)
 #pragma unroll
               for (int kh = 0; kh < 5; ++kh, ++n) {
-                if (VG_TF_ABL & 2) {
-                  d[kh] += (float)wf[kh][pa][0] * (float)win[(S * u + kh) % C::RS][sum - pa][0];
-                } else if (n & 1) {
+                if (n & 1) {
                   d1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[kh][pa], win[(S * u + kh) % C::RS][sum - pa], d1, 0, 0, 0);
                 } else {
                   d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[kh][pa], win[(S * u + kh) % C::RS][sum - pa], d, 0, 0, 0);
@@ -230,26 +222,22 @@ __global__ __launch_bounds__(512) void conv_thin_fwd_kernel(FArgs A) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           d[r] += bias_l[cg * 32 + (r & 3) + 8 * (r >> 2) + 4 * half];
-          if (!(VG_TF_ABL & 8)) {
-            s1[r] += d[r];
-            s2[r] += d[r] * d[r];
-          }
+          s1[r] += d[r];
+          s2[r] += d[r] * d[r];
         }
-        if (!(VG_TF_ABL & 1)) {
-          // opaque per row: left visible, hipcc hoists the 16 zero-extended 64-bit offsets out of the row loop (32
-          // VGPRs), spills, and waits for every outstanding store (vmcnt(0)) on each reload
-          unsigned lb = lane_byte;
-          asm volatile("" : "+v"(lb));
-          if (full) {
+        // opaque per row: left visible, hipcc hoists the 16 zero-extended 64-bit offsets out of the row loop (32
+        // VGPRs), spills, and waits for every outstanding store (vmcnt(0)) on each reload
+        unsigned lb = lane_byte;
+        asm volatile("" : "+v"(lb));
+        if (full) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r)
+          for (int r = 0; r < 16; ++r)
+            *(float*)(yrow + (lb + (unsigned)((r & 3) + 8 * (r >> 2)) * plane_byte)) = d[r];
+        } else {
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            if (cg * 32 + (r & 3) + 8 * (r >> 2) + 4 * half < Cout)
               *(float*)(yrow + (lb + (unsigned)((r & 3) + 8 * (r >> 2)) * plane_byte)) = d[r];
-          } else {
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-              if (cg * 32 + (r & 3) + 8 * (r >> 2) + 4 * half < Cout)
-                *(float*)(yrow + (lb + (unsigned)((r & 3) + 8 * (r >> 2)) * plane_byte)) = d[r];
-          }
         }
       }
     }

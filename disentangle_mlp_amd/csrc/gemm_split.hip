@@ -15,25 +15,18 @@
 // with three bf16 planes -- 6 MFMAs per multiply, matrix-bound, level with the vendor library -- and removed it; at 3
 // MFMAs the weight stream is the bound.)
 //
-// One workgroup = 8 wavefronts (2 x 4 of 64 x 32; G_W8 = 0: 4 of 64 x 64) owns a 128 x 128 output tile and a
+// One workgroup = 8 wavefronts (2 x 4 of 64 x 32) owns a 128 x 128 output tile and a
 // slice of the reduction (K split over workgroups; partial tiles go to slabs summed in a fixed order: no atomics).  A
-// stage = 32 reduction indices: a thread stages two 8-index units of A and two of B -- two 16-byte loads each where the
+// stage = 32 reduction indices: a thread stages one 8-index unit of A and one of B -- two 16-byte loads each where the
 // reduction index is contiguous, eight 4-byte loads (a row apart; consecutive lanes = consecutive rows, coalesced)
 // where it is not -- G_PD stages ahead in registers, splits them into planes and writes two 16-byte LDS units each
 // ([plane][k-block][row], k-blocks padded by two units so that the 4 lanes that share a row do not share banks);
 // stages are double-buffered in LDS, ONE barrier per stage.  Plain loads only: hipcc counts vmcnt itself.
-#include <cstdlib>
-
 #include "common.hpp"
 #include "vaegan_hip.h"
 
 namespace {
 
-// G_W8: 8 wavefronts (2 x 4 of 64 x 32) per tile instead of 4 (2 x 2 of 64 x 64): two wavefronts per SIMD on the grids
-// that give every CU one workgroup only (forward / data gradient at batch 128), half the staging per thread
-#ifndef G_W8
-#define G_W8 1
-#endif
 // M16 (template parameter of the kernel): the products on v_mfma_f32_16x16x32_f16 (a stage IS one K = 32 step: the four
 // k-blocks of the LDS layout are the four k-groups of its operands) instead of two K = 16 steps of 32x32x16; the output tile
 // is computed transposed (D[n][m]) so that a lane holds four consecutive n of one row m: 16-byte stores.  Measured
@@ -47,21 +40,17 @@ namespace {
 #ifndef G_M16
 #define G_M16 0
 #endif
-constexpr int GNT = G_W8 ? 512 : 256, GTM = 128, GTN = 128, GKC = 32;   // threads, tile rows / columns, reduction indices per stage
-constexpr int G_HN = G_W8 ? 1 : 2;                           // 32-column fragments per wavefront
+// 8 wavefronts (2 x 4 of 64 x 32) per tile rather than 4 (2 x 2 of 64 x 64): two wavefronts per SIMD on the grids that
+// give every CU one workgroup only (forward / data gradient at batch 128), half the staging per thread
+constexpr int GNT = 512, GTM = 128, GTN = 128, GKC = 32;     // threads, tile rows / columns, reduction indices per stage
+constexpr int G_HN = 1;                                      // 32-column fragments per wavefront
 constexpr int GPAD = 2;
 constexpr int G_KB = GTM + GPAD;                             // units per k-block (A and B tiles have the same height)
 constexpr int G_PL = 4 * G_KB;                               // units per plane
 constexpr int G_NP = 2;                                      // fp16 hi + lo
 constexpr int G_PD = 3;                                      // register slots: two stages in flight, one being split
-constexpr int G_NU = GTM * 4 / GNT;                          // staged units per thread and operand: 2 (4 wavefronts) or 1
-static_assert(GTM == GTN && (G_NU == 1 || G_NU == 2), "staging map");
-
-// timing experiments only (experiments/abl_build.sh gemm <bits>; results are then wrong): 1 every workgroup streams the B
-// rows of tile 0 / split 0 (cache-resident), 2 the same for A, 4 no plane split (raw bits stored), 8 no MFMAs
-#ifndef VG_GEMM_ABL
-#define VG_GEMM_ABL 0
-#endif
+constexpr int G_NU = 1;                                      // staged units per thread and operand
+static_assert(GTM == GTN && GTM * 4 == G_NU * GNT, "staging map");
 
 struct GArgs {
   const float* A;
@@ -89,18 +78,14 @@ __device__ __forceinline__ void load8(float* r, const float* p, long ks, bool st
 }
 
 // AT / BT: the operand's ROW index is the contiguous one (reduction index strided)
-// R3: three LDS buffers instead of two -- a stage writes the stage after next, so the NEXT stage's first fragments are
-// read under this stage's last MFMAs instead of behind the barrier (the convolution ring's scheme).  100 KB: one
-// workgroup per CU, for the grids that have no more than that anyway.
-template <bool AT, bool BT, bool R3, bool M16>
-__global__ __launch_bounds__(GNT, R3 ? 1 : 2) void gemm_nt_f16x3_kernel(GArgs G) {
-  static_assert(!(R3 && M16), "the ring variant keeps the 32x32x16 form");
+template <bool AT, bool BT, bool M16>
+__global__ __launch_bounds__(GNT, 2) void gemm_nt_f16x3_kernel(GArgs G) {
   constexpr int BUFU = G_NP * 2 * G_PL;
-  __shared__ f32x4 lds[(R3 ? 3 : 2) * BUFU];           // [buffer][A planes | B planes][k-block][row]
+  __shared__ f32x4 lds[2 * BUFU];                      // [buffer][A planes | B planes][k-block][row]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kb = lane >> 5, l32 = lane & 31;
-  const int wm = wid & 1, wn = wid >> 1;                // 2 x 2 wavefronts of 64 x 64, or 2 x 4 of 64 rows x 32 columns
+  const int wm = wid & 1, wn = wid >> 1;                // 2 x 4 wavefronts of 64 rows x 32 columns
   const int wcol = wn * 32 * G_HN;
   // workgroup -> (row tile, column tile, split).  Splits are dealt to the XCDs (blockIdx round-robins over the 8 of
   // them): the workgroups of one split -- they read the same reduction slice of A -- follow each other through one L2,
@@ -138,8 +123,7 @@ __global__ __launch_bounds__(GNT, R3 ? 1 : 2) void gemm_nt_f16x3_kernel(GArgs G)
     const int r0 = isb ? n0 : m0, rmax = isb ? G.N : G.M;
     const long rs = isb ? G.brs : G.ars, ks = isb ? G.bks : G.aks;
     u_ok[u] = (r0 + row) < rmax;
-    const bool cached = (VG_GEMM_ABL & (isb ? 1 : 2)) != 0;
-    up[u] = (isb ? G.B : G.A) + (size_t)min((cached ? 0 : r0) + row, rmax - 1) * rs + (size_t)((cached ? 0 : k_begin) + kblk * 8) * ks;
+    up[u] = (isb ? G.B : G.A) + (size_t)min(r0 + row, rmax - 1) * rs + (size_t)(k_begin + kblk * 8) * ks;
     u_dst[u] = (isb ? G_NP * G_PL : 0) + kblk * G_KB + row;
   }
 
@@ -158,10 +142,6 @@ __global__ __launch_bounds__(GNT, R3 ? 1 : 2) void gemm_nt_f16x3_kernel(GArgs G)
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] *= sc;
     f32x4 pl[G_NP];
-    if constexpr ((VG_GEMM_ABL & 4) != 0) {
-      pl[0] = f32x4{v[0], v[1], v[2], v[3]};
-      pl[1] = f32x4{v[4], v[5], v[6], v[7]};
-    } else
     split_planes16<G_NP, true>(v, pl);
     base[u_dst[u]] = pl[0];
     base[u_dst[u] + G_PL] = pl[1];
@@ -204,58 +184,6 @@ __global__ __launch_bounds__(GNT, R3 ? 1 : 2) void gemm_nt_f16x3_kernel(GArgs G)
     }
   };
 
-  if constexpr (R3) {
-   if (nst > 0) {
-    // slots 0, 1, 2 <- stages 0, 1, 2; stages 0 and 1 split into buffers 0 and 1; slot 0 <- stage 3
-#pragma unroll
-    for (int j = 0; j < G_PD; ++j) load_stage(j, min(j, nst - 1));
-#pragma unroll
-    for (int u = 0; u < 2 * G_NU; ++u) piece(0, u, lds);
-#pragma unroll
-    for (int u = 0; u < 2 * G_NU; ++u) piece(1, u, lds + BUFU);
-    load_stage(0, min(3, nst - 1));
-    __syncthreads();
-    bf16x8 xa[2][G_NP], xb[G_HN][G_NP], ya[2][G_NP], yb[G_HN][G_NP];    // fragments of step 0 / step 1 of a stage
-    read_frags(xa, xb, lds, 0);
-    // stage st, j = st % 3 (compile-time): buffer j is read, buffer (j + 1) % 3 holds stage st + 1 (its step-0 fragments
-    // are read under the last MFMAs), stage st + 2 (slot (j + 2) % 3, loaded two stages ago) is split into buffer
-    // (j + 2) % 3 -- last read during stage st - 1 --, stage st + 4 is loaded into slot (j + 1) % 3
-    auto stage3 = [&](int st, int j) {
-      const f32x4* base = lds + j * BUFU;
-      const f32x4* nb = lds + ((j + 1) % 3) * BUFU;
-      f32x4* wr = lds + ((j + 2) % 3) * BUFU;
-      load_stage((j + 1) % G_PD, min(st + 4, nst - 1));
-      __builtin_amdgcn_sched_barrier(0);
-      int grp = 0;
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-        for (int sum = G_NP - 1; sum >= 0; --sum)
-#pragma unroll
-          for (int pa = sum; pa >= 0; --pa) {
-#pragma unroll
-            for (int g = 0; g < 2; ++g)
-#pragma unroll
-              for (int h = 0; h < G_HN; ++h)
-                acc[g][h] = s2 == 0 ? mfma_split16<true>(xa[g][pa], xb[h][sum - pa], acc[g][h])
-                                    : mfma_split16<true>(ya[g][pa], yb[h][sum - pa], acc[g][h]);
-            if (grp == 0) read_frags(ya, yb, base, 1);
-            if (grp < 2 * G_NU) piece((j + 2) % G_PD, grp, wr);
-            if (grp == 3) read_frags(xa, xb, nb, 0);       // (after the last step-0 MFMA has been issued)
-            __builtin_amdgcn_sched_barrier(0);
-            ++grp;
-          }
-      __syncthreads();
-    };
-    int st = 0;
-    for (; st + G_PD <= nst; st += G_PD) {
-#pragma unroll
-      for (int j = 0; j < G_PD; ++j) stage3(st + j, j);
-    }
-    if (st < nst) stage3(st, 0);
-    if (st + 1 < nst) stage3(st + 1, 1);
-   }
-  } else
   if (nst > 0) {
     // stages past the end re-load the last one (never consumed): every register slot always holds valid data
 #pragma unroll
@@ -263,8 +191,8 @@ __global__ __launch_bounds__(GNT, R3 ? 1 : 2) void gemm_nt_f16x3_kernel(GArgs G)
 #pragma unroll
     for (int u = 0; u < 2 * G_NU; ++u) piece(0, u, lds);
     __syncthreads();
-    // One stage: 6 groups of 4 MFMAs (2 steps of 16 x the 3 plane products); the split of stage st + 1 (4 units) rides
-    // on the first four groups, the second step's fragments are read during the first step's second group.  `j`: the
+    // One stage: 6 groups of 2 MFMAs (2 steps of 16 x the 3 plane products); the split of stage st + 1 (2 units) rides
+    // on the first two groups, the second step's fragments are read during the first step's second group.  `j`: the
     // register slot that held stage st (compile-time: the loop below is unrolled by G_PD with no branch inside -- with
     // a per-stage `if (st < nst)` hipcc's vmcnt bookkeeping lost track across the joins and drained every load in
     // front of the next stage's address arithmetic).
@@ -287,9 +215,8 @@ __global__ __launch_bounds__(GNT, R3 ? 1 : 2) void gemm_nt_f16x3_kernel(GArgs G)
           for (int g = 0; g < 4; ++g)
 #pragma unroll
             for (int h = 0; h < 2 * G_HN; ++h)
-              if constexpr ((VG_GEMM_ABL & 8) == 0)
-                acc4[g][h] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, xb[h][sum - pa]),
-                                                                   __builtin_bit_cast(f16x8, xa[g][pa]), acc4[g][h], 0, 0, 0);
+              acc4[g][h] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, xb[h][sum - pa]),
+                                                                 __builtin_bit_cast(f16x8, xa[g][pa]), acc4[g][h], 0, 0, 0);
 #pragma unroll
           for (int u = grp16; u < 2 * G_NU; u += 3) piece((j + 1) % G_PD, u, nxt);
           __builtin_amdgcn_sched_barrier(0);
@@ -312,12 +239,8 @@ __global__ __launch_bounds__(GNT, R3 ? 1 : 2) void gemm_nt_f16x3_kernel(GArgs G)
             for (int g = 0; g < 2; ++g)
 #pragma unroll
               for (int h = 0; h < G_HN; ++h)
-                if constexpr ((VG_GEMM_ABL & 8) == 0)
                 acc[g][h] = s2 == 0 ? mfma_split16<true>(av0[g][pa], bv0[h][sum - pa], acc[g][h])
                                     : mfma_split16<true>(av1[g][pa], bv1[h][sum - pa], acc[g][h]);
-            if constexpr ((VG_GEMM_ABL & 16) != 0) {       // timing experiment: the split rides on the LAST four groups
-              if (grp >= 6 - 2 * G_NU) piece((j + 1) % G_PD, grp - (6 - 2 * G_NU), nxt);
-            } else
             if (grp < 2 * G_NU) piece((j + 1) % G_PD, grp, nxt);
             if (grp == 1) read_frags(av1, bv1, base, 1);
             __builtin_amdgcn_sched_barrier(0);
@@ -379,18 +302,12 @@ __global__ __launch_bounds__(GNT, R3 ? 1 : 2) void gemm_nt_f16x3_kernel(GArgs G)
   }
 }
 
-#ifndef G_TARGET_WGS
-#define G_TARGET_WGS 256
-#endif
 // K split: as many splits as keep >= 8 stages each and bring the grid to about G_TARGET_WGS workgroups
-int gemm_target_wgs() {      // (VG_GEMM_TARGET_WGS: timing experiments)
-  static const int t = [] { const char* e = getenv("VG_GEMM_TARGET_WGS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : G_TARGET_WGS; }();
-  return t;
-}
+constexpr int G_TARGET_WGS = 256;
 int gemm_ksplit(int M, int N, int K) {
   const long tiles = (long)cdiv(M, GTM) * cdiv(N, GTN);
   int ks = 1;
-  while (tiles * ks * 2 <= gemm_target_wgs() && K % (GKC * ks * 2) == 0 && K / (ks * 2) >= 8 * GKC) ks *= 2;
+  while (tiles * ks * 2 <= G_TARGET_WGS && K % (GKC * ks * 2) == 0 && K / (ks * 2) >= 8 * GKC) ks *= 2;
   return ks;
 }
 
@@ -431,17 +348,11 @@ extern "C" int vg_gemm_nt_f16x3(const float* A, const float* B, const float* bia
   if (grid > 0x7fffffffL) return VG_ERR_BAD_ARG;
   const bool at = a_k_stride != 1, bt = b_k_stride != 1;
   const dim3 g((unsigned)grid), b(GNT);
-  // three LDS buffers: measured, not used (the whole benchmark 13.78 ms with it everywhere, 13.65-13.69 where the grid gives
-  // a CU one workgroup anyway, 13.64 without: profiles/r04_logs/r4_gemm_r3.log -- the wavefronts do not wait for the
-  // fragment reads behind the barrier).  VG_GEMM_R3 = 1 / 2: always / on grids <= 256 -- timing experiments.
-  static const int r3_mode = [] { const char* e = getenv("VG_GEMM_R3"); return e ? atoi(e) : 0; }();
-  const bool r3 = r3_mode == 1 || (r3_mode == 2 && grid <= 256);
-  const bool m16 = !r3 && (G_M16 == 1 || (G_M16 == 2 && grid <= 512));
+  const bool m16 = G_M16 == 1 || (G_M16 == 2 && grid <= 512);
 #define VG_GEMM_LAUNCH(AT_, BT_)                                                                              \
   do {                                                                                                        \
-    if (r3) hipLaunchKernelGGL((gemm_nt_f16x3_kernel<AT_, BT_, true, false>), g, b, 0, st, G);                \
-    else if (m16) hipLaunchKernelGGL((gemm_nt_f16x3_kernel<AT_, BT_, false, true>), g, b, 0, st, G);          \
-    else hipLaunchKernelGGL((gemm_nt_f16x3_kernel<AT_, BT_, false, false>), g, b, 0, st, G);                  \
+    if (m16) hipLaunchKernelGGL((gemm_nt_f16x3_kernel<AT_, BT_, true>), g, b, 0, st, G);                      \
+    else hipLaunchKernelGGL((gemm_nt_f16x3_kernel<AT_, BT_, false>), g, b, 0, st, G);                         \
   } while (0)
   if (at && bt) VG_GEMM_LAUNCH(true, true);
   else if (at) VG_GEMM_LAUNCH(true, false);

@@ -134,11 +134,6 @@ __global__ __launch_bounds__(256) void relayout_gy_kernel(const float* __restric
 // 4-wavefront predecessor staged the patch between two barriers and prefetched gy one pixel ahead: 142 TFLOP/s on
 // 128 -> 256 @32 -> 16.)  Plain loads only: hipcc counts them (vmcnt) itself.
 constexpr int W8NT = 512;
-// timing experiments only (experiments/abl_build.sh): 1 gy always from pixel 0 (cache-resident), 2 x patch loaded once,
-// 4 patch split + LDS store once, 8 no MFMAs, 16 patch fragments read once
-#ifndef VG_WX_ABL
-#define VG_WX_ABL 0
-#endif
 
 template <int S_, int NP_, int WCO_, int TH_, bool F16_ = false>
 struct W8 {
@@ -276,11 +271,7 @@ __global__ __launch_bounds__(W8NT, 2) void conv5x5_wgrad_split8_kernel(WXArgs A)
   // A share that straddles two tiles is worked off second part first: its chunks 0 .. n2-1 of the second tile at steps
   // 0 .. n2-1, like every other workgroup's (see the chunk order below), then the end of the first tile.
   const int u_split = (u_begin / A.chunks + 1) * A.chunks;
-#if defined(VG_WX_PLAIN_ORDER)
-  const bool two = false;
-#else
   const bool two = u_split < u_end && u_end <= u_split + A.chunks;
-#endif
   int u = two ? u_split : u_begin, u_lim = u_end, pass = 0, t0 = 0;
   while (true) {
     if (u >= u_lim) {
@@ -314,7 +305,7 @@ __global__ __launch_bounds__(W8NT, 2) void conv5x5_wgrad_split8_kernel(WXArgs A)
     static_assert((PD == 3 || PD == 7) && WTW == 8, "ring indices below assume 4 or 8 sets, 8 pixels per row");
     auto load_a = [&](int set, size_t pix) {
 #pragma unroll
-      for (int pl = 0; pl < NP; ++pl) av[set][pl] = ga[((VG_WX_ABL & 1) ? 0 : pix) * gstep + (size_t)pl * 2 * CoP];
+      for (int pl = 0; pl < NP; ++pl) av[set][pl] = ga[pix * gstep + (size_t)pl * 2 * CoP];
     };
     // Order of the segment's chunks: a share starts at its chunk that is 0 (mod upw) and wraps, so that at step j EVERY
     // workgroup of the launch is at a chunk that is j (mod upw) (exactly for a share inside one tile).  The workgroups of
@@ -324,14 +315,10 @@ __global__ __launch_bounds__(W8NT, 2) void conv5x5_wgrad_split8_kernel(WXArgs A)
     // launch against 117 / 167 MB of operands: profiles/r03_hbm_traffic_by_kernel.json).  Speed only: the sum over the
     // chunks is taken in this order whatever the timing.
     const int nch = c_end - c_begin;
-#if defined(VG_WX_PLAIN_ORDER)              // timing experiments: the previous order
-    const int rot = 0;
-#else
     // step t0 + j of the share is at a chunk that is t0 + j (mod upw), as far as the segment allows
     int rot = ((t0 - c_begin) % A.upw + A.upw) % A.upw;
     rot = rot < nch ? rot : 0;
     t0 += nch;
-#endif
     auto chunk_at = [&](int j) -> int {
       int i = min(j, nch - 1) + rot;
       i -= (i >= nch) ? nch : 0;
@@ -352,35 +339,21 @@ __global__ __launch_bounds__(W8NT, 2) void conv5x5_wgrad_split8_kernel(WXArgs A)
       for (int t = 0; t < C::NPIX; ++t) {
         // gy fragments PD pixels ahead (the last PD pixels of a chunk fetch the first ones of the next chunk)
         load_a((t + PD) & PD, (t + PD < C::NPIX) ? pcur + pix_off(t + PD) : pnxt + pix_off(t + PD - C::NPIX));
-        if (t == 0 && more && !(VG_WX_ABL & 2)) load_patch(chn);
+        if (t == 0 && more) load_patch(chn);
         bf16x8 bv[FP][NP];
-        if (!(VG_WX_ABL & 16) || (j == 0 && t == 0)) {
 #pragma unroll
-          for (int f = 0; f < FP; ++f)
+        for (int f = 0; f < FP; ++f)
 #pragma unroll
-            for (int pl = 0; pl < NP; ++pl)
-              bv[f][pl] = __builtin_bit_cast(
-                  bf16x8, lds[buf * BUFU + base_b[f] + S * (t >> 3) * ROWU + S * (t & 7) + pl * 2 * KBU]);
-        }
+          for (int pl = 0; pl < NP; ++pl)
+            bv[f][pl] = __builtin_bit_cast(
+                bf16x8, lds[buf * BUFU + base_b[f] + S * (t >> 3) * ROWU + S * (t & 7) + pl * 2 * KBU]);
         // products with plane index sum < NP, smallest terms first, product-major
 #pragma unroll
         for (int sum = NP - 1; sum >= 0; --sum)
 #pragma unroll
           for (int pa = sum; pa >= 0; --pa)
 #pragma unroll
-            for (int f = 0; f < FP; ++f) {
-              if constexpr ((VG_WX_ABL & 32) != 0) {
-                // timing experiment: the same FLOPs as two v_mfma_f32_16x16x32 (numerically meaningless here), as
-                // conv_ring.hip's VG_RING_ABL = 128
-                f32x4 c0 = {acc[f][0], acc[f][1], acc[f][2], acc[f][3]}, c1 = {acc[f][4], acc[f][5], acc[f][6], acc[f][7]};
-                c0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[t & PD][pa], bv[f][sum - pa], c0, 0, 0, 0);
-                c1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[t & PD][pa], bv[f][sum - pa], c1, 0, 0, 0);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) { acc[f][r] = c0[r]; acc[f][4 + r] = c1[r]; }
-              } else
-              if (!(VG_WX_ABL & 8)) acc[f] = mfma_split16<F16>(av[t & PD][pa], bv[f][sum - pa], acc[f]);
-              else acc[f][0] += (float)av[t & PD][pa][0] + (float)bv[f][sum - pa][0];
-            }
+            for (int f = 0; f < FP; ++f) acc[f] = mfma_split16<F16>(av[t & PD][pa], bv[f][sum - pa], acc[f]);
         // one unit of the next patch per slot of the store schedule (the other buffer was last read a chunk ago).
         // (A branch-free form of this loop -- clamped re-loads instead of `more`, no wavefront groups, dump units for
         // unit-less lanes: three basic blocks per chunk instead of ~40 -- measured 3-20 % SLOWER: hipcc clusters the
@@ -389,7 +362,7 @@ __global__ __launch_bounds__(W8NT, 2) void conv5x5_wgrad_split8_kernel(WXArgs A)
           const int rel = t - C::ST0;
           if (rel >= 0 && rel % C::STEP == 0 && rel / C::STEP < 2 * NQ) {
             const int q = (rel / C::STEP) % NQ, g = (rel / C::STEP) / NQ;
-            if (more && grp == g && !(VG_WX_ABL & 4)) store_unit(q, buf ^ 1, chn);
+            if (more && grp == g) store_unit(q, buf ^ 1, chn);
           }
         }
       }

@@ -1,11 +1,17 @@
 """Where a ring-kernel wavefront's cycles go (diagnostic build of conv_ring.hip with -DVG_RING_STAMP: three s_memtime stamps
-per K step, summed per wavefront, returned through the statistics buffer).  Usage: ring_stamps.py <libabl_ring_XXXX.so> [arith]"""
+per K step, summed per wavefront, returned through the statistics buffer).  Usage: ring_stamps.py <lib.so> [arith]
+
+The library is the product build with conv_ring.o replaced (after `python -m disentangle_mlp_amd.build`):
+    C=disentangle_mlp_amd/csrc
+    hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Iinclude -I$C -Wno-unused-result -mllvm -pragma-unroll-threshold=131072 \
+          -Wno-inline-asm -DVG_RING_STAMP -c $C/conv_ring.hip -o /tmp/ring_stamp.o
+    hipcc -shared -fPIC --offload-arch=gfx950 -o /tmp/libring_stamp.so /tmp/ring_stamp.o $(ls $C/build/*.o | grep -v /conv_ring.o)"""
 import sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
 from disentangle_mlp_amd import _lib
-_lib.LIB_PATH = os.path.join(ROOT, "experiments", "abl", sys.argv[1])
+_lib.LIB_PATH = os.path.abspath(sys.argv[1])
 from disentangle_mlp_amd import ops
 ops.CONV_ARITH = sys.argv[2] if len(sys.argv) > 2 else "fp16x3"
 B = 128

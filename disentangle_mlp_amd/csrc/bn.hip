@@ -442,6 +442,41 @@ Slicing make_apply_slicing(int B, int C, int HW) {
 size_t part_bytes(int C) { return (size_t)C * NS_MAX * 2 * sizeof(double); }
 size_t ws_bytes(int C) { return part_bytes(C) + 64; }
 
+// Upper bound of max |act(x * sc + sh)| over a channel of n = count values, from its sums alone (act_amax of the
+// finalize kernels: what an fp16-plane convolution that applies sc / sh on load scales its input by).
+//   s2, m, var: the channel's sum of x^2, mean and clamped variance (s2 / n - m^2, >= 0) as the finalize kernel computed
+//   them in fp64; mu = (float)m, sc, beta: the coefficients it wrote (sh = beta - mu * sc).
+//   delta: relative error of the sums -- |S2 - T2| <= delta T2 and |S1 - T1| <= delta sum |x|, T1 / T2 the exact sums.
+// Samuelson: every x satisfies |x - T1/n| <= sigma sqrt(n - 1), sigma^2 = T2/n - (T1/n)^2 the EXACT variance.  `var` is
+// not that: when |mean| >> sigma, S2/n - m^2 cancels, the computed variance can be ~0 while sigma is not, 1/std then
+// goes up to 1/sqrt(eps), and a bound from `var` alone falls far below the data.  With q = S2/n:
+//   T2/n <= q / (1 - delta),  |m - T1/n| <= delta sum|x| / n <= delta sqrt(T2/n)          (Cauchy-Schwarz)
+//   sigma^2 - (q - m^2) = (T2/n - q) + (m - T1/n)(m + T1/n) <= (delta + delta (2 + delta)) T2/n <= 3.01 delta q
+// (delta <= 1e-3), plus fp64 rounding of q - m^2 (< 2^-50 q); so var_up = var + (3.01 delta + 2^-50) q >= sigma^2, and
+//   |x - mu| <= sqrt(var_up (n - 1)) + |T1/n - m| + |m - mu| <= sqrt(var_up (n - 1)) + 1.01 delta sqrt(q) + 2^-23 |m|.
+// |x sc + sh| <= |sc| |x - mu| + |beta| + (rounding of sh: <= 2^-23 (|beta| + |mu sc|)); the consumer's fmaf and the
+// final fp64 -> fp32 conversion round by 2^-24 each: (1 + 2^-20).  ReLU / LeakyReLU(0.2) only shrink magnitudes.
+// Where the sums are accurate (|mean| <= 8 sigma, the slots' delta) this stays within 0.1 % of the former
+// |gamma| sqrt(n) + |beta|; under cancellation it grows with sqrt(delta) |mean| instead of falling below the data.
+__device__ __forceinline__ float bn_act_bound(double s2, double m, double var, double count, double delta, float mu,
+                                              float sc, float beta) {
+  const double q = s2 / count;
+  const double var_up = var + (3.01 * delta + 0x1p-50) * q;
+  const double dev = sqrt(var_up * fmax(count - 1.0, 0.0)) + 1.01 * delta * sqrt(q) + 0x1p-23 * fabs(m);
+  const double asc = fabs((double)sc), ab = fabs((double)beta);
+  const double b = asc * dev + ab + 0x1p-23 * (ab + asc * fabs((double)mu));
+  return (float)(b * (1.0 + 0x1p-20));
+}
+
+// delta of bn_act_bound for sums made of fp32 statistics slots (each an fp32 sum in which a term goes through at most
+// D = VG_STATS_SLOT_DEPTH roundings: within gamma_D <= (D + 0.01) 2^-24 of the exact sum, relative to the sum of
+// magnitudes -- for the squares that is T2 itself) added in fp64 over nslots slots (and NS_MAX partials):
+// (nslots + 2 NS_MAX) 2^-53 more
+double slot_sums_delta(int nslots) { return (VG_STATS_SLOT_DEPTH + 1) * 0x1p-24 + (nslots + 2.0 * NS_MAX) * 0x1p-53; }
+
+// ... and for fp64 sums of fp32 values (bn_partial_kernel<0>: x^2 is exact in fp64): count + partials additions
+double fp64_sums_delta(double count) { return (count + 2.0 * NS_MAX + NT) * 0x1p-53; }
+
 }  // namespace
 
 // Per-channel coefficients of a train-mode BatchNorm from partial sums: `part` holds, for channel c and partial k,
@@ -456,9 +491,10 @@ __global__ __launch_bounds__(NT) void bn_finalize_kernel(const T* __restrict__ p
                                                          float* __restrict__ running_var, float* __restrict__ mean_out,
                                                          float* __restrict__ invstd_out, float* __restrict__ scale,
                                                          float* __restrict__ shift, float eps, float momentum,
-                                                         unsigned* __restrict__ act_amax) {
+                                                         unsigned* __restrict__ act_amax, double delta) {
   // act_amax (may be NULL): an upper bound of max |act(BN(x))| over the whole tensor is added to it (atomic maximum of
-  // the channels' bounds) -- what the fp16-plane convolution that applies these coefficients on load scales its input by
+  // the channels' bn_act_bound, delta: the relative error of the partial sums) -- what the fp16-plane convolution that
+  // applies these coefficients on load scales its input by
   // 32 channels per workgroup x 8 partial-lanes: consecutive threads read consecutive channels (the convolution's
   // slots are [slot][C][2]: 256 contiguous bytes per 32 threads), each partial-lane sums every 8th partial, and the 8
   // sums of a channel are added in a fixed order
@@ -492,10 +528,7 @@ __global__ __launch_bounds__(NT) void bn_finalize_kernel(const T* __restrict__ p
     invstd_out[c] = is;
     scale[c] = sc;
     shift[c] = beta[c] - mu * sc;
-    if (act_amax) {      // Chebyshev: |x - mean| <= sigma sqrt(n - 1), so |BN(x)| <= |gamma| sqrt(n) + |beta| (+ fp32 rounding of x * sc + sh)
-      const float bound = (fabsf(gamma[c]) * sqrtf((float)count) + fabsf(beta[c])) * 1.001f + fabsf(mu * sc) * 1e-6f;
-      atomicMax(act_amax, __float_as_uint(bound));
-    }
+    if (act_amax) atomicMax(act_amax, __float_as_uint(bn_act_bound(s2, m, var, count, delta, mu, sc, beta[c])));
     if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mu;
     if (running_var) {
       const double unb = count > 1.0 ? var * count / (count - 1.0) : var;
@@ -515,7 +548,7 @@ __global__ __launch_bounds__(1024) void bn_finalize_wide_kernel(const float* __r
                                                                 float* __restrict__ running_var, float* __restrict__ mean_out,
                                                                 float* __restrict__ invstd_out, float* __restrict__ scale,
                                                                 float* __restrict__ shift, float eps, float momentum,
-                                                                unsigned* __restrict__ act_amax) {
+                                                                unsigned* __restrict__ act_amax, double delta) {
   constexpr int CH = 8, KL = 128;
   __shared__ double r1[KL][CH], r2[KL][CH];
   const int cl = threadIdx.x % CH, kl = threadIdx.x / CH;
@@ -562,10 +595,7 @@ __global__ __launch_bounds__(1024) void bn_finalize_wide_kernel(const float* __r
     invstd_out[c] = is;
     scale[c] = sc;
     shift[c] = beta[c] - mu * sc;
-    if (act_amax) {      // Chebyshev: |x - mean| <= sigma sqrt(n - 1), so |BN(x)| <= |gamma| sqrt(n) + |beta| (+ fp32 rounding of x * sc + sh)
-      const float bound = (fabsf(gamma[c]) * sqrtf((float)count) + fabsf(beta[c])) * 1.001f + fabsf(mu * sc) * 1e-6f;
-      atomicMax(act_amax, __float_as_uint(bound));
-    }
+    if (act_amax) atomicMax(act_amax, __float_as_uint(bn_act_bound(s2, m, var, count, delta, mu, sc, beta[c])));
     if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mu;
     if (running_var) {
       const double unb = count > 1.0 ? var * count / (count - 1.0) : var;
@@ -670,19 +700,20 @@ extern "C" int vg_bn_finalize_stats(const float* stats, int nslots, int C, doubl
   if (!stats || nslots <= 0 || C <= 0 || count <= 0 || !gamma || !beta || !save_mean || !save_invstd || !scale || !shift)
     return VG_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
+  const double delta = slot_sums_delta(nslots);
   // few slots: one launch (a workgroup per 32 channels, 8 partial-lanes: up to 8 dependent loads per lane); more:
   // NS_MAX-way first stage into the BatchNorm workspace.  (The one-launch form on 1024 slots x 32 channels ran 56 us
   // -- one workgroup, 128 dependent loads per lane -- against ~6 us for the two stages.)
   if (nslots <= 64) {
     hipLaunchKernelGGL(bn_finalize_kernel<float>, dim3(cdiv(C, 32)), dim3(NT), 0, st, stats, nslots, 1L, (long)C, C,
                        count, gamma, beta, running_mean, running_var, save_mean, save_invstd, scale, shift, eps,
-                       momentum, am);      // stats[slot][C][2]: channel stride 1, slot stride C
+                       momentum, am, delta);      // stats[slot][C][2]: channel stride 1, slot stride C
     VG_CHECK_LAUNCH();
     return 0;
   }
   if (nslots <= 4096) {
     hipLaunchKernelGGL(bn_finalize_wide_kernel, dim3(cdiv(C, 8)), dim3(1024), 0, st, stats, nslots, C, count, gamma, beta,
-                       running_mean, running_var, save_mean, save_invstd, scale, shift, eps, momentum, am);
+                       running_mean, running_var, save_mean, save_invstd, scale, shift, eps, momentum, am, delta);
     VG_CHECK_LAUNCH();
     return 0;
   }
@@ -692,7 +723,7 @@ extern "C" int vg_bn_finalize_stats(const float* stats, int nslots, int C, doubl
   VG_CHECK_LAUNCH();
   hipLaunchKernelGGL(bn_finalize_kernel<double>, dim3(cdiv(C, 32)), dim3(NT), 0, st, (const double*)part, NS_MAX,
                      (long)NS_MAX, 1L, C, count, gamma, beta, running_mean, running_var, save_mean, save_invstd, scale,
-                     shift, eps, momentum, am);      // part[c][NS_MAX][2]
+                     shift, eps, momentum, am, delta);      // part[c][NS_MAX][2]: the fp32 slots' delta
   VG_CHECK_LAUNCH();
   return 0;
 }
@@ -712,7 +743,7 @@ extern "C" int vg_bn_stats(const float* x, const float* gamma, const float* beta
   VG_CHECK_LAUNCH();
   hipLaunchKernelGGL(bn_finalize_kernel<double>, dim3(cdiv(C, 32)), dim3(NT), 0, st, (const double*)part, s.ns,
                      (long)s.ns, 1L, C, (double)B * HW, gamma, beta, running_mean, running_var, save_mean, save_invstd,
-                     scale, shift, eps, momentum, (unsigned*)act_amax);      // part[c][ns][2]
+                     scale, shift, eps, momentum, (unsigned*)act_amax, fp64_sums_delta((double)B * HW));      // part[c][ns][2]
   VG_CHECK_LAUNCH();
   return 0;
 }

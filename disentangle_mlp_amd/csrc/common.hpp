@@ -64,6 +64,13 @@ constexpr size_t vg_pack_trailer_units(int nsteps, int planes, int CoutP) {
   return (size_t)(nsteps + VG_PACK_SPARE) * planes * 2 * CoutP;
 }
 
+// Statistics slots of the convolution epilogues (vg_conv_fusion.stats, [slot][Cout][2]): each slot is an fp32 sum of
+// output values (and of their squares) in which no term goes through more than this many roundings (its square and
+// every addition on its way to the slot: a per-lane fma chain, then the butterfly over 32 lanes).  Then a slot is within
+// gamma_16 ~ 16 * 2^-24 of its exact value, relative to its sum of magnitudes, whatever the number of terms;
+// vg_bn_finalize_stats relies on that (bn.hip, bn_act_bound).  A producer with deeper sums must raise it.
+constexpr int VG_STATS_SLOT_DEPTH = 16;
+
 // biased fp32 exponent of an upper bound `amax` >= 0, clamped so that both 2^(14 - E) and 2^(E - 14) are normal fp32
 // numbers (amax = 0 or subnormal: the largest scale; inf / NaN: the smallest -- the data then carries the inf / NaN)
 __device__ __forceinline__ unsigned f16_bound_exp(float amax) {

@@ -60,6 +60,7 @@ struct Cfg {
   static constexpr int NCLS = (MODE == MODE_FWD) ? 1 : S * S;
   static_assert(TN % (32 * WC) == 0 && TM % (32 * WP) == 0 && CK % 2 == 0, "tile shape");
   static_assert(RLMAX <= NT, "one filter row per pass at least");
+  static_assert(FP + 5 <= VG_STATS_SLOT_DEPTH, "statistics slot: an fma chain of FP, 5 butterfly additions");
   static_assert(KS == 1 || (CK / 2) % KS == 0, "split-K groups own whole channel pairs");
   static_assert(KS == 1 || 2 * STAGE >= (KS - 1) * TM * TN, "LDS must hold the partial tiles of the K groups");
 };

@@ -91,6 +91,7 @@ struct RCfg {
   static constexpr int NL = NQ * 8;                                    // plain global loads per staging event
   static constexpr int NCLS = (MODE == R_FWD) ? 1 : 4;
   static_assert(TM == 32 * WP * FP, "pixel tile");
+  static_assert(FP + 5 <= VG_STATS_SLOT_DEPTH, "statistics slot: an fma chain of FP, 5 butterfly additions");
   static_assert(WC == 1 || WC == 2 || WC == 4 || WC == 8, "wavefront grid");
   static_assert(SLOTU % 64 == 0, "a step's filter slice is whole DMA instructions");
   static_assert(LDSU * 16 <= 160 * 1024, "LDS");

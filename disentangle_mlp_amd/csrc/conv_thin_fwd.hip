@@ -52,6 +52,7 @@ __device__ __forceinline__ void split_frag(float* v, bf16x8* out) {
 template <int S>
 struct FCfg {
   static constexpr int RB = (S == 1) ? 8 : 4;          // output rows per workgroup
+  static_assert(RB + 1 + 5 <= VG_STATS_SLOT_DEPTH, "statistics slot: square + RB row additions, 5 butterfly additions");
   static constexpr int RS = (S == 1) ? 5 : 6;          // register ring of input rows
   static constexpr int UNR = RS / S;                   // steps per unrolled block (ring slots compile-time)
   static constexpr int PR = S * (RB - 1) + 5;          // staged input rows

@@ -296,7 +296,7 @@ class BNConvFn(Function):
     def forward(ctx, x, gamma, beta, w, bias, running_mean, running_var, eps, momentum, act, stride, transposed,
                 bias_grad, stats_in):
         count = x.numel() // x.shape[1]
-        # bound: max |act(BN(x))| <= |gamma| sqrt(count) + |beta| (None outside the fp16-plane arithmetic): what the
+        # bound: of max |act(BN(x))|, ~|gamma| sqrt(count) + |beta| (bn.hip: bn_act_bound; None outside fp16x3): what the
         # convolution -- and, in backward, the weight gradient -- scales the operand it reads through the BatchNorm by
         if stats_in is not None and stats_in.numel():
             mean, invstd, scale, shift, bound = ops.bn_finalize_stats(stats_in, count, gamma, beta, running_mean,
@@ -492,6 +492,7 @@ def linear(x, w, bias, bias_grad=BIAS_GRAD_COMPUTE):
 
 
 def batch_norm_act(x, gamma, beta, running_mean, running_var, eps=1e-5, momentum=0.1, act=ops.ACT_NONE, stats=None):
+    ops.forget_last_amax()      # only a bound set inside BNActFn's own forward may be adopted (the HW == 1 path sets none)
     return ops.adopt_amax(BNActFn.apply(x, gamma, beta, running_mean, running_var, eps, momentum, act,
                                         stats if stats is not None and stats.numel() else None))
 

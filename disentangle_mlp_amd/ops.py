@@ -185,6 +185,13 @@ def set_amax(t, slot, in_affine=None):
     return slot
 
 
+def forget_last_amax():
+    """Called right before a Function whose forward may emit no bound: a later `adopt_amax` then matches only a bound
+    set inside that forward, never one left by an earlier (possibly freed) tensor at the same address and shape."""
+    global _last_amax
+    _last_amax = None
+
+
 def adopt_amax(out):
     """``out`` is what a torch.autograd.Function just returned: autograd hands back a NEW tensor object for the tensor its
     forward produced, without the Python attribute the producing kernel's wrapper attached.  If ``out`` is that tensor

@@ -288,9 +288,13 @@ int vg_bn_act_bwd(const float* gy, const float* x, const float* gamma, const flo
  * count = B * H * W.  vg_bn_stats does the same from a pass over x (layers whose producer cannot emit statistics).
  * vg_affine_act materialises y = act(x * scale[c] + shift[c]) (16-byte accesses when HW % 4 == 0) for consumers that cannot apply the
  * coefficients while they load.
- * act_amax (NULL, or DEVICE, zeroed by the caller): receives an upper bound of max |act(BN(x))| over the tensor -- from
- * the coefficients alone (|x - mean| <= sigma sqrt(count - 1), so |BN(x)| <= |gamma| sqrt(count) + |beta|): what an
- * fp16-plane convolution that applies scale / shift on load needs as vg_conv_fusion.in_amax, without a pass over x.
+ * act_amax (NULL, or DEVICE, zeroed by the caller): receives an upper bound of max |act(x * scale + shift)| over the
+ * tensor, for the scale / shift written -- from the sums alone, without a pass over x: |x - mean| <= sigma sqrt(count - 1)
+ * for the EXACT sigma, which is bounded from the computed variance plus the sums' rounding error (relative to sum x^2;
+ * in each statistics slot no term may go through more than 16 roundings: a short fma chain and a butterfly), so that
+ * a variance lost to cancellation (|mean| >> sigma) cannot push the data above the bound.  For accurate sums it is
+ * ~|gamma| sqrt(count) + |beta|.  What an fp16-plane convolution that applies scale / shift on load needs as
+ * vg_conv_fusion.in_amax.
  * y_amax of vg_affine_act: the exact max |y| (see vg_absmax). */
 int vg_bn_finalize_stats(const float* stats, int nslots, int C, double count, const float* gamma, const float* beta,
                          float* running_mean, float* running_var, float* save_mean, float* save_invstd,

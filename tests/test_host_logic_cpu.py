@@ -385,3 +385,27 @@ def test_emitted_weight_bounds_belong_to_one_tensor_object_and_one_version():
     del w
     gc.collect()
     assert ops._wbound_emitted[key][0]() is None   # a new tensor that re-uses the id can never match the dead reference
+
+
+def test_batch_norm_act_adopts_only_a_bound_set_inside_its_own_forward(monkeypatch):
+    """functional.batch_norm_act hands its output the bound its forward's kernel emitted (ops.adopt_amax matches the
+    latest set_amax by address and shape).  A forward that emits none (the HW == 1 path) must not pass on a bound an
+    EARLIER tensor left, even when its output re-uses that tensor's memory with the same shape."""
+    import torch
+    from disentangle_mlp_amd import functional as HF, ops
+    x, gamma, beta = torch.zeros(8, 4), torch.ones(4), torch.zeros(4)
+    stale, stale_slot = torch.zeros(8, 4), torch.full((1,), 1e-3)
+    ops.set_amax(stale, stale_slot)                       # an earlier producer's output ...
+    monkeypatch.setattr(HF.BNActFn, "apply", lambda *a: stale.view(8, 4))   # ... whose block the next output re-uses
+    out = HF.batch_norm_act(x, gamma, beta, None, None)
+    assert out.data_ptr() == stale.data_ptr() and not hasattr(out, "_vg_amax")
+
+    own_slot = torch.full((1,), 7.0)
+
+    def emitting_forward(*a):                             # a forward whose kernel emits the bound of its output
+        y = torch.zeros(8, 4)
+        ops.set_amax(y, own_slot)
+        return y.view(8, 4)                               # autograd hands back a new tensor object for it
+    monkeypatch.setattr(HF.BNActFn, "apply", emitting_forward)
+    out = HF.batch_norm_act(x, gamma, beta, None, None)
+    assert out._vg_amax[2] is own_slot and out._vg_amax[0] == out._version

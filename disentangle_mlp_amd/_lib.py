@@ -90,6 +90,9 @@ TUNING_LIB_PATH = os.path.join(_HERE, "libvaegan_hip_tuning.so")
 TUNING_SIGNATURES = {
     "vg_debug_set_conv_tile": (_I, [_I, _I]),
     "vg_debug_set_wgrad": (_I, [_I, _I]),
+    "vg_debug_wgrad_plan": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "vg_debug_wgrad_split_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _P]),
+    "vg_debug_wgrad_thin_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "vg_debug_set_conv_bf16split_tile": (_I, [_I]),
     "vg_debug_set_conv_ring_tile": (_I, [_I]),
 }

@@ -193,6 +193,7 @@ int vg_internal_ring_conv(int mode, const float* x, const void* packed, const fl
 #ifdef VG_TUNING
 void vg_internal_ring_set_variant(int v);
 void vg_internal_wx_set_th(int th);
+int vg_internal_wgrad_reducer(const float* slabs, const float* dw, int n, int splits);   // conv_wgrad.hip: 0 / 1 / 2 / 3 = slab_sum4 / reduce<16> / reduce<4> / slab_sum1
 #endif
 int vg_internal_convT_s1_thin(const float* x, const float* w, const float* bias, float* y, int B, int Cin, int H,
                               int W, int Cout, hipStream_t st);

@@ -276,6 +276,19 @@ int launch_tw(const TWArgs& A, const TWPlan& p, int planes, hipStream_t st) {
 
 }  // namespace
 
+#ifdef VG_TUNING
+// the plan vg_conv5x5_thin_wgrad_bf16split would launch, and the kernel that then sums its slabs into dw (only the
+// alignment of the two pointers matters); VG_ERR_BAD_ARG: shape not taken
+extern "C" int vg_debug_wgrad_thin_plan(int B, int Cin, int H, int W, int Cout, int stride, int planes, const void* dw,
+                                        const void* workspace, int* out) {
+  TWPlan p;
+  if (!out || !make_twplan(B, Cin, H, W, Cout, stride, planes, p)) return VG_ERR_BAD_ARG;
+  out[0] = p.mt; out[1] = p.rb; out[2] = p.bands; out[3] = p.upw; out[4] = p.wgs;
+  out[5] = vg_internal_wgrad_reducer((const float*)workspace, (const float*)dw, Cout * Cin * 25, p.wgs);
+  return 0;
+}
+#endif
+
 extern "C" size_t vg_conv5x5_thin_wgrad_bf16split_workspace_bytes(int B, int Cin, int H, int W, int Cout, int stride,
                                                                   int planes) {
   TWPlan p;

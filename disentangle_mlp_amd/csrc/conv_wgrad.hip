@@ -274,28 +274,42 @@ __global__ __launch_bounds__(64 * NW) void wgrad_reduce_kernel(const float* __re
 // The same sum for the common case -- n % 4 == 0, 16-byte aligned, fewer than 64 slabs: 16 bytes per lane, eight slabs'
 // loads in flight per thread, added in slab order.  (The 4-byte form above took 10 us for the 17 MB of a Linear GEMM's
 // sixteen slabs and 13 us for a K-split convolution's 32 MB: 5 us and 8 us here.)
-__global__ __launch_bounds__(256) void slab_sum4_kernel(const f32x4* __restrict__ slabs, f32x4* __restrict__ out, int n4,
-                                                       int splits, int accumulate) {
+template <class V>
+__device__ __forceinline__ void slab_sum_body(const V* __restrict__ slabs, V* __restrict__ out, int nv, int splits,
+                                              int accumulate) {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n4) return;
-  f32x4 s = {0.f, 0.f, 0.f, 0.f};
+  if (i >= nv) return;
+  V s = V{};
   int k = 0;
   for (; k + 8 <= splits; k += 8) {
-    f32x4 v[8];
+    V v[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = slabs[(size_t)(k + j) * n4 + i];
+    for (int j = 0; j < 8; ++j) v[j] = slabs[(size_t)(k + j) * nv + i];
 #pragma unroll
     for (int j = 0; j < 8; ++j) s += v[j];
   }
   for (; k + 4 <= splits; k += 4) {
-    f32x4 v[4];
+    V v[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = slabs[(size_t)(k + j) * n4 + i];
+    for (int j = 0; j < 4; ++j) v[j] = slabs[(size_t)(k + j) * nv + i];
 #pragma unroll
     for (int j = 0; j < 4; ++j) s += v[j];
   }
-  for (; k < splits; ++k) s += slabs[(size_t)k * n4 + i];
+  for (; k < splits; ++k) s += slabs[(size_t)k * nv + i];
   out[i] = accumulate ? s + out[i] : s;
+}
+
+__global__ __launch_bounds__(256) void slab_sum4_kernel(const f32x4* __restrict__ slabs, f32x4* __restrict__ out, int n4,
+                                                       int splits, int accumulate) {
+  slab_sum_body<f32x4>(slabs, out, n4, splits, accumulate);
+}
+
+// The same sum, element by element in the same slab order -- the same bits -- for a dw (or slabs) that is only 4-byte
+// aligned: a view into a flat gradient buffer.  (The order of the sum must not depend on where dw lives:
+// wgrad_reduce_kernel adds the slabs in another order.)
+__global__ __launch_bounds__(256) void slab_sum1_kernel(const float* __restrict__ slabs, float* __restrict__ out, int n,
+                                                       int splits, int accumulate) {
+  slab_sum_body<float>(slabs, out, n, splits, accumulate);
 }
 
 struct Plan {
@@ -343,35 +357,52 @@ int launch_w(const WArgs& A, hipStream_t st) {
   return 0;
 }
 
+// K groups of the planned tile: the 8-wave K-split form exists for the 128-row, 5-channel tile only
+int plan_ks(const Plan& p) { return (p.tm == 128 && p.cit == 5 && g_wgrad_ks == 2) ? 2 : 1; }
+
+// gy rows read as aligned 16-byte pieces
+int plan_vec4(const Plan& p, const void* gy) { return (p.OW % 4 == 0 && ((uintptr_t)gy & 15) == 0 && g_wgrad_vec4) ? 1 : 0; }
+
 template <int S, int TW>
-int dispatch_tm(const WArgs& A, int tm, int cit, hipStream_t st) {
+int dispatch_tm(const WArgs& A, int tm, int cit, int ks, hipStream_t st) {
   if (tm == 128 && cit == 10) return launch_w<WCfg<S, TW, 128, 1, 10>>(A, st);
-  if (tm == 128) return g_wgrad_ks == 2 ? launch_w<WCfg<S, TW, 128, 2>>(A, st) : launch_w<WCfg<S, TW, 128>>(A, st);
+  if (tm == 128) return ks == 2 ? launch_w<WCfg<S, TW, 128, 2>>(A, st) : launch_w<WCfg<S, TW, 128>>(A, st);
   if (tm == 64) return launch_w<WCfg<S, TW, 64>>(A, st);
   return launch_w<WCfg<S, TW, 32>>(A, st);
 }
 
 template <int S>
-int dispatch_tw(const WArgs& A, int tw, int tm, int cit, hipStream_t st) {
+int dispatch_tw(const WArgs& A, int tw, int tm, int cit, int ks, hipStream_t st) {
   switch (tw) {
-    case 8: return dispatch_tm<S, 8>(A, tm, cit, st);
-    case 16: return dispatch_tm<S, 16>(A, tm, cit, st);
-    case 32: return dispatch_tm<S, 32>(A, tm, cit, st);
-    default: return dispatch_tm<S, 64>(A, tm, cit, st);
+    case 8: return dispatch_tm<S, 8>(A, tm, cit, ks, st);
+    case 16: return dispatch_tm<S, 16>(A, tm, cit, ks, st);
+    case 32: return dispatch_tm<S, 32>(A, tm, cit, ks, st);
+    default: return dispatch_tm<S, 64>(A, tm, cit, ks, st);
   }
+}
+
+// which kernel sums the slabs: 0 slab_sum4_kernel, 1 wgrad_reduce_kernel<16>, 2 wgrad_reduce_kernel<4>, 3 slab_sum1_kernel.
+// Only the shape decides the ORDER of the sum (0 and 3 add in the same order); the pointers' alignment only the load width.
+enum { RED_SUM4 = 0, RED_16 = 1, RED_4 = 2, RED_SUM1 = 3 };
+int pick_reducer(const float* slabs, const float* dw, int n, int splits) {
+  if (splits < 64 && n % 4 == 0) return ((((uintptr_t)slabs | (uintptr_t)dw) & 15) == 0) ? RED_SUM4 : RED_SUM1;
+  return (splits >= 64 && cdiv(n, 64) < 1024) ? RED_16 : RED_4;
 }
 
 }  // namespace
 
 // shared with wgrad_bf16split.hip: dw[i] = sum over `splits` slabs of n floats, fixed order
 int vg_internal_wgrad_reduce(const float* slabs, float* dw, int n, int splits, hipStream_t st, int accumulate) {
-  if (splits < 64 && n % 4 == 0 && (((uintptr_t)slabs | (uintptr_t)dw) & 15) == 0) {
+  const int red = pick_reducer(slabs, dw, n, splits);
+  if (red == RED_SUM4) {
     hipLaunchKernelGGL(slab_sum4_kernel, dim3(cdiv(n / 4, 256)), dim3(256), 0, st, (const f32x4*)slabs, (f32x4*)dw, n / 4,
                        splits, accumulate);
     VG_CHECK_LAUNCH();
     return 0;
   }
-  if (splits >= 64 && cdiv(n, 64) < 1024)
+  if (red == RED_SUM1)
+    hipLaunchKernelGGL(slab_sum1_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, slabs, dw, n, splits, accumulate);
+  else if (red == RED_16)
     hipLaunchKernelGGL(wgrad_reduce_kernel<16>, dim3(cdiv(n, 64)), dim3(1024), 0, st, slabs, dw, n, splits, accumulate);
   else
     hipLaunchKernelGGL(wgrad_reduce_kernel<4>, dim3(cdiv(n, 64)), dim3(256), 0, st, slabs, dw, n, splits, accumulate);
@@ -388,6 +419,21 @@ extern "C" int vg_debug_set_wgrad(int what, int value) {
   else if (what == 4) g_wgrad_vec4 = value;
   else if (what == 5) vg_internal_wx_set_th(value);         // split-bf16 kernel: pixel rows of a chunk (1 / 2; 0 = planned)
   else return VG_ERR_BAD_ARG;
+  return 0;
+}
+
+int vg_internal_wgrad_reducer(const float* slabs, const float* dw, int n, int splits) {
+  return pick_reducer(slabs, dw, n, splits);
+}
+
+// the plan vg_conv5x5_wgrad would launch with these pointers (only their alignment matters) under the current knobs
+extern "C" int vg_debug_wgrad_plan(int B, int Cin, int H, int W, int Cout, int stride, const void* gy, const void* dw,
+                                   const void* workspace, int* out) {
+  if (!out || B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2)) return VG_ERR_BAD_ARG;
+  const Plan p = make_plan(B, Cin, H, W, Cout, stride);
+  out[0] = p.tw; out[1] = p.tm; out[2] = p.cit; out[3] = plan_ks(p); out[4] = p.splits; out[5] = plan_vec4(p, gy);
+  out[6] = pick_reducer((const float*)workspace, (const float*)dw, Cout * Cin * 25, p.splits);
+  out[7] = p.chunks; out[8] = p.cps;
   return 0;
 }
 #endif
@@ -412,8 +458,9 @@ extern "C" int vg_conv5x5_wgrad(const float* x, const float* gy, float* dw, int 
   A.B = B; A.Cin = Cin; A.H = H; A.W = W; A.Cout = Cout; A.OH = p.OH; A.OW = p.OW;
   A.mtiles = p.mtiles; A.ntiles = p.ntiles; A.splits = p.splits;
   A.tiles_w = p.tiles_w; A.tiles_hw = p.tiles_hw; A.chunks = p.chunks; A.chunks_per_split = p.cps;
-  A.vec4 = (p.OW % 4 == 0 && ((uintptr_t)gy & 15) == 0 && g_wgrad_vec4) ? 1 : 0;
-  int rc = (stride == 2) ? dispatch_tw<2>(A, p.tw, p.tm, p.cit, st) : dispatch_tw<1>(A, p.tw, p.tm, p.cit, st);
+  A.vec4 = plan_vec4(p, gy);
+  const int ks = plan_ks(p);
+  int rc = (stride == 2) ? dispatch_tw<2>(A, p.tw, p.tm, p.cit, ks, st) : dispatch_tw<1>(A, p.tw, p.tm, p.cit, ks, st);
   if (rc) return rc;
   return vg_internal_wgrad_reduce((const float*)workspace, dw, Cout * Cin * 25, p.splits, st, accumulate ? 1 : 0);
 }

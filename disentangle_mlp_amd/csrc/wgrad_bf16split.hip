@@ -492,6 +492,16 @@ int launch_wx_by_cout(const WXArgs& A, int wco, int th, long grid, hipStream_t s
 
 #ifdef VG_TUNING
 void vg_internal_wx_set_th(int th) { g_wx_th = (th == 1 || th == 2) ? th : 0; }
+
+// the plan vg_conv5x5_wgrad_bf16split would launch under the current knobs (VG_ERR_BAD_ARG: shape not taken)
+extern "C" int vg_debug_wgrad_split_plan(int B, int Cin, int H, int W, int Cout, int stride, int planes, int* out) {
+  if (!out || B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2)) return VG_ERR_BAD_ARG;
+  XPlan p;
+  if (!make_xplan(B, Cin, H, W, Cout, stride, planes & 0xff, p)) return VG_ERR_BAD_ARG;
+  out[0] = p.th; out[1] = p.wco; out[2] = p.mtiles; out[3] = p.ntiles; out[4] = p.units; out[5] = p.upw; out[6] = p.wgs;
+  out[7] = p.pieces; out[8] = p.chunks;
+  return 0;
+}
 #endif
 
 extern "C" size_t vg_conv5x5_wgrad_bf16split_workspace_bytes(int B, int Cin, int H, int W, int Cout, int stride,

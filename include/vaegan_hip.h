@@ -432,6 +432,18 @@ int vg_debug_set_conv_tile(int mode, int variant);
  * tile (1 or 2); what=3 the input channels per column tile (5 or 10); what=4: 0 = scalar gy loads;
  * what=5: output-pixel rows per chunk of vg_conv5x5_wgrad_bf16split (1 or 2; 0 = chosen by its plan). */
 int vg_debug_set_wgrad(int what, int value);
+/* The plans the three weight-gradient entry points would launch for a shape under the current knobs (host only, nothing
+ * runs) -- from the same planning code as the launch.  Pointers: only their alignment is looked at.
+ *   vg_debug_wgrad_plan        out[9]: tw, tm, cit, ks, splits, vec4, reducer (0 slab_sum4_kernel, 1 wgrad_reduce_kernel<16>,
+ *                                      2 wgrad_reduce_kernel<4>, 3 slab_sum1_kernel), chunks, chunks per split
+ *   vg_debug_wgrad_split_plan  out[9]: th, wco, mtiles, ntiles, units, upw, wgs, pieces, chunks
+ *   vg_debug_wgrad_thin_plan   out[6]: mt, rb, bands, upw, wgs, reducer
+ * VG_ERR_BAD_ARG: the entry point does not take the shape. */
+int vg_debug_wgrad_plan(int B, int Cin, int H, int W, int Cout, int stride, const void* gy, const void* dw,
+                        const void* workspace, int* out);
+int vg_debug_wgrad_split_plan(int B, int Cin, int H, int W, int Cout, int stride, int planes, int* out);
+int vg_debug_wgrad_thin_plan(int B, int Cin, int H, int W, int Cout, int stride, int planes, const void* dw,
+                             const void* workspace, int* out);
 /* split-bf16 kernels of conv_bf16split.hip: 0 = 128x128, 1 = 64x128, 2 = 64x64, 3 = 32x128, 4 = 32x256 (transposed),
  * 5 = 128x128 with the 4 wavefronts along cout, -1 = heuristic */
 int vg_debug_set_conv_bf16split_tile(int variant);

@@ -49,8 +49,8 @@ def tuning(H):
             lib.vg_debug_set_conv_tile(1, -1)
             lib.vg_debug_set_conv_bf16split_tile(-1)
             lib.vg_debug_set_conv_ring_tile(-1)
-            lib.vg_debug_set_wgrad(0, -1)
-            lib.vg_debug_set_wgrad(1, -1)
+            for what, default in ((0, -1), (1, -1), (2, 2), (3, 5), (4, 1), (5, 0)):      # tm, blocks, ks, cit, vec4, th
+                lib.vg_debug_set_wgrad(what, default)
 
 
 @pytest.fixture

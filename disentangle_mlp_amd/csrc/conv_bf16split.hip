@@ -1,10 +1,15 @@
-// OPT-IN arithmetic mode of the 5x5 convolution / transposed convolution forward kernels
-// (vg_conv5x5_fwd_bf16split, vg_convT5x5_fwd_bf16split) for gfx950: every fp32 operand is split into two
-// bf16 values (hi = bf16(x), lo = bf16(x - hi)) and each product is evaluated as
-// lo*hi + hi*lo + hi*hi on v_mfma_f32_32x32x16_bf16 with fp32 accumulation -- 3 bf16 MFMAs per
-// 16 k in 96 cycles where the exact-fp32 MFMA needs 8 x 64.  Measured error against fp64:
-// ~4.5e-6 relative (exact-fp32 path: 5e-7 .. 1e-6), so this is NOT the default: the product path
-// stays exact fp32 (conv_igemm.hip).  DESIGN.md section 8 has the measurements behind it.
+// Split-arithmetic 5x5 convolution / transposed convolution forward kernels (vg_conv5x5_fwd_bf16split,
+// vg_convT5x5_fwd_bf16split) for gfx950: the product path of every split arithmetic (`planes`), the default
+// fp16x3 included.  Every fp32 operand is split into 16-bit planes and each product is a sum of plane products on
+// the 32x32x16 MFMA with fp32 accumulation:
+//   fp16x3 (default)  fp16 hi + lo of the operand times an exact power of two (from a bound of the tensor's largest
+//                     magnitude), 3 products hi*hi, hi*lo, lo*hi: fp32-equivalent, 4e-7 .. 6e-7 against fp64;
+//   bf16x6            3 bf16 planes (8 + 8 + 8 mantissa bits), 6 products: fp32-equivalent at any dynamic range;
+//   bf16x3            2 bf16 planes, 3 products: ~4.5e-6 relative (exact-fp32 path, conv_igemm.hip: 5e-7 .. 1e-6).
+// 3 MFMAs per 16 k take 96 cycles where the exact-fp32 MFMA needs 8 x 64.  DESIGN.md sections 2 and 8 have the
+// measurements.  The entry points hand the shapes conv_ring.hip takes to it (every stride-2 forward convolution,
+// the wide transposed ones); the kernels of this file run the stride-1 forward convolution and the remaining
+// transposed ones.
 //
 // Same computations as vg_conv5x5_fwd / vg_convT5x5_fwd (nn.Conv2d / nn.ConvTranspose2d forward of
 // /root/reference/models/model.py:389-398, 450-456, 495-507 and each other's data gradients);
@@ -14,10 +19,9 @@
 //   * K step = 16 input channels of one tap (MFMA k-block 0 / 1 = channels 0-7 / 8-15).
 //   * The input patch of a 16-channel chunk lives in LDS channel-innermost, [plane hi/lo][k-block]
 //     [image][row][column] x 8 bf16 (16 B): a lane's B operand is one ds_read_b128 at a per-lane
-//     base + tap offset.  For the stride-2 forward convolution the even / odd columns of a row are
-//     kept apart so that the 32 pixels of a fragment read consecutive 16-byte units; row strides are
-//     chosen so that the rows a fragment spans fall on disjoint banks.  The fp32 -> hi/lo split
-//     happens once per element, when the prefetched registers are written to LDS.
+//     base + tap offset.  Row strides are chosen so that the rows a fragment spans fall on disjoint
+//     banks.  The fp32 -> hi/lo split happens once per element, when the prefetched registers are
+//     written to LDS.
 //   * The filter never touches LDS: it comes pre-split and pre-packed (vg_conv5x5_pack_bf16split) as
 //     [parity class][chunk][tap][plane][k-block][cout] x 8 bf16, so a lane's A operand is one 16-byte
 //     global load (32 consecutive cout = 512 contiguous bytes), prefetched one tap ahead.
@@ -31,15 +35,10 @@ namespace {
 enum { X_FWD = 0, X_TR = 1 };
 constexpr int XNT = 256;
 
-// 16-byte units per patch row (FWD stride 2: per column parity).  Chosen so that the patch rows a
+// 16-byte units per patch row.  Chosen so that the patch rows a
 // 32-pixel fragment spans start on disjoint groups of 16 units (= 256 B, one LDS bank row):
 // fragments of 2 rows x 16 pixels need the two rows 0 (mod 16) apart, 4 rows x 8 pixels 8 (mod 16).
-constexpr int row_units(int mode, int S, int TW, int PW) {
-  if (mode == X_FWD && S == 2) {                       // returns COLS (per parity); a row is 2 * COLS units
-    const int need = (PW + 1) / 2;
-    if (TW == 8) { int c = need; while ((c & 3) != 2) ++c; return c; }   // 2 rows * 2 * COLS = 8 (mod 16)
-    return (need + 3) & ~3;                                              // 2 rows * 2 * COLS = 0 (mod 16)
-  }
+constexpr int row_units(int TW, int PW) {
   if (TW == 16) return (PW + 15) & ~15;
   if (TW == 8) { int c = PW; while ((c & 15) != 8) ++c; return c; }
   return (PW + 3) & ~3;
@@ -58,9 +57,8 @@ struct XCfg {
   static constexpr int NTMAX = (MODE == X_FWD) ? 5 : (5 + S - 1) / S;
   static constexpr int PH = (MODE == X_FWD) ? S * (TH - 1) + 5 : TH + NTMAX - 1;
   static constexpr int PW = (MODE == X_FWD) ? S * (TW - 1) + 5 : TW + NTMAX - 1;
-  static constexpr bool SPLIT = (MODE == X_FWD && S == 2);       // even / odd columns kept apart
-  static constexpr int COLS = row_units(MODE, S, TW, PW);
-  static constexpr int ROWU = SPLIT ? 2 * COLS : COLS;            // units per patch row
+  static_assert(MODE == X_TR || S == 1, "the stride-2 forward convolution runs in conv_ring.hip");
+  static constexpr int ROWU = row_units(TW, PW);                  // units per patch row
   static constexpr int IMGU = NB * PH * ROWU;                     // units per (plane, k-block) image
   static constexpr int NUNIT = 2 * NB * PH * PW;                  // staged units per chunk
   static constexpr int NQ = cdiv(NUNIT, XNT);
@@ -96,7 +94,7 @@ __host__ __device__ constexpr int x_taps_before(int S, int R, int SS) {
 template <class C, int R, int SS>
 __device__ __forceinline__ void bf16split_body(const XArgs& A, f32x4* lds, int bid, int split) {
   constexpr int MODE = C::MODE, S = C::S, NB = C::NB, TH = C::TH, TW = C::TW, PH = C::PH, PW = C::PW;
-  constexpr int COLS = C::COLS, ROWU = C::ROWU, IMGU = C::IMGU, NQ = C::NQ, FC = C::FC, FP = C::FP, NP = C::NP;
+  constexpr int ROWU = C::ROWU, IMGU = C::IMGU, NQ = C::NQ, FC = C::FC, FP = C::FP, NP = C::NP;
   constexpr int NTMAX = C::NTMAX;
   constexpr bool F16 = C::F16;
   constexpr int NTH = (MODE == X_FWD) ? 5 : (5 - R + S - 1) / S;   // taps along h / w in this class
@@ -144,7 +142,7 @@ __device__ __forceinline__ void bf16split_body(const XArgs& A, f32x4* lds, int b
     const bool ok = (e < C::NUNIT) && ih >= 0 && ih < XH && iw >= 0 && iw < XW && (b0 + nb) < A.B;
     const int nbc = min(nb, A.B - 1 - b0), ihc = min(max(ih, 0), XH - 1), iwc = min(max(iw, 0), XW - 1);
     pofs[q] = (nbc * Cin + kbs * 8) * HW + ihc * XW + iwc;
-    pdst[q] = (e < C::NUNIT) ? kbs * IMGU + (nb * PH + r) * ROWU + (C::SPLIT ? (col & 1) * COLS + (col >> 1) : col) : -1;
+    pdst[q] = (e < C::NUNIT) ? kbs * IMGU + (nb * PH + r) * ROWU + col : -1;
     pvalid |= ok ? (1u << q) : 0u;
   }
   static_assert(NQ <= 32, "validity mask");
@@ -187,8 +185,7 @@ __device__ __forceinline__ void bf16split_body(const XArgs& A, f32x4* lds, int b
   for (int f = 0; f < FP; ++f) {
     const int m = (wp * FP + f) * 32 + l32;
     const int nb = m / (TH * TW), r = m % (TH * TW);
-    // FWD stride 2: column 2*pw has parity 0 and index pw
-    base_b[f] = kb * IMGU + (nb * PH + PSTEP * (r / TW)) * ROWU + (C::SPLIT ? (r % TW) : PSTEP * (r % TW));
+    base_b[f] = kb * IMGU + (nb * PH + PSTEP * (r / TW)) * ROWU + PSTEP * (r % TW);
   }
   const int CoutP = A.CoutP;
   const size_t wstep = (size_t)2 * NP * CoutP;    // units per (chunk, tap) step
@@ -235,7 +232,7 @@ __device__ __forceinline__ void bf16split_body(const XArgs& A, f32x4* lds, int b
       constexpr bool PIN = (NP == 2) || C::WC == 4;   // 3 planes, 2 x 2 fragments: pinning makes the allocator spill
       bf16x8 bv[BPF ? 2 : 1][FP][NP];
       auto read_b = [&](int buf, int t) {
-        const int imm = (MODE == X_TR) ? (NTMAX - 1 - t) : (C::SPLIT ? (t & 1) * COLS + (t >> 1) : t);
+        const int imm = (MODE == X_TR) ? (NTMAX - 1 - t) : t;
 #pragma unroll
         for (int f = 0; f < FP; ++f)
 #pragma unroll

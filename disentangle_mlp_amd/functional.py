@@ -4,6 +4,9 @@ needed (``ctx.needs_input_grad``) is skipped -- e.g. the discriminator's weight
 gradients while it only relays gradients to the decoder (SURVEY.md section 3.1
 item 3: those gradients are discarded by the reference's next ``zero_grad``).
 """
+import os
+import threading
+
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
@@ -19,57 +22,49 @@ from . import ops
 BIAS_GRAD_COMPUTE, BIAS_GRAD_ZERO = 0, 1
 
 
-class Conv5x5Fn(Function):
-    """nn.Conv2d(k=5, p=2, stride) -- /root/reference/models/model.py:450 etc."""
+def _conv_backward(ctx, x, w, gy, need_x, need_w, need_b, aff=None, then=None):
+    """The backward of every convolution Function (``ctx``: .stride, .transposed, .bias_grad, .acc): the data gradient by
+    the opposite convolution -- handed through ``then`` (BNConvFn: the BatchNorm's backward) as soon as it is launched --,
+    the weight gradient with the roles of input and gradient swapped for a transposed layer, the layer's input read
+    through ``aff`` where the forward read it so, and the bias gradient.  Returns (gx or what ``then`` made of it, gw, gb)."""
+    s, tr = ctx.stride, ctx.transposed
+    gx = gw = gb = None
+    if need_x:
+        if not tr and (x.shape[2] % s or x.shape[3] % s):
+            raise RuntimeError("conv5x5 data gradient needs input sizes divisible by the stride")
+        gx = ops.conv5x5_fwd(gy, w, None, s) if tr else ops.convT5x5_fwd(gy, w, None, s)
+        if then is not None:
+            gx = then(gx)
+    if need_w:
+        slot = _grad_slot(ctx.acc, id(w))
+        kw = dict(out=slot.prev, accumulate=True) if slot.prev is not None else {}
+        if aff is not None:
+            kw.update(in_affine=aff, affine_on_gy=tr)
+        gw = slot.hand_over(ops.conv5x5_wgrad(gy, x, s, **kw) if tr else ops.conv5x5_wgrad(x, gy, s, **kw))
+    if need_b:
+        gb = None if ctx.bias_grad == BIAS_GRAD_ZERO else ops.channel_sum(gy)
+    return gx, gw, gb
+
+
+class ConvFn(Function):
+    """nn.Conv2d(k=5, p=2, stride) -- model.py:450 etc.; ``transposed``:
+    nn.ConvTranspose2d(k=5, p=2, stride, output_size=stride*in) -- model.py:495-507, :558-564.  Outside
+    `accumulate_param_grads`: autograd sums the gradients of a weight used twice."""
 
     @staticmethod
-    def forward(ctx, x, w, bias, stride, bias_grad):
-        ctx.stride, ctx.bias_grad = stride, bias_grad
+    def forward(ctx, x, w, bias, stride, transposed, bias_grad):
+        ctx.stride, ctx.transposed, ctx.bias_grad, ctx.acc = stride, transposed, bias_grad, None
         ctx.save_for_backward(x, w)
-        return ops.conv5x5_fwd(x, w, bias, stride)
+        return ops.convT5x5_fwd(x, w, bias, stride) if transposed else ops.conv5x5_fwd(x, w, bias, stride)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
         x, w = ctx.saved_tensors
-        gy = gy.contiguous()
-        gx = gw = gb = None
-        if ctx.needs_input_grad[0]:
-            if x.shape[2] % ctx.stride or x.shape[3] % ctx.stride:
-                raise RuntimeError("conv5x5 data gradient needs input sizes divisible by the stride")
-            gx = ops.convT5x5_fwd(gy, w, None, ctx.stride)
-        if ctx.needs_input_grad[1]:
-            gw = ops.conv5x5_wgrad(x, gy, ctx.stride)
-        if ctx.needs_input_grad[2]:
-            gb = None if ctx.bias_grad == BIAS_GRAD_ZERO else ops.channel_sum(gy)
-        return gx, gw, gb, None, None
+        return _conv_backward(ctx, x, w, gy.contiguous(), *ctx.needs_input_grad[:3]) + (None, None, None)
 
 
-class ConvT5x5Fn(Function):
-    """nn.ConvTranspose2d(k=5, p=2, stride, output_size=stride*in) -- model.py:495-507, :558-564."""
-
-    @staticmethod
-    def forward(ctx, x, w, bias, stride, bias_grad):
-        ctx.stride, ctx.bias_grad = stride, bias_grad
-        ctx.save_for_backward(x, w)
-        return ops.convT5x5_fwd(x, w, bias, stride)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gy):
-        x, w = ctx.saved_tensors
-        gy = gy.contiguous()
-        gx = gw = gb = None
-        if ctx.needs_input_grad[0]:
-            gx = ops.conv5x5_fwd(gy, w, None, ctx.stride)
-        if ctx.needs_input_grad[1]:
-            gw = ops.conv5x5_wgrad(gy, x, ctx.stride)       # roles swapped
-        if ctx.needs_input_grad[2]:
-            gb = None if ctx.bias_grad == BIAS_GRAD_ZERO else ops.channel_sum(gy)
-        return gx, gw, gb, None, None
-
-
-_defer_tls = __import__("threading").local()      # .current: the innermost active deferred_wgrad context of this thread
+_defer_tls = threading.local()      # .current: the innermost active deferred_wgrad context of this thread
 
 
 class deferred_wgrad:
@@ -103,7 +98,7 @@ class deferred_wgrad:
         return False
 
 
-_acc_tls = __import__("threading").local()
+_acc_tls = threading.local()
 
 
 class accumulate_param_grads:
@@ -138,19 +133,32 @@ def _acc_ctx():
     return getattr(_acc_tls, "current", None)
 
 
-def _acc_get(actx, key):
-    return actx.acc.get(key) if (actx is not None and actx.open) else None
+class _grad_slot:
+    """One backward pass's side of the `accumulate_param_grads` protocol for the parameter gradient(s) of one layer
+    (``key``).  ``prev``: what the layer's first pass handed autograd, for this pass's kernel to ADD into -- None on the
+    first pass and outside an open context.  `hand_over(grads)`: what this pass hands autograd -- its own result on the
+    first pass (remembered), None for everything that was added into ``prev``."""
+    __slots__ = ("acc", "key", "prev")
 
+    def __init__(self, actx, key):
+        self.acc = actx.acc if (actx is not None and actx.open) else None
+        self.key = key
+        self.prev = self.acc.get(key) if self.acc is not None else None
 
-def _acc_put(actx, key, value):
-    """Remembers ALIASES (detach(): a new tensor object on the same storage) -- a second reference to the gradient tensor
-    itself would make autograd's AccumulateGrad copy it instead of adopting it as ``.grad`` (71 copies per iteration)."""
-    if actx is not None and actx.open:
-        actx.acc[key] = tuple(t.detach() for t in value) if isinstance(value, tuple) else value.detach()
+    def hand_over(self, grads):
+        many = isinstance(grads, tuple)
+        if self.prev is not None:
+            return (None,) * len(grads) if many else None
+        if self.acc is not None:
+            # Remembers ALIASES (detach(): a new tensor object on the same storage) -- a second reference to the gradient
+            # tensor itself would make autograd's AccumulateGrad copy it instead of adopting it as ``.grad`` (71 copies
+            # per iteration).
+            self.acc[self.key] = tuple(t.detach() for t in grads) if many else grads.detach()
+        return grads
 
 
 DEFER_MIN_WEIGHTS = 1 << 20
-DEFER_WGRAD = __import__("os").environ.get("VG_DEFER_WGRAD", "1") != "0"      # 0: deferred_wgrad() does nothing
+DEFER_WGRAD = os.environ.get("VG_DEFER_WGRAD", "1") != "0"      # 0: deferred_wgrad() does nothing
 
 
 class LinearFn(Function):
@@ -196,16 +204,22 @@ class LinearFn(Function):
                     if len(pairs) > 1:
                         wg, wx = torch.cat([p[0] for p in pairs]), torch.cat([p[1] for p in pairs])
             if wg is not None:
-                prev = _acc_get(ctx.acc, id(w))
+                slot = _grad_slot(ctx.acc, id(w))
                 split = ops.linear_split_ok(wg.shape[0], w.numel())
-                if prev is None:
-                    gw = ops.linear_wgrad(wg, wx) if split else wg.t() @ wx
-                    _acc_put(ctx.acc, id(w), gw)
+                if slot.prev is None:
+                    gw = slot.hand_over(ops.linear_wgrad(wg, wx) if split else wg.t() @ wx)
                 elif split:
-                    prev.add_(ops.linear_wgrad(wg, wx))
+                    slot.prev.add_(ops.linear_wgrad(wg, wx))
                 else:
-                    prev.addmm_(wg.t(), wx)                  # the layer's second use: added in the GEMM's epilogue
+                    slot.prev.addmm_(wg.t(), wx)             # the layer's second use: added in the GEMM's epilogue
         return gx, gw, gb, None
+
+
+def _bn_backward(ctx, gy, x, gamma, beta, mean, invstd, need_p):
+    """vg_bn_act_bwd with the parameter gradients under the accumulate protocol (BNActFn, BNConvFn)."""
+    slot = _grad_slot(ctx.acc if need_p else None, id(gamma))
+    gx, dg, db = ops.bn_act_bwd(gy, x, gamma, beta, mean, invstd, ctx.act, need_p, accumulate_into=slot.prev)
+    return (gx,) + (slot.hand_over((dg, db)) if need_p else (dg, db))
 
 
 class BNActFn(Function):
@@ -232,12 +246,7 @@ class BNActFn(Function):
     def backward(ctx, gy):
         x, gamma, beta, mean, invstd = ctx.saved_tensors
         need_p = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
-        prev = _acc_get(ctx.acc, id(gamma)) if need_p else None
-        gx, dg, db = ops.bn_act_bwd(gy.contiguous(), x, gamma, beta, mean, invstd, ctx.act, need_p, accumulate_into=prev)
-        if prev is not None:
-            dg = db = None                                   # added into the first pass's tensors
-        elif need_p:
-            _acc_put(ctx.acc, id(gamma), (dg, db))
+        gx, dg, db = _bn_backward(ctx, gy.contiguous(), x, gamma, beta, mean, invstd, need_p)
         return gx, dg, db, None, None, None, None, None, None
 
 
@@ -263,24 +272,7 @@ class ConvStatsFn(Function):
         if gy is None:
             return (None,) * 6
         x, w = ctx.saved_tensors
-        gy = gy.contiguous()
-        s, tr = ctx.stride, ctx.transposed
-        gx = gw = gb = None
-        if ctx.needs_input_grad[0]:
-            if not tr and (x.shape[2] % s or x.shape[3] % s):
-                raise RuntimeError("conv5x5 data gradient needs input sizes divisible by the stride")
-            gx = ops.conv5x5_fwd(gy, w, None, s) if tr else ops.convT5x5_fwd(gy, w, None, s)
-        if ctx.needs_input_grad[1]:
-            prev = _acc_get(ctx.acc, id(w))
-            kw = dict(out=prev, accumulate=True) if prev is not None else {}
-            gw = ops.conv5x5_wgrad(gy, x, s, **kw) if tr else ops.conv5x5_wgrad(x, gy, s, **kw)
-            if prev is not None:
-                gw = None                                    # added into the first pass's tensor
-            else:
-                _acc_put(ctx.acc, id(w), gw)
-        if ctx.needs_input_grad[2]:
-            gb = None if ctx.bias_grad == BIAS_GRAD_ZERO else ops.channel_sum(gy)
-        return gx, gw, gb, None, None, None
+        return _conv_backward(ctx, x, w, gy.contiguous(), *ctx.needs_input_grad[:3]) + (None, None, None)
 
 
 class BNConvFn(Function):
@@ -320,31 +312,17 @@ class BNConvFn(Function):
         if gy is None:
             return (None,) * 14
         x, gamma, beta, mean, invstd, scale, shift, w, bound = ctx.saved_tensors
-        gy = gy.contiguous()
-        s, tr, act = ctx.stride, ctx.transposed, ctx.act
-        need_bn = ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
-        gx = dg = db = gw = gb = None
-        if need_bn:
-            ga = ops.conv5x5_fwd(gy, w, None, s) if tr else ops.convT5x5_fwd(gy, w, None, s)    # grad w.r.t. act(BN(x))
-            need_p = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
-            prev = _acc_get(ctx.acc, id(gamma)) if need_p else None
-            gx, dg, db = ops.bn_act_bwd(ga, x, gamma, beta, mean, invstd, act, need_p, accumulate_into=prev)
-            if prev is not None:
-                dg = db = None                               # added into the first pass's tensors
-            elif need_p:
-                _acc_put(ctx.acc, id(gamma), (dg, db))
-        if ctx.needs_input_grad[3]:
-            aff = (scale, shift, act, bound)
-            prev = _acc_get(ctx.acc, id(w))
-            kw = dict(out=prev, accumulate=True) if prev is not None else {}
-            gw = ops.conv5x5_wgrad(gy, x, s, in_affine=aff, affine_on_gy=True, **kw) if tr \
-                else ops.conv5x5_wgrad(x, gy, s, in_affine=aff, **kw)
-            if prev is not None:
-                gw = None
-            else:
-                _acc_put(ctx.acc, id(w), gw)
-        if ctx.needs_input_grad[4]:
-            gb = None if ctx.bias_grad == BIAS_GRAD_ZERO else ops.channel_sum(gy)
+        need = ctx.needs_input_grad
+        need_p = need[1] or need[2]
+
+        def bn_backward(ga):                                 # ga: the gradient w.r.t. act(BN(x))
+            return (ga,) + _bn_backward(ctx, ga, x, gamma, beta, mean, invstd, need_p)
+
+        bn, gw, gb = _conv_backward(ctx, x, w, gy.contiguous(), need[0] or need_p, need[3], need[4],
+                                    aff=(scale, shift, ctx.act, bound), then=bn_backward)
+        # ga stays referenced until this backward returns: the allocator hands the weight gradient's temporaries the same
+        # blocks as when the three steps were written out here
+        _ga, gx, dg, db = bn if bn is not None else (None,) * 4
         return gx, dg, db, gw, gb, None, None, None, None, None, None, None, None, None
 
 
@@ -468,23 +446,19 @@ class DotSigmoidBCEFn(Function):
             return None, None, None, None, None
         feat, w, dlogit = ctx.saved_tensors
         need_w, need_b = ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
-        prev = _acc_get(ctx.acc, id(w)) if (need_w and need_b) else None
+        slot = _grad_slot(ctx.acc if (need_w and need_b) else None, id(w))
         gfeat, gw, gb = ops.dot_sigmoid_bce_bwd(dlogit, gloss.contiguous(), feat, w, ctx.needs_input_grad[0], need_w, need_b,
-                                                accumulate_into=prev)
-        if prev is not None:
-            gw = gb = None                                   # added into the first pass's tensors
-        elif need_w and need_b:
-            _acc_put(ctx.acc, id(w), (gw, gb))
-        return gfeat, gw, gb, None, None
+                                                accumulate_into=slot.prev)
+        return (gfeat,) + slot.hand_over((gw, gb)) + (None, None)
 
 
 # ------------------------------------------------------------ functional API
 def conv5x5(x, w, bias, stride, bias_grad=BIAS_GRAD_COMPUTE):
-    return Conv5x5Fn.apply(x, w, bias, stride, bias_grad)
+    return ConvFn.apply(x, w, bias, stride, False, bias_grad)
 
 
 def conv_transpose5x5(x, w, bias, stride, bias_grad=BIAS_GRAD_COMPUTE):
-    return ConvT5x5Fn.apply(x, w, bias, stride, bias_grad)
+    return ConvFn.apply(x, w, bias, stride, True, bias_grad)
 
 
 def linear(x, w, bias, bias_grad=BIAS_GRAD_COMPUTE):

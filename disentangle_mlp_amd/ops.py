@@ -4,7 +4,10 @@ PyTorch is plumbing here: it owns device memory and the current HIP stream; ever
 arithmetic op below runs in libvaegan_hip.so.  Inputs must be CUDA (ROCm) fp32
 tensors -- there is deliberately no CPU path.
 """
+import ctypes
 import os
+import weakref
+from typing import NamedTuple
 
 import torch
 
@@ -101,7 +104,7 @@ def reserve_workspace(nbytes, device):
 # (a few microseconds); inside one -- the trainer opens it around an iteration, where it
 # alone decides when weights change -- a pack is reused until `invalidate_packed_filters()`.
 USE_PACKED_FILTERS = True
-FP32_CONV_STATS = False     # see conv5x5_fwd
+FP32_CONV_STATS = False     # see route_conv
 # Arithmetic of the three convolution kernels (forward, transposed = data gradient, weight gradient):
 #   "fp16x3"  the product DEFAULT: every fp32 operand, times an exact power of two taken from a bound of the tensor's
 #             largest magnitude, split into fp16 hi + lo (11 + 11 significand bits, residual <= 2^-24), the 3 plane
@@ -114,7 +117,7 @@ FP32_CONV_STATS = False     # see conv5x5_fwd
 #   "bf16x3"  OPT-IN: 2 bf16 planes (hi/lo), 3 MFMAs per multiply, ~4.5e-6 relative error per convolution.
 # The 3-channel edge layers (conv_thin_*.hip) run bf16x6 under fp16x3 too: they are bound by HBM and issue slots.
 # Set here, or with VG_CONV_ARITH in the environment.  DESIGN.md section 2.
-CONV_ARITH = __import__("os").environ.get("VG_CONV_ARITH", "fp16x3")
+CONV_ARITH = os.environ.get("VG_CONV_ARITH", "fp16x3")
 WGRAD_SPLIT = True      # within the split modes: False keeps the weight gradient on the exact-fp32 kernel
 if CONV_ARITH not in ("fp32", "bf16x3", "bf16x6", "fp16x3"):
     raise ImportError(f"VG_CONV_ARITH={CONV_ARITH!r}: expected 'fp16x3', 'bf16x6', 'bf16x3' or 'fp32'")
@@ -231,27 +234,118 @@ def amax_of(t, in_affine=None):
     return set_amax(t, slot, in_affine)
 
 
-def conv_runs_split(op, cin, cout=None, stride=None):
-    """Whether a convolution launch of kind ``op`` ("conv_fwd" | "convT_fwd" | "conv_wgrad") with
-    ``cin`` input channels runs on the split-bf16 kernels under the active arithmetic (bench.py:
-    which roofline a launch is priced against).  Mirrors the dispatch conditions below."""
+# ---- which kernel family takes a convolution launch ------------------------------------------------------------------
+# Every kernel is correct for every shape it accepts, so a slip here costs speed and no numeric test notices:
+# tests/test_host_logic_cpu.py pins the routes of the benchmarked layers.  The switches and the channel thresholds are
+# written here and nowhere else; what depends on the full shape is asked of the library (host-only queries).
+SPLIT, THIN, FP32_PACKED, FP32_PACKED_STATS, FP32_PLAIN = "split", "thin", "fp32_packed", "fp32_packed_stats", "fp32_plain"
+
+
+class ConvRoute(NamedTuple):
+    """SPLIT: conv_ring.hip / conv_bf16split.hip / wgrad_bf16split.hip; THIN: conv_thin_*.hip; FP32_PACKED[_STATS]:
+    conv_igemm.hip; FP32_PLAIN: the direct kernels on the plain filter layout, the exact-fp32 weight gradient."""
+    family: str
+    affine_on_load: bool    # the kernel applies the operand's affine while it loads; False with an affine: materialise it first
+    stats_floats: int       # statistics slots the launch fills, in floats (0: it leaves none)
+    workspace_bytes: int
+
+
+def _thin_transposed(op, cout, stride):
+    """A stride-1 transposed convolution with <= 4 output channels (the decoder's last layer, the data gradient of the
+    discriminator's first) reads the plain filter layout: the direct VALU kernel, or conv_thin_mfma.hip."""
+    return op == "convT_fwd" and stride == 1 and cout is not None and cout <= 4
+
+
+def _split_asked(op, cin, cout, stride):
+    """Whether the launch goes to the split kernels of the active arithmetic (the weight gradient: if they take the shape)."""
     planes = _planes()
     if not planes:
         return False
-    if cin <= 3 and op in ("conv_fwd", "conv_wgrad"):
-        return THIN_SPLIT          # conv_thin_fwd.hip / conv_thin_wgrad.hip (shapes they take: output width % 32 / % 16)
     if op == "conv_wgrad":
+        # thin inputs stay on the exact-fp32 kernel: the re-layout of gy costs more than the split arithmetic saves
+        # (measured: 2 planes pay off from 16 input channels, 3 planes from 32)
         return WGRAD_SPLIT and cin >= (16 if (planes & 0xff) == 2 else 32)
-    if op == "convT_fwd" and stride == 1 and cout is not None and cout <= 4:
-        return THIN_SPLIT and cin == 32 and cout <= 3          # conv_thin_mfma.hip
-    return cin % 16 == 0
+    return cin % 16 == 0 and not _thin_transposed(op, cout, stride)
 
 
+def _thin_asked(op, cin, cout, stride):
+    """Whether the launch is offered to the 3-channel edge kernels (they say which shapes they take)."""
+    if not (_planes() and THIN_SPLIT):
+        return False
+    return _thin_transposed(op, cout, stride) if op == "convT_fwd" else cin <= 3
+
+
+def conv_runs_split(op, cin, cout=None, stride=None):
+    """Whether a convolution launch of kind ``op`` ("conv_fwd" | "convT_fwd" | "conv_wgrad") with
+    ``cin`` input channels runs on the split-bf16 kernels under the active arithmetic (bench.py:
+    which roofline a launch is priced against).  `route_conv` without the spatial shape: the edge kernels' limits
+    on the image size are not asked (the 32 -> 3 transposed one is asked at a 16 x 16 image)."""
+    if _split_asked(op, cin, cout, stride):
+        return True
+    if not _thin_asked(op, cin, cout, stride):
+        return False
+    return op != "convT_fwd" or bool(_lib.load().vg_convT5x5_s1_thin_bf16split_ok(cin, 16, 16, cout))
+
+
+def conv_fusable(transposed, cin, cout, stride):
+    """Whether the kernel of this layer (under the active arithmetic) applies a producer's BatchNorm + activation
+    while it loads its input and can leave output statistics (include/vaegan_hip.h, vg_conv_fusion)."""
+    return bool(_planes()) and bool(_lib.load().vg_conv5x5_bf16split_fusable(1 if transposed else 0, cin, cout, stride))
+
+
+def route_conv(op, B, Cin, H, W, Cout, stride, affine=None, want_stats=False):
+    """The one decision "which kernel runs this convolution launch": ``op`` "conv_fwd" | "convT_fwd" | "conv_wgrad" on
+    the full shape (of x and, for the weight gradient, gy's channels), ``affine`` None | "x" | "gy": the operand read as
+    act(v * scale[c] + shift[c]), ``want_stats``: the caller wants the output's statistics slots (their size is asked
+    only then).  Host only: no tensor, no launch; reads the arithmetic and the switches as they are now."""
+    lib = _lib.load()
+    shape = (B, Cin, H, W, Cout, stride)
+    split, thin = _split_asked(op, Cin, Cout, stride), _thin_asked(op, Cin, Cout, stride)
+    if op == "conv_wgrad":
+        need = lib.vg_conv5x5_wgrad_bf16split_workspace_bytes(*shape, _planes()) if split else 0     # 0: shape not taken
+        if need:
+            return ConvRoute(SPLIT, affine is not None, 0, need)
+        # <= 3 input channels: one read pass over gy (a producer's BatchNorm + activation applied to it on load: the weight
+        # gradient of the decoder's last layer), x split once per workgroup into shifted plane copies in LDS
+        need = lib.vg_conv5x5_thin_wgrad_bf16split_workspace_bytes(*shape, _thin_planes()) if thin else 0   # 0: shape not taken
+        if need:
+            return ConvRoute(THIN, affine == "gy", 0, need)
+        return ConvRoute(FP32_PLAIN, False, 0, lib.vg_conv5x5_wgrad_workspace_bytes(*shape))
+    tr = op == "convT_fwd"
+    if split:
+        fus = conv_fusable(tr, Cin, Cout, stride)
+        q = "vg_convT5x5_fwd_bf16split" if tr else "vg_conv5x5_fwd_bf16split"
+        n = getattr(lib, q + "_stats_floats")(*shape, _planes()) if (want_stats and fus) else 0
+        # workspace: split-K slabs (forward: deep-K layers only, transposed: small grids only)
+        return ConvRoute(SPLIT, fus and affine is not None, n, getattr(lib, q + "_workspace_bytes")(*shape, _planes()))
+    if thin and tr and lib.vg_convT5x5_s1_thin_bf16split_ok(Cin, H, W, Cout):
+        # 32 -> (<= 3) channels: filter resident in registers, one pass over x (BatchNorm + activation applied on load)
+        return ConvRoute(THIN, affine is not None, 0, 0)
+    if thin and not tr and lib.vg_conv5x5_thin_bf16split_ok(Cin, H, W, Cout, stride):
+        # <= 3 input channels: filter resident in registers, one write pass over y, statistics on the way out
+        return ConvRoute(THIN, False, lib.vg_conv5x5_thin_bf16split_stats_floats(*shape) if want_stats else 0, 0)
+    if USE_PACKED_FILTERS and not _thin_transposed(op, Cout, stride):
+        # The exact-fp32 kernel can leave the next BatchNorm's statistics too (vg_conv5x5_fwd_packed_stats), but on the
+        # 3-channel first layers -- 16 384 slots for 32 channels at B = 128 -- writing and reducing the slots costs more
+        # than the one pass over the output it saves (measured: +0.26 ms per iteration): opt-in only.
+        n = lib.vg_conv5x5_fwd_packed_stats_floats(*shape) if (want_stats and FP32_CONV_STATS and not tr) else 0
+        return ConvRoute(FP32_PACKED_STATS if n else FP32_PACKED, False, n, 0)
+    return ConvRoute(FP32_PLAIN, False, 0, 0)
+
+
+def _launch(key, symbol, *args):
+    """One convolution launch on the current stream, timed under ``key`` while `start_timing` is active."""
+    with _timed(key):
+        check(getattr(_lib.load(), symbol)(*args, _stream()), symbol)
+
+
+# ---- packed filters --------------------------------------------------------------------------------------------------
 _pack_scope_depth = 0
 _wbound_cache = {}    # Linear weights: data_ptr -> (version, shape, bound slot); lives and dies with the pack cache's entries
-_pack_cache = {}      # (data_ptr, transposed, stride, shape) -> [valid, version, packed tensor]
+_pack_cache = {}      # (data_ptr, layout, transposed, stride, shape, planes) -> [valid, version, packed tensor]
 _pack_scratch = {}    # (device, stream, numel) -> tensor, for un-cached packs
 _PACK_CACHE_MAX = 64  # entries (a beta-VAE-GAN iteration uses 21); beyond it the cache is rebuilt
+PACK_FP32, PACK_SPLIT = "fp32", "split"      # layouts: vg_conv5x5_pack (conv_igemm.hip) / vg_conv5x5_pack_bf16split
 
 
 class packed_filter_scope:
@@ -299,42 +393,54 @@ def invalidate_packed_filters(params=None):
             _wbound_cache.pop(p.data_ptr(), None)
 
 
-def _packed_filter(lib, w, cout, cin, transposed, stride):
-    bf16x3 = transposed >= 2                      # 2 / 3: split-bf16 pack of the opt-in modes (conv / transposed conv)
-    planes = _planes()
-    if bf16x3 and _pack_log is not None:
+def _pack_floats(lib, cout, cin, layout):
+    if layout == PACK_SPLIT:
+        return lib.vg_conv5x5_packed_bf16split_bytes(cout, cin, _planes()) // 4
+    return lib.vg_conv5x5_packed_floats(cout, cin)
+
+
+def _pack_entry(lib, w, cout, cin, layout, transposed, stride):
+    """(the pack cache's entry [valid, version, packed tensor] of this weight in this layout -- created, stale, when it is
+    asked for the first time --, whether its pack is that of the weight as it is now)."""
+    key = (w.data_ptr(), layout, transposed, stride, tuple(w.shape), _planes() if layout == PACK_SPLIT else 0)
+    ent = _pack_cache.get(key)
+    if ent is None:
+        n = _pack_floats(lib, cout, cin, layout)
+        ent = _pack_cache[key] = [False, -1, torch.empty(n, dtype=torch.float32, device=w.device)]
+    return ent, ent[0] and ent[1] == w._version
+
+
+def _packed_filter(lib, w, cout, cin, layout, transposed, stride):
+    split_layout = layout == PACK_SPLIT
+    if split_layout and _pack_log is not None:
         _pack_log.append((w, cout, cin, transposed, stride))
-    n = lib.vg_conv5x5_packed_bf16split_bytes(cout, cin, planes) // 4 if bf16x3 else lib.vg_conv5x5_packed_floats(cout, cin)
     if _pack_scope_depth > 0:
-        key = (w.data_ptr(), transposed, stride, tuple(w.shape), planes if bf16x3 else 0)
-        ent = _pack_cache.get(key)
-        if ent is not None and ent[0] and ent[1] == w._version:
+        ent, fresh = _pack_entry(lib, w, cout, cin, layout, transposed, stride)
+        if fresh:
             return ent[2]
-        if ent is None:
-            ent = _pack_cache[key] = [False, -1, torch.empty(n, dtype=torch.float32, device=w.device)]
         buf = ent[2]
     else:
         ent = None
-        skey = (w.device.index, _stream(), n)
+        skey = (w.device.index, _stream(), _pack_floats(lib, cout, cin, layout))
         buf = _pack_scratch.get(skey)
         if buf is None:
-            buf = _pack_scratch[skey] = torch.empty(n, dtype=torch.float32, device=w.device)
-    if bf16x3:
+            buf = _pack_scratch[skey] = torch.empty(skey[2], dtype=torch.float32, device=w.device)
+    if split_layout:
         wmax = None
-        if planes & PLANES_F16:          # a fresh (zeroed) slot per pack: the bound follows the weights down as well as up
+        if _f16():          # a fresh (zeroed) slot per pack: the bound follows the weights down as well as up
             wmax = _amax_slot(w.device)
             check(lib.vg_absmax(w.data_ptr(), w.numel(), wmax.data_ptr(), _stream()), "vg_absmax")
-        check(lib.vg_conv5x5_pack_bf16split(w.data_ptr(), buf.data_ptr(), cout, cin, transposed - 2, stride, planes,
+        check(lib.vg_conv5x5_pack_bf16split(w.data_ptr(), buf.data_ptr(), cout, cin, int(transposed), stride, _planes(),
                                          _ptr(wmax), _stream()), "vg_conv5x5_pack_bf16split")
     else:
-        check(lib.vg_conv5x5_pack(w.data_ptr(), buf.data_ptr(), cout, cin, transposed, stride, _stream()),
+        check(lib.vg_conv5x5_pack(w.data_ptr(), buf.data_ptr(), cout, cin, int(transposed), stride, _stream()),
               "vg_conv5x5_pack")
     if ent is not None:
         ent[0], ent[1] = True, w._version
     return buf
 
 
-_pack_log = None      # while a list: every split-bf16 pack request appends (weight tensor, cout, cin, kind, stride)
+_pack_log = None      # while a list: every split-layout pack request appends (weight tensor, cout, cin, transposed, stride)
 
 
 class record_pack_requests:
@@ -355,30 +461,22 @@ class record_pack_requests:
 
 
 def prepack_filters(requests):
-    """Pack (split-bf16 layout) every listed filter whose cached pack is stale, all in one launch.  ``requests``:
-    (weight, cout, cin, kind, stride) tuples as `record_pack_requests` collects them.  Only inside a
+    """Pack (split layout) every listed filter whose cached pack is stale, all in one launch.  ``requests``:
+    (weight, cout, cin, transposed, stride) tuples as `record_pack_requests` collects them.  Only inside a
     `packed_filter_scope` (outside it nothing is cached)."""
-    if _pack_scope_depth <= 0 or not requests:
+    if _pack_scope_depth <= 0 or not requests or not _planes():
         return
     lib = _lib.load()
-    planes = _planes()
-    if not planes:
-        return
     todo = []
-    for (w, cout, cin, kind, stride) in requests:
-        key = (w.data_ptr(), kind, stride, tuple(w.shape), planes)
-        ent = _pack_cache.get(key)
-        if ent is not None and ent[0] and ent[1] == w._version:
-            continue
-        if ent is None:
-            n = lib.vg_conv5x5_packed_bf16split_bytes(cout, cin, planes) // 4
-            ent = _pack_cache[key] = [False, -1, torch.empty(n, dtype=torch.float32, device=w.device)]
-        todo.append((w, ent, cout, cin, kind, stride))
+    for (w, cout, cin, transposed, stride) in requests:
+        ent, fresh = _pack_entry(lib, w, cout, cin, PACK_SPLIT, transposed, stride)
+        if not fresh:
+            todo.append((w, ent, cout, cin, transposed, stride))
     if not todo:
         return
     arr = (_lib.PackEntry * len(todo))()
     wmax = {}
-    if planes & PLANES_F16:              # the filters' bounds first, all in one launch (one per weight, not per layout)
+    if _f16():                           # the filters' bounds first, all in one launch (one per weight, not per layout)
         for (w, *_r) in todo:
             if w.data_ptr() not in wmax:
                 wmax[w.data_ptr()] = (w, _amax_slot(w.device))
@@ -386,20 +484,15 @@ def prepack_filters(requests):
         for i, (w, slot) in enumerate(wmax.values()):
             am[i] = _lib.AbsmaxEntry(w.data_ptr(), w.numel(), slot.data_ptr())
         check(lib.vg_absmax_multi(am, len(wmax), _stream()), "vg_absmax_multi")
-    for i, (w, ent, cout, cin, kind, stride) in enumerate(todo):
+    for i, (w, ent, cout, cin, transposed, stride) in enumerate(todo):
         slot = wmax[w.data_ptr()][1].data_ptr() if wmax else None
-        arr[i] = _lib.PackEntry(w.data_ptr(), ent[2].data_ptr(), cout, cin, kind - 2, stride, slot)
-    check(lib.vg_conv5x5_pack_bf16split_multi(arr, len(todo), planes, _stream()), "vg_conv5x5_pack_bf16split_multi")
+        arr[i] = _lib.PackEntry(w.data_ptr(), ent[2].data_ptr(), cout, cin, int(transposed), stride, slot)
+    check(lib.vg_conv5x5_pack_bf16split_multi(arr, len(todo), _planes(), _stream()), "vg_conv5x5_pack_bf16split_multi")
     for (w, ent, *_rest) in todo:
         ent[0], ent[1] = True, w._version
 
 
-def conv_fusable(transposed, cin, cout, stride):
-    """Whether the kernel of this layer (under the active arithmetic) applies a producer's BatchNorm + activation
-    while it loads its input and can leave output statistics (include/vaegan_hip.h, vg_conv_fusion)."""
-    return bool(_planes()) and bool(_lib.load().vg_conv5x5_bf16split_fusable(1 if transposed else 0, cin, cout, stride))
-
-
+# ---- the three entry points: validate, route, allocate, launch --------------------------------------------------------
 def _fusion_struct(x, in_affine, stats):
     """ctypes vg_conv_fusion (or None) + the tensors it points at (kept alive by the caller).  fp16 planes: always, with
     the bound of the input as the kernel reads it."""
@@ -410,14 +503,22 @@ def _fusion_struct(x, in_affine, stats):
         f._amax = amax_of(x, in_affine)          # kept alive with the struct
         f.in_amax = f._amax.data_ptr()
     if in_affine is not None:
-        scale, shift, act = in_affine[:3]
-        _req(scale, "in_scale"), _req(shift, "in_shift")
-        if scale.numel() != x.shape[1] or shift.numel() != x.shape[1]:
-            raise RuntimeError("in_affine: one coefficient per input channel")
-        f.in_scale, f.in_shift, f.in_act = scale.data_ptr(), shift.data_ptr(), int(act)
+        f.in_scale, f.in_shift, f.in_act = _affine_args(in_affine, x.shape[1])
     if stats is not None:
         f.stats, f.stats_floats = stats.data_ptr(), stats.numel()
     return f
+
+
+def _affine_args(in_affine, channels=None):
+    """(scale pointer, shift pointer, activation) of ``in_affine`` = (scale, shift, act[, bound]) for a kernel that applies it
+    on load; (0, 0, 0) without one."""
+    if in_affine is None:
+        return 0, 0, ACT_NONE
+    scale, shift, act = in_affine[:3]
+    _req(scale, "in_scale"), _req(shift, "in_shift")
+    if channels is not None and (scale.numel() != channels or shift.numel() != channels):
+        raise RuntimeError("in_affine: one coefficient per input channel")
+    return scale.data_ptr(), shift.data_ptr(), int(act)
 
 
 def _materialize(x, in_affine):
@@ -425,124 +526,59 @@ def _materialize(x, in_affine):
     return x if in_affine is None else affine_act(x, *in_affine[:3])
 
 
+def _conv_forward(op, x, w, bias, stride, in_affine, want_stats):
+    lib = _lib.load()
+    tr = op == "convT_fwd"
+    name = "convT5x5_fwd" if tr else "conv5x5_fwd"
+    _req(x, "x"), _req(w, "w")
+    B, Cin, H, W = x.shape
+    Cout = w.shape[1 if tr else 0]
+    if w.shape != ((Cin, Cout, 5, 5) if tr else (Cout, Cin, 5, 5)):
+        raise RuntimeError(f"{name}: weight {tuple(w.shape)} does not match input channels {Cin}")
+    if bias is not None:
+        _req(bias, "bias")
+    shape = (B, Cin, H, W, Cout, stride)
+    out_hw = (H * stride, W * stride) if tr else ((H - 1) // stride + 1, (W - 1) // stride + 1)
+    y = torch.empty((B, Cout) + out_hw, dtype=torch.float32, device=x.device)
+    r = route_conv(op, *shape, affine=None if in_affine is None else "x", want_stats=want_stats)
+    if in_affine is not None and not r.affine_on_load:
+        x, in_affine = _materialize(x, in_affine), None
+    stats = torch.empty(r.stats_floats, dtype=torch.float32, device=x.device) if r.stats_floats else None
+    io = (_ptr(bias), y.data_ptr()) + shape
+    if r.family == SPLIT:
+        f = _fusion_struct(x, in_affine, stats)
+        pk = _packed_filter(lib, w, Cout, Cin, PACK_SPLIT, tr, stride)    # the stride-2 kernel has its own step order
+        ws = workspace(r.workspace_bytes, x.device) if r.workspace_bytes else None
+        sym, args = f"vg_{name}_bf16split", (x.data_ptr(), pk.data_ptr()) + io + (
+            _planes(), _ptr(ws), ws.numel() if ws is not None else 0, ctypes.byref(f) if f is not None else None)
+    elif r.family == THIN and tr:
+        sym, args = "vg_convT5x5_s1_thin_bf16split", (x.data_ptr(), w.data_ptr()) + io[:-1] + (      # (stride 1 only)
+            _thin_planes(),) + _affine_args(in_affine)
+    elif r.family == THIN:
+        sym, args = "vg_conv5x5_thin_bf16split", (x.data_ptr(), w.data_ptr()) + io + (_thin_planes(), _ptr(stats), r.stats_floats)
+    elif r.family == FP32_PLAIN:
+        sym, args = f"vg_{name}", (x.data_ptr(), w.data_ptr()) + io
+    else:
+        pk = _packed_filter(lib, w, Cout, Cin, PACK_FP32, tr, stride)
+        sym, args = f"vg_{name}_packed", (x.data_ptr(), pk.data_ptr()) + io
+        if r.family == FP32_PACKED_STATS:
+            sym, args = sym + "_stats", args + (stats.data_ptr(), r.stats_floats)
+    _launch((op,) + shape, sym, *args)
+    return (y, stats) if want_stats else y
+
+
 def conv5x5_fwd(x, w, bias, stride, in_affine=None, want_stats=False):
     """``in_affine`` = (scale, shift, act): the input is act(x * scale[c] + shift[c]) -- the producing layer's
     train-mode BatchNorm + activation -- applied on load where the kernel can, materialised first where it cannot.
     ``want_stats``: returns (y, stats) with per-channel partial sums of y for `bn_finalize_stats`, or (y, None)
     when this layer's kernel cannot emit them."""
-    lib = _lib.load()
-    _req(x, "x"), _req(w, "w")
-    B, Cin, H, W = x.shape
-    Cout = w.shape[0]
-    if w.shape != (Cout, Cin, 5, 5):
-        raise RuntimeError(f"conv5x5_fwd: weight {tuple(w.shape)} does not match input channels {Cin}")
-    if bias is not None:
-        _req(bias, "bias")
-    OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
-    y = torch.empty((B, Cout, OH, OW), dtype=torch.float32, device=x.device)
-    stats = None
-    if _planes() and Cin % 16 == 0:
-        fus = conv_fusable(False, Cin, Cout, stride)
-        if in_affine is not None and not fus:
-            x, in_affine = _materialize(x, in_affine), None
-        if want_stats and fus:
-            n = lib.vg_conv5x5_fwd_bf16split_stats_floats(B, Cin, H, W, Cout, stride, _planes())
-            stats = torch.empty(n, dtype=torch.float32, device=x.device) if n else None
-        f = _fusion_struct(x, in_affine, stats)
-        pk = _packed_filter(lib, w, Cout, Cin, 2, stride)      # the stride-2 kernel has its own step order
-        need = lib.vg_conv5x5_fwd_bf16split_workspace_bytes(B, Cin, H, W, Cout, stride, _planes())    # split-K slabs, deep-K layers only
-        ws = workspace(need, x.device) if need else None
-        with _timed(("conv_fwd", B, Cin, H, W, Cout, stride)):
-            check(lib.vg_conv5x5_fwd_bf16split(x.data_ptr(), pk.data_ptr(), _ptr(bias), y.data_ptr(), B, Cin, H, W,
-                                            Cout, stride, _planes(), _ptr(ws), ws.numel() if need else 0,
-                                            __import__("ctypes").byref(f) if f is not None else None, _stream()),
-                  "vg_conv5x5_fwd_bf16split")
-        return (y, stats) if want_stats else y
-    x = _materialize(x, in_affine)
-    if _planes() and THIN_SPLIT and Cin <= 3 and lib.vg_conv5x5_thin_bf16split_ok(Cin, H, W, Cout, stride):
-        # <= 3 input channels: filter resident in registers, one write pass over y, statistics on the way out
-        n = lib.vg_conv5x5_thin_bf16split_stats_floats(B, Cin, H, W, Cout, stride) if want_stats else 0
-        stats = torch.empty(n, dtype=torch.float32, device=x.device) if n else None
-        with _timed(("conv_fwd", B, Cin, H, W, Cout, stride)):
-            check(lib.vg_conv5x5_thin_bf16split(x.data_ptr(), w.data_ptr(), _ptr(bias), y.data_ptr(), B, Cin, H, W, Cout,
-                                                stride, _thin_planes(), _ptr(stats), n, _stream()), "vg_conv5x5_thin_bf16split")
-        return (y, stats) if want_stats else y
-    if USE_PACKED_FILTERS:
-        pk = _packed_filter(lib, w, Cout, Cin, 0, stride)
-        # The exact-fp32 kernel can leave the next BatchNorm's statistics too (vg_conv5x5_fwd_packed_stats), but on the
-        # 3-channel first layers -- 16 384 slots for 32 channels at B = 128 -- writing and reducing the slots costs more
-        # than the one pass over the output it saves (measured: +0.26 ms per iteration): opt-in only.
-        n = lib.vg_conv5x5_fwd_packed_stats_floats(B, Cin, H, W, Cout, stride) if (want_stats and FP32_CONV_STATS) else 0
-        if n:
-            stats = torch.empty(n, dtype=torch.float32, device=x.device)
-            with _timed(("conv_fwd", B, Cin, H, W, Cout, stride)):
-                check(lib.vg_conv5x5_fwd_packed_stats(x.data_ptr(), pk.data_ptr(), _ptr(bias), y.data_ptr(), B, Cin, H,
-                                                      W, Cout, stride, stats.data_ptr(), n, _stream()),
-                      "vg_conv5x5_fwd_packed_stats")
-            return y, stats
-        with _timed(("conv_fwd", B, Cin, H, W, Cout, stride)):
-            check(lib.vg_conv5x5_fwd_packed(x.data_ptr(), pk.data_ptr(), _ptr(bias), y.data_ptr(), B, Cin, H, W,
-                                            Cout, stride, _stream()), "vg_conv5x5_fwd_packed")
-        return (y, None) if want_stats else y
-    with _timed(("conv_fwd", B, Cin, H, W, Cout, stride)):
-        check(lib.vg_conv5x5_fwd(x.data_ptr(), w.data_ptr(), _ptr(bias), y.data_ptr(), B, Cin, H, W, Cout,
-                                 stride, _stream()), "vg_conv5x5_fwd")
-    return (y, None) if want_stats else y
+    return _conv_forward("conv_fwd", x, w, bias, stride, in_affine, want_stats)
 
 
 def convT5x5_fwd(x, w, bias, stride, in_affine=None, want_stats=False):
     """w is (Cin, Cout, 5, 5); output is (B, Cout, stride*H, stride*W).  ``in_affine`` / ``want_stats``: see
     `conv5x5_fwd`."""
-    lib = _lib.load()
-    _req(x, "x"), _req(w, "w")
-    B, Cin, H, W = x.shape
-    Cout = w.shape[1]
-    if w.shape != (Cin, Cout, 5, 5):
-        raise RuntimeError(f"convT5x5_fwd: weight {tuple(w.shape)} does not match input channels {Cin}")
-    if bias is not None:
-        _req(bias, "bias")
-    y = torch.empty((B, Cout, H * stride, W * stride), dtype=torch.float32, device=x.device)
-    # stride 1 with <= 4 output channels runs the direct VALU kernel on the plain layout
-    thin = stride == 1 and Cout <= 4
-    stats = None
-    if _planes() and Cin % 16 == 0 and not thin:
-        fus = conv_fusable(True, Cin, Cout, stride)
-        if in_affine is not None and not fus:
-            x, in_affine = _materialize(x, in_affine), None
-        if want_stats and fus:
-            n = lib.vg_convT5x5_fwd_bf16split_stats_floats(B, Cin, H, W, Cout, stride, _planes())
-            stats = torch.empty(n, dtype=torch.float32, device=x.device) if n else None
-        f = _fusion_struct(x, in_affine, stats)
-        pk = _packed_filter(lib, w, Cout, Cin, 3, stride)
-        need = lib.vg_convT5x5_fwd_bf16split_workspace_bytes(B, Cin, H, W, Cout, stride, _planes())   # split-K slabs, small grids only
-        ws = workspace(need, x.device) if need else None
-        with _timed(("convT_fwd", B, Cin, H, W, Cout, stride)):
-            check(lib.vg_convT5x5_fwd_bf16split(x.data_ptr(), pk.data_ptr(), _ptr(bias), y.data_ptr(), B, Cin, H, W,
-                                             Cout, stride, _planes(), _ptr(ws), ws.numel() if need else 0,
-                                             __import__("ctypes").byref(f) if f is not None else None, _stream()),
-                  "vg_convT5x5_fwd_bf16split")
-        return (y, stats) if want_stats else y
-    if thin and _planes() and THIN_SPLIT and lib.vg_convT5x5_s1_thin_bf16split_ok(Cin, H, W, Cout):
-        # 32 -> (<= 3) channels: filter resident in registers, one pass over x (BatchNorm + activation applied on load)
-        scale, shift, act = in_affine[:3] if in_affine is not None else (None, None, ACT_NONE)
-        if scale is not None:
-            _req(scale, "in_scale"), _req(shift, "in_shift")
-        with _timed(("convT_fwd", B, Cin, H, W, Cout, stride)):
-            check(lib.vg_convT5x5_s1_thin_bf16split(x.data_ptr(), w.data_ptr(), _ptr(bias), y.data_ptr(), B, Cin, H, W, Cout,
-                                                    _thin_planes(), _ptr(scale), _ptr(shift), int(act), _stream()),
-                  "vg_convT5x5_s1_thin_bf16split")
-        return (y, None) if want_stats else y
-    x = _materialize(x, in_affine)
-    if USE_PACKED_FILTERS and not thin:
-        pk = _packed_filter(lib, w, Cout, Cin, 1, stride)
-        with _timed(("convT_fwd", B, Cin, H, W, Cout, stride)):
-            check(lib.vg_convT5x5_fwd_packed(x.data_ptr(), pk.data_ptr(), _ptr(bias), y.data_ptr(), B, Cin, H, W,
-                                             Cout, stride, _stream()), "vg_convT5x5_fwd_packed")
-        return (y, None) if want_stats else y
-    with _timed(("convT_fwd", B, Cin, H, W, Cout, stride)):
-        check(lib.vg_convT5x5_fwd(x.data_ptr(), w.data_ptr(), _ptr(bias), y.data_ptr(), B, Cin, H, W, Cout,
-                                  stride, _stream()), "vg_convT5x5_fwd")
-    return (y, None) if want_stats else y
+    return _conv_forward("convT_fwd", x, w, bias, stride, in_affine, want_stats)
 
 
 def conv5x5_wgrad(x, gy, stride, out=None, in_affine=None, affine_on_gy=False, accumulate=False):
@@ -553,64 +589,36 @@ def conv5x5_wgrad(x, gy, stride, out=None, in_affine=None, affine_on_gy=False, a
     if accumulate and out is None:
         raise RuntimeError("conv5x5_wgrad: accumulate needs the tensor to accumulate into (out=)")
     acc = 1 if accumulate else 0
-    lib = _lib.load()
     _req(x, "x"), _req(gy, "gy")
     B, Cin, H, W = x.shape
     Cout = gy.shape[1]
     OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
     if gy.shape != (B, Cout, OH, OW):
         raise RuntimeError(f"conv5x5_wgrad: gy {tuple(gy.shape)} does not match x {tuple(x.shape)} stride {stride}")
+    shape = (B, Cin, H, W, Cout, stride)
     dw = out if out is not None else torch.empty((Cout, Cin, 5, 5), dtype=torch.float32, device=x.device)
-    # thin inputs stay on the exact-fp32 kernel: the re-layout of gy costs more than the split arithmetic saves
-    # (measured: 2 planes pay off from 16 input channels, 3 planes from 32)
-    if _planes() and WGRAD_SPLIT and Cin >= (16 if (_planes() & 0xff) == 2 else 32):
-        need = lib.vg_conv5x5_wgrad_bf16split_workspace_bytes(B, Cin, H, W, Cout, stride, _planes())    # 0: shape not taken
-        if need:
-            ws = workspace(need, x.device)
-            sc, sh, act = in_affine[:3] if in_affine is not None else (None, None, 0)
-            xmax = gmax = None
-            if _f16():       # bounds of the two operands as the kernel reads them
-                xmax = amax_of(x, None if affine_on_gy else in_affine)
-                gmax = amax_of(gy, in_affine if affine_on_gy else None)
-            with _timed(("conv_wgrad", B, Cin, H, W, Cout, stride)):
-                check(lib.vg_conv5x5_wgrad_bf16split(x.data_ptr(), gy.data_ptr(), dw.data_ptr(), B, Cin, H, W, Cout, stride,
-                                                  _planes(), ws.data_ptr(), ws.numel(), _ptr(sc), _ptr(sh), int(act),
-                                                  1 if affine_on_gy else 0, _ptr(xmax), _ptr(gmax), acc, _stream()),
-                      "vg_conv5x5_wgrad_bf16split")
-            return dw
-    if _planes() and THIN_SPLIT and Cin <= 3 and (in_affine is None or affine_on_gy):
-        # <= 3 input channels: one read pass over gy (a producer's BatchNorm + activation applied to it on load: the weight
-        # gradient of the decoder's last layer), x split once per workgroup into shifted plane copies in LDS
-        need = lib.vg_conv5x5_thin_wgrad_bf16split_workspace_bytes(B, Cin, H, W, Cout, stride, _thin_planes())   # 0: shape not taken
-        if need:
-            ws = workspace(need, x.device)
-            sc, sh, act = in_affine[:3] if in_affine is not None else (None, None, 0)
-            if sc is not None:
-                _req(sc, "in_scale"), _req(sh, "in_shift")
-            with _timed(("conv_wgrad", B, Cin, H, W, Cout, stride)):
-                check(lib.vg_conv5x5_thin_wgrad_bf16split(x.data_ptr(), gy.data_ptr(), dw.data_ptr(), B, Cin, H, W, Cout,
-                                                          stride, _thin_planes(), ws.data_ptr(), ws.numel(), _ptr(sc), _ptr(sh),
-                                                          int(act), acc, _stream()), "vg_conv5x5_thin_wgrad_bf16split")
-            return dw
-    if in_affine is not None:      # the kernels below take the operand as a tensor
+    r = route_conv("conv_wgrad", *shape, affine=None if in_affine is None else ("gy" if affine_on_gy else "x"))
+    if in_affine is not None and not r.affine_on_load:      # this kernel takes the operand as a tensor
         if affine_on_gy:
             gy = _materialize(gy, in_affine)
         else:
             x = _materialize(x, in_affine)
-    if _planes() and THIN_SPLIT and Cin <= 3:
-        need = lib.vg_conv5x5_thin_wgrad_bf16split_workspace_bytes(B, Cin, H, W, Cout, stride, _thin_planes())
-        if need:
-            ws = workspace(need, x.device)
-            with _timed(("conv_wgrad", B, Cin, H, W, Cout, stride)):
-                check(lib.vg_conv5x5_thin_wgrad_bf16split(x.data_ptr(), gy.data_ptr(), dw.data_ptr(), B, Cin, H, W, Cout,
-                                                          stride, _thin_planes(), ws.data_ptr(), ws.numel(), None, None, 0, acc,
-                                                          _stream()), "vg_conv5x5_thin_wgrad_bf16split")
-            return dw
-    need = lib.vg_conv5x5_wgrad_workspace_bytes(B, Cin, H, W, Cout, stride)
-    ws = workspace(need, x.device)
-    with _timed(("conv_wgrad", B, Cin, H, W, Cout, stride)):
-        check(lib.vg_conv5x5_wgrad(x.data_ptr(), gy.data_ptr(), dw.data_ptr(), B, Cin, H, W, Cout, stride,
-                                   ws.data_ptr(), ws.numel(), acc, _stream()), "vg_conv5x5_wgrad")
+        in_affine = None
+    ws = workspace(r.workspace_bytes, x.device)
+    args = (x.data_ptr(), gy.data_ptr(), dw.data_ptr()) + shape
+    if r.family == SPLIT:
+        xmax = gmax = None
+        if _f16():       # bounds of the two operands as the kernel reads them
+            xmax = amax_of(x, None if affine_on_gy else in_affine)
+            gmax = amax_of(gy, in_affine if affine_on_gy else None)
+        sym, args = "vg_conv5x5_wgrad_bf16split", args + (_planes(), ws.data_ptr(), ws.numel()) + _affine_args(in_affine) + (
+            1 if affine_on_gy else 0, _ptr(xmax), _ptr(gmax), acc)
+    elif r.family == THIN:
+        sym, args = "vg_conv5x5_thin_wgrad_bf16split", args + (_thin_planes(), ws.data_ptr(), ws.numel()) + _affine_args(
+            in_affine) + (acc,)
+    else:
+        sym, args = "vg_conv5x5_wgrad", args + (ws.data_ptr(), ws.numel(), acc)
+    _launch(("conv_wgrad",) + shape, sym, *args)
     return dw
 
 
@@ -634,7 +642,6 @@ def set_weight_bound(w, bound):
     """``bound`` (one-element device tensor) holds max |w| as of now -- HipAdam's step emits it (VgAdamTensor.amax).
     Valid for THIS tensor object (a weak reference: an address or id re-used by another tensor never matches) until the
     next torch-side in-place write (the version counter) or the next call for this weight."""
-    import weakref
     if len(_wbound_emitted) > 256:                     # weights of trainers that no longer exist
         for k in [k for k, e in _wbound_emitted.items() if e[0]() is None]:
             del _wbound_emitted[k]
@@ -970,7 +977,6 @@ def minmax(x):
 def image_grid_u8(x, nrow=8, padding=2, normalize=False, pad_value=0.0):
     """torchvision 0.2.1 make_grid + save_image quantisation on the device: x [B,C,H,W] (C = 1 or 3)
     -> uint8 [GH,GW,3]."""
-    import ctypes
     lib = _lib.load()
     _req(x, "x")
     if x.dim() == 3:

@@ -292,7 +292,7 @@ def test_captured_graph_keeps_the_buffers_it_points_at_alive():
     try:
         ops._pack_cache.clear(), ops._workspaces.clear(), ops._pack_scratch.clear()
         for i in range(ops._PACK_CACHE_MAX + 2):                       # more entries than the cache tolerates
-            ops._pack_cache[(i, 2, 2, (1,), 3)] = [True, 0, torch.zeros(8)]
+            ops._pack_cache[(i, ops.PACK_SPLIT, False, 2, (1,), 3)] = [True, 0, torch.zeros(8)]
         ops._workspaces[("cpu", None, 0)] = torch.zeros(16, dtype=torch.uint8)
         held = ops.buffers_in_use()                                      # what a capture keeps
         refs = [weakref.ref(t) for t in held]
@@ -308,6 +308,90 @@ def test_captured_graph_keeps_the_buffers_it_points_at_alive():
     finally:
         ops._pack_cache.clear(), ops._workspaces.clear(), ops._pack_scratch.clear()
         ops._pack_cache.update(saved[0]), ops._workspaces.update(saved[1]), ops._pack_scratch.update(saved[2])
+
+
+# (op, Cin, H = W, Cout, stride, operand read through an affine, want_stats) at batch 128, then what the launch does under
+# fp16x3, bf16x6, bf16x3, fp32: kernel family [+affine: applied on load] [+stats: statistics slots filled].  The eleven
+# convolution layers of BASELINE config 2 (BENCH_LAYERS of tests/test_wgrad_gpu.py), each as forward (statistics asked
+# for, as the model does), data gradient and weight gradient, the layers behind a fused BatchNorm also with its affine
+# on the operand.  Recorded on an MI355X from the launches of the commit BEFORE `ops.route_conv` existed: the library
+# symbol each call of conv5x5_fwd / convT5x5_fwd / conv5x5_wgrad reached (vg_*_bf16split: split, vg_*thin*: thin,
+# vg_*_packed[_stats]: fp32_packed[_stats], vg_conv5x5_fwd / vg_convT5x5_fwd / vg_conv5x5_wgrad: fp32_plain), whether a
+# vg_affine_act launch preceded it, whether statistics came back.
+BENCH_ROUTES = [
+    (("conv_fwd", 3, 64, 64, 2, None, True), "thin+stats", "thin+stats", "thin+stats", "fp32_packed"),
+    (("convT_fwd", 64, 32, 3, 2, None, False), "split", "split", "split", "fp32_packed"),
+    (("conv_wgrad", 3, 64, 64, 2, None, False), "thin", "thin", "thin", "fp32_plain"),
+    (("conv_fwd", 64, 32, 128, 2, None, True), "split+stats", "split+stats", "split+stats", "fp32_packed"),
+    (("conv_fwd", 64, 32, 128, 2, "x", True), "split+affine+stats", "split+affine+stats", "split+affine+stats", "fp32_packed"),
+    (("convT_fwd", 128, 16, 64, 2, None, False), "split", "split", "split", "fp32_packed"),
+    (("conv_wgrad", 64, 32, 128, 2, None, False), "split", "split", "split", "fp32_plain"),
+    (("conv_wgrad", 64, 32, 128, 2, "x", False), "split+affine", "split+affine", "split+affine", "fp32_plain"),
+    (("conv_fwd", 128, 16, 256, 2, None, True), "split", "split", "split", "fp32_packed"),
+    (("conv_fwd", 128, 16, 256, 2, "x", True), "split+affine", "split+affine", "split+affine", "fp32_packed"),
+    (("convT_fwd", 256, 8, 128, 2, None, False), "split", "split", "split", "fp32_packed"),
+    (("conv_wgrad", 128, 16, 256, 2, None, False), "split", "split", "split", "fp32_plain"),
+    (("conv_wgrad", 128, 16, 256, 2, "x", False), "split+affine", "split+affine", "split+affine", "fp32_plain"),
+    (("conv_fwd", 3, 64, 32, 1, None, True), "thin+stats", "thin+stats", "thin+stats", "fp32_packed"),
+    (("convT_fwd", 32, 64, 3, 1, None, False), "thin", "thin", "thin", "fp32_plain"),
+    (("conv_wgrad", 3, 64, 32, 1, None, False), "thin", "thin", "thin", "fp32_plain"),
+    (("conv_fwd", 32, 64, 128, 2, None, True), "split+stats", "split+stats", "split+stats", "fp32_packed"),
+    (("conv_fwd", 32, 64, 128, 2, "x", True), "split+affine+stats", "split+affine+stats", "split+affine+stats", "fp32_packed"),
+    (("convT_fwd", 128, 32, 32, 2, None, False), "split", "split", "split", "fp32_packed"),
+    (("conv_wgrad", 32, 64, 128, 2, None, False), "split", "split", "split", "fp32_plain"),
+    (("conv_wgrad", 32, 64, 128, 2, "x", False), "split+affine", "split+affine", "split+affine", "fp32_plain"),
+    (("conv_fwd", 128, 32, 256, 2, None, True), "split+stats", "split+stats", "split+stats", "fp32_packed"),
+    (("conv_fwd", 128, 32, 256, 2, "x", True), "split+affine+stats", "split+affine+stats", "split+affine+stats", "fp32_packed"),
+    (("convT_fwd", 256, 16, 128, 2, None, False), "split", "split", "split", "fp32_packed"),
+    (("conv_wgrad", 128, 32, 256, 2, None, False), "split", "split", "split", "fp32_plain"),
+    (("conv_wgrad", 128, 32, 256, 2, "x", False), "split+affine", "split+affine", "split+affine", "fp32_plain"),
+    (("conv_fwd", 256, 16, 256, 2, None, True), "split", "split", "split", "fp32_packed"),
+    (("conv_fwd", 256, 16, 256, 2, "x", True), "split+affine", "split+affine", "split+affine", "fp32_packed"),
+    (("convT_fwd", 256, 8, 256, 2, None, False), "split", "split", "split", "fp32_packed"),
+    (("conv_wgrad", 256, 16, 256, 2, None, False), "split", "split", "split", "fp32_plain"),
+    (("conv_wgrad", 256, 16, 256, 2, "x", False), "split+affine", "split+affine", "split+affine", "fp32_plain"),
+    (("convT_fwd", 256, 8, 256, 2, None, True), "split+stats", "split+stats", "split+stats", "fp32_packed"),
+    (("conv_fwd", 256, 16, 256, 2, None, False), "split", "split", "split", "fp32_packed"),
+    (("convT_fwd", 256, 16, 128, 2, None, True), "split+stats", "split+stats", "split+stats", "fp32_packed"),
+    (("convT_fwd", 256, 16, 128, 2, "x", True), "split+affine+stats", "split+affine+stats", "split+affine+stats", "fp32_packed"),
+    (("conv_fwd", 128, 32, 256, 2, None, False), "split", "split", "split", "fp32_packed"),
+    (("conv_wgrad", 128, 32, 256, 2, "gy", False), "split+affine", "split+affine", "split+affine", "fp32_plain"),
+    (("convT_fwd", 128, 32, 32, 2, None, True), "split", "split", "split", "fp32_packed"),
+    (("convT_fwd", 128, 32, 32, 2, "x", True), "split", "split", "split", "fp32_packed"),
+    (("conv_fwd", 32, 64, 128, 2, None, False), "split", "split", "split", "fp32_packed"),
+    (("conv_wgrad", 32, 64, 128, 2, "gy", False), "split+affine", "split+affine", "split+affine", "fp32_plain"),
+    (("convT_fwd", 32, 64, 3, 1, None, True), "thin", "thin", "thin", "fp32_plain"),
+    (("convT_fwd", 32, 64, 3, 1, "x", True), "thin+affine", "thin+affine", "thin+affine", "fp32_plain"),
+    (("conv_fwd", 3, 64, 32, 1, None, False), "thin", "thin", "thin", "fp32_packed"),
+    (("conv_wgrad", 3, 64, 32, 1, "gy", False), "thin+affine", "thin+affine", "thin+affine", "fp32_plain"),
+]
+
+
+def test_benchmarked_layers_take_the_recorded_routes():
+    """Every kernel is correct for every shape it accepts, so a wrong route costs speed and passes every numeric test.
+    `ops.route_conv` takes shapes only and the library's queries are host code: the routes of the benchmarked layers are
+    pinned here, in each arithmetic, against BENCH_ROUTES; `conv_runs_split` and `conv_fusable`, as bench.py calls them,
+    agree with the router."""
+    from disentangle_mlp_amd import ops
+    prev = ops.CONV_ARITH
+    assert (ops.THIN_SPLIT, ops.WGRAD_SPLIT, ops.USE_PACKED_FILTERS, ops.FP32_CONV_STATS) == (True, True, True, False)
+    try:
+        for (op, cin, hw, cout, stride, affine, want_stats), *expected in BENCH_ROUTES:
+            for arith, want in zip(("fp16x3", "bf16x6", "bf16x3", "fp32"), expected):
+                ops.CONV_ARITH = arith
+                r = ops.route_conv(op, 128, cin, hw, hw, cout, stride, affine=affine, want_stats=want_stats)
+                got = r.family + ("+affine" if r.affine_on_load else "") + ("+stats" if r.stats_floats else "")
+                assert got == want, (arith, op, cin, hw, cout, stride, affine, want_stats)
+                # bench.py: `arith != "fp32" and conv_runs_split(op, Cin)` prices the launch against the 16-bit MFMA roof
+                assert ops.conv_runs_split(op, cin) == (r.family in (ops.SPLIT, ops.THIN))
+                assert ops.conv_runs_split(op, cin, cout, stride) == (r.family in (ops.SPLIT, ops.THIN))
+                if r.family == ops.SPLIT and op != "conv_wgrad":
+                    # bench.py: the ring kernel's name for the launches conv_fusable names; the ring kernel is the one
+                    # that applies an affine on load
+                    on_load = ops.route_conv(op, 128, cin, hw, hw, cout, stride, affine="x").affine_on_load
+                    assert ops.conv_fusable(op == "convT_fwd", cin, cout, stride) == on_load
+    finally:
+        ops.CONV_ARITH = prev
 
 
 def test_rccl_unique_id_survives_the_broadcast_box():

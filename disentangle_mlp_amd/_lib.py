@@ -14,7 +14,7 @@ import torch  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvaegan_hip.so")
-ABI_VERSION = 5      # VG_ABI_VERSION of include/vaegan_hip.h this binding was written against
+ABI_VERSION = 6      # VG_ABI_VERSION of include/vaegan_hip.h this binding was written against
 
 _P, _I, _F, _Z = c_void_p, c_int, c_float, c_size_t
 
@@ -34,6 +34,9 @@ SIGNATURES = {
     "vg_gemm_nt_f16x3_workspace_bytes": (_Z, [_I, _I, _I]),
     "vg_gemm_nt_f16x3": (_I, [_P, _P, _P, _P, _I, _I, _I, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, _P, _P,
                               _P, _Z, _P]),
+    "vg_conv_general_packed_bytes": (_Z, [_I, _I, _I, _I]),
+    "vg_conv_general_pack": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    "vg_conv_general_fwd": (_I, [_P, _P, _P, _P] + [_I] * 11 + [ctypes.c_long, _I, _P, _P, _P]),
     "vg_absmax": (_I, [_P, _Z, _P, _P]),
     "vg_absmax_affine": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "vg_absmax_multi": (_I, [_P, _I, _P]),

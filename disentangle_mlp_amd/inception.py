@@ -8,19 +8,62 @@ weight file: a ``state_dict`` with torchvision's ``inception_v3`` names (``Conv2
 downloads (scoring/inception.py:13).  There is no network here: pass ``weights=`` (a path or a state_dict); without
 weights the constructor raises, it never runs on random parameters silently.
 
-Device path (MI355X): every convolution is lowered to ONE fp32 GEMM -- 1x1 convolutions directly, the others through
-``F.unfold`` (im2col; no JIT-compiled convolution library on the path) -- with the eval-mode BatchNorm
-(eps = 0.001) folded into the GEMM's weights and bias once at load time and the ReLU applied in place.  This is an
-evaluation-side component (5.7 GFLOP per image, 10 000 images per FID): library GEMMs (hipBLASLt) are
-the right tool; the hand-written kernels of this package are the training path.
+Device path (MI355X): every convolution runs on this package's general fp16x3 implicit-GEMM kernel
+(csrc/conv_general.hip, ``ops.conv2d_bias_act``): the eval-mode BatchNorm (eps = 0.001) is folded into the filter and a
+bias once at load time, the folded filter is packed once (scaled by its bound, split into fp16 planes), the activations
+are gathered from NCHW while they are staged -- no im2col matrix exists in HBM -- and bias + ReLU are applied on the
+accumulators.  The branches of a block write their channels straight into the block's concatenated output (no
+``torch.cat``).  Bounds for the fp16 scaling: one ``vg_absmax`` pass over the network input; every convolution leaves
+max |y| for its consumer; pooled tensors inherit their input's bound (|avg|, |max| <= max |x|); no host reads.
+Pooling, the bilinear resize and the final average stay on ATen.
+
+CPU tensors, and device tensors under ``VG_INCEPTION_CONV=unfold`` (or ``inception.CONV_LOWERING = "unfold"``), take
+the earlier lowering: every convolution as ONE fp32 GEMM -- 1x1 convolutions directly, the others through ``F.unfold``
+(im2col) -- with the same folded weights and the ReLU applied in place.  It is what the kernel path is measured against.
 
 **Parity unpinned**: the pretrained weights and the reference's ``fid_stats_celeba.npz`` are not obtainable offline,
 so absolute FID values cannot be compared; the architecture arithmetic is checked against the CPU oracle
 (oracle/inception.py) on seeded random weights (tests/test_inception.py).
 """
+import os
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+# Lowering of the convolutions for DEVICE tensors: "hip" (the default: csrc/conv_general.hip) or "unfold" (im2col + fp32
+# GEMM, what CPU tensors always take).  Set here, or with VG_INCEPTION_CONV in the environment.
+CONV_LOWERING = os.environ.get("VG_INCEPTION_CONV", "hip")
+if CONV_LOWERING not in ("hip", "unfold"):
+    raise ImportError(f"VG_INCEPTION_CONV={CONV_LOWERING!r}: expected 'hip' or 'unfold'")
+
+
+def _hip(x):
+    return x.is_cuda and CONV_LOWERING == "hip"
+
+
+def _ops():
+    from . import ops            # loads libvaegan_hip.so: only the device path needs it
+    return ops
+
+
+def _pooled(x, pool):
+    """pool(x) with x's bound: |avg|, |max| <= max |x|."""
+    p = pool(x)
+    if _hip(x):
+        _ops().set_amax(p, _ops().amax_of(x))
+    return p
+
+
+def _block_out(x, channels, oh, ow):
+    """The concatenated output of a block and the one bound slot its branches add their maxima into."""
+    return torch.empty((x.shape[0], channels, oh, ow), dtype=torch.float32, device=x.device), _ops().new_amax_slot(x.device)
+
+
+def _copy_pooled(x, pooled, out, offset, slot):
+    """A pooling branch without convolution: copied into its slice; the block's bound covers x's."""
+    slot.copy_(torch.maximum(slot, _ops().amax_of(x)))
+    out[:, offset:offset + pooled.shape[1]].copy_(pooled)
 
 
 class _ConvBN(nn.Module):
@@ -30,14 +73,14 @@ class _ConvBN(nn.Module):
         super().__init__()
         self.conv = nn.Conv2d(cin, cout, kernel_size, stride=stride, padding=padding, bias=False)
         self.bn = nn.BatchNorm2d(cout, eps=0.001)
-        self._folded = None
+        self._folded = self._packed = None
 
     def _load_from_state_dict(self, *a, **k):
-        self._folded = None
+        self._folded = self._packed = None
         return super()._load_from_state_dict(*a, **k)
 
     def _apply(self, fn, *a, **k):
-        self._folded = None                      # .to(device) / .float(): re-fold on first use
+        self._folded = self._packed = None       # .to(device) / .float(): re-fold and re-pack on first use
         return super()._apply(fn, *a, **k)
 
     def folded(self):
@@ -49,7 +92,19 @@ class _ConvBN(nn.Module):
             self._folded = (w, b)
         return self._folded
 
-    def forward(self, x):
+    def packed(self):
+        if self._packed is None:
+            w, _ = self.folded()
+            with torch.no_grad():
+                self._packed = _ops().conv_general_pack(w.view(self.conv.weight.shape), self.conv.stride, self.conv.padding)
+        return self._packed
+
+    def forward(self, x, out=None, offset=0, slot=None):
+        """``out`` / ``offset`` / ``slot`` (device path only): write into channels [offset, offset + cout) of a block's
+        output and add max |y| into the block's bound slot."""
+        if _hip(x):
+            packed, meta = self.packed()
+            return _ops().conv2d_bias_act(x, packed, meta, self.folded()[1], out, offset, True, slot)
         w, b = self.folded()
         B, C, H, W = x.shape
         kh, kw = self.conv.kernel_size
@@ -80,6 +135,14 @@ class _A(nn.Module):        # FIDInceptionA
         self.branch_pool = _ConvBN(cin, pool_features, 1)
 
     def forward(self, x):
+        if _hip(x):
+            out, slot = _block_out(x, 224 + self.branch_pool.conv.out_channels, x.shape[2], x.shape[3])
+            self.branch1x1(x, out, 0, slot)
+            self.branch5x5_2(self.branch5x5_1(x), out, 64, slot)
+            self.branch3x3dbl_3(self.branch3x3dbl_2(self.branch3x3dbl_1(x)), out, 128, slot)
+            self.branch_pool(_pooled(x, _avg3), out, 224, slot)
+            _ops().set_amax(out, slot)
+            return out
         return torch.cat([self.branch1x1(x), self.branch5x5_2(self.branch5x5_1(x)),
                           self.branch3x3dbl_3(self.branch3x3dbl_2(self.branch3x3dbl_1(x))),
                           self.branch_pool(_avg3(x))], 1)
@@ -94,6 +157,13 @@ class _B(nn.Module):        # torchvision InceptionB
         self.branch3x3dbl_3 = _ConvBN(96, 96, 3, stride=2)
 
     def forward(self, x):
+        if _hip(x):
+            out, slot = _block_out(x, 480 + x.shape[1], (x.shape[2] - 3) // 2 + 1, (x.shape[3] - 3) // 2 + 1)
+            self.branch3x3(x, out, 0, slot)
+            self.branch3x3dbl_3(self.branch3x3dbl_2(self.branch3x3dbl_1(x)), out, 384, slot)
+            _copy_pooled(x, F.max_pool2d(x, kernel_size=3, stride=2), out, 480, slot)
+            _ops().set_amax(out, slot)
+            return out
         return torch.cat([self.branch3x3(x), self.branch3x3dbl_3(self.branch3x3dbl_2(self.branch3x3dbl_1(x))),
                           F.max_pool2d(x, kernel_size=3, stride=2)], 1)
 
@@ -113,6 +183,15 @@ class _C(nn.Module):        # FIDInceptionC
         self.branch_pool = _ConvBN(cin, 192, 1)
 
     def forward(self, x):
+        if _hip(x):
+            out, slot = _block_out(x, 768, x.shape[2], x.shape[3])
+            self.branch1x1(x, out, 0, slot)
+            self.branch7x7_3(self.branch7x7_2(self.branch7x7_1(x)), out, 192, slot)
+            t = self.branch7x7dbl_4(self.branch7x7dbl_3(self.branch7x7dbl_2(self.branch7x7dbl_1(x))))
+            self.branch7x7dbl_5(t, out, 384, slot)
+            self.branch_pool(_pooled(x, _avg3), out, 576, slot)
+            _ops().set_amax(out, slot)
+            return out
         b7 = self.branch7x7_3(self.branch7x7_2(self.branch7x7_1(x)))
         bd = self.branch7x7dbl_5(self.branch7x7dbl_4(self.branch7x7dbl_3(self.branch7x7dbl_2(self.branch7x7dbl_1(x)))))
         return torch.cat([self.branch1x1(x), b7, bd, self.branch_pool(_avg3(x))], 1)
@@ -129,6 +208,13 @@ class _D(nn.Module):        # torchvision InceptionD
         self.branch7x7x3_4 = _ConvBN(192, 192, 3, stride=2)
 
     def forward(self, x):
+        if _hip(x):
+            out, slot = _block_out(x, 512 + x.shape[1], (x.shape[2] - 3) // 2 + 1, (x.shape[3] - 3) // 2 + 1)
+            self.branch3x3_2(self.branch3x3_1(x), out, 0, slot)
+            self.branch7x7x3_4(self.branch7x7x3_3(self.branch7x7x3_2(self.branch7x7x3_1(x))), out, 320, slot)
+            _copy_pooled(x, F.max_pool2d(x, kernel_size=3, stride=2), out, 512, slot)
+            _ops().set_amax(out, slot)
+            return out
         b7 = self.branch7x7x3_4(self.branch7x7x3_3(self.branch7x7x3_2(self.branch7x7x3_1(x))))
         return torch.cat([self.branch3x3_2(self.branch3x3_1(x)), b7, F.max_pool2d(x, kernel_size=3, stride=2)], 1)
 
@@ -147,13 +233,27 @@ class _E(nn.Module):        # FIDInceptionE_1 (avg) / FIDInceptionE_2 (max: scor
         self.branch3x3dbl_3b = _ConvBN(384, 384, (3, 1), padding=(1, 0))
         self.branch_pool = _ConvBN(cin, 192, 1)
 
+    def _pool(self, x):
+        return _avg3(x) if self.pool == "avg" else F.max_pool2d(x, kernel_size=3, stride=1, padding=1)
+
     def forward(self, x):
+        if _hip(x):
+            out, slot = _block_out(x, 2048, x.shape[2], x.shape[3])
+            self.branch1x1(x, out, 0, slot)
+            t = self.branch3x3_1(x)
+            self.branch3x3_2a(t, out, 320, slot)
+            self.branch3x3_2b(t, out, 704, slot)
+            t = self.branch3x3dbl_2(self.branch3x3dbl_1(x))
+            self.branch3x3dbl_3a(t, out, 1088, slot)
+            self.branch3x3dbl_3b(t, out, 1472, slot)
+            self.branch_pool(_pooled(x, self._pool), out, 1856, slot)
+            _ops().set_amax(out, slot)
+            return out
         t = self.branch3x3_1(x)
         b3 = torch.cat([self.branch3x3_2a(t), self.branch3x3_2b(t)], 1)
         t = self.branch3x3dbl_2(self.branch3x3dbl_1(x))
         bd = torch.cat([self.branch3x3dbl_3a(t), self.branch3x3dbl_3b(t)], 1)
-        p = _avg3(x) if self.pool == "avg" else F.max_pool2d(x, kernel_size=3, stride=1, padding=1)
-        return torch.cat([self.branch1x1(x), b3, bd, self.branch_pool(p)], 1)
+        return torch.cat([self.branch1x1(x), b3, bd, self.branch_pool(self._pool(x))], 1)
 
 
 class _FidInception(nn.Module):
@@ -208,9 +308,16 @@ class InceptionV3(nn.Module):
             x = F.interpolate(x, size=(299, 299), mode="bilinear", align_corners=False)
         if self.normalize_input:
             x = 2 * x - 1
+        if _hip(x):
+            x = x.float().contiguous()
+            _ops().amax_of(x)                       # the one explicit bound pass; every later bound comes from a producer
+
+        def pool2(t):
+            return _pooled(t, lambda v: F.max_pool2d(v, kernel_size=3, stride=2))
+
         stages = (
-            lambda t: F.max_pool2d(n.Conv2d_2b_3x3(n.Conv2d_2a_3x3(n.Conv2d_1a_3x3(t))), kernel_size=3, stride=2),
-            lambda t: F.max_pool2d(n.Conv2d_4a_3x3(n.Conv2d_3b_1x1(t)), kernel_size=3, stride=2),
+            lambda t: pool2(n.Conv2d_2b_3x3(n.Conv2d_2a_3x3(n.Conv2d_1a_3x3(t)))),
+            lambda t: pool2(n.Conv2d_4a_3x3(n.Conv2d_3b_1x1(t))),
             lambda t: n.Mixed_6e(n.Mixed_6d(n.Mixed_6c(n.Mixed_6b(n.Mixed_6a(n.Mixed_5d(n.Mixed_5c(n.Mixed_5b(t)))))))),
             lambda t: F.adaptive_avg_pool2d(n.Mixed_7c(n.Mixed_7b(n.Mixed_7a(t))), (1, 1)),
         )

@@ -622,6 +622,75 @@ def conv5x5_wgrad(x, gy, stride, out=None, in_affine=None, affine_on_gy=False, a
     return dw
 
 
+# ---------------------------------------------------- general forward convolution (csrc/conv_general.hip)
+class ConvGeneralMeta(NamedTuple):
+    """Shape of a filter packed by `conv_general_pack` and how it is applied."""
+    cout: int
+    cin: int
+    kh: int
+    kw: int
+    sh: int
+    sw: int
+    ph: int
+    pw: int
+
+
+def _pair(v):
+    return (int(v), int(v)) if isinstance(v, int) else (int(v[0]), int(v[1]))
+
+
+def new_amax_slot(device):
+    """A zeroed bound slot several launches may add their maxima into (the branches of an Inception block)."""
+    return _amax_slot(device)
+
+
+def conv_general_pack(w, stride=1, padding=0):
+    """Pack the fp32 filter ``w`` (Cout, Cin, KH, KW) once for `conv2d_bias_act` (scaled by its bound from one
+    vg_absmax pass, split into fp16 planes); returns (packed, meta)."""
+    _req(w, "w")
+    if w.dim() != 4:
+        raise RuntimeError(f"conv_general_pack: expected a (Cout, Cin, KH, KW) filter, got {tuple(w.shape)}")
+    lib = _lib.load()
+    meta = ConvGeneralMeta(*(int(s) for s in w.shape), *_pair(stride), *_pair(padding))
+    nbytes = lib.vg_conv_general_packed_bytes(meta.cout, meta.cin, meta.kh, meta.kw)
+    if not nbytes:
+        raise RuntimeError(f"conv_general_pack: filter {tuple(w.shape)} is not taken")
+    packed = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+    check(lib.vg_conv_general_pack(w.data_ptr(), packed.data_ptr(), meta.cout, meta.cin, meta.kh, meta.kw,
+                                   amax_of(w).data_ptr(), _stream()), "vg_conv_general_pack")
+    return packed, meta
+
+
+def conv2d_bias_act(x, packed, meta, bias=None, out=None, out_channel_offset=0, relu=True, amax=None):
+    """act(conv2d(x, w, stride, padding) + bias) in the fp16x3 arithmetic, w packed by `conv_general_pack`.  ``out``: a
+    (B, C, OH, OW) tensor whose images are contiguous (a whole NCHW tensor or a channel slice of one); channels
+    [out_channel_offset, out_channel_offset + Cout) are written, the others are not touched.  ``amax``: the bound slot
+    max |y| is added to (a new one by default); the returned view of the written channels carries it."""
+    _req(x, "x")
+    if bias is not None:
+        _req(bias, "bias")
+    if x.dim() != 4 or x.shape[1] != meta.cin:
+        raise RuntimeError(f"conv2d_bias_act: input {tuple(x.shape)} does not match {meta.cin} input channels")
+    B, _, H, W = x.shape
+    OH, OW = (H + 2 * meta.ph - meta.kh) // meta.sh + 1, (W + 2 * meta.pw - meta.kw) // meta.sw + 1
+    if out is None:
+        out = torch.empty((B, meta.cout, OH, OW), dtype=torch.float32, device=x.device)
+    else:
+        if not out.is_cuda or out.dtype != torch.float32 or out.dim() != 4:
+            raise RuntimeError("conv2d_bias_act: out must be a 4-D float32 CUDA/ROCm tensor")
+        if (out.shape[0], out.shape[2], out.shape[3]) != (B, OH, OW) or out.stride()[1:] != (OH * OW, OW, 1) or \
+                not 0 <= out_channel_offset <= out.shape[1] - meta.cout or (B > 1 and out.stride(0) < out.shape[1] * OH * OW):
+            raise RuntimeError(f"conv2d_bias_act: out {tuple(out.shape)} (strides {out.stride()}) cannot take channels "
+                               f"[{out_channel_offset}, {out_channel_offset + meta.cout}) of a (B={B}, {OH}x{OW}) output")
+    view = out[:, out_channel_offset:out_channel_offset + meta.cout]
+    slot = amax if amax is not None else _amax_slot(x.device)
+    _launch(("conv_general", B, H, W) + tuple(meta), "vg_conv_general_fwd", x.data_ptr(), packed.data_ptr(), _ptr(bias),
+            view.data_ptr(), B, meta.cin, H, W, meta.cout, meta.kh, meta.kw, meta.sh, meta.sw, meta.ph, meta.pw,
+            max(out.stride(0), meta.cout * OH * OW), 1 if relu else 0, amax_of(x).data_ptr(), slot.data_ptr())
+    set_amax(view, slot)
+    return view
+
+
 # ------------------------------------------------------------------- Linear layers
 # The Linear GEMMs of the big layers (16384 <-> 2048 / 512, 128 -> 16384: model.py:460-471, 402-408, 490-492) on this
 # package's fp16x3 GEMM (csrc/gemm_split.hip) under the default arithmetic; under the opt-in arithmetics, for small

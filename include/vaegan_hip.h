@@ -43,8 +43,9 @@ extern "C" {
 /* ABI version of this header: bumped on every incompatible change of a signature, of a packed-filter layout or of a
  * workspace contract.  vg_version() returns the value the library was built with; a binding must refuse a library
  * whose version is not the header's (the .so files are build products that travel with the working tree: a stale one
- * still exports every old symbol).  3: round 3.  4: round 4 (fp16 planes: VG_PLANES_F16, the *_amax arguments). */
-#define VG_ABI_VERSION 5
+ * still exports every old symbol).  3: round 3.  4: round 4 (fp16 planes: VG_PLANES_F16, the *_amax arguments).
+ * 6: vg_conv_general_* (the general forward convolution). */
+#define VG_ABI_VERSION 6
 int vg_version(void);
 
 /* ---- 5x5 convolutions, padding 2, stride 1 or 2 ----------------------------
@@ -223,6 +224,36 @@ size_t vg_gemm_nt_f16x3_workspace_bytes(int M, int N, int K);
 int vg_gemm_nt_f16x3(const float* A, const float* B, const float* bias, float* C, int M, int N, int K,
                      long a_row_stride, long a_k_stride, long b_row_stride, long b_k_stride,
                      const float* a_amax, const float* b_amax, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- general forward convolution, fp16x3 (csrc/conv_general.hip) ---------------------------------------------------
+ * y[b][co][oh][ow] = act(sum_{ci,kh,kw} x[b][ci][oh*stride_h + kh - pad_h][ow*stride_w + kw - pad_w] * w[co][ci][kh][kw]
+ *                        + bias[co]),   OH = (H + 2 pad_h - KH) / stride_h + 1, OW alike; act = ReLU when relu != 0.
+ * The convolutions of the FID Inception network (/root/reference/scoring/inception.py:16-310: BasicConv2d with its
+ * eval-mode BatchNorm folded into w and bias; replaces torch.nn.functional.conv2d + batch_norm + relu): KH, KW in 1..15,
+ * strides 1 or 2, paddings 0..15, H, W <= 8192, any channel counts.  Inference only; no im2col buffer exists.
+ * Arithmetic: planes = 2 | VG_PLANES_F16 above -- x_amax[0] >= max |x| in DEVICE memory, the filter's bound goes into
+ * the pack.  A bound that is too small gives inf / NaN, never a silently wrong number.
+ *   packed: vg_conv_general_packed_bytes(Cout, Cin, KH, KW) bytes, 16-byte aligned, written by vg_conv_general_pack
+ *     once per weight version from w[Cout][Cin][KH][KW] and w_amax[0] >= max |w| (DEVICE).  Layout, in 16-byte units,
+ *     with K = Cin KH KW, nsteps = ceil(K / 32), CoutP = Cout rounded up to 128:
+ *       [nsteps][2 planes hi, lo][4 k-blocks][CoutP] x 8 fp16: reduction index k = (kh KW + kw) Cin + ci, scaled, split,
+ *           zero beyond K and Cout                                              nsteps * 8 * CoutP units
+ *       [nsteps * 32] x (int32 ci, int32 kh << 16 | kw): what k addresses        nsteps * 16 units
+ *       trailer: the inverse of the filter's power-of-two scale (one float)      1 unit
+ *   y, y_image_stride: image b of the output starts at y + b * y_image_stride (floats, >= Cout OH OW) and is
+ *     [Cout][OH][OW] contiguous: y may point at a channel slice of a larger NCHW tensor (the concatenated output of an
+ *     Inception block), the other channels are not touched.
+ *   y_amax (may be NULL): max |y| is added to y_amax[0] (atomic maximum on the bit pattern, DEVICE memory, zeroed by the
+ *     caller): the next layer's x_amax; several launches may add into one slot.
+ *   bias may be NULL.  The reduction is never split over workgroups: no workspace, results reproducible bit for bit.
+ * Sizes whose 32-bit indices (an element of one input or output image, an output pixel of the batch) would overflow
+ * are rejected with VG_ERR_BAD_ARG. */
+size_t vg_conv_general_packed_bytes(int Cout, int Cin, int KH, int KW);
+int vg_conv_general_pack(const float* w, void* packed, int Cout, int Cin, int KH, int KW, const float* w_amax,
+                         void* stream);
+int vg_conv_general_fwd(const float* x, const void* packed, const float* bias, float* y, int B, int Cin, int H, int W,
+                        int Cout, int KH, int KW, int stride_h, int stride_w, int pad_h, int pad_w, long y_image_stride,
+                        int relu, const float* x_amax, float* y_amax, void* stream);
 
 /* Bounds for the fp16 planes: amax[0] = max(amax[0], max |x|) over n floats -- an atomic maximum on the bit pattern
  * (order-independent; a NaN in x ends up in the bound); the caller zeroes amax[0] first (or keeps accumulating a bound

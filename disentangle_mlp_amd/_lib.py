@@ -14,7 +14,7 @@ import torch  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvaegan_hip.so")
-ABI_VERSION = 6      # VG_ABI_VERSION of include/vaegan_hip.h this binding was written against
+ABI_VERSION = 7      # VG_ABI_VERSION of include/vaegan_hip.h this binding was written against
 
 _P, _I, _F, _Z = c_void_p, c_int, c_float, c_size_t
 
@@ -77,6 +77,8 @@ SIGNATURES = {
     "vg_adam_step": (_I, [_P, _I] + [ctypes.c_double] * 6 + [_P]),
     "vg_adam_prepare": (_I, [ctypes.c_double, _P, _I, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P]),
     "vg_adam_step_dev": (_I, [_P, _I] + [ctypes.c_double] * 3 + [_P, _P]),
+    "vg_adam_step_checked": (_I, [_P, _I] + [ctypes.c_double] * 6 + [_P, _P]),
+    "vg_adam_step_dev_checked": (_I, [_P, _I] + [ctypes.c_double] * 3 + [_P, _P, _P]),
     "vg_bce_loss_dev": (_I, [_P, _P, _P, _P, _I, _F, _F, _P]),
     "vg_dot_sigmoid_bce_workspace_bytes": (_Z, [_I]),
     "vg_dot_sigmoid_bce_fwd": (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _I, _I, _F, _P, _Z, _P]),

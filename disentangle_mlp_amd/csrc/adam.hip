@@ -9,6 +9,13 @@
 // One launch updates up to VG_ADAM_MAX_TENSORS tensors: their pointers travel in the kernel
 // arguments, a workgroup owns 8192 consecutive elements of one tensor (16-byte loads / stores when
 // the four pointers allow it).  Bias corrections are computed on the host in double precision.
+//
+// Non-finite guard (vg_adam_step_checked / vg_adam_step_dev_checked): the step is the one pass that reads every gradient
+// and writes every parameter, so it also notices an inf / NaN among them -- |x| as bits >= 0x7f800000 -- and ORs
+// VG_NONFINITE_GRAD / VG_NONFINITE_PARAM into the tensor's caller-owned flag word: one wavefront / LDS reduction per
+// workgroup, one atomicOr per workgroup that saw something, none in a clean step.  It DETECTS, it does not skip the
+// update: a skip would need a grid-wide answer before the first store.  When a bit is up the weights are poisoned;
+// recovery is the last good checkpoint.  The arithmetic that writes p, m, v and amax is the unchecked step's.
 #include "common.hpp"
 #include "vaegan_hip.h"
 
@@ -23,6 +30,7 @@ struct AdamPack {
   float* v[AMAX];
   unsigned long long n[AMAX];
   unsigned* amax[AMAX];               // per tensor, may be NULL: max |p| after the update is added here (atomic max)
+  unsigned* flag[AMAX];               // per tensor, may be NULL: VG_NONFINITE_* bits are ORed in here (never cleared)
   unsigned first_block[AMAX + 1];     // prefix sums of ceil(n / ACHUNK)
   int count;
 };
@@ -51,6 +59,24 @@ __global__ void adam_prepare_kernel(double step_host, double* __restrict__ step_
   scalars[1] = (float)sqrt(bc2);        // bias_correction2_sqrt
 }
 
+constexpr unsigned NONFINITE_BITS = 0x7f800000u;      // abs_bits(x) >= this: x is inf or NaN
+
+// ORs `bits` (this thread's VG_NONFINITE_* findings) over the workgroup into *out: no memory traffic unless a bit is set.
+// Every thread of the ANT-thread workgroup must call it.
+__device__ __forceinline__ void block_flag_or(unsigned bits, unsigned* out) {
+  __shared__ unsigned flag_red[ANT / 64];
+  const unsigned w = (__ballot(bits & VG_NONFINITE_GRAD) ? (unsigned)VG_NONFINITE_GRAD : 0u) |
+                     (__ballot(bits & VG_NONFINITE_PARAM) ? (unsigned)VG_NONFINITE_PARAM : 0u);
+  if ((threadIdx.x & 63) == 0) flag_red[threadIdx.x >> 6] = w;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned all = 0;
+#pragma unroll
+    for (int i = 0; i < ANT / 64; ++i) all |= flag_red[i];
+    if (all) atomicOr(out, all);
+  }
+}
+
 template <bool DEV>
 __global__ __launch_bounds__(ANT) void adam_multi_kernel(AdamPack A, float omb1, float b2, float omb2, float step_size,
                                                         float bc2s, float eps, const float* __restrict__ scalars) {
@@ -71,6 +97,7 @@ __global__ __launch_bounds__(ANT) void adam_multi_kernel(AdamPack A, float omb1,
   // bound of max |p| for the fp16-plane GEMMs that read this weight next (VgAdamTensor::amax): the step that changes the
   // weight is the one pass that sees every new value anyway -- no separate 134 MB read per weight and iteration
   unsigned am = 0;
+  unsigned gm = 0;      // max |g| as bits, of the gradients read: the non-finite guard's half of the same bookkeeping
   if (vec) {
     const unsigned long long end4 = base + ((end - base) & ~3ULL);
     for (unsigned long long i = base + 4ULL * threadIdx.x; i < end4; i += 4ULL * ANT) {
@@ -83,29 +110,38 @@ __global__ __launch_bounds__(ANT) void adam_multi_kernel(AdamPack A, float omb1,
         adam_one(pj, gv[j], mj, vj, omb1, b2, omb2, step_size, bc2s, eps);
         pv[j] = pj; mv[j] = mj; vv[j] = vj;
         am = max(am, abs_bits(pj));
+        gm = max(gm, abs_bits(gv[j]));
       }
       *reinterpret_cast<f32x4*>(p + i) = pv;
       *reinterpret_cast<f32x4*>(m + i) = mv;
       *reinterpret_cast<f32x4*>(v + i) = vv;
     }
     for (unsigned long long i = end4 + threadIdx.x; i < end; i += ANT) {
-      adam_one(p[i], g[i], m[i], v[i], omb1, b2, omb2, step_size, bc2s, eps);
+      const float gi = g[i];
+      adam_one(p[i], gi, m[i], v[i], omb1, b2, omb2, step_size, bc2s, eps);
       am = max(am, abs_bits(p[i]));
+      gm = max(gm, abs_bits(gi));
     }
   } else {
     for (unsigned long long i = base + threadIdx.x; i < end; i += ANT) {
-      adam_one(p[i], g[i], m[i], v[i], omb1, b2, omb2, step_size, bc2s, eps);
+      const float gi = g[i];
+      adam_one(p[i], gi, m[i], v[i], omb1, b2, omb2, step_size, bc2s, eps);
       am = max(am, abs_bits(p[i]));
+      gm = max(gm, abs_bits(gi));
     }
   }
   if (A.amax[t]) block_amax_atomic<ANT>(am, A.amax[t]);      // (t is uniform over the workgroup)
+  if (A.flag[t])
+    block_flag_or((gm >= NONFINITE_BITS ? (unsigned)VG_NONFINITE_GRAD : 0u) |
+                      (am >= NONFINITE_BITS ? (unsigned)VG_NONFINITE_PARAM : 0u),
+                  A.flag[t]);
 }
 
 }  // namespace
 
 namespace {
-int adam_launch(const VgAdamTensor* tensors, int count, double beta1, double beta2, double eps, float step_size, float bc2s,
-                const float* scalars, hipStream_t st) {
+int adam_launch(const VgAdamTensor* tensors, unsigned* const* flags, int count, double beta1, double beta2, double eps,
+                float step_size, float bc2s, const float* scalars, hipStream_t st) {
   const float omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);
   int i = 0;
   while (i < count) {
@@ -113,14 +149,16 @@ int adam_launch(const VgAdamTensor* tensors, int count, double beta1, double bet
     A.count = 0;
     unsigned blocks = 0;
     while (i < count && A.count < AMAX) {
+      unsigned* const flag = flags ? flags[i] : nullptr;
       const VgAdamTensor& T = tensors[i++];
-      if (T.n == 0) continue;
+      if (T.n == 0) continue;      // (its flag word is left untouched)
       if (!T.p || !T.g || !T.m || !T.v) return VG_ERR_BAD_ARG;
       const unsigned long long nb = (T.n + ACHUNK - 1) / ACHUNK;
       if (nb > 0x3fffffffULL - blocks) return VG_ERR_BAD_ARG;
       const int k = A.count++;
       A.p[k] = T.p; A.g[k] = T.g; A.m[k] = T.m; A.v[k] = T.v; A.n[k] = T.n;
       A.amax[k] = reinterpret_cast<unsigned*>(T.amax);
+      A.flag[k] = flag;
       A.first_block[k] = blocks;
       blocks += (unsigned)nb;
     }
@@ -138,13 +176,20 @@ int adam_launch(const VgAdamTensor* tensors, int count, double beta1, double bet
 }
 }  // namespace
 
-extern "C" int vg_adam_step(const VgAdamTensor* tensors, int count, double lr, double beta1, double beta2, double eps,
-                            double bias_correction1, double bias_correction2_sqrt, void* stream) {
+extern "C" int vg_adam_step_checked(const VgAdamTensor* tensors, int count, double lr, double beta1, double beta2,
+                                    double eps, double bias_correction1, double bias_correction2_sqrt,
+                                    unsigned* const* nonfinite, void* stream) {
   if (count < 0 || (count > 0 && !tensors) || !(bias_correction1 > 0.0) || !(bias_correction2_sqrt > 0.0))
     return VG_ERR_BAD_ARG;
   // scalars are formed in double and rounded once, as torch does with its Python-side hyper-parameters
-  return adam_launch(tensors, count, beta1, beta2, eps, (float)(lr / bias_correction1), (float)bias_correction2_sqrt,
-                     nullptr, (hipStream_t)stream);
+  return adam_launch(tensors, nonfinite, count, beta1, beta2, eps, (float)(lr / bias_correction1),
+                     (float)bias_correction2_sqrt, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int vg_adam_step(const VgAdamTensor* tensors, int count, double lr, double beta1, double beta2, double eps,
+                            double bias_correction1, double bias_correction2_sqrt, void* stream) {
+  return vg_adam_step_checked(tensors, count, lr, beta1, beta2, eps, bias_correction1, bias_correction2_sqrt, nullptr,
+                              stream);
 }
 
 extern "C" int vg_adam_prepare(double step, double* step_dev, int advance_device_counter, double lr, double beta1,
@@ -158,8 +203,13 @@ extern "C" int vg_adam_prepare(double step, double* step_dev, int advance_device
   return 0;
 }
 
+extern "C" int vg_adam_step_dev_checked(const VgAdamTensor* tensors, int count, double beta1, double beta2, double eps,
+                                        const float* scalars, unsigned* const* nonfinite, void* stream) {
+  if (count < 0 || (count > 0 && !tensors) || !scalars) return VG_ERR_BAD_ARG;
+  return adam_launch(tensors, nonfinite, count, beta1, beta2, eps, 0.f, 0.f, scalars, (hipStream_t)stream);
+}
+
 extern "C" int vg_adam_step_dev(const VgAdamTensor* tensors, int count, double beta1, double beta2, double eps,
                                 const float* scalars, void* stream) {
-  if (count < 0 || (count > 0 && !tensors) || !scalars) return VG_ERR_BAD_ARG;
-  return adam_launch(tensors, count, beta1, beta2, eps, 0.f, 0.f, scalars, (hipStream_t)stream);
+  return vg_adam_step_dev_checked(tensors, count, beta1, beta2, eps, scalars, nullptr, stream);
 }

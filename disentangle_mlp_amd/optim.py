@@ -7,6 +7,11 @@ reference's optimizer checkpoints load into it and its own load into ``torch.opt
 ``step()`` is replaced: one multi-tensor launch per 24 parameters instead of torch's fused
 ``multi_tensor_apply``.  Configurations the kernel does not implement (weight decay, amsgrad,
 maximize, a closure, non-fp32 / non-contiguous / CPU tensors) take the inherited ``step()``.
+
+``HipAdam(nonfinite_guard=True)``: the step also reports, per parameter, an inf / NaN among the gradients it read
+(`NONFINITE_GRAD`) and the parameters it wrote (`NONFINITE_PARAM`) -- ``vg_adam_step_checked`` -- in device words the
+host reads when it chooses to (`nonfinite`, `nonfinite_words`, `clear_nonfinite`).  It detects, it does not skip the
+update: when a word is up the weights are poisoned and the last good checkpoint is the way back.
 """
 import ctypes
 import math
@@ -16,6 +21,26 @@ from torch import optim
 
 from . import _lib, ops
 from ._lib import check
+
+
+NONFINITE_GRAD, NONFINITE_PARAM = 1, 2      # VG_NONFINITE_* of include/vaegan_hip.h
+
+
+@torch.no_grad()
+def isfinite_bits(params, device=None):
+    """The guard's bits formed by torch: int32, one per parameter -- `NONFINITE_GRAD` when ``p.grad`` holds an inf / NaN
+    now, `NONFINITE_PARAM` when ``p`` does.  For steps the kernel does not ride on (torch.optim.Adam, CPU)."""
+    params = list(params)
+    device = device if device is not None else (params[0].device if params else "cpu")
+    if not params:
+        return torch.zeros(0, dtype=torch.int32, device=device)
+    bits = []
+    for p in params:
+        b = (~torch.isfinite(p.detach()).all()).to(torch.int32) * NONFINITE_PARAM
+        if p.grad is not None:
+            b = b + (~torch.isfinite(p.grad).all()).to(torch.int32) * NONFINITE_GRAD
+        bits.append(b.to(device))
+    return torch.stack(bits)
 
 
 class _AdamTensor(ctypes.Structure):
@@ -31,7 +56,9 @@ class HipAdam(optim.Adam):
     and a replayed one give the same bits.  The ``state_dict`` stays torch.optim.Adam's (``step`` as a CPU tensor): the
     host mirrors the device counter (`prepare_capture` / `replayed`)."""
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, capturable=False):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, capturable=False,
+                 nonfinite_guard=False):
+        self._words = None
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad,
                          foreach=False, fused=False, capturable=False)
         self.device_scalars = bool(capturable)
@@ -45,6 +72,54 @@ class HipAdam(optim.Adam):
         self._bound_of = {}       # parameter -> index into self._bounds
         self._bounds = None
         self.register_state_dict_pre_hook(lambda opt: opt._flush_replays())
+        # non-finite guard: one persistent int32 word per parameter, in param_groups order, allocated here -- before any
+        # capture -- and never replaced (not by load_state_dict either): like `_bounds`, a replayed step writes where the
+        # host later reads
+        self.nonfinite_guard = bool(nonfinite_guard)
+        self._word_of = {}        # parameter -> index into self._words
+        self._torch_stepped = False      # torch's step() ran since the words were cleared: it cannot flag (see `nonfinite`)
+        if self.nonfinite_guard:
+            ps = [p for g in self.param_groups for p in g["params"]]
+            self._word_of = {p: i for i, p in enumerate(ps)}
+            self._words = torch.zeros(len(ps), dtype=torch.int32, device=ps[0].device)
+
+    def add_param_group(self, param_group):
+        if self._words is not None:
+            raise RuntimeError("HipAdam(nonfinite_guard=True): the flag words are laid out at construction; "
+                               "pass every parameter group to the constructor")
+        return super().add_param_group(param_group)
+
+    # ---- non-finite guard ----------------------------------------------------------------------------------
+    def _need_guard(self):
+        if not self.nonfinite_guard:
+            raise RuntimeError("HipAdam: construct with nonfinite_guard=True to use the non-finite guard")
+
+    def nonfinite_words(self):
+        """The device tensor of flag words itself (int32, one per parameter in ``param_groups`` order; bits
+        `NONFINITE_GRAD` | `NONFINITE_PARAM`): a trainer reads several optimizers' words in one copy."""
+        self._need_guard()
+        return self._words
+
+    @torch.no_grad()
+    def nonfinite_bits(self):
+        """`nonfinite_words()`, completed -- when torch's own ``step()`` ran since the words were cleared (weight decay,
+        amsgrad, a closure, CPU tensors: it cannot flag) -- with the same bits formed by ``torch.isfinite`` over every
+        ``p.grad`` and ``p`` as they are now, so that an unguarded path never reads as clean.  No host synchronisation."""
+        self._need_guard()
+        if not self._torch_stepped:
+            return self._words
+        return self._words | isfinite_bits([p for g in self.param_groups for p in g["params"]], self._words.device)
+
+    def nonfinite(self):
+        """One device -> host read: ``{parameter: bits}`` of the words that are up; empty when the run is clean."""
+        ps = [p for g in self.param_groups for p in g["params"]]
+        return {p: b for p, b in zip(ps, self.nonfinite_bits().tolist()) if b}
+
+    def clear_nonfinite(self):
+        """Zero the words (a device memset: no synchronisation).  The kernel only ever ORs."""
+        self._need_guard()
+        self._words.zero_()
+        self._torch_stepped = False
 
     def _native_ok(self, group):
         if group["weight_decay"] != 0 or group["amsgrad"] or group.get("maximize", False) \
@@ -136,6 +211,7 @@ class HipAdam(optim.Adam):
             if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("HipAdam: this configuration takes torch's step, which cannot be captured here")
             self._flush_replays()
+            self._torch_stepped = True
             return super().step(closure)
         lib = _lib.load()
         stream = torch.cuda.current_stream().cuda_stream
@@ -147,6 +223,7 @@ class HipAdam(optim.Adam):
         bounds = self._weight_bounds()
         if bounds is not None:
             bounds.zero_()
+        words = self._words.data_ptr() if self.nonfinite_guard else None
         for gi, group in enumerate(self.param_groups):
             beta1, beta2 = group["betas"]
             by_step = {}
@@ -169,6 +246,8 @@ class HipAdam(optim.Adam):
                 raise RuntimeError("HipAdam: a captured step needs every parameter of a group at the same step count")
             for step, items in by_step.items():
                 arr = (_AdamTensor * len(items))()
+                flags = None if words is None else (ctypes.c_void_p * len(items))(
+                    *[words + 4 * self._word_of[it[0]] for it in items])
                 for i, (p, g, m, v) in enumerate(items):
                     bi = self._bound_of.get(p) if bounds is not None else None
                     arr[i] = _AdamTensor(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(),
@@ -178,15 +257,23 @@ class HipAdam(optim.Adam):
                     # an eager step also stores its count in the device counter: replays may follow it
                     check(lib.vg_adam_prepare(float(step), step_dev.data_ptr(), 1 if capturing else 0, float(group["lr"]),
                                               float(beta1), float(beta2), scalars.data_ptr(), stream), "vg_adam_prepare")
-                    check(lib.vg_adam_step_dev(arr, len(items), float(beta1), float(beta2), float(group["eps"]),
-                                               scalars.data_ptr(), stream), "vg_adam_step_dev")
+                    if flags is not None:
+                        check(lib.vg_adam_step_dev_checked(arr, len(items), float(beta1), float(beta2), float(group["eps"]),
+                                                           scalars.data_ptr(), flags, stream), "vg_adam_step_dev_checked")
+                    else:
+                        check(lib.vg_adam_step_dev(arr, len(items), float(beta1), float(beta2), float(group["eps"]),
+                                                   scalars.data_ptr(), stream), "vg_adam_step_dev")
                     if capturing:
                         self._captured.append([it[0] for it in items])
                     continue
                 bc1 = 1.0 - beta1 ** step
                 bc2_sqrt = math.sqrt(1.0 - beta2 ** step)
-                check(lib.vg_adam_step(arr, len(items), float(group["lr"]), float(beta1), float(beta2), float(group["eps"]),
-                                       bc1, bc2_sqrt, stream), "vg_adam_step")
+                if flags is not None:
+                    check(lib.vg_adam_step_checked(arr, len(items), float(group["lr"]), float(beta1), float(beta2),
+                                                   float(group["eps"]), bc1, bc2_sqrt, flags, stream), "vg_adam_step_checked")
+                else:
+                    check(lib.vg_adam_step(arr, len(items), float(group["lr"]), float(beta1), float(beta2),
+                                           float(group["eps"]), bc1, bc2_sqrt, stream), "vg_adam_step")
         if bounds is not None:
             for p, bi in self._bound_of.items():
                 slot = bounds[bi:bi + 1]

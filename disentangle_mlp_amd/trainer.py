@@ -14,6 +14,11 @@ skipped:
     frozen (no weight gradients) and ``sim_real`` is computed without a graph.
 No host synchronisation happens inside ``step``; loss scalars stay on the device.
 
+Non-finite guard: the Adam steps flag an inf / NaN among the gradients they read and the parameters
+they wrote (optim.HipAdam(nonfinite_guard=True)); ``check_finite()`` reads the flags -- one device ->
+host copy, on demand and at the end of every ``train_epoch`` -- and raises `NonFiniteError`, so a
+poisoned epoch is never checkpointed.
+
 Data parallelism: every rank holds a replica and a shard of the batch; BatchNorm
 statistics are replica-local (as under the reference's nn.DataParallel); before each
 optimizer step the gradients, laid out in one flat fp32 buffer per network, are
@@ -31,7 +36,7 @@ from torch import optim
 
 from . import functional as F
 from . import ops
-from .optim import HipAdam
+from .optim import HipAdam, NONFINITE_GRAD, NONFINITE_PARAM, isfinite_bits
 from .model import VAE, Discriminator_celeba, Generator_celeba, weights_init, shadowed_bias_params
 
 
@@ -248,13 +253,14 @@ def _backward(losses):
     torch.autograd.backward(losses, grad_tensors=[one] * len(losses))
 
 
-def _make_adam(params, lr, fused, capturable=False):
+def _make_adam(params, lr, fused, capturable=False, nonfinite_guard=False):
     """Adam with the reference's defaults (new_betavaegan.py:49-50).  On the GPU the step runs on the
     hand-written kernel (optim.HipAdam, a torch.optim.Adam subclass: identical state_dict); ``capturable``:
-    its scalars are formed on the device so that a whole iteration can be captured in a HIP graph.  CPU
-    construction uses torch's own implementation."""
+    its scalars are formed on the device so that a whole iteration can be captured in a HIP graph;
+    ``nonfinite_guard``: the step flags non-finite gradients / parameters.  CPU construction uses torch's own
+    implementation."""
     if fused:
-        return HipAdam(params, lr=lr, capturable=capturable)
+        return HipAdam(params, lr=lr, capturable=capturable, nonfinite_guard=nonfinite_guard)
     return optim.Adam(params, lr=lr, capturable=capturable)
 
 
@@ -307,6 +313,28 @@ def _loader_global_batch(loader, local_batch, world):
 
 GRAPH_DEFAULT = __import__("os").environ.get("VG_GRAPH", "1") != "0"     # 0: trainers never capture (every step eager)
 GRAPH_WARM_STEPS = 2      # eager iterations of a shape before it is captured (workspaces, packs, GEMM plans exist then)
+
+
+NONFINITE_GUARD_DEFAULT = __import__("os").environ.get("VG_NONFINITE_GUARD", "1") != "0"    # 0: trainers do not guard unless asked
+
+
+class NonFiniteError(RuntimeError):
+    """`check_finite` found an inf / NaN among the gradients the optimizer steps read or the parameters they wrote.
+
+    ``found``: list of ``(qualified parameter name such as "netD.convs.0.weight", "grad" | "param" | "grad+param")`` of
+    this rank (empty when only another rank of a data-parallel run is poisoned); ``first_iteration`` /
+    ``last_iteration``: the trainer's ``iteration`` when its flags were last known clean, and now -- the poison arrived
+    in an iteration of that range.  The weights are poisoned (the step detects, it does not skip): reload the last
+    checkpoint."""
+
+    def __init__(self, found, first_iteration, last_iteration):
+        self.found, self.first_iteration, self.last_iteration = list(found), first_iteration, last_iteration
+        names = ", ".join(f"{n} ({k})" for n, k in self.found[:4]) + (f", ... {len(self.found)} in all" if len(self.found) > 4 else "")
+        super().__init__(
+            f"non-finite values between iterations {first_iteration} and {last_iteration}: "
+            + (names if self.found else "on another rank of this data-parallel run")
+            + ".  Likeliest causes: a non-finite input batch, or a stale fp16x3 magnitude bound.  The weights are "
+              "poisoned; reload the last good checkpoint (load / load_in_place).")
 
 
 class _CapturedIteration:
@@ -441,11 +469,75 @@ class _GraphedSteps:
         from .model import _has_hooks
         return _has_hooks([m for net in self._nets() for m in net.modules()])
 
+    # ---- non-finite guard ----------------------------------------------------------------------------------------
+    nonfinite_guard = False
+    _finite_at = 0          # `iteration` when the flags were last known clean
+
+    @staticmethod
+    def _resolve_guard(nonfinite_guard, uses_hip_adam):
+        """``None``: on whenever the optimizer steps run on HipAdam (VG_NONFINITE_GUARD=0 turns that default off)."""
+        if nonfinite_guard is None:
+            return bool(uses_hip_adam) and NONFINITE_GUARD_DEFAULT
+        return bool(nonfinite_guard)
+
+    def _guarded_optimizers(self):
+        """[(attribute name of the network, network, its optimizer)]: every trainer lists its own."""
+        raise NotImplementedError
+
+    @torch.no_grad()
+    def _read_finite(self, extra=None):
+        """The guard's check and, in the SAME device -> host copy, the values of the float64 device tensor ``extra``
+        (an epoch's loss sums: `train_epoch` still reads the device once).  Raises `NonFiniteError`, else returns the
+        values of ``extra`` as a list."""
+        names, bits = [], []
+        for attr, net, opt in self._guarded_optimizers():
+            named = {p: f"{attr}.{k}" for k, p in net.named_parameters()}
+            ps = [p for g in opt.param_groups for p in g["params"]]
+            names += [named.get(p, f"{attr}.<parameter {i}>") for i, p in enumerate(ps)]
+            if isinstance(opt, HipAdam) and opt.nonfinite_guard:
+                bits.append(opt.nonfinite_bits())
+            else:
+                bits.append(isfinite_bits(ps, self.device))
+        bits = torch.cat(bits) & (NONFINITE_GRAD | NONFINITE_PARAM)      # (the words are the optimizer's: other bits are not ours)
+        anything = (bits != 0).any().to(torch.int32).reshape(1)
+        if _dist_world() > 1:
+            dist.all_reduce(anything, op=dist.ReduceOp.MAX)
+        n_extra = 0 if extra is None else extra.numel()
+        parts = [bits.to(torch.float64), anything.to(torch.float64)]      # (small integers: exact in float64)
+        if n_extra:
+            parts.append(extra.reshape(-1).to(torch.float64))
+        host = torch.cat(parts).tolist()                                  # the one device -> host read
+        bits, anything, extra = [int(b) for b in host[:len(names)]], host[len(names)], host[len(names) + 1:]
+        if not anything:
+            self._finite_at = self.iteration
+            return extra
+        kinds = {NONFINITE_GRAD: "grad", NONFINITE_PARAM: "param", NONFINITE_GRAD | NONFINITE_PARAM: "grad+param"}
+        raise NonFiniteError([(n, kinds[b]) for n, b in zip(names, bits) if b], self._finite_at, self.iteration)
+
+    def check_finite(self):
+        """Raise `NonFiniteError` if an optimizer step since the flags were last cleared read a non-finite gradient or
+        wrote a non-finite parameter; return None when the run is clean.  One device -> host copy for all optimizers'
+        flag words -- `step` itself never synchronises; this is the check on demand after any `step`, and `train_epoch`
+        makes it once per epoch, in the copy that reads the epoch's sums.  Optimizers without the kernel's guard
+        (torch.optim.Adam: CPU, ``fused_adam=False``; ``nonfinite_guard=False``) are checked with ``torch.isfinite`` over
+        their parameters and gradients as they are now.  Data parallel: the "anything set" bit is all-reduced (MAX)
+        first, so every rank raises at the same call."""
+        self._read_finite()
+        return None
+
+    def clear_nonfinite(self):
+        """Zero the guard's flag words (device memsets, no synchronisation): after the state was restored."""
+        for _, _, opt in self._guarded_optimizers():
+            if isinstance(opt, HipAdam) and opt.nonfinite_guard:
+                opt.clear_nonfinite()
+        self._finite_at = self.iteration
+
     def _host_state_key(self):
         """Host-side switches a capture freezes besides the shapes: part of every capture key, so that flipping one
         captures anew instead of replaying the old launches."""
         from . import model as M
         return (M.FUSE_CONV_BN, M.FUSE_HEAD_BCE, F.DEFER_WGRAD, ops.THIN_SPLIT, ops.USE_PACKED_FILTERS,
+                self.nonfinite_guard,        # (checked or unchecked Adam launches)
                 tuple(net.training for net in self._nets()),
                 tuple(p.requires_grad for net in self._nets() for p in net.parameters()))
 
@@ -493,11 +585,15 @@ class BetaVAEGANTrainer(_GraphedSteps):
     ``graph`` (default: on for a single-process CUDA trainer, VG_GRAPH=0 turns it off): from the third iteration of a
     batch shape on, `step` replays a HIP graph of the whole iteration (`_CapturedIteration`) instead of launching its
     ~390 kernels one by one.  Iterations that need the host in the loop stay eager: a ``grad_hook``, data parallelism
-    (the gradient exchange runs from autograd hooks), launch timing (bench.py's instrumented step)."""
+    (the gradient exchange runs from autograd hooks), launch timing (bench.py's instrumented step).
+
+    ``nonfinite_guard`` (default: on whenever the optimizers are HipAdam, VG_NONFINITE_GUARD=0 turns that off): the Adam
+    steps flag non-finite gradients / parameters; `check_finite` -- called by `train_epoch` at the end of every epoch,
+    and by whoever wants to know after any `step` -- raises `NonFiniteError`."""
 
     def __init__(self, device="cuda", seed=999, beta=25.0, lr=1e-3, opt: Optional[ModelOpt] = None,
                  data_parallel: Optional[bool] = None, fused_adam: bool = True, capturable: Optional[bool] = None,
-                 graph: Optional[bool] = None):
+                 graph: Optional[bool] = None, nonfinite_guard: Optional[bool] = None):
         self.opt = opt or ModelOpt()
         self.device = torch.device(device)
         _use_tuned_gemms(self.device)
@@ -515,8 +611,9 @@ class BetaVAEGANTrainer(_GraphedSteps):
         self.netEG = net_eg.to(self.device)
         self.netD = net_d.to(self.device)
         fused = fused_adam and self.device.type == "cuda"
-        self.optimizerEG = _make_adam(self.netEG.parameters(), lr, fused, capturable)   # :49 (hard-coded 1e-3 there)
-        self.optimizerD = _make_adam(self.netD.parameters(), lr, fused, capturable)     # :50
+        self.nonfinite_guard = self._resolve_guard(nonfinite_guard, fused)
+        self.optimizerEG = _make_adam(self.netEG.parameters(), lr, fused, capturable, self.nonfinite_guard)   # :49 (hard-coded 1e-3 there)
+        self.optimizerD = _make_adam(self.netD.parameters(), lr, fused, capturable, self.nonfinite_guard)     # :50
         self.flat_eg = FlatGrads(self.netEG.parameters(), silent=shadowed_bias_params(self.netEG)) if self.dp else None
         self.flat_d = FlatGrads(self.netD.parameters(), silent=shadowed_bias_params(self.netD)) if self.dp else None
         self.netEG.train()
@@ -527,6 +624,9 @@ class BetaVAEGANTrainer(_GraphedSteps):
         self.rank = _dist_rank()
         self.latent_generator = _latent_generator(self.device, seed, self.rank)
         self.label_rng = _shared_label_rng(seed)          # used by train_epoch when world > 1: one draw per GLOBAL batch
+
+    def _guarded_optimizers(self):
+        return [("netEG", self.netEG, self.optimizerEG), ("netD", self.netD, self.optimizerD)]
 
     def draw_latents(self, batch):
         """One N(0,1) draw of shape (batch, n_hidden) from this replica's own stream."""
@@ -700,7 +800,9 @@ class BetaVAEGANTrainer(_GraphedSteps):
                 break
         if self.world > 1:
             dist.all_reduce(acc, op=dist.ReduceOp.SUM)
-        mse_sum, dx_sum = acc.tolist()                                    # the epoch's one device -> host read
+        # the epoch's one device -> host read; guarded, it carries the flag words too and raises on a poisoned epoch
+        # (`fit` then never checkpoints it)
+        mse_sum, dx_sum = self._read_finite(acc) if self.nonfinite_guard else acc.tolist()
         n = len(loader.dataset)
         return mse_sum / n, mse_sum / n, dx_sum / n, dx_sum / n
 
@@ -798,6 +900,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
         self.netD.load_state_dict(d_sd)
         self.optimizerEG.load_state_dict(ck["encoder_decoder_optimizer"])
         self.optimizerD.load_state_dict(ck["discriminator_optimizer"])
+        self.clear_nonfinite()                               # a good checkpoint is the way back from a NonFiniteError
         return ck["epoch"]
 
     @torch.no_grad()
@@ -824,6 +927,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
         for opt in (self.optimizerEG, self.optimizerD):      # (the bounds the captured GEMMs read beside the weights)
             if isinstance(opt, HipAdam):
                 opt.refresh_weight_bounds()
+        self.clear_nonfinite()
         return ck["epoch"]
 
 
@@ -831,7 +935,8 @@ class VAETrainer(_GraphedSteps):
     """new_vae.py:33-37 construction, :39-48 loss, :53-59 step.  ``graph``: as BetaVAEGANTrainer."""
 
     def __init__(self, device="cuda", seed=999, beta=1.0, lr=3e-3, opt: Optional[ModelOpt] = None,
-                 fused_adam: bool = True, capturable: Optional[bool] = None, graph: Optional[bool] = None):
+                 fused_adam: bool = True, capturable: Optional[bool] = None, graph: Optional[bool] = None,
+                 nonfinite_guard: Optional[bool] = None):
         self.opt = opt or ModelOpt()
         self.device = torch.device(device)
         _use_tuned_gemms(self.device)
@@ -842,11 +947,16 @@ class VAETrainer(_GraphedSteps):
         self.model = m.to(self.device)
         self.world = _dist_world()
         self._graph_init(graph, self.device.type == "cuda", fused_adam, self.world > 1)
-        self.optimizer = _make_adam(self.model.parameters(), lr, fused_adam and self.device.type == "cuda",
-                                    self.graph if capturable is None else capturable)
+        fused = fused_adam and self.device.type == "cuda"
+        self.nonfinite_guard = self._resolve_guard(nonfinite_guard, fused)
+        self.optimizer = _make_adam(self.model.parameters(), lr, fused, self.graph if capturable is None else capturable,
+                                    self.nonfinite_guard)
         self.flat = FlatGrads(self.model.parameters(), silent=shadowed_bias_params(self.model)) if self.world > 1 else None
         self.latent_generator = _latent_generator(self.device, seed, _dist_rank())
         self.model.train()
+
+    def _guarded_optimizers(self):
+        return [("model", self.model, self.optimizer)]
 
     def step(self, data, eps=None):
         def eager(inp=None):
@@ -881,6 +991,7 @@ class VAETrainer(_GraphedSteps):
         if self.flat is not None:
             self.flat.finish()
         self.optimizer.step()
+        self.iteration += 1
         return dict(mse=mse.detach(), kld=kld.detach())
 
     def train_epoch(self, loader, max_iterations=None):
@@ -896,7 +1007,8 @@ class VAETrainer(_GraphedSteps):
                 break
         if self.world > 1:
             dist.all_reduce(acc, op=dist.ReduceOp.SUM)
-        return float(acc.item()) / len(loader.dataset)
+        total, = self._read_finite(acc) if self.nonfinite_guard else [acc.item()]      # (one read, flag words included)
+        return float(total) / len(loader.dataset)
 
     def checkpoint(self, epoch):
         return {"epoch": epoch, "VAE_model": self.model.state_dict(), "optimizer": self.optimizer.state_dict()}
@@ -909,7 +1021,8 @@ class GANTrainer(_GraphedSteps):
     BetaVAEGANTrainer."""
 
     def __init__(self, device="cuda", seed=999, lr=3e-3, opt: Optional[ModelOpt] = None, fused_adam: bool = True,
-                 data_parallel: Optional[bool] = None, graph: Optional[bool] = None):
+                 data_parallel: Optional[bool] = None, graph: Optional[bool] = None,
+                 nonfinite_guard: Optional[bool] = None):
         self.opt = opt or ModelOpt()
         self.device = torch.device(device)
         _use_tuned_gemms(self.device)
@@ -923,8 +1036,9 @@ class GANTrainer(_GraphedSteps):
         self.world = _dist_world()
         self.dp = (self.world > 1) if data_parallel is None else data_parallel
         self._graph_init(graph, self.device.type == "cuda", fused_adam, self.dp)
-        self.optimizerG = _make_adam(self.netG.parameters(), lr, fused, self.graph)
-        self.optimizerD = _make_adam(self.netD.parameters(), lr, fused, self.graph)
+        self.nonfinite_guard = self._resolve_guard(nonfinite_guard, fused)
+        self.optimizerG = _make_adam(self.netG.parameters(), lr, fused, self.graph, self.nonfinite_guard)
+        self.optimizerD = _make_adam(self.netD.parameters(), lr, fused, self.graph, self.nonfinite_guard)
         self.flat_g = FlatGrads(self.netG.parameters(), silent=shadowed_bias_params(self.netG)) if self.dp else None
         self.flat_d = FlatGrads(self.netD.parameters(), silent=shadowed_bias_params(self.netD)) if self.dp else None
         self.latent_generator = _latent_generator(self.device, seed, _dist_rank())
@@ -941,6 +1055,9 @@ class GANTrainer(_GraphedSteps):
     def _exchange(self, flat):
         if flat is not None and (self.world > 1 or FlatGrads.exchange_when_alone):
             flat.finish()
+
+    def _guarded_optimizers(self):
+        return [("netG", self.netG, self.optimizerG), ("netD", self.netD, self.optimizerD)]
 
     def step(self, data, noise=None, real_label=0.9, fake_label=0.1, global_batch: Optional[int] = None,
              grad_hook=None):
@@ -1002,6 +1119,7 @@ class GANTrainer(_GraphedSteps):
         if grad_hook:
             grad_hook("G", self.netG)
         self.optimizerG.step()
+        self.iteration += 1
         return dict(errD_real=err_real.detach(), errD_fake=err_fake.detach(), errG=err_g.detach(),
                     D_x_sum=p_real.detach().sum())
 
@@ -1026,7 +1144,7 @@ class GANTrainer(_GraphedSteps):
                 break
         if self.world > 1:                       # local BCE terms are already divided by the global batch
             dist.all_reduce(acc, op=dist.ReduceOp.SUM)
-        g_sum, d_sum = acc.tolist()
+        g_sum, d_sum = self._read_finite(acc) if self.nonfinite_guard else acc.tolist()     # (one read, flag words included)
         n = len(loader.dataset)
         self.last_epoch_sums = {"errG": g_sum, "errD": d_sum}
         avg_loss_g = g_sum / n

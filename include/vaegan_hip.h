@@ -44,8 +44,8 @@ extern "C" {
  * workspace contract.  vg_version() returns the value the library was built with; a binding must refuse a library
  * whose version is not the header's (the .so files are build products that travel with the working tree: a stale one
  * still exports every old symbol).  3: round 3.  4: round 4 (fp16 planes: VG_PLANES_F16, the *_amax arguments).
- * 6: vg_conv_general_* (the general forward convolution). */
-#define VG_ABI_VERSION 6
+ * 6: vg_conv_general_* (the general forward convolution).  7: vg_adam_step_checked / vg_adam_step_dev_checked. */
+#define VG_ABI_VERSION 7
 int vg_version(void);
 
 /* ---- 5x5 convolutions, padding 2, stride 1 or 2 ----------------------------
@@ -429,6 +429,23 @@ int vg_adam_prepare(double step, double* step_dev, int advance_device_counter, d
                     float* scalars, void* stream);
 int vg_adam_step_dev(const VgAdamTensor* tensors, int count, double beta1, double beta2, double eps,
                      const float* scalars, void* stream);
+/* The two steps with a non-finite guard.  `nonfinite` is NULL or a HOST array of `count` DEVICE words parallel to
+ * `tensors` (any entry may be NULL); the words belong to the caller -- the library still holds no state.  The step ORs
+ * into tensor i's word
+ *   VG_NONFINITE_GRAD   an inf / NaN among the gradient elements it READ,
+ *   VG_NONFINITE_PARAM  an inf / NaN among the parameter elements it WROTE,
+ * and only ever ORs: a word stays up until the caller zeroes it, a clean step writes nothing (one atomicOr per
+ * workgroup that saw something).  Tensors with n == 0 are skipped, their word untouched.  p, m, v and amax are
+ * bit for bit those of the unchecked step, which is this one without words: the update is DETECTED, not skipped
+ * (that would take a grid-wide answer before the first store) -- once a bit is up the weights are poisoned and the
+ * last good checkpoint is the way back. */
+#define VG_NONFINITE_GRAD 1u
+#define VG_NONFINITE_PARAM 2u
+int vg_adam_step_checked(const VgAdamTensor* tensors, int count, double lr, double beta1, double beta2, double eps,
+                         double bias_correction1, double bias_correction2_sqrt, unsigned* const* nonfinite,
+                         void* stream);
+int vg_adam_step_dev_checked(const VgAdamTensor* tensors, int count, double beta1, double beta2, double eps,
+                             const float* scalars, unsigned* const* nonfinite, void* stream);
 
 /* ---- image I/O either side of the step -----------------
  * Input pipeline of dataloader/dataset.py:37-43 (ToTensor + Normalize(mean, std) of a

@@ -15,7 +15,9 @@ constexpr int NT = 256;
 constexpr int NS_MAX = 64;   // slices per channel in the two-stage reductions
 
 __device__ __forceinline__ float act_fwd(float v, int act) {
-  if (act == VG_ACT_RELU) return v > 0.f ? v : 0.f;
+  // compare + select with the NaN on the "keep v" side: a NaN stays a NaN, as in torch (v > 0 ? v : 0 made it 0, and a
+  // channel whose batch mean is NaN left BatchNorm + ReLU as zeros); -inf and -0 still give +0, finite values their bits
+  if (act == VG_ACT_RELU) return v <= 0.f ? 0.f : v;
   if (act == VG_ACT_LRELU) return v > 0.f ? v : 0.2f * v;
   return v;
 }
@@ -51,7 +53,10 @@ __global__ __launch_bounds__(NT) void bn_partial_kernel(const float* __restrict_
                                                         const float* __restrict__ beta,
                                                         const float* __restrict__ mean,
                                                         const float* __restrict__ invstd, double* __restrict__ part,
-                                                        int B, int C, int HW, long per, int ns, int act) {
+                                                        int B, int C, int HW, long per, int ns, int act, int vec) {
+  // vec: four elements of a plane per 16-byte load -- the host's decision.  vg_channel_sum sets it only for HW % 4 == 0
+  // AND a 16-byte aligned tensor; the BatchNorm entry points pass HW % 4 == 0 alone and, like bn_apply_kernel and the
+  // one-pass backward after them, still take x / gy on a 16-byte boundary on trust
   __shared__ double red[NT / 64];
   const int c = blockIdx.x, k = blockIdx.y;
   const long total = (long)B * HW;
@@ -77,7 +82,7 @@ __global__ __launch_bounds__(NT) void bn_partial_kernel(const float* __restrict_
       s2 += (double)(g * ((xv - mu) * is));
     }
   };
-  if ((HW & 3) == 0) {
+  if (vec) {
     for (long v = v0 + 4L * threadIdx.x; v < v1; v += 4L * NT) {
       const long b = hw_shift >= 0 ? (v >> hw_shift) : v / HW, hw = v - b * HW;
       const size_t off = ((size_t)b * C + c) * HW + hw;
@@ -739,7 +744,8 @@ extern "C" int vg_bn_stats(const float* x, const float* gamma, const float* beta
   double* part = (double*)workspace;
   const Slicing s = make_slicing(B, C, HW);
   hipLaunchKernelGGL(bn_partial_kernel<0>, dim3(C, s.ns), dim3(NT), 0, st, x, (const float*)nullptr, (const float*)nullptr,
-                     (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, part, B, C, HW, s.per, s.ns, 0);
+                     (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, part, B, C, HW, s.per, s.ns, 0,
+                     (HW & 3) == 0);
   VG_CHECK_LAUNCH();
   hipLaunchKernelGGL(bn_finalize_kernel<double>, dim3(cdiv(C, 32)), dim3(NT), 0, st, (const double*)part, s.ns,
                      (long)s.ns, 1L, C, (double)B * HW, gamma, beta, running_mean, running_var, save_mean, save_invstd,
@@ -752,7 +758,7 @@ extern "C" int vg_affine_act(const float* x, const float* scale, const float* sh
                              int act, float* y_amax, void* stream) {
   if (!x || !scale || !shift || !y || B <= 0 || C <= 0 || HW <= 0) return VG_ERR_BAD_ARG;
   if (act < VG_ACT_NONE || act > VG_ACT_LRELU) return VG_ERR_BAD_ARG;
-  if (HW & 3) {
+  if ((HW & 3) || (((uintptr_t)x | (uintptr_t)y) & 15)) {      // ... or a tensor that is not on a 16-byte boundary
     const size_t n = (size_t)B * C * HW;
     if (cdiv((long)n, (long)NT) > 0x7fffffffL) return VG_ERR_BAD_ARG;
     hipLaunchKernelGGL(affine_act_scalar_kernel, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0, (hipStream_t)stream, x,
@@ -794,7 +800,7 @@ extern "C" int vg_bn_act_fwd(const float* x, const float* gamma, const float* be
   double* part = (double*)workspace;
   const Slicing s = make_slicing(B, C, HW);
   hipLaunchKernelGGL(bn_partial_kernel<0>, dim3(C, s.ns), dim3(NT), 0, st, x, (const float*)nullptr, gamma, beta,
-                     (const float*)nullptr, (const float*)nullptr, part, B, C, HW, s.per, s.ns, act);
+                     (const float*)nullptr, (const float*)nullptr, part, B, C, HW, s.per, s.ns, act, (HW & 3) == 0);
   VG_CHECK_LAUNCH();
   const Slicing a = make_apply_slicing(B, C, HW);
   hipLaunchKernelGGL(bn_apply_kernel<false>, dim3(C, a.ns), dim3(NT), 0, st, x, (const float*)nullptr,
@@ -837,7 +843,7 @@ extern "C" int vg_bn_act_bwd(const float* gy, const float* x, const float* gamma
   double* part = (double*)workspace;
   const Slicing s = make_slicing(B, C, HW);
   hipLaunchKernelGGL(bn_partial_kernel<1>, dim3(C, s.ns), dim3(NT), 0, st, x, gy, gamma, beta, save_mean,
-                     save_invstd, part, B, C, HW, s.per, s.ns, act);
+                     save_invstd, part, B, C, HW, s.per, s.ns, act, (HW & 3) == 0);
   VG_CHECK_LAUNCH();
   const Slicing a = make_apply_slicing(B, C, HW);
   hipLaunchKernelGGL(bn_apply_kernel<true>, dim3(C, a.ns), dim3(NT), 0, st, x, gy, (const double*)part, s.ns, gamma,
@@ -856,7 +862,7 @@ extern "C" int vg_channel_sum(const float* g, float* out, int B, int C, int HW, 
   const Slicing s = make_slicing(B, C, HW);
   hipLaunchKernelGGL(bn_partial_kernel<2>, dim3(C, s.ns), dim3(NT), 0, st, g, (const float*)nullptr,
                      (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,
-                     part, B, C, HW, s.per, s.ns, 0);
+                     part, B, C, HW, s.per, s.ns, 0, (HW & 3) == 0 && ((uintptr_t)g & 15) == 0);      // a view at an odd offset: scalar loads
   VG_CHECK_LAUNCH();
   hipLaunchKernelGGL(channel_sum_finalize_kernel, dim3(cdiv(C, NT)), dim3(NT), 0, st, (const double*)part, s.ns,
                      C, out);

@@ -19,6 +19,10 @@ __device__ __forceinline__ float ew_fwd(float v, int kind) {
   if (kind == VG_EW_TANH) return tanhf(v);
   return 1.f / (1.f + expf(-v));
 }
+// nn.BCELoss's clamps (log at -100, p (1 - p) at 1e-12) as compare + select: a NaN stays a NaN, as in torch's
+// clamp(min=...) (fmaxf returns its other argument, and a NaN probability came out as a finite loss)
+__device__ __forceinline__ float clamp_min(float v, float lo) { return v < lo ? lo : v; }
+
 __device__ __forceinline__ float ew_bwd(float g, float y, int kind) {
   if (kind == VG_EW_LRELU) return y > 0.f ? g : 0.2f * g;
   if (kind == VG_EW_TANH) return g * (1.f - y * y);
@@ -26,9 +30,11 @@ __device__ __forceinline__ float ew_bwd(float g, float y, int kind) {
 }
 
 __global__ __launch_bounds__(NT) void bias_act_fwd_kernel(const float* __restrict__ x, const float* __restrict__ bias,
-                                                          float* __restrict__ y, int C, int HW, size_t n, int kind) {
+                                                          float* __restrict__ y, int C, int HW, size_t n, int kind, int vec) {
+  // vec (all 16-byte forms below alike): decided by the host -- 16-byte aligned pointers (and, here, four elements that
+  // share a channel); without it the scalar loop takes every element
   const size_t stride = (size_t)gridDim.x * NT;
-  if ((HW & 3) == 0) {
+  if (vec) {
     const size_t n4 = n >> 2;
     for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n4; i += stride) {
       const float b = bias ? bias[((i << 2) / HW) % C] : 0.f;
@@ -50,9 +56,9 @@ __global__ __launch_bounds__(NT) void bias_act_fwd_kernel(const float* __restric
 
 __global__ __launch_bounds__(NT) void act_bwd_kernel(const float* __restrict__ gy, const float* __restrict__ y,
                                                      float* __restrict__ gx, size_t n, int kind,
-                                                     unsigned* __restrict__ gx_amax) {
+                                                     unsigned* __restrict__ gx_amax, int vec) {
   const size_t stride = (size_t)gridDim.x * NT;
-  const size_t n4 = n >> 2;
+  const size_t n4 = vec ? n >> 2 : 0;
   unsigned am = 0;      // max |gx| for an fp16-plane consumer (the Linear data / weight-gradient GEMMs): vg_act_bwd
   for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n4; i += stride) {
     const float4 g = reinterpret_cast<const float4*>(gy)[i];
@@ -113,20 +119,24 @@ __global__ __launch_bounds__(NT) void reparam_kl_bwd_kernel(const float* __restr
                                                             size_t n) {
   const size_t stride = (size_t)gridDim.x * NT;
   const float kb = (gkl ? gkl[0] : 0.f) * beta;
+  // An absent upstream gradient takes its whole term out, as autograd does: every factor of that term is 0, not only
+  // the gradient (0 * inf from an inf in mu, logvar or eps would be a NaN that torch does not have).  The expressions
+  // keep their shape, so with both gradients present the results keep their bits.
   for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n; i += stride) {
-    const float g = gz ? gz[i] : 0.f;
     const float l = lv[i];
-    gmu[i] = fmaf(kb, mu[i], g);
-    glv[i] = g * eps[i] * 0.5f * expf(0.5f * l) + kb * 0.5f * (expf(l) - 1.f);
+    const float g = gz ? gz[i] : 0.f, e = gz ? eps[i] : 0.f, h = gz ? expf(0.5f * l) : 0.f;
+    const float m = gkl ? mu[i] : 0.f, q = gkl ? expf(l) - 1.f : 0.f;
+    gmu[i] = fmaf(kb, m, g);
+    glv[i] = g * e * 0.5f * h + kb * 0.5f * q;
   }
 }
 
 __global__ __launch_bounds__(NT) void sqdiff_partial_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                             float* __restrict__ ga, double* __restrict__ part,
-                                                            size_t n, float gmul) {
+                                                            size_t n, float gmul, int vec) {
   __shared__ double red[NT / 64];
   const size_t stride = (size_t)gridDim.x * NT;
-  const size_t n4 = n >> 2;
+  const size_t n4 = vec ? n >> 2 : 0;
   double s = 0.0;
   for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n4; i += stride) {
     const float4 x = reinterpret_cast<const float4*>(a)[i];
@@ -161,9 +171,9 @@ __global__ __launch_bounds__(NT) void bce_kernel(const float* __restrict__ p, fl
   double s = 0.0;
   for (int i = threadIdx.x; i < B; i += NT) {
     const float v = p[i];
-    const float lp = fmaxf(logf(v), -100.f), l1p = fmaxf(logf(1.f - v), -100.f);
+    const float lp = clamp_min(logf(v), -100.f), l1p = clamp_min(logf(1.f - v), -100.f);
     s += -(double)(target * lp + (1.f - target) * l1p);
-    if (gp) gp[i] = gscale * inv_div * (v - target) / fmaxf(v * (1.f - v), 1e-12f);
+    if (gp) gp[i] = gscale * inv_div * (v - target) / clamp_min(v * (1.f - v), 1e-12f);
   }
   const double t = block_sum<NT>(s, red);
   if (threadIdx.x == 0 && loss) loss[0] = (float)(t * inv_div);
@@ -204,10 +214,10 @@ __global__ __launch_bounds__(1024) void dot_sigmoid_bce_fwd_kernel(const float* 
   s = wave_allsum(s);
   if (lane == 0) {
     const float v = 1.f / (1.f + expf(-(s + b0)));
-    const float lp = fmaxf(logf(v), -100.f), l1p = fmaxf(logf(1.f - v), -100.f);
+    const float lp = clamp_min(logf(v), -100.f), l1p = clamp_min(logf(1.f - v), -100.f);
     p_out[b] = v;
     terms[b] = -(double)(target * lp + (1.f - target) * l1p);
-    if (dlogit) dlogit[b] = (inv_div * (v - target) / fmaxf(v * (1.f - v), 1e-12f)) * v * (1.f - v);
+    if (dlogit) dlogit[b] = (inv_div * (v - target) / clamp_min(v * (1.f - v), 1e-12f)) * v * (1.f - v);
   }
 }
 
@@ -262,10 +272,10 @@ __global__ __launch_bounds__(DSB_NT) void dot_sigmoid_bce_bwd_kernel(const float
 }
 
 __global__ __launch_bounds__(NT) void scale_by_scalar_kernel(const float* g, const float* __restrict__ s, float* out,
-                                                             size_t n) {
+                                                             size_t n, int vec) {
   const float v = s[0];
   const size_t stride = (size_t)gridDim.x * NT;
-  const size_t n4 = n >> 2;
+  const size_t n4 = vec ? n >> 2 : 0;
   for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n4; i += stride) {
     float4 t = reinterpret_cast<const float4*>(g)[i];
     t.x *= v; t.y *= v; t.z *= v; t.w *= v;
@@ -279,6 +289,11 @@ int flat_grid(size_t n) {
   return (int)(blocks > 2048 ? 2048 : (blocks < 1 ? 1 : blocks));
 }
 constexpr int SQ_PARTS = 1024;
+// the 16-byte loops need every pointer they cast on a 16-byte boundary: a contiguous view at an offset of 1-3 floats
+// is a legal argument and takes the scalar loop
+inline int aligned16(const void* a, const void* b = nullptr, const void* c = nullptr) {
+  return ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0) ? 1 : 0;
+}
 
 }  // namespace
 
@@ -289,7 +304,7 @@ extern "C" int vg_bias_act_fwd(const float* x, const float* bias, float* y, int 
   if (!x || !y || B <= 0 || C <= 0 || HW <= 0 || act_kind < 0 || act_kind > 2) return VG_ERR_BAD_ARG;
   const size_t n = (size_t)B * C * HW;
   hipLaunchKernelGGL(bias_act_fwd_kernel, dim3(flat_grid(n)), dim3(NT), 0, (hipStream_t)stream, x, bias, y, C, HW, n,
-                     act_kind);
+                     act_kind, ((HW & 3) == 0 && aligned16(x, y)) ? 1 : 0);
   VG_CHECK_LAUNCH();
   return 0;
 }
@@ -298,7 +313,7 @@ extern "C" int vg_act_bwd(const float* gy, const float* y, float* gx, size_t n, 
                           void* stream) {
   if (!gy || !y || !gx || n == 0 || act_kind < 0 || act_kind > 2) return VG_ERR_BAD_ARG;
   hipLaunchKernelGGL(act_bwd_kernel, dim3(flat_grid(n)), dim3(NT), 0, (hipStream_t)stream, gy, y, gx, n, act_kind,
-                     reinterpret_cast<unsigned*>(gx_amax));
+                     reinterpret_cast<unsigned*>(gx_amax), aligned16(gy, y, gx));
   VG_CHECK_LAUNCH();
   return 0;
 }
@@ -324,7 +339,8 @@ extern "C" int vg_reparam_kl_bwd(const float* gz, const float* mu, const float* 
 
 extern "C" int vg_scale_by_scalar(const float* g, const float* s, float* out, size_t n, void* stream) {
   if (!g || !s || !out || n == 0) return VG_ERR_BAD_ARG;
-  hipLaunchKernelGGL(scale_by_scalar_kernel, dim3(flat_grid(n)), dim3(NT), 0, (hipStream_t)stream, g, s, out, n);
+  hipLaunchKernelGGL(scale_by_scalar_kernel, dim3(flat_grid(n)), dim3(NT), 0, (hipStream_t)stream, g, s, out, n,
+                     aligned16(g, out));
   VG_CHECK_LAUNCH();
   return 0;
 }
@@ -339,7 +355,7 @@ extern "C" int vg_sqdiff_loss(const float* a, const float* b, float* loss, float
   if (grid > SQ_PARTS) grid = SQ_PARTS;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(sqdiff_partial_kernel, dim3(grid), dim3(NT), 0, st, a, b, ga, (double*)workspace, n,
-                     gscale * 2.f * scale);
+                     gscale * 2.f * scale, aligned16(a, b, ga));
   VG_CHECK_LAUNCH();
   hipLaunchKernelGGL(sum_finalize_kernel, dim3(1), dim3(NT), 0, st, (const double*)workspace, grid, loss, scale);
   VG_CHECK_LAUNCH();

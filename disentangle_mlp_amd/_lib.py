@@ -88,6 +88,10 @@ SIGNATURES = {
     "vg_minmax": (_I, [_P, _Z, _P, _P, _Z, _P]),
     "vg_image_grid_shape": (_I, [_I, _I, _I, _I, _I, _P, _P]),
     "vg_image_grid_u8": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
+    "vg_quantize_each_u8": (_I, [_P, _P, _I, _I, _I, _I, _P, _Z, _P]),
+    "vg_resize_bilinear_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _P, _P]),
+    "vg_pool3x3": (_I, [_P, _P] + [_I] * 9 + [_P, _P]),
+    "vg_global_avg_pool": (_I, [_P, _P, _I, _I, _I, _P]),
 }
 
 # the tuning build (-DVG_TUNING) adds the process-global knobs of include/vaegan_hip.h's last section

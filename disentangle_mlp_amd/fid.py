@@ -23,6 +23,14 @@ the PyTorch port of the same weights) are NOT part of this repo and cannot be fe
 ``feature_extractor`` callable (images [n,h,w,3] with values 0..255 -> [n,2048]); without either ``get_fid`` accepts
 ``.npz`` statistics on both sides and raises otherwise.  Absolute FID of images: unpinned (no weights, no reference
 statistics offline).
+
+Scoring a generator without files: ``get_fid_of_generator`` / ``sample_statistics`` take the decoder itself.  The
+reference's route (utils.py:23-29 -> scoring/fid.py:286-300) writes one file per sample and reads them back; here the
+decoder's output is quantised to the very bytes ``save_image(x[i], normalize=True)`` would have encoded
+(``ops.quantize_each_u8``: bit-identical to the per-image writer) and goes to the network as a device uint8 tensor
+(``InceptionFeatureExtractor.features_u8``) -- no PIL, no PCIe copy, no file.  Differences from the file route that are
+NOT arithmetic: the lossy JPEG-in-PDF encoding of the reference's ``.pdf`` samples is skipped (a PNG would round-trip
+these bytes exactly), and all ``n_samples`` are scored (scoring/fid.py:88 drops the remainder of the last batch of 50).
 """
 import os
 import pathlib
@@ -120,16 +128,19 @@ def _load_images(files):
     return np.stack([np.asarray(Image.open(str(fn)).convert("RGB"), dtype=np.float32) for fn in files])
 
 
+_NO_EXTRACTOR = (
+    "FID of an image folder needs the Inception pool_3 network; its weights "
+    "(classify_image_graph_def.pb, fid.py:268-283) are not distributed with this package and cannot be "
+    "downloaded here.  Pass feature_extractor=callable(images[n,h,w,3] float 0..255) -> [n,2048], or "
+    "precomputed .npz statistics.")
+
+
 def _handle_path(path, feature_extractor, device, batch_size=50):
     """fid.py:286-300: .npz statistics or a folder of *.jpg / *.png images."""
     if str(path).endswith(".npz"):
         return load_statistics(path)
     if feature_extractor is None:
-        raise RuntimeError(
-            "FID of an image folder needs the Inception pool_3 network; its weights "
-            "(classify_image_graph_def.pb, fid.py:268-283) are not distributed with this package and cannot be "
-            "downloaded here.  Pass feature_extractor=callable(images[n,h,w,3] float 0..255) -> [n,2048], or "
-            "precomputed .npz statistics.")
+        raise RuntimeError(_NO_EXTRACTOR)
     p = pathlib.Path(path)
     files = list(p.glob("*.jpg")) + list(p.glob("*.png"))
     st = None
@@ -179,3 +190,55 @@ def calculate_fid_given_paths(paths, inception_path="", low_profile=False, featu
 def get_fid(path_data, path_pretrained, inception="", lowprofile=False, feature_extractor=None, device="cuda"):
     """fid.py:320-323."""
     return calculate_fid_given_paths([path_data, path_pretrained], inception, lowprofile, feature_extractor, device)
+
+
+def sample_statistics(fn, n_samples, n_hidden, feature_extractor, device="cuda", decode_batch=None):
+    """(mu, sigma), fp64 device tensors, of the pool_3 activations of ``n_samples`` decoded N(0, 1) codes -- what
+    utils.py:23-29 + scoring/fid.py:286-300 compute through files, without leaving the device.
+
+    The codes are drawn as ``image_io.generate_fid_samples`` draws them (``torch.randn(n_samples, n_hidden)`` on the
+    CPU: the same seed gives the same latents) and decoded by ``fn`` (``netEG.decode``) as ONE batch, like the
+    reference.  ``decode_batch`` decodes them in pieces instead: a DEVIATION, because the reference never calls
+    ``.eval()`` and train-mode BatchNorm makes a sample depend on the batch it is decoded with; it is opt-in, for
+    ``n_samples`` whose activations do not fit.  Each decoded image is quantised as ``save_image(x[i], normalize=True)``
+    would (``ops.quantize_each_u8``); ``feature_extractor`` is an ``InceptionFeatureExtractor`` (its ``features_u8`` is
+    used) or any callable on device uint8 images [n,h,w,3] -> [n,d]."""
+    n_samples = int(n_samples)
+    if n_samples < 2:
+        raise ValueError("covariance needs at least 2 samples")
+    if feature_extractor is None:
+        raise RuntimeError(_NO_EXTRACTOR)
+    if decode_batch is not None and int(decode_batch) < 1:
+        raise ValueError("decode_batch must be positive")
+    extract = getattr(feature_extractor, "features_u8", feature_extractor)
+    from . import ops
+    st = None
+    with torch.no_grad():
+        z = torch.randn(n_samples, n_hidden)                 # CPU draw, like the reference
+        step = n_samples if decode_batch is None else int(decode_batch)
+        for s in range(0, n_samples, step):
+            sample = fn(z[s:s + step].to(device))
+            act = extract(ops.quantize_each_u8(sample.detach().float().contiguous()))
+            act = act.reshape(act.shape[0], -1)
+            st = st or ActivationStatistics(act.shape[1], device)
+            st.update(act)
+    return st.finalize()
+
+
+def get_fid_of_generator(fn, n_samples, n_hidden, path_pretrained, inception="", feature_extractor=None, device="cuda"):
+    """FID of the generator ``fn`` (``netEG.decode``) against ``path_pretrained`` (``.npz`` statistics, or an image
+    folder: `_handle_path`): ``generate_fid_samples`` + ``get_fid`` (new_betavaegan.py:231-235) with nothing written.
+    ``inception`` as in `get_fid`; ``feature_extractor`` as in `sample_statistics`."""
+    if int(n_samples) < 2:
+        raise ValueError("covariance needs at least 2 samples")
+    if not os.path.exists(path_pretrained):
+        raise RuntimeError("Invalid path: %s" % path_pretrained)
+    if feature_extractor is None:
+        weights = _find_inception_weights(inception)
+        if weights is None:
+            raise RuntimeError(_NO_EXTRACTOR)
+        from .inception import InceptionFeatureExtractor
+        feature_extractor = InceptionFeatureExtractor(weights, device=device)
+    m2, s2 = _handle_path(path_pretrained, feature_extractor, device)
+    m1, s1 = sample_statistics(fn, n_samples, n_hidden, feature_extractor, device)
+    return calculate_frechet_distance(m1, s1, m2, s2, device=device)

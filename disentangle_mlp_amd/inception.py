@@ -15,7 +15,14 @@ are gathered from NCHW while they are staged -- no im2col matrix exists in HBM -
 accumulators.  The branches of a block write their channels straight into the block's concatenated output (no
 ``torch.cat``).  Bounds for the fp16 scaling: one ``vg_absmax`` pass over the network input; every convolution leaves
 max |y| for its consumer; pooled tensors inherit their input's bound (|avg|, |max| <= max |x|); no host reads.
-Pooling, the bilinear resize and the final average stay on ATen.
+The bilinear resize of ``InceptionV3.forward`` stays on ATen; its pooling and its final average run on ATen by default
+and on this package's kernels (csrc/fid_front.hip) under ``VG_INCEPTION_POOL=hip`` (or ``inception.POOL_LOWERING = "hip"``): every
+3x3 pooling through ``vg_pool3x3`` -- a pooling branch without convolution writes its slice of the block's output
+itself and adds its true max |out| to the block's bound, so neither ``out[:, off:].copy_(pooled)`` nor
+``slot.copy_(torch.maximum(...))`` is launched -- and the final average through ``vg_global_avg_pool``.
+``InceptionFeatureExtractor.features_u8`` (device uint8 images, what ``ops.quantize_each_u8`` makes of the decoder's
+output) always takes those kernels, and ``vg_resize_bilinear_u8`` in front of them: resize, / 255, 2 x - 1 and the
+network input's bound in one launch -- no ``F.interpolate``, no ``vg_absmax`` pass, no ``torch.cat``, no host read.
 
 CPU tensors, and device tensors under ``VG_INCEPTION_CONV=unfold`` (or ``inception.CONV_LOWERING = "unfold"``), take
 the earlier lowering: every convolution as ONE fp32 GEMM -- 1x1 convolutions directly, the others through ``F.unfold``
@@ -38,8 +45,20 @@ if CONV_LOWERING not in ("hip", "unfold"):
     raise ImportError(f"VG_INCEPTION_CONV={CONV_LOWERING!r}: expected 'hip' or 'unfold'")
 
 
+# Lowering of the pooling layers on the device path of ``InceptionV3.forward``: "aten" (the default: what it has always
+# launched) or "hip" (csrc/fid_front.hip).  Set here, or with VG_INCEPTION_POOL.  `features_u8` always takes "hip".
+POOL_LOWERING = os.environ.get("VG_INCEPTION_POOL", "aten")
+if POOL_LOWERING not in ("aten", "hip"):
+    raise ImportError(f"VG_INCEPTION_POOL={POOL_LOWERING!r}: expected 'aten' or 'hip'")
+_force_hip_pool = False       # raised by `features_u8` around its network runs
+
+
 def _hip(x):
     return x.is_cuda and CONV_LOWERING == "hip"
+
+
+def _hip_pool(x):
+    return _hip(x) and (_force_hip_pool or POOL_LOWERING == "hip")
 
 
 def _ops():
@@ -47,9 +66,15 @@ def _ops():
     return ops
 
 
-def _pooled(x, pool):
-    """pool(x) with x's bound: |avg|, |max| <= max |x|."""
-    p = pool(x)
+def _pool3(x, mode, stride, padding):
+    """The 3x3 "max" / "avg" (padding not counted: Tensorflow's average pool, scoring/inception.py:203-205) pooling.  On
+    ATen the result inherits x's bound (|avg|, |max| <= max |x|); the HIP kernel leaves the true one."""
+    if _hip_pool(x):
+        return _ops().pool3x3(x, stride, padding, mode)
+    if mode == "max":
+        p = F.max_pool2d(x, kernel_size=3, stride=stride, padding=padding)
+    else:
+        p = F.avg_pool2d(x, kernel_size=3, stride=stride, padding=padding, count_include_pad=False)
     if _hip(x):
         _ops().set_amax(p, _ops().amax_of(x))
     return p
@@ -60,8 +85,13 @@ def _block_out(x, channels, oh, ow):
     return torch.empty((x.shape[0], channels, oh, ow), dtype=torch.float32, device=x.device), _ops().new_amax_slot(x.device)
 
 
-def _copy_pooled(x, pooled, out, offset, slot):
-    """A pooling branch without convolution: copied into its slice; the block's bound covers x's."""
+def _max_pool_branch(x, out, offset, slot):
+    """The 3x3 / stride 2 max-pooling branch of blocks B and D (no convolution behind it) into its slice of ``out``.  HIP:
+    the kernel writes the slice and adds max |pooled| to the block's bound; ATen: copied, the bound covers x's."""
+    if _hip_pool(x):
+        _ops().pool3x3(x, 2, 0, "max", out, offset, slot)
+        return
+    pooled = F.max_pool2d(x, kernel_size=3, stride=2)
     slot.copy_(torch.maximum(slot, _ops().amax_of(x)))
     out[:, offset:offset + pooled.shape[1]].copy_(pooled)
 
@@ -119,8 +149,8 @@ class _ConvBN(nn.Module):
         return torch.relu_(y).view(B, -1, OH, OW)
 
 
-def _avg3(x):       # Tensorflow's average pool: padded zeros are not counted (scoring/inception.py:203-205)
-    return F.avg_pool2d(x, kernel_size=3, stride=1, padding=1, count_include_pad=False)
+def _avg3(x):
+    return _pool3(x, "avg", 1, 1)
 
 
 class _A(nn.Module):        # FIDInceptionA
@@ -140,7 +170,7 @@ class _A(nn.Module):        # FIDInceptionA
             self.branch1x1(x, out, 0, slot)
             self.branch5x5_2(self.branch5x5_1(x), out, 64, slot)
             self.branch3x3dbl_3(self.branch3x3dbl_2(self.branch3x3dbl_1(x)), out, 128, slot)
-            self.branch_pool(_pooled(x, _avg3), out, 224, slot)
+            self.branch_pool(_avg3(x), out, 224, slot)
             _ops().set_amax(out, slot)
             return out
         return torch.cat([self.branch1x1(x), self.branch5x5_2(self.branch5x5_1(x)),
@@ -161,7 +191,7 @@ class _B(nn.Module):        # torchvision InceptionB
             out, slot = _block_out(x, 480 + x.shape[1], (x.shape[2] - 3) // 2 + 1, (x.shape[3] - 3) // 2 + 1)
             self.branch3x3(x, out, 0, slot)
             self.branch3x3dbl_3(self.branch3x3dbl_2(self.branch3x3dbl_1(x)), out, 384, slot)
-            _copy_pooled(x, F.max_pool2d(x, kernel_size=3, stride=2), out, 480, slot)
+            _max_pool_branch(x, out, 480, slot)
             _ops().set_amax(out, slot)
             return out
         return torch.cat([self.branch3x3(x), self.branch3x3dbl_3(self.branch3x3dbl_2(self.branch3x3dbl_1(x))),
@@ -189,7 +219,7 @@ class _C(nn.Module):        # FIDInceptionC
             self.branch7x7_3(self.branch7x7_2(self.branch7x7_1(x)), out, 192, slot)
             t = self.branch7x7dbl_4(self.branch7x7dbl_3(self.branch7x7dbl_2(self.branch7x7dbl_1(x))))
             self.branch7x7dbl_5(t, out, 384, slot)
-            self.branch_pool(_pooled(x, _avg3), out, 576, slot)
+            self.branch_pool(_avg3(x), out, 576, slot)
             _ops().set_amax(out, slot)
             return out
         b7 = self.branch7x7_3(self.branch7x7_2(self.branch7x7_1(x)))
@@ -212,7 +242,7 @@ class _D(nn.Module):        # torchvision InceptionD
             out, slot = _block_out(x, 512 + x.shape[1], (x.shape[2] - 3) // 2 + 1, (x.shape[3] - 3) // 2 + 1)
             self.branch3x3_2(self.branch3x3_1(x), out, 0, slot)
             self.branch7x7x3_4(self.branch7x7x3_3(self.branch7x7x3_2(self.branch7x7x3_1(x))), out, 320, slot)
-            _copy_pooled(x, F.max_pool2d(x, kernel_size=3, stride=2), out, 512, slot)
+            _max_pool_branch(x, out, 512, slot)
             _ops().set_amax(out, slot)
             return out
         b7 = self.branch7x7x3_4(self.branch7x7x3_3(self.branch7x7x3_2(self.branch7x7x3_1(x))))
@@ -234,7 +264,7 @@ class _E(nn.Module):        # FIDInceptionE_1 (avg) / FIDInceptionE_2 (max: scor
         self.branch_pool = _ConvBN(cin, 192, 1)
 
     def _pool(self, x):
-        return _avg3(x) if self.pool == "avg" else F.max_pool2d(x, kernel_size=3, stride=1, padding=1)
+        return _pool3(x, self.pool, 1, 1)
 
     def forward(self, x):
         if _hip(x):
@@ -246,7 +276,7 @@ class _E(nn.Module):        # FIDInceptionE_1 (avg) / FIDInceptionE_2 (max: scor
             t = self.branch3x3dbl_2(self.branch3x3dbl_1(x))
             self.branch3x3dbl_3a(t, out, 1088, slot)
             self.branch3x3dbl_3b(t, out, 1472, slot)
-            self.branch_pool(_pooled(x, self._pool), out, 1856, slot)
+            self.branch_pool(self._pool(x), out, 1856, slot)
             _ops().set_amax(out, slot)
             return out
         t = self.branch3x3_1(x)
@@ -303,7 +333,7 @@ class InceptionV3(nn.Module):
 
     def forward(self, inp):
         """inp (B,3,H,W) in [0,1] -> list of the requested blocks' feature maps (ascending block index)."""
-        n, outp, x = self.net, [], inp
+        x = inp
         if self.resize_input:
             x = F.interpolate(x, size=(299, 299), mode="bilinear", align_corners=False)
         if self.normalize_input:
@@ -311,15 +341,26 @@ class InceptionV3(nn.Module):
         if _hip(x):
             x = x.float().contiguous()
             _ops().amax_of(x)                       # the one explicit bound pass; every later bound comes from a producer
+        return self._blocks(x)
+
+    def _blocks(self, x, pool3_out=None):
+        """The network behind resize + normalisation (a device input under the "hip" lowering carries its bound).
+        ``pool3_out`` (HIP pooling only): the [B,2048] rows the final average is written to."""
+        n, outp = self.net, []
 
         def pool2(t):
-            return _pooled(t, lambda v: F.max_pool2d(v, kernel_size=3, stride=2))
+            return _pool3(t, "max", 2, 0)
+
+        def mean(t):
+            if _hip_pool(t):
+                return _ops().global_avg_pool(t, pool3_out).view(t.shape[0], t.shape[1], 1, 1)
+            return F.adaptive_avg_pool2d(t, (1, 1))
 
         stages = (
             lambda t: pool2(n.Conv2d_2b_3x3(n.Conv2d_2a_3x3(n.Conv2d_1a_3x3(t)))),
             lambda t: pool2(n.Conv2d_4a_3x3(n.Conv2d_3b_1x1(t))),
             lambda t: n.Mixed_6e(n.Mixed_6d(n.Mixed_6c(n.Mixed_6b(n.Mixed_6a(n.Mixed_5d(n.Mixed_5c(n.Mixed_5b(t)))))))),
-            lambda t: F.adaptive_avg_pool2d(n.Mixed_7c(n.Mixed_7b(n.Mixed_7a(t))), (1, 1)),
+            lambda t: mean(n.Mixed_7c(n.Mixed_7b(n.Mixed_7a(t)))),
         )
         for idx, stage in enumerate(stages):
             x = stage(x)
@@ -347,3 +388,29 @@ class InceptionFeatureExtractor:
             xb = x[s:s + self.batch_size].to(self.device, torch.float32).permute(0, 3, 1, 2).contiguous() / 255.0
             outs.append(self.model(xb)[0].reshape(xb.shape[0], -1))
         return torch.cat(outs)
+
+    @torch.no_grad()
+    def features_u8(self, images_u8):
+        """Device uint8 images [n,h,w,3] (``ops.quantize_each_u8`` of the decoder's output) -> pool_3 activations
+        [n,2048] fp32 on the device, in chunks of ``batch_size`` (the last one may be shorter).  Always on this
+        package's kernels: ``vg_resize_bilinear_u8`` (resize to 299 x 299, / 255, 2 x - 1 and the input's bound), the
+        convolutions, every pooling through ``vg_pool3x3``, ``vg_global_avg_pool``; no host read."""
+        global _force_hip_pool
+        if not (isinstance(images_u8, torch.Tensor) and images_u8.is_cuda and images_u8.dtype == torch.uint8
+                and images_u8.dim() == 4 and images_u8.shape[3] == 3):
+            raise RuntimeError("features_u8: expected a CUDA/ROCm uint8 [n,h,w,3] tensor (no CPU fallback)")
+        if CONV_LOWERING != "hip":
+            raise RuntimeError(f"features_u8 runs on the HIP kernels only (VG_INCEPTION_CONV={CONV_LOWERING!r})")
+        m = self.model
+        if not (m.resize_input and m.normalize_input):
+            raise RuntimeError("features_u8: the network must resize and normalise its input (the FID configuration)")
+        images_u8 = images_u8.contiguous()
+        feats = torch.empty((images_u8.shape[0], 2048), dtype=torch.float32, device=images_u8.device)
+        prev, _force_hip_pool = _force_hip_pool, True
+        try:
+            for s in range(0, images_u8.shape[0], self.batch_size):
+                x = _ops().resize_bilinear_u8(images_u8[s:s + self.batch_size], (299, 299), 2.0, -1.0)
+                m._blocks(x, feats[s:s + self.batch_size])
+        finally:
+            _force_hip_pool = prev
+        return feats

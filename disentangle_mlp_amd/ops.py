@@ -1058,3 +1058,95 @@ def image_grid_u8(x, nrow=8, padding=2, normalize=False, pad_value=0.0):
     check(lib.vg_image_grid_u8(x.data_ptr(), _ptr(mm), grid.data_ptr(), B, C, H, W, nrow, padding, float(pad_value),
                                _stream()), "vg_image_grid_u8")
     return grid
+
+
+# ------------------------------------- decoder output -> FID features on the device (csrc/fid_front.hip)
+POOL_MAX, POOL_AVG_EXCLUDE_PAD = 0, 1      # VG_POOL_* of include/vaegan_hip.h
+
+
+def _req_u8_images(t, name):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda):
+        raise RuntimeError(f"{name}: disentangle_mlp_amd ops need CUDA/ROCm tensors (no CPU fallback)")
+    if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3 or not t.is_contiguous():
+        raise RuntimeError(f"{name}: expected a contiguous uint8 [B,H,W,3] tensor, got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def quantize_each_u8(x):
+    """``save_image(x[i], normalize=True)`` for every image of x [B,C,H,W] (C = 1 or 3) at once -> uint8 [B,H,W,3] on the
+    device: bit-identical to ``image_grid_u8(x[i], normalize=True)`` per image, in two launches for the batch."""
+    _req(x, "x")
+    lib = _lib.load()
+    if x.dim() != 4 or x.shape[1] not in (1, 3):
+        raise RuntimeError(f"quantize_each_u8: expected [B,C,H,W] with C = 1 or 3, got {tuple(x.shape)}")
+    B, C, H, W = x.shape
+    out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=x.device)
+    for s in range(0, B, 65535):                      # grid.y limit
+        n = min(65535, B - s)
+        ws = workspace(8 * n, x.device)
+        check(lib.vg_quantize_each_u8(x[s:].data_ptr(), out[s:].data_ptr(), n, C, H, W, ws.data_ptr(), ws.numel(),
+                                      _stream()), "vg_quantize_each_u8")
+    return out
+
+
+def resize_bilinear_u8(images_u8, size=(299, 299), scale=2.0, shift=-1.0):
+    """images_u8 [B,H,W,3] uint8 (device) -> fp32 [B,3,OH,OW] = scale * bilinear(u8 / 255) + shift
+    (``F.interpolate(mode="bilinear", align_corners=False)`` + ``normalize_input``); the result carries its bound."""
+    _req_u8_images(images_u8, "resize_bilinear_u8")
+    lib = _lib.load()
+    B, H, W, _ = images_u8.shape
+    OH, OW = _pair(size)
+    if B > 65535:
+        raise RuntimeError("resize_bilinear_u8: at most 65535 images per call")
+    y = torch.empty((B, 3, OH, OW), dtype=torch.float32, device=images_u8.device)
+    slot = _amax_slot(y.device)
+    check(lib.vg_resize_bilinear_u8(images_u8.data_ptr(), y.data_ptr(), B, H, W, OH, OW, float(scale), float(shift),
+                                    slot.data_ptr(), _stream()), "vg_resize_bilinear_u8")
+    set_amax(y, slot)
+    return y
+
+
+def pool3x3(x, stride, padding, mode, out=None, out_channel_offset=0, amax=None):
+    """3x3 pooling of x [B,C,H,W]: ``mode`` "max" (``F.max_pool2d``: padding reads as -inf) or "avg"
+    (``F.avg_pool2d(count_include_pad=False)``), stride 1 or 2, padding 0 or 1.  ``out``: a contiguous (B, Ctot, OH, OW)
+    tensor; channels [out_channel_offset, out_channel_offset + C) are written, the others are not touched.  ``amax``: the
+    bound slot max |out| is added to (a new one by default); the returned view of the written channels carries it."""
+    _req(x, "x")
+    lib = _lib.load()
+    if x.dim() != 4 or mode not in ("max", "avg"):
+        raise RuntimeError(f"pool3x3: expected a [B,C,H,W] input and mode 'max' or 'avg', got {tuple(x.shape)}, {mode!r}")
+    B, C, H, W = x.shape
+    stride, padding = int(stride), int(padding)
+    if stride not in (1, 2) or padding not in (0, 1) or H + 2 * padding < 3 or W + 2 * padding < 3 or B > 65535:
+        raise RuntimeError(f"pool3x3: stride {stride}, padding {padding} on {tuple(x.shape)} is not taken")
+    OH, OW = (H + 2 * padding - 3) // stride + 1, (W + 2 * padding - 3) // stride + 1
+    if out is None:
+        out = torch.empty((B, C, OH, OW), dtype=torch.float32, device=x.device)
+    else:
+        _req(out, "out")
+        if out.dim() != 4 or (out.shape[0], out.shape[2], out.shape[3]) != (B, OH, OW) or \
+                not 0 <= out_channel_offset <= out.shape[1] - C:
+            raise RuntimeError(f"pool3x3: out {tuple(out.shape)} cannot take channels [{out_channel_offset}, "
+                               f"{out_channel_offset + C}) of a (B={B}, {OH}x{OW}) output")
+    slot = amax if amax is not None else _amax_slot(x.device)
+    check(lib.vg_pool3x3(x.data_ptr(), out.data_ptr(), B, C, H, W, stride, padding,
+                         POOL_MAX if mode == "max" else POOL_AVG_EXCLUDE_PAD, out.shape[1], out_channel_offset,
+                         slot.data_ptr(), _stream()), "vg_pool3x3")
+    view = out[:, out_channel_offset:out_channel_offset + C]
+    set_amax(view, slot)
+    return view
+
+
+def global_avg_pool(x, out=None):
+    """x [B,C,...] -> [B,C]: the mean over everything behind the channel axis (``adaptive_avg_pool2d(x, (1, 1))``), one
+    wavefront per (b, c) in a fixed summation order.  ``out``: a contiguous [B,C] tensor to write (rows of a larger one)."""
+    _req(x, "x")
+    lib = _lib.load()
+    if x.dim() < 3:
+        raise RuntimeError(f"global_avg_pool: expected [B,C,...], got {tuple(x.shape)}")
+    B, C = x.shape[0], x.shape[1]
+    y = torch.empty((B, C), dtype=torch.float32, device=x.device) if out is None else _req(out, "out")
+    if tuple(y.shape) != (B, C):
+        raise RuntimeError(f"global_avg_pool: out {tuple(y.shape)} does not match ({B}, {C})")
+    check(lib.vg_global_avg_pool(x.data_ptr(), y.data_ptr(), B, C, x.numel() // (B * C), _stream()), "vg_global_avg_pool")
+    return y

@@ -808,16 +808,25 @@ class BetaVAEGANTrainer(_GraphedSteps):
 
     # -- the experiment script's ``__main__`` (new_betavaegan.py:211-267) -----------------
     def fit(self, loader, epochs, start_epoch=0, model_path=None, label_rng=None, calc_fid=False, n_samples=1000,
-            fid_path_recons=None, fid_path_pretrained=None, get_fid=None, log=None, max_iterations=None, verbose=True):
+            fid_path_recons=None, fid_path_pretrained=None, get_fid=None, log=None, max_iterations=None, verbose=True,
+            fid_on_device=False, fid_inception="", fid_feature_extractor=None):
         """The training half of the reference's ``__main__`` (new_betavaegan.py:218-246): per epoch ``train(epoch)``
         (`train_epoch`), the checkpoint ``{model_path}/model_{epoch+1}.tar`` (:222-228), optionally
         ``generate_fid_samples`` + ``get_fid`` (:231-235), the printed line (:237-238) and the logger row (:241-246:
         ``log(row)``, e.g. the reference's ``Logger.log``).  ``get_fid`` defaults to this package's
         (`fid.get_fid`; it needs Inception weights on disk, so ``calc_fid`` is off unless asked for).  Under data
-        parallelism every rank trains, rank 0 writes.  Returns the rows (with ``Dx`` added)."""
+        parallelism every rank trains, rank 0 writes.  Returns the rows (with ``Dx`` added).
+
+        ``fid_on_device=True`` (with ``calc_fid``): the epoch's FID is ``fid.get_fid_of_generator(self.netEG.decode, ...)``
+        -- the samples go from the decoder to the Inception network as a device tensor, no file is written and
+        ``fid_path_recons`` / ``get_fid`` are not used.  The network comes from ``fid_inception`` (as `fid.get_fid`'s
+        ``inception``) or ``fid_feature_extractor``, is built once and kept for the whole call.  The default keeps the
+        reference's route, including its mismatch: the samples are written as ``.pdf`` while ``get_fid`` looks for
+        ``*.jpg`` / ``*.png`` (utils.py:26 vs scoring/fid.py:293), so with the defaults that route finds no image."""
         import os
         from . import image_io
         rows = []
+        fid_extractor = self._fid_extractor(fid_inception, fid_feature_extractor) if calc_fid and fid_on_device else None
         for epoch in range(start_epoch, epochs):
             enc_loss, dec_loss, dis_loss, dx = self.train_epoch(loader, label_rng=label_rng, max_iterations=max_iterations)
             fid = "N/A"
@@ -825,7 +834,11 @@ class BetaVAEGANTrainer(_GraphedSteps):
                 with torch.no_grad():
                     if model_path is not None:
                         self.save(os.path.join(model_path, f"model_{epoch + 1}.tar"), epoch + 1)
-                    if calc_fid:
+                    if calc_fid and fid_on_device:
+                        from .fid import get_fid_of_generator
+                        fid = get_fid_of_generator(self.netEG.decode, n_samples, self.opt.n_hidden, fid_path_pretrained,
+                                                   feature_extractor=fid_extractor, device=self.device)
+                    elif calc_fid:
                         if get_fid is None:
                             from .fid import get_fid
                         image_io.generate_fid_samples(self.netEG.decode, epoch, n_samples, self.opt.n_hidden,
@@ -841,24 +854,43 @@ class BetaVAEGANTrainer(_GraphedSteps):
                 rows.append(dict(row, Dx=dx))
         return rows
 
+    def _fid_extractor(self, inception, feature_extractor):
+        """The Inception network of the ``fid_on_device`` route: the caller's, or one built from the weights at
+        ``inception``; without either the same loud error as `fid.get_fid`."""
+        if feature_extractor is not None:
+            return feature_extractor
+        from . import fid
+        weights = fid._find_inception_weights(inception)
+        if weights is None:
+            raise RuntimeError(fid._NO_EXTRACTOR)
+        from .inception import InceptionFeatureExtractor
+        return InceptionFeatureExtractor(weights, device=self.device)
+
     def evaluate(self, load_paths, test_loader=None, start_epoch=0, calc_fid=False, n_samples=1000, fid_path_samples=None,
                  fid_path_pretrained=None, get_fid=None, test_recons=False, test_results_path_recons=None,
-                 test_results_path_originals="", test_samples=False, test_results_path_samples=None):
+                 test_results_path_originals="", test_samples=False, test_results_path_samples=None,
+                 fid_on_device=False, fid_inception="", fid_feature_extractor=None):
         """The evaluation half (new_betavaegan.py:248-267): for every checkpoint of ``load_paths`` -- load it, renumber
         its epoch the way the reference does so that files of several checkpoints do not overwrite each other (:252-254),
         then FID samples + score (:256-259), one grid of test reconstructions with ``nrow=1`` (+ the originals, :260-263)
         and five samples named after ``start_epoch`` (:264-267: the reference passes ``start_epoch`` there, so several
         checkpoints write the same file; kept).  Train-mode BatchNorm throughout: the reference never calls ``.eval()``
-        (SURVEY.md section 3.1 item 5).  Returns one dict per checkpoint."""
+        (SURVEY.md section 3.1 item 5).  Returns one dict per checkpoint.  ``fid_on_device`` / ``fid_inception`` /
+        ``fid_feature_extractor``: as in `fit` -- the FID straight from the decoder, no sample files."""
         from . import image_io
         out, tmp_epoch = [], 0
+        fid_extractor = self._fid_extractor(fid_inception, fid_feature_extractor) if calc_fid and fid_on_device else None
         for m in load_paths:
             epoch = self.load(m)
             epoch = epoch if epoch != tmp_epoch and tmp_epoch < epoch else tmp_epoch + 1
             tmp_epoch = epoch
             res = {"path": m, "epoch": epoch, "FID": "N/A"}
             with torch.no_grad():
-                if calc_fid:
+                if calc_fid and fid_on_device:
+                    from .fid import get_fid_of_generator
+                    res["FID"] = get_fid_of_generator(self.netEG.decode, n_samples, self.opt.n_hidden, fid_path_pretrained,
+                                                      feature_extractor=fid_extractor, device=self.device)
+                elif calc_fid:
                     if get_fid is None:
                         from .fid import get_fid
                     image_io.generate_fid_samples(self.netEG.decode, epoch, n_samples, self.opt.n_hidden, fid_path_samples,

@@ -44,7 +44,9 @@ extern "C" {
  * workspace contract.  vg_version() returns the value the library was built with; a binding must refuse a library
  * whose version is not the header's (the .so files are build products that travel with the working tree: a stale one
  * still exports every old symbol).  3: round 3.  4: round 4 (fp16 planes: VG_PLANES_F16, the *_amax arguments).
- * 6: vg_conv_general_* (the general forward convolution).  7: vg_adam_step_checked / vg_adam_step_dev_checked. */
+ * 6: vg_conv_general_* (the general forward convolution).  7: vg_adam_step_checked / vg_adam_step_dev_checked.
+ * Entry points that are only ADDED (the four of csrc/fid_front.hip) change nothing an existing caller sees and keep the
+ * version: a binding that needs them and finds a library without them fails at the symbol lookup, as loudly. */
 #define VG_ABI_VERSION 7
 int vg_version(void);
 
@@ -468,6 +470,45 @@ int vg_minmax(const float* x, size_t n, float* out2, void* workspace, size_t wor
 int vg_image_grid_shape(int B, int H, int W, int nrow, int padding, int* grid_h, int* grid_w);
 int vg_image_grid_u8(const float* x, const float* minmax, uint8_t* grid, int B, int C, int H, int W,
                      int nrow, int padding, float pad_value, void* stream);
+
+/* ---- from the decoder's output to the FID features without a host round trip (csrc/fid_front.hip) ----------------
+ * The FID route of experiments/new_betavaegan.py:231-235 is utils.py:23-29 (save_image(x[i], normalize=True) per
+ * sample) -> files -> scoring/fid.py:68-105 (load, / 255, the Inception network).  These four kernels keep it on the
+ * device; all are HBM-bound streaming kernels, correct for any base alignment and any width (16-byte accesses where
+ * the addresses allow).
+ *
+ * vg_quantize_each_u8: save_image(x[i], normalize=True) for every image i of x[B,C,H,W] (C = 1 or 3; C = 1 is
+ * replicated) at once: out[B][H][W][3] uint8, per image v = (clamp(x, min, max) - min) / (max - min + 1e-5),
+ * byte = trunc(clamp(v * 255, 0, 255)) with that image's own min and max.  Bit-identical to vg_minmax +
+ * vg_image_grid_u8 on each image alone (same operation order); two launches for the whole batch.
+ * workspace: 2 * B floats (4-byte aligned). */
+int vg_quantize_each_u8(const float* x, uint8_t* out, int B, int C, int H, int W, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
+/* y[B,3,OH,OW] = scale * bilinear(img[B,H,W,3] / 255) + shift: F.interpolate(mode="bilinear", align_corners=False)
+ * (scoring/inception.py:147-150; ATen's rule in fp32: source coordinate max(0, (o + 0.5) * in / out - 0.5), upper
+ * neighbour clamped to in - 1) and normalize_input (:152-153: scale = 2, shift = -1) in one pass.  Any sizes; in == out
+ * is the identity.  amax (may be NULL): max |y| is added to amax[0] (atomic maximum on the bit pattern, DEVICE memory,
+ * zeroed by the caller: see vg_absmax) -- the first convolution's x_amax. */
+int vg_resize_bilinear_u8(const uint8_t* img, float* y, int B, int H, int W, int OH, int OW, float scale, float shift,
+                          float* amax, void* stream);
+
+/* 3x3 pooling of x[B,C,H,W], stride 1 or 2, padding 0 or 1, OH = (H + 2 pad - 3) / stride + 1 (OW alike) -- the three
+ * poolings of the FID Inception network (scoring/inception.py:210, 238, 271, 306; the MaxPool2d(3, 2) of its blocks and of torchvision's InceptionB / D):
+ *   VG_POOL_MAX               F.max_pool2d(x, 3, stride, pad): padding reads as -inf, a NaN wins;
+ *   VG_POOL_AVG_EXCLUDE_PAD   F.avg_pool2d(x, 3, stride, pad, count_include_pad=False).
+ * out is a (B, out_channels_total, OH, OW) tensor: channels [out_channel_offset, out_channel_offset + C) are written,
+ * the others are not touched (the contract of vg_conv_general_fwd's y / y_image_stride: a pooling branch writes its
+ * slice of an Inception block's concatenated output).  amax (may be NULL): the true max |out| is added to amax[0]
+ * (see vg_absmax; DEVICE, zeroed by the caller; several launches may add into one slot). */
+#define VG_POOL_MAX 0
+#define VG_POOL_AVG_EXCLUDE_PAD 1
+int vg_pool3x3(const float* x, float* out, int B, int C, int H, int W, int stride, int pad, int mode,
+               int out_channels_total, int out_channel_offset, float* amax, void* stream);
+
+/* y[b][c] = mean over hw of x[b][c][hw]: nn.AdaptiveAvgPool2d((1, 1)) (scoring/inception.py:122).  One wavefront
+ * per (b, c), a summation order that depends on HW alone: bit-reproducible, no atomics, no workspace. */
+int vg_global_avg_pool(const float* x, float* y, int B, int C, int HW, void* stream);
 
 #ifdef VG_TUNING
 /* ---- tuning build only (libvaegan_hip_tuning.so): process-global knobs, never in the product library ---- */

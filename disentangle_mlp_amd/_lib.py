@@ -34,6 +34,9 @@ SIGNATURES = {
     "vg_gemm_nt_f16x3_workspace_bytes": (_Z, [_I, _I, _I]),
     "vg_gemm_nt_f16x3": (_I, [_P, _P, _P, _P, _I, _I, _I, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, _P, _P,
                               _P, _Z, _P]),
+    "vg_gemm_nt_f16x3_grouped_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "vg_gemm_nt_f16x3_grouped": (_I, [_I, _P, _P, _P, _P, _I, _I, _I, ctypes.c_long, ctypes.c_long, ctypes.c_long,
+                                      ctypes.c_long, _P, _P, _P, _Z, _P]),
     "vg_conv_general_packed_bytes": (_Z, [_I, _I, _I, _I]),
     "vg_conv_general_pack": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "vg_conv_general_fwd": (_I, [_P, _P, _P, _P] + [_I] * 11 + [ctypes.c_long, _I, _P, _P, _P]),

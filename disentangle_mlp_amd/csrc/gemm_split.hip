@@ -22,6 +22,12 @@
 // where it is not -- G_PD stages ahead in registers, splits them into planes and writes two 16-byte LDS units each
 // ([plane][k-block][row], k-blocks padded by two units so that the 4 lanes that share a row do not share banks);
 // stages are double-buffered in LDS, ONE barrier per stage.  Plain loads only: hipcc counts vmcnt itself.
+//
+// Grouped form (vg_gemm_nt_f16x3_grouped, template parameter NG = 1..3): NG activations A_g against the SAME B -- the
+// discriminator's passes of one phase over its unchanged 16384 x 2048 weight.  A workgroup owns its (tile, K slice) for
+// all groups: a stage loads, scales, splits and writes the B unit once, stages NG A units and runs each group's 12
+// MFMAs against the same B fragments into the group's own accumulators.  Tiling, K slicing, the order of a group's
+// MFMAs, the epilogue and the slab sum are those of a single call, so C_g is bit for bit vg_gemm_nt_f16x3 on A_g.
 #include "common.hpp"
 #include "vaegan_hip.h"
 
@@ -52,17 +58,19 @@ constexpr int G_PD = 3;                                      // register slots: 
 constexpr int G_NU = 1;                                      // staged units per thread and operand
 static_assert(GTM == GTN && GTM * 4 == G_NU * GNT, "staging map");
 
+constexpr int G_MAXG = VG_GEMM_MAX_GROUPS;
+
 struct GArgs {
-  const float* A;
+  const float* A[G_MAXG];   // per group
   const float* B;
   const float* bias;
-  float* C;            // ksplit == 1: the output [M][N]; else the slabs [ksplit][M][N]
+  float* C[G_MAXG];         // per group; ksplit == 1: the output [M][N]; else the group's slabs [ksplit][M][N]
   int M, N, K;
   long ars, aks, brs, bks;
   int kper;            // reduction indices per split (multiple of GKC)
   int ksplit;
   int tiles_m, tiles_n;
-  const float* a_amax; // device: upper bounds of max |A|, max |B|
+  const float* a_amax[G_MAXG];   // device: upper bounds of max |A_g|, max |B|
   const float* b_amax;
 };
 
@@ -77,11 +85,14 @@ __device__ __forceinline__ void load8(float* r, const float* p, long ks, bool st
   }
 }
 
-// AT / BT: the operand's ROW index is the contiguous one (reduction index strided)
-template <bool AT, bool BT, bool M16>
-__global__ __launch_bounds__(GNT, 2) void gemm_nt_f16x3_kernel(GArgs G) {
-  constexpr int BUFU = G_NP * 2 * G_PL;
-  __shared__ f32x4 lds[2 * BUFU];                      // [buffer][A planes | B planes][k-block][row]
+// AT / BT: the operand's ROW index is the contiguous one (reduction index strided); NG: groups (A_g, C_g) sharing B.
+// NG > 1: one workgroup per CU (LDS: 2 x (NG + 1) x 16.6 KB; NG accumulator sets)
+template <bool AT, bool BT, bool M16, int NG>
+__global__ __launch_bounds__(GNT, NG == 1 ? 2 : 1) void gemm_nt_f16x3_kernel(GArgs G) {
+  constexpr int NA = NG * G_NU, NUN = NA + G_NU;       // staged units per thread: [0, NA) A of group u / G_NU; then B
+  constexpr int BOFF = G_NP * NG * G_PL;               // B planes follow the groups' A planes
+  constexpr int BUFU = BOFF + G_NP * G_PL;
+  __shared__ f32x4 lds[2 * BUFU];                      // [buffer][A_0 planes | .. | A_{NG-1} planes | B planes][k-block][row]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kb = lane >> 5, l32 = lane & 31;
@@ -108,11 +119,15 @@ __global__ __launch_bounds__(GNT, 2) void gemm_nt_f16x3_kernel(GArgs G) {
   const int m0 = mt * GTM, n0 = nt * GTN;
   const int k_begin = split * G.kper, k_end = min(k_begin + G.kper, G.K);
   const int nst = (k_end - k_begin) / GKC;
-  const float a_scale = f16_scale_of(*G.a_amax), b_scale = f16_scale_of(*G.b_amax);
+  const float b_scale = f16_scale_of(*G.b_amax);
+  float a_scale[NG];
+#pragma unroll
+  for (int gi = 0; gi < NG; ++gi) a_scale[gi] = f16_scale_of(*G.a_amax[gi]);
 
   // ---- staging map: unit (row, k-block) -> thread.  Reduction contiguous: 4 consecutive lanes cover the 32 indices
   // (128 B) of a row; row contiguous: consecutive lanes = consecutive rows, the unit's 8 indices a k-stride apart.
-  const float* up[2 * G_NU];      // units [0, G_NU): A; [G_NU, 2 G_NU): B
+  // the groups' A units share one map (same M and strides): slots [0, G_NU) describe A, [G_NU, 2 G_NU) B
+  size_t u_off[2 * G_NU];
   int u_dst[2 * G_NU];
   bool u_ok[2 * G_NU];
 #pragma unroll
@@ -123,65 +138,81 @@ __global__ __launch_bounds__(GNT, 2) void gemm_nt_f16x3_kernel(GArgs G) {
     const int r0 = isb ? n0 : m0, rmax = isb ? G.N : G.M;
     const long rs = isb ? G.brs : G.ars, ks = isb ? G.bks : G.aks;
     u_ok[u] = (r0 + row) < rmax;
-    up[u] = (isb ? G.B : G.A) + (size_t)min(r0 + row, rmax - 1) * rs + (size_t)(k_begin + kblk * 8) * ks;
-    u_dst[u] = (isb ? G_NP * G_PL : 0) + kblk * G_KB + row;
+    u_off[u] = (size_t)min(r0 + row, rmax - 1) * rs + (size_t)(k_begin + kblk * 8) * ks;
+    u_dst[u] = kblk * G_KB + row;
   }
 
-  float rg[G_PD][2 * G_NU][8];
+  float rg[G_PD][NUN][8];
   auto load_stage = [&](int slot, int st) {            // st: stage index within this split
 #pragma unroll
-    for (int u = 0; u < 2 * G_NU; ++u)
-      load8(rg[slot][u], up[u] + (size_t)st * GKC * (u >= G_NU ? G.bks : G.aks), u >= G_NU ? G.bks : G.aks, u >= G_NU ? BT : AT);
+    for (int u = 0; u < NUN; ++u) {
+      const bool isb = u >= NA;
+      const float* p = (isb ? G.B : G.A[isb ? 0 : u / G_NU]) + u_off[isb ? G_NU + (u - NA) : u % G_NU];
+      load8(rg[slot][u], p + (size_t)st * GKC * (isb ? G.bks : G.aks), isb ? G.bks : G.aks, isb ? BT : AT);
+    }
   };
   // one staged unit: scale, split into hi / lo, two LDS units
   auto piece = [&](int slot, int u, f32x4* base) {
     float* v = rg[slot][u];
+    const bool isb = u >= NA;
+    const int m = isb ? G_NU + (u - NA) : u % G_NU;
     // rows beyond M / N (clamped re-reads of the last row) are multiplied by zero: they only ever meet output rows /
     // columns that are not stored
-    const float sc = u_ok[u] ? (u >= G_NU ? b_scale : a_scale) : 0.f;
+    const float sc = u_ok[m] ? (isb ? b_scale : a_scale[isb ? 0 : u / G_NU]) : 0.f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] *= sc;
     f32x4 pl[G_NP];
     split_planes16<G_NP, true>(v, pl);
-    base[u_dst[u]] = pl[0];
-    base[u_dst[u] + G_PL] = pl[1];
+    const int dst = u_dst[m] + (isb ? BOFF : (u / G_NU) * G_NP * G_PL);
+    base[dst] = pl[0];
+    base[dst + G_PL] = pl[1];
   };
-  auto read_frags = [&](bf16x8 (&av)[2][G_NP], bf16x8 (&bv)[G_HN][G_NP], const f32x4* base, int s2) {
+  auto read_a = [&](bf16x8 (&av)[2][G_NP], const f32x4* base, int gi, int s2) {
 #pragma unroll
-    for (int p = 0; p < G_NP; ++p) {
+    for (int p = 0; p < G_NP; ++p)
 #pragma unroll
       for (int g = 0; g < 2; ++g)
-        av[g][p] = __builtin_bit_cast(bf16x8, base[p * G_PL + (2 * s2 + kb) * G_KB + wm * 64 + g * 32 + l32]);
+        av[g][p] = __builtin_bit_cast(bf16x8, base[(gi * G_NP + p) * G_PL + (2 * s2 + kb) * G_KB + wm * 64 + g * 32 + l32]);
+  };
+  auto read_b = [&](bf16x8 (&bv)[G_HN][G_NP], const f32x4* base, int s2) {
+#pragma unroll
+    for (int p = 0; p < G_NP; ++p)
 #pragma unroll
       for (int h = 0; h < G_HN; ++h)
-        bv[h][p] = __builtin_bit_cast(bf16x8, base[(G_NP + p) * G_PL + (2 * s2 + kb) * G_KB + wcol + h * 32 + l32]);
-    }
+        bv[h][p] = __builtin_bit_cast(bf16x8, base[BOFF + p * G_PL + (2 * s2 + kb) * G_KB + wcol + h * 32 + l32]);
   };
 
-  f32x16 acc[2][G_HN];
+  f32x16 acc[NG][2][G_HN];
 #pragma unroll
-  for (int g = 0; g < 2; ++g)
+  for (int gi = 0; gi < NG; ++gi)
 #pragma unroll
-    for (int h = 0; h < G_HN; ++h)
+    for (int g = 0; g < 2; ++g)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[g][h][r] = 0.f;
+      for (int h = 0; h < G_HN; ++h)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[gi][g][h][r] = 0.f;
   // 16x16x32 form: 4 row blocks x 2 G_HN column blocks of 16 x 16, lane = (k-group q, index l16 within the block)
   const int q16 = lane >> 4, l16 = lane & 15;
-  f32x4 acc4[4][2 * G_HN];
+  f32x4 acc4[NG][4][2 * G_HN];
 #pragma unroll
-  for (int g = 0; g < 4; ++g)
+  for (int gi = 0; gi < NG; ++gi)
 #pragma unroll
-    for (int h = 0; h < 2 * G_HN; ++h) acc4[g][h] = f32x4{0.f, 0.f, 0.f, 0.f};
-  auto read_frags16 = [&](bf16x8 (&xa)[4][G_NP], bf16x8 (&xb)[2 * G_HN][G_NP], const f32x4* base) {
+    for (int g = 0; g < 4; ++g)
 #pragma unroll
-    for (int p = 0; p < G_NP; ++p) {
+      for (int h = 0; h < 2 * G_HN; ++h) acc4[gi][g][h] = f32x4{0.f, 0.f, 0.f, 0.f};
+  auto read_a16 = [&](bf16x8 (&xa)[4][G_NP], const f32x4* base, int gi) {
+#pragma unroll
+    for (int p = 0; p < G_NP; ++p)
 #pragma unroll
       for (int g = 0; g < 4; ++g)
-        xa[g][p] = __builtin_bit_cast(bf16x8, base[p * G_PL + q16 * G_KB + wm * 64 + g * 16 + l16]);
+        xa[g][p] = __builtin_bit_cast(bf16x8, base[(gi * G_NP + p) * G_PL + q16 * G_KB + wm * 64 + g * 16 + l16]);
+  };
+  auto read_b16 = [&](bf16x8 (&xb)[2 * G_HN][G_NP], const f32x4* base) {
+#pragma unroll
+    for (int p = 0; p < G_NP; ++p)
 #pragma unroll
       for (int h = 0; h < 2 * G_HN; ++h)
-        xb[h][p] = __builtin_bit_cast(bf16x8, base[(G_NP + p) * G_PL + q16 * G_KB + wcol + h * 16 + l16]);
-    }
+        xb[h][p] = __builtin_bit_cast(bf16x8, base[BOFF + p * G_PL + q16 * G_KB + wcol + h * 16 + l16]);
   };
 
   if (nst > 0) {
@@ -189,10 +220,12 @@ __global__ __launch_bounds__(GNT, 2) void gemm_nt_f16x3_kernel(GArgs G) {
 #pragma unroll
     for (int j = 0; j < G_PD; ++j) load_stage(j, min(j, nst - 1));
 #pragma unroll
-    for (int u = 0; u < 2 * G_NU; ++u) piece(0, u, lds);
+    for (int u = 0; u < NUN; ++u) piece(0, u, lds);
     __syncthreads();
-    // One stage: 6 groups of 2 MFMAs (2 steps of 16 x the 3 plane products); the split of stage st + 1 (2 units) rides
-    // on the first two groups, the second step's fragments are read during the first step's second group.  `j`: the
+    // One stage: per group 6 batches of 2 MFMAs (2 steps of 16 x the 3 plane products), ordered step, group, product:
+    // the B fragments of a step serve every group.  The split of stage st + 1 (NG + 1 units) rides on the first
+    // batches, one unit each; the A fragments of the next (step, group) -- and the B fragments of the next step -- are
+    // read during the second batch of the one before.  `j`: the
     // register slot that held stage st (compile-time: the loop below is unrolled by G_PD with no branch inside -- with
     // a per-stage `if (st < nst)` hipcc's vmcnt bookkeeping lost track across the joins and drained every load in
     // front of the next stage's address arithmetic).
@@ -204,48 +237,60 @@ __global__ __launch_bounds__(GNT, 2) void gemm_nt_f16x3_kernel(GArgs G) {
       load_stage(j, min(st + G_PD, nst - 1));        // slot j held stage st: split during stage st - 1
       if constexpr (M16) {
       bf16x8 xa[4][G_NP], xb[2 * G_HN][G_NP];
-      read_frags16(xa, xb, base);
-      __builtin_amdgcn_sched_barrier(0);
+      read_b16(xb, base);
       int grp16 = 0;
+#pragma unroll
+      for (int gi = 0; gi < NG; ++gi) {
+      read_a16(xa, base, gi);
+      __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int sum = G_NP - 1; sum >= 0; --sum)
 #pragma unroll
-        for (int pa = sum; pa >= 0; --pa) {           // 3 groups of 8 G_HN MFMAs, the split of stage st + 1 rides on them
+        for (int pa = sum; pa >= 0; --pa) {           // 3 batches of 8 G_HN MFMAs per group, the split of stage st + 1 rides on them
 #pragma unroll
           for (int g = 0; g < 4; ++g)
 #pragma unroll
             for (int h = 0; h < 2 * G_HN; ++h)
-              acc4[g][h] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, xb[h][sum - pa]),
-                                                                 __builtin_bit_cast(f16x8, xa[g][pa]), acc4[g][h], 0, 0, 0);
+              acc4[gi][g][h] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, xb[h][sum - pa]),
+                                                                     __builtin_bit_cast(f16x8, xa[g][pa]), acc4[gi][g][h], 0, 0, 0);
 #pragma unroll
-          for (int u = grp16; u < 2 * G_NU; u += 3) piece((j + 1) % G_PD, u, nxt);
+          for (int u = grp16; u < NUN; u += 3 * NG) piece((j + 1) % G_PD, u, nxt);
           __builtin_amdgcn_sched_barrier(0);
           ++grp16;
         }
+      }
       __syncthreads();
       return;
       }
-      bf16x8 av0[2][G_NP], bv0[G_HN][G_NP], av1[2][G_NP], bv1[G_HN][G_NP];
-      read_frags(av0, bv0, base, 0);
+      bf16x8 av[2][2][G_NP], bv[2][G_HN][G_NP];      // A: [parity of (step, group)], B: [step]
+      read_a(av[0], base, 0, 0);
+      read_b(bv[0], base, 0);
       __builtin_amdgcn_sched_barrier(0);
       int grp = 0;
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
-        for (int sum = G_NP - 1; sum >= 0; --sum)
+        for (int gi = 0; gi < NG; ++gi) {
+          const int sg = s2 * NG + gi, cur = sg & 1;
+          int sub = 0;
 #pragma unroll
-          for (int pa = sum; pa >= 0; --pa) {
+          for (int sum = G_NP - 1; sum >= 0; --sum)
 #pragma unroll
-            for (int g = 0; g < 2; ++g)
+            for (int pa = sum; pa >= 0; --pa) {
 #pragma unroll
-              for (int h = 0; h < G_HN; ++h)
-                acc[g][h] = s2 == 0 ? mfma_split16<true>(av0[g][pa], bv0[h][sum - pa], acc[g][h])
-                                    : mfma_split16<true>(av1[g][pa], bv1[h][sum - pa], acc[g][h]);
-            if (grp < 2 * G_NU) piece((j + 1) % G_PD, grp, nxt);
-            if (grp == 1) read_frags(av1, bv1, base, 1);
-            __builtin_amdgcn_sched_barrier(0);
-            ++grp;
-          }
+              for (int g = 0; g < 2; ++g)
+#pragma unroll
+                for (int h = 0; h < G_HN; ++h)
+                  acc[gi][g][h] = mfma_split16<true>(av[cur][g][pa], bv[s2][h][sum - pa], acc[gi][g][h]);
+              if (grp < NUN) piece((j + 1) % G_PD, grp, nxt);
+              if (sub == 1 && sg + 1 < 2 * NG) {
+                read_a(av[cur ^ 1], base, (sg + 1) % NG, (sg + 1) / NG);
+                if (gi == NG - 1) read_b(bv[1], base, 1);
+              }
+              __builtin_amdgcn_sched_barrier(0);
+              ++grp, ++sub;
+            }
+        }
       __syncthreads();
     };
     int st = 0;
@@ -260,8 +305,11 @@ __global__ __launch_bounds__(GNT, 2) void gemm_nt_f16x3_kernel(GArgs G) {
   }
 
   // ---- epilogue: undo the two scales (exact), C (or this split's slab) row-major [M][N]; the bias goes in with split 0
-  const float ua = f16_unscale_of(*G.a_amax), ub = f16_unscale_of(*G.b_amax);
-  float* out = G.C + (G.ksplit > 1 ? (size_t)split * G.M * G.N : 0);
+  const float ub = f16_unscale_of(*G.b_amax);
+#pragma unroll
+  for (int gi = 0; gi < NG; ++gi) {
+  const float ua = f16_unscale_of(*G.a_amax[gi]);
+  float* out = G.C[gi] + (G.ksplit > 1 ? (size_t)split * G.M * G.N : 0);
   if constexpr (M16) {
     const bool vec = (G.N & 3) == 0;
 #pragma unroll
@@ -276,7 +324,7 @@ __global__ __launch_bounds__(GNT, 2) void gemm_nt_f16x3_kernel(GArgs G) {
         if (m >= G.M) continue;
         f32x4 v;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = acc4[g][h][r] * ua * ub + bvv[r];
+        for (int r = 0; r < 4; ++r) v[r] = acc4[gi][g][h][r] * ua * ub + bvv[r];
         float* o = out + (size_t)m * G.N + n;
         if (vec && n + 3 < G.N) *reinterpret_cast<f32x4*>(o) = v;
         else {
@@ -286,7 +334,7 @@ __global__ __launch_bounds__(GNT, 2) void gemm_nt_f16x3_kernel(GArgs G) {
         }
       }
     }
-    return;
+    continue;
   }
 #pragma unroll
   for (int h = 0; h < G_HN; ++h) {
@@ -297,8 +345,9 @@ __global__ __launch_bounds__(GNT, 2) void gemm_nt_f16x3_kernel(GArgs G) {
 #pragma unroll
       for (int r16 = 0; r16 < 16; ++r16) {
         const int m = m0 + wm * 64 + g * 32 + acc_row(r16, lane);
-        if (m < G.M && n < G.N) out[(size_t)m * G.N + n] = acc[g][h][r16] * ua * ub + bvv;
+        if (m < G.M && n < G.N) out[(size_t)m * G.N + n] = acc[gi][g][h][r16] * ua * ub + bvv;
       }
+  }
   }
 }
 
@@ -318,6 +367,66 @@ bool gemm_ok(int M, int N, int K, long ars, long aks, long brs, long bks) {
   return true;
 }
 
+// ng groups (A[g], C[g], a_amax[g]) against one B; the single call is ng == 1
+int gemm_launch(int ng, const float* const* A, const float* B, const float* bias, float* const* C, int M, int N, int K,
+                long a_row_stride, long a_k_stride, long b_row_stride, long b_k_stride, const float* const* a_amax,
+                const float* b_amax, void* workspace, size_t workspace_bytes, void* stream) {
+  if (ng < 1 || ng > G_MAXG || !A || !B || !C || !a_amax || !b_amax) return VG_ERR_BAD_ARG;
+  for (int g = 0; g < ng; ++g)
+    if (!A[g] || !C[g] || !a_amax[g]) return VG_ERR_BAD_ARG;
+  if (!gemm_ok(M, N, K, a_row_stride, a_k_stride, b_row_stride, b_k_stride)) return VG_ERR_BAD_ARG;
+  for (int g = 0; g < ng; ++g)
+    if (a_k_stride == 1 && ((uintptr_t)A[g] & 15)) return VG_ERR_BAD_ARG;
+  if (b_k_stride == 1 && ((uintptr_t)B & 15)) return VG_ERR_BAD_ARG;
+  const int ks = gemm_ksplit(M, N, K);
+  const size_t slabs = (size_t)ks * M * N;               // floats per group
+  if (ks > 1 && (!workspace || workspace_bytes < ng * slabs * sizeof(float))) return VG_ERR_WORKSPACE;
+  if ((size_t)M * N > 0x7fffffffUL) return VG_ERR_BAD_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  GArgs G = {};
+  for (int g = 0; g < ng; ++g) {
+    G.A[g] = A[g];
+    G.C[g] = ks > 1 ? (float*)workspace + g * slabs : C[g];
+    G.a_amax[g] = a_amax[g];
+  }
+  G.B = B; G.bias = bias;
+  G.M = M; G.N = N; G.K = K;
+  G.ars = a_row_stride; G.aks = a_k_stride; G.brs = b_row_stride; G.bks = b_k_stride;
+  G.kper = K / ks; G.ksplit = ks;
+  G.tiles_m = cdiv(M, GTM); G.tiles_n = cdiv(N, GTN);
+  G.b_amax = b_amax;
+  const long grid = (long)G.tiles_m * G.tiles_n * ks;
+  if (grid > 0x7fffffffL) return VG_ERR_BAD_ARG;
+  const bool at = a_k_stride != 1, bt = b_k_stride != 1;
+  const dim3 g((unsigned)grid), b(GNT);
+  const bool m16 = G_M16 == 1 || (G_M16 == 2 && grid <= 512);
+#define VG_GEMM_LAUNCH_NG(AT_, BT_, NG_)                                                                      \
+  do {                                                                                                        \
+    if (m16) hipLaunchKernelGGL((gemm_nt_f16x3_kernel<AT_, BT_, G_M16 != 0, NG_>), g, b, 0, st, G);           \
+    else hipLaunchKernelGGL((gemm_nt_f16x3_kernel<AT_, BT_, false, NG_>), g, b, 0, st, G);                    \
+  } while (0)
+#define VG_GEMM_LAUNCH(AT_, BT_)                                                                              \
+  do {                                                                                                        \
+    if (ng == 1) VG_GEMM_LAUNCH_NG(AT_, BT_, 1);                                                              \
+    else if (ng == 2) VG_GEMM_LAUNCH_NG(AT_, BT_, 2);                                                         \
+    else VG_GEMM_LAUNCH_NG(AT_, BT_, 3);                                                                      \
+  } while (0)
+  if (at && bt) VG_GEMM_LAUNCH(true, true);
+  else if (at) VG_GEMM_LAUNCH(true, false);
+  else if (bt) VG_GEMM_LAUNCH(false, true);
+  else VG_GEMM_LAUNCH(false, false);
+#undef VG_GEMM_LAUNCH
+#undef VG_GEMM_LAUNCH_NG
+  static_assert(G_MAXG == 3, "dispatch above");
+  VG_CHECK_LAUNCH();
+  if (ks > 1)                                            // fixed-order sum of each group's slabs
+    for (int gi = 0; gi < ng; ++gi) {
+      const int rc = vg_internal_wgrad_reduce((const float*)workspace + gi * slabs, C[gi], M * N, ks, st);
+      if (rc) return rc;
+    }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" size_t vg_gemm_nt_f16x3_workspace_bytes(int M, int N, int K) {
@@ -330,36 +439,20 @@ extern "C" int vg_gemm_nt_f16x3(const float* A, const float* B, const float* bia
                                 long a_row_stride, long a_k_stride, long b_row_stride, long b_k_stride,
                                 const float* a_amax, const float* b_amax, void* workspace, size_t workspace_bytes,
                                 void* stream) {
-  if (!A || !B || !C || !a_amax || !b_amax) return VG_ERR_BAD_ARG;
-  if (!gemm_ok(M, N, K, a_row_stride, a_k_stride, b_row_stride, b_k_stride)) return VG_ERR_BAD_ARG;
-  if ((a_k_stride == 1 && ((uintptr_t)A & 15)) || (b_k_stride == 1 && ((uintptr_t)B & 15))) return VG_ERR_BAD_ARG;
-  const int ks = gemm_ksplit(M, N, K);
-  if (ks > 1 && (!workspace || workspace_bytes < (size_t)ks * M * N * sizeof(float))) return VG_ERR_WORKSPACE;
-  if ((size_t)M * N > 0x7fffffffUL) return VG_ERR_BAD_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  GArgs G;
-  G.A = A; G.B = B; G.bias = bias; G.C = ks > 1 ? (float*)workspace : C;
-  G.M = M; G.N = N; G.K = K;
-  G.ars = a_row_stride; G.aks = a_k_stride; G.brs = b_row_stride; G.bks = b_k_stride;
-  G.kper = K / ks; G.ksplit = ks;
-  G.tiles_m = cdiv(M, GTM); G.tiles_n = cdiv(N, GTN);
-  G.a_amax = a_amax; G.b_amax = b_amax;
-  const long grid = (long)G.tiles_m * G.tiles_n * ks;
-  if (grid > 0x7fffffffL) return VG_ERR_BAD_ARG;
-  const bool at = a_k_stride != 1, bt = b_k_stride != 1;
-  const dim3 g((unsigned)grid), b(GNT);
-  const bool m16 = G_M16 == 1 || (G_M16 == 2 && grid <= 512);
-#define VG_GEMM_LAUNCH(AT_, BT_)                                                                              \
-  do {                                                                                                        \
-    if (m16) hipLaunchKernelGGL((gemm_nt_f16x3_kernel<AT_, BT_, true>), g, b, 0, st, G);                      \
-    else hipLaunchKernelGGL((gemm_nt_f16x3_kernel<AT_, BT_, false>), g, b, 0, st, G);                         \
-  } while (0)
-  if (at && bt) VG_GEMM_LAUNCH(true, true);
-  else if (at) VG_GEMM_LAUNCH(true, false);
-  else if (bt) VG_GEMM_LAUNCH(false, true);
-  else VG_GEMM_LAUNCH(false, false);
-#undef VG_GEMM_LAUNCH
-  VG_CHECK_LAUNCH();
-  if (ks > 1) return vg_internal_wgrad_reduce((const float*)workspace, C, M * N, ks, st);   // fixed-order sum of the slabs
-  return 0;
+  if (!A || !C || !a_amax) return VG_ERR_BAD_ARG;
+  return gemm_launch(1, &A, B, bias, &C, M, N, K, a_row_stride, a_k_stride, b_row_stride, b_k_stride, &a_amax, b_amax,
+                     workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t vg_gemm_nt_f16x3_grouped_workspace_bytes(int groups, int M, int N, int K) {
+  if (groups < 1 || groups > G_MAXG) return 0;
+  return groups * vg_gemm_nt_f16x3_workspace_bytes(M, N, K);
+}
+
+extern "C" int vg_gemm_nt_f16x3_grouped(int groups, const float* const* A, const float* B, const float* bias,
+                                        float* const* C, int M, int N, int K, long a_row_stride, long a_k_stride,
+                                        long b_row_stride, long b_k_stride, const float* const* a_amax,
+                                        const float* b_amax, void* workspace, size_t workspace_bytes, void* stream) {
+  return gemm_launch(groups, A, B, bias, C, M, N, K, a_row_stride, a_k_stride, b_row_stride, b_k_stride, a_amax, b_amax,
+                     workspace, workspace_bytes, stream);
 }

@@ -161,6 +161,31 @@ DEFER_MIN_WEIGHTS = 1 << 20
 DEFER_WGRAD = os.environ.get("VG_DEFER_WGRAD", "1") != "0"      # 0: deferred_wgrad() does nothing
 
 
+def _linear_weight_grad(acc, defer, w, gy, x):
+    """The weight gradient of one pass (gy, x) of a Linear layer under both protocols -- `deferred_wgrad` (``defer``: the
+    context the pass was made in, or None) and `accumulate_param_grads` (``acc``).  Returns what the pass hands autograd:
+    the gradient, or None when a later pass computes it for all or it was added into an earlier pass's tensor."""
+    wg, wx = gy, x                                   # what the weight gradient is taken over
+    d, k = defer, id(w)
+    if d is not None and d.open and d.pending.get(k, 0) > 0:
+        d.stash.setdefault(k, []).append((gy, x))
+        d.pending[k] -= 1
+        if d.pending[k] > 0:
+            return None                              # a later pass of this layer does it for all
+        pairs = d.stash.pop(k)
+        if len(pairs) > 1:
+            wg, wx = torch.cat([p[0] for p in pairs]), torch.cat([p[1] for p in pairs])
+    slot = _grad_slot(acc, id(w))
+    split = ops.linear_split_ok(wg.shape[0], w.numel())
+    if slot.prev is None:
+        return slot.hand_over(ops.linear_wgrad(wg, wx) if split else wg.t() @ wx)
+    if split:
+        slot.prev.add_(ops.linear_wgrad(wg, wx))
+    else:
+        slot.prev.addmm_(wg.t(), wx)                 # the layer's second use: added in the GEMM's epilogue
+    return None
+
+
 class LinearFn(Function):
     """nn.Linear (model.py:460-471, 402-408, 490-492).  Layers with >= 2^20 weights run on this package's fp16x3 GEMM
     under the default arithmetic (ops.linear_*; a GEMM whose reduction length is not a multiple of 32 -- the weight
@@ -192,27 +217,56 @@ class LinearFn(Function):
         if ctx.needs_input_grad[2] and ctx.bias_grad != BIAS_GRAD_ZERO:      # (a bias that feeds a BatchNorm1d: no gradient)
             gb = gy.sum(0)
         if ctx.needs_input_grad[1]:
-            wg, wx = gy, x                                   # what the weight gradient is taken over
-            d, k = ctx.defer, id(w)
-            if d is not None and d.open and d.pending.get(k, 0) > 0:
-                d.stash.setdefault(k, []).append((gy, x))
-                d.pending[k] -= 1
-                if d.pending[k] > 0:
-                    wg = None                                # a later pass of this layer does it for all
-                else:
-                    pairs = d.stash.pop(k)
-                    if len(pairs) > 1:
-                        wg, wx = torch.cat([p[0] for p in pairs]), torch.cat([p[1] for p in pairs])
-            if wg is not None:
-                slot = _grad_slot(ctx.acc, id(w))
-                split = ops.linear_split_ok(wg.shape[0], w.numel())
-                if slot.prev is None:
-                    gw = slot.hand_over(ops.linear_wgrad(wg, wx) if split else wg.t() @ wx)
-                elif split:
-                    slot.prev.add_(ops.linear_wgrad(wg, wx))
-                else:
-                    slot.prev.addmm_(wg.t(), wx)             # the layer's second use: added in the GEMM's epilogue
+            gw = _linear_weight_grad(ctx.acc, ctx.defer, w, gy, x)
         return gx, gw, gb, None
+
+
+class LinearGroupedFn(Function):
+    """`LinearFn` for G = 1..3 inputs through the SAME layer in one node: one grouped forward GEMM and one grouped
+    data-gradient GEMM (ops.linear_*_grouped: the weight is streamed and split once for all groups), so the layer must be
+    one `ops.linear_split_ok` takes.  Every output, input gradient and parameter gradient is bit for bit what G
+    `LinearFn` calls in the same order give: the groups are independent rows of the GEMMs, and the parameter gradients
+    go through the same protocols pass by pass, last group first -- the order in which autograd runs the G nodes.
+    ``detached[g]``: group g is a pass made under ``no_grad`` -- its output is not differentiable and the pass takes no
+    part in the backward.  apply(w, bias, bias_grad, detached, *xs) -> G outputs."""
+
+    @staticmethod
+    def forward(ctx, w, bias, bias_grad, detached, *xs):
+        live = [g for g in range(len(xs)) if not detached[g]]
+        ctx.save_for_backward(w, *(xs[g] for g in live))
+        ctx.bias_grad, ctx.live, ctx.ngroups = bias_grad, live, len(xs)
+        ctx.acc = _acc_ctx()
+        dctx = getattr(_defer_tls, "current", None)
+        ctx.defer = dctx if (dctx is not None and ctx.needs_input_grad[0] and w.numel() >= DEFER_MIN_WEIGHTS) else None
+        if ctx.defer is not None:
+            dctx.pending[id(w)] = dctx.pending.get(id(w), 0) + len(live)
+        ctx.set_materialize_grads(False)
+        ys = ops.linear_fwd_grouped(list(xs), w, bias)
+        ctx.mark_non_differentiable(*(ys[g] for g in range(len(xs)) if detached[g]))
+        return tuple(ys)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *gys):
+        w, *xs = ctx.saved_tensors
+        gxs = [None] * ctx.ngroups
+        gw = gb = None
+        passes = []                                      # (group, gy, x) of the passes that got a gradient
+        for g, x in zip(ctx.live, xs):
+            if gys[g] is not None:
+                passes.append((g, gys[g].contiguous(), x))
+        want = [p for p in passes if ctx.needs_input_grad[4 + p[0]]]
+        if want:
+            for p, gx in zip(want, ops.linear_dgrad_grouped([p[1] for p in want], w)):
+                gxs[p[0]] = gx
+        for g, gy, x in reversed(passes):
+            if ctx.needs_input_grad[1] and ctx.bias_grad != BIAS_GRAD_ZERO:
+                gb = gy.sum(0) if gb is None else gb.add_(gy.sum(0))
+            if ctx.needs_input_grad[0]:
+                one = _linear_weight_grad(ctx.acc, ctx.defer, w, gy, x)
+                if one is not None:
+                    gw = one if gw is None else gw.add_(one)
+        return (gw, gb, None, None, *gxs)
 
 
 def _bn_backward(ctx, gy, x, gamma, beta, mean, invstd, need_p):
@@ -463,6 +517,22 @@ def conv_transpose5x5(x, w, bias, stride, bias_grad=BIAS_GRAD_COMPUTE):
 
 def linear(x, w, bias, bias_grad=BIAS_GRAD_COMPUTE):
     return LinearFn.apply(x.contiguous(), w, bias, bias_grad)
+
+
+def linear_grouped(xs, w, bias, bias_grad=BIAS_GRAD_COMPUTE, detached=None):
+    """[linear(x, w, bias) for x in xs] with the weight read once (LinearGroupedFn) where the layer runs on this package's
+    GEMM and there are 2..3 inputs of one shape; pass by pass otherwise.  ``detached[g]``: pass g is made under no_grad."""
+    detached = tuple(bool(d) for d in detached) if detached is not None else (False,) * len(xs)
+    xs = [x.contiguous() for x in xs]
+    grouped = (2 <= len(xs) <= ops.GEMM_MAX_GROUPS and all(x.dim() == 2 and x.shape == xs[0].shape for x in xs)
+               and ops.linear_split_ok(xs[0].shape[1], w.numel()) and ops.linear_split_ok(w.shape[0], w.numel()))
+    if grouped:
+        return list(LinearGroupedFn.apply(w, bias, bias_grad, detached, *xs))
+    outs = []
+    for x, det in zip(xs, detached):
+        with torch.set_grad_enabled(torch.is_grad_enabled() and not det):
+            outs.append(LinearFn.apply(x, w, bias, bias_grad))
+    return outs
 
 
 def batch_norm_act(x, gamma, beta, running_mean, running_var, eps=1e-5, momentum=0.1, act=ops.ACT_NONE, stats=None):

@@ -183,6 +183,9 @@ FUSE_CONV_BN = True
 # The discriminator's head + BCE as one kernel each way (Discriminator_celeba.forward_with_bce); False /
 # VG_FUSE_HEAD=0: Linear, Sigmoid and the BCE kernel one after the other (A/B timing, tests).
 FUSE_HEAD_BCE = __import__("os").environ.get("VG_FUSE_HEAD", "1") != "0"
+# The discriminator's passes of one phase share ONE launch of the big Linear layer's forward GEMM and one of its data
+# gradient (Discriminator_celeba.features_grouped); False / VG_GROUP_PASSES=0: one launch per pass (same bits; A/B, tests).
+GROUP_PASSES = __import__("os").environ.get("VG_GROUP_PASSES", "1") != "0"
 
 
 def _has_hooks(mods):
@@ -356,19 +359,48 @@ class Discriminator_celeba(nn.Module):
         p = self.sigmoid_output(feat)
         return p.squeeze(), feat.squeeze()
 
-    def forward_with_bce(self, x, label, divisor=None):
-        """``forward`` plus ``nn.BCELoss()(p, full(label))`` (new_betavaegan.py:101,118,153-154; ``divisor``: the batch the
-        mean runs over -- the global batch under data parallelism) with the head -- Linear(2048 -> 1) + Sigmoid -- and the
-        loss in ONE kernel each way (SURVEY K11).  Returns (p, features, bce)."""
-        bs = x.size(0)
-        c = self.convs(x)
-        feat = self.lth_features(ops.keep_amax(c, c.view(bs, -1)))
+    def _features_of(self, x, no_grad=False):
+        with torch.set_grad_enabled(torch.is_grad_enabled() and not no_grad):
+            c = self.convs(x)
+            return ops.keep_amax(c, c.view(x.size(0), -1))
+
+    def features_grouped(self, xs, no_grad=None):
+        """``lth_features`` of 2..3 batches of one shape, the passes of one phase over unchanged weights: the convolution
+        / BatchNorm trunk runs per input in the order given (batch statistics and running averages update pass by pass as
+        in separate calls), then the 16384 -> 2048 Linear layer runs ONCE for all (functional.linear_grouped: its 134 MB
+        weight is streamed and split once instead of once per pass), then the LeakyReLU per pass.  ``no_grad[i]``: pass i
+        is made as under ``torch.no_grad()``.  Every result is bit for bit that of ``self.lth_features(trunk(x))``.
+        Falls back to pass by pass (GROUP_PASSES off, a hooked layer, a Linear layer the package's GEMM does not take)."""
+        no_grad = tuple(no_grad) if no_grad is not None else (False,) * len(xs)
+        lin, act = self.lth_features[0], self.lth_features[1]
+        hooked = _has_hooks([self.lth_features, lin, act])
+        nw = lin.weight.numel()
+        takes = (2 <= len(xs) <= ops.GEMM_MAX_GROUPS and all(x.is_cuda and x.shape == xs[0].shape for x in xs)
+                 and ops.linear_split_ok(lin.in_features, nw) and ops.linear_split_ok(lin.out_features, nw))
+        if not GROUP_PASSES or hooked or not takes:
+            feats = []
+            for x, ng in zip(xs, no_grad):
+                with torch.set_grad_enabled(torch.is_grad_enabled() and not ng):
+                    feats.append(self.lth_features(self._features_of(x)))
+            return feats
+        cs = [self._features_of(x, ng) for x, ng in zip(xs, no_grad)]
+        ys = F.linear_grouped(cs, lin.weight, lin.bias, F.BIAS_GRAD_COMPUTE, no_grad)
+        return [act(y) for y in ys]
+
+    def head_with_bce(self, feat, label, divisor=None):
+        """The head of `forward_with_bce` on features already computed (`features_grouped`): (p, features, bce)."""
         lin = self.sigmoid_output[0]
         if not FUSE_HEAD_BCE or lin._forward_hooks or lin._forward_pre_hooks or self.sigmoid_output[1]._forward_hooks:
             p = self.sigmoid_output(feat).squeeze()              # hooked head: module by module
             return p, feat.squeeze(), F.bce_loss(p, label, divisor)
         p, bce = F.dot_sigmoid_bce(feat, lin.weight, lin.bias, label, divisor)
         return p, feat.squeeze(), bce
+
+    def forward_with_bce(self, x, label, divisor=None):
+        """``forward`` plus ``nn.BCELoss()(p, full(label))`` (new_betavaegan.py:101,118,153-154; ``divisor``: the batch the
+        mean runs over -- the global batch under data parallelism) with the head -- Linear(2048 -> 1) + Sigmoid -- and the
+        loss in ONE kernel each way (SURVEY K11).  Returns (p, features, bce)."""
+        return self.head_with_bce(self.lth_features(self._features_of(x)), label, divisor)
 
 
 class VAE(nn.Module, _DecoderMixin):

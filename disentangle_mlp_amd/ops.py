@@ -763,6 +763,51 @@ def linear_dgrad(gy, w):
     return _gemm_nt(gy, w, None, gx, M, K, N, N, 1, 1, K, amax_of(gy), weight_bound(w))
 
 
+GEMM_MAX_GROUPS = 3      # VG_GEMM_MAX_GROUPS of include/vaegan_hip.h
+
+
+def _gemm_nt_grouped(As, B, bias, Cs, M, N, K, ars, aks, brs, bks, a_amaxes, b_amax):
+    """vg_gemm_nt_f16x3_grouped: every Cs[g] = As[g] B^T (+ bias), bit for bit `_gemm_nt` on As[g], with B read once."""
+    lib = _lib.load()
+    G = len(As)
+    if not 1 <= G <= GEMM_MAX_GROUPS:
+        raise RuntimeError(f"grouped Linear GEMM: 1..{GEMM_MAX_GROUPS} groups, got {G}")
+    need = lib.vg_gemm_nt_f16x3_grouped_workspace_bytes(G, M, N, K)
+    ws = workspace(need, B.device) if need else None
+    ptrs = ctypes.c_void_p * G
+    check(lib.vg_gemm_nt_f16x3_grouped(G, ptrs(*(a.data_ptr() for a in As)), B.data_ptr(), _ptr(bias),
+                                       ptrs(*(c.data_ptr() for c in Cs)), M, N, K, ars, aks, brs, bks,
+                                       ptrs(*(a.data_ptr() for a in a_amaxes)), b_amax.data_ptr(), _ptr(ws),
+                                       ws.numel() if need else 0, _stream()), "vg_gemm_nt_f16x3_grouped")
+    return Cs
+
+
+def _req_group(ts, name):
+    for t in ts:
+        _req(t, name)
+        if t.shape != ts[0].shape:
+            raise RuntimeError(f"grouped Linear GEMM: every {name} of a group call has the same shape")
+
+
+def linear_fwd_grouped(xs, w, bias):
+    """`linear_fwd` for 1..3 inputs of one shape against the same weight, the weight streamed and split once: the passes
+    of the discriminator over unchanged weights.  Returns the list of outputs, each bit for bit `linear_fwd(x, w, bias)`."""
+    _req_group(xs, "x"), _req(w, "w")
+    M, K = xs[0].shape
+    N = w.shape[0]
+    ys = [torch.empty((M, N), dtype=torch.float32, device=w.device) for _ in xs]
+    return _gemm_nt_grouped(xs, w, bias, ys, M, N, K, K, 1, K, 1, [amax_of(x) for x in xs], weight_bound(w))
+
+
+def linear_dgrad_grouped(gys, w):
+    """`linear_dgrad` for 1..3 output gradients of one shape against the same weight (read once)."""
+    _req_group(gys, "gy"), _req(w, "w")
+    M, N = gys[0].shape
+    K = w.shape[1]
+    gxs = [torch.empty((M, K), dtype=torch.float32, device=w.device) for _ in gys]
+    return _gemm_nt_grouped(gys, w, None, gxs, M, K, N, N, 1, 1, K, [amax_of(g) for g in gys], weight_bound(w))
+
+
 def linear_wgrad(gy, x):
     """gW = gy^T x: gy (M, N), x (M, K) -> (N, K); the reduction runs over the batch M (both operands strided)."""
     _req(gy, "gy"), _req(x, "x")

@@ -720,8 +720,10 @@ class BetaVAEGANTrainer(_GraphedSteps):
         if self.probe is not None and fake.requires_grad:    # diagnostics (bench.py `regime`): such an iteration is eager
             fake.register_hook(lambda g: self.probe("grad_wrt_fake", g))
         with F.deferred_wgrad():                             # D runs twice, one backward: big Linear weight gradient once
-            p_real, _, err_real = netD.forward_with_bce(data, real_label, gb)
-            p_fake, _, err_fake = netD.forward_with_bce(fake.detach(), fake_label, gb)
+            # ... and its big Linear layer reads its weight once for both passes, forward and data gradient
+            f_real, f_fake = netD.features_grouped([data, fake.detach()])
+            p_real, _, err_real = netD.head_with_bce(f_real, real_label, gb)
+            p_fake, _, err_fake = netD.head_with_bce(f_fake, fake_label, gb)
             _backward([err_real, err_fake])
         self._exchange(self.flat_d)
         if grad_hook:
@@ -736,11 +738,13 @@ class BetaVAEGANTrainer(_GraphedSteps):
         # ---- phase 2: "decoder" -- every EG parameter moves (:127-164)
         self._zero(netEG, self.flat_eg)
         self._set_d_frozen(True)
-        with torch.no_grad():
-            _, sim_real = netD(data)                         # D fwd #3: BN statistics still update
         recon, mu, logvar = netEG(data, eps2)
-        _, _, err_g_fake = netD.forward_with_bce(fake, real_label, gb)
-        _, sim_rec, err_g_rec = netD.forward_with_bce(recon, real_label, gb)
+        # D three times on frozen weights -- on data as under no_grad (D fwd #3: BN statistics still update), on fake and
+        # on recon, in that order: the big Linear layer reads its weight once for the three
+        f_data, f_fake, f_rec = netD.features_grouped([data, fake, recon], no_grad=(True, False, False))
+        sim_real = f_data.squeeze()
+        _, _, err_g_fake = netD.head_with_bce(f_fake, real_label, gb)
+        _, sim_rec, err_g_rec = netD.head_with_bce(f_rec, real_label, gb)
         sim = F.sim_loss(sim_rec, sim_real)
         mse2 = F.reconstruction_loss(recon, data)
         _backward([err_g_fake, err_g_rec, sim, mse2])
@@ -1130,8 +1134,9 @@ class GANTrainer(_GraphedSteps):
         self._zero(self.netD, self.flat_d)
         fake = self.netG(noise)
         with F.deferred_wgrad():                             # as BetaVAEGANTrainer's discriminator phase
-            p_real, _, err_real = self.netD.forward_with_bce(data, real_label, gb)
-            p_fake, _, err_fake = self.netD.forward_with_bce(fake.detach(), fake_label, gb)
+            f_real, f_fake = self.netD.features_grouped([data, fake.detach()])
+            p_real, _, err_real = self.netD.head_with_bce(f_real, real_label, gb)
+            p_fake, _, err_fake = self.netD.head_with_bce(f_fake, fake_label, gb)
             _backward([err_real, err_fake])
         self._exchange(self.flat_d)
         if grad_hook:

@@ -226,6 +226,17 @@ size_t vg_gemm_nt_f16x3_workspace_bytes(int M, int N, int K);
 int vg_gemm_nt_f16x3(const float* A, const float* B, const float* bias, float* C, int M, int N, int K,
                      long a_row_stride, long a_k_stride, long b_row_stride, long b_k_stride,
                      const float* a_amax, const float* b_amax, void* workspace, size_t workspace_bytes, void* stream);
+/* Grouped form: 1 <= groups <= VG_GEMM_MAX_GROUPS activations against ONE B (the passes of a network over unchanged
+ * weights): C[g] = A[g] B^T (+ bias) for every g, B streamed, scaled and split once per launch.  A, C and a_amax are HOST
+ * arrays of `groups` device pointers; M, N, K, the four strides, bias, B and b_amax are shared.  Every C[g] is bit for
+ * bit what vg_gemm_nt_f16x3 returns for A[g] alone (same tiling, K split, MFMA order and slab sum).  Workspace: the
+ * groups' slabs one after another (groups x the single call's). */
+#define VG_GEMM_MAX_GROUPS 3
+size_t vg_gemm_nt_f16x3_grouped_workspace_bytes(int groups, int M, int N, int K);
+int vg_gemm_nt_f16x3_grouped(int groups, const float* const* A, const float* B, const float* bias, float* const* C,
+                             int M, int N, int K, long a_row_stride, long a_k_stride, long b_row_stride,
+                             long b_k_stride, const float* const* a_amax, const float* b_amax, void* workspace,
+                             size_t workspace_bytes, void* stream);
 
 /* ---- general forward convolution, fp16x3 (csrc/conv_general.hip) ---------------------------------------------------
  * y[b][co][oh][ow] = act(sum_{ci,kh,kw} x[b][ci][oh*stride_h + kh - pad_h][ow*stride_w + kw - pad_w] * w[co][ci][kh][kw]

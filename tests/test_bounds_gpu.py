@@ -279,6 +279,7 @@ def _bn_conv_case(x, stats_in, seed, B_ref):
     """bn_act_conv (BNConvFn) on x with the given slots, forward + backward: everything finite, the output equal (fp64,
     image by image for the images in B_ref) to the convolution of act(x * scale + shift) with the kernel's own
     coefficients (the same slots through vg_bn_finalize_stats again: deterministic)."""
+    # (bounds and finiteness only: the six gradients are compared with an fp64 reference in tests/test_fused_functions_gpu.py)
     g = torch.Generator(device="cuda").manual_seed(seed)
     Cin, Cout = x.shape[1], 256
     act = 2

@@ -279,7 +279,8 @@ def _bn_backward(ctx, gy, x, gamma, beta, mean, invstd, need_p):
 class BNActFn(Function):
     """Train-mode BatchNorm1d/2d + {none, ReLU, LeakyReLU(0.2)} -- model.py:451-452 etc.
     running_mean / running_var are updated in place by the kernel.  ``stats``: the statistics slots the producing
-    convolution left (ops.conv5x5_fwd(..., want_stats=True)); then the statistics pass over x is skipped."""
+    convolution left (ops.conv5x5_fwd(..., want_stats=True)); then the statistics pass over x is skipped.
+    Returns (y, the bound slot of max |y| its kernel emitted -- a non-differentiable side product -- or None)."""
 
     @staticmethod
     def forward(ctx, x, gamma, beta, running_mean, running_var, eps, momentum, act, stats=None):
@@ -293,11 +294,17 @@ class BNActFn(Function):
         ctx.act = act
         ctx.acc = _acc_ctx()
         ctx.save_for_backward(x, gamma, beta, mean, invstd)
-        return y
+        bound = ops.known_amax(y)
+        if bound is not None:
+            ctx.mark_non_differentiable(bound)
+        ctx.set_materialize_grads(False)      # as ConvStatsFn
+        return y, bound
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, gy):
+    def backward(ctx, gy, _):
+        if gy is None:
+            return (None,) * 9
         x, gamma, beta, mean, invstd = ctx.saved_tensors
         need_p = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
         gx, dg, db = _bn_backward(ctx, gy.contiguous(), x, gamma, beta, mean, invstd, need_p)
@@ -536,9 +543,11 @@ def linear_grouped(xs, w, bias, bias_grad=BIAS_GRAD_COMPUTE, detached=None):
 
 
 def batch_norm_act(x, gamma, beta, running_mean, running_var, eps=1e-5, momentum=0.1, act=ops.ACT_NONE, stats=None):
-    ops.forget_last_amax()      # only a bound set inside BNActFn's own forward may be adopted (the HW == 1 path sets none)
-    return ops.adopt_amax(BNActFn.apply(x, gamma, beta, running_mean, running_var, eps, momentum, act,
-                                        stats if stats is not None and stats.numel() else None))
+    y, bound = BNActFn.apply(x, gamma, beta, running_mean, running_var, eps, momentum, act,
+                             stats if stats is not None and stats.numel() else None)
+    if bound is not None:
+        ops.set_amax(y, bound)
+    return y
 
 
 def conv_with_stats(x, w, bias, stride, transposed=False, bias_grad=BIAS_GRAD_COMPUTE):

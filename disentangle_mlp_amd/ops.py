@@ -144,14 +144,16 @@ def _thin_planes():
 
 # ---- bounds of max |tensor| for the fp16 planes (csrc/absmax.hip) ---------------------------------------------------
 # A bound is a one-element fp32 device tensor.  Slots come zeroed from an arena (one fill launch per 512 of them); the
-# producing kernel adds its maximum with an atomic.  A tensor object remembers its bound (`_vg_amax`: the tensor's version
-# counter, what was applied on load, the slot), so that a gradient used by the data gradient AND the weight gradient, or
-# an input used forward and again by the weight gradient, is measured once.
+# producing kernel adds its maximum with an atomic.  A tensor object remembers its bound (an `_Amax` record, written by
+# `set_amax` and read by `known_amax` alone), so that a gradient used by the data gradient AND the weight gradient, or
+# an input used forward and again by the weight gradient, is measured once.  Nothing here is keyed by an address or an
+# id: a torch.autograd.Function whose output needs a bound outside returns the slot next to it (functional.BNActFn).
 _AMAX_CHUNK = 512
 _amax_arenas = {}        # (device index, capturing) -> [chunk, next free]
 
 
-def _amax_slot(device):
+def new_amax_slot(device):
+    """A zeroed bound slot: one launch, or several (the branches of an Inception block), add their maxima into it."""
     key = (device.index, torch.cuda.is_current_stream_capturing())
     a = _amax_arenas.get(key)
     if a is None or a[1] >= _AMAX_CHUNK:
@@ -176,41 +178,32 @@ class amax_capture_scope:
         return False
 
 
-_last_amax = None      # (data_ptr, shape, slot) of the latest plain set_amax: see adopt_amax
+class _Amax(NamedTuple):
+    version: int            # the tensor's version counter when the bound was taken
+    through: object         # the scale tensor of the affine the tensor was read through (compared with `is`), or None
+    slot: torch.Tensor
 
 
 def set_amax(t, slot, in_affine=None):
     """Remember ``slot`` as the bound of ``t`` (as read through ``in_affine``); returns ``slot``."""
-    global _last_amax
-    t._vg_amax = (t._version, None if in_affine is None else id(in_affine[0]), slot)
-    if in_affine is None:
-        _last_amax = (t.data_ptr(), tuple(t.shape), slot)
+    t._vg_amax = _Amax(t._version, None if in_affine is None else in_affine[0], slot)
     return slot
 
 
-def forget_last_amax():
-    """Called right before a Function whose forward may emit no bound: a later `adopt_amax` then matches only a bound
-    set inside that forward, never one left by an earlier (possibly freed) tensor at the same address and shape."""
-    global _last_amax
-    _last_amax = None
-
-
-def adopt_amax(out):
-    """``out`` is what a torch.autograd.Function just returned: autograd hands back a NEW tensor object for the tensor its
-    forward produced, without the Python attribute the producing kernel's wrapper attached.  If ``out`` is that tensor
-    (same memory, same shape, set just now), it inherits the bound."""
-    global _last_amax
-    la, _last_amax = _last_amax, None
-    if la is not None and la[0] == out.data_ptr() and la[1] == tuple(out.shape) and not hasattr(out, "_vg_amax"):
-        out._vg_amax = (out._version, None, la[2])
-    return out
+def known_amax(t, in_affine=None):
+    """The bound slot remembered for ``t`` as it is now, read through ``in_affine`` (None: as it is) -- or None."""
+    known = getattr(t, "_vg_amax", None)
+    through = None if in_affine is None else in_affine[0]
+    if known is not None and known.version == t._version and known.through is through:
+        return known.slot
+    return None
 
 
 def keep_amax(src, view):
     """``view`` is a reshape of ``src`` (same elements): it inherits the bound a producer attached to ``src``."""
-    known = getattr(src, "_vg_amax", None)
-    if known is not None and known[0] == src._version and known[1] is None:
-        view._vg_amax = (view._version, None, known[2])
+    slot = known_amax(src)
+    if slot is not None:
+        set_amax(view, slot)
     return view
 
 
@@ -219,12 +212,11 @@ def amax_of(t, in_affine=None):
     one-element device tensor: the one a producer attached, the 4th element of ``in_affine``, or one pass over t."""
     if in_affine is not None and len(in_affine) > 3 and in_affine[3] is not None:
         return in_affine[3]
-    known = getattr(t, "_vg_amax", None)
-    tag = None if in_affine is None else id(in_affine[0])
-    if known is not None and known[0] == t._version and known[1] == tag:
-        return known[2]
+    slot = known_amax(t, in_affine)
+    if slot is not None:
+        return slot
     lib = _lib.load()
-    slot = _amax_slot(t.device)
+    slot = new_amax_slot(t.device)
     if in_affine is None:
         check(lib.vg_absmax(t.data_ptr(), t.numel(), slot.data_ptr(), _stream()), "vg_absmax")
     else:
@@ -341,7 +333,7 @@ def _launch(key, symbol, *args):
 
 # ---- packed filters --------------------------------------------------------------------------------------------------
 _pack_scope_depth = 0
-_wbound_cache = {}    # Linear weights: data_ptr -> (version, shape, bound slot); lives and dies with the pack cache's entries
+_wbounds = {}         # Linear weights: id(w) -> _WeightBound (see weight_bound)
 _pack_cache = {}      # (data_ptr, layout, transposed, stride, shape, planes) -> [valid, version, packed tensor]
 _pack_scratch = {}    # (device, stream, numel) -> tensor, for un-cached packs
 _PACK_CACHE_MAX = 64  # entries (a beta-VAE-GAN iteration uses 21); beyond it the cache is rebuilt
@@ -378,19 +370,16 @@ def buffers_in_use():
 
 
 def invalidate_packed_filters(params=None):
-    """Drop cached packs -- all of them, or those of the given weight tensors."""
-    if params is None:
-        for ent in _pack_cache.values():
-            ent[0] = False
-        _wbound_cache.clear()
-        return
-    ptrs = {p.data_ptr() for p in params if p.dim() == 4}
+    """Drop cached packs and measured Linear-weight bounds -- all of them, or those of the given weight tensors.  The
+    fused Adam step writes weights without moving their version counter: that is why measured entries need this call.
+    A bound the step emitted itself (`set_weight_bound`) is as new as the weights and is never dropped here."""
+    ptrs = None if params is None else {p.data_ptr() for p in params if p.dim() == 4}
     for key, ent in _pack_cache.items():
-        if key[0] in ptrs:
+        if ptrs is None or key[0] in ptrs:
             ent[0] = False
-    for p in params:
-        if p.dim() == 2:
-            _wbound_cache.pop(p.data_ptr(), None)
+    ids = None if params is None else {id(p) for p in params if p.dim() == 2}
+    for k in [k for k, e in _wbounds.items() if not e.emitted and (ids is None or k in ids)]:
+        del _wbounds[k]
 
 
 def _pack_floats(lib, cout, cin, layout):
@@ -428,7 +417,7 @@ def _packed_filter(lib, w, cout, cin, layout, transposed, stride):
     if split_layout:
         wmax = None
         if _f16():          # a fresh (zeroed) slot per pack: the bound follows the weights down as well as up
-            wmax = _amax_slot(w.device)
+            wmax = new_amax_slot(w.device)
             check(lib.vg_absmax(w.data_ptr(), w.numel(), wmax.data_ptr(), _stream()), "vg_absmax")
         check(lib.vg_conv5x5_pack_bf16split(w.data_ptr(), buf.data_ptr(), cout, cin, int(transposed), stride, _planes(),
                                          _ptr(wmax), _stream()), "vg_conv5x5_pack_bf16split")
@@ -479,7 +468,7 @@ def prepack_filters(requests):
     if _f16():                           # the filters' bounds first, all in one launch (one per weight, not per layout)
         for (w, *_r) in todo:
             if w.data_ptr() not in wmax:
-                wmax[w.data_ptr()] = (w, _amax_slot(w.device))
+                wmax[w.data_ptr()] = (w, new_amax_slot(w.device))
         am = (_lib.AbsmaxEntry * len(wmax))()
         for i, (w, slot) in enumerate(wmax.values()):
             am[i] = _lib.AbsmaxEntry(w.data_ptr(), w.numel(), slot.data_ptr())
@@ -639,11 +628,6 @@ def _pair(v):
     return (int(v), int(v)) if isinstance(v, int) else (int(v[0]), int(v[1]))
 
 
-def new_amax_slot(device):
-    """A zeroed bound slot several launches may add their maxima into (the branches of an Inception block)."""
-    return _amax_slot(device)
-
-
 def conv_general_pack(w, stride=1, padding=0):
     """Pack the fp32 filter ``w`` (Cout, Cin, KH, KW) once for `conv2d_bias_act` (scaled by its bound from one
     vg_absmax pass, split into fp16 planes); returns (packed, meta)."""
@@ -683,7 +667,7 @@ def conv2d_bias_act(x, packed, meta, bias=None, out=None, out_channel_offset=0, 
             raise RuntimeError(f"conv2d_bias_act: out {tuple(out.shape)} (strides {out.stride()}) cannot take channels "
                                f"[{out_channel_offset}, {out_channel_offset + meta.cout}) of a (B={B}, {OH}x{OW}) output")
     view = out[:, out_channel_offset:out_channel_offset + meta.cout]
-    slot = amax if amax is not None else _amax_slot(x.device)
+    slot = amax if amax is not None else new_amax_slot(x.device)
     _launch(("conv_general", B, H, W) + tuple(meta), "vg_conv_general_fwd", x.data_ptr(), packed.data_ptr(), _ptr(bias),
             view.data_ptr(), B, meta.cin, H, W, meta.cout, meta.kh, meta.kw, meta.sh, meta.sw, meta.ph, meta.pw,
             max(out.stride(0), meta.cout * OH * OW), 1 if relu else 0, amax_of(x).data_ptr(), slot.data_ptr())
@@ -704,34 +688,40 @@ def linear_split_ok(reduction, nweights):
     return LINEAR_SPLIT and _f16() and reduction % 32 == 0 and nweights >= LINEAR_SPLIT_MIN_WEIGHTS
 
 
-_wbound_emitted = {}      # id(weight) -> (weak reference, version, bound): what the optimizer step that last wrote it emitted
+class _WeightBound(NamedTuple):
+    ref: weakref.ref        # to the weight: an id re-used by another tensor never matches
+    version: int
+    slot: torch.Tensor
+    emitted: bool           # by the optimizer step that wrote the weight; False: measured inside a packed_filter_scope
+
+
+def _weight_bound_entry(w):
+    """The table's entry for THIS tensor object as it is now (same object, same version counter), or None."""
+    ent = _wbounds.get(id(w))
+    return ent if ent is not None and ent.ref() is w and ent.version == w._version else None
 
 
 def set_weight_bound(w, bound):
     """``bound`` (one-element device tensor) holds max |w| as of now -- HipAdam's step emits it (VgAdamTensor.amax).
-    Valid for THIS tensor object (a weak reference: an address or id re-used by another tensor never matches) until the
-    next torch-side in-place write (the version counter) or the next call for this weight."""
-    if len(_wbound_emitted) > 256:                     # weights of trainers that no longer exist
-        for k in [k for k, e in _wbound_emitted.items() if e[0]() is None]:
-            del _wbound_emitted[k]
-    _wbound_emitted[id(w)] = (weakref.ref(w), w._version, bound)
+    Valid for THIS tensor object until the next torch-side in-place write (the version counter) or the next call for
+    this weight."""
+    if len(_wbounds) > 256:                            # weights of trainers that no longer exist
+        for k in [k for k, e in _wbounds.items() if e.ref() is None]:
+            del _wbounds[k]
+    _wbounds[id(w)] = _WeightBound(weakref.ref(w), w._version, bound, True)
 
 
 def weight_bound(w):
     """Bound of max |w| of a Linear weight: the one the optimizer step emitted when it wrote the weight; failing that,
     inside a `packed_filter_scope`, measured once per weight version (the scope's owner invalidates after optimizer
     steps, as for the packed filters), otherwise per call."""
-    ent = _wbound_emitted.get(id(w))
-    if ent is not None and ent[0]() is w and ent[1] == w._version:
-        return ent[2]
-    if _pack_scope_depth > 0:
-        ent = _wbound_cache.get(w.data_ptr())
-        if ent is not None and ent[0] == w._version and ent[1] == tuple(w.shape):
-            return ent[2]
-    slot = _amax_slot(w.device)          # a fresh (zeroed) slot: the bound follows the weights down as well as up
+    ent = _weight_bound_entry(w)
+    if ent is not None and (ent.emitted or _pack_scope_depth > 0):
+        return ent.slot
+    slot = new_amax_slot(w.device)       # a fresh (zeroed) slot: the bound follows the weights down as well as up
     check(_lib.load().vg_absmax(w.data_ptr(), w.numel(), slot.data_ptr(), _stream()), "vg_absmax")
-    if _pack_scope_depth > 0:
-        _wbound_cache[w.data_ptr()] = (w._version, tuple(w.shape), slot)
+    if _pack_scope_depth > 0:         # (a measured entry of a dead weight lives until the scope's next invalidation)
+        _wbounds[id(w)] = _WeightBound(weakref.ref(w), w._version, slot, False)
     return slot
 
 
@@ -839,7 +829,7 @@ def bn_act_fwd(x, gamma, beta, running_mean, running_var, eps, momentum, act):
     mean = torch.empty(C, dtype=torch.float32, device=x.device)
     invstd = torch.empty(C, dtype=torch.float32, device=x.device)
     ws = workspace(lib.vg_bn_workspace_bytes(C), x.device)
-    slot = _amax_slot(x.device) if (_f16() and HW > 1) else None      # max |y| on the way out (as affine_act)
+    slot = new_amax_slot(x.device) if (_f16() and HW > 1) else None      # max |y| on the way out (as affine_act)
     check(lib.vg_bn_act_fwd(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), _ptr(running_mean),
                             _ptr(running_var), mean.data_ptr(), invstd.data_ptr(), B, C, HW, eps, momentum, act, _ptr(slot),
                             ws.data_ptr(), ws.numel(), _stream()), "vg_bn_act_fwd")
@@ -859,7 +849,7 @@ def bn_finalize_stats(stats, count, gamma, beta, running_mean, running_var, eps,
     nslots = stats.numel() // (2 * C)
     out = torch.empty((4, C), dtype=torch.float32, device=gamma.device)
     mean, invstd, scale, shift = out[0], out[1], out[2], out[3]
-    bound = _amax_slot(gamma.device) if (want_bound and _f16()) else None
+    bound = new_amax_slot(gamma.device) if (want_bound and _f16()) else None
     ws = workspace(lib.vg_bn_workspace_bytes(C), gamma.device)
     check(lib.vg_bn_finalize_stats(stats.data_ptr(), nslots, C, float(count), gamma.data_ptr(), beta.data_ptr(),
                                    _ptr(running_mean), _ptr(running_var), mean.data_ptr(), invstd.data_ptr(),
@@ -876,7 +866,7 @@ def bn_stats(x, gamma, beta, running_mean, running_var, eps, momentum, want_boun
     HW = x.numel() // (B * C)
     out = torch.empty((4, C), dtype=torch.float32, device=x.device)
     mean, invstd, scale, shift = out[0], out[1], out[2], out[3]
-    bound = _amax_slot(x.device) if (want_bound and _f16()) else None
+    bound = new_amax_slot(x.device) if (want_bound and _f16()) else None
     ws = workspace(lib.vg_bn_workspace_bytes(C), x.device)
     check(lib.vg_bn_stats(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(running_mean), _ptr(running_var),
                           mean.data_ptr(), invstd.data_ptr(), scale.data_ptr(), shift.data_ptr(), B, C, HW, eps, momentum,
@@ -891,7 +881,7 @@ def affine_act(x, scale, shift, act):
     B, C = x.shape[0], x.shape[1]
     HW = x.numel() // (B * C)
     y = torch.empty_like(x)
-    slot = _amax_slot(x.device) if _f16() else None          # max |y| on the way out: y feeds a convolution
+    slot = new_amax_slot(x.device) if _f16() else None          # max |y| on the way out: y feeds a convolution
     check(lib.vg_affine_act(x.data_ptr(), scale.data_ptr(), shift.data_ptr(), y.data_ptr(), B, C, HW, int(act), _ptr(slot),
                             _stream()), "vg_affine_act")
     if slot is not None:
@@ -913,7 +903,7 @@ def bn_act_bwd(gy, x, gamma, beta, mean, invstd, act, need_param_grads=True, acc
         dgamma = torch.empty(C, dtype=torch.float32, device=x.device) if need_param_grads else None
         dbeta = torch.empty(C, dtype=torch.float32, device=x.device) if need_param_grads else None
     ws = workspace(lib.vg_bn_workspace_bytes(C), x.device)
-    slot = _amax_slot(x.device) if (_f16() and HW > 1) else None   # max |gx| on the way out: gx feeds a data / weight gradient
+    slot = new_amax_slot(x.device) if (_f16() and HW > 1) else None   # max |gx| on the way out: gx feeds a data / weight gradient
     check(lib.vg_bn_act_bwd(gy.data_ptr(), x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(),
                             invstd.data_ptr(), gx.data_ptr(), _ptr(dgamma), _ptr(dbeta), B, C, HW, act,
                             1 if accumulate_into is not None else 0, _ptr(slot), ws.data_ptr(), ws.numel(), _stream()),
@@ -939,7 +929,7 @@ def act_bwd(gy, y, kind):
     lib = _lib.load()
     _req(gy, "gy"), _req(y, "y")
     gx = torch.empty_like(y)
-    slot = _amax_slot(y.device) if (_f16() and LINEAR_SPLIT and y.dim() == 2) else None      # feeds a Linear layer's backward GEMMs
+    slot = new_amax_slot(y.device) if (_f16() and LINEAR_SPLIT and y.dim() == 2) else None      # feeds a Linear layer's backward GEMMs
     check(lib.vg_act_bwd(gy.data_ptr(), y.data_ptr(), gx.data_ptr(), y.numel(), kind, _ptr(slot), _stream()), "vg_act_bwd")
     if slot is not None:
         set_amax(gx, slot)
@@ -1144,7 +1134,7 @@ def resize_bilinear_u8(images_u8, size=(299, 299), scale=2.0, shift=-1.0):
     if B > 65535:
         raise RuntimeError("resize_bilinear_u8: at most 65535 images per call")
     y = torch.empty((B, 3, OH, OW), dtype=torch.float32, device=images_u8.device)
-    slot = _amax_slot(y.device)
+    slot = new_amax_slot(y.device)
     check(lib.vg_resize_bilinear_u8(images_u8.data_ptr(), y.data_ptr(), B, H, W, OH, OW, float(scale), float(shift),
                                     slot.data_ptr(), _stream()), "vg_resize_bilinear_u8")
     set_amax(y, slot)
@@ -1173,7 +1163,7 @@ def pool3x3(x, stride, padding, mode, out=None, out_channel_offset=0, amax=None)
                 not 0 <= out_channel_offset <= out.shape[1] - C:
             raise RuntimeError(f"pool3x3: out {tuple(out.shape)} cannot take channels [{out_channel_offset}, "
                                f"{out_channel_offset + C}) of a (B={B}, {OH}x{OW}) output")
-    slot = amax if amax is not None else _amax_slot(x.device)
+    slot = amax if amax is not None else new_amax_slot(x.device)
     check(lib.vg_pool3x3(x.data_ptr(), out.data_ptr(), B, C, H, W, stride, padding,
                          POOL_MAX if mode == "max" else POOL_AVG_EXCLUDE_PAD, out.shape[1], out_channel_offset,
                          slot.data_ptr(), _stream()), "vg_pool3x3")

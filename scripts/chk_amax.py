@@ -1,8 +1,8 @@
 """Which bounds of max |tensor| (ops.amax_of) a Discriminator forward + backward finds attached by a producer ("cached") and
 which it has to measure with a pass of its own.  (The conv-chain entries with a BatchNorm-on-load print MEASURED although their
-bound travels in the in_affine tuple: the spy looks at the tensor attribute only.)"""
+bound travels in the in_affine tuple: the spy asks ops.known_amax, which looks at the tensor's own record only.)"""
 import sys, os
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import torch
 from disentangle_mlp_amd import ops, model
 from disentangle_mlp_amd.trainer import ModelOpt
@@ -14,12 +14,11 @@ calls = []
 lib = ops._lib.load()
 orig = ops.amax_of
 def spy(t, in_affine=None):
-    known = getattr(t, "_vg_amax", None)
-    calls.append((tuple(t.shape), known is not None and known[0] == t._version))
+    calls.append((tuple(t.shape), ops.known_amax(t, in_affine) is not None))
     return orig(t, in_affine)
 ops.amax_of = spy
 c = D.convs(x)
-print("convs out has bound:", hasattr(c, "_vg_amax"), type(D.convs[-1]).__name__)
+print("convs out has bound:", ops.known_amax(c) is not None, type(D.convs[-1]).__name__)
 p, f = D(x)
 (p.sum() + f.sum()).backward()
 for s, k in calls: print(s, "cached" if k else "MEASURED")

@@ -451,10 +451,12 @@ def test_linear_layers_dispatch_and_the_adam_tensor_struct_match_the_header():
     assert fields == [f[0] for f in optim._AdamTensor._fields_] == ["p", "g", "m", "v", "n", "amax"]
 
 
-def test_emitted_weight_bounds_belong_to_one_tensor_object_and_one_version():
-    """ops.set_weight_bound / weight_bound (the bound HipAdam's step emits for a big Linear weight): a hit needs the SAME
-    tensor object at the SAME version -- not merely the same address, shape or id."""
+def test_emitted_weight_bounds_belong_to_one_tensor_object_and_one_version(monkeypatch):
+    """ops.set_weight_bound / weight_bound (the bound HipAdam's step emits for a big Linear weight, or one measured inside
+    a packed_filter_scope): a hit needs the SAME tensor object at the SAME version -- not merely the same address, shape
+    or id.  Invalidation drops measured bounds and never emitted ones."""
     import gc
+    import types
     import torch
     from disentangle_mlp_amd import ops
     w, b = torch.zeros(4, 4), torch.ones(1)
@@ -462,34 +464,166 @@ def test_emitted_weight_bounds_belong_to_one_tensor_object_and_one_version():
     assert ops.weight_bound(w) is b
     key = id(w)
     w.add_(1.0)                                   # version bump: stale
-    ent = ops._wbound_emitted[key]
-    assert ent[0]() is w and ent[1] != w._version
+    ent = ops._wbounds[key]
+    assert ent.ref() is w and ent.version != w._version and ops._weight_bound_entry(w) is None
     ops.set_weight_bound(w, b)
     assert ops.weight_bound(w) is b
     del w
     gc.collect()
-    assert ops._wbound_emitted[key][0]() is None   # a new tensor that re-uses the id can never match the dead reference
+    assert ops._wbounds[key].ref() is None        # a new tensor that re-uses the id can never match the dead reference
+
+    # measured bounds, the measuring launch stubbed out: every measurement hands out a new slot
+    slots = []
+    monkeypatch.setattr(ops, "new_amax_slot", lambda device: slots.append(torch.zeros(1)) or slots[-1])
+    monkeypatch.setattr(ops._lib, "load", lambda: types.SimpleNamespace(vg_absmax=lambda *a: 0))
+    monkeypatch.setattr(ops, "_stream", lambda: 0)
+    w = torch.zeros(4, 4)
+    first = ops.weight_bound(w)                   # outside a scope: measured per call, nothing stored
+    assert ops.weight_bound(w) is not first and len(slots) == 2 and id(w) not in ops._wbounds
+    with ops.packed_filter_scope():
+        m = ops.weight_bound(w)
+        assert ops.weight_bound(w) is m and len(slots) == 3           # returned again for the same object
+        alias = w.detach()                        # same address, shape and version counter: another object
+        assert alias.data_ptr() == w.data_ptr() and alias._version == w._version
+        assert ops.weight_bound(alias) is not m and ops.weight_bound(w) is m
+        ops.invalidate_packed_filters([w])
+        m2 = ops.weight_bound(w)
+        assert m2 is not m and ops.weight_bound(w) is m2
+        ops.invalidate_packed_filters()
+        m3 = ops.weight_bound(w)
+        assert m3 is not m2
+        w.add_(1.0)                               # version bump: measured again
+        assert ops.weight_bound(w) is not m3
+        ops.set_weight_bound(w, b)                # an emitted bound survives both invalidations
+        ops.invalidate_packed_filters([w])
+        assert ops.weight_bound(w) is b
+        ops.invalidate_packed_filters()
+        assert ops.weight_bound(w) is b
+        other = torch.zeros(4, 4)
+        mo = ops.weight_bound(other)
+        assert ops.weight_bound(other) is mo
+    n = len(slots)
+    assert ops.weight_bound(w) is b and len(slots) == n               # emitted: valid outside the scope too
+    assert ops.weight_bound(other) is not mo and len(slots) == n + 1  # measured: gone with the scope
 
 
-def test_batch_norm_act_adopts_only_a_bound_set_inside_its_own_forward(monkeypatch):
-    """functional.batch_norm_act hands its output the bound its forward's kernel emitted (ops.adopt_amax matches the
-    latest set_amax by address and shape).  A forward that emits none (the HW == 1 path) must not pass on a bound an
-    EARLIER tensor left, even when its output re-uses that tensor's memory with the same shape."""
+def test_a_bound_read_through_an_affine_belongs_to_that_scale_tensor(monkeypatch):
+    """ops.amax_of(t, in_affine) remembers the bound of t AS READ THROUGH that affine: it is returned again for the same
+    scale tensor object only -- not for another one, including one created after the first was freed (whose id, and
+    memory, it may re-use)."""
+    import gc
+    import types
+    import torch
+    from disentangle_mlp_amd import ops
+    slots = []
+    monkeypatch.setattr(ops, "new_amax_slot", lambda device: slots.append(torch.zeros(1)) or slots[-1])
+    monkeypatch.setattr(ops._lib, "load", lambda: types.SimpleNamespace(vg_absmax=lambda *a: 0, vg_absmax_affine=lambda *a: 0))
+    monkeypatch.setattr(ops, "_stream", lambda: 0)
+    t, shift = torch.zeros(2, 4, 3, 3), torch.zeros(4)
+    s1, s2 = torch.ones(4), torch.ones(4)
+    b1 = ops.amax_of(t, (s1, shift, 0))
+    assert ops.amax_of(t, (s1, shift, 0)) is b1 and ops.known_amax(t, (s1, shift, 0)) is b1 and len(slots) == 1
+    assert ops.known_amax(t) is None and ops.known_amax(t, (s2, shift, 0)) is None
+    for _ in range(64):                           # scale tensors that come and go: some re-use an id
+        s = torch.ones(4)
+        aff = (s, shift, 0)
+        bs = ops.amax_of(t, aff)
+        assert ops.known_amax(t, aff) is bs
+        del s, aff
+        gc.collect()
+        s = torch.ones(4)                         # created after the other was freed
+        assert ops.known_amax(t, (s, shift, 0)) is None
+        del s
+    b1 = ops.amax_of(t, (s1, shift, 0))
+    n = len(slots)
+    assert ops.known_amax(t, (s2, shift, 0)) is None
+    assert ops.amax_of(t, (s1, shift, 0)) is b1 and len(slots) == n   # returned again for s1
+    t.add_(1.0)                                   # ... until t is written
+    assert ops.known_amax(t, (s1, shift, 0)) is None
+
+
+def test_batch_norm_act_hands_out_the_bound_its_own_forward_set(monkeypatch):
+    """functional.batch_norm_act through the real BNActFn.apply and autograd, the op wrappers replaced by torch stand-ins
+    that call ops.set_amax where the real ones do: the output carries exactly the slot its forward set (BNActFn returns
+    it next to y), and none when the forward set none (the HW == 1 path) -- whatever another tensor was given lately."""
     import torch
     from disentangle_mlp_amd import functional as HF, ops
-    x, gamma, beta = torch.zeros(8, 4), torch.ones(4), torch.zeros(4)
-    stale, stale_slot = torch.zeros(8, 4), torch.full((1,), 1e-3)
-    ops.set_amax(stale, stale_slot)                       # an earlier producer's output ...
-    monkeypatch.setattr(HF.BNActFn, "apply", lambda *a: stale.view(8, 4))   # ... whose block the next output re-uses
-    out = HF.batch_norm_act(x, gamma, beta, None, None)
-    assert out.data_ptr() == stale.data_ptr() and not hasattr(out, "_vg_amax")
+    emitted = []
 
-    own_slot = torch.full((1,), 7.0)
+    def emit(y):
+        emitted.append(torch.full((1,), 7.0))
+        ops.set_amax(y, emitted[-1])
 
-    def emitting_forward(*a):                             # a forward whose kernel emits the bound of its output
-        y = torch.zeros(8, 4)
-        ops.set_amax(y, own_slot)
-        return y.view(8, 4)                               # autograd hands back a new tensor object for it
-    monkeypatch.setattr(HF.BNActFn, "apply", emitting_forward)
+    def bn_act_fwd(x, gamma, beta, rm, rv, eps, momentum, act):
+        dims = [0] + list(range(2, x.dim()))
+        shp = (1, -1) + (1,) * (x.dim() - 2)
+        mean, invstd = x.mean(dims), (x.var(dims, unbiased=False) + eps).rsqrt()
+        y = (x - mean.view(shp)) * (invstd * gamma).view(shp) + beta.view(shp)
+        if x.numel() // (x.shape[0] * x.shape[1]) > 1:
+            emit(y)
+        return y, mean, invstd
+
+    def bn_finalize_stats(stats, count, gamma, beta, rm, rv, eps, momentum, want_bound=False):
+        mean = stats[0] / count
+        invstd = (stats[1] / count - mean * mean + eps).rsqrt()
+        return mean, invstd, gamma * invstd, beta - mean * gamma * invstd
+
+    def affine_act(x, scale, shift, act):
+        y = x * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1)
+        emit(y)
+        return y
+
+    def bn_act_bwd(gy, x, gamma, beta, mean, invstd, act, need_param_grads=True, accumulate_into=None):
+        dims = [0] + list(range(2, x.dim()))
+        shp = (1, -1) + (1,) * (x.dim() - 2)
+        xh = (x - mean.view(shp)) * invstd.view(shp)
+        dg, db = (gy * xh).sum(dims), gy.sum(dims)
+        n = x.numel() // x.shape[1]
+        gx = (gamma * invstd).view(shp) * (gy - db.view(shp) / n - xh * dg.view(shp) / n)
+        return gx, dg, db
+
+    for name, f in (("bn_act_fwd", bn_act_fwd), ("bn_finalize_stats", bn_finalize_stats), ("affine_act", affine_act),
+                    ("bn_act_bwd", bn_act_bwd)):
+        monkeypatch.setattr(ops, name, f)
+    g = torch.Generator().manual_seed(3)
+
+    def inputs(*shape):
+        return (torch.randn(*shape, generator=g).requires_grad_(), (1 + 0.1 * torch.randn(4, generator=g)).requires_grad_(),
+                torch.randn(4, generator=g).requires_grad_())
+
+    x, gamma, beta = inputs(8, 4, 2, 2)
+    xd = x.detach()
+    stats = torch.stack([xd.sum((0, 2, 3)), (xd * xd).sum((0, 2, 3))])
+    for st in (None, stats):                      # the two-pass kernel / the producer's slots + the normalise pass
+        for grad in (True, False):
+            with torch.set_grad_enabled(grad):
+                out = HF.batch_norm_act(x, gamma, beta, None, None, stats=st)
+            assert out.requires_grad == grad
+            assert ops.known_amax(out) is emitted[-1]      # that very slot, valid for out as it is now
+    n = len(emitted)
     out = HF.batch_norm_act(x, gamma, beta, None, None)
-    assert out._vg_amax[2] is own_slot and out._vg_amax[0] == out._version
+    out.sum().backward()
+    assert len(emitted) == n + 1
+    ref = torch.nn.functional.batch_norm(xd, None, None, gamma.detach(), beta.detach(), True)
+    assert torch.allclose(out.detach(), ref, atol=1e-5)
+    assert all(t.grad is not None and bool(torch.isfinite(t.grad).all()) for t in (x, gamma, beta))
+    assert torch.allclose(beta.grad, torch.full((4,), 32.0)) and float(x.grad.abs().max()) < 1e-4
+
+    # a forward that emits no bound: none is handed out, not even one another tensor of the same shape got just now
+    x, gamma, beta = inputs(8, 4)
+    for grad in (False, True):
+        ops.set_amax(torch.zeros(8, 4), torch.full((1,), 1e-3))
+        with torch.set_grad_enabled(grad):
+            out = HF.batch_norm_act(x, gamma, beta, None, None)
+        assert out.shape == (8, 4) and ops.known_amax(out) is None
+    out.sum().backward()
+    assert all(t.grad is not None for t in (x, gamma, beta))
+
+    # a graph in which the output is not used
+    x, gamma, beta = inputs(8, 4, 2, 2)
+    out = HF.batch_norm_act(x, gamma, beta, None, None)
+    (x * 2.0).sum().backward()
+    assert torch.equal(x.grad, torch.full_like(x, 2.0)) and gamma.grad is None
+    x.grad = None
+    (out * 0.0).sum().backward()                  # and one in which it is, next to it
+    assert x.grad is not None

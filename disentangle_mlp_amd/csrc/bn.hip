@@ -54,9 +54,9 @@ __global__ __launch_bounds__(NT) void bn_partial_kernel(const float* __restrict_
                                                         const float* __restrict__ mean,
                                                         const float* __restrict__ invstd, double* __restrict__ part,
                                                         int B, int C, int HW, long per, int ns, int act, int vec) {
-  // vec: four elements of a plane per 16-byte load -- the host's decision.  vg_channel_sum sets it only for HW % 4 == 0
-  // AND a 16-byte aligned tensor; the BatchNorm entry points pass HW % 4 == 0 alone and, like bn_apply_kernel and the
-  // one-pass backward after them, still take x / gy on a 16-byte boundary on trust
+  // vec: four elements of a plane per 16-byte load -- the host's decision (streams_vec below): HW % 4 == 0 AND every
+  // streamed tensor on a 16-byte boundary.  A contiguous view at an odd offset takes the scalar loop, here and in
+  // bn_apply_kernel; the one-pass backward, which has no scalar form, is not launched for it
   __shared__ double red[NT / 64];
   const int c = blockIdx.x, k = blockIdx.y;
   const long total = (long)B * HW;
@@ -135,7 +135,8 @@ __global__ __launch_bounds__(NT) void bn_apply_kernel(const float* __restrict__ 
                                                       float* __restrict__ running_var, float* __restrict__ dgamma,
                                                       float* __restrict__ dbeta, float* __restrict__ out, int B,
                                                       int C, int HW, long per, float eps, float momentum, int act,
-                                                      unsigned* __restrict__ out_amax) {
+                                                      unsigned* __restrict__ out_amax, int vec) {
+  // vec: as in bn_partial_kernel (x, gy and out are streamed)
   // out_amax (backward, may be NULL): max |gx| is added to it (common.hpp block_amax_atomic) -- the bound the fp16-plane
   // convolutions that consume gx scale it by, emitted here instead of by a pass of its own
   const bool accp = (act & 0x100) != 0;        // backward: dgamma / dbeta are accumulated into (bit 8 of `act`)
@@ -210,7 +211,7 @@ __global__ __launch_bounds__(NT) void bn_apply_kernel(const float* __restrict__ 
   const long total = (long)B * HW;
   const long v0 = (long)k * per, v1 = min(v0 + per, total);
   const int hw_shift = (HW & (HW - 1)) == 0 ? __builtin_ctz(HW) : -1;
-  if ((HW & 3) == 0) {
+  if (vec) {
     for (long v = v0 + 4L * threadIdx.x; v < v1; v += 4L * NT) {
       const long b = hw_shift >= 0 ? (v >> hw_shift) : v / HW, hw = v - b * HW;
       const size_t off = ((size_t)b * C + c) * HW + hw;
@@ -442,6 +443,12 @@ Slicing make_apply_slicing(int B, int C, int HW) {
   s.per = per;
   s.ns = (int)((total + per - 1) / per);
   return s;
+}
+
+// The 16-byte loops are taken only when four elements of a plane share a load (HW % 4 == 0) and every tensor that is
+// streamed starts on a 16-byte boundary (pass nullptr for one that is not there); otherwise the scalar loops.
+int streams_vec(int HW, const void* a, const void* b = nullptr, const void* c = nullptr) {
+  return (HW & 3) == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
 }
 
 size_t part_bytes(int C) { return (size_t)C * NS_MAX * 2 * sizeof(double); }
@@ -745,7 +752,7 @@ extern "C" int vg_bn_stats(const float* x, const float* gamma, const float* beta
   const Slicing s = make_slicing(B, C, HW);
   hipLaunchKernelGGL(bn_partial_kernel<0>, dim3(C, s.ns), dim3(NT), 0, st, x, (const float*)nullptr, (const float*)nullptr,
                      (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, part, B, C, HW, s.per, s.ns, 0,
-                     (HW & 3) == 0);
+                     streams_vec(HW, x));
   VG_CHECK_LAUNCH();
   hipLaunchKernelGGL(bn_finalize_kernel<double>, dim3(cdiv(C, 32)), dim3(NT), 0, st, (const double*)part, s.ns,
                      (long)s.ns, 1L, C, (double)B * HW, gamma, beta, running_mean, running_var, save_mean, save_invstd,
@@ -798,15 +805,16 @@ extern "C" int vg_bn_act_fwd(const float* x, const float* gamma, const float* be
   }
   if (!workspace || workspace_bytes < ws_bytes(C)) return VG_ERR_WORKSPACE;
   double* part = (double*)workspace;
+  const int vec = streams_vec(HW, x, y);
   const Slicing s = make_slicing(B, C, HW);
   hipLaunchKernelGGL(bn_partial_kernel<0>, dim3(C, s.ns), dim3(NT), 0, st, x, (const float*)nullptr, gamma, beta,
-                     (const float*)nullptr, (const float*)nullptr, part, B, C, HW, s.per, s.ns, act, (HW & 3) == 0);
+                     (const float*)nullptr, (const float*)nullptr, part, B, C, HW, s.per, s.ns, act, vec);
   VG_CHECK_LAUNCH();
   const Slicing a = make_apply_slicing(B, C, HW);
   hipLaunchKernelGGL(bn_apply_kernel<false>, dim3(C, a.ns), dim3(NT), 0, st, x, (const float*)nullptr,
                      (const double*)part, s.ns, gamma, beta, save_mean, save_invstd, running_mean, running_var,
                      (float*)nullptr, (float*)nullptr, y, B, C, HW, a.per, eps, momentum, act,
-                     reinterpret_cast<unsigned*>(y_amax));
+                     reinterpret_cast<unsigned*>(y_amax), vec);
   VG_CHECK_LAUNCH();
   return 0;
 }
@@ -828,8 +836,10 @@ extern "C" int vg_bn_act_bwd(const float* gy, const float* x, const float* gamma
     return 0;
   }
   // one pass when a channel fits a workgroup's registers and there are channels enough to fill the chip's memory system
+  // (16-byte loads only: a misaligned x / gy / gx goes to the two passes' scalar loops)
   const long per_channel = (long)B * HW;
-  if ((HW & 3) == 0 && per_channel >= 4 && per_channel <= (long)ONE_NT * 4 * 8 && C >= 128) {
+  const int vec = streams_vec(HW, x, gy, gx);
+  if (vec && per_channel >= 4 && per_channel <= (long)ONE_NT * 4 * 8 && C >= 128) {
     if (per_channel <= (long)ONE_NT * 4 * 2)
       hipLaunchKernelGGL(bn_bwd_onepass_kernel<2>, dim3(C), dim3(ONE_NT), 0, st, x, gy, gamma, beta, save_mean, save_invstd,
                          gx, dgamma, dbeta, B, C, HW, act_apply, am);
@@ -843,12 +853,12 @@ extern "C" int vg_bn_act_bwd(const float* gy, const float* x, const float* gamma
   double* part = (double*)workspace;
   const Slicing s = make_slicing(B, C, HW);
   hipLaunchKernelGGL(bn_partial_kernel<1>, dim3(C, s.ns), dim3(NT), 0, st, x, gy, gamma, beta, save_mean,
-                     save_invstd, part, B, C, HW, s.per, s.ns, act, (HW & 3) == 0);
+                     save_invstd, part, B, C, HW, s.per, s.ns, act, vec);
   VG_CHECK_LAUNCH();
   const Slicing a = make_apply_slicing(B, C, HW);
   hipLaunchKernelGGL(bn_apply_kernel<true>, dim3(C, a.ns), dim3(NT), 0, st, x, gy, (const double*)part, s.ns, gamma,
                      beta, const_cast<float*>(save_mean), const_cast<float*>(save_invstd), (float*)nullptr,
-                     (float*)nullptr, dgamma, dbeta, gx, B, C, HW, a.per, 0.f, 0.f, act_apply, am);
+                     (float*)nullptr, dgamma, dbeta, gx, B, C, HW, a.per, 0.f, 0.f, act_apply, am, vec);
   VG_CHECK_LAUNCH();
   return 0;
 }

@@ -102,7 +102,8 @@ def reserve_workspace(nbytes, device):
 # Packed filters (vg_conv5x5_pack): the implicit-GEMM kernels read the filter as
 # [class][ci][tap][cout].  Outside a `packed_filter_scope` every launch re-packs its weight
 # (a few microseconds); inside one -- the trainer opens it around an iteration, where it
-# alone decides when weights change -- a pack is reused until `invalidate_packed_filters()`.
+# alone decides when weights change -- a pack is reused until `invalidate_packed_filters()`.  It belongs
+# to the weight tensor OBJECT (`_WeightRecord`), not to its address, and lives as long as that.
 USE_PACKED_FILTERS = True
 FP32_CONV_STATS = False     # see route_conv
 # Arithmetic of the three convolution kernels (forward, transposed = data gradient, weight gradient):
@@ -146,8 +147,8 @@ def _thin_planes():
 # A bound is a one-element fp32 device tensor.  Slots come zeroed from an arena (one fill launch per 512 of them); the
 # producing kernel adds its maximum with an atomic.  A tensor object remembers its bound (an `_Amax` record, written by
 # `set_amax` and read by `known_amax` alone), so that a gradient used by the data gradient AND the weight gradient, or
-# an input used forward and again by the weight gradient, is measured once.  Nothing here is keyed by an address or an
-# id: a torch.autograd.Function whose output needs a bound outside returns the slot next to it (functional.BNActFn).
+# an input used forward and again by the weight gradient, is measured once.  Nothing here or in the weights' records
+# (`_WeightRecord`) is matched by an address or by an id alone: a Function whose output needs a bound outside returns it.
 _AMAX_CHUNK = 512
 _amax_arenas = {}        # (device index, capturing) -> [chunk, next free]
 
@@ -333,23 +334,41 @@ def _launch(key, symbol, *args):
 
 # ---- packed filters --------------------------------------------------------------------------------------------------
 _pack_scope_depth = 0
-_wbounds = {}         # Linear weights: id(w) -> _WeightBound (see weight_bound)
-_pack_cache = {}      # (data_ptr, layout, transposed, stride, shape, planes) -> [valid, version, packed tensor]
+_records = {}         # id(w) -> _WeightRecord of a live weight: its weak reference takes it out before the id can be re-used
 _pack_scratch = {}    # (device, stream, numel) -> tensor, for un-cached packs
-_PACK_CACHE_MAX = 64  # entries (a beta-VAE-GAN iteration uses 21); beyond it the cache is rebuilt
 PACK_FP32, PACK_SPLIT = "fp32", "split"      # layouts: vg_conv5x5_pack (conv_igemm.hip) / vg_conv5x5_pack_bf16split
 
 
+class _Bound(NamedTuple):
+    version: int            # the weight's version counter when the bound was taken
+    slot: torch.Tensor
+    emitted: bool           # by the optimizer step that wrote the weight; False: measured inside a packed_filter_scope
+
+
+class _WeightRecord:
+    """What is derived from ONE weight tensor object and lives as long as it: ``bound``, the `_Bound` of a Linear weight
+    (or None), and ``packs``, (layout, transposed, stride, planes) -> [valid, version, packed tensor] of a convolution
+    filter.  A pack's tensor is allocated when its key is first asked for and never replaced."""
+    __slots__ = ("ref", "bound", "packs")
+
+    def __init__(self, ref):
+        self.ref, self.bound, self.packs = ref, None, {}
+
+
+def _record(w, create=False):
+    """The record of THIS tensor object, or None: never that of another tensor at its address or with its id."""
+    rec = _records.get(id(w))
+    if (rec is None or rec.ref() is not w) and create:
+        rec = _records[id(w)] = _WeightRecord(weakref.ref(w, lambda _ref, key=id(w): _records.pop(key, None)))
+    return rec if rec is not None and rec.ref() is w else None
+
+
 class packed_filter_scope:
-    """Within the scope packed filters are cached per weight storage; the owner of the scope
-    promises to call `invalidate_packed_filters()` after every in-place weight update."""
+    """Within the scope packed filters are cached per weight tensor object; the owner of the scope promises to call
+    `invalidate_packed_filters()` after every in-place weight update.  Outside one every pack is stale (`__exit__`)."""
 
     def __enter__(self):
         global _pack_scope_depth
-        if _pack_scope_depth == 0:
-            if len(_pack_cache) > _PACK_CACHE_MAX:     # weights of trainers that no longer exist
-                _pack_cache.clear()
-            invalidate_packed_filters()
         _pack_scope_depth += 1
         return self
 
@@ -362,24 +381,22 @@ class packed_filter_scope:
 
 
 def buffers_in_use():
-    """Every cached pack buffer and scratch buffer that exists now, as a list of tensors.  A HIP graph captured over
-    launches that read or write them holds raw device pointers: its owner keeps this list alive for as long as the graph
-    may be replayed, so that a cache rebuilt (`_PACK_CACHE_MAX`) or a workspace regrown by somebody else never hands the
-    memory a replay still writes to another tensor."""
-    return [ent[2] for ent in _pack_cache.values()] + list(_workspaces.values()) + list(_pack_scratch.values())
+    """Every pack buffer of a live weight, every workspace and scratch buffer that exists now, as a list of tensors.  A
+    HIP graph captured over launches that read or write them holds raw device pointers: its owner keeps this list for as
+    long as the graph may be replayed, so that the memory outlives a weight dropped or a workspace regrown meanwhile."""
+    packs = [ent[2] for rec in list(_records.values()) for ent in rec.packs.values()]
+    return packs + list(_workspaces.values()) + list(_pack_scratch.values())
 
 
 def invalidate_packed_filters(params=None):
-    """Drop cached packs and measured Linear-weight bounds -- all of them, or those of the given weight tensors.  The
+    """Mark the packs stale and drop the measured bounds -- of every live weight, or of the given tensor objects.  The
     fused Adam step writes weights without moving their version counter: that is why measured entries need this call.
     A bound the step emitted itself (`set_weight_bound`) is as new as the weights and is never dropped here."""
-    ptrs = None if params is None else {p.data_ptr() for p in params if p.dim() == 4}
-    for key, ent in _pack_cache.items():
-        if ptrs is None or key[0] in ptrs:
+    for rec in list(_records.values()) if params is None else filter(None, map(_record, params)):
+        for ent in rec.packs.values():
             ent[0] = False
-    ids = None if params is None else {id(p) for p in params if p.dim() == 2}
-    for k in [k for k, e in _wbounds.items() if not e.emitted and (ids is None or k in ids)]:
-        del _wbounds[k]
+        if rec.bound is not None and not rec.bound.emitted:
+            rec.bound = None
 
 
 def _pack_floats(lib, cout, cin, layout):
@@ -389,47 +406,45 @@ def _pack_floats(lib, cout, cin, layout):
 
 
 def _pack_entry(lib, w, cout, cin, layout, transposed, stride):
-    """(the pack cache's entry [valid, version, packed tensor] of this weight in this layout -- created, stale, when it is
-    asked for the first time --, whether its pack is that of the weight as it is now)."""
-    key = (w.data_ptr(), layout, transposed, stride, tuple(w.shape), _planes() if layout == PACK_SPLIT else 0)
-    ent = _pack_cache.get(key)
+    """(the entry [valid, version, packed tensor] of this weight object in this layout -- created, stale, when it is asked
+    for the first time --, whether its pack is that of the weight as it is now)."""
+    packs = _record(w, create=True).packs
+    key = (layout, transposed, stride, _planes() if layout == PACK_SPLIT else 0)
+    ent = packs.get(key)
     if ent is None:
-        n = _pack_floats(lib, cout, cin, layout)
-        ent = _pack_cache[key] = [False, -1, torch.empty(n, dtype=torch.float32, device=w.device)]
+        ent = packs[key] = [False, -1, torch.empty(_pack_floats(lib, cout, cin, layout), dtype=torch.float32, device=w.device)]
     return ent, ent[0] and ent[1] == w._version
 
 
 def _packed_filter(lib, w, cout, cin, layout, transposed, stride):
     split_layout = layout == PACK_SPLIT
     if split_layout and _pack_log is not None:
-        _pack_log.append((w, cout, cin, transposed, stride))
+        _pack_log.append(PackRequest(w, cout, cin, transposed, stride))
     if _pack_scope_depth > 0:
         ent, fresh = _pack_entry(lib, w, cout, cin, layout, transposed, stride)
         if fresh:
             return ent[2]
-        buf = ent[2]
     else:
-        ent = None
         skey = (w.device.index, _stream(), _pack_floats(lib, cout, cin, layout))
-        buf = _pack_scratch.get(skey)
-        if buf is None:
-            buf = _pack_scratch[skey] = torch.empty(skey[2], dtype=torch.float32, device=w.device)
+        if skey not in _pack_scratch:
+            _pack_scratch[skey] = torch.empty(skey[2], dtype=torch.float32, device=w.device)
+        ent = [False, -1, _pack_scratch[skey]]          # un-cached: an entry nobody reads again
     if split_layout:
         wmax = None
         if _f16():          # a fresh (zeroed) slot per pack: the bound follows the weights down as well as up
             wmax = new_amax_slot(w.device)
             check(lib.vg_absmax(w.data_ptr(), w.numel(), wmax.data_ptr(), _stream()), "vg_absmax")
-        check(lib.vg_conv5x5_pack_bf16split(w.data_ptr(), buf.data_ptr(), cout, cin, int(transposed), stride, _planes(),
+        check(lib.vg_conv5x5_pack_bf16split(w.data_ptr(), ent[2].data_ptr(), cout, cin, int(transposed), stride, _planes(),
                                          _ptr(wmax), _stream()), "vg_conv5x5_pack_bf16split")
     else:
-        check(lib.vg_conv5x5_pack(w.data_ptr(), buf.data_ptr(), cout, cin, int(transposed), stride, _stream()),
+        check(lib.vg_conv5x5_pack(w.data_ptr(), ent[2].data_ptr(), cout, cin, int(transposed), stride, _stream()),
               "vg_conv5x5_pack")
-    if ent is not None:
-        ent[0], ent[1] = True, w._version
-    return buf
+    ent[0], ent[1] = True, w._version
+    return ent[2]
 
 
-_pack_log = None      # while a list: every split-layout pack request appends (weight tensor, cout, cin, transposed, stride)
+PackRequest = NamedTuple("PackRequest", [("w", torch.Tensor), ("cout", int), ("cin", int), ("transposed", bool), ("stride", int)])
+_pack_log = None      # while a list: every split-layout pack request appends its PackRequest (which keeps the weight alive)
 
 
 class record_pack_requests:
@@ -450,35 +465,32 @@ class record_pack_requests:
 
 
 def prepack_filters(requests):
-    """Pack (split layout) every listed filter whose cached pack is stale, all in one launch.  ``requests``:
-    (weight, cout, cin, transposed, stride) tuples as `record_pack_requests` collects them.  Only inside a
+    """Pack (split layout) every listed filter whose pack is stale, all in one launch, each into the one buffer its weight
+    object ever has.  ``requests``: `PackRequest`s as `record_pack_requests` collects them.  Only inside a
     `packed_filter_scope` (outside it nothing is cached)."""
     if _pack_scope_depth <= 0 or not requests or not _planes():
         return
     lib = _lib.load()
-    todo = []
-    for (w, cout, cin, transposed, stride) in requests:
-        ent, fresh = _pack_entry(lib, w, cout, cin, PACK_SPLIT, transposed, stride)
-        if not fresh:
-            todo.append((w, ent, cout, cin, transposed, stride))
+    entries = [(r, *_pack_entry(lib, r.w, r.cout, r.cin, PACK_SPLIT, r.transposed, r.stride)) for r in requests]
+    todo = [(r, _record(r.w), ent) for r, ent, fresh in entries if not fresh]
     if not todo:
         return
     arr = (_lib.PackEntry * len(todo))()
-    wmax = {}
+    wmax = {}                            # weight record -> bound slot
     if _f16():                           # the filters' bounds first, all in one launch (one per weight, not per layout)
-        for (w, *_r) in todo:
-            if w.data_ptr() not in wmax:
-                wmax[w.data_ptr()] = (w, new_amax_slot(w.device))
+        for r, rec, _ent in todo:
+            if rec not in wmax:
+                wmax[rec] = new_amax_slot(r.w.device)
         am = (_lib.AbsmaxEntry * len(wmax))()
-        for i, (w, slot) in enumerate(wmax.values()):
-            am[i] = _lib.AbsmaxEntry(w.data_ptr(), w.numel(), slot.data_ptr())
+        for i, (rec, slot) in enumerate(wmax.items()):
+            am[i] = _lib.AbsmaxEntry(rec.ref().data_ptr(), rec.ref().numel(), slot.data_ptr())
         check(lib.vg_absmax_multi(am, len(wmax), _stream()), "vg_absmax_multi")
-    for i, (w, ent, cout, cin, transposed, stride) in enumerate(todo):
-        slot = wmax[w.data_ptr()][1].data_ptr() if wmax else None
-        arr[i] = _lib.PackEntry(w.data_ptr(), ent[2].data_ptr(), cout, cin, int(transposed), stride, slot)
+    for i, (r, rec, ent) in enumerate(todo):
+        slot = wmax[rec].data_ptr() if wmax else None
+        arr[i] = _lib.PackEntry(r.w.data_ptr(), ent[2].data_ptr(), r.cout, r.cin, int(r.transposed), r.stride, slot)
     check(lib.vg_conv5x5_pack_bf16split_multi(arr, len(todo), _planes(), _stream()), "vg_conv5x5_pack_bf16split_multi")
-    for (w, ent, *_rest) in todo:
-        ent[0], ent[1] = True, w._version
+    for r, _rec, ent in todo:
+        ent[0], ent[1] = True, r.w._version
 
 
 # ---- the three entry points: validate, route, allocate, launch --------------------------------------------------------
@@ -688,27 +700,17 @@ def linear_split_ok(reduction, nweights):
     return LINEAR_SPLIT and _f16() and reduction % 32 == 0 and nweights >= LINEAR_SPLIT_MIN_WEIGHTS
 
 
-class _WeightBound(NamedTuple):
-    ref: weakref.ref        # to the weight: an id re-used by another tensor never matches
-    version: int
-    slot: torch.Tensor
-    emitted: bool           # by the optimizer step that wrote the weight; False: measured inside a packed_filter_scope
-
-
 def _weight_bound_entry(w):
-    """The table's entry for THIS tensor object as it is now (same object, same version counter), or None."""
-    ent = _wbounds.get(id(w))
-    return ent if ent is not None and ent.ref() is w and ent.version == w._version else None
+    """The `_Bound` recorded for THIS tensor object as it is now (same object, same version counter), or None."""
+    rec = _record(w)
+    return rec.bound if rec is not None and rec.bound is not None and rec.bound.version == w._version else None
 
 
 def set_weight_bound(w, bound):
     """``bound`` (one-element device tensor) holds max |w| as of now -- HipAdam's step emits it (VgAdamTensor.amax).
     Valid for THIS tensor object until the next torch-side in-place write (the version counter) or the next call for
     this weight."""
-    if len(_wbounds) > 256:                            # weights of trainers that no longer exist
-        for k in [k for k, e in _wbounds.items() if e.ref() is None]:
-            del _wbounds[k]
-    _wbounds[id(w)] = _WeightBound(weakref.ref(w), w._version, bound, True)
+    _record(w, create=True).bound = _Bound(w._version, bound, True)
 
 
 def weight_bound(w):
@@ -720,8 +722,8 @@ def weight_bound(w):
         return ent.slot
     slot = new_amax_slot(w.device)       # a fresh (zeroed) slot: the bound follows the weights down as well as up
     check(_lib.load().vg_absmax(w.data_ptr(), w.numel(), slot.data_ptr(), _stream()), "vg_absmax")
-    if _pack_scope_depth > 0:         # (a measured entry of a dead weight lives until the scope's next invalidation)
-        _wbounds[id(w)] = _WeightBound(weakref.ref(w), w._version, slot, False)
+    if _pack_scope_depth > 0:
+        _record(w, create=True).bound = _Bound(w._version, slot, False)
     return slot
 
 

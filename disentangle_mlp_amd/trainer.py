@@ -379,7 +379,7 @@ class _CapturedIteration:
                     o.state[p]["step"].fill_(v)
                 o._captured = []
             raise
-        # the graph holds raw pointers into the pack cache and the scratch buffers of ops: they live as long as it does
+        # the graph holds raw pointers into the weights' pack buffers and ops' scratch buffers: they live as long as it does
         self._buffers = ops.buffers_in_use()
         self.nbt_delta = [m._nbt_pending - n for m, n in zip(bn_modules, before_nbt)]
         self.flat_delta = [(f.bytes_reduced - b0, f.collectives - c0) for f, (b0, c0) in zip(self.flats, before_flat)]
@@ -440,14 +440,12 @@ class _GraphedSteps:
         if self._pack_plans is None:
             with ops.record_pack_requests() as rec:
                 out = body(lambda name=None: None)
-            owner = {p.data_ptr(): name for name, net in nets.items() for p in net.parameters()}
-            seen, plans = set(), {name: [] for name in nets}
-            for r in rec.requests:
-                k = (r[0].data_ptr(), r[3], r[4])
-                if k not in seen and r[0].data_ptr() in owner:
-                    seen.add(k)
-                    plans[owner[r[0].data_ptr()]].append(r)
-            self._pack_plans = plans
+            self._pack_plans = plans = {name: [] for name in nets}
+            for r in rec.requests:          # under the network that owns the parameter OBJECT, once per (object, layout)
+                name = next((n for n, net in nets.items() if any(p is r.w for p in net.parameters())), None)
+                if name is not None and not any(q.w is r.w and (q.transposed, q.stride) == (r.transposed, r.stride)
+                                                for q in plans[name]):
+                    plans[name].append(r)
             return out
         plans = self._pack_plans
         return body(lambda name=None: ops.prepack_filters(plans[name] if name is not None
@@ -943,7 +941,8 @@ class BetaVAEGANTrainer(_GraphedSteps):
     def load_in_place(self, ck):
         """`load` of a checkpoint dict of THIS trainer's shapes that copies into the existing parameter, buffer and moment
         tensors: a captured iteration stays valid and the next `step` replays it from the loaded state (bench.py times
-        from the initial state this way).  The packs a replay does not rewrite itself are rewritten here."""
+        from the initial state this way).  The packs a replay does not rewrite itself are rewritten here: into the very
+        buffers the graph reads, because `ops` allocates the pack buffer of a weight object once and never replaces it."""
         d_sd = ck["discriminator_model"]
         if all(k.startswith("module.") for k in d_sd):
             d_sd = {k[len("module."):]: v for k, v in d_sd.items()}

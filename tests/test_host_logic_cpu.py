@@ -280,25 +280,63 @@ def test_accumulate_param_grads_adds_inside_the_second_pass(monkeypatch):
 
 
 
-def test_captured_graph_keeps_the_buffers_it_points_at_alive():
-    """ADVICE (round 3, medium): a captured HIP graph holds raw device pointers into the pack cache and the scratch
-    buffers of `ops`; `packed_filter_scope.__enter__` rebuilds the cache once it exceeds `_PACK_CACHE_MAX` entries, and a
-    workspace is replaced when it grows.  `_CapturedIteration` therefore keeps `ops.buffers_in_use()`: the tensors outlive
-    the cache entries that pointed at them.  Host logic only (CPU tensors stand in for the device buffers)."""
+def _stub_pack_library(monkeypatch):
+    """`ops` with the library, the stream and the bound slots stubbed out, so that the packed-filter bookkeeping runs on
+    CPU tensors: returns (ops, lib, calls); every pack the "library" is asked for appends (symbol, weight pointer,
+    buffer pointer) to ``calls``."""
+    import types
+    from disentangle_mlp_amd import ops
+    calls = []
+
+    def multi(arr, n, planes, stream):
+        calls.extend(("vg_conv5x5_pack_bf16split_multi", arr[i].w, arr[i].packed) for i in range(n))
+        return 0
+
+    lib = types.SimpleNamespace(
+        vg_absmax=lambda *a: 0, vg_absmax_multi=lambda *a: 0,
+        vg_conv5x5_packed_floats=lambda cout, cin: 2 * cout * cin,
+        vg_conv5x5_packed_bf16split_bytes=lambda cout, cin, planes: 4 * 3 * cout * cin,
+        vg_conv5x5_pack=lambda w, buf, *a: calls.append(("vg_conv5x5_pack", w, buf)) or 0,
+        vg_conv5x5_pack_bf16split=lambda w, buf, *a: calls.append(("vg_conv5x5_pack_bf16split", w, buf)) or 0,
+        vg_conv5x5_pack_bf16split_multi=multi)
+    monkeypatch.setattr(ops._lib, "load", lambda: lib)
+    monkeypatch.setattr(ops, "_stream", lambda: 0)
+    monkeypatch.setattr(ops, "new_amax_slot", lambda device: torch.zeros(1))
+    return ops, lib, calls
+
+
+def test_captured_graph_keeps_the_buffers_it_points_at_alive(monkeypatch):
+    """ADVICE (round 3, medium): a captured HIP graph holds raw device pointers into the pack buffers and the scratch
+    buffers of `ops`; a pack buffer goes with its weight (the record of a collected weight leaves the table, nothing is
+    swept), and a workspace is replaced when it grows.  `_CapturedIteration` therefore keeps `ops.buffers_in_use()`: the
+    tensors outlive whatever `ops` does meanwhile.  Host logic only (CPU tensors stand in for the device buffers)."""
     import gc
     import weakref
-    from disentangle_mlp_amd import ops
-    saved = dict(ops._pack_cache), dict(ops._workspaces), dict(ops._pack_scratch)
+    ops, lib, _calls = _stub_pack_library(monkeypatch)
+    saved = dict(ops._records), dict(ops._workspaces), dict(ops._pack_scratch)
     try:
-        ops._pack_cache.clear(), ops._workspaces.clear(), ops._pack_scratch.clear()
-        for i in range(ops._PACK_CACHE_MAX + 2):                       # more entries than the cache tolerates
-            ops._pack_cache[(i, ops.PACK_SPLIT, False, 2, (1,), 3)] = [True, 0, torch.zeros(8)]
+        ops._records.clear(), ops._workspaces.clear(), ops._pack_scratch.clear()
+        # without a capture: the packs of a weight live exactly as long as the weight object
+        w = torch.zeros(4, 4, 5, 5)
+        with ops.packed_filter_scope():
+            lone = weakref.ref(ops._packed_filter(lib, w, 4, 4, ops.PACK_SPLIT, False, 2))
+        assert ops._record(w) is not None and len(ops._records) == 1 and lone() is not None
+        del w
+        gc.collect()
+        assert len(ops._records) == 0 and lone() is None                 # no record left, its buffer freed
+        # with one: what `buffers_in_use()` returned survives the weight, the scopes, the invalidations
+        w = torch.zeros(4, 4, 5, 5)
+        with ops.packed_filter_scope():
+            bufs = [ops._packed_filter(lib, w, 4, 4, layout, False, 2) for layout in (ops.PACK_SPLIT, ops.PACK_FP32)]
         ops._workspaces[("cpu", None, 0)] = torch.zeros(16, dtype=torch.uint8)
         held = ops.buffers_in_use()                                      # what a capture keeps
         refs = [weakref.ref(t) for t in held]
-        assert len(held) == ops._PACK_CACHE_MAX + 3
-        with ops.packed_filter_scope():                                  # the next trainer's scope: the cache is rebuilt
-            assert len(ops._pack_cache) == 0
+        assert len(held) == 3 and all(any(t is b for t in held) for b in bufs)
+        del bufs, w                                                      # the weight is dropped while the graph lives
+        gc.collect()
+        assert len(ops._records) == 0 and [t is held[2] for t in ops.buffers_in_use()] == [True]
+        with ops.packed_filter_scope():                                  # the next trainer's scope
+            ops.invalidate_packed_filters()
         ops._workspaces[("cpu", None, 0)] = torch.zeros(32, dtype=torch.uint8)      # ... and the workspace regrown
         gc.collect()
         assert all(r() is not None for r in refs)                        # alive: the "graph" still owns them
@@ -306,8 +344,105 @@ def test_captured_graph_keeps_the_buffers_it_points_at_alive():
         gc.collect()
         assert all(r() is None for r in refs)                            # and gone with it
     finally:
-        ops._pack_cache.clear(), ops._workspaces.clear(), ops._pack_scratch.clear()
-        ops._pack_cache.update(saved[0]), ops._workspaces.update(saved[1]), ops._pack_scratch.update(saved[2])
+        ops._records.clear(), ops._workspaces.clear(), ops._pack_scratch.clear()
+        ops._records.update(saved[0]), ops._workspaces.update(saved[1]), ops._pack_scratch.update(saved[2])
+
+
+@pytest.mark.parametrize("layout", ["fp32", "split"])
+def test_a_pack_belongs_to_the_weight_object_not_to_its_address(monkeypatch, layout):
+    """Inside one scope a second tensor OBJECT over the same memory, with the same shape and the same version counter (a
+    weight that died and one allocated in its place look like this), is packed on its own; the first still hits."""
+    ops, lib, calls = _stub_pack_library(monkeypatch)
+    assert layout in (ops.PACK_FP32, ops.PACK_SPLIT)
+    w1 = torch.zeros(4, 4, 5, 5)
+    with ops.packed_filter_scope():
+        b1 = ops._packed_filter(lib, w1, 4, 4, layout, False, 2)
+        assert ops._packed_filter(lib, w1, 4, 4, layout, False, 2) is b1 and len(calls) == 1
+        w2 = w1.detach()
+        assert w2 is not w1
+        assert w2.data_ptr() == w1.data_ptr() and w2.shape == w1.shape and w2._version == w1._version
+        b2 = ops._packed_filter(lib, w2, 4, 4, layout, False, 2)
+        assert len(calls) == 2 and b2 is not b1                          # a pack call of its own, into its own buffer
+        assert calls[1][1:] == (w2.data_ptr(), b2.data_ptr()) and calls[0][2] == b1.data_ptr()
+        assert ops._packed_filter(lib, w1, 4, 4, layout, False, 2) is b1 and len(calls) == 2
+        assert ops._packed_filter(lib, w2, 4, 4, layout, False, 2) is b2 and len(calls) == 2
+
+
+def test_a_recorded_plan_is_repacked_into_the_buffer_it_was_recorded_with(monkeypatch):
+    """`trainer.load_in_place` re-packs a recorded plan for a captured graph that reads the buffers of the recording: the
+    buffer of (weight object, layout, transposed, stride, planes) is one tensor for as long as the weight lives, however
+    many other weights were packed, and however many scopes and invalidations passed, in between."""
+    ops, lib, calls = _stub_pack_library(monkeypatch)
+    w = torch.zeros(4, 4, 5, 5)
+    with ops.record_pack_requests() as rec, ops.packed_filter_scope():
+        buf = ops._packed_filter(lib, w, 4, 4, ops.PACK_SPLIT, True, 2)
+    plan = list(rec.requests)
+    assert len(plan) == 1 and plan[0].w is w and plan[0] == ops.PackRequest(w, 4, 4, True, 2)
+    others = [torch.zeros(4, 4, 5, 5) for _ in range(70)]
+    for o in others:
+        with ops.packed_filter_scope():
+            ops._packed_filter(lib, o, 4, 4, ops.PACK_SPLIT, True, 2)
+    ops.invalidate_packed_filters()
+    del calls[:]
+    with ops.packed_filter_scope():
+        ops.prepack_filters(plan)
+        assert calls == [("vg_conv5x5_pack_bf16split_multi", w.data_ptr(), buf.data_ptr())]
+        assert ops._packed_filter(lib, w, 4, 4, ops.PACK_SPLIT, True, 2) is buf and len(calls) == 1
+
+
+def test_invalidation_reaches_the_given_weight_objects_only(monkeypatch):
+    """`invalidate_packed_filters([w])` marks the packs of ``w`` stale, whatever its rank, and leaves those of another
+    weight fresh; without an argument it reaches every live weight.  A tensor that has no record is passed over."""
+    ops, lib, calls = _stub_pack_library(monkeypatch)
+    w, other = torch.zeros(4, 4, 5, 5), torch.zeros(4, 4, 5, 5)
+    ask = lambda t, transposed=False: ops._packed_filter(lib, t, 4, 4, ops.PACK_SPLIT, transposed, 2)
+    with ops.packed_filter_scope():
+        bw, bt, bo = ask(w), ask(w, True), ask(other)
+        assert len(calls) == 3 and bw is not bt
+        ops.invalidate_packed_filters([w, torch.zeros(4)])
+        assert all(not ent[0] for ent in ops._record(w).packs.values())
+        assert all(ent[0] for ent in ops._record(other).packs.values())
+        assert ask(other) is bo and len(calls) == 3                      # fresh: no pack call
+        assert ask(w) is bw and ask(w, True) is bt and len(calls) == 5   # stale: packed again, into the same buffers
+        assert calls[3][2] == bw.data_ptr() and calls[4][2] == bt.data_ptr()
+        ops.invalidate_packed_filters()
+        assert ask(other) is bo and ask(w) is bw and len(calls) == 7
+    assert all(not ent[0] for t in (w, other) for ent in ops._record(t).packs.values())     # stale outside a scope
+
+
+def test_pack_plan_sorts_requests_under_the_network_that_owns_the_parameter_object(monkeypatch):
+    """`_GraphedSteps._run_with_pack_plan`: the first iteration records what the convolutions ask for; the plan holds each
+    (parameter object, transposed, stride) once, under the network whose parameter it IS, and drops a weight that belongs
+    to none -- also one that merely shares a parameter's memory.  Later iterations re-pack per network from the plan."""
+    from disentangle_mlp_amd.trainer import _GraphedSteps
+    ops, lib, calls = _stub_pack_library(monkeypatch)
+    nets = {"a": torch.nn.Conv2d(4, 4, 5), "b": torch.nn.Conv2d(4, 4, 5)}
+    wa, wb = nets["a"].weight, nets["b"].weight
+    foreign, alias = torch.zeros(4, 4, 5, 5), wa.detach()
+    asked = [(wb, False), (wa, False), (foreign, False), (wa, True), (wa, False), (alias, False), (wb, False)]
+
+    def body(prepack):
+        with ops.packed_filter_scope():
+            prepack()
+            for t, transposed in asked:
+                ops._packed_filter(lib, t, 4, 4, ops.PACK_SPLIT, transposed, 2)
+            ops.invalidate_packed_filters()
+            prepack("a")
+            return len(calls)
+
+    steps = _GraphedSteps()
+    assert steps._run_with_pack_plan(body, nets) == 5                    # recorded only: packed one by one on first use
+    plans = steps._pack_plans
+    assert list(plans) == ["a", "b"]
+    assert [(r.w is wa, r.transposed, r.stride) for r in plans["a"]] == [(True, False, 2), (True, True, 2)]
+    assert [(r.w is wb, r.transposed, r.stride) for r in plans["b"]] == [(True, False, 2)]
+    del calls[:]
+    steps._run_with_pack_plan(body, nets)
+    multi = [c for c in calls if c[0] == "vg_conv5x5_pack_bf16split_multi"]
+    assert [c[1] for c in multi[:3]] == [wa.data_ptr(), wa.data_ptr(), wb.data_ptr()]     # prepack(): every network
+    assert [c[1] for c in multi[3:]] == [wa.data_ptr(), wa.data_ptr()]                    # prepack("a"): that one alone
+    singles = [c for c in calls if c[0] == "vg_conv5x5_pack_bf16split"]
+    assert len(singles) == 2 and {c[1] for c in singles} == {foreign.data_ptr(), alias.data_ptr()}
 
 
 # (op, Cin, H = W, Cout, stride, operand read through an affine, want_stats) at batch 128, then what the launch does under
@@ -464,13 +599,13 @@ def test_emitted_weight_bounds_belong_to_one_tensor_object_and_one_version(monke
     assert ops.weight_bound(w) is b
     key = id(w)
     w.add_(1.0)                                   # version bump: stale
-    ent = ops._wbounds[key]
-    assert ent.ref() is w and ent.version != w._version and ops._weight_bound_entry(w) is None
+    rec = ops._records[key]
+    assert rec.ref() is w and rec.bound.version != w._version and ops._weight_bound_entry(w) is None
     ops.set_weight_bound(w, b)
     assert ops.weight_bound(w) is b
-    del w
+    del w, rec
     gc.collect()
-    assert ops._wbounds[key].ref() is None        # a new tensor that re-uses the id can never match the dead reference
+    assert key not in ops._records                # a new tensor that re-uses the id finds no record at all
 
     # measured bounds, the measuring launch stubbed out: every measurement hands out a new slot
     slots = []
@@ -479,7 +614,7 @@ def test_emitted_weight_bounds_belong_to_one_tensor_object_and_one_version(monke
     monkeypatch.setattr(ops, "_stream", lambda: 0)
     w = torch.zeros(4, 4)
     first = ops.weight_bound(w)                   # outside a scope: measured per call, nothing stored
-    assert ops.weight_bound(w) is not first and len(slots) == 2 and id(w) not in ops._wbounds
+    assert ops.weight_bound(w) is not first and len(slots) == 2 and id(w) not in ops._records
     with ops.packed_filter_scope():
         m = ops.weight_bound(w)
         assert ops.weight_bound(w) is m and len(slots) == 3           # returned again for the same object

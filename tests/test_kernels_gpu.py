@@ -493,6 +493,32 @@ def test_packed_filter_cache_scope(H, fp32_arith):
     assert torch.equal(H.conv5x5_fwd(x, w, None, 1), y0)   # leaving the scope dropped the cache
 
 
+@pytest.mark.parametrize("arith", ["fp32", None], ids=["fp32", "default"])
+def test_packed_filters_belong_to_the_weight_object_not_to_its_address(H, arith):
+    """Two distinct tensor objects over the same memory, same shape, same version counter, with different contents
+    (written through .data) inside ONE scope: each convolution sees its own weight's values, bit for bit the un-scoped
+    call -- the second is never served the first one's pack."""
+    g = torch.Generator().manual_seed(6)
+    x = torch.randn(2, 16, 8, 8, generator=g).cuda()
+    a, b = ((torch.randn(32, 16, 5, 5, generator=g) * 0.1).cuda() for _ in range(2))
+    prev = H.CONV_ARITH
+    try:
+        H.CONV_ARITH = arith or prev
+        ya, yb = H.conv5x5_fwd(x, a, None, 1), H.conv5x5_fwd(x, b, None, 1)
+        assert not torch.equal(ya, yb)
+        mem = torch.empty_like(a)
+        w1, w2 = mem.detach(), mem.detach()
+        assert w1 is not w2 and w1.data_ptr() == w2.data_ptr() and w1.shape == w2.shape
+        with H.packed_filter_scope():
+            w1.data.copy_(a)
+            assert torch.equal(H.conv5x5_fwd(x, w1, None, 1), ya)
+            w2.data.copy_(b)
+            assert w1._version == w2._version
+            assert torch.equal(H.conv5x5_fwd(x, w2, None, 1), yb)
+    finally:
+        H.CONV_ARITH = prev
+
+
 def test_packed_filter_bad_args(H, fp32_arith):
     from disentangle_mlp_amd import _lib
     lib = _lib.load()

@@ -330,6 +330,40 @@ def test_betavaegan_notices_an_inf_pixel_and_recovers_from_a_checkpoint(graph):
     _assert_same(_weights(tr), ref_w)
 
 
+def test_load_in_place_rewrites_the_pack_buffers_the_captured_graph_reads():
+    """The captured phase 1 reads the discriminator's packs from buffers whose addresses the graph holds; `load_in_place`
+    re-packs them from the recorded plan.  70 other filters packed in between (another trainer, a test's throw-away
+    weights) must not make it write anywhere else: a pack buffer belongs to its weight object for life.  The step on
+    another batch before the load is what makes stale buffers visible -- without it they hold the checkpoint's packs.
+    With the address-keyed cache this replaced, more than 64 entries made the next scope clear the cache, so that the load
+    packed into new buffers while the replay read the old ones: so the code read; that failure was never run."""
+    from disentangle_mlp_amd import ops
+    from disentangle_mlp_amd import trainer as T
+    x, lat = _batch()
+    tr, twin = T.BetaVAEGANTrainer(beta=25.0, graph=True), T.BetaVAEGANTrainer(beta=25.0, graph=True)
+    for _ in range(4):                                       # two eager warm-up iterations, the capture, one more replay
+        tr.step(x, *lat)
+        twin.step(x, *lat)
+    assert len(tr._graphs) == 1 and len(twin._graphs) == 1
+    cap = next(iter(tr._graphs.values()))
+    _assert_same(_weights(tr), _weights(twin))
+    ck = copy.deepcopy(tr.checkpoint(1))
+    x2, lat2 = _batch(seed=12)
+    tr.step(x2, *lat2)                                       # the weights, and the packs, move on
+    g = torch.Generator().manual_seed(13)
+    xs = torch.randn(1, 16, 8, 8, generator=g).cuda()
+    for _ in range(70):
+        with ops.packed_filter_scope():
+            ops.conv5x5_fwd(xs, (torch.randn(16, 16, 5, 5, generator=g) * 0.1).cuda(), None, 1)
+    tr.load_in_place(ck)
+    out = {k: v.clone() for k, v in tr.step(x, *lat).items()}
+    ref = {k: v.clone() for k, v in twin.step(x, *lat).items()}
+    assert len(tr._graphs) == 1 and next(iter(tr._graphs.values())) is cap           # the same capture replayed
+    for k in ref:
+        assert torch.equal(_bits(out[k].float()), _bits(ref[k].float())), k
+    _assert_same(_weights(tr), _weights(twin))
+
+
 @pytest.mark.parametrize("graph", [True, False], ids=["graph", "eager"])
 @pytest.mark.parametrize("which", ["vae", "gan"])
 def test_vae_and_gan_trainers_notice_an_inf_pixel(which, graph):

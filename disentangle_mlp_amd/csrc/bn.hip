@@ -863,6 +863,259 @@ extern "C" int vg_bn_act_bwd(const float* gy, const float* x, const float* gamma
   return 0;
 }
 
+// ---- BatchNorm on RUNNING statistics (eval mode: nn.BatchNorm*.eval() of the reference's modules, model.py:451-458, 462,
+// 468, 492, 496-505, 390-400) ---------------------------------------------------------------------------------------------
+namespace {
+
+// Coefficients from the running statistics: scale = gamma / sqrt(running_var + eps), shift = beta - running_mean * scale,
+// invstd for the backward.  The running buffers are read, never written.  With the producing convolution's statistics
+// slots (stats[slot][C][2], `count` values per channel) and act_amax: also an upper bound of max |act(scale x + shift)|
+// over the tensor the slots were taken of, from the sums alone.  bn_act_bound's argument, centred on the batch mean
+// instead of on the BatchNorm's own: with S1, S2 the computed sums, m = S1 / n, q = S2 / n, var = max(q - m^2, 0),
+//   |x - T1/n| <= sigma sqrt(n - 1)  (Samuelson, EXACT mean and sigma),  sigma^2 <= var_up = var + (3.01 delta + 2^-50) q,
+//   |T1/n - m| <= 1.01 delta sqrt(q)                                      (both derived above bn_act_bound)
+//   => |scale x + shift| <= |scale| (sqrt(var_up (n - 1)) + 1.01 delta sqrt(q)) + |scale m + shift|.
+// scale m + shift is evaluated in fp64 from the fp32 coefficients WRITTEN (what the consumer multiplies by); 2^-21 of its
+// two terms covers that evaluation, the consumer's fmaf and coefficients rounded otherwise (the exact ones differ from
+// the written by 2^-23 relative); (1 + 2^-20): the fp64 -> fp32 conversion.  ReLU / LeakyReLU(0.2) only shrink magnitudes.
+// A constant channel has sigma = 0 <= var_up; a variance lost to cancellation is covered by the delta q term.
+// CH channels per workgroup x KL partial-lanes: lane kl sums every KL-th slot, the KL sums of a channel are added in order.
+template <int CH, int KL>
+__global__ __launch_bounds__(CH * KL) void bn_eval_coeffs_kernel(const float* __restrict__ gamma,
+                                                                 const float* __restrict__ beta,
+                                                                 const float* __restrict__ running_mean,
+                                                                 const float* __restrict__ running_var,
+                                                                 float* __restrict__ scale, float* __restrict__ shift,
+                                                                 float* __restrict__ invstd, int C, float eps,
+                                                                 const float* __restrict__ stats, int nslots, double count,
+                                                                 unsigned* __restrict__ act_amax, double delta) {
+  __shared__ double r1[KL][CH], r2[KL][CH];
+  const int cl = threadIdx.x % CH, kl = threadIdx.x / CH;
+  const int c = blockIdx.x * CH + cl;
+  const bool bound = stats != nullptr && act_amax != nullptr;      // uniform over the grid
+  if (bound) {
+    double s1 = 0.0, s2 = 0.0;
+    if (c < C)
+      for (int k = kl; k < nslots; k += KL) {
+        s1 += (double)stats[((size_t)k * C + c) * 2];
+        s2 += (double)stats[((size_t)k * C + c) * 2 + 1];
+      }
+    r1[kl][cl] = s1;
+    r2[kl][cl] = s2;
+    __syncthreads();
+  }
+  if (kl != 0 || c >= C) return;
+  const float is = (float)(1.0 / sqrt((double)running_var[c] + (double)eps));
+  const float sc = gamma[c] * is;
+  const float sh = beta[c] - running_mean[c] * sc;
+  scale[c] = sc;
+  shift[c] = sh;
+  invstd[c] = is;
+  if (!bound) return;
+  double s1 = 0.0, s2 = 0.0;
+  for (int k = 0; k < KL; ++k) {
+    s1 += r1[k][cl];
+    s2 += r2[k][cl];
+  }
+  const double m = s1 / count, q = s2 / count;
+  double var = q - m * m;
+  if (var < 0.0) var = 0.0;
+  const double var_up = var + (3.01 * delta + 0x1p-50) * q;
+  const double dev = sqrt(var_up * fmax(count - 1.0, 0.0)) + 1.01 * delta * sqrt(q);
+  const double asc = fabs((double)sc);
+  const double b = asc * dev + fabs((double)sc * m + (double)sh) + 0x1p-21 * (asc * fabs(m) + fabs((double)sh));
+  atomicMax(act_amax, __float_as_uint((float)(b * (1.0 + 0x1p-20))));
+}
+
+__device__ __forceinline__ float act_slope_of(int act) { return act == VG_ACT_RELU ? 0.f : act == VG_ACT_LRELU ? 0.2f : 1.f; }
+
+// gy * act'(pre): a multiplication by 1 or by the slope (a NaN gradient stays a NaN, as act_slope keeps a NaN value); a NaN
+// pre-activation under ReLU / LeakyReLU has no derivative: NaN
+__device__ __forceinline__ float eval_act_grad(float pre, float g, float slope) {
+  const float d = pre > 0.f ? 1.f : slope;
+  return (pre != pre && slope != 1.f) ? pre : g * d;
+}
+
+// Backward of y = act(x * sc + sh) with FROZEN coefficients, one pass: gx = gy act'(pre) sc; dbeta = sum gy act'(pre),
+// dgamma = sum gy act'(pre) (x - mean) invstd.  Workgroup (c, k) owns slice k of channel c (make_slicing), writes its gx
+// and -- part != NULL -- its fp64 partial sums part[c][k][2]; with ONE slice per channel it writes dgamma / dbeta itself.
+__global__ __launch_bounds__(NT) void bn_eval_bwd_kernel(const float* __restrict__ gy, const float* __restrict__ x,
+                                                         const float* __restrict__ scale, const float* __restrict__ shift,
+                                                         const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                         float* __restrict__ gx, double* __restrict__ part,
+                                                         float* __restrict__ dgamma, float* __restrict__ dbeta, int B,
+                                                         int C, int HW, long per, int ns, int act,
+                                                         unsigned* __restrict__ gx_amax, int vec) {
+  __shared__ double red[NT / 64];
+  const bool accp = (act & 0x100) != 0;        // as bn_apply_kernel
+  const float slope = act_slope_of(act & 0xff);
+  const int c = blockIdx.x, k = blockIdx.y;
+  const long total = (long)B * HW;
+  const long v0 = (long)k * per, v1 = min(v0 + per, total);
+  const int hw_shift = (HW & (HW - 1)) == 0 ? __builtin_ctz(HW) : -1;
+  const float sc = scale[c], sh = shift[c], mu = mean[c], is = invstd[c];
+  double s1 = 0.0, s2 = 0.0;
+  unsigned am = 0;
+  auto one = [&](float xv, float gv) -> float {
+    const float g = eval_act_grad(fmaf(xv, sc, sh), gv, slope);
+    s1 += g;
+    s2 += (double)(g * ((xv - mu) * is));
+    const float r = g * sc;
+    am = max(am, abs_bits(r));
+    return r;
+  };
+  if (vec) {
+    for (long v = v0 + 4L * threadIdx.x; v < v1; v += 4L * NT) {
+      const long b = hw_shift >= 0 ? (v >> hw_shift) : v / HW, hw = v - b * HW;
+      const size_t off = ((size_t)b * C + c) * HW + hw;
+      const float4 xv = *reinterpret_cast<const float4*>(x + off);
+      const float4 gv = *reinterpret_cast<const float4*>(gy + off);
+      float4 o;
+      o.x = one(xv.x, gv.x);
+      o.y = one(xv.y, gv.y);
+      o.z = one(xv.z, gv.z);
+      o.w = one(xv.w, gv.w);
+      *reinterpret_cast<float4*>(gx + off) = o;
+    }
+  } else {
+    for (long v = v0 + threadIdx.x; v < v1; v += NT) {
+      const long b = hw_shift >= 0 ? (v >> hw_shift) : v / HW, hw = v - b * HW;
+      const size_t off = ((size_t)b * C + c) * HW + hw;
+      gx[off] = one(x[off], gy[off]);
+    }
+  }
+  if (part || dgamma || dbeta) {               // uniform over the grid
+    const double t1 = block_sum<NT>(s1, red);
+    const double t2 = block_sum<NT>(s2, red);
+    if (threadIdx.x == 0) {
+      if (part) {
+        part[((size_t)c * ns + k) * 2 + 0] = t1;
+        part[((size_t)c * ns + k) * 2 + 1] = t2;
+      } else {                                 // ns == 1
+        if (dbeta) dbeta[c] = (float)t1 + (accp ? dbeta[c] : 0.f);
+        if (dgamma) dgamma[c] = (float)t2 + (accp ? dgamma[c] : 0.f);
+      }
+    }
+  }
+  if (gx_amax) block_amax_atomic<NT>(am, gx_amax);
+}
+
+__global__ __launch_bounds__(NT) void bn_eval_bwd_finalize_kernel(const double* __restrict__ part, int ns, int C,
+                                                                  float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                                  int accp) {
+  const int c = blockIdx.x * NT + threadIdx.x;
+  if (c >= C) return;
+  double s1 = 0.0, s2 = 0.0;
+  for (int k = 0; k < ns; ++k) {               // fixed order
+    s1 += part[((size_t)c * ns + k) * 2];
+    s2 += part[((size_t)c * ns + k) * 2 + 1];
+  }
+  if (dbeta) dbeta[c] = (float)s1 + (accp ? dbeta[c] : 0.f);
+  if (dgamma) dgamma[c] = (float)s2 + (accp ? dgamma[c] : 0.f);
+}
+
+// The same for BatchNorm1d, x [B][C]: the geometry of bn1d_bwd_kernel, one pass.
+__global__ __launch_bounds__(NT) void bn1d_eval_bwd_kernel(const float* __restrict__ gy, const float* __restrict__ x,
+                                                           const float* __restrict__ scale, const float* __restrict__ shift,
+                                                           const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                           float* __restrict__ gx, float* __restrict__ dgamma,
+                                                           float* __restrict__ dbeta, int B, int C, int act,
+                                                           unsigned* __restrict__ gx_amax) {
+  const bool accp = (act & 0x100) != 0;
+  const float slope = act_slope_of(act & 0xff);
+  __shared__ double r1[B1_SL][B1_CH], r2[B1_SL][B1_CH];
+  const int cl = threadIdx.x % B1_CH, sl = threadIdx.x / B1_CH;
+  const int c = blockIdx.x * B1_CH + cl;
+  const bool cok = c < C;
+  double s1 = 0.0, s2 = 0.0;
+  unsigned am = 0;
+  if (cok) {
+    const float sc = scale[c], sh = shift[c], mu = mean[c], is = invstd[c];
+    for (int b = sl; b < B; b += B1_SL) {
+      const size_t o = (size_t)b * C + c;
+      const float xv = x[o];
+      const float g = eval_act_grad(fmaf(xv, sc, sh), gy[o], slope);
+      s1 += g;
+      s2 += (double)(g * ((xv - mu) * is));
+      const float r = g * sc;
+      am = max(am, abs_bits(r));
+      gx[o] = r;
+    }
+  }
+  r1[sl][cl] = s1;
+  r2[sl][cl] = s2;
+  __syncthreads();
+  if (sl == 0 && cok) {
+    double t1 = 0.0, t2 = 0.0;
+#pragma unroll
+    for (int k = 0; k < B1_SL; ++k) {
+      t1 += r1[k][cl];
+      t2 += r2[k][cl];
+    }
+    if (dbeta) dbeta[c] = (float)t1 + (accp ? dbeta[c] : 0.f);
+    if (dgamma) dgamma[c] = (float)t2 + (accp ? dgamma[c] : 0.f);
+  }
+  if (gx_amax) block_amax_atomic<NT>(am, gx_amax);
+}
+
+}  // namespace
+
+extern "C" int vg_bn_eval_coeffs(const float* gamma, const float* beta, const float* running_mean,
+                                 const float* running_var, float* scale, float* shift, float* invstd, int C, float eps,
+                                 int act, const float* stats, int nslots, double count, float* act_amax, void* stream) {
+  if (!gamma || !beta || !running_mean || !running_var || !scale || !shift || !invstd || C <= 0) return VG_ERR_BAD_ARG;
+  if (act < VG_ACT_NONE || act > VG_ACT_LRELU) return VG_ERR_BAD_ARG;
+  const bool bound = stats != nullptr && act_amax != nullptr;
+  if (bound && (nslots <= 0 || !(count > 0))) return VG_ERR_BAD_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const double delta = bound ? slot_sums_delta(nslots) : 0.0;
+  const float* sp = bound ? stats : nullptr;
+  unsigned* am = bound ? (unsigned*)act_amax : nullptr;
+  // few slots (or none): 32 channels x 8 partial-lanes; many (the ring kernels leave 512-2048, a thin first layer 16 384):
+  // 8 channels x 128 partial-lanes, as bn_finalize_wide_kernel -- ONE launch either way
+  if (!bound || nslots <= 64)
+    hipLaunchKernelGGL((bn_eval_coeffs_kernel<32, 8>), dim3(cdiv(C, 32)), dim3(256), 0, st, gamma, beta, running_mean,
+                       running_var, scale, shift, invstd, C, eps, sp, nslots, count, am, delta);
+  else
+    hipLaunchKernelGGL((bn_eval_coeffs_kernel<8, 128>), dim3(cdiv(C, 8)), dim3(1024), 0, st, gamma, beta, running_mean,
+                       running_var, scale, shift, invstd, C, eps, sp, nslots, count, am, delta);
+  VG_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int vg_bn_eval_act_bwd(const float* gy, const float* x, const float* scale, const float* shift,
+                                  const float* mean, const float* invstd, float* gx, float* dgamma, float* dbeta, int B,
+                                  int C, int HW, int act, int accumulate_param_grads, float* gx_amax, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+  unsigned* am = (unsigned*)gx_amax;
+  if (!gy || !x || !scale || !shift || !mean || !invstd || !gx || B <= 0 || C <= 0 || HW <= 0) return VG_ERR_BAD_ARG;
+  if (act < VG_ACT_NONE || act > VG_ACT_LRELU) return VG_ERR_BAD_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const int act_apply = act | (accumulate_param_grads ? 0x100 : 0);
+  if (HW == 1) {
+    hipLaunchKernelGGL(bn1d_eval_bwd_kernel, dim3(cdiv(C, B1_CH)), dim3(NT), 0, st, gy, x, scale, shift, mean, invstd, gx,
+                       dgamma, dbeta, B, C, act_apply, am);
+    VG_CHECK_LAUNCH();
+    return 0;
+  }
+  const Slicing s = make_slicing(B, C, HW);      // ns <= NS_MAX: the partials fit vg_bn_workspace_bytes(C)
+  const bool want_p = dgamma || dbeta;
+  double* part = nullptr;
+  if (want_p && s.ns > 1) {
+    if (!workspace || workspace_bytes < ws_bytes(C)) return VG_ERR_WORKSPACE;
+    part = (double*)workspace;
+  }
+  hipLaunchKernelGGL(bn_eval_bwd_kernel, dim3(C, s.ns), dim3(NT), 0, st, gy, x, scale, shift, mean, invstd, gx, part,
+                     dgamma, dbeta, B, C, HW, s.per, s.ns, act_apply, am, streams_vec(HW, x, gy, gx));
+  VG_CHECK_LAUNCH();
+  if (part) {
+    hipLaunchKernelGGL(bn_eval_bwd_finalize_kernel, dim3(cdiv(C, NT)), dim3(NT), 0, st, (const double*)part, s.ns, C,
+                       dgamma, dbeta, accumulate_param_grads ? 1 : 0);
+    VG_CHECK_LAUNCH();
+  }
+  return 0;
+}
+
 extern "C" int vg_channel_sum(const float* g, float* out, int B, int C, int HW, void* workspace,
                               size_t workspace_bytes, void* stream) {
   if (!g || !out || B <= 0 || C <= 0 || HW <= 0) return VG_ERR_BAD_ARG;

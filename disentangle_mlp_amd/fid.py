@@ -192,15 +192,32 @@ def get_fid(path_data, path_pretrained, inception="", lowprofile=False, feature_
     return calculate_fid_given_paths([path_data, path_pretrained], inception, lowprofile, feature_extractor, device)
 
 
-def sample_statistics(fn, n_samples, n_hidden, feature_extractor, device="cuda", decode_batch=None):
+def _eval_nets(fn, eval_mode):
+    """The networks ``eval_mode=True`` puts into eval mode around ``fn``: ``fn`` itself when it is a module, the module
+    it is a bound method of (``netEG.decode``) otherwise.  () for False."""
+    if not eval_mode:
+        return ()
+    net = fn if isinstance(fn, torch.nn.Module) else getattr(fn, "__self__", None)
+    if not isinstance(net, torch.nn.Module):
+        raise ValueError("eval_mode=True needs fn to be a module or a bound method of one (netEG.decode); wrap a "
+                         "plain function's call in model.eval_mode(net) yourself")
+    return (net,)
+
+
+def sample_statistics(fn, n_samples, n_hidden, feature_extractor, device="cuda", decode_batch=None, eval_mode=False):
     """(mu, sigma), fp64 device tensors, of the pool_3 activations of ``n_samples`` decoded N(0, 1) codes -- what
     utils.py:23-29 + scoring/fid.py:286-300 compute through files, without leaving the device.
 
     The codes are drawn as ``image_io.generate_fid_samples`` draws them (``torch.randn(n_samples, n_hidden)`` on the
     CPU: the same seed gives the same latents) and decoded by ``fn`` (``netEG.decode``) as ONE batch, like the
-    reference.  ``decode_batch`` decodes them in pieces instead: a DEVIATION, because the reference never calls
-    ``.eval()`` and train-mode BatchNorm makes a sample depend on the batch it is decoded with; it is opt-in, for
-    ``n_samples`` whose activations do not fit.  Each decoded image is quantised as ``save_image(x[i], normalize=True)``
+    reference.  ``decode_batch`` decodes them in pieces instead: under the default train-mode BatchNorm a DEVIATION,
+    because the reference never calls ``.eval()`` and batch statistics make a sample depend on the batch it is decoded
+    with; it is opt-in, for ``n_samples`` whose activations do not fit.  ``eval_mode=True`` wraps the decoding in
+    ``model.eval_mode(net)``, ``net`` the module ``fn`` is (or is a bound method of): BatchNorm on its running
+    statistics, every sample a function of its own latent alone -- ``decode_batch`` is then no deviation, only a memory
+    setting -- and the network is back in its previous mode afterwards.  The default keeps the reference's train-mode
+    behaviour.
+    Each decoded image is quantised as ``save_image(x[i], normalize=True)``
     would (``ops.quantize_each_u8``); ``feature_extractor`` is an ``InceptionFeatureExtractor`` (its ``features_u8`` is
     used) or any callable on device uint8 images [n,h,w,3] -> [n,d]."""
     n_samples = int(n_samples)
@@ -211,9 +228,9 @@ def sample_statistics(fn, n_samples, n_hidden, feature_extractor, device="cuda",
     if decode_batch is not None and int(decode_batch) < 1:
         raise ValueError("decode_batch must be positive")
     extract = getattr(feature_extractor, "features_u8", feature_extractor)
-    from . import ops
+    from . import model, ops
     st = None
-    with torch.no_grad():
+    with torch.no_grad(), model.eval_mode(*_eval_nets(fn, eval_mode)):
         z = torch.randn(n_samples, n_hidden)                 # CPU draw, like the reference
         step = n_samples if decode_batch is None else int(decode_batch)
         for s in range(0, n_samples, step):
@@ -225,10 +242,11 @@ def sample_statistics(fn, n_samples, n_hidden, feature_extractor, device="cuda",
     return st.finalize()
 
 
-def get_fid_of_generator(fn, n_samples, n_hidden, path_pretrained, inception="", feature_extractor=None, device="cuda"):
+def get_fid_of_generator(fn, n_samples, n_hidden, path_pretrained, inception="", feature_extractor=None, device="cuda",
+                         eval_mode=False):
     """FID of the generator ``fn`` (``netEG.decode``) against ``path_pretrained`` (``.npz`` statistics, or an image
     folder: `_handle_path`): ``generate_fid_samples`` + ``get_fid`` (new_betavaegan.py:231-235) with nothing written.
-    ``inception`` as in `get_fid`; ``feature_extractor`` as in `sample_statistics`."""
+    ``inception`` as in `get_fid`; ``feature_extractor`` and ``eval_mode`` as in `sample_statistics`."""
     if int(n_samples) < 2:
         raise ValueError("covariance needs at least 2 samples")
     if not os.path.exists(path_pretrained):
@@ -240,5 +258,5 @@ def get_fid_of_generator(fn, n_samples, n_hidden, path_pretrained, inception="",
         from .inception import InceptionFeatureExtractor
         feature_extractor = InceptionFeatureExtractor(weights, device=device)
     m2, s2 = _handle_path(path_pretrained, feature_extractor, device)
-    m1, s1 = sample_statistics(fn, n_samples, n_hidden, feature_extractor, device)
+    m1, s1 = sample_statistics(fn, n_samples, n_hidden, feature_extractor, device, eval_mode=eval_mode)
     return calculate_frechet_distance(m1, s1, m2, s2, device=device)

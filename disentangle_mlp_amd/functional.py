@@ -387,6 +387,93 @@ class BNConvFn(Function):
         return gx, dg, db, gw, gb, None, None, None, None, None, None, None, None, None
 
 
+def _bn_eval_backward(ctx, gy, x, scale, shift, mean, invstd, need_p, key):
+    """vg_bn_eval_act_bwd with the parameter gradients under the accumulate protocol (BNEvalActFn, BNEvalConvFn); ``key``:
+    id of the layer's gamma, as in `_bn_backward`."""
+    slot = _grad_slot(ctx.acc if need_p else None, key)
+    gx, dg, db = ops.bn_eval_act_bwd(gy, x, scale, shift, mean, invstd, ctx.act, need_p, accumulate_into=slot.prev)
+    return (gx,) + (slot.hand_over((dg, db)) if need_p else (dg, db))
+
+
+def _frozen(ctx, running_mean):
+    """The running mean as the backward will need it: a copy where a backward can follow (the buffer may move before
+    it), the buffer itself where none can (inference: no copy launch per layer)."""
+    return running_mean.clone() if any(ctx.needs_input_grad) else running_mean
+
+
+class BNEvalActFn(Function):
+    """Eval-mode BatchNorm1d/2d (running statistics, F.batch_norm(training=False)) + {none, ReLU, LeakyReLU(0.2)},
+    materialised: one coefficient launch, one normalise pass.  The running buffers are read and never written.  The
+    Function keeps its own scale / shift / invstd and a copy of the running mean: a train-mode step between forward and
+    backward moves the buffers and must not move the gradient.
+    Returns (y, the bound slot of max |y| the normalise pass emitted -- non-differentiable -- or None)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, eps, act):
+        scale, shift, invstd = ops.bn_eval_coeffs(gamma, beta, running_mean, running_var, eps, act)
+        y = ops.affine_act(x, scale, shift, act)
+        ctx.act, ctx.key = act, id(gamma)
+        ctx.acc = _acc_ctx()
+        ctx.save_for_backward(x, scale, shift, invstd, _frozen(ctx, running_mean))
+        bound = ops.known_amax(y)
+        if bound is not None:
+            ctx.mark_non_differentiable(bound)
+        ctx.set_materialize_grads(False)      # as ConvStatsFn
+        return y, bound
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy, _):
+        if gy is None:
+            return (None,) * 7
+        x, scale, shift, invstd, mean = ctx.saved_tensors
+        need_p = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        gx, dg, db = _bn_eval_backward(ctx, gy.contiguous(), x, scale, shift, mean, invstd, need_p, ctx.key)
+        return gx, dg, db, None, None, None, None
+
+
+class BNEvalConvFn(Function):
+    """[eval-mode BatchNorm2d + activation] -> [5x5 conv / transposed conv], the normalised tensor never materialised:
+    `BNConvFn` with the coefficients from the running statistics (one small launch, no finalisation, no buffer update).
+    ``stats_in``: the statistics slots the producing convolution left of x -- they no longer decide the coefficients,
+    they give the fp16 planes' bound of max |act(BN(x))| without a pass over x (vg_bn_eval_coeffs); without them
+    `ops.amax_of` measures x through the affine.  Backward: data gradient of the convolution, then the frozen-statistics
+    BatchNorm backward against the saved raw x; the weight gradient reads x through the same affine.
+    Returns (y, statistics slots of y -- empty when the kernel cannot emit them)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, w, bias, running_mean, running_var, eps, act, stride, transposed, bias_grad, stats_in):
+        count = x.numel() // x.shape[1]
+        scale, shift, invstd, bound = ops.bn_eval_coeffs(gamma, beta, running_mean, running_var, eps, act, stats_in, count,
+                                                         want_bound=True)
+        conv = ops.convT5x5_fwd if transposed else ops.conv5x5_fwd
+        y, stats = conv(x, w, bias, stride, in_affine=(scale, shift, act, bound), want_stats=True)
+        stats = stats if stats is not None else x.new_empty(0)
+        ctx.act, ctx.stride, ctx.transposed, ctx.bias_grad, ctx.key = act, stride, transposed, bias_grad, id(gamma)
+        ctx.acc = _acc_ctx()
+        ctx.save_for_backward(x, scale, shift, invstd, _frozen(ctx, running_mean), w, bound)
+        ctx.mark_non_differentiable(stats)
+        ctx.set_materialize_grads(False)      # as ConvStatsFn
+        return y, stats
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy, _):
+        if gy is None:
+            return (None,) * 13
+        x, scale, shift, invstd, mean, w, bound = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        need_p = need[1] or need[2]
+
+        def bn_backward(ga):                                 # ga: the gradient w.r.t. act(BN(x))
+            return (ga,) + _bn_eval_backward(ctx, ga, x, scale, shift, mean, invstd, need_p, ctx.key)
+
+        bn, gw, gb = _conv_backward(ctx, x, w, gy.contiguous(), need[0] or need_p, need[3], need[4],
+                                    aff=(scale, shift, ctx.act, bound), then=bn_backward)
+        _ga, gx, dg, db = bn if bn is not None else (None,) * 4
+        return gx, dg, db, gw, gb, None, None, None, None, None, None, None, None
+
+
 class BiasActFn(Function):
     """y = act(x + bias[c]) for LeakyReLU(0.2) / tanh / sigmoid -- model.py:404, 509, 408."""
 
@@ -560,6 +647,21 @@ def bn_act_conv(x, gamma, beta, running_mean, running_var, eps, momentum, act, w
     """conv(act(BN_train(x))) with nothing materialised in between -- see BNConvFn.  Returns (y, stats of y)."""
     return BNConvFn.apply(x, gamma, beta, w, bias, running_mean, running_var, eps, momentum, act, stride, transposed,
                           bias_grad, stats_in)
+
+
+def batch_norm_eval_act(x, gamma, beta, running_mean, running_var, eps=1e-5, act=ops.ACT_NONE):
+    """act(BN_eval(x)) on the running statistics, materialised -- see BNEvalActFn."""
+    y, bound = BNEvalActFn.apply(x, gamma, beta, running_mean, running_var, eps, act)
+    if bound is not None:
+        ops.set_amax(y, bound)
+    return y
+
+
+def bn_eval_act_conv(x, gamma, beta, running_mean, running_var, eps, act, w, bias, stride, transposed=False,
+                     bias_grad=BIAS_GRAD_COMPUTE, stats_in=None):
+    """conv(act(BN_eval(x))) with nothing materialised in between -- see BNEvalConvFn.  Returns (y, stats of y)."""
+    return BNEvalConvFn.apply(x, gamma, beta, w, bias, running_mean, running_var, eps, act, stride, transposed, bias_grad,
+                              stats_in)
 
 
 def bias_act(x, bias, kind):

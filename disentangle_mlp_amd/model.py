@@ -18,7 +18,12 @@ sigmoid epilogues are HIP; the Linear GEMMs go to hipBLASLt through
 ``torch.nn.functional.linear``.
 
 There is no CPU path: calling a module with CPU tensors raises.
+
+Eval mode (BatchNorm on its running statistics) is opt-in per network: `enable_eval` / `eval_mode`.  A network that
+was not opted in still refuses ``.eval()``, as it always has.
 """
+import contextlib
+
 import torch
 from torch import nn
 import torch.nn.functional as tF
@@ -40,19 +45,22 @@ def weights_init(m):
 # --------------------------------------------------------------------- layers
 class HipConv2d(nn.Conv2d):
     """5x5 / pad 2 / stride 1|2 convolution.  ``bn_shadowed``: the bias feeds a train-mode
-    BatchNorm, so its gradient is analytically zero and is returned as exact zeros."""
+    BatchNorm, so its gradient is analytically zero and is returned as exact zeros (`_bias_mode`: unless that
+    BatchNorm runs on its running statistics)."""
+    _next_bn = ()
 
     def __init__(self, cin, cout, stride, bn_shadowed=True):
         super().__init__(cin, cout, 5, stride=stride, padding=2)
         self.bn_shadowed = bn_shadowed
 
     def forward(self, x):
-        mode = F.BIAS_GRAD_ZERO if self.bn_shadowed else F.BIAS_GRAD_COMPUTE
+        mode = _bias_mode(self)
         return F.conv5x5(x.contiguous(), self.weight, self.bias, self.stride[0], mode)
 
 
 class HipConvTranspose2d(nn.ConvTranspose2d):
     """5x5 / pad 2 / stride 1|2 transposed convolution producing exactly stride*input."""
+    _next_bn = ()
 
     def __init__(self, cin, cout, stride, bn_shadowed=True):
         super().__init__(cin, cout, 5, stride=stride, padding=2)
@@ -65,29 +73,40 @@ class HipConvTranspose2d(nn.ConvTranspose2d):
             if want != (x.shape[2] * s, x.shape[3] * s):
                 raise ValueError(f"requested output size {want} is not stride*input "
                                  f"{(x.shape[2] * s, x.shape[3] * s)}")
-        mode = F.BIAS_GRAD_ZERO if self.bn_shadowed else F.BIAS_GRAD_COMPUTE
+        mode = _bias_mode(self)
         return F.conv_transpose5x5(x.contiguous(), self.weight, self.bias, s, mode)
 
 
 class _HipBatchNormMixin:
-    """Train-mode batch norm fused with the following activation.  The reference never
-    calls .eval() (SURVEY.md section 3.1 item 5), so only batch statistics exist here;
-    eval mode is rejected rather than silently approximated."""
+    """Batch norm fused with the following activation.  Training: batch statistics, the reference's only path (it never
+    calls .eval()).  Not training: the running statistics -- for a module that
+    `enable_eval` marked (``eval_enabled``, a plain attribute: no buffer, not in the state_dict); an unmarked module
+    rejects eval mode rather than silently approximating it.  Each BatchNorm decides by its own flags."""
     act = ops.ACT_NONE
+    eval_enabled = False
 
     def _init_pending(self):
         self._nbt_pending = 0
         self.register_state_dict_pre_hook(_flush_nbt)
 
     def _note_forward(self):
+        """True: this forward normalises with batch statistics (and is counted); False: with the running statistics
+        (nothing of the module moves)."""
         if not self.training:
-            raise RuntimeError("HipBatchNorm: eval-mode (running-statistics) normalisation is not part "
-                               "of the reference's path and is not implemented")
+            if not self.eval_enabled:
+                raise RuntimeError("HipBatchNorm: eval-mode (running-statistics) normalisation is not part of the "
+                                   "reference's path and is opt-in: call model.enable_eval(net) (or use "
+                                   "model.eval_mode(net)) before net.eval()")
+            return False
         self._nbt_pending += 1     # num_batches_tracked, materialised lazily (no launch per call)
+        return True
 
     def forward(self, x, stats=None):
         """``stats``: statistics slots left by the producing convolution (skips the statistics pass)."""
-        self._note_forward()
+        if not self._note_forward():
+            # materialised: the normalise pass emits the exact bound of its output, the slots are not needed
+            return F.batch_norm_eval_act(x.contiguous(), self.weight, self.bias, self.running_mean, self.running_var,
+                                         self.eps, self.act)
         return F.batch_norm_act(x.contiguous(), self.weight, self.bias, self.running_mean, self.running_var,
                                 self.eps, self.momentum, self.act, stats)
 
@@ -152,6 +171,7 @@ class HipLinear(nn.Linear):
     x_to_logvar.0, preprocess.0: model.py:461-462, 467-468, 491-492), so its gradient is analytically zero and is defined
     as exactly zero like the convolution biases' (SURVEY.md section 3.1 item 9).  Refuses CPU tensors like every other
     layer here."""
+    _next_bn = ()
 
     def __init__(self, fin, fout, bn_shadowed=False):
         super().__init__(fin, fout)
@@ -163,13 +183,76 @@ class HipLinear(nn.Linear):
         # big layers (and the shadowed ones) go through this package's Function: the batched weight gradient of
         # functional.deferred_wgrad(), no bias-gradient reduction where it is zero by construction
         if (self.weight.numel() >= F.DEFER_MIN_WEIGHTS or self.bn_shadowed) and x.dim() == 2:
-            return F.linear(x, self.weight, self.bias, F.BIAS_GRAD_ZERO if self.bn_shadowed else F.BIAS_GRAD_COMPUTE)
+            return F.linear(x, self.weight, self.bias, _bias_mode(self))
         return tF.linear(x, self.weight, self.bias)
+
+
+def _link_bn(layer, bn):
+    """Tell a ``bn_shadowed`` layer which BatchNorm its output feeds.  A tuple, not the module: nothing is registered
+    (no child module, no state_dict key), and a deep copy of the network links the copies."""
+    layer._next_bn = (bn,)
+
+
+def _link_chain(mods):
+    """`_link_bn` for every convolution / Linear layer of ``mods`` that is directly followed by a HipBatchNorm."""
+    for a, b in zip(mods[:-1], mods[1:]):
+        if isinstance(a, (HipConv2d, HipConvTranspose2d, HipLinear)) and isinstance(b, _HipBatchNormMixin):
+            _link_bn(a, b)
+
+
+def _bias_mode(layer, bn=None):
+    """How a layer's bias gradient is produced.  A train-mode BatchNorm behind a ``bn_shadowed`` layer cancels the bias:
+    BIAS_GRAD_ZERO.  Running statistics cancel nothing: whenever the BatchNorm that follows (``bn``, or the one the
+    layer was linked to) is not training, the gradient is computed."""
+    if bn is None and layer._next_bn:
+        bn = layer._next_bn[0]
+    frozen = bn is not None and not bn.training
+    return F.BIAS_GRAD_ZERO if (layer.bn_shadowed and not frozen) else F.BIAS_GRAD_COMPUTE
+
+
+def enable_eval(*nets):
+    """Opt the networks in to eval mode: every HipBatchNorm1d / 2d of ``nets`` normalises with its running statistics
+    whenever it is not training (``net.eval()``).  Returns the networks (the network, for one)."""
+    for net in nets:
+        for m in net.modules():
+            if isinstance(m, _HipBatchNormMixin):
+                m.eval_enabled = True
+    return nets[0] if len(nets) == 1 else nets
+
+
+def disable_eval(*nets):
+    """Undo `enable_eval`: the networks refuse ``.eval()`` again."""
+    for net in nets:
+        for m in net.modules():
+            if isinstance(m, _HipBatchNormMixin):
+                m.__dict__.pop("eval_enabled", None)
+    return nets[0] if len(nets) == 1 else nets
+
+
+@contextlib.contextmanager
+def eval_mode(*nets):
+    """``with eval_mode(netEG): x = netEG.decode(z)``: `enable_eval` + ``.eval()``; on exit (also after an exception)
+    every module has the ``training`` flag and every BatchNorm the mark it had before."""
+    before = [(m, m.training, m.__dict__.get("eval_enabled")) for net in nets for m in net.modules()]
+    try:
+        enable_eval(*nets)
+        for net in nets:
+            net.eval()
+        yield nets[0] if len(nets) == 1 else nets
+    finally:
+        for m, training, mark in before:
+            m.training = training
+            if isinstance(m, _HipBatchNormMixin):
+                if mark is None:
+                    m.__dict__.pop("eval_enabled", None)
+                else:
+                    m.eval_enabled = mark
 
 
 def shadowed_bias_params(net):
     """The convolution biases whose gradient is defined as exactly zero (they feed a train-mode BatchNorm: HipConv2d /
-    HipConvTranspose2d with ``bn_shadowed``): their backward returns no gradient at all, see functional.BIAS_GRAD_ZERO."""
+    HipConvTranspose2d with ``bn_shadowed``): their backward returns no gradient at all, see functional.BIAS_GRAD_ZERO.
+    (What the always-training trainers ask; a layer whose BatchNorm is in eval computes its bias gradient: `_bias_mode`.)"""
     return [m.bias for m in net.modules()
             if isinstance(m, (HipConv2d, HipConvTranspose2d, HipLinear)) and m.bn_shadowed and m.bias is not None]
 
@@ -210,15 +293,19 @@ def run_conv_bn_chain(mods, x):
             t = pending(t, stats=stats)
             pending, stats = None, None
         return t
-    for m in mods:
+    for i, m in enumerate(mods):
         if isinstance(m, (HipConv2d, HipConvTranspose2d)):
             tr = isinstance(m, HipConvTranspose2d)
-            mode = F.BIAS_GRAD_ZERO if m.bn_shadowed else F.BIAS_GRAD_COMPUTE
+            nxt = mods[i + 1] if i + 1 < len(mods) else None          # the chain knows its next module
+            mode = _bias_mode(m, nxt if isinstance(nxt, _HipBatchNormMixin) else None)
             if pending is not None:
                 bn = pending
-                bn._note_forward()
-                x, stats = F.bn_act_conv(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum,
-                                         bn.act, m.weight, m.bias, m.stride[0], tr, mode, stats)
+                if bn._note_forward():
+                    x, stats = F.bn_act_conv(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum,
+                                             bn.act, m.weight, m.bias, m.stride[0], tr, mode, stats)
+                else:      # running statistics; the producer's slots still give the bound without a pass over x
+                    x, stats = F.bn_eval_act_conv(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.act,
+                                                  m.weight, m.bias, m.stride[0], tr, mode, stats)
                 pending = None
             else:
                 x, stats = F.conv_with_stats(x.contiguous(), m.weight, m.bias, m.stride[0], tr, mode)
@@ -236,6 +323,10 @@ def run_conv_bn_chain(mods, x):
 class FusedChain(nn.Sequential):
     """nn.Sequential with the reference's indices (``features.0`` ... ``features.8``, ``convs.0`` ...), run fused.
     (The class name must contain neither "Conv" nor "BatchNorm": weights_init matches class names, model.py:8-14.)"""
+
+    def __init__(self, *args):
+        super().__init__(*args)
+        _link_chain(list(self))
 
     def forward(self, x):
         mods = list(self)
@@ -262,8 +353,10 @@ def _latent_hw(opt):
 
 
 def _enc_head(width, n_hidden, spatial=(8, 8)):
-    return nn.Sequential(HipLinear(width * 4 * spatial[0] * spatial[1], 2048, bn_shadowed=True), HipBatchNorm1d(2048, ops.ACT_RELU),
+    head = nn.Sequential(HipLinear(width * 4 * spatial[0] * spatial[1], 2048, bn_shadowed=True), HipBatchNorm1d(2048, ops.ACT_RELU),
                          FusedIntoBN("ReLU"), HipLinear(2048, n_hidden))
+    _link_chain(list(head))
+    return head
 
 
 def _bn_relu(c):
@@ -283,6 +376,9 @@ class _DecoderMixin:
         self.act3 = _bn_relu(32)
         self.deconv4 = HipConvTranspose2d(32, 3, 1, bn_shadowed=False)
         self.activation = HipTanh()
+        _link_chain(list(self.preprocess))
+        for conv, bn in ((self.deconv1, self.act1), (self.deconv2, self.act2), (self.deconv3, self.act3)):
+            _link_bn(conv, bn[0])
 
     def _decode(self, code, n_z):
         bs = code.size(0)

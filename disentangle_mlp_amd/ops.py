@@ -915,6 +915,63 @@ def bn_act_bwd(gy, x, gamma, beta, mean, invstd, act, need_param_grads=True, acc
     return gx, dgamma, dbeta
 
 
+# ---------------------------------------------------- BatchNorm on running statistics (eval mode)
+def bn_eval_coeffs(gamma, beta, running_mean, running_var, eps, act, stats=None, count=None, want_bound=False):
+    """Coefficients of an eval-mode BatchNorm: (scale, shift, invstd) with scale = gamma / sqrt(running_var + eps),
+    shift = beta - running_mean * scale; the running buffers are only read.  ``want_bound``: a 4th result, an upper bound
+    of max |act(x * scale + shift)| for the x whose statistics slots ``stats`` (with ``count`` values per channel) the
+    producing convolution left -- from the sums alone, no pass over x; None in other arithmetics and without slots
+    (`amax_of` then measures the tensor through the affine)."""
+    lib = _lib.load()
+    _req(gamma, "gamma"), _req(beta, "beta"), _req(running_mean, "running_mean"), _req(running_var, "running_var")
+    C = gamma.numel()
+    if beta.numel() != C or running_mean.numel() != C or running_var.numel() != C:
+        raise RuntimeError("bn_eval_coeffs: one gamma, beta, running mean and running variance per channel")
+    have = stats is not None and stats.numel() > 0
+    nslots = 0
+    if have:
+        _req(stats, "stats")
+        if count is None or count <= 0 or stats.numel() % (2 * C):
+            raise RuntimeError("bn_eval_coeffs: stats holds [nslots][C][2] floats and comes with the count per channel")
+        nslots = stats.numel() // (2 * C)
+    out = torch.empty((3, C), dtype=torch.float32, device=gamma.device)
+    scale, shift, invstd = out[0], out[1], out[2]
+    bound = new_amax_slot(gamma.device) if (want_bound and have and _f16()) else None
+    check(lib.vg_bn_eval_coeffs(gamma.data_ptr(), beta.data_ptr(), running_mean.data_ptr(), running_var.data_ptr(),
+                                scale.data_ptr(), shift.data_ptr(), invstd.data_ptr(), C, eps, int(act),
+                                stats.data_ptr() if bound is not None else 0, nslots if bound is not None else 0,
+                                float(count) if bound is not None else 0.0, _ptr(bound), _stream()), "vg_bn_eval_coeffs")
+    return (scale, shift, invstd, bound) if want_bound else (scale, shift, invstd)
+
+
+def bn_eval_act_bwd(gy, x, scale, shift, mean, invstd, act, need_param_grads=True, accumulate_into=None):
+    """Backward of y = act(x * scale[c] + shift[c]) with frozen coefficients (``mean``: the running mean they were made
+    of): (gx, dgamma, dbeta).  ``need_param_grads`` / ``accumulate_into``: as `bn_act_bwd`."""
+    lib = _lib.load()
+    _req(gy, "gy"), _req(x, "x"), _req(scale, "scale"), _req(shift, "shift"), _req(mean, "mean"), _req(invstd, "invstd")
+    if gy.shape != x.shape:
+        raise RuntimeError(f"bn_eval_act_bwd: gy {tuple(gy.shape)} does not match x {tuple(x.shape)}")
+    B, C = x.shape[0], x.shape[1]
+    if any(t.numel() != C for t in (scale, shift, mean, invstd)):
+        raise RuntimeError("bn_eval_act_bwd: one coefficient per channel")
+    HW = x.numel() // (B * C)
+    gx = torch.empty_like(x)
+    if accumulate_into is not None:
+        dgamma, dbeta = accumulate_into
+    else:
+        dgamma = torch.empty(C, dtype=torch.float32, device=x.device) if need_param_grads else None
+        dbeta = torch.empty(C, dtype=torch.float32, device=x.device) if need_param_grads else None
+    ws = workspace(lib.vg_bn_workspace_bytes(C), x.device)
+    slot = new_amax_slot(x.device) if (_f16() and HW > 1) else None   # max |gx| on the way out (as bn_act_bwd)
+    check(lib.vg_bn_eval_act_bwd(gy.data_ptr(), x.data_ptr(), scale.data_ptr(), shift.data_ptr(), mean.data_ptr(),
+                                 invstd.data_ptr(), gx.data_ptr(), _ptr(dgamma), _ptr(dbeta), B, C, HW, int(act),
+                                 1 if accumulate_into is not None else 0, _ptr(slot), ws.data_ptr(), ws.numel(), _stream()),
+          "vg_bn_eval_act_bwd")
+    if slot is not None:
+        set_amax(gx, slot)
+    return gx, dgamma, dbeta
+
+
 # ----------------------------------------------------------------- elementwise
 def bias_act_fwd(x, bias, kind):
     lib = _lib.load()

@@ -35,6 +35,7 @@ import torch.distributed as dist
 from torch import optim
 
 from . import functional as F
+from . import model as _model
 from . import ops
 from .optim import HipAdam, NONFINITE_GRAD, NONFINITE_PARAM, isfinite_bits
 from .model import VAE, Discriminator_celeba, Generator_celeba, weights_init, shadowed_bias_params
@@ -871,13 +872,15 @@ class BetaVAEGANTrainer(_GraphedSteps):
     def evaluate(self, load_paths, test_loader=None, start_epoch=0, calc_fid=False, n_samples=1000, fid_path_samples=None,
                  fid_path_pretrained=None, get_fid=None, test_recons=False, test_results_path_recons=None,
                  test_results_path_originals="", test_samples=False, test_results_path_samples=None,
-                 fid_on_device=False, fid_inception="", fid_feature_extractor=None):
+                 fid_on_device=False, fid_inception="", fid_feature_extractor=None, eval_mode=False):
         """The evaluation half (new_betavaegan.py:248-267): for every checkpoint of ``load_paths`` -- load it, renumber
         its epoch the way the reference does so that files of several checkpoints do not overwrite each other (:252-254),
         then FID samples + score (:256-259), one grid of test reconstructions with ``nrow=1`` (+ the originals, :260-263)
         and five samples named after ``start_epoch`` (:264-267: the reference passes ``start_epoch`` there, so several
-        checkpoints write the same file; kept).  Train-mode BatchNorm throughout: the reference never calls ``.eval()``
-        (SURVEY.md section 3.1 item 5).  Returns one dict per checkpoint.  ``fid_on_device`` / ``fid_inception`` /
+        checkpoints write the same file; kept).  Train-mode BatchNorm throughout by default: the reference never calls
+        ``.eval()``; ``eval_mode=True`` decodes and reconstructs inside
+        ``model.eval_mode(self.netEG)`` instead (running statistics; the network is back in training mode afterwards).
+        Returns one dict per checkpoint.  ``fid_on_device`` / ``fid_inception`` /
         ``fid_feature_extractor``: as in `fit` -- the FID straight from the decoder, no sample files."""
         from . import image_io
         out, tmp_epoch = [], 0
@@ -887,7 +890,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
             epoch = epoch if epoch != tmp_epoch and tmp_epoch < epoch else tmp_epoch + 1
             tmp_epoch = epoch
             res = {"path": m, "epoch": epoch, "FID": "N/A"}
-            with torch.no_grad():
+            with torch.no_grad(), _model.eval_mode(*((self.netEG,) if eval_mode else ())):
                 if calc_fid and fid_on_device:
                     from .fid import get_fid_of_generator
                     res["FID"] = get_fid_of_generator(self.netEG.decode, n_samples, self.opt.n_hidden, fid_path_pretrained,

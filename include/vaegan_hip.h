@@ -45,8 +45,9 @@ extern "C" {
  * whose version is not the header's (the .so files are build products that travel with the working tree: a stale one
  * still exports every old symbol).  3: round 3.  4: round 4 (fp16 planes: VG_PLANES_F16, the *_amax arguments).
  * 6: vg_conv_general_* (the general forward convolution).  7: vg_adam_step_checked / vg_adam_step_dev_checked.
- * Entry points that are only ADDED (the four of csrc/fid_front.hip) change nothing an existing caller sees and keep the
- * version: a binding that needs them and finds a library without them fails at the symbol lookup, as loudly. */
+ * Entry points that are only ADDED (the four of csrc/fid_front.hip; vg_bn_eval_coeffs, vg_bn_eval_act_bwd) change
+ * nothing an existing caller sees and keep the version: a binding that needs them and finds a library without them
+ * fails at the symbol lookup, as loudly. */
 #define VG_ABI_VERSION 7
 int vg_version(void);
 
@@ -349,6 +350,35 @@ int vg_bn_stats(const float* x, const float* gamma, const float* beta, float* ru
                 float eps, float momentum, float* act_amax, void* workspace, size_t workspace_bytes, void* stream);
 int vg_affine_act(const float* x, const float* scale, const float* shift, float* y, int B, int C, int HW, int act,
                   float* y_amax, void* stream);
+
+/* ---- BatchNorm on running statistics (eval mode) -----------------------------
+ * nn.BatchNorm2d / 1d after .eval(): F.batch_norm(training=False) of the modules at model.py:451-458, 462, 468, 492,
+ * 496-505, 390-400 -- the reference's modules accept .eval() on the checkpoints exchanged with it; opt-in here
+ * (model.enable_eval).  y = act(x * scale[c] + shift[c]) with FROZEN coefficients, applied by vg_affine_act or by the
+ * consuming convolution on load (vg_conv_fusion.in_scale / in_shift), exactly as in train mode.
+ * vg_bn_eval_coeffs (one launch): scale = gamma / sqrt(running_var + eps), shift = beta - running_mean * scale, and
+ * invstd = 1 / sqrt(running_var + eps) for the backward.  The running buffers are inputs only; nothing else is written.
+ * `act`: the activation the consumer applies (validated; ReLU / LeakyReLU only shrink the bound).
+ * stats / nslots / count (optional: NULL / 0 / 0): the statistics slots the producing convolution left of x
+ * ([nslots][C][2]: vg_conv_fusion.stats; count = B * H * W) -- with them AND act_amax (DEVICE, zeroed by the caller) an
+ * upper bound of max |act(x * scale + shift)| is added to act_amax[0] (atomic maximum), from the sums alone, no pass over
+ * x: |x - m| <= sigma sqrt(count - 1) for the batch's exact mean and sigma, sigma bounded from the computed variance plus
+ * the sums' rounding error as for vg_bn_finalize_stats, hence |scale x + shift| <= |scale| sigma sqrt(count - 1) +
+ * |scale m + shift|.  Never below the data, also for a constant channel or a variance lost to cancellation.  Without
+ * slots: coefficients only (vg_absmax_affine gives the exact bound).
+ * vg_bn_eval_act_bwd: one pass over gy and the saved raw x.  gx = gy act'(scale x + shift) scale;
+ * dbeta[c] = sum gy act', dgamma[c] = sum gy act' (x - mean[c]) invstd[c] (mean: the running mean the forward used).
+ * dgamma / dbeta may be NULL; accumulate_param_grads, gx_amax, HW == 1, the fixed summation order and the 16-byte
+ * accesses (HW % 4 == 0 and 16-byte aligned gy, x, gx only) as vg_bn_act_bwd.  A NaN gradient stays a NaN; a NaN
+ * pre-activation under ReLU / LeakyReLU gives a NaN gradient.  B = 1 is an ordinary input.
+ * workspace >= vg_bn_workspace_bytes(C) (needed only for parameter gradients of channels cut into several slices). */
+int vg_bn_eval_coeffs(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                      float* scale, float* shift, float* invstd, int C, float eps, int act,
+                      const float* stats, int nslots, double count, float* act_amax, void* stream);
+int vg_bn_eval_act_bwd(const float* gy, const float* x, const float* scale, const float* shift,
+                       const float* mean, const float* invstd, float* gx, float* dgamma, float* dbeta,
+                       int B, int C, int HW, int act, int accumulate_param_grads, float* gx_amax,
+                       void* workspace, size_t workspace_bytes, void* stream);
 
 
 /* ---- elementwise activations ------------------------------------------------

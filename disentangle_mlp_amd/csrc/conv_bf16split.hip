@@ -26,7 +26,17 @@
 //     [parity class][chunk][tap][plane][k-block][cout] x 8 bf16, so a lane's A operand is one 16-byte
 //     global load (32 consecutive cout = 512 contiguous bytes), prefetched one tap ahead.
 //   * The stride-2 transposed convolution runs as its 4 output-parity classes (3x3, 3x2, 2x3, 2x2
-//     taps), exactly as in conv_igemm.hip.
+//     taps), exactly as in conv_igemm.hip: one workgroup per (pixel tile, class).
+//   * Quad form (conv5x5_bf16split_quad_kernel; <= 32 output channels, 2 planes, grids of >= 256 workgroups): one
+//     workgroup per 8 x 32 input tile computes all four classes.  The four per-class workgroups of a tile stage the
+//     same patch; here it is loaded, scaled, split and written to LDS once, the 25 taps of a chunk run between one
+//     pair of barriers on four accumulator sets (128 registers; 234 VGPRs in all, no scratch), a pixel fragment read
+//     from LDS serves every class with a tap at that patch offset (9 reads per chunk, not 25), and a lane stores the
+//     2 x 2 output block of its pixel as two 8-byte pairs: 32 lanes write 256 contiguous bytes where a class wrote
+//     every other dword.  Every output element sums in the order of the per-class kernel (chunks, tap rows, tap
+//     columns, plane products): the results are bit-identical.  113 -> 85 us per launch at B = 128, 128 -> 32
+//     channels, 32 x 32 -> 64 x 64; WRITE_SIZE 129.5 -> 65.5 MB for the 65.5 MB (2^26 B) output
+//     (profiles/r08_convT_quad.json).
 #include "common.hpp"
 #include "vaegan_hip.h"
 
@@ -91,7 +101,35 @@ __host__ __device__ constexpr int x_taps_before(int S, int R, int SS) {
   return n;
 }
 
-template <class C, int R, int SS>
+// Quad form of the stride-2 transposed convolution: one workgroup runs the 25 taps of a chunk for all four parity
+// classes.  Step i is tap (a, b) of class cls = 2 R + SS; the steps walk the 3 x 3 patch offsets (2 - a, 2 - b) row by
+// row, and at each offset the classes that have a tap there (a < 3 - R, b < 3 - SS) in class order: 4 + 4 + 2, twice,
+// then 2 + 2 + 1.  A class meets its own taps rows first, then columns -- the order of the per-class kernel.
+struct XQStep { int a, b, cls; };
+constexpr XQStep x_quad_step(int i) {
+  int n = 0;
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b)
+      for (int cls = 0; cls < 4; ++cls)
+        if (a < 3 - cls / 2 && b < 3 - cls % 2) {
+          if (n == i) return {a, b, cls};
+          ++n;
+        }
+  return {0, 0, 0};     // i = 25: the next chunk's first step
+}
+static_assert(x_quad_step(24).a == 2 && x_quad_step(24).b == 2 && x_quad_step(24).cls == 0 && x_quad_step(9).cls == 2 && x_quad_step(17).cls == 3, "25 steps");
+
+template <int I> struct XIdx { static constexpr int value = I; };
+template <int I, int N, class F>
+__device__ __forceinline__ void x_static_for(F&& f) {      // f(XIdx<I>) ... f(XIdx<N - 1>): the index is a constant in f
+  if constexpr (I < N) {
+    f(XIdx<I>{});
+    x_static_for<I + 1, N>(f);
+  }
+}
+
+// QUAD (with R = SS = 0): all four classes of the tile, see x_quad_step
+template <class C, int R, int SS, bool QUAD = false>
 __device__ __forceinline__ void bf16split_body(const XArgs& A, f32x4* lds, int bid, int split) {
   constexpr int MODE = C::MODE, S = C::S, NB = C::NB, TH = C::TH, TW = C::TW, PH = C::PH, PW = C::PW;
   constexpr int ROWU = C::ROWU, IMGU = C::IMGU, NQ = C::NQ, FC = C::FC, FP = C::FP, NP = C::NP;
@@ -101,6 +139,8 @@ __device__ __forceinline__ void bf16split_body(const XArgs& A, f32x4* lds, int b
   constexpr int NTW = (MODE == X_FWD) ? 5 : (5 - SS + S - 1) / S;
   constexpr int NTAP = NTH * NTW;
   constexpr int PSTEP = (MODE == X_FWD) ? S : 1;                   // patch rows / columns per tile pixel
+  constexpr int NACC = QUAD ? 4 : FC;                              // accumulator sets: one per class / per cout fragment
+  static_assert(!QUAD || (MODE == X_TR && S == 2 && C::WC == 1 && FC == 1 && NP == 2 && R == 0 && SS == 0), "quad form");
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int kb = lane >> 5, l32 = lane & 31;
@@ -195,9 +235,9 @@ __device__ __forceinline__ void bf16split_body(const XArgs& A, f32x4* lds, int b
   for (int g = 0; g < FC; ++g)
     wa[g] = A.w + (size_t)x_taps_before(S, R, SS) * nchunks * wstep + (size_t)kb * CoutP + n0 + (wc * FC + g) * 32 + l32;
 
-  f32x16 acc[FC][FP];
+  f32x16 acc[NACC][FP];
 #pragma unroll
-  for (int g = 0; g < FC; ++g)
+  for (int g = 0; g < NACC; ++g)
 #pragma unroll
     for (int f = 0; f < FP; ++f)
 #pragma unroll
@@ -216,60 +256,98 @@ __device__ __forceinline__ void bf16split_body(const XArgs& A, f32x4* lds, int b
   for (int ch = c_begin; ch < c_end; ++ch) {
     const bool more = (ch + 1) < c_end;
     if (more) load_chunk((ch + 1) * 16);
-    // one filter row (NTW taps) per trip of a rolled loop: keeps the filter prefetch one tap deep
-    // (fully unrolled, hipcc hoists every tap's loads and spills).  When NTW is odd the prefetched
-    // step is moved back into buffer 0 at the end of the row, so `cur` stays compile-time.
-#pragma unroll 1
-    for (int ta = 0; ta < NTH; ++ta) {
-      const bf16x8* wrow[FC];
-#pragma unroll
-      for (int g = 0; g < FC; ++g) wrow[g] = wa[g] + ((size_t)ch * NTAP + ta * NTW) * wstep;
-      const int rowoff = (MODE == X_FWD) ? ta * ROWU : (NTMAX - 1 - ta) * ROWU;
-      // Pinned software pipeline (hipcc otherwise sinks the prefetch loads next to their first use, one
-      // vmcnt wait per MFMA pair): at the top of a tap issue the NEXT tap's filter fragments (global) and
-      // pixel fragments (LDS, within the row), then run this tap's MFMAs on registers loaded a tap ago.
-      constexpr bool BPF = (NP == 2);      // pixel fragments one tap ahead too (3 planes: no registers left for it)
-      constexpr bool PIN = (NP == 2) || C::WC == 4;   // 3 planes, 2 x 2 fragments: pinning makes the allocator spill
-      bf16x8 bv[BPF ? 2 : 1][FP][NP];
-      auto read_b = [&](int buf, int t) {
-        const int imm = (MODE == X_TR) ? (NTMAX - 1 - t) : t;
+    if constexpr (QUAD) {
+      // The 25 steps unrolled, pinned like the per-class pipeline below: a step issues the next step's filter fragments
+      // (the step after the last one is the next chunk's first; after the last chunk it reads class 1's first step,
+      // unused), the first step at a patch offset also the next offset's pixel fragments, which every class with a tap
+      // there shares: 9 fragment reads per chunk where the four per-class workgroups made 25.
+      bf16x8 bv[2][FP][NP];
+      auto read_b = [&](int buf, int o) {
+        const int off = (NTMAX - 1 - o / 3) * ROWU + (NTMAX - 1 - o % 3);
 #pragma unroll
         for (int f = 0; f < FP; ++f)
 #pragma unroll
-          for (int p = 0; p < NP; ++p) bv[buf][f][p] = __builtin_bit_cast(bf16x8, lds[base_b[f] + rowoff + imm + p * 2 * IMGU]);
+          for (int p = 0; p < NP; ++p) bv[buf][f][p] = __builtin_bit_cast(bf16x8, lds[base_b[f] + off + p * 2 * IMGU]);
       };
-      if (BPF) read_b(0, 0);
+      read_b(0, 0);
+      x_static_for<0, 25>([&](auto idx) {
+        constexpr int i = decltype(idx)::value;
+        constexpr XQStep s = x_quad_step(i), n = x_quad_step(i + 1), before = x_quad_step(i > 0 ? i - 1 : 0);
+        constexpr int cur = i & 1, nxt = cur ^ 1, o = s.a * 3 + s.b;
+        constexpr bool first = i == 0 || before.a != s.a || before.b != s.b;
+        constexpr int nntw = 3 - n.cls % 2, nntap = (3 - n.cls / 2) * nntw;
+        const size_t nstep = (size_t)x_taps_before(S, n.cls / 2, n.cls % 2) * nchunks + (size_t)(ch + (i == 24 ? 1 : 0)) * nntap +
+                             n.a * nntw + n.b;
 #pragma unroll
-      for (int tb = 0; tb < NTW; ++tb) {
-        const int cur = tb & 1, nxt = cur ^ 1;
-        // next tap's filter fragments (the pack has one spare step after the last one)
-#pragma unroll
-        for (int g = 0; g < FC; ++g)
-#pragma unroll
-          for (int p = 0; p < NP; ++p) av[nxt][g][p] = wrow[g][(size_t)(tb + 1) * wstep + (size_t)p * 2 * CoutP];
-        if (BPF) {
-          if (tb + 1 < NTW) read_b(nxt, tb + 1);
-        } else {
-          read_b(0, tb);
-        }
-        if (PIN) __builtin_amdgcn_sched_barrier(0);
-        // products with plane index sum <= NP - 1, smallest terms first; product-major so that independent
-        // accumulators sit between dependent MFMAs
+        for (int p = 0; p < NP; ++p) av[nxt][0][p] = wa[0][nstep * wstep + (size_t)p * 2 * CoutP];
+        if constexpr (first && o + 1 < 9) read_b((o + 1) & 1, o + 1);
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int sum = NP - 1; sum >= 0; --sum)
 #pragma unroll
           for (int pa = sum; pa >= 0; --pa)
 #pragma unroll
-            for (int g = 0; g < FC; ++g)
+            for (int f = 0; f < FP; ++f) acc[s.cls][f] = mfma_split16<F16>(av[cur][0][pa], bv[o & 1][f][sum - pa], acc[s.cls][f]);
+        __builtin_amdgcn_sched_barrier(0);
+      });
 #pragma unroll
-              for (int f = 0; f < FP; ++f) acc[g][f] = mfma_split16<F16>(av[cur][g][pa], bv[BPF ? cur : 0][f][sum - pa], acc[g][f]);
-        if (PIN) __builtin_amdgcn_sched_barrier(0);
-      }
-      if (NTW & 1) {
+      for (int p = 0; p < NP; ++p) av[0][0][p] = av[1][0][p];      // 25 steps: the prefetched one is back in buffer 0
+    } else {
+      // one filter row (NTW taps) per trip of a rolled loop: keeps the filter prefetch one tap deep
+      // (fully unrolled, hipcc hoists every tap's loads and spills).  When NTW is odd the prefetched
+      // step is moved back into buffer 0 at the end of the row, so `cur` stays compile-time.
+#pragma unroll 1
+      for (int ta = 0; ta < NTH; ++ta) {
+        const bf16x8* wrow[FC];
 #pragma unroll
-        for (int g = 0; g < FC; ++g)
+        for (int g = 0; g < FC; ++g) wrow[g] = wa[g] + ((size_t)ch * NTAP + ta * NTW) * wstep;
+        const int rowoff = (MODE == X_FWD) ? ta * ROWU : (NTMAX - 1 - ta) * ROWU;
+        // Pinned software pipeline (hipcc otherwise sinks the prefetch loads next to their first use, one
+        // vmcnt wait per MFMA pair): at the top of a tap issue the NEXT tap's filter fragments (global) and
+        // pixel fragments (LDS, within the row), then run this tap's MFMAs on registers loaded a tap ago.
+        constexpr bool BPF = (NP == 2);      // pixel fragments one tap ahead too (3 planes: no registers left for it)
+        constexpr bool PIN = (NP == 2) || C::WC == 4;   // 3 planes, 2 x 2 fragments: pinning makes the allocator spill
+        bf16x8 bv[BPF ? 2 : 1][FP][NP];
+        auto read_b = [&](int buf, int t) {
+          const int imm = (MODE == X_TR) ? (NTMAX - 1 - t) : t;
 #pragma unroll
-          for (int p = 0; p < NP; ++p) av[0][g][p] = av[1][g][p];
+          for (int f = 0; f < FP; ++f)
+#pragma unroll
+            for (int p = 0; p < NP; ++p) bv[buf][f][p] = __builtin_bit_cast(bf16x8, lds[base_b[f] + rowoff + imm + p * 2 * IMGU]);
+        };
+        if (BPF) read_b(0, 0);
+#pragma unroll
+        for (int tb = 0; tb < NTW; ++tb) {
+          const int cur = tb & 1, nxt = cur ^ 1;
+          // next tap's filter fragments (the pack has one spare step after the last one)
+#pragma unroll
+          for (int g = 0; g < FC; ++g)
+#pragma unroll
+            for (int p = 0; p < NP; ++p) av[nxt][g][p] = wrow[g][(size_t)(tb + 1) * wstep + (size_t)p * 2 * CoutP];
+          if (BPF) {
+            if (tb + 1 < NTW) read_b(nxt, tb + 1);
+          } else {
+            read_b(0, tb);
+          }
+          if (PIN) __builtin_amdgcn_sched_barrier(0);
+          // products with plane index sum <= NP - 1, smallest terms first; product-major so that independent
+          // accumulators sit between dependent MFMAs
+#pragma unroll
+          for (int sum = NP - 1; sum >= 0; --sum)
+#pragma unroll
+            for (int pa = sum; pa >= 0; --pa)
+#pragma unroll
+              for (int g = 0; g < FC; ++g)
+#pragma unroll
+                for (int f = 0; f < FP; ++f) acc[g][f] = mfma_split16<F16>(av[cur][g][pa], bv[BPF ? cur : 0][f][sum - pa], acc[g][f]);
+          if (PIN) __builtin_amdgcn_sched_barrier(0);
+        }
+        if (NTW & 1) {
+#pragma unroll
+          for (int g = 0; g < FC; ++g)
+#pragma unroll
+            for (int p = 0; p < NP; ++p) av[0][g][p] = av[1][g][p];
+        }
       }
     }
     __syncthreads();
@@ -282,7 +360,7 @@ __device__ __forceinline__ void bf16split_body(const XArgs& A, f32x4* lds, int b
   if constexpr (F16) {   // undo the two operands' power-of-two scales (two exact multiplications)
     const float w_unscale = *A.w_unscale;
 #pragma unroll
-    for (int g = 0; g < FC; ++g)
+    for (int g = 0; g < NACC; ++g)
 #pragma unroll
       for (int f = 0; f < FP; ++f)
 #pragma unroll
@@ -290,6 +368,42 @@ __device__ __forceinline__ void bf16split_body(const XArgs& A, f32x4* lds, int b
   }
   // ---- epilogue: + bias, NCHW store (as conv_igemm.hip)
   const int YH = A.YH, YW = A.YW;
+  if constexpr (QUAD) {
+    // A lane holds the 2 x 2 output block of its pixel for 16 channels: the two columns of a row go out as one 8-byte
+    // store (32 lanes = 256 contiguous bytes per row and channel) where the row has both and the address allows it.
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    const bool pair8 = ((uintptr_t)A.y & 7) == 0 && (YW & 1) == 0;
+    float bq[16];
+#pragma unroll
+    for (int r16 = 0; r16 < 16; ++r16) bq[r16] = A.bias ? A.bias[min(n0 + acc_row(r16, lane), Cout - 1)] : 0.f;
+#pragma unroll
+    for (int f = 0; f < FP; ++f) {
+      const int m = (wp * FP + f) * 32 + l32;
+      const int nb = m / (TH * TW), r = m % (TH * TW);
+      const int th = th0 + r / TW, tw = tw0 + r % TW, b = b0 + nb, ow = S * tw;
+#pragma unroll
+      for (int rr = 0; rr < 2; ++rr) {
+        const int oh = S * th + rr;
+        const bool pok = b < A.B && oh < YH;
+        float* yb = A.y + ((size_t)b * Cout * YH + oh) * YW + ow;
+#pragma unroll
+        for (int r16 = 0; r16 < 16; ++r16) {
+          const int co = n0 + acc_row(r16, lane);
+          const float v0 = acc[2 * rr][f][r16] + bq[r16], v1 = acc[2 * rr + 1][f][r16] + bq[r16];
+          float* yp = yb + (size_t)co * YH * YW;
+          if (pok && co < Cout) {
+            if (pair8 && ow + 1 < YW) {
+              *(f32x2*)yp = f32x2{v0, v1};
+            } else {
+              if (ow < YW) yp[0] = v0;
+              if (ow + 1 < YW) yp[1] = v1;
+            }
+          }
+        }
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int f = 0; f < FP; ++f) {
     const int m = (wp * FP + f) * 32 + l32;
@@ -335,13 +449,19 @@ __global__ __launch_bounds__(XNT, 2) void conv5x5_bf16split_kernel(XArgs A) {
   }
 }
 
+template <class C>
+__global__ __launch_bounds__(XNT, 2) void conv5x5_bf16split_quad_kernel(XArgs A) {
+  __shared__ f32x4 lds[2 * C::NP * C::IMGU];     // the per-class kernel's patch, staged once for the four classes
+  bf16split_body<C, 0, 0, true>(A, lds, blockIdx.x, 0);
+}
+
 struct XSplit {
   int k;          // 1: no split
   float* slabs;   // k partial outputs
   const float* in_amax;   // fp16 planes only
 };
 
-template <class C>
+template <class C, bool QUAD = false>
 int launch_x(const float* x, const bf16x8* w, const float* bias, float* y, int B, int Cin, int XH, int XW, int Cout,
              XSplit xs, hipStream_t st) {
   XArgs A;
@@ -360,7 +480,7 @@ int launch_x(const float* x, const bf16x8* w, const float* bias, float* y, int B
   A.ntiles_n = cdiv(Cout, C::TN);
   const long per_cls = (long)A.ntiles_n * A.tiles_hw * cdiv(B, C::NB);
   const int ksplit = (C::MODE == X_FWD) ? xs.k : 1;
-  const long grid = per_cls * C::NCLS * ksplit;
+  const long grid = per_cls * (QUAD ? 1 : C::NCLS) * ksplit;
   if (grid <= 0 || grid > 0x7fffffffL) return VG_ERR_BAD_ARG;
   A.blocks_per_cls = (int)per_cls;
   A.ksplit = ksplit;
@@ -369,7 +489,10 @@ int launch_x(const float* x, const bf16x8* w, const float* bias, float* y, int B
   if (ksplit > 1) A.y = xs.slabs;
   A.in_amax = xs.in_amax;
   A.w_unscale = (const float*)(w + vg_pack_trailer_units(Cin / 16 * 25, C::NP, A.CoutP));      // the pack's trailer
-  hipLaunchKernelGGL(conv5x5_bf16split_kernel<C>, dim3((unsigned)grid), dim3(XNT), 0, st, A);
+  if constexpr (QUAD)
+    hipLaunchKernelGGL(conv5x5_bf16split_quad_kernel<C>, dim3((unsigned)grid), dim3(XNT), 0, st, A);
+  else
+    hipLaunchKernelGGL(conv5x5_bf16split_kernel<C>, dim3((unsigned)grid), dim3(XNT), 0, st, A);
   VG_CHECK_LAUNCH();
   if (ksplit > 1) {
     if (A.ysplit > 0x7fffffffUL) return VG_ERR_BAD_ARG;
@@ -378,7 +501,9 @@ int launch_x(const float* x, const bf16x8* w, const float* bias, float* y, int B
   return 0;
 }
 
-VG_KNOB(int, g_x_tile_override, -1);   // diagnostics: 0 = 128 cout x 128 px, 1 = 64 x 128, 2 = 64 x 64, 3 = 32 cout x 128 px, 4 = 32 x 256 (transposed)
+// diagnostics: 0 = 128 cout x 128 px, 1 = 64 x 128, 2 = 64 x 64, 3 = 32 cout x 128 px, 4 = 32 x 256 (transposed, one workgroup
+// per parity class), 5 = 128 x 128 along cout, 6 = 32 x 256 quad (transposed, stride 2, 2 planes: all four classes per workgroup)
+VG_KNOB(int, g_x_tile_override, -1);
 
 template <int MODE, int S, int WC, int FC, int FP, int NP, bool F16>
 int dispatch_geom(const float* x, const bf16x8* w, const float* bias, float* y, int B, int Cin, int XH, int XW,
@@ -415,8 +540,14 @@ int dispatch_x(const float* x, const bf16x8* w, const float* bias, float* y, int
   // 3 planes: the 128 x 128 tile with the four wavefronts along cout (each loads only its own filter fragment)
   // measured 0-15 % faster than the 2 x 2 arrangement, never slower
   if (NP == 3 && (var == 0 || var == 1) && Cout >= 128 && px128 * cdiv(Cout, 128) >= 256) var = 5;
+  // stride 2, 2 planes, images at least one 8 x 32 tile wide: the quad form of that tile (bit-identical to variant 4),
+  // once its grid -- a quarter of the per-class one -- has a workgroup for every CU.  Measured (profiles/r08_convT_quad.json):
+  // 0.56 - 0.89 of the per-class time at 256 and 512 workgroups, 1.0 - 1.5 of it at 128.
+  constexpr bool HAS_QUAD = MODE == X_TR && S == 2 && NP == 2;
+  if (HAS_QUAD && var == 4 && tsw >= 32 && (long)B * cdiv(tsh, 8) * cdiv(tsw, 32) >= 256) var = 6;
   if (MODE == X_FWD && xs.k > 1) var = 0;             // split-K is sized for the 128 x 128 tile
-  else if (g_x_tile_override >= 0 && g_x_tile_override <= 5 && !(g_x_tile_override == 4 && MODE == X_FWD))
+  else if (g_x_tile_override >= 0 && g_x_tile_override <= 6 && !(g_x_tile_override == 4 && MODE == X_FWD) &&
+           !(g_x_tile_override == 6 && !HAS_QUAD))
     var = g_x_tile_override;
   if (var == 0) return dispatch_geom<MODE, S, 2, 2, 2, NP, F16>(x, w, bias, y, B, Cin, XH, XW, Cout, xs, st);
   if (var == 1) return dispatch_geom<MODE, S, 2, 1, 2, NP, F16>(x, w, bias, y, B, Cin, XH, XW, Cout, xs, st);
@@ -424,6 +555,9 @@ int dispatch_x(const float* x, const bf16x8* w, const float* bias, float* y, int
   if (var == 5) return dispatch_geom<MODE, S, 4, 1, 4, NP, F16>(x, w, bias, y, B, Cin, XH, XW, Cout, xs, st);   // 4 wavefronts along cout
   if constexpr (MODE == X_TR) {
     if (var == 4) return dispatch_geom<MODE, S, 1, 1, 2, NP, F16>(x, w, bias, y, B, Cin, XH, XW, Cout, xs, st);
+  }
+  if constexpr (HAS_QUAD) {     // one geometry: the 8 x 32 tile, whatever the image (narrower ones are masked)
+    if (var == 6) return launch_x<XCfg<MODE, S, 1, 8, 32, 1, 1, 2, NP, F16>, true>(x, w, bias, y, B, Cin, XH, XW, Cout, xs, st);
   }
   return dispatch_geom<MODE, S, 2, 1, 1, NP, F16>(x, w, bias, y, B, Cin, XH, XW, Cout, xs, st);
 }

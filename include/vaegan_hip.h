@@ -574,8 +574,9 @@ int vg_debug_wgrad_plan(int B, int Cin, int H, int W, int Cout, int stride, cons
 int vg_debug_wgrad_split_plan(int B, int Cin, int H, int W, int Cout, int stride, int planes, int* out);
 int vg_debug_wgrad_thin_plan(int B, int Cin, int H, int W, int Cout, int stride, int planes, const void* dw,
                              const void* workspace, int* out);
-/* split-bf16 kernels of conv_bf16split.hip: 0 = 128x128, 1 = 64x128, 2 = 64x64, 3 = 32x128, 4 = 32x256 (transposed),
- * 5 = 128x128 with the 4 wavefronts along cout, -1 = heuristic */
+/* split-bf16 kernels of conv_bf16split.hip: 0 = 128x128, 1 = 64x128, 2 = 64x64, 3 = 32x128, 4 = 32x256 (transposed, one
+ * workgroup per output-parity class), 5 = 128x128 with the 4 wavefronts along cout, 6 = 32x256 quad (transposed, stride 2,
+ * two planes: all four parity classes per workgroup, bit-identical to 4; ignored elsewhere), -1 = heuristic */
 int vg_debug_set_conv_bf16split_tile(int variant);
 /* stride-2 ring kernel of conv_ring.hip: 0 = 256 cout x 128 px, 1 / 2 = 128 x 128 (2x4 / 4x2 wavefronts),
  * 3 = 128 x 256 (transposed), -1 = heuristic */

@@ -16,8 +16,16 @@
 // workgroup, one atomicOr per workgroup that saw something, none in a clean step.  It DETECTS, it does not skip the
 // update: a skip would need a grid-wide answer before the first store.  When a bit is up the weights are poisoned;
 // recovery is the last good checkpoint.  The arithmetic that writes p, m, v and amax is the unchecked step's.
+//
+// Weight EMA (vg_adam_step_ema / vg_adam_step_dev_ema): the thread that has just formed an element's new p also moves
+// the element's running average, e <- e + (1 - decay) (p_new - e) (torch's lerp form for weights below 0.5), from the
+// value in its register: 8 more bytes per parameter instead of the 12 of a separate pass over p and e.  It is a
+// compile-time variant with a pack of its own (AdamPackEma): the kernels of the entry points above are what they
+// were.  An inf / NaN in p goes into e unfiltered; the guard reports it as before.
 #include "common.hpp"
 #include "vaegan_hip.h"
+
+#include <type_traits>
 
 namespace {
 
@@ -35,6 +43,12 @@ struct AdamPack {
   int count;
 };
 
+// The pack of the EMA variant: e[t] may be NULL (that tensor is not averaged); omd = (float)(1 - decay).
+struct AdamPackEma : AdamPack {
+  float* e[AMAX];
+  float omd;
+};
+
 __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, float omb1, float b2, float omb2,
                                          float step_size, float bc2s, float eps) {
   m = m + omb1 * (g - m);
@@ -42,6 +56,25 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
   const float denom = sqrtf(v) / bc2s + eps;
   p = p - step_size * (m / denom);
 }
+
+// adam_one for the EMA variant, which must give the bits of the kernels without EMA element by element -- wherever its
+// own alignment rule (the EMA pointer counts) sends the element.  Those kernels are compiled under the default
+// contraction, and the compiler forms v differently in their two loops: in the 16-byte body as ONE fma,
+// fma(b2, v, (omb2 g) g), in the scalar loops as two rounded products and a rounded sum; m and p are an fma in both.
+// So this copy spells the roundings out (no contraction of its own) and takes, per element, which of the two loops
+// the step without EMA would have run it in.  tests/test_adam_ema_gpu.py compares the bits on every path.
+__device__ __forceinline__ void adam_one_as(bool body, float& p, float g, float& m, float& v, float omb1, float b2,
+                                            float omb2, float step_size, float bc2s, float eps) {
+#pragma clang fp contract(off)
+  m = __builtin_fmaf(omb1, g - m, m);
+  const float gg = (omb2 * g) * g;
+  const float b2v = b2 * v;
+  v = body ? __builtin_fmaf(b2, v, gg) : b2v + gg;
+  const float denom = sqrtf(v) / bc2s + eps;
+  p = __builtin_fmaf(-step_size, m / denom, p);
+}
+
+__device__ __forceinline__ float ema_one(float e, float p, float omd) { return e + omd * (p - e); }
 
 // One thread: the scalars of an optimizer step whose step count lives on the device (a step captured in a HIP graph
 // cannot take them as kernel arguments: they change from replay to replay).  `advance`: the device counter is advanced
@@ -77,9 +110,10 @@ __device__ __forceinline__ void block_flag_or(unsigned bits, unsigned* out) {
   }
 }
 
-template <bool DEV>
-__global__ __launch_bounds__(ANT) void adam_multi_kernel(AdamPack A, float omb1, float b2, float omb2, float step_size,
-                                                        float bc2s, float eps, const float* __restrict__ scalars) {
+template <bool DEV, bool EMA>
+__global__ __launch_bounds__(ANT) void adam_multi_kernel(std::conditional_t<EMA, AdamPackEma, AdamPack> A, float omb1,
+                                                        float b2, float omb2, float step_size, float bc2s, float eps,
+                                                        const float* __restrict__ scalars) {
   if constexpr (DEV) {
     step_size = scalars[0];
     bc2s = scalars[1];
@@ -93,7 +127,15 @@ __global__ __launch_bounds__(ANT) void adam_multi_kernel(AdamPack A, float omb1,
   const float* __restrict__ g = A.g[t];
   float* __restrict__ m = A.m[t];
   float* __restrict__ v = A.v[t];
-  const bool vec = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
+  bool vec = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
+  [[maybe_unused]] const bool vec_step = vec;      // what the step without EMA decides for this tensor (adam_one_as)
+  float* __restrict__ e = nullptr;      // (uniform over the workgroup, like t)
+  float omd = 0.f;
+  if constexpr (EMA) {
+    e = A.e[t];
+    omd = A.omd;
+    vec = vec && (((uintptr_t)e & 15) == 0);      // NULL passes: the choice of a tensor without an average is unchanged
+  }
   // bound of max |p| for the fp16-plane GEMMs that read this weight next (VgAdamTensor::amax): the step that changes the
   // weight is the one pass that sees every new value anyway -- no separate 134 MB read per weight and iteration
   unsigned am = 0;
@@ -107,7 +149,10 @@ __global__ __launch_bounds__(ANT) void adam_multi_kernel(AdamPack A, float omb1,
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         float pj = pv[j], mj = mv[j], vj = vv[j];
-        adam_one(pj, gv[j], mj, vj, omb1, b2, omb2, step_size, bc2s, eps);
+        if constexpr (EMA)
+          adam_one_as(true, pj, gv[j], mj, vj, omb1, b2, omb2, step_size, bc2s, eps);
+        else
+          adam_one(pj, gv[j], mj, vj, omb1, b2, omb2, step_size, bc2s, eps);
         pv[j] = pj; mv[j] = mj; vv[j] = vj;
         am = max(am, abs_bits(pj));
         gm = max(gm, abs_bits(gv[j]));
@@ -115,18 +160,43 @@ __global__ __launch_bounds__(ANT) void adam_multi_kernel(AdamPack A, float omb1,
       *reinterpret_cast<f32x4*>(p + i) = pv;
       *reinterpret_cast<f32x4*>(m + i) = mv;
       *reinterpret_cast<f32x4*>(v + i) = vv;
+      if constexpr (EMA) {
+        if (e) {
+          f32x4 ev = *reinterpret_cast<f32x4*>(e + i);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) ev[j] = ema_one(ev[j], pv[j], omd);
+          *reinterpret_cast<f32x4*>(e + i) = ev;
+        }
+      }
     }
     for (unsigned long long i = end4 + threadIdx.x; i < end; i += ANT) {
       const float gi = g[i];
-      adam_one(p[i], gi, m[i], v[i], omb1, b2, omb2, step_size, bc2s, eps);
-      am = max(am, abs_bits(p[i]));
+      if constexpr (EMA) {
+        float pi = p[i];      // the average below takes the new p from this register
+        adam_one_as(false, pi, gi, m[i], v[i], omb1, b2, omb2, step_size, bc2s, eps);
+        p[i] = pi;
+        if (e) e[i] = ema_one(e[i], pi, omd);
+        am = max(am, abs_bits(pi));
+      } else {
+        adam_one(p[i], gi, m[i], v[i], omb1, b2, omb2, step_size, bc2s, eps);
+        am = max(am, abs_bits(p[i]));
+      }
       gm = max(gm, abs_bits(gi));
     }
   } else {
+    [[maybe_unused]] const unsigned long long end4 = base + ((end - base) & ~3ULL);
     for (unsigned long long i = base + threadIdx.x; i < end; i += ANT) {
       const float gi = g[i];
-      adam_one(p[i], gi, m[i], v[i], omb1, b2, omb2, step_size, bc2s, eps);
-      am = max(am, abs_bits(p[i]));
+      if constexpr (EMA) {
+        float pi = p[i];      // the average below takes the new p from this register
+        adam_one_as(vec_step && i < end4, pi, gi, m[i], v[i], omb1, b2, omb2, step_size, bc2s, eps);
+        p[i] = pi;
+        if (e) e[i] = ema_one(e[i], pi, omd);
+        am = max(am, abs_bits(pi));
+      } else {
+        adam_one(p[i], gi, m[i], v[i], omb1, b2, omb2, step_size, bc2s, eps);
+        am = max(am, abs_bits(p[i]));
+      }
       gm = max(gm, abs_bits(gi));
     }
   }
@@ -140,16 +210,21 @@ __global__ __launch_bounds__(ANT) void adam_multi_kernel(AdamPack A, float omb1,
 }  // namespace
 
 namespace {
+template <bool EMA>
 int adam_launch(const VgAdamTensor* tensors, unsigned* const* flags, int count, double beta1, double beta2, double eps,
-                float step_size, float bc2s, const float* scalars, hipStream_t st) {
+                float step_size, float bc2s, const float* scalars, hipStream_t st, float* const* ema = nullptr,
+                double ema_decay = 0.0) {
   const float omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);
   int i = 0;
   while (i < count) {
-    AdamPack A;
+    std::conditional_t<EMA, AdamPackEma, AdamPack> A;
+    if constexpr (EMA) A.omd = (float)(1.0 - ema_decay);
     A.count = 0;
     unsigned blocks = 0;
     while (i < count && A.count < AMAX) {
       unsigned* const flag = flags ? flags[i] : nullptr;
+      float* ema_i = nullptr;
+      if constexpr (EMA) ema_i = ema[i];
       const VgAdamTensor& T = tensors[i++];
       if (T.n == 0) continue;      // (its flag word is left untouched)
       if (!T.p || !T.g || !T.m || !T.v) return VG_ERR_BAD_ARG;
@@ -159,17 +234,18 @@ int adam_launch(const VgAdamTensor* tensors, unsigned* const* flags, int count, 
       A.p[k] = T.p; A.g[k] = T.g; A.m[k] = T.m; A.v[k] = T.v; A.n[k] = T.n;
       A.amax[k] = reinterpret_cast<unsigned*>(T.amax);
       A.flag[k] = flag;
+      if constexpr (EMA) A.e[k] = ema_i;
       A.first_block[k] = blocks;
       blocks += (unsigned)nb;
     }
     if (A.count == 0) break;
     A.first_block[A.count] = blocks;
     if (scalars)
-      hipLaunchKernelGGL(adam_multi_kernel<true>, dim3(blocks), dim3(ANT), 0, st, A, omb1, (float)beta2, omb2, 0.f, 0.f,
-                         (float)eps, scalars);
+      hipLaunchKernelGGL((adam_multi_kernel<true, EMA>), dim3(blocks), dim3(ANT), 0, st, A, omb1, (float)beta2, omb2, 0.f,
+                         0.f, (float)eps, scalars);
     else
-      hipLaunchKernelGGL(adam_multi_kernel<false>, dim3(blocks), dim3(ANT), 0, st, A, omb1, (float)beta2, omb2, step_size,
-                         bc2s, (float)eps, (const float*)nullptr);
+      hipLaunchKernelGGL((adam_multi_kernel<false, EMA>), dim3(blocks), dim3(ANT), 0, st, A, omb1, (float)beta2, omb2,
+                         step_size, bc2s, (float)eps, (const float*)nullptr);
     VG_CHECK_LAUNCH();
   }
   return 0;
@@ -182,8 +258,18 @@ extern "C" int vg_adam_step_checked(const VgAdamTensor* tensors, int count, doub
   if (count < 0 || (count > 0 && !tensors) || !(bias_correction1 > 0.0) || !(bias_correction2_sqrt > 0.0))
     return VG_ERR_BAD_ARG;
   // scalars are formed in double and rounded once, as torch does with its Python-side hyper-parameters
-  return adam_launch(tensors, nonfinite, count, beta1, beta2, eps, (float)(lr / bias_correction1),
-                     (float)bias_correction2_sqrt, nullptr, (hipStream_t)stream);
+  return adam_launch<false>(tensors, nonfinite, count, beta1, beta2, eps, (float)(lr / bias_correction1),
+                            (float)bias_correction2_sqrt, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int vg_adam_step_ema(const VgAdamTensor* tensors, int count, double lr, double beta1, double beta2, double eps,
+                                double bias_correction1, double bias_correction2_sqrt, unsigned* const* nonfinite,
+                                float* const* ema, double ema_decay, void* stream) {
+  if (count < 0 || (count > 0 && !tensors) || !(bias_correction1 > 0.0) || !(bias_correction2_sqrt > 0.0) || !ema ||
+      !(ema_decay > 0.0 && ema_decay < 1.0))
+    return VG_ERR_BAD_ARG;
+  return adam_launch<true>(tensors, nonfinite, count, beta1, beta2, eps, (float)(lr / bias_correction1),
+                           (float)bias_correction2_sqrt, nullptr, (hipStream_t)stream, ema, ema_decay);
 }
 
 extern "C" int vg_adam_step(const VgAdamTensor* tensors, int count, double lr, double beta1, double beta2, double eps,
@@ -206,7 +292,16 @@ extern "C" int vg_adam_prepare(double step, double* step_dev, int advance_device
 extern "C" int vg_adam_step_dev_checked(const VgAdamTensor* tensors, int count, double beta1, double beta2, double eps,
                                         const float* scalars, unsigned* const* nonfinite, void* stream) {
   if (count < 0 || (count > 0 && !tensors) || !scalars) return VG_ERR_BAD_ARG;
-  return adam_launch(tensors, nonfinite, count, beta1, beta2, eps, 0.f, 0.f, scalars, (hipStream_t)stream);
+  return adam_launch<false>(tensors, nonfinite, count, beta1, beta2, eps, 0.f, 0.f, scalars, (hipStream_t)stream);
+}
+
+extern "C" int vg_adam_step_dev_ema(const VgAdamTensor* tensors, int count, double beta1, double beta2, double eps,
+                                    const float* scalars, unsigned* const* nonfinite, float* const* ema,
+                                    double ema_decay, void* stream) {
+  if (count < 0 || (count > 0 && !tensors) || !scalars || !ema || !(ema_decay > 0.0 && ema_decay < 1.0))
+    return VG_ERR_BAD_ARG;
+  return adam_launch<true>(tensors, nonfinite, count, beta1, beta2, eps, 0.f, 0.f, scalars, (hipStream_t)stream, ema,
+                           ema_decay);
 }
 
 extern "C" int vg_adam_step_dev(const VgAdamTensor* tensors, int count, double beta1, double beta2, double eps,

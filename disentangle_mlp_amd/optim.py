@@ -12,6 +12,12 @@ maximize, a closure, non-fp32 / non-contiguous / CPU tensors) take the inherited
 (`NONFINITE_GRAD`) and the parameters it wrote (`NONFINITE_PARAM`) -- ``vg_adam_step_checked`` -- in device words the
 host reads when it chooses to (`nonfinite`, `nonfinite_words`, `clear_nonfinite`).  It detects, it does not skip the
 update: when a word is up the weights are poisoned and the last good checkpoint is the way back.
+
+``HipAdam(ema_decay=d)``: the step also keeps an exponential moving average of the weights it writes, ``e <- e +
+(1 - d) (p - e)`` -- inside the same kernel (``vg_adam_step_ema``), from the value the thread has just formed, so the
+average costs 8 bytes per parameter and no launch of its own.  The averages live in tensors fixed at construction
+(fp32 clones, or the caller's ``ema_targets``: a trainer's shadow module), are NOT part of ``state_dict()`` -- that
+stays torch.optim.Adam's -- and travel through `ema_state` / `load_ema_state`.
 """
 import ctypes
 import math
@@ -57,8 +63,13 @@ class HipAdam(optim.Adam):
     host mirrors the device counter (`prepare_capture` / `replayed`)."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, capturable=False,
-                 nonfinite_guard=False):
+                 nonfinite_guard=False, ema_decay=None, ema_targets=None):
         self._words = None
+        self._ema = None
+        if ema_decay is not None and not (0.0 < float(ema_decay) < 1.0):      # (NaN fails both comparisons)
+            raise ValueError(f"HipAdam: ema_decay must lie in (0, 1), got {ema_decay!r}")
+        if ema_decay is None and ema_targets is not None:
+            raise ValueError("HipAdam: ema_targets without ema_decay")
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad,
                          foreach=False, fused=False, capturable=False)
         self.device_scalars = bool(capturable)
@@ -82,12 +93,68 @@ class HipAdam(optim.Adam):
             ps = [p for g in self.param_groups for p in g["params"]]
             self._word_of = {p: i for i, p in enumerate(ps)}
             self._words = torch.zeros(len(ps), dtype=torch.int32, device=ps[0].device)
+        # weight EMA: one fp32 tensor per parameter, in param_groups order, fixed here and never replaced -- like
+        # `_words`, a captured step writes where later readers (a trainer's shadow module) read
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self._ema_of = {}         # parameter -> index into self._ema
+        if self.ema_decay is not None:
+            ps = [p for g in self.param_groups for p in g["params"]]
+            if ema_targets is None:
+                ema = [p.detach().clone(memory_format=torch.contiguous_format) for p in ps]
+            else:
+                ema = [t.detach() if t.requires_grad else t for t in ema_targets]
+                if len(ema) != len(ps):
+                    raise ValueError(f"HipAdam: {len(ema)} ema_targets for {len(ps)} parameters")
+                for i, (t, p) in enumerate(zip(ema, ps)):
+                    if t.shape != p.shape or t.device != p.device or t.dtype != p.dtype or not t.is_contiguous():
+                        raise ValueError(f"HipAdam: ema_targets[{i}] must be a contiguous tensor of its parameter's "
+                                         f"shape, device and dtype ({tuple(p.shape)}, {p.device}, {p.dtype})")
+                    if t.data_ptr() == p.data_ptr() and t.numel():
+                        raise ValueError(f"HipAdam: ema_targets[{i}] is its parameter's own storage")
+            self._ema_of = {p: i for i, p in enumerate(ps)}
+            self._ema = ema
 
     def add_param_group(self, param_group):
         if self._words is not None:
             raise RuntimeError("HipAdam(nonfinite_guard=True): the flag words are laid out at construction; "
                                "pass every parameter group to the constructor")
+        if self._ema is not None:
+            raise RuntimeError("HipAdam(ema_decay=...): the EMA tensors are laid out at construction; "
+                               "pass every parameter group to the constructor")
         return super().add_param_group(param_group)
+
+    # ---- weight EMA ------------------------------------------------------------------------------------------
+    def _need_ema(self):
+        if self._ema is None:
+            raise RuntimeError("HipAdam: construct with ema_decay=... to track an EMA of the weights")
+
+    def ema_tensors(self):
+        """The EMA tensors themselves, one per parameter in ``param_groups`` order (the step writes them in place)."""
+        self._need_ema()
+        return list(self._ema)
+
+    @torch.no_grad()
+    def reset_ema(self):
+        """EMA <- the parameters as they are now (after weights were loaded from a checkpoint without an average)."""
+        self._need_ema()
+        for e, p in zip(self._ema, (p for g in self.param_groups for p in g["params"])):
+            e.copy_(p)
+
+    @torch.no_grad()
+    def ema_state(self):
+        """Clones of the EMA tensors, in ``param_groups`` order: what `load_ema_state` takes."""
+        self._need_ema()
+        return [e.clone() for e in self._ema]
+
+    @torch.no_grad()
+    def load_ema_state(self, tensors):
+        """Copy ``tensors`` (parallel to `ema_tensors`) INTO the EMA tensors: their storage stays where it is."""
+        self._need_ema()
+        tensors = list(tensors)
+        if len(tensors) != len(self._ema) or any(t.shape != e.shape for t, e in zip(tensors, self._ema)):
+            raise ValueError("HipAdam.load_ema_state: one tensor per parameter, of the parameter's shape")
+        for e, t in zip(self._ema, tensors):
+            e.copy_(t)
 
     # ---- non-finite guard ----------------------------------------------------------------------------------
     def _need_guard(self):
@@ -206,13 +273,23 @@ class HipAdam(optim.Adam):
                 self._dev[gi][0].fill_(steps.pop())          # the device counter a replayed step advances
 
     @torch.no_grad()
-    def step(self, closure=None):
+    def step(self, closure=None, update_ema=True):
+        """``update_ema`` (with ``ema_decay`` set): False steps without touching the averages -- exactly the launches of
+        an optimizer without EMA (a trainer that steps twice per iteration averages once).  A parameter the step skips
+        (``grad is None``) keeps its EMA that step: the average follows the weights the optimizer writes, and a frozen
+        weight's average would only drift towards the value it already tracks."""
+        ema_on = self._ema is not None and update_ema
         if closure is not None or not all(self._native_ok(g) for g in self.param_groups):
             if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("HipAdam: this configuration takes torch's step, which cannot be captured here")
             self._flush_replays()
             self._torch_stepped = True
-            return super().step(closure)
+            stepped = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
+            loss = super().step(closure)
+            if ema_on and stepped:      # never silently stale: the same average, formed by torch after its step
+                torch._foreach_lerp_([self._ema[self._ema_of[p]] for p in stepped], [p.detach() for p in stepped],
+                                     1.0 - self.ema_decay)
+            return loss
         lib = _lib.load()
         stream = torch.cuda.current_stream().cuda_stream
         capturing = torch.cuda.is_current_stream_capturing()
@@ -248,6 +325,8 @@ class HipAdam(optim.Adam):
                 arr = (_AdamTensor * len(items))()
                 flags = None if words is None else (ctypes.c_void_p * len(items))(
                     *[words + 4 * self._word_of[it[0]] for it in items])
+                ema = None if not ema_on else (ctypes.c_void_p * len(items))(
+                    *[self._ema[self._ema_of[it[0]]].data_ptr() for it in items])
                 for i, (p, g, m, v) in enumerate(items):
                     bi = self._bound_of.get(p) if bounds is not None else None
                     arr[i] = _AdamTensor(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(),
@@ -257,7 +336,11 @@ class HipAdam(optim.Adam):
                     # an eager step also stores its count in the device counter: replays may follow it
                     check(lib.vg_adam_prepare(float(step), step_dev.data_ptr(), 1 if capturing else 0, float(group["lr"]),
                                               float(beta1), float(beta2), scalars.data_ptr(), stream), "vg_adam_prepare")
-                    if flags is not None:
+                    if ema is not None:
+                        check(lib.vg_adam_step_dev_ema(arr, len(items), float(beta1), float(beta2), float(group["eps"]),
+                                                       scalars.data_ptr(), flags, ema, self.ema_decay, stream),
+                              "vg_adam_step_dev_ema")
+                    elif flags is not None:
                         check(lib.vg_adam_step_dev_checked(arr, len(items), float(beta1), float(beta2), float(group["eps"]),
                                                            scalars.data_ptr(), flags, stream), "vg_adam_step_dev_checked")
                     else:
@@ -268,7 +351,11 @@ class HipAdam(optim.Adam):
                     continue
                 bc1 = 1.0 - beta1 ** step
                 bc2_sqrt = math.sqrt(1.0 - beta2 ** step)
-                if flags is not None:
+                if ema is not None:
+                    check(lib.vg_adam_step_ema(arr, len(items), float(group["lr"]), float(beta1), float(beta2),
+                                               float(group["eps"]), bc1, bc2_sqrt, flags, ema, self.ema_decay, stream),
+                          "vg_adam_step_ema")
+                elif flags is not None:
                     check(lib.vg_adam_step_checked(arr, len(items), float(group["lr"]), float(beta1), float(beta2),
                                                    float(group["eps"]), bc1, bc2_sqrt, flags, stream), "vg_adam_step_checked")
                 else:

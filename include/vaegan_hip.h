@@ -45,7 +45,8 @@ extern "C" {
  * whose version is not the header's (the .so files are build products that travel with the working tree: a stale one
  * still exports every old symbol).  3: round 3.  4: round 4 (fp16 planes: VG_PLANES_F16, the *_amax arguments).
  * 6: vg_conv_general_* (the general forward convolution).  7: vg_adam_step_checked / vg_adam_step_dev_checked.
- * Entry points that are only ADDED (the four of csrc/fid_front.hip; vg_bn_eval_coeffs, vg_bn_eval_act_bwd) change
+ * Entry points that are only ADDED (the four of csrc/fid_front.hip; vg_bn_eval_coeffs, vg_bn_eval_act_bwd;
+ * vg_adam_step_ema, vg_adam_step_dev_ema) change
  * nothing an existing caller sees and keep the version: a binding that needs them and finds a library without them
  * fails at the symbol lookup, as loudly. */
 #define VG_ABI_VERSION 7
@@ -489,6 +490,21 @@ int vg_adam_step_checked(const VgAdamTensor* tensors, int count, double lr, doub
                          void* stream);
 int vg_adam_step_dev_checked(const VgAdamTensor* tensors, int count, double beta1, double beta2, double eps,
                              const float* scalars, unsigned* const* nonfinite, void* stream);
+/* The two checked steps that also keep an exponential moving average of the weights they write.  `ema` is a HOST
+ * array of `count` DEVICE pointers parallel to `tensors` (fp32, n elements each, not overlapping p, g, m, v); after
+ * an element's p is updated the same thread does
+ *   e <- e + (float)(1 - ema_decay) * (p_new - e)
+ * from the p it has just formed (8 more bytes per parameter; an inf / NaN in p goes into e unfiltered and is
+ * reported by the guard as before).  Single entries may be NULL: those tensors are stepped and not averaged.
+ * ema == NULL is VG_ERR_BAD_ARG (that is what the entry points above are for), as is an ema_decay outside (0, 1) --
+ * before any launch.  `nonfinite` as above (may be NULL).  p, m, v, amax and the flag words are bit for bit those of
+ * the checked step. */
+int vg_adam_step_ema(const VgAdamTensor* tensors, int count, double lr, double beta1, double beta2, double eps,
+                     double bias_correction1, double bias_correction2_sqrt, unsigned* const* nonfinite,
+                     float* const* ema, double ema_decay, void* stream);
+int vg_adam_step_dev_ema(const VgAdamTensor* tensors, int count, double beta1, double beta2, double eps,
+                         const float* scalars, unsigned* const* nonfinite, float* const* ema, double ema_decay,
+                         void* stream);
 
 /* ---- image I/O either side of the step -----------------
  * Input pipeline of dataloader/dataset.py:37-43 (ToTensor + Normalize(mean, std) of a

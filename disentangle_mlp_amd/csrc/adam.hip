@@ -13,15 +13,28 @@
 // Non-finite guard (vg_adam_step_checked / vg_adam_step_dev_checked): the step is the one pass that reads every gradient
 // and writes every parameter, so it also notices an inf / NaN among them -- |x| as bits >= 0x7f800000 -- and ORs
 // VG_NONFINITE_GRAD / VG_NONFINITE_PARAM into the tensor's caller-owned flag word: one wavefront / LDS reduction per
-// workgroup, one atomicOr per workgroup that saw something, none in a clean step.  It DETECTS, it does not skip the
-// update: a skip would need a grid-wide answer before the first store.  When a bit is up the weights are poisoned;
-// recovery is the last good checkpoint.  The arithmetic that writes p, m, v and amax is the unchecked step's.
+// workgroup, one atomicOr per workgroup that saw something, none in a clean step.  By itself it DETECTS, it does not
+// skip the update: a skip needs a grid-wide answer before the first store -- which the opt-in norm pass below gives
+// (vg_adam_step_clip with skip_nonfinite).  Without that opt-in, when a bit is up the weights are poisoned; recovery
+// is the last good checkpoint.  The arithmetic that writes p, m, v and amax is the unchecked step's.
 //
 // Weight EMA (vg_adam_step_ema / vg_adam_step_dev_ema): the thread that has just formed an element's new p also moves
 // the element's running average, e <- e + (1 - decay) (p_new - e) (torch's lerp form for weights below 0.5), from the
 // value in its register: 8 more bytes per parameter instead of the 12 of a separate pass over p and e.  It is a
 // compile-time variant with a pack of its own (AdamPackEma): the kernels of the entry points above are what they
 // were.  An inf / NaN in p goes into e unfiltered; the guard reports it as before.
+//
+// Clipping by global norm / skipping a non-finite step (vg_grad_sumsq_multi, vg_grad_clip_finalize, vg_adam_step_clip /
+// vg_adam_step_dev_clip): one deterministic pass over the gradients in front of the step -- fp64 squares and sums from
+// the thread level on (the square of an fp32 number is exact in fp64, and no |g| overflows), one fp64 partial per
+// workgroup in a slot of its own, no atomics -- and a one-workgroup kernel that adds the partials in a fixed order and
+// writes a four-word record: the norm, the clip coefficient min(1, max_norm / (norm + 1e-6)) (clip_grad_norm_'s
+// formula, formed in double, rounded once), a skip word and a running count of skips.  The clip variant of the step
+// reads the record at its top and uses every gradient as gs = coef * g (one fp32 rounding, that of g.mul_(coef)), from
+// registers: 4 more bytes per parameter instead of the 12 of torch's recipe.  With the skip word up it stores nothing to
+// p, m, v or the EMA; it still emits max |p| (the bounds words were zeroed in front of the step) and flags the tensor
+// that holds the inf / NaN.  It is a kernel and a pack of its own: the kernels of the entry points above are what
+// they were.
 #include "common.hpp"
 #include "vaegan_hip.h"
 
@@ -207,13 +220,189 @@ __global__ __launch_bounds__(ANT) void adam_multi_kernel(std::conditional_t<EMA,
                   A.flag[t]);
 }
 
+// ---- clipping by global norm, skipping a non-finite step --------------------------------------------------------------
+// The record vg_grad_clip_finalize writes and the clip step reads: four 32-bit words.
+constexpr int REC_NORM = 0, REC_COEF = 1, REC_SKIP = 2, REC_SKIPPED = 3;
+
+struct SumsqPack {
+  const float* g[AMAX];
+  unsigned long long n[AMAX];
+  unsigned first_block[AMAX + 1];     // prefix sums of ceil(n / ACHUNK) within this launch
+  int count;
+};
+
+// One workgroup: the sum of squares, in fp64, of its ACHUNK elements of one tensor -> partials[blockIdx.x] (`partials`
+// already points at this launch's first slot).  Every thread adds its elements in index order, the wavefronts and the
+// workgroup reduce in a fixed tree: the same bits run to run.
+__global__ __launch_bounds__(ANT) void grad_sumsq_multi_kernel(SumsqPack A, double* __restrict__ partials) {
+  __shared__ double red[ANT / 64];
+  int t = 0;
+  while (t + 1 < A.count && blockIdx.x >= A.first_block[t + 1]) ++t;
+  const unsigned long long n = A.n[t];
+  const unsigned long long base = (unsigned long long)(blockIdx.x - A.first_block[t]) * ACHUNK;
+  const unsigned long long end = min(base + (unsigned long long)ACHUNK, n);
+  const float* __restrict__ g = A.g[t];
+  double s = 0.0;
+  unsigned long long tail = base;
+  if (((uintptr_t)g & 15) == 0) {      // (base is a multiple of ACHUNK: g + base is aligned when g is)
+    const unsigned long long end4 = base + ((end - base) & ~3ULL);
+    for (unsigned long long i = base + 4ULL * threadIdx.x; i < end4; i += 4ULL * ANT) {
+      const f32x4 gv = *reinterpret_cast<const f32x4*>(g + i);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const double d = (double)gv[j];
+        s += d * d;
+      }
+    }
+    tail = end4;
+  }
+  for (unsigned long long i = tail + threadIdx.x; i < end; i += ANT) {
+    const double d = (double)g[i];
+    s += d * d;
+  }
+  s = block_sum<ANT, double>(s, red);
+  if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// One workgroup: norm = sqrt(sum of the partials), added in a fixed order in fp64, and the record.
+__global__ __launch_bounds__(ANT) void grad_clip_finalize_kernel(const double* __restrict__ partials,
+                                                                 unsigned long long n_partials, double max_norm,
+                                                                 int skip_nonfinite, float* __restrict__ record) {
+  __shared__ double red[ANT / 64];
+  double s = 0.0;
+  for (unsigned long long i = threadIdx.x; i < n_partials; i += ANT) s += partials[i];
+  s = block_sum<ANT, double>(s, red);
+  if (threadIdx.x == 0) {
+    const double norm = sqrt(s);
+    const bool finite = isfinite(norm);
+    double coef = 1.0;
+    if (max_norm > 0.0) {
+      // torch: clamp(max_norm / (total_norm + 1e-6), max=1.0) -- a NaN stays a NaN (fmin would drop it)
+      const double c = max_norm / (norm + 1e-6);
+      coef = c < 1.0 ? c : (c != c ? c : 1.0);
+    }
+    const unsigned skip = (!finite && skip_nonfinite) ? 1u : 0u;
+    if (skip) coef = 0.0;
+    unsigned* const words = reinterpret_cast<unsigned*>(record);
+    record[REC_NORM] = (float)norm;
+    record[REC_COEF] = (float)coef;
+    words[REC_SKIP] = skip;
+    words[REC_SKIPPED] = words[REC_SKIPPED] + skip;
+  }
+}
+
+// gs = coef * g, rounded once as g.mul_(coef) rounds it: kept from being fused into the m update that follows.
+__device__ __forceinline__ float clip_scale(float coef, float g) {
+#pragma clang fp contract(off)
+  return coef * g;
+}
+
+// The step of adam_multi_kernel<DEV, true> with every gradient scaled by the record's coefficient, or -- the record's
+// skip word up -- no step at all: p and g are read for max |p| and the flag words, nothing is stored to p, m, v, e.
+// e[t] may be NULL as in the EMA variant; a launch without any average passes NULLs.  adam_one_as and its `body` rule
+// give, element by element, the bits of the step without the feature on the scaled gradient.
+template <bool DEV>
+__global__ __launch_bounds__(ANT) void adam_clip_multi_kernel(AdamPackEma A, float omb1, float b2, float omb2,
+                                                             float step_size, float bc2s, float eps,
+                                                             const float* __restrict__ scalars,
+                                                             const float* __restrict__ record) {
+  if constexpr (DEV) {
+    step_size = scalars[0];
+    bc2s = scalars[1];
+  }
+  const float coef = record[REC_COEF];
+  const bool skip = reinterpret_cast<const unsigned*>(record)[REC_SKIP] != 0u;      // (uniform over the grid)
+  int t = 0;
+  while (t + 1 < A.count && blockIdx.x >= A.first_block[t + 1]) ++t;
+  const unsigned long long n = A.n[t];
+  const unsigned long long base = (unsigned long long)(blockIdx.x - A.first_block[t]) * ACHUNK;
+  const unsigned long long end = min(base + (unsigned long long)ACHUNK, n);
+  float* __restrict__ p = A.p[t];
+  const float* __restrict__ g = A.g[t];
+  float* __restrict__ m = A.m[t];
+  float* __restrict__ v = A.v[t];
+  float* __restrict__ e = A.e[t];
+  const float omd = A.omd;
+  const bool vec_step = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
+  const bool vec = vec_step && (((uintptr_t)e & 15) == 0);
+  const unsigned long long end4 = base + ((end - base) & ~3ULL);
+  unsigned am = 0, gm = 0;
+  if (skip) {
+    unsigned long long tail = base;
+    if (vec_step) {
+      for (unsigned long long i = base + 4ULL * threadIdx.x; i < end4; i += 4ULL * ANT) {
+        const f32x4 pv = *reinterpret_cast<const f32x4*>(p + i);
+        const f32x4 gv = *reinterpret_cast<const f32x4*>(g + i);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          am = max(am, abs_bits(pv[j]));
+          gm = max(gm, abs_bits(gv[j]));
+        }
+      }
+      tail = end4;
+    }
+    for (unsigned long long i = tail + threadIdx.x; i < end; i += ANT) {
+      am = max(am, abs_bits(p[i]));
+      gm = max(gm, abs_bits(g[i]));
+    }
+  } else if (vec) {
+    for (unsigned long long i = base + 4ULL * threadIdx.x; i < end4; i += 4ULL * ANT) {
+      f32x4 pv = *reinterpret_cast<f32x4*>(p + i), mv = *reinterpret_cast<f32x4*>(m + i);
+      f32x4 vv = *reinterpret_cast<f32x4*>(v + i);
+      const f32x4 gv = *reinterpret_cast<const f32x4*>(g + i);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float pj = pv[j], mj = mv[j], vj = vv[j];
+        const float gs = clip_scale(coef, gv[j]);
+        adam_one_as(true, pj, gs, mj, vj, omb1, b2, omb2, step_size, bc2s, eps);
+        pv[j] = pj; mv[j] = mj; vv[j] = vj;
+        am = max(am, abs_bits(pj));
+        gm = max(gm, abs_bits(gs));
+      }
+      *reinterpret_cast<f32x4*>(p + i) = pv;
+      *reinterpret_cast<f32x4*>(m + i) = mv;
+      *reinterpret_cast<f32x4*>(v + i) = vv;
+      if (e) {
+        f32x4 ev = *reinterpret_cast<f32x4*>(e + i);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ev[j] = ema_one(ev[j], pv[j], omd);
+        *reinterpret_cast<f32x4*>(e + i) = ev;
+      }
+    }
+    for (unsigned long long i = end4 + threadIdx.x; i < end; i += ANT) {
+      const float gs = clip_scale(coef, g[i]);
+      float pi = p[i];
+      adam_one_as(false, pi, gs, m[i], v[i], omb1, b2, omb2, step_size, bc2s, eps);
+      p[i] = pi;
+      if (e) e[i] = ema_one(e[i], pi, omd);
+      am = max(am, abs_bits(pi));
+      gm = max(gm, abs_bits(gs));
+    }
+  } else {
+    for (unsigned long long i = base + threadIdx.x; i < end; i += ANT) {
+      const float gs = clip_scale(coef, g[i]);
+      float pi = p[i];
+      adam_one_as(vec_step && i < end4, pi, gs, m[i], v[i], omb1, b2, omb2, step_size, bc2s, eps);
+      p[i] = pi;
+      if (e) e[i] = ema_one(e[i], pi, omd);
+      am = max(am, abs_bits(pi));
+      gm = max(gm, abs_bits(gs));
+    }
+  }
+  if (A.amax[t]) block_amax_atomic<ANT>(am, A.amax[t]);
+  if (A.flag[t])
+    block_flag_or((gm >= NONFINITE_BITS ? (unsigned)VG_NONFINITE_GRAD : 0u) |
+                      (am >= NONFINITE_BITS ? (unsigned)VG_NONFINITE_PARAM : 0u),
+                  A.flag[t]);
+}
+
 }  // namespace
 
 namespace {
 template <bool EMA>
 int adam_launch(const VgAdamTensor* tensors, unsigned* const* flags, int count, double beta1, double beta2, double eps,
                 float step_size, float bc2s, const float* scalars, hipStream_t st, float* const* ema = nullptr,
-                double ema_decay = 0.0) {
+                double ema_decay = 0.0, const float* clip_record = nullptr) {
   const float omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);
   int i = 0;
   while (i < count) {
@@ -224,7 +413,7 @@ int adam_launch(const VgAdamTensor* tensors, unsigned* const* flags, int count, 
     while (i < count && A.count < AMAX) {
       unsigned* const flag = flags ? flags[i] : nullptr;
       float* ema_i = nullptr;
-      if constexpr (EMA) ema_i = ema[i];
+      if constexpr (EMA) ema_i = ema ? ema[i] : nullptr;      // (ema == NULL: the clip step without an average)
       const VgAdamTensor& T = tensors[i++];
       if (T.n == 0) continue;      // (its flag word is left untouched)
       if (!T.p || !T.g || !T.m || !T.v) return VG_ERR_BAD_ARG;
@@ -240,6 +429,18 @@ int adam_launch(const VgAdamTensor* tensors, unsigned* const* flags, int count, 
     }
     if (A.count == 0) break;
     A.first_block[A.count] = blocks;
+    if constexpr (EMA) {
+      if (clip_record) {
+        if (scalars)
+          hipLaunchKernelGGL((adam_clip_multi_kernel<true>), dim3(blocks), dim3(ANT), 0, st, A, omb1, (float)beta2, omb2,
+                             0.f, 0.f, (float)eps, scalars, clip_record);
+        else
+          hipLaunchKernelGGL((adam_clip_multi_kernel<false>), dim3(blocks), dim3(ANT), 0, st, A, omb1, (float)beta2, omb2,
+                             step_size, bc2s, (float)eps, (const float*)nullptr, clip_record);
+        VG_CHECK_LAUNCH();
+        continue;
+      }
+    }
     if (scalars)
       hipLaunchKernelGGL((adam_multi_kernel<true, EMA>), dim3(blocks), dim3(ANT), 0, st, A, omb1, (float)beta2, omb2, 0.f,
                          0.f, (float)eps, scalars);
@@ -307,4 +508,74 @@ extern "C" int vg_adam_step_dev_ema(const VgAdamTensor* tensors, int count, doub
 extern "C" int vg_adam_step_dev(const VgAdamTensor* tensors, int count, double beta1, double beta2, double eps,
                                 const float* scalars, void* stream) {
   return vg_adam_step_dev_checked(tensors, count, beta1, beta2, eps, scalars, nullptr, stream);
+}
+
+// ---- clipping by global norm / skipping a non-finite step: the entry points --------------------------------------------
+extern "C" size_t vg_grad_sumsq_partials(const size_t* n, int count) {
+  size_t slots = 0;
+  if (!n) return 0;
+  for (int i = 0; i < count; ++i) slots += (n[i] + ACHUNK - 1) / ACHUNK;
+  return slots;
+}
+
+extern "C" int vg_grad_sumsq_multi(const float* const* grads, const size_t* n, int count, double* partials,
+                                   size_t capacity, void* stream) {
+  if (count < 0 || (count > 0 && (!grads || !n)) || !partials) return VG_ERR_BAD_ARG;
+  if (vg_grad_sumsq_partials(n, count) > capacity) return VG_ERR_BAD_ARG;
+  for (int i = 0; i < count; ++i)
+    if (n[i] && (!grads[i] || (n[i] + ACHUNK - 1) / ACHUNK > 0x3fffffffULL)) return VG_ERR_BAD_ARG;
+  size_t first = 0;      // this launch's first slot
+  int i = 0;
+  while (i < count) {
+    SumsqPack A;
+    A.count = 0;
+    unsigned blocks = 0;
+    while (i < count && A.count < AMAX) {
+      const unsigned long long nb = (n[i] + ACHUNK - 1) / ACHUNK;
+      if (nb == 0) { ++i; continue; }
+      if (nb > 0x3fffffffULL - blocks) break;      // (a launch of its own for what does not fit this grid)
+      const int k = A.count++;
+      A.g[k] = grads[i];
+      A.n[k] = n[i];
+      A.first_block[k] = blocks;
+      blocks += (unsigned)nb;
+      ++i;
+    }
+    if (A.count == 0) break;
+    A.first_block[A.count] = blocks;
+    hipLaunchKernelGGL(grad_sumsq_multi_kernel, dim3(blocks), dim3(ANT), 0, (hipStream_t)stream, A, partials + first);
+    VG_CHECK_LAUNCH();
+    first += blocks;
+  }
+  return 0;
+}
+
+extern "C" int vg_grad_clip_finalize(const double* partials, size_t n_partials, double max_norm, int skip_nonfinite,
+                                     float* record, void* stream) {
+  if (!partials || !record || max_norm != max_norm) return VG_ERR_BAD_ARG;
+  hipLaunchKernelGGL(grad_clip_finalize_kernel, dim3(1), dim3(ANT), 0, (hipStream_t)stream, partials,
+                     (unsigned long long)n_partials, max_norm, skip_nonfinite ? 1 : 0, record);
+  VG_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int vg_adam_step_clip(const VgAdamTensor* tensors, int count, double lr, double beta1, double beta2, double eps,
+                                 double bias_correction1, double bias_correction2_sqrt, unsigned* const* nonfinite,
+                                 float* const* ema, double ema_decay, const float* clip_record, void* stream) {
+  if (count < 0 || (count > 0 && !tensors) || !(bias_correction1 > 0.0) || !(bias_correction2_sqrt > 0.0) ||
+      !clip_record || (ema && !(ema_decay > 0.0 && ema_decay < 1.0)))
+    return VG_ERR_BAD_ARG;
+  return adam_launch<true>(tensors, nonfinite, count, beta1, beta2, eps, (float)(lr / bias_correction1),
+                           (float)bias_correction2_sqrt, nullptr, (hipStream_t)stream, ema, ema ? ema_decay : 0.5,
+                           clip_record);
+}
+
+extern "C" int vg_adam_step_dev_clip(const VgAdamTensor* tensors, int count, double beta1, double beta2, double eps,
+                                     const float* scalars, unsigned* const* nonfinite, float* const* ema,
+                                     double ema_decay, const float* clip_record, void* stream) {
+  if (count < 0 || (count > 0 && !tensors) || !scalars || !clip_record ||
+      (ema && !(ema_decay > 0.0 && ema_decay < 1.0)))
+    return VG_ERR_BAD_ARG;
+  return adam_launch<true>(tensors, nonfinite, count, beta1, beta2, eps, 0.f, 0.f, scalars, (hipStream_t)stream, ema,
+                           ema ? ema_decay : 0.5, clip_record);
 }

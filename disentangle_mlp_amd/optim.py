@@ -10,8 +10,16 @@ maximize, a closure, non-fp32 / non-contiguous / CPU tensors) take the inherited
 
 ``HipAdam(nonfinite_guard=True)``: the step also reports, per parameter, an inf / NaN among the gradients it read
 (`NONFINITE_GRAD`) and the parameters it wrote (`NONFINITE_PARAM`) -- ``vg_adam_step_checked`` -- in device words the
-host reads when it chooses to (`nonfinite`, `nonfinite_words`, `clear_nonfinite`).  It detects, it does not skip the
-update: when a word is up the weights are poisoned and the last good checkpoint is the way back.
+host reads when it chooses to (`nonfinite`, `nonfinite_words`, `clear_nonfinite`).  By itself it detects, it does not
+skip the update: when a PARAM bit is up the weights are poisoned and the last good checkpoint is the way back.
+``skip_nonfinite=True`` (below) is the opt-in that prevents the damage.
+
+``HipAdam(max_grad_norm=c, skip_nonfinite=bool)``: one deterministic pass over the gradients in front of the step
+(``vg_grad_sumsq_multi`` + ``vg_grad_clip_finalize``) leaves their global L2 norm, the coefficient ``min(1, c / (norm +
+1e-6))`` of ``torch.nn.utils.clip_grad_norm_`` and a skip decision in a four-word device record; the fused step
+(``vg_adam_step_clip``) scales every gradient by the coefficient in registers -- the gradients themselves are never
+written -- and, with ``skip_nonfinite``, stores nothing at all when the norm is inf / NaN.  No host synchronisation:
+the whole of it is capturable.  `grad_norm`, `clip_coef` (device views), `skipped_steps`, `reset_skipped`.
 
 ``HipAdam(ema_decay=d)``: the step also keeps an exponential moving average of the weights it writes, ``e <- e +
 (1 - d) (p - e)`` -- inside the same kernel (``vg_adam_step_ema``), from the value the thread has just formed, so the
@@ -49,6 +57,17 @@ def isfinite_bits(params, device=None):
     return torch.stack(bits)
 
 
+_CLIP_CHUNK = 8192      # elements per workgroup, and per fp64 partial, of vg_grad_sumsq_multi (csrc/adam.hip: ACHUNK)
+
+
+def _torch_total_norm(grads):
+    """The global L2 norm as ``torch.nn.utils.clip_grad_norm_`` forms it."""
+    fn = getattr(torch.nn.utils, "get_total_norm", None)
+    if fn is not None:
+        return fn(grads, 2.0)
+    return torch.linalg.vector_norm(torch.stack([torch.linalg.vector_norm(g, 2.0) for g in grads]), 2.0)
+
+
 class _AdamTensor(ctypes.Structure):
     _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p),
                 ("n", ctypes.c_size_t), ("amax", ctypes.c_void_p)]
@@ -63,9 +82,12 @@ class HipAdam(optim.Adam):
     host mirrors the device counter (`prepare_capture` / `replayed`)."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, capturable=False,
-                 nonfinite_guard=False, ema_decay=None, ema_targets=None):
+                 nonfinite_guard=False, ema_decay=None, ema_targets=None, max_grad_norm=None, skip_nonfinite=False):
         self._words = None
         self._ema = None
+        self._clip_rec = None
+        if max_grad_norm is not None and not (0.0 < float(max_grad_norm) < math.inf):      # (NaN fails both comparisons)
+            raise ValueError(f"HipAdam: max_grad_norm must be finite and > 0, got {max_grad_norm!r}")
         if ema_decay is not None and not (0.0 < float(ema_decay) < 1.0):      # (NaN fails both comparisons)
             raise ValueError(f"HipAdam: ema_decay must lie in (0, 1), got {ema_decay!r}")
         if ema_decay is None and ema_targets is not None:
@@ -113,6 +135,17 @@ class HipAdam(optim.Adam):
                         raise ValueError(f"HipAdam: ema_targets[{i}] is its parameter's own storage")
             self._ema_of = {p: i for i, p in enumerate(ps)}
             self._ema = ema
+        # clipping by global norm / skipping a non-finite step: the record [norm, coef, skip, skipped] and one fp64 slot
+        # per 8192-element chunk of every parameter, allocated here and never replaced -- like `_words`, a captured step
+        # writes where later readers read
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        if self.max_grad_norm is not None or self.skip_nonfinite:
+            ps = [p for g in self.param_groups for p in g["params"]]
+            self._clip_rec = torch.zeros(4, dtype=torch.float32, device=ps[0].device)
+            self._clip_rec[1] = 1.0
+            slots = sum((p.numel() + _CLIP_CHUNK - 1) // _CLIP_CHUNK for p in ps)
+            self._partials = torch.zeros(max(1, slots), dtype=torch.float64, device=ps[0].device)
 
     def add_param_group(self, param_group):
         if self._words is not None:
@@ -121,6 +154,9 @@ class HipAdam(optim.Adam):
         if self._ema is not None:
             raise RuntimeError("HipAdam(ema_decay=...): the EMA tensors are laid out at construction; "
                                "pass every parameter group to the constructor")
+        if self._clip_rec is not None:
+            raise RuntimeError("HipAdam(max_grad_norm=... / skip_nonfinite=True): the norm pass's partial sums are laid "
+                               "out at construction; pass every parameter group to the constructor")
         return super().add_param_group(param_group)
 
     # ---- weight EMA ------------------------------------------------------------------------------------------
@@ -155,6 +191,70 @@ class HipAdam(optim.Adam):
             raise ValueError("HipAdam.load_ema_state: one tensor per parameter, of the parameter's shape")
         for e, t in zip(self._ema, tensors):
             e.copy_(t)
+
+    # ---- clipping by global norm, skipping a non-finite step ---------------------------------------------------
+    def _need_clip(self):
+        if self._clip_rec is None:
+            raise RuntimeError("HipAdam: construct with max_grad_norm=... or skip_nonfinite=True")
+
+    def grad_norm(self):
+        """The global L2 norm of the gradients the last `step` read: a 0-dim fp32 VIEW of the device record (no host
+        synchronisation; the next step overwrites it)."""
+        self._need_clip()
+        return self._clip_rec[0]
+
+    def clip_coef(self):
+        """The coefficient the last `step` scaled its gradients by (1.0 exactly when nothing was clipped, 0.0 in a
+        skipped step): a 0-dim fp32 view of the device record, like `grad_norm`."""
+        self._need_clip()
+        return self._clip_rec[1]
+
+    def clip_record(self):
+        """The record itself, int32 view: words [norm bits, coef bits, skip, skipped] (a trainer reads several optimizers'
+        counts in one copy)."""
+        self._need_clip()
+        return self._clip_rec.view(torch.int32)
+
+    def skipped_steps(self):
+        """Steps skipped (``skip_nonfinite``) since construction or `reset_skipped`.  One device -> host read."""
+        return int(self.clip_record()[3])
+
+    def reset_skipped(self):
+        """`skipped_steps`, and the count back to zero."""
+        n = self.skipped_steps()
+        self.clip_record()[3] = 0
+        return n
+
+    @torch.no_grad()
+    def _torch_clip(self, stepped):
+        """The feature on torch's path.  Returns None when the step is skipped, else the list of gradients to step on
+        (scaled copies when the clip is active: the gradients themselves stay as they are, as on the kernel's path).  The
+        coefficient is ``clip_grad_norm_``'s own -- from torch's fp32 norm, by its fp32 expression, so the step is that
+        recipe bit for bit; the RECORDED norm, and the skip decision, come from an fp64 sum of squares as the kernel's do
+        (torch's fp32 norm of a tensor of 10^7 elements is good to about 10^-4 only).  One host read: this path is not
+        capturable anyway."""
+        grads = [p.grad for p in stepped]
+        rec, words = self._clip_rec, self._clip_rec.view(torch.int32)
+        if grads:
+            norm64 = torch.linalg.vector_norm(torch.stack(
+                [torch.linalg.vector_norm(g.detach().to_dense() if g.is_sparse else g.detach(), 2.0, dtype=torch.float64)
+                 .to(rec.device) for g in grads]), 2.0)
+        else:
+            norm64 = torch.zeros((), dtype=torch.float64, device=rec.device)
+        rec[0] = norm64.to(torch.float32)
+        if self.skip_nonfinite and not bool(torch.isfinite(norm64)):
+            rec[1] = 0.0
+            words[2] = 1
+            words[3] += 1
+            return None
+        words[2] = 0
+        if self.max_grad_norm is None or not grads:
+            rec[1] = 1.0
+            return grads
+        total = _torch_total_norm(grads)
+        coef = torch.clamp(self.max_grad_norm / (total + 1e-6), max=1.0)      # torch.nn.utils.clip_grads_with_norm_
+        rec[1] = coef.to(rec.device)
+        return [g * coef.to(g.device) for g in grads]
 
     # ---- non-finite guard ----------------------------------------------------------------------------------
     def _need_guard(self):
@@ -272,20 +372,62 @@ class HipAdam(optim.Adam):
             if gi in self._dev and len(steps) == 1:
                 self._dev[gi][0].fill_(steps.pop())          # the device counter a replayed step advances
 
+    def _init_state(self, p, group):
+        """torch.optim.Adam._init_group for one parameter without state."""
+        st = self.state[p]
+        if len(st) == 0:
+            st["step"] = torch.tensor(0.0, dtype=torch.float32)
+            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            if group.get("amsgrad", False):
+                st["max_exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+
     @torch.no_grad()
     def step(self, closure=None, update_ema=True):
         """``update_ema`` (with ``ema_decay`` set): False steps without touching the averages -- exactly the launches of
         an optimizer without EMA (a trainer that steps twice per iteration averages once).  A parameter the step skips
         (``grad is None``) keeps its EMA that step: the average follows the weights the optimizer writes, and a frozen
-        weight's average would only drift towards the value it already tracks."""
+        weight's average would only drift towards the value it already tracks.
+
+        ``max_grad_norm`` / ``skip_nonfinite``: ONE norm per call, over the gradients of every group this call steps
+        (``clip_grad_norm_`` over all parameters; ``grad is None`` does not count).  A skipped step leaves ``p``,
+        ``exp_avg``, ``exp_avg_sq`` and the EMA untouched but still ADVANCES the step count, the host's and the device
+        counter alike: a count that depends on the data would need a host read inside a captured iteration.  The bias
+        corrections of later steps therefore see one more step than updates were made."""
         ema_on = self._ema is not None and update_ema
+        clip_on = self._clip_rec is not None
         if closure is not None or not all(self._native_ok(g) for g in self.param_groups):
             if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("HipAdam: this configuration takes torch's step, which cannot be captured here")
             self._flush_replays()
             self._torch_stepped = True
+            if clip_on and closure is not None:      # the norm needs this call's gradients: the closure runs here
+                with torch.enable_grad():
+                    loss0 = closure()
+                closure = None
+            else:
+                loss0 = None
             stepped = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
-            loss = super().step(closure)
+            if clip_on:
+                use = self._torch_clip(stepped)
+                if use is None:                      # skipped: only the step counts move
+                    for group in self.param_groups:
+                        for p in group["params"]:
+                            if p.grad is not None:
+                                self._init_state(p, group)
+                                self.state[p]["step"] += 1
+                    return loss0
+                kept = [p.grad for p in stepped]
+                for p, g in zip(stepped, use):
+                    p.grad = g
+                try:
+                    super().step()
+                finally:
+                    for p, g in zip(stepped, kept):
+                        p.grad = g
+                loss = loss0
+            else:
+                loss = super().step(closure)
             if ema_on and stepped:      # never silently stale: the same average, formed by torch after its step
                 torch._foreach_lerp_([self._ema[self._ema_of[p]] for p in stepped], [p.detach() for p in stepped],
                                      1.0 - self.ema_decay)
@@ -301,6 +443,19 @@ class HipAdam(optim.Adam):
         if bounds is not None:
             bounds.zero_()
         words = self._words.data_ptr() if self.nonfinite_guard else None
+        rec = None
+        if clip_on:                                  # the grid-wide answer in front of the first store
+            grads = [p.grad for g in self.param_groups for p in g["params"] if p.grad is not None]
+            n = len(grads)
+            ptrs = (ctypes.c_void_p * max(1, n))(*[g.data_ptr() for g in grads])
+            lens = (ctypes.c_size_t * max(1, n))(*[g.numel() for g in grads])
+            slots = lib.vg_grad_sumsq_partials(lens, n)
+            check(lib.vg_grad_sumsq_multi(ptrs, lens, n, self._partials.data_ptr(), self._partials.numel(), stream),
+                  "vg_grad_sumsq_multi")
+            rec = self._clip_rec.data_ptr()
+            check(lib.vg_grad_clip_finalize(self._partials.data_ptr(), slots,
+                                            0.0 if self.max_grad_norm is None else self.max_grad_norm,
+                                            1 if self.skip_nonfinite else 0, rec, stream), "vg_grad_clip_finalize")
         for gi, group in enumerate(self.param_groups):
             beta1, beta2 = group["betas"]
             by_step = {}
@@ -308,10 +463,8 @@ class HipAdam(optim.Adam):
                 if p.grad is None:
                     continue
                 st = self.state[p]
-                if len(st) == 0:                                   # torch.optim.Adam._init_group
-                    st["step"] = torch.tensor(0.0, dtype=torch.float32)
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                if len(st) == 0:
+                    self._init_state(p, group)
                 if st["step"].is_cuda:                             # a checkpoint written by a fused / capturable Adam
                     st["step"] = st["step"].cpu()
                 st["step"] += 1
@@ -336,7 +489,11 @@ class HipAdam(optim.Adam):
                     # an eager step also stores its count in the device counter: replays may follow it
                     check(lib.vg_adam_prepare(float(step), step_dev.data_ptr(), 1 if capturing else 0, float(group["lr"]),
                                               float(beta1), float(beta2), scalars.data_ptr(), stream), "vg_adam_prepare")
-                    if ema is not None:
+                    if rec is not None:
+                        check(lib.vg_adam_step_dev_clip(arr, len(items), float(beta1), float(beta2), float(group["eps"]),
+                                                        scalars.data_ptr(), flags, ema, self.ema_decay or 0.0, rec, stream),
+                              "vg_adam_step_dev_clip")
+                    elif ema is not None:
                         check(lib.vg_adam_step_dev_ema(arr, len(items), float(beta1), float(beta2), float(group["eps"]),
                                                        scalars.data_ptr(), flags, ema, self.ema_decay, stream),
                               "vg_adam_step_dev_ema")
@@ -351,7 +508,11 @@ class HipAdam(optim.Adam):
                     continue
                 bc1 = 1.0 - beta1 ** step
                 bc2_sqrt = math.sqrt(1.0 - beta2 ** step)
-                if ema is not None:
+                if rec is not None:
+                    check(lib.vg_adam_step_clip(arr, len(items), float(group["lr"]), float(beta1), float(beta2),
+                                                float(group["eps"]), bc1, bc2_sqrt, flags, ema, self.ema_decay or 0.0, rec,
+                                                stream), "vg_adam_step_clip")
+                elif ema is not None:
                     check(lib.vg_adam_step_ema(arr, len(items), float(group["lr"]), float(beta1), float(beta2),
                                                float(group["eps"]), bc1, bc2_sqrt, flags, ema, self.ema_decay, stream),
                           "vg_adam_step_ema")

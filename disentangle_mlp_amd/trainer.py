@@ -254,14 +254,18 @@ def _backward(losses):
     torch.autograd.backward(losses, grad_tensors=[one] * len(losses))
 
 
-def _make_adam(params, lr, fused, capturable=False, nonfinite_guard=False):
+def _make_adam(params, lr, fused, capturable=False, nonfinite_guard=False, max_grad_norm=None, skip_nonfinite=False):
     """Adam with the reference's defaults (new_betavaegan.py:49-50).  On the GPU the step runs on the
     hand-written kernel (optim.HipAdam, a torch.optim.Adam subclass: identical state_dict); ``capturable``:
     its scalars are formed on the device so that a whole iteration can be captured in a HIP graph;
     ``nonfinite_guard``: the step flags non-finite gradients / parameters.  CPU construction uses torch's own
-    implementation."""
+    implementation -- unless ``max_grad_norm`` / ``skip_nonfinite`` (clipping by global norm, skipping a non-finite
+    step: optim.HipAdam) is asked for: then it is a HipAdam there too, whose inherited step carries those semantics."""
     if fused:
-        return HipAdam(params, lr=lr, capturable=capturable, nonfinite_guard=nonfinite_guard)
+        return HipAdam(params, lr=lr, capturable=capturable, nonfinite_guard=nonfinite_guard,
+                       max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+    if max_grad_norm is not None or skip_nonfinite:
+        return HipAdam(params, lr=lr, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
     return optim.Adam(params, lr=lr, capturable=capturable)
 
 
@@ -325,8 +329,8 @@ class NonFiniteError(RuntimeError):
     ``found``: list of ``(qualified parameter name such as "netD.convs.0.weight", "grad" | "param" | "grad+param")`` of
     this rank (empty when only another rank of a data-parallel run is poisoned); ``first_iteration`` /
     ``last_iteration``: the trainer's ``iteration`` when its flags were last known clean, and now -- the poison arrived
-    in an iteration of that range.  The weights are poisoned (the step detects, it does not skip): reload the last
-    checkpoint."""
+    in an iteration of that range.  The weights are poisoned (without ``skip_nonfinite=True`` the step detects, it does
+    not skip; with it, a forward pass or a parameter went non-finite by another way): reload the last checkpoint."""
 
     def __init__(self, found, first_iteration, last_iteration):
         self.found, self.first_iteration, self.last_iteration = list(found), first_iteration, last_iteration
@@ -368,6 +372,11 @@ class _CapturedIteration:
                       for o in optimizers]
         for o in optimizers:
             o.prepare_capture()
+        # Buffers that exist now AND those that exist afterwards: a workspace regrown in the middle of the capture is
+        # already referenced by the nodes captured before that.  When it came from the pool of an earlier, since destroyed
+        # graph (all captures share one stream, hence one workspace), dropping it here hands its memory back for good --
+        # the next capture's empty_cache() unmaps it under this graph's replays.
+        before = ops.buffers_in_use()
         try:
             with ops.amax_capture_scope(), torch.cuda.graph(self.graph):
                 self.out = run(self.inputs, self.labels[0:1], self.labels[1:2])
@@ -381,7 +390,7 @@ class _CapturedIteration:
                 o._captured = []
             raise
         # the graph holds raw pointers into the weights' pack buffers and ops' scratch buffers: they live as long as it does
-        self._buffers = ops.buffers_in_use()
+        self._buffers = before + ops.buffers_in_use()
         self.nbt_delta = [m._nbt_pending - n for m, n in zip(bn_modules, before_nbt)]
         self.flat_delta = [(f.bytes_reduced - b0, f.collectives - c0) for f, (b0, c0) in zip(self.flats, before_flat)]
         self.fresh = True          # the capture pass already did the host-side bookkeeping of the first replay
@@ -470,6 +479,8 @@ class _GraphedSteps:
 
     # ---- non-finite guard ----------------------------------------------------------------------------------------
     nonfinite_guard = False
+    max_grad_norm, skip_nonfinite = None, False      # clipping by global norm / skipping a non-finite step (optim.HipAdam)
+    _skipped = {}
     _finite_at = 0          # `iteration` when the flags were last known clean
 
     @staticmethod
@@ -488,15 +499,24 @@ class _GraphedSteps:
         """The guard's check and, in the SAME device -> host copy, the values of the float64 device tensor ``extra``
         (an epoch's loss sums: `train_epoch` still reads the device once).  Raises `NonFiniteError`, else returns the
         values of ``extra`` as a list."""
-        names, bits = [], []
+        names, bits, skipping = [], [], []
         for attr, net, opt in self._guarded_optimizers():
             named = {p: f"{attr}.{k}" for k, p in net.named_parameters()}
             ps = [p for g in opt.param_groups for p in g["params"]]
             names += [named.get(p, f"{attr}.<parameter {i}>") for i, p in enumerate(ps)]
             if isinstance(opt, HipAdam) and opt.nonfinite_guard:
-                bits.append(opt.nonfinite_bits())
+                b = opt.nonfinite_bits()
             else:
-                bits.append(isfinite_bits(ps, self.device))
+                b = isfinite_bits(ps, self.device)
+            if isinstance(opt, HipAdam) and opt.skip_nonfinite:
+                # a word with only GRAD up is a step that was SKIPPED: the weights are clean.  Those bits are dropped here
+                # and cleared in the optimizer's words (device ops, no synchronisation); the count travels in the copy below
+                skipping.append((attr, opt))
+                b = torch.where(b == NONFINITE_GRAD, torch.zeros_like(b), b)
+                if opt.nonfinite_guard:
+                    w = opt.nonfinite_words()
+                    w.copy_(torch.where(w == NONFINITE_GRAD, torch.zeros_like(w), w))
+            bits.append(b)
         bits = torch.cat(bits) & (NONFINITE_GRAD | NONFINITE_PARAM)      # (the words are the optimizer's: other bits are not ours)
         anything = (bits != 0).any().to(torch.int32).reshape(1)
         if _dist_world() > 1:
@@ -505,7 +525,11 @@ class _GraphedSteps:
         parts = [bits.to(torch.float64), anything.to(torch.float64)]      # (small integers: exact in float64)
         if n_extra:
             parts.append(extra.reshape(-1).to(torch.float64))
+        parts += [opt.clip_record()[3:4].to(device=bits.device, dtype=torch.float64) for _, opt in skipping]
         host = torch.cat(parts).tolist()                                  # the one device -> host read
+        if skipping:
+            self._skipped = {attr: int(c) for (attr, _), c in zip(skipping, host[-len(skipping):])}
+            host = host[:-len(skipping)]
         bits, anything, extra = [int(b) for b in host[:len(names)]], host[len(names)], host[len(names) + 1:]
         if not anything:
             self._finite_at = self.iteration
@@ -517,12 +541,22 @@ class _GraphedSteps:
         """Raise `NonFiniteError` if an optimizer step since the flags were last cleared read a non-finite gradient or
         wrote a non-finite parameter; return None when the run is clean.  One device -> host copy for all optimizers'
         flag words -- `step` itself never synchronises; this is the check on demand after any `step`, and `train_epoch`
-        makes it once per epoch, in the copy that reads the epoch's sums.  Optimizers without the kernel's guard
+        makes it once per epoch, in the copy that reads the epoch's sums.  With ``skip_nonfinite=True`` a word with only
+        the GRAD bit up is a step that was skipped -- the weights are clean: it does not raise, the bit is cleared, and
+        `skipped_steps` counts it; a PARAM bit raises as ever.  Optimizers without the kernel's guard
         (torch.optim.Adam: CPU, ``fused_adam=False``; ``nonfinite_guard=False``) are checked with ``torch.isfinite`` over
         their parameters and gradients as they are now.  Data parallel: the "anything set" bit is all-reduced (MAX)
         first, so every rank raises at the same call."""
         self._read_finite()
         return None
+
+    def skipped_steps(self):
+        """``{network attribute: optimizer steps skipped so far}`` of the optimizers built with ``skip_nonfinite=True``
+        (empty without): `check_finite`, whose one device -> host copy carries the counts -- so this raises
+        `NonFiniteError` where that does."""
+        self._skipped = {}
+        self._read_finite()
+        return dict(self._skipped)
 
     def clear_nonfinite(self):
         """Zero the guard's flag words (device memsets, no synchronisation): after the state was restored."""
@@ -537,6 +571,7 @@ class _GraphedSteps:
         from . import model as M
         return (M.FUSE_CONV_BN, M.FUSE_HEAD_BCE, F.DEFER_WGRAD, ops.THIN_SPLIT, ops.USE_PACKED_FILTERS,
                 self.nonfinite_guard,        # (checked or unchecked Adam launches)
+                self.max_grad_norm, self.skip_nonfinite,      # (the norm pass and the clip step, or neither)
                 tuple(net.training for net in self._nets()),
                 tuple(p.requires_grad for net in self._nets() for p in net.parameters()))
 
@@ -588,15 +623,22 @@ class BetaVAEGANTrainer(_GraphedSteps):
 
     ``nonfinite_guard`` (default: on whenever the optimizers are HipAdam, VG_NONFINITE_GUARD=0 turns that off): the Adam
     steps flag non-finite gradients / parameters; `check_finite` -- called by `train_epoch` at the end of every epoch,
-    and by whoever wants to know after any `step` -- raises `NonFiniteError`."""
+    and by whoever wants to know after any `step` -- raises `NonFiniteError`.
+
+    ``max_grad_norm`` / ``skip_nonfinite`` (default: off -- then every launch is what it was): every optimizer step clips
+    its gradients by their global L2 norm, and / or skips itself when that norm is inf / NaN (optim.HipAdam: one norm pass
+    in front of the fused step, nothing on the host, captured with the iteration).  `skipped_steps` counts the skips.  What
+    a skip does NOT undo: a forward pass that was non-finite already has written its BatchNorm running statistics."""
 
     def __init__(self, device="cuda", seed=999, beta=25.0, lr=1e-3, opt: Optional[ModelOpt] = None,
                  data_parallel: Optional[bool] = None, fused_adam: bool = True, capturable: Optional[bool] = None,
-                 graph: Optional[bool] = None, nonfinite_guard: Optional[bool] = None):
+                 graph: Optional[bool] = None, nonfinite_guard: Optional[bool] = None,
+                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
         self.opt = opt or ModelOpt()
         self.device = torch.device(device)
         _use_tuned_gemms(self.device)
         self.beta = float(beta)
+        self.max_grad_norm, self.skip_nonfinite = max_grad_norm, bool(skip_nonfinite)
         self.world = _dist_world()
         self.dp = (self.world > 1) if data_parallel is None else data_parallel
         self._graph_init(graph, self.device.type == "cuda", fused_adam, self.dp)
@@ -611,8 +653,9 @@ class BetaVAEGANTrainer(_GraphedSteps):
         self.netD = net_d.to(self.device)
         fused = fused_adam and self.device.type == "cuda"
         self.nonfinite_guard = self._resolve_guard(nonfinite_guard, fused)
-        self.optimizerEG = _make_adam(self.netEG.parameters(), lr, fused, capturable, self.nonfinite_guard)   # :49 (hard-coded 1e-3 there)
-        self.optimizerD = _make_adam(self.netD.parameters(), lr, fused, capturable, self.nonfinite_guard)     # :50
+        clip = dict(max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+        self.optimizerEG = _make_adam(self.netEG.parameters(), lr, fused, capturable, self.nonfinite_guard, **clip)   # :49 (hard-coded 1e-3 there)
+        self.optimizerD = _make_adam(self.netD.parameters(), lr, fused, capturable, self.nonfinite_guard, **clip)     # :50
         self.flat_eg = FlatGrads(self.netEG.parameters(), silent=shadowed_bias_params(self.netEG)) if self.dp else None
         self.flat_d = FlatGrads(self.netD.parameters(), silent=shadowed_bias_params(self.netD)) if self.dp else None
         self.netEG.train()
@@ -970,15 +1013,18 @@ class BetaVAEGANTrainer(_GraphedSteps):
 
 
 class VAETrainer(_GraphedSteps):
-    """new_vae.py:33-37 construction, :39-48 loss, :53-59 step.  ``graph``: as BetaVAEGANTrainer."""
+    """new_vae.py:33-37 construction, :39-48 loss, :53-59 step.  ``graph``, ``max_grad_norm``, ``skip_nonfinite``: as
+    BetaVAEGANTrainer."""
 
     def __init__(self, device="cuda", seed=999, beta=1.0, lr=3e-3, opt: Optional[ModelOpt] = None,
                  fused_adam: bool = True, capturable: Optional[bool] = None, graph: Optional[bool] = None,
-                 nonfinite_guard: Optional[bool] = None):
+                 nonfinite_guard: Optional[bool] = None, max_grad_norm: Optional[float] = None,
+                 skip_nonfinite: bool = False):
         self.opt = opt or ModelOpt()
         self.device = torch.device(device)
         _use_tuned_gemms(self.device)
         self.beta = float(beta)
+        self.max_grad_norm, self.skip_nonfinite = max_grad_norm, bool(skip_nonfinite)
         torch.manual_seed(seed)
         m = VAE(self.opt)
         m.apply(weights_init)
@@ -988,7 +1034,7 @@ class VAETrainer(_GraphedSteps):
         fused = fused_adam and self.device.type == "cuda"
         self.nonfinite_guard = self._resolve_guard(nonfinite_guard, fused)
         self.optimizer = _make_adam(self.model.parameters(), lr, fused, self.graph if capturable is None else capturable,
-                                    self.nonfinite_guard)
+                                    self.nonfinite_guard, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
         self.flat = FlatGrads(self.model.parameters(), silent=shadowed_bias_params(self.model)) if self.world > 1 else None
         self.latent_generator = _latent_generator(self.device, seed, _dist_rank())
         self.model.train()
@@ -1056,14 +1102,16 @@ class GANTrainer(_GraphedSteps):
     """new_gan.py:47-61 construction, :66-141 step.  Data parallel like the beta-VAE-GAN driver (the
     reference wraps both nets in nn.DataParallel, new_gan.py:51-53): replica-local BatchNorm, one
     gradient exchange (SUM) per optimizer step, BCE divided by the global batch.  ``graph``: as
-    BetaVAEGANTrainer."""
+    BetaVAEGANTrainer; so are ``max_grad_norm`` and ``skip_nonfinite``."""
 
     def __init__(self, device="cuda", seed=999, lr=3e-3, opt: Optional[ModelOpt] = None, fused_adam: bool = True,
                  data_parallel: Optional[bool] = None, graph: Optional[bool] = None,
-                 nonfinite_guard: Optional[bool] = None):
+                 nonfinite_guard: Optional[bool] = None, max_grad_norm: Optional[float] = None,
+                 skip_nonfinite: bool = False):
         self.opt = opt or ModelOpt()
         self.device = torch.device(device)
         _use_tuned_gemms(self.device)
+        self.max_grad_norm, self.skip_nonfinite = max_grad_norm, bool(skip_nonfinite)
         torch.manual_seed(seed)
         g = Generator_celeba(self.opt)
         d = Discriminator_celeba(self.opt)
@@ -1075,8 +1123,9 @@ class GANTrainer(_GraphedSteps):
         self.dp = (self.world > 1) if data_parallel is None else data_parallel
         self._graph_init(graph, self.device.type == "cuda", fused_adam, self.dp)
         self.nonfinite_guard = self._resolve_guard(nonfinite_guard, fused)
-        self.optimizerG = _make_adam(self.netG.parameters(), lr, fused, self.graph, self.nonfinite_guard)
-        self.optimizerD = _make_adam(self.netD.parameters(), lr, fused, self.graph, self.nonfinite_guard)
+        clip = dict(max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+        self.optimizerG = _make_adam(self.netG.parameters(), lr, fused, self.graph, self.nonfinite_guard, **clip)
+        self.optimizerD = _make_adam(self.netD.parameters(), lr, fused, self.graph, self.nonfinite_guard, **clip)
         self.flat_g = FlatGrads(self.netG.parameters(), silent=shadowed_bias_params(self.netG)) if self.dp else None
         self.flat_d = FlatGrads(self.netD.parameters(), silent=shadowed_bias_params(self.netD)) if self.dp else None
         self.latent_generator = _latent_generator(self.device, seed, _dist_rank())

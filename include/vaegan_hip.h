@@ -46,7 +46,8 @@ extern "C" {
  * still exports every old symbol).  3: round 3.  4: round 4 (fp16 planes: VG_PLANES_F16, the *_amax arguments).
  * 6: vg_conv_general_* (the general forward convolution).  7: vg_adam_step_checked / vg_adam_step_dev_checked.
  * Entry points that are only ADDED (the four of csrc/fid_front.hip; vg_bn_eval_coeffs, vg_bn_eval_act_bwd;
- * vg_adam_step_ema, vg_adam_step_dev_ema) change
+ * vg_adam_step_ema, vg_adam_step_dev_ema; vg_grad_sumsq_partials, vg_grad_sumsq_multi, vg_grad_clip_finalize,
+ * vg_adam_step_clip, vg_adam_step_dev_clip) change
  * nothing an existing caller sees and keep the version: a binding that needs them and finds a library without them
  * fails at the symbol lookup, as loudly. */
 #define VG_ABI_VERSION 7
@@ -480,9 +481,9 @@ int vg_adam_step_dev(const VgAdamTensor* tensors, int count, double beta1, doubl
  *   VG_NONFINITE_PARAM  an inf / NaN among the parameter elements it WROTE,
  * and only ever ORs: a word stays up until the caller zeroes it, a clean step writes nothing (one atomicOr per
  * workgroup that saw something).  Tensors with n == 0 are skipped, their word untouched.  p, m, v and amax are
- * bit for bit those of the unchecked step, which is this one without words: the update is DETECTED, not skipped
- * (that would take a grid-wide answer before the first store) -- once a bit is up the weights are poisoned and the
- * last good checkpoint is the way back. */
+ * bit for bit those of the unchecked step, which is this one without words: these entry points DETECT, they do not
+ * skip (that takes a grid-wide answer before the first store: the opt-in norm pass in front of vg_adam_step_clip
+ * below) -- once a bit is up the weights are poisoned and the last good checkpoint is the way back. */
 #define VG_NONFINITE_GRAD 1u
 #define VG_NONFINITE_PARAM 2u
 int vg_adam_step_checked(const VgAdamTensor* tensors, int count, double lr, double beta1, double beta2, double eps,
@@ -505,6 +506,46 @@ int vg_adam_step_ema(const VgAdamTensor* tensors, int count, double lr, double b
 int vg_adam_step_dev_ema(const VgAdamTensor* tensors, int count, double beta1, double beta2, double eps,
                          const float* scalars, unsigned* const* nonfinite, float* const* ema, double ema_decay,
                          void* stream);
+/* Clipping by global norm and skipping a non-finite step: one pass over the gradients in front of the step, all
+ * answers in DEVICE memory (nothing here synchronises; the three calls can be captured in a HIP graph).
+ *
+ * vg_grad_sumsq_multi: `grads` / `n` are HOST arrays of `count` DEVICE pointers (fp32) and lengths; any count, 24
+ * tensors per launch, tensors with n == 0 skipped.  Every workgroup writes the sum of squares of its 8192 elements,
+ * formed in double from the first product on (exact squares, no overflow for any finite fp32), into a slot of its own:
+ * partials[0 .. vg_grad_sumsq_partials(n, count)) in tensor order -- no atomics, the same bits run to run.
+ * vg_grad_sumsq_partials (host only) is that number of slots, sum of ceil(n[i] / 8192); `capacity` is the number of
+ * doubles `partials` holds.  An inf / NaN among the gradients makes its slot, and so the total, inf / NaN.
+ *
+ * vg_grad_clip_finalize (one workgroup) adds the partials in a fixed order in double and writes the caller-owned
+ * record, four 32-bit words:
+ *   record[0]  norm     float   (float)sqrt(sum)
+ *   record[1]  coef     float   max_norm > 0: (float)min(1, max_norm / (norm + 1e-6)) in double -- torch's
+ *                               clip_grad_norm_ formula (a NaN norm gives NaN, an inf norm 0: torch's behaviour);
+ *                               max_norm <= 0: no clipping, 1.  With `skip` up: 0.
+ *   record[2]  skip     uint32  1 when the norm is inf / NaN and skip_nonfinite != 0, else 0
+ *   record[3]  skipped  uint32  += skip: a running count the caller zeroes and the kernel only increments
+ *
+ * vg_adam_step_clip / vg_adam_step_dev_clip: vg_adam_step_ema / vg_adam_step_dev_ema reading that record.  Every
+ * gradient element is used as gs = coef * g (one fp32 rounding, that of g.mul_(coef)); p, m, v, amax, the flag words
+ * and the averages are bit for bit those of the step above on such a gradient (the GRAD bit is judged on gs).  `ema`
+ * may be NULL here (no average at all; ema_decay is then ignored), and single entries as above.  With `skip` up the
+ * step stores nothing to p, m, v or an average: it adds max |p| of the unchanged weights to amax (the caller zeroed the
+ * word) and ORs VG_NONFINITE_GRAD into the word of each tensor whose gradient holds an inf / NaN (VG_NONFINITE_PARAM
+ * only if p was non-finite already).  The gradients themselves are never written.
+ *
+ * VG_ERR_BAD_ARG before any launch: partials or record NULL, capacity too small, a NaN max_norm, an ema_decay outside
+ * (0, 1) when ema is given. */
+size_t vg_grad_sumsq_partials(const size_t* n, int count);
+int vg_grad_sumsq_multi(const float* const* grads, const size_t* n, int count, double* partials, size_t capacity,
+                        void* stream);
+int vg_grad_clip_finalize(const double* partials, size_t n_partials, double max_norm, int skip_nonfinite, float* record,
+                          void* stream);
+int vg_adam_step_clip(const VgAdamTensor* tensors, int count, double lr, double beta1, double beta2, double eps,
+                      double bias_correction1, double bias_correction2_sqrt, unsigned* const* nonfinite,
+                      float* const* ema, double ema_decay, const float* clip_record, void* stream);
+int vg_adam_step_dev_clip(const VgAdamTensor* tensors, int count, double beta1, double beta2, double eps,
+                          const float* scalars, unsigned* const* nonfinite, float* const* ema, double ema_decay,
+                          const float* clip_record, void* stream);
 
 /* ---- image I/O either side of the step -----------------
  * Input pipeline of dataloader/dataset.py:37-43 (ToTensor + Normalize(mean, std) of a

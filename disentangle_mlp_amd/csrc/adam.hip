@@ -35,6 +35,14 @@
 // p, m, v or the EMA; it still emits max |p| (the bounds words were zeroed in front of the step) and flags the tensor
 // that holds the inf / NaN.  It is a kernel and a pack of its own: the kernels of the entry points above are what
 // they were.
+//
+// Weight decay and hyper-parameters on the device (vg_adam_prepare_dev, vg_adam_step_decay / vg_adam_step_dev_decay):
+// the learning rate and the weight decay of a captured step live in a device pair [lr, weight_decay] the prepare kernel
+// reads, so a schedule changes them between replays.  The decay step is the clip step with one more register operation
+// per element in front of the update -- coupled (L2): gd = gs + (wd * p), a rounded product and a rounded sum;
+// decoupled (AdamW): pd = p * s2 with s2 = (float)(1 - lr * wd) formed in double -- and no memory traffic of its own.
+// With wd == 0 neither term is formed (no 0 * inf) and the bits are the clip step's.  Again a kernel and a pack of its
+// own.
 #include "common.hpp"
 #include "vaegan_hip.h"
 
@@ -103,6 +111,32 @@ __global__ void adam_prepare_kernel(double step_host, double* __restrict__ step_
   const double bc2 = 1.0 - pow(beta2, step);
   scalars[0] = (float)(lr / bc1);       // step_size
   scalars[1] = (float)sqrt(bc2);        // bias_correction2_sqrt
+}
+
+// s2 of the decoupled decay: 1 - lr * wd in double, a rounded product and a rounded difference (what Python's
+// ``1 - lr * wd`` gives; contracted to one fma the host's and the device's value could differ in the last bit).
+__host__ __device__ __forceinline__ float decoupled_factor(double lr, double wd) {
+#pragma clang fp contract(off)
+  const double prod = lr * wd;
+  return (float)(1.0 - prod);
+}
+
+// adam_prepare_kernel with lr and the weight decay read from DEVICE memory (hyper = [lr, weight_decay]): a schedule
+// changes them between the replays of a captured step.  scalars[0..1] by the expressions above (same lr, same bits);
+// scalars[2] the decoupled factor (1 when there is nothing to decay), scalars[3] the coupled coefficient (0 likewise).
+__global__ void adam_prepare_dev_kernel(double step_host, double* __restrict__ step_dev, int advance,
+                                        const double* __restrict__ hyper, int decoupled, double beta1, double beta2,
+                                        float* __restrict__ scalars) {
+  double step = step_host;
+  if (advance) step = step_dev[0] + 1.0;
+  if (step_dev) step_dev[0] = step;
+  const double lr = hyper[0], wd = hyper[1];
+  const double bc1 = 1.0 - pow(beta1, step);
+  const double bc2 = 1.0 - pow(beta2, step);
+  scalars[0] = (float)(lr / bc1);       // step_size
+  scalars[1] = (float)sqrt(bc2);        // bias_correction2_sqrt
+  scalars[2] = (decoupled && wd != 0.0) ? decoupled_factor(lr, wd) : 1.f;
+  scalars[3] = decoupled ? 0.f : (float)wd;
 }
 
 constexpr unsigned NONFINITE_BITS = 0x7f800000u;      // abs_bits(x) >= this: x is inf or NaN
@@ -396,6 +430,130 @@ __global__ __launch_bounds__(ANT) void adam_clip_multi_kernel(AdamPackEma A, flo
                   A.flag[t]);
 }
 
+// ---- weight decay inside the step -------------------------------------------------------------------------------------
+// The pack of the decay variant: s2 / wdc are what vg_adam_prepare_dev leaves in scalars[2..3], formed on the host.
+struct AdamPackDecay : AdamPackEma {
+  float s2;       // decoupled: p is multiplied by this before the update; 1: not
+  float wdc;      // coupled: this times p is added to the gradient; 0: not
+};
+
+// wd * p and gs + (wd * p): a rounded product and a rounded sum (torch: p.mul(wd), then g.add_), never one fma.
+__device__ __forceinline__ float decay_grad(float gs, float wdc, float p) {
+#pragma clang fp contract(off)
+  const float wp = wdc * p;
+  return gs + wp;
+}
+
+// p * s2, one rounding (torch: p.mul_(1 - lr * wd)): kept from being fused into the update that follows.
+__device__ __forceinline__ float decay_param(float p, float s2) {
+#pragma clang fp contract(off)
+  return p * s2;
+}
+
+// adam_clip_multi_kernel with the weights decayed in registers in front of the update.  `record` may be NULL here (no
+// clipping, nothing skipped: gs = g).  l2 / dec are uniform over the grid; with neither, every element takes the clip
+// step's operations and nothing else.  The GRAD bit is judged on gs -- the gradient the caller handed in, scaled -- not
+// on gd, which an inf WEIGHT would poison as well; amax and the PARAM bit on the final p.
+template <bool DEV>
+__global__ __launch_bounds__(ANT) void adam_decay_multi_kernel(AdamPackDecay A, float omb1, float b2, float omb2,
+                                                              float step_size, float bc2s, float eps,
+                                                              const float* __restrict__ scalars,
+                                                              const float* __restrict__ record) {
+  float s2 = A.s2, wdc = A.wdc;
+  if constexpr (DEV) {
+    step_size = scalars[0];
+    bc2s = scalars[1];
+    s2 = scalars[2];
+    wdc = scalars[3];
+  }
+  const bool dec = s2 != 1.f, l2 = wdc != 0.f;
+  const bool scale = record != nullptr;
+  const float coef = scale ? record[REC_COEF] : 1.f;
+  const bool skip = scale && reinterpret_cast<const unsigned*>(record)[REC_SKIP] != 0u;      // (uniform over the grid)
+  int t = 0;
+  while (t + 1 < A.count && blockIdx.x >= A.first_block[t + 1]) ++t;
+  const unsigned long long n = A.n[t];
+  const unsigned long long base = (unsigned long long)(blockIdx.x - A.first_block[t]) * ACHUNK;
+  const unsigned long long end = min(base + (unsigned long long)ACHUNK, n);
+  float* __restrict__ p = A.p[t];
+  const float* __restrict__ g = A.g[t];
+  float* __restrict__ m = A.m[t];
+  float* __restrict__ v = A.v[t];
+  float* __restrict__ e = A.e[t];
+  const float omd = A.omd;
+  const bool vec_step = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
+  const bool vec = vec_step && (((uintptr_t)e & 15) == 0);
+  const unsigned long long end4 = base + ((end - base) & ~3ULL);
+  unsigned am = 0, gm = 0;
+  // one element: (p, g as read) -> the new p; m and v in place
+  auto one = [&](bool body, float& pj, float gj, float& mj, float& vj) {
+    const float gs = scale ? clip_scale(coef, gj) : gj;
+    gm = max(gm, abs_bits(gs));
+    const float gd = l2 ? decay_grad(gs, wdc, pj) : gs;
+    if (dec) pj = decay_param(pj, s2);
+    adam_one_as(body, pj, gd, mj, vj, omb1, b2, omb2, step_size, bc2s, eps);
+    am = max(am, abs_bits(pj));
+  };
+  if (skip) {
+    unsigned long long tail = base;
+    if (vec_step) {
+      for (unsigned long long i = base + 4ULL * threadIdx.x; i < end4; i += 4ULL * ANT) {
+        const f32x4 pv = *reinterpret_cast<const f32x4*>(p + i);
+        const f32x4 gv = *reinterpret_cast<const f32x4*>(g + i);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          am = max(am, abs_bits(pv[j]));
+          gm = max(gm, abs_bits(gv[j]));
+        }
+      }
+      tail = end4;
+    }
+    for (unsigned long long i = tail + threadIdx.x; i < end; i += ANT) {
+      am = max(am, abs_bits(p[i]));
+      gm = max(gm, abs_bits(g[i]));
+    }
+  } else if (vec) {
+    for (unsigned long long i = base + 4ULL * threadIdx.x; i < end4; i += 4ULL * ANT) {
+      f32x4 pv = *reinterpret_cast<f32x4*>(p + i), mv = *reinterpret_cast<f32x4*>(m + i);
+      f32x4 vv = *reinterpret_cast<f32x4*>(v + i);
+      const f32x4 gv = *reinterpret_cast<const f32x4*>(g + i);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float pj = pv[j], mj = mv[j], vj = vv[j];
+        one(true, pj, gv[j], mj, vj);
+        pv[j] = pj; mv[j] = mj; vv[j] = vj;
+      }
+      *reinterpret_cast<f32x4*>(p + i) = pv;
+      *reinterpret_cast<f32x4*>(m + i) = mv;
+      *reinterpret_cast<f32x4*>(v + i) = vv;
+      if (e) {
+        f32x4 ev = *reinterpret_cast<f32x4*>(e + i);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ev[j] = ema_one(ev[j], pv[j], omd);
+        *reinterpret_cast<f32x4*>(e + i) = ev;
+      }
+    }
+    for (unsigned long long i = end4 + threadIdx.x; i < end; i += ANT) {
+      float pi = p[i];
+      one(false, pi, g[i], m[i], v[i]);
+      p[i] = pi;
+      if (e) e[i] = ema_one(e[i], pi, omd);
+    }
+  } else {
+    for (unsigned long long i = base + threadIdx.x; i < end; i += ANT) {
+      float pi = p[i];
+      one(vec_step && i < end4, pi, g[i], m[i], v[i]);
+      p[i] = pi;
+      if (e) e[i] = ema_one(e[i], pi, omd);
+    }
+  }
+  if (A.amax[t]) block_amax_atomic<ANT>(am, A.amax[t]);
+  if (A.flag[t])
+    block_flag_or((gm >= NONFINITE_BITS ? (unsigned)VG_NONFINITE_GRAD : 0u) |
+                      (am >= NONFINITE_BITS ? (unsigned)VG_NONFINITE_PARAM : 0u),
+                  A.flag[t]);
+}
+
 }  // namespace
 
 namespace {
@@ -578,4 +736,83 @@ extern "C" int vg_adam_step_dev_clip(const VgAdamTensor* tensors, int count, dou
     return VG_ERR_BAD_ARG;
   return adam_launch<true>(tensors, nonfinite, count, beta1, beta2, eps, 0.f, 0.f, scalars, (hipStream_t)stream, ema,
                            ema ? ema_decay : 0.5, clip_record);
+}
+
+// ---- weight decay inside the step, hyper-parameters on the device: the entry points -----------------------------------
+namespace {
+int adam_decay_launch(const VgAdamTensor* tensors, unsigned* const* flags, int count, double beta1, double beta2,
+                      double eps, float step_size, float bc2s, float s2, float wdc, const float* scalars, hipStream_t st,
+                      float* const* ema, double ema_decay, const float* clip_record) {
+  const float omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);
+  int i = 0;
+  while (i < count) {
+    AdamPackDecay A;
+    A.omd = (float)(1.0 - ema_decay);
+    A.s2 = s2;
+    A.wdc = wdc;
+    A.count = 0;
+    unsigned blocks = 0;
+    while (i < count && A.count < AMAX) {
+      unsigned* const flag = flags ? flags[i] : nullptr;
+      float* const ema_i = ema ? ema[i] : nullptr;
+      const VgAdamTensor& T = tensors[i++];
+      if (T.n == 0) continue;      // (its flag word is left untouched)
+      if (!T.p || !T.g || !T.m || !T.v) return VG_ERR_BAD_ARG;
+      const unsigned long long nb = (T.n + ACHUNK - 1) / ACHUNK;
+      if (nb > 0x3fffffffULL - blocks) return VG_ERR_BAD_ARG;
+      const int k = A.count++;
+      A.p[k] = T.p; A.g[k] = T.g; A.m[k] = T.m; A.v[k] = T.v; A.n[k] = T.n;
+      A.amax[k] = reinterpret_cast<unsigned*>(T.amax);
+      A.flag[k] = flag;
+      A.e[k] = ema_i;
+      A.first_block[k] = blocks;
+      blocks += (unsigned)nb;
+    }
+    if (A.count == 0) break;
+    A.first_block[A.count] = blocks;
+    if (scalars)
+      hipLaunchKernelGGL((adam_decay_multi_kernel<true>), dim3(blocks), dim3(ANT), 0, st, A, omb1, (float)beta2, omb2, 0.f,
+                         0.f, (float)eps, scalars, clip_record);
+    else
+      hipLaunchKernelGGL((adam_decay_multi_kernel<false>), dim3(blocks), dim3(ANT), 0, st, A, omb1, (float)beta2, omb2,
+                         step_size, bc2s, (float)eps, (const float*)nullptr, clip_record);
+    VG_CHECK_LAUNCH();
+  }
+  return 0;
+}
+}  // namespace
+
+extern "C" int vg_adam_prepare_dev(double step, double* step_dev, int advance_device_counter, const double* hyper,
+                                   int decoupled, double beta1, double beta2, float* scalars, void* stream) {
+  if (!hyper || !scalars || (advance_device_counter ? !step_dev : !(step >= 1.0)) || !(beta1 >= 0.0 && beta1 < 1.0) ||
+      !(beta2 >= 0.0 && beta2 < 1.0))
+    return VG_ERR_BAD_ARG;
+  hipLaunchKernelGGL(adam_prepare_dev_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step, step_dev,
+                     advance_device_counter ? 1 : 0, hyper, decoupled ? 1 : 0, beta1, beta2, scalars);
+  VG_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int vg_adam_step_decay(const VgAdamTensor* tensors, int count, double lr, double beta1, double beta2,
+                                  double eps, double bias_correction1, double bias_correction2_sqrt,
+                                  unsigned* const* nonfinite, float* const* ema, double ema_decay,
+                                  const float* clip_record, double weight_decay, int decoupled, void* stream) {
+  if (count < 0 || (count > 0 && !tensors) || !(bias_correction1 > 0.0) || !(bias_correction2_sqrt > 0.0) ||
+      (ema && !(ema_decay > 0.0 && ema_decay < 1.0)) || !(weight_decay >= 0.0))      // (a NaN fails the comparison)
+    return VG_ERR_BAD_ARG;
+  // the two words vg_adam_prepare_dev would leave in scalars[2..3]
+  const float s2 = (decoupled && weight_decay != 0.0) ? decoupled_factor(lr, weight_decay) : 1.f;
+  const float wdc = decoupled ? 0.f : (float)weight_decay;
+  return adam_decay_launch(tensors, nonfinite, count, beta1, beta2, eps, (float)(lr / bias_correction1),
+                           (float)bias_correction2_sqrt, s2, wdc, nullptr, (hipStream_t)stream, ema,
+                           ema ? ema_decay : 0.5, clip_record);
+}
+
+extern "C" int vg_adam_step_dev_decay(const VgAdamTensor* tensors, int count, double beta1, double beta2, double eps,
+                                      const float* scalars, unsigned* const* nonfinite, float* const* ema,
+                                      double ema_decay, const float* clip_record, void* stream) {
+  if (count < 0 || (count > 0 && !tensors) || !scalars || (ema && !(ema_decay > 0.0 && ema_decay < 1.0)))
+    return VG_ERR_BAD_ARG;
+  return adam_decay_launch(tensors, nonfinite, count, beta1, beta2, eps, 0.f, 0.f, 1.f, 0.f, scalars,
+                           (hipStream_t)stream, ema, ema ? ema_decay : 0.5, clip_record);
 }

@@ -82,11 +82,16 @@ __global__ __launch_bounds__(NT) void act_bwd_kernel(const float* __restrict__ g
 // One workgroup of 1024 threads (16 wavefronts); a wavefront owns a row at a time,
 // so the per-sample KL is one 64-lane shuffle reduction and the total is summed in a
 // fixed order.
+// BETA_DEV: beta is read from DEVICE memory (beta_dev[0]) -- a KL weight that changes between the replays of a captured
+// iteration; the expressions it enters are the same, so the same fp32 beta gives the same bits.
+template <bool BETA_DEV>
 __global__ __launch_bounds__(1024) void reparam_kl_fwd_kernel(const float* __restrict__ mu,
                                                               const float* __restrict__ lv,
                                                               const float* __restrict__ eps, float* __restrict__ z,
                                                               float* __restrict__ kl, float* __restrict__ kl_rows,
-                                                              int B, int D, float beta) {
+                                                              int B, int D, float beta,
+                                                              const float* __restrict__ beta_dev) {
+  if constexpr (BETA_DEV) beta = beta_dev[0];
   __shared__ double red[16];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   double wave_total = 0.0;
@@ -112,11 +117,14 @@ __global__ __launch_bounds__(1024) void reparam_kl_fwd_kernel(const float* __res
   }
 }
 
+template <bool BETA_DEV>
 __global__ __launch_bounds__(NT) void reparam_kl_bwd_kernel(const float* __restrict__ gz, const float* __restrict__ mu,
                                                             const float* __restrict__ lv,
                                                             const float* __restrict__ eps, const float* __restrict__ gkl, float beta,
+                                                            const float* __restrict__ beta_dev,
                                                             float* __restrict__ gmu, float* __restrict__ glv,
                                                             size_t n) {
+  if constexpr (BETA_DEV) beta = beta_dev[0];
   const size_t stride = (size_t)gridDim.x * NT;
   const float kb = (gkl ? gkl[0] : 0.f) * beta;
   // An absent upstream gradient takes its whole term out, as autograd does: every factor of that term is 0, not only
@@ -321,8 +329,17 @@ extern "C" int vg_act_bwd(const float* gy, const float* y, float* gx, size_t n, 
 extern "C" int vg_reparam_kl_fwd(const float* mu, const float* logvar, const float* eps, float* z, float* kl,
                                  float* kl_rows, int B, int D, float beta, void* stream) {
   if (!mu || !logvar || B <= 0 || D <= 0 || (z && !eps)) return VG_ERR_BAD_ARG;
-  hipLaunchKernelGGL(reparam_kl_fwd_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, mu, logvar, eps, z, kl,
-                     kl_rows, B, D, beta);
+  hipLaunchKernelGGL(reparam_kl_fwd_kernel<false>, dim3(1), dim3(1024), 0, (hipStream_t)stream, mu, logvar, eps, z, kl,
+                     kl_rows, B, D, beta, (const float*)nullptr);
+  VG_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int vg_reparam_kl_fwd_dev(const float* mu, const float* logvar, const float* eps, float* z, float* kl,
+                                     float* kl_rows, int B, int D, const float* beta_dev, void* stream) {
+  if (!mu || !logvar || B <= 0 || D <= 0 || (z && !eps) || !beta_dev) return VG_ERR_BAD_ARG;
+  hipLaunchKernelGGL(reparam_kl_fwd_kernel<true>, dim3(1), dim3(1024), 0, (hipStream_t)stream, mu, logvar, eps, z, kl,
+                     kl_rows, B, D, 0.f, beta_dev);
   VG_CHECK_LAUNCH();
   return 0;
 }
@@ -331,8 +348,19 @@ extern "C" int vg_reparam_kl_bwd(const float* gz, const float* mu, const float* 
                                  const float* gkl, float beta, float* gmu, float* glogvar, int B, int D, void* stream) {
   if (!mu || !logvar || !eps || !gmu || !glogvar || B <= 0 || D <= 0) return VG_ERR_BAD_ARG;
   const size_t n = (size_t)B * D;
-  hipLaunchKernelGGL(reparam_kl_bwd_kernel, dim3(flat_grid(n * 4)), dim3(NT), 0, (hipStream_t)stream, gz, mu, logvar,
-                     eps, gkl, beta, gmu, glogvar, n);
+  hipLaunchKernelGGL(reparam_kl_bwd_kernel<false>, dim3(flat_grid(n * 4)), dim3(NT), 0, (hipStream_t)stream, gz, mu,
+                     logvar, eps, gkl, beta, (const float*)nullptr, gmu, glogvar, n);
+  VG_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int vg_reparam_kl_bwd_dev(const float* gz, const float* mu, const float* logvar, const float* eps,
+                                     const float* gkl, const float* beta_dev, float* gmu, float* glogvar, int B, int D,
+                                     void* stream) {
+  if (!mu || !logvar || !eps || !gmu || !glogvar || B <= 0 || D <= 0 || !beta_dev) return VG_ERR_BAD_ARG;
+  const size_t n = (size_t)B * D;
+  hipLaunchKernelGGL(reparam_kl_bwd_kernel<true>, dim3(flat_grid(n * 4)), dim3(NT), 0, (hipStream_t)stream, gz, mu,
+                     logvar, eps, gkl, 0.f, beta_dev, gmu, glogvar, n);
   VG_CHECK_LAUNCH();
   return 0;
 }

@@ -495,12 +495,14 @@ class BiasActFn(Function):
 
 class ReparamKLFn(Function):
     """z = mu + eps*exp(logvar/2) and kl = beta*KL(q||N(0,1)) summed over the batch --
-    model.py:532-535 + experiments/new_betavaegan.py:64-65, one fused kernel each way."""
+    model.py:532-535 + experiments/new_betavaegan.py:64-65, one fused kernel each way.  ``beta``: a float, or a
+    one-element fp32 device tensor the kernels read (not differentiable; the backward reads the word as it is THEN: it
+    changes between iterations, not inside one)."""
 
     @staticmethod
     def forward(ctx, mu, logvar, eps, beta):
         z, kl, _ = ops.reparam_kl_fwd(mu, logvar, eps, beta)
-        ctx.beta = beta
+        ctx.beta = beta      # (a tensor is kept as the word itself, not saved: it takes no gradient)
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(mu, logvar, eps)
         return z, kl
@@ -668,13 +670,17 @@ def bias_act(x, bias, kind):
     return BiasActFn.apply(x, bias, kind)
 
 
+def _beta_arg(beta):
+    return beta.detach() if isinstance(beta, torch.Tensor) else float(beta)
+
+
 def reparam_kl(mu, logvar, eps, beta):
-    return ReparamKLFn.apply(mu, logvar, eps, float(beta))
+    return ReparamKLFn.apply(mu, logvar, eps, _beta_arg(beta))
 
 
 def kld_loss(mu, logvar, beta):
     """KLD of experiments/new_betavaegan.py:64-65 (no sampling)."""
-    _, kl = ReparamKLFn.apply(mu, logvar, torch.zeros_like(mu), float(beta))
+    _, kl = ReparamKLFn.apply(mu, logvar, torch.zeros_like(mu), _beta_arg(beta))
     return kl
 
 

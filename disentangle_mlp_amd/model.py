@@ -533,7 +533,8 @@ class VAE(nn.Module, _DecoderMixin):
         return self.decode(self.reparameterize(mu, logvar, eps)), mu, logvar
 
     def forward_with_kl(self, x, eps, beta):
-        """Same as forward plus the fused beta*KL scalar (one kernel for reparam + KL)."""
+        """Same as forward plus the fused beta*KL scalar (one kernel for reparam + KL).  ``beta``: a float, or a
+        one-element fp32 device tensor (functional.reparam_kl)."""
         mu, logvar = self.encode(x)
         if eps is None:
             eps = torch.randn_like(mu)

@@ -1006,13 +1006,26 @@ def scale_by_scalar(g, s):
 
 
 # ---------------------------------------------------------------------- losses
+def _beta_word(beta):
+    """``beta`` given as a tensor: the one-element fp32 device word the ``_dev`` KL kernels read."""
+    if beta.numel() != 1 or beta.dtype != torch.float32 or not beta.is_cuda:
+        raise RuntimeError("reparam_kl: beta as a tensor must be one fp32 element on the GPU")
+    return beta
+
+
 def reparam_kl_fwd(mu, logvar, eps, beta, want_rows=False):
+    """``beta``: a float, or a one-element fp32 device tensor read by the kernel (a value that changes between the replays
+    of a captured iteration); the same fp32 value gives the same bits either way."""
     lib = _lib.load()
     _req(mu, "mu"), _req(logvar, "logvar"), _req(eps, "eps")
     B, D = mu.shape
     z = torch.empty_like(mu)
     kl = torch.empty((), dtype=torch.float32, device=mu.device)
     rows = torch.empty(B, dtype=torch.float32, device=mu.device) if want_rows else None
+    if isinstance(beta, torch.Tensor):
+        check(lib.vg_reparam_kl_fwd_dev(mu.data_ptr(), logvar.data_ptr(), eps.data_ptr(), z.data_ptr(), kl.data_ptr(),
+                                        _ptr(rows), B, D, _beta_word(beta).data_ptr(), _stream()), "vg_reparam_kl_fwd_dev")
+        return z, kl, rows
     check(lib.vg_reparam_kl_fwd(mu.data_ptr(), logvar.data_ptr(), eps.data_ptr(), z.data_ptr(), kl.data_ptr(),
                                 _ptr(rows), B, D, float(beta), _stream()), "vg_reparam_kl_fwd")
     return z, kl, rows
@@ -1027,6 +1040,11 @@ def reparam_kl_bwd(gz, mu, logvar, eps, gkl, beta):
         _req(gz, "gz")
     if gkl is not None:
         _req(gkl, "gkl")
+    if isinstance(beta, torch.Tensor):
+        check(lib.vg_reparam_kl_bwd_dev(_ptr(gz), mu.data_ptr(), logvar.data_ptr(), eps.data_ptr(), _ptr(gkl),
+                                        _beta_word(beta).data_ptr(), gmu.data_ptr(), glv.data_ptr(), B, D, _stream()),
+              "vg_reparam_kl_bwd_dev")
+        return gmu, glv
     check(lib.vg_reparam_kl_bwd(_ptr(gz), mu.data_ptr(), logvar.data_ptr(), eps.data_ptr(), _ptr(gkl), float(beta),
                                 gmu.data_ptr(), glv.data_ptr(), B, D, _stream()), "vg_reparam_kl_bwd")
     return gmu, glv

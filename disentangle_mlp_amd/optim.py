@@ -5,8 +5,8 @@ hand-written HIP kernel (``vg_adam_step``).
 ``state`` (``step``, ``exp_avg``, ``exp_avg_sq``) and ``state_dict`` / ``load_state_dict`` -- the
 reference's optimizer checkpoints load into it and its own load into ``torch.optim.Adam``.  Only
 ``step()`` is replaced: one multi-tensor launch per 24 parameters instead of torch's fused
-``multi_tensor_apply``.  Configurations the kernel does not implement (weight decay, amsgrad,
-maximize, a closure, non-fp32 / non-contiguous / CPU tensors) take the inherited ``step()``.
+``multi_tensor_apply``.  Configurations the kernel does not implement (amsgrad, maximize, a
+closure, non-fp32 / non-contiguous / CPU tensors) take the inherited ``step()``.
 
 ``HipAdam(nonfinite_guard=True)``: the step also reports, per parameter, an inf / NaN among the gradients it read
 (`NONFINITE_GRAD`) and the parameters it wrote (`NONFINITE_PARAM`) -- ``vg_adam_step_checked`` -- in device words the
@@ -26,6 +26,14 @@ the whole of it is capturable.  `grad_norm`, `clip_coef` (device views), `skippe
 average costs 8 bytes per parameter and no launch of its own.  The averages live in tensors fixed at construction
 (fp32 clones, or the caller's ``ema_targets``: a trainer's shadow module), are NOT part of ``state_dict()`` -- that
 stays torch.optim.Adam's -- and travel through `ema_state` / `load_ema_state`.
+
+``HipAdam(weight_decay=w, decoupled_weight_decay=bool)``: the fused step decays the weights itself
+(``vg_adam_step_decay``) -- coupled (L2) ``g + w p`` or decoupled (AdamW) ``p (1 - lr w)``, in registers, no memory
+traffic of its own.  Groups without decay make the launches they always made.
+
+``HipAdam(capturable=True, device_hyper=True)``: every group's ``[lr, weight_decay]`` lives in a persistent device pair
+the step's prepare kernel reads (``vg_adam_prepare_dev``), so both may change between the replays of a captured step:
+set ``group["lr"]`` (or let a ``torch.optim.lr_scheduler`` do it) and call `sync_hyper` before the replay.
 """
 import ctypes
 import math
@@ -82,8 +90,13 @@ class HipAdam(optim.Adam):
     host mirrors the device counter (`prepare_capture` / `replayed`)."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, capturable=False,
-                 nonfinite_guard=False, ema_decay=None, ema_targets=None, max_grad_norm=None, skip_nonfinite=False):
+                 nonfinite_guard=False, ema_decay=None, ema_targets=None, max_grad_norm=None, skip_nonfinite=False,
+                 decoupled_weight_decay=False, device_hyper=False):
         self._words = None
+        self.device_hyper = False
+        if device_hyper and not capturable:
+            raise ValueError("HipAdam: device_hyper=True keeps lr and weight decay on the device for a captured step; "
+                             "it requires capturable=True")
         self._ema = None
         self._clip_rec = None
         if max_grad_norm is not None and not (0.0 < float(max_grad_norm) < math.inf):      # (NaN fails both comparisons)
@@ -93,9 +106,17 @@ class HipAdam(optim.Adam):
         if ema_decay is None and ema_targets is not None:
             raise ValueError("HipAdam: ema_targets without ema_decay")
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad,
-                         foreach=False, fused=False, capturable=False)
+                         foreach=False, fused=False, capturable=False, decoupled_weight_decay=decoupled_weight_decay)
         self.device_scalars = bool(capturable)
-        self._dev = {}            # group index -> (device step counter float64[1], scalars float32[2])
+        self._dev = {}            # group index -> (device step counter float64[1], scalars float32[4])
+        # lr and weight decay on the device: one persistent float64 pair [lr, weight_decay] per group, allocated here and
+        # never replaced -- like `_words`, a captured step reads where the host later writes (`sync_hyper`)
+        self._hyper = {}          # group index -> float64[2] device tensor
+        self._hyper_written = {}  # group index -> (lr, weight_decay) as last written
+        self.device_hyper = bool(device_hyper)
+        if self.device_hyper:
+            for gi in range(len(self.param_groups)):
+                self._hyper_words(gi)
         self._captured = []       # per captured step() call: the parameters it stepped (host bookkeeping of a replay)
         self._debt = 0            # replays whose host-side step counts have not been added yet (flushed lazily)
         self.state_generation = 0 # bumped by load_state_dict: captured graphs point at the moment tensors of one generation
@@ -148,6 +169,9 @@ class HipAdam(optim.Adam):
             self._partials = torch.zeros(max(1, slots), dtype=torch.float64, device=ps[0].device)
 
     def add_param_group(self, param_group):
+        if self.device_hyper:
+            raise RuntimeError("HipAdam(device_hyper=True): the hyper-parameter words are laid out at construction; "
+                               "pass every parameter group to the constructor")
         if self._words is not None:
             raise RuntimeError("HipAdam(nonfinite_guard=True): the flag words are laid out at construction; "
                                "pass every parameter group to the constructor")
@@ -158,6 +182,34 @@ class HipAdam(optim.Adam):
             raise RuntimeError("HipAdam(max_grad_norm=... / skip_nonfinite=True): the norm pass's partial sums are laid "
                                "out at construction; pass every parameter group to the constructor")
         return super().add_param_group(param_group)
+
+    # ---- lr and weight decay on the device --------------------------------------------------------------------
+    def _hyper_words(self, gi):
+        """Group ``gi``'s device pair [lr, weight_decay].  With ``device_hyper`` every pair exists from construction; a
+        capturable optimizer without it gets one the first time a group with weight decay steps (its decay step reads
+        the device scalars) -- outside a capture."""
+        h = self._hyper.get(gi)
+        if h is None:
+            if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("HipAdam: weight decay appeared inside a capture; step once eagerly first")
+            h = self._hyper[gi] = torch.zeros(2, dtype=torch.float64, device=self.param_groups[gi]["params"][0].device)
+        return h
+
+    def sync_hyper(self):
+        """Write ``group["lr"]`` and ``group["weight_decay"]`` into the device words where they differ from what was last
+        written: device fills, no synchronisation.  Every eager `step` and `prepare_capture` call it; whoever replays a
+        captured step calls it in front of the replay.  Never inside a capture: a captured fill would freeze the value."""
+        for gi, h in self._hyper.items():
+            group = self.param_groups[gi]
+            now = (float(group["lr"]), float(group["weight_decay"]))
+            was = self._hyper_written.get(gi)
+            if was is not None and self._captured and (was[1] != 0.0) != (now[1] != 0.0):
+                raise RuntimeError("HipAdam: a captured step was recorded with or without the decay kernel; weight decay "
+                                   "cannot be switched on or off under it (capture anew)")
+            if now != was:
+                h[0].fill_(now[0])
+                h[1].fill_(now[1])
+                self._hyper_written[gi] = now
 
     # ---- weight EMA ------------------------------------------------------------------------------------------
     def _need_ema(self):
@@ -289,8 +341,10 @@ class HipAdam(optim.Adam):
         self._torch_stepped = False
 
     def _native_ok(self, group):
-        if group["weight_decay"] != 0 or group["amsgrad"] or group.get("maximize", False) \
+        if group["amsgrad"] or group.get("maximize", False) \
                 or group.get("capturable", False) or group.get("differentiable", False):
+            return False
+        if not float(group["weight_decay"]) >= 0.0:      # (negative or NaN: torch's constructor refuses it too)
             return False
         for p in group["params"]:
             if p.grad is None:
@@ -306,7 +360,7 @@ class HipAdam(optim.Adam):
         d = self._dev.get(gi)
         if d is None:
             d = self._dev[gi] = (torch.zeros(1, dtype=torch.float64, device=device),
-                                 torch.zeros(2, dtype=torch.float32, device=device))
+                                 torch.zeros(4, dtype=torch.float32, device=device))
         return d
 
     def _flush_replays(self):
@@ -331,10 +385,14 @@ class HipAdam(optim.Adam):
                 raise RuntimeError("HipAdam.prepare_capture: parameters of one group are at different step counts")
             dev = group["params"][0].device
             self._device_state(gi, dev)[0].fill_(steps.pop() if steps else 0.0)
+        self.sync_hyper()
 
     def replayed(self, times=1):
-        """A captured iteration was replayed: the device counters advanced inside the graph, the host's follow (lazily)."""
+        """A captured iteration was replayed: the device counters advanced inside the graph, the host's follow (lazily).
+        A replay is an optimizer step as far as torch's lr schedulers are concerned (they warn when ``scheduler.step()``
+        comes before the first ``optimizer.step()``, which a replay never calls)."""
         self._debt += times
+        self._opt_called = True
 
     def load_state_dict(self, state_dict):
         """(torch replaces the moment tensors: a graph captured before holds the old ones -- `state_generation` tells the
@@ -439,6 +497,7 @@ class HipAdam(optim.Adam):
             raise RuntimeError("HipAdam: construct with capturable=True to capture its step in a HIP graph")
         if not capturing:
             self._flush_replays()
+            self.sync_hyper()
         bounds = self._weight_bounds()
         if bounds is not None:
             bounds.zero_()
@@ -484,12 +543,27 @@ class HipAdam(optim.Adam):
                     bi = self._bound_of.get(p) if bounds is not None else None
                     arr[i] = _AdamTensor(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(),
                                          None if bi is None else bounds[bi:bi + 1].data_ptr())
+                wd = float(group["weight_decay"])
+                decoupled = 1 if group.get("decoupled_weight_decay", False) else 0
                 if self.device_scalars:
                     step_dev, scalars = self._device_state(gi, items[0][0].device)
                     # an eager step also stores its count in the device counter: replays may follow it
-                    check(lib.vg_adam_prepare(float(step), step_dev.data_ptr(), 1 if capturing else 0, float(group["lr"]),
-                                              float(beta1), float(beta2), scalars.data_ptr(), stream), "vg_adam_prepare")
-                    if rec is not None:
+                    if self.device_hyper or wd != 0.0:
+                        hyper = self._hyper_words(gi)
+                        if not capturing:
+                            self.sync_hyper()      # (words that came into being just now)
+                        check(lib.vg_adam_prepare_dev(float(step), step_dev.data_ptr(), 1 if capturing else 0,
+                                                      hyper.data_ptr(), decoupled, float(beta1), float(beta2),
+                                                      scalars.data_ptr(), stream), "vg_adam_prepare_dev")
+                    else:
+                        check(lib.vg_adam_prepare(float(step), step_dev.data_ptr(), 1 if capturing else 0,
+                                                  float(group["lr"]), float(beta1), float(beta2), scalars.data_ptr(),
+                                                  stream), "vg_adam_prepare")
+                    if wd != 0.0:
+                        check(lib.vg_adam_step_dev_decay(arr, len(items), float(beta1), float(beta2), float(group["eps"]),
+                                                         scalars.data_ptr(), flags, ema, self.ema_decay or 0.0, rec,
+                                                         stream), "vg_adam_step_dev_decay")
+                    elif rec is not None:
                         check(lib.vg_adam_step_dev_clip(arr, len(items), float(beta1), float(beta2), float(group["eps"]),
                                                         scalars.data_ptr(), flags, ema, self.ema_decay or 0.0, rec, stream),
                               "vg_adam_step_dev_clip")
@@ -508,7 +582,11 @@ class HipAdam(optim.Adam):
                     continue
                 bc1 = 1.0 - beta1 ** step
                 bc2_sqrt = math.sqrt(1.0 - beta2 ** step)
-                if rec is not None:
+                if wd != 0.0:
+                    check(lib.vg_adam_step_decay(arr, len(items), float(group["lr"]), float(beta1), float(beta2),
+                                                 float(group["eps"]), bc1, bc2_sqrt, flags, ema, self.ema_decay or 0.0, rec,
+                                                 wd, decoupled, stream), "vg_adam_step_decay")
+                elif rec is not None:
                     check(lib.vg_adam_step_clip(arr, len(items), float(group["lr"]), float(beta1), float(beta2),
                                                 float(group["eps"]), bc1, bc2_sqrt, flags, ema, self.ema_decay or 0.0, rec,
                                                 stream), "vg_adam_step_clip")

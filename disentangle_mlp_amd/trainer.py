@@ -254,19 +254,23 @@ def _backward(losses):
     torch.autograd.backward(losses, grad_tensors=[one] * len(losses))
 
 
-def _make_adam(params, lr, fused, capturable=False, nonfinite_guard=False, max_grad_norm=None, skip_nonfinite=False):
+def _make_adam(params, lr, fused, capturable=False, nonfinite_guard=False, max_grad_norm=None, skip_nonfinite=False,
+               weight_decay=0.0, decoupled_weight_decay=False, device_hyper=False):
     """Adam with the reference's defaults (new_betavaegan.py:49-50).  On the GPU the step runs on the
     hand-written kernel (optim.HipAdam, a torch.optim.Adam subclass: identical state_dict); ``capturable``:
     its scalars are formed on the device so that a whole iteration can be captured in a HIP graph;
     ``nonfinite_guard``: the step flags non-finite gradients / parameters.  CPU construction uses torch's own
     implementation -- unless ``max_grad_norm`` / ``skip_nonfinite`` (clipping by global norm, skipping a non-finite
-    step: optim.HipAdam) is asked for: then it is a HipAdam there too, whose inherited step carries those semantics."""
+    step: optim.HipAdam) is asked for: then it is a HipAdam there too, whose inherited step carries those semantics.
+    ``weight_decay`` / ``decoupled_weight_decay``: torch.optim.Adam's, inside the fused step on the GPU; ``device_hyper``:
+    lr and weight decay in device words a captured step reads (optim.HipAdam)."""
+    decay = dict(weight_decay=weight_decay, decoupled_weight_decay=decoupled_weight_decay)
     if fused:
         return HipAdam(params, lr=lr, capturable=capturable, nonfinite_guard=nonfinite_guard,
-                       max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+                       max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, device_hyper=device_hyper, **decay)
     if max_grad_norm is not None or skip_nonfinite:
-        return HipAdam(params, lr=lr, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
-    return optim.Adam(params, lr=lr, capturable=capturable)
+        return HipAdam(params, lr=lr, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, **decay)
+    return optim.Adam(params, lr=lr, capturable=capturable, **decay)
 
 
 def _dist_world():
@@ -350,6 +354,8 @@ class _CapturedIteration:
       * inputs / latents: static device buffers the caller's tensors are copied into before a replay;
       * the two label scalars (new_betavaegan.py:89-90): a device tensor the BCE kernels read (vg_bce_loss_dev);
       * Adam's step count: a device counter advanced inside the graph (optim.HipAdam(capturable=True));
+      * with ``device_hyper``: the learning rate, the weight decay and the KL weight beta -- device words the prepare kernel
+        and the KL kernels read, refreshed from the host's values in front of every replay (`sync_hyper`);
       * Python-side bookkeeping a replay does not execute -- BatchNorm ``num_batches_tracked`` (counted lazily by the
         modules), Adam's host step counts, the trainer's iteration counter -- is re-applied after each replay from what
         the capture pass recorded.
@@ -361,6 +367,7 @@ class _CapturedIteration:
         self.labels = torch.zeros(2, dtype=torch.float32, device=trainer.device)     # [real, fake]
         self.label_values = None
         self.optimizers, self.bn = optimizers, bn_modules
+        self._trainer = __import__("weakref").ref(trainer)
         self.graph = torch.cuda.CUDAGraph()
         for k, v in inputs.items():
             self.inputs[k].copy_(v)
@@ -403,6 +410,11 @@ class _CapturedIteration:
             self.labels[0].fill_(real_label)
             self.labels[1].fill_(fake_label)
             self.label_values = (real_label, fake_label)
+        for o in self.optimizers:                # lr / weight decay words (nothing to do without them)
+            o.sync_hyper()
+        trainer = self._trainer()
+        if trainer is not None:
+            trainer._sync_beta()
         self.graph.replay()
         if self.fresh:
             self.fresh = False
@@ -565,6 +577,123 @@ class _GraphedSteps:
                 opt.clear_nonfinite()
         self._finite_at = self.iteration
 
+    # ---- schedules: learning rate, beta and weight decay ---------------------------------------------------------
+    lr_schedulers = {}
+    beta_schedule = None
+    device_hyper = False
+    weight_decay, decoupled_weight_decay = 0.0, False
+    _beta_dev = None          # with device_hyper: the persistent fp32 word the KL kernels read
+    _beta_written = None
+    _optimizer_names = ()     # every trainer lists its own
+
+    def _schedule_args(self, lr_scheduler, beta_schedule, device_hyper, weight_decay, decoupled_weight_decay, capturable,
+                       has_beta=True):
+        """Validate the schedule arguments and resolve ``device_hyper`` (None: on exactly when a scheduler or a beta schedule
+        is given -- and the optimizers can carry it: HipAdam with device scalars; without, the schedules still run and the
+        steps stay eager or re-key as before).  Returns the keyword arguments of `_make_adam`."""
+        if beta_schedule is not None and not has_beta:
+            raise TypeError(f"{type(self).__name__} has no KL term: beta_schedule does not apply")
+        for name, fn in (("lr_scheduler", lr_scheduler), ("beta_schedule", beta_schedule)):
+            if fn is not None and not callable(fn):
+                raise TypeError(f"{name} must be a callable, got {type(fn).__name__}")
+        wd = float(weight_decay)
+        if not wd >= 0.0:
+            raise ValueError(f"weight_decay must be >= 0, got {weight_decay!r}")
+        self.weight_decay, self.decoupled_weight_decay = wd, bool(decoupled_weight_decay)
+        self._lr_scheduler_factory, self.beta_schedule = lr_scheduler, beta_schedule
+        if device_hyper is None:
+            self.device_hyper = (lr_scheduler is not None or beta_schedule is not None) and bool(capturable)
+        else:
+            self.device_hyper = bool(device_hyper)
+            if self.device_hyper and not capturable:
+                raise ValueError("device_hyper=True needs optimizers whose step can be captured (a CUDA trainer with "
+                                 "fused_adam and graph / capturable on)")
+        if self.device_hyper and has_beta:
+            self._beta_dev = torch.full((1,), self.beta, dtype=torch.float32, device=self.device)
+            self._beta_written = self.beta
+        return dict(weight_decay=wd, decoupled_weight_decay=self.decoupled_weight_decay, device_hyper=self.device_hyper)
+
+    def _optimizers(self):
+        return {n: getattr(self, n) for n in self._optimizer_names}
+
+    def _make_schedulers(self):
+        """``lr_scheduler(optimizer)`` for each of the trainer's optimizers -> `lr_schedulers`, keyed by attribute name."""
+        self.lr_schedulers = {}
+        if self._lr_scheduler_factory is None:
+            return
+        from torch.optim.lr_scheduler import LRScheduler
+        for name, opt in self._optimizers().items():
+            sched = self._lr_scheduler_factory(opt)
+            if not isinstance(sched, LRScheduler):
+                raise TypeError(f"lr_scheduler must return a torch.optim.lr_scheduler.LRScheduler, got "
+                                f"{type(sched).__name__} for {name}")
+            self.lr_schedulers[name] = sched
+
+    def _kl_beta(self):
+        """What the KL kernels take: the device word with ``device_hyper`` (eager and captured alike), else the float."""
+        return self._beta_dev if self._beta_dev is not None else self.beta
+
+    def _sync_beta(self):
+        """`beta` into its device word when it differs from what was last written (a device fill, no synchronisation;
+        never inside a capture: `step` and a replay call it in front of the launches)."""
+        if self._beta_dev is not None and self.beta != self._beta_written:
+            self._beta_dev.fill_(self.beta)
+            self._beta_written = self.beta
+
+    def _begin_step(self):
+        if self.beta_schedule is not None:
+            self.beta = float(self.beta_schedule(self.iteration))
+        self._sync_beta()
+
+    def _end_step(self):
+        for sched in self.lr_schedulers.values():      # once per iteration: EG's two optimizer steps share one lr
+            sched.step()
+
+    def set_lr(self, value, which=None):
+        """Set the learning rate by hand: of every optimizer, or of the one named ``which`` (its attribute name, a key of
+        `_optimizers`).  With ``device_hyper`` the next step picks it up without a new capture; an lr scheduler, if any,
+        overwrites it at its next step."""
+        opts = self._optimizers()
+        if which is not None and which not in opts:
+            raise KeyError(f"no optimizer {which!r}: {sorted(opts)}")
+        for name, opt in opts.items():
+            if which is None or name == which:
+                for group in opt.param_groups:
+                    group["lr"] = float(value)
+
+    def set_beta(self, value):
+        """Set the KL weight by hand (a ``beta_schedule``, if any, overwrites it at the start of the next step)."""
+        if not hasattr(self, "beta"):
+            raise TypeError(f"{type(self).__name__} has no KL term")
+        self.beta = float(value)
+
+    def _schedule_checkpoint(self):
+        """The additional checkpoint keys -- present only when a schedule exists."""
+        extra = {}
+        if self.lr_schedulers:
+            extra["lr_schedulers"] = {n: s.state_dict() for n, s in self.lr_schedulers.items()}
+        if self.lr_schedulers or self.beta_schedule is not None:
+            extra["iteration"] = self.iteration
+        return extra
+
+    def _schedule_restore(self, ck, in_place=False):
+        """Restore the additional keys when the checkpoint has them (a reference checkpoint has none).  ``in_place``: the
+        optimizers' param_groups were not loaded (only their state was copied), so the learning rates are taken over
+        here."""
+        if "iteration" in ck:
+            self.iteration = int(ck["iteration"])
+        for name, sd in ck.get("lr_schedulers", {}).items():
+            if name in self.lr_schedulers:
+                self.lr_schedulers[name].load_state_dict(sd)
+        if in_place and "lr_schedulers" in ck:
+            for name, key in self._checkpoint_optimizer_keys.items():
+                for group, saved in zip(getattr(self, name).param_groups, ck[key]["param_groups"]):
+                    group["lr"] = saved["lr"]
+        if self.beta_schedule is not None and "iteration" in ck:
+            self.beta = float(self.beta_schedule(max(self.iteration - 1, 0)))      # (the last step's; the next step sets its own)
+
+    _checkpoint_optimizer_keys = {}
+
     def _host_state_key(self):
         """Host-side switches a capture freezes besides the shapes: part of every capture key, so that flipping one
         captures anew instead of replaying the old launches."""
@@ -572,6 +701,7 @@ class _GraphedSteps:
         return (M.FUSE_CONV_BN, M.FUSE_HEAD_BCE, F.DEFER_WGRAD, ops.THIN_SPLIT, ops.USE_PACKED_FILTERS,
                 self.nonfinite_guard,        # (checked or unchecked Adam launches)
                 self.max_grad_norm, self.skip_nonfinite,      # (the norm pass and the clip step, or neither)
+                self.device_hyper,           # (lr, weight decay and beta read from device words, or frozen arguments)
                 tuple(net.training for net in self._nets()),
                 tuple(p.requires_grad for net in self._nets() for p in net.parameters()))
 
@@ -580,6 +710,11 @@ class _GraphedSteps:
         buffer (same generator, same order as the eager path's torch.randn)."""
         buf = cap.inputs[name] if cap is not None else torch.empty(batch, self.opt.n_hidden, device=self.device)
         return buf.normal_(generator=self.latent_generator)
+
+    def _frozen(self, *values):
+        """Learning rates / beta as part of a capture key: frozen kernel arguments -- unless ``device_hyper`` keeps them
+        in device words, where they may change under one capture."""
+        return None if self.device_hyper else values
 
     def _run_graphed(self, key, make_inputs, labels, run, optimizers, nets, eager):
         """``key``: everything the capture freezes (shapes, divisors, learning rates, arithmetic).  ``make_inputs(cap)``
@@ -628,12 +763,26 @@ class BetaVAEGANTrainer(_GraphedSteps):
     ``max_grad_norm`` / ``skip_nonfinite`` (default: off -- then every launch is what it was): every optimizer step clips
     its gradients by their global L2 norm, and / or skips itself when that norm is inf / NaN (optim.HipAdam: one norm pass
     in front of the fused step, nothing on the host, captured with the iteration).  `skipped_steps` counts the skips.  What
-    a skip does NOT undo: a forward pass that was non-finite already has written its BatchNorm running statistics."""
+    a skip does NOT undo: a forward pass that was non-finite already has written its BatchNorm running statistics.
+
+    Schedules (default: none -- then every launch and every capture key is what it was): ``lr_scheduler``, a callable
+    ``optimizer -> torch.optim.lr_scheduler.LRScheduler`` applied to each optimizer (kept in `lr_schedulers` under the
+    optimizer's attribute name, stepped once at the end of every `step`); ``beta_schedule``, a callable ``iteration ->
+    float`` evaluated with `iteration` at the start of every `step` (-> `beta`); ``weight_decay`` /
+    ``decoupled_weight_decay`` as torch.optim.Adam's, inside the fused step.  ``device_hyper`` (default: on exactly when a
+    scheduler or a beta schedule is given): lr, weight decay and beta live in device words the captured kernels read, so a
+    value that changes every iteration still replays ONE graph.  `set_lr` / `set_beta`: the same by hand.  Data parallel:
+    every rank evaluates the same schedule on the same iteration counter; nothing is exchanged."""
+
+    _optimizer_names = ("optimizerEG", "optimizerD")
+    _checkpoint_optimizer_keys = {"optimizerEG": "encoder_decoder_optimizer", "optimizerD": "discriminator_optimizer"}
 
     def __init__(self, device="cuda", seed=999, beta=25.0, lr=1e-3, opt: Optional[ModelOpt] = None,
                  data_parallel: Optional[bool] = None, fused_adam: bool = True, capturable: Optional[bool] = None,
                  graph: Optional[bool] = None, nonfinite_guard: Optional[bool] = None,
-                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
+                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False,
+                 lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0, decoupled_weight_decay: bool = False,
+                 device_hyper: Optional[bool] = None):
         self.opt = opt or ModelOpt()
         self.device = torch.device(device)
         _use_tuned_gemms(self.device)
@@ -654,8 +803,11 @@ class BetaVAEGANTrainer(_GraphedSteps):
         fused = fused_adam and self.device.type == "cuda"
         self.nonfinite_guard = self._resolve_guard(nonfinite_guard, fused)
         clip = dict(max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+        clip.update(self._schedule_args(lr_scheduler, beta_schedule, device_hyper, weight_decay, decoupled_weight_decay,
+                                        fused and capturable))
         self.optimizerEG = _make_adam(self.netEG.parameters(), lr, fused, capturable, self.nonfinite_guard, **clip)   # :49 (hard-coded 1e-3 there)
         self.optimizerD = _make_adam(self.netD.parameters(), lr, fused, capturable, self.nonfinite_guard, **clip)     # :50
+        self._make_schedulers()
         self.flat_eg = FlatGrads(self.netEG.parameters(), silent=shadowed_bias_params(self.netEG)) if self.dp else None
         self.flat_d = FlatGrads(self.netD.parameters(), silent=shadowed_bias_params(self.netD)) if self.dp else None
         self.netEG.train()
@@ -695,18 +847,26 @@ class BetaVAEGANTrainer(_GraphedSteps):
         """One iteration; returns the nine loss scalars as device tensors (no host sync).  From the third iteration of a
         batch shape on the iteration is a HIP-graph replay and the returned tensors are the capture's STATIC outputs: the
         next replay overwrites them -- ``.clone()`` (or ``float()``) what is kept across steps."""
+        self._begin_step()
         if self._graph_usable((self.optimizerD, self.optimizerEG), data, grad_hook):
-            return self._step_graphed(data, noise, eps2, eps3, float(real_label), float(fake_label), global_batch)
-        # weights change only at the three optimizer steps below: packed filters are reused between them
-        with ops.packed_filter_scope():
-            return self._step(data, noise, eps2, eps3, real_label, fake_label, global_batch, grad_hook)
+            out = self._step_graphed(data, noise, eps2, eps3, float(real_label), float(fake_label), global_batch)
+        else:
+            # weights change only at the three optimizer steps below: packed filters are reused between them
+            with ops.packed_filter_scope():
+                out = self._step(data, noise, eps2, eps3, real_label, fake_label, global_batch, grad_hook)
+        self._end_step()
+        return out
 
     def _step_graphed(self, data, noise, eps2, eps3, real_label, fake_label, global_batch):
         B = data.size(0)
         gb = global_batch if global_batch is not None else B * self.world
-        key = (tuple(data.shape), int(gb), self.beta, self.optimizerEG.param_groups[0]["lr"],
-               self.optimizerD.param_groups[0]["lr"], ops.CONV_ARITH, self.optimizerEG.state_generation,
-               self.optimizerD.state_generation)
+        if self.device_hyper:
+            key = (tuple(data.shape), int(gb), ops.CONV_ARITH, self.optimizerEG.state_generation,
+                   self.optimizerD.state_generation)
+        else:
+            key = (tuple(data.shape), int(gb), self.beta, self.optimizerEG.param_groups[0]["lr"],
+                   self.optimizerD.param_groups[0]["lr"], ops.CONV_ARITH, self.optimizerEG.state_generation,
+                   self.optimizerD.state_generation)
 
         def make_inputs(cap):                        # latents left to the trainer: drawn in the eager path's order
             lat = {name: (t if t is not None else self._draw_into(cap, name, B))
@@ -803,7 +963,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
 
         # ---- phase 3: "encoder" -- again every EG parameter moves (:167-193)
         self._zero(netEG, self.flat_eg)
-        recon, mu, logvar, kld = netEG.forward_with_kl(data, eps3, self.beta)
+        recon, mu, logvar, kld = netEG.forward_with_kl(data, eps3, self._kl_beta())
         mse3 = F.reconstruction_loss(recon, data)
         _backward([kld, mse3])
         self._exchange(self.flat_eg)
@@ -964,6 +1124,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
             "discriminator_model": {"module." + k: v for k, v in self.netD.state_dict().items()},
             "encoder_decoder_optimizer": self.optimizerEG.state_dict(),
             "discriminator_optimizer": self.optimizerD.state_dict(),
+            **self._schedule_checkpoint(),       # (additional keys, only when a schedule exists)
         }
 
     def save(self, path, epoch, legacy_format=False):
@@ -980,6 +1141,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
         self.netD.load_state_dict(d_sd)
         self.optimizerEG.load_state_dict(ck["encoder_decoder_optimizer"])
         self.optimizerD.load_state_dict(ck["discriminator_optimizer"])
+        self._schedule_restore(ck)
         self.clear_nonfinite()                               # a good checkpoint is the way back from a NonFiniteError
         return ck["epoch"]
 
@@ -1008,18 +1170,24 @@ class BetaVAEGANTrainer(_GraphedSteps):
         for opt in (self.optimizerEG, self.optimizerD):      # (the bounds the captured GEMMs read beside the weights)
             if isinstance(opt, HipAdam):
                 opt.refresh_weight_bounds()
+        self._schedule_restore(ck, in_place=True)
         self.clear_nonfinite()
         return ck["epoch"]
 
 
 class VAETrainer(_GraphedSteps):
-    """new_vae.py:33-37 construction, :39-48 loss, :53-59 step.  ``graph``, ``max_grad_norm``, ``skip_nonfinite``: as
-    BetaVAEGANTrainer."""
+    """new_vae.py:33-37 construction, :39-48 loss, :53-59 step.  ``graph``, ``max_grad_norm``, ``skip_nonfinite``, and the
+    schedule arguments (``lr_scheduler``, ``beta_schedule``, ``weight_decay``, ``decoupled_weight_decay``,
+    ``device_hyper``): as BetaVAEGANTrainer."""
+
+    _optimizer_names = ("optimizer",)
+    _checkpoint_optimizer_keys = {"optimizer": "optimizer"}
 
     def __init__(self, device="cuda", seed=999, beta=1.0, lr=3e-3, opt: Optional[ModelOpt] = None,
                  fused_adam: bool = True, capturable: Optional[bool] = None, graph: Optional[bool] = None,
                  nonfinite_guard: Optional[bool] = None, max_grad_norm: Optional[float] = None,
-                 skip_nonfinite: bool = False):
+                 skip_nonfinite: bool = False, lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0,
+                 decoupled_weight_decay: bool = False, device_hyper: Optional[bool] = None):
         self.opt = opt or ModelOpt()
         self.device = torch.device(device)
         _use_tuned_gemms(self.device)
@@ -1033,8 +1201,12 @@ class VAETrainer(_GraphedSteps):
         self._graph_init(graph, self.device.type == "cuda", fused_adam, self.world > 1)
         fused = fused_adam and self.device.type == "cuda"
         self.nonfinite_guard = self._resolve_guard(nonfinite_guard, fused)
-        self.optimizer = _make_adam(self.model.parameters(), lr, fused, self.graph if capturable is None else capturable,
-                                    self.nonfinite_guard, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+        capturable = self.graph if capturable is None else capturable
+        hyper = self._schedule_args(lr_scheduler, beta_schedule, device_hyper, weight_decay, decoupled_weight_decay,
+                                    fused and capturable)
+        self.optimizer = _make_adam(self.model.parameters(), lr, fused, capturable, self.nonfinite_guard,
+                                    max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, **hyper)
+        self._make_schedulers()
         self.flat = FlatGrads(self.model.parameters(), silent=shadowed_bias_params(self.model)) if self.world > 1 else None
         self.latent_generator = _latent_generator(self.device, seed, _dist_rank())
         self.model.train()
@@ -1043,6 +1215,12 @@ class VAETrainer(_GraphedSteps):
         return [("model", self.model, self.optimizer)]
 
     def step(self, data, eps=None):
+        self._begin_step()
+        out = self._step_any(data, eps)
+        self._end_step()
+        return out
+
+    def _step_any(self, data, eps):
         def eager(inp=None):
             with ops.packed_filter_scope():       # one optimizer step at the end: packs live for the iteration
                 return self._step(data, inp["eps"] if inp is not None else eps)
@@ -1052,7 +1230,7 @@ class VAETrainer(_GraphedSteps):
         def run(inp, real_dev, fake_dev):
             with ops.packed_filter_scope():
                 return self._step(inp["data"], inp["eps"])
-        key = (tuple(data.shape), self.beta, self.optimizer.param_groups[0]["lr"], ops.CONV_ARITH,
+        key = (tuple(data.shape), self._frozen(self.beta, self.optimizer.param_groups[0]["lr"]), ops.CONV_ARITH,
                self.optimizer.state_generation)
         return self._run_graphed(key, lambda cap: dict(data=data.contiguous(),
                                                        eps=eps if eps is not None else self._draw_into(cap, "eps", data.size(0))),
@@ -1069,7 +1247,7 @@ class VAETrainer(_GraphedSteps):
             self.flat.zero_and_attach()
         else:
             _zero_grads(self.model)
-        recon, mu, logvar, kld = self.model.forward_with_kl(data, eps, self.beta)
+        recon, mu, logvar, kld = self.model.forward_with_kl(data, eps, self._kl_beta())
         mse = F.reconstruction_loss(recon, data)
         _backward([mse, kld])
         if self.flat is not None:
@@ -1095,19 +1273,26 @@ class VAETrainer(_GraphedSteps):
         return float(total) / len(loader.dataset)
 
     def checkpoint(self, epoch):
-        return {"epoch": epoch, "VAE_model": self.model.state_dict(), "optimizer": self.optimizer.state_dict()}
+        return {"epoch": epoch, "VAE_model": self.model.state_dict(), "optimizer": self.optimizer.state_dict(),
+                **self._schedule_checkpoint()}
 
 
 class GANTrainer(_GraphedSteps):
     """new_gan.py:47-61 construction, :66-141 step.  Data parallel like the beta-VAE-GAN driver (the
     reference wraps both nets in nn.DataParallel, new_gan.py:51-53): replica-local BatchNorm, one
     gradient exchange (SUM) per optimizer step, BCE divided by the global batch.  ``graph``: as
-    BetaVAEGANTrainer; so are ``max_grad_norm`` and ``skip_nonfinite``."""
+    BetaVAEGANTrainer; so are ``max_grad_norm``, ``skip_nonfinite`` and the schedule arguments (``lr_scheduler``,
+    ``weight_decay``, ``decoupled_weight_decay``, ``device_hyper``; there is no KL term, so a ``beta_schedule`` is a
+    TypeError)."""
+
+    _optimizer_names = ("optimizerG", "optimizerD")
+    _checkpoint_optimizer_keys = {"optimizerG": "G_trainer", "optimizerD": "D_trainer"}
 
     def __init__(self, device="cuda", seed=999, lr=3e-3, opt: Optional[ModelOpt] = None, fused_adam: bool = True,
                  data_parallel: Optional[bool] = None, graph: Optional[bool] = None,
                  nonfinite_guard: Optional[bool] = None, max_grad_norm: Optional[float] = None,
-                 skip_nonfinite: bool = False):
+                 skip_nonfinite: bool = False, lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0,
+                 decoupled_weight_decay: bool = False, device_hyper: Optional[bool] = None):
         self.opt = opt or ModelOpt()
         self.device = torch.device(device)
         _use_tuned_gemms(self.device)
@@ -1124,8 +1309,11 @@ class GANTrainer(_GraphedSteps):
         self._graph_init(graph, self.device.type == "cuda", fused_adam, self.dp)
         self.nonfinite_guard = self._resolve_guard(nonfinite_guard, fused)
         clip = dict(max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+        clip.update(self._schedule_args(lr_scheduler, beta_schedule, device_hyper, weight_decay, decoupled_weight_decay,
+                                        fused and self.graph, has_beta=False))
         self.optimizerG = _make_adam(self.netG.parameters(), lr, fused, self.graph, self.nonfinite_guard, **clip)
         self.optimizerD = _make_adam(self.netD.parameters(), lr, fused, self.graph, self.nonfinite_guard, **clip)
+        self._make_schedulers()
         self.flat_g = FlatGrads(self.netG.parameters(), silent=shadowed_bias_params(self.netG)) if self.dp else None
         self.flat_d = FlatGrads(self.netD.parameters(), silent=shadowed_bias_params(self.netD)) if self.dp else None
         self.latent_generator = _latent_generator(self.device, seed, _dist_rank())
@@ -1148,6 +1336,12 @@ class GANTrainer(_GraphedSteps):
 
     def step(self, data, noise=None, real_label=0.9, fake_label=0.1, global_batch: Optional[int] = None,
              grad_hook=None):
+        self._begin_step()
+        out = self._step_any(data, noise, real_label, fake_label, global_batch, grad_hook)
+        self._end_step()
+        return out
+
+    def _step_any(self, data, noise, real_label, fake_label, global_batch, grad_hook):
         def eager(inp=None):
             with ops.packed_filter_scope():
                 return self._step(data, inp["noise"] if inp is not None else noise, real_label, fake_label, global_batch,
@@ -1160,7 +1354,8 @@ class GANTrainer(_GraphedSteps):
         def run(inp, real_dev, fake_dev):
             with ops.packed_filter_scope():
                 return self._step(inp["data"], inp["noise"], real_dev, fake_dev, gb, None)
-        key = (tuple(data.shape), int(gb), self.optimizerG.param_groups[0]["lr"], self.optimizerD.param_groups[0]["lr"],
+        key = (tuple(data.shape), int(gb), self._frozen(self.optimizerG.param_groups[0]["lr"],
+                                                        self.optimizerD.param_groups[0]["lr"]),
                ops.CONV_ARITH, self.optimizerG.state_generation, self.optimizerD.state_generation)
         return self._run_graphed(key, lambda cap: dict(data=data.contiguous(),
                                                        noise=noise if noise is not None else self._draw_into(cap, "noise", B)),
@@ -1240,4 +1435,5 @@ class GANTrainer(_GraphedSteps):
 
     def checkpoint(self, epoch):
         return {"epoch": epoch, "netG": self.netG.state_dict(), "netD": self.netD.state_dict(),
-                "G_trainer": self.optimizerG.state_dict(), "D_trainer": self.optimizerD.state_dict()}
+                "G_trainer": self.optimizerG.state_dict(), "D_trainer": self.optimizerD.state_dict(),
+                **self._schedule_checkpoint()}

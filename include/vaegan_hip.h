@@ -47,7 +47,8 @@ extern "C" {
  * 6: vg_conv_general_* (the general forward convolution).  7: vg_adam_step_checked / vg_adam_step_dev_checked.
  * Entry points that are only ADDED (the four of csrc/fid_front.hip; vg_bn_eval_coeffs, vg_bn_eval_act_bwd;
  * vg_adam_step_ema, vg_adam_step_dev_ema; vg_grad_sumsq_partials, vg_grad_sumsq_multi, vg_grad_clip_finalize,
- * vg_adam_step_clip, vg_adam_step_dev_clip) change
+ * vg_adam_step_clip, vg_adam_step_dev_clip; vg_adam_prepare_dev, vg_adam_step_decay, vg_adam_step_dev_decay,
+ * vg_reparam_kl_fwd_dev, vg_reparam_kl_bwd_dev) change
  * nothing an existing caller sees and keep the version: a binding that needs them and finds a library without them
  * fails at the symbol lookup, as loudly. */
 #define VG_ABI_VERSION 7
@@ -408,6 +409,14 @@ int vg_reparam_kl_fwd(const float* mu, const float* logvar, const float* eps, fl
  * NULL (treated as 0). */
 int vg_reparam_kl_bwd(const float* gz, const float* mu, const float* logvar, const float* eps,
                       const float* gkl, float beta, float* gmu, float* glogvar, int B, int D, void* stream);
+/* The two with beta read from DEVICE memory (beta_dev[0], fp32): a KL weight on a schedule changes between the replays
+ * of an iteration captured in a HIP graph.  Same expressions -- (float)(beta * t), gkl * beta -- so the same fp32 beta
+ * gives the same bits.  beta_dev == NULL is VG_ERR_BAD_ARG. */
+int vg_reparam_kl_fwd_dev(const float* mu, const float* logvar, const float* eps, float* z, float* kl,
+                          float* kl_rows, int B, int D, const float* beta_dev, void* stream);
+int vg_reparam_kl_bwd_dev(const float* gz, const float* mu, const float* logvar, const float* eps,
+                          const float* gkl, const float* beta_dev, float* gmu, float* glogvar, int B, int D,
+                          void* stream);
 
 /* out[i] = g[i] * s[0] with s a DEVICE scalar: applies the upstream gradient of a
  * loss scalar to a gradient precomputed by the fused loss kernels, without a
@@ -451,7 +460,7 @@ int vg_dot_sigmoid_bce_bwd(const float* dlogit, const float* gloss, const float*
  * p -= (lr / bias_correction1) * m / (sqrt(v) / bias_correction2_sqrt + eps),
  * with bias_correction1 = 1 - beta1^step and bias_correction2_sqrt = sqrt(1 - beta2^step) computed by
  * the caller (double).  `tensors` is a HOST array of DEVICE pointers (fp32, n elements each);
- * any number of tensors, 24 per kernel launch.  No weight decay / amsgrad / maximize. */
+ * any number of tensors, 24 per kernel launch.  No amsgrad / maximize; weight decay: vg_adam_step_decay below. */
 typedef struct {
   float* p;
   const float* g;
@@ -546,6 +555,38 @@ int vg_adam_step_clip(const VgAdamTensor* tensors, int count, double lr, double 
 int vg_adam_step_dev_clip(const VgAdamTensor* tensors, int count, double beta1, double beta2, double eps,
                           const float* scalars, unsigned* const* nonfinite, float* const* ema, double ema_decay,
                           const float* clip_record, void* stream);
+/* Learning rate and weight decay on the DEVICE, weight decay inside the step.
+ *
+ * vg_adam_prepare_dev: vg_adam_prepare with lr and the weight decay read from DEVICE memory, hyper = [lr, weight_decay]
+ * (two doubles) -- a schedule writes them between the replays of a captured step.  It leaves four floats:
+ *   scalars[0]  (float)(lr / (1 - beta1^step))     the expressions of vg_adam_prepare: same lr, same bits
+ *   scalars[1]  (float)sqrt(1 - beta2^step)
+ *   scalars[2]  decoupled != 0 and wd != 0: (float)(1 - lr * wd), product and difference each rounded in double; else 1
+ *   scalars[3]  decoupled == 0: (float)wd; else 0
+ * Step and counter handling as vg_adam_prepare.  VG_ERR_BAD_ARG before the launch for a NULL hyper or scalars.
+ *
+ * vg_adam_step_decay / vg_adam_step_dev_decay: vg_adam_step_clip / vg_adam_step_dev_clip that also decay the weights,
+ * in registers, with no memory traffic of their own.  `nonfinite`, `ema` and `clip_record` may each be NULL (no record:
+ * gs = g, nothing is skipped).  Per element, in fp32, with gs = coef * g as in the clip step:
+ *   coupled (L2, decoupled == 0), wd != 0:   gd = gs + (wd * p)   a rounded product, then a rounded sum;
+ *                                            the update of the clip step runs on (p, gd)
+ *   decoupled (AdamW), wd != 0:              pd = p * s2          one rounding, s2 as scalars[2];
+ *                                            the update runs on (pd, gs)
+ *   wd == 0:                                 neither term is formed (no 0 * inf): the bits of the clip step
+ * p, m, v, amax, the flag words and the averages are bit for bit those of the clip step on such inputs; the GRAD bit is
+ * judged on gs, amax and the PARAM bit on the final p.  With the record's skip word up nothing is stored and nothing
+ * decays (the clip step's skip).  The host form takes weight_decay and decoupled as arguments and forms scalars[2..3]
+ * by the expressions above; the _dev form reads all four scalars.  VG_ERR_BAD_ARG before any launch: a negative or
+ * NaN weight_decay, and what the clip step rejects (but for the record). */
+int vg_adam_prepare_dev(double step, double* step_dev, int advance_device_counter, const double* hyper, int decoupled,
+                        double beta1, double beta2, float* scalars, void* stream);
+int vg_adam_step_decay(const VgAdamTensor* tensors, int count, double lr, double beta1, double beta2, double eps,
+                       double bias_correction1, double bias_correction2_sqrt, unsigned* const* nonfinite,
+                       float* const* ema, double ema_decay, const float* clip_record, double weight_decay, int decoupled,
+                       void* stream);
+int vg_adam_step_dev_decay(const VgAdamTensor* tensors, int count, double beta1, double beta2, double eps,
+                           const float* scalars, unsigned* const* nonfinite, float* const* ema, double ema_decay,
+                           const float* clip_record, void* stream);
 
 /* ---- image I/O either side of the step -----------------
  * Input pipeline of dataloader/dataset.py:37-43 (ToTensor + Normalize(mean, std) of a

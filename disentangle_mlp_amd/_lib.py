@@ -94,6 +94,7 @@ SIGNATURES = {
     "vg_adam_prepare_dev": (_I, [ctypes.c_double, _P, _I, _P, _I, ctypes.c_double, ctypes.c_double, _P, _P]),
     "vg_adam_step_decay": (_I, [_P, _I] + [ctypes.c_double] * 6 + [_P, _P, ctypes.c_double, _P, ctypes.c_double, _I, _P]),
     "vg_adam_step_dev_decay": (_I, [_P, _I] + [ctypes.c_double] * 3 + [_P, _P, _P, ctypes.c_double, _P, _P]),
+    "vg_adam_step_dev_ema_dev": (_I, [_P, _I] + [ctypes.c_double] * 3 + [_P, _P, _P, _P, _P, _P]),
     "vg_reparam_kl_fwd_dev": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P]),
     "vg_reparam_kl_bwd_dev": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "vg_bce_loss_dev": (_I, [_P, _P, _P, _P, _I, _F, _F, _P]),

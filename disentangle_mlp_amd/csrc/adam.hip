@@ -43,6 +43,11 @@
 // decoupled (AdamW): pd = p * s2 with s2 = (float)(1 - lr * wd) formed in double -- and no memory traffic of its own.
 // With wd == 0 neither term is formed (no 0 * inf) and the bits are the clip step's.  Again a kernel and a pack of its
 // own.
+//
+// EMA decay on the device (vg_adam_step_dev_ema_dev): the decay step with (float)(1 - decay) read from a device word
+// instead of the pack -- an ordinary global load, uniform over the grid -- so a warm-up changes the decay between the
+// replays of a captured step.  A compile-time variant of the decay kernel with a pack of its own; the word 1.0f
+// ("follow the weights") stores p itself, since e + 1 (p - e) is not p in fp32.
 #include "common.hpp"
 #include "vaegan_hip.h"
 
@@ -437,6 +442,11 @@ struct AdamPackDecay : AdamPackEma {
   float wdc;      // coupled: this times p is added to the gradient; 0: not
 };
 
+// The pack of the variant that reads (float)(1 - decay) from device memory: omd is not used.
+struct AdamPackDecayDev : AdamPackDecay {
+  const float* omd_dev;
+};
+
 // wd * p and gs + (wd * p): a rounded product and a rounded sum (torch: p.mul(wd), then g.add_), never one fma.
 __device__ __forceinline__ float decay_grad(float gs, float wdc, float p) {
 #pragma clang fp contract(off)
@@ -454,10 +464,11 @@ __device__ __forceinline__ float decay_param(float p, float s2) {
 // clipping, nothing skipped: gs = g).  l2 / dec are uniform over the grid; with neither, every element takes the clip
 // step's operations and nothing else.  The GRAD bit is judged on gs -- the gradient the caller handed in, scaled -- not
 // on gd, which an inf WEIGHT would poison as well; amax and the PARAM bit on the final p.
-template <bool DEV>
-__global__ __launch_bounds__(ANT) void adam_decay_multi_kernel(AdamPackDecay A, float omb1, float b2, float omb2,
-                                                              float step_size, float bc2s, float eps,
-                                                              const float* __restrict__ scalars,
+// EDEV: (float)(1 - decay) comes from the device word A.omd_dev; 1.0f stores p itself, anything else takes ema_one.
+template <bool DEV, bool EDEV = false>
+__global__ __launch_bounds__(ANT) void adam_decay_multi_kernel(std::conditional_t<EDEV, AdamPackDecayDev, AdamPackDecay> A,
+                                                              float omb1, float b2, float omb2, float step_size,
+                                                              float bc2s, float eps, const float* __restrict__ scalars,
                                                               const float* __restrict__ record) {
   float s2 = A.s2, wdc = A.wdc;
   if constexpr (DEV) {
@@ -480,7 +491,19 @@ __global__ __launch_bounds__(ANT) void adam_decay_multi_kernel(AdamPackDecay A, 
   float* __restrict__ m = A.m[t];
   float* __restrict__ v = A.v[t];
   float* __restrict__ e = A.e[t];
-  const float omd = A.omd;
+  float omd = A.omd;
+  [[maybe_unused]] bool follow = false;      // (uniform over the grid)
+  if constexpr (EDEV) {
+    omd = A.omd_dev[0];
+    follow = omd == 1.f;
+  }
+  // one element of the average from the p just formed
+  auto avg = [&](float ej, float pj) {
+    if constexpr (EDEV) {
+      if (follow) return pj;
+    }
+    return ema_one(ej, pj, omd);
+  };
   const bool vec_step = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
   const bool vec = vec_step && (((uintptr_t)e & 15) == 0);
   const unsigned long long end4 = base + ((end - base) & ~3ULL);
@@ -529,7 +552,7 @@ __global__ __launch_bounds__(ANT) void adam_decay_multi_kernel(AdamPackDecay A, 
       if (e) {
         f32x4 ev = *reinterpret_cast<f32x4*>(e + i);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) ev[j] = ema_one(ev[j], pv[j], omd);
+        for (int j = 0; j < 4; ++j) ev[j] = avg(ev[j], pv[j]);
         *reinterpret_cast<f32x4*>(e + i) = ev;
       }
     }
@@ -537,14 +560,14 @@ __global__ __launch_bounds__(ANT) void adam_decay_multi_kernel(AdamPackDecay A, 
       float pi = p[i];
       one(false, pi, g[i], m[i], v[i]);
       p[i] = pi;
-      if (e) e[i] = ema_one(e[i], pi, omd);
+      if (e) e[i] = avg(e[i], pi);
     }
   } else {
     for (unsigned long long i = base + threadIdx.x; i < end; i += ANT) {
       float pi = p[i];
       one(vec_step && i < end4, pi, g[i], m[i], v[i]);
       p[i] = pi;
-      if (e) e[i] = ema_one(e[i], pi, omd);
+      if (e) e[i] = avg(e[i], pi);
     }
   }
   if (A.amax[t]) block_amax_atomic<ANT>(am, A.amax[t]);
@@ -740,14 +763,17 @@ extern "C" int vg_adam_step_dev_clip(const VgAdamTensor* tensors, int count, dou
 
 // ---- weight decay inside the step, hyper-parameters on the device: the entry points -----------------------------------
 namespace {
+// EDEV (with `scalars` only): (float)(1 - decay) is read from the device word `ema_omd`, ema_decay is not used.
+template <bool EDEV = false>
 int adam_decay_launch(const VgAdamTensor* tensors, unsigned* const* flags, int count, double beta1, double beta2,
                       double eps, float step_size, float bc2s, float s2, float wdc, const float* scalars, hipStream_t st,
-                      float* const* ema, double ema_decay, const float* clip_record) {
+                      float* const* ema, double ema_decay, const float* clip_record, const float* ema_omd = nullptr) {
   const float omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);
   int i = 0;
   while (i < count) {
-    AdamPackDecay A;
+    std::conditional_t<EDEV, AdamPackDecayDev, AdamPackDecay> A;
     A.omd = (float)(1.0 - ema_decay);
+    if constexpr (EDEV) A.omd_dev = ema_omd;
     A.s2 = s2;
     A.wdc = wdc;
     A.count = 0;
@@ -770,7 +796,10 @@ int adam_decay_launch(const VgAdamTensor* tensors, unsigned* const* flags, int c
     }
     if (A.count == 0) break;
     A.first_block[A.count] = blocks;
-    if (scalars)
+    if constexpr (EDEV)
+      hipLaunchKernelGGL((adam_decay_multi_kernel<true, true>), dim3(blocks), dim3(ANT), 0, st, A, omb1, (float)beta2,
+                         omb2, 0.f, 0.f, (float)eps, scalars, clip_record);
+    else if (scalars)
       hipLaunchKernelGGL((adam_decay_multi_kernel<true>), dim3(blocks), dim3(ANT), 0, st, A, omb1, (float)beta2, omb2, 0.f,
                          0.f, (float)eps, scalars, clip_record);
     else
@@ -815,4 +844,12 @@ extern "C" int vg_adam_step_dev_decay(const VgAdamTensor* tensors, int count, do
     return VG_ERR_BAD_ARG;
   return adam_decay_launch(tensors, nonfinite, count, beta1, beta2, eps, 0.f, 0.f, 1.f, 0.f, scalars,
                            (hipStream_t)stream, ema, ema ? ema_decay : 0.5, clip_record);
+}
+
+extern "C" int vg_adam_step_dev_ema_dev(const VgAdamTensor* tensors, int count, double beta1, double beta2, double eps,
+                                        const float* scalars, unsigned* const* nonfinite, float* const* ema,
+                                        const float* ema_omd, const float* clip_record, void* stream) {
+  if (count < 0 || (count > 0 && !tensors) || !scalars || !ema || !ema_omd) return VG_ERR_BAD_ARG;
+  return adam_decay_launch<true>(tensors, nonfinite, count, beta1, beta2, eps, 0.f, 0.f, 1.f, 0.f, scalars,
+                                 (hipStream_t)stream, ema, 0.5, clip_record, ema_omd);
 }

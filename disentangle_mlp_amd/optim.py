@@ -34,6 +34,11 @@ traffic of its own.  Groups without decay make the launches they always made.
 ``HipAdam(capturable=True, device_hyper=True)``: every group's ``[lr, weight_decay]`` lives in a persistent device pair
 the step's prepare kernel reads (``vg_adam_prepare_dev``), so both may change between the replays of a captured step:
 set ``group["lr"]`` (or let a ``torch.optim.lr_scheduler`` do it) and call `sync_hyper` before the replay.
+
+``HipAdam(capturable=True, ema_decay=d, ema_decay_on_device=True)``: ``(float)(1 - d)`` lives in one persistent fp32
+device word the averaging step reads (``vg_adam_step_dev_ema_dev``), so the decay too may change between the replays of
+a captured step -- a warm-up: `set_ema_decay`, then `sync_hyper` before the replay.  Here ``d`` may be 0: the average
+then takes the bits of the weights.
 """
 import ctypes
 import math
@@ -91,17 +96,25 @@ class HipAdam(optim.Adam):
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, capturable=False,
                  nonfinite_guard=False, ema_decay=None, ema_targets=None, max_grad_norm=None, skip_nonfinite=False,
-                 decoupled_weight_decay=False, device_hyper=False):
+                 decoupled_weight_decay=False, device_hyper=False, ema_decay_on_device=False):
         self._words = None
         self.device_hyper = False
         if device_hyper and not capturable:
             raise ValueError("HipAdam: device_hyper=True keeps lr and weight decay on the device for a captured step; "
                              "it requires capturable=True")
         self._ema = None
+        self._ema_omd = None
+        if ema_decay_on_device and not capturable:
+            raise ValueError("HipAdam: ema_decay_on_device=True keeps the EMA decay on the device for a captured step; "
+                             "it requires capturable=True")
+        if ema_decay_on_device and ema_decay is None:
+            raise ValueError("HipAdam: ema_decay_on_device=True without ema_decay")
         self._clip_rec = None
         if max_grad_norm is not None and not (0.0 < float(max_grad_norm) < math.inf):      # (NaN fails both comparisons)
             raise ValueError(f"HipAdam: max_grad_norm must be finite and > 0, got {max_grad_norm!r}")
-        if ema_decay is not None and not (0.0 < float(ema_decay) < 1.0):      # (NaN fails both comparisons)
+        if ema_decay_on_device:
+            self._check_device_decay(ema_decay)
+        elif ema_decay is not None and not (0.0 < float(ema_decay) < 1.0):      # (NaN fails both comparisons)
             raise ValueError(f"HipAdam: ema_decay must lie in (0, 1), got {ema_decay!r}")
         if ema_decay is None and ema_targets is not None:
             raise ValueError("HipAdam: ema_targets without ema_decay")
@@ -156,6 +169,15 @@ class HipAdam(optim.Adam):
                         raise ValueError(f"HipAdam: ema_targets[{i}] is its parameter's own storage")
             self._ema_of = {p: i for i, p in enumerate(ps)}
             self._ema = ema
+            # the decay on the device: one persistent fp32 word holding (float)(1 - decay), allocated here and never
+            # replaced -- a captured step reads where the host later writes (`sync_hyper`); its prepare kernel is
+            # vg_adam_prepare_dev, so every group's [lr, weight_decay] pair exists from here on too
+            if ema_decay_on_device:
+                self._ema_omd = torch.zeros(1, dtype=torch.float32, device=ps[0].device)
+                self._ema_omd_written = None
+                for gi in range(len(self.param_groups)):
+                    self._hyper_words(gi)
+                self.sync_hyper()
         # clipping by global norm / skipping a non-finite step: the record [norm, coef, skip, skipped] and one fp64 slot
         # per 8192-element chunk of every parameter, allocated here and never replaced -- like `_words`, a captured step
         # writes where later readers read
@@ -210,11 +232,29 @@ class HipAdam(optim.Adam):
                 h[0].fill_(now[0])
                 h[1].fill_(now[1])
                 self._hyper_written[gi] = now
+        if self._ema_omd is not None and self.ema_decay != self._ema_omd_written:
+            self._ema_omd.fill_(1.0 - self.ema_decay)      # (rounded once to fp32: the kernels' (float)(1 - decay))
+            self._ema_omd_written = self.ema_decay
 
     # ---- weight EMA ------------------------------------------------------------------------------------------
     def _need_ema(self):
         if self._ema is None:
             raise RuntimeError("HipAdam: construct with ema_decay=... to track an EMA of the weights")
+
+    @staticmethod
+    def _check_device_decay(d):
+        if not (0.0 <= float(d) < 1.0):      # (NaN fails both comparisons)
+            raise ValueError(f"HipAdam: with ema_decay_on_device the decay must lie in [0, 1), got {d!r}")
+
+    def set_ema_decay(self, d):
+        """The decay of the next averaging steps, ``0 <= d < 1`` (0: the average takes the bits of the weights).  Needs
+        ``ema_decay_on_device=True``; the device word follows at the next `sync_hyper` -- every eager `step` calls it,
+        whoever replays a captured step calls it in front of the replay."""
+        self._need_ema()
+        if self._ema_omd is None:
+            raise RuntimeError("HipAdam: construct with ema_decay_on_device=True to change the EMA decay")
+        self._check_device_decay(d)
+        self.ema_decay = float(d)
 
     def ema_tensors(self):
         """The EMA tensors themselves, one per parameter in ``param_groups`` order (the step writes them in place)."""
@@ -548,7 +588,8 @@ class HipAdam(optim.Adam):
                 if self.device_scalars:
                     step_dev, scalars = self._device_state(gi, items[0][0].device)
                     # an eager step also stores its count in the device counter: replays may follow it
-                    if self.device_hyper or wd != 0.0:
+                    ema_dev = ema is not None and self._ema_omd is not None
+                    if self.device_hyper or wd != 0.0 or ema_dev:
                         hyper = self._hyper_words(gi)
                         if not capturing:
                             self.sync_hyper()      # (words that came into being just now)
@@ -559,7 +600,12 @@ class HipAdam(optim.Adam):
                         check(lib.vg_adam_prepare(float(step), step_dev.data_ptr(), 1 if capturing else 0,
                                                   float(group["lr"]), float(beta1), float(beta2), scalars.data_ptr(),
                                                   stream), "vg_adam_prepare")
-                    if wd != 0.0:
+                    if ema_dev:
+                        check(lib.vg_adam_step_dev_ema_dev(arr, len(items), float(beta1), float(beta2),
+                                                           float(group["eps"]), scalars.data_ptr(), flags, ema,
+                                                           self._ema_omd.data_ptr(), rec, stream),
+                              "vg_adam_step_dev_ema_dev")
+                    elif wd != 0.0:
                         check(lib.vg_adam_step_dev_decay(arr, len(items), float(beta1), float(beta2), float(group["eps"]),
                                                          scalars.data_ptr(), flags, ema, self.ema_decay or 0.0, rec,
                                                          stream), "vg_adam_step_dev_decay")

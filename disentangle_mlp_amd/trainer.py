@@ -26,6 +26,7 @@ summed with a single RCCL all-reduce (SUM, not mean: sum-reduced losses use loca
 sums, BCE is divided by the *global* batch), which reproduces the global-batch
 gradient.
 """
+import copy
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional
 
@@ -255,7 +256,7 @@ def _backward(losses):
 
 
 def _make_adam(params, lr, fused, capturable=False, nonfinite_guard=False, max_grad_norm=None, skip_nonfinite=False,
-               weight_decay=0.0, decoupled_weight_decay=False, device_hyper=False):
+               weight_decay=0.0, decoupled_weight_decay=False, device_hyper=False, ema=None):
     """Adam with the reference's defaults (new_betavaegan.py:49-50).  On the GPU the step runs on the
     hand-written kernel (optim.HipAdam, a torch.optim.Adam subclass: identical state_dict); ``capturable``:
     its scalars are formed on the device so that a whole iteration can be captured in a HIP graph;
@@ -263,8 +264,14 @@ def _make_adam(params, lr, fused, capturable=False, nonfinite_guard=False, max_g
     implementation -- unless ``max_grad_norm`` / ``skip_nonfinite`` (clipping by global norm, skipping a non-finite
     step: optim.HipAdam) is asked for: then it is a HipAdam there too, whose inherited step carries those semantics.
     ``weight_decay`` / ``decoupled_weight_decay``: torch.optim.Adam's, inside the fused step on the GPU; ``device_hyper``:
-    lr and weight decay in device words a captured step reads (optim.HipAdam)."""
+    lr and weight decay in device words a captured step reads (optim.HipAdam).  ``ema``: ``(decay, targets)`` of the one
+    optimizer whose step keeps the weight EMA (`_GraphedSteps._ema_setup`) -- a HipAdam with device scalars and the decay
+    in a device word, whether or not the iteration is captured."""
     decay = dict(weight_decay=weight_decay, decoupled_weight_decay=decoupled_weight_decay)
+    if ema is not None:
+        return HipAdam(params, lr=lr, capturable=True, nonfinite_guard=nonfinite_guard, max_grad_norm=max_grad_norm,
+                       skip_nonfinite=skip_nonfinite, device_hyper=device_hyper, ema_decay=ema[0], ema_targets=ema[1],
+                       ema_decay_on_device=True, **decay)
     if fused:
         return HipAdam(params, lr=lr, capturable=capturable, nonfinite_guard=nonfinite_guard,
                        max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, device_hyper=device_hyper, **decay)
@@ -318,6 +325,22 @@ def _loader_global_batch(loader, local_batch, world):
     ranks); for a foreign loader every rank is assumed to hold an equal share."""
     gb = getattr(loader, "last_global_batch", None)
     return int(gb) if gb else int(local_batch) * world
+
+
+def ema_warmup(decay, start_iteration=0):
+    """A per-iteration EMA decay for the trainers' ``ema_decay=``: 0 -- the average follows the weights -- before
+    ``start_iteration``, then ``min(decay, (1 + n) / (10 + n))`` with ``n = iteration - start_iteration``: the early
+    iterations weigh little, so the random initialisation does not sit in the average for thousands of steps."""
+    decay, start = float(decay), int(start_iteration)
+    if not 0.0 < decay < 1.0:      # (NaN fails both comparisons)
+        raise ValueError(f"ema_warmup: decay must lie in (0, 1), got {decay!r}")
+    if start < 0 or start != start_iteration:
+        raise ValueError(f"ema_warmup: start_iteration must be an integer >= 0, got {start_iteration!r}")
+
+    def schedule(iteration):
+        n = int(iteration) - start
+        return 0.0 if n < 0 else min(decay, (1.0 + n) / (10.0 + n))
+    return schedule
 
 
 GRAPH_DEFAULT = __import__("os").environ.get("VG_GRAPH", "1") != "0"     # 0: trainers never capture (every step eager)
@@ -644,6 +667,8 @@ class _GraphedSteps:
         if self.beta_schedule is not None:
             self.beta = float(self.beta_schedule(self.iteration))
         self._sync_beta()
+        if self.ema_schedule is not None:      # the decay word follows in front of the launches (`HipAdam.sync_hyper`)
+            self._ema_pair()[1].set_ema_decay(float(self.ema_schedule(self.iteration)))
 
     def _end_step(self):
         for sched in self.lr_schedulers.values():      # once per iteration: EG's two optimizer steps share one lr
@@ -672,7 +697,7 @@ class _GraphedSteps:
         extra = {}
         if self.lr_schedulers:
             extra["lr_schedulers"] = {n: s.state_dict() for n, s in self.lr_schedulers.items()}
-        if self.lr_schedulers or self.beta_schedule is not None:
+        if self.lr_schedulers or self.beta_schedule is not None or self.ema_schedule is not None:
             extra["iteration"] = self.iteration
         return extra
 
@@ -693,6 +718,114 @@ class _GraphedSteps:
             self.beta = float(self.beta_schedule(max(self.iteration - 1, 0)))      # (the last step's; the next step sets its own)
 
     _checkpoint_optimizer_keys = {}
+
+    # ---- weight EMA of the generating network --------------------------------------------------------------------
+    ema_model = None          # the shadow network: a deep copy whose parameters the averaging Adam step writes
+    ema_schedule = None       # callable iteration -> decay in [0, 1), or None (a constant decay)
+    _ema_names = None         # (attribute of the averaged network, of its optimizer, checkpoint key of the shadow)
+
+    def _ema_setup(self, ema_decay, net, fused_adam):
+        """``ema_decay`` of a trainer's constructor -> the ``ema`` argument of `_make_adam` (None: no average).  Builds
+        `ema_model`: a ``copy.deepcopy`` of ``net`` as it is now (on its device; a deep copy draws no random number, so
+        the initialisation stream is the reference's), parameters without gradient, BatchNorm buffers its own."""
+        if ema_decay is None:
+            return None
+        if callable(ema_decay):
+            schedule, first = ema_decay, float(ema_decay(0))
+            if not 0.0 <= first < 1.0:
+                raise ValueError(f"ema_decay: the schedule must return a decay in [0, 1), got {first!r} at iteration 0")
+        else:
+            schedule, first = None, float(ema_decay)
+            if not 0.0 < first < 1.0:
+                raise ValueError(f"ema_decay must be a float in (0, 1) or a callable iteration -> [0, 1), got {ema_decay!r}")
+        if self.device.type != "cuda" or not fused_adam:
+            why = f"its device is {self.device.type!r}" if self.device.type != "cuda" else "fused_adam=False"
+            raise ValueError("ema_decay: the average is kept inside the fused Adam step (optim.HipAdam), and this "
+                             f"trainer's optimizers are torch.optim.Adam: {why}")
+        self.ema_schedule = schedule
+        self.ema_model = copy.deepcopy(net)
+        for p in self.ema_model.parameters():
+            p.requires_grad_(False)
+        return first, list(self.ema_model.parameters())
+
+    def _ema_pair(self):
+        if self.ema_model is None:
+            raise ValueError(f"{type(self).__name__}: construct with ema_decay=... to keep and use an average of the weights")
+        return getattr(self, self._ema_names[0]), getattr(self, self._ema_names[1])
+
+    def _sampling_net(self, use_ema):
+        """The network that samples and reconstructs: the live one, or -- ``use_ema`` -- the shadow."""
+        if not use_ema:
+            return getattr(self, self._ema_names[0])
+        self._ema_pair()
+        return self.ema_model
+
+    @torch.no_grad()
+    def reset_ema(self):
+        """Shadow <- the live network as it is now: weights and BatchNorm buffers, copied into the existing tensors."""
+        live, _ = self._ema_pair()
+        src = live.state_dict()
+        for k, v in self.ema_model.state_dict().items():
+            v.copy_(src[k])
+
+    @torch.no_grad()
+    def _ema_restore(self, ck):
+        """After the live network was loaded: the shadow from its checkpoint key -- copied into the existing tensors, a
+        captured iteration writes into them -- or, the key absent, from the live network (`reset_ema`)."""
+        if self.ema_model is None:
+            return
+        sd = ck.get(self._ema_names[2])
+        if sd is None:
+            return self.reset_ema()
+        mine = self.ema_model.state_dict()
+        if set(mine) != set(sd):
+            raise KeyError(f"{self._ema_names[2]}: keys differ from the shadow network's: "
+                           f"{sorted(set(mine) ^ set(sd))[:4]}")
+        for k, v in mine.items():
+            v.copy_(sd[k])
+
+    def _ema_checkpoint(self):
+        """The additional checkpoint key -- present only with an average: the shadow's plain state_dict."""
+        return {} if self.ema_model is None else {self._ema_names[2]: self.ema_model.state_dict()}
+
+    @torch.no_grad()
+    def recalibrate_ema_bn(self, batches, max_batches=None, eps_generator=None):
+        """Standing statistics: BatchNorm running statistics that belong to the averaged weights, for eval-mode use of
+        `ema_model` (``model.eval_mode(trainer.ema_model)``).  The shadow runs its full forward in train mode over
+        ``batches`` (an iterable of input batches, or of ``(batch, ...)`` tuples as a loader yields them: images for a
+        VAE shadow, latents for a generator); for batch k every BatchNorm has ``momentum = 1 / k``, so afterwards each
+        running statistic is the arithmetic mean of the batch statistics (torch's ``momentum=None``).  The momenta are
+        restored afterwards, also after an exception; the live network is not touched.  A VAE shadow draws its latent
+        noise from ``eps_generator`` (default: a generator of the shadow's device seeded with 0 -- no training stream is
+        consumed).  Returns the number of batches used."""
+        self._ema_pair()
+        net = self.ema_model
+        bns = [m for m in net.modules() if isinstance(m, _model._HipBatchNormMixin)]
+        momenta = [m.momentum for m in bns]
+        is_vae = isinstance(net, VAE)
+        if is_vae and eps_generator is None:
+            eps_generator = torch.Generator(device=self.device)
+            eps_generator.manual_seed(0)
+        was_training = net.training
+        k = 0
+        try:
+            net.train()
+            for batch in batches:
+                if max_batches is not None and k >= max_batches:
+                    break
+                x = (batch[0] if isinstance(batch, (tuple, list)) else batch).to(self.device)
+                k += 1
+                for m in bns:
+                    m.momentum = 1.0 / k
+                if is_vae:
+                    net(x, torch.randn(x.size(0), self.opt.n_hidden, device=self.device, generator=eps_generator))
+                else:
+                    net(x)
+        finally:
+            for m, mom in zip(bns, momenta):
+                m.momentum = mom
+            net.train(was_training)
+        return k
 
     def _host_state_key(self):
         """Host-side switches a capture freezes besides the shapes: part of every capture key, so that flipping one
@@ -772,9 +905,19 @@ class BetaVAEGANTrainer(_GraphedSteps):
     ``decoupled_weight_decay`` as torch.optim.Adam's, inside the fused step.  ``device_hyper`` (default: on exactly when a
     scheduler or a beta schedule is given): lr, weight decay and beta live in device words the captured kernels read, so a
     value that changes every iteration still replays ONE graph.  `set_lr` / `set_beta`: the same by hand.  Data parallel:
-    every rank evaluates the same schedule on the same iteration counter; nothing is exchanged."""
+    every rank evaluates the same schedule on the same iteration counter; nothing is exchanged.
+
+    ``ema_decay`` (default: none -- then every launch, capture key and checkpoint key is what it was): a float in (0, 1) or
+    a callable ``iteration -> decay in [0, 1)`` (`ema_warmup`), evaluated with `iteration` at the start of every `step`.
+    `ema_model` is then a shadow of netEG -- a deep copy made once, never replaced -- whose parameters the phase-3 Adam
+    step moves, ``e <- e + (1 - decay)(p - e)``, inside its own kernel (the phase-2 step leaves them alone: one average
+    per iteration).  The decay lives in a device word, so a value that changes every iteration still replays ONE graph.
+    The discriminator is not averaged.  ``fit`` / ``evaluate(use_ema=True)`` sample, reconstruct and score through the
+    shadow; `recalibrate_ema_bn` gives it BatchNorm running statistics of its own for eval-mode use; checkpoints carry
+    it under ``encoder_decoder_ema``.  Data parallel: every rank forms the same average from the same weights."""
 
     _optimizer_names = ("optimizerEG", "optimizerD")
+    _ema_names = ("netEG", "optimizerEG", "encoder_decoder_ema")
     _checkpoint_optimizer_keys = {"optimizerEG": "encoder_decoder_optimizer", "optimizerD": "discriminator_optimizer"}
 
     def __init__(self, device="cuda", seed=999, beta=25.0, lr=1e-3, opt: Optional[ModelOpt] = None,
@@ -782,7 +925,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
                  graph: Optional[bool] = None, nonfinite_guard: Optional[bool] = None,
                  max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False,
                  lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0, decoupled_weight_decay: bool = False,
-                 device_hyper: Optional[bool] = None):
+                 device_hyper: Optional[bool] = None, ema_decay=None):
         self.opt = opt or ModelOpt()
         self.device = torch.device(device)
         _use_tuned_gemms(self.device)
@@ -805,7 +948,9 @@ class BetaVAEGANTrainer(_GraphedSteps):
         clip = dict(max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
         clip.update(self._schedule_args(lr_scheduler, beta_schedule, device_hyper, weight_decay, decoupled_weight_decay,
                                         fused and capturable))
-        self.optimizerEG = _make_adam(self.netEG.parameters(), lr, fused, capturable, self.nonfinite_guard, **clip)   # :49 (hard-coded 1e-3 there)
+        ema = self._ema_setup(ema_decay, self.netEG, fused_adam)
+        self.optimizerEG = _make_adam(self.netEG.parameters(), lr, fused, capturable, self.nonfinite_guard, ema=ema,
+                                      **clip)                                                                         # :49 (hard-coded 1e-3 there)
         self.optimizerD = _make_adam(self.netD.parameters(), lr, fused, capturable, self.nonfinite_guard, **clip)     # :50
         self._make_schedulers()
         self.flat_eg = FlatGrads(self.netEG.parameters(), silent=shadowed_bias_params(self.netEG)) if self.dp else None
@@ -954,7 +1099,10 @@ class BetaVAEGANTrainer(_GraphedSteps):
         self._exchange(self.flat_eg)
         if grad_hook:
             grad_hook("EG2", netEG)
-        self.optimizerEG.step()
+        if self.ema_model is not None:
+            self.optimizerEG.step(update_ema=False)          # one average per iteration: phase 3 forms it
+        else:
+            self.optimizerEG.step()
         ops.invalidate_packed_filters(self._eg_params)
         prepack("eg")
         acc.reset()
@@ -1015,7 +1163,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
     # -- the experiment script's ``__main__`` (new_betavaegan.py:211-267) -----------------
     def fit(self, loader, epochs, start_epoch=0, model_path=None, label_rng=None, calc_fid=False, n_samples=1000,
             fid_path_recons=None, fid_path_pretrained=None, get_fid=None, log=None, max_iterations=None, verbose=True,
-            fid_on_device=False, fid_inception="", fid_feature_extractor=None):
+            fid_on_device=False, fid_inception="", fid_feature_extractor=None, use_ema=False):
         """The training half of the reference's ``__main__`` (new_betavaegan.py:218-246): per epoch ``train(epoch)``
         (`train_epoch`), the checkpoint ``{model_path}/model_{epoch+1}.tar`` (:222-228), optionally
         ``generate_fid_samples`` + ``get_fid`` (:231-235), the printed line (:237-238) and the logger row (:241-246:
@@ -1028,10 +1176,13 @@ class BetaVAEGANTrainer(_GraphedSteps):
         ``fid_path_recons`` / ``get_fid`` are not used.  The network comes from ``fid_inception`` (as `fid.get_fid`'s
         ``inception``) or ``fid_feature_extractor``, is built once and kept for the whole call.  The default keeps the
         reference's route, including its mismatch: the samples are written as ``.pdf`` while ``get_fid`` looks for
-        ``*.jpg`` / ``*.png`` (utils.py:26 vs scoring/fid.py:293), so with the defaults that route finds no image."""
+        ``*.jpg`` / ``*.png`` (utils.py:26 vs scoring/fid.py:293), so with the defaults that route finds no image.
+
+        ``use_ema=True`` (a trainer with ``ema_decay``): the FID samples of both routes come from `ema_model`."""
         import os
         from . import image_io
         rows = []
+        net = self._sampling_net(use_ema)
         fid_extractor = self._fid_extractor(fid_inception, fid_feature_extractor) if calc_fid and fid_on_device else None
         for epoch in range(start_epoch, epochs):
             enc_loss, dec_loss, dis_loss, dx = self.train_epoch(loader, label_rng=label_rng, max_iterations=max_iterations)
@@ -1042,12 +1193,12 @@ class BetaVAEGANTrainer(_GraphedSteps):
                         self.save(os.path.join(model_path, f"model_{epoch + 1}.tar"), epoch + 1)
                     if calc_fid and fid_on_device:
                         from .fid import get_fid_of_generator
-                        fid = get_fid_of_generator(self.netEG.decode, n_samples, self.opt.n_hidden, fid_path_pretrained,
+                        fid = get_fid_of_generator(net.decode, n_samples, self.opt.n_hidden, fid_path_pretrained,
                                                    feature_extractor=fid_extractor, device=self.device)
                     elif calc_fid:
                         if get_fid is None:
                             from .fid import get_fid
-                        image_io.generate_fid_samples(self.netEG.decode, epoch, n_samples, self.opt.n_hidden,
+                        image_io.generate_fid_samples(net.decode, epoch, n_samples, self.opt.n_hidden,
                                                       fid_path_recons, device=self.device)
                         fid = get_fid(fid_path_recons, fid_path_pretrained)
                 if verbose:
@@ -1075,7 +1226,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
     def evaluate(self, load_paths, test_loader=None, start_epoch=0, calc_fid=False, n_samples=1000, fid_path_samples=None,
                  fid_path_pretrained=None, get_fid=None, test_recons=False, test_results_path_recons=None,
                  test_results_path_originals="", test_samples=False, test_results_path_samples=None,
-                 fid_on_device=False, fid_inception="", fid_feature_extractor=None, eval_mode=False):
+                 fid_on_device=False, fid_inception="", fid_feature_extractor=None, eval_mode=False, use_ema=False):
         """The evaluation half (new_betavaegan.py:248-267): for every checkpoint of ``load_paths`` -- load it, renumber
         its epoch the way the reference does so that files of several checkpoints do not overwrite each other (:252-254),
         then FID samples + score (:256-259), one grid of test reconstructions with ``nrow=1`` (+ the originals, :260-263)
@@ -1084,32 +1235,36 @@ class BetaVAEGANTrainer(_GraphedSteps):
         ``.eval()``; ``eval_mode=True`` decodes and reconstructs inside
         ``model.eval_mode(self.netEG)`` instead (running statistics; the network is back in training mode afterwards).
         Returns one dict per checkpoint.  ``fid_on_device`` / ``fid_inception`` /
-        ``fid_feature_extractor``: as in `fit` -- the FID straight from the decoder, no sample files."""
+        ``fid_feature_extractor``: as in `fit` -- the FID straight from the decoder, no sample files.  ``use_ema=True`` (a
+        trainer with ``ema_decay``): everything above samples and reconstructs through `ema_model` -- loaded from the
+        checkpoint's ``encoder_decoder_ema``, or equal to the live network when the checkpoint has none -- and
+        ``eval_mode`` then applies to it (see `recalibrate_ema_bn`)."""
         from . import image_io
         out, tmp_epoch = [], 0
+        net = self._sampling_net(use_ema)
         fid_extractor = self._fid_extractor(fid_inception, fid_feature_extractor) if calc_fid and fid_on_device else None
         for m in load_paths:
             epoch = self.load(m)
             epoch = epoch if epoch != tmp_epoch and tmp_epoch < epoch else tmp_epoch + 1
             tmp_epoch = epoch
             res = {"path": m, "epoch": epoch, "FID": "N/A"}
-            with torch.no_grad(), _model.eval_mode(*((self.netEG,) if eval_mode else ())):
+            with torch.no_grad(), _model.eval_mode(*((net,) if eval_mode else ())):
                 if calc_fid and fid_on_device:
                     from .fid import get_fid_of_generator
-                    res["FID"] = get_fid_of_generator(self.netEG.decode, n_samples, self.opt.n_hidden, fid_path_pretrained,
+                    res["FID"] = get_fid_of_generator(net.decode, n_samples, self.opt.n_hidden, fid_path_pretrained,
                                                       feature_extractor=fid_extractor, device=self.device)
                 elif calc_fid:
                     if get_fid is None:
                         from .fid import get_fid
-                    image_io.generate_fid_samples(self.netEG.decode, epoch, n_samples, self.opt.n_hidden, fid_path_samples,
+                    image_io.generate_fid_samples(net.decode, epoch, n_samples, self.opt.n_hidden, fid_path_samples,
                                                   device=self.device)
                     res["FID"] = get_fid(fid_path_samples, fid_path_pretrained)
                 if test_recons:
-                    image_io.gen_reconstructions(lambda x: self.netEG(x.to(self.device))[0], test_loader, epoch,
+                    image_io.gen_reconstructions(lambda x: net(x.to(self.device))[0], test_loader, epoch,
                                                  test_results_path_recons, nrow=1,
                                                  path_for_originals=test_results_path_originals, device=self.device)
                 if test_samples:
-                    image_io.generate_samples(self.netEG.decode, start_epoch, 5, self.opt.n_hidden,
+                    image_io.generate_samples(net.decode, start_epoch, 5, self.opt.n_hidden,
                                               test_results_path_samples, nrow=1, device=self.device)
             out.append(res)
         return out
@@ -1125,6 +1280,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
             "encoder_decoder_optimizer": self.optimizerEG.state_dict(),
             "discriminator_optimizer": self.optimizerD.state_dict(),
             **self._schedule_checkpoint(),       # (additional keys, only when a schedule exists)
+            **self._ema_checkpoint(),            # (encoder_decoder_ema, only with an average)
         }
 
     def save(self, path, epoch, legacy_format=False):
@@ -1142,6 +1298,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
         self.optimizerEG.load_state_dict(ck["encoder_decoder_optimizer"])
         self.optimizerD.load_state_dict(ck["discriminator_optimizer"])
         self._schedule_restore(ck)
+        self._ema_restore(ck)
         self.clear_nonfinite()                               # a good checkpoint is the way back from a NonFiniteError
         return ck["epoch"]
 
@@ -1171,6 +1328,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
             if isinstance(opt, HipAdam):
                 opt.refresh_weight_bounds()
         self._schedule_restore(ck, in_place=True)
+        self._ema_restore(ck)
         self.clear_nonfinite()
         return ck["epoch"]
 
@@ -1178,16 +1336,18 @@ class BetaVAEGANTrainer(_GraphedSteps):
 class VAETrainer(_GraphedSteps):
     """new_vae.py:33-37 construction, :39-48 loss, :53-59 step.  ``graph``, ``max_grad_norm``, ``skip_nonfinite``, and the
     schedule arguments (``lr_scheduler``, ``beta_schedule``, ``weight_decay``, ``decoupled_weight_decay``,
-    ``device_hyper``): as BetaVAEGANTrainer."""
+    ``device_hyper``): as BetaVAEGANTrainer.  ``ema_decay``: as there, of the one network -- `ema_model` shadows `model`,
+    the checkpoint key is ``VAE_model_ema``."""
 
     _optimizer_names = ("optimizer",)
+    _ema_names = ("model", "optimizer", "VAE_model_ema")
     _checkpoint_optimizer_keys = {"optimizer": "optimizer"}
 
     def __init__(self, device="cuda", seed=999, beta=1.0, lr=3e-3, opt: Optional[ModelOpt] = None,
                  fused_adam: bool = True, capturable: Optional[bool] = None, graph: Optional[bool] = None,
                  nonfinite_guard: Optional[bool] = None, max_grad_norm: Optional[float] = None,
                  skip_nonfinite: bool = False, lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0,
-                 decoupled_weight_decay: bool = False, device_hyper: Optional[bool] = None):
+                 decoupled_weight_decay: bool = False, device_hyper: Optional[bool] = None, ema_decay=None):
         self.opt = opt or ModelOpt()
         self.device = torch.device(device)
         _use_tuned_gemms(self.device)
@@ -1205,7 +1365,8 @@ class VAETrainer(_GraphedSteps):
         hyper = self._schedule_args(lr_scheduler, beta_schedule, device_hyper, weight_decay, decoupled_weight_decay,
                                     fused and capturable)
         self.optimizer = _make_adam(self.model.parameters(), lr, fused, capturable, self.nonfinite_guard,
-                                    max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, **hyper)
+                                    max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite,
+                                    ema=self._ema_setup(ema_decay, self.model, fused_adam), **hyper)
         self._make_schedulers()
         self.flat = FlatGrads(self.model.parameters(), silent=shadowed_bias_params(self.model)) if self.world > 1 else None
         self.latent_generator = _latent_generator(self.device, seed, _dist_rank())
@@ -1274,7 +1435,7 @@ class VAETrainer(_GraphedSteps):
 
     def checkpoint(self, epoch):
         return {"epoch": epoch, "VAE_model": self.model.state_dict(), "optimizer": self.optimizer.state_dict(),
-                **self._schedule_checkpoint()}
+                **self._schedule_checkpoint(), **self._ema_checkpoint()}
 
 
 class GANTrainer(_GraphedSteps):
@@ -1283,16 +1444,18 @@ class GANTrainer(_GraphedSteps):
     gradient exchange (SUM) per optimizer step, BCE divided by the global batch.  ``graph``: as
     BetaVAEGANTrainer; so are ``max_grad_norm``, ``skip_nonfinite`` and the schedule arguments (``lr_scheduler``,
     ``weight_decay``, ``decoupled_weight_decay``, ``device_hyper``; there is no KL term, so a ``beta_schedule`` is a
-    TypeError)."""
+    TypeError).  ``ema_decay``: as BetaVAEGANTrainer, of the generator -- `ema_model` shadows `netG`, the checkpoint key is
+    ``netG_ema``; the discriminator is not averaged."""
 
     _optimizer_names = ("optimizerG", "optimizerD")
+    _ema_names = ("netG", "optimizerG", "netG_ema")
     _checkpoint_optimizer_keys = {"optimizerG": "G_trainer", "optimizerD": "D_trainer"}
 
     def __init__(self, device="cuda", seed=999, lr=3e-3, opt: Optional[ModelOpt] = None, fused_adam: bool = True,
                  data_parallel: Optional[bool] = None, graph: Optional[bool] = None,
                  nonfinite_guard: Optional[bool] = None, max_grad_norm: Optional[float] = None,
                  skip_nonfinite: bool = False, lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0,
-                 decoupled_weight_decay: bool = False, device_hyper: Optional[bool] = None):
+                 decoupled_weight_decay: bool = False, device_hyper: Optional[bool] = None, ema_decay=None):
         self.opt = opt or ModelOpt()
         self.device = torch.device(device)
         _use_tuned_gemms(self.device)
@@ -1311,7 +1474,8 @@ class GANTrainer(_GraphedSteps):
         clip = dict(max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
         clip.update(self._schedule_args(lr_scheduler, beta_schedule, device_hyper, weight_decay, decoupled_weight_decay,
                                         fused and self.graph, has_beta=False))
-        self.optimizerG = _make_adam(self.netG.parameters(), lr, fused, self.graph, self.nonfinite_guard, **clip)
+        self.optimizerG = _make_adam(self.netG.parameters(), lr, fused, self.graph, self.nonfinite_guard,
+                                     ema=self._ema_setup(ema_decay, self.netG, fused_adam), **clip)
         self.optimizerD = _make_adam(self.netD.parameters(), lr, fused, self.graph, self.nonfinite_guard, **clip)
         self._make_schedulers()
         self.flat_g = FlatGrads(self.netG.parameters(), silent=shadowed_bias_params(self.netG)) if self.dp else None
@@ -1436,4 +1600,4 @@ class GANTrainer(_GraphedSteps):
     def checkpoint(self, epoch):
         return {"epoch": epoch, "netG": self.netG.state_dict(), "netD": self.netD.state_dict(),
                 "G_trainer": self.optimizerG.state_dict(), "D_trainer": self.optimizerD.state_dict(),
-                **self._schedule_checkpoint()}
+                **self._schedule_checkpoint(), **self._ema_checkpoint()}

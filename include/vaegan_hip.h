@@ -48,7 +48,7 @@ extern "C" {
  * Entry points that are only ADDED (the four of csrc/fid_front.hip; vg_bn_eval_coeffs, vg_bn_eval_act_bwd;
  * vg_adam_step_ema, vg_adam_step_dev_ema; vg_grad_sumsq_partials, vg_grad_sumsq_multi, vg_grad_clip_finalize,
  * vg_adam_step_clip, vg_adam_step_dev_clip; vg_adam_prepare_dev, vg_adam_step_decay, vg_adam_step_dev_decay,
- * vg_reparam_kl_fwd_dev, vg_reparam_kl_bwd_dev) change
+ * vg_reparam_kl_fwd_dev, vg_reparam_kl_bwd_dev; vg_adam_step_dev_ema_dev) change
  * nothing an existing caller sees and keep the version: a binding that needs them and finds a library without them
  * fails at the symbol lookup, as loudly. */
 #define VG_ABI_VERSION 7
@@ -587,6 +587,19 @@ int vg_adam_step_decay(const VgAdamTensor* tensors, int count, double lr, double
 int vg_adam_step_dev_decay(const VgAdamTensor* tensors, int count, double beta1, double beta2, double eps,
                            const float* scalars, unsigned* const* nonfinite, float* const* ema, double ema_decay,
                            const float* clip_record, void* stream);
+/* The EMA decay on the DEVICE: vg_adam_step_dev_decay with (float)(1 - decay) read from the device word `ema_omd` (one
+ * fp32, an ordinary load, uniform over the grid) instead of formed from a host double -- a warm-up writes it between
+ * the replays of a captured step.  Per element, after p is updated:
+ *   *ema_omd == 1.0f   e <- p_new            the bits of p ("follow the weights": e + 1 (p - e) is not p in fp32)
+ *   otherwise          e <- e + *ema_omd * (p_new - e)      as above; 0.0f follows the formula (e stays, p finite)
+ * `scalars` from vg_adam_prepare_dev (all four words are read); `nonfinite`, `clip_record` and single ema[i] entries
+ * may be NULL as there.  With the word holding (float)(1.0 - d) for a d in (0, 1): p, m, v, the averages, amax, the flag
+ * words and the record are bit for bit those of vg_adam_step_dev_ema / _dev_clip / _dev_decay with ema_decay = d.  A
+ * skipped step (the record's skip word up) stores nothing to an average.  VG_ERR_BAD_ARG before any launch: ema or
+ * ema_omd NULL (the entry points above step without an average), and what vg_adam_step_dev_decay rejects. */
+int vg_adam_step_dev_ema_dev(const VgAdamTensor* tensors, int count, double beta1, double beta2, double eps,
+                             const float* scalars, unsigned* const* nonfinite, float* const* ema, const float* ema_omd,
+                             const float* clip_record, void* stream);
 
 /* ---- image I/O either side of the step -----------------
  * Input pipeline of dataloader/dataset.py:37-43 (ToTensor + Normalize(mean, std) of a

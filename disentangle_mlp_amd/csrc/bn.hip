@@ -6,6 +6,8 @@
 // Replaces F.batch_norm(training=True) + activation reached from
 // /root/reference/models/model.py:451-458 (encoder), :462,468 (heads), :492
 // (decoder preprocess), :496-505 (decoder), :390-400 (discriminator).
+#include <atomic>
+
 #include "common.hpp"
 #include "vaegan_hip.h"
 
@@ -312,6 +314,171 @@ __global__ __launch_bounds__(ONE_NT) void bn_bwd_onepass_kernel(const float* __r
   if (gx_amax) block_amax_atomic<ONE_NT>(am, gx_amax);      // max |gx| for the fp16-plane consumers (bn_apply_kernel)
 }
 
+// The one pass for channels LARGER than a workgroup's registers (the 32 x 32 and 64 x 64 layers at B = 128: 131 072 and
+// 524 288 elements per channel): a TEAM of T workgroups owns a channel.  Member j holds the virtual elements
+// [j * cap, (j + 1) * cap), cap = ONE_NT * 4 * NV, exactly as the kernel above holds a whole channel (clamped unconditional
+// loads, mask, index paths), forms g_pre in place and its two fp64 sums, publishes them, collects the T pairs of its team,
+// adds them in member order 0 .. T - 1 -- every member gets the same c1, c2 bit for bit, whatever the timing -- and writes
+// its gx from registers.  Member 0 writes dgamma / dbeta.
+//
+// The grid is persistent: teams * T <= the device's compute units, one 1024-thread workgroup on each (128 VGPRs x 16
+// wavefronts fill a CU's register file), team t works off channels t, t + teams, ... one per round; a team whose round
+// has no channel left stops, nobody waits on it.  Every workgroup of the grid is resident at once, so a member only ever
+// waits for workgroups that are running (or about to: the grid never exceeds the CUs).
+//
+// Exchange: "the data is the flag".  A member's two doubles are four 8-byte granules {tag = round + 1, 32 bits of value},
+// each ONE relaxed agent-scope atomic store; wavefront 0 of every member re-reads its team's 4 * T (<= 64) granules, one per
+// lane, with relaxed agent-scope atomic loads until every tag matches.  No flag, no fence, no plain store or scalar load
+// of a handed-off word, nothing that depends on which XCD a member runs on.  Two granule sets per team, by round parity:
+// a member stores round r + 1 only after it has seen every team-mate's round r, and a team-mate stores round r only after
+// it has read round r - 1 -- the set that round r + 1 overwrites.  xch: [status word, 12 bytes of padding][teams][2][T][4]
+// granules, zeroed by the launch function before EVERY launch (team_zero_kernel: a kernel node under capture).
+//
+// Bounded spin: a sweep gives up after about a second of wall clock (a resident partner answers in microseconds), sets the
+// status word, and the workgroup goes on with NaN for c1 / c2: its gx slices, and member 0's dgamma / dbeta, are NaN from
+// there on (it sweeps no more, but still publishes, so that it costs its team-mates one bound, not one per round).  The
+// trainers' non-finite guard stops the run; the kernel cannot hang.
+typedef __attribute__((address_space(1))) unsigned long long gu64;
+typedef __attribute__((address_space(1))) unsigned gu32;
+constexpr int TEAM_MAX_T = 16;                   // 4 * T granules: one per lane of the sweeping wavefront
+constexpr int TEAM_MAX_WGS = 1024;               // the exchange block is sized for grids up to this (vg_bn_workspace_bytes)
+constexpr size_t TEAM_HDR = 16;                  // status word, padded: the granules stay 16-byte aligned
+constexpr long long TEAM_SPIN_TICKS = 100000000; // wall_clock64() counts at 100 MHz: one second
+size_t team_block_bytes(int grid) { return TEAM_HDR + (size_t)grid * 2 * 4 * sizeof(unsigned long long); }
+
+__global__ __launch_bounds__(NT) void team_zero_kernel(unsigned long long* __restrict__ xch, int words) {
+  const int i = blockIdx.x * NT + threadIdx.x;
+  if (i < words) xch[i] = 0ull;
+}
+
+template <int NV>
+__global__ __launch_bounds__(ONE_NT) void bn_bwd_team_kernel(const float* __restrict__ x, const float* __restrict__ gy,
+                                                             const float* __restrict__ gamma,
+                                                             const float* __restrict__ beta,
+                                                             const float* __restrict__ mean,
+                                                             const float* __restrict__ invstd, float* __restrict__ gx,
+                                                             float* __restrict__ dgamma, float* __restrict__ dbeta, int B,
+                                                             int C, int HW, int act, unsigned* __restrict__ gx_amax, int T,
+                                                             int teams, unsigned long long* xch) {
+  __shared__ double red[ONE_NT / 64];
+  __shared__ float s_c[2];
+  __shared__ int s_failed;
+  const bool accp = (act & 0x100) != 0;
+  act &= 0xff;
+  const int team = blockIdx.x / T, member = blockIdx.x - team * T;
+  const int total = B * HW;
+  const int hw_shift = (HW & (HW - 1)) == 0 ? __builtin_ctz(HW) : -1;
+  const int v_base = member * (ONE_NT * 4 * NV);
+  gu32* status = (gu32*)xch;
+  gu64* sets = (gu64*)xch + TEAM_HDR / sizeof(unsigned long long) + (size_t)team * 2 * T * 4;
+  unsigned am = 0;
+  bool failed = false;
+  int round = 0;
+  for (int c = team; c < C; c += teams, ++round) {
+    const float mu = mean[c], is = invstd[c], sc = gamma[c] * is, sh = beta[c] - mu * sc;
+    float4 xv[NV], gv[NV];
+    // the offsets are computed again for the stores: 2 * NV registers of them would not fit next to the 8 * NV of data
+    auto offset_of = [&](int j) -> size_t {
+      const int v = v_base + (j * ONE_NT + (int)threadIdx.x) * 4;
+      const int vc = min(v, total - 4);                     // clamped, unconditional; masked below
+      const int b = hw_shift >= 0 ? (vc >> hw_shift) : vc / HW, hw = vc - b * HW;
+      return ((size_t)b * C + c) * HW + hw;
+    };
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      const size_t off = offset_of(j);
+      xv[j] = *reinterpret_cast<const float4*>(x + off);
+      gv[j] = *reinterpret_cast<const float4*>(gy + off);
+    }
+    double s1 = 0.0, s2 = 0.0;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      const bool ok = v_base + (j * ONE_NT + (int)threadIdx.x) * 4 < total;
+      float* xp = reinterpret_cast<float*>(&xv[j]);
+      float* gp = reinterpret_cast<float*>(&gv[j]);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float g = ok ? act_grad(fmaf(xp[e], sc, sh), gp[e], act) : 0.f;
+        gp[e] = g;                                          // g_pre replaces gy
+        s1 += g;
+        s2 += (double)(g * ((xp[e] - mu) * is));
+      }
+    }
+    const double t1 = block_sum<ONE_NT>(s1, red);
+    const double t2 = block_sum<ONE_NT>(s2, red);
+    if (threadIdx.x < 64) {                                 // wavefront 0: publish, sweep, add in member order
+      const int lane = threadIdx.x;
+      const unsigned tag = (unsigned)round + 1u;
+      gu64* set = sets + (size_t)(round & 1) * T * 4;
+      if (lane == 0) {
+        const unsigned long long b1 = (unsigned long long)__double_as_longlong(t1);
+        const unsigned long long b2 = (unsigned long long)__double_as_longlong(t2);
+        const unsigned long long hi = (unsigned long long)tag << 32;
+        gu64* mine = set + member * 4;
+        __hip_atomic_store(mine + 0, hi | (b1 & 0xffffffffull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(mine + 1, hi | (b1 >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(mine + 2, hi | (b2 & 0xffffffffull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(mine + 3, hi | (b2 >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      bool ok = false;
+      unsigned val = 0;
+      if (!failed) {                                        // wave-uniform (read back from LDS below)
+        const bool has = lane < 4 * T;
+        const long long start = wall_clock64();
+        for (unsigned spins = 1;; ++spins) {
+          const unsigned long long g =
+              has ? __hip_atomic_load(set + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : (unsigned long long)tag << 32;
+          val = (unsigned)g;
+          if (__all((unsigned)(g >> 32) == tag)) {
+            ok = true;
+            break;
+          }
+          __builtin_amdgcn_s_sleep(2);
+          if ((spins & 63u) == 0 && __any(wall_clock64() - start > TEAM_SPIN_TICKS)) break;
+        }
+      }
+      double a1 = 0.0, a2 = 0.0;
+      for (int m = 0; m < T; ++m) {                         // member order: the same sums in every member
+        const unsigned l1 = __shfl(val, 4 * m, 64), h1 = __shfl(val, 4 * m + 1, 64);
+        const unsigned l2 = __shfl(val, 4 * m + 2, 64), h2 = __shfl(val, 4 * m + 3, 64);
+        a1 += __longlong_as_double((long long)(((unsigned long long)h1 << 32) | l1));
+        a2 += __longlong_as_double((long long)(((unsigned long long)h2 << 32) | l2));
+      }
+      if (lane == 0) {
+        if (!ok) {
+          if (!failed) __hip_atomic_store(status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          a1 = a2 = __longlong_as_double(0x7ff8000000000000ll);
+        }
+        const double count = (double)total;
+        s_c[0] = (float)(a1 / count);
+        s_c[1] = (float)(a2 / count);
+        s_failed = !ok;
+        if (member == 0) {
+          if (dbeta) dbeta[c] = (float)a1 + (accp ? dbeta[c] : 0.f);
+          if (dgamma) dgamma[c] = (float)a2 + (accp ? dgamma[c] : 0.f);
+        }
+      }
+    }
+    __syncthreads();
+    const float c1 = s_c[0], c2 = s_c[1];
+    failed = s_failed != 0;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      if (v_base + (j * ONE_NT + (int)threadIdx.x) * 4 >= total) continue;
+      const float* xp = reinterpret_cast<const float*>(&xv[j]);
+      const float* gp = reinterpret_cast<const float*>(&gv[j]);
+      float4 o;
+      o.x = sc * (gp[0] - c1 - ((xp[0] - mu) * is) * c2);
+      o.y = sc * (gp[1] - c1 - ((xp[1] - mu) * is) * c2);
+      o.z = sc * (gp[2] - c1 - ((xp[2] - mu) * is) * c2);
+      o.w = sc * (gp[3] - c1 - ((xp[3] - mu) * is) * c2);
+      am = max(max(am, abs_bits(o.x)), max(max(abs_bits(o.y), abs_bits(o.z)), abs_bits(o.w)));
+      *reinterpret_cast<float4*>(gx + offset_of(j)) = o;
+    }
+  }
+  if (gx_amax) block_amax_atomic<ONE_NT>(am, gx_amax);      // one atomic per workgroup, after its last round
+}
+
 // BatchNorm1d: x [B][C].  A workgroup owns 32 consecutive channels (128-byte coalesced rows);
 // its 8 row-slices (threads 32*s .. 32*s+31) each sum every 8th batch row in fp64 and combine
 // through LDS in a fixed order; the normalise / gradient pass re-reads the rows from L2.
@@ -452,7 +619,63 @@ int streams_vec(int HW, const void* a, const void* b = nullptr, const void* c = 
 }
 
 size_t part_bytes(int C) { return (size_t)C * NS_MAX * 2 * sizeof(double); }
-size_t ws_bytes(int C) { return part_bytes(C) + 64; }
+// the two-stage partials, or (team backward) the exchange block: either one starts at the workspace's first byte
+size_t ws_bytes(int C) { return part_bytes(C) + 64 + team_block_bytes(TEAM_MAX_WGS); }
+
+// Compute units of the current device: what a persistent grid is sized by.  Asked of the runtime once per device and kept
+// (a write-once cache of a device constant, not state: every caller computes the same value); 0 if it cannot be had.
+int device_cus() {
+  constexpr int MAX_DEV = 64;
+  static std::atomic<int> cus[MAX_DEV];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEV) return 0;
+  int n = cus[dev].load(std::memory_order_relaxed);
+  if (n == 0) {
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 0) n = 0;
+    cus[dev].store(n, std::memory_order_relaxed);
+  }
+  return n;
+}
+
+VG_KNOB(int, g_team_nv, 0);            // tuning build: 1 / 8 force the team backward with that NV (vg_debug_set_bn_team)
+VG_KNOB(int, g_team_max_wgs, 0);       // tuning build: cap of the resident workgroups (0: the device's)
+
+// What vg_bn_act_bwd launches.  One pass when a channel fits a workgroup's registers and there are channels enough to fill
+// the chip's memory system (16-byte loads only: a misaligned x / gy / gx goes to the two passes' scalar loops); the team
+// form of the one pass for larger channels of up to 16 members where channels x members reach the same 128 workgroups;
+// the two passes for everything else.
+enum { BWD_1D = 0, BWD_ONE2 = 1, BWD_ONE8 = 2, BWD_TWO = 3, BWD_TEAM = 4 };
+struct BwdPlan {
+  int path, nv, T, teams, rounds;
+};
+BwdPlan make_bwd_plan(int B, int C, int HW, int vec) {
+  BwdPlan p = {BWD_TWO, 0, 0, 0, 0};
+  if (HW == 1) {
+    p.path = BWD_1D;
+    return p;
+  }
+  const long per_channel = (long)B * HW;
+  const bool forced = g_team_nv != 0;
+  if (!forced && vec && per_channel >= 4 && per_channel <= (long)ONE_NT * 4 * 8 && C >= 128) {
+    p.path = per_channel <= (long)ONE_NT * 4 * 2 ? BWD_ONE2 : BWD_ONE8;
+    return p;
+  }
+  if (!vec || per_channel < 4 || (!forced && per_channel <= (long)ONE_NT * 4 * 8)) return p;
+  const int nv = forced ? g_team_nv : 8;
+  const long cap = (long)ONE_NT * 4 * nv;
+  const long T = (per_channel + cap - 1) / cap;
+  if (T > TEAM_MAX_T || (!forced && (long)C * T < 128)) return p;
+  int max_wgs = device_cus();
+  if (g_team_max_wgs > 0 && g_team_max_wgs < max_wgs) max_wgs = g_team_max_wgs;
+  if (max_wgs > TEAM_MAX_WGS) max_wgs = TEAM_MAX_WGS;
+  if (max_wgs < T) return p;            // a channel's members must all be resident at once
+  p.path = BWD_TEAM;
+  p.nv = nv;
+  p.T = (int)T;
+  p.teams = (int)(C < max_wgs / T ? C : max_wgs / T);
+  p.rounds = (C + p.teams - 1) / p.teams;
+  return p;
+}
 
 // Upper bound of max |act(x * sc + sh)| over a channel of n = count values, from its sums alone (act_amax of the
 // finalize kernels: what an fp16-plane convolution that applies sc / sh on load scales its input by).
@@ -835,12 +1058,34 @@ extern "C" int vg_bn_act_bwd(const float* gy, const float* x, const float* gamma
     VG_CHECK_LAUNCH();
     return 0;
   }
-  // one pass when a channel fits a workgroup's registers and there are channels enough to fill the chip's memory system
-  // (16-byte loads only: a misaligned x / gy / gx goes to the two passes' scalar loops)
-  const long per_channel = (long)B * HW;
   const int vec = streams_vec(HW, x, gy, gx);
-  if (vec && per_channel >= 4 && per_channel <= (long)ONE_NT * 4 * 8 && C >= 128) {
-    if (per_channel <= (long)ONE_NT * 4 * 2)
+  const BwdPlan plan = make_bwd_plan(B, C, HW, vec);
+  if (plan.path == BWD_TEAM) {
+    const int grid = plan.teams * plan.T;
+    const size_t xbytes = team_block_bytes(grid);
+    if (!workspace || workspace_bytes < xbytes || ((uintptr_t)workspace & 15)) return VG_ERR_WORKSPACE;
+    // status word and granules: zeroed before every launch (tags count rounds within a launch, from 1).  By a kernel of
+    // our own, not hipMemsetAsync: the memset NODE of a captured call wrote stale bytes instead of zeros from its second
+    // replay on whenever other launches had run in between (seen on the status word: profiles/README.md, Round 12)
+    unsigned long long* xch = (unsigned long long*)workspace;
+    const int words = (int)(xbytes / sizeof(unsigned long long));
+    hipLaunchKernelGGL(team_zero_kernel, dim3(cdiv(words, NT)), dim3(NT), 0, st, xch, words);
+    VG_CHECK_LAUNCH();
+    if (plan.nv == 8)
+      hipLaunchKernelGGL(bn_bwd_team_kernel<8>, dim3(grid), dim3(ONE_NT), 0, st, x, gy, gamma, beta, save_mean, save_invstd,
+                         gx, dgamma, dbeta, B, C, HW, act_apply, am, plan.T, plan.teams, xch);
+#ifdef VG_TUNING
+    else if (plan.nv == 1)
+      hipLaunchKernelGGL(bn_bwd_team_kernel<1>, dim3(grid), dim3(ONE_NT), 0, st, x, gy, gamma, beta, save_mean, save_invstd,
+                         gx, dgamma, dbeta, B, C, HW, act_apply, am, plan.T, plan.teams, xch);
+#endif
+    else
+      return VG_ERR_BAD_ARG;
+    VG_CHECK_LAUNCH();
+    return 0;
+  }
+  if (plan.path == BWD_ONE2 || plan.path == BWD_ONE8) {
+    if (plan.path == BWD_ONE2)
       hipLaunchKernelGGL(bn_bwd_onepass_kernel<2>, dim3(C), dim3(ONE_NT), 0, st, x, gy, gamma, beta, save_mean, save_invstd,
                          gx, dgamma, dbeta, B, C, HW, act_apply, am);
     else
@@ -862,6 +1107,23 @@ extern "C" int vg_bn_act_bwd(const float* gy, const float* x, const float* gamma
   VG_CHECK_LAUNCH();
   return 0;
 }
+
+#ifdef VG_TUNING
+extern "C" int vg_debug_set_bn_team(int nv, int max_wgs) {
+  if ((nv != 0 && nv != 1 && nv != 8) || max_wgs < 0) return VG_ERR_BAD_ARG;
+  g_team_nv = nv;
+  g_team_max_wgs = max_wgs;
+  return 0;
+}
+
+// the plan vg_bn_act_bwd would launch under the current knobs (make_bwd_plan: the launch's own planning code)
+extern "C" int vg_debug_bn_bwd_plan(int B, int C, int HW, const void* gy, const void* x, const void* gx, int* out) {
+  if (!out || B <= 0 || C <= 0 || HW <= 0) return VG_ERR_BAD_ARG;
+  const BwdPlan p = make_bwd_plan(B, C, HW, streams_vec(HW, x, gy, gx));
+  out[0] = p.path; out[1] = p.nv; out[2] = p.T; out[3] = p.teams; out[4] = p.rounds;
+  return 0;
+}
+#endif
 
 // ---- BatchNorm on RUNNING statistics (eval mode: nn.BatchNorm*.eval() of the reference's modules, model.py:451-458, 462,
 // 468, 492, 496-505, 390-400) ---------------------------------------------------------------------------------------------

@@ -692,6 +692,17 @@ int vg_debug_set_conv_bf16split_tile(int variant);
 /* stride-2 ring kernel of conv_ring.hip: 0 = 256 cout x 128 px, 1 / 2 = 128 x 128 (2x4 / 4x2 wavefronts),
  * 3 = 128 x 256 (transposed), -1 = heuristic */
 int vg_debug_set_conv_ring_tile(int variant);
+/* One-pass BatchNorm backward by workgroup teams (bn.hip, bn_bwd_team_kernel): nv = 1 or 8 forces the team form, with that
+ * many 16-byte vectors of x and of gy per lane (a member then holds 4096 * nv elements), on every shape it can take
+ * (16-byte streams, <= 16 members per channel, max_wgs >= the members of one channel); nv = 0 restores the dispatch rule
+ * of vg_bn_act_bwd.  max_wgs > 0 caps the resident workgroups the grid is sized by (0: the device's compute units), so
+ * that small tensors get several members, ragged last members and several rounds. */
+int vg_debug_set_bn_team(int nv, int max_wgs);
+/* What vg_bn_act_bwd would launch for a shape under the current knobs, on the current device (nothing runs; gy, x, gx:
+ * only their alignment is looked at) -- from the same planning code as the launch.
+ *   out[5]: path (0 BatchNorm1d, 1 one pass <2>, 2 one pass <8>, 3 two passes, 4 team), nv, T (members per channel),
+ *           teams, rounds; nv = T = teams = rounds = 0 off the team path. */
+int vg_debug_bn_bwd_plan(int B, int C, int HW, const void* gy, const void* x, const void* gx, int* out);
 #endif
 
 #ifdef __cplusplus

@@ -8,54 +8,61 @@
 //
 // One launch updates up to VG_ADAM_MAX_TENSORS tensors: their pointers travel in the kernel
 // arguments, a workgroup owns 8192 consecutive elements of one tensor (16-byte loads / stores when
-// the four pointers allow it).  Bias corrections are computed on the host in double precision.
+// the pointers allow it).  Bias corrections are computed on the host in double precision, or by a one-thread prepare
+// kernel from a device step counter (steps captured in a HIP graph).
 //
-// Non-finite guard (vg_adam_step_checked / vg_adam_step_dev_checked): the step is the one pass that reads every gradient
-// and writes every parameter, so it also notices an inf / NaN among them -- |x| as bits >= 0x7f800000 -- and ORs
-// VG_NONFINITE_GRAD / VG_NONFINITE_PARAM into the tensor's caller-owned flag word: one wavefront / LDS reduction per
-// workgroup, one atomicOr per workgroup that saw something, none in a clean step.  By itself it DETECTS, it does not
-// skip the update: a skip needs a grid-wide answer before the first store -- which the opt-in norm pass below gives
-// (vg_adam_step_clip with skip_nonfinite).  Without that opt-in, when a bit is up the weights are poisoned; recovery
-// is the last good checkpoint.  The arithmetic that writes p, m, v and amax is the unchecked step's.
+// Two step kernels stand behind the entry points; both emit max |p| into the tensor's amax word and OR
+// VG_NONFINITE_GRAD / VG_NONFINITE_PARAM -- |x| as bits >= 0x7f800000 among the gradients read / the parameters
+// written -- into the tensor's caller-owned flag word (one wavefront / LDS reduction per workgroup, one atomicOr per
+// workgroup that saw something, none in a clean step), where the caller hands such words in.
 //
-// Weight EMA (vg_adam_step_ema / vg_adam_step_dev_ema): the thread that has just formed an element's new p also moves
-// the element's running average, e <- e + (1 - decay) (p_new - e) (torch's lerp form for weights below 0.5), from the
-// value in its register: 8 more bytes per parameter instead of the 12 of a separate pass over p and e.  It is a
-// compile-time variant with a pack of its own (AdamPackEma): the kernels of the entry points above are what they
-// were.  An inf / NaN in p goes into e unfiltered; the guard reports it as before.
+// The plain kernel (adam_multi_kernel<DEV>; vg_adam_step, _checked, _dev, _dev_checked): the step above and nothing
+// else.  It is the default path and the yardstick: compiled under the default contraction, its bits are what the tests
+// root every other entry point in.  By itself it DETECTS an inf / NaN, it does not skip the update -- a skip needs a
+// grid-wide answer before the first store; once a bit is up the weights are poisoned and the last good checkpoint is
+// the way back.
 //
-// Clipping by global norm / skipping a non-finite step (vg_grad_sumsq_multi, vg_grad_clip_finalize, vg_adam_step_clip /
-// vg_adam_step_dev_clip): one deterministic pass over the gradients in front of the step -- fp64 squares and sums from
-// the thread level on (the square of an fp32 number is exact in fp64, and no |g| overflows), one fp64 partial per
-// workgroup in a slot of its own, no atomics -- and a one-workgroup kernel that adds the partials in a fixed order and
-// writes a four-word record: the norm, the clip coefficient min(1, max_norm / (norm + 1e-6)) (clip_grad_norm_'s
-// formula, formed in double, rounded once), a skip word and a running count of skips.  The clip variant of the step
-// reads the record at its top and uses every gradient as gs = coef * g (one fp32 rounding, that of g.mul_(coef)), from
-// registers: 4 more bytes per parameter instead of the 12 of torch's recipe.  With the skip word up it stores nothing to
-// p, m, v or the EMA; it still emits max |p| (the bounds words were zeroed in front of the step) and flags the tensor
-// that holds the inf / NaN.  It is a kernel and a pack of its own: the kernels of the entry points above are what
-// they were.
+// The feature kernel (adam_multi_feature_kernel; every other entry point): the same step, element by element the plain
+// kernel's bits (adam_one_as), with four features that are each a uniform run-time test and cost nothing when off:
 //
-// Weight decay and hyper-parameters on the device (vg_adam_prepare_dev, vg_adam_step_decay / vg_adam_step_dev_decay):
-// the learning rate and the weight decay of a captured step live in a device pair [lr, weight_decay] the prepare kernel
-// reads, so a schedule changes them between replays.  The decay step is the clip step with one more register operation
-// per element in front of the update -- coupled (L2): gd = gs + (wd * p), a rounded product and a rounded sum;
-// decoupled (AdamW): pd = p * s2 with s2 = (float)(1 - lr * wd) formed in double -- and no memory traffic of its own.
-// With wd == 0 neither term is formed (no 0 * inf) and the bits are the clip step's.  Again a kernel and a pack of its
-// own.
+//   weight EMA      e[t] != NULL: the thread that has just formed an element's new p also moves the element's running
+//                   average, e <- e + (1 - decay) (p_new - e) (torch's lerp form for weights below 0.5), from the value
+//                   in its register: 8 more bytes per parameter instead of the 12 of a separate pass.  An inf / NaN in p
+//                   goes into e unfiltered.  (1 - decay) is a host float in the pack, or -- omd_dev != NULL -- a device
+//                   word a warm-up changes between the replays of a captured step; the device word 1.0f ("follow the
+//                   weights") stores p itself, since e + 1 (p - e) is not p in fp32.
+//   clip / skip     record != NULL: every gradient is used as gs = coef * g (one fp32 rounding, that of g.mul_(coef)),
+//                   4 more bytes per parameter instead of the 12 of torch's recipe.  With the record's skip word up
+//                   nothing is stored to p, m, v or an average; max |p| and the flag of the tensor that holds the
+//                   inf / NaN are still emitted.  The record comes from one deterministic pass over the gradients in
+//                   front of the step (vg_grad_sumsq_multi: fp64 squares and sums from the thread level on, one partial
+//                   per workgroup in a slot of its own, no atomics) and a one-workgroup kernel that adds the partials in
+//                   a fixed order (vg_grad_clip_finalize: norm, coefficient min(1, max_norm / (norm + 1e-6)) formed in
+//                   double, skip word, running count of skips).
+//   weight decay    one more register operation per element in front of the update, no memory traffic: coupled (L2),
+//                   wdc != 0: gd = gs + (wdc * p), a rounded product and a rounded sum; decoupled (AdamW), s2 != 1:
+//                   pd = p * s2 with s2 = (float)(1 - lr * wd) formed in double.  With wd == 0 neither term is formed
+//                   (no 0 * inf).  s2 / wdc are host floats in the pack, or -- decay_dev -- scalars[2..3] as
+//                   vg_adam_prepare_dev leaves them from a device pair [lr, weight_decay] a schedule changes between
+//                   replays.
 //
-// EMA decay on the device (vg_adam_step_dev_ema_dev): the decay step with (float)(1 - decay) read from a device word
-// instead of the pack -- an ordinary global load, uniform over the grid -- so a warm-up changes the decay between the
-// replays of a captured step.  A compile-time variant of the decay kernel with a pack of its own; the word 1.0f
-// ("follow the weights") stores p itself, since e + 1 (p - e) is not p in fp32.
+//   entry point                 scalars             EMA                       record      decay
+//   vg_adam_step_ema            host                required, host decay      --          --
+//   vg_adam_step_dev_ema        device, 2 words     required, host decay      --          --
+//   vg_adam_step_clip           host                optional, host decay      required    --
+//   vg_adam_step_dev_clip       device, 2 words     optional, host decay      required    --
+//   vg_adam_step_decay          host                optional, host decay      optional    host (weight_decay, decoupled)
+//   vg_adam_step_dev_decay      device, 4 words     optional, host decay      optional    scalars[2..3]
+//   vg_adam_step_dev_ema_dev    device, 4 words     required, device word     optional    scalars[2..3]
 #include "common.hpp"
 #include "vaegan_hip.h"
-
-#include <type_traits>
 
 namespace {
 
 constexpr int ANT = 256, ACHUNK = 8192, AMAX = 24;
+constexpr unsigned long long MAX_GRID = 0x3fffffffULL;      // workgroups of one launch
+
+__host__ __device__ constexpr unsigned long long chunks_of(unsigned long long n) { return (n + ACHUNK - 1) / ACHUNK; }
 
 struct AdamPack {
   float* p[AMAX];
@@ -69,11 +76,30 @@ struct AdamPack {
   int count;
 };
 
-// The pack of the EMA variant: e[t] may be NULL (that tensor is not averaged); omd = (float)(1 - decay).
-struct AdamPackEma : AdamPack {
-  float* e[AMAX];
-  float omd;
+// The pack of the feature kernel.
+struct AdamFeaturePack : AdamPack {
+  float* e[AMAX];           // per tensor, may be NULL: that tensor is not averaged
+  float omd;                // (float)(1 - decay) formed on the host; used when omd_dev == NULL
+  const float* omd_dev;     // NULL, or the device word that holds (float)(1 - decay)
+  float s2;                 // decoupled decay: p is multiplied by this before the update; 1: not
+  float wdc;                // coupled decay: this times p is added to the gradient; 0: not
+  int decay_dev;            // s2 / wdc are read from scalars[2..3] (vg_adam_prepare_dev wrote them) instead
 };
+
+// The workgroup's tensor and its ACHUNK elements [base, end) of it (uniform over the workgroup).
+struct Chunk {
+  int t;
+  unsigned long long base, end;
+};
+
+template <typename Pack>
+__device__ __forceinline__ Chunk chunk_of_block(const Pack& A) {
+  int t = 0;
+  while (t + 1 < A.count && blockIdx.x >= A.first_block[t + 1]) ++t;
+  const unsigned long long n = A.n[t];
+  const unsigned long long base = (unsigned long long)(blockIdx.x - A.first_block[t]) * ACHUNK;
+  return {t, base, min(base + (unsigned long long)ACHUNK, n)};
+}
 
 __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, float omb1, float b2, float omb2,
                                          float step_size, float bc2s, float eps) {
@@ -83,12 +109,12 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
   p = p - step_size * (m / denom);
 }
 
-// adam_one for the EMA variant, which must give the bits of the kernels without EMA element by element -- wherever its
-// own alignment rule (the EMA pointer counts) sends the element.  Those kernels are compiled under the default
-// contraction, and the compiler forms v differently in their two loops: in the 16-byte body as ONE fma,
+// adam_one for the feature kernel, which must give the bits of the plain kernel element by element -- wherever its
+// own alignment rule (the EMA pointer counts) sends the element.  The plain kernel is compiled under the default
+// contraction, and the compiler forms v differently in its two loops: in the 16-byte body as ONE fma,
 // fma(b2, v, (omb2 g) g), in the scalar loops as two rounded products and a rounded sum; m and p are an fma in both.
 // So this copy spells the roundings out (no contraction of its own) and takes, per element, which of the two loops
-// the step without EMA would have run it in.  tests/test_adam_ema_gpu.py compares the bits on every path.
+// the plain kernel would have run it in.  tests/test_adam_ema_gpu.py compares the bits on every path.
 __device__ __forceinline__ void adam_one_as(bool body, float& p, float g, float& m, float& v, float omb1, float b2,
                                             float omb2, float step_size, float bc2s, float eps) {
 #pragma clang fp contract(off)
@@ -162,32 +188,33 @@ __device__ __forceinline__ void block_flag_or(unsigned bits, unsigned* out) {
   }
 }
 
-template <bool DEV, bool EMA>
-__global__ __launch_bounds__(ANT) void adam_multi_kernel(std::conditional_t<EMA, AdamPackEma, AdamPack> A, float omb1,
-                                                        float b2, float omb2, float step_size, float bc2s, float eps,
-                                                        const float* __restrict__ scalars) {
+// The end of a step kernel: this thread's max |p| (`am`) and max |g| (`gm`), as bits, go into the tensor's amax word
+// and flag word (either may be NULL; both pointers are uniform over the workgroup).  Every thread must call it.
+__device__ __forceinline__ void emit_amax_and_flags(unsigned am, unsigned gm, unsigned* amax, unsigned* flag) {
+  if (amax) block_amax_atomic<ANT>(am, amax);
+  if (flag)
+    block_flag_or((gm >= NONFINITE_BITS ? (unsigned)VG_NONFINITE_GRAD : 0u) |
+                      (am >= NONFINITE_BITS ? (unsigned)VG_NONFINITE_PARAM : 0u),
+                  flag);
+}
+
+// ---- the plain step ----------------------------------------------------------------------------------------------------
+// Its three loops are the reference bits of every other entry point (adam_one_as names the compiler's choices in them).
+template <bool DEV>
+__global__ __launch_bounds__(ANT) void adam_multi_kernel(AdamPack A, float omb1, float b2, float omb2, float step_size,
+                                                        float bc2s, float eps, const float* __restrict__ scalars) {
   if constexpr (DEV) {
     step_size = scalars[0];
     bc2s = scalars[1];
   }
-  int t = 0;
-  while (t + 1 < A.count && blockIdx.x >= A.first_block[t + 1]) ++t;
-  const unsigned long long n = A.n[t];
-  const unsigned long long base = (unsigned long long)(blockIdx.x - A.first_block[t]) * ACHUNK;
-  const unsigned long long end = min(base + (unsigned long long)ACHUNK, n);
+  const Chunk c = chunk_of_block(A);
+  const int t = c.t;
+  const unsigned long long base = c.base, end = c.end;
   float* __restrict__ p = A.p[t];
   const float* __restrict__ g = A.g[t];
   float* __restrict__ m = A.m[t];
   float* __restrict__ v = A.v[t];
-  bool vec = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
-  [[maybe_unused]] const bool vec_step = vec;      // what the step without EMA decides for this tensor (adam_one_as)
-  float* __restrict__ e = nullptr;      // (uniform over the workgroup, like t)
-  float omd = 0.f;
-  if constexpr (EMA) {
-    e = A.e[t];
-    omd = A.omd;
-    vec = vec && (((uintptr_t)e & 15) == 0);      // NULL passes: the choice of a tensor without an average is unchanged
-  }
+  const bool vec = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
   // bound of max |p| for the fp16-plane GEMMs that read this weight next (VgAdamTensor::amax): the step that changes the
   // weight is the one pass that sees every new value anyway -- no separate 134 MB read per weight and iteration
   unsigned am = 0;
@@ -201,10 +228,7 @@ __global__ __launch_bounds__(ANT) void adam_multi_kernel(std::conditional_t<EMA,
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         float pj = pv[j], mj = mv[j], vj = vv[j];
-        if constexpr (EMA)
-          adam_one_as(true, pj, gv[j], mj, vj, omb1, b2, omb2, step_size, bc2s, eps);
-        else
-          adam_one(pj, gv[j], mj, vj, omb1, b2, omb2, step_size, bc2s, eps);
+        adam_one(pj, gv[j], mj, vj, omb1, b2, omb2, step_size, bc2s, eps);
         pv[j] = pj; mv[j] = mj; vv[j] = vj;
         am = max(am, abs_bits(pj));
         gm = max(gm, abs_bits(gv[j]));
@@ -212,55 +236,26 @@ __global__ __launch_bounds__(ANT) void adam_multi_kernel(std::conditional_t<EMA,
       *reinterpret_cast<f32x4*>(p + i) = pv;
       *reinterpret_cast<f32x4*>(m + i) = mv;
       *reinterpret_cast<f32x4*>(v + i) = vv;
-      if constexpr (EMA) {
-        if (e) {
-          f32x4 ev = *reinterpret_cast<f32x4*>(e + i);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) ev[j] = ema_one(ev[j], pv[j], omd);
-          *reinterpret_cast<f32x4*>(e + i) = ev;
-        }
-      }
     }
     for (unsigned long long i = end4 + threadIdx.x; i < end; i += ANT) {
       const float gi = g[i];
-      if constexpr (EMA) {
-        float pi = p[i];      // the average below takes the new p from this register
-        adam_one_as(false, pi, gi, m[i], v[i], omb1, b2, omb2, step_size, bc2s, eps);
-        p[i] = pi;
-        if (e) e[i] = ema_one(e[i], pi, omd);
-        am = max(am, abs_bits(pi));
-      } else {
-        adam_one(p[i], gi, m[i], v[i], omb1, b2, omb2, step_size, bc2s, eps);
-        am = max(am, abs_bits(p[i]));
-      }
+      adam_one(p[i], gi, m[i], v[i], omb1, b2, omb2, step_size, bc2s, eps);
+      am = max(am, abs_bits(p[i]));
       gm = max(gm, abs_bits(gi));
     }
   } else {
-    [[maybe_unused]] const unsigned long long end4 = base + ((end - base) & ~3ULL);
     for (unsigned long long i = base + threadIdx.x; i < end; i += ANT) {
       const float gi = g[i];
-      if constexpr (EMA) {
-        float pi = p[i];      // the average below takes the new p from this register
-        adam_one_as(vec_step && i < end4, pi, gi, m[i], v[i], omb1, b2, omb2, step_size, bc2s, eps);
-        p[i] = pi;
-        if (e) e[i] = ema_one(e[i], pi, omd);
-        am = max(am, abs_bits(pi));
-      } else {
-        adam_one(p[i], gi, m[i], v[i], omb1, b2, omb2, step_size, bc2s, eps);
-        am = max(am, abs_bits(p[i]));
-      }
+      adam_one(p[i], gi, m[i], v[i], omb1, b2, omb2, step_size, bc2s, eps);
+      am = max(am, abs_bits(p[i]));
       gm = max(gm, abs_bits(gi));
     }
   }
-  if (A.amax[t]) block_amax_atomic<ANT>(am, A.amax[t]);      // (t is uniform over the workgroup)
-  if (A.flag[t])
-    block_flag_or((gm >= NONFINITE_BITS ? (unsigned)VG_NONFINITE_GRAD : 0u) |
-                      (am >= NONFINITE_BITS ? (unsigned)VG_NONFINITE_PARAM : 0u),
-                  A.flag[t]);
+  emit_amax_and_flags(am, gm, A.amax[t], A.flag[t]);      // (t is uniform over the workgroup)
 }
 
 // ---- clipping by global norm, skipping a non-finite step --------------------------------------------------------------
-// The record vg_grad_clip_finalize writes and the clip step reads: four 32-bit words.
+// The record vg_grad_clip_finalize writes and the feature kernel reads: four 32-bit words.
 constexpr int REC_NORM = 0, REC_COEF = 1, REC_SKIP = 2, REC_SKIPPED = 3;
 
 struct SumsqPack {
@@ -275,12 +270,9 @@ struct SumsqPack {
 // workgroup reduce in a fixed tree: the same bits run to run.
 __global__ __launch_bounds__(ANT) void grad_sumsq_multi_kernel(SumsqPack A, double* __restrict__ partials) {
   __shared__ double red[ANT / 64];
-  int t = 0;
-  while (t + 1 < A.count && blockIdx.x >= A.first_block[t + 1]) ++t;
-  const unsigned long long n = A.n[t];
-  const unsigned long long base = (unsigned long long)(blockIdx.x - A.first_block[t]) * ACHUNK;
-  const unsigned long long end = min(base + (unsigned long long)ACHUNK, n);
-  const float* __restrict__ g = A.g[t];
+  const Chunk c = chunk_of_block(A);
+  const unsigned long long base = c.base, end = c.end;
+  const float* __restrict__ g = A.g[c.t];
   double s = 0.0;
   unsigned long long tail = base;
   if (((uintptr_t)g & 15) == 0) {      // (base is a multiple of ACHUNK: g + base is aligned when g is)
@@ -330,122 +322,12 @@ __global__ __launch_bounds__(ANT) void grad_clip_finalize_kernel(const double* _
   }
 }
 
+// ---- the step with features -------------------------------------------------------------------------------------------
 // gs = coef * g, rounded once as g.mul_(coef) rounds it: kept from being fused into the m update that follows.
 __device__ __forceinline__ float clip_scale(float coef, float g) {
 #pragma clang fp contract(off)
   return coef * g;
 }
-
-// The step of adam_multi_kernel<DEV, true> with every gradient scaled by the record's coefficient, or -- the record's
-// skip word up -- no step at all: p and g are read for max |p| and the flag words, nothing is stored to p, m, v, e.
-// e[t] may be NULL as in the EMA variant; a launch without any average passes NULLs.  adam_one_as and its `body` rule
-// give, element by element, the bits of the step without the feature on the scaled gradient.
-template <bool DEV>
-__global__ __launch_bounds__(ANT) void adam_clip_multi_kernel(AdamPackEma A, float omb1, float b2, float omb2,
-                                                             float step_size, float bc2s, float eps,
-                                                             const float* __restrict__ scalars,
-                                                             const float* __restrict__ record) {
-  if constexpr (DEV) {
-    step_size = scalars[0];
-    bc2s = scalars[1];
-  }
-  const float coef = record[REC_COEF];
-  const bool skip = reinterpret_cast<const unsigned*>(record)[REC_SKIP] != 0u;      // (uniform over the grid)
-  int t = 0;
-  while (t + 1 < A.count && blockIdx.x >= A.first_block[t + 1]) ++t;
-  const unsigned long long n = A.n[t];
-  const unsigned long long base = (unsigned long long)(blockIdx.x - A.first_block[t]) * ACHUNK;
-  const unsigned long long end = min(base + (unsigned long long)ACHUNK, n);
-  float* __restrict__ p = A.p[t];
-  const float* __restrict__ g = A.g[t];
-  float* __restrict__ m = A.m[t];
-  float* __restrict__ v = A.v[t];
-  float* __restrict__ e = A.e[t];
-  const float omd = A.omd;
-  const bool vec_step = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
-  const bool vec = vec_step && (((uintptr_t)e & 15) == 0);
-  const unsigned long long end4 = base + ((end - base) & ~3ULL);
-  unsigned am = 0, gm = 0;
-  if (skip) {
-    unsigned long long tail = base;
-    if (vec_step) {
-      for (unsigned long long i = base + 4ULL * threadIdx.x; i < end4; i += 4ULL * ANT) {
-        const f32x4 pv = *reinterpret_cast<const f32x4*>(p + i);
-        const f32x4 gv = *reinterpret_cast<const f32x4*>(g + i);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          am = max(am, abs_bits(pv[j]));
-          gm = max(gm, abs_bits(gv[j]));
-        }
-      }
-      tail = end4;
-    }
-    for (unsigned long long i = tail + threadIdx.x; i < end; i += ANT) {
-      am = max(am, abs_bits(p[i]));
-      gm = max(gm, abs_bits(g[i]));
-    }
-  } else if (vec) {
-    for (unsigned long long i = base + 4ULL * threadIdx.x; i < end4; i += 4ULL * ANT) {
-      f32x4 pv = *reinterpret_cast<f32x4*>(p + i), mv = *reinterpret_cast<f32x4*>(m + i);
-      f32x4 vv = *reinterpret_cast<f32x4*>(v + i);
-      const f32x4 gv = *reinterpret_cast<const f32x4*>(g + i);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        float pj = pv[j], mj = mv[j], vj = vv[j];
-        const float gs = clip_scale(coef, gv[j]);
-        adam_one_as(true, pj, gs, mj, vj, omb1, b2, omb2, step_size, bc2s, eps);
-        pv[j] = pj; mv[j] = mj; vv[j] = vj;
-        am = max(am, abs_bits(pj));
-        gm = max(gm, abs_bits(gs));
-      }
-      *reinterpret_cast<f32x4*>(p + i) = pv;
-      *reinterpret_cast<f32x4*>(m + i) = mv;
-      *reinterpret_cast<f32x4*>(v + i) = vv;
-      if (e) {
-        f32x4 ev = *reinterpret_cast<f32x4*>(e + i);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) ev[j] = ema_one(ev[j], pv[j], omd);
-        *reinterpret_cast<f32x4*>(e + i) = ev;
-      }
-    }
-    for (unsigned long long i = end4 + threadIdx.x; i < end; i += ANT) {
-      const float gs = clip_scale(coef, g[i]);
-      float pi = p[i];
-      adam_one_as(false, pi, gs, m[i], v[i], omb1, b2, omb2, step_size, bc2s, eps);
-      p[i] = pi;
-      if (e) e[i] = ema_one(e[i], pi, omd);
-      am = max(am, abs_bits(pi));
-      gm = max(gm, abs_bits(gs));
-    }
-  } else {
-    for (unsigned long long i = base + threadIdx.x; i < end; i += ANT) {
-      const float gs = clip_scale(coef, g[i]);
-      float pi = p[i];
-      adam_one_as(vec_step && i < end4, pi, gs, m[i], v[i], omb1, b2, omb2, step_size, bc2s, eps);
-      p[i] = pi;
-      if (e) e[i] = ema_one(e[i], pi, omd);
-      am = max(am, abs_bits(pi));
-      gm = max(gm, abs_bits(gs));
-    }
-  }
-  if (A.amax[t]) block_amax_atomic<ANT>(am, A.amax[t]);
-  if (A.flag[t])
-    block_flag_or((gm >= NONFINITE_BITS ? (unsigned)VG_NONFINITE_GRAD : 0u) |
-                      (am >= NONFINITE_BITS ? (unsigned)VG_NONFINITE_PARAM : 0u),
-                  A.flag[t]);
-}
-
-// ---- weight decay inside the step -------------------------------------------------------------------------------------
-// The pack of the decay variant: s2 / wdc are what vg_adam_prepare_dev leaves in scalars[2..3], formed on the host.
-struct AdamPackDecay : AdamPackEma {
-  float s2;       // decoupled: p is multiplied by this before the update; 1: not
-  float wdc;      // coupled: this times p is added to the gradient; 0: not
-};
-
-// The pack of the variant that reads (float)(1 - decay) from device memory: omd is not used.
-struct AdamPackDecayDev : AdamPackDecay {
-  const float* omd_dev;
-};
 
 // wd * p and gs + (wd * p): a rounded product and a rounded sum (torch: p.mul(wd), then g.add_), never one fma.
 __device__ __forceinline__ float decay_grad(float gs, float wdc, float p) {
@@ -460,52 +342,47 @@ __device__ __forceinline__ float decay_param(float p, float s2) {
   return p * s2;
 }
 
-// adam_clip_multi_kernel with the weights decayed in registers in front of the update.  `record` may be NULL here (no
-// clipping, nothing skipped: gs = g).  l2 / dec are uniform over the grid; with neither, every element takes the clip
-// step's operations and nothing else.  The GRAD bit is judged on gs -- the gradient the caller handed in, scaled -- not
-// on gd, which an inf WEIGHT would poison as well; amax and the PARAM bit on the final p.
-// EDEV: (float)(1 - decay) comes from the device word A.omd_dev; 1.0f stores p itself, anything else takes ema_one.
-template <bool DEV, bool EDEV = false>
-__global__ __launch_bounds__(ANT) void adam_decay_multi_kernel(std::conditional_t<EDEV, AdamPackDecayDev, AdamPackDecay> A,
-                                                              float omb1, float b2, float omb2, float step_size,
-                                                              float bc2s, float eps, const float* __restrict__ scalars,
-                                                              const float* __restrict__ record) {
+// The plain step with the weight EMA, the clip record and the weight decay, each a test that is uniform over the grid
+// (per tensor for e): `scalars` NULL -- step_size / bc2s are the arguments; `record` NULL -- gs = g, nothing is
+// skipped; s2 == 1 and wdc == 0 -- nothing decays; e[t] NULL -- the tensor is not averaged.  With everything off an
+// element takes the plain kernel's operations and nothing else: adam_one_as and its `body` rule give the plain
+// kernel's bits on (p, g) as this kernel has prepared them.  With the record's skip word up p and g are read for
+// max |p| and the flag words, nothing is stored to p, m, v, e.  The GRAD bit is judged on gs -- the gradient the caller
+// handed in, scaled (unscaled in a skipped step) -- not on gd, which an inf WEIGHT would poison as well; amax and the
+// PARAM bit on the final p.
+__global__ __launch_bounds__(ANT) void adam_multi_feature_kernel(AdamFeaturePack A, float omb1, float b2, float omb2,
+                                                                float step_size, float bc2s, float eps,
+                                                                const float* __restrict__ scalars,
+                                                                const float* __restrict__ record) {
   float s2 = A.s2, wdc = A.wdc;
-  if constexpr (DEV) {
+  if (scalars) {
     step_size = scalars[0];
     bc2s = scalars[1];
+  }
+  // scalars[2..3] exist only behind vg_adam_prepare_dev: vg_adam_prepare leaves a two-word buffer
+  if (A.decay_dev) {
     s2 = scalars[2];
     wdc = scalars[3];
   }
   const bool dec = s2 != 1.f, l2 = wdc != 0.f;
   const bool scale = record != nullptr;
   const float coef = scale ? record[REC_COEF] : 1.f;
-  const bool skip = scale && reinterpret_cast<const unsigned*>(record)[REC_SKIP] != 0u;      // (uniform over the grid)
-  int t = 0;
-  while (t + 1 < A.count && blockIdx.x >= A.first_block[t + 1]) ++t;
-  const unsigned long long n = A.n[t];
-  const unsigned long long base = (unsigned long long)(blockIdx.x - A.first_block[t]) * ACHUNK;
-  const unsigned long long end = min(base + (unsigned long long)ACHUNK, n);
+  const bool skip = scale && reinterpret_cast<const unsigned*>(record)[REC_SKIP] != 0u;
+  const Chunk c = chunk_of_block(A);
+  const int t = c.t;
+  const unsigned long long base = c.base, end = c.end;
   float* __restrict__ p = A.p[t];
   const float* __restrict__ g = A.g[t];
   float* __restrict__ m = A.m[t];
   float* __restrict__ v = A.v[t];
   float* __restrict__ e = A.e[t];
-  float omd = A.omd;
-  [[maybe_unused]] bool follow = false;      // (uniform over the grid)
-  if constexpr (EDEV) {
-    omd = A.omd_dev[0];
-    follow = omd == 1.f;
-  }
+  const float omd = A.omd_dev ? A.omd_dev[0] : A.omd;
+  // "follow the weights" is the DEVICE word's 1.0f alone: a host (float)(1 - decay) that rounds to 1 takes ema_one
+  const bool follow = A.omd_dev && omd == 1.f;
   // one element of the average from the p just formed
-  auto avg = [&](float ej, float pj) {
-    if constexpr (EDEV) {
-      if (follow) return pj;
-    }
-    return ema_one(ej, pj, omd);
-  };
-  const bool vec_step = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
-  const bool vec = vec_step && (((uintptr_t)e & 15) == 0);
+  auto avg = [&](float ej, float pj) { return follow ? pj : ema_one(ej, pj, omd); };
+  const bool vec_step = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0);      // the plain kernel's choice
+  const bool vec = vec_step && (((uintptr_t)e & 15) == 0);      // NULL passes
   const unsigned long long end4 = base + ((end - base) & ~3ULL);
   unsigned am = 0, gm = 0;
   // one element: (p, g as read) -> the new p; m and v in place
@@ -557,7 +434,7 @@ __global__ __launch_bounds__(ANT) void adam_decay_multi_kernel(std::conditional_
       }
     }
     for (unsigned long long i = end4 + threadIdx.x; i < end; i += ANT) {
-      float pi = p[i];
+      float pi = p[i];      // the average takes the new p from this register
       one(false, pi, g[i], m[i], v[i]);
       p[i] = pi;
       if (e) e[i] = avg(e[i], pi);
@@ -570,88 +447,96 @@ __global__ __launch_bounds__(ANT) void adam_decay_multi_kernel(std::conditional_
       if (e) e[i] = avg(e[i], pi);
     }
   }
-  if (A.amax[t]) block_amax_atomic<ANT>(am, A.amax[t]);
-  if (A.flag[t])
-    block_flag_or((gm >= NONFINITE_BITS ? (unsigned)VG_NONFINITE_GRAD : 0u) |
-                      (am >= NONFINITE_BITS ? (unsigned)VG_NONFINITE_PARAM : 0u),
-                  A.flag[t]);
+  emit_amax_and_flags(am, gm, A.amax[t], A.flag[t]);
 }
 
-}  // namespace
+// ---- packing and launching -------------------------------------------------------------------------------------------
+// What an entry point asks for.  The first block is every step's; `feature` and what follows select the feature
+// kernel and what it turns on (the defaults turn everything off).
+struct StepArgs {
+  const VgAdamTensor* tensors;
+  int count;
+  unsigned* const* flags;               // NULL, or `count` flag words
+  double beta1, beta2, eps;
+  float step_size, bc2s;                // host scalars; not read when `scalars` is given
+  const float* scalars;                 // NULL, or the device scalars
+  hipStream_t st;
+  bool feature = false;
+  float* const* ema = nullptr;          // NULL (no average at all), or `count` averages
+  double ema_decay = 0.5;               // (0.5: a placeholder where nothing is averaged, or the decay is on the device)
+  const float* ema_omd = nullptr;       // the device word with (float)(1 - decay): ema_decay is not used
+  const float* clip_record = nullptr;
+  float s2 = 1.f, wdc = 0.f;            // the two words vg_adam_prepare_dev would leave in scalars[2..3]
+  bool decay_dev = false;               // ... or those of `scalars` themselves
+};
 
-namespace {
-template <bool EMA>
-int adam_launch(const VgAdamTensor* tensors, unsigned* const* flags, int count, double beta1, double beta2, double eps,
-                float step_size, float bc2s, const float* scalars, hipStream_t st, float* const* ema = nullptr,
-                double ema_decay = 0.0, const float* clip_record = nullptr) {
-  const float omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);
+StepArgs host_step(const VgAdamTensor* tensors, int count, unsigned* const* flags, double lr, double beta1, double beta2,
+                   double eps, double bias_correction1, double bias_correction2_sqrt, void* stream) {
+  // scalars are formed in double and rounded once, as torch does with its Python-side hyper-parameters
+  return {tensors, count, flags, beta1, beta2, eps, (float)(lr / bias_correction1), (float)bias_correction2_sqrt,
+          nullptr, (hipStream_t)stream};
+}
+
+StepArgs dev_step(const VgAdamTensor* tensors, int count, unsigned* const* flags, double beta1, double beta2, double eps,
+                  const float* scalars, void* stream) {
+  return {tensors, count, flags, beta1, beta2, eps, 0.f, 0.f, scalars, (hipStream_t)stream};
+}
+
+int adam_launch(const StepArgs& S) {
+  const float omb1 = (float)(1.0 - S.beta1), b2 = (float)S.beta2, omb2 = (float)(1.0 - S.beta2), eps = (float)S.eps;
   int i = 0;
-  while (i < count) {
-    std::conditional_t<EMA, AdamPackEma, AdamPack> A;
-    if constexpr (EMA) A.omd = (float)(1.0 - ema_decay);
+  while (i < S.count) {
+    AdamFeaturePack A;
+    A.omd = (float)(1.0 - S.ema_decay);
+    A.omd_dev = S.ema_omd;
+    A.s2 = S.s2;
+    A.wdc = S.wdc;
+    A.decay_dev = S.decay_dev ? 1 : 0;
     A.count = 0;
     unsigned blocks = 0;
-    while (i < count && A.count < AMAX) {
-      unsigned* const flag = flags ? flags[i] : nullptr;
-      float* ema_i = nullptr;
-      if constexpr (EMA) ema_i = ema ? ema[i] : nullptr;      // (ema == NULL: the clip step without an average)
-      const VgAdamTensor& T = tensors[i++];
+    while (i < S.count && A.count < AMAX) {
+      unsigned* const flag = S.flags ? S.flags[i] : nullptr;
+      float* const ema_i = S.ema ? S.ema[i] : nullptr;
+      const VgAdamTensor& T = S.tensors[i++];
       if (T.n == 0) continue;      // (its flag word is left untouched)
       if (!T.p || !T.g || !T.m || !T.v) return VG_ERR_BAD_ARG;
-      const unsigned long long nb = (T.n + ACHUNK - 1) / ACHUNK;
-      if (nb > 0x3fffffffULL - blocks) return VG_ERR_BAD_ARG;
+      const unsigned long long nb = chunks_of(T.n);
+      if (nb > MAX_GRID - blocks) return VG_ERR_BAD_ARG;
       const int k = A.count++;
       A.p[k] = T.p; A.g[k] = T.g; A.m[k] = T.m; A.v[k] = T.v; A.n[k] = T.n;
       A.amax[k] = reinterpret_cast<unsigned*>(T.amax);
       A.flag[k] = flag;
-      if constexpr (EMA) A.e[k] = ema_i;
+      A.e[k] = ema_i;
       A.first_block[k] = blocks;
       blocks += (unsigned)nb;
     }
     if (A.count == 0) break;
     A.first_block[A.count] = blocks;
-    if constexpr (EMA) {
-      if (clip_record) {
-        if (scalars)
-          hipLaunchKernelGGL((adam_clip_multi_kernel<true>), dim3(blocks), dim3(ANT), 0, st, A, omb1, (float)beta2, omb2,
-                             0.f, 0.f, (float)eps, scalars, clip_record);
-        else
-          hipLaunchKernelGGL((adam_clip_multi_kernel<false>), dim3(blocks), dim3(ANT), 0, st, A, omb1, (float)beta2, omb2,
-                             step_size, bc2s, (float)eps, (const float*)nullptr, clip_record);
-        VG_CHECK_LAUNCH();
-        continue;
-      }
-    }
-    if (scalars)
-      hipLaunchKernelGGL((adam_multi_kernel<true, EMA>), dim3(blocks), dim3(ANT), 0, st, A, omb1, (float)beta2, omb2, 0.f,
-                         0.f, (float)eps, scalars);
+    if (S.feature)
+      hipLaunchKernelGGL(adam_multi_feature_kernel, dim3(blocks), dim3(ANT), 0, S.st, A, omb1, b2, omb2, S.step_size,
+                         S.bc2s, eps, S.scalars, S.clip_record);
+    else if (S.scalars)      // (the plain kernels take the pack's base)
+      hipLaunchKernelGGL(adam_multi_kernel<true>, dim3(blocks), dim3(ANT), 0, S.st, static_cast<const AdamPack&>(A), omb1,
+                         b2, omb2, 0.f, 0.f, eps, S.scalars);
     else
-      hipLaunchKernelGGL((adam_multi_kernel<false, EMA>), dim3(blocks), dim3(ANT), 0, st, A, omb1, (float)beta2, omb2,
-                         step_size, bc2s, (float)eps, (const float*)nullptr);
+      hipLaunchKernelGGL(adam_multi_kernel<false>, dim3(blocks), dim3(ANT), 0, S.st, static_cast<const AdamPack&>(A), omb1,
+                         b2, omb2, S.step_size, S.bc2s, eps, (const float*)nullptr);
     VG_CHECK_LAUNCH();
   }
   return 0;
 }
+
+bool bad_tensors(const VgAdamTensor* tensors, int count) { return count < 0 || (count > 0 && !tensors); }
+bool bad_decay(double ema_decay) { return !(ema_decay > 0.0 && ema_decay < 1.0); }      // (a NaN is bad)
+
 }  // namespace
 
 extern "C" int vg_adam_step_checked(const VgAdamTensor* tensors, int count, double lr, double beta1, double beta2,
                                     double eps, double bias_correction1, double bias_correction2_sqrt,
                                     unsigned* const* nonfinite, void* stream) {
-  if (count < 0 || (count > 0 && !tensors) || !(bias_correction1 > 0.0) || !(bias_correction2_sqrt > 0.0))
-    return VG_ERR_BAD_ARG;
-  // scalars are formed in double and rounded once, as torch does with its Python-side hyper-parameters
-  return adam_launch<false>(tensors, nonfinite, count, beta1, beta2, eps, (float)(lr / bias_correction1),
-                            (float)bias_correction2_sqrt, nullptr, (hipStream_t)stream);
-}
-
-extern "C" int vg_adam_step_ema(const VgAdamTensor* tensors, int count, double lr, double beta1, double beta2, double eps,
-                                double bias_correction1, double bias_correction2_sqrt, unsigned* const* nonfinite,
-                                float* const* ema, double ema_decay, void* stream) {
-  if (count < 0 || (count > 0 && !tensors) || !(bias_correction1 > 0.0) || !(bias_correction2_sqrt > 0.0) || !ema ||
-      !(ema_decay > 0.0 && ema_decay < 1.0))
-    return VG_ERR_BAD_ARG;
-  return adam_launch<true>(tensors, nonfinite, count, beta1, beta2, eps, (float)(lr / bias_correction1),
-                           (float)bias_correction2_sqrt, nullptr, (hipStream_t)stream, ema, ema_decay);
+  if (bad_tensors(tensors, count) || !(bias_correction1 > 0.0) || !(bias_correction2_sqrt > 0.0)) return VG_ERR_BAD_ARG;
+  return adam_launch(
+      host_step(tensors, count, nonfinite, lr, beta1, beta2, eps, bias_correction1, bias_correction2_sqrt, stream));
 }
 
 extern "C" int vg_adam_step(const VgAdamTensor* tensors, int count, double lr, double beta1, double beta2, double eps,
@@ -673,17 +558,8 @@ extern "C" int vg_adam_prepare(double step, double* step_dev, int advance_device
 
 extern "C" int vg_adam_step_dev_checked(const VgAdamTensor* tensors, int count, double beta1, double beta2, double eps,
                                         const float* scalars, unsigned* const* nonfinite, void* stream) {
-  if (count < 0 || (count > 0 && !tensors) || !scalars) return VG_ERR_BAD_ARG;
-  return adam_launch<false>(tensors, nonfinite, count, beta1, beta2, eps, 0.f, 0.f, scalars, (hipStream_t)stream);
-}
-
-extern "C" int vg_adam_step_dev_ema(const VgAdamTensor* tensors, int count, double beta1, double beta2, double eps,
-                                    const float* scalars, unsigned* const* nonfinite, float* const* ema,
-                                    double ema_decay, void* stream) {
-  if (count < 0 || (count > 0 && !tensors) || !scalars || !ema || !(ema_decay > 0.0 && ema_decay < 1.0))
-    return VG_ERR_BAD_ARG;
-  return adam_launch<true>(tensors, nonfinite, count, beta1, beta2, eps, 0.f, 0.f, scalars, (hipStream_t)stream, ema,
-                           ema_decay);
+  if (bad_tensors(tensors, count) || !scalars) return VG_ERR_BAD_ARG;
+  return adam_launch(dev_step(tensors, count, nonfinite, beta1, beta2, eps, scalars, stream));
 }
 
 extern "C" int vg_adam_step_dev(const VgAdamTensor* tensors, int count, double beta1, double beta2, double eps,
@@ -691,11 +567,36 @@ extern "C" int vg_adam_step_dev(const VgAdamTensor* tensors, int count, double b
   return vg_adam_step_dev_checked(tensors, count, beta1, beta2, eps, scalars, nullptr, stream);
 }
 
+// ---- weight EMA: the entry points --------------------------------------------------------------------------------------
+extern "C" int vg_adam_step_ema(const VgAdamTensor* tensors, int count, double lr, double beta1, double beta2, double eps,
+                                double bias_correction1, double bias_correction2_sqrt, unsigned* const* nonfinite,
+                                float* const* ema, double ema_decay, void* stream) {
+  if (bad_tensors(tensors, count) || !(bias_correction1 > 0.0) || !(bias_correction2_sqrt > 0.0) || !ema ||
+      bad_decay(ema_decay))
+    return VG_ERR_BAD_ARG;
+  StepArgs S = host_step(tensors, count, nonfinite, lr, beta1, beta2, eps, bias_correction1, bias_correction2_sqrt, stream);
+  S.feature = true;
+  S.ema = ema;
+  S.ema_decay = ema_decay;
+  return adam_launch(S);
+}
+
+extern "C" int vg_adam_step_dev_ema(const VgAdamTensor* tensors, int count, double beta1, double beta2, double eps,
+                                    const float* scalars, unsigned* const* nonfinite, float* const* ema,
+                                    double ema_decay, void* stream) {
+  if (bad_tensors(tensors, count) || !scalars || !ema || bad_decay(ema_decay)) return VG_ERR_BAD_ARG;
+  StepArgs S = dev_step(tensors, count, nonfinite, beta1, beta2, eps, scalars, stream);
+  S.feature = true;
+  S.ema = ema;
+  S.ema_decay = ema_decay;
+  return adam_launch(S);
+}
+
 // ---- clipping by global norm / skipping a non-finite step: the entry points --------------------------------------------
 extern "C" size_t vg_grad_sumsq_partials(const size_t* n, int count) {
   size_t slots = 0;
   if (!n) return 0;
-  for (int i = 0; i < count; ++i) slots += (n[i] + ACHUNK - 1) / ACHUNK;
+  for (int i = 0; i < count; ++i) slots += chunks_of(n[i]);
   return slots;
 }
 
@@ -704,7 +605,7 @@ extern "C" int vg_grad_sumsq_multi(const float* const* grads, const size_t* n, i
   if (count < 0 || (count > 0 && (!grads || !n)) || !partials) return VG_ERR_BAD_ARG;
   if (vg_grad_sumsq_partials(n, count) > capacity) return VG_ERR_BAD_ARG;
   for (int i = 0; i < count; ++i)
-    if (n[i] && (!grads[i] || (n[i] + ACHUNK - 1) / ACHUNK > 0x3fffffffULL)) return VG_ERR_BAD_ARG;
+    if (n[i] && (!grads[i] || chunks_of(n[i]) > MAX_GRID)) return VG_ERR_BAD_ARG;
   size_t first = 0;      // this launch's first slot
   int i = 0;
   while (i < count) {
@@ -712,9 +613,9 @@ extern "C" int vg_grad_sumsq_multi(const float* const* grads, const size_t* n, i
     A.count = 0;
     unsigned blocks = 0;
     while (i < count && A.count < AMAX) {
-      const unsigned long long nb = (n[i] + ACHUNK - 1) / ACHUNK;
+      const unsigned long long nb = chunks_of(n[i]);
       if (nb == 0) { ++i; continue; }
-      if (nb > 0x3fffffffULL - blocks) break;      // (a launch of its own for what does not fit this grid)
+      if (nb > MAX_GRID - blocks) break;      // (a launch of its own for what does not fit this grid)
       const int k = A.count++;
       A.g[k] = grads[i];
       A.n[k] = n[i];
@@ -743,74 +644,30 @@ extern "C" int vg_grad_clip_finalize(const double* partials, size_t n_partials, 
 extern "C" int vg_adam_step_clip(const VgAdamTensor* tensors, int count, double lr, double beta1, double beta2, double eps,
                                  double bias_correction1, double bias_correction2_sqrt, unsigned* const* nonfinite,
                                  float* const* ema, double ema_decay, const float* clip_record, void* stream) {
-  if (count < 0 || (count > 0 && !tensors) || !(bias_correction1 > 0.0) || !(bias_correction2_sqrt > 0.0) ||
-      !clip_record || (ema && !(ema_decay > 0.0 && ema_decay < 1.0)))
+  if (bad_tensors(tensors, count) || !(bias_correction1 > 0.0) || !(bias_correction2_sqrt > 0.0) || !clip_record ||
+      (ema && bad_decay(ema_decay)))
     return VG_ERR_BAD_ARG;
-  return adam_launch<true>(tensors, nonfinite, count, beta1, beta2, eps, (float)(lr / bias_correction1),
-                           (float)bias_correction2_sqrt, nullptr, (hipStream_t)stream, ema, ema ? ema_decay : 0.5,
-                           clip_record);
+  StepArgs S = host_step(tensors, count, nonfinite, lr, beta1, beta2, eps, bias_correction1, bias_correction2_sqrt, stream);
+  S.feature = true;
+  S.ema = ema;
+  S.ema_decay = ema ? ema_decay : 0.5;
+  S.clip_record = clip_record;
+  return adam_launch(S);
 }
 
 extern "C" int vg_adam_step_dev_clip(const VgAdamTensor* tensors, int count, double beta1, double beta2, double eps,
                                      const float* scalars, unsigned* const* nonfinite, float* const* ema,
                                      double ema_decay, const float* clip_record, void* stream) {
-  if (count < 0 || (count > 0 && !tensors) || !scalars || !clip_record ||
-      (ema && !(ema_decay > 0.0 && ema_decay < 1.0)))
-    return VG_ERR_BAD_ARG;
-  return adam_launch<true>(tensors, nonfinite, count, beta1, beta2, eps, 0.f, 0.f, scalars, (hipStream_t)stream, ema,
-                           ema ? ema_decay : 0.5, clip_record);
+  if (bad_tensors(tensors, count) || !scalars || !clip_record || (ema && bad_decay(ema_decay))) return VG_ERR_BAD_ARG;
+  StepArgs S = dev_step(tensors, count, nonfinite, beta1, beta2, eps, scalars, stream);
+  S.feature = true;
+  S.ema = ema;
+  S.ema_decay = ema ? ema_decay : 0.5;
+  S.clip_record = clip_record;
+  return adam_launch(S);
 }
 
 // ---- weight decay inside the step, hyper-parameters on the device: the entry points -----------------------------------
-namespace {
-// EDEV (with `scalars` only): (float)(1 - decay) is read from the device word `ema_omd`, ema_decay is not used.
-template <bool EDEV = false>
-int adam_decay_launch(const VgAdamTensor* tensors, unsigned* const* flags, int count, double beta1, double beta2,
-                      double eps, float step_size, float bc2s, float s2, float wdc, const float* scalars, hipStream_t st,
-                      float* const* ema, double ema_decay, const float* clip_record, const float* ema_omd = nullptr) {
-  const float omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);
-  int i = 0;
-  while (i < count) {
-    std::conditional_t<EDEV, AdamPackDecayDev, AdamPackDecay> A;
-    A.omd = (float)(1.0 - ema_decay);
-    if constexpr (EDEV) A.omd_dev = ema_omd;
-    A.s2 = s2;
-    A.wdc = wdc;
-    A.count = 0;
-    unsigned blocks = 0;
-    while (i < count && A.count < AMAX) {
-      unsigned* const flag = flags ? flags[i] : nullptr;
-      float* const ema_i = ema ? ema[i] : nullptr;
-      const VgAdamTensor& T = tensors[i++];
-      if (T.n == 0) continue;      // (its flag word is left untouched)
-      if (!T.p || !T.g || !T.m || !T.v) return VG_ERR_BAD_ARG;
-      const unsigned long long nb = (T.n + ACHUNK - 1) / ACHUNK;
-      if (nb > 0x3fffffffULL - blocks) return VG_ERR_BAD_ARG;
-      const int k = A.count++;
-      A.p[k] = T.p; A.g[k] = T.g; A.m[k] = T.m; A.v[k] = T.v; A.n[k] = T.n;
-      A.amax[k] = reinterpret_cast<unsigned*>(T.amax);
-      A.flag[k] = flag;
-      A.e[k] = ema_i;
-      A.first_block[k] = blocks;
-      blocks += (unsigned)nb;
-    }
-    if (A.count == 0) break;
-    A.first_block[A.count] = blocks;
-    if constexpr (EDEV)
-      hipLaunchKernelGGL((adam_decay_multi_kernel<true, true>), dim3(blocks), dim3(ANT), 0, st, A, omb1, (float)beta2,
-                         omb2, 0.f, 0.f, (float)eps, scalars, clip_record);
-    else if (scalars)
-      hipLaunchKernelGGL((adam_decay_multi_kernel<true>), dim3(blocks), dim3(ANT), 0, st, A, omb1, (float)beta2, omb2, 0.f,
-                         0.f, (float)eps, scalars, clip_record);
-    else
-      hipLaunchKernelGGL((adam_decay_multi_kernel<false>), dim3(blocks), dim3(ANT), 0, st, A, omb1, (float)beta2, omb2,
-                         step_size, bc2s, (float)eps, (const float*)nullptr, clip_record);
-    VG_CHECK_LAUNCH();
-  }
-  return 0;
-}
-}  // namespace
-
 extern "C" int vg_adam_prepare_dev(double step, double* step_dev, int advance_device_counter, const double* hyper,
                                    int decoupled, double beta1, double beta2, float* scalars, void* stream) {
   if (!hyper || !scalars || (advance_device_counter ? !step_dev : !(step >= 1.0)) || !(beta1 >= 0.0 && beta1 < 1.0) ||
@@ -826,30 +683,41 @@ extern "C" int vg_adam_step_decay(const VgAdamTensor* tensors, int count, double
                                   double eps, double bias_correction1, double bias_correction2_sqrt,
                                   unsigned* const* nonfinite, float* const* ema, double ema_decay,
                                   const float* clip_record, double weight_decay, int decoupled, void* stream) {
-  if (count < 0 || (count > 0 && !tensors) || !(bias_correction1 > 0.0) || !(bias_correction2_sqrt > 0.0) ||
-      (ema && !(ema_decay > 0.0 && ema_decay < 1.0)) || !(weight_decay >= 0.0))      // (a NaN fails the comparison)
+  if (bad_tensors(tensors, count) || !(bias_correction1 > 0.0) || !(bias_correction2_sqrt > 0.0) ||
+      (ema && bad_decay(ema_decay)) || !(weight_decay >= 0.0))      // (a NaN fails the comparison)
     return VG_ERR_BAD_ARG;
-  // the two words vg_adam_prepare_dev would leave in scalars[2..3]
-  const float s2 = (decoupled && weight_decay != 0.0) ? decoupled_factor(lr, weight_decay) : 1.f;
-  const float wdc = decoupled ? 0.f : (float)weight_decay;
-  return adam_decay_launch(tensors, nonfinite, count, beta1, beta2, eps, (float)(lr / bias_correction1),
-                           (float)bias_correction2_sqrt, s2, wdc, nullptr, (hipStream_t)stream, ema,
-                           ema ? ema_decay : 0.5, clip_record);
+  StepArgs S = host_step(tensors, count, nonfinite, lr, beta1, beta2, eps, bias_correction1, bias_correction2_sqrt, stream);
+  S.feature = true;
+  S.ema = ema;
+  S.ema_decay = ema ? ema_decay : 0.5;
+  S.clip_record = clip_record;
+  S.s2 = (decoupled && weight_decay != 0.0) ? decoupled_factor(lr, weight_decay) : 1.f;
+  S.wdc = decoupled ? 0.f : (float)weight_decay;
+  return adam_launch(S);
 }
 
 extern "C" int vg_adam_step_dev_decay(const VgAdamTensor* tensors, int count, double beta1, double beta2, double eps,
                                       const float* scalars, unsigned* const* nonfinite, float* const* ema,
                                       double ema_decay, const float* clip_record, void* stream) {
-  if (count < 0 || (count > 0 && !tensors) || !scalars || (ema && !(ema_decay > 0.0 && ema_decay < 1.0)))
-    return VG_ERR_BAD_ARG;
-  return adam_decay_launch(tensors, nonfinite, count, beta1, beta2, eps, 0.f, 0.f, 1.f, 0.f, scalars,
-                           (hipStream_t)stream, ema, ema ? ema_decay : 0.5, clip_record);
+  if (bad_tensors(tensors, count) || !scalars || (ema && bad_decay(ema_decay))) return VG_ERR_BAD_ARG;
+  StepArgs S = dev_step(tensors, count, nonfinite, beta1, beta2, eps, scalars, stream);
+  S.feature = true;
+  S.ema = ema;
+  S.ema_decay = ema ? ema_decay : 0.5;
+  S.clip_record = clip_record;
+  S.decay_dev = true;
+  return adam_launch(S);
 }
 
 extern "C" int vg_adam_step_dev_ema_dev(const VgAdamTensor* tensors, int count, double beta1, double beta2, double eps,
                                         const float* scalars, unsigned* const* nonfinite, float* const* ema,
                                         const float* ema_omd, const float* clip_record, void* stream) {
-  if (count < 0 || (count > 0 && !tensors) || !scalars || !ema || !ema_omd) return VG_ERR_BAD_ARG;
-  return adam_decay_launch<true>(tensors, nonfinite, count, beta1, beta2, eps, 0.f, 0.f, 1.f, 0.f, scalars,
-                                 (hipStream_t)stream, ema, 0.5, clip_record, ema_omd);
+  if (bad_tensors(tensors, count) || !scalars || !ema || !ema_omd) return VG_ERR_BAD_ARG;
+  StepArgs S = dev_step(tensors, count, nonfinite, beta1, beta2, eps, scalars, stream);
+  S.feature = true;
+  S.ema = ema;
+  S.ema_omd = ema_omd;
+  S.clip_record = clip_record;
+  S.decay_dev = true;
+  return adam_launch(S);
 }

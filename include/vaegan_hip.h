@@ -460,7 +460,12 @@ int vg_dot_sigmoid_bce_bwd(const float* dlogit, const float* gloss, const float*
  * p -= (lr / bias_correction1) * m / (sqrt(v) / bias_correction2_sqrt + eps),
  * with bias_correction1 = 1 - beta1^step and bias_correction2_sqrt = sqrt(1 - beta2^step) computed by
  * the caller (double).  `tensors` is a HOST array of DEVICE pointers (fp32, n elements each);
- * any number of tensors, 24 per kernel launch.  No amsgrad / maximize; weight decay: vg_adam_step_decay below. */
+ * any number of tensors, 24 per kernel launch.  No amsgrad / maximize; weight decay: vg_adam_step_decay below.
+ * Two kernels stand behind the step entry points: the plain step (vg_adam_step, _checked, _dev, _dev_checked) and one
+ * feature kernel, which every other entry point launches with what it turns on -- the averages, the clip record, the
+ * weight decay, the decay word on the device -- as run-time arguments; element by element it gives the plain step's
+ * bits.  `scalars` is two floats for the entry points paired with vg_adam_prepare (_dev, _dev_checked, _dev_ema,
+ * _dev_clip: scalars[2..3] are never read) and four for those paired with vg_adam_prepare_dev (_dev_decay, _dev_ema_dev). */
 typedef struct {
   float* p;
   const float* g;

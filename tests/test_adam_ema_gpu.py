@@ -80,8 +80,17 @@ def _fresh_grads(sts, gen, scale=0.1):
             st[i]["g"].copy_(g)
 
 
-def _step(st, mode, step, words=None, amax=None, decay=DECAY, null_ema=NULL_EMA):
-    """One step through the C ABI.  ``mode``: "checked" | "ema" | "dev_ema"."""
+def _two_scalars():
+    """The two device scalars ``vg_adam_prepare`` writes, as the front of a four-float buffer whose words [2:4] hold NaN.
+    The entry points paired with ``vg_adam_prepare`` own two words: had one of them read scalars[2..3] (the decay words
+    of ``vg_adam_prepare_dev``), every weight would decay by NaN and no bit comparison below would hold."""
+    buf = torch.full((4,), float("nan"), device="cuda")
+    return buf, buf[:2]
+
+
+def _step(st, mode, step, words=None, amax=None, decay=DECAY, null_ema=NULL_EMA, omd_word=None):
+    """One step through the C ABI.  ``mode``: "checked" | "ema" | "dev_ema" | "dev_ema_dev" (the decay read from the
+    device word ``omd_word``; no weight decay, no record)."""
     from disentangle_mlp_amd import _lib
     from disentangle_mlp_amd._lib import check
     from disentangle_mlp_amd.optim import _AdamTensor
@@ -99,10 +108,21 @@ def _step(st, mode, step, words=None, amax=None, decay=DECAY, null_ema=NULL_EMA)
         check(lib.vg_adam_step_checked(arr, n, LR, B1, B2, EPS, bc1, bc2s, flags, stream), "checked")
     elif mode == "ema":
         check(lib.vg_adam_step_ema(arr, n, LR, B1, B2, EPS, bc1, bc2s, flags, ema, decay, stream), "ema")
-    else:
-        scal = torch.zeros(2, device="cuda")
+    elif mode == "dev_ema":
+        buf, scal = _two_scalars()
         check(lib.vg_adam_prepare(float(step), None, 0, LR, B1, B2, scal.data_ptr(), stream), "vg_adam_prepare")
         check(lib.vg_adam_step_dev_ema(arr, n, B1, B2, EPS, scal.data_ptr(), flags, ema, decay, stream), "dev_ema")
+        torch.cuda.synchronize()
+        assert bool(torch.isnan(buf[2:]).all()) and bool(torch.isfinite(scal).all())
+    elif mode == "dev_ema_dev":
+        hyper = torch.tensor([LR, 0.0], dtype=torch.float64, device="cuda")
+        scal = torch.zeros(4, device="cuda")
+        check(lib.vg_adam_prepare_dev(float(step), None, 0, hyper.data_ptr(), 0, B1, B2, scal.data_ptr(), stream),
+              "vg_adam_prepare_dev")
+        check(lib.vg_adam_step_dev_ema_dev(arr, n, B1, B2, EPS, scal.data_ptr(), flags, ema, omd_word.data_ptr(), None,
+                                           stream), "dev_ema_dev")
+    else:
+        raise ValueError(mode)
     torch.cuda.synchronize()
 
 
@@ -209,6 +229,39 @@ def test_nan_propagates_into_its_own_ema_alone():
             assert not bool(nan.any()) and bool(torch.isfinite(s["e"]).all()), i
         for name in "pmv":
             assert torch.equal(_bits(s[name]), _bits(b[i][name])), (i, name)
+
+
+def test_host_decay_that_rounds_to_one_still_lerps_and_only_the_device_word_follows():
+    """Following the weights (e <- the bits of p) belongs to the DEVICE word 1.0f alone.  A host decay whose
+    ``(float)(1 - decay)`` rounds to 1.0f keeps the lerp: e <- e + 1 * (p_new - e), which is fl(e + fl(p_new - e)) however
+    the product and the sum are contracted -- and that is not p_new wherever p_new - e rounds."""
+    decay = 1e-9
+    assert 0.0 < decay < 1.0 and float(torch.tensor(1.0 - decay, dtype=torch.float64).float()) == 1.0
+    base = _state(8)
+    a, b, c = _clone(base), _clone(base), _clone(base)
+    _fresh_grads((a, b, c), torch.Generator().manual_seed(9))
+    _step(a, "ema", 1.0, decay=decay)
+    _step(b, "checked", 1.0)
+    differ = 0
+    for i, (x, y, s0) in enumerate(zip(a, b, base)):
+        for name in "pmv":
+            assert torch.equal(_bits(x[name]), _bits(y[name])), (i, name)
+        if i in NULL_EMA:
+            assert torch.equal(_bits(x["ebuf"]), _bits(s0["ebuf"])), i
+            continue
+        want = s0["e"] + (x["p"] - s0["e"])                        # torch on the device: two fp32 roundings
+        assert torch.equal(_bits(x["e"]), _bits(want)), i
+        differ += int((_bits(want) != _bits(x["p"])).sum())
+    assert differ > 0                                              # (the lerp and the copy are told apart)
+    # the same inputs, the decay word 1.0f on the device: the average IS the new weights
+    _step(c, "dev_ema_dev", 1.0, omd_word=torch.ones(1, device="cuda"))
+    for i, (x, y, s0) in enumerate(zip(c, b, base)):
+        for name in "pmv":
+            assert torch.equal(_bits(x[name]), _bits(y[name])), (i, name)
+        if i in NULL_EMA:
+            assert torch.equal(_bits(x["ebuf"]), _bits(s0["ebuf"])), i
+        else:
+            assert torch.equal(_bits(x["e"]), _bits(x["p"])), i
 
 
 @pytest.mark.parametrize("capturable", [False, True], ids=["host-scalars", "device-scalars"])

@@ -234,7 +234,10 @@ def _step(st, mode, step, words, amax, rec=None, ema_on=True, grads=None):
     if ema_on:
         ema = (ctypes.c_void_p * n)(*[None if i in NULL_EMA else s["e"].data_ptr() for i, s in enumerate(st)])
     bc1, bc2s = 1.0 - B1 ** step, (1.0 - B2 ** step) ** 0.5
-    scal = torch.zeros(2, device="cuda")
+    # two scalars in front of two NaN words: the entry points paired with vg_adam_prepare own scalars[0..1] alone -- had
+    # one read scalars[2..3] (the decay words of vg_adam_prepare_dev), no bit comparison against the host-scalar variants
+    # would hold
+    scal = torch.full((4,), float("nan"), device="cuda")[:2]
     if mode.startswith("dev"):
         check(lib.vg_adam_prepare(float(step), None, 0, LR, B1, B2, scal.data_ptr(), stream), "vg_adam_prepare")
     if mode == "clip":

@@ -4,6 +4,7 @@ needed (``ctx.needs_input_grad``) is skipped -- e.g. the discriminator's weight
 gradients while it only relays gradients to the decoder (SURVEY.md section 3.1
 item 3: those gradients are discarded by the reference's next ``zero_grad``).
 """
+import math
 import os
 import threading
 
@@ -519,6 +520,35 @@ class ReparamKLFn(Function):
         return gmu, glv, None, None
 
 
+class ReparamTCFn(Function):
+    """z = mu + eps*exp(logvar/2) and the beta-TCVAE decomposition of the KL term by minibatch-weighted sampling
+    (Chen et al. 2018): ``loss = alpha*mi + beta*tc + gamma*dwkl``, all three summed over the
+    batch, in one fused kernel pair each way.  Returns ``z``, ``loss`` and the non-differentiable ``[3]`` tensor
+    ``(mi, tc, dwkl)``.  ``beta``: a float or the device word, as `ReparamKLFn`; ``log_bn`` = log(B * dataset size)
+    moves the values of the parts and no gradient."""
+
+    @staticmethod
+    def forward(ctx, mu, logvar, eps, beta, alpha, gamma, log_bn):
+        z, out4, lse_joint, lse_dim = ops.reparam_tc_fwd(mu, logvar, eps, beta, alpha, gamma, log_bn)
+        ctx.beta, ctx.alpha, ctx.gamma = beta, alpha, gamma      # (a tensor is kept as the word itself, as in ReparamKLFn)
+        loss, parts = out4[0], out4[1:]
+        ctx.mark_non_differentiable(parts)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(mu, logvar, eps, z, lse_joint, lse_dim)
+        return z, loss, parts
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gz, gloss, _):
+        if gz is None and gloss is None:
+            return None, None, None, None, None, None, None
+        mu, logvar, eps, z, lse_joint, lse_dim = ctx.saved_tensors
+        gz = gz.contiguous() if gz is not None else None
+        gloss = gloss.contiguous() if gloss is not None else None
+        gmu, glv = ops.reparam_tc_bwd(gz, mu, logvar, eps, z, lse_joint, lse_dim, gloss, ctx.beta, ctx.alpha, ctx.gamma)
+        return gmu, glv, None, None, None, None, None
+
+
 class KLRowsFn(Function):
     """Encoder_celeba's per-sample KL (model.py:321) together with z."""
 
@@ -676,6 +706,15 @@ def _beta_arg(beta):
 
 def reparam_kl(mu, logvar, eps, beta):
     return ReparamKLFn.apply(mu, logvar, eps, _beta_arg(beta))
+
+
+def reparam_tc(mu, logvar, eps, beta, alpha=1.0, gamma=1.0, dataset_size=None):
+    """`ReparamTCFn`: ``(z, loss, parts)`` with ``loss = alpha*mi + beta*tc + gamma*dwkl`` and ``parts = (mi, tc, dwkl)``.
+    ``dataset_size``: the N of minibatch-weighted sampling, the number of samples the batch was drawn from."""
+    if dataset_size is None or not dataset_size >= 1:
+        raise ValueError(f"reparam_tc: dataset_size must be the number of training samples (>= 1), got {dataset_size!r}")
+    log_bn = math.log(float(mu.shape[0]) * float(dataset_size))
+    return ReparamTCFn.apply(mu, logvar, eps, _beta_arg(beta), float(alpha), float(gamma), log_bn)
 
 
 def kld_loss(mu, logvar, beta):

@@ -540,3 +540,12 @@ class VAE(nn.Module, _DecoderMixin):
             eps = torch.randn_like(mu)
         z, kl = F.reparam_kl(mu, logvar, eps, beta)
         return self.decode(z), mu, logvar, kl
+
+    def forward_with_tc(self, x, eps, beta, alpha, gamma, dataset_size):
+        """`forward_with_kl` with the KL term decomposed (functional.reparam_tc): returns ``recon, mu, logvar, loss,
+        parts`` -- ``loss = alpha*mi + beta*tc + gamma*dwkl``, ``parts`` the ``[3]`` tensor ``(mi, tc, dwkl)``."""
+        mu, logvar = self.encode(x)
+        if eps is None:
+            eps = torch.randn_like(mu)
+        z, loss, parts = F.reparam_tc(mu, logvar, eps, beta, alpha, gamma, dataset_size)
+        return self.decode(z), mu, logvar, loss, parts

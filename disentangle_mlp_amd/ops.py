@@ -1050,6 +1050,55 @@ def reparam_kl_bwd(gz, mu, logvar, eps, gkl, beta):
     return gmu, glv
 
 
+def reparam_tc_fwd(mu, logvar, eps, beta, alpha, gamma, log_bn):
+    """Reparameterisation + the beta-TCVAE decomposition of the KL term (vg_reparam_tc_fwd).
+    ``beta`` (the total-correlation weight): a float or the device word, as `reparam_kl_fwd`; ``alpha`` / ``gamma``: the
+    weights of the mutual-information and dimension-wise-KL parts; ``log_bn``: log(B * dataset size).  Returns ``z``,
+    ``out4`` = [loss, mi, tc, dwkl] and the two log-sum-exps the backward reads (``lse_joint`` [B] fp64, ``lse_dim`` [B, D])."""
+    lib = _lib.load()
+    _req(mu, "mu"), _req(logvar, "logvar"), _req(eps, "eps")
+    if mu.dim() != 2 or logvar.shape != mu.shape or eps.shape != mu.shape:
+        raise RuntimeError("reparam_tc: mu, logvar and eps must be [B, D] tensors of one shape")
+    B, D = mu.shape
+    z, lse_dim = torch.empty_like(mu), torch.empty_like(mu)
+    out4 = torch.empty(4, dtype=torch.float32, device=mu.device)
+    lse_joint = torch.empty(B, dtype=torch.float64, device=mu.device)
+    nbytes = lib.vg_reparam_tc_workspace_bytes(B, D)
+    ws = workspace(nbytes, mu.device)
+    head = (mu.data_ptr(), logvar.data_ptr(), eps.data_ptr(), z.data_ptr(), out4.data_ptr(), lse_joint.data_ptr(),
+            lse_dim.data_ptr(), B, D, float(alpha))
+    tail = (float(gamma), float(log_bn), ws.data_ptr(), ws.numel(), _stream())
+    if isinstance(beta, torch.Tensor):
+        check(lib.vg_reparam_tc_fwd_dev(*head, _beta_word(beta).data_ptr(), *tail), "vg_reparam_tc_fwd_dev")
+    else:
+        check(lib.vg_reparam_tc_fwd(*head, float(beta), *tail), "vg_reparam_tc_fwd")
+    return z, out4, lse_joint, lse_dim
+
+
+def reparam_tc_bwd(gz, mu, logvar, eps, z, lse_joint, lse_dim, gloss, beta, alpha, gamma):
+    """gz: tensor or None; gloss: 0-dim device tensor (upstream gradient of the weighted loss) or None."""
+    lib = _lib.load()
+    for t, name in ((mu, "mu"), (logvar, "logvar"), (eps, "eps"), (z, "z"), (lse_dim, "lse_dim")):
+        _req(t, name)
+    if gz is not None:
+        _req(gz, "gz")
+    if gloss is not None:
+        _req(gloss, "gloss")
+    if not lse_joint.is_cuda or lse_joint.dtype != torch.float64 or not lse_joint.is_contiguous():
+        raise RuntimeError("reparam_tc_bwd: lse_joint must be the contiguous float64 device tensor of reparam_tc_fwd")
+    B, D = mu.shape
+    gmu, glv = torch.empty_like(mu), torch.empty_like(mu)
+    ws = workspace(lib.vg_reparam_tc_workspace_bytes(B, D), mu.device)
+    head = (_ptr(gz), mu.data_ptr(), logvar.data_ptr(), eps.data_ptr(), z.data_ptr(), lse_joint.data_ptr(),
+            lse_dim.data_ptr(), _ptr(gloss), float(alpha))
+    tail = (float(gamma), gmu.data_ptr(), glv.data_ptr(), B, D, ws.data_ptr(), ws.numel(), _stream())
+    if isinstance(beta, torch.Tensor):
+        check(lib.vg_reparam_tc_bwd_dev(*head, _beta_word(beta).data_ptr(), *tail), "vg_reparam_tc_bwd_dev")
+    else:
+        check(lib.vg_reparam_tc_bwd(*head, float(beta), *tail), "vg_reparam_tc_bwd")
+    return gmu, glv
+
+
 def sqdiff_loss(a, b, scale, gscale=1.0, want_grad=True):
     lib = _lib.load()
     _req(a, "a"), _req(b, "b")

@@ -652,6 +652,47 @@ class _GraphedSteps:
                                 f"{type(sched).__name__} for {name}")
             self.lr_schedulers[name] = sched
 
+    # ---- the KL term decomposed (beta-TCVAE) --------------------------------------------------------------------------
+    tc_decomposition = None   # (alpha, gamma): the weights of the mutual-information and the dimension-wise-KL parts
+    dataset_size = None       # N of minibatch-weighted sampling
+
+    def _tc_args(self, tc_decomposition, dataset_size, has_beta=True):
+        """Validate ``tc_decomposition=(alpha, gamma)`` and ``dataset_size`` of a trainer's constructor."""
+        if tc_decomposition is None and dataset_size is None:
+            return
+        if not has_beta:
+            raise TypeError(f"{type(self).__name__} has no KL term: tc_decomposition does not apply")
+        if tc_decomposition is not None:
+            try:
+                alpha, gamma = (float(v) for v in tc_decomposition)
+            except (TypeError, ValueError):
+                raise TypeError(f"tc_decomposition must be a pair (alpha, gamma) of floats, got {tc_decomposition!r}") from None
+            if not (np.isfinite(alpha) and np.isfinite(gamma)):
+                raise ValueError(f"tc_decomposition: alpha and gamma must be finite, got {tc_decomposition!r}")
+            self.tc_decomposition = (alpha, gamma)
+        if dataset_size is not None:
+            if int(dataset_size) != dataset_size or int(dataset_size) < 1:
+                raise ValueError(f"dataset_size must be an integer >= 1, got {dataset_size!r}")
+            self.dataset_size = int(dataset_size)
+
+    def _dataset_size_from(self, loader):
+        """`train_epoch` / `fit`: a ``dataset_size`` that was not given is the loader's ``len(loader.dataset)``."""
+        if self.tc_decomposition is not None and self.dataset_size is None:
+            self.dataset_size = int(len(loader.dataset))
+
+    def _forward_kl(self, net, data, eps):
+        """The encoder-side forward of the KL phase: ``recon, mu, logvar, kld, parts`` -- the analytic KL (``parts`` is
+        None), or with ``tc_decomposition`` the decomposed one, whose total-correlation weight is `beta`."""
+        if self.tc_decomposition is None:
+            return (*net.forward_with_kl(data, eps, self._kl_beta()), None)
+        alpha, gamma = self.tc_decomposition
+        return net.forward_with_tc(data, eps, self._kl_beta(), alpha, gamma, self.dataset_size)
+
+    @staticmethod
+    def _tc_outputs(parts):
+        """The additional loss keys -- present only with ``tc_decomposition``."""
+        return {} if parts is None else dict(mi=parts[0], tc=parts[1], dwkl=parts[2])
+
     def _kl_beta(self):
         """What the KL kernels take: the device word with ``device_hyper`` (eager and captured alike), else the float."""
         return self._beta_dev if self._beta_dev is not None else self.beta
@@ -664,6 +705,9 @@ class _GraphedSteps:
             self._beta_written = self.beta
 
     def _begin_step(self):
+        if self.tc_decomposition is not None and self.dataset_size is None:
+            raise ValueError(f"{type(self).__name__}: tc_decomposition needs dataset_size (the number of training samples): "
+                             "pass dataset_size=..., or train through train_epoch / fit, which take it from the loader")
         if self.beta_schedule is not None:
             self.beta = float(self.beta_schedule(self.iteration))
         self._sync_beta()
@@ -835,6 +879,7 @@ class _GraphedSteps:
                 self.nonfinite_guard,        # (checked or unchecked Adam launches)
                 self.max_grad_norm, self.skip_nonfinite,      # (the norm pass and the clip step, or neither)
                 self.device_hyper,           # (lr, weight decay and beta read from device words, or frozen arguments)
+                self.tc_decomposition and (*self.tc_decomposition, self.dataset_size),      # (frozen kernel arguments)
                 tuple(net.training for net in self._nets()),
                 tuple(p.requires_grad for net in self._nets() for p in net.parameters()))
 
@@ -914,7 +959,18 @@ class BetaVAEGANTrainer(_GraphedSteps):
     per iteration).  The decay lives in a device word, so a value that changes every iteration still replays ONE graph.
     The discriminator is not averaged.  ``fit`` / ``evaluate(use_ema=True)`` sample, reconstruct and score through the
     shadow; `recalibrate_ema_bn` gives it BatchNorm running statistics of its own for eval-mode use; checkpoints carry
-    it under ``encoder_decoder_ema``.  Data parallel: every rank forms the same average from the same weights."""
+    it under ``encoder_decoder_ema``.  Data parallel: every rank forms the same average from the same weights.
+
+    ``tc_decomposition=(alpha, gamma)`` (default: none -- then every launch, loss key, capture key and checkpoint key is
+    what it was): phase 3's KL term becomes the beta-TCVAE decomposition by minibatch-weighted sampling (Chen et al.
+    2018), ``alpha * mutual information + beta * total correlation + gamma * dimension-wise KL``,
+    on one fused kernel pair (`VAE.forward_with_tc`).  The total-correlation weight is the trainer's own `beta`, so
+    ``beta_schedule``, `set_beta` and ``device_hyper`` apply unchanged and a beta annealed every iteration still replays
+    ONE graph.  ``kld`` of the returned dict is the weighted loss that was backpropagated; ``mi``, ``tc``, ``dwkl`` (each
+    summed over the batch) are added to it.  ``dataset_size``: the N of the estimator, the number of training samples;
+    `fit` / `train_epoch` take it from ``len(loader.dataset)`` when it was not given, `step` without one raises
+    ValueError.  The option adds no checkpoint state.  Data parallel: every rank estimates the three parts from its LOCAL
+    batch -- the pair terms never cross ranks -- so the estimator is replica-local, as the BatchNorm statistics are."""
 
     _optimizer_names = ("optimizerEG", "optimizerD")
     _ema_names = ("netEG", "optimizerEG", "encoder_decoder_ema")
@@ -925,11 +981,13 @@ class BetaVAEGANTrainer(_GraphedSteps):
                  graph: Optional[bool] = None, nonfinite_guard: Optional[bool] = None,
                  max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False,
                  lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0, decoupled_weight_decay: bool = False,
-                 device_hyper: Optional[bool] = None, ema_decay=None):
+                 device_hyper: Optional[bool] = None, ema_decay=None, tc_decomposition=None,
+                 dataset_size: Optional[int] = None):
         self.opt = opt or ModelOpt()
         self.device = torch.device(device)
         _use_tuned_gemms(self.device)
         self.beta = float(beta)
+        self._tc_args(tc_decomposition, dataset_size)
         self.max_grad_norm, self.skip_nonfinite = max_grad_norm, bool(skip_nonfinite)
         self.world = _dist_world()
         self.dp = (self.world > 1) if data_parallel is None else data_parallel
@@ -1111,7 +1169,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
 
         # ---- phase 3: "encoder" -- again every EG parameter moves (:167-193)
         self._zero(netEG, self.flat_eg)
-        recon, mu, logvar, kld = netEG.forward_with_kl(data, eps3, self._kl_beta())
+        recon, mu, logvar, kld, parts = self._forward_kl(netEG, data, eps3)
         mse3 = F.reconstruction_loss(recon, data)
         _backward([kld, mse3])
         self._exchange(self.flat_eg)
@@ -1119,7 +1177,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
             grad_hook("EG3", netEG)
         self.optimizerEG.step()
         ops.invalidate_packed_filters(self._eg_params)
-        out.update(kld=kld.detach(), mse_enc=mse3.detach())
+        out.update(kld=kld.detach(), mse_enc=mse3.detach(), **self._tc_outputs(parts))
         self.iteration += 1
         return out
 
@@ -1139,6 +1197,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
         global-batch values the reference's DataParallel run would log, and the labels come -- unless
         ``label_rng`` is given -- from the trainer's own stream, seeded alike on every rank: one label pair
         per global batch, as in the reference's single process."""
+        self._dataset_size_from(loader)
         acc = torch.zeros(2, dtype=torch.float64, device=self.device)     # [sum of mse_enc, sum of mean D(x)]
         n_it = 0
         if label_rng is None and self.world > 1:
@@ -1182,6 +1241,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
         import os
         from . import image_io
         rows = []
+        self._dataset_size_from(loader)
         net = self._sampling_net(use_ema)
         fid_extractor = self._fid_extractor(fid_inception, fid_feature_extractor) if calc_fid and fid_on_device else None
         for epoch in range(start_epoch, epochs):
@@ -1337,7 +1397,8 @@ class VAETrainer(_GraphedSteps):
     """new_vae.py:33-37 construction, :39-48 loss, :53-59 step.  ``graph``, ``max_grad_norm``, ``skip_nonfinite``, and the
     schedule arguments (``lr_scheduler``, ``beta_schedule``, ``weight_decay``, ``decoupled_weight_decay``,
     ``device_hyper``): as BetaVAEGANTrainer.  ``ema_decay``: as there, of the one network -- `ema_model` shadows `model`,
-    the checkpoint key is ``VAE_model_ema``."""
+    the checkpoint key is ``VAE_model_ema``.  ``tc_decomposition`` / ``dataset_size``: as there, of the step's KL term
+    (`train_epoch` fills a ``dataset_size`` that was not given); replica-local under data parallelism."""
 
     _optimizer_names = ("optimizer",)
     _ema_names = ("model", "optimizer", "VAE_model_ema")
@@ -1347,11 +1408,13 @@ class VAETrainer(_GraphedSteps):
                  fused_adam: bool = True, capturable: Optional[bool] = None, graph: Optional[bool] = None,
                  nonfinite_guard: Optional[bool] = None, max_grad_norm: Optional[float] = None,
                  skip_nonfinite: bool = False, lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0,
-                 decoupled_weight_decay: bool = False, device_hyper: Optional[bool] = None, ema_decay=None):
+                 decoupled_weight_decay: bool = False, device_hyper: Optional[bool] = None, ema_decay=None,
+                 tc_decomposition=None, dataset_size: Optional[int] = None):
         self.opt = opt or ModelOpt()
         self.device = torch.device(device)
         _use_tuned_gemms(self.device)
         self.beta = float(beta)
+        self._tc_args(tc_decomposition, dataset_size)
         self.max_grad_norm, self.skip_nonfinite = max_grad_norm, bool(skip_nonfinite)
         torch.manual_seed(seed)
         m = VAE(self.opt)
@@ -1375,17 +1438,19 @@ class VAETrainer(_GraphedSteps):
     def _guarded_optimizers(self):
         return [("model", self.model, self.optimizer)]
 
-    def step(self, data, eps=None):
+    def step(self, data, eps=None, grad_hook=None):
+        """``grad_hook(phase, net)`` (tests): called with ``("VAE", model)`` right before the optimizer step; such an
+        iteration is eager, as BetaVAEGANTrainer's."""
         self._begin_step()
-        out = self._step_any(data, eps)
+        out = self._step_any(data, eps, grad_hook)
         self._end_step()
         return out
 
-    def _step_any(self, data, eps):
+    def _step_any(self, data, eps, grad_hook=None):
         def eager(inp=None):
             with ops.packed_filter_scope():       # one optimizer step at the end: packs live for the iteration
-                return self._step(data, inp["eps"] if inp is not None else eps)
-        if not self._graph_usable((self.optimizer,), data, None):
+                return self._step(data, inp["eps"] if inp is not None else eps, grad_hook)
+        if not self._graph_usable((self.optimizer,), data, grad_hook):
             return eager()
 
         def run(inp, real_dev, fake_dev):
@@ -1397,29 +1462,32 @@ class VAETrainer(_GraphedSteps):
                                                        eps=eps if eps is not None else self._draw_into(cap, "eps", data.size(0))),
                                  (0.0, 0.0), run, [self.optimizer], (self.model,), eager)
 
-    def _step(self, data, eps):
+    def _step(self, data, eps, grad_hook=None):
         if eps is None:                       # model.py:534, from this replica's own stream
             eps = torch.randn(data.size(0), self.opt.n_hidden, device=self.device, generator=self.latent_generator)
-        return self._run_with_pack_plan(lambda prepack: self._step_body(data, eps, prepack), {"vae": self.model})
+        return self._run_with_pack_plan(lambda prepack: self._step_body(data, eps, prepack, grad_hook), {"vae": self.model})
 
-    def _step_body(self, data, eps, prepack):
+    def _step_body(self, data, eps, prepack, grad_hook=None):
         prepack()                             # the filters the previous optimizer step changed: one pack launch
         if self.flat is not None:
             self.flat.zero_and_attach()
         else:
             _zero_grads(self.model)
-        recon, mu, logvar, kld = self.model.forward_with_kl(data, eps, self._kl_beta())
+        recon, mu, logvar, kld, parts = self._forward_kl(self.model, data, eps)
         mse = F.reconstruction_loss(recon, data)
         _backward([mse, kld])
         if self.flat is not None:
             self.flat.finish()
+        if grad_hook:
+            grad_hook("VAE", self.model)
         self.optimizer.step()
         self.iteration += 1
-        return dict(mse=mse.detach(), kld=kld.detach())
+        return dict(mse=mse.detach(), kld=kld.detach(), **self._tc_outputs(parts))
 
     def train_epoch(self, loader, max_iterations=None):
         """``train(epoch)`` of new_vae.py:48-68: returns ``avg_loss`` = sum over the epoch of
         (MSE + KLD) / len(dataset); one device -> host read per epoch."""
+        self._dataset_size_from(loader)
         acc = torch.zeros((), dtype=torch.float64, device=self.device)
         n_it = 0
         for data, _ in loader:
@@ -1443,8 +1511,8 @@ class GANTrainer(_GraphedSteps):
     reference wraps both nets in nn.DataParallel, new_gan.py:51-53): replica-local BatchNorm, one
     gradient exchange (SUM) per optimizer step, BCE divided by the global batch.  ``graph``: as
     BetaVAEGANTrainer; so are ``max_grad_norm``, ``skip_nonfinite`` and the schedule arguments (``lr_scheduler``,
-    ``weight_decay``, ``decoupled_weight_decay``, ``device_hyper``; there is no KL term, so a ``beta_schedule`` is a
-    TypeError).  ``ema_decay``: as BetaVAEGANTrainer, of the generator -- `ema_model` shadows `netG`, the checkpoint key is
+    ``weight_decay``, ``decoupled_weight_decay``, ``device_hyper``; there is no KL term, so a ``beta_schedule`` or a
+    ``tc_decomposition`` is a TypeError).  ``ema_decay``: as BetaVAEGANTrainer, of the generator -- `ema_model` shadows `netG`, the checkpoint key is
     ``netG_ema``; the discriminator is not averaged."""
 
     _optimizer_names = ("optimizerG", "optimizerD")
@@ -1455,10 +1523,12 @@ class GANTrainer(_GraphedSteps):
                  data_parallel: Optional[bool] = None, graph: Optional[bool] = None,
                  nonfinite_guard: Optional[bool] = None, max_grad_norm: Optional[float] = None,
                  skip_nonfinite: bool = False, lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0,
-                 decoupled_weight_decay: bool = False, device_hyper: Optional[bool] = None, ema_decay=None):
+                 decoupled_weight_decay: bool = False, device_hyper: Optional[bool] = None, ema_decay=None,
+                 tc_decomposition=None, dataset_size: Optional[int] = None):
         self.opt = opt or ModelOpt()
         self.device = torch.device(device)
         _use_tuned_gemms(self.device)
+        self._tc_args(tc_decomposition, dataset_size, has_beta=False)
         self.max_grad_norm, self.skip_nonfinite = max_grad_norm, bool(skip_nonfinite)
         torch.manual_seed(seed)
         g = Generator_celeba(self.opt)

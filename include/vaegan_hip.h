@@ -48,7 +48,8 @@ extern "C" {
  * Entry points that are only ADDED (the four of csrc/fid_front.hip; vg_bn_eval_coeffs, vg_bn_eval_act_bwd;
  * vg_adam_step_ema, vg_adam_step_dev_ema; vg_grad_sumsq_partials, vg_grad_sumsq_multi, vg_grad_clip_finalize,
  * vg_adam_step_clip, vg_adam_step_dev_clip; vg_adam_prepare_dev, vg_adam_step_decay, vg_adam_step_dev_decay,
- * vg_reparam_kl_fwd_dev, vg_reparam_kl_bwd_dev; vg_adam_step_dev_ema_dev) change
+ * vg_reparam_kl_fwd_dev, vg_reparam_kl_bwd_dev; vg_adam_step_dev_ema_dev; the five vg_reparam_tc_* of
+ * csrc/reparam_tc.hip) change
  * nothing an existing caller sees and keep the version: a binding that needs them and finds a library without them
  * fails at the symbol lookup, as loudly. */
 #define VG_ABI_VERSION 7
@@ -417,6 +418,40 @@ int vg_reparam_kl_fwd_dev(const float* mu, const float* logvar, const float* eps
 int vg_reparam_kl_bwd_dev(const float* gz, const float* mu, const float* logvar, const float* eps,
                           const float* gkl, const float* beta_dev, float* gmu, float* glogvar, int B, int D,
                           void* stream);
+
+/* ---- reparameterisation + the beta-TCVAE decomposition of the KL term (Chen et al. 2018, minibatch-weighted sampling;
+ * DESIGN.md section 4.17; csrc/reparam_tc.hip).  With z_i = mu_i + eps_i*exp(logvar_i/2) and, for i, j < B, d < D,
+ *   lq[i,j,d] = -0.5*(log 2pi + logvar[j,d] + (z[i,d] - mu[j,d])^2 * exp(-logvar[j,d]))
+ *   lqzx_i = sum_d lq[i,i,d]       lqz_i = LSE_j(sum_d lq[i,j,d]) - log_bn       lqprod_i = sum_d (LSE_j lq[i,j,d] - log_bn)
+ *   lpz_i  = sum_d -0.5*(log 2pi + z[i,d]^2)
+ * the forward writes z and out4 = {loss, mi, tc, dwkl}: mi = sum_i (lqzx_i - lqz_i), tc = sum_i (lqz_i - lqprod_i),
+ * dwkl = sum_i (lqprod_i - lpz_i), loss = alpha*mi + beta*tc + gamma*dwkl (sums over the batch; log_bn = log(B * dataset
+ * size)), and what the backward reads instead of the pair terms: lse_joint ([B], fp64: LSE_j sum_d lq[i,j,d]) and lse_dim
+ * ([B,D]: LSE_j lq[i,j,d]).  Two launches: one workgroup per sample, then one wavefront that sums the per-sample parts in
+ * a fixed order.  The backward writes
+ *   gmu = gloss*(Gmu + Gz) + gz      glogvar = gloss*(Glv + Gz*eps*0.5*exp(logvar/2)) + gz*eps*0.5*exp(logvar/2)
+ * (Gz, Gmu, Glv: the partial derivatives of loss with z, mu, logvar taken as independent) in two launches -- the sums over
+ * j in sample i's workgroup, the sums over i in workgroup j; gz (tensor) and gloss (DEVICE scalar, upstream of out4[0]) may
+ * each be NULL: that term is absent (gloss == NULL is one elementwise launch).  No floating-point atomics: the same
+ * inputs give the same bits.  1 <= B, D <= 1024.  `workspace`: vg_reparam_tc_workspace_bytes(B, D) bytes, 8-byte aligned
+ * (the forward's content is not needed by the backward). */
+size_t vg_reparam_tc_workspace_bytes(int B, int D);
+int vg_reparam_tc_fwd(const float* mu, const float* logvar, const float* eps, float* z, float* out4, double* lse_joint,
+                      float* lse_dim, int B, int D, float alpha, float beta, float gamma, float log_bn, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int vg_reparam_tc_bwd(const float* gz, const float* mu, const float* logvar, const float* eps, const float* z,
+                      const double* lse_joint, const float* lse_dim, const float* gloss, float alpha, float beta,
+                      float gamma, float* gmu, float* glogvar, int B, int D, void* workspace, size_t workspace_bytes,
+                      void* stream);
+/* beta read from DEVICE memory (beta_dev[0], fp32), as vg_reparam_kl_fwd_dev: the same fp32 beta gives the same bits.
+ * beta_dev == NULL is VG_ERR_BAD_ARG. */
+int vg_reparam_tc_fwd_dev(const float* mu, const float* logvar, const float* eps, float* z, float* out4,
+                          double* lse_joint, float* lse_dim, int B, int D, float alpha, const float* beta_dev, float gamma,
+                          float log_bn, void* workspace, size_t workspace_bytes, void* stream);
+int vg_reparam_tc_bwd_dev(const float* gz, const float* mu, const float* logvar, const float* eps, const float* z,
+                          const double* lse_joint, const float* lse_dim, const float* gloss, float alpha,
+                          const float* beta_dev, float gamma, float* gmu, float* glogvar, int B, int D, void* workspace,
+                          size_t workspace_bytes, void* stream);
 
 /* out[i] = g[i] * s[0] with s a DEVICE scalar: applies the upstream gradient of a
  * loss scalar to a gradient precomputed by the fused loss kernels, without a

@@ -27,8 +27,12 @@ sums, BCE is divided by the *global* batch), which reproduces the global-batch
 gradient.
 """
 import copy
+import os
+import warnings
+import weakref
+from contextlib import nullcontext
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -68,7 +72,7 @@ class FlatGrads:
     all the rings / trees RCCL builds busy."""
 
     exchange_when_alone = False      # tests: run the collectives even in a process group of one
-    own_rccl = __import__("os").environ.get("VG_OWN_RCCL", "1") != "0"     # 0: c10d's collectives on the GPU too (not capturable)
+    own_rccl = os.environ.get("VG_OWN_RCCL", "1") != "0"     # 0: c10d's collectives on the GPU too (not capturable)
 
     def __init__(self, params, bucket_bytes=8 << 20, direct_bytes=1 << 20, overlap=True, silent=()):
         """``silent``: parameters that never receive a gradient from autograd (the biases whose gradient is defined as
@@ -343,11 +347,11 @@ def ema_warmup(decay, start_iteration=0):
     return schedule
 
 
-GRAPH_DEFAULT = __import__("os").environ.get("VG_GRAPH", "1") != "0"     # 0: trainers never capture (every step eager)
+GRAPH_DEFAULT = os.environ.get("VG_GRAPH", "1") != "0"     # 0: trainers never capture (every step eager)
 GRAPH_WARM_STEPS = 2      # eager iterations of a shape before it is captured (workspaces, packs, GEMM plans exist then)
 
 
-NONFINITE_GUARD_DEFAULT = __import__("os").environ.get("VG_NONFINITE_GUARD", "1") != "0"    # 0: trainers do not guard unless asked
+NONFINITE_GUARD_DEFAULT = os.environ.get("VG_NONFINITE_GUARD", "1") != "0"    # 0: trainers do not guard unless asked
 
 
 class NonFiniteError(RuntimeError):
@@ -390,13 +394,13 @@ class _CapturedIteration:
         self.labels = torch.zeros(2, dtype=torch.float32, device=trainer.device)     # [real, fake]
         self.label_values = None
         self.optimizers, self.bn = optimizers, bn_modules
-        self._trainer = __import__("weakref").ref(trainer)
+        self._trainer = weakref.ref(trainer)
         self.graph = torch.cuda.CUDAGraph()
         for k, v in inputs.items():
             self.inputs[k].copy_(v)
         before_nbt = [m._nbt_pending for m in bn_modules]
         # a data-parallel iteration: the exchange's counters (bench.py's data_parallel block) advance per replay as well
-        self.flats = [f for f in (getattr(trainer, n, None) for n in ("flat_d", "flat_eg", "flat_g", "flat")) if f is not None]
+        self.flats = trainer._flats()
         before_flat = [(f.bytes_reduced, f.collectives) for f in self.flats]
         host_steps = [{p: float(o.state[p]["step"]) for g in o.param_groups for p in g["params"] if len(o.state[p])}
                       for o in optimizers]
@@ -459,12 +463,94 @@ def _use_tuned_gemms(device):
         tuned_gemms.enable()
 
 
+class _Part(NamedTuple):
+    """One network of a trainer and what belongs to it: attribute NAMES, looked up on the trainer when used (an
+    optimizer assigned after construction is the one that steps)."""
+    net: str          # attribute of the network
+    cls: type         # its module class
+    opt: str          # attribute of its optimizer
+    flat: str         # attribute of its FlatGrads (None there without data parallelism)
+    plan: str         # its name in the pack plans (`_run_with_pack_plan`)
+    ckpt: str         # checkpoint key of its optimizer
+
+
 class _GraphedSteps:
-    """What the three trainers share to replay their iteration as a HIP graph: `_graph_usable` (may this call be a
-    replay at all) and `_run_graphed` (warm-up count per shape, capture, replay, fallback)."""
+    """What the three trainers share: the construction (`_setup`), the one path an iteration takes (`_drive`: eager, or
+    -- `_graph_usable` -- a HIP-graph replay with its warm-up count per shape, capture and fallback), the guard, the
+    schedules and the weight EMA.  A trainer declares `_parts` (who is in it; everything that lists networks, optimizers
+    or exchanges derives from that table), `_latents`, `_has_labels`, `_accumulate`, and `_iteration`: the iteration
+    itself on given tensors."""
     graph = False
     iteration = 0
-    probe = None      # callable(name, tensor): taps of an (eager) iteration, see BetaVAEGANTrainer._phases
+    probe = None      # callable(name, tensor): taps of an (eager) iteration, see BetaVAEGANTrainer._iteration
+    _parts = ()       # the table: one `_Part` per network, in the order the reference constructs them
+    _latents = ()     # names of the (batch, n_hidden) N(0,1) draws of an iteration, in draw order
+    _has_labels = False       # the iteration takes the two label scalars and the global batch (the BCE's divisor)
+    _accumulate = False       # layers applied twice before one backward add their second parameter gradient in-kernel
+
+    def _setup(self, device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
+               beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition, dataset_size,
+               data_parallel=None, capturable=None):
+        """The constructor body of every trainer (new_betavaegan.py:36-53, new_vae.py:33-37, new_gan.py:47-61).  A trainer
+        with a KL term has set `beta` before."""
+        has_beta = hasattr(self, "beta")
+        self.opt = opt or ModelOpt()
+        self.device = torch.device(device)
+        on_gpu = self.device.type == "cuda"
+        _use_tuned_gemms(self.device)
+        self._tc_args(tc_decomposition, dataset_size, has_beta)
+        self.max_grad_norm, self.skip_nonfinite = max_grad_norm, bool(skip_nonfinite)
+        self._skipped = {}
+        self.world, self.rank = _dist_world(), _dist_rank()
+        self.dp = (self.world > 1) if data_parallel is None else data_parallel
+        self._graph_init(graph, on_gpu, fused_adam, self.dp)
+        if capturable is None:
+            capturable = self.graph
+        # Constructed on the CPU right behind the seed, then initialised, both in table order: the reference's RNG
+        # stream, hence its weights (new_betavaegan.py:36-47).  Nothing that draws from the CPU generator may come between.
+        torch.manual_seed(seed)
+        nets = [p.cls(self.opt) for p in self._parts]
+        for net in nets:
+            net.apply(weights_init)
+        for p, net in zip(self._parts, nets):
+            setattr(self, p.net, net.to(self.device))
+        fused = fused_adam and on_gpu
+        self.nonfinite_guard = self._resolve_guard(nonfinite_guard, fused)
+        adam = dict(max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+        adam.update(self._schedule_args(lr_scheduler, beta_schedule, device_hyper, weight_decay, decoupled_weight_decay,
+                                        fused and capturable, has_beta))
+        ema = self._ema_setup(ema_decay, getattr(self, self._ema_names[0]), fused_adam)      # (deep copy: on the device)
+        for p in self._parts:
+            setattr(self, p.opt, _make_adam(getattr(self, p.net).parameters(), lr, fused, capturable, self.nonfinite_guard,
+                                            ema=ema if p.opt == self._ema_names[1] else None, **adam))
+        self._make_schedulers()
+        for p in self._parts:         # in table order on every rank: creating the communicator is collective
+            net = getattr(self, p.net)
+            setattr(self, p.flat, FlatGrads(net.parameters(), silent=shadowed_bias_params(net)) if self.dp else None)
+        self.latent_generator = _latent_generator(self.device, seed, self.rank)
+        if self._has_labels:
+            self.label_rng = _shared_label_rng(seed)      # used by train_epoch when world > 1: one draw per GLOBAL batch
+        for net in self._nets():
+            net.train()
+        self.iteration = 0
+
+    # ---- the table of parts, read ------------------------------------------------------------------------------------
+    def _nets(self):
+        return [getattr(self, p.net) for p in self._parts]
+
+    def _optimizers(self):
+        return {p.opt: getattr(self, p.opt) for p in self._parts}
+
+    def _flats(self):
+        return [f for f in (getattr(self, p.flat) for p in self._parts) if f is not None]
+
+    def _guarded_optimizers(self):
+        """[(attribute name of the network, network, its optimizer)]"""
+        return [(p.net, getattr(self, p.net), getattr(self, p.opt)) for p in self._parts]
+
+    @property
+    def _checkpoint_optimizer_keys(self):
+        return {p.opt: p.ckpt for p in self._parts}
 
     def _graph_init(self, graph, on_gpu, fused_adam, dp):
         """A data-parallel iteration is captured too when its exchange is capturable (FlatGrads on our own RCCL
@@ -496,17 +582,13 @@ class _GraphedSteps:
         return body(lambda name=None: ops.prepack_filters(plans[name] if name is not None
                                                           else [r for v in plans.values() for r in v]))
 
-    def _graph_usable(self, optimizers, data, grad_hook):
-        flats = [f for f in (getattr(self, n, None) for n in ("flat_d", "flat_eg", "flat_g", "flat")) if f is not None]
+    def _graph_usable(self, data, grad_hook):
         if self.graph and self._any_module_hooks():      # a replay would never fire them (and a capture would run their
             return False                                 # Python body once): hooked networks step eagerly
         return (self.graph and grad_hook is None and self.probe is None and ops._timing is None and data.is_cuda
-                and all(f.capturable for f in flats)
-                and all(isinstance(o, HipAdam) and o.device_scalars for o in optimizers)
+                and all(f.capturable for f in self._flats())
+                and all(isinstance(o, HipAdam) and o.device_scalars for o in self._optimizers().values())
                 and not torch.cuda.is_current_stream_capturing())
-
-    def _nets(self):
-        return [n for n in (getattr(self, a, None) for a in ("netEG", "netD", "netG", "model")) if n is not None]
 
     def _any_module_hooks(self):
         from .model import _has_hooks
@@ -515,7 +597,6 @@ class _GraphedSteps:
     # ---- non-finite guard ----------------------------------------------------------------------------------------
     nonfinite_guard = False
     max_grad_norm, skip_nonfinite = None, False      # clipping by global norm / skipping a non-finite step (optim.HipAdam)
-    _skipped = {}
     _finite_at = 0          # `iteration` when the flags were last known clean
 
     @staticmethod
@@ -524,10 +605,6 @@ class _GraphedSteps:
         if nonfinite_guard is None:
             return bool(uses_hip_adam) and NONFINITE_GUARD_DEFAULT
         return bool(nonfinite_guard)
-
-    def _guarded_optimizers(self):
-        """[(attribute name of the network, network, its optimizer)]: every trainer lists its own."""
-        raise NotImplementedError
 
     @torch.no_grad()
     def _read_finite(self, extra=None):
@@ -601,13 +678,11 @@ class _GraphedSteps:
         self._finite_at = self.iteration
 
     # ---- schedules: learning rate, beta and weight decay ---------------------------------------------------------
-    lr_schedulers = {}
     beta_schedule = None
     device_hyper = False
     weight_decay, decoupled_weight_decay = 0.0, False
     _beta_dev = None          # with device_hyper: the persistent fp32 word the KL kernels read
     _beta_written = None
-    _optimizer_names = ()     # every trainer lists its own
 
     def _schedule_args(self, lr_scheduler, beta_schedule, device_hyper, weight_decay, decoupled_weight_decay, capturable,
                        has_beta=True):
@@ -635,9 +710,6 @@ class _GraphedSteps:
             self._beta_dev = torch.full((1,), self.beta, dtype=torch.float32, device=self.device)
             self._beta_written = self.beta
         return dict(weight_decay=wd, decoupled_weight_decay=self.decoupled_weight_decay, device_hyper=self.device_hyper)
-
-    def _optimizers(self):
-        return {n: getattr(self, n) for n in self._optimizer_names}
 
     def _make_schedulers(self):
         """``lr_scheduler(optimizer)`` for each of the trainer's optimizers -> `lr_schedulers`, keyed by attribute name."""
@@ -761,8 +833,6 @@ class _GraphedSteps:
         if self.beta_schedule is not None and "iteration" in ck:
             self.beta = float(self.beta_schedule(max(self.iteration - 1, 0)))      # (the last step's; the next step sets its own)
 
-    _checkpoint_optimizer_keys = {}
-
     # ---- weight EMA of the generating network --------------------------------------------------------------------
     ema_model = None          # the shadow network: a deep copy whose parameters the averaging Adam step writes
     ema_schedule = None       # callable iteration -> decay in [0, 1), or None (a constant decay)
@@ -883,45 +953,115 @@ class _GraphedSteps:
                 tuple(net.training for net in self._nets()),
                 tuple(p.requires_grad for net in self._nets() for p in net.parameters()))
 
-    def _draw_into(self, cap, name, batch):
-        """A latent the caller left to the trainer: drawn from this replica's stream straight into the capture's static
-        buffer (same generator, same order as the eager path's torch.randn)."""
-        buf = cap.inputs[name] if cap is not None else torch.empty(batch, self.opt.n_hidden, device=self.device)
-        return buf.normal_(generator=self.latent_generator)
+    # ---- one iteration: the path every `step` takes ----------------------------------------------------------------------
+    def draw_latents(self, batch):
+        """One N(0,1) draw of shape (batch, n_hidden) from this replica's own stream."""
+        return torch.randn(batch, self.opt.n_hidden, device=self.device, generator=self.latent_generator)
+
+    def _draw(self, given, batch, cap=None):
+        """The latents of one iteration, in `_latents` order: the caller's, and each one left to the trainer (None) drawn
+        from this replica's stream (``noise`` of new_betavaegan.py:111, ``eps`` of model.py:534) -- straight into the
+        static buffer of the capture ``cap`` when there is one: same generator, same order, same values."""
+        return tuple(t if t is not None
+                     else self.draw_latents(batch) if cap is None
+                     else cap.inputs[name].normal_(generator=self.latent_generator)
+                     for name, t in zip(self._latents, given))
+
+    def _zero(self, net, flat):
+        if flat is not None:
+            flat.zero_and_attach()
+        else:
+            _zero_grads(net)
+
+    def _exchange(self, flat):
+        if flat is not None and (self.world > 1 or FlatGrads.exchange_when_alone):
+            flat.finish()
+
+    @staticmethod
+    def _set_frozen(net, frozen):
+        """A network that only relays gradients: no weight gradients are formed for it."""
+        for p in net.parameters():
+            p.requires_grad_(not frozen)
+
+    def _iteration(self, data, latents, labels, grad_hook, prepack, acc):
+        """The iteration itself: ``latents`` in `_latents` order, ``labels`` = (real, fake, global batch) -- floats, or
+        the device scalars of a capture -- or None without `_has_labels`; ``grad_hook(phase, net)`` (tests) is called
+        right before each optimizer step; ``prepack``: see `_run_with_pack_plan`; ``acc``: the open
+        `F.accumulate_param_grads`, or None without `_accumulate`.  Counts `iteration`; returns the losses as device
+        scalars (no synchronisation)."""
+        raise NotImplementedError
+
+    def _eager(self, data, latents, labels, grad_hook=None):
+        """`_iteration` launched kernel by kernel -- which is also what a capture records.  Weights change only at the
+        optimizer steps: packed filters are reused between them, and all the filters a step has changed are re-packed
+        in ONE launch."""
+        def body(prepack):
+            with (F.accumulate_param_grads() if self._accumulate else nullcontext()) as acc:
+                return self._iteration(data, latents, labels, grad_hook, prepack, acc)
+        with ops.packed_filter_scope():
+            return self._run_with_pack_plan(body, {p.plan: getattr(self, p.net) for p in self._parts})
 
     def _frozen(self, *values):
         """Learning rates / beta as part of a capture key: frozen kernel arguments -- unless ``device_hyper`` keeps them
         in device words, where they may change under one capture."""
         return None if self.device_hyper else values
 
-    def _run_graphed(self, key, make_inputs, labels, run, optimizers, nets, eager):
-        """``key``: everything the capture freezes (shapes, divisors, learning rates, arithmetic).  ``make_inputs(cap)``
-        -> dict of device tensors; ``run(inputs, real_dev, fake_dev)`` -> the iteration on static tensors;
-        ``eager(inputs=None)``: the same iteration launched kernel by kernel (the first GRAPH_WARM_STEPS iterations of a
-        shape, and for good after a failed capture -- then on the inputs ``make_inputs`` has already produced)."""
-        key = (key, self._host_state_key())
+    def _capture_key(self, data, labels):
+        """Everything a capture freezes: shapes, the BCE's divisor, learning rates and beta (`_frozen`), the arithmetic,
+        the identity of Adam's moment tensors, and the host-side switches."""
+        opts = self._optimizers().values()
+        return (tuple(data.shape), labels and int(labels[2]),
+                self._frozen(getattr(self, "beta", None), *(o.param_groups[0]["lr"] for o in opts)),
+                ops.CONV_ARITH, tuple(o.state_generation for o in opts), self._host_state_key())
+
+    def _drive(self, data, given, real_label=None, fake_label=None, global_batch=None, grad_hook=None):
+        """One iteration from `_begin_step` to `_end_step`.  ``given``: the caller's latents in `_latents` order, None
+        where the trainer is to draw.  Eager -- or, `_graph_usable`: the first GRAPH_WARM_STEPS iterations of a capture
+        key eager (workspaces, packs, GEMM plans exist then), the next one captured and replayed, later ones replayed;
+        and eager for good after a failed capture."""
+        self._begin_step()
+        batch, labels = data.size(0), None
+        if self._has_labels:
+            # BCE is a mean over the GLOBAL batch (DataParallel gathers the outputs before the loss); equal shards are
+            # assumed unless the caller says otherwise (train_epoch passes the loader's count)
+            labels = (real_label, fake_label, global_batch if global_batch is not None else batch * self.world)
+        if self._graph_usable(data, grad_hook):
+            out = self._replayed(data, given, labels)
+        else:
+            out = self._eager(data, self._draw(given, batch), labels, grad_hook)
+        self._end_step()
+        return out
+
+    def _replayed(self, data, given, labels):
+        """The graph side of `_drive`: warm-up count per capture key, static inputs, capture, replay, fallback."""
+        key = self._capture_key(data, labels)
         cap = self._graphs.get(key)
         if cap is None and self._shape_steps.get(key, 0) < GRAPH_WARM_STEPS:
             self._shape_steps[key] = self._shape_steps.get(key, 0) + 1
-            return eager()
-        inputs = make_inputs(cap)
+            return self._eager(data, self._draw(given, data.size(0)), labels)
+        latents = self._draw(given, data.size(0), cap)
+        inputs = dict(data=data.contiguous(), **dict(zip(self._latents, latents)))
         if cap is None:
             if len(self._graphs) >= 4:               # each capture keeps its own memory pool: bound them
                 self._graphs.pop(next(iter(self._graphs)))
-            bns = [m for net in nets for m in net.modules() if hasattr(m, "_nbt_pending")]
+
+            def run(inp, real_dev, fake_dev):        # the iteration on the capture's static tensors
+                return self._eager(inp["data"], tuple(inp[n] for n in self._latents),
+                                   labels and (real_dev, fake_dev, labels[2]))
+            bns = [m for net in self._nets() for m in net.modules() if hasattr(m, "_nbt_pending")]
             it0 = self.iteration
             try:
-                cap = _CapturedIteration(self, run, inputs, optimizers, bns)
+                cap = _CapturedIteration(self, run, inputs, list(self._optimizers().values()), bns)
             except Exception as e:                   # stay correct: this trainer goes on eagerly
-                import warnings
                 warnings.warn(f"HIP-graph capture of the training iteration failed ({type(e).__name__}: {e}); "
                               "continuing with eager launches")
                 self.iteration = it0
                 self.graph = False                   # for good: a capture that fails once is not retried
-                return eager(inputs)                 # (with the latents already drawn: the RNG stream stays an eager run's)
+                return self._eager(data, latents, labels)      # (the latents already drawn: the RNG stream stays an eager run's)
             self._graphs[key] = cap
             self.iteration = it0                     # counted below, once per executed iteration
-        out = cap.replay(inputs, *labels)
+        real, fake = (float(labels[0]), float(labels[1])) if labels else (0.0, 0.0)
+        out = cap.replay(inputs, real, fake)
         self.iteration += 1
         return out
 
@@ -931,8 +1071,10 @@ class BetaVAEGANTrainer(_GraphedSteps):
 
     ``graph`` (default: on for a single-process CUDA trainer, VG_GRAPH=0 turns it off): from the third iteration of a
     batch shape on, `step` replays a HIP graph of the whole iteration (`_CapturedIteration`) instead of launching its
-    ~390 kernels one by one.  Iterations that need the host in the loop stay eager: a ``grad_hook``, data parallelism
-    (the gradient exchange runs from autograd hooks), launch timing (bench.py's instrumented step).
+    ~390 kernels one by one.  Iterations that need the host in the loop stay eager: a ``grad_hook``, a `probe`, module
+    hooks, launch timing (bench.py's instrumented step).  A data-parallel iteration is captured too when its gradient
+    exchange runs on the project's own RCCL communicator (`FlatGrads.capturable`); over torch.distributed's collectives it
+    stays eager.
 
     ``nonfinite_guard`` (default: on whenever the optimizers are HipAdam, VG_NONFINITE_GUARD=0 turns that off): the Adam
     steps flag non-finite gradients / parameters; `check_finite` -- called by `train_epoch` at the end of every epoch,
@@ -972,9 +1114,11 @@ class BetaVAEGANTrainer(_GraphedSteps):
     ValueError.  The option adds no checkpoint state.  Data parallel: every rank estimates the three parts from its LOCAL
     batch -- the pair terms never cross ranks -- so the estimator is replica-local, as the BatchNorm statistics are."""
 
-    _optimizer_names = ("optimizerEG", "optimizerD")
+    _parts = (_Part("netEG", VAE, "optimizerEG", "flat_eg", "eg", "encoder_decoder_optimizer"),              # :41, :49
+              _Part("netD", Discriminator_celeba, "optimizerD", "flat_d", "d", "discriminator_optimizer"))    # :43, :50
+    _latents = ("noise", "eps2", "eps3")
+    _has_labels = _accumulate = True
     _ema_names = ("netEG", "optimizerEG", "encoder_decoder_ema")
-    _checkpoint_optimizer_keys = {"optimizerEG": "encoder_decoder_optimizer", "optimizerD": "discriminator_optimizer"}
 
     def __init__(self, device="cuda", seed=999, beta=25.0, lr=1e-3, opt: Optional[ModelOpt] = None,
                  data_parallel: Optional[bool] = None, fused_adam: bool = True, capturable: Optional[bool] = None,
@@ -983,66 +1127,12 @@ class BetaVAEGANTrainer(_GraphedSteps):
                  lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0, decoupled_weight_decay: bool = False,
                  device_hyper: Optional[bool] = None, ema_decay=None, tc_decomposition=None,
                  dataset_size: Optional[int] = None):
-        self.opt = opt or ModelOpt()
-        self.device = torch.device(device)
-        _use_tuned_gemms(self.device)
         self.beta = float(beta)
-        self._tc_args(tc_decomposition, dataset_size)
-        self.max_grad_norm, self.skip_nonfinite = max_grad_norm, bool(skip_nonfinite)
-        self.world = _dist_world()
-        self.dp = (self.world > 1) if data_parallel is None else data_parallel
-        self._graph_init(graph, self.device.type == "cuda", fused_adam, self.dp)
-        if capturable is None:
-            capturable = self.graph
-        torch.manual_seed(seed)                       # new_betavaegan.py:36
-        net_eg = VAE(self.opt)                        # :41  (constructed on CPU: same RNG stream
-        net_d = Discriminator_celeba(self.opt)        # :43   as the reference => identical weights)
-        net_eg.apply(weights_init)                    # :46
-        net_d.apply(weights_init)                     # :47
-        self.netEG = net_eg.to(self.device)
-        self.netD = net_d.to(self.device)
-        fused = fused_adam and self.device.type == "cuda"
-        self.nonfinite_guard = self._resolve_guard(nonfinite_guard, fused)
-        clip = dict(max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
-        clip.update(self._schedule_args(lr_scheduler, beta_schedule, device_hyper, weight_decay, decoupled_weight_decay,
-                                        fused and capturable))
-        ema = self._ema_setup(ema_decay, self.netEG, fused_adam)
-        self.optimizerEG = _make_adam(self.netEG.parameters(), lr, fused, capturable, self.nonfinite_guard, ema=ema,
-                                      **clip)                                                                         # :49 (hard-coded 1e-3 there)
-        self.optimizerD = _make_adam(self.netD.parameters(), lr, fused, capturable, self.nonfinite_guard, **clip)     # :50
-        self._make_schedulers()
-        self.flat_eg = FlatGrads(self.netEG.parameters(), silent=shadowed_bias_params(self.netEG)) if self.dp else None
-        self.flat_d = FlatGrads(self.netD.parameters(), silent=shadowed_bias_params(self.netD)) if self.dp else None
-        self.netEG.train()
-        self.netD.train()
-        self.iteration = 0
+        self._setup(device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
+                    beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition,
+                    dataset_size, data_parallel, capturable)      # (lr: hard-coded 1e-3 at new_betavaegan.py:49-50)
         self._eg_params = [p for p in self.netEG.parameters() if p.dim() == 4]   # convolution filters
         self._d_params = [p for p in self.netD.parameters() if p.dim() == 4]
-        self.rank = _dist_rank()
-        self.latent_generator = _latent_generator(self.device, seed, self.rank)
-        self.label_rng = _shared_label_rng(seed)          # used by train_epoch when world > 1: one draw per GLOBAL batch
-
-    def _guarded_optimizers(self):
-        return [("netEG", self.netEG, self.optimizerEG), ("netD", self.netD, self.optimizerD)]
-
-    def draw_latents(self, batch):
-        """One N(0,1) draw of shape (batch, n_hidden) from this replica's own stream."""
-        return torch.randn(batch, self.opt.n_hidden, device=self.device, generator=self.latent_generator)
-
-    # -- gradient plumbing ------------------------------------------------------
-    def _zero(self, net, flat):
-        if flat is not None:
-            flat.zero_and_attach()
-        else:
-            _zero_grads(net)
-
-    def _exchange(self, flat):
-        if flat is not None and (self.world > 1 or FlatGrads.exchange_when_alone):
-            flat.finish()
-
-    def _set_d_frozen(self, frozen):
-        for p in self.netD.parameters():
-            p.requires_grad_(not frozen)
 
     # -- one iteration ------------------------------------------------------------
     def step(self, data, noise=None, eps2=None, eps3=None, real_label=0.9, fake_label=0.1,
@@ -1050,73 +1140,15 @@ class BetaVAEGANTrainer(_GraphedSteps):
         """One iteration; returns the nine loss scalars as device tensors (no host sync).  From the third iteration of a
         batch shape on the iteration is a HIP-graph replay and the returned tensors are the capture's STATIC outputs: the
         next replay overwrites them -- ``.clone()`` (or ``float()``) what is kept across steps."""
-        self._begin_step()
-        if self._graph_usable((self.optimizerD, self.optimizerEG), data, grad_hook):
-            out = self._step_graphed(data, noise, eps2, eps3, float(real_label), float(fake_label), global_batch)
-        else:
-            # weights change only at the three optimizer steps below: packed filters are reused between them
-            with ops.packed_filter_scope():
-                out = self._step(data, noise, eps2, eps3, real_label, fake_label, global_batch, grad_hook)
-        self._end_step()
-        return out
+        return self._drive(data, (noise, eps2, eps3), real_label, fake_label, global_batch, grad_hook)
 
-    def _step_graphed(self, data, noise, eps2, eps3, real_label, fake_label, global_batch):
-        B = data.size(0)
-        gb = global_batch if global_batch is not None else B * self.world
-        if self.device_hyper:
-            key = (tuple(data.shape), int(gb), ops.CONV_ARITH, self.optimizerEG.state_generation,
-                   self.optimizerD.state_generation)
-        else:
-            key = (tuple(data.shape), int(gb), self.beta, self.optimizerEG.param_groups[0]["lr"],
-                   self.optimizerD.param_groups[0]["lr"], ops.CONV_ARITH, self.optimizerEG.state_generation,
-                   self.optimizerD.state_generation)
-
-        def make_inputs(cap):                        # latents left to the trainer: drawn in the eager path's order
-            lat = {name: (t if t is not None else self._draw_into(cap, name, B))
-                   for name, t in (("noise", noise), ("eps2", eps2), ("eps3", eps3))}
-            return dict(data=data.contiguous(), **lat)
-
-        def run(inp, real_dev, fake_dev):
-            with ops.packed_filter_scope():
-                return self._step(inp["data"], inp["noise"], inp["eps2"], inp["eps3"], real_dev, fake_dev, gb, None)
-
-        def eager(inp=None):
-            lat = (inp["noise"], inp["eps2"], inp["eps3"]) if inp is not None else (noise, eps2, eps3)
-            with ops.packed_filter_scope():
-                return self._step(data, *lat, real_label, fake_label, global_batch, None)
-        return self._run_graphed(key, make_inputs, (real_label, fake_label), run, [self.optimizerD, self.optimizerEG],
-                                 (self.netEG, self.netD), eager)
-
-    def _step(self, data, noise, eps2, eps3, real_label, fake_label, global_batch, grad_hook):
-        """data (B,3,64,64) in [-1,1]; noise / eps2 / eps3 (B, n_hidden) ~ N(0,1) are drawn on
-        the device when omitted (new_betavaegan.py:111, model.py:534).  Labels are the
-        per-iteration scalars of :89-90.  Returns device scalars (no sync).
-        ``grad_hook(phase, net)`` (tests) is called right before each optimizer step."""
+    def _iteration(self, data, latents, labels, grad_hook, prepack, acc):
+        """data (B,3,64,64) in [-1,1]; noise / eps2 / eps3 (B, n_hidden) ~ N(0,1) (new_betavaegan.py:111, model.py:534);
+        the labels are the per-iteration scalars of :89-90."""
         netEG, netD = self.netEG, self.netD
-        B = data.size(0)
-        if noise is None:
-            noise = self.draw_latents(B)
-        if eps2 is None:
-            eps2 = self.draw_latents(B)
-        if eps3 is None:
-            eps3 = self.draw_latents(B)
-        # Packed filters: all filters an optimizer step has changed are re-packed in ONE launch (32 launches -> 3)
-        return self._run_with_pack_plan(
-            lambda prepack: self._step_body(data, noise, eps2, eps3, real_label, fake_label, global_batch, grad_hook, prepack),
-            {"d": netD, "eg": netEG})
-
-    def _step_body(self, data, noise, eps2, eps3, real_label, fake_label, global_batch, grad_hook, prepack):
-        # layers applied twice before one backward add their second parameter gradient inside its own kernel
-        with F.accumulate_param_grads() as acc:
-            return self._phases(data, noise, eps2, eps3, real_label, fake_label, global_batch, grad_hook, prepack, acc)
-
-    def _phases(self, data, noise, eps2, eps3, real_label, fake_label, global_batch, grad_hook, prepack, acc):
-        netEG, netD = self.netEG, self.netD
-        B = data.size(0)
+        noise, eps2, eps3 = latents
+        real_label, fake_label, gb = labels
         prepack()
-        # BCE is a mean over the GLOBAL batch (DataParallel gathers the outputs before the loss); equal
-        # shards are assumed unless the caller says otherwise (train_epoch passes the loader's count)
-        gb = global_batch if global_batch is not None else B * self.world
         out = {}
 
         # ---- phase 1: discriminator (:95-123)
@@ -1142,7 +1174,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
 
         # ---- phase 2: "decoder" -- every EG parameter moves (:127-164)
         self._zero(netEG, self.flat_eg)
-        self._set_d_frozen(True)
+        self._set_frozen(netD, True)
         recon, mu, logvar = netEG(data, eps2)
         # D three times on frozen weights -- on data as under no_grad (D fwd #3: BN statistics still update), on fake and
         # on recon, in that order: the big Linear layer reads its weight once for the three
@@ -1153,7 +1185,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
         sim = F.sim_loss(sim_rec, sim_real)
         mse2 = F.reconstruction_loss(recon, data)
         _backward([err_g_fake, err_g_rec, sim, mse2])
-        self._set_d_frozen(False)
+        self._set_frozen(netD, False)
         self._exchange(self.flat_eg)
         if grad_hook:
             grad_hook("EG2", netEG)
@@ -1238,7 +1270,6 @@ class BetaVAEGANTrainer(_GraphedSteps):
         ``*.jpg`` / ``*.png`` (utils.py:26 vs scoring/fid.py:293), so with the defaults that route finds no image.
 
         ``use_ema=True`` (a trainer with ``ema_decay``): the FID samples of both routes come from `ema_model`."""
-        import os
         from . import image_io
         rows = []
         self._dataset_size_from(loader)
@@ -1400,9 +1431,9 @@ class VAETrainer(_GraphedSteps):
     the checkpoint key is ``VAE_model_ema``.  ``tc_decomposition`` / ``dataset_size``: as there, of the step's KL term
     (`train_epoch` fills a ``dataset_size`` that was not given); replica-local under data parallelism."""
 
-    _optimizer_names = ("optimizer",)
+    _parts = (_Part("model", VAE, "optimizer", "flat", "vae", "optimizer"),)
+    _latents = ("eps",)
     _ema_names = ("model", "optimizer", "VAE_model_ema")
-    _checkpoint_optimizer_keys = {"optimizer": "optimizer"}
 
     def __init__(self, device="cuda", seed=999, beta=1.0, lr=3e-3, opt: Optional[ModelOpt] = None,
                  fused_adam: bool = True, capturable: Optional[bool] = None, graph: Optional[bool] = None,
@@ -1410,74 +1441,24 @@ class VAETrainer(_GraphedSteps):
                  skip_nonfinite: bool = False, lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0,
                  decoupled_weight_decay: bool = False, device_hyper: Optional[bool] = None, ema_decay=None,
                  tc_decomposition=None, dataset_size: Optional[int] = None):
-        self.opt = opt or ModelOpt()
-        self.device = torch.device(device)
-        _use_tuned_gemms(self.device)
         self.beta = float(beta)
-        self._tc_args(tc_decomposition, dataset_size)
-        self.max_grad_norm, self.skip_nonfinite = max_grad_norm, bool(skip_nonfinite)
-        torch.manual_seed(seed)
-        m = VAE(self.opt)
-        m.apply(weights_init)
-        self.model = m.to(self.device)
-        self.world = _dist_world()
-        self._graph_init(graph, self.device.type == "cuda", fused_adam, self.world > 1)
-        fused = fused_adam and self.device.type == "cuda"
-        self.nonfinite_guard = self._resolve_guard(nonfinite_guard, fused)
-        capturable = self.graph if capturable is None else capturable
-        hyper = self._schedule_args(lr_scheduler, beta_schedule, device_hyper, weight_decay, decoupled_weight_decay,
-                                    fused and capturable)
-        self.optimizer = _make_adam(self.model.parameters(), lr, fused, capturable, self.nonfinite_guard,
-                                    max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite,
-                                    ema=self._ema_setup(ema_decay, self.model, fused_adam), **hyper)
-        self._make_schedulers()
-        self.flat = FlatGrads(self.model.parameters(), silent=shadowed_bias_params(self.model)) if self.world > 1 else None
-        self.latent_generator = _latent_generator(self.device, seed, _dist_rank())
-        self.model.train()
-
-    def _guarded_optimizers(self):
-        return [("model", self.model, self.optimizer)]
+        self._setup(device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
+                    beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition,
+                    dataset_size, capturable=capturable)
 
     def step(self, data, eps=None, grad_hook=None):
         """``grad_hook(phase, net)`` (tests): called with ``("VAE", model)`` right before the optimizer step; such an
         iteration is eager, as BetaVAEGANTrainer's."""
-        self._begin_step()
-        out = self._step_any(data, eps, grad_hook)
-        self._end_step()
-        return out
+        return self._drive(data, (eps,), grad_hook=grad_hook)
 
-    def _step_any(self, data, eps, grad_hook=None):
-        def eager(inp=None):
-            with ops.packed_filter_scope():       # one optimizer step at the end: packs live for the iteration
-                return self._step(data, inp["eps"] if inp is not None else eps, grad_hook)
-        if not self._graph_usable((self.optimizer,), data, grad_hook):
-            return eager()
-
-        def run(inp, real_dev, fake_dev):
-            with ops.packed_filter_scope():
-                return self._step(inp["data"], inp["eps"])
-        key = (tuple(data.shape), self._frozen(self.beta, self.optimizer.param_groups[0]["lr"]), ops.CONV_ARITH,
-               self.optimizer.state_generation)
-        return self._run_graphed(key, lambda cap: dict(data=data.contiguous(),
-                                                       eps=eps if eps is not None else self._draw_into(cap, "eps", data.size(0))),
-                                 (0.0, 0.0), run, [self.optimizer], (self.model,), eager)
-
-    def _step(self, data, eps, grad_hook=None):
-        if eps is None:                       # model.py:534, from this replica's own stream
-            eps = torch.randn(data.size(0), self.opt.n_hidden, device=self.device, generator=self.latent_generator)
-        return self._run_with_pack_plan(lambda prepack: self._step_body(data, eps, prepack, grad_hook), {"vae": self.model})
-
-    def _step_body(self, data, eps, prepack, grad_hook=None):
+    def _iteration(self, data, latents, labels, grad_hook, prepack, acc):
+        eps, = latents
         prepack()                             # the filters the previous optimizer step changed: one pack launch
-        if self.flat is not None:
-            self.flat.zero_and_attach()
-        else:
-            _zero_grads(self.model)
+        self._zero(self.model, self.flat)
         recon, mu, logvar, kld, parts = self._forward_kl(self.model, data, eps)
         mse = F.reconstruction_loss(recon, data)
         _backward([mse, kld])
-        if self.flat is not None:
-            self.flat.finish()
+        self._exchange(self.flat)
         if grad_hook:
             grad_hook("VAE", self.model)
         self.optimizer.step()
@@ -1515,9 +1496,11 @@ class GANTrainer(_GraphedSteps):
     ``tc_decomposition`` is a TypeError).  ``ema_decay``: as BetaVAEGANTrainer, of the generator -- `ema_model` shadows `netG`, the checkpoint key is
     ``netG_ema``; the discriminator is not averaged."""
 
-    _optimizer_names = ("optimizerG", "optimizerD")
+    _parts = (_Part("netG", Generator_celeba, "optimizerG", "flat_g", "g", "G_trainer"),
+              _Part("netD", Discriminator_celeba, "optimizerD", "flat_d", "d", "D_trainer"))
+    _latents = ("noise",)
+    _has_labels = _accumulate = True              # (D runs twice before its backward, as BetaVAEGANTrainer's)
     _ema_names = ("netG", "optimizerG", "netG_ema")
-    _checkpoint_optimizer_keys = {"optimizerG": "G_trainer", "optimizerD": "D_trainer"}
 
     def __init__(self, device="cuda", seed=999, lr=3e-3, opt: Optional[ModelOpt] = None, fused_adam: bool = True,
                  data_parallel: Optional[bool] = None, graph: Optional[bool] = None,
@@ -1525,91 +1508,17 @@ class GANTrainer(_GraphedSteps):
                  skip_nonfinite: bool = False, lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0,
                  decoupled_weight_decay: bool = False, device_hyper: Optional[bool] = None, ema_decay=None,
                  tc_decomposition=None, dataset_size: Optional[int] = None):
-        self.opt = opt or ModelOpt()
-        self.device = torch.device(device)
-        _use_tuned_gemms(self.device)
-        self._tc_args(tc_decomposition, dataset_size, has_beta=False)
-        self.max_grad_norm, self.skip_nonfinite = max_grad_norm, bool(skip_nonfinite)
-        torch.manual_seed(seed)
-        g = Generator_celeba(self.opt)
-        d = Discriminator_celeba(self.opt)
-        g.apply(weights_init)
-        d.apply(weights_init)
-        self.netG, self.netD = g.to(self.device), d.to(self.device)
-        fused = fused_adam and self.device.type == "cuda"
-        self.world = _dist_world()
-        self.dp = (self.world > 1) if data_parallel is None else data_parallel
-        self._graph_init(graph, self.device.type == "cuda", fused_adam, self.dp)
-        self.nonfinite_guard = self._resolve_guard(nonfinite_guard, fused)
-        clip = dict(max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
-        clip.update(self._schedule_args(lr_scheduler, beta_schedule, device_hyper, weight_decay, decoupled_weight_decay,
-                                        fused and self.graph, has_beta=False))
-        self.optimizerG = _make_adam(self.netG.parameters(), lr, fused, self.graph, self.nonfinite_guard,
-                                     ema=self._ema_setup(ema_decay, self.netG, fused_adam), **clip)
-        self.optimizerD = _make_adam(self.netD.parameters(), lr, fused, self.graph, self.nonfinite_guard, **clip)
-        self._make_schedulers()
-        self.flat_g = FlatGrads(self.netG.parameters(), silent=shadowed_bias_params(self.netG)) if self.dp else None
-        self.flat_d = FlatGrads(self.netD.parameters(), silent=shadowed_bias_params(self.netD)) if self.dp else None
-        self.latent_generator = _latent_generator(self.device, seed, _dist_rank())
-        self.label_rng = _shared_label_rng(seed)
-        self.netG.train()
-        self.netD.train()
-
-    def _zero(self, net, flat):
-        if flat is not None:
-            flat.zero_and_attach()
-        else:
-            _zero_grads(net)
-
-    def _exchange(self, flat):
-        if flat is not None and (self.world > 1 or FlatGrads.exchange_when_alone):
-            flat.finish()
-
-    def _guarded_optimizers(self):
-        return [("netG", self.netG, self.optimizerG), ("netD", self.netD, self.optimizerD)]
+        self._setup(device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
+                    beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition,
+                    dataset_size, data_parallel)
 
     def step(self, data, noise=None, real_label=0.9, fake_label=0.1, global_batch: Optional[int] = None,
              grad_hook=None):
-        self._begin_step()
-        out = self._step_any(data, noise, real_label, fake_label, global_batch, grad_hook)
-        self._end_step()
-        return out
+        return self._drive(data, (noise,), real_label, fake_label, global_batch, grad_hook)
 
-    def _step_any(self, data, noise, real_label, fake_label, global_batch, grad_hook):
-        def eager(inp=None):
-            with ops.packed_filter_scope():
-                return self._step(data, inp["noise"] if inp is not None else noise, real_label, fake_label, global_batch,
-                                  grad_hook)
-        if not self._graph_usable((self.optimizerD, self.optimizerG), data, grad_hook):
-            return eager()
-        B = data.size(0)
-        gb = global_batch if global_batch is not None else B * self.world
-
-        def run(inp, real_dev, fake_dev):
-            with ops.packed_filter_scope():
-                return self._step(inp["data"], inp["noise"], real_dev, fake_dev, gb, None)
-        key = (tuple(data.shape), int(gb), self._frozen(self.optimizerG.param_groups[0]["lr"],
-                                                        self.optimizerD.param_groups[0]["lr"]),
-               ops.CONV_ARITH, self.optimizerG.state_generation, self.optimizerD.state_generation)
-        return self._run_graphed(key, lambda cap: dict(data=data.contiguous(),
-                                                       noise=noise if noise is not None else self._draw_into(cap, "noise", B)),
-                                 (float(real_label), float(fake_label)), run, [self.optimizerD, self.optimizerG],
-                                 (self.netG, self.netD), eager)
-
-    def _step(self, data, noise, real_label, fake_label, global_batch, grad_hook):
-        if noise is None:
-            noise = torch.randn(data.size(0), self.opt.n_hidden, device=self.device, generator=self.latent_generator)
-        return self._run_with_pack_plan(
-            lambda prepack: self._step_body(data, noise, real_label, fake_label, global_batch, grad_hook, prepack),
-            {"d": self.netD, "g": self.netG})
-
-    def _step_body(self, data, noise, real_label, fake_label, global_batch, grad_hook, prepack):
-        with F.accumulate_param_grads() as acc:              # D runs twice before its backward (as BetaVAEGANTrainer)
-            return self._phases(data, noise, real_label, fake_label, global_batch, grad_hook, prepack, acc)
-
-    def _phases(self, data, noise, real_label, fake_label, global_batch, grad_hook, prepack, acc):
-        B = data.size(0)
-        gb = global_batch if global_batch is not None else B * self.world
+    def _iteration(self, data, latents, labels, grad_hook, prepack, acc):
+        noise, = latents
+        real_label, fake_label, gb = labels
         prepack()
         self._zero(self.netD, self.flat_d)
         fake = self.netG(noise)
@@ -1626,12 +1535,10 @@ class GANTrainer(_GraphedSteps):
         prepack("d")
         acc.reset()
         self._zero(self.netG, self.flat_g)
-        for p in self.netD.parameters():
-            p.requires_grad_(False)
+        self._set_frozen(self.netD, True)
         _, _, err_g = self.netD.forward_with_bce(fake, real_label, gb)
         _backward([err_g])
-        for p in self.netD.parameters():
-            p.requires_grad_(True)
+        self._set_frozen(self.netD, False)
         self._exchange(self.flat_g)
         if grad_hook:
             grad_hook("G", self.netG)

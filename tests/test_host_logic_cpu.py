@@ -762,3 +762,51 @@ def test_batch_norm_act_hands_out_the_bound_its_own_forward_set(monkeypatch):
     x.grad = None
     (out * 0.0).sum().backward()                  # and one in which it is, next to it
     assert x.grad is not None
+
+
+# (constructor, seed, networks in the reference's construction order, then per network: attribute, optimizer attribute,
+# pack-plan name, checkpoint key of the optimizer)
+TRAINER_PARTS = [
+    ("BetaVAEGANTrainer", 999, ("VAE", "Discriminator_celeba"),
+     [("netEG", "optimizerEG", "eg", "encoder_decoder_optimizer"), ("netD", "optimizerD", "d", "discriminator_optimizer")]),
+    ("VAETrainer", 5, ("VAE",), [("model", "optimizer", "vae", "optimizer")]),
+    ("GANTrainer", 7, ("Generator_celeba", "Discriminator_celeba"),
+     [("netG", "optimizerG", "g", "G_trainer"), ("netD", "optimizerD", "d", "D_trainer")]),
+]
+
+
+@pytest.mark.parametrize("name, seed, classes, parts", TRAINER_PARTS, ids=[c[0] for c in TRAINER_PARTS])
+def test_trainer_parts_table_and_seeded_construction(name, seed, classes, parts):
+    """Who is in a trainer, in `_guarded_optimizers` order (what `NonFiniteError.found` lists first), and the
+    construction recipe: networks built on the CPU right behind ``torch.manual_seed(seed)`` in the reference's order
+    (new_betavaegan.py:36-47, new_vae.py:25-34, new_gan.py:47-57), then initialised in that order -- nothing else draws
+    from the CPU generator in between, so the weights are those of the same modules built by hand."""
+    from disentangle_mlp_amd import model as M
+    from disentangle_mlp_amd import trainer as T
+    torch.manual_seed(123)                  # (the trainer's own seed decides, not the generator's state before)
+    tr = getattr(T, name)(device="cpu", seed=seed)
+    guarded = tr._guarded_optimizers()
+    assert [n for n, _, _ in guarded] == [p[0] for p in parts]
+    assert all(net is getattr(tr, p[0]) and opt is getattr(tr, p[1]) for (_, net, opt), p in zip(guarded, parts))
+    assert list(tr._optimizers()) == [p[1] for p in parts]
+    assert all(tr._optimizers()[p[1]] is getattr(tr, p[1]) for p in parts)
+    assert [p.plan for p in tr._parts] == [p[2] for p in parts]
+    assert tr._checkpoint_optimizer_keys == {p[1]: p[3] for p in parts}
+    assert list(tr._checkpoint_optimizer_keys) == [p[1] for p in parts]
+    assert all(net.training for net in tr._nets()) and tr._skipped == {} and tr.lr_schedulers == {}
+    assert "_skipped" in vars(tr) and "lr_schedulers" in vars(tr)        # the trainer's own dicts, not the class's
+    # an optimizer assigned after construction is the one the table finds
+    swapped = torch.optim.Adam(getattr(tr, parts[-1][0]).parameters(), lr=1e-3)
+    setattr(tr, parts[-1][1], swapped)
+    assert tr._guarded_optimizers()[-1][2] is swapped and tr._optimizers()[parts[-1][1]] is swapped
+
+    twin = getattr(T, name)(device="cpu", seed=seed)
+    torch.manual_seed(seed)
+    by_hand = [getattr(M, c)(T.ModelOpt()) for c in classes]
+    for net in by_hand:
+        net.apply(M.weights_init)
+    for p, hand in zip(parts, by_hand):
+        mine, theirs, want = getattr(tr, p[0]).state_dict(), getattr(twin, p[0]).state_dict(), hand.state_dict()
+        assert list(mine) == list(theirs) == list(want)
+        for k, v in mine.items():
+            assert torch.equal(v, theirs[k]) and torch.equal(v, want[k]), (p[0], k)

@@ -436,15 +436,16 @@ def test_tuned_gemm_table_is_accepted_on_this_installation(T):
 
 def test_vae_and_gan_captured_steps_equal_eager(T):
     """VAETrainer (new_vae.py) and GANTrainer (new_gan.py) replay their iteration as a HIP graph the same way: losses
-    of five iterations and the final weights bit for bit against eager stepping."""
+    of five iterations and the final weights bit for bit against eager stepping.  In iteration 3 -- a plain replay -- the
+    latent is left to the trainer: drawn from its own stream, into the capture's static buffer in the graph twin."""
     g = torch.Generator().manual_seed(4)
     data = [torch.rand(8, 3, 64, 64, generator=g) * 2 - 1 for _ in range(5)]
-    lat = [torch.randn(8, 128, generator=g) for _ in range(5)]
+    lat = [None if i == 3 else torch.randn(8, 128, generator=g).cuda() for i in range(5)]
     labels = [(0.9, 0.1), (0.9, 0.1), (0.9, 0.1), (0.1, 0.1), (0.9, 0.9)]
     for make, call, nets in (
-            (lambda gr: T.VAETrainer(beta=1.0, graph=gr, capturable=True), lambda tr, i: tr.step(data[i].cuda(), lat[i].cuda()),
+            (lambda gr: T.VAETrainer(beta=1.0, graph=gr, capturable=True), lambda tr, i: tr.step(data[i].cuda(), lat[i]),
              lambda tr: (tr.model,)),
-            (lambda gr: T.GANTrainer(graph=gr), lambda tr, i: tr.step(data[i].cuda(), lat[i].cuda(), real_label=labels[i][0],
+            (lambda gr: T.GANTrainer(graph=gr), lambda tr, i: tr.step(data[i].cuda(), lat[i], real_label=labels[i][0],
                                                                       fake_label=labels[i][1]), lambda tr: (tr.netG, tr.netD))):
         res = {}
         for mode in (False, True):
@@ -462,6 +463,50 @@ def test_vae_and_gan_captured_steps_equal_eager(T):
                 assert torch.equal(v, res[True][0][i][k]), (i, k)
         for k, v in res[False][1].items():
             assert torch.equal(v, res[True][1][k]), k
+
+
+@pytest.mark.parametrize("which", ["betavaegan", "vae", "gan"])
+def test_failed_capture_falls_back_to_eager_for_good(T, monkeypatch, which):
+    """A capture that fails (here: on the host, before anything is captured) is not retried: one warning, ``graph`` off,
+    no capture kept, every iteration counted once -- and the run is an eager run's, bit for bit: the latents drawn for
+    the failed capture are the ones the fallback iteration uses, so the trainer's generator stream does not shift.
+    Four iterations (two warm-up, the failed capture, one after it), latents left to the trainer."""
+    import warnings
+    from disentangle_mlp_amd.optim import HipAdam
+
+    class Failing:
+        def __init__(self, *args, **kwargs):
+            raise RuntimeError("no capture today")
+
+    make = {"betavaegan": lambda gr: T.BetaVAEGANTrainer(beta=25.0, graph=gr, capturable=True),
+            "vae": lambda gr: T.VAETrainer(beta=1.0, graph=gr, capturable=True),
+            "gan": lambda gr: T.GANTrainer(graph=gr)}[which]
+    g = torch.Generator().manual_seed(6)
+    data = [(torch.rand(4, 3, 64, 64, generator=g) * 2 - 1).cuda() for _ in range(4)]
+    labels = [(0.9, 0.1), (0.1, 0.1), (0.9, 0.9), (0.9, 0.1)]
+    res = {}
+    for mode in (False, True):
+        tr = make(mode)
+        if which == "gan" and not mode:       # eager twin of the GAN: the same device-scalar Adam arithmetic
+            tr.optimizerG = HipAdam(tr.netG.parameters(), lr=3e-3, capturable=True)
+            tr.optimizerD = HipAdam(tr.netD.parameters(), lr=3e-3, capturable=True)
+        kw = [{} if which == "vae" else dict(real_label=r, fake_label=f) for r, f in labels]
+        with monkeypatch.context() as mp, warnings.catch_warnings(record=True) as caught:
+            warnings.simplefilter("always")
+            mp.setattr(T, "_CapturedIteration", Failing)
+            assert tr.graph == mode
+            losses = [{k: v.clone() for k, v in tr.step(data[i], **kw[i]).items()} for i in range(4)]
+        failed = [w for w in caught if "capture of the training iteration failed" in str(w.message)]
+        assert len(failed) == (1 if mode else 0) and all("no capture today" in str(w.message) for w in failed)
+        assert tr.graph is False and tr.iteration == 4 and not tr._graphs
+        res[mode] = (losses, {f"{j}.{k}": v.detach().clone() for j, n in enumerate(tr._nets()) for k, v in n.state_dict().items()})
+    for i in range(4):
+        assert res[False][0][i].keys() == res[True][0][i].keys()
+        for k, v in res[False][0][i].items():
+            assert torch.equal(v, res[True][0][i][k]), (i, k)
+    assert res[False][1].keys() == res[True][1].keys()
+    for k, v in res[False][1].items():
+        assert torch.equal(v, res[True][1][k]), k
 
 
 # ------------------------------------------------------------------ parity AWAY from the initial weights

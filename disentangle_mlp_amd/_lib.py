@@ -84,6 +84,8 @@ SIGNATURES = {
     "vg_adam_step_dev": (_I, [_P, _I] + [ctypes.c_double] * 3 + [_P, _P]),
     "vg_adam_step_checked": (_I, [_P, _I] + [ctypes.c_double] * 6 + [_P, _P]),
     "vg_adam_step_dev_checked": (_I, [_P, _I] + [ctypes.c_double] * 3 + [_P, _P, _P]),
+    "vg_linear_wgrad_adam": (_I, [_P, _P, _I, _I, _I] + [_P] * 7 + [ctypes.c_double] * 6 + [_P, _P]),
+    "vg_linear_wgrad_adam_dev": (_I, [_P, _P, _I, _I, _I] + [_P] * 7 + [ctypes.c_double] * 3 + [_P, _P, _P]),
     "vg_adam_step_ema": (_I, [_P, _I] + [ctypes.c_double] * 6 + [_P, _P, ctypes.c_double, _P]),
     "vg_adam_step_dev_ema": (_I, [_P, _I] + [ctypes.c_double] * 3 + [_P, _P, _P, ctypes.c_double, _P]),
     "vg_grad_sumsq_partials": (_Z, [_P, _I]),

@@ -61,6 +61,7 @@ namespace {
 
 constexpr int ANT = 256, ACHUNK = 8192, AMAX = 24;
 constexpr unsigned long long MAX_GRID = 0x3fffffffULL;      // workgroups of one launch
+static_assert(VG_FLAG_GRAD == VG_NONFINITE_GRAD && VG_FLAG_PARAM == VG_NONFINITE_PARAM, "common.hpp's flag bits");
 
 __host__ __device__ constexpr unsigned long long chunks_of(unsigned long long n) { return (n + ACHUNK - 1) / ACHUNK; }
 
@@ -110,21 +111,7 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
 }
 
 // adam_one for the feature kernel, which must give the bits of the plain kernel element by element -- wherever its
-// own alignment rule (the EMA pointer counts) sends the element.  The plain kernel is compiled under the default
-// contraction, and the compiler forms v differently in its two loops: in the 16-byte body as ONE fma,
-// fma(b2, v, (omb2 g) g), in the scalar loops as two rounded products and a rounded sum; m and p are an fma in both.
-// So this copy spells the roundings out (no contraction of its own) and takes, per element, which of the two loops
-// the plain kernel would have run it in.  tests/test_adam_ema_gpu.py compares the bits on every path.
-__device__ __forceinline__ void adam_one_as(bool body, float& p, float g, float& m, float& v, float omb1, float b2,
-                                            float omb2, float step_size, float bc2s, float eps) {
-#pragma clang fp contract(off)
-  m = __builtin_fmaf(omb1, g - m, m);
-  const float gg = (omb2 * g) * g;
-  const float b2v = b2 * v;
-  v = body ? __builtin_fmaf(b2, v, gg) : b2v + gg;
-  const float denom = sqrtf(v) / bc2s + eps;
-  p = __builtin_fmaf(-step_size, m / denom, p);
-}
+// own alignment rule (the EMA pointer counts) sends the element: adam_one_as of common.hpp.
 
 __device__ __forceinline__ float ema_one(float e, float p, float omd) { return e + omd * (p - e); }
 
@@ -170,33 +157,7 @@ __global__ void adam_prepare_dev_kernel(double step_host, double* __restrict__ s
   scalars[3] = decoupled ? 0.f : (float)wd;
 }
 
-constexpr unsigned NONFINITE_BITS = 0x7f800000u;      // abs_bits(x) >= this: x is inf or NaN
-
-// ORs `bits` (this thread's VG_NONFINITE_* findings) over the workgroup into *out: no memory traffic unless a bit is set.
-// Every thread of the ANT-thread workgroup must call it.
-__device__ __forceinline__ void block_flag_or(unsigned bits, unsigned* out) {
-  __shared__ unsigned flag_red[ANT / 64];
-  const unsigned w = (__ballot(bits & VG_NONFINITE_GRAD) ? (unsigned)VG_NONFINITE_GRAD : 0u) |
-                     (__ballot(bits & VG_NONFINITE_PARAM) ? (unsigned)VG_NONFINITE_PARAM : 0u);
-  if ((threadIdx.x & 63) == 0) flag_red[threadIdx.x >> 6] = w;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned all = 0;
-#pragma unroll
-    for (int i = 0; i < ANT / 64; ++i) all |= flag_red[i];
-    if (all) atomicOr(out, all);
-  }
-}
-
-// The end of a step kernel: this thread's max |p| (`am`) and max |g| (`gm`), as bits, go into the tensor's amax word
-// and flag word (either may be NULL; both pointers are uniform over the workgroup).  Every thread must call it.
-__device__ __forceinline__ void emit_amax_and_flags(unsigned am, unsigned gm, unsigned* amax, unsigned* flag) {
-  if (amax) block_amax_atomic<ANT>(am, amax);
-  if (flag)
-    block_flag_or((gm >= NONFINITE_BITS ? (unsigned)VG_NONFINITE_GRAD : 0u) |
-                      (am >= NONFINITE_BITS ? (unsigned)VG_NONFINITE_PARAM : 0u),
-                  flag);
-}
+// (block_flag_or and emit_amax_and_flags, the end of both step kernels: common.hpp)
 
 // ---- the plain step ----------------------------------------------------------------------------------------------------
 // Its three loops are the reference bits of every other entry point (adam_one_as names the compiler's choices in them).
@@ -251,7 +212,7 @@ __global__ __launch_bounds__(ANT) void adam_multi_kernel(AdamPack A, float omb1,
       gm = max(gm, abs_bits(gi));
     }
   }
-  emit_amax_and_flags(am, gm, A.amax[t], A.flag[t]);      // (t is uniform over the workgroup)
+  emit_amax_and_flags<ANT>(am, gm, A.amax[t], A.flag[t]);      // (t is uniform over the workgroup)
 }
 
 // ---- clipping by global norm, skipping a non-finite step --------------------------------------------------------------
@@ -447,7 +408,7 @@ __global__ __launch_bounds__(ANT) void adam_multi_feature_kernel(AdamFeaturePack
       if (e) e[i] = avg(e[i], pi);
     }
   }
-  emit_amax_and_flags(am, gm, A.amax[t], A.flag[t]);
+  emit_amax_and_flags<ANT>(am, gm, A.amax[t], A.flag[t]);
 }
 
 // ---- packing and launching -------------------------------------------------------------------------------------------

@@ -179,6 +179,52 @@ __device__ __forceinline__ void block_amax_atomic(unsigned m, unsigned* out) {
   }
 }
 
+// ---- the Adam element and the end of a step kernel, shared by adam.hip and the fused weight-gradient step of
+// gemm_split.hip ------------------------------------------------------------------------------------------------------
+// One element of the plain step with its roundings spelled out.  The plain kernel (adam.hip, adam_multi_kernel) is
+// compiled under the default contraction, and the compiler forms v differently in its two loops: in the 16-byte body as
+// ONE fma, fma(b2, v, (omb2 g) g), in the scalar loops as two rounded products and a rounded sum; m and p are an fma
+// in both.  So this copy takes no contraction of its own and, per element, which of the two loops the plain kernel
+// would have run it in.  tests/test_adam_ema_gpu.py compares the bits on every path.
+__device__ __forceinline__ void adam_one_as(bool body, float& p, float g, float& m, float& v, float omb1, float b2,
+                                            float omb2, float step_size, float bc2s, float eps) {
+#pragma clang fp contract(off)
+  m = __builtin_fmaf(omb1, g - m, m);
+  const float gg = (omb2 * g) * g;
+  const float b2v = b2 * v;
+  v = body ? __builtin_fmaf(b2, v, gg) : b2v + gg;
+  const float denom = sqrtf(v) / bc2s + eps;
+  p = __builtin_fmaf(-step_size, m / denom, p);
+}
+
+constexpr unsigned VG_NONFINITE_BITS = 0x7f800000u;      // abs_bits(x) >= this: x is inf or NaN
+constexpr unsigned VG_FLAG_GRAD = 1u, VG_FLAG_PARAM = 2u;      // == VG_NONFINITE_GRAD / VG_NONFINITE_PARAM of vaegan_hip.h
+
+// ORs `bits` (this thread's non-finite findings) over the workgroup into *out: no memory traffic unless a bit is set.
+// Every thread of the NT-thread workgroup must call it.
+template <int NT>
+__device__ __forceinline__ void block_flag_or(unsigned bits, unsigned* out) {
+  __shared__ unsigned flag_red[NT / 64];
+  const unsigned w = (__ballot(bits & VG_FLAG_GRAD) ? VG_FLAG_GRAD : 0u) | (__ballot(bits & VG_FLAG_PARAM) ? VG_FLAG_PARAM : 0u);
+  if ((threadIdx.x & 63) == 0) flag_red[threadIdx.x >> 6] = w;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned all = 0;
+#pragma unroll
+    for (int i = 0; i < NT / 64; ++i) all |= flag_red[i];
+    if (all) atomicOr(out, all);
+  }
+}
+
+// The end of a step kernel: this thread's max |p| (`am`) and max |g| (`gm`), as bits, go into the tensor's amax word
+// and flag word (either may be NULL; both pointers are uniform over the workgroup).  Every thread must call it.
+template <int NT>
+__device__ __forceinline__ void emit_amax_and_flags(unsigned am, unsigned gm, unsigned* amax, unsigned* flag) {
+  if (amax) block_amax_atomic<NT>(am, amax);
+  if (flag)
+    block_flag_or<NT>((gm >= VG_NONFINITE_BITS ? VG_FLAG_GRAD : 0u) | (am >= VG_NONFINITE_BITS ? VG_FLAG_PARAM : 0u), flag);
+}
+
 __host__ __device__ constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // cross-file internal entry points (not part of the C ABI)

@@ -74,6 +74,21 @@ struct GArgs {
   const float* b_amax;
 };
 
+// The Adam half of the fused weight-gradient step (vg_linear_wgrad_adam, _dev): the tile's gradient never leaves the
+// workgroup (g_out apart) -- it is the g of the plain Adam step on the tile's p, m, v (row-major [G.M][G.N], as C).
+struct WAdam {
+  float* p;
+  float* m;
+  float* v;
+  unsigned* amax;           // may be NULL: max |p| after the update is added here (atomic max)
+  unsigned* flag;           // may be NULL: VG_NONFINITE_* bits are ORed in here
+  float* g_out;             // may be NULL: the gradient is stored here as well
+  float omb1, b2, omb2, step_size, bc2s, eps;
+  const float* scalars;     // NULL, or the device words [step_size, bc2s] of vg_adam_prepare
+};
+constexpr int G_TSTR = GTN / 4 + 1;      // fused step: 16-byte units per row of the gradient tile in LDS (one of padding)
+constexpr int G_TIT = GTM * (GTN / 4) / GNT;      // ... and 16-byte units of it per thread
+
 __device__ __forceinline__ void load8(float* r, const float* p, long ks, bool strided) {
   if (strided) {
 #pragma unroll
@@ -87,12 +102,21 @@ __device__ __forceinline__ void load8(float* r, const float* p, long ks, bool st
 
 // AT / BT: the operand's ROW index is the contiguous one (reduction index strided); NG: groups (A_g, C_g) sharing B.
 // NG > 1: one workgroup per CU (LDS: 2 x (NG + 1) x 16.6 KB; NG accumulator sets)
-template <bool AT, bool BT, bool M16, int NG>
-__global__ __launch_bounds__(GNT, NG == 1 ? 2 : 1) void gemm_nt_f16x3_kernel(GArgs G) {
+//
+// ADAM (the fused weight-gradient step; AT, BT, no K split, one group): the tile is not stored.  A thread owns G_TIT
+// 16-byte units of the tile's p, m, v -- unit (row it * 16 + tid / 32, columns 4 (tid % 32) ..): a wavefront covers two
+// whole 512-byte row segments.  After the last stage the accumulators go through LDS (the staging buffers are free
+// then) into that layout: 16-byte accesses on p, m, v, whole rows of the tile per wavefront.  The gradient element is the
+// epilogue's own expression; the update is adam_one_as' "body" form: p, m, v, the amax word and the flag bits are those
+// of vg_gemm_nt_f16x3 followed by the plain Adam step.
+template <bool AT, bool BT, bool M16, int NG, bool ADAM>
+__device__ __forceinline__ void gemm_nt_f16x3_body(const GArgs& G, const WAdam& W) {
+  static_assert(!ADAM || (AT && BT && !M16 && NG == 1 && G_HN == 1), "the fused step is the weight gradient's orientation");
   constexpr int NA = NG * G_NU, NUN = NA + G_NU;       // staged units per thread: [0, NA) A of group u / G_NU; then B
   constexpr int BOFF = G_NP * NG * G_PL;               // B planes follow the groups' A planes
   constexpr int BUFU = BOFF + G_NP * G_PL;
-  __shared__ f32x4 lds[2 * BUFU];                      // [buffer][A_0 planes | .. | A_{NG-1} planes | B planes][k-block][row]
+  constexpr int LDSU = (ADAM && GTM * G_TSTR > 2 * BUFU) ? GTM * G_TSTR : 2 * BUFU;
+  __shared__ f32x4 lds[LDSU];                          // [buffer][A_0 planes | .. | A_{NG-1} planes | B planes][k-block][row]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kb = lane >> 5, l32 = lane & 31;
@@ -215,6 +239,11 @@ __global__ __launch_bounds__(GNT, NG == 1 ? 2 : 1) void gemm_nt_f16x3_kernel(GAr
         xb[h][p] = __builtin_bit_cast(bf16x8, base[BOFF + p * G_PL + q16 * G_KB + wcol + h * 16 + l16]);
   };
 
+  // fused step: this thread's units of the tile
+  const int t_row = tid >> 5, t_col = n0 + 4 * (tid & 31);      // (G.N % 4 == 0: a unit is inside the row or outside)
+  auto t_ok = [&](int it) { return m0 + it * (GNT / 32) + t_row < G.M && t_col < G.N; };
+  auto t_off = [&](int it) { return (size_t)(m0 + it * (GNT / 32) + t_row) * G.N + t_col; };
+
   if (nst > 0) {
     // stages past the end re-load the last one (never consumed): every register slot always holds valid data
 #pragma unroll
@@ -306,6 +335,58 @@ __global__ __launch_bounds__(GNT, NG == 1 ? 2 : 1) void gemm_nt_f16x3_kernel(GAr
 
   // ---- epilogue: undo the two scales (exact), C (or this split's slab) row-major [M][N]; the bias goes in with split 0
   const float ub = f16_unscale_of(*G.b_amax);
+  if constexpr (ADAM) {
+    const float ua = f16_unscale_of(*G.a_amax[0]);
+    float* const tile = reinterpret_cast<float*>(lds);      // (every stage ends with a barrier: the buffers are free)
+#pragma unroll
+    for (int g = 0; g < 2; ++g)
+#pragma unroll
+      for (int r16 = 0; r16 < 16; ++r16)
+        tile[(wm * 64 + g * 32 + acc_row(r16, lane)) * (4 * G_TSTR) + wcol + l32] = acc[0][g][0][r16] * ua * ub + 0.f;
+    __syncthreads();
+    float step_size = W.step_size, bc2s = W.bc2s;
+    if (W.scalars) {
+      step_size = W.scalars[0];
+      bc2s = W.scalars[1];
+    }
+    unsigned am = 0, gm = 0;
+    // G_TB units at a time: their p, m, v loads are issued together, in the registers the accumulators have left
+    constexpr int G_TB = 4;
+    static_assert(G_TIT % G_TB == 0, "batches of the fused step");
+#pragma unroll
+    for (int it0 = 0; it0 < G_TIT; it0 += G_TB) {
+    f32x4 sp[G_TB], sm[G_TB], sv[G_TB];
+#pragma unroll
+    for (int j = 0; j < G_TB; ++j) {
+      sp[j] = sm[j] = sv[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (t_ok(it0 + j)) {
+        sp[j] = *reinterpret_cast<const f32x4*>(W.p + t_off(it0 + j));
+        sm[j] = *reinterpret_cast<const f32x4*>(W.m + t_off(it0 + j));
+        sv[j] = *reinterpret_cast<const f32x4*>(W.v + t_off(it0 + j));
+      }
+    }
+#pragma unroll
+    for (int it = it0; it < it0 + G_TB; ++it) {
+      if (!t_ok(it)) continue;
+      const f32x4 gv = lds[(it * (GNT / 32) + t_row) * G_TSTR + (tid & 31)];
+      f32x4 pv = sp[it - it0], mv = sm[it - it0], vv = sv[it - it0];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float pj = pv[j], mj = mv[j], vj = vv[j];
+        adam_one_as(true, pj, gv[j], mj, vj, W.omb1, W.b2, W.omb2, step_size, bc2s, W.eps);
+        pv[j] = pj; mv[j] = mj; vv[j] = vj;
+        am = max(am, abs_bits(pj));
+        gm = max(gm, abs_bits(gv[j]));
+      }
+      *reinterpret_cast<f32x4*>(W.p + t_off(it)) = pv;
+      *reinterpret_cast<f32x4*>(W.m + t_off(it)) = mv;
+      *reinterpret_cast<f32x4*>(W.v + t_off(it)) = vv;
+      if (W.g_out) *reinterpret_cast<f32x4*>(W.g_out + t_off(it)) = gv;
+    }
+    }
+    emit_amax_and_flags<GNT>(am, gm, W.amax, W.flag);
+    return;
+  }
 #pragma unroll
   for (int gi = 0; gi < NG; ++gi) {
   const float ua = f16_unscale_of(*G.a_amax[gi]);
@@ -350,6 +431,22 @@ __global__ __launch_bounds__(GNT, NG == 1 ? 2 : 1) void gemm_nt_f16x3_kernel(GAr
   }
   }
 }
+
+template <bool AT, bool BT, bool M16, int NG>
+__global__ __launch_bounds__(GNT, NG == 1 ? 2 : 1) void gemm_nt_f16x3_kernel(GArgs G) {
+  gemm_nt_f16x3_body<AT, BT, M16, NG, false>(G, WAdam{});
+}
+
+// The fused weight-gradient step: two workgroups per CU, as the GEMM -- one streams its p, m, v while the other is in its
+// reduction or in the update's divisions and square roots (one workgroup per CU with the tile's state loaded under the
+// reduction left the memory pipe idle through both: DESIGN.md section 4.19).
+__global__ __launch_bounds__(GNT, 2) void linear_wgrad_adam_kernel(GArgs G, WAdam W) {
+  gemm_nt_f16x3_body<true, true, false, 1, true>(G, W);
+}
+
+// One thread: the weight's bound word back to zero in front of the fused step's atomic maxima -- in stream order behind
+// the layer's data-gradient GEMM, which still scales the weight by the old bound.
+__global__ void zero_word_kernel(unsigned* __restrict__ w) { w[0] = 0u; }
 
 // K split: as many splits as keep >= 8 stages each and bring the grid to about G_TARGET_WGS workgroups
 constexpr int G_TARGET_WGS = 256;
@@ -455,4 +552,56 @@ extern "C" int vg_gemm_nt_f16x3_grouped(int groups, const float* const* A, const
                                         const float* b_amax, void* workspace, size_t workspace_bytes, void* stream) {
   return gemm_launch(groups, A, B, bias, C, M, N, K, a_row_stride, a_k_stride, b_row_stride, b_k_stride, a_amax, b_amax,
                      workspace, workspace_bytes, stream);
+}
+
+// ---- the weight gradient of a Linear layer and its Adam step in one kernel -------------------------------------------
+namespace {
+
+int wgrad_adam_launch(const float* gy, const float* x, int M, int N, int K, const float* gy_amax, const float* x_amax,
+                      float* p, float* m, float* v, float* amax, unsigned* nonfinite, double beta1, double beta2,
+                      double eps, float step_size, float bc2s, const float* scalars, float* g_out, void* stream) {
+  if (!gy || !x || !gy_amax || !x_amax || !p || !m || !v) return VG_ERR_BAD_ARG;
+  // the GEMM is C[N][K] = sum over M: A = gy read as [n][b], B = x read as [k][b]
+  if (!gemm_ok(N, K, M, 1, N, 1, K)) return VG_ERR_BAD_ARG;      // (the reduction M is a multiple of 32)
+  if (gemm_ksplit(N, K, M) != 1) return VG_ERR_BAD_ARG;          // slabs: the gradient is not complete in one workgroup
+  if (K % 4 || ((size_t)N * K) % 4) return VG_ERR_BAD_ARG;       // every element on the step's 16-byte body
+  if (((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)g_out) & 15) return VG_ERR_BAD_ARG;
+  if ((size_t)N * K > 0x7fffffffUL) return VG_ERR_BAD_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  GArgs G = {};
+  G.A[0] = gy; G.B = x; G.a_amax[0] = gy_amax; G.b_amax = x_amax;
+  G.M = N; G.N = K; G.K = M;
+  G.ars = 1; G.aks = N; G.brs = 1; G.bks = K;
+  G.kper = M; G.ksplit = 1;
+  G.tiles_m = cdiv(N, GTM); G.tiles_n = cdiv(K, GTN);
+  WAdam W = {p, m, v, reinterpret_cast<unsigned*>(amax), nonfinite, g_out, (float)(1.0 - beta1), (float)beta2,
+             (float)(1.0 - beta2), step_size, bc2s, (float)eps, scalars};
+  if (amax) {
+    hipLaunchKernelGGL(zero_word_kernel, dim3(1), dim3(1), 0, st, reinterpret_cast<unsigned*>(amax));
+    VG_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(linear_wgrad_adam_kernel, dim3((unsigned)(G.tiles_m * G.tiles_n)), dim3(GNT), 0, st, G, W);
+  VG_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int vg_linear_wgrad_adam(const float* gy, const float* x, int M, int N, int K, const float* gy_amax,
+                                    const float* x_amax, float* p, float* m, float* v, float* amax, unsigned* nonfinite,
+                                    double lr, double beta1, double beta2, double eps, double bias_correction1,
+                                    double bias_correction2_sqrt, float* g_out, void* stream) {
+  if (!(bias_correction1 > 0.0) || !(bias_correction2_sqrt > 0.0)) return VG_ERR_BAD_ARG;
+  // scalars formed in double and rounded once, as vg_adam_step forms them
+  return wgrad_adam_launch(gy, x, M, N, K, gy_amax, x_amax, p, m, v, amax, nonfinite, beta1, beta2, eps,
+                           (float)(lr / bias_correction1), (float)bias_correction2_sqrt, nullptr, g_out, stream);
+}
+
+extern "C" int vg_linear_wgrad_adam_dev(const float* gy, const float* x, int M, int N, int K, const float* gy_amax,
+                                        const float* x_amax, float* p, float* m, float* v, float* amax,
+                                        unsigned* nonfinite, double beta1, double beta2, double eps, const float* scalars,
+                                        float* g_out, void* stream) {
+  if (!scalars) return VG_ERR_BAD_ARG;
+  return wgrad_adam_launch(gy, x, M, N, K, gy_amax, x_amax, p, m, v, amax, nonfinite, beta1, beta2, eps, 0.f, 0.f, scalars,
+                           g_out, stream);
 }

@@ -162,6 +162,30 @@ DEFER_MIN_WEIGHTS = 1 << 20
 DEFER_WGRAD = os.environ.get("VG_DEFER_WGRAD", "1") != "0"      # 0: deferred_wgrad() does nothing
 
 
+# The weight gradient of a big Linear layer and its Adam step in one launch (ops.linear_wgrad_adam; DESIGN.md section
+# 4.19): on where a trainer has opened registrations for the backward (`open_fused_linear_steps`).  0: never.
+FUSE_LINEAR_ADAM = os.environ.get("VG_FUSE_LINEAR_ADAM", "1") != "0"
+# {id(weight): optim.FusedLinearStep} of the backward passes about to run.  A plain module dictionary, not a thread-local:
+# autograd runs the backward nodes of a device on its own worker thread.  An entry counts only while it is `open` and only
+# for the weight object it was made for, so two trainers in two threads do not see each other's.
+_fused_steps = {}
+
+
+def open_fused_linear_steps(regs):
+    """``regs``: what `optim.HipAdam.begin_fused_step` returned (None / empty: nothing is added).  From here to the
+    optimizer's `step` -- which closes every registration -- the backward of a registered weight updates it in place
+    and hands autograd no gradient.  Registrations that were closed since are forgotten here."""
+    for k in [k for k, r in _fused_steps.items() if not r.open]:
+        del _fused_steps[k]
+    if regs:
+        _fused_steps.update(regs)
+
+
+def _fused_step_of(w):
+    reg = _fused_steps.get(id(w))
+    return reg if (reg is not None and reg.open and reg.p is w) else None
+
+
 def _linear_weight_grad(acc, defer, w, gy, x):
     """The weight gradient of one pass (gy, x) of a Linear layer under both protocols -- `deferred_wgrad` (``defer``: the
     context the pass was made in, or None) and `accumulate_param_grads` (``acc``).  Returns what the pass hands autograd:
@@ -178,6 +202,15 @@ def _linear_weight_grad(acc, defer, w, gy, x):
             wg, wx = torch.cat([p[0] for p in pairs]), torch.cat([p[1] for p in pairs])
     slot = _grad_slot(acc, id(w))
     split = ops.linear_split_ok(wg.shape[0], w.numel())
+    reg = _fused_step_of(w) if FUSE_LINEAR_ADAM else None
+    if reg is not None:
+        if reg.done:
+            raise RuntimeError("a Linear weight that took the fused weight-gradient + Adam step was used a second time "
+                               "in the same backward")
+        # (a slot that already holds a gradient: the layer's second use in this backward -- the two launches)
+        if split and slot.prev is None and ops.linear_wgrad_adam(wg, wx, reg):
+            reg.done = True
+            return None                              # the weight is updated: nothing for autograd, no ``.grad``
     if slot.prev is None:
         return slot.hand_over(ops.linear_wgrad(wg, wx) if split else wg.t() @ wx)
     if split:

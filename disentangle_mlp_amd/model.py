@@ -257,6 +257,23 @@ def shadowed_bias_params(net):
             if isinstance(m, (HipConv2d, HipConvTranspose2d, HipLinear)) and m.bn_shadowed and m.bias is not None]
 
 
+def single_use_linear_weights(net, deferred=True):
+    """The weights of the big Linear layers whose weight gradient a trainer's backward of ``net`` forms exactly once: the
+    encoder heads ``x_to_mu.0`` / ``x_to_logvar.0`` (one pass per backward) and -- ``deferred``: inside
+    `functional.deferred_wgrad`, which batches its passes into one -- the discriminator's ``lth_features.0``.  These may
+    be updated inside the backward (functional.FUSE_LINEAR_ADAM).  The decoder's 128 -> 16384 layer is not among them:
+    the beta-VAE-GAN's second phase runs it on the prior sample and on the reconstruction before one backward, and its
+    first backward pass must not change a weight the second still reads."""
+    names = ("x_to_mu", "x_to_logvar") + (("lth_features",) if deferred else ())
+    out = []
+    for m in net.modules():
+        for name in names:
+            seq = getattr(m, name, None)
+            if isinstance(seq, nn.Sequential) and len(seq) and isinstance(seq[0], HipLinear):
+                out.append(seq[0].weight)
+    return out
+
+
 # --------------------------------------------------------------- building blocks
 # Conv <-> BatchNorm fusion (SURVEY.md K5): inside a chain conv -> BN -> act -> conv -> ... the statistics of every
 # BatchNorm come from the producing convolution's epilogue, and its normalise + activation are applied by the

@@ -809,6 +809,32 @@ def linear_wgrad(gy, x):
     return _gemm_nt(gy, x, None, gw, N, K, M, 1, N, 1, K, amax_of(gy), amax_of(x))
 
 
+def linear_wgrad_adam(gy, x, reg):
+    """`linear_wgrad` and the plain Adam step of the weight in ONE launch (``vg_linear_wgrad_adam`` / ``_dev``): the
+    gradient gy^T x is consumed in registers and never written.  ``reg``: the weight's registration for this step
+    (optim.FusedLinearStep: p, m, v, its bound word -- zeroed by the entry, in stream order behind the layer's data
+    gradient -- its flag word, the step's scalars).  p, m, v, the bound and the flag bits are what `linear_wgrad` followed
+    by the optimizer's own launch leave.  Returns False -- nothing was launched -- when the entry point refuses the
+    shape (a reduction that is split over workgroups): the caller takes the two launches."""
+    _req(gy, "gy"), _req(x, "x")
+    lib = _lib.load()
+    M, N = gy.shape
+    K = x.shape[1]
+    if tuple(reg.p.shape) != (N, K):
+        raise RuntimeError(f"linear_wgrad_adam: weight {tuple(reg.p.shape)} against a ({N}, {K}) gradient")
+    head = (gy.data_ptr(), x.data_ptr(), M, N, K, amax_of(gy).data_ptr(), amax_of(x).data_ptr(), reg.p.data_ptr(),
+            reg.m.data_ptr(), reg.v.data_ptr(), reg.amax.data_ptr(), _ptr(reg.flag))
+    if reg.scalars is not None:
+        rc = lib.vg_linear_wgrad_adam_dev(*head, reg.beta1, reg.beta2, reg.eps, reg.scalars.data_ptr(), None, _stream())
+    else:
+        rc = lib.vg_linear_wgrad_adam(*head, reg.lr, reg.beta1, reg.beta2, reg.eps, reg.bc1, reg.bc2_sqrt, None,
+                                      _stream())
+    if rc == -1:                                         # VG_ERR_BAD_ARG: refused before any launch
+        return False
+    check(rc, "vg_linear_wgrad_adam")
+    return True
+
+
 def channel_sum(g):
     lib = _lib.load()
     _req(g, "g")

@@ -86,6 +86,38 @@ class _AdamTensor(ctypes.Structure):
                 ("n", ctypes.c_size_t), ("amax", ctypes.c_void_p)]
 
 
+def linear_adam_eligible(*, switch=True, grad_hook=False, exchange=False, update_ema=False, clip=False,
+                         weight_decay=0.0, device_hyper=False, amsgrad=False, maximize=False, requires_grad=True,
+                         dim=2, numel=0, in_features=0, native_tensor=True, split_ok=True):
+    """Whether a Linear weight may take the fused weight-gradient + Adam launch (``vg_linear_wgrad_adam``) in the step
+    that is about to begin -- a pure function of the switches.  The route is for the plain native step alone: no EMA on
+    this call, no clip / skip record, no weight decay, no ``device_hyper``, not amsgrad / maximize; the trainer's side
+    (``switch``: functional.FUSE_LINEAR_ADAM; a ``grad_hook`` wants to see the gradient; a FlatGrads ``exchange`` must
+    reduce it first; a frozen weight gets none); and the entry point's own conditions on the weight (``split_ok``:
+    `ops.linear_split_ok` takes the layer; rows of a multiple of 4 floats; a contiguous fp32 device tensor).  The
+    conditions on the REDUCTION (a multiple of 32, not split over workgroups) are only known in the backward: the entry
+    point refuses there and the backward falls back to the two launches."""
+    if not switch or grad_hook or exchange:
+        return False
+    if update_ema or clip or float(weight_decay) != 0.0 or device_hyper or amsgrad or maximize:
+        return False
+    if not requires_grad or not native_tensor or dim != 2 or not split_ok:
+        return False
+    return in_features % 4 == 0 and numel % 4 == 0 and 0 < numel <= 0x7fffffff
+
+
+class FusedLinearStep:
+    """One weight's registration for one step (`HipAdam.begin_fused_step`): what `ops.linear_wgrad_adam` hands the
+    entry point.  ``done``: the backward has updated the weight; ``open``: until the step() that closes it."""
+    __slots__ = ("p", "m", "v", "amax", "flag", "scalars", "lr", "beta1", "beta2", "eps", "bc1", "bc2_sqrt", "gi", "step",
+                 "born", "done", "open")
+
+    def __init__(self, **kw):
+        self.done, self.open = False, True
+        for k, val in kw.items():
+            setattr(self, k, val)
+
+
 class HipAdam(optim.Adam):
     """``capturable=True``: the step's scalars (lr / bias_correction1, sqrt(bias_correction2)) are formed on the DEVICE
     by ``vg_adam_prepare`` -- from the host's step count in an eager step, from a device counter in a step that is being
@@ -130,6 +162,8 @@ class HipAdam(optim.Adam):
         if self.device_hyper:
             for gi in range(len(self.param_groups)):
                 self._hyper_words(gi)
+        self._fused = None        # the open registrations of `begin_fused_step`: ([FusedLinearStep], {group index: step})
+        self._bound_masks = {}    # frozenset of bound-word indices the backward wrote -> bool mask of the words to zero
         self._captured = []       # per captured step() call: the parameters it stepped (host bookkeeping of a replay)
         self._debt = 0            # replays whose host-side step counts have not been added yet (flushed lazily)
         self.state_generation = 0 # bumped by load_state_dict: captured graphs point at the moment tensors of one generation
@@ -480,6 +514,108 @@ class HipAdam(optim.Adam):
             if group.get("amsgrad", False):
                 st["max_exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
 
+    # ---- the fused weight-gradient + Adam launch of the big Linear layers -------------------------------------------
+    @torch.no_grad()
+    def begin_fused_step(self, update_ema=True, switch=True, grad_hook=False, exchange=False, only=None):
+        """The first half of a two-part step: registers every big Linear weight that may be updated INSIDE the backward
+        (`linear_adam_eligible`; ``vg_linear_wgrad_adam``: the weight gradient is consumed in registers and never
+        written) and returns ``{id(weight): FusedLinearStep}`` for `functional.open_fused_linear_steps`.  Creates missing
+        state and, for a capturable optimizer, runs the ONE ``vg_adam_prepare`` of the group's step; the host step count
+        of a weight moves in `step`, and only if the backward reached it -- one that it did not reach is not stepped, as
+        with ``grad is None``.  `step(update_ema=...)` with the same ``update_ema`` must follow.  ``only``: the weights
+        the caller knows to get ONE weight-gradient pass in the coming backward (a layer used twice must not take the
+        route: its first pass would change a weight its second still reads); None: every eligible one."""
+        self._fused = None
+        only = None if only is None else {id(p) for p in only}
+        if not all(self._native_ok(g) for g in self.param_groups):
+            return {}
+        capturing = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+        if capturing and not self.device_scalars:
+            return {}
+        bounds = self._weight_bounds()
+        if bounds is None:
+            return {}
+        if not capturing:
+            self._flush_replays()
+        ema_on = self._ema is not None and update_ema
+        regs, prepared = [], {}
+        for gi, group in enumerate(self.param_groups):
+            mine = []
+            for p in group["params"]:
+                if p not in self._bound_of or (only is not None and id(p) not in only):
+                    continue
+                ok = linear_adam_eligible(
+                    switch=switch, grad_hook=grad_hook, exchange=exchange, update_ema=ema_on,
+                    clip=self._clip_rec is not None, weight_decay=group["weight_decay"], device_hyper=self.device_hyper,
+                    amsgrad=group["amsgrad"], maximize=group.get("maximize", False), requires_grad=p.requires_grad,
+                    dim=p.dim(), numel=p.numel(), in_features=p.shape[-1],
+                    native_tensor=p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.data_ptr() % 16 == 0,
+                    split_ok=bool(ops.linear_split_ok(32, p.numel())))
+                if ok:
+                    mine.append(p)
+            if not mine:
+                continue
+            born = [p for p in mine if len(self.state[p]) == 0]
+            born_ids = {id(p) for p in born}
+            for p in born:
+                self._init_state(p, group)
+            for p in mine:
+                if self.state[p]["step"].is_cuda:
+                    self.state[p]["step"] = self.state[p]["step"].cpu()
+            steps = {float(self.state[p]["step"]) + 1.0 for p in mine}
+            if len(steps) > 1:                           # (one prepare per group: they must share its step)
+                for p in born:
+                    del self.state[p]
+                continue
+            step = steps.pop()
+            beta1, beta2 = group["betas"]
+            scalars = None
+            if self.device_scalars:
+                step_dev, scalars = self._device_state(gi, mine[0].device)
+                check(_lib.load().vg_adam_prepare(float(step), step_dev.data_ptr(), 1 if capturing else 0,
+                                                  float(group["lr"]), float(beta1), float(beta2), scalars.data_ptr(),
+                                                  torch.cuda.current_stream().cuda_stream), "vg_adam_prepare")
+                prepared[gi] = step
+            for p in mine:
+                st = self.state[p]
+                m, v = st["exp_avg"], st["exp_avg_sq"]
+                if not (m.is_contiguous() and v.is_contiguous() and m.data_ptr() % 16 == 0 and v.data_ptr() % 16 == 0):
+                    continue
+                bi = self._bound_of[p]
+                regs.append(FusedLinearStep(
+                    p=p, m=m, v=v, amax=bounds[bi:bi + 1],
+                    flag=self._words[self._word_of[p]:self._word_of[p] + 1] if self.nonfinite_guard else None,
+                    scalars=scalars, lr=float(group["lr"]), beta1=float(beta1), beta2=float(beta2),
+                    eps=float(group["eps"]), bc1=1.0 - beta1 ** step, bc2_sqrt=math.sqrt(1.0 - beta2 ** step), gi=gi,
+                    step=step, born=id(p) in born_ids))
+        self._fused = (regs, prepared)
+        return {id(r.p): r for r in regs}
+
+    def _close_fused(self, capturing):
+        """The second half: closes the registrations; counts the weights the backward updated (host step count, replay
+        bookkeeping) and forgets the state created for one it never reached.  Returns (the updated weights, {group index:
+        the step `begin_fused_step` has prepared the device scalars for})."""
+        if self._fused is None:
+            return set(), {}
+        regs, prepared = self._fused
+        self._fused = None
+        done = set()
+        by_group = {}
+        for r in regs:
+            r.open = False
+            if r.done:
+                if r.p.grad is not None:
+                    raise RuntimeError("HipAdam: a weight updated inside the backward also received a gradient (a layer "
+                                       "used twice in one backward must not take the fused step)")
+                self.state[r.p]["step"] += 1
+                done.add(r.p)
+                by_group.setdefault(r.gi, []).append(r.p)
+            elif r.born and r.p.grad is None:
+                del self.state[r.p]
+        if capturing:
+            self._captured.extend(by_group.values())
+        return done, prepared
+
     @torch.no_grad()
     def step(self, closure=None, update_ema=True):
         """``update_ema`` (with ``ema_decay`` set): False steps without touching the averages -- exactly the launches of
@@ -492,6 +628,17 @@ class HipAdam(optim.Adam):
         ``exp_avg``, ``exp_avg_sq`` and the EMA untouched but still ADVANCES the step count, the host's and the device
         counter alike: a count that depends on the data would need a host read inside a captured iteration.  The bias
         corrections of later steps therefore see one more step than updates were made."""
+        born = self._fused is not None and any(r.born for r in self._fused[0])
+        fused_done, fused_prepared = self._close_fused(torch.cuda.is_available()
+                                                       and torch.cuda.is_current_stream_capturing())
+        loss = self._step_rest(closure, update_ema, fused_done, fused_prepared)
+        if born:      # `begin_fused_step` created state ahead of the others: back to the order step() alone creates it in
+            for p in [p for g in self.param_groups for p in g["params"] if p in self.state]:
+                self.state[p] = self.state.pop(p)
+        return loss
+
+    def _step_rest(self, closure, update_ema, fused_done, fused_prepared):
+        """`step` behind the registrations of `begin_fused_step`: everything that still has a gradient."""
         ema_on = self._ema is not None and update_ema
         clip_on = self._clip_rec is not None
         if closure is not None or not all(self._native_ok(g) for g in self.param_groups):
@@ -540,7 +687,10 @@ class HipAdam(optim.Adam):
             self.sync_hyper()
         bounds = self._weight_bounds()
         if bounds is not None:
-            bounds.zero_()
+            if not fused_done:
+                bounds.zero_()
+            else:                                        # the words the backward has written already stay
+                self._zero_bounds_except(bounds, fused_done)
         words = self._words.data_ptr() if self.nonfinite_guard else None
         rec = None
         if clip_on:                                  # the grid-wide answer in front of the first store
@@ -571,7 +721,7 @@ class HipAdam(optim.Adam):
                 if not (m.is_contiguous() and v.is_contiguous()):
                     raise RuntimeError("HipAdam: optimizer state must be contiguous")
                 by_step.setdefault(float(st["step"]), []).append((p, p.grad, m, v))
-            if capturing and len(by_step) > 1:
+            if capturing and len(set(by_step) | ({fused_prepared[gi]} if gi in fused_prepared else set())) > 1:
                 raise RuntimeError("HipAdam: a captured step needs every parameter of a group at the same step count")
             for step, items in by_step.items():
                 arr = (_AdamTensor * len(items))()
@@ -589,7 +739,9 @@ class HipAdam(optim.Adam):
                     step_dev, scalars = self._device_state(gi, items[0][0].device)
                     # an eager step also stores its count in the device counter: replays may follow it
                     ema_dev = ema is not None and self._ema_omd is not None
-                    if self.device_hyper or wd != 0.0 or ema_dev:
+                    if fused_prepared.get(gi) == step and not (self.device_hyper or wd != 0.0 or ema_dev):
+                        pass                             # `begin_fused_step` ran this step's vg_adam_prepare
+                    elif self.device_hyper or wd != 0.0 or ema_dev:
                         hyper = self._hyper_words(gi)
                         if not capturing:
                             self.sync_hyper()      # (words that came into being just now)
@@ -649,7 +801,9 @@ class HipAdam(optim.Adam):
         if bounds is not None:
             for p, bi in self._bound_of.items():
                 slot = bounds[bi:bi + 1]
-                if p.grad is None:      # not stepped: its word was zeroed with the others -- measured again (rare: a frozen layer)
+                if p in fused_done:     # stepped inside the backward: the fused launch wrote its word
+                    pass
+                elif p.grad is None:    # not stepped: its word was zeroed with the others -- measured again (rare: a frozen layer)
                     check(lib.vg_absmax(p.data_ptr(), p.numel(), slot.data_ptr(), stream), "vg_absmax")
                 ops.set_weight_bound(p, slot)
         return None
@@ -668,6 +822,20 @@ class HipAdam(optim.Adam):
             slot = bounds[bi:bi + 1]
             check(lib.vg_absmax(p.data_ptr(), p.numel(), slot.data_ptr(), stream), "vg_absmax")
             ops.set_weight_bound(p, slot)
+
+    def _zero_bounds_except(self, bounds, keep):
+        """Zero the bound words of every weight but those in ``keep`` (one fill-by-mask launch; the mask is built once
+        per set, from device fills alone, so that a capture may build it too)."""
+        key = frozenset(self._bound_of[p] for p in keep)
+        if len(key) == bounds.numel():
+            return
+        mask = self._bound_masks.get(key)
+        if mask is None:
+            mask = torch.ones(bounds.numel(), dtype=torch.bool, device=bounds.device)
+            for i in key:
+                mask[i:i + 1].fill_(False)
+            self._bound_masks[key] = mask
+        bounds.masked_fill_(mask, 0.0)
 
     def _weight_bounds(self):
         """The bounds tensor (one word per Linear weight the fp16x3 GEMM takes), or None when there is none."""

@@ -496,6 +496,7 @@ class _GraphedSteps:
         has_beta = hasattr(self, "beta")
         self.opt = opt or ModelOpt()
         self.device = torch.device(device)
+        self._single_use = {}     # (id(network), DEFER_WGRAD) -> its weights that may be updated inside the backward
         on_gpu = self.device.type == "cuda"
         _use_tuned_gemms(self.device)
         self._tc_args(tc_decomposition, dataset_size, has_beta)
@@ -945,7 +946,7 @@ class _GraphedSteps:
         """Host-side switches a capture freezes besides the shapes: part of every capture key, so that flipping one
         captures anew instead of replaying the old launches."""
         from . import model as M
-        return (M.FUSE_CONV_BN, M.FUSE_HEAD_BCE, F.DEFER_WGRAD, ops.THIN_SPLIT, ops.USE_PACKED_FILTERS,
+        return (M.FUSE_CONV_BN, M.FUSE_HEAD_BCE, F.DEFER_WGRAD, F.FUSE_LINEAR_ADAM, ops.THIN_SPLIT, ops.USE_PACKED_FILTERS,
                 self.nonfinite_guard,        # (checked or unchecked Adam launches)
                 self.max_grad_norm, self.skip_nonfinite,      # (the norm pass and the clip step, or neither)
                 self.device_hyper,           # (lr, weight decay and beta read from device words, or frozen arguments)
@@ -967,11 +968,22 @@ class _GraphedSteps:
                      else cap.inputs[name].normal_(generator=self.latent_generator)
                      for name, t in zip(self._latents, given))
 
-    def _zero(self, net, flat):
+    def _zero(self, net, flat, opt=None, grad_hook=None, update_ema=True):
+        """A phase's zeroing.  ``opt``: the optimizer whose `step` ends the phase -- the big Linear weights the coming
+        backward reaches once are registered with it and updated INSIDE the backward (HipAdam.begin_fused_step,
+        functional.FUSE_LINEAR_ADAM; ``update_ema`` as that `step` will be called), unless a ``grad_hook`` wants to see
+        their gradients or a gradient exchange has to reduce them first.  The `step` closes the registrations."""
         if flat is not None:
             flat.zero_and_attach()
         else:
             _zero_grads(net)
+        regs = None
+        if isinstance(opt, HipAdam) and F.FUSE_LINEAR_ADAM and grad_hook is None and flat is None:
+            only = self._single_use.get((id(net), F.DEFER_WGRAD))
+            if only is None:                             # (a walk over the modules: once per network)
+                only = self._single_use[(id(net), F.DEFER_WGRAD)] = _model.single_use_linear_weights(net, F.DEFER_WGRAD)
+            regs = opt.begin_fused_step(update_ema=update_ema, only=only)
+        F.open_fused_linear_steps(regs)
 
     def _exchange(self, flat):
         if flat is not None and (self.world > 1 or FlatGrads.exchange_when_alone):
@@ -1152,7 +1164,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
         out = {}
 
         # ---- phase 1: discriminator (:95-123)
-        self._zero(netD, self.flat_d)
+        self._zero(netD, self.flat_d, self.optimizerD, grad_hook)
         fake = netEG.decode(noise)                           # graph kept for phase 2 (:113)
         if self.probe is not None and fake.requires_grad:    # diagnostics (bench.py `regime`): such an iteration is eager
             fake.register_hook(lambda g: self.probe("grad_wrt_fake", g))
@@ -1173,7 +1185,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
         out["D_x_sum"] = p_real.detach().sum()
 
         # ---- phase 2: "decoder" -- every EG parameter moves (:127-164)
-        self._zero(netEG, self.flat_eg)
+        self._zero(netEG, self.flat_eg, self.optimizerEG, grad_hook, update_ema=False)      # (phase 2 never averages)
         self._set_frozen(netD, True)
         recon, mu, logvar = netEG(data, eps2)
         # D three times on frozen weights -- on data as under no_grad (D fwd #3: BN statistics still update), on fake and
@@ -1200,7 +1212,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
                    mse_dec=mse2.detach())
 
         # ---- phase 3: "encoder" -- again every EG parameter moves (:167-193)
-        self._zero(netEG, self.flat_eg)
+        self._zero(netEG, self.flat_eg, self.optimizerEG, grad_hook)
         recon, mu, logvar, kld, parts = self._forward_kl(netEG, data, eps3)
         mse3 = F.reconstruction_loss(recon, data)
         _backward([kld, mse3])
@@ -1454,7 +1466,7 @@ class VAETrainer(_GraphedSteps):
     def _iteration(self, data, latents, labels, grad_hook, prepack, acc):
         eps, = latents
         prepack()                             # the filters the previous optimizer step changed: one pack launch
-        self._zero(self.model, self.flat)
+        self._zero(self.model, self.flat, self.optimizer, grad_hook)
         recon, mu, logvar, kld, parts = self._forward_kl(self.model, data, eps)
         mse = F.reconstruction_loss(recon, data)
         _backward([mse, kld])
@@ -1520,7 +1532,7 @@ class GANTrainer(_GraphedSteps):
         noise, = latents
         real_label, fake_label, gb = labels
         prepack()
-        self._zero(self.netD, self.flat_d)
+        self._zero(self.netD, self.flat_d, self.optimizerD, grad_hook)
         fake = self.netG(noise)
         with F.deferred_wgrad():                             # as BetaVAEGANTrainer's discriminator phase
             f_real, f_fake = self.netD.features_grouped([data, fake.detach()])
@@ -1534,7 +1546,7 @@ class GANTrainer(_GraphedSteps):
         ops.invalidate_packed_filters([p for p in self.netD.parameters() if p.dim() == 4])
         prepack("d")
         acc.reset()
-        self._zero(self.netG, self.flat_g)
+        self._zero(self.netG, self.flat_g, self.optimizerG, grad_hook)
         self._set_frozen(self.netD, True)
         _, _, err_g = self.netD.forward_with_bce(fake, real_label, gb)
         _backward([err_g])

@@ -49,7 +49,7 @@ extern "C" {
  * vg_adam_step_ema, vg_adam_step_dev_ema; vg_grad_sumsq_partials, vg_grad_sumsq_multi, vg_grad_clip_finalize,
  * vg_adam_step_clip, vg_adam_step_dev_clip; vg_adam_prepare_dev, vg_adam_step_decay, vg_adam_step_dev_decay,
  * vg_reparam_kl_fwd_dev, vg_reparam_kl_bwd_dev; vg_adam_step_dev_ema_dev; the five vg_reparam_tc_* of
- * csrc/reparam_tc.hip) change
+ * csrc/reparam_tc.hip; vg_linear_wgrad_adam, vg_linear_wgrad_adam_dev) change
  * nothing an existing caller sees and keep the version: a binding that needs them and finds a library without them
  * fails at the symbol lookup, as loudly. */
 #define VG_ABI_VERSION 7
@@ -540,6 +540,26 @@ int vg_adam_step_checked(const VgAdamTensor* tensors, int count, double lr, doub
                          void* stream);
 int vg_adam_step_dev_checked(const VgAdamTensor* tensors, int count, double beta1, double beta2, double eps,
                              const float* scalars, unsigned* const* nonfinite, void* stream);
+/* The weight gradient of a big Linear layer and its plain Adam step in ONE kernel: gy (M x N), x (M x K), the weight
+ * and its moments p, m, v (N x K, fp32).  Every gradient element gW = gy^T x is formed as vg_gemm_nt_f16x3 forms it in
+ * this orientation (A = gy with a_row_stride = 1, B = x with b_row_stride = 1, reduction M) and is used, in registers,
+ * as the g of vg_adam_step_checked (host scalars) / vg_adam_step_dev_checked (the two device scalars of
+ * vg_adam_prepare): p, m, v, the amax word and the flag bits are bit for bit what that pair leaves, and the gradient
+ * is never written -- unless g_out (N x K, normally NULL) is given, which receives it as well (tests, diagnostics).
+ * gy_amax / x_amax: the operands' bound words, as for vg_gemm_nt_f16x3.  amax: NULL, or the weight's bound word -- it
+ * is ZEROED by a one-thread kernel in front of the fused kernel (in stream order behind the layer's data-gradient GEMM,
+ * which reads the old bound), then max |p| is added to it.  nonfinite: NULL, or the weight's flag word (the GRAD bit
+ * is judged on the gradient element, the PARAM bit on the new weight).
+ * VG_ERR_BAD_ARG before any launch unless: the reduction M is a multiple of 32 and not split over workgroups
+ * (vg_gemm_nt_f16x3_workspace_bytes(N, K, M) == 0), K % 4 == 0, and p, m, v (g_out) are 16-byte aligned -- every
+ * element is then on the plain step's 16-byte body. */
+int vg_linear_wgrad_adam(const float* gy, const float* x, int M, int N, int K, const float* gy_amax, const float* x_amax,
+                         float* p, float* m, float* v, float* amax, unsigned* nonfinite, double lr, double beta1,
+                         double beta2, double eps, double bias_correction1, double bias_correction2_sqrt, float* g_out,
+                         void* stream);
+int vg_linear_wgrad_adam_dev(const float* gy, const float* x, int M, int N, int K, const float* gy_amax,
+                             const float* x_amax, float* p, float* m, float* v, float* amax, unsigned* nonfinite,
+                             double beta1, double beta2, double eps, const float* scalars, float* g_out, void* stream);
 /* The two checked steps that also keep an exponential moving average of the weights they write.  `ema` is a HOST
  * array of `count` DEVICE pointers parallel to `tensors` (fp32, n elements each, not overlapping p, g, m, v); after
  * an element's p is updated the same thread does

@@ -16,6 +16,7 @@ fam = {}
 for t, c, a, n in out:
     key = ("ring conv" if "ring_kernel" in n else "wgrad split" if "wgrad_split8" in n else "other split conv" if "bf16split_kernel" in n
            else "thin (3-channel)" if "thin" in n else "relayout gy" if "relayout" in n else "slab sums" if ("reduce" in n or "slab_sum" in n)
+           else "Linear wgrad+Adam" if ("linear_wgrad_adam" in n or "zero_word" in n)
            else "BatchNorm" if ("bn_" in n or "bn1d" in n or "affine_act" in n or "stats_partial" in n) else "Adam" if "adam" in n
            else "absmax" if "absmax" in n else "pack" if "pack" in n else "vendor GEMM" if ("Cijk" in n or "gemm" in n.lower()) else "other")
     fam[key] = fam.get(key, 0.0) + t

@@ -86,6 +86,42 @@ class _AdamTensor(ctypes.Structure):
                 ("n", ctypes.c_size_t), ("amax", ctypes.c_void_p)]
 
 
+# The step's launch table, in priority order per kind of scalars: (entry point, device scalars?, the feature that selects
+# it, the arguments it takes between the common prefix and the stream -- names of `HipAdam._launch`'s values).  The
+# feature kernel behind clip and decay takes flag words, averages and a decay whether or not they are in use (NULL, 0.0).
+_STEP_TABLE = (
+    ("vg_adam_step_dev_ema_dev", True, "ema_dev", ("flags", "ema", "omd", "rec")),
+    ("vg_adam_step_dev_decay", True, "decay", ("flags", "ema", "ema_decay", "rec")),
+    ("vg_adam_step_dev_clip", True, "clip", ("flags", "ema", "ema_decay", "rec")),
+    ("vg_adam_step_dev_ema", True, "ema", ("flags", "ema", "ema_decay")),
+    ("vg_adam_step_dev_checked", True, "flags", ("flags",)),
+    ("vg_adam_step_dev", True, None, ()),
+    ("vg_adam_step_decay", False, "decay", ("flags", "ema", "ema_decay", "rec", "wd", "decoupled")),
+    ("vg_adam_step_clip", False, "clip", ("flags", "ema", "ema_decay", "rec")),
+    ("vg_adam_step_ema", False, "ema", ("flags", "ema", "ema_decay")),
+    ("vg_adam_step_checked", False, "flags", ("flags",)),
+    ("vg_adam_step", False, None, ()),
+)
+
+
+def step_entry(*, dev, flags, ema, ema_dev, decay, clip):
+    """(entry point, its tail) of one launch -- a pure function of the features: ``dev`` the scalars come from the device
+    (capturable); ``flags`` the guard's words; ``ema`` an average on this call; ``ema_dev`` its decay in the device word;
+    ``decay`` the group's weight decay is not 0; ``clip`` there is a clip / skip record.  The first row of `_STEP_TABLE`
+    for these scalars whose feature is on."""
+    on = {"ema_dev": ema_dev, "decay": decay, "clip": clip, "ema": ema, "flags": flags, None: True}
+    return next((name, tail) for name, on_dev, feature, tail in _STEP_TABLE if on_dev == bool(dev) and on[feature])
+
+
+def prepare_entry(*, device_hyper, decay, ema_dev, prepared):
+    """The kernel that forms a capturable step's scalars: ``vg_adam_prepare_dev`` when the step reads the group's device
+    pair [lr, weight_decay] (``device_hyper``, a weight decay that is not 0, or the EMA decay on the device, whose step
+    takes that route); else ``vg_adam_prepare`` -- or None when `HipAdam.begin_fused_step` has run it for this step."""
+    if device_hyper or decay or ema_dev:
+        return "vg_adam_prepare_dev"
+    return None if prepared else "vg_adam_prepare"
+
+
 def linear_adam_eligible(*, switch=True, grad_hook=False, exchange=False, update_ema=False, clip=False,
                          weight_decay=0.0, device_hyper=False, amsgrad=False, maximize=False, requires_grad=True,
                          dim=2, numel=0, in_features=0, native_tensor=True, split_ok=True):
@@ -126,22 +162,25 @@ class HipAdam(optim.Adam):
     and a replayed one give the same bits.  The ``state_dict`` stays torch.optim.Adam's (``step`` as a CPU tensor): the
     host mirrors the device counter (`prepare_capture` / `replayed`)."""
 
+    # What is laid out at construction, one slot per parameter or group -- so that a captured step writes where later
+    # readers read -- and therefore refuses a later `add_param_group`: (the attribute that holds it, its constructor
+    # argument as the message names it, what it is)
+    _LAID_OUT = (("device_hyper", "device_hyper=True", "hyper-parameter words"),
+                 ("_words", "nonfinite_guard=True", "flag words"),
+                 ("_ema", "ema_decay=...", "EMA tensors"),
+                 ("_clip_rec", "max_grad_norm=... / skip_nonfinite=True", "norm pass's partial sums"))
+
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, capturable=False,
                  nonfinite_guard=False, ema_decay=None, ema_targets=None, max_grad_norm=None, skip_nonfinite=False,
                  decoupled_weight_decay=False, device_hyper=False, ema_decay_on_device=False):
-        self._words = None
-        self.device_hyper = False
         if device_hyper and not capturable:
             raise ValueError("HipAdam: device_hyper=True keeps lr and weight decay on the device for a captured step; "
                              "it requires capturable=True")
-        self._ema = None
-        self._ema_omd = None
         if ema_decay_on_device and not capturable:
             raise ValueError("HipAdam: ema_decay_on_device=True keeps the EMA decay on the device for a captured step; "
                              "it requires capturable=True")
         if ema_decay_on_device and ema_decay is None:
             raise ValueError("HipAdam: ema_decay_on_device=True without ema_decay")
-        self._clip_rec = None
         if max_grad_norm is not None and not (0.0 < float(max_grad_norm) < math.inf):      # (NaN fails both comparisons)
             raise ValueError(f"HipAdam: max_grad_norm must be finite and > 0, got {max_grad_norm!r}")
         if ema_decay_on_device:
@@ -150,93 +189,87 @@ class HipAdam(optim.Adam):
             raise ValueError(f"HipAdam: ema_decay must lie in (0, 1), got {ema_decay!r}")
         if ema_decay is None and ema_targets is not None:
             raise ValueError("HipAdam: ema_targets without ema_decay")
+        # (what `add_param_group`, which torch's constructor calls, looks at: nothing is laid out yet)
+        self.device_hyper, self._words, self._ema, self._ema_omd, self._clip_rec = False, None, None, None, None
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad,
                          foreach=False, fused=False, capturable=False, decoupled_weight_decay=decoupled_weight_decay)
+        ps = self._params()
+        device = ps[0].device
         self.device_scalars = bool(capturable)
         self._dev = {}            # group index -> (device step counter float64[1], scalars float32[4])
-        # lr and weight decay on the device: one persistent float64 pair [lr, weight_decay] per group, allocated here and
-        # never replaced -- like `_words`, a captured step reads where the host later writes (`sync_hyper`)
-        self._hyper = {}          # group index -> float64[2] device tensor
-        self._hyper_written = {}  # group index -> (lr, weight_decay) as last written
-        self.device_hyper = bool(device_hyper)
-        if self.device_hyper:
-            for gi in range(len(self.param_groups)):
-                self._hyper_words(gi)
         self._fused = None        # the open registrations of `begin_fused_step`: ([FusedLinearStep], {group index: step})
         self._bound_masks = {}    # frozenset of bound-word indices the backward wrote -> bool mask of the words to zero
         self._captured = []       # per captured step() call: the parameters it stepped (host bookkeeping of a replay)
         self._debt = 0            # replays whose host-side step counts have not been added yet (flushed lazily)
         self.state_generation = 0 # bumped by load_state_dict: captured graphs point at the moment tensors of one generation
         # max |w| of the big Linear weights, emitted by the step itself (VgAdamTensor.amax) for the fp16x3 GEMMs that read
-        # the weight next: one persistent fp32 word per weight (persistent: a replayed step writes where the next replay's
-        # GEMMs read), zeroed in front of every step
-        self._bound_of = {}       # parameter -> index into self._bounds
-        self._bounds = None
+        # the weight next: one persistent fp32 word per weight, zeroed in front of every step (`_weight_bounds`)
+        self._bound_of, self._bounds = {}, None      # parameter -> index into self._bounds
         self.register_state_dict_pre_hook(lambda opt: opt._flush_replays())
-        # non-finite guard: one persistent int32 word per parameter, in param_groups order, allocated here -- before any
-        # capture -- and never replaced (not by load_state_dict either): like `_bounds`, a replayed step writes where the
-        # host later reads
+        # Every feature's device words are allocated here -- before any capture -- and never replaced (not by
+        # load_state_dict either): a replayed step writes where the host later reads, and reads where it later writes.
+        # -- non-finite guard: one int32 flag word per parameter, in param_groups order
         self.nonfinite_guard = bool(nonfinite_guard)
         self._word_of = {}        # parameter -> index into self._words
         self._torch_stepped = False      # torch's step() ran since the words were cleared: it cannot flag (see `nonfinite`)
         if self.nonfinite_guard:
-            ps = [p for g in self.param_groups for p in g["params"]]
             self._word_of = {p: i for i, p in enumerate(ps)}
-            self._words = torch.zeros(len(ps), dtype=torch.int32, device=ps[0].device)
-        # weight EMA: one fp32 tensor per parameter, in param_groups order, fixed here and never replaced -- like
-        # `_words`, a captured step writes where later readers (a trainer's shadow module) read
+            self._words = torch.zeros(len(ps), dtype=torch.int32, device=device)
+        # -- weight EMA: one fp32 tensor per parameter, in param_groups order (a trainer's shadow module reads them); the
+        # decay on the device: one fp32 word holding (float)(1 - decay), which the host writes in `sync_hyper`
         self.ema_decay = None if ema_decay is None else float(ema_decay)
         self._ema_of = {}         # parameter -> index into self._ema
         if self.ema_decay is not None:
-            ps = [p for g in self.param_groups for p in g["params"]]
-            if ema_targets is None:
-                ema = [p.detach().clone(memory_format=torch.contiguous_format) for p in ps]
-            else:
-                ema = [t.detach() if t.requires_grad else t for t in ema_targets]
-                if len(ema) != len(ps):
-                    raise ValueError(f"HipAdam: {len(ema)} ema_targets for {len(ps)} parameters")
-                for i, (t, p) in enumerate(zip(ema, ps)):
-                    if t.shape != p.shape or t.device != p.device or t.dtype != p.dtype or not t.is_contiguous():
-                        raise ValueError(f"HipAdam: ema_targets[{i}] must be a contiguous tensor of its parameter's "
-                                         f"shape, device and dtype ({tuple(p.shape)}, {p.device}, {p.dtype})")
-                    if t.data_ptr() == p.data_ptr() and t.numel():
-                        raise ValueError(f"HipAdam: ema_targets[{i}] is its parameter's own storage")
             self._ema_of = {p: i for i, p in enumerate(ps)}
-            self._ema = ema
-            # the decay on the device: one persistent fp32 word holding (float)(1 - decay), allocated here and never
-            # replaced -- a captured step reads where the host later writes (`sync_hyper`); its prepare kernel is
-            # vg_adam_prepare_dev, so every group's [lr, weight_decay] pair exists from here on too
+            self._ema = self._ema_tensors(ps, ema_targets)
             if ema_decay_on_device:
-                self._ema_omd = torch.zeros(1, dtype=torch.float32, device=ps[0].device)
+                self._ema_omd = torch.zeros(1, dtype=torch.float32, device=device)
                 self._ema_omd_written = None
-                for gi in range(len(self.param_groups)):
-                    self._hyper_words(gi)
-                self.sync_hyper()
-        # clipping by global norm / skipping a non-finite step: the record [norm, coef, skip, skipped] and one fp64 slot
-        # per 8192-element chunk of every parameter, allocated here and never replaced -- like `_words`, a captured step
-        # writes where later readers read
+        # -- clipping by global norm / skipping a non-finite step: the record [norm, coef, skip, skipped] and one fp64
+        # slot per 8192-element chunk of every parameter
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.skip_nonfinite = bool(skip_nonfinite)
         if self.max_grad_norm is not None or self.skip_nonfinite:
-            ps = [p for g in self.param_groups for p in g["params"]]
-            self._clip_rec = torch.zeros(4, dtype=torch.float32, device=ps[0].device)
+            self._clip_rec = torch.zeros(4, dtype=torch.float32, device=device)
             self._clip_rec[1] = 1.0
             slots = sum((p.numel() + _CLIP_CHUNK - 1) // _CLIP_CHUNK for p in ps)
-            self._partials = torch.zeros(max(1, slots), dtype=torch.float64, device=ps[0].device)
+            self._partials = torch.zeros(max(1, slots), dtype=torch.float64, device=device)
+        # -- lr and weight decay on the device: one float64 pair [lr, weight_decay] per group, written in `sync_hyper`.
+        # The step that reads the EMA decay from the device is prepared from them too: they exist and are written here
+        self._hyper = {}          # group index -> float64[2] device tensor
+        self._hyper_written = {}  # group index -> (lr, weight_decay) as last written
+        self.device_hyper = bool(device_hyper)
+        if self.device_hyper or self._ema_omd is not None:
+            for gi in range(len(self.param_groups)):
+                self._hyper_words(gi)
+        if self._ema_omd is not None:
+            self.sync_hyper()
+
+    @staticmethod
+    def _ema_tensors(ps, ema_targets):
+        """The EMA tensors of ``ps``: fp32 clones, or the caller's ``ema_targets`` once they are seen to fit."""
+        if ema_targets is None:
+            return [p.detach().clone(memory_format=torch.contiguous_format) for p in ps]
+        ema = [t.detach() if t.requires_grad else t for t in ema_targets]
+        if len(ema) != len(ps):
+            raise ValueError(f"HipAdam: {len(ema)} ema_targets for {len(ps)} parameters")
+        for i, (t, p) in enumerate(zip(ema, ps)):
+            if t.shape != p.shape or t.device != p.device or t.dtype != p.dtype or not t.is_contiguous():
+                raise ValueError(f"HipAdam: ema_targets[{i}] must be a contiguous tensor of its parameter's "
+                                 f"shape, device and dtype ({tuple(p.shape)}, {p.device}, {p.dtype})")
+            if t.data_ptr() == p.data_ptr() and t.numel():
+                raise ValueError(f"HipAdam: ema_targets[{i}] is its parameter's own storage")
+        return ema
+
+    def _params(self):
+        """Every parameter, in ``param_groups`` order: the order of the flag words, the EMA tensors and `nonfinite`."""
+        return [p for g in self.param_groups for p in g["params"]]
 
     def add_param_group(self, param_group):
-        if self.device_hyper:
-            raise RuntimeError("HipAdam(device_hyper=True): the hyper-parameter words are laid out at construction; "
-                               "pass every parameter group to the constructor")
-        if self._words is not None:
-            raise RuntimeError("HipAdam(nonfinite_guard=True): the flag words are laid out at construction; "
-                               "pass every parameter group to the constructor")
-        if self._ema is not None:
-            raise RuntimeError("HipAdam(ema_decay=...): the EMA tensors are laid out at construction; "
-                               "pass every parameter group to the constructor")
-        if self._clip_rec is not None:
-            raise RuntimeError("HipAdam(max_grad_norm=... / skip_nonfinite=True): the norm pass's partial sums are laid "
-                               "out at construction; pass every parameter group to the constructor")
+        for attr, argument, what in self._LAID_OUT:
+            if getattr(self, attr) is not None and getattr(self, attr) is not False:
+                raise RuntimeError(f"HipAdam({argument}): the {what} are laid out at construction; "
+                                   "pass every parameter group to the constructor")
         return super().add_param_group(param_group)
 
     # ---- lr and weight decay on the device --------------------------------------------------------------------
@@ -299,7 +332,7 @@ class HipAdam(optim.Adam):
     def reset_ema(self):
         """EMA <- the parameters as they are now (after weights were loaded from a checkpoint without an average)."""
         self._need_ema()
-        for e, p in zip(self._ema, (p for g in self.param_groups for p in g["params"])):
+        for e, p in zip(self._ema, self._params()):
             e.copy_(p)
 
     @torch.no_grad()
@@ -401,12 +434,11 @@ class HipAdam(optim.Adam):
         self._need_guard()
         if not self._torch_stepped:
             return self._words
-        return self._words | isfinite_bits([p for g in self.param_groups for p in g["params"]], self._words.device)
+        return self._words | isfinite_bits(self._params(), self._words.device)
 
     def nonfinite(self):
         """One device -> host read: ``{parameter: bits}`` of the words that are up; empty when the run is clean."""
-        ps = [p for g in self.param_groups for p in g["params"]]
-        return {p: b for p, b in zip(ps, self.nonfinite_bits().tolist()) if b}
+        return {p: b for p, b in zip(self._params(), self.nonfinite_bits().tolist()) if b}
 
     def clear_nonfinite(self):
         """Zero the words (a device memset: no synchronisation).  The kernel only ever ORs."""
@@ -514,7 +546,49 @@ class HipAdam(optim.Adam):
             if group.get("amsgrad", False):
                 st["max_exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
 
+    def _ready_state(self, p, group):
+        """``state[p]`` of a parameter about to be stepped: created if missing, ``step`` on the CPU (a checkpoint written
+        by a fused / capturable Adam has it on the device).  Shared by the step and its fused first half; what they do
+        with it differs on purpose -- see `begin_fused_step`."""
+        st = self.state[p]
+        if len(st) == 0:
+            self._init_state(p, group)
+        if st["step"].is_cuda:
+            st["step"] = st["step"].cpu()
+        return st
+
+    def _prepare(self, gi, group, step, capturing, ema_dev=False, prepared=False):
+        """The ONE place a capturable step's scalars are formed, for group ``gi`` at count ``step``: launches what
+        `prepare_entry` names (nothing when the fused half has prepared this step) and returns the scalars.  An eager step
+        also stores its count in the device counter: replays may follow it."""
+        step_dev, scalars = self._device_state(gi, group["params"][0].device)
+        name = prepare_entry(device_hyper=self.device_hyper, decay=float(group["weight_decay"]) != 0.0, ema_dev=ema_dev,
+                             prepared=prepared)
+        if name is None:
+            return scalars
+        if name.endswith("_dev"):
+            hyper = self._hyper_words(gi)
+            if not capturing:
+                self.sync_hyper()      # (words that came into being just now)
+            source = (hyper.data_ptr(), 1 if group.get("decoupled_weight_decay", False) else 0)
+        else:
+            source = (float(group["lr"]),)
+        beta1, beta2 = group["betas"]
+        check(getattr(_lib.load(), name)(float(step), step_dev.data_ptr(), 1 if capturing else 0, *source, float(beta1),
+                                         float(beta2), scalars.data_ptr(), torch.cuda.current_stream().cuda_stream), name)
+        return scalars
+
     # ---- the fused weight-gradient + Adam launch of the big Linear layers -------------------------------------------
+    def _fused_candidates(self, group, only, ema_on, **trainer_side):
+        """The weights of ``group`` that `linear_adam_eligible` admits to the fused launch."""
+        return [p for p in group["params"] if p in self._bound_of and (only is None or id(p) in only)
+                and linear_adam_eligible(
+                    update_ema=ema_on, clip=self._clip_rec is not None, weight_decay=group["weight_decay"],
+                    device_hyper=self.device_hyper, amsgrad=group["amsgrad"], maximize=group.get("maximize", False),
+                    requires_grad=p.requires_grad, dim=p.dim(), numel=p.numel(), in_features=p.shape[-1],
+                    native_tensor=p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.data_ptr() % 16 == 0,
+                    split_ok=bool(ops.linear_split_ok(32, p.numel())), **trainer_side)]
+
     @torch.no_grad()
     def begin_fused_step(self, update_ema=True, switch=True, grad_hook=False, exchange=False, only=None):
         """The first half of a two-part step: registers every big Linear weight that may be updated INSIDE the backward
@@ -537,48 +611,30 @@ class HipAdam(optim.Adam):
             return {}
         if not capturing:
             self._flush_replays()
-        ema_on = self._ema is not None and update_ema
         regs, prepared = [], {}
         for gi, group in enumerate(self.param_groups):
-            mine = []
-            for p in group["params"]:
-                if p not in self._bound_of or (only is not None and id(p) not in only):
-                    continue
-                ok = linear_adam_eligible(
-                    switch=switch, grad_hook=grad_hook, exchange=exchange, update_ema=ema_on,
-                    clip=self._clip_rec is not None, weight_decay=group["weight_decay"], device_hyper=self.device_hyper,
-                    amsgrad=group["amsgrad"], maximize=group.get("maximize", False), requires_grad=p.requires_grad,
-                    dim=p.dim(), numel=p.numel(), in_features=p.shape[-1],
-                    native_tensor=p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.data_ptr() % 16 == 0,
-                    split_ok=bool(ops.linear_split_ok(32, p.numel())))
-                if ok:
-                    mine.append(p)
+            mine = self._fused_candidates(group, only, self._ema is not None and update_ema, switch=switch,
+                                          grad_hook=grad_hook, exchange=exchange)
             if not mine:
                 continue
-            born = [p for p in mine if len(self.state[p]) == 0]
-            born_ids = {id(p) for p in born}
-            for p in born:
-                self._init_state(p, group)
-            for p in mine:
-                if self.state[p]["step"].is_cuda:
-                    self.state[p]["step"] = self.state[p]["step"].cpu()
-            steps = {float(self.state[p]["step"]) + 1.0 for p in mine}
+            # Unlike `step`, this half does not advance the count -- the backward may never reach the weight -- and it
+            # remembers the state it created (``born``) so that it can be forgotten again; state it cannot use (moments
+            # that are not contiguous or not 16-byte aligned) leaves the weight to `step`, which raises where it must.
+            born = {id(p) for p in mine if len(self.state[p]) == 0}
+            steps = {float(self._ready_state(p, group)["step"]) + 1.0 for p in mine}
             if len(steps) > 1:                           # (one prepare per group: they must share its step)
-                for p in born:
-                    del self.state[p]
+                for p in mine:
+                    if id(p) in born:
+                        del self.state[p]
                 continue
             step = steps.pop()
             beta1, beta2 = group["betas"]
             scalars = None
             if self.device_scalars:
-                step_dev, scalars = self._device_state(gi, mine[0].device)
-                check(_lib.load().vg_adam_prepare(float(step), step_dev.data_ptr(), 1 if capturing else 0,
-                                                  float(group["lr"]), float(beta1), float(beta2), scalars.data_ptr(),
-                                                  torch.cuda.current_stream().cuda_stream), "vg_adam_prepare")
+                scalars = self._prepare(gi, group, step, capturing)
                 prepared[gi] = step
             for p in mine:
-                st = self.state[p]
-                m, v = st["exp_avg"], st["exp_avg_sq"]
+                m, v = self.state[p]["exp_avg"], self.state[p]["exp_avg_sq"]
                 if not (m.is_contiguous() and v.is_contiguous() and m.data_ptr() % 16 == 0 and v.data_ptr() % 16 == 0):
                     continue
                 bi = self._bound_of[p]
@@ -587,16 +643,16 @@ class HipAdam(optim.Adam):
                     flag=self._words[self._word_of[p]:self._word_of[p] + 1] if self.nonfinite_guard else None,
                     scalars=scalars, lr=float(group["lr"]), beta1=float(beta1), beta2=float(beta2),
                     eps=float(group["eps"]), bc1=1.0 - beta1 ** step, bc2_sqrt=math.sqrt(1.0 - beta2 ** step), gi=gi,
-                    step=step, born=id(p) in born_ids))
+                    step=step, born=id(p) in born))
         self._fused = (regs, prepared)
         return {id(r.p): r for r in regs}
 
     def _close_fused(self, capturing):
         """The second half: closes the registrations; counts the weights the backward updated (host step count, replay
         bookkeeping) and forgets the state created for one it never reached.  Returns (the updated weights, {group index:
-        the step `begin_fused_step` has prepared the device scalars for})."""
+        the step `begin_fused_step` has prepared the device scalars for}, whether state was created ahead of `step`)."""
         if self._fused is None:
-            return set(), {}
+            return set(), {}, False
         regs, prepared = self._fused
         self._fused = None
         done = set()
@@ -614,8 +670,9 @@ class HipAdam(optim.Adam):
                 del self.state[r.p]
         if capturing:
             self._captured.extend(by_group.values())
-        return done, prepared
+        return done, prepared, any(r.born for r in regs)
 
+    # ---- the step ------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def step(self, closure=None, update_ema=True):
         """``update_ema`` (with ``ema_decay`` set): False steps without touching the averages -- exactly the launches of
@@ -628,185 +685,147 @@ class HipAdam(optim.Adam):
         ``exp_avg``, ``exp_avg_sq`` and the EMA untouched but still ADVANCES the step count, the host's and the device
         counter alike: a count that depends on the data would need a host read inside a captured iteration.  The bias
         corrections of later steps therefore see one more step than updates were made."""
-        born = self._fused is not None and any(r.born for r in self._fused[0])
-        fused_done, fused_prepared = self._close_fused(torch.cuda.is_available()
-                                                       and torch.cuda.is_current_stream_capturing())
-        loss = self._step_rest(closure, update_ema, fused_done, fused_prepared)
+        capturing = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+        fused_done, fused_prepared, born = self._close_fused(capturing)
+        ema_on = self._ema is not None and update_ema
+        if closure is not None or not all(self._native_ok(g) for g in self.param_groups):
+            loss = self._torch_step(closure, ema_on, capturing)
+        else:
+            loss = None
+            lib, stream = _lib.load(), torch.cuda.current_stream().cuda_stream
+            if capturing and not self.device_scalars:
+                raise RuntimeError("HipAdam: construct with capturable=True to capture its step in a HIP graph")
+            if not capturing:
+                self._flush_replays()
+                self.sync_hyper()
+            bounds = self._weight_bounds()
+            if bounds is not None:                           # the words the backward has written already stay
+                self._zero_bounds(bounds, fused_done)
+            rec = self._norm_pass(lib, stream) if self._clip_rec is not None else None
+            for gi, group in enumerate(self.param_groups):
+                by_step = self._collect(group)
+                if capturing and len(set(by_step) | ({fused_prepared[gi]} if gi in fused_prepared else set())) > 1:
+                    raise RuntimeError("HipAdam: a captured step needs every parameter of a group at the same step count")
+                for step, items in by_step.items():
+                    self._launch(lib, stream, gi, group, step, items, ema_on=ema_on, rec=rec, bounds=bounds,
+                                 capturing=capturing, prepared=fused_prepared.get(gi) == step)
+            if bounds is not None:      # (a weight without a gradient was zeroed with the others: measured again; rare)
+                self._publish_bounds(bounds, {p for p in self._bound_of if p in fused_done or p.grad is not None})
         if born:      # `begin_fused_step` created state ahead of the others: back to the order step() alone creates it in
-            for p in [p for g in self.param_groups for p in g["params"] if p in self.state]:
+            for p in [p for p in self._params() if p in self.state]:
                 self.state[p] = self.state.pop(p)
         return loss
 
-    def _step_rest(self, closure, update_ema, fused_done, fused_prepared):
-        """`step` behind the registrations of `begin_fused_step`: everything that still has a gradient."""
-        ema_on = self._ema is not None and update_ema
+    def _torch_step(self, closure, ema_on, capturing):
+        """torch's own step, for what the kernel does not implement -- with this class's features formed by torch around
+        it: the clip / skip record (`_torch_clip`; the closure then runs first, the norm needs its gradients) and the
+        average."""
+        if capturing:
+            raise RuntimeError("HipAdam: this configuration takes torch's step, which cannot be captured here")
+        self._flush_replays()
+        self._torch_stepped = True
         clip_on = self._clip_rec is not None
-        if closure is not None or not all(self._native_ok(g) for g in self.param_groups):
-            if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("HipAdam: this configuration takes torch's step, which cannot be captured here")
-            self._flush_replays()
-            self._torch_stepped = True
-            if clip_on and closure is not None:      # the norm needs this call's gradients: the closure runs here
-                with torch.enable_grad():
-                    loss0 = closure()
-                closure = None
-            else:
-                loss0 = None
-            stepped = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
-            if clip_on:
-                use = self._torch_clip(stepped)
-                if use is None:                      # skipped: only the step counts move
-                    for group in self.param_groups:
-                        for p in group["params"]:
-                            if p.grad is not None:
-                                self._init_state(p, group)
-                                self.state[p]["step"] += 1
-                    return loss0
-                kept = [p.grad for p in stepped]
-                for p, g in zip(stepped, use):
+        loss = None
+        if clip_on and closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        stepped = [p for p in self._params() if p.grad is not None]
+        if not clip_on:
+            loss = super().step(closure)
+        else:
+            use = self._torch_clip(stepped)
+            if use is None:                          # skipped: only the step counts move
+                for group in self.param_groups:
+                    for p in group["params"]:
+                        if p.grad is not None:
+                            self._init_state(p, group)
+                            self.state[p]["step"] += 1
+                return loss
+            kept = [p.grad for p in stepped]
+            for p, g in zip(stepped, use):
+                p.grad = g
+            try:
+                super().step()
+            finally:
+                for p, g in zip(stepped, kept):
                     p.grad = g
-                try:
-                    super().step()
-                finally:
-                    for p, g in zip(stepped, kept):
-                        p.grad = g
-                loss = loss0
-            else:
-                loss = super().step(closure)
-            if ema_on and stepped:      # never silently stale: the same average, formed by torch after its step
-                torch._foreach_lerp_([self._ema[self._ema_of[p]] for p in stepped], [p.detach() for p in stepped],
-                                     1.0 - self.ema_decay)
-            return loss
-        lib = _lib.load()
-        stream = torch.cuda.current_stream().cuda_stream
-        capturing = torch.cuda.is_current_stream_capturing()
-        if capturing and not self.device_scalars:
-            raise RuntimeError("HipAdam: construct with capturable=True to capture its step in a HIP graph")
-        if not capturing:
-            self._flush_replays()
-            self.sync_hyper()
-        bounds = self._weight_bounds()
-        if bounds is not None:
-            if not fused_done:
-                bounds.zero_()
-            else:                                        # the words the backward has written already stay
-                self._zero_bounds_except(bounds, fused_done)
+        if ema_on and stepped:      # never silently stale: the same average, formed by torch after its step
+            torch._foreach_lerp_([self._ema[self._ema_of[p]] for p in stepped], [p.detach() for p in stepped],
+                                 1.0 - self.ema_decay)
+        return loss
+
+    def _norm_pass(self, lib, stream):
+        """The grid-wide answer in front of the first store: the norm of every gradient this call steps on, the
+        coefficient and the skip decision, into the clip record.  Returns the record's address."""
+        grads = [p.grad for p in self._params() if p.grad is not None]
+        n = len(grads)
+        ptrs = (ctypes.c_void_p * max(1, n))(*[g.data_ptr() for g in grads])
+        lens = (ctypes.c_size_t * max(1, n))(*[g.numel() for g in grads])
+        slots = lib.vg_grad_sumsq_partials(lens, n)
+        check(lib.vg_grad_sumsq_multi(ptrs, lens, n, self._partials.data_ptr(), self._partials.numel(), stream),
+              "vg_grad_sumsq_multi")
+        rec = self._clip_rec.data_ptr()
+        check(lib.vg_grad_clip_finalize(self._partials.data_ptr(), slots,
+                                        0.0 if self.max_grad_norm is None else self.max_grad_norm,
+                                        1 if self.skip_nonfinite else 0, rec, stream), "vg_grad_clip_finalize")
+        return rec
+
+    def _collect(self, group):
+        """``{step count: [(p, grad, exp_avg, exp_avg_sq)]}`` of the parameters of ``group`` that have a gradient, their
+        counts advanced: one launch per count."""
+        by_step = {}
+        for p in group["params"]:
+            if p.grad is None:
+                continue
+            st = self._ready_state(p, group)
+            st["step"] += 1
+            m, v = st["exp_avg"], st["exp_avg_sq"]
+            if not (m.is_contiguous() and v.is_contiguous()):
+                raise RuntimeError("HipAdam: optimizer state must be contiguous")
+            by_step.setdefault(float(st["step"]), []).append((p, p.grad, m, v))
+        return by_step
+
+    def _launch(self, lib, stream, gi, group, step, items, *, ema_on, rec, bounds, capturing, prepared):
+        """One multi-tensor launch: the entry point `step_entry` names, on the common prefix (host scalars: ``arr, n, lr,
+        beta1, beta2, eps, bc1, bc2_sqrt``; device scalars, behind `_prepare`: ``arr, n, beta1, beta2, eps, scalars``), the
+        tail that entry point takes, and the stream."""
+        n = len(items)
+        arr = (_AdamTensor * n)()
+        for i, (p, g, m, v) in enumerate(items):
+            bi = self._bound_of.get(p) if bounds is not None else None
+            arr[i] = _AdamTensor(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(),
+                                 None if bi is None else bounds[bi:bi + 1].data_ptr())
         words = self._words.data_ptr() if self.nonfinite_guard else None
-        rec = None
-        if clip_on:                                  # the grid-wide answer in front of the first store
-            grads = [p.grad for g in self.param_groups for p in g["params"] if p.grad is not None]
-            n = len(grads)
-            ptrs = (ctypes.c_void_p * max(1, n))(*[g.data_ptr() for g in grads])
-            lens = (ctypes.c_size_t * max(1, n))(*[g.numel() for g in grads])
-            slots = lib.vg_grad_sumsq_partials(lens, n)
-            check(lib.vg_grad_sumsq_multi(ptrs, lens, n, self._partials.data_ptr(), self._partials.numel(), stream),
-                  "vg_grad_sumsq_multi")
-            rec = self._clip_rec.data_ptr()
-            check(lib.vg_grad_clip_finalize(self._partials.data_ptr(), slots,
-                                            0.0 if self.max_grad_norm is None else self.max_grad_norm,
-                                            1 if self.skip_nonfinite else 0, rec, stream), "vg_grad_clip_finalize")
-        for gi, group in enumerate(self.param_groups):
-            beta1, beta2 = group["betas"]
-            by_step = {}
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                st = self.state[p]
-                if len(st) == 0:
-                    self._init_state(p, group)
-                if st["step"].is_cuda:                             # a checkpoint written by a fused / capturable Adam
-                    st["step"] = st["step"].cpu()
-                st["step"] += 1
-                m, v = st["exp_avg"], st["exp_avg_sq"]
-                if not (m.is_contiguous() and v.is_contiguous()):
-                    raise RuntimeError("HipAdam: optimizer state must be contiguous")
-                by_step.setdefault(float(st["step"]), []).append((p, p.grad, m, v))
-            if capturing and len(set(by_step) | ({fused_prepared[gi]} if gi in fused_prepared else set())) > 1:
-                raise RuntimeError("HipAdam: a captured step needs every parameter of a group at the same step count")
-            for step, items in by_step.items():
-                arr = (_AdamTensor * len(items))()
-                flags = None if words is None else (ctypes.c_void_p * len(items))(
-                    *[words + 4 * self._word_of[it[0]] for it in items])
-                ema = None if not ema_on else (ctypes.c_void_p * len(items))(
-                    *[self._ema[self._ema_of[it[0]]].data_ptr() for it in items])
-                for i, (p, g, m, v) in enumerate(items):
-                    bi = self._bound_of.get(p) if bounds is not None else None
-                    arr[i] = _AdamTensor(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(),
-                                         None if bi is None else bounds[bi:bi + 1].data_ptr())
-                wd = float(group["weight_decay"])
-                decoupled = 1 if group.get("decoupled_weight_decay", False) else 0
-                if self.device_scalars:
-                    step_dev, scalars = self._device_state(gi, items[0][0].device)
-                    # an eager step also stores its count in the device counter: replays may follow it
-                    ema_dev = ema is not None and self._ema_omd is not None
-                    if fused_prepared.get(gi) == step and not (self.device_hyper or wd != 0.0 or ema_dev):
-                        pass                             # `begin_fused_step` ran this step's vg_adam_prepare
-                    elif self.device_hyper or wd != 0.0 or ema_dev:
-                        hyper = self._hyper_words(gi)
-                        if not capturing:
-                            self.sync_hyper()      # (words that came into being just now)
-                        check(lib.vg_adam_prepare_dev(float(step), step_dev.data_ptr(), 1 if capturing else 0,
-                                                      hyper.data_ptr(), decoupled, float(beta1), float(beta2),
-                                                      scalars.data_ptr(), stream), "vg_adam_prepare_dev")
-                    else:
-                        check(lib.vg_adam_prepare(float(step), step_dev.data_ptr(), 1 if capturing else 0,
-                                                  float(group["lr"]), float(beta1), float(beta2), scalars.data_ptr(),
-                                                  stream), "vg_adam_prepare")
-                    if ema_dev:
-                        check(lib.vg_adam_step_dev_ema_dev(arr, len(items), float(beta1), float(beta2),
-                                                           float(group["eps"]), scalars.data_ptr(), flags, ema,
-                                                           self._ema_omd.data_ptr(), rec, stream),
-                              "vg_adam_step_dev_ema_dev")
-                    elif wd != 0.0:
-                        check(lib.vg_adam_step_dev_decay(arr, len(items), float(beta1), float(beta2), float(group["eps"]),
-                                                         scalars.data_ptr(), flags, ema, self.ema_decay or 0.0, rec,
-                                                         stream), "vg_adam_step_dev_decay")
-                    elif rec is not None:
-                        check(lib.vg_adam_step_dev_clip(arr, len(items), float(beta1), float(beta2), float(group["eps"]),
-                                                        scalars.data_ptr(), flags, ema, self.ema_decay or 0.0, rec, stream),
-                              "vg_adam_step_dev_clip")
-                    elif ema is not None:
-                        check(lib.vg_adam_step_dev_ema(arr, len(items), float(beta1), float(beta2), float(group["eps"]),
-                                                       scalars.data_ptr(), flags, ema, self.ema_decay, stream),
-                              "vg_adam_step_dev_ema")
-                    elif flags is not None:
-                        check(lib.vg_adam_step_dev_checked(arr, len(items), float(beta1), float(beta2), float(group["eps"]),
-                                                           scalars.data_ptr(), flags, stream), "vg_adam_step_dev_checked")
-                    else:
-                        check(lib.vg_adam_step_dev(arr, len(items), float(beta1), float(beta2), float(group["eps"]),
-                                                   scalars.data_ptr(), stream), "vg_adam_step_dev")
-                    if capturing:
-                        self._captured.append([it[0] for it in items])
-                    continue
-                bc1 = 1.0 - beta1 ** step
-                bc2_sqrt = math.sqrt(1.0 - beta2 ** step)
-                if wd != 0.0:
-                    check(lib.vg_adam_step_decay(arr, len(items), float(group["lr"]), float(beta1), float(beta2),
-                                                 float(group["eps"]), bc1, bc2_sqrt, flags, ema, self.ema_decay or 0.0, rec,
-                                                 wd, decoupled, stream), "vg_adam_step_decay")
-                elif rec is not None:
-                    check(lib.vg_adam_step_clip(arr, len(items), float(group["lr"]), float(beta1), float(beta2),
-                                                float(group["eps"]), bc1, bc2_sqrt, flags, ema, self.ema_decay or 0.0, rec,
-                                                stream), "vg_adam_step_clip")
-                elif ema is not None:
-                    check(lib.vg_adam_step_ema(arr, len(items), float(group["lr"]), float(beta1), float(beta2),
-                                               float(group["eps"]), bc1, bc2_sqrt, flags, ema, self.ema_decay, stream),
-                          "vg_adam_step_ema")
-                elif flags is not None:
-                    check(lib.vg_adam_step_checked(arr, len(items), float(group["lr"]), float(beta1), float(beta2),
-                                                   float(group["eps"]), bc1, bc2_sqrt, flags, stream), "vg_adam_step_checked")
-                else:
-                    check(lib.vg_adam_step(arr, len(items), float(group["lr"]), float(beta1), float(beta2),
-                                           float(group["eps"]), bc1, bc2_sqrt, stream), "vg_adam_step")
-        if bounds is not None:
-            for p, bi in self._bound_of.items():
-                slot = bounds[bi:bi + 1]
-                if p in fused_done:     # stepped inside the backward: the fused launch wrote its word
-                    pass
-                elif p.grad is None:    # not stepped: its word was zeroed with the others -- measured again (rare: a frozen layer)
-                    check(lib.vg_absmax(p.data_ptr(), p.numel(), slot.data_ptr(), stream), "vg_absmax")
-                ops.set_weight_bound(p, slot)
-        return None
+        ema_dev = ema_on and self._ema_omd is not None
+        have = {
+            "flags": None if words is None else (ctypes.c_void_p * n)(*[words + 4 * self._word_of[it[0]] for it in items]),
+            "ema": None if not ema_on else (ctypes.c_void_p * n)(*[self._ema[self._ema_of[it[0]]].data_ptr()
+                                                                   for it in items]),
+            "ema_decay": self.ema_decay or 0.0,      # (0.0 where the entry takes a decay and nothing is averaged)
+            "omd": self._ema_omd.data_ptr() if ema_dev else None, "rec": rec, "wd": float(group["weight_decay"]),
+            "decoupled": 1 if group.get("decoupled_weight_decay", False) else 0}
+        name, tail = step_entry(dev=self.device_scalars, flags=words is not None, ema=ema_on, ema_dev=ema_dev,
+                                decay=have["wd"] != 0.0, clip=rec is not None)
+        beta1, beta2 = group["betas"]
+        if self.device_scalars:
+            scalars = self._prepare(gi, group, step, capturing, ema_dev=ema_dev, prepared=prepared)
+            prefix = (arr, n, float(beta1), float(beta2), float(group["eps"]), scalars.data_ptr())
+        else:
+            prefix = (arr, n, float(group["lr"]), float(beta1), float(beta2), float(group["eps"]), 1.0 - beta1 ** step,
+                      math.sqrt(1.0 - beta2 ** step))
+        check(getattr(lib, name)(*prefix, *[have[k] for k in tail], stream), name)
+        if capturing:
+            self._captured.append([it[0] for it in items])
+
+    def _publish_bounds(self, bounds, written=()):
+        """Hand the bound words to the GEMMs that read the weights next (`ops.set_weight_bound`), measuring (``vg_absmax``
+        into the zeroed word) every weight that is not among ``written``: those whose word a step has just emitted."""
+        lib, stream = _lib.load(), torch.cuda.current_stream().cuda_stream
+        for p, bi in self._bound_of.items():
+            slot = bounds[bi:bi + 1]
+            if p not in written:
+                check(lib.vg_absmax(p.data_ptr(), p.numel(), slot.data_ptr(), stream), "vg_absmax")
+            ops.set_weight_bound(p, slot)
 
     @torch.no_grad()
     def refresh_weight_bounds(self):
@@ -814,18 +833,16 @@ class HipAdam(optim.Adam):
         something other than `step` -- a checkpoint copied in place under a captured iteration, whose GEMMs read these
         words)."""
         bounds = self._weight_bounds()
-        if bounds is None:
-            return
-        bounds.zero_()
-        lib, stream = _lib.load(), torch.cuda.current_stream().cuda_stream
-        for p, bi in self._bound_of.items():
-            slot = bounds[bi:bi + 1]
-            check(lib.vg_absmax(p.data_ptr(), p.numel(), slot.data_ptr(), stream), "vg_absmax")
-            ops.set_weight_bound(p, slot)
+        if bounds is not None:
+            bounds.zero_()
+            self._publish_bounds(bounds)
 
-    def _zero_bounds_except(self, bounds, keep):
+
+    def _zero_bounds(self, bounds, keep):
         """Zero the bound words of every weight but those in ``keep`` (one fill-by-mask launch; the mask is built once
         per set, from device fills alone, so that a capture may build it too)."""
+        if not keep:
+            return bounds.zero_()
         key = frozenset(self._bound_of[p] for p in keep)
         if len(key) == bounds.numel():
             return
@@ -840,8 +857,7 @@ class HipAdam(optim.Adam):
     def _weight_bounds(self):
         """The bounds tensor (one word per Linear weight the fp16x3 GEMM takes), or None when there is none."""
         if self._bounds is None:
-            big = [p for g in self.param_groups for p in g["params"]
-                   if p.dim() == 2 and p.is_cuda and p.numel() >= ops.LINEAR_SPLIT_MIN_WEIGHTS]
+            big = [p for p in self._params() if p.dim() == 2 and p.is_cuda and p.numel() >= ops.LINEAR_SPLIT_MIN_WEIGHTS]
             if not big:
                 return None
             self._bound_of = {p: i for i, p in enumerate(big)}

@@ -582,6 +582,35 @@ class ReparamTCFn(Function):
         return gmu, glv, None, None, None, None, None
 
 
+class ReparamDIPFn(Function):
+    """z = mu + eps*exp(logvar/2) and the DIP-VAE objective (Kumar et al. 2018):
+    ``loss = beta*kl + B*(lambda_od*od + lambda_d*dg)`` with ``od`` / ``dg`` the off-diagonal / diagonal distance of the
+    aggregate posterior's covariance from the identity, in three launches forward and one backward.  Returns ``z``,
+    ``loss`` and the non-differentiable ``[3]`` tensor ``(kl, od, dg)``.  ``beta``: a float or the device word, as
+    `ReparamKLFn`; ``variant``: ``"i"`` (the covariance of the means) or ``"ii"`` (of z)."""
+
+    @staticmethod
+    def forward(ctx, mu, logvar, eps, beta, lambda_od, lambda_d, variant):
+        z, out4, cov, mean = ops.reparam_dip_fwd(mu, logvar, eps, beta, lambda_od, lambda_d, variant)
+        ctx.beta, ctx.lambdas, ctx.variant = beta, (lambda_od, lambda_d), variant      # (a tensor is kept as the word itself)
+        loss, parts = out4[0], out4[1:]
+        ctx.mark_non_differentiable(parts)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(mu, logvar, eps, cov, mean)
+        return z, loss, parts
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gz, gloss, _):
+        if gz is None and gloss is None:
+            return None, None, None, None, None, None, None
+        mu, logvar, eps, cov, mean = ctx.saved_tensors
+        gz = gz.contiguous() if gz is not None else None
+        gloss = gloss.contiguous() if gloss is not None else None
+        gmu, glv = ops.reparam_dip_bwd(gz, mu, logvar, eps, cov, mean, gloss, ctx.beta, *ctx.lambdas, ctx.variant)
+        return gmu, glv, None, None, None, None, None
+
+
 class KLRowsFn(Function):
     """Encoder_celeba's per-sample KL (model.py:321) together with z."""
 
@@ -748,6 +777,12 @@ def reparam_tc(mu, logvar, eps, beta, alpha=1.0, gamma=1.0, dataset_size=None):
         raise ValueError(f"reparam_tc: dataset_size must be the number of training samples (>= 1), got {dataset_size!r}")
     log_bn = math.log(float(mu.shape[0]) * float(dataset_size))
     return ReparamTCFn.apply(mu, logvar, eps, _beta_arg(beta), float(alpha), float(gamma), log_bn)
+
+
+def reparam_dip(mu, logvar, eps, beta, lambda_od, lambda_d, variant="i"):
+    """`ReparamDIPFn`: ``(z, loss, parts)`` with ``loss = beta*kl + B*(lambda_od*od + lambda_d*dg)`` and ``parts = (kl, od,
+    dg)``; ``variant``: ``"i"`` or ``"ii"``."""
+    return ReparamDIPFn.apply(mu, logvar, eps, _beta_arg(beta), float(lambda_od), float(lambda_d), ops.dip_variant(variant))
 
 
 def kld_loss(mu, logvar, beta):

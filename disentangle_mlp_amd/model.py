@@ -566,3 +566,13 @@ class VAE(nn.Module, _DecoderMixin):
             eps = torch.randn_like(mu)
         z, loss, parts = F.reparam_tc(mu, logvar, eps, beta, alpha, gamma, dataset_size)
         return self.decode(z), mu, logvar, loss, parts
+
+    def forward_with_dip(self, x, eps, beta, variant, lambda_od, lambda_d):
+        """`forward_with_kl` with the DIP-VAE covariance penalty added (functional.reparam_dip): returns ``recon, mu,
+        logvar, loss, parts`` -- ``loss = beta*kl + B*(lambda_od*od + lambda_d*dg)``, ``parts`` the ``[3]`` tensor ``(kl,
+        od, dg)``."""
+        mu, logvar = self.encode(x)
+        if eps is None:
+            eps = torch.randn_like(mu)
+        z, loss, parts = F.reparam_dip(mu, logvar, eps, beta, lambda_od, lambda_d, variant)
+        return self.decode(z), mu, logvar, loss, parts

@@ -1125,6 +1125,67 @@ def reparam_tc_bwd(gz, mu, logvar, eps, z, lse_joint, lse_dim, gloss, beta, alph
     return gmu, glv
 
 
+DIP_VARIANTS = {"i": 1, "ii": 2}      # the C ABI's `variant`: Cov_p[mu(x)] / Cov_q[z]
+
+
+def dip_variant(variant):
+    """``"i"`` / ``"ii"`` (or the C ABI's 1 / 2) -> 1 / 2."""
+    v = DIP_VARIANTS.get(variant, variant)
+    if isinstance(v, bool) or v not in (1, 2):
+        raise ValueError(f"DIP-VAE variant must be 'i' or 'ii', got {variant!r}")
+    return int(v)
+
+
+def reparam_dip_fwd(mu, logvar, eps, beta, lambda_od, lambda_d, variant):
+    """Reparameterisation + the DIP-VAE objective (vg_reparam_dip_fwd).  ``beta`` (the KL weight):
+    a float or the device word, as `reparam_kl_fwd`; ``lambda_od`` / ``lambda_d``: the weights of the off-diagonal and the
+    diagonal penalty; ``variant``: ``"i"`` or ``"ii"``.  Returns ``z``, ``out4`` = [loss, kl, od, dg] and what the backward
+    reads (``cov`` [D, D], ``mean`` [D] fp64)."""
+    lib = _lib.load()
+    _req(mu, "mu"), _req(logvar, "logvar"), _req(eps, "eps")
+    if mu.dim() != 2 or logvar.shape != mu.shape or eps.shape != mu.shape:
+        raise RuntimeError("reparam_dip: mu, logvar and eps must be [B, D] tensors of one shape")
+    variant = dip_variant(variant)
+    B, D = mu.shape
+    z = torch.empty_like(mu)
+    out4 = torch.empty(4, dtype=torch.float32, device=mu.device)
+    cov = torch.empty(D, D, dtype=torch.float32, device=mu.device)
+    mean = torch.empty(D, dtype=torch.float64, device=mu.device)
+    ws = workspace(lib.vg_reparam_dip_workspace_bytes(B, D), mu.device)
+    head = (mu.data_ptr(), logvar.data_ptr(), eps.data_ptr(), z.data_ptr(), out4.data_ptr(), cov.data_ptr(), mean.data_ptr(),
+            B, D, variant)
+    tail = (float(lambda_od), float(lambda_d), ws.data_ptr(), ws.numel(), _stream())
+    if isinstance(beta, torch.Tensor):
+        check(lib.vg_reparam_dip_fwd_dev(*head, _beta_word(beta).data_ptr(), *tail), "vg_reparam_dip_fwd_dev")
+    else:
+        check(lib.vg_reparam_dip_fwd(*head, float(beta), *tail), "vg_reparam_dip_fwd")
+    return z, out4, cov, mean
+
+
+def reparam_dip_bwd(gz, mu, logvar, eps, cov, mean, gloss, beta, lambda_od, lambda_d, variant):
+    """gz: tensor or None; gloss: 0-dim device tensor (upstream gradient of the weighted loss) or None."""
+    lib = _lib.load()
+    for t, name in ((mu, "mu"), (logvar, "logvar"), (eps, "eps"), (cov, "cov")):
+        _req(t, name)
+    if gz is not None:
+        _req(gz, "gz")
+    if gloss is not None:
+        _req(gloss, "gloss")
+    B, D = mu.shape
+    if not mean.is_cuda or mean.dtype != torch.float64 or not mean.is_contiguous() or mean.numel() != D or cov.shape != (D, D):
+        raise RuntimeError("reparam_dip_bwd: cov and mean must be the [D, D] fp32 and [D] float64 tensors of reparam_dip_fwd")
+    variant = dip_variant(variant)
+    gmu, glv = torch.empty_like(mu), torch.empty_like(mu)
+    ws = workspace(lib.vg_reparam_dip_workspace_bytes(B, D), mu.device)
+    head = (_ptr(gz), mu.data_ptr(), logvar.data_ptr(), eps.data_ptr(), cov.data_ptr(), mean.data_ptr(), _ptr(gloss), variant)
+    tail = (float(lambda_od), float(lambda_d), gmu.data_ptr(), glv.data_ptr(), B, D, ws.data_ptr(), ws.numel(), _stream())
+    if isinstance(beta, torch.Tensor):
+        check(lib.vg_reparam_dip_bwd_dev(*head, _beta_word(beta).data_ptr(), *tail), "vg_reparam_dip_bwd_dev")
+    else:
+        check(lib.vg_reparam_dip_bwd(*head, float(beta), *tail), "vg_reparam_dip_bwd")
+    return gmu, glv
+
+
 def sqdiff_loss(a, b, scale, gscale=1.0, want_grad=True):
     lib = _lib.load()
     _req(a, "a"), _req(b, "b")

@@ -490,7 +490,7 @@ class _GraphedSteps:
 
     def _setup(self, device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
                beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition, dataset_size,
-               data_parallel=None, capturable=None):
+               data_parallel=None, capturable=None, dip_vae=None):
         """The constructor body of every trainer (new_betavaegan.py:36-53, new_vae.py:33-37, new_gan.py:47-61).  A trainer
         with a KL term has set `beta` before."""
         has_beta = hasattr(self, "beta")
@@ -500,6 +500,7 @@ class _GraphedSteps:
         on_gpu = self.device.type == "cuda"
         _use_tuned_gemms(self.device)
         self._tc_args(tc_decomposition, dataset_size, has_beta)
+        self._dip_args(dip_vae, has_beta)
         self.max_grad_norm, self.skip_nonfinite = max_grad_norm, bool(skip_nonfinite)
         self._skipped = {}
         self.world, self.rank = _dist_world(), _dist_rank()
@@ -753,18 +754,45 @@ class _GraphedSteps:
         if self.tc_decomposition is not None and self.dataset_size is None:
             self.dataset_size = int(len(loader.dataset))
 
+    # ---- the KL term plus the DIP-VAE covariance penalty ----------------------------------------------------------------
+    dip_vae = None            # (variant, lambda_od, lambda_d): "i" | "ii", the weights of the off-diagonal / diagonal penalty
+
+    def _dip_args(self, dip_vae, has_beta=True):
+        """Validate ``dip_vae=(variant, lambda_od, lambda_d)`` of a trainer's constructor."""
+        if dip_vae is None:
+            return
+        if not has_beta:
+            raise TypeError(f"{type(self).__name__} has no KL term: dip_vae does not apply")
+        if self.tc_decomposition is not None:
+            raise ValueError("dip_vae and tc_decomposition each replace the KL term of the encoder phase: pass one of them")
+        try:
+            variant, lambda_od, lambda_d = dip_vae
+            lambda_od, lambda_d = float(lambda_od), float(lambda_d)
+        except (TypeError, ValueError):
+            raise TypeError(f"dip_vae must be a triple (variant, lambda_od, lambda_d), got {dip_vae!r}") from None
+        if variant not in ("i", "ii"):
+            raise ValueError(f"dip_vae: variant must be 'i' or 'ii', got {variant!r}")
+        if not (np.isfinite(lambda_od) and np.isfinite(lambda_d) and lambda_od >= 0.0 and lambda_d >= 0.0):
+            raise ValueError(f"dip_vae: lambda_od and lambda_d must be finite and >= 0, got {dip_vae!r}")
+        self.dip_vae = (variant, lambda_od, lambda_d)
+
     def _forward_kl(self, net, data, eps):
         """The encoder-side forward of the KL phase: ``recon, mu, logvar, kld, parts`` -- the analytic KL (``parts`` is
-        None), or with ``tc_decomposition`` the decomposed one, whose total-correlation weight is `beta`."""
+        None), or with ``tc_decomposition`` the decomposed one, whose total-correlation weight is `beta`, or with
+        ``dip_vae`` the KL, weighted by `beta`, plus the covariance penalty."""
+        if self.dip_vae is not None:
+            return net.forward_with_dip(data, eps, self._kl_beta(), *self.dip_vae)
         if self.tc_decomposition is None:
             return (*net.forward_with_kl(data, eps, self._kl_beta()), None)
         alpha, gamma = self.tc_decomposition
         return net.forward_with_tc(data, eps, self._kl_beta(), alpha, gamma, self.dataset_size)
 
-    @staticmethod
-    def _tc_outputs(parts):
-        """The additional loss keys -- present only with ``tc_decomposition``."""
-        return {} if parts is None else dict(mi=parts[0], tc=parts[1], dwkl=parts[2])
+    def _kl_part_outputs(self, parts):
+        """The additional loss keys -- present only with ``tc_decomposition`` or ``dip_vae``."""
+        if parts is None:
+            return {}
+        names = ("kl", "dip_od", "dip_d") if self.dip_vae is not None else ("mi", "tc", "dwkl")
+        return {name: parts[n] for n, name in enumerate(names)}
 
     def _kl_beta(self):
         """What the KL kernels take: the device word with ``device_hyper`` (eager and captured alike), else the float."""
@@ -951,6 +979,7 @@ class _GraphedSteps:
                 self.max_grad_norm, self.skip_nonfinite,      # (the norm pass and the clip step, or neither)
                 self.device_hyper,           # (lr, weight decay and beta read from device words, or frozen arguments)
                 self.tc_decomposition and (*self.tc_decomposition, self.dataset_size),      # (frozen kernel arguments)
+                self.dip_vae,                # (the same: variant and both lambdas)
                 tuple(net.training for net in self._nets()),
                 tuple(p.requires_grad for net in self._nets() for p in net.parameters()))
 
@@ -1124,7 +1153,18 @@ class BetaVAEGANTrainer(_GraphedSteps):
     summed over the batch) are added to it.  ``dataset_size``: the N of the estimator, the number of training samples;
     `fit` / `train_epoch` take it from ``len(loader.dataset)`` when it was not given, `step` without one raises
     ValueError.  The option adds no checkpoint state.  Data parallel: every rank estimates the three parts from its LOCAL
-    batch -- the pair terms never cross ranks -- so the estimator is replica-local, as the BatchNorm statistics are."""
+    batch -- the pair terms never cross ranks -- so the estimator is replica-local, as the BatchNorm statistics are.
+
+    ``dip_vae=(variant, lambda_od, lambda_d)`` (default: none, with the same guarantee): phase 3 keeps the KL term,
+    weighted by `beta`, and adds the DIP-VAE penalty on the covariance ``C`` of the aggregate posterior (Kumar et al.
+    2018): ``beta * kl + B * (lambda_od * sum_{i != j} C_ij^2 + lambda_d * sum_i (C_ii - 1)^2)``,
+    ``variant`` ``"i"`` with the covariance of the means, ``"ii"`` with the mean posterior variance added to its diagonal
+    (`VAE.forward_with_dip`; three launches forward, one backward).  The lambdas are finite and >= 0, frozen kernel
+    arguments; ``beta_schedule``, `set_beta` and ``device_hyper`` apply unchanged and an annealed beta still replays ONE
+    graph.  ``kld`` of the returned dict is the weighted loss that was backpropagated; ``kl``, ``dip_od``, ``dip_d`` are
+    added to it.  No checkpoint state; together with ``tc_decomposition`` it is a ValueError.  Data parallel: every rank
+    forms the means and the covariance from its LOCAL batch -- replica-local, as the BatchNorm statistics and the
+    total-correlation estimate are."""
 
     _parts = (_Part("netEG", VAE, "optimizerEG", "flat_eg", "eg", "encoder_decoder_optimizer"),              # :41, :49
               _Part("netD", Discriminator_celeba, "optimizerD", "flat_d", "d", "discriminator_optimizer"))    # :43, :50
@@ -1138,11 +1178,11 @@ class BetaVAEGANTrainer(_GraphedSteps):
                  max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False,
                  lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0, decoupled_weight_decay: bool = False,
                  device_hyper: Optional[bool] = None, ema_decay=None, tc_decomposition=None,
-                 dataset_size: Optional[int] = None):
+                 dataset_size: Optional[int] = None, dip_vae=None):
         self.beta = float(beta)
         self._setup(device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
                     beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition,
-                    dataset_size, data_parallel, capturable)      # (lr: hard-coded 1e-3 at new_betavaegan.py:49-50)
+                    dataset_size, data_parallel, capturable, dip_vae)      # (lr: hard-coded 1e-3 at new_betavaegan.py:49-50)
         self._eg_params = [p for p in self.netEG.parameters() if p.dim() == 4]   # convolution filters
         self._d_params = [p for p in self.netD.parameters() if p.dim() == 4]
 
@@ -1221,7 +1261,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
             grad_hook("EG3", netEG)
         self.optimizerEG.step()
         ops.invalidate_packed_filters(self._eg_params)
-        out.update(kld=kld.detach(), mse_enc=mse3.detach(), **self._tc_outputs(parts))
+        out.update(kld=kld.detach(), mse_enc=mse3.detach(), **self._kl_part_outputs(parts))
         self.iteration += 1
         return out
 
@@ -1441,7 +1481,8 @@ class VAETrainer(_GraphedSteps):
     schedule arguments (``lr_scheduler``, ``beta_schedule``, ``weight_decay``, ``decoupled_weight_decay``,
     ``device_hyper``): as BetaVAEGANTrainer.  ``ema_decay``: as there, of the one network -- `ema_model` shadows `model`,
     the checkpoint key is ``VAE_model_ema``.  ``tc_decomposition`` / ``dataset_size``: as there, of the step's KL term
-    (`train_epoch` fills a ``dataset_size`` that was not given); replica-local under data parallelism."""
+    (`train_epoch` fills a ``dataset_size`` that was not given); replica-local under data parallelism.  ``dip_vae``: as
+    there -- the covariance is that of this replica's batch."""
 
     _parts = (_Part("model", VAE, "optimizer", "flat", "vae", "optimizer"),)
     _latents = ("eps",)
@@ -1452,11 +1493,11 @@ class VAETrainer(_GraphedSteps):
                  nonfinite_guard: Optional[bool] = None, max_grad_norm: Optional[float] = None,
                  skip_nonfinite: bool = False, lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0,
                  decoupled_weight_decay: bool = False, device_hyper: Optional[bool] = None, ema_decay=None,
-                 tc_decomposition=None, dataset_size: Optional[int] = None):
+                 tc_decomposition=None, dataset_size: Optional[int] = None, dip_vae=None):
         self.beta = float(beta)
         self._setup(device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
                     beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition,
-                    dataset_size, capturable=capturable)
+                    dataset_size, capturable=capturable, dip_vae=dip_vae)
 
     def step(self, data, eps=None, grad_hook=None):
         """``grad_hook(phase, net)`` (tests): called with ``("VAE", model)`` right before the optimizer step; such an
@@ -1475,7 +1516,7 @@ class VAETrainer(_GraphedSteps):
             grad_hook("VAE", self.model)
         self.optimizer.step()
         self.iteration += 1
-        return dict(mse=mse.detach(), kld=kld.detach(), **self._tc_outputs(parts))
+        return dict(mse=mse.detach(), kld=kld.detach(), **self._kl_part_outputs(parts))
 
     def train_epoch(self, loader, max_iterations=None):
         """``train(epoch)`` of new_vae.py:48-68: returns ``avg_loss`` = sum over the epoch of
@@ -1504,8 +1545,8 @@ class GANTrainer(_GraphedSteps):
     reference wraps both nets in nn.DataParallel, new_gan.py:51-53): replica-local BatchNorm, one
     gradient exchange (SUM) per optimizer step, BCE divided by the global batch.  ``graph``: as
     BetaVAEGANTrainer; so are ``max_grad_norm``, ``skip_nonfinite`` and the schedule arguments (``lr_scheduler``,
-    ``weight_decay``, ``decoupled_weight_decay``, ``device_hyper``; there is no KL term, so a ``beta_schedule`` or a
-    ``tc_decomposition`` is a TypeError).  ``ema_decay``: as BetaVAEGANTrainer, of the generator -- `ema_model` shadows `netG`, the checkpoint key is
+    ``weight_decay``, ``decoupled_weight_decay``, ``device_hyper``; there is no KL term, so a ``beta_schedule``, a
+    ``tc_decomposition`` or a ``dip_vae`` is a TypeError).  ``ema_decay``: as BetaVAEGANTrainer, of the generator -- `ema_model` shadows `netG`, the checkpoint key is
     ``netG_ema``; the discriminator is not averaged."""
 
     _parts = (_Part("netG", Generator_celeba, "optimizerG", "flat_g", "g", "G_trainer"),
@@ -1519,10 +1560,10 @@ class GANTrainer(_GraphedSteps):
                  nonfinite_guard: Optional[bool] = None, max_grad_norm: Optional[float] = None,
                  skip_nonfinite: bool = False, lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0,
                  decoupled_weight_decay: bool = False, device_hyper: Optional[bool] = None, ema_decay=None,
-                 tc_decomposition=None, dataset_size: Optional[int] = None):
+                 tc_decomposition=None, dataset_size: Optional[int] = None, dip_vae=None):
         self._setup(device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
                     beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition,
-                    dataset_size, data_parallel)
+                    dataset_size, data_parallel, dip_vae=dip_vae)
 
     def step(self, data, noise=None, real_label=0.9, fake_label=0.1, global_batch: Optional[int] = None,
              grad_hook=None):

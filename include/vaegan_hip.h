@@ -49,7 +49,8 @@ extern "C" {
  * vg_adam_step_ema, vg_adam_step_dev_ema; vg_grad_sumsq_partials, vg_grad_sumsq_multi, vg_grad_clip_finalize,
  * vg_adam_step_clip, vg_adam_step_dev_clip; vg_adam_prepare_dev, vg_adam_step_decay, vg_adam_step_dev_decay,
  * vg_reparam_kl_fwd_dev, vg_reparam_kl_bwd_dev; vg_adam_step_dev_ema_dev; the five vg_reparam_tc_* of
- * csrc/reparam_tc.hip; vg_linear_wgrad_adam, vg_linear_wgrad_adam_dev) change
+ * csrc/reparam_tc.hip; vg_linear_wgrad_adam, vg_linear_wgrad_adam_dev; the five vg_reparam_dip_* of
+ * csrc/reparam_dip.hip) change
  * nothing an existing caller sees and keep the version: a binding that needs them and finds a library without them
  * fails at the symbol lookup, as loudly. */
 #define VG_ABI_VERSION 7
@@ -452,6 +453,42 @@ int vg_reparam_tc_bwd_dev(const float* gz, const float* mu, const float* logvar,
                           const double* lse_joint, const float* lse_dim, const float* gloss, float alpha,
                           const float* beta_dev, float gamma, float* gmu, float* glogvar, int B, int D, void* workspace,
                           size_t workspace_bytes, void* stream);
+
+/* ---- reparameterisation + the DIP-VAE objectives (Kumar et al. 2018, variants I and II; DESIGN.md section 4.21;
+ * csrc/reparam_dip.hip).  With z = mu + eps*exp(logvar/2) and, for b < B, i, j, d < D,
+ *   kl   = -0.5*sum_{b,d}(1 + logvar - mu^2 - exp(logvar))
+ *   m[d] = (1/B)*sum_b mu[b,d]        c[b,d] = mu[b,d] - m[d]
+ *   C    = (1/B)*sum_b c_b c_b^T                                   variant 1  (Cov_p[mu(x)])
+ *   C    = that + diag((1/B)*sum_b exp(logvar[b,:]))               variant 2  (Cov_q[z])
+ *   od   = sum_{i != j} C_ij^2        dg = sum_i (C_ii - 1)^2
+ * the forward writes z and out4 = {loss, kl, od, dg}, loss = beta*kl + B*(lambda_od*od + lambda_d*dg) (batch sums: loss / B
+ * is the paper's objective with the paper's lambdas), and what the backward reads: cov ([D,D] fp32: C, symmetric to the
+ * bit) and mean ([D] fp64: m).  Three launches: column statistics (fp64), one workgroup per 32 x 32 tile of C on or above
+ * the diagonal (centred columns in LDS, fp32 FMA chains of 64 rows in a fixed order, their sums added in fp64), one
+ * wavefront that sums the partials in a fixed order.  With G_ij = 2*lambda_od*C_ij (i != j), G_ii = 2*lambda_d*(C_ii - 1)
+ * the backward writes
+ *   gmu     = gloss*(beta*mu + 2*(c_b . G)) + gz
+ *   glogvar = gloss*(beta*0.5*(exp(logvar) - 1) + [variant 2: G_dd*exp(logvar)]) + gz*eps*0.5*exp(logvar/2)
+ * in one launch; gz (tensor) and gloss (DEVICE scalar, upstream of out4[0]) may each be NULL: that term is absent (gloss
+ * == NULL is one elementwise launch).  No floating-point atomics: the same inputs give the same bits.  1 <= B, D <= 1024;
+ * variant is 1 or 2.  `workspace`: vg_reparam_dip_workspace_bytes(B, D) bytes, 8-byte aligned (the forward's content is
+ * not needed by the backward). */
+size_t vg_reparam_dip_workspace_bytes(int B, int D);
+int vg_reparam_dip_fwd(const float* mu, const float* logvar, const float* eps, float* z, float* out4, float* cov,
+                       double* mean, int B, int D, int variant, float beta, float lambda_od, float lambda_d,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int vg_reparam_dip_bwd(const float* gz, const float* mu, const float* logvar, const float* eps, const float* cov,
+                       const double* mean, const float* gloss, int variant, float beta, float lambda_od, float lambda_d,
+                       float* gmu, float* glogvar, int B, int D, void* workspace, size_t workspace_bytes, void* stream);
+/* beta read from DEVICE memory (beta_dev[0], fp32), as vg_reparam_kl_fwd_dev: the same fp32 beta gives the same bits.
+ * beta_dev == NULL is VG_ERR_BAD_ARG. */
+int vg_reparam_dip_fwd_dev(const float* mu, const float* logvar, const float* eps, float* z, float* out4, float* cov,
+                           double* mean, int B, int D, int variant, const float* beta_dev, float lambda_od,
+                           float lambda_d, void* workspace, size_t workspace_bytes, void* stream);
+int vg_reparam_dip_bwd_dev(const float* gz, const float* mu, const float* logvar, const float* eps, const float* cov,
+                           const double* mean, const float* gloss, int variant, const float* beta_dev, float lambda_od,
+                           float lambda_d, float* gmu, float* glogvar, int B, int D, void* workspace,
+                           size_t workspace_bytes, void* stream);
 
 /* out[i] = g[i] * s[0] with s a DEVICE scalar: applies the upstream gradient of a
  * loss scalar to a gradient precomputed by the fused loss kernels, without a

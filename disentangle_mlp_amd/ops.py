@@ -1101,6 +1101,38 @@ def reparam_tc_fwd(mu, logvar, eps, beta, alpha, gamma, log_bn):
     return z, out4, lse_joint, lse_dim
 
 
+AGG_POINT_TILE = 64      # VG_AGG_POINT_TILE: evaluation points per wavefront of vg_agg_posterior_lse
+AGG_WORKGROUP_WAVES = 4  # wavefronts (point tiles) per workgroup of its two main kernels
+AGG_ROW_TILE = 8         # VG_AGG_ROW_TILE: rows per row tile, the unit of its splits
+
+
+def agg_posterior_splits(M, N, D, splits=None):
+    """The number of row ranges `agg_posterior_lse` runs for these sizes: the launcher's choice for ``None``, else the
+    request clamped to the number of row tiles (ceil(N / AGG_ROW_TILE)) with ranges left empty by the rounding dropped."""
+    return int(_lib.load().vg_agg_posterior_splits(int(M), int(N), int(D), 0 if splits is None else int(splits)))
+
+
+def agg_posterior_lse(z, mu, logvar, splits=None):
+    """log sum_j N(z_m; mu_j, exp(logvar_j)), unnormalised (the caller subtracts log N), for M evaluation points under N
+    diagonal Gaussians (vg_agg_posterior_lse): ``lse_joint`` [M] fp64 over whole vectors and
+    ``lse_dim`` [M, D] fp32 per dimension.  ``z``: [M, D]; ``mu``, ``logvar``: [N, D].  ``splits``: the number of row
+    ranges (tests), ``None`` = chosen from the sizes alone.  Forward only."""
+    lib = _lib.load()
+    _req(z, "z"), _req(mu, "mu"), _req(logvar, "logvar")
+    if z.dim() != 2 or mu.dim() != 2 or logvar.shape != mu.shape or z.shape[1] != mu.shape[1]:
+        raise RuntimeError("agg_posterior_lse: z must be [M, D], mu and logvar [N, D]")
+    (M, D), N = z.shape, mu.shape[0]
+    splits = 0 if splits is None else int(splits)      # (0, as in the C ABI, is None)
+    if splits < 0:
+        raise RuntimeError("agg_posterior_lse: splits must not be negative")
+    lse_joint = torch.empty(M, dtype=torch.float64, device=z.device)
+    lse_dim = torch.empty(M, D, dtype=torch.float32, device=z.device)
+    ws = workspace(lib.vg_agg_posterior_workspace_bytes(M, N, D, splits), z.device)
+    check(lib.vg_agg_posterior_lse(z.data_ptr(), mu.data_ptr(), logvar.data_ptr(), lse_joint.data_ptr(), lse_dim.data_ptr(),
+                                   M, N, D, splits, ws.data_ptr(), ws.numel(), _stream()), "vg_agg_posterior_lse")
+    return lse_joint, lse_dim
+
+
 def reparam_tc_bwd(gz, mu, logvar, eps, z, lse_joint, lse_dim, gloss, beta, alpha, gamma):
     """gz: tensor or None; gloss: 0-dim device tensor (upstream gradient of the weighted loss) or None."""
     lib = _lib.load()

@@ -903,6 +903,22 @@ class _GraphedSteps:
         self._ema_pair()
         return self.ema_model
 
+    def latent_report(self, loader, n_eval=None, eval_mode=False, use_ema=False, factors=None, generator=None):
+        """Whether the encoder disentangled anything (metrics.py): encodes every image of
+        ``loader`` and returns `metrics.elbo_decomposition` of the posteriors -- ``mi``, ``tc``, ``dwkl``, ``kl``,
+        ``h_joint``, ``h_dim``, ``kl_dim``, ``active_units`` -- plus the keys of `metrics.mig` when ``factors`` ([N] or
+        [N, K] integers, in the loader's order) is given or the loader's labels take more than one value.  ``n_eval``:
+        evaluation points of the decomposition (default: every row).  ``eval_mode`` / ``use_ema``: as in `evaluate`."""
+        from . import metrics
+        net = self._sampling_net(use_ema)
+        mu, logvar, labels = metrics.encode_dataset(net, loader, eval_mode=eval_mode)
+        report = metrics.elbo_decomposition(mu, logvar, n_eval=n_eval, generator=generator)
+        if factors is None and labels is not None and not labels.is_floating_point() and bool((labels != labels[0]).any()):
+            factors = labels
+        if factors is not None:
+            report.update(metrics.mig(mu, logvar, factors, generator=generator))
+        return report
+
     @torch.no_grad()
     def reset_ema(self):
         """Shadow <- the live network as it is now: weights and BatchNorm buffers, copied into the existing tensors."""
@@ -1369,7 +1385,8 @@ class BetaVAEGANTrainer(_GraphedSteps):
     def evaluate(self, load_paths, test_loader=None, start_epoch=0, calc_fid=False, n_samples=1000, fid_path_samples=None,
                  fid_path_pretrained=None, get_fid=None, test_recons=False, test_results_path_recons=None,
                  test_results_path_originals="", test_samples=False, test_results_path_samples=None,
-                 fid_on_device=False, fid_inception="", fid_feature_extractor=None, eval_mode=False, use_ema=False):
+                 fid_on_device=False, fid_inception="", fid_feature_extractor=None, eval_mode=False, use_ema=False,
+                 latent_report=None):
         """The evaluation half (new_betavaegan.py:248-267): for every checkpoint of ``load_paths`` -- load it, renumber
         its epoch the way the reference does so that files of several checkpoints do not overwrite each other (:252-254),
         then FID samples + score (:256-259), one grid of test reconstructions with ``nrow=1`` (+ the originals, :260-263)
@@ -1381,7 +1398,9 @@ class BetaVAEGANTrainer(_GraphedSteps):
         ``fid_feature_extractor``: as in `fit` -- the FID straight from the decoder, no sample files.  ``use_ema=True`` (a
         trainer with ``ema_decay``): everything above samples and reconstructs through `ema_model` -- loaded from the
         checkpoint's ``encoder_decoder_ema``, or equal to the live network when the checkpoint has none -- and
-        ``eval_mode`` then applies to it (see `recalibrate_ema_bn`)."""
+        ``eval_mode`` then applies to it (see `recalibrate_ema_bn`).  ``latent_report=loader`` (opt-in): each
+        checkpoint's dict also carries, under ``latent``, `latent_report` of that loader (same ``eval_mode`` / ``use_ema``);
+        without it no launch, key or file differs."""
         from . import image_io
         out, tmp_epoch = [], 0
         net = self._sampling_net(use_ema)
@@ -1409,6 +1428,8 @@ class BetaVAEGANTrainer(_GraphedSteps):
                 if test_samples:
                     image_io.generate_samples(net.decode, start_epoch, 5, self.opt.n_hidden,
                                               test_results_path_samples, nrow=1, device=self.device)
+            if latent_report is not None:
+                res["latent"] = self.latent_report(latent_report, eval_mode=eval_mode, use_ema=use_ema)
             out.append(res)
         return out
 

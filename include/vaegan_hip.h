@@ -50,7 +50,7 @@ extern "C" {
  * vg_adam_step_clip, vg_adam_step_dev_clip; vg_adam_prepare_dev, vg_adam_step_decay, vg_adam_step_dev_decay,
  * vg_reparam_kl_fwd_dev, vg_reparam_kl_bwd_dev; vg_adam_step_dev_ema_dev; the five vg_reparam_tc_* of
  * csrc/reparam_tc.hip; vg_linear_wgrad_adam, vg_linear_wgrad_adam_dev; the five vg_reparam_dip_* of
- * csrc/reparam_dip.hip) change
+ * csrc/reparam_dip.hip; the three vg_agg_posterior_* of csrc/agg_posterior.hip) change
  * nothing an existing caller sees and keep the version: a binding that needs them and finds a library without them
  * fails at the symbol lookup, as loudly. */
 #define VG_ABI_VERSION 7
@@ -489,6 +489,30 @@ int vg_reparam_dip_bwd_dev(const float* gz, const float* mu, const float* logvar
                            const double* mean, const float* gloss, int variant, const float* beta_dev, float lambda_od,
                            float lambda_d, float* gmu, float* glogvar, int B, int D, void* workspace,
                            size_t workspace_bytes, void* stream);
+
+/* ---- log-density under the aggregate posterior, at evaluation scale (the ELBO decomposition over a dataset and MIG:
+ * Chen et al. 2018, section 4 and appendix C; csrc/agg_posterior.hip).  Forward only.  With
+ *   lq[m,j,d] = log N(z[m,d]; mu[j,d], exp(logvar[j,d]))      m < M evaluation points, j < N posteriors, d < D
+ * it writes the two UNNORMALISED log-sum-exps (the caller subtracts log N)
+ *   lse_joint[m] = LSE_j sum_d lq[m,j,d]   (fp64, [M])        lse_dim[m,d] = LSE_j lq[m,j,d]   (fp32, [M,D])
+ * A lane owns an evaluation point, a wavefront VG_AGG_POINT_TILE of them (four wavefronts to a workgroup); the rows stream
+ * past as wavefront-uniform values, their constants sqrt(exp(-logvar)/2) and -(log 2 pi + logvar)/2 formed once per row
+ * by a prepare pass.  The row sum over d is accumulated in fp64; both log-sum-exps keep a running maximum (no fixed
+ * shift: a point far from every posterior gives a finite, correct value).  N is cut into `splits` ranges of whole row
+ * tiles (VG_AGG_ROW_TILE rows) whose partial (max, sum) pairs a last kernel merges in split order: no atomics, the same
+ * inputs and `splits` give the same bits.  splits == 0: chosen from (M, N, D) alone, separately for the joint kernel (many
+ * short ranges: its partials are 16 bytes a point) and the per-dimension kernel.  A `splits` above the number of row
+ * tiles (or above 1024) is CLAMPED, and ranges left empty by the rounding are dropped; vg_agg_posterior_splits returns
+ * the count that runs (with splits == 0: the per-dimension kernel's; 0 for rejected sizes).  Six launches.
+ * 1 <= D <= 1024, 1 <= N <= 2^24, 1 <= M with M * D < 2^38, splits >= 0: otherwise VG_ERR_BAD_ARG.  `workspace`:
+ * vg_agg_posterior_workspace_bytes(M, N, D, splits) bytes (the same `splits` as the call), 256-byte aligned; a shorter
+ * one is VG_ERR_WORKSPACE. */
+#define VG_AGG_POINT_TILE 64
+#define VG_AGG_ROW_TILE 8
+int vg_agg_posterior_splits(int M, int N, int D, int splits);
+size_t vg_agg_posterior_workspace_bytes(int M, int N, int D, int splits);
+int vg_agg_posterior_lse(const float* z, const float* mu, const float* logvar, double* lse_joint, float* lse_dim, int M,
+                         int N, int D, int splits, void* workspace, size_t workspace_bytes, void* stream);
 
 /* out[i] = g[i] * s[0] with s a DEVICE scalar: applies the upstream gradient of a
  * loss scalar to a gradient precomputed by the fused loss kernels, without a

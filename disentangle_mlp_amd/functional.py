@@ -611,6 +611,35 @@ class ReparamDIPFn(Function):
         return gmu, glv, None, None, None, None, None
 
 
+class ReparamMMDFn(Function):
+    """z = mu + eps*exp(logvar/2) and the InfoVAE / WAE-MMD objective (Zhao et al. 2019, Tolstikhin et al. 2018; DESIGN.md
+    section 4.23): ``loss = beta*kl + B*lambda_mmd*mmd`` with ``mmd`` the unbiased maximum mean discrepancy between the
+    batch of z and the prior draws ``zp``, in three launches forward and one backward.  Returns ``z``, ``loss`` and the
+    non-differentiable ``[3]`` tensor ``(kl, mmd, kzz)``.  ``beta``: a float or the device word, as `ReparamKLFn`; ``kind``:
+    1 (rbf) or 2 (imq); ``bandwidths``: a tuple of floats.  ``zp`` takes no gradient."""
+
+    @staticmethod
+    def forward(ctx, mu, logvar, eps, zp, beta, lambda_mmd, kind, bandwidths):
+        z, out4, w = ops.reparam_mmd_fwd(mu, logvar, eps, zp, beta, lambda_mmd, kind, bandwidths)
+        ctx.beta, ctx.lambda_mmd, ctx.kernel = beta, lambda_mmd, (kind, bandwidths)      # (a tensor is kept as the word itself)
+        loss, parts = out4[0], out4[1:]
+        ctx.mark_non_differentiable(parts)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(mu, logvar, eps, z, zp, w)
+        return z, loss, parts
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gz, gloss, _):
+        if gz is None and gloss is None:
+            return None, None, None, None, None, None, None, None
+        mu, logvar, eps, z, zp, w = ctx.saved_tensors
+        gz = gz.contiguous() if gz is not None else None
+        gloss = gloss.contiguous() if gloss is not None else None
+        gmu, glv = ops.reparam_mmd_bwd(gz, mu, logvar, eps, z, zp, w, gloss, ctx.beta, ctx.lambda_mmd, *ctx.kernel)
+        return gmu, glv, None, None, None, None, None, None
+
+
 class KLRowsFn(Function):
     """Encoder_celeba's per-sample KL (model.py:321) together with z."""
 
@@ -783,6 +812,15 @@ def reparam_dip(mu, logvar, eps, beta, lambda_od, lambda_d, variant="i"):
     """`ReparamDIPFn`: ``(z, loss, parts)`` with ``loss = beta*kl + B*(lambda_od*od + lambda_d*dg)`` and ``parts = (kl, od,
     dg)``; ``variant``: ``"i"`` or ``"ii"``."""
     return ReparamDIPFn.apply(mu, logvar, eps, _beta_arg(beta), float(lambda_od), float(lambda_d), ops.dip_variant(variant))
+
+
+def reparam_mmd(mu, logvar, eps, zp, beta, lambda_mmd, kernel="imq", bandwidths=None):
+    """`ReparamMMDFn`: ``(z, loss, parts)`` with ``loss = beta*kl + B*lambda_mmd*mmd`` and ``parts = (kl, mmd, kzz)``;
+    ``zp``: draws from the prior, one per sample; ``kernel``: ``"rbf"`` or ``"imq"``; ``bandwidths``: ``None`` for WAE's
+    defaults (`ops.mmd_bandwidths`) or 1 to 8 positive numbers."""
+    kind = ops.mmd_kernel(kernel)
+    return ReparamMMDFn.apply(mu, logvar, eps, zp, _beta_arg(beta), float(lambda_mmd), kind,
+                              ops.mmd_bandwidths(kind, mu.shape[-1], bandwidths))
 
 
 def kld_loss(mu, logvar, beta):

@@ -576,3 +576,15 @@ class VAE(nn.Module, _DecoderMixin):
             eps = torch.randn_like(mu)
         z, loss, parts = F.reparam_dip(mu, logvar, eps, beta, lambda_od, lambda_d, variant)
         return self.decode(z), mu, logvar, loss, parts
+
+    def forward_with_mmd(self, x, eps, prior, beta, kernel, lambda_mmd, bandwidths=None):
+        """`forward_with_kl` with the InfoVAE / WAE-MMD penalty added (functional.reparam_mmd): returns ``recon, mu,
+        logvar, loss, parts`` -- ``loss = beta*kl + B*lambda_mmd*mmd``, ``parts`` the ``[3]`` tensor ``(kl, mmd, kzz)``.
+        ``prior``: draws from N(0, I) of the shape of ``mu``; like ``eps``, ``None`` is drawn here."""
+        mu, logvar = self.encode(x)
+        if eps is None:
+            eps = torch.randn_like(mu)
+        if prior is None:
+            prior = torch.randn_like(mu)
+        z, loss, parts = F.reparam_mmd(mu, logvar, eps, prior, beta, lambda_mmd, kernel, bandwidths)
+        return self.decode(z), mu, logvar, loss, parts

@@ -5,6 +5,7 @@ arithmetic op below runs in libvaegan_hip.so.  Inputs must be CUDA (ROCm) fp32
 tensors -- there is deliberately no CPU path.
 """
 import ctypes
+import math
 import os
 import weakref
 from typing import NamedTuple
@@ -1215,6 +1216,92 @@ def reparam_dip_bwd(gz, mu, logvar, eps, cov, mean, gloss, beta, lambda_od, lamb
         check(lib.vg_reparam_dip_bwd_dev(*head, _beta_word(beta).data_ptr(), *tail), "vg_reparam_dip_bwd_dev")
     else:
         check(lib.vg_reparam_dip_bwd(*head, float(beta), *tail), "vg_reparam_dip_bwd")
+    return gmu, glv
+
+
+MMD_KERNELS = {"rbf": 1, "imq": 2}      # the C ABI's `kind`: sum_s exp(-d/h_s) / sum_s h_s/(h_s + d)
+MMD_MAX_BANDWIDTHS = 8
+MMD_IMQ_SCALES = (0.1, 0.2, 0.5, 1.0, 2.0, 5.0, 10.0)      # WAE's set, times 2 D sigma_p^2
+
+
+def mmd_kernel(kernel):
+    """``"rbf"`` / ``"imq"`` (or the C ABI's 1 / 2) -> 1 / 2."""
+    k = MMD_KERNELS.get(kernel, kernel) if isinstance(kernel, (str, int)) else None
+    if isinstance(k, bool) or k not in (1, 2):
+        raise ValueError(f"MMD kernel must be 'rbf' or 'imq', got {kernel!r}")
+    return int(k)
+
+
+def mmd_bandwidths(kind, D, bandwidths=None):
+    """The bandwidths of the kernel sum as a tuple of floats.  ``None``: WAE's convention with sigma_p^2 = 1 --
+    ``(2 D,)`` for rbf, ``2 D (0.1, 0.2, 0.5, 1, 2, 5, 10)`` for imq.  Otherwise 1 to 8 finite positive numbers."""
+    if bandwidths is None:
+        return (2.0 * D,) if mmd_kernel(kind) == 1 else tuple(2.0 * D * s for s in MMD_IMQ_SCALES)
+    try:
+        hs = tuple(float(h) for h in bandwidths)
+    except TypeError:
+        raise ValueError(f"MMD bandwidths must be a sequence of numbers, got {bandwidths!r}") from None
+    if not 1 <= len(hs) <= MMD_MAX_BANDWIDTHS or not all(math.isfinite(h) and h > 0.0 for h in hs):
+        raise ValueError(f"MMD bandwidths must be 1 to {MMD_MAX_BANDWIDTHS} finite positive numbers, got {bandwidths!r}")
+    return hs
+
+
+def _mmd_host_bandwidths(kind, D, bandwidths):
+    hs = mmd_bandwidths(kind, D, bandwidths)
+    return (ctypes.c_float * len(hs))(*hs), len(hs)
+
+
+def reparam_mmd_fwd(mu, logvar, eps, zp, beta, lambda_mmd, kind, bandwidths=None):
+    """Reparameterisation + the InfoVAE / WAE-MMD objective (vg_reparam_mmd_fwd).  ``zp``: [B, D]
+    draws from the prior; ``beta`` (the KL weight): a float or the device word, as `reparam_kl_fwd`; ``lambda_mmd``: the
+    weight of the MMD; ``kind``: ``"rbf"`` or ``"imq"``; ``bandwidths``: as `mmd_bandwidths`.  Returns ``z``, ``out4`` =
+    [loss, kl, mmd, kzz] and what the backward reads (``w`` [2, B, B])."""
+    lib = _lib.load()
+    _req(mu, "mu"), _req(logvar, "logvar"), _req(eps, "eps"), _req(zp, "zp")
+    if mu.dim() != 2 or logvar.shape != mu.shape or eps.shape != mu.shape or zp.shape != mu.shape:
+        raise RuntimeError("reparam_mmd: mu, logvar, eps and zp must be [B, D] tensors of one shape")
+    kind = mmd_kernel(kind)
+    B, D = mu.shape
+    if B < 2:
+        raise RuntimeError("reparam_mmd: the unbiased MMD needs a batch of at least 2")
+    hs, n = _mmd_host_bandwidths(kind, D, bandwidths)
+    z = torch.empty_like(mu)
+    out4 = torch.empty(4, dtype=torch.float32, device=mu.device)
+    w = torch.empty(2, B, B, dtype=torch.float32, device=mu.device)
+    ws = workspace(lib.vg_reparam_mmd_workspace_bytes(B, D), mu.device)
+    head = (mu.data_ptr(), logvar.data_ptr(), eps.data_ptr(), zp.data_ptr(), z.data_ptr(), out4.data_ptr(), w.data_ptr(),
+            B, D, kind)
+    tail = (float(lambda_mmd), ctypes.addressof(hs), n, ws.data_ptr(), ws.numel(), _stream())
+    if isinstance(beta, torch.Tensor):
+        check(lib.vg_reparam_mmd_fwd_dev(*head, _beta_word(beta).data_ptr(), *tail), "vg_reparam_mmd_fwd_dev")
+    else:
+        check(lib.vg_reparam_mmd_fwd(*head, float(beta), *tail), "vg_reparam_mmd_fwd")
+    return z, out4, w
+
+
+def reparam_mmd_bwd(gz, mu, logvar, eps, z, zp, w, gloss, beta, lambda_mmd, kind=None, bandwidths=None):
+    """gz: tensor or None; gloss: 0-dim device tensor (upstream gradient of the weighted loss) or None.  The kernel and its
+    bandwidths are already in ``w``: ``kind`` / ``bandwidths`` are accepted for symmetry with the forward and only checked."""
+    lib = _lib.load()
+    for t, name in ((mu, "mu"), (logvar, "logvar"), (eps, "eps"), (z, "z"), (zp, "zp"), (w, "w")):
+        _req(t, name)
+    if gz is not None:
+        _req(gz, "gz")
+    if gloss is not None:
+        _req(gloss, "gloss")
+    B, D = mu.shape
+    if w.shape != (2, B, B) or z.shape != mu.shape or zp.shape != mu.shape:
+        raise RuntimeError("reparam_mmd_bwd: z, zp and w must be the [B, D], [B, D] and [2, B, B] tensors of reparam_mmd_fwd")
+    if kind is not None:
+        mmd_bandwidths(mmd_kernel(kind), D, bandwidths)
+    gmu, glv = torch.empty_like(mu), torch.empty_like(mu)
+    ws = workspace(lib.vg_reparam_mmd_workspace_bytes(B, D), mu.device)
+    head = (_ptr(gz), mu.data_ptr(), logvar.data_ptr(), eps.data_ptr(), z.data_ptr(), zp.data_ptr(), w.data_ptr(), _ptr(gloss))
+    tail = (float(lambda_mmd), gmu.data_ptr(), glv.data_ptr(), B, D, ws.data_ptr(), ws.numel(), _stream())
+    if isinstance(beta, torch.Tensor):
+        check(lib.vg_reparam_mmd_bwd_dev(*head, _beta_word(beta).data_ptr(), *tail), "vg_reparam_mmd_bwd_dev")
+    else:
+        check(lib.vg_reparam_mmd_bwd(*head, float(beta), *tail), "vg_reparam_mmd_bwd")
     return gmu, glv
 
 

@@ -490,7 +490,7 @@ class _GraphedSteps:
 
     def _setup(self, device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
                beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition, dataset_size,
-               data_parallel=None, capturable=None, dip_vae=None):
+               data_parallel=None, capturable=None, dip_vae=None, mmd_vae=None):
         """The constructor body of every trainer (new_betavaegan.py:36-53, new_vae.py:33-37, new_gan.py:47-61).  A trainer
         with a KL term has set `beta` before."""
         has_beta = hasattr(self, "beta")
@@ -501,6 +501,7 @@ class _GraphedSteps:
         _use_tuned_gemms(self.device)
         self._tc_args(tc_decomposition, dataset_size, has_beta)
         self._dip_args(dip_vae, has_beta)
+        self._mmd_args(mmd_vae, has_beta)
         self.max_grad_norm, self.skip_nonfinite = max_grad_norm, bool(skip_nonfinite)
         self._skipped = {}
         self.world, self.rank = _dist_world(), _dist_rank()
@@ -776,10 +777,45 @@ class _GraphedSteps:
             raise ValueError(f"dip_vae: lambda_od and lambda_d must be finite and >= 0, got {dip_vae!r}")
         self.dip_vae = (variant, lambda_od, lambda_d)
 
-    def _forward_kl(self, net, data, eps):
+    # ---- the KL term plus the InfoVAE / WAE-MMD penalty ------------------------------------------------------------------
+    mmd_vae = None            # (kernel, lambda_mmd, bandwidths): "rbf" | "imq", the MMD's weight, a tuple of floats or None
+
+    def _mmd_args(self, mmd_vae, has_beta=True):
+        """Validate ``mmd_vae=(kernel, lambda_mmd[, bandwidths])`` of a trainer's constructor.  With the option the
+        iteration takes one more latent, the prior's draw, last in draw order."""
+        if mmd_vae is None:
+            return
+        if not has_beta:
+            raise TypeError(f"{type(self).__name__} has no KL term: mmd_vae does not apply")
+        if self.tc_decomposition is not None or self.dip_vae is not None:
+            raise ValueError("mmd_vae, dip_vae and tc_decomposition each replace the KL term of the encoder phase: pass one "
+                             "of them")
+        try:
+            kernel, lambda_mmd, *rest = mmd_vae
+            lambda_mmd = float(lambda_mmd)
+            bandwidths, = rest or (None,)
+        except (TypeError, ValueError):
+            raise TypeError(f"mmd_vae must be (kernel, lambda_mmd) or (kernel, lambda_mmd, bandwidths), got {mmd_vae!r}") from None
+        if kernel not in ("rbf", "imq"):
+            raise ValueError(f"mmd_vae: kernel must be 'rbf' or 'imq', got {kernel!r}")
+        if not (np.isfinite(lambda_mmd) and lambda_mmd >= 0.0):
+            raise ValueError(f"mmd_vae: lambda_mmd must be finite and >= 0, got {mmd_vae!r}")
+        if bandwidths is not None:
+            try:
+                bandwidths = ops.mmd_bandwidths(kernel, self.opt.n_hidden, bandwidths)
+            except ValueError as e:
+                raise ValueError(f"mmd_vae: {e}") from None
+        self.mmd_vae = (kernel, lambda_mmd, bandwidths)
+        self._latents = (*type(self)._latents, "prior")
+
+    def _forward_kl(self, net, data, eps, prior=None):
         """The encoder-side forward of the KL phase: ``recon, mu, logvar, kld, parts`` -- the analytic KL (``parts`` is
         None), or with ``tc_decomposition`` the decomposed one, whose total-correlation weight is `beta`, or with
-        ``dip_vae`` the KL, weighted by `beta`, plus the covariance penalty."""
+        ``dip_vae`` the KL, weighted by `beta`, plus the covariance penalty, or with ``mmd_vae`` that KL plus the MMD
+        between the batch of z and ``prior``."""
+        if self.mmd_vae is not None:
+            kernel, lambda_mmd, bandwidths = self.mmd_vae
+            return net.forward_with_mmd(data, eps, prior, self._kl_beta(), kernel, lambda_mmd, bandwidths)
         if self.dip_vae is not None:
             return net.forward_with_dip(data, eps, self._kl_beta(), *self.dip_vae)
         if self.tc_decomposition is None:
@@ -787,11 +823,20 @@ class _GraphedSteps:
         alpha, gamma = self.tc_decomposition
         return net.forward_with_tc(data, eps, self._kl_beta(), alpha, gamma, self.dataset_size)
 
+    def _with_prior(self, given, prior):
+        """`step`'s latents in `_latents` order: with ``mmd_vae`` the prior's draw (or None: drawn) comes last."""
+        if self.mmd_vae is None:
+            if prior is not None:
+                raise TypeError(f"{type(self).__name__}.step: prior= belongs to mmd_vae, which is off")
+            return given
+        return (*given, prior)
+
     def _kl_part_outputs(self, parts):
-        """The additional loss keys -- present only with ``tc_decomposition`` or ``dip_vae``."""
+        """The additional loss keys -- present only with ``tc_decomposition``, ``dip_vae`` or ``mmd_vae``."""
         if parts is None:
             return {}
-        names = ("kl", "dip_od", "dip_d") if self.dip_vae is not None else ("mi", "tc", "dwkl")
+        names = (("kl", "mmd", "mmd_kzz") if self.mmd_vae is not None
+                 else ("kl", "dip_od", "dip_d") if self.dip_vae is not None else ("mi", "tc", "dwkl"))
         return {name: parts[n] for n, name in enumerate(names)}
 
     def _kl_beta(self):
@@ -996,6 +1041,7 @@ class _GraphedSteps:
                 self.device_hyper,           # (lr, weight decay and beta read from device words, or frozen arguments)
                 self.tc_decomposition and (*self.tc_decomposition, self.dataset_size),      # (frozen kernel arguments)
                 self.dip_vae,                # (the same: variant and both lambdas)
+                self.mmd_vae,                # (the same: kernel, lambda and the bandwidths)
                 tuple(net.training for net in self._nets()),
                 tuple(p.requires_grad for net in self._nets() for p in net.parameters()))
 
@@ -1180,7 +1226,19 @@ class BetaVAEGANTrainer(_GraphedSteps):
     graph.  ``kld`` of the returned dict is the weighted loss that was backpropagated; ``kl``, ``dip_od``, ``dip_d`` are
     added to it.  No checkpoint state; together with ``tc_decomposition`` it is a ValueError.  Data parallel: every rank
     forms the means and the covariance from its LOCAL batch -- replica-local, as the BatchNorm statistics and the
-    total-correlation estimate are."""
+    total-correlation estimate are.
+
+    ``mmd_vae=(kernel, lambda_mmd)`` or ``(kernel, lambda_mmd, bandwidths)`` (default: none, with the same guarantee):
+    phase 3 keeps the KL term, weighted by `beta`, and adds the unbiased maximum mean discrepancy between the batch of z
+    and as many draws from the prior (InfoVAE, Zhao et al. 2019; WAE-MMD, Tolstikhin et al. 2018; DESIGN.md section
+    4.23): ``beta * kl + B * lambda_mmd * mmd`` under a sum of ``"rbf"`` or ``"imq"`` kernels (`VAE.forward_with_mmd`;
+    three launches forward, one backward).  ``bandwidths``: 1 to 8 finite positive numbers, default WAE's (``2 D`` for
+    rbf, ``2 D (0.1 ... 10)`` for imq).  ``lambda_mmd`` is finite and >= 0; it and the kernel are frozen kernel arguments,
+    while ``beta_schedule``, `set_beta` and ``device_hyper`` apply unchanged, an annealed beta still replays ONE graph,
+    and ``beta = 0`` (a WAE) is allowed.  The iteration takes one more latent, ``prior``, drawn after ``eps3`` (`step`
+    accepts ``prior=``).  ``kld`` of the returned dict is the weighted loss that was backpropagated; ``kl``, ``mmd``,
+    ``mmd_kzz`` are added to it.  No checkpoint state; together with ``tc_decomposition`` or ``dip_vae`` it is a
+    ValueError.  Data parallel: replica-local, as those are."""
 
     _parts = (_Part("netEG", VAE, "optimizerEG", "flat_eg", "eg", "encoder_decoder_optimizer"),              # :41, :49
               _Part("netD", Discriminator_celeba, "optimizerD", "flat_d", "d", "discriminator_optimizer"))    # :43, :50
@@ -1194,27 +1252,28 @@ class BetaVAEGANTrainer(_GraphedSteps):
                  max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False,
                  lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0, decoupled_weight_decay: bool = False,
                  device_hyper: Optional[bool] = None, ema_decay=None, tc_decomposition=None,
-                 dataset_size: Optional[int] = None, dip_vae=None):
+                 dataset_size: Optional[int] = None, dip_vae=None, mmd_vae=None):
         self.beta = float(beta)
         self._setup(device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
                     beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition,
-                    dataset_size, data_parallel, capturable, dip_vae)      # (lr: hard-coded 1e-3 at new_betavaegan.py:49-50)
+                    dataset_size, data_parallel, capturable, dip_vae, mmd_vae)      # (lr: hard-coded 1e-3 at new_betavaegan.py:49-50)
         self._eg_params = [p for p in self.netEG.parameters() if p.dim() == 4]   # convolution filters
         self._d_params = [p for p in self.netD.parameters() if p.dim() == 4]
 
     # -- one iteration ------------------------------------------------------------
     def step(self, data, noise=None, eps2=None, eps3=None, real_label=0.9, fake_label=0.1,
-             global_batch: Optional[int] = None, grad_hook=None) -> Dict[str, torch.Tensor]:
+             global_batch: Optional[int] = None, grad_hook=None, prior=None) -> Dict[str, torch.Tensor]:
         """One iteration; returns the nine loss scalars as device tensors (no host sync).  From the third iteration of a
         batch shape on the iteration is a HIP-graph replay and the returned tensors are the capture's STATIC outputs: the
-        next replay overwrites them -- ``.clone()`` (or ``float()``) what is kept across steps."""
-        return self._drive(data, (noise, eps2, eps3), real_label, fake_label, global_batch, grad_hook)
+        next replay overwrites them -- ``.clone()`` (or ``float()``) what is kept across steps.
+        ``prior`` (with ``mmd_vae`` only): phase 3's draws from the prior, (B, n_hidden); None is drawn, after ``eps3``."""
+        return self._drive(data, self._with_prior((noise, eps2, eps3), prior), real_label, fake_label, global_batch, grad_hook)
 
     def _iteration(self, data, latents, labels, grad_hook, prepack, acc):
         """data (B,3,64,64) in [-1,1]; noise / eps2 / eps3 (B, n_hidden) ~ N(0,1) (new_betavaegan.py:111, model.py:534);
         the labels are the per-iteration scalars of :89-90."""
         netEG, netD = self.netEG, self.netD
-        noise, eps2, eps3 = latents
+        noise, eps2, eps3, *prior = latents                  # (prior: one more draw with ``mmd_vae``, else nothing)
         real_label, fake_label, gb = labels
         prepack()
         out = {}
@@ -1269,7 +1328,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
 
         # ---- phase 3: "encoder" -- again every EG parameter moves (:167-193)
         self._zero(netEG, self.flat_eg, self.optimizerEG, grad_hook)
-        recon, mu, logvar, kld, parts = self._forward_kl(netEG, data, eps3)
+        recon, mu, logvar, kld, parts = self._forward_kl(netEG, data, eps3, *prior)
         mse3 = F.reconstruction_loss(recon, data)
         _backward([kld, mse3])
         self._exchange(self.flat_eg)
@@ -1503,7 +1562,7 @@ class VAETrainer(_GraphedSteps):
     ``device_hyper``): as BetaVAEGANTrainer.  ``ema_decay``: as there, of the one network -- `ema_model` shadows `model`,
     the checkpoint key is ``VAE_model_ema``.  ``tc_decomposition`` / ``dataset_size``: as there, of the step's KL term
     (`train_epoch` fills a ``dataset_size`` that was not given); replica-local under data parallelism.  ``dip_vae``: as
-    there -- the covariance is that of this replica's batch."""
+    there -- the covariance is that of this replica's batch.  ``mmd_vae``: as there -- ``prior`` is drawn after ``eps``."""
 
     _parts = (_Part("model", VAE, "optimizer", "flat", "vae", "optimizer"),)
     _latents = ("eps",)
@@ -1514,22 +1573,23 @@ class VAETrainer(_GraphedSteps):
                  nonfinite_guard: Optional[bool] = None, max_grad_norm: Optional[float] = None,
                  skip_nonfinite: bool = False, lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0,
                  decoupled_weight_decay: bool = False, device_hyper: Optional[bool] = None, ema_decay=None,
-                 tc_decomposition=None, dataset_size: Optional[int] = None, dip_vae=None):
+                 tc_decomposition=None, dataset_size: Optional[int] = None, dip_vae=None, mmd_vae=None):
         self.beta = float(beta)
         self._setup(device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
                     beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition,
-                    dataset_size, capturable=capturable, dip_vae=dip_vae)
+                    dataset_size, capturable=capturable, dip_vae=dip_vae, mmd_vae=mmd_vae)
 
-    def step(self, data, eps=None, grad_hook=None):
+    def step(self, data, eps=None, grad_hook=None, prior=None):
         """``grad_hook(phase, net)`` (tests): called with ``("VAE", model)`` right before the optimizer step; such an
-        iteration is eager, as BetaVAEGANTrainer's."""
-        return self._drive(data, (eps,), grad_hook=grad_hook)
+        iteration is eager, as BetaVAEGANTrainer's.  ``prior`` (with ``mmd_vae`` only): the draws from the prior, (B,
+        n_hidden); None is drawn, after ``eps``."""
+        return self._drive(data, self._with_prior((eps,), prior), grad_hook=grad_hook)
 
     def _iteration(self, data, latents, labels, grad_hook, prepack, acc):
-        eps, = latents
+        eps, *prior = latents                 # (prior: one more draw with ``mmd_vae``, else nothing)
         prepack()                             # the filters the previous optimizer step changed: one pack launch
         self._zero(self.model, self.flat, self.optimizer, grad_hook)
-        recon, mu, logvar, kld, parts = self._forward_kl(self.model, data, eps)
+        recon, mu, logvar, kld, parts = self._forward_kl(self.model, data, eps, *prior)
         mse = F.reconstruction_loss(recon, data)
         _backward([mse, kld])
         self._exchange(self.flat)
@@ -1567,7 +1627,7 @@ class GANTrainer(_GraphedSteps):
     gradient exchange (SUM) per optimizer step, BCE divided by the global batch.  ``graph``: as
     BetaVAEGANTrainer; so are ``max_grad_norm``, ``skip_nonfinite`` and the schedule arguments (``lr_scheduler``,
     ``weight_decay``, ``decoupled_weight_decay``, ``device_hyper``; there is no KL term, so a ``beta_schedule``, a
-    ``tc_decomposition`` or a ``dip_vae`` is a TypeError).  ``ema_decay``: as BetaVAEGANTrainer, of the generator -- `ema_model` shadows `netG`, the checkpoint key is
+    ``tc_decomposition``, a ``dip_vae`` or an ``mmd_vae`` is a TypeError).  ``ema_decay``: as BetaVAEGANTrainer, of the generator -- `ema_model` shadows `netG`, the checkpoint key is
     ``netG_ema``; the discriminator is not averaged."""
 
     _parts = (_Part("netG", Generator_celeba, "optimizerG", "flat_g", "g", "G_trainer"),
@@ -1581,10 +1641,10 @@ class GANTrainer(_GraphedSteps):
                  nonfinite_guard: Optional[bool] = None, max_grad_norm: Optional[float] = None,
                  skip_nonfinite: bool = False, lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0,
                  decoupled_weight_decay: bool = False, device_hyper: Optional[bool] = None, ema_decay=None,
-                 tc_decomposition=None, dataset_size: Optional[int] = None, dip_vae=None):
+                 tc_decomposition=None, dataset_size: Optional[int] = None, dip_vae=None, mmd_vae=None):
         self._setup(device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
                     beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition,
-                    dataset_size, data_parallel, dip_vae=dip_vae)
+                    dataset_size, data_parallel, dip_vae=dip_vae, mmd_vae=mmd_vae)
 
     def step(self, data, noise=None, real_label=0.9, fake_label=0.1, global_batch: Optional[int] = None,
              grad_hook=None):

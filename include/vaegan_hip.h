@@ -50,7 +50,8 @@ extern "C" {
  * vg_adam_step_clip, vg_adam_step_dev_clip; vg_adam_prepare_dev, vg_adam_step_decay, vg_adam_step_dev_decay,
  * vg_reparam_kl_fwd_dev, vg_reparam_kl_bwd_dev; vg_adam_step_dev_ema_dev; the five vg_reparam_tc_* of
  * csrc/reparam_tc.hip; vg_linear_wgrad_adam, vg_linear_wgrad_adam_dev; the five vg_reparam_dip_* of
- * csrc/reparam_dip.hip; the three vg_agg_posterior_* of csrc/agg_posterior.hip) change
+ * csrc/reparam_dip.hip; the three vg_agg_posterior_* of csrc/agg_posterior.hip; the five vg_reparam_mmd_* of
+ * csrc/reparam_mmd.hip) change
  * nothing an existing caller sees and keep the version: a binding that needs them and finds a library without them
  * fails at the symbol lookup, as loudly. */
 #define VG_ABI_VERSION 7
@@ -489,6 +490,49 @@ int vg_reparam_dip_bwd_dev(const float* gz, const float* mu, const float* logvar
                            const double* mean, const float* gloss, int variant, const float* beta_dev, float lambda_od,
                            float lambda_d, float* gmu, float* glogvar, int B, int D, void* workspace,
                            size_t workspace_bytes, void* stream);
+
+/* ---- reparameterisation + the InfoVAE / WAE-MMD objective (Zhao et al. 2019; Tolstikhin et al. 2018; DESIGN.md section
+ * 4.23; csrc/reparam_mmd.hip).  With z = mu + eps*exp(logvar/2), zp ([B,D]) draws from the prior N(0, I), d(a,b) = |a-b|^2
+ * and the kernel k summed over n_bandwidths <= 8 bandwidths h_s > 0,
+ *   kind 1 (rbf): k(d) = sum_s exp(-d/h_s)        kind 2 (imq): k(d) = sum_s h_s/(h_s + d)
+ *   kl  = -0.5*sum_{b,d}(1 + logvar - mu^2 - exp(logvar))
+ *   kzz = 1/(B(B-1))*sum_{i != j} k(z_i, z_j)     kpp = 1/(B(B-1))*sum_{i != j} k(zp_i, zp_j)     kzp = 1/B^2*sum_{i,j} k(z_i, zp_j)
+ *   mmd = kzz + kpp - 2*kzp      (the unbiased U-statistic: it may be negative)
+ * the forward writes z and out4 = {loss, kl, mmd, kzz}, loss = beta*kl + B*lambda_mmd*mmd (batch sums: loss / B is the
+ * paper's objective with the paper's lambda), and what the backward reads: w ([2,B,B] fp32): w[0] = 4/(B(B-1))*k'(d(z_i,
+ * z_j)), symmetric to the bit with a zero diagonal, and w[1] = -4/B^2*k'(d(z_i, zp_j)).  Three launches: z and the KL
+ * partials (fp64), one workgroup per 32 x 32 tile of a pair matrix (zz and pp on or above the diagonal, zp in full; both
+ * row blocks in LDS 64 columns at a time, every squared distance fp32 FMA chains of 16 DIFFERENCES in a fixed order, the
+ * chain sums added in fp64 -- never |a|^2 + |b|^2 - 2 a.b, which cancels for close points; k and k' once per pair in
+ * fp64, exp and true division), one wavefront that sums the partials in a fixed order.  With Gz_i = B*lambda_mmd*sum_j (w[0,i,j]*(z_i - z_j) + w[1,i,j]*
+ * (z_i - zp_j)) the backward writes
+ *   gmu     = gloss*(beta*mu + Gz) + gz
+ *   glogvar = gloss*(beta*0.5*(exp(logvar) - 1) + Gz*eps*0.5*exp(logvar/2)) + gz*eps*0.5*exp(logvar/2)
+ * in one launch; gz (tensor) and gloss (DEVICE scalar, upstream of out4[0]) may each be NULL: that term is absent (gloss
+ * == NULL is one elementwise launch).  zp takes no gradient.  No floating-point atomics: the same inputs give the same
+ * bits.  `bandwidths` is a HOST array of n_bandwidths floats, copied into the kernel arguments.  `workspace`:
+ * vg_reparam_mmd_workspace_bytes(B, D) bytes (0 outside the shape range), 8-byte aligned (the forward's content is not
+ * needed by the backward).  VG_ERR_BAD_ARG before any launch: a NULL pointer other than gz / gloss, B outside [2, 1024]
+ * (the U-statistic has no value at B = 1), D outside [1, 1024], kind outside {1, 2}, n_bandwidths outside [1, 8], a
+ * bandwidth that is not finite and > 0, a lambda_mmd that is not finite and >= 0, and -- here also VG_ERR_BAD_ARG -- a
+ * workspace shorter than that. */
+size_t vg_reparam_mmd_workspace_bytes(int B, int D);
+int vg_reparam_mmd_fwd(const float* mu, const float* logvar, const float* eps, const float* zp, float* z, float* out4,
+                       float* w, int B, int D, int kind, float beta, float lambda_mmd, const float* bandwidths,
+                       int n_bandwidths, void* workspace, size_t workspace_bytes, void* stream);
+int vg_reparam_mmd_bwd(const float* gz, const float* mu, const float* logvar, const float* eps, const float* z,
+                       const float* zp, const float* w, const float* gloss, float beta, float lambda_mmd, float* gmu,
+                       float* glogvar, int B, int D, void* workspace, size_t workspace_bytes, void* stream);
+/* beta read from DEVICE memory (beta_dev[0], fp32), as vg_reparam_kl_fwd_dev: the same fp32 beta gives the same bits.
+ * beta_dev == NULL is VG_ERR_BAD_ARG. */
+int vg_reparam_mmd_fwd_dev(const float* mu, const float* logvar, const float* eps, const float* zp, float* z, float* out4,
+                           float* w, int B, int D, int kind, const float* beta_dev, float lambda_mmd,
+                           const float* bandwidths, int n_bandwidths, void* workspace, size_t workspace_bytes,
+                           void* stream);
+int vg_reparam_mmd_bwd_dev(const float* gz, const float* mu, const float* logvar, const float* eps, const float* z,
+                           const float* zp, const float* w, const float* gloss, const float* beta_dev, float lambda_mmd,
+                           float* gmu, float* glogvar, int B, int D, void* workspace, size_t workspace_bytes,
+                           void* stream);
 
 /* ---- log-density under the aggregate posterior, at evaluation scale (the ELBO decomposition over a dataset and MIG:
  * Chen et al. 2018, section 4 and appendix C; csrc/agg_posterior.hip).  Forward only.  With

@@ -15,24 +15,13 @@
 // chunked FMA chains, over i) and applies the elementwise terms.  No floating-point atomic anywhere, every cross-lane,
 // cross-wavefront and cross-workgroup sum in a fixed order: the same inputs give the same bits.  Plain FMAs, no MFMA: the
 // whole product is 2 B D^2 = 4 MFLOP at (128, 128), and the time is launch and latency.
-#include "common.hpp"
+#include "reparam_common.hpp"
 #include "vaegan_hip.h"
-
-#include <math.h>
 
 namespace {
 
-constexpr int MAX_DIM = 1024;      // B and D
-constexpr int STRIP = 64;          // columns of a stats workgroup: one per lane
-constexpr int SNW = 16;            // its wavefronts
-constexpr int TILE = 32;           // a covariance tile is TILE x TILE, 2 x 2 outputs per thread
-constexpr int CNT = 256;
-constexpr int BK = 64;             // rows (cov) / columns i (backward) of one LDS chunk: the length of an fp32 FMA chain
-constexpr int RB = 16;             // rows of a backward workgroup: 4 per wavefront
-constexpr int KL_SLOTS = MAX_DIM / STRIP;
-
-__host__ __device__ constexpr int tiles_of(int D) { return cdiv(D, TILE); }
-__host__ __device__ constexpr int upper_tiles(int D) { return tiles_of(D) * (tiles_of(D) + 1) / 2; }
+// The geometry is reparam_common.hpp's: a strip is a stats workgroup's, a tile one of the covariance, BK rows (cov) /
+// columns i (backward) of one LDS chunk: the length of an fp32 FMA chain.
 
 // the centred element, formed the same way wherever it is needed: exact in fp64, rounded once
 __device__ __forceinline__ float centred(float mu, double mean) { return (float)((double)mu - mean); }
@@ -50,11 +39,11 @@ __global__ __launch_bounds__(SNW * 64) void dip_stats_kernel(const float* __rest
     for (int b = wid; b < B; b += SNW) {
       const size_t o = (size_t)b * D + d;
       const float m = mu[o], l = lv[o];
-      z[o] = fmaf(eps[o], expf(0.5f * l), m);      // (the expression of reparam_kl_fwd_kernel: the same bits)
+      z[o] = reparam_z(m, l, eps[o]);
       const float el = expf(l);
       sm += (double)m;
       se += (double)el;
-      sk += 1.0 + (double)l - (double)m * (double)m - (double)el;
+      sk += kl_term(m, l);
     }
   }
   red[0][wid][lane] = sm;
@@ -82,13 +71,7 @@ __global__ __launch_bounds__(CNT) void dip_cov_kernel(const float* __restrict__ 
                                                       double* __restrict__ covp, int B, int D, int variant) {
   __shared__ float sa[BK][TILE], sb[BK][TILE];
   __shared__ double red[2][CNT / 64];
-  const int nt = tiles_of(D);
-  int idx = blockIdx.x, tr = 0;      // the blockIdx-th pair (tr <= tc) in row-major order of the upper triangle
-  while (idx >= nt - tr) {
-    idx -= nt - tr;
-    ++tr;
-  }
-  const int tc = tr + idx;
+  const auto [tr, tc] = upper_tile(blockIdx.x, tiles_of(D));
   const int i0 = tr * TILE, j0 = tc * TILE;
   const int t = threadIdx.x, ti = t >> 4, tj = t & 15;      // outputs (ti, ti + 16) x (tj, tj + 16) of the tile
   const int lc = t & 31, lr = t >> 5;                        // staging: column lc, rows lr + 8 k
@@ -118,7 +101,8 @@ __global__ __launch_bounds__(CNT) void dip_cov_kernel(const float* __restrict__ 
     tot[1][0] += (double)a10;
     tot[1][1] += (double)a11;
   }
-  double od = 0.0, dg = 0.0;
+  double part[2] = {0.0, 0.0};      // {od, dg}
+  double &od = part[0], &dg = part[1];
 #pragma unroll
   for (int p = 0; p < 2; ++p)
 #pragma unroll
@@ -136,23 +120,7 @@ __global__ __launch_bounds__(CNT) void dip_cov_kernel(const float* __restrict__ 
           od += (tr != tc ? 2.0 : 1.0) * (double)c * (double)c;
       }
     }
-  od = wave_sum(od);
-  dg = wave_sum(dg);
-  const int lane = t & 63, wid = t >> 6;
-  if (lane == 0) {
-    red[0][wid] = od;
-    red[1][wid] = dg;
-  }
-  __syncthreads();
-  if (t == 0) {
-    od = dg = 0.0;
-    for (int w = 0; w < CNT / 64; ++w) {
-      od += red[0][w];
-      dg += red[1][w];
-    }
-    covp[2 * blockIdx.x + 0] = od;
-    covp[2 * blockIdx.x + 1] = dg;
-  }
+  tile_slot_sums(part, red, covp + 2 * blockIdx.x);
 }
 
 // ---- forward 3: one wavefront, the partials in slot order ---------------------------------------------------------------
@@ -235,18 +203,6 @@ __global__ __launch_bounds__(CNT) void dip_bwd_kernel(const float* __restrict__ 
   }
 }
 
-// gloss absent: the loss term is out as a whole (as in reparam_kl_bwd_kernel); what is left is the decoder's gradient
-__global__ __launch_bounds__(256) void dip_bwd_gz_only_kernel(const float* __restrict__ gz, const float* __restrict__ lv,
-                                                              const float* __restrict__ eps, float* __restrict__ gmu,
-                                                              float* __restrict__ glv, size_t n) {
-  const size_t stride = (size_t)gridDim.x * 256;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-    const float g = gz ? gz[i] : 0.f, e = gz ? eps[i] : 0.f, h = gz ? expf(0.5f * lv[i]) : 0.f;
-    gmu[i] = g;
-    glv[i] = g * e * 0.5f * h;
-  }
-}
-
 bool dims_ok(int B, int D) { return B >= 1 && B <= MAX_DIM && D >= 1 && D <= MAX_DIM; }
 bool variant_ok(int v) { return v == 1 || v == 2; }
 
@@ -281,12 +237,7 @@ int dip_bwd(const float* gz, const float* mu, const float* lv, const float* eps,
     return VG_ERR_BAD_ARG;
   if (BETA_DEV && !beta_dev) return VG_ERR_BAD_ARG;
   if (workspace_bytes < vg_reparam_dip_workspace_bytes(B, D)) return VG_ERR_WORKSPACE;
-  if (!gloss) {
-    const size_t n = (size_t)B * D;
-    hipLaunchKernelGGL(dip_bwd_gz_only_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, gz, lv, eps, gmu, glv, n);
-    VG_CHECK_LAUNCH();
-    return 0;
-  }
+  if (!gloss) return reparam_bwd_gz_only(gz, lv, eps, gmu, glv, B, D, st);
   hipLaunchKernelGGL(dip_bwd_kernel<BETA_DEV>, dim3(cdiv(D, 64), cdiv(B, RB)), dim3(CNT), 0, st, gz, mu, lv, eps, cov, mean,
                      gloss, variant, beta, beta_dev, lambda_od, lambda_d, gmu, glv, B, D);
   VG_CHECK_LAUNCH();

@@ -17,25 +17,17 @@
 // longer chain comes back multiplied) and applies the elementwise terms.  No floating-point atomic anywhere, every
 // cross-lane, cross-wavefront and cross-workgroup sum in a fixed order: the same inputs give the same bits.  Plain VALU
 // work, no MFMA: 3 B^2 D subtract-multiply-adds are 6 MFLOP at (128, 128), and the time is launch and latency.
-#include "common.hpp"
+#include "reparam_common.hpp"
 #include "vaegan_hip.h"
-
-#include <math.h>
 
 namespace {
 
-constexpr int MAX_DIM = 1024;      // B and D
+// The geometry is reparam_common.hpp's: a strip is a z workgroup's, a tile one of a pair matrix, BK columns (pairs) / rows j
+// (backward) of one LDS chunk.
 constexpr int MAX_BW = 8;          // bandwidths of one kernel sum
-constexpr int STRIP = 64;          // columns of a z workgroup: one per lane
-constexpr int SNW = 16;            // its wavefronts
-constexpr int TILE = 32;           // a pair tile is TILE x TILE, 2 x 2 outputs per thread
-constexpr int CNT = 256;
-constexpr int BK = 64;             // columns (pairs) / rows j (backward) of one LDS chunk
 constexpr int CHAIN_D = 16;        // length of an fp32 FMA chain of squared differences; the chain sums are added in fp64
 constexpr int CHAIN_J = 8;         // the same in the backward, where the zz and the zp sums cancel: see mmd_bwd_kernel
-constexpr int RB = 16;             // rows of a backward workgroup: 4 per wavefront
 static_assert(BK % CHAIN_D == 0 && BK % CHAIN_J == 0, "chains tile a chunk");
-constexpr int KL_SLOTS = MAX_DIM / STRIP;
 constexpr int KIND_RBF = 1, KIND_IMQ = 2;
 
 struct Bandwidths {      // copied into the kernel arguments
@@ -43,8 +35,6 @@ struct Bandwidths {      // copied into the kernel arguments
   int n;
 };
 
-__host__ __device__ constexpr int tiles_of(int B) { return cdiv(B, TILE); }
-__host__ __device__ constexpr int upper_tiles(int B) { return tiles_of(B) * (tiles_of(B) + 1) / 2; }
 __host__ __device__ constexpr int pair_tiles(int B) { return 2 * upper_tiles(B) + tiles_of(B) * tiles_of(B); }
 
 // ---- forward 1: z and the KL partial of a strip ---------------------------------------------------------------------------
@@ -59,8 +49,8 @@ __global__ __launch_bounds__(SNW * 64) void mmd_z_kernel(const float* __restrict
     for (int b = wid; b < B; b += SNW) {
       const size_t o = (size_t)b * D + d;
       const float m = mu[o], l = lv[o];
-      z[o] = fmaf(eps[o], expf(0.5f * l), m);      // (the expression of reparam_kl_fwd_kernel: the same bits)
-      sk += 1.0 + (double)l - (double)m * (double)m - (double)expf(l);
+      z[o] = reparam_z(m, l, eps[o]);
+      sk += kl_term(m, l);
     }
   }
   red[wid][lane] = sk;
@@ -99,9 +89,9 @@ __global__ __launch_bounds__(CNT) void mmd_pairs_kernel(const float* __restrict_
                                                         float* __restrict__ w, double* __restrict__ pairp, int B, int D,
                                                         Bandwidths bw) {
   __shared__ float sa[BK][TILE + 1], sb[BK][TILE + 1];      // [column][row]: the pad keeps the staging stores off one bank
-  __shared__ double red[CNT / 64];
+  __shared__ double red[1][CNT / 64];
   const int nt = tiles_of(B), U = upper_tiles(B);
-  int idx = blockIdx.x, which = 0, tr = 0, tc;      // which: 0 zz, 1 pp, 2 zp
+  int idx = blockIdx.x, which = 0, tr, tc;      // which: 0 zz, 1 pp, 2 zp
   if (idx >= 2 * U) {
     which = 2;
     idx -= 2 * U;
@@ -112,11 +102,9 @@ __global__ __launch_bounds__(CNT) void mmd_pairs_kernel(const float* __restrict_
       which = 1;
       idx -= U;
     }
-    while (idx >= nt - tr) {      // the idx-th pair (tr <= tc) in row-major order of the upper triangle
-      idx -= nt - tr;
-      ++tr;
-    }
-    tc = tr + idx;
+    const TilePair upper = upper_tile(idx, nt);
+    tr = upper.tr;
+    tc = upper.tc;
   }
   const float* __restrict__ xa = which == 1 ? zp : z;
   const float* __restrict__ xb = which == 0 ? z : zp;
@@ -156,7 +144,8 @@ __global__ __launch_bounds__(CNT) void mmd_pairs_kernel(const float* __restrict_
   const double pref = which == 0 ? 4.0 / ((double)B * (double)(B - 1)) : -4.0 / ((double)B * (double)B);
   const bool mirrored = which != 2 && tr != tc;
   float* __restrict__ wm = w + (which == 2 ? (size_t)B * B : 0);
-  double ks = 0.0;
+  double part[1] = {0.0};
+  double& ks = part[0];
 #pragma unroll
   for (int p = 0; p < 2; ++p)
 #pragma unroll
@@ -174,15 +163,7 @@ __global__ __launch_bounds__(CNT) void mmd_pairs_kernel(const float* __restrict_
         }
       }
     }
-  ks = wave_sum(ks);
-  const int lane = t & 63, wid = t >> 6;
-  if (lane == 0) red[wid] = ks;
-  __syncthreads();
-  if (t == 0) {
-    ks = 0.0;
-    for (int v = 0; v < CNT / 64; ++v) ks += red[v];
-    pairp[blockIdx.x] = ks;
-  }
+  tile_slot_sums(part, red, pairp + blockIdx.x);
 }
 
 // ---- forward 3: one wavefront, the partials in slot order -------------------------------------------------------------------
@@ -284,18 +265,6 @@ __global__ __launch_bounds__(CNT) void mmd_bwd_kernel(const float* __restrict__ 
   }
 }
 
-// gloss absent: the loss term is out as a whole (as in reparam_kl_bwd_kernel); what is left is the decoder's gradient
-__global__ __launch_bounds__(256) void mmd_bwd_gz_only_kernel(const float* __restrict__ gz, const float* __restrict__ lv,
-                                                              const float* __restrict__ eps, float* __restrict__ gmu,
-                                                              float* __restrict__ glv, size_t n) {
-  const size_t stride = (size_t)gridDim.x * 256;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-    const float g = gz ? gz[i] : 0.f, e = gz ? eps[i] : 0.f, h = gz ? expf(0.5f * lv[i]) : 0.f;
-    gmu[i] = g;
-    glv[i] = g * e * 0.5f * h;
-  }
-}
-
 bool dims_ok(int B, int D) { return B >= 2 && B <= MAX_DIM && D >= 1 && D <= MAX_DIM; }
 bool lambda_ok(float l) { return isfinite(l) && l >= 0.f; }
 
@@ -338,12 +307,7 @@ int mmd_bwd(const float* gz, const float* mu, const float* lv, const float* eps,
     return VG_ERR_BAD_ARG;
   if (BETA_DEV && !beta_dev) return VG_ERR_BAD_ARG;
   if (workspace_bytes < vg_reparam_mmd_workspace_bytes(B, D)) return VG_ERR_BAD_ARG;
-  if (!gloss) {
-    const size_t n = (size_t)B * D;
-    hipLaunchKernelGGL(mmd_bwd_gz_only_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, gz, lv, eps, gmu, glv, n);
-    VG_CHECK_LAUNCH();
-    return 0;
-  }
+  if (!gloss) return reparam_bwd_gz_only(gz, lv, eps, gmu, glv, B, D, st);
   hipLaunchKernelGGL(mmd_bwd_kernel<BETA_DEV>, dim3(cdiv(D, 64), cdiv(B, RB)), dim3(CNT), 0, st, gz, mu, lv, eps, z, zp, w,
                      gloss, beta, beta_dev, lambda_mmd, gmu, glv, B, D);
   VG_CHECK_LAUNCH();

@@ -11,16 +11,14 @@
 // recomputes the pair terms the same way from the two saved log-sum-exps: the sums over j in sample i's workgroup (Gz),
 // the sums over i in workgroup j (Gmu, Glv).  All cross-wavefront and cross-workgroup sums run in a fixed order and there
 // is no floating-point atomic: the same inputs give the same bits.
-#include "common.hpp"
+#include "reparam_common.hpp"
 #include "vaegan_hip.h"
-
-#include <math.h>
 
 namespace {
 
 constexpr int NW = 8;              // wavefronts per workgroup
 constexpr int NT = NW * 64;
-constexpr int MAX_DIM = 1024;      // B and D: 16 elements of a row per lane at most
+static_assert(MAX_DIM == 16 * 64, "B and D: 16 elements of a row per lane at most");
 constexpr float LOG_2PI = 1.8378770664093453f;
 
 // lq for one (i, j, d): diff = z[i,d] - mu[j,d], lv = logvar[j,d], iv = exp(-lv)
@@ -316,18 +314,6 @@ __global__ __launch_bounds__(NT) void tc_bwd_q_kernel(const float* __restrict__ 
   }
 }
 
-// gloss absent: the loss term is out as a whole (as in reparam_kl_bwd_kernel); what is left is the decoder's gradient
-__global__ __launch_bounds__(256) void tc_bwd_gz_only_kernel(const float* __restrict__ gz, const float* __restrict__ lv,
-                                                             const float* __restrict__ eps, float* __restrict__ gmu,
-                                                             float* __restrict__ glv, size_t n) {
-  const size_t stride = (size_t)gridDim.x * 256;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-    const float g = gz ? gz[i] : 0.f, e = gz ? eps[i] : 0.f, h = gz ? expf(0.5f * lv[i]) : 0.f;
-    gmu[i] = g;
-    glv[i] = g * e * 0.5f * h;
-  }
-}
-
 bool dims_ok(int B, int D) { return B >= 1 && B <= MAX_DIM && D >= 1 && D <= MAX_DIM; }
 size_t parts_bytes(int B) { return (size_t)B * 3 * sizeof(double); }
 
@@ -358,12 +344,7 @@ int tc_bwd(const float* gz, const float* mu, const float* lv, const float* eps, 
   if (!mu || !lv || !eps || !z || !lse_joint || !lse_dim || !gmu || !glv || !workspace || !dims_ok(B, D)) return VG_ERR_BAD_ARG;
   if (BETA_DEV && !beta_dev) return VG_ERR_BAD_ARG;
   if (workspace_bytes < vg_reparam_tc_workspace_bytes(B, D)) return VG_ERR_WORKSPACE;
-  if (!gloss) {
-    const size_t n = (size_t)B * D;
-    hipLaunchKernelGGL(tc_bwd_gz_only_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, gz, lv, eps, gmu, glv, n);
-    VG_CHECK_LAUNCH();
-    return 0;
-  }
+  if (!gloss) return reparam_bwd_gz_only(gz, lv, eps, gmu, glv, B, D, st);
   float* Gz = (float*)((char*)workspace + parts_bytes(B));
   const size_t lds = (size_t)NW * D * sizeof(float);
   if (D <= 128) {

@@ -553,7 +553,34 @@ class ReparamKLFn(Function):
         return gmu, glv, None, None
 
 
-class ReparamTCFn(Function):
+class _ReparamObjectiveFn(Function):
+    """What `ReparamTCFn`, `ReparamDIPFn` and `ReparamMMDFn` share: the end of the forward (`_finish`) and the whole
+    backward.  A subclass's ``forward`` calls its `ops` forward and hands `_finish` what the backward needs:
+    ``ops.<bwd>(gz, *saved, gloss, beta, *kept)``.  ``beta``: a float or the device word, as `ReparamKLFn` (a tensor is kept
+    as the word itself, not saved: it takes no gradient)."""
+
+    @staticmethod
+    def _finish(ctx, z, out4, bwd, saved, beta, kept, nargs):
+        """``bwd``: the name of the backward in `ops` (looked up when it runs); ``nargs``: how many arguments the forward took."""
+        ctx.bwd, ctx.beta, ctx.kept, ctx.nargs = bwd, beta, kept, nargs
+        loss, parts = out4[0], out4[1:]
+        ctx.mark_non_differentiable(parts)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(*saved)
+        return z, loss, parts
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gz, gloss, _):
+        if gz is None and gloss is None:
+            return (None,) * ctx.nargs
+        gz = gz.contiguous() if gz is not None else None
+        gloss = gloss.contiguous() if gloss is not None else None
+        gmu, glv = getattr(ops, ctx.bwd)(gz, *ctx.saved_tensors, gloss, ctx.beta, *ctx.kept)
+        return (gmu, glv) + (None,) * (ctx.nargs - 2)
+
+
+class ReparamTCFn(_ReparamObjectiveFn):
     """z = mu + eps*exp(logvar/2) and the beta-TCVAE decomposition of the KL term by minibatch-weighted sampling
     (Chen et al. 2018): ``loss = alpha*mi + beta*tc + gamma*dwkl``, all three summed over the
     batch, in one fused kernel pair each way.  Returns ``z``, ``loss`` and the non-differentiable ``[3]`` tensor
@@ -563,26 +590,11 @@ class ReparamTCFn(Function):
     @staticmethod
     def forward(ctx, mu, logvar, eps, beta, alpha, gamma, log_bn):
         z, out4, lse_joint, lse_dim = ops.reparam_tc_fwd(mu, logvar, eps, beta, alpha, gamma, log_bn)
-        ctx.beta, ctx.alpha, ctx.gamma = beta, alpha, gamma      # (a tensor is kept as the word itself, as in ReparamKLFn)
-        loss, parts = out4[0], out4[1:]
-        ctx.mark_non_differentiable(parts)
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(mu, logvar, eps, z, lse_joint, lse_dim)
-        return z, loss, parts
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gz, gloss, _):
-        if gz is None and gloss is None:
-            return None, None, None, None, None, None, None
-        mu, logvar, eps, z, lse_joint, lse_dim = ctx.saved_tensors
-        gz = gz.contiguous() if gz is not None else None
-        gloss = gloss.contiguous() if gloss is not None else None
-        gmu, glv = ops.reparam_tc_bwd(gz, mu, logvar, eps, z, lse_joint, lse_dim, gloss, ctx.beta, ctx.alpha, ctx.gamma)
-        return gmu, glv, None, None, None, None, None
+        return ReparamTCFn._finish(ctx, z, out4, "reparam_tc_bwd", (mu, logvar, eps, z, lse_joint, lse_dim), beta,
+                                   (alpha, gamma), 7)
 
 
-class ReparamDIPFn(Function):
+class ReparamDIPFn(_ReparamObjectiveFn):
     """z = mu + eps*exp(logvar/2) and the DIP-VAE objective (Kumar et al. 2018):
     ``loss = beta*kl + B*(lambda_od*od + lambda_d*dg)`` with ``od`` / ``dg`` the off-diagonal / diagonal distance of the
     aggregate posterior's covariance from the identity, in three launches forward and one backward.  Returns ``z``,
@@ -592,26 +604,11 @@ class ReparamDIPFn(Function):
     @staticmethod
     def forward(ctx, mu, logvar, eps, beta, lambda_od, lambda_d, variant):
         z, out4, cov, mean = ops.reparam_dip_fwd(mu, logvar, eps, beta, lambda_od, lambda_d, variant)
-        ctx.beta, ctx.lambdas, ctx.variant = beta, (lambda_od, lambda_d), variant      # (a tensor is kept as the word itself)
-        loss, parts = out4[0], out4[1:]
-        ctx.mark_non_differentiable(parts)
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(mu, logvar, eps, cov, mean)
-        return z, loss, parts
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gz, gloss, _):
-        if gz is None and gloss is None:
-            return None, None, None, None, None, None, None
-        mu, logvar, eps, cov, mean = ctx.saved_tensors
-        gz = gz.contiguous() if gz is not None else None
-        gloss = gloss.contiguous() if gloss is not None else None
-        gmu, glv = ops.reparam_dip_bwd(gz, mu, logvar, eps, cov, mean, gloss, ctx.beta, *ctx.lambdas, ctx.variant)
-        return gmu, glv, None, None, None, None, None
+        return ReparamDIPFn._finish(ctx, z, out4, "reparam_dip_bwd", (mu, logvar, eps, cov, mean), beta,
+                                    (lambda_od, lambda_d, variant), 7)
 
 
-class ReparamMMDFn(Function):
+class ReparamMMDFn(_ReparamObjectiveFn):
     """z = mu + eps*exp(logvar/2) and the InfoVAE / WAE-MMD objective (Zhao et al. 2019, Tolstikhin et al. 2018; DESIGN.md
     section 4.23): ``loss = beta*kl + B*lambda_mmd*mmd`` with ``mmd`` the unbiased maximum mean discrepancy between the
     batch of z and the prior draws ``zp``, in three launches forward and one backward.  Returns ``z``, ``loss`` and the
@@ -621,23 +618,8 @@ class ReparamMMDFn(Function):
     @staticmethod
     def forward(ctx, mu, logvar, eps, zp, beta, lambda_mmd, kind, bandwidths):
         z, out4, w = ops.reparam_mmd_fwd(mu, logvar, eps, zp, beta, lambda_mmd, kind, bandwidths)
-        ctx.beta, ctx.lambda_mmd, ctx.kernel = beta, lambda_mmd, (kind, bandwidths)      # (a tensor is kept as the word itself)
-        loss, parts = out4[0], out4[1:]
-        ctx.mark_non_differentiable(parts)
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(mu, logvar, eps, z, zp, w)
-        return z, loss, parts
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gz, gloss, _):
-        if gz is None and gloss is None:
-            return None, None, None, None, None, None, None, None
-        mu, logvar, eps, z, zp, w = ctx.saved_tensors
-        gz = gz.contiguous() if gz is not None else None
-        gloss = gloss.contiguous() if gloss is not None else None
-        gmu, glv = ops.reparam_mmd_bwd(gz, mu, logvar, eps, z, zp, w, gloss, ctx.beta, ctx.lambda_mmd, *ctx.kernel)
-        return gmu, glv, None, None, None, None, None, None
+        return ReparamMMDFn._finish(ctx, z, out4, "reparam_mmd_bwd", (mu, logvar, eps, z, zp, w), beta,
+                                    (lambda_mmd, kind, bandwidths), 8)
 
 
 class KLRowsFn(Function):

@@ -558,33 +558,33 @@ class VAE(nn.Module, _DecoderMixin):
         z, kl = F.reparam_kl(mu, logvar, eps, beta)
         return self.decode(z), mu, logvar, kl
 
-    def forward_with_tc(self, x, eps, beta, alpha, gamma, dataset_size):
-        """`forward_with_kl` with the KL term decomposed (functional.reparam_tc): returns ``recon, mu, logvar, loss,
-        parts`` -- ``loss = alpha*mi + beta*tc + gamma*dwkl``, ``parts`` the ``[3]`` tensor ``(mi, tc, dwkl)``."""
+    def _forward_with_objective(self, x, eps, reparam):
+        """The body of `forward_with_tc` / `_dip` / `_mmd`: encode, draw ``eps`` if None, ``reparam(mu, logvar, eps) -> z,
+        loss, parts``, decode.  Returns ``recon, mu, logvar, loss, parts``."""
         mu, logvar = self.encode(x)
         if eps is None:
             eps = torch.randn_like(mu)
-        z, loss, parts = F.reparam_tc(mu, logvar, eps, beta, alpha, gamma, dataset_size)
+        z, loss, parts = reparam(mu, logvar, eps)
         return self.decode(z), mu, logvar, loss, parts
+
+    def forward_with_tc(self, x, eps, beta, alpha, gamma, dataset_size):
+        """`forward_with_kl` with the KL term decomposed (functional.reparam_tc): returns ``recon, mu, logvar, loss,
+        parts`` -- ``loss = alpha*mi + beta*tc + gamma*dwkl``, ``parts`` the ``[3]`` tensor ``(mi, tc, dwkl)``."""
+        return self._forward_with_objective(
+            x, eps, lambda mu, logvar, eps: F.reparam_tc(mu, logvar, eps, beta, alpha, gamma, dataset_size))
 
     def forward_with_dip(self, x, eps, beta, variant, lambda_od, lambda_d):
         """`forward_with_kl` with the DIP-VAE covariance penalty added (functional.reparam_dip): returns ``recon, mu,
         logvar, loss, parts`` -- ``loss = beta*kl + B*(lambda_od*od + lambda_d*dg)``, ``parts`` the ``[3]`` tensor ``(kl,
         od, dg)``."""
-        mu, logvar = self.encode(x)
-        if eps is None:
-            eps = torch.randn_like(mu)
-        z, loss, parts = F.reparam_dip(mu, logvar, eps, beta, lambda_od, lambda_d, variant)
-        return self.decode(z), mu, logvar, loss, parts
+        return self._forward_with_objective(
+            x, eps, lambda mu, logvar, eps: F.reparam_dip(mu, logvar, eps, beta, lambda_od, lambda_d, variant))
 
     def forward_with_mmd(self, x, eps, prior, beta, kernel, lambda_mmd, bandwidths=None):
         """`forward_with_kl` with the InfoVAE / WAE-MMD penalty added (functional.reparam_mmd): returns ``recon, mu,
         logvar, loss, parts`` -- ``loss = beta*kl + B*lambda_mmd*mmd``, ``parts`` the ``[3]`` tensor ``(kl, mmd, kzz)``.
-        ``prior``: draws from N(0, I) of the shape of ``mu``; like ``eps``, ``None`` is drawn here."""
-        mu, logvar = self.encode(x)
-        if eps is None:
-            eps = torch.randn_like(mu)
-        if prior is None:
-            prior = torch.randn_like(mu)
-        z, loss, parts = F.reparam_mmd(mu, logvar, eps, prior, beta, lambda_mmd, kernel, bandwidths)
-        return self.decode(z), mu, logvar, loss, parts
+        ``prior``: draws from N(0, I) of the shape of ``mu``; like ``eps``, ``None`` is drawn here, after ``eps``."""
+        def reparam(mu, logvar, eps):
+            zp = torch.randn_like(mu) if prior is None else prior
+            return F.reparam_mmd(mu, logvar, eps, zp, beta, lambda_mmd, kernel, bandwidths)
+        return self._forward_with_objective(x, eps, reparam)

@@ -1077,6 +1077,20 @@ def reparam_kl_bwd(gz, mu, logvar, eps, gkl, beta):
     return gmu, glv
 
 
+def _objective_launch(workspace_bytes, fn, fn_dev, mu, head, beta, tail):
+    """The one call site of the KL-phase objectives' entry points (beta-TCVAE, DIP-VAE, InfoVAE / WAE-MMD; DESIGN.md section
+    4.24): ``fn(*head, beta, *tail, workspace, bytes, stream)`` -- or, ``beta`` given as a tensor, ``fn_dev`` with the word's
+    address in that place.  ``workspace_bytes``, ``fn``, ``fn_dev``: the objective's three entries of the library; ``mu``
+    gives B, D and the device."""
+    B, D = mu.shape
+    ws = workspace(workspace_bytes(B, D), mu.device)
+    if isinstance(beta, torch.Tensor):
+        fn, beta = fn_dev, _beta_word(beta).data_ptr()
+    else:
+        beta = float(beta)
+    check(fn(*head, beta, *tail, ws.data_ptr(), ws.numel(), _stream()), fn.__name__)
+
+
 def reparam_tc_fwd(mu, logvar, eps, beta, alpha, gamma, log_bn):
     """Reparameterisation + the beta-TCVAE decomposition of the KL term (vg_reparam_tc_fwd).
     ``beta`` (the total-correlation weight): a float or the device word, as `reparam_kl_fwd`; ``alpha`` / ``gamma``: the
@@ -1090,15 +1104,10 @@ def reparam_tc_fwd(mu, logvar, eps, beta, alpha, gamma, log_bn):
     z, lse_dim = torch.empty_like(mu), torch.empty_like(mu)
     out4 = torch.empty(4, dtype=torch.float32, device=mu.device)
     lse_joint = torch.empty(B, dtype=torch.float64, device=mu.device)
-    nbytes = lib.vg_reparam_tc_workspace_bytes(B, D)
-    ws = workspace(nbytes, mu.device)
     head = (mu.data_ptr(), logvar.data_ptr(), eps.data_ptr(), z.data_ptr(), out4.data_ptr(), lse_joint.data_ptr(),
             lse_dim.data_ptr(), B, D, float(alpha))
-    tail = (float(gamma), float(log_bn), ws.data_ptr(), ws.numel(), _stream())
-    if isinstance(beta, torch.Tensor):
-        check(lib.vg_reparam_tc_fwd_dev(*head, _beta_word(beta).data_ptr(), *tail), "vg_reparam_tc_fwd_dev")
-    else:
-        check(lib.vg_reparam_tc_fwd(*head, float(beta), *tail), "vg_reparam_tc_fwd")
+    _objective_launch(lib.vg_reparam_tc_workspace_bytes, lib.vg_reparam_tc_fwd, lib.vg_reparam_tc_fwd_dev, mu, head, beta,
+                      (float(gamma), float(log_bn)))
     return z, out4, lse_joint, lse_dim
 
 
@@ -1147,14 +1156,10 @@ def reparam_tc_bwd(gz, mu, logvar, eps, z, lse_joint, lse_dim, gloss, beta, alph
         raise RuntimeError("reparam_tc_bwd: lse_joint must be the contiguous float64 device tensor of reparam_tc_fwd")
     B, D = mu.shape
     gmu, glv = torch.empty_like(mu), torch.empty_like(mu)
-    ws = workspace(lib.vg_reparam_tc_workspace_bytes(B, D), mu.device)
     head = (_ptr(gz), mu.data_ptr(), logvar.data_ptr(), eps.data_ptr(), z.data_ptr(), lse_joint.data_ptr(),
             lse_dim.data_ptr(), _ptr(gloss), float(alpha))
-    tail = (float(gamma), gmu.data_ptr(), glv.data_ptr(), B, D, ws.data_ptr(), ws.numel(), _stream())
-    if isinstance(beta, torch.Tensor):
-        check(lib.vg_reparam_tc_bwd_dev(*head, _beta_word(beta).data_ptr(), *tail), "vg_reparam_tc_bwd_dev")
-    else:
-        check(lib.vg_reparam_tc_bwd(*head, float(beta), *tail), "vg_reparam_tc_bwd")
+    _objective_launch(lib.vg_reparam_tc_workspace_bytes, lib.vg_reparam_tc_bwd, lib.vg_reparam_tc_bwd_dev, mu, head, beta,
+                      (float(gamma), gmu.data_ptr(), glv.data_ptr(), B, D))
     return gmu, glv
 
 
@@ -1184,14 +1189,10 @@ def reparam_dip_fwd(mu, logvar, eps, beta, lambda_od, lambda_d, variant):
     out4 = torch.empty(4, dtype=torch.float32, device=mu.device)
     cov = torch.empty(D, D, dtype=torch.float32, device=mu.device)
     mean = torch.empty(D, dtype=torch.float64, device=mu.device)
-    ws = workspace(lib.vg_reparam_dip_workspace_bytes(B, D), mu.device)
     head = (mu.data_ptr(), logvar.data_ptr(), eps.data_ptr(), z.data_ptr(), out4.data_ptr(), cov.data_ptr(), mean.data_ptr(),
             B, D, variant)
-    tail = (float(lambda_od), float(lambda_d), ws.data_ptr(), ws.numel(), _stream())
-    if isinstance(beta, torch.Tensor):
-        check(lib.vg_reparam_dip_fwd_dev(*head, _beta_word(beta).data_ptr(), *tail), "vg_reparam_dip_fwd_dev")
-    else:
-        check(lib.vg_reparam_dip_fwd(*head, float(beta), *tail), "vg_reparam_dip_fwd")
+    _objective_launch(lib.vg_reparam_dip_workspace_bytes, lib.vg_reparam_dip_fwd, lib.vg_reparam_dip_fwd_dev, mu, head, beta,
+                      (float(lambda_od), float(lambda_d)))
     return z, out4, cov, mean
 
 
@@ -1209,13 +1210,9 @@ def reparam_dip_bwd(gz, mu, logvar, eps, cov, mean, gloss, beta, lambda_od, lamb
         raise RuntimeError("reparam_dip_bwd: cov and mean must be the [D, D] fp32 and [D] float64 tensors of reparam_dip_fwd")
     variant = dip_variant(variant)
     gmu, glv = torch.empty_like(mu), torch.empty_like(mu)
-    ws = workspace(lib.vg_reparam_dip_workspace_bytes(B, D), mu.device)
     head = (_ptr(gz), mu.data_ptr(), logvar.data_ptr(), eps.data_ptr(), cov.data_ptr(), mean.data_ptr(), _ptr(gloss), variant)
-    tail = (float(lambda_od), float(lambda_d), gmu.data_ptr(), glv.data_ptr(), B, D, ws.data_ptr(), ws.numel(), _stream())
-    if isinstance(beta, torch.Tensor):
-        check(lib.vg_reparam_dip_bwd_dev(*head, _beta_word(beta).data_ptr(), *tail), "vg_reparam_dip_bwd_dev")
-    else:
-        check(lib.vg_reparam_dip_bwd(*head, float(beta), *tail), "vg_reparam_dip_bwd")
+    _objective_launch(lib.vg_reparam_dip_workspace_bytes, lib.vg_reparam_dip_bwd, lib.vg_reparam_dip_bwd_dev, mu, head, beta,
+                      (float(lambda_od), float(lambda_d), gmu.data_ptr(), glv.data_ptr(), B, D))
     return gmu, glv
 
 
@@ -1268,14 +1265,10 @@ def reparam_mmd_fwd(mu, logvar, eps, zp, beta, lambda_mmd, kind, bandwidths=None
     z = torch.empty_like(mu)
     out4 = torch.empty(4, dtype=torch.float32, device=mu.device)
     w = torch.empty(2, B, B, dtype=torch.float32, device=mu.device)
-    ws = workspace(lib.vg_reparam_mmd_workspace_bytes(B, D), mu.device)
     head = (mu.data_ptr(), logvar.data_ptr(), eps.data_ptr(), zp.data_ptr(), z.data_ptr(), out4.data_ptr(), w.data_ptr(),
             B, D, kind)
-    tail = (float(lambda_mmd), ctypes.addressof(hs), n, ws.data_ptr(), ws.numel(), _stream())
-    if isinstance(beta, torch.Tensor):
-        check(lib.vg_reparam_mmd_fwd_dev(*head, _beta_word(beta).data_ptr(), *tail), "vg_reparam_mmd_fwd_dev")
-    else:
-        check(lib.vg_reparam_mmd_fwd(*head, float(beta), *tail), "vg_reparam_mmd_fwd")
+    _objective_launch(lib.vg_reparam_mmd_workspace_bytes, lib.vg_reparam_mmd_fwd, lib.vg_reparam_mmd_fwd_dev, mu, head, beta,
+                      (float(lambda_mmd), ctypes.addressof(hs), n))
     return z, out4, w
 
 
@@ -1295,13 +1288,9 @@ def reparam_mmd_bwd(gz, mu, logvar, eps, z, zp, w, gloss, beta, lambda_mmd, kind
     if kind is not None:
         mmd_bandwidths(mmd_kernel(kind), D, bandwidths)
     gmu, glv = torch.empty_like(mu), torch.empty_like(mu)
-    ws = workspace(lib.vg_reparam_mmd_workspace_bytes(B, D), mu.device)
     head = (_ptr(gz), mu.data_ptr(), logvar.data_ptr(), eps.data_ptr(), z.data_ptr(), zp.data_ptr(), w.data_ptr(), _ptr(gloss))
-    tail = (float(lambda_mmd), gmu.data_ptr(), glv.data_ptr(), B, D, ws.data_ptr(), ws.numel(), _stream())
-    if isinstance(beta, torch.Tensor):
-        check(lib.vg_reparam_mmd_bwd_dev(*head, _beta_word(beta).data_ptr(), *tail), "vg_reparam_mmd_bwd_dev")
-    else:
-        check(lib.vg_reparam_mmd_bwd(*head, float(beta), *tail), "vg_reparam_mmd_bwd")
+    _objective_launch(lib.vg_reparam_mmd_workspace_bytes, lib.vg_reparam_mmd_bwd, lib.vg_reparam_mmd_bwd_dev, mu, head, beta,
+                      (float(lambda_mmd), gmu.data_ptr(), glv.data_ptr(), B, D))
     return gmu, glv
 
 

@@ -32,7 +32,7 @@ import warnings
 import weakref
 from contextlib import nullcontext
 from dataclasses import dataclass, field
-from typing import Dict, List, NamedTuple, Optional
+from typing import Callable, Dict, List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -474,6 +474,81 @@ class _Part(NamedTuple):
     ckpt: str         # checkpoint key of its optimizer
 
 
+class _Objective(NamedTuple):
+    """One objective that replaces or extends the KL term of the encoder phase, and all that differs between them.
+    DESIGN.md section 4.24 lists what a new one touches; here it is one entry of `_OBJECTIVES`."""
+    keyword: str              # the constructor keyword it answers to; the trainer's attribute of that name reads its arguments
+    parse: Callable           # (the keyword's value, ModelOpt) -> the frozen, hashable argument tuple
+    forward: Callable         # (net, data, eps, beta, args, prior) -> recon, mu, logvar, loss, parts
+    parts: tuple              # the loss keys of parts[0..2]
+    latents: tuple = ()       # latents the iteration draws on top of the trainer's own, last in draw order
+    needs_dataset_size: bool = False      # `dataset_size` joins the arguments: required before a step, filled from a loader
+
+
+def _parse_tc(tc_decomposition, opt):
+    """``tc_decomposition=(alpha, gamma)``: the weights of the mutual-information and the dimension-wise-KL parts."""
+    try:
+        alpha, gamma = (float(v) for v in tc_decomposition)
+    except (TypeError, ValueError):
+        raise TypeError(f"tc_decomposition must be a pair (alpha, gamma) of floats, got {tc_decomposition!r}") from None
+    if not (np.isfinite(alpha) and np.isfinite(gamma)):
+        raise ValueError(f"tc_decomposition: alpha and gamma must be finite, got {tc_decomposition!r}")
+    return alpha, gamma
+
+
+def _parse_dip(dip_vae, opt):
+    """``dip_vae=(variant, lambda_od, lambda_d)``: "i" | "ii", the weights of the off-diagonal / diagonal penalty."""
+    try:
+        variant, lambda_od, lambda_d = dip_vae
+        lambda_od, lambda_d = float(lambda_od), float(lambda_d)
+    except (TypeError, ValueError):
+        raise TypeError(f"dip_vae must be a triple (variant, lambda_od, lambda_d), got {dip_vae!r}") from None
+    if variant not in ("i", "ii"):
+        raise ValueError(f"dip_vae: variant must be 'i' or 'ii', got {variant!r}")
+    if not (np.isfinite(lambda_od) and np.isfinite(lambda_d) and lambda_od >= 0.0 and lambda_d >= 0.0):
+        raise ValueError(f"dip_vae: lambda_od and lambda_d must be finite and >= 0, got {dip_vae!r}")
+    return variant, lambda_od, lambda_d
+
+
+def _parse_mmd(mmd_vae, opt):
+    """``mmd_vae=(kernel, lambda_mmd[, bandwidths])``: "rbf" | "imq", the MMD's weight, a tuple of floats or None."""
+    try:
+        kernel, lambda_mmd, *rest = mmd_vae
+        lambda_mmd = float(lambda_mmd)
+        bandwidths, = rest or (None,)
+    except (TypeError, ValueError):
+        raise TypeError(f"mmd_vae must be (kernel, lambda_mmd) or (kernel, lambda_mmd, bandwidths), got {mmd_vae!r}") from None
+    if kernel not in ("rbf", "imq"):
+        raise ValueError(f"mmd_vae: kernel must be 'rbf' or 'imq', got {kernel!r}")
+    if not (np.isfinite(lambda_mmd) and lambda_mmd >= 0.0):
+        raise ValueError(f"mmd_vae: lambda_mmd must be finite and >= 0, got {mmd_vae!r}")
+    if bandwidths is not None:
+        try:
+            bandwidths = ops.mmd_bandwidths(kernel, opt.n_hidden, bandwidths)
+        except ValueError as e:
+            raise ValueError(f"mmd_vae: {e}") from None
+    return kernel, lambda_mmd, bandwidths
+
+
+# The table: the methods are looked up on the network when called (a test may replace one).
+_OBJECTIVES = (
+    _Objective("tc_decomposition", _parse_tc,       # args: (alpha, gamma, dataset_size); `beta` weighs the total correlation
+               lambda net, data, eps, beta, args, prior: net.forward_with_tc(data, eps, beta, *args),
+               ("mi", "tc", "dwkl"), needs_dataset_size=True),
+    _Objective("dip_vae", _parse_dip,               # args: (variant, lambda_od, lambda_d); `beta` weighs the KL
+               lambda net, data, eps, beta, args, prior: net.forward_with_dip(data, eps, beta, *args),
+               ("kl", "dip_od", "dip_d")),
+    _Objective("mmd_vae", _parse_mmd,               # args: (kernel, lambda_mmd, bandwidths); the MMD is between z and `prior`
+               lambda net, data, eps, beta, args, prior: net.forward_with_mmd(data, eps, prior, beta, *args),
+               ("kl", "mmd", "mmd_kzz"), latents=("prior",)),
+)
+
+
+def _objective_args(keyword):
+    """The public attribute of a trainer named as the constructor keyword: the objective's parsed arguments, None when off."""
+    return property(lambda self: self._objective[1] if self._objective and self._objective[0].keyword == keyword else None)
+
+
 class _GraphedSteps:
     """What the three trainers share: the construction (`_setup`), the one path an iteration takes (`_drive`: eager, or
     -- `_graph_usable` -- a HIP-graph replay with its warm-up count per shape, capture and fallback), the guard, the
@@ -499,9 +574,7 @@ class _GraphedSteps:
         self._single_use = {}     # (id(network), DEFER_WGRAD) -> its weights that may be updated inside the backward
         on_gpu = self.device.type == "cuda"
         _use_tuned_gemms(self.device)
-        self._tc_args(tc_decomposition, dataset_size, has_beta)
-        self._dip_args(dip_vae, has_beta)
-        self._mmd_args(mmd_vae, has_beta)
+        self._select_objective(dict(tc_decomposition=tc_decomposition, dip_vae=dip_vae, mmd_vae=mmd_vae), dataset_size, has_beta)
         self.max_grad_norm, self.skip_nonfinite = max_grad_norm, bool(skip_nonfinite)
         self._skipped = {}
         self.world, self.rank = _dist_world(), _dist_rank()
@@ -727,117 +800,72 @@ class _GraphedSteps:
                                 f"{type(sched).__name__} for {name}")
             self.lr_schedulers[name] = sched
 
-    # ---- the KL term decomposed (beta-TCVAE) --------------------------------------------------------------------------
-    tc_decomposition = None   # (alpha, gamma): the weights of the mutual-information and the dimension-wise-KL parts
+    # ---- the objective of the KL phase: the analytic KL, or one entry of `_OBJECTIVES` ---------------------------------------
+    _objective = None         # (entry, its parsed arguments) of the selected one
     dataset_size = None       # N of minibatch-weighted sampling
+    tc_decomposition = _objective_args("tc_decomposition")
+    dip_vae = _objective_args("dip_vae")
+    mmd_vae = _objective_args("mmd_vae")
 
-    def _tc_args(self, tc_decomposition, dataset_size, has_beta=True):
-        """Validate ``tc_decomposition=(alpha, gamma)`` and ``dataset_size`` of a trainer's constructor."""
-        if tc_decomposition is None and dataset_size is None:
-            return
-        if not has_beta:
-            raise TypeError(f"{type(self).__name__} has no KL term: tc_decomposition does not apply")
-        if tc_decomposition is not None:
-            try:
-                alpha, gamma = (float(v) for v in tc_decomposition)
-            except (TypeError, ValueError):
-                raise TypeError(f"tc_decomposition must be a pair (alpha, gamma) of floats, got {tc_decomposition!r}") from None
-            if not (np.isfinite(alpha) and np.isfinite(gamma)):
-                raise ValueError(f"tc_decomposition: alpha and gamma must be finite, got {tc_decomposition!r}")
-            self.tc_decomposition = (alpha, gamma)
-        if dataset_size is not None:
-            if int(dataset_size) != dataset_size or int(dataset_size) < 1:
-                raise ValueError(f"dataset_size must be an integer >= 1, got {dataset_size!r}")
-            self.dataset_size = int(dataset_size)
+    def _select_objective(self, given, dataset_size, has_beta=True):
+        """A trainer's constructor: ``given`` maps every keyword of the table to its value; at most one is not None.  The
+        entries are taken in table order, each checked in full before the next."""
+        for o in _OBJECTIVES:
+            value = given[o.keyword]
+            with_size = o.needs_dataset_size and dataset_size is not None
+            if value is None and not with_size:
+                continue
+            if not has_beta:
+                raise TypeError(f"{type(self).__name__} has no KL term: {o.keyword} does not apply")
+            if value is not None:
+                if self._objective is not None:
+                    every = [e.keyword for e in reversed(_OBJECTIVES)]
+                    raise ValueError(f"{', '.join(every[:-1])} and {every[-1]} each replace the KL term of the encoder phase: "
+                                     f"pass one of them (got {o.keyword} and {self._objective[0].keyword})")
+                self._objective = (o, o.parse(value, self.opt))
+                self._latents = (*type(self)._latents, *o.latents)
+            if with_size:
+                if int(dataset_size) != dataset_size or int(dataset_size) < 1:
+                    raise ValueError(f"dataset_size must be an integer >= 1, got {dataset_size!r}")
+                self.dataset_size = int(dataset_size)
+
+    def _objective_key(self):
+        """The selected objective with every frozen kernel argument, `dataset_size` included where it is one."""
+        if self._objective is None:
+            return None
+        o, args = self._objective
+        return o.keyword, (*args, self.dataset_size) if o.needs_dataset_size else args
+
+    def _dataset_size_missing(self):
+        return self._objective is not None and self._objective[0].needs_dataset_size and self.dataset_size is None
 
     def _dataset_size_from(self, loader):
         """`train_epoch` / `fit`: a ``dataset_size`` that was not given is the loader's ``len(loader.dataset)``."""
-        if self.tc_decomposition is not None and self.dataset_size is None:
+        if self._dataset_size_missing():
             self.dataset_size = int(len(loader.dataset))
 
-    # ---- the KL term plus the DIP-VAE covariance penalty ----------------------------------------------------------------
-    dip_vae = None            # (variant, lambda_od, lambda_d): "i" | "ii", the weights of the off-diagonal / diagonal penalty
-
-    def _dip_args(self, dip_vae, has_beta=True):
-        """Validate ``dip_vae=(variant, lambda_od, lambda_d)`` of a trainer's constructor."""
-        if dip_vae is None:
-            return
-        if not has_beta:
-            raise TypeError(f"{type(self).__name__} has no KL term: dip_vae does not apply")
-        if self.tc_decomposition is not None:
-            raise ValueError("dip_vae and tc_decomposition each replace the KL term of the encoder phase: pass one of them")
-        try:
-            variant, lambda_od, lambda_d = dip_vae
-            lambda_od, lambda_d = float(lambda_od), float(lambda_d)
-        except (TypeError, ValueError):
-            raise TypeError(f"dip_vae must be a triple (variant, lambda_od, lambda_d), got {dip_vae!r}") from None
-        if variant not in ("i", "ii"):
-            raise ValueError(f"dip_vae: variant must be 'i' or 'ii', got {variant!r}")
-        if not (np.isfinite(lambda_od) and np.isfinite(lambda_d) and lambda_od >= 0.0 and lambda_d >= 0.0):
-            raise ValueError(f"dip_vae: lambda_od and lambda_d must be finite and >= 0, got {dip_vae!r}")
-        self.dip_vae = (variant, lambda_od, lambda_d)
-
-    # ---- the KL term plus the InfoVAE / WAE-MMD penalty ------------------------------------------------------------------
-    mmd_vae = None            # (kernel, lambda_mmd, bandwidths): "rbf" | "imq", the MMD's weight, a tuple of floats or None
-
-    def _mmd_args(self, mmd_vae, has_beta=True):
-        """Validate ``mmd_vae=(kernel, lambda_mmd[, bandwidths])`` of a trainer's constructor.  With the option the
-        iteration takes one more latent, the prior's draw, last in draw order."""
-        if mmd_vae is None:
-            return
-        if not has_beta:
-            raise TypeError(f"{type(self).__name__} has no KL term: mmd_vae does not apply")
-        if self.tc_decomposition is not None or self.dip_vae is not None:
-            raise ValueError("mmd_vae, dip_vae and tc_decomposition each replace the KL term of the encoder phase: pass one "
-                             "of them")
-        try:
-            kernel, lambda_mmd, *rest = mmd_vae
-            lambda_mmd = float(lambda_mmd)
-            bandwidths, = rest or (None,)
-        except (TypeError, ValueError):
-            raise TypeError(f"mmd_vae must be (kernel, lambda_mmd) or (kernel, lambda_mmd, bandwidths), got {mmd_vae!r}") from None
-        if kernel not in ("rbf", "imq"):
-            raise ValueError(f"mmd_vae: kernel must be 'rbf' or 'imq', got {kernel!r}")
-        if not (np.isfinite(lambda_mmd) and lambda_mmd >= 0.0):
-            raise ValueError(f"mmd_vae: lambda_mmd must be finite and >= 0, got {mmd_vae!r}")
-        if bandwidths is not None:
-            try:
-                bandwidths = ops.mmd_bandwidths(kernel, self.opt.n_hidden, bandwidths)
-            except ValueError as e:
-                raise ValueError(f"mmd_vae: {e}") from None
-        self.mmd_vae = (kernel, lambda_mmd, bandwidths)
-        self._latents = (*type(self)._latents, "prior")
-
     def _forward_kl(self, net, data, eps, prior=None):
-        """The encoder-side forward of the KL phase: ``recon, mu, logvar, kld, parts`` -- the analytic KL (``parts`` is
-        None), or with ``tc_decomposition`` the decomposed one, whose total-correlation weight is `beta`, or with
-        ``dip_vae`` the KL, weighted by `beta`, plus the covariance penalty, or with ``mmd_vae`` that KL plus the MMD
-        between the batch of z and ``prior``."""
-        if self.mmd_vae is not None:
-            kernel, lambda_mmd, bandwidths = self.mmd_vae
-            return net.forward_with_mmd(data, eps, prior, self._kl_beta(), kernel, lambda_mmd, bandwidths)
-        if self.dip_vae is not None:
-            return net.forward_with_dip(data, eps, self._kl_beta(), *self.dip_vae)
-        if self.tc_decomposition is None:
+        """The encoder-side forward of the KL phase: ``recon, mu, logvar, kld, parts`` -- the analytic KL weighted by `beta`
+        (``parts`` is None), or the selected objective's loss and its three parts."""
+        if self._objective is None:
             return (*net.forward_with_kl(data, eps, self._kl_beta()), None)
-        alpha, gamma = self.tc_decomposition
-        return net.forward_with_tc(data, eps, self._kl_beta(), alpha, gamma, self.dataset_size)
+        return self._objective[0].forward(net, data, eps, self._kl_beta(), self._objective_key()[1], prior)
 
     def _with_prior(self, given, prior):
-        """`step`'s latents in `_latents` order: with ``mmd_vae`` the prior's draw (or None: drawn) comes last."""
-        if self.mmd_vae is None:
-            if prior is not None:
-                raise TypeError(f"{type(self).__name__}.step: prior= belongs to mmd_vae, which is off")
-            return given
-        return (*given, prior)
+        """`step`'s latents in `_latents` order: behind the trainer's own, the prior's draw (or None: drawn) of an objective
+        that takes one."""
+        if "prior" in self._latents:
+            return (*given, prior)
+        if prior is not None:
+            owners = " / ".join(o.keyword for o in _OBJECTIVES if "prior" in o.latents)
+            raise TypeError(f"{type(self).__name__}.step: prior= belongs to {owners}, which is off")
+        return given
 
     def _kl_part_outputs(self, parts):
-        """The additional loss keys -- present only with ``tc_decomposition``, ``dip_vae`` or ``mmd_vae``."""
+        """The additional loss keys -- present only with an objective."""
         if parts is None:
             return {}
-        names = (("kl", "mmd", "mmd_kzz") if self.mmd_vae is not None
-                 else ("kl", "dip_od", "dip_d") if self.dip_vae is not None else ("mi", "tc", "dwkl"))
-        return {name: parts[n] for n, name in enumerate(names)}
+        return {name: parts[n] for n, name in enumerate(self._objective[0].parts)}
 
     def _kl_beta(self):
         """What the KL kernels take: the device word with ``device_hyper`` (eager and captured alike), else the float."""
@@ -851,9 +879,9 @@ class _GraphedSteps:
             self._beta_written = self.beta
 
     def _begin_step(self):
-        if self.tc_decomposition is not None and self.dataset_size is None:
-            raise ValueError(f"{type(self).__name__}: tc_decomposition needs dataset_size (the number of training samples): "
-                             "pass dataset_size=..., or train through train_epoch / fit, which take it from the loader")
+        if self._dataset_size_missing():
+            raise ValueError(f"{type(self).__name__}: {self._objective[0].keyword} needs dataset_size (the number of training "
+                             "samples): pass dataset_size=..., or train through train_epoch / fit, which take it from the loader")
         if self.beta_schedule is not None:
             self.beta = float(self.beta_schedule(self.iteration))
         self._sync_beta()
@@ -1039,9 +1067,7 @@ class _GraphedSteps:
                 self.nonfinite_guard,        # (checked or unchecked Adam launches)
                 self.max_grad_norm, self.skip_nonfinite,      # (the norm pass and the clip step, or neither)
                 self.device_hyper,           # (lr, weight decay and beta read from device words, or frozen arguments)
-                self.tc_decomposition and (*self.tc_decomposition, self.dataset_size),      # (frozen kernel arguments)
-                self.dip_vae,                # (the same: variant and both lambdas)
-                self.mmd_vae,                # (the same: kernel, lambda and the bandwidths)
+                self._objective_key(),       # (which objective, and its frozen kernel arguments)
                 tuple(net.training for net in self._nets()),
                 tuple(p.requires_grad for net in self._nets() for p in net.parameters()))
 
@@ -1273,7 +1299,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
         """data (B,3,64,64) in [-1,1]; noise / eps2 / eps3 (B, n_hidden) ~ N(0,1) (new_betavaegan.py:111, model.py:534);
         the labels are the per-iteration scalars of :89-90."""
         netEG, netD = self.netEG, self.netD
-        noise, eps2, eps3, *prior = latents                  # (prior: one more draw with ``mmd_vae``, else nothing)
+        noise, eps2, eps3, *prior = latents                  # (prior: one more draw with an objective that takes it, else nothing)
         real_label, fake_label, gb = labels
         prepack()
         out = {}
@@ -1586,7 +1612,7 @@ class VAETrainer(_GraphedSteps):
         return self._drive(data, self._with_prior((eps,), prior), grad_hook=grad_hook)
 
     def _iteration(self, data, latents, labels, grad_hook, prepack, acc):
-        eps, *prior = latents                 # (prior: one more draw with ``mmd_vae``, else nothing)
+        eps, *prior = latents                 # (prior: one more draw with an objective that takes it, else nothing)
         prepack()                             # the filters the previous optimizer step changed: one pack launch
         self._zero(self.model, self.flat, self.optimizer, grad_hook)
         recon, mu, logvar, kld, parts = self._forward_kl(self.model, data, eps, *prior)

@@ -137,10 +137,17 @@ def test_trainer_arguments():
         with pytest.raises(ValueError, match="mmd_vae"):
             T.VAETrainer(device="cpu", mmd_vae=bad)
     for cls in (T.VAETrainer, T.BetaVAEGANTrainer):
-        with pytest.raises(ValueError, match="mmd_vae, dip_vae and tc_decomposition"):
+        # one rule for every clash: the table's keywords, then the two that met
+        with pytest.raises(ValueError, match=r"mmd_vae, dip_vae and tc_decomposition.*\(got mmd_vae and tc_decomposition\)"):
             cls(device="cpu", mmd_vae=("imq", 1000.0), tc_decomposition=(1.0, 1.0), dataset_size=100)
-        with pytest.raises(ValueError, match="mmd_vae, dip_vae and tc_decomposition"):
+        with pytest.raises(ValueError, match=r"mmd_vae, dip_vae and tc_decomposition.*\(got mmd_vae and dip_vae\)"):
             cls(device="cpu", mmd_vae=("imq", 1000.0), dip_vae=("i", 10.0, 100.0))
+        with pytest.raises(ValueError, match=r"mmd_vae, dip_vae and tc_decomposition.*\(got dip_vae and tc_decomposition\)"):
+            cls(device="cpu", dip_vae=("i", 10.0, 100.0), tc_decomposition=(1.0, 1.0), dataset_size=100)
+        with pytest.raises(ValueError, match=r"\(got dip_vae and tc_decomposition\)"):      # all three: the first clash in table order
+            cls(device="cpu", mmd_vae=("imq", 1000.0), dip_vae=("i", 10.0, 100.0), tc_decomposition=(1.0, 1.0), dataset_size=100)
+        with pytest.raises(TypeError, match="pair"):      # a malformed earlier keyword is reported before the clash
+            cls(device="cpu", mmd_vae=("imq", 1000.0), tc_decomposition=1.0)
     plain, keyed = T.VAETrainer(device="cpu"), T.VAETrainer(device="cpu", mmd_vae=("imq", 1000))
     assert plain.mmd_vae is None and keyed.mmd_vae == ("imq", 1000.0, None)
     assert plain._latents == ("eps",) and keyed._latents == ("eps", "prior")      # one more draw, last

@@ -31,6 +31,10 @@ decoder's output is quantised to the very bytes ``save_image(x[i], normalize=Tru
 (``InceptionFeatureExtractor.features_u8``) -- no PIL, no PCIe copy, no file.  Differences from the file route that are
 NOT arithmetic: the lossy JPEG-in-PDF encoding of the reference's ``.pdf`` samples is skipped (a PNG would round-trip
 these bytes exactly), and all ``n_samples`` are scored (scoring/fid.py:88 drops the remainder of the last batch of 50).
+
+Keeping the activations: ``sample_features`` / ``path_features`` return the [n, d] activations themselves (the same loops
+as ``sample_statistics`` / the folder route, unfolded), ``save_features`` writes them beside ``mu`` and ``sigma`` -- what
+the metrics of sample_quality.py (precision / recall, density / coverage, KID) need and the statistics cannot give.
 """
 import os
 import pathlib
@@ -135,26 +139,59 @@ _NO_EXTRACTOR = (
     "precomputed .npz statistics.")
 
 
-def _handle_path(path, feature_extractor, device, batch_size=50):
-    """fid.py:286-300: .npz statistics or a folder of *.jpg / *.png images."""
-    if str(path).endswith(".npz"):
-        return load_statistics(path)
+def _path_activations(path, feature_extractor, batch_size=50):
+    """The activations [n_i, d] of a folder of *.jpg / *.png images, batch by batch (fid.py:88: the remainder of the
+    last batch is never propagated)."""
     if feature_extractor is None:
         raise RuntimeError(_NO_EXTRACTOR)
     p = pathlib.Path(path)
     files = list(p.glob("*.jpg")) + list(p.glob("*.png"))
-    st = None
     n_batches = len(files) // min(batch_size, max(len(files), 1))   # fid.py:88: the remainder is never propagated
     bs = min(batch_size, len(files))
     for i in range(n_batches):
         act = feature_extractor(_load_images(files[i * bs:(i + 1) * bs]))
         act = torch.as_tensor(np.asarray(act) if not isinstance(act, torch.Tensor) else act)
-        act = act.reshape(act.shape[0], -1)
+        yield act.reshape(act.shape[0], -1)
+
+
+def _handle_path(path, feature_extractor, device, batch_size=50):
+    """fid.py:286-300: .npz statistics or a folder of *.jpg / *.png images."""
+    if str(path).endswith(".npz"):
+        return load_statistics(path)
+    st = None
+    for act in _path_activations(path, feature_extractor, batch_size):
         st = st or ActivationStatistics(act.shape[1], device)
         st.update(act)
     if st is None:
         raise RuntimeError(f"no *.jpg / *.png images under {path}")
     return st.finalize()
+
+
+def path_features(path, feature_extractor=None, device="cuda"):
+    """[n, d] fp32 on ``device``: the ``features`` array of an ``.npz`` written by `save_features`, or the activations of
+    an image folder -- the same files and the same remainder rule as the FID of that folder (`_handle_path`)."""
+    if str(path).endswith(".npz"):
+        with np.load(path) as f:
+            if "features" not in f.files:
+                raise RuntimeError(f"{path} holds no `features` array (keys: {sorted(f.files)}): statistics alone "
+                                   "(mu, sigma) cannot serve the sample-quality metrics; write the file with "
+                                   "fid.save_features")
+            feats = f["features"][:]
+        return torch.as_tensor(feats).to(device=device, dtype=torch.float32).contiguous()
+    acts = [act.to(device=device, dtype=torch.float32) for act in _path_activations(path, feature_extractor)]
+    if not acts:
+        raise RuntimeError(f"no *.jpg / *.png images under {path}")
+    return torch.cat(acts).contiguous()
+
+
+def save_features(path, features):
+    """`save_statistics` plus the activations themselves: ``mu``, ``sigma`` (fp64, of all rows) and ``features`` (fp32
+    [n, d]) in one ``.npz``, which then serves `get_fid`, `get_fid_of_generator` and `path_features` alike."""
+    feats = features.detach() if isinstance(features, torch.Tensor) else torch.as_tensor(np.asarray(features))
+    if feats.dim() != 2 or feats.shape[0] < 2:
+        raise ValueError("save_features: features must be [n, d] with n >= 2")
+    mu, sigma = calculate_activation_statistics(feats, device=feats.device)
+    np.savez(path, mu=mu.cpu().numpy(), sigma=sigma.cpu().numpy(), features=feats.float().cpu().numpy())
 
 
 def _find_inception_weights(inception_path):
@@ -204,6 +241,24 @@ def _eval_nets(fn, eval_mode):
     return (net,)
 
 
+def _sample_activations(fn, n_samples, n_hidden, feature_extractor, device, decode_batch, eval_mode):
+    """The one loop behind `sample_statistics` and `sample_features`: yields the activations [n_i, d] of each decoded
+    piece, in order -- the CPU draw, the decoding, the quantisation and the extractor calls documented there."""
+    if feature_extractor is None:
+        raise RuntimeError(_NO_EXTRACTOR)
+    if decode_batch is not None and int(decode_batch) < 1:
+        raise ValueError("decode_batch must be positive")
+    extract = getattr(feature_extractor, "features_u8", feature_extractor)
+    from . import model, ops
+    with torch.no_grad(), model.eval_mode(*_eval_nets(fn, eval_mode)):
+        z = torch.randn(n_samples, n_hidden)                 # CPU draw, like the reference
+        step = n_samples if decode_batch is None else int(decode_batch)
+        for s in range(0, n_samples, step):
+            sample = fn(z[s:s + step].to(device))
+            act = extract(ops.quantize_each_u8(sample.detach().float().contiguous()))
+            yield act.reshape(act.shape[0], -1)
+
+
 def sample_statistics(fn, n_samples, n_hidden, feature_extractor, device="cuda", decode_batch=None, eval_mode=False):
     """(mu, sigma), fp64 device tensors, of the pool_3 activations of ``n_samples`` decoded N(0, 1) codes -- what
     utils.py:23-29 + scoring/fid.py:286-300 compute through files, without leaving the device.
@@ -223,23 +278,24 @@ def sample_statistics(fn, n_samples, n_hidden, feature_extractor, device="cuda",
     n_samples = int(n_samples)
     if n_samples < 2:
         raise ValueError("covariance needs at least 2 samples")
-    if feature_extractor is None:
-        raise RuntimeError(_NO_EXTRACTOR)
-    if decode_batch is not None and int(decode_batch) < 1:
-        raise ValueError("decode_batch must be positive")
-    extract = getattr(feature_extractor, "features_u8", feature_extractor)
-    from . import model, ops
     st = None
-    with torch.no_grad(), model.eval_mode(*_eval_nets(fn, eval_mode)):
-        z = torch.randn(n_samples, n_hidden)                 # CPU draw, like the reference
-        step = n_samples if decode_batch is None else int(decode_batch)
-        for s in range(0, n_samples, step):
-            sample = fn(z[s:s + step].to(device))
-            act = extract(ops.quantize_each_u8(sample.detach().float().contiguous()))
-            act = act.reshape(act.shape[0], -1)
-            st = st or ActivationStatistics(act.shape[1], device)
-            st.update(act)
+    for act in _sample_activations(fn, n_samples, n_hidden, feature_extractor, device, decode_batch, eval_mode):
+        st = st or ActivationStatistics(act.shape[1], device)
+        st.update(act)
     return st.finalize()
+
+
+def sample_features(fn, n_samples, n_hidden, feature_extractor, device="cuda", decode_batch=None, eval_mode=False):
+    """The activations themselves, [n_samples, d] fp32 on ``device``: the same draw, decoding, quantisation and extractor
+    calls as `sample_statistics` (one loop serves both), kept instead of folded into the statistics -- what
+    `sample_quality` needs (``ActivationStatistics(d, device).update(features).finalize()`` of an undivided decode is
+    `sample_statistics` of the same seed)."""
+    n_samples = int(n_samples)
+    if n_samples < 1:
+        raise ValueError("n_samples must be positive")
+    acts = [act.to(device=device, dtype=torch.float32)
+            for act in _sample_activations(fn, n_samples, n_hidden, feature_extractor, device, decode_batch, eval_mode)]
+    return (acts[0] if len(acts) == 1 else torch.cat(acts)).contiguous()
 
 
 def get_fid_of_generator(fn, n_samples, n_hidden, path_pretrained, inception="", feature_extractor=None, device="cuda",

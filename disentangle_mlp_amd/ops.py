@@ -1143,6 +1143,67 @@ def agg_posterior_lse(z, mu, logvar, splits=None):
     return lse_joint, lse_dim
 
 
+PAIR_TILE = 64           # VG_PAIR_TILE: rows of a per workgroup and rows of b per column tile, the unit of vg_pair_* splits
+PAIR_MAX_K = 8           # VG_PAIR_MAX_K
+
+
+def _pair_splits_arg(splits, name):
+    splits = 0 if splits is None else int(splits)      # (0, as in the C ABI, is None)
+    if splits < 0:
+        raise RuntimeError(f"{name}: splits must not be negative")
+    return splits
+
+
+def _pair_operands(a, b, name):
+    _req(a, "a"), _req(b, "b")
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1] or a.device != b.device:
+        raise RuntimeError(f"{name}: a must be [M, D] and b [N, D] on one device")
+    return a.shape[0], b.shape[0], a.shape[1]
+
+
+def pair_splits(M, N, D, splits=None):
+    """The number of column ranges `pair_knn` / `pair_hits` run for these sizes: the launcher's choice for ``None``, else
+    the request clamped to the number of column tiles (ceil(N / PAIR_TILE)) with ranges left empty by the rounding
+    dropped; 0 for sizes the kernels reject."""
+    return int(_lib.load().vg_pair_splits(int(M), int(N), int(D), _pair_splits_arg(splits, "pair_splits")))
+
+
+def pair_knn(a, b=None, k=1, splits=None):
+    """[M, k] fp32: per row of ``a`` [M, D] the ``k`` smallest SQUARED Euclidean distances to the rows of ``b`` [N, D],
+    ascending (vg_pair_knn); ``+inf`` where fewer than ``k`` candidates exist.  ``b=None``: ``a``
+    against itself with each row's own index excluded (a duplicate row elsewhere still counts, with distance 0).
+    ``splits``: the number of column ranges (tests), ``None`` = chosen from the sizes; the bits do not depend on it."""
+    k = int(k)
+    if not 1 <= k <= PAIR_MAX_K:
+        raise ValueError(f"pair_knn: k must be in 1..{PAIR_MAX_K}, got {k}")
+    splits = _pair_splits_arg(splits, "pair_knn")
+    exclude_self = b is None
+    b = a if exclude_self else b
+    M, N, D = _pair_operands(a, b, "pair_knn")
+    lib = _lib.load()
+    out = torch.empty(M, k, dtype=torch.float32, device=a.device)
+    ws = workspace(lib.vg_pair_workspace_bytes(M, N, D, k, splits), a.device)
+    check(lib.vg_pair_knn(a.data_ptr(), b.data_ptr(), int(exclude_self), out.data_ptr(), M, N, D, k, splits, ws.data_ptr(),
+                          ws.numel(), _stream()), "vg_pair_knn")
+    return out
+
+
+def pair_hits(a, b, thr, splits=None):
+    """[M] int32: per row i of ``a`` [M, D] the number of rows j of ``b`` [N, D] with squared distance ``<= thr[j]``
+    (``thr`` [N] fp32, one threshold per row of ``b``; vg_pair_hits).  ``splits`` as in `pair_knn`."""
+    splits = _pair_splits_arg(splits, "pair_hits")
+    M, N, D = _pair_operands(a, b, "pair_hits")
+    _req(thr, "thr")
+    if thr.shape != (N,) or thr.device != a.device:
+        raise RuntimeError("pair_hits: thr must be [N], one threshold per row of b, on the operands' device")
+    lib = _lib.load()
+    count = torch.empty(M, dtype=torch.int32, device=a.device)
+    ws = workspace(lib.vg_pair_workspace_bytes(M, N, D, 1, splits), a.device)
+    check(lib.vg_pair_hits(a.data_ptr(), b.data_ptr(), thr.data_ptr(), count.data_ptr(), M, N, D, splits, ws.data_ptr(),
+                           ws.numel(), _stream()), "vg_pair_hits")
+    return count
+
+
 def reparam_tc_bwd(gz, mu, logvar, eps, z, lse_joint, lse_dim, gloss, beta, alpha, gamma):
     """gz: tensor or None; gloss: 0-dim device tensor (upstream gradient of the weighted loss) or None."""
     lib = _lib.load()

@@ -1467,11 +1467,28 @@ class BetaVAEGANTrainer(_GraphedSteps):
         from .inception import InceptionFeatureExtractor
         return InceptionFeatureExtractor(weights, device=self.device)
 
+    def _sample_quality(self, net, n_samples, extractor, real_feats, args, fid_path_pretrained=None):
+        """``{"sample_quality": report}`` of ``n_samples`` decoded samples against ``real_feats`` and, given the path of
+        the reference statistics, ``"FID"`` from the SAME features: `fid.get_fid_of_generator` step by step (the path
+        first, one undivided decode, one statistics update), the features kept in between."""
+        from . import fid, sample_quality
+        res = {}
+        if fid_path_pretrained is not None:
+            if not os.path.exists(fid_path_pretrained):
+                raise RuntimeError("Invalid path: %s" % fid_path_pretrained)
+            m2, s2 = fid._handle_path(fid_path_pretrained, extractor, self.device)
+        feats = fid.sample_features(net.decode, n_samples, self.opt.n_hidden, extractor, self.device)
+        if fid_path_pretrained is not None:
+            m1, s1 = fid.ActivationStatistics(feats.shape[1], self.device).update(feats).finalize()
+            res["FID"] = fid.calculate_frechet_distance(m1, s1, m2, s2, device=self.device)
+        res["sample_quality"] = sample_quality.report(real_feats, feats, **(args or {}))
+        return res
+
     def evaluate(self, load_paths, test_loader=None, start_epoch=0, calc_fid=False, n_samples=1000, fid_path_samples=None,
                  fid_path_pretrained=None, get_fid=None, test_recons=False, test_results_path_recons=None,
                  test_results_path_originals="", test_samples=False, test_results_path_samples=None,
                  fid_on_device=False, fid_inception="", fid_feature_extractor=None, eval_mode=False, use_ema=False,
-                 latent_report=None):
+                 latent_report=None, sample_quality=None, sample_quality_args=None):
         """The evaluation half (new_betavaegan.py:248-267): for every checkpoint of ``load_paths`` -- load it, renumber
         its epoch the way the reference does so that files of several checkpoints do not overwrite each other (:252-254),
         then FID samples + score (:256-259), one grid of test reconstructions with ``nrow=1`` (+ the originals, :260-263)
@@ -1485,21 +1502,37 @@ class BetaVAEGANTrainer(_GraphedSteps):
         checkpoint's ``encoder_decoder_ema``, or equal to the live network when the checkpoint has none -- and
         ``eval_mode`` then applies to it (see `recalibrate_ema_bn`).  ``latent_report=loader`` (opt-in): each
         checkpoint's dict also carries, under ``latent``, `latent_report` of that loader (same ``eval_mode`` / ``use_ema``);
-        without it no launch, key or file differs."""
+        without it no launch, key or file differs.  ``sample_quality=`` real features (an ``.npz`` written by
+        `fid.save_features`, an image folder, or a [n, d] device tensor; opt-in): each checkpoint's dict also carries,
+        under ``sample_quality``, `sample_quality.report` (precision / recall, density / coverage, KID;
+        ``sample_quality_args`` are its keywords) of ``n_samples`` decoded samples against them, through the same network
+        as the device FID (``fid_inception`` / ``fid_feature_extractor``) and under the same ``eval_mode`` / ``use_ema``.
+        The generated features are computed once: with ``calc_fid`` and ``fid_on_device`` the FID statistics come from
+        them too, not from a second decode-and-extract pass.  Without the keyword nothing differs."""
         from . import image_io
         out, tmp_epoch = [], 0
         net = self._sampling_net(use_ema)
-        fid_extractor = self._fid_extractor(fid_inception, fid_feature_extractor) if calc_fid and fid_on_device else None
+        want_sq = sample_quality is not None
+        fid_extractor = (self._fid_extractor(fid_inception, fid_feature_extractor)
+                         if (calc_fid and fid_on_device) or want_sq else None)
+        if want_sq:
+            from .fid import path_features
+            real_feats = (sample_quality.to(self.device) if isinstance(sample_quality, torch.Tensor)
+                          else path_features(sample_quality, fid_extractor, self.device))
         for m in load_paths:
             epoch = self.load(m)
             epoch = epoch if epoch != tmp_epoch and tmp_epoch < epoch else tmp_epoch + 1
             tmp_epoch = epoch
             res = {"path": m, "epoch": epoch, "FID": "N/A"}
             with torch.no_grad(), _model.eval_mode(*((net,) if eval_mode else ())):
+                if want_sq:
+                    res.update(self._sample_quality(net, n_samples, fid_extractor, real_feats, sample_quality_args,
+                                                    fid_path_pretrained if calc_fid and fid_on_device else None))
                 if calc_fid and fid_on_device:
-                    from .fid import get_fid_of_generator
-                    res["FID"] = get_fid_of_generator(net.decode, n_samples, self.opt.n_hidden, fid_path_pretrained,
-                                                      feature_extractor=fid_extractor, device=self.device)
+                    if not want_sq:                      # (else scored above, from the features the report used)
+                        from .fid import get_fid_of_generator
+                        res["FID"] = get_fid_of_generator(net.decode, n_samples, self.opt.n_hidden, fid_path_pretrained,
+                                                          feature_extractor=fid_extractor, device=self.device)
                 elif calc_fid:
                     if get_fid is None:
                         from .fid import get_fid

@@ -51,7 +51,7 @@ extern "C" {
  * vg_reparam_kl_fwd_dev, vg_reparam_kl_bwd_dev; vg_adam_step_dev_ema_dev; the five vg_reparam_tc_* of
  * csrc/reparam_tc.hip; vg_linear_wgrad_adam, vg_linear_wgrad_adam_dev; the five vg_reparam_dip_* of
  * csrc/reparam_dip.hip; the three vg_agg_posterior_* of csrc/agg_posterior.hip; the five vg_reparam_mmd_* of
- * csrc/reparam_mmd.hip) change
+ * csrc/reparam_mmd.hip; the four vg_pair_* of csrc/pair_dist.hip) change
  * nothing an existing caller sees and keep the version: a binding that needs them and finds a library without them
  * fails at the symbol lookup, as loudly. */
 #define VG_ABI_VERSION 7
@@ -557,6 +557,37 @@ int vg_agg_posterior_splits(int M, int N, int D, int splits);
 size_t vg_agg_posterior_workspace_bytes(int M, int N, int D, int splits);
 int vg_agg_posterior_lse(const float* z, const float* mu, const float* logvar, double* lse_joint, float* lse_dim, int M,
                          int N, int D, int splits, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- all-pairs squared Euclidean distances of two feature sets, reduced on the fly (sample-quality metrics: improved
+ * precision / recall, Kynkaanniemi et al. 2019; density / coverage, Naeem et al. 2020; DESIGN.md section 4.25;
+ * csrc/pair_dist.hip).  a[M,D] and b[N,D] are row-major fp32; no pointer needs more than a float's alignment.  With
+ *   d2[i,j] = sum_d (a[i,d] - b[j,d])^2      formed from the DIFFERENCES (never the Gram form: identical rows give
+ * exactly 0), one fp32 FMA chain in ascending d whose order depends neither on the tile, nor on `splits`, nor on which
+ * operand is a and which is b -- d2 of two given rows has the same bits in every call that forms it;
+ * |d2 - exact| <= (D + 3) 2^-24 exact.
+ *   vg_pair_knn:   out[i, 0..K) (fp32, [M,K]) = the K smallest d2[i, .], ascending, 1 <= K <= VG_PAIR_MAX_K; slots for
+ *                  which no candidate exists hold +inf.  exclude_self = 1 skips j == i BY INDEX (a duplicate row
+ *                  elsewhere still counts, with distance 0); it requires a == b and M == N.  Any other non-zero value,
+ *                  or 1 without those, is VG_ERR_BAD_ARG.
+ *   vg_pair_hits:  count[i] (int32, [M]) = #{ j : d2[i,j] <= thr[j] }, thr fp32 [N], one threshold per COLUMN.  The
+ *                  comparison is <=, as in Kynkaanniemi's code (the prdc package of Naeem et al. uses <: the two differ
+ *                  on exact ties only); a NaN threshold or distance counts nothing.
+ * A workgroup owns VG_PAIR_TILE rows of a and walks a range of column tiles (VG_PAIR_TILE rows of b each); N is cut into
+ * `splits` ranges of whole column tiles whose partial lists / counts a second kernel merges in range order: no atomics,
+ * nothing of size M x N in memory, the same bits every run and for every `splits`.  splits == 0: chosen from (M, N)
+ * alone.  A `splits` above the number of column tiles (or above 1024) is CLAMPED, and ranges left empty by the rounding
+ * are dropped; vg_pair_splits returns the count that runs (0 for rejected sizes).  Two launches each.
+ * 1 <= M, N <= 2^20, 1 <= D <= 4096, splits >= 0: otherwise VG_ERR_BAD_ARG (the two planners return 0).  `workspace`:
+ * vg_pair_workspace_bytes(M, N, D, K, splits) bytes (the same `splits` as the call; K = 1 for vg_pair_hits), 256-byte
+ * aligned; a shorter one is VG_ERR_WORKSPACE. */
+#define VG_PAIR_TILE 64
+#define VG_PAIR_MAX_K 8
+int vg_pair_splits(int M, int N, int D, int splits);
+size_t vg_pair_workspace_bytes(int M, int N, int D, int K, int splits);
+int vg_pair_knn(const float* a, const float* b, int exclude_self, float* out, int M, int N, int D, int K, int splits,
+                void* workspace, size_t workspace_bytes, void* stream);
+int vg_pair_hits(const float* a, const float* b, const float* thr, int* count, int M, int N, int D, int splits,
+                 void* workspace, size_t workspace_bytes, void* stream);
 
 /* out[i] = g[i] * s[0] with s a DEVICE scalar: applies the upstream gradient of a
  * loss scalar to a gradient precomputed by the fused loss kernels, without a

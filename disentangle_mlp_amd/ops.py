@@ -1204,6 +1204,44 @@ def pair_hits(a, b, thr, splits=None):
     return count
 
 
+RECON_BAND_ROWS = 16     # VG_RECON_BAND_ROWS: output rows of the SSIM map per workgroup of vg_recon_quality
+RECON_TILE_COLS = 32     # VG_RECON_TILE_COLS: output columns per workgroup
+RECON_WINDOWS = (3, 5, 7, 9, 11)
+
+
+def recon_quality(x, y, data_range=2.0, window=11, sigma=1.5, k1=0.01, k2=0.03):
+    """[B, 3] fp64 on the device: per image of ``x`` against ``y`` (contiguous fp32 [B, C, H, W]) the sum of squared
+    errors, the mean SSIM and the mean contrast-structure term over the valid positions of a ``window`` x ``window``
+    Gaussian window (vg_recon_quality): fp64 window moments, no intermediate of their size, two
+    launches, the same bits every run.  ``data_range``: the span L of the pixel values (2 for the tanh decoder's
+    [-1, 1]); C1 = (k1 L)^2, C2 = (k2 L)^2.  A batch of any size goes in one call: the images share grid.x."""
+    _req(x, "x"), _req(y, "y")
+    if x.dim() != 4 or y.shape != x.shape or y.device != x.device:
+        raise RuntimeError(f"recon_quality: x and y must be [B, C, H, W] tensors of one shape on one device, got "
+                           f"{tuple(x.shape)} and {tuple(y.shape)}")
+    window = int(window)
+    if window not in RECON_WINDOWS:
+        raise ValueError(f"recon_quality: window must be odd and in 3..11, got {window}")
+    B, C, H, W = x.shape
+    if min(B, C) < 1 or H < window or W < window:
+        raise RuntimeError(f"recon_quality: a {window} x {window} window needs B, C >= 1 and H, W >= {window}, got "
+                           f"{tuple(x.shape)}")
+    for name, v, low in (("sigma", sigma, 0.0), ("data_range", data_range, 0.0), ("k1", k1, None), ("k2", k2, None)):
+        v = float(v)
+        if not math.isfinite(v) or v < 0.0 or (low is not None and v <= low):
+            raise ValueError(f"recon_quality: {name} must be finite and {'positive' if low is not None else 'non-negative'}, got {v}")
+    lib = _lib.load()
+    nbytes = lib.vg_recon_quality_workspace_bytes(B, C, H, W, window)
+    if nbytes == 0:
+        raise RuntimeError(f"recon_quality: {tuple(x.shape)} needs more workgroups than one launch holds: score it in pieces")
+    out = torch.empty(B, 3, dtype=torch.float64, device=x.device)
+    ws = workspace(nbytes, x.device)
+    check(lib.vg_recon_quality(x.data_ptr(), y.data_ptr(), out.data_ptr(), B, C, H, W, window, float(sigma),
+                               float(data_range), float(k1), float(k2), ws.data_ptr(), ws.numel(), _stream()),
+          "vg_recon_quality")
+    return out
+
+
 def reparam_tc_bwd(gz, mu, logvar, eps, z, lse_joint, lse_dim, gloss, beta, alpha, gamma):
     """gz: tensor or None; gloss: 0-dim device tensor (upstream gradient of the weighted loss) or None."""
     lib = _lib.load()

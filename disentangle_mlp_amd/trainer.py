@@ -992,6 +992,44 @@ class _GraphedSteps:
             report.update(metrics.mig(mu, logvar, factors, generator=generator))
         return report
 
+    def reconstruction_report(self, loader, sample=False, eval_mode=False, use_ema=False, dis_l=False, generator=None):
+        """How well held-out images come back through encoder and decoder (recon_quality.py):
+        under ``no_grad`` every batch of ``loader`` (``(data, labels)`` pairs, or bare image batches) is encoded, decoded
+        and scored against itself; returns `recon_quality.report` over all of them -- ``n``, ``mse`` (the mean per-image
+        sum of squared errors), ``psnr``, ``ssim``, ``ssim_std``, ``ms_ssim``, ``ms_ssim_scales``; the scalars are 0-dim
+        fp64 device tensors.  ``sample=False`` decodes the posterior mean, ``z = mu``; ``sample=True`` runs the network's
+        own ``forward`` with the latent noise drawn from ``generator`` (default: the device's global one).
+        ``eval_mode`` / ``use_ema``: as in `evaluate`.  BatchNorm runs in TRAINING mode by default, as everywhere in the
+        evaluation half: batch statistics, and the running ones move; ``eval_mode=True`` runs inside
+        ``model.eval_mode(net)`` and moves nothing.  ``dis_l=True`` (`BetaVAEGANTrainer`) adds ``dis_l``, the VAE-GAN's
+        learned similarity per image, ``0.5 sum((f(recon) - f(x))^2)`` over the discriminator's ``lth_features`` (the
+        per-image sum in fp64), averaged over the images; the discriminator stays in training mode whatever
+        ``eval_mode`` says, so its two forwards per batch move ITS running statistics.  ``TypeError`` for a trainer
+        whose network has no encoder (`GANTrainer`) or, with ``dis_l``, no discriminator."""
+        from . import metrics, recon_quality
+        net = self._sampling_net(use_ema)
+        if not all(hasattr(net, a) for a in ("encode", "decode")):
+            raise TypeError(f"{type(self).__name__}: {type(net).__name__} has no encoder, there is nothing to reconstruct")
+        netD = getattr(self, "netD", None) if dis_l else None
+        if dis_l and netD is None:
+            raise TypeError(f"{type(self).__name__} has no discriminator: dis_l needs its features")
+        acc, dis = recon_quality.Accumulator(), []
+        with torch.no_grad(), _model.eval_mode(*((net,) if eval_mode else ())):
+            for batch in loader:
+                x = (batch[0] if isinstance(batch, (tuple, list)) else batch).to(self.device)
+                if sample:
+                    recon = net(x, metrics._randn((x.size(0), net.n_hidden), x.device, generator))[0]
+                else:
+                    recon = net.decode(net.encode(x)[0])
+                acc.update(recon, x)
+                if netD is not None:
+                    fr, fx = (netD(t)[1].reshape(x.size(0), -1).double() for t in (recon, x))
+                    dis.append(0.5 * ((fr - fx) ** 2).sum(1))
+        report = acc.result()
+        if netD is not None:
+            report["dis_l"] = torch.cat(dis).mean()
+        return report
+
     @torch.no_grad()
     def reset_ema(self):
         """Shadow <- the live network as it is now: weights and BatchNorm buffers, copied into the existing tensors."""
@@ -1488,7 +1526,8 @@ class BetaVAEGANTrainer(_GraphedSteps):
                  fid_path_pretrained=None, get_fid=None, test_recons=False, test_results_path_recons=None,
                  test_results_path_originals="", test_samples=False, test_results_path_samples=None,
                  fid_on_device=False, fid_inception="", fid_feature_extractor=None, eval_mode=False, use_ema=False,
-                 latent_report=None, sample_quality=None, sample_quality_args=None):
+                 latent_report=None, sample_quality=None, sample_quality_args=None, reconstruction_report=None,
+                 reconstruction_args=None):
         """The evaluation half (new_betavaegan.py:248-267): for every checkpoint of ``load_paths`` -- load it, renumber
         its epoch the way the reference does so that files of several checkpoints do not overwrite each other (:252-254),
         then FID samples + score (:256-259), one grid of test reconstructions with ``nrow=1`` (+ the originals, :260-263)
@@ -1508,7 +1547,11 @@ class BetaVAEGANTrainer(_GraphedSteps):
         ``sample_quality_args`` are its keywords) of ``n_samples`` decoded samples against them, through the same network
         as the device FID (``fid_inception`` / ``fid_feature_extractor``) and under the same ``eval_mode`` / ``use_ema``.
         The generated features are computed once: with ``calc_fid`` and ``fid_on_device`` the FID statistics come from
-        them too, not from a second decode-and-extract pass.  Without the keyword nothing differs."""
+        them too, not from a second decode-and-extract pass.  Without the keyword nothing differs.
+        ``reconstruction_report=loader`` (opt-in): each checkpoint's dict also carries, under ``reconstruction``,
+        `reconstruction_report` of that loader (PSNR / SSIM / MS-SSIM of its images through encoder and decoder;
+        ``reconstruction_args``: its keywords ``sample``, ``dis_l``, ``generator``) under the same ``eval_mode`` /
+        ``use_ema``; without it no launch, key or file differs."""
         from . import image_io
         out, tmp_epoch = [], 0
         net = self._sampling_net(use_ema)
@@ -1548,6 +1591,9 @@ class BetaVAEGANTrainer(_GraphedSteps):
                                               test_results_path_samples, nrow=1, device=self.device)
             if latent_report is not None:
                 res["latent"] = self.latent_report(latent_report, eval_mode=eval_mode, use_ema=use_ema)
+            if reconstruction_report is not None:
+                res["reconstruction"] = self.reconstruction_report(reconstruction_report, eval_mode=eval_mode,
+                                                                   use_ema=use_ema, **(reconstruction_args or {}))
             out.append(res)
         return out
 

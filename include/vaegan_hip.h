@@ -51,7 +51,8 @@ extern "C" {
  * vg_reparam_kl_fwd_dev, vg_reparam_kl_bwd_dev; vg_adam_step_dev_ema_dev; the five vg_reparam_tc_* of
  * csrc/reparam_tc.hip; vg_linear_wgrad_adam, vg_linear_wgrad_adam_dev; the five vg_reparam_dip_* of
  * csrc/reparam_dip.hip; the three vg_agg_posterior_* of csrc/agg_posterior.hip; the five vg_reparam_mmd_* of
- * csrc/reparam_mmd.hip; the four vg_pair_* of csrc/pair_dist.hip) change
+ * csrc/reparam_mmd.hip; the four vg_pair_* of csrc/pair_dist.hip; the two vg_recon_quality* of
+ * csrc/recon_quality.hip) change
  * nothing an existing caller sees and keep the version: a binding that needs them and finds a library without them
  * fails at the symbol lookup, as loudly. */
 #define VG_ABI_VERSION 7
@@ -588,6 +589,35 @@ int vg_pair_knn(const float* a, const float* b, int exclude_self, float* out, in
                 void* workspace, size_t workspace_bytes, void* stream);
 int vg_pair_hits(const float* a, const float* b, const float* thr, int* count, int M, int N, int D, int splits,
                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- reconstruction quality of an image batch against its originals (the distortion side of a beta sweep: PSNR, SSIM,
+ * Wang et al. 2004, and MS-SSIM, Wang et al. 2003, are formed from these three numbers per image; the reference logs only
+ * a pixel MSE, new_betavaegan.py:189-197; csrc/recon_quality.hip).  x, y: contiguous fp32
+ * [B,C,H,W]; out: fp64 [B,3], per image
+ *   out[b,0] = sse  = sum_{c,h,w} (x - y)^2                                    (differences and squares in fp64)
+ *   out[b,1] = ssim = mean of (2 mx my + C1)(2 sxy + C2) / ((mx^2 + my^2 + C1)(sx2 + sy2 + C2))
+ *   out[b,2] = cs   = mean of (2 sxy + C2) / (sx2 + sy2 + C2)
+ * both means over the C (H - window + 1)(W - window + 1) VALID window positions (no padding), with mx, my, sx2, sy2, sxy the
+ * Gaussian-weighted window moments, C1 = (k1 L)^2, C2 = (k2 L)^2, L = data_range.  `window` is odd, 3..11; the taps
+ * exp(-(i - (window - 1)/2)^2 / (2 sigma^2)), normalised to sum 1, are formed on the host in fp64.
+ * Arithmetic: the five moments (x, y, x^2, y^2, xy) by a separable filter, a horizontal then a vertical pass, each ONE fp64
+ * FMA chain in ascending tap order from 0 (products of the fp32 inputs formed in fp64: exact); sx2 = E[x^2] - mx^2 and
+ * everything after it fp64 without contraction.  A pixel's value does not depend on the band or tile that formed it; x
+ * against itself gives sse = 0 and ssim = cs = 1 exactly.  Per-pixel error against an exact evaluation <= ~3e-12 at the
+ * defaults on |x|, |y| <= L/2.  A NaN or inf pixel makes its image's three outputs non-finite, no other's.
+ * A workgroup owns one (image, channel, band of VG_RECON_BAND_ROWS output rows, tile of VG_RECON_TILE_COLS output
+ * columns): inputs with their halo in LDS as fp32, the horizontal pass's results in LDS as fp64, a reduction by wavefront
+ * shuffles into the workgroup's workspace slot; a second kernel adds an image's slots in index order.  No atomics, nothing
+ * of the moments' size in memory, two launches, the same bits every run and wherever in the batch an image stands.
+ * VG_ERR_BAD_ARG: a NULL pointer, a dimension < 1, `window` even or outside 3..11, H or W < window, sigma or data_range
+ * not finite and > 0, k1 or k2 not finite and >= 0, more than 2^31 - 1 workgroups (B * C * bands * tiles), out or
+ * workspace not 8-byte aligned; the workspace query returns 0 for the rejected sizes.  `workspace`:
+ * vg_recon_quality_workspace_bytes(...) bytes; a shorter one is VG_ERR_WORKSPACE. */
+#define VG_RECON_BAND_ROWS 16
+#define VG_RECON_TILE_COLS 32
+size_t vg_recon_quality_workspace_bytes(int B, int C, int H, int W, int window);
+int vg_recon_quality(const float* x, const float* y, double* out, int B, int C, int H, int W, int window, double sigma,
+                     double data_range, double k1, double k2, void* workspace, size_t workspace_bytes, void* stream);
 
 /* out[i] = g[i] * s[0] with s a DEVICE scalar: applies the upstream gradient of a
  * loss scalar to a gradient precomputed by the fused loss kernels, without a

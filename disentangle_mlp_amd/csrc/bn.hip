@@ -1,11 +1,16 @@
-// Train-mode BatchNorm (2-D and 1-D) fused with ReLU / LeakyReLU(0.2), forward and
-// backward, plus the per-channel sum used for convolution bias gradients.
+// BatchNorm (2-D and 1-D) fused with ReLU / LeakyReLU(0.2): train mode forward and backward, eval mode on the running
+// statistics, the coefficients from a convolution's statistics slots, plus the per-channel sum used for convolution bias
+// gradients.
 // HBM-bound kernels: float4 coalesced streams over NCHW planes, fp64 partial sums
 // reduced with 64-lane wavefront shuffles, deterministic two-stage reductions.
 //
 // Replaces F.batch_norm(training=True) + activation reached from
 // /root/reference/models/model.py:451-458 (encoder), :462,468 (heads), :492
-// (decoder preprocess), :496-505 (decoder), :390-400 (discriminator).
+// (decoder preprocess), :496-505 (decoder), :390-400 (discriminator), and nn.BatchNorm*.eval() of the same modules.
+//
+// Every formula, walk and reduction is stated once, in the first section; the kernels below call them.  Order of the file:
+// shared helpers -- train forward (with the two passes the backward shares) -- train backward (one pass, team, the plan)
+// -- coefficients from slots -- eval -- the C entry points.
 #include <atomic>
 
 #include "common.hpp"
@@ -13,8 +18,11 @@
 
 namespace {
 
+// ---- shared helpers -------------------------------------------------------------------------------------------------
 constexpr int NT = 256;
 constexpr int NS_MAX = 64;   // slices per channel in the two-stage reductions
+
+bool act_ok(int act) { return act >= VG_ACT_NONE && act <= VG_ACT_LRELU; }
 
 __device__ __forceinline__ float act_fwd(float v, int act) {
   // compare + select with the NaN on the "keep v" side: a NaN stays a NaN, as in torch (v > 0 ? v : 0 made it 0, and a
@@ -23,10 +31,215 @@ __device__ __forceinline__ float act_fwd(float v, int act) {
   if (act == VG_ACT_LRELU) return v > 0.f ? v : 0.2f * v;
   return v;
 }
+
+// gy * act'(pre), in two forms that differ ONLY in a NaN pre-activation under ReLU / LeakyReLU: the train-mode form takes
+// it for "not positive" (the gradient is 0, or 0.2 g), the eval-mode form has no derivative there and returns the NaN.
+// (Train mode meets a NaN pre-activation only in a channel whose statistics are NaN, where c1 / c2 make gx NaN anyway;
+// with frozen coefficients nothing else would carry it.)  Making them agree changes results: not done here.
 __device__ __forceinline__ float act_grad(float pre, float g, int act) {
   if (act == VG_ACT_RELU) return pre > 0.f ? g : 0.f;
   if (act == VG_ACT_LRELU) return pre > 0.f ? g : 0.2f * g;
   return g;
+}
+__device__ __forceinline__ float act_slope_of(int act) { return act == VG_ACT_RELU ? 0.f : act == VG_ACT_LRELU ? 0.2f : 1.f; }
+// a multiplication by 1 or by the slope (a NaN gradient stays a NaN, as act_slope keeps a NaN value)
+__device__ __forceinline__ float eval_act_grad(float pre, float g, float slope) {
+  const float d = pre > 0.f ? 1.f : slope;
+  return (pre != pre && slope != 1.f) ? pre : g * d;
+}
+
+// Mean and biased variance of `count` values from their fp64 sums; cancellation can leave the difference below 0: clamped.
+__device__ __forceinline__ void mean_and_variance(double s1, double s2, double count, double& m, double& var) {
+  m = s1 / count;
+  var = s2 / count - m * m;
+  if (var < 0.0) var = 0.0;
+}
+
+// A channel's coefficients from its sums over `count` values (fp64): m, var (biased, clamped at 0) for the bound and the
+// running statistics; mu, invstd saved for the backward; scale = gamma * invstd, shift = beta - mu * scale.
+struct Coeffs {
+  double m, var;
+  float mu, invstd, scale, shift;
+};
+__device__ __forceinline__ Coeffs channel_coefficients(double s1, double s2, double count, float eps, float gamma,
+                                                       float beta) {
+  Coeffs k;
+  mean_and_variance(s1, s2, count, k.m, k.var);
+  k.mu = (float)k.m;
+  k.invstd = (float)(1.0 / sqrt(k.var + (double)eps));
+  k.scale = gamma * k.invstd;
+  k.shift = beta - k.mu * k.scale;
+  return k;
+}
+// ... and the running statistics they update (either may be NULL): the variance enters unbiased
+__device__ __forceinline__ void update_running(float* running_mean, float* running_var, int c, const Coeffs& k, double count,
+                                               float momentum) {
+  if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * k.mu;
+  if (running_var) {
+    const double unb = count > 1.0 ? k.var * count / (count - 1.0) : k.var;
+    running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unb;
+  }
+}
+
+// What a train-mode backward knows of its channel: the saved statistics and the forward's coefficients again.
+struct Saved {
+  float mu, is, sc, sh;
+};
+__device__ __forceinline__ Saved saved_coefficients(const float* mean, const float* invstd, const float* gamma,
+                                                    const float* beta, int c) {
+  Saved k;
+  k.mu = mean[c];
+  k.is = invstd[c];
+  k.sc = gamma[c] * k.is;
+  k.sh = beta[c] - k.mu * k.sc;
+  return k;
+}
+
+// The backward's terms: xhat; the two fp64 sums of g_pre (dbeta) and g_pre * xhat (dgamma) -- the product is rounded to
+// fp32 before it is added; gx = sc * (g_pre - c1 - xhat * c2), c1 = sum(g_pre) / N, c2 = sum(g_pre * xhat) / N.
+__device__ __forceinline__ float bn_xhat(float x, float mu, float is) { return (x - mu) * is; }
+__device__ __forceinline__ void add_grad_sums(double& s1, double& s2, float g, float x, float mu, float is) {
+  s1 += g;
+  s2 += (double)(g * bn_xhat(x, mu, is));
+}
+__device__ __forceinline__ float bn_gx(float g, float x, const Saved& k, float c1, float c2) {
+  return k.sc * (g - c1 - bn_xhat(x, k.mu, k.is) * c2);
+}
+
+// dbeta / dgamma of channel c (either may be NULL) from the two sums; accumulate: added to what is there (a layer used
+// twice before one backward: no add launch)
+__device__ __forceinline__ void store_param_grads(float* dgamma, float* dbeta, int c, double t1, double t2, int accumulate) {
+  if (dbeta) dbeta[c] = (float)t1 + (accumulate ? dbeta[c] : 0.f);
+  if (dgamma) dgamma[c] = (float)t2 + (accumulate ? dgamma[c] : 0.f);
+}
+
+// The two-stage partials part[c][ns][2] (fp64): a slice's pair, and a channel's pairs added in slice order.
+__device__ __forceinline__ void store_partial(double* part, int c, int ns, int k, double t1, double t2) {
+  part[((size_t)c * ns + k) * 2 + 0] = t1;
+  part[((size_t)c * ns + k) * 2 + 1] = t2;
+}
+__device__ __forceinline__ void sum_partials(const double* part, int c, int ns, double& s1, double& s2) {
+  for (int k = 0; k < ns; ++k) {               // fixed order
+    s1 += part[((size_t)c * ns + k) * 2];
+    s2 += part[((size_t)c * ns + k) * 2 + 1];
+  }
+}
+
+// Where virtual element v = b * HW + hw of channel c lies in NCHW; hw_shift >= 0: power-of-two planes, no division per load
+// (64-bit in the walk, 32-bit in the register tile).
+__device__ __forceinline__ int hw_shift_of(int HW) { return (HW & (HW - 1)) == 0 ? __builtin_ctz(HW) : -1; }
+template <typename I>
+__device__ __forceinline__ size_t plane_offset(I v, int C, int HW, int hw_shift, int c) {
+  const I b = hw_shift >= 0 ? (v >> hw_shift) : v / HW, hw = v - b * HW;
+  return ((size_t)b * C + c) * HW + hw;
+}
+
+// The plane walk: slice k of channel c is the virtual elements v = b * HW + hw in [k * per, (k + 1) * per) of its B planes;
+// a workgroup of NT threads goes through them 16 bytes (vec) or one element per lane at a time and calls one(x, gy) on
+// each (gy = 0 without HAS_G); with WRITE what it returns is stored to `out` at the same place.
+// vec: four elements of a plane per 16-byte load -- the host's decision (streams_vec below): HW % 4 == 0 AND every streamed
+// tensor on a 16-byte boundary.  A contiguous view at an odd offset takes the scalar loop; the one-pass backward, which
+// has no scalar form, is not launched for it.
+template <bool HAS_G, bool WRITE, typename F>
+__device__ __forceinline__ void plane_walk(const float* x, const float* gy, float* out, int B, int C, int HW, int c, int k,
+                                           long per, int vec, F one) {
+  const long total = (long)B * HW;
+  const long v0 = (long)k * per, v1 = min(v0 + per, total);
+  const int hw_shift = hw_shift_of(HW);
+  if (vec) {
+    for (long v = v0 + 4L * threadIdx.x; v < v1; v += 4L * NT) {
+      const size_t off = plane_offset(v, C, HW, hw_shift, c);
+      const float4 xv = *reinterpret_cast<const float4*>(x + off);
+      float4 gv = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (HAS_G) gv = *reinterpret_cast<const float4*>(gy + off);
+      if constexpr (WRITE) {
+        float4 o;
+        o.x = one(xv.x, gv.x);
+        o.y = one(xv.y, gv.y);
+        o.z = one(xv.z, gv.z);
+        o.w = one(xv.w, gv.w);
+        *reinterpret_cast<float4*>(out + off) = o;
+      } else {
+        one(xv.x, gv.x);
+        one(xv.y, gv.y);
+        one(xv.z, gv.z);
+        one(xv.w, gv.w);
+      }
+    }
+  } else {
+    for (long v = v0 + threadIdx.x; v < v1; v += NT) {
+      const size_t off = plane_offset(v, C, HW, hw_shift, c);
+      if constexpr (WRITE)
+        out[off] = one(x[off], HAS_G ? gy[off] : 0.f);
+      else
+        one(x[off], HAS_G ? gy[off] : 0.f);
+    }
+  }
+}
+
+// CH columns (channels) x KL lanes, thread = kl * CH + cl: every thread brings a pair of fp64 sums, the KL pairs of a
+// column are added through LDS in a fixed order and are valid, on return, in the threads with kl == 0.  The order is a
+// compile-time choice: serial 0 .. KL - 1, or (TREE) KL / 8 lanes that each add 8 consecutive ones, then those serially.
+// Every thread of the workgroup must call it.
+template <int CH, int KL, bool TREE>
+__device__ __forceinline__ void column_sums(double& s1, double& s2) {
+  __shared__ double r1[KL][CH], r2[KL][CH];
+  const int cl = threadIdx.x % CH, kl = threadIdx.x / CH;
+  r1[kl][cl] = s1;
+  r2[kl][cl] = s2;
+  __syncthreads();
+  constexpr int LAST = TREE ? KL / 8 : KL;
+  if constexpr (TREE) {
+    if (kl < LAST) {
+      s1 = 0.0;
+      s2 = 0.0;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        s1 += r1[kl * 8 + k][cl];
+        s2 += r2[kl * 8 + k][cl];
+      }
+    }
+    __syncthreads();
+    if (kl < LAST) {
+      r1[kl][cl] = s1;
+      r2[kl][cl] = s2;
+    }
+    __syncthreads();
+  }
+  if (kl == 0) {
+    s1 = 0.0;
+    s2 = 0.0;
+#pragma unroll
+    for (int k = 0; k < LAST; ++k) {
+      s1 += r1[k][cl];
+      s2 += r2[k][cl];
+    }
+  }
+}
+
+// The same over partial sums in memory: pair k of channel c at part[(c * cs + k * ks) * 2 + {0, 1}] -- a convolution's
+// fp32 statistics slots [slot][C][2] (cs = 1, ks = C; PAIR: read as one 8-byte load) or fp64 partials [c][n][2] (cs = n,
+// ks = 1).  Lane kl adds every KL-th pair of [k0, k1), then column_sums.
+template <int CH, int KL, bool TREE, bool PAIR, typename T>
+__device__ __forceinline__ void slot_sums(const T* part, long cs, long ks, int k0, int k1, int c, int C, double& s1,
+                                          double& s2) {
+  static_assert(!PAIR || sizeof(T) == sizeof(float), "8-byte pairs: fp32 slots");
+  const int kl = threadIdx.x / CH;
+  s1 = 0.0;
+  s2 = 0.0;
+  if (c < C)
+    for (int k = k0 + kl; k < k1; k += KL) {
+      const T* p = part + ((size_t)c * cs + (size_t)k * ks) * 2;
+      if constexpr (PAIR) {
+        const float2 v = *reinterpret_cast<const float2*>(p);
+        s1 += (double)v.x;
+        s2 += (double)v.y;
+      } else {
+        s1 += (double)p[0];
+        s2 += (double)p[1];
+      }
+    }
+  column_sums<CH, KL, TREE>(s1, s2);
 }
 
 struct Slicing {
@@ -48,7 +261,64 @@ Slicing make_slicing(int B, int C, int HW) {
   return s;
 }
 
-// MODE 0: sum x, sum x^2.   MODE 1: sum g_pre, sum g_pre*xhat (backward).   MODE 2: sum x only.
+// slices of the apply pass: >= 4096 elements per workgroup so that the per-workgroup prologue (partials
+// reduction + barrier) is amortised, but enough workgroups to fill the chip
+Slicing make_apply_slicing(int B, int C, int HW) {
+  const long total = (long)B * HW;
+  long ns = 4096 / C;
+  if (ns < 1) ns = 1;
+  long per = (total + ns - 1) / ns;
+  if (per < 4096) per = 4096;
+  per = (per + 3) / 4 * 4;
+  Slicing s;
+  s.per = per;
+  s.ns = (int)((total + per - 1) / per);
+  return s;
+}
+
+// The 16-byte loops are taken only when four elements of a plane share a load (HW % 4 == 0) and every tensor that is
+// streamed starts on a 16-byte boundary (pass nullptr for one that is not there); otherwise the scalar loops.
+int streams_vec(int HW, const void* a, const void* b = nullptr, const void* c = nullptr) {
+  return (HW & 3) == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
+}
+
+// Upper bound of max |act(x * sc + sh)| over a channel of n = count values, from its sums alone (act_amax of the
+// finalize kernels: what an fp16-plane convolution that applies sc / sh on load scales its input by).
+//   s2, m, var: the channel's sum of x^2, mean and clamped variance (s2 / n - m^2, >= 0) as the finalize kernel computed
+//   them in fp64; mu = (float)m, sc, beta: the coefficients it wrote (sh = beta - mu * sc).
+//   delta: relative error of the sums -- |S2 - T2| <= delta T2 and |S1 - T1| <= delta sum |x|, T1 / T2 the exact sums.
+// Samuelson: every x satisfies |x - T1/n| <= sigma sqrt(n - 1), sigma^2 = T2/n - (T1/n)^2 the EXACT variance.  `var` is
+// not that: when |mean| >> sigma, S2/n - m^2 cancels, the computed variance can be ~0 while sigma is not, 1/std then
+// goes up to 1/sqrt(eps), and a bound from `var` alone falls far below the data.  With q = S2/n:
+//   T2/n <= q / (1 - delta),  |m - T1/n| <= delta sum|x| / n <= delta sqrt(T2/n)          (Cauchy-Schwarz)
+//   sigma^2 - (q - m^2) = (T2/n - q) + (m - T1/n)(m + T1/n) <= (delta + delta (2 + delta)) T2/n <= 3.01 delta q
+// (delta <= 1e-3), plus fp64 rounding of q - m^2 (< 2^-50 q); so var_up = var + (3.01 delta + 2^-50) q >= sigma^2, and
+//   |x - mu| <= sqrt(var_up (n - 1)) + |T1/n - m| + |m - mu| <= sqrt(var_up (n - 1)) + 1.01 delta sqrt(q) + 2^-23 |m|.
+// |x sc + sh| <= |sc| |x - mu| + |beta| + (rounding of sh: <= 2^-23 (|beta| + |mu sc|)); the consumer's fmaf and the
+// final fp64 -> fp32 conversion round by 2^-24 each: (1 + 2^-20).  ReLU / LeakyReLU(0.2) only shrink magnitudes.
+// Where the sums are accurate (|mean| <= 8 sigma, the slots' delta) this stays within 0.1 % of the former
+// |gamma| sqrt(n) + |beta|; under cancellation it grows with sqrt(delta) |mean| instead of falling below the data.
+__device__ __forceinline__ float bn_act_bound(double s2, double m, double var, double count, double delta, float mu,
+                                              float sc, float beta) {
+  const double q = s2 / count;
+  const double var_up = var + (3.01 * delta + 0x1p-50) * q;
+  const double dev = sqrt(var_up * fmax(count - 1.0, 0.0)) + 1.01 * delta * sqrt(q) + 0x1p-23 * fabs(m);
+  const double asc = fabs((double)sc), ab = fabs((double)beta);
+  const double b = asc * dev + ab + 0x1p-23 * (ab + asc * fabs((double)mu));
+  return (float)(b * (1.0 + 0x1p-20));
+}
+
+// delta of bn_act_bound for sums made of fp32 statistics slots (each an fp32 sum in which a term goes through at most
+// D = VG_STATS_SLOT_DEPTH roundings: within gamma_D <= (D + 0.01) 2^-24 of the exact sum, relative to the sum of
+// magnitudes -- for the squares that is T2 itself) added in fp64 over nslots slots (and NS_MAX partials):
+// (nslots + 2 NS_MAX) 2^-53 more
+double slot_sums_delta(int nslots) { return (VG_STATS_SLOT_DEPTH + 1) * 0x1p-24 + (nslots + 2.0 * NS_MAX) * 0x1p-53; }
+
+// ... and for fp64 sums of fp32 values (bn_partial_kernel<0>: x^2 is exact in fp64): count + partials additions
+double fp64_sums_delta(double count) { return (count + 2.0 * NS_MAX + NT) * 0x1p-53; }
+
+// ---- train forward, and the two passes that the backward shares with it ---------------------------------------------
+// First pass.  MODE 0: sum x, sum x^2.   MODE 1: sum g_pre, sum g_pre*xhat (backward).   MODE 2: sum x only.
 template <int MODE>
 __global__ __launch_bounds__(NT) void bn_partial_kernel(const float* __restrict__ x, const float* __restrict__ gy,
                                                         const float* __restrict__ gamma,
@@ -56,67 +326,32 @@ __global__ __launch_bounds__(NT) void bn_partial_kernel(const float* __restrict_
                                                         const float* __restrict__ mean,
                                                         const float* __restrict__ invstd, double* __restrict__ part,
                                                         int B, int C, int HW, long per, int ns, int act, int vec) {
-  // vec: four elements of a plane per 16-byte load -- the host's decision (streams_vec below): HW % 4 == 0 AND every
-  // streamed tensor on a 16-byte boundary.  A contiguous view at an odd offset takes the scalar loop, here and in
-  // bn_apply_kernel; the one-pass backward, which has no scalar form, is not launched for it
   __shared__ double red[NT / 64];
   const int c = blockIdx.x, k = blockIdx.y;
-  const long total = (long)B * HW;
-  const long v0 = (long)k * per, v1 = min(v0 + per, total);
-  const int hw_shift = (HW & (HW - 1)) == 0 ? __builtin_ctz(HW) : -1;      // power-of-two planes: no 64-bit division per load
   double s1 = 0.0, s2 = 0.0;
-  float mu = 0.f, is = 0.f, sc = 0.f, sh = 0.f;
-  if (MODE == 1) {
-    mu = mean[c];
-    is = invstd[c];
-    sc = gamma[c] * is;
-    sh = beta[c] - mu * sc;
-  }
-  auto accum = [&](float xv, float gv) {
+  Saved co = {0.f, 0.f, 0.f, 0.f};
+  if (MODE == 1) co = saved_coefficients(mean, invstd, gamma, beta, c);
+  plane_walk<MODE == 1, false>(x, gy, nullptr, B, C, HW, c, k, per, vec, [&](float xv, float gv) {
     if (MODE == 0) {
       s1 += xv;
       s2 += (double)xv * xv;
     } else if (MODE == 2) {
       s1 += xv;
     } else {
-      const float g = act_grad(fmaf(xv, sc, sh), gv, act);
-      s1 += g;
-      s2 += (double)(g * ((xv - mu) * is));
+      add_grad_sums(s1, s2, act_grad(fmaf(xv, co.sc, co.sh), gv, act), xv, co.mu, co.is);
     }
-  };
-  if (vec) {
-    for (long v = v0 + 4L * threadIdx.x; v < v1; v += 4L * NT) {
-      const long b = hw_shift >= 0 ? (v >> hw_shift) : v / HW, hw = v - b * HW;
-      const size_t off = ((size_t)b * C + c) * HW + hw;
-      const float4 xv = *reinterpret_cast<const float4*>(x + off);
-      float4 gv = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (MODE == 1) gv = *reinterpret_cast<const float4*>(gy + off);
-      accum(xv.x, gv.x);
-      accum(xv.y, gv.y);
-      accum(xv.z, gv.z);
-      accum(xv.w, gv.w);
-    }
-  } else {
-    for (long v = v0 + threadIdx.x; v < v1; v += NT) {
-      const long b = hw_shift >= 0 ? (v >> hw_shift) : v / HW, hw = v - b * HW;
-      const size_t off = ((size_t)b * C + c) * HW + hw;
-      accum(x[off], MODE == 1 ? gy[off] : 0.f);
-    }
-  }
+  });
   const double t1 = block_sum<NT>(s1, red);
   const double t2 = block_sum<NT>(s2, red);
-  if (threadIdx.x == 0) {
-    part[((size_t)c * ns + k) * 2 + 0] = t1;
-    part[((size_t)c * ns + k) * 2 + 1] = t2;
-  }
+  if (threadIdx.x == 0) store_partial(part, c, ns, k, t1, t2);
 }
 
 __global__ __launch_bounds__(NT) void channel_sum_finalize_kernel(const double* __restrict__ part, int ns, int C,
                                                                   float* __restrict__ out) {
   const int c = blockIdx.x * NT + threadIdx.x;
   if (c >= C) return;
-  double s1 = 0.0;
-  for (int k = 0; k < ns; ++k) s1 += part[((size_t)c * ns + k) * 2];
+  double s1 = 0.0, s2 = 0.0;
+  sum_partials(part, c, ns, s1, s2);
   out[c] = (float)s1;
 }
 
@@ -125,8 +360,7 @@ __global__ __launch_bounds__(NT) void channel_sum_finalize_kernel(const double* 
 // (<= 64) fp64 partial sums in a fixed order -- no separate finalize launch, no coefficient
 // table, coefficients live in registers -- and streams its slice as float4.  The slice-0
 // workgroup of a channel also writes the saved / running statistics (FWD) or dgamma / dbeta (BWD).
-//   FWD: y  = act(x*sc + sh)            sc = gamma*invstd, sh = beta - mean*sc
-//   BWD: gx = sc * (g_pre - c1 - xhat*c2),  c1 = sum(g_pre)/N, c2 = sum(g_pre*xhat)/N
+//   FWD: y  = act(x*sc + sh)            BWD: gx = bn_gx(g_pre, x)
 template <bool BWD>
 __global__ __launch_bounds__(NT) void bn_apply_kernel(const float* __restrict__ x, const float* __restrict__ gy,
                                                       const double* __restrict__ part, int ns,
@@ -137,12 +371,10 @@ __global__ __launch_bounds__(NT) void bn_apply_kernel(const float* __restrict__ 
                                                       float* __restrict__ running_var, float* __restrict__ dgamma,
                                                       float* __restrict__ dbeta, float* __restrict__ out, int B,
                                                       int C, int HW, long per, float eps, float momentum, int act,
-                                                      unsigned* __restrict__ out_amax, int vec) {
-  // vec: as in bn_partial_kernel (x, gy and out are streamed)
+                                                      int accp, unsigned* __restrict__ out_amax, int vec) {
+  // vec: x, gy and out are streamed
   // out_amax (backward, may be NULL): max |gx| is added to it (common.hpp block_amax_atomic) -- the bound the fp16-plane
   // convolutions that consume gx scale it by, emitted here instead of by a pass of its own
-  const bool accp = (act & 0x100) != 0;        // backward: dgamma / dbeta are accumulated into (bit 8 of `act`)
-  act &= 0xff;
   // `per`: elements of this channel per workgroup of THIS pass (independent of the partial pass)
   __shared__ float s_co[4];
   // slices in descending order: the sums pass before this one went through the channel's slices in ascending order (same
@@ -159,82 +391,181 @@ __global__ __launch_bounds__(NT) void bn_apply_kernel(const float* __restrict__ 
     s2 = wave_allsum(s2);
     if (threadIdx.x == 0) {
       if (!BWD) {
-        const double m = s1 / count;
-        double var = s2 / count - m * m;
-        if (var < 0.0) var = 0.0;
-        const float mu = (float)m, is = (float)(1.0 / sqrt(var + (double)eps));
-        const float sc = gamma[c] * is;
-        s_co[0] = sc;
-        s_co[1] = beta[c] - mu * sc;
+        const Coeffs co = channel_coefficients(s1, s2, count, eps, gamma[c], beta[c]);
+        s_co[0] = co.scale;
+        s_co[1] = co.shift;
         if (k == 0) {
-          mean_io[c] = mu;
-          invstd_io[c] = is;
-          if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mu;
-          if (running_var) {
-            const double unb = count > 1.0 ? var * count / (count - 1.0) : var;
-            running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unb;
-          }
+          mean_io[c] = co.mu;
+          invstd_io[c] = co.invstd;
+          update_running(running_mean, running_var, c, co, count, momentum);
         }
       } else {
-        const float mu = mean_io[c], is = invstd_io[c], sc = gamma[c] * is;
-        s_co[0] = sc;
-        s_co[1] = beta[c] - mu * sc;
+        const Saved co = saved_coefficients(mean_io, invstd_io, gamma, beta, c);
+        s_co[0] = co.sc;
+        s_co[1] = co.sh;
         s_co[2] = (float)(s1 / count);
         s_co[3] = (float)(s2 / count);
-        if (k == 0) {       // accp: added to what is there (a layer used twice before one backward: no add launch)
-          if (dbeta) dbeta[c] = (float)s1 + (accp ? dbeta[c] : 0.f);
-          if (dgamma) dgamma[c] = (float)s2 + (accp ? dgamma[c] : 0.f);
-        }
+        if (k == 0) store_param_grads(dgamma, dbeta, c, s1, s2, accp);
       }
     }
   }
   __syncthreads();
-  const float sc = s_co[0], sh = s_co[1];
-  float c1 = 0.f, c2 = 0.f, mu = 0.f, is = 0.f;
+  Saved co = {0.f, 0.f, s_co[0], s_co[1]};
+  float c1 = 0.f, c2 = 0.f;
   if (BWD) {
     c1 = s_co[2];
     c2 = s_co[3];
-    mu = mean_io[c];
-    is = invstd_io[c];
+    co.mu = mean_io[c];
+    co.is = invstd_io[c];
   }
   unsigned am = 0;
-  auto one = [&](float xv, float gv) -> float {
-    const float pre = fmaf(xv, sc, sh);
-    if (!BWD) {
-      const float r = act_fwd(pre, act);
-      am = max(am, abs_bits(r));
-      return r;
-    }
-    const float g = act_grad(pre, gv, act);
-    const float r = sc * (g - c1 - ((xv - mu) * is) * c2);
+  plane_walk<BWD, true>(x, gy, out, B, C, HW, c, k, per, vec, [&](float xv, float gv) -> float {
+    const float pre = fmaf(xv, co.sc, co.sh);
+    const float r = BWD ? bn_gx(act_grad(pre, gv, act), xv, co, c1, c2) : act_fwd(pre, act);
     am = max(am, abs_bits(r));
     return r;
-  };
-  const long total = (long)B * HW;
-  const long v0 = (long)k * per, v1 = min(v0 + per, total);
-  const int hw_shift = (HW & (HW - 1)) == 0 ? __builtin_ctz(HW) : -1;
-  if (vec) {
-    for (long v = v0 + 4L * threadIdx.x; v < v1; v += 4L * NT) {
-      const long b = hw_shift >= 0 ? (v >> hw_shift) : v / HW, hw = v - b * HW;
-      const size_t off = ((size_t)b * C + c) * HW + hw;
-      const float4 xv = *reinterpret_cast<const float4*>(x + off);
-      float4 gv = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (BWD) gv = *reinterpret_cast<const float4*>(gy + off);
-      float4 o;
-      o.x = one(xv.x, gv.x);
-      o.y = one(xv.y, gv.y);
-      o.z = one(xv.z, gv.z);
-      o.w = one(xv.w, gv.w);
-      *reinterpret_cast<float4*>(out + off) = o;
+  });
+  if (out_amax) block_amax_atomic<NT>(am, out_amax);      // wave-uniform condition
+}
+
+// BatchNorm1d: x [B][C].  A workgroup owns 32 consecutive channels (128-byte coalesced rows);
+// its 8 row-slices (threads 32*s .. 32*s+31) each sum every 8th batch row in fp64 and combine
+// through LDS in a fixed order (column_sums); the normalise / gradient pass re-reads the rows from L2.
+constexpr int B1_CH = 32, B1_SL = 8;
+
+__global__ __launch_bounds__(NT) void bn1d_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                      const float* __restrict__ beta, float* __restrict__ y,
+                                                      float* __restrict__ running_mean,
+                                                      float* __restrict__ running_var, float* __restrict__ save_mean,
+                                                      float* __restrict__ save_invstd, int B, int C, float eps,
+                                                      float momentum, int act) {
+  __shared__ float s_sc[B1_CH], s_sh[B1_CH];
+  const int cl = threadIdx.x % B1_CH, sl = threadIdx.x / B1_CH;
+  const int c = blockIdx.x * B1_CH + cl;
+  const bool cok = c < C;
+  double s1 = 0.0, s2 = 0.0;
+  if (cok)
+    for (int b = sl; b < B; b += B1_SL) {
+      const float v = x[(size_t)b * C + c];
+      s1 += v;
+      s2 += (double)v * v;
     }
-  } else {
-    for (long v = v0 + threadIdx.x; v < v1; v += NT) {
-      const long b = hw_shift >= 0 ? (v >> hw_shift) : v / HW, hw = v - b * HW;
-      const size_t off = ((size_t)b * C + c) * HW + hw;
-      out[off] = one(x[off], BWD ? gy[off] : 0.f);
+  column_sums<B1_CH, B1_SL, false>(s1, s2);
+  if (sl == 0 && cok) {
+    const Coeffs co = channel_coefficients(s1, s2, (double)B, eps, gamma[c], beta[c]);
+    save_mean[c] = co.mu;
+    save_invstd[c] = co.invstd;
+    update_running(running_mean, running_var, c, co, (double)B, momentum);
+    s_sc[cl] = co.scale;
+    s_sh[cl] = co.shift;
+  }
+  __syncthreads();
+  if (cok) {
+    const float sc = s_sc[cl], sh = s_sh[cl];
+    for (int b = sl; b < B; b += B1_SL) {
+      const size_t o = (size_t)b * C + c;
+      y[o] = act_fwd(fmaf(x[o], sc, sh), act);
     }
   }
-  if (out_amax) block_amax_atomic<NT>(am, out_amax);      // wave-uniform condition
+}
+
+constexpr int AA_U = 4;
+// y = act(x * scale[c] + shift[c]): the normalise pass with given coefficients (layers whose consumer cannot apply
+// them while it loads)
+// hw4_shift >= 0: H*W/4 is a power of two (every layer of the reference) -- the channel is a shift and a 32-bit remainder;
+// the 64-bit division per thread that this replaces made the pass run at 0.8 TB/s (20 us for 16 MB).
+__global__ __launch_bounds__(NT) void affine_act_kernel(const float* __restrict__ x, const float* __restrict__ scale,
+                                                        const float* __restrict__ shift, float* __restrict__ y, int C,
+                                                        int HW, size_t n4, int act, int hw4_shift,
+                                                        unsigned* __restrict__ y_amax) {
+  // A workgroup walks chunks of NT * AA_U units of 16 bytes, grid-stride (<= 2048 workgroups: one maximum and one atomic
+  // per workgroup, not per 4 KB); within a chunk a thread's AA_U units are NT apart (contiguous per round, all loads of
+  // a chunk in flight together).
+  unsigned am = 0;
+  for (size_t base = (size_t)blockIdx.x * (NT * AA_U) + threadIdx.x; base < n4 + threadIdx.x;
+       base += (size_t)gridDim.x * (NT * AA_U)) {
+    float4 v[AA_U];
+    float sc[AA_U], sh[AA_U];
+#pragma unroll
+    for (int u = 0; u < AA_U; ++u) {
+      const size_t i0 = base + (size_t)u * NT;
+      const size_t i = i0 < n4 ? i0 : n4 - 1;               // past the end: the last unit again (not stored)
+      // HW % 4 == 0: the four elements share a channel
+      const int c = hw4_shift >= 0 ? (int)((unsigned)(i >> hw4_shift) % (unsigned)C) : (int)(((4 * i) / HW) % C);
+      sc[u] = scale[c];
+      sh[u] = shift[c];
+      v[u] = *reinterpret_cast<const float4*>(x + 4 * i);
+    }
+#pragma unroll
+    for (int u = 0; u < AA_U; ++u) {
+      const size_t i0 = base + (size_t)u * NT;
+      float4 o;
+      o.x = act_fwd(fmaf(v[u].x, sc[u], sh[u]), act);
+      o.y = act_fwd(fmaf(v[u].y, sc[u], sh[u]), act);
+      o.z = act_fwd(fmaf(v[u].z, sc[u], sh[u]), act);
+      o.w = act_fwd(fmaf(v[u].w, sc[u], sh[u]), act);
+      if (i0 < n4) *reinterpret_cast<float4*>(y + 4 * i0) = o;
+      am = max(max(am, abs_bits(o.x)), max(max(abs_bits(o.y), abs_bits(o.z)), abs_bits(o.w)));
+    }
+  }
+  if (y_amax) block_amax_atomic<NT>(am, y_amax);      // max |y| for an fp16-plane consumer (common.hpp)
+}
+
+// the same for H*W not a multiple of 4 (odd image sizes): one element per lane
+__global__ __launch_bounds__(NT) void affine_act_scalar_kernel(const float* __restrict__ x, const float* __restrict__ scale,
+                                                               const float* __restrict__ shift, float* __restrict__ y,
+                                                               int C, int HW, size_t n, int act,
+                                                               unsigned* __restrict__ y_amax) {
+  const size_t e0 = (size_t)blockIdx.x * NT + threadIdx.x;
+  const size_t e = e0 < n ? e0 : n - 1;
+  const int c = (int)((e / HW) % C);
+  const float r = act_fwd(fmaf(x[e], scale[c], shift[c]), act);
+  if (e0 < n) y[e] = r;
+  if (y_amax) block_amax_atomic<NT>(abs_bits(r), y_amax);
+}
+
+// ---- train backward --------------------------------------------------------------------------------------------------
+// Two passes: bn_partial_kernel<1> + bn_apply_kernel<true> above.  BatchNorm1d: one kernel, the geometry of bn1d_fwd_kernel.
+__global__ __launch_bounds__(NT) void bn1d_bwd_kernel(const float* __restrict__ gy, const float* __restrict__ x,
+                                                      const float* __restrict__ gamma,
+                                                      const float* __restrict__ beta,
+                                                      const float* __restrict__ mean,
+                                                      const float* __restrict__ invstd, float* __restrict__ gx,
+                                                      float* __restrict__ dgamma, float* __restrict__ dbeta, int B,
+                                                      int C, int act, int accp, unsigned* __restrict__ gx_amax) {
+  __shared__ float s_c1[B1_CH], s_c2[B1_CH];
+  const int cl = threadIdx.x % B1_CH, sl = threadIdx.x / B1_CH;
+  const int c = blockIdx.x * B1_CH + cl;
+  const bool cok = c < C;
+  Saved co = {0.f, 0.f, 0.f, 0.f};
+  double s1 = 0.0, s2 = 0.0;
+  if (cok) {
+    co = saved_coefficients(mean, invstd, gamma, beta, c);
+    for (int b = sl; b < B; b += B1_SL) {
+      const size_t o = (size_t)b * C + c;
+      const float xv = x[o];
+      add_grad_sums(s1, s2, act_grad(fmaf(xv, co.sc, co.sh), gy[o], act), xv, co.mu, co.is);
+    }
+  }
+  column_sums<B1_CH, B1_SL, false>(s1, s2);
+  if (sl == 0 && cok) {
+    store_param_grads(dgamma, dbeta, c, s1, s2, accp);
+    s_c1[cl] = (float)(s1 / B);
+    s_c2[cl] = (float)(s2 / B);
+  }
+  __syncthreads();
+  unsigned am = 0;
+  if (cok) {
+    const float c1 = s_c1[cl], c2 = s_c2[cl];
+    for (int b = sl; b < B; b += B1_SL) {
+      const size_t o = (size_t)b * C + c;
+      const float xv = x[o];
+      const float r = bn_gx(act_grad(fmaf(xv, co.sc, co.sh), gy[o], act), xv, co, c1, c2);
+      am = max(am, abs_bits(r));
+      gx[o] = r;
+    }
+  }
+  if (gx_amax) block_amax_atomic<NT>(am, gx_amax);
 }
 
 // Backward in ONE pass for channels that fit a workgroup's registers (B * HW <= ONE_NT * 4 * NV elements: the 16 x 16 and
@@ -244,6 +575,73 @@ __global__ __launch_bounds__(NT) void bn_apply_kernel(const float* __restrict__ 
 // bn_apply_kernel<true>; only the order of the fp64 sums differs.
 constexpr int ONE_NT = 1024;
 
+// The register tile of a 1024-thread workgroup: the ONE_NT * 4 * NV virtual elements of channel c from v_base on, float4 j
+// of a lane at v_base + (j * ONE_NT + lane) * 4.  Loads are unconditional at a clamped place; what lies past `total` is
+// masked out of the sums and not written.
+struct TileGeom {
+  int C, HW, hw_shift, total, v_base;
+  __device__ __forceinline__ TileGeom(int B, int C_, int HW_, int v_base_)
+      : C(C_), HW(HW_), hw_shift(hw_shift_of(HW_)), total(B * HW_), v_base(v_base_) {}
+  __device__ __forceinline__ bool live(int j) const { return v_base + (j * ONE_NT + (int)threadIdx.x) * 4 < total; }
+  __device__ __forceinline__ size_t offset_of(int c, int j) const {
+    const int v = v_base + (j * ONE_NT + (int)threadIdx.x) * 4;
+    return plane_offset(min(v, total - 4), C, HW, hw_shift, c);      // clamped, unconditional; masked below
+  }
+};
+// KEEP_OFF: the offsets of the loads are kept for the stores (2 * NV registers) instead of being computed again
+template <int NV, bool KEEP_OFF>
+struct BwdTile {
+  float4 xv[NV], gv[NV];
+  size_t off[KEEP_OFF ? NV : 1];
+
+  __device__ __forceinline__ void load(const float* x, const float* gy, const TileGeom& t, int c) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      const size_t o = t.offset_of(c, j);
+      if constexpr (KEEP_OFF) off[j] = o;
+      xv[j] = *reinterpret_cast<const float4*>(x + o);
+      gv[j] = *reinterpret_cast<const float4*>(gy + o);
+    }
+  }
+  // g_pre replaces gy; its two sums, in register order
+  __device__ __forceinline__ void form_g_pre(const TileGeom& t, const Saved& co, int act, double& s1, double& s2) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      const bool ok = t.live(j);
+      float* xp = reinterpret_cast<float*>(&xv[j]);
+      float* gp = reinterpret_cast<float*>(&gv[j]);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float g = ok ? act_grad(fmaf(xp[e], co.sc, co.sh), gp[e], act) : 0.f;
+        gp[e] = g;
+        add_grad_sums(s1, s2, g, xp[e], co.mu, co.is);
+      }
+    }
+  }
+  // gx from the registers; max |gx| joins `am`
+  __device__ __forceinline__ void write_gx(float* gx, const TileGeom& t, int c, const Saved& co, float c1, float c2,
+                                           unsigned& am) const {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      if (!t.live(j)) continue;
+      const float* xp = reinterpret_cast<const float*>(&xv[j]);
+      const float* gp = reinterpret_cast<const float*>(&gv[j]);
+      float4 o;
+      o.x = bn_gx(gp[0], xp[0], co, c1, c2);
+      o.y = bn_gx(gp[1], xp[1], co, c1, c2);
+      o.z = bn_gx(gp[2], xp[2], co, c1, c2);
+      o.w = bn_gx(gp[3], xp[3], co, c1, c2);
+      am = max(max(am, abs_bits(o.x)), max(max(abs_bits(o.y), abs_bits(o.z)), abs_bits(o.w)));
+      size_t o_off;
+      if constexpr (KEEP_OFF)
+        o_off = off[j];
+      else
+        o_off = t.offset_of(c, j);
+      *reinterpret_cast<float4*>(gx + o_off) = o;
+    }
+  }
+};
+
 template <int NV>
 __global__ __launch_bounds__(ONE_NT) void bn_bwd_onepass_kernel(const float* __restrict__ x, const float* __restrict__ gy,
                                                                 const float* __restrict__ gamma,
@@ -251,73 +649,36 @@ __global__ __launch_bounds__(ONE_NT) void bn_bwd_onepass_kernel(const float* __r
                                                                 const float* __restrict__ mean,
                                                                 const float* __restrict__ invstd, float* __restrict__ gx,
                                                                 float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                                int B, int C, int HW, int act,
+                                                                int B, int C, int HW, int act, int accp,
                                                                 unsigned* __restrict__ gx_amax) {
   __shared__ double red[ONE_NT / 64];
   __shared__ float s_c[2];
-  const bool accp = (act & 0x100) != 0;
-  act &= 0xff;
   const int c = blockIdx.x;
-  const int total = B * HW;
-  const int hw_shift = (HW & (HW - 1)) == 0 ? __builtin_ctz(HW) : -1;
-  const float mu = mean[c], is = invstd[c], sc = gamma[c] * is, sh = beta[c] - mu * sc;
-  float4 xv[NV], gv[NV];
-  size_t off[NV];
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    const int v = (j * ONE_NT + (int)threadIdx.x) * 4;
-    const int vc = min(v, total - 4);                       // clamped, unconditional; masked below
-    const int b = hw_shift >= 0 ? (vc >> hw_shift) : vc / HW, hw = vc - b * HW;
-    off[j] = ((size_t)b * C + c) * HW + hw;
-    xv[j] = *reinterpret_cast<const float4*>(x + off[j]);
-    gv[j] = *reinterpret_cast<const float4*>(gy + off[j]);
-  }
+  const TileGeom geom(B, C, HW, 0);
+  const Saved co = saved_coefficients(mean, invstd, gamma, beta, c);
+  BwdTile<NV, true> tile;
+  tile.load(x, gy, geom, c);
   double s1 = 0.0, s2 = 0.0;
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    const bool ok = (j * ONE_NT + (int)threadIdx.x) * 4 < total;
-    float* xp = reinterpret_cast<float*>(&xv[j]);
-    float* gp = reinterpret_cast<float*>(&gv[j]);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float g = ok ? act_grad(fmaf(xp[e], sc, sh), gp[e], act) : 0.f;
-      gp[e] = g;                                            // g_pre replaces gy
-      s1 += g;
-      s2 += (double)(g * ((xp[e] - mu) * is));
-    }
-  }
+  tile.form_g_pre(geom, co, act, s1, s2);
   const double t1 = block_sum<ONE_NT>(s1, red);
   const double t2 = block_sum<ONE_NT>(s2, red);
   if (threadIdx.x == 0) {
-    const double count = (double)total;
+    const double count = (double)geom.total;
     s_c[0] = (float)(t1 / count);
     s_c[1] = (float)(t2 / count);
-    if (dbeta) dbeta[c] = (float)t1 + (accp ? dbeta[c] : 0.f);
-    if (dgamma) dgamma[c] = (float)t2 + (accp ? dgamma[c] : 0.f);
+    store_param_grads(dgamma, dbeta, c, t1, t2, accp);
   }
   __syncthreads();
   const float c1 = s_c[0], c2 = s_c[1];
   unsigned am = 0;
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    if ((j * ONE_NT + (int)threadIdx.x) * 4 >= total) continue;
-    const float* xp = reinterpret_cast<const float*>(&xv[j]);
-    const float* gp = reinterpret_cast<const float*>(&gv[j]);
-    float4 o;
-    o.x = sc * (gp[0] - c1 - ((xp[0] - mu) * is) * c2);
-    o.y = sc * (gp[1] - c1 - ((xp[1] - mu) * is) * c2);
-    o.z = sc * (gp[2] - c1 - ((xp[2] - mu) * is) * c2);
-    o.w = sc * (gp[3] - c1 - ((xp[3] - mu) * is) * c2);
-    am = max(max(am, abs_bits(o.x)), max(max(abs_bits(o.y), abs_bits(o.z)), abs_bits(o.w)));
-    *reinterpret_cast<float4*>(gx + off[j]) = o;
-  }
+  tile.write_gx(gx, geom, c, co, c1, c2, am);
   if (gx_amax) block_amax_atomic<ONE_NT>(am, gx_amax);      // max |gx| for the fp16-plane consumers (bn_apply_kernel)
 }
 
 // The one pass for channels LARGER than a workgroup's registers (the 32 x 32 and 64 x 64 layers at B = 128: 131 072 and
 // 524 288 elements per channel): a TEAM of T workgroups owns a channel.  Member j holds the virtual elements
-// [j * cap, (j + 1) * cap), cap = ONE_NT * 4 * NV, exactly as the kernel above holds a whole channel (clamped unconditional
-// loads, mask, index paths), forms g_pre in place and its two fp64 sums, publishes them, collects the T pairs of its team,
+// [j * cap, (j + 1) * cap), cap = ONE_NT * 4 * NV, exactly as the kernel above holds a whole channel (the same tile),
+// forms g_pre in place and its two fp64 sums, publishes them, collects the T pairs of its team,
 // adds them in member order 0 .. T - 1 -- every member gets the same c1, c2 bit for bit, whatever the timing -- and writes
 // its gx from registers.  Member 0 writes dgamma / dbeta.
 //
@@ -358,52 +719,27 @@ __global__ __launch_bounds__(ONE_NT) void bn_bwd_team_kernel(const float* __rest
                                                              const float* __restrict__ mean,
                                                              const float* __restrict__ invstd, float* __restrict__ gx,
                                                              float* __restrict__ dgamma, float* __restrict__ dbeta, int B,
-                                                             int C, int HW, int act, unsigned* __restrict__ gx_amax, int T,
-                                                             int teams, unsigned long long* xch) {
+                                                             int C, int HW, int act, int accp,
+                                                             unsigned* __restrict__ gx_amax, int T, int teams,
+                                                             unsigned long long* xch) {
   __shared__ double red[ONE_NT / 64];
   __shared__ float s_c[2];
   __shared__ int s_failed;
-  const bool accp = (act & 0x100) != 0;
-  act &= 0xff;
   const int team = blockIdx.x / T, member = blockIdx.x - team * T;
-  const int total = B * HW;
-  const int hw_shift = (HW & (HW - 1)) == 0 ? __builtin_ctz(HW) : -1;
-  const int v_base = member * (ONE_NT * 4 * NV);
+  const TileGeom geom(B, C, HW, member * (ONE_NT * 4 * NV));
+  const int total = geom.total;
   gu32* status = (gu32*)xch;
   gu64* sets = (gu64*)xch + TEAM_HDR / sizeof(unsigned long long) + (size_t)team * 2 * T * 4;
   unsigned am = 0;
   bool failed = false;
   int round = 0;
   for (int c = team; c < C; c += teams, ++round) {
-    const float mu = mean[c], is = invstd[c], sc = gamma[c] * is, sh = beta[c] - mu * sc;
-    float4 xv[NV], gv[NV];
+    const Saved co = saved_coefficients(mean, invstd, gamma, beta, c);
     // the offsets are computed again for the stores: 2 * NV registers of them would not fit next to the 8 * NV of data
-    auto offset_of = [&](int j) -> size_t {
-      const int v = v_base + (j * ONE_NT + (int)threadIdx.x) * 4;
-      const int vc = min(v, total - 4);                     // clamped, unconditional; masked below
-      const int b = hw_shift >= 0 ? (vc >> hw_shift) : vc / HW, hw = vc - b * HW;
-      return ((size_t)b * C + c) * HW + hw;
-    };
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-      const size_t off = offset_of(j);
-      xv[j] = *reinterpret_cast<const float4*>(x + off);
-      gv[j] = *reinterpret_cast<const float4*>(gy + off);
-    }
+    BwdTile<NV, false> tile;
+    tile.load(x, gy, geom, c);
     double s1 = 0.0, s2 = 0.0;
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-      const bool ok = v_base + (j * ONE_NT + (int)threadIdx.x) * 4 < total;
-      float* xp = reinterpret_cast<float*>(&xv[j]);
-      float* gp = reinterpret_cast<float*>(&gv[j]);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float g = ok ? act_grad(fmaf(xp[e], sc, sh), gp[e], act) : 0.f;
-        gp[e] = g;                                          // g_pre replaces gy
-        s1 += g;
-        s2 += (double)(g * ((xp[e] - mu) * is));
-      }
-    }
+    tile.form_g_pre(geom, co, act, s1, s2);
     const double t1 = block_sum<ONE_NT>(s1, red);
     const double t2 = block_sum<ONE_NT>(s2, red);
     if (threadIdx.x < 64) {                                 // wavefront 0: publish, sweep, add in member order
@@ -453,169 +789,15 @@ __global__ __launch_bounds__(ONE_NT) void bn_bwd_team_kernel(const float* __rest
         s_c[0] = (float)(a1 / count);
         s_c[1] = (float)(a2 / count);
         s_failed = !ok;
-        if (member == 0) {
-          if (dbeta) dbeta[c] = (float)a1 + (accp ? dbeta[c] : 0.f);
-          if (dgamma) dgamma[c] = (float)a2 + (accp ? dgamma[c] : 0.f);
-        }
+        if (member == 0) store_param_grads(dgamma, dbeta, c, a1, a2, accp);
       }
     }
     __syncthreads();
     const float c1 = s_c[0], c2 = s_c[1];
     failed = s_failed != 0;
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-      if (v_base + (j * ONE_NT + (int)threadIdx.x) * 4 >= total) continue;
-      const float* xp = reinterpret_cast<const float*>(&xv[j]);
-      const float* gp = reinterpret_cast<const float*>(&gv[j]);
-      float4 o;
-      o.x = sc * (gp[0] - c1 - ((xp[0] - mu) * is) * c2);
-      o.y = sc * (gp[1] - c1 - ((xp[1] - mu) * is) * c2);
-      o.z = sc * (gp[2] - c1 - ((xp[2] - mu) * is) * c2);
-      o.w = sc * (gp[3] - c1 - ((xp[3] - mu) * is) * c2);
-      am = max(max(am, abs_bits(o.x)), max(max(abs_bits(o.y), abs_bits(o.z)), abs_bits(o.w)));
-      *reinterpret_cast<float4*>(gx + offset_of(j)) = o;
-    }
+    tile.write_gx(gx, geom, c, co, c1, c2, am);
   }
   if (gx_amax) block_amax_atomic<ONE_NT>(am, gx_amax);      // one atomic per workgroup, after its last round
-}
-
-// BatchNorm1d: x [B][C].  A workgroup owns 32 consecutive channels (128-byte coalesced rows);
-// its 8 row-slices (threads 32*s .. 32*s+31) each sum every 8th batch row in fp64 and combine
-// through LDS in a fixed order; the normalise / gradient pass re-reads the rows from L2.
-constexpr int B1_CH = 32, B1_SL = 8;
-
-__global__ __launch_bounds__(NT) void bn1d_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                      const float* __restrict__ beta, float* __restrict__ y,
-                                                      float* __restrict__ running_mean,
-                                                      float* __restrict__ running_var, float* __restrict__ save_mean,
-                                                      float* __restrict__ save_invstd, int B, int C, float eps,
-                                                      float momentum, int act) {
-  __shared__ double r1[B1_SL][B1_CH], r2[B1_SL][B1_CH];
-  __shared__ float s_sc[B1_CH], s_sh[B1_CH];
-  const int cl = threadIdx.x % B1_CH, sl = threadIdx.x / B1_CH;
-  const int c = blockIdx.x * B1_CH + cl;
-  const bool cok = c < C;
-  double s1 = 0.0, s2 = 0.0;
-  if (cok)
-    for (int b = sl; b < B; b += B1_SL) {
-      const float v = x[(size_t)b * C + c];
-      s1 += v;
-      s2 += (double)v * v;
-    }
-  r1[sl][cl] = s1;
-  r2[sl][cl] = s2;
-  __syncthreads();
-  if (sl == 0 && cok) {
-    double t1 = 0.0, t2 = 0.0;
-#pragma unroll
-    for (int k = 0; k < B1_SL; ++k) {
-      t1 += r1[k][cl];
-      t2 += r2[k][cl];
-    }
-    const double m = t1 / B;
-    double var = t2 / B - m * m;
-    if (var < 0.0) var = 0.0;
-    const float mu = (float)m, is = (float)(1.0 / sqrt(var + (double)eps));
-    save_mean[c] = mu;
-    save_invstd[c] = is;
-    if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mu;
-    if (running_var) {
-      const double unb = B > 1 ? var * B / (B - 1.0) : var;
-      running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unb;
-    }
-    const float sc = gamma[c] * is;
-    s_sc[cl] = sc;
-    s_sh[cl] = beta[c] - mu * sc;
-  }
-  __syncthreads();
-  if (cok) {
-    const float sc = s_sc[cl], sh = s_sh[cl];
-    for (int b = sl; b < B; b += B1_SL) {
-      const size_t o = (size_t)b * C + c;
-      y[o] = act_fwd(fmaf(x[o], sc, sh), act);
-    }
-  }
-}
-
-__global__ __launch_bounds__(NT) void bn1d_bwd_kernel(const float* __restrict__ gy, const float* __restrict__ x,
-                                                      const float* __restrict__ gamma,
-                                                      const float* __restrict__ beta,
-                                                      const float* __restrict__ mean,
-                                                      const float* __restrict__ invstd, float* __restrict__ gx,
-                                                      float* __restrict__ dgamma, float* __restrict__ dbeta, int B,
-                                                      int C, int act, unsigned* __restrict__ gx_amax) {
-  const bool accp = (act & 0x100) != 0;        // as bn_apply_kernel
-  act &= 0xff;
-  __shared__ double r1[B1_SL][B1_CH], r2[B1_SL][B1_CH];
-  __shared__ float s_c1[B1_CH], s_c2[B1_CH];
-  const int cl = threadIdx.x % B1_CH, sl = threadIdx.x / B1_CH;
-  const int c = blockIdx.x * B1_CH + cl;
-  const bool cok = c < C;
-  float mu = 0.f, is = 0.f, sc = 0.f, sh = 0.f;
-  double s1 = 0.0, s2 = 0.0;
-  if (cok) {
-    mu = mean[c];
-    is = invstd[c];
-    sc = gamma[c] * is;
-    sh = beta[c] - mu * sc;
-    for (int b = sl; b < B; b += B1_SL) {
-      const size_t o = (size_t)b * C + c;
-      const float xv = x[o];
-      const float g = act_grad(fmaf(xv, sc, sh), gy[o], act);
-      s1 += g;
-      s2 += (double)(g * ((xv - mu) * is));
-    }
-  }
-  r1[sl][cl] = s1;
-  r2[sl][cl] = s2;
-  __syncthreads();
-  if (sl == 0 && cok) {
-    double t1 = 0.0, t2 = 0.0;
-#pragma unroll
-    for (int k = 0; k < B1_SL; ++k) {
-      t1 += r1[k][cl];
-      t2 += r2[k][cl];
-    }
-    if (dbeta) dbeta[c] = (float)t1 + (accp ? dbeta[c] : 0.f);
-    if (dgamma) dgamma[c] = (float)t2 + (accp ? dgamma[c] : 0.f);
-    s_c1[cl] = (float)(t1 / B);
-    s_c2[cl] = (float)(t2 / B);
-  }
-  __syncthreads();
-  unsigned am = 0;
-  if (cok) {
-    const float c1 = s_c1[cl], c2 = s_c2[cl];
-    for (int b = sl; b < B; b += B1_SL) {
-      const size_t o = (size_t)b * C + c;
-      const float xv = x[o];
-      const float g = act_grad(fmaf(xv, sc, sh), gy[o], act);
-      const float r = sc * (g - c1 - ((xv - mu) * is) * c2);
-      am = max(am, abs_bits(r));
-      gx[o] = r;
-    }
-  }
-  if (gx_amax) block_amax_atomic<NT>(am, gx_amax);
-}
-
-// slices of the apply pass: >= 4096 elements per workgroup so that the per-workgroup prologue (partials
-// reduction + barrier) is amortised, but enough workgroups to fill the chip
-Slicing make_apply_slicing(int B, int C, int HW) {
-  const long total = (long)B * HW;
-  long ns = 4096 / C;
-  if (ns < 1) ns = 1;
-  long per = (total + ns - 1) / ns;
-  if (per < 4096) per = 4096;
-  per = (per + 3) / 4 * 4;
-  Slicing s;
-  s.per = per;
-  s.ns = (int)((total + per - 1) / per);
-  return s;
-}
-
-// The 16-byte loops are taken only when four elements of a plane share a load (HW % 4 == 0) and every tensor that is
-// streamed starts on a 16-byte boundary (pass nullptr for one that is not there); otherwise the scalar loops.
-int streams_vec(int HW, const void* a, const void* b = nullptr, const void* c = nullptr) {
-  return (HW & 3) == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
 }
 
 size_t part_bytes(int C) { return (size_t)C * NS_MAX * 2 * sizeof(double); }
@@ -677,165 +859,43 @@ BwdPlan make_bwd_plan(int B, int C, int HW, int vec) {
   return p;
 }
 
-// Upper bound of max |act(x * sc + sh)| over a channel of n = count values, from its sums alone (act_amax of the
-// finalize kernels: what an fp16-plane convolution that applies sc / sh on load scales its input by).
-//   s2, m, var: the channel's sum of x^2, mean and clamped variance (s2 / n - m^2, >= 0) as the finalize kernel computed
-//   them in fp64; mu = (float)m, sc, beta: the coefficients it wrote (sh = beta - mu * sc).
-//   delta: relative error of the sums -- |S2 - T2| <= delta T2 and |S1 - T1| <= delta sum |x|, T1 / T2 the exact sums.
-// Samuelson: every x satisfies |x - T1/n| <= sigma sqrt(n - 1), sigma^2 = T2/n - (T1/n)^2 the EXACT variance.  `var` is
-// not that: when |mean| >> sigma, S2/n - m^2 cancels, the computed variance can be ~0 while sigma is not, 1/std then
-// goes up to 1/sqrt(eps), and a bound from `var` alone falls far below the data.  With q = S2/n:
-//   T2/n <= q / (1 - delta),  |m - T1/n| <= delta sum|x| / n <= delta sqrt(T2/n)          (Cauchy-Schwarz)
-//   sigma^2 - (q - m^2) = (T2/n - q) + (m - T1/n)(m + T1/n) <= (delta + delta (2 + delta)) T2/n <= 3.01 delta q
-// (delta <= 1e-3), plus fp64 rounding of q - m^2 (< 2^-50 q); so var_up = var + (3.01 delta + 2^-50) q >= sigma^2, and
-//   |x - mu| <= sqrt(var_up (n - 1)) + |T1/n - m| + |m - mu| <= sqrt(var_up (n - 1)) + 1.01 delta sqrt(q) + 2^-23 |m|.
-// |x sc + sh| <= |sc| |x - mu| + |beta| + (rounding of sh: <= 2^-23 (|beta| + |mu sc|)); the consumer's fmaf and the
-// final fp64 -> fp32 conversion round by 2^-24 each: (1 + 2^-20).  ReLU / LeakyReLU(0.2) only shrink magnitudes.
-// Where the sums are accurate (|mean| <= 8 sigma, the slots' delta) this stays within 0.1 % of the former
-// |gamma| sqrt(n) + |beta|; under cancellation it grows with sqrt(delta) |mean| instead of falling below the data.
-__device__ __forceinline__ float bn_act_bound(double s2, double m, double var, double count, double delta, float mu,
-                                              float sc, float beta) {
-  const double q = s2 / count;
-  const double var_up = var + (3.01 * delta + 0x1p-50) * q;
-  const double dev = sqrt(var_up * fmax(count - 1.0, 0.0)) + 1.01 * delta * sqrt(q) + 0x1p-23 * fabs(m);
-  const double asc = fabs((double)sc), ab = fabs((double)beta);
-  const double b = asc * dev + ab + 0x1p-23 * (ab + asc * fabs((double)mu));
-  return (float)(b * (1.0 + 0x1p-20));
-}
-
-// delta of bn_act_bound for sums made of fp32 statistics slots (each an fp32 sum in which a term goes through at most
-// D = VG_STATS_SLOT_DEPTH roundings: within gamma_D <= (D + 0.01) 2^-24 of the exact sum, relative to the sum of
-// magnitudes -- for the squares that is T2 itself) added in fp64 over nslots slots (and NS_MAX partials):
-// (nslots + 2 NS_MAX) 2^-53 more
-double slot_sums_delta(int nslots) { return (VG_STATS_SLOT_DEPTH + 1) * 0x1p-24 + (nslots + 2.0 * NS_MAX) * 0x1p-53; }
-
-// ... and for fp64 sums of fp32 values (bn_partial_kernel<0>: x^2 is exact in fp64): count + partials additions
-double fp64_sums_delta(double count) { return (count + 2.0 * NS_MAX + NT) * 0x1p-53; }
-
-}  // namespace
-
-// Per-channel coefficients of a train-mode BatchNorm from partial sums: `part` holds, for channel c and partial k,
-// (sum, sum of squares) at part[(c * cs + k * ks) * 2 + {0, 1}] -- fp32 slots written by a convolution epilogue
-// (cs = 1... see vg_bn_finalize_stats) or the fp64 slices of bn_partial_kernel<0>.  Fixed summation order, fp64.
+// ---- coefficients from slots -----------------------------------------------------------------------------------------
+// Per-channel coefficients of a train-mode BatchNorm from partial sums (slot_sums: fp32 slots written by a convolution
+// epilogue, or the fp64 slices of bn_partial_kernel<0>).  Fixed summation order, fp64.
 // Writes mean / invstd (saved for backward), scale = gamma * invstd, shift = beta - mean * scale, and updates the
 // running statistics exactly as bn_apply_kernel's slice-0 workgroup does.
-template <typename T>
-__global__ __launch_bounds__(NT) void bn_finalize_kernel(const T* __restrict__ part, int np, long cs, long ks, int C,
-                                                         double count, const float* __restrict__ gamma,
-                                                         const float* __restrict__ beta, float* __restrict__ running_mean,
-                                                         float* __restrict__ running_var, float* __restrict__ mean_out,
-                                                         float* __restrict__ invstd_out, float* __restrict__ scale,
-                                                         float* __restrict__ shift, float eps, float momentum,
-                                                         unsigned* __restrict__ act_amax, double delta) {
-  // act_amax (may be NULL): an upper bound of max |act(BN(x))| over the whole tensor is added to it (atomic maximum of
-  // the channels' bn_act_bound, delta: the relative error of the partial sums) -- what the fp16-plane convolution that
-  // applies these coefficients on load scales its input by
-  // 32 channels per workgroup x 8 partial-lanes: consecutive threads read consecutive channels (the convolution's
-  // slots are [slot][C][2]: 256 contiguous bytes per 32 threads), each partial-lane sums every 8th partial, and the 8
-  // sums of a channel are added in a fixed order
-  constexpr int CH = 32, KL = NT / CH;
-  __shared__ double r1[KL][CH], r2[KL][CH];
-  const int cl = threadIdx.x % CH, kl = threadIdx.x / CH;
-  const int c = blockIdx.x * CH + cl;
-  double s1 = 0.0, s2 = 0.0;
-  if (c < C)
-    for (int k = kl; k < np; k += KL) {
-      s1 += (double)part[((size_t)c * cs + (size_t)k * ks) * 2];
-      s2 += (double)part[((size_t)c * cs + (size_t)k * ks) * 2 + 1];
-    }
-  r1[kl][cl] = s1;
-  r2[kl][cl] = s2;
-  __syncthreads();
-  if (kl == 0 && c < C) {
-    s1 = 0.0;
-    s2 = 0.0;
-#pragma unroll
-    for (int k = 0; k < KL; ++k) {
-      s1 += r1[k][cl];
-      s2 += r2[k][cl];
-    }
-    const double m = s1 / count;
-    double var = s2 / count - m * m;
-    if (var < 0.0) var = 0.0;
-    const float mu = (float)m, is = (float)(1.0 / sqrt(var + (double)eps));
-    const float sc = gamma[c] * is;
-    mean_out[c] = mu;
-    invstd_out[c] = is;
-    scale[c] = sc;
-    shift[c] = beta[c] - mu * sc;
-    if (act_amax) atomicMax(act_amax, __float_as_uint(bn_act_bound(s2, m, var, count, delta, mu, sc, beta[c])));
-    if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mu;
-    if (running_var) {
-      const double unb = count > 1.0 ? var * count / (count - 1.0) : var;
-      running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unb;
-    }
-  }
-}
-
-// MANY slots in ONE launch (the ring kernels leave 512-2048 of them at B = 128): a workgroup of 1024 threads owns 8
-// channels, 128 partial-lanes each -- every lane sums every 128th slot (4-16 independent loads), the 128 fp64 sums of a
-// channel are added in a fixed order through LDS (16 lanes x 8, then 16).  Replaces stats_partial + finalize (two launches
-// of ~5 us and a kernel boundary) wherever a channel has <= 4096 slots.
-__global__ __launch_bounds__(1024) void bn_finalize_wide_kernel(const float* __restrict__ stats, int nslots, int C,
-                                                                double count, const float* __restrict__ gamma,
-                                                                const float* __restrict__ beta,
-                                                                float* __restrict__ running_mean,
-                                                                float* __restrict__ running_var, float* __restrict__ mean_out,
-                                                                float* __restrict__ invstd_out, float* __restrict__ scale,
-                                                                float* __restrict__ shift, float eps, float momentum,
-                                                                unsigned* __restrict__ act_amax, double delta) {
-  constexpr int CH = 8, KL = 128;
-  __shared__ double r1[KL][CH], r2[KL][CH];
-  const int cl = threadIdx.x % CH, kl = threadIdx.x / CH;
-  const int c = blockIdx.x * CH + cl;
-  double s1 = 0.0, s2 = 0.0;
-  if (c < C)
-    for (int k = kl; k < nslots; k += KL) {
-      const float2 v = *reinterpret_cast<const float2*>(stats + ((size_t)k * C + c) * 2);
-      s1 += (double)v.x;
-      s2 += (double)v.y;
-    }
-  r1[kl][cl] = s1;
-  r2[kl][cl] = s2;
-  __syncthreads();
-  if (kl < 16) {                      // 16 lanes per channel: each adds 8 consecutive partial-lanes, in order
-    s1 = 0.0;
-    s2 = 0.0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      s1 += r1[kl * 8 + k][cl];
-      s2 += r2[kl * 8 + k][cl];
-    }
-  }
-  __syncthreads();
-  if (kl < 16) {
-    r1[kl][cl] = s1;
-    r2[kl][cl] = s2;
-  }
-  __syncthreads();
-  if (kl == 0 && c < C) {
-    s1 = 0.0;
-    s2 = 0.0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      s1 += r1[k][cl];
-      s2 += r2[k][cl];
-    }
-    const double m = s1 / count;
-    double var = s2 / count - m * m;
-    if (var < 0.0) var = 0.0;
-    const float mu = (float)m, is = (float)(1.0 / sqrt(var + (double)eps));
-    const float sc = gamma[c] * is;
-    mean_out[c] = mu;
-    invstd_out[c] = is;
-    scale[c] = sc;
-    shift[c] = beta[c] - mu * sc;
-    if (act_amax) atomicMax(act_amax, __float_as_uint(bn_act_bound(s2, m, var, count, delta, mu, sc, beta[c])));
-    if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mu;
-    if (running_var) {
-      const double unb = count > 1.0 ? var * count / (count - 1.0) : var;
-      running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unb;
-    }
+// act_amax (may be NULL): an upper bound of max |act(BN(x))| over the whole tensor is added to it (atomic maximum of
+// the channels' bn_act_bound, delta: the relative error of the partial sums) -- what the fp16-plane convolution that
+// applies these coefficients on load scales its input by.
+// <T, 32, 8>: 32 channels per workgroup x 8 partial-lanes: consecutive threads read consecutive channels (the convolution's
+// slots are [slot][C][2]: 256 contiguous bytes per 32 threads), each partial-lane sums every 8th partial, and the 8
+// sums of a channel are added in order.
+// <float, 8, 128>: MANY slots in ONE launch (the ring kernels leave 512-2048 of them at B = 128): a workgroup of 1024
+// threads owns 8 channels, 128 partial-lanes each -- every lane sums every 128th slot (4-16 independent 8-byte loads), the
+// 128 fp64 sums of a channel are added 16 lanes x 8, then 16.  Replaces stats_partial + finalize (two launches of ~5 us and
+// a kernel boundary) wherever a channel has <= 4096 slots.
+template <typename T, int CH, int KL>
+__global__ __launch_bounds__(CH * KL) void bn_finalize_kernel(const T* __restrict__ part, int np, long cs, long ks, int C,
+                                                              double count, const float* __restrict__ gamma,
+                                                              const float* __restrict__ beta,
+                                                              float* __restrict__ running_mean,
+                                                              float* __restrict__ running_var, float* __restrict__ mean_out,
+                                                              float* __restrict__ invstd_out, float* __restrict__ scale,
+                                                              float* __restrict__ shift, float eps, float momentum,
+                                                              unsigned* __restrict__ act_amax, double delta) {
+  constexpr bool WIDE = KL > 8;
+  const int c = blockIdx.x * CH + threadIdx.x % CH;
+  double s1, s2;
+  slot_sums<CH, KL, WIDE, WIDE>(part, cs, ks, 0, np, c, C, s1, s2);
+  if (threadIdx.x / CH == 0 && c < C) {
+    const Coeffs co = channel_coefficients(s1, s2, count, eps, gamma[c], beta[c]);
+    mean_out[c] = co.mu;
+    invstd_out[c] = co.invstd;
+    scale[c] = co.scale;
+    shift[c] = co.shift;
+    if (act_amax)
+      atomicMax(act_amax, __float_as_uint(bn_act_bound(s2, co.m, co.var, count, delta, co.mu, co.scale, beta[c])));
+    update_running(running_mean, running_var, c, co, count, momentum);
   }
 }
 
@@ -844,87 +904,138 @@ __global__ __launch_bounds__(1024) void bn_finalize_wide_kernel(const float* __r
 __global__ __launch_bounds__(NT) void stats_partial_kernel(const float* __restrict__ stats, int nslots, int C, int nsplit,
                                                            double* __restrict__ part) {
   constexpr int CH = 32, KL = NT / CH;
-  __shared__ double r1[KL][CH], r2[KL][CH];
-  const int cl = threadIdx.x % CH, kl = threadIdx.x / CH;
-  const int c = blockIdx.x * CH + cl, sp = blockIdx.y;
+  const int c = blockIdx.x * CH + threadIdx.x % CH, sp = blockIdx.y;
   const int per = cdiv(nslots, nsplit), k0 = sp * per, k1 = min(k0 + per, nslots);
+  double s1, s2;
+  slot_sums<CH, KL, false, false>(stats, 1L, (long)C, k0, k1, c, C, s1, s2);
+  if (threadIdx.x / CH == 0 && c < C) store_partial(part, c, nsplit, sp, s1, s2);
+}
+
+// ---- eval: BatchNorm on RUNNING statistics (nn.BatchNorm*.eval() of the reference's modules, model.py:451-458, 462,
+// 468, 492, 496-505, 390-400) -----------------------------------------------------------------------------------------
+// Coefficients from the running statistics: scale = gamma / sqrt(running_var + eps), shift = beta - running_mean * scale,
+// invstd for the backward.  The running buffers are read, never written.  With the producing convolution's statistics
+// slots (stats[slot][C][2], `count` values per channel) and act_amax: also an upper bound of max |act(scale x + shift)|
+// over the tensor the slots were taken of, from the sums alone.  bn_act_bound's argument, centred on the batch mean
+// instead of on the BatchNorm's own: with S1, S2 the computed sums, m = S1 / n, q = S2 / n, var = max(q - m^2, 0),
+//   |x - T1/n| <= sigma sqrt(n - 1)  (Samuelson, EXACT mean and sigma),  sigma^2 <= var_up = var + (3.01 delta + 2^-50) q,
+//   |T1/n - m| <= 1.01 delta sqrt(q)                                      (both derived above bn_act_bound)
+//   => |scale x + shift| <= |scale| (sqrt(var_up (n - 1)) + 1.01 delta sqrt(q)) + |scale m + shift|.
+// scale m + shift is evaluated in fp64 from the fp32 coefficients WRITTEN (what the consumer multiplies by); 2^-21 of its
+// two terms covers that evaluation, the consumer's fmaf and coefficients rounded otherwise (the exact ones differ from
+// the written by 2^-23 relative); (1 + 2^-20): the fp64 -> fp32 conversion.  ReLU / LeakyReLU(0.2) only shrink magnitudes.
+// A constant channel has sigma = 0 <= var_up; a variance lost to cancellation is covered by the delta q term.
+// CH channels per workgroup x KL partial-lanes (slot_sums); the KL sums of a channel are added serially, also the 128.
+template <int CH, int KL>
+__global__ __launch_bounds__(CH * KL) void bn_eval_coeffs_kernel(const float* __restrict__ gamma,
+                                                                 const float* __restrict__ beta,
+                                                                 const float* __restrict__ running_mean,
+                                                                 const float* __restrict__ running_var,
+                                                                 float* __restrict__ scale, float* __restrict__ shift,
+                                                                 float* __restrict__ invstd, int C, float eps,
+                                                                 const float* __restrict__ stats, int nslots, double count,
+                                                                 unsigned* __restrict__ act_amax, double delta) {
+  const int c = blockIdx.x * CH + threadIdx.x % CH;
+  const bool bound = stats != nullptr && act_amax != nullptr;      // uniform over the grid
   double s1 = 0.0, s2 = 0.0;
-  if (c < C)
-    for (int k = k0 + kl; k < k1; k += KL) {
-      s1 += (double)stats[((size_t)k * C + c) * 2];
-      s2 += (double)stats[((size_t)k * C + c) * 2 + 1];
-    }
-  r1[kl][cl] = s1;
-  r2[kl][cl] = s2;
-  __syncthreads();
-  if (kl == 0 && c < C) {
-    s1 = 0.0;
-    s2 = 0.0;
-#pragma unroll
-    for (int k = 0; k < KL; ++k) {
-      s1 += r1[k][cl];
-      s2 += r2[k][cl];
-    }
-    part[((size_t)c * nsplit + sp) * 2] = s1;
-    part[((size_t)c * nsplit + sp) * 2 + 1] = s2;
-  }
+  if (bound) slot_sums<CH, KL, false, false>(stats, 1L, (long)C, 0, nslots, c, C, s1, s2);
+  if (threadIdx.x / CH != 0 || c >= C) return;
+  const float is = (float)(1.0 / sqrt((double)running_var[c] + (double)eps));
+  const float sc = gamma[c] * is;
+  const float sh = beta[c] - running_mean[c] * sc;
+  scale[c] = sc;
+  shift[c] = sh;
+  invstd[c] = is;
+  if (!bound) return;
+  double m, var;
+  mean_and_variance(s1, s2, count, m, var);
+  const double q = s2 / count;
+  const double var_up = var + (3.01 * delta + 0x1p-50) * q;
+  const double dev = sqrt(var_up * fmax(count - 1.0, 0.0)) + 1.01 * delta * sqrt(q);
+  const double asc = fabs((double)sc);
+  const double b = asc * dev + fabs((double)sc * m + (double)sh) + 0x1p-21 * (asc * fabs(m) + fabs((double)sh));
+  atomicMax(act_amax, __float_as_uint((float)(b * (1.0 + 0x1p-20))));
 }
 
-constexpr int AA_U = 4;
-// y = act(x * scale[c] + shift[c]): the normalise pass with given coefficients (layers whose consumer cannot apply
-// them while it loads)
-// hw4_shift >= 0: H*W/4 is a power of two (every layer of the reference) -- the channel is a shift and a 32-bit remainder;
-// the 64-bit division per thread that this replaces made the pass run at 0.8 TB/s (20 us for 16 MB).
-__global__ __launch_bounds__(NT) void affine_act_kernel(const float* __restrict__ x, const float* __restrict__ scale,
-                                                        const float* __restrict__ shift, float* __restrict__ y, int C,
-                                                        int HW, size_t n4, int act, int hw4_shift,
-                                                        unsigned* __restrict__ y_amax) {
-  // A workgroup walks chunks of NT * AA_U units of 16 bytes, grid-stride (<= 2048 workgroups: one maximum and one atomic
-  // per workgroup, not per 4 KB); within a chunk a thread's AA_U units are NT apart (contiguous per round, all loads of
-  // a chunk in flight together).
+// Backward of y = act(x * sc + sh) with FROZEN coefficients, one pass: gx = gy act'(pre) sc; dbeta = sum gy act'(pre),
+// dgamma = sum gy act'(pre) (x - mean) invstd.  Workgroup (c, k) owns slice k of channel c (make_slicing), writes its gx
+// and -- part != NULL -- its fp64 partial sums part[c][k][2]; with ONE slice per channel it writes dgamma / dbeta itself.
+__global__ __launch_bounds__(NT) void bn_eval_bwd_kernel(const float* __restrict__ gy, const float* __restrict__ x,
+                                                         const float* __restrict__ scale, const float* __restrict__ shift,
+                                                         const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                         float* __restrict__ gx, double* __restrict__ part,
+                                                         float* __restrict__ dgamma, float* __restrict__ dbeta, int B,
+                                                         int C, int HW, long per, int ns, int act, int accp,
+                                                         unsigned* __restrict__ gx_amax, int vec) {
+  __shared__ double red[NT / 64];
+  const float slope = act_slope_of(act);
+  const int c = blockIdx.x, k = blockIdx.y;
+  const float sc = scale[c], sh = shift[c], mu = mean[c], is = invstd[c];
+  double s1 = 0.0, s2 = 0.0;
   unsigned am = 0;
-  for (size_t base = (size_t)blockIdx.x * (NT * AA_U) + threadIdx.x; base < n4 + threadIdx.x;
-       base += (size_t)gridDim.x * (NT * AA_U)) {
-    float4 v[AA_U];
-    float sc[AA_U], sh[AA_U];
-#pragma unroll
-    for (int u = 0; u < AA_U; ++u) {
-      const size_t i0 = base + (size_t)u * NT;
-      const size_t i = i0 < n4 ? i0 : n4 - 1;               // past the end: the last unit again (not stored)
-      // HW % 4 == 0: the four elements share a channel
-      const int c = hw4_shift >= 0 ? (int)((unsigned)(i >> hw4_shift) % (unsigned)C) : (int)(((4 * i) / HW) % C);
-      sc[u] = scale[c];
-      sh[u] = shift[c];
-      v[u] = *reinterpret_cast<const float4*>(x + 4 * i);
-    }
-#pragma unroll
-    for (int u = 0; u < AA_U; ++u) {
-      const size_t i0 = base + (size_t)u * NT;
-      float4 o;
-      o.x = act_fwd(fmaf(v[u].x, sc[u], sh[u]), act);
-      o.y = act_fwd(fmaf(v[u].y, sc[u], sh[u]), act);
-      o.z = act_fwd(fmaf(v[u].z, sc[u], sh[u]), act);
-      o.w = act_fwd(fmaf(v[u].w, sc[u], sh[u]), act);
-      if (i0 < n4) *reinterpret_cast<float4*>(y + 4 * i0) = o;
-      am = max(max(am, abs_bits(o.x)), max(max(abs_bits(o.y), abs_bits(o.z)), abs_bits(o.w)));
+  plane_walk<true, true>(x, gy, gx, B, C, HW, c, k, per, vec, [&](float xv, float gv) -> float {
+    const float g = eval_act_grad(fmaf(xv, sc, sh), gv, slope);
+    add_grad_sums(s1, s2, g, xv, mu, is);
+    const float r = g * sc;
+    am = max(am, abs_bits(r));
+    return r;
+  });
+  if (part || dgamma || dbeta) {               // uniform over the grid
+    const double t1 = block_sum<NT>(s1, red);
+    const double t2 = block_sum<NT>(s2, red);
+    if (threadIdx.x == 0) {
+      if (part)
+        store_partial(part, c, ns, k, t1, t2);
+      else                                     // ns == 1
+        store_param_grads(dgamma, dbeta, c, t1, t2, accp);
     }
   }
-  if (y_amax) block_amax_atomic<NT>(am, y_amax);      // max |y| for an fp16-plane consumer (common.hpp)
+  if (gx_amax) block_amax_atomic<NT>(am, gx_amax);
 }
 
-// the same for H*W not a multiple of 4 (odd image sizes): one element per lane
-__global__ __launch_bounds__(NT) void affine_act_scalar_kernel(const float* __restrict__ x, const float* __restrict__ scale,
-                                                               const float* __restrict__ shift, float* __restrict__ y,
-                                                               int C, int HW, size_t n, int act,
-                                                               unsigned* __restrict__ y_amax) {
-  const size_t e0 = (size_t)blockIdx.x * NT + threadIdx.x;
-  const size_t e = e0 < n ? e0 : n - 1;
-  const int c = (int)((e / HW) % C);
-  const float r = act_fwd(fmaf(x[e], scale[c], shift[c]), act);
-  if (e0 < n) y[e] = r;
-  if (y_amax) block_amax_atomic<NT>(abs_bits(r), y_amax);
+__global__ __launch_bounds__(NT) void bn_eval_bwd_finalize_kernel(const double* __restrict__ part, int ns, int C,
+                                                                  float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                                  int accp) {
+  const int c = blockIdx.x * NT + threadIdx.x;
+  if (c >= C) return;
+  double s1 = 0.0, s2 = 0.0;
+  sum_partials(part, c, ns, s1, s2);
+  store_param_grads(dgamma, dbeta, c, s1, s2, accp);
 }
 
+// The same for BatchNorm1d, x [B][C]: the geometry of bn1d_bwd_kernel, one pass.
+__global__ __launch_bounds__(NT) void bn1d_eval_bwd_kernel(const float* __restrict__ gy, const float* __restrict__ x,
+                                                           const float* __restrict__ scale, const float* __restrict__ shift,
+                                                           const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                           float* __restrict__ gx, float* __restrict__ dgamma,
+                                                           float* __restrict__ dbeta, int B, int C, int act, int accp,
+                                                           unsigned* __restrict__ gx_amax) {
+  const float slope = act_slope_of(act);
+  const int cl = threadIdx.x % B1_CH, sl = threadIdx.x / B1_CH;
+  const int c = blockIdx.x * B1_CH + cl;
+  const bool cok = c < C;
+  double s1 = 0.0, s2 = 0.0;
+  unsigned am = 0;
+  if (cok) {
+    const float sc = scale[c], sh = shift[c], mu = mean[c], is = invstd[c];
+    for (int b = sl; b < B; b += B1_SL) {
+      const size_t o = (size_t)b * C + c;
+      const float xv = x[o];
+      const float g = eval_act_grad(fmaf(xv, sc, sh), gy[o], slope);
+      add_grad_sums(s1, s2, g, xv, mu, is);
+      const float r = g * sc;
+      am = max(am, abs_bits(r));
+      gx[o] = r;
+    }
+  }
+  column_sums<B1_CH, B1_SL, false>(s1, s2);
+  if (sl == 0 && cok) store_param_grads(dgamma, dbeta, c, s1, s2, accp);
+  if (gx_amax) block_amax_atomic<NT>(am, gx_amax);
+}
+
+}  // namespace
+
+// ---- the C entry points ------------------------------------------------------------------------------------------------
 extern "C" size_t vg_bn_workspace_bytes(int C) { return C > 0 ? ws_bytes(C) : 0; }
 
 extern "C" int vg_bn_finalize_stats(const float* stats, int nslots, int C, double count, const float* gamma,
@@ -940,15 +1051,16 @@ extern "C" int vg_bn_finalize_stats(const float* stats, int nslots, int C, doubl
   // NS_MAX-way first stage into the BatchNorm workspace.  (The one-launch form on 1024 slots x 32 channels ran 56 us
   // -- one workgroup, 128 dependent loads per lane -- against ~6 us for the two stages.)
   if (nslots <= 64) {
-    hipLaunchKernelGGL(bn_finalize_kernel<float>, dim3(cdiv(C, 32)), dim3(NT), 0, st, stats, nslots, 1L, (long)C, C,
+    hipLaunchKernelGGL((bn_finalize_kernel<float, 32, 8>), dim3(cdiv(C, 32)), dim3(NT), 0, st, stats, nslots, 1L, (long)C, C,
                        count, gamma, beta, running_mean, running_var, save_mean, save_invstd, scale, shift, eps,
                        momentum, am, delta);      // stats[slot][C][2]: channel stride 1, slot stride C
     VG_CHECK_LAUNCH();
     return 0;
   }
   if (nslots <= 4096) {
-    hipLaunchKernelGGL(bn_finalize_wide_kernel, dim3(cdiv(C, 8)), dim3(1024), 0, st, stats, nslots, C, count, gamma, beta,
-                       running_mean, running_var, save_mean, save_invstd, scale, shift, eps, momentum, am, delta);
+    hipLaunchKernelGGL((bn_finalize_kernel<float, 8, 128>), dim3(cdiv(C, 8)), dim3(1024), 0, st, stats, nslots, 1L, (long)C,
+                       C, count, gamma, beta, running_mean, running_var, save_mean, save_invstd, scale, shift, eps,
+                       momentum, am, delta);
     VG_CHECK_LAUNCH();
     return 0;
   }
@@ -956,7 +1068,7 @@ extern "C" int vg_bn_finalize_stats(const float* stats, int nslots, int C, doubl
   double* part = (double*)workspace;
   hipLaunchKernelGGL(stats_partial_kernel, dim3(cdiv(C, 32), NS_MAX), dim3(NT), 0, st, stats, nslots, C, NS_MAX, part);
   VG_CHECK_LAUNCH();
-  hipLaunchKernelGGL(bn_finalize_kernel<double>, dim3(cdiv(C, 32)), dim3(NT), 0, st, (const double*)part, NS_MAX,
+  hipLaunchKernelGGL((bn_finalize_kernel<double, 32, 8>), dim3(cdiv(C, 32)), dim3(NT), 0, st, (const double*)part, NS_MAX,
                      (long)NS_MAX, 1L, C, count, gamma, beta, running_mean, running_var, save_mean, save_invstd, scale,
                      shift, eps, momentum, am, delta);      // part[c][NS_MAX][2]: the fp32 slots' delta
   VG_CHECK_LAUNCH();
@@ -977,7 +1089,7 @@ extern "C" int vg_bn_stats(const float* x, const float* gamma, const float* beta
                      (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, part, B, C, HW, s.per, s.ns, 0,
                      streams_vec(HW, x));
   VG_CHECK_LAUNCH();
-  hipLaunchKernelGGL(bn_finalize_kernel<double>, dim3(cdiv(C, 32)), dim3(NT), 0, st, (const double*)part, s.ns,
+  hipLaunchKernelGGL((bn_finalize_kernel<double, 32, 8>), dim3(cdiv(C, 32)), dim3(NT), 0, st, (const double*)part, s.ns,
                      (long)s.ns, 1L, C, (double)B * HW, gamma, beta, running_mean, running_var, save_mean, save_invstd,
                      scale, shift, eps, momentum, (unsigned*)act_amax, fp64_sums_delta((double)B * HW));      // part[c][ns][2]
   VG_CHECK_LAUNCH();
@@ -986,9 +1098,8 @@ extern "C" int vg_bn_stats(const float* x, const float* gamma, const float* beta
 
 extern "C" int vg_affine_act(const float* x, const float* scale, const float* shift, float* y, int B, int C, int HW,
                              int act, float* y_amax, void* stream) {
-  if (!x || !scale || !shift || !y || B <= 0 || C <= 0 || HW <= 0) return VG_ERR_BAD_ARG;
-  if (act < VG_ACT_NONE || act > VG_ACT_LRELU) return VG_ERR_BAD_ARG;
-  if ((HW & 3) || (((uintptr_t)x | (uintptr_t)y) & 15)) {      // ... or a tensor that is not on a 16-byte boundary
+  if (!x || !scale || !shift || !y || B <= 0 || C <= 0 || HW <= 0 || !act_ok(act)) return VG_ERR_BAD_ARG;
+  if (!streams_vec(HW, x, y)) {      // H*W not a multiple of 4, or a tensor that is not on a 16-byte boundary
     const size_t n = (size_t)B * C * HW;
     if (cdiv((long)n, (long)NT) > 0x7fffffffL) return VG_ERR_BAD_ARG;
     hipLaunchKernelGGL(affine_act_scalar_kernel, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0, (hipStream_t)stream, x,
@@ -1016,9 +1127,8 @@ extern "C" int vg_bn_act_fwd(const float* x, const float* gamma, const float* be
                              float* running_var, float* save_mean, float* save_invstd, int B, int C, int HW,
                              float eps, float momentum, int act, float* y_amax, void* workspace,
                              size_t workspace_bytes, void* stream) {
-  if (!x || !gamma || !beta || !y || !save_mean || !save_invstd || B <= 0 || C <= 0 || HW <= 0)
+  if (!x || !gamma || !beta || !y || !save_mean || !save_invstd || B <= 0 || C <= 0 || HW <= 0 || !act_ok(act))
     return VG_ERR_BAD_ARG;
-  if (act < VG_ACT_NONE || act > VG_ACT_LRELU) return VG_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
   if (HW == 1) {
     hipLaunchKernelGGL(bn1d_fwd_kernel, dim3(cdiv(C, B1_CH)), dim3(NT), 0, st, x, gamma, beta, y, running_mean,
@@ -1036,7 +1146,7 @@ extern "C" int vg_bn_act_fwd(const float* x, const float* gamma, const float* be
   const Slicing a = make_apply_slicing(B, C, HW);
   hipLaunchKernelGGL(bn_apply_kernel<false>, dim3(C, a.ns), dim3(NT), 0, st, x, (const float*)nullptr,
                      (const double*)part, s.ns, gamma, beta, save_mean, save_invstd, running_mean, running_var,
-                     (float*)nullptr, (float*)nullptr, y, B, C, HW, a.per, eps, momentum, act,
+                     (float*)nullptr, (float*)nullptr, y, B, C, HW, a.per, eps, momentum, act, 0,
                      reinterpret_cast<unsigned*>(y_amax), vec);
   VG_CHECK_LAUNCH();
   return 0;
@@ -1047,14 +1157,13 @@ extern "C" int vg_bn_act_bwd(const float* gy, const float* x, const float* gamma
                              float* dbeta, int B, int C, int HW, int act, int accumulate_param_grads, float* gx_amax,
                              void* workspace, size_t workspace_bytes, void* stream) {
   unsigned* am = (unsigned*)gx_amax;
-  if (!gy || !x || !gamma || !beta || !save_mean || !save_invstd || !gx || B <= 0 || C <= 0 || HW <= 0)
+  if (!gy || !x || !gamma || !beta || !save_mean || !save_invstd || !gx || B <= 0 || C <= 0 || HW <= 0 || !act_ok(act))
     return VG_ERR_BAD_ARG;
-  if (act < VG_ACT_NONE || act > VG_ACT_LRELU) return VG_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
-  const int act_apply = act | (accumulate_param_grads ? 0x100 : 0);      // bit 8: dgamma / dbeta += (kernels decode it)
+  const int accp = accumulate_param_grads ? 1 : 0;      // dgamma / dbeta +=
   if (HW == 1) {
     hipLaunchKernelGGL(bn1d_bwd_kernel, dim3(cdiv(C, B1_CH)), dim3(NT), 0, st, gy, x, gamma, beta, save_mean,
-                       save_invstd, gx, dgamma, dbeta, B, C, act_apply, am);
+                       save_invstd, gx, dgamma, dbeta, B, C, act, accp, am);
     VG_CHECK_LAUNCH();
     return 0;
   }
@@ -1073,11 +1182,11 @@ extern "C" int vg_bn_act_bwd(const float* gy, const float* x, const float* gamma
     VG_CHECK_LAUNCH();
     if (plan.nv == 8)
       hipLaunchKernelGGL(bn_bwd_team_kernel<8>, dim3(grid), dim3(ONE_NT), 0, st, x, gy, gamma, beta, save_mean, save_invstd,
-                         gx, dgamma, dbeta, B, C, HW, act_apply, am, plan.T, plan.teams, xch);
+                         gx, dgamma, dbeta, B, C, HW, act, accp, am, plan.T, plan.teams, xch);
 #ifdef VG_TUNING
     else if (plan.nv == 1)
       hipLaunchKernelGGL(bn_bwd_team_kernel<1>, dim3(grid), dim3(ONE_NT), 0, st, x, gy, gamma, beta, save_mean, save_invstd,
-                         gx, dgamma, dbeta, B, C, HW, act_apply, am, plan.T, plan.teams, xch);
+                         gx, dgamma, dbeta, B, C, HW, act, accp, am, plan.T, plan.teams, xch);
 #endif
     else
       return VG_ERR_BAD_ARG;
@@ -1087,10 +1196,10 @@ extern "C" int vg_bn_act_bwd(const float* gy, const float* x, const float* gamma
   if (plan.path == BWD_ONE2 || plan.path == BWD_ONE8) {
     if (plan.path == BWD_ONE2)
       hipLaunchKernelGGL(bn_bwd_onepass_kernel<2>, dim3(C), dim3(ONE_NT), 0, st, x, gy, gamma, beta, save_mean, save_invstd,
-                         gx, dgamma, dbeta, B, C, HW, act_apply, am);
+                         gx, dgamma, dbeta, B, C, HW, act, accp, am);
     else
       hipLaunchKernelGGL(bn_bwd_onepass_kernel<8>, dim3(C), dim3(ONE_NT), 0, st, x, gy, gamma, beta, save_mean, save_invstd,
-                         gx, dgamma, dbeta, B, C, HW, act_apply, am);
+                         gx, dgamma, dbeta, B, C, HW, act, accp, am);
     VG_CHECK_LAUNCH();
     return 0;
   }
@@ -1103,7 +1212,7 @@ extern "C" int vg_bn_act_bwd(const float* gy, const float* x, const float* gamma
   const Slicing a = make_apply_slicing(B, C, HW);
   hipLaunchKernelGGL(bn_apply_kernel<true>, dim3(C, a.ns), dim3(NT), 0, st, x, gy, (const double*)part, s.ns, gamma,
                      beta, const_cast<float*>(save_mean), const_cast<float*>(save_invstd), (float*)nullptr,
-                     (float*)nullptr, dgamma, dbeta, gx, B, C, HW, a.per, 0.f, 0.f, act_apply, am, vec);
+                     (float*)nullptr, dgamma, dbeta, gx, B, C, HW, a.per, 0.f, 0.f, act, accp, am, vec);
   VG_CHECK_LAUNCH();
   return 0;
 }
@@ -1125,208 +1234,11 @@ extern "C" int vg_debug_bn_bwd_plan(int B, int C, int HW, const void* gy, const 
 }
 #endif
 
-// ---- BatchNorm on RUNNING statistics (eval mode: nn.BatchNorm*.eval() of the reference's modules, model.py:451-458, 462,
-// 468, 492, 496-505, 390-400) ---------------------------------------------------------------------------------------------
-namespace {
-
-// Coefficients from the running statistics: scale = gamma / sqrt(running_var + eps), shift = beta - running_mean * scale,
-// invstd for the backward.  The running buffers are read, never written.  With the producing convolution's statistics
-// slots (stats[slot][C][2], `count` values per channel) and act_amax: also an upper bound of max |act(scale x + shift)|
-// over the tensor the slots were taken of, from the sums alone.  bn_act_bound's argument, centred on the batch mean
-// instead of on the BatchNorm's own: with S1, S2 the computed sums, m = S1 / n, q = S2 / n, var = max(q - m^2, 0),
-//   |x - T1/n| <= sigma sqrt(n - 1)  (Samuelson, EXACT mean and sigma),  sigma^2 <= var_up = var + (3.01 delta + 2^-50) q,
-//   |T1/n - m| <= 1.01 delta sqrt(q)                                      (both derived above bn_act_bound)
-//   => |scale x + shift| <= |scale| (sqrt(var_up (n - 1)) + 1.01 delta sqrt(q)) + |scale m + shift|.
-// scale m + shift is evaluated in fp64 from the fp32 coefficients WRITTEN (what the consumer multiplies by); 2^-21 of its
-// two terms covers that evaluation, the consumer's fmaf and coefficients rounded otherwise (the exact ones differ from
-// the written by 2^-23 relative); (1 + 2^-20): the fp64 -> fp32 conversion.  ReLU / LeakyReLU(0.2) only shrink magnitudes.
-// A constant channel has sigma = 0 <= var_up; a variance lost to cancellation is covered by the delta q term.
-// CH channels per workgroup x KL partial-lanes: lane kl sums every KL-th slot, the KL sums of a channel are added in order.
-template <int CH, int KL>
-__global__ __launch_bounds__(CH * KL) void bn_eval_coeffs_kernel(const float* __restrict__ gamma,
-                                                                 const float* __restrict__ beta,
-                                                                 const float* __restrict__ running_mean,
-                                                                 const float* __restrict__ running_var,
-                                                                 float* __restrict__ scale, float* __restrict__ shift,
-                                                                 float* __restrict__ invstd, int C, float eps,
-                                                                 const float* __restrict__ stats, int nslots, double count,
-                                                                 unsigned* __restrict__ act_amax, double delta) {
-  __shared__ double r1[KL][CH], r2[KL][CH];
-  const int cl = threadIdx.x % CH, kl = threadIdx.x / CH;
-  const int c = blockIdx.x * CH + cl;
-  const bool bound = stats != nullptr && act_amax != nullptr;      // uniform over the grid
-  if (bound) {
-    double s1 = 0.0, s2 = 0.0;
-    if (c < C)
-      for (int k = kl; k < nslots; k += KL) {
-        s1 += (double)stats[((size_t)k * C + c) * 2];
-        s2 += (double)stats[((size_t)k * C + c) * 2 + 1];
-      }
-    r1[kl][cl] = s1;
-    r2[kl][cl] = s2;
-    __syncthreads();
-  }
-  if (kl != 0 || c >= C) return;
-  const float is = (float)(1.0 / sqrt((double)running_var[c] + (double)eps));
-  const float sc = gamma[c] * is;
-  const float sh = beta[c] - running_mean[c] * sc;
-  scale[c] = sc;
-  shift[c] = sh;
-  invstd[c] = is;
-  if (!bound) return;
-  double s1 = 0.0, s2 = 0.0;
-  for (int k = 0; k < KL; ++k) {
-    s1 += r1[k][cl];
-    s2 += r2[k][cl];
-  }
-  const double m = s1 / count, q = s2 / count;
-  double var = q - m * m;
-  if (var < 0.0) var = 0.0;
-  const double var_up = var + (3.01 * delta + 0x1p-50) * q;
-  const double dev = sqrt(var_up * fmax(count - 1.0, 0.0)) + 1.01 * delta * sqrt(q);
-  const double asc = fabs((double)sc);
-  const double b = asc * dev + fabs((double)sc * m + (double)sh) + 0x1p-21 * (asc * fabs(m) + fabs((double)sh));
-  atomicMax(act_amax, __float_as_uint((float)(b * (1.0 + 0x1p-20))));
-}
-
-__device__ __forceinline__ float act_slope_of(int act) { return act == VG_ACT_RELU ? 0.f : act == VG_ACT_LRELU ? 0.2f : 1.f; }
-
-// gy * act'(pre): a multiplication by 1 or by the slope (a NaN gradient stays a NaN, as act_slope keeps a NaN value); a NaN
-// pre-activation under ReLU / LeakyReLU has no derivative: NaN
-__device__ __forceinline__ float eval_act_grad(float pre, float g, float slope) {
-  const float d = pre > 0.f ? 1.f : slope;
-  return (pre != pre && slope != 1.f) ? pre : g * d;
-}
-
-// Backward of y = act(x * sc + sh) with FROZEN coefficients, one pass: gx = gy act'(pre) sc; dbeta = sum gy act'(pre),
-// dgamma = sum gy act'(pre) (x - mean) invstd.  Workgroup (c, k) owns slice k of channel c (make_slicing), writes its gx
-// and -- part != NULL -- its fp64 partial sums part[c][k][2]; with ONE slice per channel it writes dgamma / dbeta itself.
-__global__ __launch_bounds__(NT) void bn_eval_bwd_kernel(const float* __restrict__ gy, const float* __restrict__ x,
-                                                         const float* __restrict__ scale, const float* __restrict__ shift,
-                                                         const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                         float* __restrict__ gx, double* __restrict__ part,
-                                                         float* __restrict__ dgamma, float* __restrict__ dbeta, int B,
-                                                         int C, int HW, long per, int ns, int act,
-                                                         unsigned* __restrict__ gx_amax, int vec) {
-  __shared__ double red[NT / 64];
-  const bool accp = (act & 0x100) != 0;        // as bn_apply_kernel
-  const float slope = act_slope_of(act & 0xff);
-  const int c = blockIdx.x, k = blockIdx.y;
-  const long total = (long)B * HW;
-  const long v0 = (long)k * per, v1 = min(v0 + per, total);
-  const int hw_shift = (HW & (HW - 1)) == 0 ? __builtin_ctz(HW) : -1;
-  const float sc = scale[c], sh = shift[c], mu = mean[c], is = invstd[c];
-  double s1 = 0.0, s2 = 0.0;
-  unsigned am = 0;
-  auto one = [&](float xv, float gv) -> float {
-    const float g = eval_act_grad(fmaf(xv, sc, sh), gv, slope);
-    s1 += g;
-    s2 += (double)(g * ((xv - mu) * is));
-    const float r = g * sc;
-    am = max(am, abs_bits(r));
-    return r;
-  };
-  if (vec) {
-    for (long v = v0 + 4L * threadIdx.x; v < v1; v += 4L * NT) {
-      const long b = hw_shift >= 0 ? (v >> hw_shift) : v / HW, hw = v - b * HW;
-      const size_t off = ((size_t)b * C + c) * HW + hw;
-      const float4 xv = *reinterpret_cast<const float4*>(x + off);
-      const float4 gv = *reinterpret_cast<const float4*>(gy + off);
-      float4 o;
-      o.x = one(xv.x, gv.x);
-      o.y = one(xv.y, gv.y);
-      o.z = one(xv.z, gv.z);
-      o.w = one(xv.w, gv.w);
-      *reinterpret_cast<float4*>(gx + off) = o;
-    }
-  } else {
-    for (long v = v0 + threadIdx.x; v < v1; v += NT) {
-      const long b = hw_shift >= 0 ? (v >> hw_shift) : v / HW, hw = v - b * HW;
-      const size_t off = ((size_t)b * C + c) * HW + hw;
-      gx[off] = one(x[off], gy[off]);
-    }
-  }
-  if (part || dgamma || dbeta) {               // uniform over the grid
-    const double t1 = block_sum<NT>(s1, red);
-    const double t2 = block_sum<NT>(s2, red);
-    if (threadIdx.x == 0) {
-      if (part) {
-        part[((size_t)c * ns + k) * 2 + 0] = t1;
-        part[((size_t)c * ns + k) * 2 + 1] = t2;
-      } else {                                 // ns == 1
-        if (dbeta) dbeta[c] = (float)t1 + (accp ? dbeta[c] : 0.f);
-        if (dgamma) dgamma[c] = (float)t2 + (accp ? dgamma[c] : 0.f);
-      }
-    }
-  }
-  if (gx_amax) block_amax_atomic<NT>(am, gx_amax);
-}
-
-__global__ __launch_bounds__(NT) void bn_eval_bwd_finalize_kernel(const double* __restrict__ part, int ns, int C,
-                                                                  float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                                  int accp) {
-  const int c = blockIdx.x * NT + threadIdx.x;
-  if (c >= C) return;
-  double s1 = 0.0, s2 = 0.0;
-  for (int k = 0; k < ns; ++k) {               // fixed order
-    s1 += part[((size_t)c * ns + k) * 2];
-    s2 += part[((size_t)c * ns + k) * 2 + 1];
-  }
-  if (dbeta) dbeta[c] = (float)s1 + (accp ? dbeta[c] : 0.f);
-  if (dgamma) dgamma[c] = (float)s2 + (accp ? dgamma[c] : 0.f);
-}
-
-// The same for BatchNorm1d, x [B][C]: the geometry of bn1d_bwd_kernel, one pass.
-__global__ __launch_bounds__(NT) void bn1d_eval_bwd_kernel(const float* __restrict__ gy, const float* __restrict__ x,
-                                                           const float* __restrict__ scale, const float* __restrict__ shift,
-                                                           const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                           float* __restrict__ gx, float* __restrict__ dgamma,
-                                                           float* __restrict__ dbeta, int B, int C, int act,
-                                                           unsigned* __restrict__ gx_amax) {
-  const bool accp = (act & 0x100) != 0;
-  const float slope = act_slope_of(act & 0xff);
-  __shared__ double r1[B1_SL][B1_CH], r2[B1_SL][B1_CH];
-  const int cl = threadIdx.x % B1_CH, sl = threadIdx.x / B1_CH;
-  const int c = blockIdx.x * B1_CH + cl;
-  const bool cok = c < C;
-  double s1 = 0.0, s2 = 0.0;
-  unsigned am = 0;
-  if (cok) {
-    const float sc = scale[c], sh = shift[c], mu = mean[c], is = invstd[c];
-    for (int b = sl; b < B; b += B1_SL) {
-      const size_t o = (size_t)b * C + c;
-      const float xv = x[o];
-      const float g = eval_act_grad(fmaf(xv, sc, sh), gy[o], slope);
-      s1 += g;
-      s2 += (double)(g * ((xv - mu) * is));
-      const float r = g * sc;
-      am = max(am, abs_bits(r));
-      gx[o] = r;
-    }
-  }
-  r1[sl][cl] = s1;
-  r2[sl][cl] = s2;
-  __syncthreads();
-  if (sl == 0 && cok) {
-    double t1 = 0.0, t2 = 0.0;
-#pragma unroll
-    for (int k = 0; k < B1_SL; ++k) {
-      t1 += r1[k][cl];
-      t2 += r2[k][cl];
-    }
-    if (dbeta) dbeta[c] = (float)t1 + (accp ? dbeta[c] : 0.f);
-    if (dgamma) dgamma[c] = (float)t2 + (accp ? dgamma[c] : 0.f);
-  }
-  if (gx_amax) block_amax_atomic<NT>(am, gx_amax);
-}
-
-}  // namespace
-
 extern "C" int vg_bn_eval_coeffs(const float* gamma, const float* beta, const float* running_mean,
                                  const float* running_var, float* scale, float* shift, float* invstd, int C, float eps,
                                  int act, const float* stats, int nslots, double count, float* act_amax, void* stream) {
-  if (!gamma || !beta || !running_mean || !running_var || !scale || !shift || !invstd || C <= 0) return VG_ERR_BAD_ARG;
-  if (act < VG_ACT_NONE || act > VG_ACT_LRELU) return VG_ERR_BAD_ARG;
+  if (!gamma || !beta || !running_mean || !running_var || !scale || !shift || !invstd || C <= 0 || !act_ok(act))
+    return VG_ERR_BAD_ARG;
   const bool bound = stats != nullptr && act_amax != nullptr;
   if (bound && (nslots <= 0 || !(count > 0))) return VG_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
@@ -1334,7 +1246,7 @@ extern "C" int vg_bn_eval_coeffs(const float* gamma, const float* beta, const fl
   const float* sp = bound ? stats : nullptr;
   unsigned* am = bound ? (unsigned*)act_amax : nullptr;
   // few slots (or none): 32 channels x 8 partial-lanes; many (the ring kernels leave 512-2048, a thin first layer 16 384):
-  // 8 channels x 128 partial-lanes, as bn_finalize_wide_kernel -- ONE launch either way
+  // 8 channels x 128 partial-lanes, as bn_finalize_kernel<float, 8, 128> -- ONE launch either way
   if (!bound || nslots <= 64)
     hipLaunchKernelGGL((bn_eval_coeffs_kernel<32, 8>), dim3(cdiv(C, 32)), dim3(256), 0, st, gamma, beta, running_mean,
                        running_var, scale, shift, invstd, C, eps, sp, nslots, count, am, delta);
@@ -1350,13 +1262,13 @@ extern "C" int vg_bn_eval_act_bwd(const float* gy, const float* x, const float* 
                                   int C, int HW, int act, int accumulate_param_grads, float* gx_amax, void* workspace,
                                   size_t workspace_bytes, void* stream) {
   unsigned* am = (unsigned*)gx_amax;
-  if (!gy || !x || !scale || !shift || !mean || !invstd || !gx || B <= 0 || C <= 0 || HW <= 0) return VG_ERR_BAD_ARG;
-  if (act < VG_ACT_NONE || act > VG_ACT_LRELU) return VG_ERR_BAD_ARG;
+  if (!gy || !x || !scale || !shift || !mean || !invstd || !gx || B <= 0 || C <= 0 || HW <= 0 || !act_ok(act))
+    return VG_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
-  const int act_apply = act | (accumulate_param_grads ? 0x100 : 0);
+  const int accp = accumulate_param_grads ? 1 : 0;
   if (HW == 1) {
     hipLaunchKernelGGL(bn1d_eval_bwd_kernel, dim3(cdiv(C, B1_CH)), dim3(NT), 0, st, gy, x, scale, shift, mean, invstd, gx,
-                       dgamma, dbeta, B, C, act_apply, am);
+                       dgamma, dbeta, B, C, act, accp, am);
     VG_CHECK_LAUNCH();
     return 0;
   }
@@ -1368,11 +1280,11 @@ extern "C" int vg_bn_eval_act_bwd(const float* gy, const float* x, const float* 
     part = (double*)workspace;
   }
   hipLaunchKernelGGL(bn_eval_bwd_kernel, dim3(C, s.ns), dim3(NT), 0, st, gy, x, scale, shift, mean, invstd, gx, part,
-                     dgamma, dbeta, B, C, HW, s.per, s.ns, act_apply, am, streams_vec(HW, x, gy, gx));
+                     dgamma, dbeta, B, C, HW, s.per, s.ns, act, accp, am, streams_vec(HW, x, gy, gx));
   VG_CHECK_LAUNCH();
   if (part) {
     hipLaunchKernelGGL(bn_eval_bwd_finalize_kernel, dim3(cdiv(C, NT)), dim3(NT), 0, st, (const double*)part, s.ns, C,
-                       dgamma, dbeta, accumulate_param_grads ? 1 : 0);
+                       dgamma, dbeta, accp);
     VG_CHECK_LAUNCH();
   }
   return 0;
@@ -1387,7 +1299,7 @@ extern "C" int vg_channel_sum(const float* g, float* out, int B, int C, int HW, 
   const Slicing s = make_slicing(B, C, HW);
   hipLaunchKernelGGL(bn_partial_kernel<2>, dim3(C, s.ns), dim3(NT), 0, st, g, (const float*)nullptr,
                      (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,
-                     part, B, C, HW, s.per, s.ns, 0, (HW & 3) == 0 && ((uintptr_t)g & 15) == 0);      // a view at an odd offset: scalar loads
+                     part, B, C, HW, s.per, s.ns, 0, streams_vec(HW, g));      // a view at an odd offset: scalar loads
   VG_CHECK_LAUNCH();
   hipLaunchKernelGGL(channel_sum_finalize_kernel, dim3(cdiv(C, NT)), dim3(NT), 0, st, (const double*)part, s.ns,
                      C, out);

@@ -2,7 +2,7 @@
 registers is held by T cooperating workgroups, one pass over x and gy) through ops.bn_act_bwd, judged as
 tests/test_bn_gpu.py judges the other paths: gx, dgamma, dbeta per element against the fp64 reference R.bn_bwd with the
 tolerances R.K (from the CPU restatement table; nothing measured from a kernel), the emitted gx_amax exactly, for the
-three activations, with and without the accumulate bit.
+three activations, with and without the accumulate flag.
 
 Forced cases (tuning library, vg_debug_set_bn_team(1, max_wgs): 4096 elements per member) are the smallest shapes that
 reach each edge of the team kernel; the natural cases run the product rule (32768 per member); tests/test_bn_team_cpu.py
@@ -87,7 +87,7 @@ def test_bn_team_bwd(H, shape, nv, max_wgs, act):
     gx3, none_g, none_b = ops.bn_act_bwd(gy, x, gamma, beta, mean, invstd, code, need_param_grads=False)
     assert none_g is None and none_b is None and torch.equal(gx3, gx), what + ": need_param_grads=False changes gx"
 
-    # the accumulate bit: dgamma / dbeta are added to what is there, gx and its bound are what they were
+    # the accumulate flag: dgamma / dbeta are added to what is there, gx and its bound are what they were
     g0, b0 = R.randn(C, seed=31).cuda(), R.randn(C, seed=32).cuda()
     acc_g, acc_b = g0.clone(), b0.clone()
     gx4, rg, rb = ops.bn_act_bwd(gy, x, gamma, beta, mean, invstd, code, accumulate_into=(acc_g, acc_b))

@@ -26,7 +26,9 @@
 //     [parity class][chunk][tap][plane][k-block][cout] x 8 bf16, so a lane's A operand is one 16-byte
 //     global load (32 consecutive cout = 512 contiguous bytes), prefetched one tap ahead.
 //   * The stride-2 transposed convolution runs as its 4 output-parity classes (3x3, 3x2, 2x3, 2x2
-//     taps), exactly as in conv_igemm.hip: one workgroup per (pixel tile, class).
+//     taps; conv_tile.hpp): one workgroup per (pixel tile, class).
+//   * Tap algebra, tile placement, fragment decode, patch address and host geometry are
+//     conv_tile.hpp's, shared with conv_igemm.hip and conv_ring.hip.
 //   * Quad form (conv5x5_bf16split_quad_kernel; <= 32 output channels, 2 planes, grids of >= 256 workgroups): one
 //     workgroup per 8 x 32 input tile computes all four classes.  The four per-class workgroups of a tile stage the
 //     same patch; here it is loaded, scaled, split and written to LDS once, the 25 taps of a chunk run between one
@@ -37,22 +39,11 @@
 //     columns, plane products): the results are bit-identical.  113 -> 85 us per launch at B = 128, 128 -> 32
 //     channels, 32 x 32 -> 64 x 64; WRITE_SIZE 129.5 -> 65.5 MB for the 65.5 MB (2^26 B) output
 //     (profiles/r08_convT_quad.json).
-#include "common.hpp"
-#include "vaegan_hip.h"
+#include "conv_tile.hpp"
 
 namespace {
 
-enum { X_FWD = 0, X_TR = 1 };
 constexpr int XNT = 256;
-
-// 16-byte units per patch row.  Chosen so that the patch rows a
-// 32-pixel fragment spans start on disjoint groups of 16 units (= 256 B, one LDS bank row):
-// fragments of 2 rows x 16 pixels need the two rows 0 (mod 16) apart, 4 rows x 8 pixels 8 (mod 16).
-constexpr int row_units(int TW, int PW) {
-  if (TW == 16) return (PW + 15) & ~15;
-  if (TW == 8) { int c = PW; while ((c & 15) != 8) ++c; return c; }
-  return (PW + 3) & ~3;
-}
 
 // WC x WP wavefronts (WC * WP = 4), FC x FP fragments each: cout tile 32*WC*FC, pixel tile 32*WP*FP
 // NP_: operand planes -- 2: hi/lo split, 3 products ("bf16x3", ~4.5e-6); 3: exact hi/mid/lo split of the fp32
@@ -64,42 +55,18 @@ struct XCfg {
   static constexpr bool F16 = F16_;       // fp16 planes (NP = 2): common.hpp, "split arithmetics"
   static_assert(!F16_ || NP_ == 2, "fp16 planes: hi + lo");
   static constexpr int TN = 32 * WC * FC, TM = NB * TH * TW;
-  static constexpr int NTMAX = (MODE == X_FWD) ? 5 : (5 + S - 1) / S;
-  static constexpr int PH = (MODE == X_FWD) ? S * (TH - 1) + 5 : TH + NTMAX - 1;
-  static constexpr int PW = (MODE == X_FWD) ? S * (TW - 1) + 5 : TW + NTMAX - 1;
-  static_assert(MODE == X_TR || S == 1, "the stride-2 forward convolution runs in conv_ring.hip");
+  using Taps = TileTaps<MODE, S, TH, TW>;
+  static constexpr int NTMAX = Taps::NTMAX, PH = Taps::PH, PW = Taps::PW, NCLS = Taps::NCLS;
+  static_assert(MODE == CONV_TR || S == 1, "the stride-2 forward convolution runs in conv_ring.hip");
   static constexpr int ROWU = row_units(TW, PW);                  // units per patch row
   static constexpr int IMGU = NB * PH * ROWU;                     // units per (plane, k-block) image
   static constexpr int NUNIT = 2 * NB * PH * PW;                  // staged units per chunk
   static constexpr int NQ = cdiv(NUNIT, XNT);
-  static constexpr int NCLS = (MODE == X_FWD) ? 1 : S * S;
   static_assert(TM == 32 * WP * FP, "pixel tile");
   static_assert(WC == 1 || WC == 2 || WC == 4, "wavefront grid");
 };
 
-struct XArgs {
-  const float* x;
-  const bf16x8* w;     // packed filter
-  const float* bias;
-  float* y;
-  int B, Cin, XH, XW, Cout, CoutP, YH, YW;
-  int ntiles_n, tiles_w, tiles_hw, blocks_per_cls;
-  int ksplit, cps;       // forward only: grid-level split of the channel chunks (deep-K, small-grid layers)
-  size_t ysplit;         // elements per partial output slab (then y points at the slabs)
-  const float* in_amax;  // fp16 planes: in_amax[0] >= max |x| (device); w_unscale[0]: the pack's trailer
-  const float* w_unscale;
-};
-
-// taps of the output-parity classes before (R, SS) (same order as conv_igemm.hip)
-__host__ __device__ constexpr int x_taps_before(int S, int R, int SS) {
-  int n = 0;
-  for (int r = 0; r < S; ++r)
-    for (int s = 0; s < S; ++s) {
-      if (r == R && s == SS) return n;
-      n += ((5 - r + S - 1) / S) * ((5 - s + S - 1) / S);
-    }
-  return n;
-}
+using XArgs = SplitGeom;      // the K split (cps, ysplit) is forward only: deep-K, small-grid layers
 
 // Quad form of the stride-2 transposed convolution: one workgroup runs the 25 taps of a chunk for all four parity
 // classes.  Step i is tap (a, b) of class cls = 2 R + SS; the steps walk the 3 x 3 patch offsets (2 - a, 2 - b) row by
@@ -119,11 +86,10 @@ constexpr XQStep x_quad_step(int i) {
 }
 static_assert(x_quad_step(24).a == 2 && x_quad_step(24).b == 2 && x_quad_step(24).cls == 0 && x_quad_step(9).cls == 2 && x_quad_step(17).cls == 3, "25 steps");
 
-template <int I> struct XIdx { static constexpr int value = I; };
 template <int I, int N, class F>
-__device__ __forceinline__ void x_static_for(F&& f) {      // f(XIdx<I>) ... f(XIdx<N - 1>): the index is a constant in f
+__device__ __forceinline__ void x_static_for(F&& f) {      // f(IntC<I>) ... f(IntC<N - 1>): the index is a constant in f
   if constexpr (I < N) {
-    f(XIdx<I>{});
+    f(IntC<I>{});
     x_static_for<I + 1, N>(f);
   }
 }
@@ -135,36 +101,20 @@ __device__ __forceinline__ void bf16split_body(const XArgs& A, f32x4* lds, int b
   constexpr int ROWU = C::ROWU, IMGU = C::IMGU, NQ = C::NQ, FC = C::FC, FP = C::FP, NP = C::NP;
   constexpr int NTMAX = C::NTMAX;
   constexpr bool F16 = C::F16;
-  constexpr int NTH = (MODE == X_FWD) ? 5 : (5 - R + S - 1) / S;   // taps along h / w in this class
-  constexpr int NTW = (MODE == X_FWD) ? 5 : (5 - SS + S - 1) / S;
+  constexpr int NTH = C::Taps::nth(R), NTW = C::Taps::nth(SS);     // taps along h / w in this class
   constexpr int NTAP = NTH * NTW;
-  constexpr int PSTEP = (MODE == X_FWD) ? S : 1;                   // patch rows / columns per tile pixel
+  constexpr int PSTEP = C::Taps::PSTEP;
   constexpr int NACC = QUAD ? 4 : FC;                              // accumulator sets: one per class / per cout fragment
-  static_assert(!QUAD || (MODE == X_TR && S == 2 && C::WC == 1 && FC == 1 && NP == 2 && R == 0 && SS == 0), "quad form");
+  static_assert(!QUAD || (MODE == CONV_TR && S == 2 && C::WC == 1 && FC == 1 && NP == 2 && R == 0 && SS == 0), "quad form");
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int kb = lane >> 5, l32 = lane & 31;
   const int wc = wid % C::WC, wp = wid / C::WC;
-  // XCD-aware placement, as in conv_igemm.hip: the cout tiles of one pixel tile share an XCD
   int nt, pt;
-  {
-    const int ntn = A.ntiles_n, npatch = A.blocks_per_cls / ntn, full = (npatch / 8) * 8 * ntn;
-    if (bid < full) {
-      const int xcd = bid & 7, j = bid >> 3;
-      pt = (j / ntn) * 8 + xcd;
-      nt = j % ntn;
-    } else {
-      const int t = bid - full;
-      pt = (npatch / 8) * 8 + t / ntn;
-      nt = t % ntn;
-    }
-  }
-  const int sp = pt % A.tiles_hw, bg = pt / A.tiles_hw;
-  const int th0 = (sp / A.tiles_w) * TH, tw0 = (sp % A.tiles_w) * TW;
-  const int b0 = bg * NB, n0 = nt * C::TN;
-  const int Cin = A.Cin, Cout = A.Cout, XH = A.XH, XW = A.XW, HW = XH * XW;
-  const int ih0 = (MODE == X_FWD) ? th0 * S - 2 : th0 - (NTMAX - 1 - 2 / S);
-  const int iw0 = (MODE == X_FWD) ? tw0 * S - 2 : tw0 - (NTMAX - 1 - 2 / S);
+  place_tile<false>(bid, A.ntiles_n, A.blocks_per_cls, nt, pt);
+  const TileOrigin org = tile_origin<C>(pt, nt, A);
+  const int b0 = org.b0, n0 = org.n0;
+  const int Cin = A.Cin, Cout = A.Cout, HW = A.XH * A.XW;
   const float* xb = A.x + (size_t)b0 * Cin * HW;
 
   // ---- staging map: unit e = (k-block, image, row, column); addresses clamped, validity masked
@@ -178,12 +128,10 @@ __device__ __forceinline__ void bf16split_body(const XArgs& A, f32x4* lds, int b
     const int r = t % PH;
     t /= PH;
     const int nb = t % NB, kbs = min(t / NB, 1);
-    const int ih = ih0 + r, iw = iw0 + col;
-    const bool ok = (e < C::NUNIT) && ih >= 0 && ih < XH && iw >= 0 && iw < XW && (b0 + nb) < A.B;
-    const int nbc = min(nb, A.B - 1 - b0), ihc = min(max(ih, 0), XH - 1), iwc = min(max(iw, 0), XW - 1);
-    pofs[q] = (nbc * Cin + kbs * 8) * HW + ihc * XW + iwc;
+    const PatchElem pe = patch_elem(A, org, nb, r, col, e < C::NUNIT);
+    pofs[q] = pe.ofs + kbs * 8 * HW;
     pdst[q] = (e < C::NUNIT) ? kbs * IMGU + (nb * PH + r) * ROWU + col : -1;
-    pvalid |= ok ? (1u << q) : 0u;
+    pvalid |= pe.ok ? (1u << q) : 0u;
   }
   static_assert(NQ <= 32, "validity mask");
 
@@ -223,9 +171,8 @@ __device__ __forceinline__ void bf16split_body(const XArgs& A, f32x4* lds, int b
   int base_b[FP];
 #pragma unroll
   for (int f = 0; f < FP; ++f) {
-    const int m = (wp * FP + f) * 32 + l32;
-    const int nb = m / (TH * TW), r = m % (TH * TW);
-    base_b[f] = kb * IMGU + (nb * PH + PSTEP * (r / TW)) * ROWU + PSTEP * (r % TW);
+    const FragPixel fp = frag_pixel<C>(wp, f, l32);
+    base_b[f] = kb * IMGU + (fp.nb * PH + PSTEP * fp.row) * ROWU + PSTEP * fp.col;
   }
   const int CoutP = A.CoutP;
   const size_t wstep = (size_t)2 * NP * CoutP;    // units per (chunk, tap) step
@@ -233,7 +180,7 @@ __device__ __forceinline__ void bf16split_body(const XArgs& A, f32x4* lds, int b
   const bf16x8* wa[FC];                      // this class' first step, this lane's cout and k-block
 #pragma unroll
   for (int g = 0; g < FC; ++g)
-    wa[g] = A.w + (size_t)x_taps_before(S, R, SS) * nchunks * wstep + (size_t)kb * CoutP + n0 + (wc * FC + g) * 32 + l32;
+    wa[g] = A.w + (size_t)class_taps_before(S, R, SS) * nchunks * wstep + (size_t)kb * CoutP + n0 + (wc * FC + g) * 32 + l32;
 
   f32x16 acc[NACC][FP];
 #pragma unroll
@@ -276,7 +223,7 @@ __device__ __forceinline__ void bf16split_body(const XArgs& A, f32x4* lds, int b
         constexpr int cur = i & 1, nxt = cur ^ 1, o = s.a * 3 + s.b;
         constexpr bool first = i == 0 || before.a != s.a || before.b != s.b;
         constexpr int nntw = 3 - n.cls % 2, nntap = (3 - n.cls / 2) * nntw;
-        const size_t nstep = (size_t)x_taps_before(S, n.cls / 2, n.cls % 2) * nchunks + (size_t)(ch + (i == 24 ? 1 : 0)) * nntap +
+        const size_t nstep = (size_t)class_taps_before(S, n.cls / 2, n.cls % 2) * nchunks + (size_t)(ch + (i == 24 ? 1 : 0)) * nntap +
                              n.a * nntw + n.b;
 #pragma unroll
         for (int p = 0; p < NP; ++p) av[nxt][0][p] = wa[0][nstep * wstep + (size_t)p * 2 * CoutP];
@@ -301,7 +248,7 @@ __device__ __forceinline__ void bf16split_body(const XArgs& A, f32x4* lds, int b
         const bf16x8* wrow[FC];
 #pragma unroll
         for (int g = 0; g < FC; ++g) wrow[g] = wa[g] + ((size_t)ch * NTAP + ta * NTW) * wstep;
-        const int rowoff = (MODE == X_FWD) ? ta * ROWU : (NTMAX - 1 - ta) * ROWU;
+        const int rowoff = (MODE == CONV_FWD) ? ta * ROWU : (NTMAX - 1 - ta) * ROWU;
         // Pinned software pipeline (hipcc otherwise sinks the prefetch loads next to their first use, one
         // vmcnt wait per MFMA pair): at the top of a tap issue the NEXT tap's filter fragments (global) and
         // pixel fragments (LDS, within the row), then run this tap's MFMAs on registers loaded a tap ago.
@@ -309,7 +256,7 @@ __device__ __forceinline__ void bf16split_body(const XArgs& A, f32x4* lds, int b
         constexpr bool PIN = (NP == 2) || C::WC == 4;   // 3 planes, 2 x 2 fragments: pinning makes the allocator spill
         bf16x8 bv[BPF ? 2 : 1][FP][NP];
         auto read_b = [&](int buf, int t) {
-          const int imm = (MODE == X_TR) ? (NTMAX - 1 - t) : t;
+          const int imm = (MODE == CONV_TR) ? (NTMAX - 1 - t) : t;
 #pragma unroll
           for (int f = 0; f < FP; ++f)
 #pragma unroll
@@ -366,21 +313,20 @@ __device__ __forceinline__ void bf16split_body(const XArgs& A, f32x4* lds, int b
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[g][f][r] = acc[g][f][r] * x_unscale * w_unscale;
   }
-  // ---- epilogue: + bias, NCHW store (as conv_igemm.hip)
-  const int YH = A.YH, YW = A.YW;
+  // ---- epilogue: + bias, NCHW store
   if constexpr (QUAD) {
     // A lane holds the 2 x 2 output block of its pixel for 16 channels: the two columns of a row go out as one 8-byte
     // store (32 lanes = 256 contiguous bytes per row and channel) where the row has both and the address allows it.
     typedef float f32x2 __attribute__((ext_vector_type(2)));
+    const int YH = A.YH, YW = A.YW;
     const bool pair8 = ((uintptr_t)A.y & 7) == 0 && (YW & 1) == 0;
     float bq[16];
 #pragma unroll
     for (int r16 = 0; r16 < 16; ++r16) bq[r16] = A.bias ? A.bias[min(n0 + acc_row(r16, lane), Cout - 1)] : 0.f;
 #pragma unroll
     for (int f = 0; f < FP; ++f) {
-      const int m = (wp * FP + f) * 32 + l32;
-      const int nb = m / (TH * TW), r = m % (TH * TW);
-      const int th = th0 + r / TW, tw = tw0 + r % TW, b = b0 + nb, ow = S * tw;
+      const FragPixel fp = frag_pixel<C>(wp, f, l32);
+      const int th = org.th0 + fp.row, tw = org.tw0 + fp.col, b = b0 + fp.nb, ow = S * tw;
 #pragma unroll
       for (int rr = 0; rr < 2; ++rr) {
         const int oh = S * th + rr;
@@ -402,15 +348,15 @@ __device__ __forceinline__ void bf16split_body(const XArgs& A, f32x4* lds, int b
         }
       }
     }
-    return;
-  }
+  } else {
+    const int YH = A.YH, YW = A.YW;
 #pragma unroll
   for (int f = 0; f < FP; ++f) {
     const int m = (wp * FP + f) * 32 + l32;
     const int nb = m / (TH * TW), r = m % (TH * TW);
-    const int th = th0 + r / TW, tw = tw0 + r % TW, b = b0 + nb;
-    const int oh = (MODE == X_FWD) ? th : S * th + R;
-    const int ow = (MODE == X_FWD) ? tw : S * tw + SS;
+    const int th = org.th0 + r / TW, tw = org.tw0 + r % TW, b = b0 + nb;
+    const int oh = (MODE == CONV_FWD) ? th : S * th + R;
+    const int ow = (MODE == CONV_FWD) ? tw : S * tw + SS;
     const bool pok = b < A.B && oh < YH && ow < YW;
     float* yb = A.y + (size_t)split * A.ysplit + ((size_t)b * Cout * YH + oh) * YW + ow;
 #pragma unroll
@@ -428,6 +374,7 @@ __device__ __forceinline__ void bf16split_body(const XArgs& A, f32x4* lds, int b
       }
     }
   }
+  }
 }
 
 template <class C>
@@ -440,12 +387,9 @@ __global__ __launch_bounds__(XNT, 2) void conv5x5_bf16split_kernel(XArgs A) {
   } else {
     const int cls = bid / A.blocks_per_cls;   // class 0 (3x3 taps) first: longest blocks start earliest
     bid -= cls * A.blocks_per_cls;
-    switch (cls) {
-      case 0: bf16split_body<C, 0, 0>(A, lds, bid, 0); break;
-      case 1: bf16split_body<C, 0, 1>(A, lds, bid, 0); break;
-      case 2: bf16split_body<C, 1, 0>(A, lds, bid, 0); break;
-      default: bf16split_body<C, 1, 1>(A, lds, bid, 0); break;
-    }
+    for_class(cls, [&](auto R, auto SS) __attribute__((always_inline)) {
+      bf16split_body<C, decltype(R)::value, decltype(SS)::value>(A, lds, bid, 0);
+    });
   }
 }
 
@@ -465,40 +409,16 @@ template <class C, bool QUAD = false>
 int launch_x(const float* x, const bf16x8* w, const float* bias, float* y, int B, int Cin, int XH, int XW, int Cout,
              XSplit xs, hipStream_t st) {
   XArgs A;
-  A.x = x; A.w = w; A.bias = bias; A.y = y;
-  A.B = B; A.Cin = Cin; A.XH = XH; A.XW = XW; A.Cout = Cout; A.CoutP = (Cout + 127) & ~127;
-  int tsh, tsw;
-  if (C::MODE == X_FWD) {
-    A.YH = (XH - 1) / C::S + 1; A.YW = (XW - 1) / C::S + 1;
-    tsh = A.YH; tsw = A.YW;
-  } else {
-    A.YH = XH * C::S; A.YW = XW * C::S;
-    tsh = XH; tsw = XW;
-  }
-  A.tiles_w = cdiv(tsw, C::TW);
-  A.tiles_hw = cdiv(tsh, C::TH) * A.tiles_w;
-  A.ntiles_n = cdiv(Cout, C::TN);
-  const long per_cls = (long)A.ntiles_n * A.tiles_hw * cdiv(B, C::NB);
-  const int ksplit = (C::MODE == X_FWD) ? xs.k : 1;
+  const int ksplit = (C::MODE == CONV_FWD) ? xs.k : 1;
+  const long per_cls = fill_split<C>(A, x, w, bias, y, B, Cin, XH, XW, Cout, ksplit, xs.slabs, xs.in_amax);
   const long grid = per_cls * (QUAD ? 1 : C::NCLS) * ksplit;
-  if (grid <= 0 || grid > 0x7fffffffL) return VG_ERR_BAD_ARG;
-  A.blocks_per_cls = (int)per_cls;
-  A.ksplit = ksplit;
-  A.cps = cdiv(Cin / 16, ksplit);
-  A.ysplit = (size_t)B * Cout * A.YH * A.YW;
-  if (ksplit > 1) A.y = xs.slabs;
-  A.in_amax = xs.in_amax;
-  A.w_unscale = (const float*)(w + vg_pack_trailer_units(Cin / 16 * 25, C::NP, A.CoutP));      // the pack's trailer
+  if (!grid_ok(grid)) return VG_ERR_BAD_ARG;
   if constexpr (QUAD)
     hipLaunchKernelGGL(conv5x5_bf16split_quad_kernel<C>, dim3((unsigned)grid), dim3(XNT), 0, st, A);
   else
     hipLaunchKernelGGL(conv5x5_bf16split_kernel<C>, dim3((unsigned)grid), dim3(XNT), 0, st, A);
   VG_CHECK_LAUNCH();
-  if (ksplit > 1) {
-    if (A.ysplit > 0x7fffffffUL) return VG_ERR_BAD_ARG;
-    return vg_internal_wgrad_reduce(xs.slabs, y, (int)A.ysplit, ksplit, st);   // fixed-order sum of the slabs
-  }
-  return 0;
+  return reduce_slabs(A, xs.slabs, y, ksplit, st);
 }
 
 // diagnostics: 0 = 128 cout x 128 px, 1 = 64 x 128, 2 = 64 x 64, 3 = 32 cout x 128 px, 4 = 32 x 256 (transposed, one workgroup
@@ -508,7 +428,7 @@ VG_KNOB(int, g_x_tile_override, -1);
 template <int MODE, int S, int WC, int FC, int FP, int NP, bool F16>
 int dispatch_geom(const float* x, const bf16x8* w, const float* bias, float* y, int B, int Cin, int XH, int XW,
                   int Cout, XSplit xs, hipStream_t st) {
-  const int tsw = (MODE == X_FWD) ? (XW - 1) / S + 1 : XW;
+  const int tsw = tile_extent(MODE, S, XW);
   constexpr int TM = 32 * (4 / WC) * FP;
   if constexpr (TM == 128) {
     if (tsw >= 32) return launch_x<XCfg<MODE, S, 1, 4, 32, WC, FC, FP, NP, F16>>(x, w, bias, y, B, Cin, XH, XW, Cout, xs, st);
@@ -530,12 +450,12 @@ int dispatch_geom(const float* x, const bf16x8* w, const float* bias, float* y, 
 template <int MODE, int S, int NP, bool F16 = false>
 int dispatch_x(const float* x, const bf16x8* w, const float* bias, float* y, int B, int Cin, int XH, int XW, int Cout,
                XSplit xs, hipStream_t st) {
-  const int tsw = (MODE == X_FWD) ? (XW - 1) / S + 1 : XW, tsh = (MODE == X_FWD) ? (XH - 1) / S + 1 : XH;
-  const int ncls = (MODE == X_TR) ? S * S : 1;
+  const int tsw = tile_extent(MODE, S, XW), tsh = tile_extent(MODE, S, XH);
+  const int ncls = (MODE == CONV_TR) ? S * S : 1;
   const long px128 = (long)cdiv(B * cdiv(tsh, 8) * cdiv(tsw, 8) * 64, 128) * ncls;
   int var = 2;
-  if (Cout <= 32) var = (MODE == X_TR && px128 >= 1024) ? 4 : 3;      // transposed, large grid: 256 pixels per workgroup
-  else if (MODE == X_FWD && Cout > 64 && px128 * cdiv(Cout, 128) >= 512) var = 0;   // transposed: 64 x 128 measured faster
+  if (Cout <= 32) var = (MODE == CONV_TR && px128 >= 1024) ? 4 : 3;      // transposed, large grid: 256 pixels per workgroup
+  else if (MODE == CONV_FWD && Cout > 64 && px128 * cdiv(Cout, 128) >= 512) var = 0;   // transposed: 64 x 128 measured faster
   else if (px128 * cdiv(Cout, 64) >= 512) var = 1;
   // 3 planes: the 128 x 128 tile with the four wavefronts along cout (each loads only its own filter fragment)
   // measured 0-15 % faster than the 2 x 2 arrangement, never slower
@@ -543,17 +463,17 @@ int dispatch_x(const float* x, const bf16x8* w, const float* bias, float* y, int
   // stride 2, 2 planes, images at least one 8 x 32 tile wide: the quad form of that tile (bit-identical to variant 4),
   // once its grid -- a quarter of the per-class one -- has a workgroup for every CU.  Measured (profiles/r08_convT_quad.json):
   // 0.56 - 0.89 of the per-class time at 256 and 512 workgroups, 1.0 - 1.5 of it at 128.
-  constexpr bool HAS_QUAD = MODE == X_TR && S == 2 && NP == 2;
+  constexpr bool HAS_QUAD = MODE == CONV_TR && S == 2 && NP == 2;
   if (HAS_QUAD && var == 4 && tsw >= 32 && (long)B * cdiv(tsh, 8) * cdiv(tsw, 32) >= 256) var = 6;
-  if (MODE == X_FWD && xs.k > 1) var = 0;             // split-K is sized for the 128 x 128 tile
-  else if (g_x_tile_override >= 0 && g_x_tile_override <= 6 && !(g_x_tile_override == 4 && MODE == X_FWD) &&
+  if (MODE == CONV_FWD && xs.k > 1) var = 0;             // split-K is sized for the 128 x 128 tile
+  else if (g_x_tile_override >= 0 && g_x_tile_override <= 6 && !(g_x_tile_override == 4 && MODE == CONV_FWD) &&
            !(g_x_tile_override == 6 && !HAS_QUAD))
     var = g_x_tile_override;
   if (var == 0) return dispatch_geom<MODE, S, 2, 2, 2, NP, F16>(x, w, bias, y, B, Cin, XH, XW, Cout, xs, st);
   if (var == 1) return dispatch_geom<MODE, S, 2, 1, 2, NP, F16>(x, w, bias, y, B, Cin, XH, XW, Cout, xs, st);
   if (var == 3) return dispatch_geom<MODE, S, 1, 1, 1, NP, F16>(x, w, bias, y, B, Cin, XH, XW, Cout, xs, st);
   if (var == 5) return dispatch_geom<MODE, S, 4, 1, 4, NP, F16>(x, w, bias, y, B, Cin, XH, XW, Cout, xs, st);   // 4 wavefronts along cout
-  if constexpr (MODE == X_TR) {
+  if constexpr (MODE == CONV_TR) {
     if (var == 4) return dispatch_geom<MODE, S, 1, 1, 2, NP, F16>(x, w, bias, y, B, Cin, XH, XW, Cout, xs, st);
   }
   if constexpr (HAS_QUAD) {     // one geometry: the 8 x 32 tile, whatever the image (narrower ones are masked)
@@ -633,36 +553,19 @@ __device__ __forceinline__ void pack_bf16split_body(float* T, const float* __res
       tap = (q < 12) ? 2 * q + kb : (q == 12 ? 24 : 2 * (q - 13) + kb);
     } else if (transposed) {                     // parity classes, class-major step order
       const int kh = q / 5, kw = q - 5 * kh;
-      const int R = kh % S, SS = kw % S;
-      int base = 0;
-      for (int r2 = 0; r2 < S; ++r2)
-        for (int s2 = 0; s2 < S; ++s2)
-          if (r2 < R || (r2 == R && s2 < SS)) base += ((5 - r2 + S - 1) / S) * ((5 - s2 + S - 1) / S) * nchunks;
-      const int nth = (5 - R + S - 1) / S, ntw = (5 - SS + S - 1) / S;
-      step = base + c16 * (nth * ntw) + (kh / S) * ntw + kw / S;
+      const int R = kh % S, SS = kw % S, ntw = class_taps(S, SS);
+      step = class_taps_before(S, R, SS) * nchunks + c16 * (class_taps(S, R) * ntw) + (kh / S) * ntw + kw / S;
     }
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = T[col * PK_PITCH + (half * 8 + j) * 25 + tap] * wscale;
-    if (f16) {
-      f32x4 q2[2];
-      split_planes16<2, true>(v, q2);
-      if (cok) {
-        p[((size_t)step * 4 + kb) * CoutP + co0 + col] = __builtin_bit_cast(bf16x8, q2[0]);
-        p[((size_t)step * 4 + 2 + kb) * CoutP + co0 + col] = __builtin_bit_cast(bf16x8, q2[1]);
-      }
-      continue;
-    }
-    for (int pl = 0; pl < planes; ++pl) {       // hi, (mid,) lo
-      bf16x8 qv;
+    f32x4 pl[3];                                 // hi, (mid,) lo
+    if (f16) split_planes16<2, true>(v, pl);
+    else if (planes == 2) split_planes16<2, false>(v, pl);
+    else split_planes16<3, false>(v, pl);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const __bf16 h = (__bf16)v[j];
-        qv[j] = h;
-        v[j] -= (float)h;
-      }
-      if (cok) p[((size_t)step * planes * 2 + pl * 2 + kb) * CoutP + co0 + col] = qv;
-    }
+    for (int k = 0; k < 3; ++k)
+      if (cok && k < planes) p[((size_t)step * planes * 2 + k * 2 + kb) * CoutP + co0 + col] = __builtin_bit_cast(bf16x8, pl[k]);
   }
   // the spare steps (the DMA ring's run-ahead reads them): zeros, written by the first chunk's workgroups
   if (c16 == 0 && cok) {
@@ -696,7 +599,7 @@ __global__ __launch_bounds__(256) void pack_bf16split_multi_kernel(PackBatch P, 
   __shared__ float T[PK_CO * PK_PITCH];
   int t = 0;
   while (t + 1 < P.count && blockIdx.x >= P.first_block[t + 1]) ++t;
-  const int CoutP = (P.Cout[t] + 127) & ~127, nbx = CoutP / PK_CO;
+  const int CoutP = packed_cout(P.Cout[t]), nbx = CoutP / PK_CO;
   const int b = blockIdx.x - P.first_block[t];
   pack_bf16split_body(T, P.w[t], P.p[t], P.Cout[t], P.Cin[t], CoutP, P.Cin[t] / 16 * 25, P.transposed[t], P.S[t], planes,
                       P.w_amax[t], b % nbx, b / nbx);
@@ -706,7 +609,7 @@ __global__ __launch_bounds__(256) void pack_bf16split_multi_kernel(PackBatch P, 
 // over k workgroups, partial outputs summed in a fixed order.  1 = no split.
 int fwd_ksplit(int B, int Cin, int H, int W, int Cout, int S) {
   if (g_x_tile_override >= 0) return 1;
-  const int tsw = (W - 1) / S + 1, tsh = (H - 1) / S + 1, nchunks = Cin / 16;
+  const int tsw = tile_extent(CONV_FWD, S, W), tsh = tile_extent(CONV_FWD, S, H), nchunks = Cin / 16;
   const long wgs = (long)cdiv(B * cdiv(tsh, 8) * cdiv(tsw, 8) * 64, 128) * cdiv(Cout, 128);
   if (Cout <= 64 || wgs >= 512 || nchunks < 8) return 1;
   int k = 2;     // every split must own at least one chunk: (k - 1) * ceil(nchunks / k) < nchunks
@@ -714,13 +617,37 @@ int fwd_ksplit(int B, int Cin, int H, int W, int Cout, int S) {
   return k;
 }
 
-// 2 / 3 bf16 planes, or 2 fp16 planes (VG_PLANES_F16 | 2)
-int planes_ok(int planes) { return planes == 2 || planes == 3 || planes == (VG_PLANES_F16_FLAG | 2); }
+// the shape every entry point of the split arithmetics takes
+bool shape_ok(int B, int Cin, int H, int W, int Cout, int stride, int planes) {
+  if (B <= 0 || Cin <= 0 || Cin % 16 || Cout <= 0 || H <= 0 || W <= 0) return false;
+  return (stride == 1 || stride == 2) && planes_ok(planes);
+}
 
-int x_args_ok(const float* x, const void* packed, float* y, int B, int Cin, int H, int W, int Cout, int stride,
-              int planes) {
-  if (!x || !packed || !y || B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return 0;
-  return (stride == 1 || stride == 2) && Cin % 16 == 0 && ((uintptr_t)packed & 15) == 0 && planes_ok(planes);
+bool x_args_ok(const float* x, const void* packed, float* y, int B, int Cin, int H, int W, int Cout, int stride, int planes) {
+  return x && packed && y && ((uintptr_t)packed & 15) == 0 && shape_ok(B, Cin, H, W, Cout, stride, planes);
+}
+
+// Stride 2 runs on the 8-wave ring kernel (conv_ring.hip) -- except transposed convolutions with <= 64 output
+// channels, whose thin tiles (32 cout x 128 / 256 pixels) live here; stride 1 runs here.
+bool on_ring(int mode, int Cout, int stride) { return stride == 2 && (mode == CONV_FWD || Cout > 64); }
+
+// The layers that stay here take no fusion (vg_conv5x5_bf16split_fusable says which do); in_amax is not one.
+bool fuse_empty(const vg_conv_fusion* f) { return !f || (!f->in_scale && !f->in_shift && !f->stats); }
+
+// (planes, stride) -> dispatch_x<MODE, S, NP, F16>
+template <int MODE>
+int dispatch_planes(const float* x, const void* packed, const float* bias, float* y, int B, int Cin, int H, int W, int Cout,
+                    int stride, int planes, int ksplit, void* workspace, const vg_conv_fusion* fuse, hipStream_t st) {
+  const XSplit xs = {ksplit, (float*)workspace, fuse ? fuse->in_amax : nullptr};
+  if ((planes & VG_PLANES_F16_FLAG) && !xs.in_amax) return VG_ERR_BAD_ARG;
+  return for_planes(planes, [&](auto np, auto f16) {
+    auto run = [&](auto s) {
+      return dispatch_x<MODE, decltype(s)::value, decltype(np)::value, decltype(f16)::value != 0>(
+          x, (const bf16x8*)packed, bias, y, B, Cin, H, W, Cout, xs, st);
+    };
+    if constexpr (MODE == CONV_FWD) return run(IntC<1>{});
+    else return for_stride(stride, run);
+  });
 }
 
 }  // namespace
@@ -740,7 +667,7 @@ extern "C" int vg_debug_set_conv_ring_tile(int variant) {
 extern "C" size_t vg_conv5x5_packed_bf16split_bytes(int Cout, int Cin, int planes) {
   if (Cout <= 0 || Cin <= 0 || Cin % 16 || !planes_ok(planes)) return 0;
   // fp16 planes: + a 16-byte trailer holding the inverse of the filter's power-of-two scale
-  return vg_pack_trailer_units(Cin / 16 * 25, planes & 0xff, (Cout + 127) & ~127) * 16 +
+  return vg_pack_trailer_units(Cin / 16 * 25, planes & 0xff, packed_cout(Cout)) * 16 +
          ((planes & VG_PLANES_F16_FLAG) ? 16 : 0);
 }
 
@@ -749,7 +676,7 @@ extern "C" int vg_conv5x5_pack_bf16split(const float* w, void* packed, int Cout,
   if (!w || !packed || Cout <= 0 || Cin <= 0 || Cin % 16 || ((uintptr_t)packed & 15)) return VG_ERR_BAD_ARG;
   if ((stride != 1 && stride != 2) || !planes_ok(planes)) return VG_ERR_BAD_ARG;
   if ((planes & VG_PLANES_F16_FLAG) && !w_amax) return VG_ERR_BAD_ARG;
-  const int CoutP = (Cout + 127) & ~127, nsteps = Cin / 16 * 25;
+  const int CoutP = packed_cout(Cout), nsteps = Cin / 16 * 25;
   hipLaunchKernelGGL(pack_bf16split_kernel, dim3(CoutP / PK_CO, Cin / 16), dim3(256), 0,
                      (hipStream_t)stream, w, (bf16x8*)packed, Cout, Cin, CoutP, nsteps, transposed ? 1 : 0, stride, planes,
                      w_amax);
@@ -774,7 +701,7 @@ extern "C" int vg_conv5x5_pack_bf16split_multi(const VgPackEntry* entries, int c
       P.w[k] = E.w; P.p[k] = (bf16x8*)E.packed; P.Cout[k] = E.Cout; P.Cin[k] = E.Cin;
       P.transposed[k] = E.transposed ? 1 : 0; P.S[k] = E.stride;
       P.first_block[k] = blocks;
-      blocks += (unsigned)(((E.Cout + 127) & ~127) / PK_CO) * (unsigned)(E.Cin / 16);
+      blocks += (unsigned)(packed_cout(E.Cout) / PK_CO) * (unsigned)(E.Cin / 16);
     }
     P.first_block[P.count] = blocks;
     hipLaunchKernelGGL(pack_bf16split_multi_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, P, planes);
@@ -783,33 +710,27 @@ extern "C" int vg_conv5x5_pack_bf16split_multi(const VgPackEntry* entries, int c
   return 0;
 }
 
-// Stride 2 runs on the 8-wave ring kernel (conv_ring.hip) -- except transposed convolutions with <= 64 output
-// channels, whose thin tiles (32 cout x 128 / 256 pixels) live here; stride 1 runs here.
-static bool tr_on_ring(int Cout, int stride) { return stride == 2 && Cout > 64; }
-
 extern "C" size_t vg_conv5x5_fwd_bf16split_workspace_bytes(int B, int Cin, int H, int W, int Cout, int stride, int planes) {
-  if (B <= 0 || Cin <= 0 || Cin % 16 || Cout <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2) || !planes_ok(planes)) return 0;
-  if (stride == 2) return vg_internal_ring_workspace_bytes(0, B, Cin, H, W, Cout, planes);
+  if (!shape_ok(B, Cin, H, W, Cout, stride, planes)) return 0;
+  if (stride == 2) return vg_internal_ring_workspace_bytes(CONV_FWD, B, Cin, H, W, Cout, planes);
   const int k = fwd_ksplit(B, Cin, H, W, Cout, stride);
   if (k <= 1) return 0;
-  return (size_t)k * B * Cout * ((H - 1) / stride + 1) * ((W - 1) / stride + 1) * sizeof(float);
+  return (size_t)k * B * Cout * out_extent(CONV_FWD, stride, H) * out_extent(CONV_FWD, stride, W) * sizeof(float);
 }
-
-static bool fuse_empty(const vg_conv_fusion* f) { return !f || (!f->in_scale && !f->in_shift && !f->stats); }   // in_amax is not a fusion
 
 extern "C" int vg_conv5x5_bf16split_fusable(int transposed, int Cin, int Cout, int stride) {
   if (Cin <= 0 || Cin % 16 || Cout <= 0) return 0;
-  return transposed ? (tr_on_ring(Cout, stride) ? 1 : 0) : (stride == 2 ? 1 : 0);
+  return on_ring(transposed ? CONV_TR : CONV_FWD, Cout, stride) ? 1 : 0;
 }
 
 extern "C" size_t vg_conv5x5_fwd_bf16split_stats_floats(int B, int Cin, int H, int W, int Cout, int stride, int planes) {
-  if (B <= 0 || Cin <= 0 || Cin % 16 || Cout <= 0 || H <= 0 || W <= 0 || stride != 2 || !planes_ok(planes)) return 0;
-  return vg_internal_ring_stats_floats(0, B, Cin, H, W, Cout, planes);
+  if (!shape_ok(B, Cin, H, W, Cout, stride, planes) || !on_ring(CONV_FWD, Cout, stride)) return 0;
+  return vg_internal_ring_stats_floats(CONV_FWD, B, Cin, H, W, Cout, planes);
 }
 
 extern "C" size_t vg_convT5x5_fwd_bf16split_stats_floats(int B, int Cin, int H, int W, int Cout, int stride, int planes) {
-  if (B <= 0 || Cin <= 0 || Cin % 16 || Cout <= 0 || H <= 0 || W <= 0 || !tr_on_ring(Cout, stride) || !planes_ok(planes)) return 0;
-  return vg_internal_ring_stats_floats(1, B, Cin, H, W, Cout, planes);
+  if (!shape_ok(B, Cin, H, W, Cout, stride, planes) || !on_ring(CONV_TR, Cout, stride)) return 0;
+  return vg_internal_ring_stats_floats(CONV_TR, B, Cin, H, W, Cout, planes);
 }
 
 extern "C" int vg_conv5x5_fwd_bf16split(const float* x, const void* packed, const float* bias, float* y, int B, int Cin,
@@ -817,27 +738,18 @@ extern "C" int vg_conv5x5_fwd_bf16split(const float* x, const void* packed, cons
                                      size_t workspace_bytes, const vg_conv_fusion* fuse, void* stream) {
   if (!x_args_ok(x, packed, y, B, Cin, H, W, Cout, stride, planes)) return VG_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
-  if (stride == 2)
-    return vg_internal_ring_conv(0, x, packed, bias, y, B, Cin, H, W, Cout, planes, workspace, workspace_bytes,
-                                 fuse ? fuse->in_scale : nullptr, fuse ? fuse->in_shift : nullptr, fuse ? fuse->in_act : 0,
-                                 fuse ? fuse->stats : nullptr, fuse ? fuse->stats_floats : 0, fuse ? fuse->in_amax : nullptr, st);
-  if (!fuse_empty(fuse)) return VG_ERR_BAD_ARG;        // vg_conv5x5_bf16split_fusable says which layers take it
-  const bf16x8* w = (const bf16x8*)packed;
+  if (on_ring(CONV_FWD, Cout, stride))
+    return vg_internal_ring_conv(CONV_FWD, x, packed, bias, y, B, Cin, H, W, Cout, planes, workspace, workspace_bytes, fuse, st);
+  if (!fuse_empty(fuse)) return VG_ERR_BAD_ARG;
   const int k = fwd_ksplit(B, Cin, H, W, Cout, stride);
   if (k > 1 && (!workspace || workspace_bytes < vg_conv5x5_fwd_bf16split_workspace_bytes(B, Cin, H, W, Cout, stride, planes)))
     return VG_ERR_WORKSPACE;
-  const XSplit xs = {k, (float*)workspace, fuse ? fuse->in_amax : nullptr};
-  if (planes & VG_PLANES_F16_FLAG) {
-    if (!xs.in_amax) return VG_ERR_BAD_ARG;
-    return dispatch_x<X_FWD, 1, 2, true>(x, w, bias, y, B, Cin, H, W, Cout, xs, st);
-  }
-  if (planes == 2) return dispatch_x<X_FWD, 1, 2>(x, w, bias, y, B, Cin, H, W, Cout, xs, st);
-  return dispatch_x<X_FWD, 1, 3>(x, w, bias, y, B, Cin, H, W, Cout, xs, st);
+  return dispatch_planes<CONV_FWD>(x, packed, bias, y, B, Cin, H, W, Cout, stride, planes, k, workspace, fuse, st);
 }
 
 extern "C" size_t vg_convT5x5_fwd_bf16split_workspace_bytes(int B, int Cin, int H, int W, int Cout, int stride, int planes) {
-  if (B <= 0 || Cin <= 0 || Cin % 16 || Cout <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2) || !planes_ok(planes)) return 0;
-  return tr_on_ring(Cout, stride) ? vg_internal_ring_workspace_bytes(1, B, Cin, H, W, Cout, planes) : 0;
+  if (!shape_ok(B, Cin, H, W, Cout, stride, planes)) return 0;
+  return on_ring(CONV_TR, Cout, stride) ? vg_internal_ring_workspace_bytes(CONV_TR, B, Cin, H, W, Cout, planes) : 0;
 }
 
 extern "C" int vg_convT5x5_fwd_bf16split(const float* x, const void* packed, const float* bias, float* y, int B, int Cin,
@@ -845,22 +757,8 @@ extern "C" int vg_convT5x5_fwd_bf16split(const float* x, const void* packed, con
                                       size_t workspace_bytes, const vg_conv_fusion* fuse, void* stream) {
   if (!x_args_ok(x, packed, y, B, Cin, H, W, Cout, stride, planes)) return VG_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
-  if (tr_on_ring(Cout, stride))
-    return vg_internal_ring_conv(1, x, packed, bias, y, B, Cin, H, W, Cout, planes, workspace, workspace_bytes,
-                                 fuse ? fuse->in_scale : nullptr, fuse ? fuse->in_shift : nullptr, fuse ? fuse->in_act : 0,
-                                 fuse ? fuse->stats : nullptr, fuse ? fuse->stats_floats : 0, fuse ? fuse->in_amax : nullptr, st);
+  if (on_ring(CONV_TR, Cout, stride))
+    return vg_internal_ring_conv(CONV_TR, x, packed, bias, y, B, Cin, H, W, Cout, planes, workspace, workspace_bytes, fuse, st);
   if (!fuse_empty(fuse)) return VG_ERR_BAD_ARG;
-  const bf16x8* w = (const bf16x8*)packed;
-  const XSplit xs = {1, nullptr, fuse ? fuse->in_amax : nullptr};
-  if (planes & VG_PLANES_F16_FLAG) {
-    if (!xs.in_amax) return VG_ERR_BAD_ARG;
-    if (stride == 2) return dispatch_x<X_TR, 2, 2, true>(x, w, bias, y, B, Cin, H, W, Cout, xs, st);
-    return dispatch_x<X_TR, 1, 2, true>(x, w, bias, y, B, Cin, H, W, Cout, xs, st);
-  }
-  if (planes == 2) {
-    if (stride == 2) return dispatch_x<X_TR, 2, 2>(x, w, bias, y, B, Cin, H, W, Cout, xs, st);
-    return dispatch_x<X_TR, 1, 2>(x, w, bias, y, B, Cin, H, W, Cout, xs, st);
-  }
-  if (stride == 2) return dispatch_x<X_TR, 2, 3>(x, w, bias, y, B, Cin, H, W, Cout, xs, st);
-  return dispatch_x<X_TR, 1, 3>(x, w, bias, y, B, Cin, H, W, Cout, xs, st);
+  return dispatch_planes<CONV_TR>(x, packed, bias, y, B, Cin, H, W, Cout, stride, planes, 1, nullptr, fuse, st);
 }

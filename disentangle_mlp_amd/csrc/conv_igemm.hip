@@ -17,21 +17,18 @@
 //     workgroup stages into LDS (double buffered, next chunk prefetched into
 //     registers under the MFMAs): the NCHW input patch [NB][CK][PH][PW] with
 //     coalesced row loads and zero-filled halo, and the filter slab [TN][CK*NTAP].
-//     Staging loads are never predicated (addresses clamped into the tensor, halo
-//     zeroed at the LDS store): predicated loads made hipcc merge the dummy loads
-//     and drain vmcnt in the middle of the prefetch.
+//     Staging loads are never predicated (conv_tile.hpp, patch_elem).
 //   * im2col never exists in memory: lane (j,h) reads patch[c0+2cp+h][...] at a
 //     per-lane base + compile-time immediate; one staged input pixel feeds up to
 //     25/S^2 MFMA operands.
 //   * the stride-2 transposed convolution is decomposed into its 4 output-parity
-//     classes (3x3, 3x2, 2x3, 2x2 taps): no zero insertion, no atomics; a block
-//     owns one class of one input-space tile, heavy classes are dispatched first.
-#include "common.hpp"
-#include "vaegan_hip.h"
+//     classes (3x3, 3x2, 2x3, 2x2 taps; conv_tile.hpp): a block owns one class of
+//     one input-space tile, heavy classes are dispatched first.
+// Tap algebra, tile placement, patch address and host geometry are conv_tile.hpp's,
+// shared with conv_bf16split.hip and conv_ring.hip.
+#include "conv_tile.hpp"
 
 namespace {
-
-enum { MODE_FWD = 0, MODE_TR = 1 };
 
 
 template <int MODE_, int S_, int NB_, int TH_, int TW_, int TN_, int WC_, int WP_, int CK_, int MINW_ = 2, int KS_ = 1,
@@ -47,9 +44,8 @@ struct Cfg {
   static constexpr int TM = NB * TH * TW;
   static constexpr int FC = TN / 32 / WC;  // 32-row cout fragments per wave
   static constexpr int FP = TM / 32 / WP;  // 32-col pixel fragments per wave
-  static constexpr int NTMAX = (MODE == MODE_FWD) ? 5 : (5 + S - 1) / S;  // taps per dim, largest class
-  static constexpr int PH = (MODE == MODE_FWD) ? S * (TH - 1) + 5 : TH + NTMAX - 1;
-  static constexpr int PW = (MODE == MODE_FWD) ? S * (TW - 1) + 5 : TW + NTMAX - 1;
+  using Taps = TileTaps<MODE, S, TH, TW>;
+  static constexpr int NTMAX = Taps::NTMAX, PH = Taps::PH, PW = Taps::PW, NCLS = Taps::NCLS;
   static constexpr int PWP = PW | 1;
   static constexpr int NP = NB * CK * PH * PWP;  // patch floats per stage
   static constexpr int NQP = cdiv(NP, NT);
@@ -57,7 +53,6 @@ struct Cfg {
   static constexpr int WSMAX = RLMAX | 1;
   static constexpr int WOFF = (NP + 3) & ~3;         // filter slab starts 16-byte aligned
   static constexpr int STAGE = (WOFF + TN * WSMAX + 1 + 3) & ~3;  // +1: dummy slot for masked-off stores
-  static constexpr int NCLS = (MODE == MODE_FWD) ? 1 : S * S;
   static_assert(TN % (32 * WC) == 0 && TM % (32 * WP) == 0 && CK % 2 == 0, "tile shape");
   static_assert(RLMAX <= NT, "one filter row per pass at least");
   static_assert(FP + 5 <= VG_STATS_SLOT_DEPTH, "statistics slot: an fma chain of FP, 5 butterfly additions");
@@ -65,86 +60,43 @@ struct Cfg {
   static_assert(KS == 1 || 2 * STAGE >= (KS - 1) * TM * TN, "LDS must hold the partial tiles of the K groups");
 };
 
-struct Args {
-  const float* x;
+struct Args : ConvGeom {
   const float* w;    // PK: the packed filter
-  const float* bias;
-  float* y;
-  int B, Cin, XH, XW, Cout, YH, YW;
   int CinP, CoutP;   // PK: padded extents of the packed filter
-  int ntiles_n, tiles_w, tiles_hw, blocks_per_cls;
   float* stats;      // optional [slot][Cout][2]: per-channel sum y, sum y^2 of each (pixel tile, wavefront row) --
                      // the statistics of the BatchNorm that follows (forward convolution only; vg_conv_fusion.stats)
 };
 
-// Padded extents of the packed filter: whole K chunks (<= 8 channels) and whole cout tiles.
+// Padded extents of the packed filter: whole K chunks (<= 8 channels) and whole cout tiles (packed_cout).
 __host__ __device__ constexpr int packed_cin(int Cin) { return (Cin + 7) & ~7; }
-__host__ __device__ constexpr int packed_cout(int Cout) { return (Cout + 127) & ~127; }
 
-// Taps of the parity classes that precede class (R, SS) in the packed filter.
-__host__ __device__ constexpr int taps_before(int S, int R, int SS) {
-  int n = 0;
-  for (int r = 0; r < S; ++r)
-    for (int s = 0; s < S; ++s) {
-      if (r == R && s == SS) return n;
-      n += ((5 - r + S - 1) / S) * ((5 - s + S - 1) / S);
-    }
-  return n;
-}
-
-// R, SS: output parity class of the transposed convolution (0,0 for MODE_FWD).
+// R, SS: output parity class of the transposed convolution (0,0 for CONV_FWD).
 template <class C, int R, int SS>
 __device__ __forceinline__ void igemm_body(const Args& A, float* smem, int bid) {
   constexpr int MODE = C::MODE, S = C::S, NB = C::NB, TH = C::TH, TW = C::TW, TN = C::TN, CK = C::CK;
   constexpr int NT = C::NT, FC = C::FC, FP = C::FP, PH = C::PH, PW = C::PW, PWP = C::PWP;
   constexpr int NP = C::NP, NQP = C::NQP, NTMAX = C::NTMAX, WOFF = C::WOFF;
   constexpr bool PK = C::PK;
-  constexpr int NTH = (MODE == MODE_FWD) ? 5 : (5 - R + S - 1) / S;   // taps along h in this class
-  constexpr int NTW = (MODE == MODE_FWD) ? 5 : (5 - SS + S - 1) / S;
+  constexpr int NTH = C::Taps::nth(R), NTW = C::Taps::nth(SS);        // taps along h / w in this class
   constexpr int NTAP = NTH * NTW;
   constexpr int RL = CK * NTAP;    // filter row: one cout, CK channels, NTAP taps
   constexpr int WS = RL | 1;       // odd LDS row stride: conflict-free b32 operand reads
   constexpr int RP = NT / RL;      // filter rows staged per pass
   constexpr int NQW = cdiv(TN, RP);
-  constexpr int PSTEP = (MODE == MODE_FWD) ? S : 1;  // patch step per tile pixel
+  constexpr int PSTEP = C::Taps::PSTEP;
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int h = lane >> 5, l32 = lane & 31;
   const int kg = wid / (C::WC * C::WP), w2 = wid % (C::WC * C::WP);   // K group, wave within the tile
   const int wc = w2 % C::WC, wp = w2 / C::WC;
-  // XCD-aware placement: workgroups are dealt round-robin over the 8 XCDs (bid % 8 labels the
-  // XCD, each with its own L2).  The ntiles_n cout tiles that read the SAME input patch are
-  // given to ONE XCD, back to back, so the patch is fetched from HBM once and re-read from that
-  // L2; every XCD streams the whole (L2-sized) filter.  Placement affects speed only.
   int nt, pt;
-  {
-    const int ntn = A.ntiles_n;
-    const int npatch = A.blocks_per_cls / ntn;
-    const int full = (npatch / 8) * 8 * ntn;
-    if (bid < full) {
-      const int xcd = bid & 7, j = bid >> 3;
-      pt = (j / ntn) * 8 + xcd;
-      nt = j % ntn;
-    } else {
-      const int t = bid - full;
-      pt = (npatch / 8) * 8 + t / ntn;
-      nt = t % ntn;
-    }
-  }
-  const int sp = pt % A.tiles_hw, bg = pt / A.tiles_hw;
-  const int th0 = (sp / A.tiles_w) * TH, tw0 = (sp % A.tiles_w) * TW;  // tile origin (tile space)
-  const int b0 = bg * NB, n0 = nt * TN;
-  const int Cin = A.Cin, Cout = A.Cout, XH = A.XH, XW = A.XW;
-  const int HW = XH * XW;
-  // patch origin in input coordinates
-  const int ih0 = (MODE == MODE_FWD) ? th0 * S - 2 : th0 - (NTMAX - 1 - 2 / S);
-  const int iw0 = (MODE == MODE_FWD) ? tw0 * S - 2 : tw0 - (NTMAX - 1 - 2 / S);
+  place_tile<false>(bid, A.ntiles_n, A.blocks_per_cls, nt, pt);
+  const TileOrigin org = tile_origin<C>(pt, nt, A);
+  const int b0 = org.b0, n0 = org.n0;
+  const int Cin = A.Cin, Cout = A.Cout, HW = A.XH * A.XW;
   const float* xb = A.x + (size_t)b0 * Cin * HW;
 
-  // ---- per-thread patch staging map (invariant over the K loop).  Every load address is
-  // CLAMPED into the tensor (distinct, always valid) instead of being predicated: the prefetch
-  // is straight-line code with no dependent or merged loads; halo / tail elements are replaced
-  // by 0 when the registers are written to LDS.
+  // ---- per-thread patch staging map (invariant over the K loop)
   int pofs[NQP];
   unsigned pvalid = 0;   // bit q: spatially inside the image (and a real image)
 #pragma unroll
@@ -155,11 +107,9 @@ __device__ __forceinline__ void igemm_body(const Args& A, float* smem, int bid) 
     const int r = t % PH;
     t /= PH;
     const int nb = t / CK;
-    const int ih = ih0 + r, iw = iw0 + col;
-    const bool ok = (e < NP) && (col < PW) && ih >= 0 && ih < XH && iw >= 0 && iw < XW && (b0 + nb) < A.B;
-    const int nbc = min(nb, A.B - 1 - b0), ihc = min(max(ih, 0), XH - 1), iwc = min(max(iw, 0), XW - 1);
-    pofs[q] = nbc * Cin * HW + ihc * XW + iwc;
-    pvalid |= ok ? (1u << q) : 0u;
+    const PatchElem pe = patch_elem(A, org, nb, r, col, e < NP && col < PW);
+    pofs[q] = pe.ofs;
+    pvalid |= pe.ok ? (1u << q) : 0u;
   }
   static_assert(NQP <= 32, "patch validity mask is 32-bit");
 
@@ -167,11 +117,11 @@ __device__ __forceinline__ void igemm_body(const Args& A, float* smem, int bid) 
   const int w_sub = tid / RL, w_r = tid % RL;
   const bool wrow_ok = w_sub < RP;
   const int w_c = w_r / NTAP, w_t = w_r % NTAP;
-  const int w_kh = (MODE == MODE_FWD) ? w_t / 5 : R + S * (w_t / NTW);
-  const int w_kw = (MODE == MODE_FWD) ? w_t % 5 : SS + S * (w_t % NTW);
+  const int w_kh = (MODE == CONV_FWD) ? w_t / 5 : R + S * (w_t / NTW);
+  const int w_kw = (MODE == CONV_FWD) ? w_t % 5 : SS + S * (w_t % NTW);
   // conv weight [Cout][Cin][25]; transposed-conv weight [Cin][Cout][25]
-  const int w_row_stride = (MODE == MODE_FWD) ? Cin * 25 : 25;
-  const int w_ch_stride = (MODE == MODE_FWD) ? 25 : Cout * 25;
+  const int w_row_stride = (MODE == CONV_FWD) ? Cin * 25 : 25;
+  const int w_ch_stride = (MODE == CONV_FWD) ? 25 : Cout * 25;
   const int w_tap = w_kh * 5 + w_kw;
 
   // ---- packed filter (PK): the chunk's slab is RL rows x TN floats of the [ci*NTAP+tap][CoutP]
@@ -180,7 +130,7 @@ __device__ __forceinline__ void igemm_body(const Args& A, float* smem, int bid) 
   constexpr int NQ4 = PK ? cdiv(RL, RPQ) : 1;
   static_assert(NT % TN4 == 0, "packed staging: whole rows per pass");
   const int pk_c4 = tid % TN4, pk_k0 = tid / TN4;
-  const float* wpk = A.w + ((size_t)taps_before(S, R, SS) * A.CinP) * A.CoutP + n0 + 4 * pk_c4;
+  const float* wpk = A.w + ((size_t)class_taps_before(S, R, SS) * A.CinP) * A.CoutP + n0 + 4 * pk_c4;
 
   float preg[NQP], wreg[PK ? 1 : NQW];
   f32x4 wreg4[NQ4];
@@ -252,6 +202,9 @@ __device__ __forceinline__ void igemm_body(const Args& A, float* smem, int bid) 
                    : WOFF + ((wc * FC + g) * 32 + l32) * WS + h * NTAP + kg * CPG * 2 * NTAP;
 #pragma unroll
   for (int f = 0; f < FP; ++f) {
+    // (frag_pixel<C> written out, here and in the two epilogues: through the helper the same arithmetic is folded in
+    // another order -- a fragment's base no longer comes out as the previous one plus a constant -- and 8-wave tiles
+    // lose an occupancy step, e.g. 120 -> 130 VGPRs.  DESIGN.md section 4.28)
     const int m = (wp * FP + f) * 32 + l32;
     const int nb = m / (TH * TW), r = m % (TH * TW);
     base_p[f] = ((nb * CK + h + kg * CPG * 2) * PH + PSTEP * (r / TW)) * PWP + PSTEP * (r % TW);
@@ -279,8 +232,8 @@ __device__ __forceinline__ void igemm_body(const Args& A, float* smem, int bid) 
     float a_cur[FC], b_cur[FP];
     auto read_step = [&](int stp, float* a, float* b) {
       const int cp = stp / NTAP, t = stp % NTAP;
-      const int ro = (MODE == MODE_FWD) ? t / 5 : NTMAX - 1 - t / NTW;   // patch row / col offset of the tap
-      const int cof = (MODE == MODE_FWD) ? t % 5 : NTMAX - 1 - t % NTW;
+      const int ro = (MODE == CONV_FWD) ? t / 5 : NTMAX - 1 - t / NTW;   // patch row / col offset of the tap
+      const int cof = (MODE == CONV_FWD) ? t % 5 : NTMAX - 1 - t % NTW;
 #pragma unroll
       for (int g = 0; g < FC; ++g) a[g] = st[base_w[g] + (cp * 2 * NTAP + t) * (PK ? TN : 1)];
 #pragma unroll
@@ -323,15 +276,14 @@ __device__ __forceinline__ void igemm_body(const Args& A, float* smem, int bid) 
           for (int r = 0; r < 16; ++r) acc[g][f][r] += src[((g * FP + f) * 16 + r) * 64];
     }
   }
-  // ---- epilogue: + bias, NCHW store
-  const int YH = A.YH, YW = A.YW;
-  if (MODE == MODE_FWD && A.stats) {
+  // ---- epilogue: statistics of this (pixel tile, wavefront row) on request, then + bias, NCHW store.
+  if (MODE == CONV_FWD && A.stats) {
     bool pokf[FP];
 #pragma unroll
     for (int f = 0; f < FP; ++f) {
       const int m = (wp * FP + f) * 32 + l32;
       const int nb = m / (TH * TW), r = m % (TH * TW);
-      pokf[f] = (b0 + nb) < A.B && (th0 + r / TW) < YH && (tw0 + r % TW) < YW;
+      pokf[f] = (b0 + nb) < A.B && (org.th0 + r / TW) < A.YH && (org.tw0 + r % TW) < A.YW;
     }
     float* sb = A.stats + (size_t)(pt * C::WP + wp) * Cout * 2;
 #pragma unroll
@@ -358,13 +310,14 @@ __device__ __forceinline__ void igemm_body(const Args& A, float* smem, int bid) 
         }
       }
   }
+  const int YH = A.YH, YW = A.YW;
 #pragma unroll
   for (int f = 0; f < FP; ++f) {
     const int m = (wp * FP + f) * 32 + l32;
     const int nb = m / (TH * TW), r = m % (TH * TW);
-    const int th = th0 + r / TW, tw = tw0 + r % TW, b = b0 + nb;
-    const int oh = (MODE == MODE_FWD) ? th : S * th + R;
-    const int ow = (MODE == MODE_FWD) ? tw : S * tw + SS;
+    const int th = org.th0 + r / TW, tw = org.tw0 + r % TW, b = b0 + nb;
+    const int oh = (MODE == CONV_FWD) ? th : S * th + R;
+    const int ow = (MODE == CONV_FWD) ? tw : S * tw + SS;
     const bool pok = b < A.B && oh < YH && ow < YW;
     float* yb = A.y + ((size_t)b * Cout * YH + oh) * YW + ow;
 #pragma unroll
@@ -393,12 +346,9 @@ __global__ __launch_bounds__(C::NT, C::MINW) void conv5x5_igemm_kernel(Args A) {
   } else {
     const int cls = bid / A.blocks_per_cls;  // class 0 (3x3 taps) first: longest blocks start earliest
     bid -= cls * A.blocks_per_cls;
-    switch (cls) {
-      case 0: igemm_body<C, 0, 0>(A, smem, bid); break;
-      case 1: igemm_body<C, 0, 1>(A, smem, bid); break;
-      case 2: igemm_body<C, 1, 0>(A, smem, bid); break;
-      default: igemm_body<C, 1, 1>(A, smem, bid); break;
-    }
+    for_class(cls, [&](auto R, auto SS) __attribute__((always_inline)) {
+      igemm_body<C, decltype(R)::value, decltype(SS)::value>(A, smem, bid);
+    });
   }
 }
 
@@ -413,28 +363,14 @@ template <class C>
 int launch(const float* x, const float* w, const float* bias, float* y, int B, int Cin, int XH, int XW,
            int Cout, hipStream_t st, const IgStats* sx = nullptr) {
   Args A;
-  A.x = x; A.w = w; A.bias = bias; A.y = y;
+  const long per_cls = fill_geom<C>(A, x, bias, y, B, Cin, XH, XW, Cout);
+  A.w = w;
   A.stats = nullptr;
-  A.B = B; A.Cin = Cin; A.XH = XH; A.XW = XW; A.Cout = Cout;
   A.CinP = packed_cin(Cin); A.CoutP = packed_cout(Cout);
-  int tsh, tsw;  // tile-space extent
-  if (C::MODE == MODE_FWD) {
-    A.YH = (XH - 1) / C::S + 1; A.YW = (XW - 1) / C::S + 1;
-    tsh = A.YH; tsw = A.YW;
-  } else {
-    A.YH = XH * C::S; A.YW = XW * C::S;
-    tsh = XH; tsw = XW;
-  }
-  const int tiles_h = cdiv(tsh, C::TH);
-  A.tiles_w = cdiv(tsw, C::TW);
-  A.tiles_hw = tiles_h * A.tiles_w;
-  A.ntiles_n = cdiv(Cout, C::TN);
-  const long per_cls = (long)A.ntiles_n * A.tiles_hw * cdiv(B, C::NB);
-  A.blocks_per_cls = (int)per_cls;
   const long grid = per_cls * C::NCLS;
-  if (grid <= 0 || grid > 0x7fffffffL) return VG_ERR_BAD_ARG;
+  if (!grid_ok(grid)) return VG_ERR_BAD_ARG;
   if (sx) {
-    const size_t floats = (C::MODE == MODE_FWD) ? (size_t)(per_cls / A.ntiles_n) * C::WP * Cout * 2 : 0;
+    const size_t floats = (C::MODE == CONV_FWD) ? (size_t)(per_cls / A.ntiles_n) * C::WP * Cout * 2 : 0;
     if (sx->need) {
       *sx->need = floats;
       return 0;
@@ -461,7 +397,7 @@ struct Pick;
 #define VG_PICK(WIDTH, VAR, NB, TH, TW, TN, WC, WP, CKF, CKT, KS)                                             \
   template <int MODE, int S, bool PK>                                                                         \
   struct Pick<MODE, S, WIDTH, VAR, PK> {                                                                      \
-    using type = Cfg<MODE, S, NB, TH, TW, TN, WC, WP, ((MODE == MODE_FWD || S == 1) ? CKF : CKT), 2, KS, PK>; \
+    using type = Cfg<MODE, S, NB, TH, TW, TN, WC, WP, ((MODE == CONV_FWD || S == 1) ? CKF : CKT), 2, KS, PK>; \
   };
 //       W  V NB TH TW   TN WC WP CKF CKT KS
 VG_PICK(32, 0, 1, 4, 32, 128, 2, 2, 2, 4, 1)
@@ -518,19 +454,18 @@ int launch_var(int var, const float* x, const float* w, const float* bias, float
 template <int MODE, int S, bool PK>
 int dispatch(const float* x, const float* w, const float* bias, float* y, int B, int Cin, int XH, int XW,
              int Cout, hipStream_t st, const IgStats* sx = nullptr) {
-  const int tsw = (MODE == MODE_FWD) ? (XW - 1) / S + 1 : XW;
-  const int tsh = (MODE == MODE_FWD) ? (XH - 1) / S + 1 : XH;
+  const int tsw = tile_extent(MODE, S, XW), tsh = tile_extent(MODE, S, XH);
   const int width = tsw >= 32 ? 32 : (tsw >= 16 ? 16 : 8);
   // Measured on MI355X at B=128 (scripts/tune_conv.py).  Staging (global loads -> LDS) is the
   // cost next to the MFMAs, so the biggest pixel tile that still fills the chip wins: 256 px x
   // 128 / 64 cout (8 waves) on the large grids, 128 px x 64 cout otherwise -- with 8 waves
   // (in-workgroup split of the K chunk) where 4 waves would leave SIMDs with a single wave.
   const long px256 = (long)cdiv(B * cdiv(tsh, 8) * cdiv(tsw, 8) * 64, 256);
-  const int ncls = (MODE == MODE_TR) ? S * S : 1;
+  const int ncls = (MODE == CONV_TR) ? S * S : 1;
   int var;
   if (Cout <= 32) {
     var = (px256 * ncls >= 2048) ? 7 : 6;
-  } else if (MODE == MODE_FWD) {
+  } else if (MODE == CONV_FWD) {
     if (px256 * cdiv(Cout, 128) >= 256 && Cout > 64) var = 4;
     else if (px256 * cdiv(Cout, 64) >= 256) var = 1;
     else var = 5;
@@ -570,8 +505,8 @@ __global__ __launch_bounds__(256) void pack_filter_kernel(const float* __restric
     const int tap = e / 64, col = e % 64;
     const int kh = tap / 5, kw = tap % 5;
     const int R = kh % S, SS = kw % S;
-    const int ntw = (5 - SS + S - 1) / S, nth = (5 - R + S - 1) / S;
-    const int tb = taps_before(S, R, SS);
+    const int ntw = class_taps(S, SS), nth = class_taps(S, R);
+    const int tb = class_taps_before(S, R, SS);
     const size_t row = (size_t)tb * CinP + (size_t)ci * (nth * ntw) + (kh / S) * ntw + kw / S;
     p[row * CoutP + co0 + col] = t[col * 25 + tap];
   }
@@ -618,8 +553,8 @@ extern "C" int vg_conv5x5_fwd(const float* x, const float* w, const float* bias,
                               int H, int W, int Cout, int stride, void* stream) {
   if (!conv_args_ok(x, w, y, B, Cin, H, W, Cout, stride)) return VG_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
-  if (stride == 2) return dispatch<MODE_FWD, 2, false>(x, w, bias, y, B, Cin, H, W, Cout, st);
-  return dispatch<MODE_FWD, 1, false>(x, w, bias, y, B, Cin, H, W, Cout, st);
+  if (stride == 2) return dispatch<CONV_FWD, 2, false>(x, w, bias, y, B, Cin, H, W, Cout, st);
+  return dispatch<CONV_FWD, 1, false>(x, w, bias, y, B, Cin, H, W, Cout, st);
 }
 
 extern "C" int vg_conv5x5_fwd_packed(const float* x, const float* packed, const float* bias, float* y, int B,
@@ -627,16 +562,16 @@ extern "C" int vg_conv5x5_fwd_packed(const float* x, const float* packed, const 
   if (!conv_args_ok(x, packed, y, B, Cin, H, W, Cout, stride) || ((uintptr_t)packed & 15) != 0)
     return VG_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
-  if (stride == 2) return dispatch<MODE_FWD, 2, true>(x, packed, bias, y, B, Cin, H, W, Cout, st);
-  return dispatch<MODE_FWD, 1, true>(x, packed, bias, y, B, Cin, H, W, Cout, st);
+  if (stride == 2) return dispatch<CONV_FWD, 2, true>(x, packed, bias, y, B, Cin, H, W, Cout, st);
+  return dispatch<CONV_FWD, 1, true>(x, packed, bias, y, B, Cin, H, W, Cout, st);
 }
 
 extern "C" size_t vg_conv5x5_fwd_packed_stats_floats(int B, int Cin, int H, int W, int Cout, int stride) {
   if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2)) return 0;
   size_t need = 0;
   const IgStats sx = {nullptr, 0, &need};
-  const int rc = (stride == 2) ? dispatch<MODE_FWD, 2, true>(nullptr, nullptr, nullptr, nullptr, B, Cin, H, W, Cout, nullptr, &sx)
-                               : dispatch<MODE_FWD, 1, true>(nullptr, nullptr, nullptr, nullptr, B, Cin, H, W, Cout, nullptr, &sx);
+  const int rc = (stride == 2) ? dispatch<CONV_FWD, 2, true>(nullptr, nullptr, nullptr, nullptr, B, Cin, H, W, Cout, nullptr, &sx)
+                               : dispatch<CONV_FWD, 1, true>(nullptr, nullptr, nullptr, nullptr, B, Cin, H, W, Cout, nullptr, &sx);
   return rc == 0 ? need : 0;
 }
 
@@ -647,18 +582,18 @@ extern "C" int vg_conv5x5_fwd_packed_stats(const float* x, const float* packed, 
     return VG_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
   const IgStats sx = {stats, stats_floats, nullptr};
-  if (stride == 2) return dispatch<MODE_FWD, 2, true>(x, packed, bias, y, B, Cin, H, W, Cout, st, &sx);
-  return dispatch<MODE_FWD, 1, true>(x, packed, bias, y, B, Cin, H, W, Cout, st, &sx);
+  if (stride == 2) return dispatch<CONV_FWD, 2, true>(x, packed, bias, y, B, Cin, H, W, Cout, st, &sx);
+  return dispatch<CONV_FWD, 1, true>(x, packed, bias, y, B, Cin, H, W, Cout, st, &sx);
 }
 
 extern "C" int vg_convT5x5_fwd(const float* x, const float* w, const float* bias, float* y, int B, int Cin,
                                int H, int W, int Cout, int stride, void* stream) {
   if (!conv_args_ok(x, w, y, B, Cin, H, W, Cout, stride)) return VG_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
-  if (stride == 2) return dispatch<MODE_TR, 2, false>(x, w, bias, y, B, Cin, H, W, Cout, st);
+  if (stride == 2) return dispatch<CONV_TR, 2, false>(x, w, bias, y, B, Cin, H, W, Cout, st);
   // <= 4 output channels: direct VALU kernel (an MFMA tile would be 3/32 full)
-  if (Cout <= 4 && g_tile_override[MODE_TR] < 0) return vg_internal_convT_s1_thin(x, w, bias, y, B, Cin, H, W, Cout, st);
-  return dispatch<MODE_TR, 1, false>(x, w, bias, y, B, Cin, H, W, Cout, st);
+  if (Cout <= 4 && g_tile_override[CONV_TR] < 0) return vg_internal_convT_s1_thin(x, w, bias, y, B, Cin, H, W, Cout, st);
+  return dispatch<CONV_TR, 1, false>(x, w, bias, y, B, Cin, H, W, Cout, st);
 }
 
 extern "C" int vg_convT5x5_fwd_packed(const float* x, const float* packed, const float* bias, float* y, int B,
@@ -666,6 +601,6 @@ extern "C" int vg_convT5x5_fwd_packed(const float* x, const float* packed, const
   if (!conv_args_ok(x, packed, y, B, Cin, H, W, Cout, stride) || ((uintptr_t)packed & 15) != 0)
     return VG_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
-  if (stride == 2) return dispatch<MODE_TR, 2, true>(x, packed, bias, y, B, Cin, H, W, Cout, st);
-  return dispatch<MODE_TR, 1, true>(x, packed, bias, y, B, Cin, H, W, Cout, st);
+  if (stride == 2) return dispatch<CONV_TR, 2, true>(x, packed, bias, y, B, Cin, H, W, Cout, st);
+  return dispatch<CONV_TR, 1, true>(x, packed, bias, y, B, Cin, H, W, Cout, st);
 }

@@ -18,14 +18,13 @@
 //   * fragments for step k+1 are read (ds_read_b128, conflict-free layouts) while the MFMAs of step k run.
 // Forward (stride 2): a K step is 8 channels x 2 taps (k-block 0 / 1 = consecutive taps), so that the two
 // resident patch buffers are 8-channel halves: 25 steps per 16-channel chunk, step 12 pairs tap 24 of both
-// halves -- no padding step.  Transposed (stride 2): the 4 output-parity classes (3x3, 3x2, 2x3, 2x2 taps) as
-// in conv_igemm.hip, K step = 16 channels x 1 tap.
-#include "common.hpp"
-#include "vaegan_hip.h"
+// halves -- no padding step.  Transposed (stride 2): the 4 output-parity classes (3x3, 3x2, 2x3, 2x2 taps;
+// conv_tile.hpp), K step = 16 channels x 1 tap.  Tap algebra, tile placement, fragment decode, patch address and
+// host geometry are conv_tile.hpp's, shared with conv_igemm.hip and conv_bf16split.hip.
+#include "conv_tile.hpp"
 
 namespace {
 
-enum { R_FWD = 0, R_TR = 1 };
 constexpr int RNT = 512;          // 8 wavefronts
 // Depth of the filter ring: DMA(k + NSLOT) is issued in body k.  3 slots.  With fp16 planes a step holds half the MFMAs
 // of a bf16x6 step and three steps of run-ahead looked marginal against the L2 -> LDS latency, so round 4 timed 4, 5 and
@@ -49,17 +48,13 @@ constexpr int ring_slots(bool f16, int slotu, int patchu) {
 // the run-ahead past the last step reads the pack's zero spare steps (conv_bf16split.hip, pack kernel)
 static_assert(VG_RING_SLOTS >= 3 && VG_RING_SLOTS <= VG_PACK_SPARE, "ring depth");
 
-// 16-byte units per patch row; same bank rules as conv_bf16split.hip (fragments of 2 rows x 16 pixels need the
-// two rows 0 (mod 16) units apart, 4 rows x 8 pixels 8 (mod 16))
+// 16-byte units per patch row (transposed) or per column parity of one (forward: a row is 2 * COLS units); the bank
+// rules of row_units (conv_tile.hpp)
 constexpr int ring_cols(int mode, int TW, int PW) {
-  if (mode == R_FWD) {                                   // per column parity; a row is 2 * COLS units
-    const int need = (PW + 1) / 2;
-    if (TW == 8) { int c = need; while ((c & 3) != 2) ++c; return c; }
-    return (need + 3) & ~3;
-  }
-  if (TW == 16) return (PW + 15) & ~15;
-  if (TW == 8) { int c = PW; while ((c & 15) != 8) ++c; return c; }
-  return (PW + 3) & ~3;
+  if (mode == CONV_TR) return row_units(TW, PW);
+  const int need = (PW + 1) / 2;
+  if (TW == 8) { int c = need; while ((c & 3) != 2) ++c; return c; }
+  return (need + 3) & ~3;
 }
 
 template <int MODE_, int NB_, int TH_, int TW_, int WC_, int FC_, int FP_, int NP_, bool F16_ = false>
@@ -69,14 +64,13 @@ struct RCfg {
   static_assert(!F16_ || NP_ == 2, "fp16 planes: hi + lo");
   static constexpr int S = 2;
   static constexpr int TN = 32 * WC * FC, TM = NB * TH * TW;
-  static constexpr int NTMAX = (MODE == R_FWD) ? 5 : 3;
-  static constexpr int PH = (MODE == R_FWD) ? S * (TH - 1) + 5 : TH + NTMAX - 1;
-  static constexpr int PW = (MODE == R_FWD) ? S * (TW - 1) + 5 : TW + NTMAX - 1;
+  using Taps = TileTaps<MODE, S, TH, TW>;
+  static constexpr int NTMAX = Taps::NTMAX, PH = Taps::PH, PW = Taps::PW, NCLS = Taps::NCLS;
   static constexpr int COLS = ring_cols(MODE, TW, PW);
-  static constexpr int ROWU = (MODE == R_FWD) ? 2 * COLS : COLS;      // units per patch row
+  static constexpr int ROWU = (MODE == CONV_FWD) ? 2 * COLS : COLS;      // units per patch row
   static constexpr int IMGU = NB * PH * ROWU;                         // units per (plane, 8-channel block) image
   // patch buffers: FWD two 8-channel halves [half][plane][image]; TR two 16-channel chunks [buf][plane][kb][image]
-  static constexpr int BUFU = (MODE == R_FWD) ? NP * IMGU : NP * 2 * IMGU;
+  static constexpr int BUFU = (MODE == CONV_FWD) ? NP * IMGU : NP * 2 * IMGU;
   static constexpr int PATCHU = 2 * BUFU;
   static constexpr int SLOTU = NP * 2 * TN;                            // one K step of the filter: [plane][kb][cout]
   static constexpr int NSLOT = ring_slots(F16_, SLOTU, PATCHU);
@@ -87,25 +81,15 @@ struct RCfg {
   // staged units per staging event: NB * PH * PW pixels of 8 channels (FWD) or of 2 x 8 channels (TR: unit q of a
   // thread belongs to k-block q & 1, so that a unit's channels are wave-uniform)
   static constexpr int NPIX = NB * PH * PW;
-  static constexpr int NQ = ((MODE == R_FWD) ? 1 : 2) * ((NPIX + RNT - 1) / RNT);
+  static constexpr int NQ = ((MODE == CONV_FWD) ? 1 : 2) * ((NPIX + RNT - 1) / RNT);
   static constexpr int NL = NQ * 8;                                    // plain global loads per staging event
-  static constexpr int NCLS = (MODE == R_FWD) ? 1 : 4;
   static_assert(TM == 32 * WP * FP, "pixel tile");
-  static_assert(FP + 5 <= VG_STATS_SLOT_DEPTH, "statistics slot: an fma chain of FP, 5 butterfly additions");
   static_assert(WC == 1 || WC == 2 || WC == 4 || WC == 8, "wavefront grid");
   static_assert(SLOTU % 64 == 0, "a step's filter slice is whole DMA instructions");
   static_assert(LDSU * 16 <= 160 * 1024, "LDS");
 };
 
-struct RArgs {
-  const float* x;
-  const bf16x8* w;     // packed filter
-  const float* bias;
-  float* y;
-  int B, Cin, XH, XW, Cout, CoutP, YH, YW;
-  int ntiles_n, tiles_w, tiles_hw, blocks_per_cls;
-  int cps;             // channel chunks per K split
-  size_t ysplit;       // elements per partial output slab (ksplit > 1: y points at the slabs)
+struct RArgs : SplitGeom {
   // fused BatchNorm (vg_conv_fusion): the INPUT is read as act(x * in_scale[c] + in_shift[c]) -- the train-mode
   // BatchNorm + activation of the producing layer applied while the patch is staged (zero padding applies to the
   // activated tensor) -- and per-channel sums of the OUTPUT (sum y, sum y^2 over this workgroup's pixels, one slot
@@ -114,23 +98,8 @@ struct RArgs {
   const float* in_shift;
   int in_act;
   float* stats;        // [slot][Cout][2]
-  // fp16 planes: in_amax[0] >= max |activated input| (device); w_unscale[0] = the inverse of the power of two the pack
-  // kernel multiplied the filter by (stored behind the pack).  NULL for bf16 planes.
-  const float* in_amax;
-  const float* w_unscale;
   int paired;          // transposed: a workgroup runs two parity classes of its tile (see conv5x5_ring_kernel)
 };
-
-// steps (of 16 k) of the transposed classes before (R, SS), per chunk of 16 channels
-__host__ __device__ constexpr int tr_taps_before(int R, int SS) {
-  int n = 0;
-  for (int r = 0; r < 2; ++r)
-    for (int s = 0; s < 2; ++s) {
-      if (r == R && s == SS) return n;
-      n += ((5 - r + 1) / 2) * ((5 - s + 1) / 2);
-    }
-  return n;
-}
 
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
@@ -154,44 +123,26 @@ __device__ __forceinline__ void ring_body(const RArgs& A, f32x4* lds, int bid, i
   constexpr int NTMAX = C::NTMAX, BUFU = C::BUFU, SLOTU = C::SLOTU, NDMA = C::NDMA, NL = C::NL, TN = C::TN;
   constexpr int NSLOT = C::NSLOT;
   constexpr bool F16 = C::F16;
-  constexpr int NTH = (MODE == R_FWD) ? 5 : (5 - R + 1) / 2;     // taps along h / w in this class
-  constexpr int NTW = (MODE == R_FWD) ? 5 : (5 - SS + 1) / 2;
+  constexpr int NTH = C::Taps::nth(R), NTW = C::Taps::nth(SS);    // taps along h / w in this class
   constexpr bool TWO = R2 >= 0;
-  static_assert(!TWO || MODE == R_TR, "two classes: transposed form");
-  constexpr int NTH2 = TWO ? (5 - R2 + 1) / 2 : 0, NTW2 = TWO ? (5 - SS2 + 1) / 2 : 1;
+  static_assert(!TWO || MODE == CONV_TR, "two classes: transposed form");
+  constexpr int NTH2 = TWO ? class_taps(S, R2) : 0, NTW2 = TWO ? class_taps(S, SS2) : 1;
   constexpr int NA = NTH * NTW, NB2 = NTH2 * NTW2;                // K steps of the first / second class per chunk
   constexpr int NSTEP = NA + NB2;                                 // K steps per 16-channel chunk (FWD: 25)
   constexpr int NACC = TWO ? 2 : 1;
   static_assert(!TWO || NA >= NSLOT, "the prologue's DMAs all belong to the first class");
-  constexpr int PSTEP = (MODE == R_FWD) ? S : 1;
+  constexpr int PSTEP = C::Taps::PSTEP;
   constexpr int RING0 = 0, PATCH0 = C::RINGU, DUMMY = C::RINGU + C::PATCHU;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);       // wave-uniform: keeps the DMA's LDS base in SGPRs
   const int kb = lane >> 5, l32 = lane & 31;
   const int wc = wid % C::WC, wp = wid / C::WC;
-  // XCD-aware placement (conv_igemm.hip): the cout tiles of one pixel tile share an XCD
   int nt, pt;
-  {
-    const int ntn = A.ntiles_n, npatch = A.blocks_per_cls / ntn, full = (npatch / 8) * 8 * ntn;
-    if (bid < full) {
-      const int xcd = bid & 7, j = bid >> 3;
-      // an XCD works through a contiguous run of pixel tiles: neighbours in the image (shared halo rows, shared cache
-      // lines of a row) follow each other through the same L2
-      pt = xcd * (npatch / 8) + j / ntn;
-      nt = j % ntn;
-    } else {
-      const int t = bid - full;
-      pt = (npatch / 8) * 8 + t / ntn;
-      nt = t % ntn;
-    }
-  }
-  const int sp = pt % A.tiles_hw, bg = pt / A.tiles_hw;
-  const int th0 = (sp / A.tiles_w) * TH, tw0 = (sp % A.tiles_w) * TW;
-  const int b0 = bg * NB, n0 = nt * TN;
-  const int Cin = A.Cin, Cout = A.Cout, XH = A.XH, XW = A.XW, HW = XH * XW;
-  const int ih0 = (MODE == R_FWD) ? th0 * S - 2 : th0 - (NTMAX - 1 - 2 / S);
-  const int iw0 = (MODE == R_FWD) ? tw0 * S - 2 : tw0 - (NTMAX - 1 - 2 / S);
+  place_tile<true>(bid, A.ntiles_n, A.blocks_per_cls, nt, pt);      // contiguous runs of pixel tiles per XCD
+  const TileOrigin org = tile_origin<C>(pt, nt, A);
+  const int b0 = org.b0, n0 = org.n0;
+  const int Cin = A.Cin, Cout = A.Cout, HW = A.XH * A.XW;
   const float* xb = A.x + (size_t)b0 * Cin * HW;
 
   // ---- staging map.  FWD: unit e = (image, row, column) of ONE 8-channel half; TR: (k-block, image, row, column).
@@ -205,20 +156,19 @@ __device__ __forceinline__ void ring_body(const RArgs& A, f32x4* lds, int bid, i
   auto unit_of = [&](int q) -> Unit {
     int t0 = tid;
     asm volatile("" : "+v"(t0));                       // opaque: keeps the map from being hoisted out of the loop
-    const int kbs = (MODE == R_FWD) ? 0 : (q & 1);
-    const int e = t0 + ((MODE == R_FWD) ? q : (q >> 1)) * RNT;
+    const int kbs = (MODE == CONV_FWD) ? 0 : (q & 1);
+    const int e = t0 + ((MODE == CONV_FWD) ? q : (q >> 1)) * RNT;
     const int col = e % PW;
     int t = e / PW;
     const int r = t % PH;
     t /= PH;
     const int nb = t % NB;
-    const int ih = ih0 + r, iw = iw0 + col;
     const bool in = e < C::NPIX;
+    const PatchElem pe = patch_elem(A, org, nb, r, col, in);
     Unit u;
-    u.ok = in && ih >= 0 && ih < XH && iw >= 0 && iw < XW && (b0 + nb) < A.B;
-    const int nbc = min(nb, A.B - 1 - b0), ihc = min(max(ih, 0), XH - 1), iwc = min(max(iw, 0), XW - 1);
-    u.ofs = 4u * (unsigned)((nbc * Cin + kbs * 8) * HW + ihc * XW + iwc);
-    u.dst = in ? kbs * IMGU + (nb * PH + r) * ROWU + ((MODE == R_FWD) ? (col & 1) * COLS + (col >> 1) : col) : -1;
+    u.ok = pe.ok;
+    u.ofs = 4u * (unsigned)(pe.ofs + kbs * 8 * HW);
+    u.dst = in ? kbs * IMGU + (nb * PH + r) * ROWU + ((MODE == CONV_FWD) ? (col & 1) * COLS + (col >> 1) : col) : -1;
     return u;
   };
 
@@ -235,7 +185,7 @@ __device__ __forceinline__ void ring_body(const RArgs& A, f32x4* lds, int bid, i
   // c0 = first channel of the 8 (FWD) / 16 (TR) channels to stage; clamped so that the address stays in the tensor
   // (past-the-end events happen at the last chunk and are never consumed)
   auto stage_load = [&](int c0) {
-    c0 = min(c0, Cin - ((MODE == R_FWD) ? 8 : 16));
+    c0 = min(c0, Cin - ((MODE == CONV_FWD) ? 8 : 16));
     staged_c0 = c0;
     unsigned ofs[NQ];
 #pragma unroll
@@ -252,7 +202,7 @@ __device__ __forceinline__ void ring_body(const RArgs& A, f32x4* lds, int bid, i
     f32x4 pl[NP];
     float vv[8];
     // BatchNorm + activation of the producing layer, on load.  Scalar loads: a unit's channels are wave-uniform.
-    const int cb = __builtin_amdgcn_readfirstlane(staged_c0 + ((MODE == R_FWD) ? 0 : (q & 1) * 8));
+    const int cb = __builtin_amdgcn_readfirstlane(staged_c0 + ((MODE == CONV_FWD) ? 0 : (q & 1) * 8));
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       float v = preg[q][j];
@@ -267,7 +217,7 @@ __device__ __forceinline__ void ring_body(const RArgs& A, f32x4* lds, int bid, i
     const int d = PATCH0 + bufu + u.dst;            // masked units go to the dummy unit (no divergent branch)
 #pragma unroll
     for (int p = 0; p < NP; ++p)
-      lds[(u.dst >= 0) ? d + p * ((MODE == R_FWD) ? IMGU : 2 * IMGU) : DUMMY] = pl[p];
+      lds[(u.dst >= 0) ? d + p * ((MODE == CONV_FWD) ? IMGU : 2 * IMGU) : DUMMY] = pl[p];
   };
   auto stage_store = [&](int bufu) {
 #pragma unroll
@@ -278,8 +228,8 @@ __device__ __forceinline__ void ring_body(const RArgs& A, f32x4* lds, int bid, i
   const int CoutP = A.CoutP;
   const size_t wstep = (size_t)2 * NP * CoutP;      // units per step in the pack
   const int nchunks = Cin / 16;
-  const bf16x8* wcls = A.w + (size_t)((MODE == R_FWD) ? 0 : tr_taps_before(R, SS)) * nchunks * wstep;
-  const bf16x8* dma_ptr2 = A.w + (size_t)(TWO ? tr_taps_before(R2 < 0 ? 0 : R2, SS2 < 0 ? 0 : SS2) : 0) * nchunks * wstep;
+  const bf16x8* wcls = A.w + (size_t)((MODE == CONV_FWD) ? 0 : class_taps_before(S, R, SS)) * nchunks * wstep;
+  const bf16x8* dma_ptr2 = A.w + (size_t)(TWO ? class_taps_before(S, R2 < 0 ? 0 : R2, SS2 < 0 ? 0 : SS2) : 0) * nchunks * wstep;
   // DMA instruction i of a step covers units [64 i, 64 i + 64) of the slot image [plane][kb][TN]
   unsigned dma_src[NDMA];     // per-lane BYTE offset within a pack step
   int dma_dst[NDMA];          // wave-uniform unit offset within the slot
@@ -312,9 +262,8 @@ __device__ __forceinline__ void ring_body(const RArgs& A, f32x4* lds, int bid, i
   for (int g = 0; g < FC; ++g) base_a[g] = RING0 + kb * TN + (wc * FC + g) * 32 + l32;
 #pragma unroll
   for (int f = 0; f < FP; ++f) {
-    const int m = (wp * FP + f) * 32 + l32;
-    const int nb = m / (TH * TW), r = m % (TH * TW);
-    base_b[f] = PATCH0 + (nb * PH + PSTEP * (r / TW)) * ROWU + r % TW + ((MODE == R_TR) ? kb * IMGU : 0);
+    const FragPixel fp = frag_pixel<C>(wp, f, l32);
+    base_b[f] = PATCH0 + (fp.nb * PH + PSTEP * fp.row) * ROWU + fp.col + ((MODE == CONV_TR) ? kb * IMGU : 0);
   }
 
   f32x16 accs[NACC][FC][FP];
@@ -333,7 +282,7 @@ __device__ __forceinline__ void ring_body(const RArgs& A, f32x4* lds, int bid, i
   // patch offset (units) of K step `s` of a chunk for k-block `k`, relative to base_b: FWD buffer = 8-channel half
   auto fwd_tap_off = [](int t) constexpr { return (t / 5) * ROWU + ((t % 5) & 1) * COLS + ((t % 5) >> 1); };
   auto step_off = [&](int s, int k) constexpr -> int {
-    if constexpr (MODE == R_FWD) {
+    if constexpr (MODE == CONV_FWD) {
       const int half = (s < 12) ? 0 : (s == 12 ? k : 1);
       const int tap = (s < 12) ? 2 * s + k : (s == 12 ? 24 : 2 * (s - 13) + k);
       return half * BUFU + fwd_tap_off(tap);
@@ -352,12 +301,12 @@ __device__ __forceinline__ void ring_body(const RArgs& A, f32x4* lds, int bid, i
       av[buf][g][p] = __builtin_bit_cast(bf16x8, lds[base_a[g] + so + p * 2 * TN]);
     } else {
       const int f = (j - FC * NP) / NP, p = (j - FC * NP) % NP;
-      bv[buf][f][p] = __builtin_bit_cast(bf16x8, lds[base_b[f] + bo + p * ((MODE == R_FWD) ? IMGU : 2 * IMGU)]);
+      bv[buf][f][p] = __builtin_bit_cast(bf16x8, lds[base_b[f] + bo + p * ((MODE == CONV_FWD) ? IMGU : 2 * IMGU)]);
     }
   };
   // patch offset of chunk-step s for this lane's k-block (+ TR: the chunk's patch buffer)
   auto patch_off = [&](int s, int pbuf) -> int {
-    if constexpr (MODE == R_FWD) return kb ? step_off(s, 1) : step_off(s, 0);
+    if constexpr (MODE == CONV_FWD) return kb ? step_off(s, 1) : step_off(s, 0);
     else return pbuf + step_off(s, 0);
   };
   // MFMA i of a step (i < NMF): plane products with index sum < NP, smallest terms first, all fragments per product
@@ -402,8 +351,8 @@ __device__ __forceinline__ void ring_body(const RArgs& A, f32x4* lds, int bid, i
 #endif
   int slot = 0;        // ring slot of the current step
   for (int ch = c_begin; ch < c_end; ++ch) {
-    const int pcur = (MODE == R_TR) ? ((ch - c_begin) & 1) * BUFU : 0;
-    const int pnxt = (MODE == R_TR) ? BUFU - pcur : 0;
+    const int pcur = (MODE == CONV_TR) ? ((ch - c_begin) & 1) * BUFU : 0;
+    const int pnxt = (MODE == CONV_TR) ? BUFU - pcur : 0;
 #pragma unroll
     for (int s = 0; s < NSTEP; ++s) {
       const int cur = s & 1, nxt = cur ^ 1;
@@ -411,9 +360,9 @@ __device__ __forceinline__ void ring_body(const RArgs& A, f32x4* lds, int bid, i
       // by the reads of step 12, issued in body 11); half A of the NEXT chunk is loaded at body 13 (its buffer is
       // free once step 12 has been read) and written at body 17.  TR: the next chunk at body 0 / body LW.
       constexpr int LW = (NSTEP >= 6) ? 3 : 2;
-      const bool ld = (MODE == R_FWD) ? (s == 0 || s == 13) : (s == 0);
-      const bool wr = (MODE == R_FWD) ? (s == 4 || s == 17) : (s == LW);
-      const int wbuf = (MODE == R_FWD) ? (s == 4 ? BUFU : 0) : pnxt;
+      const bool ld = (MODE == CONV_FWD) ? (s == 0 || s == 13) : (s == 0);
+      const bool wr = (MODE == CONV_FWD) ? (s == 4 || s == 17) : (s == LW);
+      const int wbuf = (MODE == CONV_FWD) ? (s == 4 ? BUFU : 0) : pnxt;
       // B_k: slot (k+1)%3 and the patch writes of body k-1 are visible
 #ifdef VG_RING_STAMP
       asm volatile("s_memtime %0" : "=s"(tk_a));
@@ -447,7 +396,7 @@ __device__ __forceinline__ void ring_body(const RArgs& A, f32x4* lds, int bid, i
         else
           dma_next(slot, TWO && (s + NSLOT) % NSTEP >= NA);        // step k+NSLOT into the slot read during body k-1
         if (ld) {
-          if constexpr (MODE == R_FWD) stage_load(ch * 16 + (s == 0 ? 8 : 16));
+          if constexpr (MODE == CONV_FWD) stage_load(ch * 16 + (s == 0 ? 8 : 16));
           else stage_load((ch + 1) * 16);
         }
       };
@@ -486,7 +435,7 @@ __device__ __forceinline__ void ring_body(const RArgs& A, f32x4* lds, int bid, i
       // In flight behind DMA(k+2), in issue order: DMA(k+3) .. DMA(k+NSLOT), and a staging event's loads for the NSLOT - 1
       // bodies from the one that issued them (they follow that body's DMA; hipcc itself waits for them where the
       // registers are used)
-      const bool ldw = (MODE == R_FWD) ? ((s >= 0 && s < NSLOT - 1) || (s >= 13 && s < 13 + NSLOT - 1)) : (s >= 0 && s < NSLOT - 1);
+      const bool ldw = (MODE == CONV_FWD) ? ((s >= 0 && s < NSLOT - 1) || (s >= 13 && s < 13 + NSLOT - 1)) : (s >= 0 && s < NSLOT - 1);
       if (ldw) wait_vmcnt<(NSLOT - 2) * NDMA + NL>(); else wait_vmcnt<(NSLOT - 2) * NDMA>();
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #ifdef VG_RING_STAMP
@@ -530,7 +479,6 @@ __device__ __forceinline__ void ring_body(const RArgs& A, f32x4* lds, int bid, i
           for (int r = 0; r < 16; ++r) accs[a][g][f][r] = accs[a][g][f][r] * x_unscale * w_unscale;
   }
 
-  const int YH = A.YH, YW = A.YW;
 #ifdef VG_RING_STAMP
   if (A.stats && lane == 0 && bid < 64) {
     unsigned long long* o = (unsigned long long*)A.stats + (size_t)(bid * 8 + wid) * 4;
@@ -544,6 +492,7 @@ __device__ __forceinline__ void ring_body(const RArgs& A, f32x4* lds, int bid, i
 #else
   const bool emit_stats = A.stats != nullptr;
 #endif
+  const int YH = A.YH, YW = A.YW;
   // one class's statistics + output (two classes: called twice)
   auto emit = [&](auto& acc, int Rc, int SSc) {
   // ---- optional: per-channel sums of the output for the next BatchNorm (ksplit == 1 only: the host says so)
@@ -553,11 +502,11 @@ __device__ __forceinline__ void ring_body(const RArgs& A, f32x4* lds, int bid, i
     for (int f = 0; f < FP; ++f) {
       const int m = (wp * FP + f) * 32 + l32;
       const int nb = m / (TH * TW), r = m % (TH * TW);
-      const int th = th0 + r / TW, tw = tw0 + r % TW;
-      const int oh = (MODE == R_FWD) ? th : S * th + Rc, ow = (MODE == R_FWD) ? tw : S * tw + SSc;
+      const int th = org.th0 + r / TW, tw = org.tw0 + r % TW;
+      const int oh = (MODE == CONV_FWD) ? th : S * th + Rc, ow = (MODE == CONV_FWD) ? tw : S * tw + SSc;
       pokf[f] = (b0 + nb) < A.B && oh < YH && ow < YW;
     }
-    const int cls = (MODE == R_FWD) ? 0 : 2 * Rc + SSc;
+    const int cls = (MODE == CONV_FWD) ? 0 : 2 * Rc + SSc;
     const int slot = (cls * (A.blocks_per_cls / A.ntiles_n) + pt) * C::WP + wp;
     float* sb = A.stats + (size_t)slot * Cout * 2;
 #pragma unroll
@@ -584,14 +533,14 @@ __device__ __forceinline__ void ring_body(const RArgs& A, f32x4* lds, int bid, i
         }
       }
   }
-  // ---- epilogue: + bias, NCHW store (as conv_igemm.hip)
+  // ---- epilogue: + bias, NCHW store
 #pragma unroll
   for (int f = 0; f < FP; ++f) {
     const int m = (wp * FP + f) * 32 + l32;
     const int nb = m / (TH * TW), r = m % (TH * TW);
-    const int th = th0 + r / TW, tw = tw0 + r % TW, b = b0 + nb;
-    const int oh = (MODE == R_FWD) ? th : S * th + Rc;
-    const int ow = (MODE == R_FWD) ? tw : S * tw + SSc;
+    const int th = org.th0 + r / TW, tw = org.tw0 + r % TW, b = b0 + nb;
+    const int oh = (MODE == CONV_FWD) ? th : S * th + Rc;
+    const int ow = (MODE == CONV_FWD) ? tw : S * tw + SSc;
     const bool pok = b < A.B && oh < YH && ow < YW;
     float* yb = A.y + (size_t)split * A.ysplit + ((size_t)b * Cout * YH + oh) * YW + ow;
 #pragma unroll
@@ -650,76 +599,42 @@ __global__ __launch_bounds__(RNT, 2) void conv5x5_ring_kernel(RArgs A) {
     bid -= cls * per * nsplit;
     const int split = bid / per;
     bid -= split * per;
-    switch (cls) {
-      case 0: ring_body<C, 0, 0, AFF>(A, lds, bid, split); break;
-      case 1: ring_body<C, 0, 1, AFF>(A, lds, bid, split); break;
-      case 2: ring_body<C, 1, 0, AFF>(A, lds, bid, split); break;
-      default: ring_body<C, 1, 1, AFF>(A, lds, bid, split); break;
-    }
+    for_class(cls, [&](auto R, auto SS) __attribute__((always_inline)) {
+      ring_body<C, decltype(R)::value, decltype(SS)::value, AFF>(A, lds, bid, split);
+    });
   }
 }
 
-struct RFuse {
-  const float* in_scale;
-  const float* in_shift;
-  int in_act;
-  float* stats;
-  const float* in_amax;
-};
-
+// fu: the caller's fusion (never NULL here; stats only without a K split: the host says so)
 template <class C>
 int launch_ring(const float* x, const bf16x8* w, const float* bias, float* y, int B, int Cin, int XH, int XW, int Cout,
-                int ksplit, float* slabs, RFuse fu, hipStream_t st) {
+                int ksplit, float* slabs, const vg_conv_fusion& fu, hipStream_t st) {
   RArgs A;
-  A.x = x; A.w = w; A.bias = bias; A.y = y;
+  const long per_cls = fill_split<C>(A, x, w, bias, y, B, Cin, XH, XW, Cout, ksplit, slabs, fu.in_amax);
   A.in_scale = fu.in_scale; A.in_shift = fu.in_shift; A.in_act = fu.in_act;
   A.stats = (ksplit == 1) ? fu.stats : nullptr;
-  A.in_amax = fu.in_amax;
-  A.B = B; A.Cin = Cin; A.XH = XH; A.XW = XW; A.Cout = Cout; A.CoutP = (Cout + 127) & ~127;
-  // the pack's trailer (common.hpp): behind the steps and the spare steps
-  A.w_unscale = (const float*)(w + vg_pack_trailer_units(Cin / 16 * 25, C::NP, A.CoutP));
-  int tsh, tsw;
-  if (C::MODE == R_FWD) {
-    A.YH = (XH - 1) / 2 + 1; A.YW = (XW - 1) / 2 + 1;
-    tsh = A.YH; tsw = A.YW;
-  } else {
-    A.YH = XH * 2; A.YW = XW * 2;
-    tsh = XH; tsw = XW;
-  }
-  A.tiles_w = cdiv(tsw, C::TW);
-  A.tiles_hw = cdiv(tsh, C::TH) * A.tiles_w;
-  A.ntiles_n = cdiv(Cout, C::TN);
-  const long per_cls = (long)A.ntiles_n * A.tiles_hw * cdiv(B, C::NB);
   // transposed: two classes per workgroup when that still gives every CU a workgroup (and the XCD arithmetic holds)
   A.paired = (C::NCLS == 4 && C::F16 && per_cls * ksplit * 2 >= 256 && per_cls % 8 == 0) ? 1 : 0;
   const long grid = per_cls * (A.paired ? 2 : C::NCLS) * ksplit;
-  if (grid <= 0 || grid > 0x7fffffffL) return VG_ERR_BAD_ARG;
-  A.blocks_per_cls = (int)per_cls;
-  A.cps = cdiv(Cin / 16, ksplit);
-  A.ysplit = (size_t)B * Cout * A.YH * A.YW;
-  if (ksplit > 1) A.y = slabs;
+  if (!grid_ok(grid)) return VG_ERR_BAD_ARG;
   if (A.in_scale) hipLaunchKernelGGL((conv5x5_ring_kernel<C, true>), dim3((unsigned)grid), dim3(RNT), 0, st, A);
   else hipLaunchKernelGGL((conv5x5_ring_kernel<C, false>), dim3((unsigned)grid), dim3(RNT), 0, st, A);
   VG_CHECK_LAUNCH();
-  if (ksplit > 1) {
-    if (A.ysplit > 0x7fffffffUL) return VG_ERR_BAD_ARG;
-    return vg_internal_wgrad_reduce(slabs, y, (int)A.ysplit, ksplit, st);   // fixed-order sum of the slabs
-  }
-  return 0;
+  return reduce_slabs(A, slabs, y, ksplit, st);
 }
 
 // pixel-tile geometry by the width of the tiled image (forward: output, transposed: input)
 template <int MODE, int WC, int FC, int FP, int NP, bool F16>
 int ring_geom(const float* x, const bf16x8* w, const float* bias, float* y, int B, int Cin, int XH, int XW, int Cout,
-              int ksplit, float* slabs, RFuse fu, hipStream_t st) {
-  const int tsw = (MODE == R_FWD) ? (XW - 1) / 2 + 1 : XW;
+              int ksplit, float* slabs, const vg_conv_fusion& fu, hipStream_t st) {
+  const int tsw = tile_extent(MODE, 2, XW);
   constexpr int TM = 32 * (8 / WC) * FP;
   static_assert(TM == 128 || TM == 256, "pixel tile");
   if constexpr (TM == 128) {
     if (tsw > 8) return launch_ring<RCfg<MODE, 1, 8, 16, WC, FC, FP, NP, F16>>(x, w, bias, y, B, Cin, XH, XW, Cout, ksplit, slabs, fu, st);
     // transposed, 8-wide images, 256 cout, three planes: ring + the two 2 x 10 x 10 patches (24 units per row) exceed
     // the LDS; the plan sends those layers to the 128-cout tiles
-    if constexpr (MODE == R_TR && WC * FC * 32 == 256 && NP == 3) return VG_ERR_BAD_ARG;
+    if constexpr (MODE == CONV_TR && WC * FC * 32 == 256 && NP == 3) return VG_ERR_BAD_ARG;
     else return launch_ring<RCfg<MODE, 2, 8, 8, WC, FC, FP, NP, F16>>(x, w, bias, y, B, Cin, XH, XW, Cout, ksplit, slabs, fu, st);
   } else {   // 256 pixels: whole 16 x 16 tiles only (the plan never picks it for narrower images)
     return launch_ring<RCfg<MODE, 1, 16, 16, WC, FC, FP, NP, F16>>(x, w, bias, y, B, Cin, XH, XW, Cout, ksplit, slabs, fu, st);
@@ -735,13 +650,13 @@ VG_KNOB(int, g_ring_variant, -1);   // tuning build only: forced tile variant
 // 128 cout x 256 px (2 x 4 wavefronts of 64 x 64).
 template <int MODE, int NP, bool F16>
 static int ring_dispatch(int variant, const float* x, const bf16x8* w, const float* bias, float* y, int B, int Cin, int XH,
-                         int XW, int Cout, int ksplit, float* slabs, RFuse fu, hipStream_t st) {
+                         int XW, int Cout, int ksplit, float* slabs, const vg_conv_fusion& fu, hipStream_t st) {
   switch (variant) {
     case 0: return ring_geom<MODE, 4, 2, 2, NP, F16>(x, w, bias, y, B, Cin, XH, XW, Cout, ksplit, slabs, fu, st);
     case 1: return ring_geom<MODE, 2, 2, 1, NP, F16>(x, w, bias, y, B, Cin, XH, XW, Cout, ksplit, slabs, fu, st);
     case 2: return ring_geom<MODE, 4, 1, 2, NP, F16>(x, w, bias, y, B, Cin, XH, XW, Cout, ksplit, slabs, fu, st);
     default:      // forward: with fp16 planes only (its patch does not fit beside the ring otherwise)
-      if constexpr (MODE == R_TR || F16) return ring_geom<MODE, 2, 2, 2, NP, F16>(x, w, bias, y, B, Cin, XH, XW, Cout, ksplit, slabs, fu, st);
+      if constexpr (MODE == CONV_TR || F16) return ring_geom<MODE, 2, 2, 2, NP, F16>(x, w, bias, y, B, Cin, XH, XW, Cout, ksplit, slabs, fu, st);
       return VG_ERR_BAD_ARG;
   }
 }
@@ -761,8 +676,8 @@ struct RingPlan {
 
 static RingPlan ring_plan(int mode, int B, int Cin, int XH, int XW, int Cout, int planes) {
   const bool f16 = (planes & VG_PLANES_F16_FLAG) != 0;      // two fp16 planes: smaller ring slots and patches, more tiles fit
-  const int tsw = (mode == R_FWD) ? (XW - 1) / 2 + 1 : XW, tsh = (mode == R_FWD) ? (XH - 1) / 2 + 1 : XH;
-  const int ncls = (mode == R_TR) ? 4 : 1;
+  const int tsw = tile_extent(mode, 2, XW), tsh = tile_extent(mode, 2, XH);
+  const int ncls = (mode == CONV_TR) ? 4 : 1;
   // pixel tiles of 128 (geometry 8 x 16 per image, or 2 images x 8 x 8)
   const long pt128 = (tsw > 8) ? (long)B * cdiv(tsh, 8) * cdiv(tsw, 16) : (long)cdiv(B, 2) * cdiv(tsh, 8) * cdiv(tsw, 8);
   RingPlan p;
@@ -770,16 +685,16 @@ static RingPlan ring_plan(int mode, int B, int Cin, int XH, int XW, int Cout, in
   // 4 x 2 wavefront arrangement (32 cout x 64 px per wavefront), and for the transposed form -- small patch -- the
   // 256-pixel tile when the image has whole 16 x 16 tiles
   if (Cout > 128) p.variant = 0;
-  else p.variant = (mode == R_TR && tsw >= 16 && tsh >= 16) ? 3 : 2;
+  else p.variant = (mode == CONV_TR && tsw >= 16 && tsh >= 16) ? 3 : 2;
   // fp16 planes, forward: the 128 cout x 256 px tile fits too (89.6 KB patch + 24 KB ring; with three bf16 planes 170 KB)
   // -- half the workgroups, half the filter DMA per MFMA -- where whole 16 x 16 tiles still give every CU a workgroup
-  if (f16 && mode == R_FWD && Cout <= 128 && tsw >= 16 && tsh >= 16 && tsw % 16 == 0 && tsh % 16 == 0 &&
+  if (f16 && mode == CONV_FWD && Cout <= 128 && tsw >= 16 && tsh >= 16 && tsw % 16 == 0 && tsh % 16 == 0 &&
       (long)B * (tsh / 16) * (tsw / 16) * cdiv(Cout, 128) >= 256)
     p.variant = 3;
   if (g_ring_variant >= 0) p.variant = g_ring_variant;
-  if (p.variant == 3 && ((mode == R_FWD && !f16) || tsw <= 8 || tsw % 16 || tsh % 16)) p.variant = 1;
+  if (p.variant == 3 && ((mode == CONV_FWD && !f16) || tsw <= 8 || tsw % 16 || tsh % 16)) p.variant = 1;
   // transposed, 8-wide images: the 256-cout tile's ring + two 2 x 10 x 10 patches exceed the LDS with three planes
-  if (p.variant == 0 && mode == R_TR && tsw <= 8 && !f16) p.variant = 2;
+  if (p.variant == 0 && mode == CONV_TR && tsw <= 8 && !f16) p.variant = 2;
   const int tn = (p.variant == 0) ? 256 : 128;
   const long wgs = ((p.variant == 3) ? (pt128 + 1) / 2 : pt128) * cdiv(Cout, tn) * ncls;
   p.ksplit = ring_ksplit(wgs, Cin / 16);
@@ -789,7 +704,7 @@ static RingPlan ring_plan(int mode, int B, int Cin, int XH, int XW, int Cout, in
 size_t vg_internal_ring_workspace_bytes(int mode, int B, int Cin, int H, int W, int Cout, int planes) {
   const RingPlan p = ring_plan(mode, B, Cin, H, W, Cout, planes);
   if (p.ksplit <= 1) return 0;
-  const size_t yh = (mode == R_FWD) ? (H - 1) / 2 + 1 : 2 * H, yw = (mode == R_FWD) ? (W - 1) / 2 + 1 : 2 * W;
+  const size_t yh = out_extent(mode, 2, H), yw = out_extent(mode, 2, W);
   return (size_t)p.ksplit * B * Cout * yh * yw * sizeof(float);
 }
 
@@ -798,37 +713,33 @@ size_t vg_internal_ring_workspace_bytes(int mode, int B, int Cin, int H, int W, 
 size_t vg_internal_ring_stats_floats(int mode, int B, int Cin, int H, int W, int Cout, int planes) {
   const RingPlan p = ring_plan(mode, B, Cin, H, W, Cout, planes);
   if (p.ksplit > 1) return 0;
-  const int tsw = (mode == R_FWD) ? (W - 1) / 2 + 1 : W, tsh = (mode == R_FWD) ? (H - 1) / 2 + 1 : H;
+  const int tsw = tile_extent(mode, 2, W), tsh = tile_extent(mode, 2, H);
   long tiles;
   if (p.variant == 3) tiles = (long)B * cdiv(tsh, 16) * cdiv(tsw, 16);
   else tiles = (tsw > 8) ? (long)B * cdiv(tsh, 8) * cdiv(tsw, 16) : (long)cdiv(B, 2) * cdiv(tsh, 8) * cdiv(tsw, 8);
   const int wp = (p.variant == 0 || p.variant == 2) ? 2 : 4;
-  return (size_t)tiles * wp * ((mode == R_TR) ? 4 : 1) * Cout * 2;
+  return (size_t)tiles * wp * ((mode == CONV_TR) ? 4 : 1) * Cout * 2;
 }
 
 int vg_internal_ring_conv(int mode, const float* x, const void* packed, const float* bias, float* y, int B, int Cin, int H,
-                          int W, int Cout, int planes, void* workspace, size_t workspace_bytes, const float* in_scale,
-                          const float* in_shift, int in_act, float* stats, size_t stats_floats, const float* in_amax,
+                          int W, int Cout, int planes, void* workspace, size_t workspace_bytes, const vg_conv_fusion* fuse,
                           hipStream_t st) {
+  const vg_conv_fusion none = {};
+  const vg_conv_fusion& fu = fuse ? *fuse : none;
   const RingPlan p = ring_plan(mode, B, Cin, H, W, Cout, planes);
   if (p.ksplit > 1 && (!workspace || workspace_bytes < vg_internal_ring_workspace_bytes(mode, B, Cin, H, W, Cout, planes)))
     return VG_ERR_WORKSPACE;
-  if ((in_scale == nullptr) != (in_shift == nullptr) || in_act < VG_ACT_NONE || in_act > VG_ACT_LRELU) return VG_ERR_BAD_ARG;
-  if (stats && (p.ksplit > 1 || stats_floats < vg_internal_ring_stats_floats(mode, B, Cin, H, W, Cout, planes))) return VG_ERR_BAD_ARG;
-  const bool f16 = (planes & VG_PLANES_F16_FLAG) != 0;
-  planes &= 0xff;
-  if (f16 && (planes != 2 || !in_amax)) return VG_ERR_BAD_ARG;
-  const RFuse fu = {in_scale, in_shift, in_act, stats, in_amax};
-  const bf16x8* w = (const bf16x8*)packed;
-  float* slabs = (float*)workspace;
-  if (mode == R_FWD) {
-    if (f16) return ring_dispatch<R_FWD, 2, true>(p.variant, x, w, bias, y, B, Cin, H, W, Cout, p.ksplit, slabs, fu, st);
-    if (planes == 3) return ring_dispatch<R_FWD, 3, false>(p.variant, x, w, bias, y, B, Cin, H, W, Cout, p.ksplit, slabs, fu, st);
-    return ring_dispatch<R_FWD, 2, false>(p.variant, x, w, bias, y, B, Cin, H, W, Cout, p.ksplit, slabs, fu, st);
-  }
-  if (f16) return ring_dispatch<R_TR, 2, true>(p.variant, x, w, bias, y, B, Cin, H, W, Cout, p.ksplit, slabs, fu, st);
-  if (planes == 3) return ring_dispatch<R_TR, 3, false>(p.variant, x, w, bias, y, B, Cin, H, W, Cout, p.ksplit, slabs, fu, st);
-  return ring_dispatch<R_TR, 2, false>(p.variant, x, w, bias, y, B, Cin, H, W, Cout, p.ksplit, slabs, fu, st);
+  if ((fu.in_scale == nullptr) != (fu.in_shift == nullptr) || fu.in_act < VG_ACT_NONE || fu.in_act > VG_ACT_LRELU) return VG_ERR_BAD_ARG;
+  if (fu.stats && (p.ksplit > 1 || fu.stats_floats < vg_internal_ring_stats_floats(mode, B, Cin, H, W, Cout, planes))) return VG_ERR_BAD_ARG;
+  if ((planes & VG_PLANES_F16_FLAG) && ((planes & 0xff) != 2 || !fu.in_amax)) return VG_ERR_BAD_ARG;
+  return for_planes(planes, [&](auto np, auto f16) {
+    constexpr int NP = decltype(np)::value;
+    constexpr bool F16 = decltype(f16)::value != 0;
+    const bf16x8* w = (const bf16x8*)packed;
+    float* slabs = (float*)workspace;
+    if (mode == CONV_FWD) return ring_dispatch<CONV_FWD, NP, F16>(p.variant, x, w, bias, y, B, Cin, H, W, Cout, p.ksplit, slabs, fu, st);
+    return ring_dispatch<CONV_TR, NP, F16>(p.variant, x, w, bias, y, B, Cin, H, W, Cout, p.ksplit, slabs, fu, st);
+  });
 }
 
 #ifdef VG_TUNING

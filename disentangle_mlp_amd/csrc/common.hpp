@@ -39,6 +39,11 @@ __device__ __forceinline__ int acc_row(int r, int lane) {
 // Activation applied on load: identity (slope 1), ReLU (0), LeakyReLU (0.2).  One compare, one select, one multiply,
 // no branch -- and a NaN stays a NaN, as in torch (fmaxf / fminf drop it: max(NaN, 0) = 0).
 __device__ __forceinline__ float act_slope(float v, float slope) { return v * (v > 0.f ? 1.f : slope); }
+// An operand read as act(v * scale[c] + shift[c]): the producing layer's BatchNorm and activation, applied on load
+// (vg_conv_fusion semantics; the host side is affine_on_load_slope, conv_tile.hpp).
+__device__ __forceinline__ float affine_act(float v, float sc, float sh, float slope) { return act_slope(fmaf(v, sc, sh), slope); }
+
+template <int V> struct IntC { static constexpr int value = V; };      // a compile-time int as a (generic lambda) argument
 
 // ---- split arithmetics of the convolution kernels -------------------------------------------
 // An fp32 operand becomes NP 16-bit planes; the plane products whose indices sum to < NP go to the 16-bit MFMA with
@@ -81,6 +86,34 @@ __device__ __forceinline__ unsigned f16_bound_exp(float amax) {
 __device__ __forceinline__ float f16_scale_of(float amax) { return __uint_as_float((268u - f16_bound_exp(amax)) << 23); }
 __device__ __forceinline__ float f16_unscale_of(float amax) { return __uint_as_float((f16_bound_exp(amax) - 14u) << 23); }
 
+// One bf16 plane of v[8]: the leading 8 significand bits of every element; v keeps what is left.
+__device__ __forceinline__ bf16x8 take_bf16_plane(float* v) {
+  bf16x8 q;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const __bf16 h = (__bf16)v[j];
+    q[j] = h;
+    v[j] -= (float)h;
+  }
+  return q;
+}
+// v[8] -> NP bf16 planes hi, (mid,) lo, typed; v is consumed.  The kernels that feed the planes straight to the MFMA
+// (conv_thin_*.hip) use this form: no bit casts on their fragments.
+template <int NP>
+__device__ __forceinline__ void split_bf16(float* v, bf16x8* out) {
+#pragma unroll
+  for (int p = 0; p < NP; ++p) out[p] = take_bf16_plane(v);
+}
+
+// The plane products of one MFMA step, index sum < NP, smallest terms first: f(IntC<pa>, IntC<pb>) for sum = NP - 1 .. 0,
+// pa = sum .. 0, pb = sum - pa -- (2,0) (1,1) (0,2) (1,0) (0,1) (0,0) for three planes, (1,0) (0,1) (0,0) for two.
+template <int NP, int SUM = NP - 1, int PA = SUM, class F>
+__device__ __forceinline__ void for_plane_products(F&& f) {
+  f(IntC<PA>{}, IntC<SUM - PA>{});
+  if constexpr (PA > 0) for_plane_products<NP, SUM, PA - 1>(f);
+  else if constexpr (SUM > 0) for_plane_products<NP, SUM - 1, SUM - 1>(f);
+}
+
 // v[8] (already scaled when F16) -> NP planes as raw 16-byte units; v is consumed
 template <int NP, bool F16>
 __device__ __forceinline__ void split_planes16(float* v, f32x4* out) {
@@ -104,16 +137,7 @@ __device__ __forceinline__ void split_planes16(float* v, f32x4* out) {
     out[1] = __builtin_bit_cast(f32x4, P4{{lo[0], lo[1], lo[2], lo[3]}});
   } else {
 #pragma unroll
-    for (int p = 0; p < NP; ++p) {                // hi, (mid,) lo: each plane takes the leading 8 bits of what is left
-      bf16x8 q;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const __bf16 h = (__bf16)v[j];
-        q[j] = h;
-        v[j] -= (float)h;
-      }
-      out[p] = __builtin_bit_cast(f32x4, q);
-    }
+    for (int p = 0; p < NP; ++p) out[p] = __builtin_bit_cast(f32x4, take_bf16_plane(v));      // hi, (mid,) lo
   }
 }
 

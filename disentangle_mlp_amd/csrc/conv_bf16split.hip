@@ -619,8 +619,7 @@ int fwd_ksplit(int B, int Cin, int H, int W, int Cout, int S) {
 
 // the shape every entry point of the split arithmetics takes
 bool shape_ok(int B, int Cin, int H, int W, int Cout, int stride, int planes) {
-  if (B <= 0 || Cin <= 0 || Cin % 16 || Cout <= 0 || H <= 0 || W <= 0) return false;
-  return (stride == 1 || stride == 2) && planes_ok(planes);
+  return conv_shape_ok(B, Cin, H, W, Cout, stride) && Cin % 16 == 0 && planes_ok(planes);
 }
 
 bool x_args_ok(const float* x, const void* packed, float* y, int B, int Cin, int H, int W, int Cout, int stride, int planes) {

@@ -729,7 +729,7 @@ int vg_internal_ring_conv(int mode, const float* x, const void* packed, const fl
   const RingPlan p = ring_plan(mode, B, Cin, H, W, Cout, planes);
   if (p.ksplit > 1 && (!workspace || workspace_bytes < vg_internal_ring_workspace_bytes(mode, B, Cin, H, W, Cout, planes)))
     return VG_ERR_WORKSPACE;
-  if ((fu.in_scale == nullptr) != (fu.in_shift == nullptr) || fu.in_act < VG_ACT_NONE || fu.in_act > VG_ACT_LRELU) return VG_ERR_BAD_ARG;
+  if (affine_on_load_slope(fu.in_scale, fu.in_shift, fu.in_act) < 0.f) return VG_ERR_BAD_ARG;      // (the kernel derives the slope from in_act)
   if (fu.stats && (p.ksplit > 1 || fu.stats_floats < vg_internal_ring_stats_floats(mode, B, Cin, H, W, Cout, planes))) return VG_ERR_BAD_ARG;
   if ((planes & VG_PLANES_F16_FLAG) && ((planes & 0xff) != 2 || !fu.in_amax)) return VG_ERR_BAD_ARG;
   return for_planes(planes, [&](auto np, auto f16) {

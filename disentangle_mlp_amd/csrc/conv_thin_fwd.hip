@@ -20,12 +20,9 @@
 //     (vg_conv_fusion.stats layout [slot][Cout][2], consumed by vg_bn_finalize_stats).
 // No barrier after the staging one.  Arithmetic: operands split exactly into NP bf16 planes, plane products with index
 // sum < NP, fp32 accumulate (NP = 3: fp32-equivalent, as conv_ring.hip).
-#include "common.hpp"
-#include "vaegan_hip.h"
+#include "conv_tile.hpp"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 
 struct FArgs {
   const float* x;
@@ -35,19 +32,6 @@ struct FArgs {
   float* stats;        // [slot][Cout][2] or NULL
   int B, Cin, H, W, Cout, OH, OW, bands, strips;
 };
-
-template <int NP>
-__device__ __forceinline__ void split_frag(float* v, bf16x8* out) {
-#pragma unroll
-  for (int p = 0; p < NP; ++p) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const __bf16 h = (__bf16)v[j];
-      out[p][j] = h;
-      v[j] -= (float)h;
-    }
-  }
-}
 
 template <int S>
 struct FCfg {
@@ -123,7 +107,7 @@ __global__ __launch_bounds__(512) void conv_thin_fwd_kernel(FArgs A) {
 
   // ---- filter fragments A[co][k] of every kh.  k-block h, element j: j < 5 -> (channel 2h, kw = j);
   // j >= 5 -> (channel 1, kw = 3h + j - 5), kw = 5 does not exist: zero.  Accumulator register r of this lane is channel
-  // (r & 3) + 8 * (r >> 2) + 4 * half of the group.
+  // acc_row(r, lane) of the group.
   const int c5 = 2 * half, o3 = 3 * half;
   const int co_l = cg * 32 + l32;
   bf16x8 wf[5][NP];
@@ -145,7 +129,7 @@ __global__ __launch_bounds__(512) void conv_thin_fwd_kernel(FArgs A) {
         const float t = wl3[kh * 5 + j];               // kw = 5 (half 1, j = 2): masked, the read stays inside LDS
         v[5 + j] = (ok3 && !(half && j == 2)) ? t : 0.f;
       }
-      split_frag<NP>(v, wf[kh]);
+      split_bf16<NP>(v, wf[kh]);
     }
   }
 
@@ -168,7 +152,7 @@ __global__ __launch_bounds__(512) void conv_thin_fwd_kernel(FArgs A) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] = 0.f;
     }
-    split_frag<NP>(v, win[slot]);
+    split_bf16<NP>(v, win[slot]);
   };
 
   float s1[16], s2[16];
@@ -196,6 +180,9 @@ __global__ __launch_bounds__(512) void conv_thin_fwd_kernel(FArgs A) {
         f32x16 d, d1;
 #pragma unroll
         for (int r = 0; r < 16; ++r) d[r] = d1[r] = 0.f;
+        // (the order of for_plane_products, common.hpp, written out: through the helper AND split_bf16 together hipcc
+        // fuses the three-plane kernels' s2 update below into v_pk_fma_f32 where it otherwise keeps a rounded product
+        // and a sum -- other statistics bits)
         {
           int n = 0;
 #pragma unroll
@@ -222,7 +209,7 @@ __global__ __launch_bounds__(512) void conv_thin_fwd_kernel(FArgs A) {
         const bool full = (cg + 1) * 32 <= Cout;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          d[r] += bias_l[cg * 32 + (r & 3) + 8 * (r >> 2) + 4 * half];
+          d[r] += bias_l[cg * 32 + acc_row(r, lane)];
           s1[r] += d[r];
           s2[r] += d[r] * d[r];
         }
@@ -233,12 +220,12 @@ __global__ __launch_bounds__(512) void conv_thin_fwd_kernel(FArgs A) {
         if (full) {
 #pragma unroll
           for (int r = 0; r < 16; ++r)
-            *(float*)(yrow + (lb + (unsigned)((r & 3) + 8 * (r >> 2)) * plane_byte)) = d[r];
+            *(float*)(yrow + (lb + (unsigned)acc_row(r, 0) * plane_byte)) = d[r];      // (the lane half is in lb)
         } else {
 #pragma unroll
           for (int r = 0; r < 16; ++r)
-            if (cg * 32 + (r & 3) + 8 * (r >> 2) + 4 * half < Cout)
-              *(float*)(yrow + (lb + (unsigned)((r & 3) + 8 * (r >> 2)) * plane_byte)) = d[r];
+            if (cg * 32 + acc_row(r, lane) < Cout)
+              *(float*)(yrow + (lb + (unsigned)acc_row(r, 0) * plane_byte)) = d[r];
         }
       }
     }
@@ -255,7 +242,7 @@ __global__ __launch_bounds__(512) void conv_thin_fwd_kernel(FArgs A) {
         a += __shfl_xor(a, msk, 64);
         q += __shfl_xor(q, msk, 64);
       }
-      const int co = cg * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+      const int co = cg * 32 + acc_row(r, lane);
       if (l32 == 0 && co < Cout) {
         slot[co * 2] = a;
         slot[co * 2 + 1] = q;
@@ -270,9 +257,9 @@ struct FPlan {
 };
 
 bool make_fplan(int B, int Cin, int H, int W, int Cout, int S, FPlan& p) {
-  if (Cin < 1 || Cin > 3 || Cout < 1 || (S != 1 && S != 2) || H < 1 || W < 1 || B < 1) return false;
-  p.OH = (H - 1) / S + 1;
-  p.OW = (W - 1) / S + 1;
+  if (!conv_shape_ok(B, Cin, H, W, Cout, S) || Cin > 3) return false;
+  p.OH = out_dim(H, S);
+  p.OW = out_dim(W, S);
   if (S == 2 && (W % 2)) return false;                 // patch columns S*ow + kw <= W + 3
   if (p.OW % 32 || (size_t)p.OH * p.OW > ((size_t)1 << 24)) return false;     // 32-bit byte offsets inside a 32-channel group
   p.strips = p.OW / 32;

@@ -23,12 +23,9 @@
 //     thread (co, ow) sums its 5 terms, adds the bias and stores 256-byte runs.
 // Arithmetic: operands split exactly into NP bf16 planes, the plane products with index sum < NP, fp32 accumulate
 // (NP = 3: fp32-equivalent, as conv_ring.hip).
-#include "common.hpp"
-#include "vaegan_hip.h"
+#include "conv_tile.hpp"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 
 constexpr int TCIN = 32, TRB = 16;            // input channels (= one MFMA K), output rows per workgroup
 constexpr int TPITCH = 17;                    // floats per column of the LDS row buffer (16 + 1: conflict-free reads)
@@ -43,19 +40,6 @@ struct TArgs {
   float* y;
   int B, H, W, bands;
 };
-
-template <int NP>
-__device__ __forceinline__ void split_frag(float* v, bf16x8* out) {
-#pragma unroll
-  for (int p = 0; p < NP; ++p) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const __bf16 h = (__bf16)v[j];
-      out[p][j] = h;
-      v[j] -= (float)h;
-    }
-  }
-}
 
 template <int COUT, int NP>
 __global__ __launch_bounds__(512) void convT_s1_thin_mfma_kernel(TArgs A) {
@@ -80,7 +64,7 @@ __global__ __launch_bounds__(512) void convT_s1_thin_mfma_kernel(TArgs A) {
         const float t = A.w[((kblk * 8 + j) * COUT + min(co, COUT - 1)) * 25 + kh * 5 + kw];   // read, then select
         v[j] = (m < COUT * 5) ? t : 0.f;
       }
-      split_frag<NP>(v, bf[kh]);
+      split_bf16<NP>(v, bf[kh]);
     }
   }
   float sc[8], sh[8];
@@ -110,11 +94,10 @@ __global__ __launch_bounds__(512) void convT_s1_thin_mfma_kernel(TArgs A) {
     const bool ok = ih >= 0 && ih < H;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      float t = fmaf(raw[slot][j], sc[j], sh[j]);                   // the producing layer's BatchNorm ...
-      t = act_slope(t, A.in_slope);                                 // ... and activation, on load
+      const float t = affine_act(raw[slot][j], sc[j], sh[j], A.in_slope);   // the producer's BatchNorm and activation, on load
       v[j] = ok ? t : 0.f;                                          // padding pads the activated tensor
     }
-    split_frag<NP>(v, win[slot]);
+    split_bf16<NP>(v, win[slot]);
   };
 
   // this thread's outputs in the epilogue: (co, ow), for tid < COUT * W
@@ -199,11 +182,11 @@ extern "C" int vg_convT5x5_s1_thin_bf16split(const float* x, const float* w, con
                                              const float* in_shift, int in_act, void* stream) {
   if (!x || !w || !y || B <= 0 || (planes != 2 && planes != 3)) return VG_ERR_BAD_ARG;
   if (!vg_convT5x5_s1_thin_bf16split_ok(Cin, H, W, Cout)) return VG_ERR_BAD_ARG;
-  if ((in_scale == nullptr) != (in_shift == nullptr) || in_act < VG_ACT_NONE || in_act > VG_ACT_LRELU) return VG_ERR_BAD_ARG;
+  const float slope = affine_on_load_slope(in_scale, in_shift, in_act);
+  if (slope < 0.f) return VG_ERR_BAD_ARG;
   TArgs A;
   A.x = x; A.w = w; A.bias = bias; A.y = y;
-  A.in_scale = in_scale; A.in_shift = in_shift;
-  A.in_slope = (!in_scale || in_act == VG_ACT_NONE) ? 1.f : (in_act == VG_ACT_RELU ? 0.f : 0.2f);
+  A.in_scale = in_scale; A.in_shift = in_shift; A.in_slope = slope;
   A.B = B; A.H = H; A.W = W; A.bands = cdiv(H, TRB);
   if ((long)B * A.bands > 0x7fffffffL || (size_t)TCIN * H * W > 0x7fffffffUL) return VG_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;

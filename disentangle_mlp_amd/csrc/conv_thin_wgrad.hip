@@ -17,41 +17,23 @@
 //     conv_wgrad.hip's reduction sums the slabs in order (deterministic).
 // Arithmetic: operands split exactly into NP bf16 planes, plane products with index sum < NP, fp32 accumulate (NP = 3:
 // fp32-equivalent, as conv_ring.hip).
-#include "common.hpp"
-#include "vaegan_hip.h"
+#include "conv_tile.hpp"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-
 constexpr int WNT = 512;
 
-struct TWArgs {
+struct TWArgs : WgradGeom {
   // the gy operand read as act(gy * gy_scale[c] + gy_shift[c]) -- the weight gradient of deconv4 passes the layer's INPUT
   // in this slot, whose producer's BatchNorm + ReLU is applied here instead of being materialised (NULL: plain)
   const float* gy_scale;
   const float* gy_shift;
   float gy_slope;
-  const float* x;
   const float* gy;
   float* slabs;        // [workgroup][Cout][Cin * 25]
-  int B, Cin, H, W, Cout, OH, OW;
   int rb, rbi, ng, kg;         // band: output rows, staged input rows, 8-pixel groups per row, 16-pixel steps per row
   int bands, units_per_wg, total_units;       // unit = (image, band)
 };
-
-template <int NP>
-__device__ __forceinline__ void split_frag(float* v, bf16x8* out) {
-#pragma unroll
-  for (int p = 0; p < NP; ++p) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const __bf16 h = (__bf16)v[j];
-      out[p][j] = h;
-      v[j] -= (float)h;
-    }
-  }
-}
 
 // MT: 32-channel groups of gy handled together (they share the B fragments)
 template <int S, int MT, int NP>
@@ -135,7 +117,7 @@ __global__ __launch_bounds__(WNT) void conv_thin_wgrad_kernel(TWArgs A) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] = xr[S * j];
       bf16x8 pl[NP];
-      split_frag<NP>(v, pl);
+      split_bf16<NP>(v, pl);
       f32x4* dst = cp + kw * kw_units + ci * ci_units + r * row_units + g * NP;
 #pragma unroll
       for (int p = 0; p < NP; ++p) dst[p] = __builtin_bit_cast(f32x4, pl[p]);
@@ -169,12 +151,9 @@ __global__ __launch_bounds__(WNT) void conv_thin_wgrad_kernel(TWArgs A) {
       for (int m = 0; m < MT; ++m) {
         if (aff) {                                     // wave-uniform: a lane's channel is fixed, its coefficients are loaded once
 #pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const float v = fmaf(raw[slot][m][j], a_sc[m], a_sh[m]);
-            raw[slot][m][j] = act_slope(v, A.gy_slope);
-          }
+          for (int j = 0; j < 8; ++j) raw[slot][m][j] = affine_act(raw[slot][m][j], a_sc[m], a_sh[m], A.gy_slope);
         }
-        split_frag<NP>(raw[slot][m], af[m]);
+        split_bf16<NP>(raw[slot][m], af[m]);
       }
       const int boff = (S * row) * row_units + (2 * k16) * NP;
 #pragma unroll
@@ -182,13 +161,11 @@ __global__ __launch_bounds__(WNT) void conv_thin_wgrad_kernel(TWArgs A) {
         bf16x8 bf[NP];
 #pragma unroll
         for (int p = 0; p < NP; ++p) bf[p] = __builtin_bit_cast(bf16x8, cp[bbase[t] + boff + p]);
+        for_plane_products<NP>([&](auto pa, auto pb) {
 #pragma unroll
-        for (int sum = NP - 1; sum >= 0; --sum)
-#pragma unroll
-          for (int pa = sum; pa >= 0; --pa)
-#pragma unroll
-            for (int m = 0; m < MT; ++m)
-              acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[m][pa], bf[sum - pa], acc[m][t], 0, 0, 0);
+          for (int m = 0; m < MT; ++m)
+            acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[m][pa.value], bf[pb.value], acc[m][t], 0, 0, 0);
+        });
       }
     };
     const int nmine = (nsteps > wid) ? (nsteps - wid + 7) / 8 : 0;     // steps wid, wid + 8, ...
@@ -217,7 +194,7 @@ __global__ __launch_bounds__(WNT) void conv_thin_wgrad_kernel(TWArgs A) {
       __syncthreads();
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int rowi = (r & 3) + 8 * (r >> 2) + 4 * half;             // channel within the group
+        const int rowi = acc_row(r, lane);                               // channel within the group
         red[(wid * 32 + rowi) * 32 + l32] = acc[m][t][r];
       }
       __syncthreads();
@@ -238,10 +215,10 @@ struct TWPlan {
 };
 
 bool make_twplan(int B, int Cin, int H, int W, int Cout, int S, int planes, TWPlan& p) {
-  if (B < 1 || Cin < 1 || Cin > 3 || Cout < 1 || Cout > 64 || H < 1 || W < 1 || (S != 1 && S != 2)) return false;
+  if (!conv_shape_ok(B, Cin, H, W, Cout, S) || Cin > 3 || Cout > 64) return false;
   if (planes != 2 && planes != 3) return false;
-  p.OH = (H - 1) / S + 1;
-  p.OW = (W - 1) / S + 1;
+  p.OH = out_dim(H, S);
+  p.OW = out_dim(W, S);
   if (p.OW % 16 || (S == 2 && (W % 2))) return false;
   p.ng = p.OW / 8;
   p.kg = p.OW / 16;
@@ -299,17 +276,16 @@ extern "C" int vg_conv5x5_thin_wgrad_bf16split(const float* x, const float* gy, 
                                                int Cout, int stride, int planes, void* workspace, size_t workspace_bytes,
                                                const float* gy_scale, const float* gy_shift, int gy_act, int accumulate,
                                                void* stream) {
-  if (!x || !gy || !dw) return VG_ERR_BAD_ARG;
-  if ((gy_scale == nullptr) != (gy_shift == nullptr) || gy_act < VG_ACT_NONE || gy_act > VG_ACT_LRELU) return VG_ERR_BAD_ARG;
+  const float slope = affine_on_load_slope(gy_scale, gy_shift, gy_act);
+  if (!x || !gy || !dw || slope < 0.f) return VG_ERR_BAD_ARG;
   TWPlan p;
   if (!make_twplan(B, Cin, H, W, Cout, stride, planes, p)) return VG_ERR_BAD_ARG;
   if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < p.slab_bytes) return VG_ERR_WORKSPACE;
   if (((uintptr_t)gy & 15) != 0) return VG_ERR_BAD_ARG;
   TWArgs A;
-  A.x = x; A.gy = gy; A.slabs = (float*)workspace;
-  A.gy_scale = gy_scale; A.gy_shift = gy_shift;
-  A.gy_slope = (!gy_scale || gy_act == VG_ACT_NONE) ? 1.f : (gy_act == VG_ACT_RELU ? 0.f : 0.2f);
-  A.B = B; A.Cin = Cin; A.H = H; A.W = W; A.Cout = Cout; A.OH = p.OH; A.OW = p.OW;
+  fill_wgrad(A, x, B, Cin, H, W, Cout, p);
+  A.gy = gy; A.slabs = (float*)workspace;
+  A.gy_scale = gy_scale; A.gy_shift = gy_shift; A.gy_slope = slope;
   A.rb = p.rb; A.rbi = p.rbi; A.ng = p.ng; A.kg = p.kg; A.bands = p.bands; A.units_per_wg = p.upw; A.total_units = p.total;
   hipStream_t st = (hipStream_t)stream;
   int rc;

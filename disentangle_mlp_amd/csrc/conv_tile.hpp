@@ -3,6 +3,10 @@
 // the tap algebra of the parity classes, workgroup -> tile placement, the fragment-pixel decode, the clamped patch address,
 // the class dispatch and the host-side tile geometry.  Everything is constexpr or __forceinline__ and holds no state; the
 // staging maps, LDS layouts, MFMA loops and -- measured, DESIGN.md section 4.28 -- the output epilogues stay in the kernels.
+// Below them, what the weight-gradient and <= 3-channel kernels share with them and with each other (DESIGN.md section
+// 4.29; conv_wgrad.hip, wgrad_bf16split.hip, conv_thin_wgrad.hip, conv_thin_fwd.hip, conv_thin_mfma.hip): the shape
+// predicate and out_dim, the host side of an affine-on-load operand, the weight-gradient argument blocks, the chunk
+// decode and the partial-slab store.  The arithmetic pieces (plane split, product order, affine_act) are in common.hpp.
 //
 // A tile configuration C (Cfg / XCfg / RCfg) names MODE, S, NB, TH, TW, TN, WC, WP, FC, FP: a workgroup computes TN output
 // channels x NB * TH * TW pixels of the tile space (forward: the output; transposed: the input, one output-parity class at
@@ -12,8 +16,6 @@
 #include "vaegan_hip.h"
 
 enum { CONV_FWD = 0, CONV_TR = 1 };
-
-template <int V> struct IntC { static constexpr int value = V; };      // a compile-time int as a (generic lambda) argument
 
 // ---- tap algebra ------------------------------------------------------------------------------------------------------
 // The stride-S transposed convolution runs as its S * S output-parity classes: output (S*i + R, S*j + SS) sums the taps
@@ -152,9 +154,22 @@ int for_stride(int stride, F&& f) {
 }
 
 // ---- host geometry -----------------------------------------------------------------------------------------------------
+// the shape every 5x5 / pad 2 entry point takes (each adds its own conditions), and the output extent of a stride-S
+// convolution along a dimension of X input elements
+inline bool conv_shape_ok(int B, int Cin, int H, int W, int Cout, int stride) {
+  return B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0 && (stride == 1 || stride == 2);
+}
+constexpr int out_dim(int X, int S) { return (X - 1) / S + 1; }
 // extent of the tile space / of the output along a dimension of X input elements
-constexpr int tile_extent(int mode, int S, int X) { return (mode == CONV_FWD) ? (X - 1) / S + 1 : X; }
-constexpr int out_extent(int mode, int S, int X) { return (mode == CONV_FWD) ? (X - 1) / S + 1 : X * S; }
+constexpr int tile_extent(int mode, int S, int X) { return (mode == CONV_FWD) ? out_dim(X, S) : X; }
+constexpr int out_extent(int mode, int S, int X) { return (mode == CONV_FWD) ? out_dim(X, S) : X * S; }
+
+// An operand with an affine + activation applied on load (common.hpp, affine_act): scale and shift come together, act is
+// a VG_ACT_*.  Returns the slope act_slope takes -- 1 where there is nothing to apply -- or a negative value: bad argument.
+inline float affine_on_load_slope(const float* scale, const float* shift, int act) {
+  if ((scale == nullptr) != (shift == nullptr) || act < VG_ACT_NONE || act > VG_ACT_LRELU) return -1.f;
+  return (!scale || act == VG_ACT_NONE) ? 1.f : (act == VG_ACT_RELU ? 0.f : 0.2f);
+}
 
 // Fills the shared fields for tile configuration C; returns the workgroups per class (and per K split).
 template <class C>
@@ -202,6 +217,48 @@ size_t vg_internal_ring_stats_floats(int mode, int B, int Cin, int H, int W, int
 int vg_internal_ring_conv(int mode, const float* x, const void* packed, const float* bias, float* y, int B, int Cin, int H,
                           int W, int Cout, int planes, void* workspace, size_t workspace_bytes, const vg_conv_fusion* fuse,
                           hipStream_t st);
+
+// ---- the weight-gradient kernels (conv_wgrad.hip, wgrad_bf16split.hip, conv_thin_wgrad.hip) -----------------------------
+// dw[co][ci][kh][kw] = sum_{b,oh,ow} gy[b][co][oh][ow] * x[b][ci][S*oh+kh-2][S*ow+kw-2]: what every argument block starts
+// with (filled by fill_wgrad from the plan's OH / OW) ...
+struct WgradGeom {
+  const float* x;
+  int B, Cin, H, W, Cout, OH, OW;
+};
+template <class P>
+void fill_wgrad(WgradGeom& A, const float* x, int B, int Cin, int H, int W, int Cout, const P& plan) {
+  A.x = x;
+  A.B = B; A.Cin = Cin; A.H = H; A.W = W; A.Cout = Cout; A.OH = plan.OH; A.OW = plan.OW;
+}
+// ... and, for the two implicit GEMMs D[co][ci * 25 + tap], the tiling: mtiles x ntiles output tiles, the reduction cut
+// into `chunks` = (image or image group) x tiles_hw pixel tiles, tiles_w of them across a row.
+struct WgradTiles : WgradGeom {
+  int mtiles, ntiles, tiles_w, tiles_hw, chunks;
+};
+template <class P>
+void fill_wgrad_tiles(WgradTiles& A, const float* x, int B, int Cin, int H, int W, int Cout, const P& plan) {
+  fill_wgrad(A, x, B, Cin, H, W, Cout, plan);
+  A.mtiles = plan.mtiles; A.ntiles = plan.ntiles; A.tiles_w = plan.tiles_w; A.tiles_hw = plan.tiles_hw; A.chunks = plan.chunks;
+}
+// chunk -> (image or image group, first output row, first output column) of its TH x TW pixel tile
+template <int TH, int TW>
+__device__ __forceinline__ void chunk_pos(const WgradTiles& A, int chunk, int& b, int& oh0, int& ow0) {
+  b = chunk / A.tiles_hw;
+  const int sp = chunk % A.tiles_hw;
+  oh0 = (sp / A.tiles_w) * TH;
+  ow0 = (sp % A.tiles_w) * TW;
+}
+// One 32 x 32 accumulator fragment into a partial slab ws[co][ci * 25 + tap]: rows co0 + acc_row, column n of the tile
+// of CIT input channels from ci0 (lanes = consecutive n: coalesced); columns past the tile or Cin and rows past Cout stay.
+template <int CIT>
+__device__ __forceinline__ void store_slab_frag(float* ws, const f32x16& acc, int co0, int ci0, int n, int lane, int Cin, int Cout) {
+  const bool nok = n < CIT * 25 && (ci0 + n / 25) < Cin;
+#pragma unroll
+  for (int r16 = 0; r16 < 16; ++r16) {
+    const int co = co0 + acc_row(r16, lane);
+    if (nok && co < Cout) ws[((size_t)co * Cin + ci0) * 25 + n] = acc[r16];
+  }
+}
 
 // after the launch: fixed-order sum of the K split's slabs into y
 inline int reduce_slabs(const SplitGeom& A, float* slabs, float* y, int ksplit, hipStream_t st) {

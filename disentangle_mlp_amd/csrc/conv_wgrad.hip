@@ -15,8 +15,10 @@
 // [5][PH][PW] in LDS; lane (j,h) reads x-patch[ci(j)][S*oh+kh(j)][S*ow+kw(j)] at a
 // per-lane base + compile-time immediate.  Partial slabs go to the workspace
 // and are summed in a fixed order by a second kernel (deterministic, no atomics).
-#include "common.hpp"
-#include "vaegan_hip.h"
+// The argument block's base, the chunk decode and the slab store are shared with
+// wgrad_bf16split.hip (conv_tile.hpp); the slab reducers below serve all three
+// weight-gradient files.
+#include "conv_tile.hpp"
 
 namespace {
 
@@ -41,12 +43,10 @@ struct WCfg {
   static_assert(KS == 1 || STAGE >= 4 * (128 / 32 / (4 / WM)) * 16 * 64, "LDS holds one fragment row of partials per wave");
 };
 
-struct WArgs {
-  const float* x;
+struct WArgs : WgradTiles {
   const float* gy;
   float* ws;
-  int B, Cin, H, W, Cout, OH, OW;
-  int mtiles, ntiles, splits, tiles_w, tiles_hw, chunks, chunks_per_split;
+  int splits, chunks_per_split;
   int vec4;   // gy rows can be read as aligned 16-byte pieces (OW % 4 == 0, 16-byte aligned base)
 };
 
@@ -90,8 +90,8 @@ __global__ __launch_bounds__(C::NT, 2) void conv5x5_wgrad_kernel(WArgs A) {
 
   float preg[NQP], areg[NQA];
   auto load_chunk = [&](int chunk) {
-    const int b = chunk / A.tiles_hw, sp = chunk % A.tiles_hw;
-    const int th0 = (sp / A.tiles_w) * TH, tw0 = (sp % A.tiles_w) * TW;
+    int b, th0, tw0;
+    chunk_pos<TH, TW>(A, chunk, b, th0, tw0);
     const int ih0 = S * th0 - 2, iw0 = S * tw0 - 2;
     const float* xb = A.x + ((size_t)b * Cin + ci0) * HW;
     const int shift = ih0 * W + iw0;
@@ -225,16 +225,9 @@ __global__ __launch_bounds__(C::NT, 2) void conv5x5_wgrad_kernel(WArgs A) {
   float* wsb = A.ws + (size_t)split * Cout * Cin * 25;
 #pragma unroll
   for (int f = 0; f < FN; ++f) {
-    const int n = (wn * FN + f) * 32 + l32;
-    const bool nok = n < CIT * 25 && (ci0 + n / 25) < Cin;
 #pragma unroll
-    for (int g = 0; g < FC; ++g) {
-#pragma unroll
-      for (int r16 = 0; r16 < 16; ++r16) {
-        const int co = m0 + (wm * FC + g) * 32 + acc_row(r16, lane);
-        if (nok && co < Cout) wsb[((size_t)co * Cin + ci0) * 25 + n] = acc[g][f][r16];
-      }
-    }
+    for (int g = 0; g < FC; ++g)
+      store_slab_frag<CIT>(wsb, acc[g][f], m0 + (wm * FC + g) * 32, ci0, (wn * FN + f) * 32 + l32, lane, Cin, Cout);
   }
 }
 
@@ -324,8 +317,8 @@ VG_KNOB(int, g_wgrad_blocks_target, -1);     // diagnostics only
 
 Plan make_plan(int B, int Cin, int H, int W, int Cout, int S) {
   Plan p;
-  p.OH = (H - 1) / S + 1;
-  p.OW = (W - 1) / S + 1;
+  p.OH = out_dim(H, S);
+  p.OW = out_dim(W, S);
   p.tw = p.OW <= 8 ? 8 : (p.OW <= 16 ? 16 : (p.OW <= 32 ? 32 : 64));
   p.tm = Cout > 64 ? 128 : (Cout > 32 ? 64 : 32);
   if (p.tm == 128 && Cout <= 128 && Cin <= 32) p.tm = 64;   // few column tiles: more row tiles instead
@@ -429,7 +422,7 @@ int vg_internal_wgrad_reducer(const float* slabs, const float* dw, int n, int sp
 // the plan vg_conv5x5_wgrad would launch with these pointers (only their alignment matters) under the current knobs
 extern "C" int vg_debug_wgrad_plan(int B, int Cin, int H, int W, int Cout, int stride, const void* gy, const void* dw,
                                    const void* workspace, int* out) {
-  if (!out || B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2)) return VG_ERR_BAD_ARG;
+  if (!out || !conv_shape_ok(B, Cin, H, W, Cout, stride)) return VG_ERR_BAD_ARG;
   const Plan p = make_plan(B, Cin, H, W, Cout, stride);
   out[0] = p.tw; out[1] = p.tm; out[2] = p.cit; out[3] = plan_ks(p); out[4] = p.splits; out[5] = plan_vec4(p, gy);
   out[6] = pick_reducer((const float*)workspace, (const float*)dw, Cout * Cin * 25, p.splits);
@@ -439,7 +432,7 @@ extern "C" int vg_debug_wgrad_plan(int B, int Cin, int H, int W, int Cout, int s
 #endif
 
 extern "C" size_t vg_conv5x5_wgrad_workspace_bytes(int B, int Cin, int H, int W, int Cout, int stride) {
-  if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2)) return 0;
+  if (!conv_shape_ok(B, Cin, H, W, Cout, stride)) return 0;
   const Plan p = make_plan(B, Cin, H, W, Cout, stride);
   return (size_t)p.splits * Cout * Cin * 25 * sizeof(float);
 }
@@ -447,17 +440,15 @@ extern "C" size_t vg_conv5x5_wgrad_workspace_bytes(int B, int Cin, int H, int W,
 extern "C" int vg_conv5x5_wgrad(const float* x, const float* gy, float* dw, int B, int Cin, int H, int W,
                                 int Cout, int stride, void* workspace, size_t workspace_bytes, int accumulate,
                                 void* stream) {
-  if (!x || !gy || !dw || B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return VG_ERR_BAD_ARG;
-  if (stride != 1 && stride != 2) return VG_ERR_BAD_ARG;
+  if (!x || !gy || !dw || !conv_shape_ok(B, Cin, H, W, Cout, stride)) return VG_ERR_BAD_ARG;
   const Plan p = make_plan(B, Cin, H, W, Cout, stride);
   const size_t need = (size_t)p.splits * Cout * Cin * 25 * sizeof(float);
   if (!workspace || workspace_bytes < need) return VG_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   WArgs A;
-  A.x = x; A.gy = gy; A.ws = (float*)workspace;
-  A.B = B; A.Cin = Cin; A.H = H; A.W = W; A.Cout = Cout; A.OH = p.OH; A.OW = p.OW;
-  A.mtiles = p.mtiles; A.ntiles = p.ntiles; A.splits = p.splits;
-  A.tiles_w = p.tiles_w; A.tiles_hw = p.tiles_hw; A.chunks = p.chunks; A.chunks_per_split = p.cps;
+  fill_wgrad_tiles(A, x, B, Cin, H, W, Cout, p);
+  A.gy = gy; A.ws = (float*)workspace;
+  A.splits = p.splits; A.chunks_per_split = p.cps;
   A.vec4 = plan_vec4(p, gy);
   const int ks = plan_ks(p);
   int rc = (stride == 2) ? dispatch_tw<2>(A, p.tw, p.tm, p.cit, ks, st) : dispatch_tw<1>(A, p.tw, p.tm, p.cit, ks, st);

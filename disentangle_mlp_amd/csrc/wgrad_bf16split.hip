@@ -20,28 +20,26 @@
 //     that column n lands on bank group n mod 16 (conflict-free ds_read_b128);
 //   * the gy operand goes global -> register (32 consecutive co = 512 contiguous bytes), prefetched
 //     one pixel ahead -- no LDS, no barrier for it;
-//   * split-K over chunks, partial slabs summed in a fixed order by conv_wgrad.hip's reduction.
+//   * split-K over chunks, partial slabs summed in a fixed order (wx_reduce_kernel below).
+// Shared with conv_wgrad.hip through conv_tile.hpp: the argument block's base, the chunk decode, the slab store; the plane
+// split, the product order and the affine on load are common.hpp's.
 #include <algorithm>
 #include <vector>
 
-#include "common.hpp"
-#include "vaegan_hip.h"
+#include "conv_tile.hpp"
 
 namespace {
 
 constexpr int WTW = 8, WCIT = 5;
 
-struct WXArgs {
-  const float* x;      // NCHW fp32 (the patch is split while it is staged)
-  int B;
+struct WXArgs : WgradTiles {      // x: NCHW fp32 (the patch is split while it is staged); chunks of 16 images
   // fused BatchNorm: x is read as act(x * in_scale[ci] + in_shift[ci]) (vg_conv_fusion semantics); NULL: as it is
   const float* in_scale;
   const float* in_shift;
   float in_slope;      // activation as max(v, 0) + slope * min(v, 0): 1 none, 0 ReLU, 0.2 LeakyReLU
   const bf16x8* gp;
   float* ws;
-  int Cin, H, W, Cout, CoP, OH, OW;
-  int mtiles, ntiles, tiles_w, tiles_hw, chunks;
+  int CoP;
   int units, upw;                 // units = output tiles x chunks; every workgroup works off upw consecutive ones
   unsigned short order[256];      // launch slot (blockIdx.x) -> workgroup index
   const float* x_amax;            // fp16 planes: x_amax[0] >= max |activated x| (device); the slab sum undoes the scales
@@ -78,11 +76,7 @@ __global__ __launch_bounds__(256) void relayout_gy_kernel(const float* __restric
       const bool ok = (bg * 16 + kb * 8 + j) < B && co < Co;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        float t = v[j][e];
-        if (g_scale) {
-          t = fmaf(t, sc, sh);
-          t = act_slope(t, g_slope);
-        }
+        const float t = g_scale ? affine_act(v[j][e], sc, sh, g_slope) : v[j][e];
         tile[j][tid >> 3][q4 + e] = ok ? t : 0.f;
       }
     }
@@ -97,10 +91,7 @@ __global__ __launch_bounds__(256) void relayout_gy_kernel(const float* __restric
         float v = 0.f;
         if (b < B && co < Co && p0 + pl < P) {
           v = gy[((size_t)b * Co + co) * P + p0 + pl];
-          if (g_scale) {
-            v = fmaf(v, g_scale[co], g_shift[co]);
-            v = act_slope(v, g_slope);
-          }
+          if (g_scale) v = affine_act(v, g_scale[co], g_shift[co], g_slope);
         }
         tile[j][r + 8 * rr][pl] = v;
       }
@@ -196,19 +187,12 @@ __global__ __launch_bounds__(W8NT, 2) void conv5x5_wgrad_split8_kernel(WXArgs A)
   }
   static_assert(PH <= 16 && PW <= 32 && WCIT <= 8, "descriptor fields");
 
-  // chunk -> (image group, output row, first output column)
-  auto chunk_pos = [&](int chunk, int& bg, int& oh, int& ow0) {
-    bg = chunk / A.tiles_hw;
-    const int sp = chunk % A.tiles_hw;
-    oh = (sp / A.tiles_w) * C::TH;
-    ow0 = (sp % A.tiles_w) * WTW;
-  };
   float preg[NQ][8], psc[NQ], psh[NQ];
   unsigned pvalid = 0;
   const size_t chw = (size_t)Cin * HW;
   auto load_patch = [&](int chunk) {
-    int bg, oh, ow0;
-    chunk_pos(chunk, bg, oh, ow0);
+    int bg, oh, ow0;      // image group, output row, first output column
+    chunk_pos<C::TH, WTW>(A, chunk, bg, oh, ow0);
     const int ih0 = S * oh - 2, iw0 = S * ow0 - 2;
     pvalid = 0;
 #pragma unroll
@@ -238,8 +222,7 @@ __global__ __launch_bounds__(W8NT, 2) void conv5x5_wgrad_split8_kernel(WXArgs A)
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      float t = fmaf(preg[q][j], psc[q], psh[q]);                    // the producing layer's BatchNorm ...
-      t = act_slope(t, A.in_slope);                                  // ... and activation, on load
+      float t = affine_act(preg[q][j], psc[q], psh[q], A.in_slope);  // the producing layer's BatchNorm and activation, on load
       t = F16 ? t * x_scale : t;
       v[j] = (live && (bgrp * 16 + kbs * 8 + j) < A.B) ? t : 0.f;    // padding pads the activated tensor
     }
@@ -298,7 +281,7 @@ __global__ __launch_bounds__(W8NT, 2) void conv5x5_wgrad_split8_kernel(WXArgs A)
     // first pixel (in Gp) of a chunk, clamped to the last chunk of the segment (prefetches past the end are unused)
     auto chunk_pix = [&](int chunk) -> size_t {
       int bg, oh, ow0;
-      chunk_pos(min(chunk, c_end - 1), bg, oh, ow0);
+      chunk_pos<C::TH, WTW>(A, min(chunk, c_end - 1), bg, oh, ow0);
       return (size_t)bg * P + (size_t)oh * OW + ow0;
     };
     bf16x8 av[PD + 1][NP];      // gy fragments of pixels t .. t+PD, ring indexed by (pixel & PD) (PD + 1 = 4 or 8 sets)
@@ -348,12 +331,10 @@ __global__ __launch_bounds__(W8NT, 2) void conv5x5_wgrad_split8_kernel(WXArgs A)
             bv[f][pl] = __builtin_bit_cast(
                 bf16x8, lds[buf * BUFU + base_b[f] + S * (t >> 3) * ROWU + S * (t & 7) + pl * 2 * KBU]);
         // products with plane index sum < NP, smallest terms first, product-major
+        for_plane_products<NP>([&](auto pa, auto pb) {
 #pragma unroll
-        for (int sum = NP - 1; sum >= 0; --sum)
-#pragma unroll
-          for (int pa = sum; pa >= 0; --pa)
-#pragma unroll
-            for (int f = 0; f < FP; ++f) acc[f] = mfma_split16<F16>(av[t & PD][pa], bv[f][sum - pa], acc[f]);
+          for (int f = 0; f < FP; ++f) acc[f] = mfma_split16<F16>(av[t & PD][pa.value], bv[f][pb.value], acc[f]);
+        });
         // one unit of the next patch per slot of the store schedule (the other buffer was last read a chunk ago).
         // (A branch-free form of this loop -- clamped re-loads instead of `more`, no wavefront groups, dump units for
         // unit-less lanes: three basic blocks per chunk instead of ~40 -- measured 3-20 % SLOWER: hipcc clusters the
@@ -374,15 +355,8 @@ __global__ __launch_bounds__(W8NT, 2) void conv5x5_wgrad_split8_kernel(WXArgs A)
     const int piece = wg - (int)(((long)tile * A.chunks) / A.upw);
     float* wsb = A.ws + (size_t)piece * Cout * Cin * 25;
 #pragma unroll
-    for (int f = 0; f < FP; ++f) {
-      const int n = (wn * FP + f) * 32 + l32;
-      const bool nok = n < WCIT * 25 && (ci0 + n / 25) < Cin;
-#pragma unroll
-      for (int r16 = 0; r16 < 16; ++r16) {
-        const int co = m0 + wm * 32 + acc_row(r16, lane);
-        if (nok && co < Cout) wsb[((size_t)co * Cin + ci0) * 25 + n] = acc[f][r16];
-      }
-    }
+    for (int f = 0; f < FP; ++f)
+      store_slab_frag<WCIT>(wsb, acc[f], m0 + wm * 32, ci0, (wn * FP + f) * 32 + l32, lane, Cin, Cout);
   }
 }
 
@@ -433,8 +407,8 @@ void plan_shares(XPlan& p, int th) {
 }
 
 bool make_xplan(int B, int Cin, int H, int W, int Cout, int S, int planes, XPlan& p) {
-  p.OH = (H - 1) / S + 1;
-  p.OW = (W - 1) / S + 1;
+  p.OH = out_dim(H, S);
+  p.OW = out_dim(W, S);
   if (p.OW % WTW) return false;                         // whole 1 x 8 pixel tiles only (caller falls back to fp32)
   p.BG = cdiv(B, 16);
   p.CoP = (Cout + 127) & ~127;
@@ -495,7 +469,7 @@ void vg_internal_wx_set_th(int th) { g_wx_th = (th == 1 || th == 2) ? th : 0; }
 
 // the plan vg_conv5x5_wgrad_bf16split would launch under the current knobs (VG_ERR_BAD_ARG: shape not taken)
 extern "C" int vg_debug_wgrad_split_plan(int B, int Cin, int H, int W, int Cout, int stride, int planes, int* out) {
-  if (!out || B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2)) return VG_ERR_BAD_ARG;
+  if (!out || !conv_shape_ok(B, Cin, H, W, Cout, stride)) return VG_ERR_BAD_ARG;
   XPlan p;
   if (!make_xplan(B, Cin, H, W, Cout, stride, planes & 0xff, p)) return VG_ERR_BAD_ARG;
   out[0] = p.th; out[1] = p.wco; out[2] = p.mtiles; out[3] = p.ntiles; out[4] = p.units; out[5] = p.upw; out[6] = p.wgs;
@@ -506,8 +480,7 @@ extern "C" int vg_debug_wgrad_split_plan(int B, int Cin, int H, int W, int Cout,
 
 extern "C" size_t vg_conv5x5_wgrad_bf16split_workspace_bytes(int B, int Cin, int H, int W, int Cout, int stride,
                                                           int planes) {
-  if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2)) return 0;
-  if (planes != 2 && planes != 3 && planes != (VG_PLANES_F16_FLAG | 2)) return 0;
+  if (!conv_shape_ok(B, Cin, H, W, Cout, stride) || !planes_ok(planes)) return 0;
   XPlan p;
   if (!make_xplan(B, Cin, H, W, Cout, stride, planes & 0xff, p)) return 0;     // 0: shape not supported by this mode
   return p.gp_bytes + p.slab_bytes;
@@ -517,17 +490,16 @@ extern "C" int vg_conv5x5_wgrad_bf16split(const float* x, const float* gy, float
                                        int Cout, int stride, int planes, void* workspace, size_t workspace_bytes,
                                        const float* in_scale, const float* in_shift, int in_act, int affine_on_gy,
                                        const float* x_amax, const float* gy_amax, int accumulate, void* stream) {
-  if (!x || !gy || !dw || B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return VG_ERR_BAD_ARG;
+  if (!x || !gy || !dw || !conv_shape_ok(B, Cin, H, W, Cout, stride)) return VG_ERR_BAD_ARG;
   const bool f16 = (planes & VG_PLANES_F16_FLAG) != 0;
   planes &= 0xff;
   if (f16 && (planes != 2 || !x_amax || !gy_amax)) return VG_ERR_BAD_ARG;
   if (!f16) x_amax = gy_amax = nullptr;
-  if ((in_scale == nullptr) != (in_shift == nullptr) || in_act < VG_ACT_NONE || in_act > VG_ACT_LRELU) return VG_ERR_BAD_ARG;
-  const float slope = (!in_scale || in_act == VG_ACT_NONE) ? 1.f : (in_act == VG_ACT_RELU ? 0.f : 0.2f);
+  const float slope = affine_on_load_slope(in_scale, in_shift, in_act);
+  if (slope < 0.f || (planes != 2 && planes != 3)) return VG_ERR_BAD_ARG;
   const float* gsc = affine_on_gy ? in_scale : nullptr;      // coefficients per channel of gy (Cout of them) ...
   const float* gsh = affine_on_gy ? in_shift : nullptr;
   if (affine_on_gy) in_scale = in_shift = nullptr;           // ... or per channel of x (Cin)
-  if ((stride != 1 && stride != 2) || (planes != 2 && planes != 3)) return VG_ERR_BAD_ARG;
   XPlan p;
   if (!make_xplan(B, Cin, H, W, Cout, stride, planes, p)) return VG_ERR_BAD_ARG;
   if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < p.gp_bytes + p.slab_bytes)
@@ -543,12 +515,11 @@ extern "C" int vg_conv5x5_wgrad_bf16split(const float* x, const float* gy, float
   else hipLaunchKernelGGL((relayout_gy_kernel<3, false>), gg, dim3(256), 0, st, gy, gp, B, Cout, p.CoP, P, gsc, gsh, slope, gy_amax);
   VG_CHECK_LAUNCH();
   WXArgs A;
-  A.x = x; A.B = B; A.gp = gp; A.ws = slabs; A.x_amax = x_amax;
+  fill_wgrad_tiles(A, x, B, Cin, H, W, Cout, p);
+  A.gp = gp; A.ws = slabs; A.x_amax = x_amax;
   A.in_scale = in_scale; A.in_shift = in_shift;
   A.in_slope = in_scale ? slope : 1.f;
-  A.Cin = Cin; A.H = H; A.W = W; A.Cout = Cout; A.CoP = p.CoP; A.OH = p.OH; A.OW = p.OW;
-  A.mtiles = p.mtiles; A.ntiles = p.ntiles; A.tiles_w = p.tiles_w; A.tiles_hw = p.tiles_hw;
-  A.chunks = p.chunks; A.units = p.units; A.upw = p.upw;
+  A.CoP = p.CoP; A.units = p.units; A.upw = p.upw;
   make_order(p, A.order);
   const long grid = p.wgs;
   int rc;

@@ -114,6 +114,11 @@ SIGNATURES = {
     "vg_reparam_mmd_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _F, _F, _P, _P, _I, _I, _P, _Z, _P]),
     "vg_reparam_mmd_fwd_dev": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _F, _P, _I, _P, _Z, _P]),
     "vg_reparam_mmd_bwd_dev": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _I, _I, _P, _Z, _P]),
+    "vg_reparam_klc_workspace_bytes": (_Z, [_I, _I]),
+    "vg_reparam_klc_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _F, _P, _Z, _P]),
+    "vg_reparam_klc_bwd": (_I, [_P, _P, _P, _P, _P, _P, _F, _F, _F, _P, _P, _I, _I, _P, _Z, _P]),
+    "vg_reparam_klc_fwd_dev": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _F, _P, _Z, _P]),
+    "vg_reparam_klc_bwd_dev": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _I, _I, _P, _Z, _P]),
     "vg_agg_posterior_splits": (_I, [_I, _I, _I, _I]),
     "vg_agg_posterior_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "vg_agg_posterior_lse": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),

@@ -1,9 +1,9 @@
 // What the reparameterisation kernels fused with an objective of the KL phase -- reparam_tc.hip, reparam_dip.hip,
-// reparam_mmd.hip -- have in common to the letter: DESIGN.md section 4.24.  Only that: a kernel whose inner loop differs
-// between two of them (chain lengths, staging layout) stays in its file, and nothing here asks who calls it.  All three
-// files use MAX_DIM, the per-element expressions and the gz-only backward; the strip / tile geometry, the tile decode and
-// the slot sums belong to reparam_dip.hip and reparam_mmd.hip alone.  Everything has internal linkage: each file compiles
-// its own copy.
+// reparam_mmd.hip, reparam_klc.hip -- have in common to the letter: DESIGN.md section 4.24.  Only that: a kernel whose
+// inner loop differs between two of them (chain lengths, staging layout) stays in its file, and nothing here asks who
+// calls it.  All four files use MAX_DIM, the per-element expressions and the gz-only backward; the tile geometry, the
+// tile decode and the slot sums belong to reparam_dip.hip and reparam_mmd.hip alone (reparam_klc.hip takes the strip's
+// width and the workgroup size from it).  Everything has internal linkage: each file compiles its own copy.
 #pragma once
 #include "common.hpp"
 

@@ -554,24 +554,25 @@ class ReparamKLFn(Function):
 
 
 class _ReparamObjectiveFn(Function):
-    """What `ReparamTCFn`, `ReparamDIPFn` and `ReparamMMDFn` share: the end of the forward (`_finish`) and the whole
-    backward.  A subclass's ``forward`` calls its `ops` forward and hands `_finish` what the backward needs:
+    """What `ReparamTCFn`, `ReparamDIPFn`, `ReparamMMDFn` and `ReparamKLCFn` share: the end of the forward (`_finish`) and
+    the whole backward.  A subclass's ``forward`` calls its `ops` forward and hands `_finish` what the backward needs:
     ``ops.<bwd>(gz, *saved, gloss, beta, *kept)``.  ``beta``: a float or the device word, as `ReparamKLFn` (a tensor is kept
     as the word itself, not saved: it takes no gradient)."""
 
     @staticmethod
-    def _finish(ctx, z, out4, bwd, saved, beta, kept, nargs):
-        """``bwd``: the name of the backward in `ops` (looked up when it runs); ``nargs``: how many arguments the forward took."""
+    def _finish(ctx, z, out4, bwd, saved, beta, kept, nargs, extra=()):
+        """``bwd``: the name of the backward in `ops` (looked up when it runs); ``nargs``: how many arguments the forward took;
+        ``extra``: further outputs behind ``parts`` that take no gradient either."""
         ctx.bwd, ctx.beta, ctx.kept, ctx.nargs = bwd, beta, kept, nargs
         loss, parts = out4[0], out4[1:]
-        ctx.mark_non_differentiable(parts)
+        ctx.mark_non_differentiable(parts, *extra)
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(*saved)
-        return z, loss, parts
+        return (z, loss, parts, *extra)
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, gz, gloss, _):
+    def backward(ctx, gz, gloss, *_):
         if gz is None and gloss is None:
             return (None,) * ctx.nargs
         gz = gz.contiguous() if gz is not None else None
@@ -620,6 +621,21 @@ class ReparamMMDFn(_ReparamObjectiveFn):
         z, out4, w = ops.reparam_mmd_fwd(mu, logvar, eps, zp, beta, lambda_mmd, kind, bandwidths)
         return ReparamMMDFn._finish(ctx, z, out4, "reparam_mmd_bwd", (mu, logvar, eps, z, zp, w), beta,
                                     (lambda_mmd, kind, bandwidths), 8)
+
+
+class ReparamKLCFn(_ReparamObjectiveFn):
+    """z = mu + eps*exp(logvar/2) and the controlled KL term (Burgess et al. 2018 over Kingma et al. 2016's free bits;
+    DESIGN.md section 4.30): ``loss = beta*|T - B*capacity|`` with ``T = sum_d max(K[d], B*free_bits)``, ``K[d]`` the
+    dimension's KL summed over the batch, in two launches forward and one backward.  Returns ``z``, ``loss``, the
+    non-differentiable ``[3]`` tensor ``(kl, kl_floored, dims_above)`` and the non-differentiable ``[D]`` tensor ``kl_dim`` =
+    K / B.  ``beta`` and ``capacity``: both floats or both device words (kept as the words themselves, as `ReparamKLFn`'s
+    beta); ``free_bits``: a float."""
+
+    @staticmethod
+    def forward(ctx, mu, logvar, eps, beta, capacity, free_bits):
+        z, out4, gate, kl_dim = ops.reparam_klc_fwd(mu, logvar, eps, beta, capacity, free_bits)
+        return ReparamKLCFn._finish(ctx, z, out4, "reparam_klc_bwd", (mu, logvar, eps, gate), beta, (capacity, free_bits), 6,
+                                    extra=(kl_dim,))
 
 
 class KLRowsFn(Function):
@@ -803,6 +819,19 @@ def reparam_mmd(mu, logvar, eps, zp, beta, lambda_mmd, kernel="imq", bandwidths=
     kind = ops.mmd_kernel(kernel)
     return ReparamMMDFn.apply(mu, logvar, eps, zp, _beta_arg(beta), float(lambda_mmd), kind,
                               ops.mmd_bandwidths(kind, mu.shape[-1], bandwidths))
+
+
+def reparam_klc_dims(mu, logvar, eps, beta, capacity=0.0, free_bits=0.0):
+    """`ReparamKLCFn`: ``(z, loss, parts, kl_dim)`` with ``loss = beta*|kl_floored - B*capacity|``, ``parts = (kl, kl_floored,
+    dims_above)`` and ``kl_dim`` the [D] per-dimension KL averaged over the batch (which dimensions are active, which
+    collapsed).  ``capacity``: nats per sample, a float -- or, with ``beta`` a device word, a device word too;
+    ``free_bits``: nats per dimension per sample, a float."""
+    return ReparamKLCFn.apply(mu, logvar, eps, _beta_arg(beta), _beta_arg(capacity), ops.kl_free_bits(free_bits))
+
+
+def reparam_klc(mu, logvar, eps, beta, capacity=0.0, free_bits=0.0):
+    """`reparam_klc_dims` without ``kl_dim``: ``(z, loss, parts)``, as the other objectives."""
+    return reparam_klc_dims(mu, logvar, eps, beta, capacity, free_bits)[:3]
 
 
 def kld_loss(mu, logvar, beta):

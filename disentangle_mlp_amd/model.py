@@ -559,7 +559,7 @@ class VAE(nn.Module, _DecoderMixin):
         return self.decode(z), mu, logvar, kl
 
     def _forward_with_objective(self, x, eps, reparam):
-        """The body of `forward_with_tc` / `_dip` / `_mmd`: encode, draw ``eps`` if None, ``reparam(mu, logvar, eps) -> z,
+        """The body of `forward_with_tc` / `_dip` / `_mmd` / `_klc`: encode, draw ``eps`` if None, ``reparam(mu, logvar, eps) -> z,
         loss, parts``, decode.  Returns ``recon, mu, logvar, loss, parts``."""
         mu, logvar = self.encode(x)
         if eps is None:
@@ -588,3 +588,10 @@ class VAE(nn.Module, _DecoderMixin):
             zp = torch.randn_like(mu) if prior is None else prior
             return F.reparam_mmd(mu, logvar, eps, zp, beta, lambda_mmd, kernel, bandwidths)
         return self._forward_with_objective(x, eps, reparam)
+
+    def forward_with_klc(self, x, eps, beta, capacity, free_bits):
+        """`forward_with_kl` with the KL term under a capacity and per-dimension free bits (functional.reparam_klc): returns
+        ``recon, mu, logvar, loss, parts`` -- ``loss = beta*|kl_floored - B*capacity|``, ``parts`` the ``[3]`` tensor ``(kl,
+        kl_floored, dims_above)``.  ``beta`` / ``capacity``: both floats or both one-element fp32 device tensors."""
+        return self._forward_with_objective(
+            x, eps, lambda mu, logvar, eps: F.reparam_klc(mu, logvar, eps, beta, capacity, free_bits))

@@ -1077,18 +1077,34 @@ def reparam_kl_bwd(gz, mu, logvar, eps, gkl, beta):
     return gmu, glv
 
 
-def _objective_launch(workspace_bytes, fn, fn_dev, mu, head, beta, tail):
-    """The one call site of the KL-phase objectives' entry points (beta-TCVAE, DIP-VAE, InfoVAE / WAE-MMD; DESIGN.md section
-    4.24): ``fn(*head, beta, *tail, workspace, bytes, stream)`` -- or, ``beta`` given as a tensor, ``fn_dev`` with the word's
-    address in that place.  ``workspace_bytes``, ``fn``, ``fn_dev``: the objective's three entries of the library; ``mu``
-    gives B, D and the device."""
+def _objective_launch(workspace_bytes, fn, fn_dev, mu, head, beta, tail, second=None):
+    """The one call site of the KL-phase objectives' entry points (beta-TCVAE, DIP-VAE, InfoVAE / WAE-MMD, KL capacity;
+    DESIGN.md section 4.24): ``fn(*head, beta, *tail, workspace, bytes, stream)`` -- or, ``beta`` given as a tensor,
+    ``fn_dev`` with the word's address in that place.  ``workspace_bytes``, ``fn``, ``fn_dev``: the objective's three entries
+    of the library; ``mu`` gives B, D and the device.  ``second``: ``(name, value)`` of an objective's OWN scheduled word,
+    the argument right behind beta -- a float with a float beta, a one-element fp32 device tensor with beta's word (the
+    ``_dev`` entry reads both); a mix is a TypeError.  An objective without one passes nothing and pays nothing."""
     B, D = mu.shape
     ws = workspace(workspace_bytes(B, D), mu.device)
     if isinstance(beta, torch.Tensor):
         fn, beta = fn_dev, _beta_word(beta).data_ptr()
     else:
         beta = float(beta)
+    if second is not None:
+        tail = (_second_word(*second, fn is fn_dev), *tail)
     check(fn(*head, beta, *tail, ws.data_ptr(), ws.numel(), _stream()), fn.__name__)
+
+
+def _second_word(name, value, dev):
+    """`_objective_launch`'s ``second`` as the C argument: the word's address (``dev``) or the float."""
+    if isinstance(value, torch.Tensor) != dev:
+        raise TypeError(f"beta and {name} must both be floats or both be one-element fp32 device tensors "
+                        f"(beta is a {'tensor' if dev else 'float'}, {name} is not)")
+    if not dev:
+        return float(value)
+    if value.numel() != 1 or value.dtype != torch.float32 or not value.is_cuda:
+        raise RuntimeError(f"{name} as a tensor must be one fp32 element on the GPU")
+    return value.data_ptr()
 
 
 def reparam_tc_fwd(mu, logvar, eps, beta, alpha, gamma, log_bn):
@@ -1390,6 +1406,57 @@ def reparam_mmd_bwd(gz, mu, logvar, eps, z, zp, w, gloss, beta, lambda_mmd, kind
     head = (_ptr(gz), mu.data_ptr(), logvar.data_ptr(), eps.data_ptr(), z.data_ptr(), zp.data_ptr(), w.data_ptr(), _ptr(gloss))
     _objective_launch(lib.vg_reparam_mmd_workspace_bytes, lib.vg_reparam_mmd_bwd, lib.vg_reparam_mmd_bwd_dev, mu, head, beta,
                       (float(lambda_mmd), gmu.data_ptr(), glv.data_ptr(), B, D))
+    return gmu, glv
+
+
+def kl_free_bits(free_bits):
+    """The per-dimension floor as the C ABI's float: finite and >= 0."""
+    v = float(free_bits)
+    if not (math.isfinite(v) and v >= 0.0):
+        raise ValueError(f"free_bits must be finite and >= 0, got {free_bits!r}")
+    return v
+
+
+def reparam_klc_fwd(mu, logvar, eps, beta, capacity, free_bits):
+    """Reparameterisation + the controlled KL term (vg_reparam_klc_fwd): ``loss = beta * |T - B *
+    capacity|`` with ``T`` the sum over the dimensions of ``max(K[d], B * free_bits)``, ``K[d]`` the dimension's KL summed over
+    the batch.  ``beta`` and ``capacity`` (nats per sample, >= 0): both floats, or both one-element fp32 device words read by
+    the kernel; ``free_bits``: a float, nats per dimension per sample.  Returns ``z``, ``out4`` = [loss, kl, T, dims above the
+    floor], ``gate`` [D] (what the backward reads: sgn(T - B capacity) where a dimension is above its floor, else 0) and
+    ``kl_dim`` [D] = K / B."""
+    lib = _lib.load()
+    _req(mu, "mu"), _req(logvar, "logvar"), _req(eps, "eps")
+    if mu.dim() != 2 or logvar.shape != mu.shape or eps.shape != mu.shape:
+        raise RuntimeError("reparam_klc: mu, logvar and eps must be [B, D] tensors of one shape")
+    B, D = mu.shape
+    z = torch.empty_like(mu)
+    out4 = torch.empty(4, dtype=torch.float32, device=mu.device)
+    gate = torch.empty(D, dtype=torch.float32, device=mu.device)
+    kl_dim = torch.empty(D, dtype=torch.float32, device=mu.device)
+    head = (mu.data_ptr(), logvar.data_ptr(), eps.data_ptr(), z.data_ptr(), out4.data_ptr(), gate.data_ptr(), kl_dim.data_ptr(),
+            B, D)
+    _objective_launch(lib.vg_reparam_klc_workspace_bytes, lib.vg_reparam_klc_fwd, lib.vg_reparam_klc_fwd_dev, mu, head, beta,
+                      (kl_free_bits(free_bits),), second=("capacity", capacity))
+    return z, out4, gate, kl_dim
+
+
+def reparam_klc_bwd(gz, mu, logvar, eps, gate, gloss, beta, capacity, free_bits):
+    """gz: tensor or None; gloss: 0-dim device tensor (upstream gradient of the weighted loss) or None.  The sign and the
+    floor are already in ``gate``: ``capacity`` / ``free_bits`` are taken for symmetry with the forward and only checked."""
+    lib = _lib.load()
+    for t, name in ((mu, "mu"), (logvar, "logvar"), (eps, "eps"), (gate, "gate")):
+        _req(t, name)
+    if gz is not None:
+        _req(gz, "gz")
+    if gloss is not None:
+        _req(gloss, "gloss")
+    B, D = mu.shape
+    if gate.shape != (D,):
+        raise RuntimeError("reparam_klc_bwd: gate must be the [D] tensor of reparam_klc_fwd")
+    gmu, glv = torch.empty_like(mu), torch.empty_like(mu)
+    head = (_ptr(gz), mu.data_ptr(), logvar.data_ptr(), eps.data_ptr(), gate.data_ptr(), _ptr(gloss))
+    _objective_launch(lib.vg_reparam_klc_workspace_bytes, lib.vg_reparam_klc_bwd, lib.vg_reparam_klc_bwd_dev, mu, head, beta,
+                      (kl_free_bits(free_bits), gmu.data_ptr(), glv.data_ptr(), B, D), second=("capacity", capacity))
     return gmu, glv
 
 

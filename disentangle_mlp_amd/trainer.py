@@ -347,6 +347,20 @@ def ema_warmup(decay, start_iteration=0):
     return schedule
 
 
+def linear_capacity(c_max, iterations, c_start=0.0):
+    """A per-iteration KL capacity for the trainers' ``kl_control=``: from ``c_start`` at iteration 0 linearly up to ``c_max``
+    at ``iterations``, and ``c_max`` from there on (Burgess et al. 2018: C from 0 to 25 nats over 100000 iterations)."""
+    c_max, c_start, n = float(c_max), float(c_start), int(iterations)
+    if not (np.isfinite(c_max) and np.isfinite(c_start) and c_max >= 0.0 and c_start >= 0.0):      # (NaN fails the comparisons)
+        raise ValueError(f"linear_capacity: c_max and c_start must be finite and >= 0, got {c_max!r} and {c_start!r}")
+    if n < 1 or n != iterations:
+        raise ValueError(f"linear_capacity: iterations must be an integer >= 1, got {iterations!r}")
+
+    def schedule(iteration):
+        return c_start + (c_max - c_start) * min(max(int(iteration), 0) / n, 1.0)
+    return schedule
+
+
 GRAPH_DEFAULT = os.environ.get("VG_GRAPH", "1") != "0"     # 0: trainers never capture (every step eager)
 GRAPH_WARM_STEPS = 2      # eager iterations of a shape before it is captured (workspaces, packs, GEMM plans exist then)
 
@@ -483,6 +497,9 @@ class _Objective(NamedTuple):
     parts: tuple              # the loss keys of parts[0..2]
     latents: tuple = ()       # latents the iteration draws on top of the trainer's own, last in draw order
     needs_dataset_size: bool = False      # `dataset_size` joins the arguments: required before a step, filled from a loader
+    word: Optional[str] = None            # its OWN scheduled value: the name it goes by.  `parse` returns it FIRST (a float, or a
+    #                                       callable iteration -> float); it is no frozen argument -- `forward` gets it first among
+    #                                       ``args`` as a float, or under ``device_hyper`` as a device word beside beta's
 
 
 def _parse_tc(tc_decomposition, opt):
@@ -530,6 +547,29 @@ def _parse_mmd(mmd_vae, opt):
     return kernel, lambda_mmd, bandwidths
 
 
+def _nonneg(name, value):
+    """``value`` as a finite float >= 0 (TypeError: no number; ValueError: negative, inf or NaN)."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise TypeError(f"{name} must be a number, got {value!r}") from None
+    if not (np.isfinite(v) and v >= 0.0):
+        raise ValueError(f"{name} must be finite and >= 0, got {value!r}")
+    return v
+
+
+def _parse_klc(kl_control, opt):
+    """``kl_control=(capacity, free_bits)``: nats per sample -- a float or a callable iteration -> float --, and the floor in
+    nats per dimension per sample."""
+    try:
+        capacity, free_bits = kl_control
+    except (TypeError, ValueError):
+        raise TypeError(f"kl_control must be a pair (capacity, free_bits), got {kl_control!r}") from None
+    if not callable(capacity):
+        capacity = _nonneg("kl_control: capacity", capacity)
+    return capacity, _nonneg("kl_control: free_bits", free_bits)
+
+
 # The table: the methods are looked up on the network when called (a test may replace one).
 _OBJECTIVES = (
     _Objective("tc_decomposition", _parse_tc,       # args: (alpha, gamma, dataset_size); `beta` weighs the total correlation
@@ -541,6 +581,9 @@ _OBJECTIVES = (
     _Objective("mmd_vae", _parse_mmd,               # args: (kernel, lambda_mmd, bandwidths); the MMD is between z and `prior`
                lambda net, data, eps, beta, args, prior: net.forward_with_mmd(data, eps, prior, beta, *args),
                ("kl", "mmd", "mmd_kzz"), latents=("prior",)),
+    _Objective("kl_control", _parse_klc,            # args: (capacity: its word, free_bits); `beta` weighs |kl_floored - B capacity|
+               lambda net, data, eps, beta, args, prior: net.forward_with_klc(data, eps, beta, *args),
+               ("kl", "kl_floored", "dims_above"), word="capacity"),
 )
 
 
@@ -565,7 +608,7 @@ class _GraphedSteps:
 
     def _setup(self, device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
                beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition, dataset_size,
-               data_parallel=None, capturable=None, dip_vae=None, mmd_vae=None):
+               data_parallel=None, capturable=None, dip_vae=None, mmd_vae=None, kl_control=None):
         """The constructor body of every trainer (new_betavaegan.py:36-53, new_vae.py:33-37, new_gan.py:47-61).  A trainer
         with a KL term has set `beta` before."""
         has_beta = hasattr(self, "beta")
@@ -574,7 +617,8 @@ class _GraphedSteps:
         self._single_use = {}     # (id(network), DEFER_WGRAD) -> its weights that may be updated inside the backward
         on_gpu = self.device.type == "cuda"
         _use_tuned_gemms(self.device)
-        self._select_objective(dict(tc_decomposition=tc_decomposition, dip_vae=dip_vae, mmd_vae=mmd_vae), dataset_size, has_beta)
+        self._select_objective(dict(tc_decomposition=tc_decomposition, dip_vae=dip_vae, mmd_vae=mmd_vae, kl_control=kl_control),
+                               dataset_size, has_beta)
         self.max_grad_norm, self.skip_nonfinite = max_grad_norm, bool(skip_nonfinite)
         self._skipped = {}
         self.world, self.rank = _dist_world(), _dist_rank()
@@ -762,8 +806,9 @@ class _GraphedSteps:
 
     def _schedule_args(self, lr_scheduler, beta_schedule, device_hyper, weight_decay, decoupled_weight_decay, capturable,
                        has_beta=True):
-        """Validate the schedule arguments and resolve ``device_hyper`` (None: on exactly when a scheduler or a beta schedule
-        is given -- and the optimizers can carry it: HipAdam with device scalars; without, the schedules still run and the
+        """Validate the schedule arguments and resolve ``device_hyper`` (None: on exactly when a scheduler, a beta schedule or
+        a schedule of the objective's own word is given -- and the optimizers can carry it: HipAdam with device scalars;
+        without, the schedules still run and the
         steps stay eager or re-key as before).  Returns the keyword arguments of `_make_adam`."""
         if beta_schedule is not None and not has_beta:
             raise TypeError(f"{type(self).__name__} has no KL term: beta_schedule does not apply")
@@ -776,7 +821,8 @@ class _GraphedSteps:
         self.weight_decay, self.decoupled_weight_decay = wd, bool(decoupled_weight_decay)
         self._lr_scheduler_factory, self.beta_schedule = lr_scheduler, beta_schedule
         if device_hyper is None:
-            self.device_hyper = (lr_scheduler is not None or beta_schedule is not None) and bool(capturable)
+            self.device_hyper = ((lr_scheduler is not None or beta_schedule is not None or self._word_schedule is not None)
+                                 and bool(capturable))
         else:
             self.device_hyper = bool(device_hyper)
             if self.device_hyper and not capturable:
@@ -785,6 +831,9 @@ class _GraphedSteps:
         if self.device_hyper and has_beta:
             self._beta_dev = torch.full((1,), self.beta, dtype=torch.float32, device=self.device)
             self._beta_written = self.beta
+            if self._word is not None:      # the objective's own word lives beside beta's: both floats or both words
+                self._word_dev = torch.full((1,), self._word, dtype=torch.float32, device=self.device)
+                self._word_written = self._word
         return dict(weight_decay=wd, decoupled_weight_decay=self.decoupled_weight_decay, device_hyper=self.device_hyper)
 
     def _make_schedulers(self):
@@ -806,6 +855,10 @@ class _GraphedSteps:
     tc_decomposition = _objective_args("tc_decomposition")
     dip_vae = _objective_args("dip_vae")
     mmd_vae = _objective_args("mmd_vae")
+    _word = None              # the current value of the selected objective's own scheduled word (`_Objective.word`), a float
+    _word_schedule = None     # callable iteration -> that value, or None (a constant, or set by hand)
+    _word_dev = None          # with device_hyper: the persistent fp32 word the objective's kernels read
+    _word_written = None
 
     def _select_objective(self, given, dataset_size, has_beta=True):
         """A trainer's constructor: ``given`` maps every keyword of the table to its value; at most one is not None.  The
@@ -822,7 +875,13 @@ class _GraphedSteps:
                     every = [e.keyword for e in reversed(_OBJECTIVES)]
                     raise ValueError(f"{', '.join(every[:-1])} and {every[-1]} each replace the KL term of the encoder phase: "
                                      f"pass one of them (got {o.keyword} and {self._objective[0].keyword})")
-                self._objective = (o, o.parse(value, self.opt))
+                args = o.parse(value, self.opt)
+                if o.word is not None:
+                    word, *args = args
+                    self._word_schedule = word if callable(word) else None
+                self._objective = (o, tuple(args))
+                if o.word is not None:
+                    self._word = self._word_checked(word(0)) if callable(word) else word
                 self._latents = (*type(self)._latents, *o.latents)
             if with_size:
                 if int(dataset_size) != dataset_size or int(dataset_size) < 1:
@@ -849,7 +908,10 @@ class _GraphedSteps:
         (``parts`` is None), or the selected objective's loss and its three parts."""
         if self._objective is None:
             return (*net.forward_with_kl(data, eps, self._kl_beta()), None)
-        return self._objective[0].forward(net, data, eps, self._kl_beta(), self._objective_key()[1], prior)
+        args = self._objective_key()[1]
+        if self._word is not None:
+            args = (self._word_dev if self._word_dev is not None else self._word, *args)
+        return self._objective[0].forward(net, data, eps, self._kl_beta(), args, prior)
 
     def _with_prior(self, given, prior):
         """`step`'s latents in `_latents` order: behind the trainer's own, the prior's draw (or None: drawn) of an objective
@@ -878,6 +940,33 @@ class _GraphedSteps:
             self._beta_dev.fill_(self.beta)
             self._beta_written = self.beta
 
+    def _word_checked(self, value):
+        """A value of the objective's own word (a schedule's, or set by hand) as a finite float >= 0."""
+        return _nonneg(f"{self._objective[0].keyword}: {self._objective[0].word}", value)
+
+    def _sync_word(self):
+        """The objective's own value into its device word, as `_sync_beta` (a device fill, never inside a capture)."""
+        if self._word_dev is not None and self._word != self._word_written:
+            self._word_dev.fill_(self._word)
+            self._word_written = self._word
+
+    @property
+    def capacity(self):
+        """The KL capacity of ``kl_control`` this step runs (ran) with, in nats per sample; None without the option."""
+        return self._word if self._objective and self._objective[0].word == "capacity" else None
+
+    def set_capacity(self, value):
+        """Set the KL capacity by hand (a schedule, if any, overwrites it at the start of the next step).  With
+        ``device_hyper`` the next step picks it up without a new capture."""
+        if self.capacity is None:
+            raise TypeError(f"{type(self).__name__}: construct with kl_control=... to have a KL capacity")
+        self._word = self._word_checked(value)
+
+    @property
+    def kl_control(self):
+        """``(capacity, free_bits)`` as they are now (read-only); None when the option is off."""
+        return None if self.capacity is None else (self._word, *self._objective[1])
+
     def _begin_step(self):
         if self._dataset_size_missing():
             raise ValueError(f"{type(self).__name__}: {self._objective[0].keyword} needs dataset_size (the number of training "
@@ -885,6 +974,9 @@ class _GraphedSteps:
         if self.beta_schedule is not None:
             self.beta = float(self.beta_schedule(self.iteration))
         self._sync_beta()
+        if self._word_schedule is not None:
+            self._word = self._word_checked(self._word_schedule(self.iteration))
+        self._sync_word()
         if self.ema_schedule is not None:      # the decay word follows in front of the launches (`HipAdam.sync_hyper`)
             self._ema_pair()[1].set_ema_decay(float(self.ema_schedule(self.iteration)))
 
@@ -915,7 +1007,8 @@ class _GraphedSteps:
         extra = {}
         if self.lr_schedulers:
             extra["lr_schedulers"] = {n: s.state_dict() for n, s in self.lr_schedulers.items()}
-        if self.lr_schedulers or self.beta_schedule is not None or self.ema_schedule is not None:
+        if (self.lr_schedulers or self.beta_schedule is not None or self.ema_schedule is not None
+                or self._word_schedule is not None):
             extra["iteration"] = self.iteration
         return extra
 
@@ -934,6 +1027,8 @@ class _GraphedSteps:
                     group["lr"] = saved["lr"]
         if self.beta_schedule is not None and "iteration" in ck:
             self.beta = float(self.beta_schedule(max(self.iteration - 1, 0)))      # (the last step's; the next step sets its own)
+        if self._word_schedule is not None and "iteration" in ck:
+            self._word = self._word_checked(self._word_schedule(max(self.iteration - 1, 0)))
 
     # ---- weight EMA of the generating network --------------------------------------------------------------------
     ema_model = None          # the shadow network: a deep copy whose parameters the averaging Adam step writes
@@ -1169,8 +1264,8 @@ class _GraphedSteps:
             return self._run_with_pack_plan(body, {p.plan: getattr(self, p.net) for p in self._parts})
 
     def _frozen(self, *values):
-        """Learning rates / beta as part of a capture key: frozen kernel arguments -- unless ``device_hyper`` keeps them
-        in device words, where they may change under one capture."""
+        """Learning rates / beta / the objective's own word as part of a capture key: frozen kernel arguments -- unless
+        ``device_hyper`` keeps them in device words, where they may change under one capture."""
         return None if self.device_hyper else values
 
     def _capture_key(self, data, labels):
@@ -1178,7 +1273,8 @@ class _GraphedSteps:
         the identity of Adam's moment tensors, and the host-side switches."""
         opts = self._optimizers().values()
         return (tuple(data.shape), labels and int(labels[2]),
-                self._frozen(getattr(self, "beta", None), *(o.param_groups[0]["lr"] for o in opts)),
+                self._frozen(getattr(self, "beta", None), *(o.param_groups[0]["lr"] for o in opts),
+                             *(() if self._word is None else (self._word,))),
                 ops.CONV_ARITH, tuple(o.state_generation for o in opts), self._host_state_key())
 
     def _drive(self, data, given, real_label=None, fake_label=None, global_batch=None, grad_hook=None):
@@ -1302,7 +1398,21 @@ class BetaVAEGANTrainer(_GraphedSteps):
     and ``beta = 0`` (a WAE) is allowed.  The iteration takes one more latent, ``prior``, drawn after ``eps3`` (`step`
     accepts ``prior=``).  ``kld`` of the returned dict is the weighted loss that was backpropagated; ``kl``, ``mmd``,
     ``mmd_kzz`` are added to it.  No checkpoint state; together with ``tc_decomposition`` or ``dip_vae`` it is a
-    ValueError.  Data parallel: replica-local, as those are."""
+    ValueError.  Data parallel: replica-local, as those are.
+
+    ``kl_control=(capacity, free_bits)`` (default: none, with the same guarantee): phase 3's KL term is held at a capacity
+    over per-dimension free bits (Burgess et al. 2018, disentanglement_lib's AnnealedVAE; Kingma et al. 2016; DESIGN.md
+    section 4.30): ``beta * |kl_floored - B * capacity|`` with ``kl_floored = sum_d max(K[d], B * free_bits)``, ``K[d]`` the
+    dimension's KL summed over the batch (`VAE.forward_with_klc`; two launches forward, one backward); `beta` plays
+    Burgess's gamma.  ``capacity`` (nats per sample): a float >= 0, or a callable ``iteration -> float``
+    (`linear_capacity`) evaluated with `iteration` at the start of every `step`; `capacity` reads it, `set_capacity` sets it
+    by hand, `kl_control` reads the pair.  ``free_bits`` (nats per dimension per sample): a finite float >= 0, a frozen
+    kernel argument.  With ``device_hyper`` -- on by default also when the capacity is a callable -- the capacity lives in
+    a device word beside beta's, so a capacity annealed every iteration still replays ONE graph; without, it is a frozen
+    value of the capture key, as beta is.  ``kld`` of the returned dict is the weighted loss that was backpropagated;
+    ``kl``, ``kl_floored`` and ``dims_above`` (the number of dimensions above their floor) are added to it.  A callable
+    capacity adds the ``iteration`` checkpoint key, a constant one no key; together with another objective it is a
+    ValueError.  Data parallel: the sums are those of this replica's batch -- replica-local, as those are."""
 
     _parts = (_Part("netEG", VAE, "optimizerEG", "flat_eg", "eg", "encoder_decoder_optimizer"),              # :41, :49
               _Part("netD", Discriminator_celeba, "optimizerD", "flat_d", "d", "discriminator_optimizer"))    # :43, :50
@@ -1316,11 +1426,11 @@ class BetaVAEGANTrainer(_GraphedSteps):
                  max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False,
                  lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0, decoupled_weight_decay: bool = False,
                  device_hyper: Optional[bool] = None, ema_decay=None, tc_decomposition=None,
-                 dataset_size: Optional[int] = None, dip_vae=None, mmd_vae=None):
+                 dataset_size: Optional[int] = None, dip_vae=None, mmd_vae=None, kl_control=None):
         self.beta = float(beta)
         self._setup(device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
                     beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition,
-                    dataset_size, data_parallel, capturable, dip_vae, mmd_vae)      # (lr: hard-coded 1e-3 at new_betavaegan.py:49-50)
+                    dataset_size, data_parallel, capturable, dip_vae, mmd_vae, kl_control)      # (lr: hard-coded 1e-3 at new_betavaegan.py:49-50)
         self._eg_params = [p for p in self.netEG.parameters() if p.dim() == 4]   # convolution filters
         self._d_params = [p for p in self.netD.parameters() if p.dim() == 4]
 
@@ -1667,7 +1777,8 @@ class VAETrainer(_GraphedSteps):
     ``device_hyper``): as BetaVAEGANTrainer.  ``ema_decay``: as there, of the one network -- `ema_model` shadows `model`,
     the checkpoint key is ``VAE_model_ema``.  ``tc_decomposition`` / ``dataset_size``: as there, of the step's KL term
     (`train_epoch` fills a ``dataset_size`` that was not given); replica-local under data parallelism.  ``dip_vae``: as
-    there -- the covariance is that of this replica's batch.  ``mmd_vae``: as there -- ``prior`` is drawn after ``eps``."""
+    there -- the covariance is that of this replica's batch.  ``mmd_vae``: as there -- ``prior`` is drawn after ``eps``.
+    ``kl_control``: as there -- the per-dimension sums are those of this replica's batch."""
 
     _parts = (_Part("model", VAE, "optimizer", "flat", "vae", "optimizer"),)
     _latents = ("eps",)
@@ -1678,11 +1789,11 @@ class VAETrainer(_GraphedSteps):
                  nonfinite_guard: Optional[bool] = None, max_grad_norm: Optional[float] = None,
                  skip_nonfinite: bool = False, lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0,
                  decoupled_weight_decay: bool = False, device_hyper: Optional[bool] = None, ema_decay=None,
-                 tc_decomposition=None, dataset_size: Optional[int] = None, dip_vae=None, mmd_vae=None):
+                 tc_decomposition=None, dataset_size: Optional[int] = None, dip_vae=None, mmd_vae=None, kl_control=None):
         self.beta = float(beta)
         self._setup(device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
                     beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition,
-                    dataset_size, capturable=capturable, dip_vae=dip_vae, mmd_vae=mmd_vae)
+                    dataset_size, capturable=capturable, dip_vae=dip_vae, mmd_vae=mmd_vae, kl_control=kl_control)
 
     def step(self, data, eps=None, grad_hook=None, prior=None):
         """``grad_hook(phase, net)`` (tests): called with ``("VAE", model)`` right before the optimizer step; such an
@@ -1732,7 +1843,7 @@ class GANTrainer(_GraphedSteps):
     gradient exchange (SUM) per optimizer step, BCE divided by the global batch.  ``graph``: as
     BetaVAEGANTrainer; so are ``max_grad_norm``, ``skip_nonfinite`` and the schedule arguments (``lr_scheduler``,
     ``weight_decay``, ``decoupled_weight_decay``, ``device_hyper``; there is no KL term, so a ``beta_schedule``, a
-    ``tc_decomposition``, a ``dip_vae`` or an ``mmd_vae`` is a TypeError).  ``ema_decay``: as BetaVAEGANTrainer, of the generator -- `ema_model` shadows `netG`, the checkpoint key is
+    ``tc_decomposition``, a ``dip_vae``, an ``mmd_vae`` or a ``kl_control`` is a TypeError).  ``ema_decay``: as BetaVAEGANTrainer, of the generator -- `ema_model` shadows `netG`, the checkpoint key is
     ``netG_ema``; the discriminator is not averaged."""
 
     _parts = (_Part("netG", Generator_celeba, "optimizerG", "flat_g", "g", "G_trainer"),
@@ -1746,10 +1857,10 @@ class GANTrainer(_GraphedSteps):
                  nonfinite_guard: Optional[bool] = None, max_grad_norm: Optional[float] = None,
                  skip_nonfinite: bool = False, lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0,
                  decoupled_weight_decay: bool = False, device_hyper: Optional[bool] = None, ema_decay=None,
-                 tc_decomposition=None, dataset_size: Optional[int] = None, dip_vae=None, mmd_vae=None):
+                 tc_decomposition=None, dataset_size: Optional[int] = None, dip_vae=None, mmd_vae=None, kl_control=None):
         self._setup(device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
                     beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition,
-                    dataset_size, data_parallel, dip_vae=dip_vae, mmd_vae=mmd_vae)
+                    dataset_size, data_parallel, dip_vae=dip_vae, mmd_vae=mmd_vae, kl_control=kl_control)
 
     def step(self, data, noise=None, real_label=0.9, fake_label=0.1, global_batch: Optional[int] = None,
              grad_hook=None):

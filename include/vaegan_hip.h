@@ -52,7 +52,7 @@ extern "C" {
  * csrc/reparam_tc.hip; vg_linear_wgrad_adam, vg_linear_wgrad_adam_dev; the five vg_reparam_dip_* of
  * csrc/reparam_dip.hip; the three vg_agg_posterior_* of csrc/agg_posterior.hip; the five vg_reparam_mmd_* of
  * csrc/reparam_mmd.hip; the four vg_pair_* of csrc/pair_dist.hip; the two vg_recon_quality* of
- * csrc/recon_quality.hip) change
+ * csrc/recon_quality.hip; the five vg_reparam_klc_* of csrc/reparam_klc.hip) change
  * nothing an existing caller sees and keep the version: a binding that needs them and finds a library without them
  * fails at the symbol lookup, as loudly. */
 #define VG_ABI_VERSION 7
@@ -532,6 +532,44 @@ int vg_reparam_mmd_fwd_dev(const float* mu, const float* logvar, const float* ep
                            void* stream);
 int vg_reparam_mmd_bwd_dev(const float* gz, const float* mu, const float* logvar, const float* eps, const float* z,
                            const float* zp, const float* w, const float* gloss, const float* beta_dev, float lambda_mmd,
+                           float* gmu, float* glogvar, int B, int D, void* workspace, size_t workspace_bytes,
+                           void* stream);
+
+/* ---- reparameterisation + the controlled KL term: a capacity (Burgess et al. 2018; AnnealedVAE) over per-dimension
+ * free bits (Kingma et al. 2016); csrc/reparam_klc.hip.  With z = mu + eps*exp(logvar/2), the
+ * capacity C >= 0 (nats per sample) and the floor lambda = free_bits >= 0 (nats per dimension per sample),
+ *   K[d] = -0.5*sum_b(1 + logvar - mu^2 - exp(logvar))      (fp64, fixed order)
+ *   F[d] = max(K[d], B*lambda)                              (a NaN K[d] stays NaN)
+ *   kl   = sum_d K[d]        T = sum_d F[d]                 (fp64, index order)
+ *   above = #{d : K[d] > B*lambda}
+ * the forward writes z and out4 = {loss, kl, T, above}, loss = beta*|T - B*C| (batch sums: loss / B is Burgess's term over
+ * Kingma's batch-averaged floor; lambda = 0, C = 0 is the plain beta*kl), and what the backward reads and a caller may
+ * want: gate ([D] fp32) = sgn(T - B*C)*[K[d] > B*lambda] in {-1, 0, +1} (sgn(0) = 0; NaN where a NaN went into T) and
+ * kl_dim ([D] fp32) = K[d]/B.  Two launches: one workgroup per 64 rows x 64 columns writes z and its column sums to fixed
+ * fp64 slots; ONE workgroup adds the slots in index order, applies the floor and forms the totals.  The backward writes
+ *   gmu     = gloss*beta*gate[d]*mu + gz
+ *   glogvar = gloss*beta*gate[d]*0.5*(exp(logvar) - 1) + gz*eps*0.5*exp(logvar/2)
+ * in one elementwise launch; gz (tensor) and gloss (DEVICE scalar, upstream of out4[0]) may each be NULL: that term is
+ * absent.  No floating-point atomics: the same inputs give the same bits.  `workspace`:
+ * vg_reparam_klc_workspace_bytes(B, D) bytes (0 outside the shape range), 8-byte aligned (the forward's content is not
+ * needed by the backward; the backward takes capacity and free_bits for symmetry and only checks them).  VG_ERR_BAD_ARG
+ * before any launch: a NULL pointer other than gz / gloss, B or D outside [1, 1024], a free_bits or a capacity that is not
+ * finite and >= 0, and -- here also VG_ERR_BAD_ARG -- a workspace shorter than that. */
+size_t vg_reparam_klc_workspace_bytes(int B, int D);
+int vg_reparam_klc_fwd(const float* mu, const float* logvar, const float* eps, float* z, float* out4, float* gate,
+                       float* kl_dim, int B, int D, float beta, float capacity, float free_bits, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int vg_reparam_klc_bwd(const float* gz, const float* mu, const float* logvar, const float* eps, const float* gate,
+                       const float* gloss, float beta, float capacity, float free_bits, float* gmu, float* glogvar, int B,
+                       int D, void* workspace, size_t workspace_bytes, void* stream);
+/* beta AND the capacity read from DEVICE memory (beta_dev[0], capacity_dev[0], fp32): a capacity annealed every iteration
+ * replays one captured graph.  The same fp32 values give the same bits.  Either word NULL is VG_ERR_BAD_ARG; the words'
+ * values are not checked (a NaN capacity is a NaN loss). */
+int vg_reparam_klc_fwd_dev(const float* mu, const float* logvar, const float* eps, float* z, float* out4, float* gate,
+                           float* kl_dim, int B, int D, const float* beta_dev, const float* capacity_dev, float free_bits,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int vg_reparam_klc_bwd_dev(const float* gz, const float* mu, const float* logvar, const float* eps, const float* gate,
+                           const float* gloss, const float* beta_dev, const float* capacity_dev, float free_bits,
                            float* gmu, float* glogvar, int B, int D, void* workspace, size_t workspace_bytes,
                            void* stream);
 

@@ -153,6 +153,7 @@ TUNING_SIGNATURES = {
     "vg_debug_wgrad_thin_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "vg_debug_set_conv_bf16split_tile": (_I, [_I]),
     "vg_debug_set_conv_ring_tile": (_I, [_I]),
+    "vg_debug_ring_route": (_I, [_I, _I, _I, _I, _I, _I, _I, _P]),
     "vg_debug_set_bn_team": (_I, [_I, _I]),
     "vg_debug_bn_bwd_plan": (_I, [_I, _I, _I, _P, _P, _P, _P]),
 }

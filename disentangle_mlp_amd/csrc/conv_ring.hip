@@ -605,6 +605,14 @@ __global__ __launch_bounds__(RNT, 2) void conv5x5_ring_kernel(RArgs A) {
   }
 }
 
+// transposed: two classes per workgroup when that still gives every CU a workgroup (and the XCD arithmetic holds)
+template <class C>
+constexpr bool ring_paired(long per_cls, int ksplit) {
+  return C::NCLS == 4 && C::F16 && per_cls * ksplit * 2 >= 256 && per_cls % 8 == 0;
+}
+
+VG_KNOB(int*, g_ring_route_out, nullptr);   // tuning build only: vg_debug_ring_route's out[6]; the launch reports, runs nothing
+
 // fu: the caller's fusion (never NULL here; stats only without a K split: the host says so)
 template <class C>
 int launch_ring(const float* x, const bf16x8* w, const float* bias, float* y, int B, int Cin, int XH, int XW, int Cout,
@@ -613,10 +621,14 @@ int launch_ring(const float* x, const bf16x8* w, const float* bias, float* y, in
   const long per_cls = fill_split<C>(A, x, w, bias, y, B, Cin, XH, XW, Cout, ksplit, slabs, fu.in_amax);
   A.in_scale = fu.in_scale; A.in_shift = fu.in_shift; A.in_act = fu.in_act;
   A.stats = (ksplit == 1) ? fu.stats : nullptr;
-  // transposed: two classes per workgroup when that still gives every CU a workgroup (and the XCD arithmetic holds)
-  A.paired = (C::NCLS == 4 && C::F16 && per_cls * ksplit * 2 >= 256 && per_cls % 8 == 0) ? 1 : 0;
+  A.paired = ring_paired<C>(per_cls, ksplit) ? 1 : 0;
   const long grid = per_cls * (A.paired ? 2 : C::NCLS) * ksplit;
   if (!grid_ok(grid)) return VG_ERR_BAD_ARG;
+  if (g_ring_route_out) {     // (a constant NULL in the product library)
+    const int route[6] = {-1, ksplit, C::NB, C::TH, C::TW, A.paired};
+    for (int i = 1; i < 6; ++i) g_ring_route_out[i] = route[i];
+    return 0;
+  }
   if (A.in_scale) hipLaunchKernelGGL((conv5x5_ring_kernel<C, true>), dim3((unsigned)grid), dim3(RNT), 0, st, A);
   else hipLaunchKernelGGL((conv5x5_ring_kernel<C, false>), dim3((unsigned)grid), dim3(RNT), 0, st, A);
   VG_CHECK_LAUNCH();
@@ -744,4 +756,20 @@ int vg_internal_ring_conv(int mode, const float* x, const void* packed, const fl
 
 #ifdef VG_TUNING
 void vg_internal_ring_set_variant(int v) { g_ring_variant = v; }
+
+// Host only: the shape goes down the launch's own path (ring_plan, ring_dispatch, ring_geom, launch_ring), which reports
+// instead of launching while g_ring_route_out is set.  No pointer is dereferenced on the way.
+extern "C" int vg_debug_ring_route(int mode, int B, int Cin, int H, int W, int Cout, int planes, int* out) {
+  if (!out || (mode != CONV_FWD && mode != CONV_TR) || !conv_shape_ok(B, Cin, H, W, Cout, 2) || Cin % 16 || !planes_ok(planes))
+    return VG_ERR_BAD_ARG;
+  const RingPlan p = ring_plan(mode, B, Cin, H, W, Cout, planes);
+  alignas(16) static float word[4];
+  vg_conv_fusion fu = {};
+  fu.in_amax = word;
+  out[0] = p.variant;
+  g_ring_route_out = out;
+  const int rc = vg_internal_ring_conv(mode, word, word, nullptr, word, B, Cin, H, W, Cout, planes, word, (size_t)-1, &fu, nullptr);
+  g_ring_route_out = nullptr;
+  return rc;
+}
 #endif

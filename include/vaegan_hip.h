@@ -956,6 +956,12 @@ int vg_debug_set_conv_bf16split_tile(int variant);
 /* stride-2 ring kernel of conv_ring.hip: 0 = 256 cout x 128 px, 1 / 2 = 128 x 128 (2x4 / 4x2 wavefronts),
  * 3 = 128 x 256 (transposed), -1 = heuristic */
 int vg_debug_set_conv_ring_tile(int variant);
+/* What the ring kernel would launch for a stride-2 shape (mode 0 forward, 1 transposed) under the current knob (host
+ * only, nothing runs) -- from the same planning and dispatch code as the launch.
+ *   out[6]: tile variant, K splits, then the pixel tile: images, rows, columns (of the output forward, of the input
+ *           transposed); paired (transposed: 1 = a workgroup runs two parity classes).
+ * VG_ERR_BAD_ARG: the kernel does not take the shape. */
+int vg_debug_ring_route(int mode, int B, int Cin, int H, int W, int Cout, int planes, int* out);
 /* One-pass BatchNorm backward by workgroup teams (bn.hip, bn_bwd_team_kernel): nv = 1 or 8 forces the team form, with that
  * many 16-byte vectors of x and of gy per lane (a member then holds 4096 * nv elements), on every shape it can take
  * (16-byte streams, <= 16 members per channel, max_wgs >= the members of one channel); nv = 0 restores the dispatch rule

@@ -128,6 +128,9 @@ SIGNATURES = {
     "vg_pair_hits": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
     "vg_recon_quality_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
     "vg_recon_quality": (_I, [_P, _P, _P, _I, _I, _I, _I, _I] + [ctypes.c_double] * 4 + [_P, _Z, _P]),
+    "vg_diff_augment_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "vg_diff_augment_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _Z, _P]),
+    "vg_diff_augment_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _Z, _P]),
     "vg_bce_loss_dev": (_I, [_P, _P, _P, _P, _I, _F, _F, _P]),
     "vg_dot_sigmoid_bce_workspace_bytes": (_Z, [_I]),
     "vg_dot_sigmoid_bce_fwd": (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _I, _I, _F, _P, _Z, _P]),

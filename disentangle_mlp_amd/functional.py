@@ -693,6 +693,24 @@ class BCELossFn(Function):
         return ops.scale_by_scalar(gp, gout.contiguous()), None, None
 
 
+class DiffAugmentFn(Function):
+    """Differentiable augmentation of an image batch (ops.diff_augment_fwd).  Given ``u`` the map is
+    affine in ``x``: the backward is the transpose of its linear part, from ``gy`` and ``u`` alone -- ``u`` is all that is
+    saved.  ``policy``: the bit set; ``u`` gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, u, policy, p):
+        ctx.save_for_backward(u)
+        ctx.policy, ctx.p = policy, p
+        return ops.diff_augment_fwd(x, u, policy, p)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        (u,) = ctx.saved_tensors
+        return ops.diff_augment_bwd(gy.contiguous(), u, ctx.policy, ctx.p), None, None, None
+
+
 class DotSigmoidBCEFn(Function):
     """Linear(K -> 1) + Sigmoid + nn.BCELoss against a constant label in one launch each way (model.py:406-408,
     new_betavaegan.py:101,118,153-154).  Returns (p (B,), loss); p is not differentiable here (the iteration only reads
@@ -865,3 +883,17 @@ def dot_sigmoid_bce(feat, w, bias, label_value, divisor=None):
         label_value = float(label_value)
     return DotSigmoidBCEFn.apply(feat.contiguous(), w, bias, label_value, divisor)
 
+
+
+def diff_augment(x, u, policy="color,translation,cutout", p=1.0):
+    """Differentiable augmentation (Zhao et al. 2020) of ``x`` [B, C, H, W] under ``u`` [B, 8] (`diff_augment_uniforms`):
+    ``policy`` names the transforms (any order; applied as colour, translation, cutout), an image is transformed iff
+    ``u[:, 7] < p``.  Differentiable in ``x``; see DiffAugmentFn."""
+    return DiffAugmentFn.apply(x.contiguous(), u, ops.augment_policy(policy), ops.augment_probability(p))
+
+
+def diff_augment_uniforms(batch, device, generator=None, sets=None):
+    """The uniforms of `diff_augment` for ``batch`` images: [batch, 8] in [0, 1), or [sets, batch, 8] -- one parameter set per
+    call of an iteration -- from ``generator`` (default: the device's global stream)."""
+    shape = (batch, ops.AUGMENT_UNIFORMS) if sets is None else (sets, batch, ops.AUGMENT_UNIFORMS)
+    return torch.rand(shape, device=device, generator=generator)

@@ -1258,6 +1258,74 @@ def recon_quality(x, y, data_range=2.0, window=11, sigma=1.5, k1=0.01, k2=0.03):
     return out
 
 
+# ---- differentiable augmentation (csrc/diff_augment.hip) ---------------------------------------
+AUGMENT_BITS = {"color": 1, "translation": 2, "cutout": 4}      # VG_AUGMENT_* of include/vaegan_hip.h
+AUGMENT_UNIFORMS = 8                                            # uniforms per image: u[B, 8]
+
+
+def augment_policy(policy):
+    """``policy`` -- a comma-separated set of ``"color"``, ``"translation"``, ``"cutout"`` in any order, or its bit set
+    1..7 -- as the C ABI's bit set.  TypeError: neither a string nor an int; ValueError: an unknown name, an empty set."""
+    if isinstance(policy, bool) or not isinstance(policy, (str, int)):
+        raise TypeError(f"diff_augment: policy must be a string of names or a bit set, got {policy!r}")
+    if isinstance(policy, int):
+        if not 1 <= policy <= 7:
+            raise ValueError(f"diff_augment: a policy bit set is in 1..7, got {policy}")
+        return policy
+    bits = 0
+    for name in (n.strip() for n in policy.split(",")):
+        if not name:
+            continue
+        if name not in AUGMENT_BITS:
+            raise ValueError(f"diff_augment: unknown policy {name!r} (known: {', '.join(AUGMENT_BITS)})")
+        bits |= AUGMENT_BITS[name]
+    if not bits:
+        raise ValueError(f"diff_augment: the policy names no transform, got {policy!r}")
+    return bits
+
+
+def augment_probability(p):
+    """``p`` as a float in [0, 1] (TypeError: no number; ValueError: outside the range, inf or NaN)."""
+    try:
+        v = float(p)
+    except (TypeError, ValueError):
+        raise TypeError(f"diff_augment: p must be a number, got {p!r}") from None
+    if not (math.isfinite(v) and 0.0 <= v <= 1.0):
+        raise ValueError(f"diff_augment: p must be in [0, 1], got {p!r}")
+    return v
+
+
+def _diff_augment(symbol, v, u, policy, p):
+    bits, p = augment_policy(policy), augment_probability(p)
+    _req(v, symbol), _req(u, "u")
+    if v.dim() != 4 or u.shape != (v.shape[0], AUGMENT_UNIFORMS) or u.device != v.device:
+        raise RuntimeError(f"{symbol}: a [B, C, H, W] tensor and u [B, {AUGMENT_UNIFORMS}] on one device, got "
+                           f"{tuple(v.shape)} and {tuple(u.shape)}")
+    B, C, H, W = v.shape
+    lib = _lib.load()
+    nbytes = lib.vg_diff_augment_workspace_bytes(B, C, H, W)
+    if nbytes == 0:
+        raise RuntimeError(f"{symbol}: needs B >= 1, 1 <= C <= 4, H, W >= 2 and an image below 2^31 elements, got {tuple(v.shape)}")
+    out = torch.empty_like(v)
+    ws = workspace(nbytes, v.device) if bits & AUGMENT_BITS["color"] else None      # (the image sums: the colour step alone)
+    check(getattr(lib, symbol)(v.data_ptr(), u.data_ptr(), out.data_ptr(), B, C, H, W, bits, p, _ptr(ws),
+                               ws.numel() if ws is not None else 0, _stream()), symbol)
+    return out
+
+
+def diff_augment_fwd(x, u, policy, p=1.0):
+    """The augmented batch of ``x`` [B, C, H, W] under the rows of ``u`` [B, 8], uniforms in [0, 1): colour, translation,
+    cutout in that order, each if ``policy`` names it, on the images with ``u[:, 7] < p``; the others are copied
+    (vg_diff_augment_fwd).  Two launches with the colour step, one without; no bound of the output
+    is emitted -- its consumers, the 3-channel convolutions, ask for none."""
+    return _diff_augment("vg_diff_augment_fwd", x, u, policy, p)
+
+
+def diff_augment_bwd(gy, u, policy, p=1.0):
+    """The transpose of `diff_augment_fwd`'s linear part applied to ``gy``: it reads ``gy`` and ``u`` alone."""
+    return _diff_augment("vg_diff_augment_bwd", gy, u, policy, p)
+
+
 def reparam_tc_bwd(gz, mu, logvar, eps, z, lse_joint, lse_dim, gloss, beta, alpha, gamma):
     """gz: tensor or None; gloss: 0-dim device tensor (upstream gradient of the weighted loss) or None."""
     lib = _lib.load()

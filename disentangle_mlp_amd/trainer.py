@@ -303,6 +303,26 @@ def _latent_generator(device, seed, rank):
     return g
 
 
+def _augment_generator(device, seed, rank):
+    """Generator of the uniforms of ``diff_augment``: a stream of its own per replica, seeded from (seed, rank) as the latent
+    one is -- apart from it, so that the latents are bit for bit what they are without the option."""
+    g = torch.Generator(device=device)
+    g.manual_seed(int(seed) + (1 << 32) + int(rank))      # (far from every rank's latent seed, seed + 1 + rank)
+    return g
+
+
+def _parse_diff_augment(diff_augment):
+    """``diff_augment=policy`` or ``(policy, p)`` -> (the policy's names in canonical order, its bit set, p)."""
+    try:
+        policy, p = (diff_augment, 1.0) if isinstance(diff_augment, str) else diff_augment
+    except (TypeError, ValueError):
+        raise TypeError(f"diff_augment must be a policy string or a pair (policy, p), got {diff_augment!r}") from None
+    if not isinstance(policy, str):
+        raise TypeError(f"diff_augment: the policy is a string of names, got {policy!r}")
+    bits, p = ops.augment_policy(policy), ops.augment_probability(p)
+    return ",".join(n for n, b in ops.AUGMENT_BITS.items() if bits & b), bits, p
+
+
 def sample_labels(rng=None):
     """The per-iteration label draw of new_betavaegan.py:89-90 (new_gan.py:68-69 alike): soft labels
     0.9 / 0.1, each flipped with probability 5 %.  Draw order as in the reference -- the fake label
@@ -392,7 +412,8 @@ class _CapturedIteration:
     one graph launch, so the host no longer paces the GPU.
 
     What the graph freezes and how it stays correct from replay to replay:
-      * inputs / latents: static device buffers the caller's tensors are copied into before a replay;
+      * inputs / latents / the uniforms of ``diff_augment``: static device buffers the caller's tensors are copied into
+        before a replay (what the trainer draws itself, it draws straight into them);
       * the two label scalars (new_betavaegan.py:89-90): a device tensor the BCE kernels read (vg_bce_loss_dev);
       * Adam's step count: a device counter advanced inside the graph (optim.HipAdam(capturable=True));
       * with ``device_hyper``: the learning rate, the weight decay and the KL weight beta -- device words the prepare kernel
@@ -475,6 +496,13 @@ def _use_tuned_gemms(device):
     if torch.device(device).type == "cuda":
         from . import tuned_gemms
         tuned_gemms.enable()
+
+
+class _Drawn(NamedTuple):
+    """One random input of an iteration (`_GraphedSteps._drawn`): what the trainer draws when the caller passes None."""
+    name: str             # its key among a capture's static inputs
+    dist: str             # "normal": N(0, 1) | "uniform": U[0, 1)
+    generator: str        # attribute of the trainer's generator it is drawn from
 
 
 class _Part(NamedTuple):
@@ -595,9 +623,9 @@ def _objective_args(keyword):
 class _GraphedSteps:
     """What the three trainers share: the construction (`_setup`), the one path an iteration takes (`_drive`: eager, or
     -- `_graph_usable` -- a HIP-graph replay with its warm-up count per shape, capture and fallback), the guard, the
-    schedules and the weight EMA.  A trainer declares `_parts` (who is in it; everything that lists networks, optimizers
-    or exchanges derives from that table), `_latents`, `_has_labels`, `_accumulate`, and `_iteration`: the iteration
-    itself on given tensors."""
+    schedules, the weight EMA and the augmentation of the discriminator's inputs.  A trainer declares `_parts` (who is in
+    it; everything that lists networks, optimizers or exchanges derives from that table), `_latents`, `_has_labels`,
+    `_accumulate`, `_augment_sets`, and `_iteration`: the iteration itself on given tensors."""
     graph = False
     iteration = 0
     probe = None      # callable(name, tensor): taps of an (eager) iteration, see BetaVAEGANTrainer._iteration
@@ -605,10 +633,12 @@ class _GraphedSteps:
     _latents = ()     # names of the (batch, n_hidden) N(0,1) draws of an iteration, in draw order
     _has_labels = False       # the iteration takes the two label scalars and the global batch (the BCE's divisor)
     _accumulate = False       # layers applied twice before one backward add their second parameter gradient in-kernel
+    _augment_sets = 0         # parameter sets of ``diff_augment`` an iteration uses (0: the trainer has no discriminator)
+    _augment = None           # (policy names, bit set, p) of ``diff_augment``, None when off
 
     def _setup(self, device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
                beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition, dataset_size,
-               data_parallel=None, capturable=None, dip_vae=None, mmd_vae=None, kl_control=None):
+               data_parallel=None, capturable=None, dip_vae=None, mmd_vae=None, kl_control=None, diff_augment=None):
         """The constructor body of every trainer (new_betavaegan.py:36-53, new_vae.py:33-37, new_gan.py:47-61).  A trainer
         with a KL term has set `beta` before."""
         has_beta = hasattr(self, "beta")
@@ -619,6 +649,10 @@ class _GraphedSteps:
         _use_tuned_gemms(self.device)
         self._select_objective(dict(tc_decomposition=tc_decomposition, dip_vae=dip_vae, mmd_vae=mmd_vae, kl_control=kl_control),
                                dataset_size, has_beta)
+        if diff_augment is not None:
+            if not self._augment_sets:
+                raise TypeError(f"{type(self).__name__} has no discriminator: diff_augment does not apply")
+            self._augment = _parse_diff_augment(diff_augment)
         self.max_grad_norm, self.skip_nonfinite = max_grad_norm, bool(skip_nonfinite)
         self._skipped = {}
         self.world, self.rank = _dist_world(), _dist_rank()
@@ -648,6 +682,8 @@ class _GraphedSteps:
             net = getattr(self, p.net)
             setattr(self, p.flat, FlatGrads(net.parameters(), silent=shadowed_bias_params(net)) if self.dp else None)
         self.latent_generator = _latent_generator(self.device, seed, self.rank)
+        if self._augment is not None:
+            self.augment_generator = _augment_generator(self.device, seed, self.rank)
         if self._has_labels:
             self.label_rng = _shared_label_rng(seed)      # used by train_epoch when world > 1: one draw per GLOBAL batch
         for net in self._nets():
@@ -1202,21 +1238,61 @@ class _GraphedSteps:
                 self.device_hyper,           # (lr, weight decay and beta read from device words, or frozen arguments)
                 self._objective_key(),       # (which objective, and its frozen kernel arguments)
                 tuple(net.training for net in self._nets()),
-                tuple(p.requires_grad for net in self._nets() for p in net.parameters()))
+                tuple(p.requires_grad for net in self._nets() for p in net.parameters()),
+                *(() if self._augment is None else (self._augment,)))      # (the augmentation's launches: policy and p)
 
     # ---- one iteration: the path every `step` takes ----------------------------------------------------------------------
     def draw_latents(self, batch):
         """One N(0,1) draw of shape (batch, n_hidden) from this replica's own stream."""
         return torch.randn(batch, self.opt.n_hidden, device=self.device, generator=self.latent_generator)
 
+    def draw_augment(self, batch):
+        """One iteration's uniforms of ``diff_augment``, [sets, batch, 8], from this replica's augmentation stream."""
+        if self._augment is None:
+            raise TypeError(f"{type(self).__name__}: construct with diff_augment=... to draw its uniforms")
+        return F.diff_augment_uniforms(batch, self.device, self.augment_generator, sets=self._augment_sets)
+
+    def _drawn(self):
+        """The random inputs of one iteration in draw order, each naming its distribution: the latents, N(0,1) of shape
+        (batch, n_hidden) from the latent stream, then -- with ``diff_augment`` -- ``augment``, U[0,1) of shape (sets, batch,
+        8) from the augmentation stream."""
+        drawn = [_Drawn(name, "normal", "latent_generator") for name in self._latents]
+        if self._augment is not None:
+            drawn.append(_Drawn("augment", "uniform", "augment_generator"))
+        return drawn
+
     def _draw(self, given, batch, cap=None):
-        """The latents of one iteration, in `_latents` order: the caller's, and each one left to the trainer (None) drawn
-        from this replica's stream (``noise`` of new_betavaegan.py:111, ``eps`` of model.py:534) -- straight into the
-        static buffer of the capture ``cap`` when there is one: same generator, same order, same values."""
-        return tuple(t if t is not None
-                     else self.draw_latents(batch) if cap is None
-                     else cap.inputs[name].normal_(generator=self.latent_generator)
-                     for name, t in zip(self._latents, given))
+        """The random inputs of one iteration, in `_drawn` order: the caller's, and each one left to the trainer (None) drawn
+        from this replica's stream of that input (``noise`` of new_betavaegan.py:111, ``eps`` of model.py:534) -- straight
+        into the static buffer of the capture ``cap`` when there is one: same generator, same order, same values."""
+        out = []
+        for d, t in zip(self._drawn(), given):
+            if t is None and cap is None:
+                t = self.draw_latents(batch) if d.dist == "normal" else self.draw_augment(batch)
+            elif t is None:
+                g = getattr(self, d.generator)
+                t = cap.inputs[d.name].normal_(generator=g) if d.dist == "normal" else cap.inputs[d.name].uniform_(generator=g)
+            out.append(t)
+        return tuple(out)
+
+    def _with_augment(self, given, augment, batch):
+        """`step`'s random inputs in `_drawn` order: behind the latents, the caller's ``augment`` (or None: drawn)."""
+        if self._augment is None:
+            if augment is not None:
+                raise TypeError(f"{type(self).__name__}.step: augment= belongs to diff_augment, which is off")
+            return given
+        shape = (self._augment_sets, batch, ops.AUGMENT_UNIFORMS)
+        if augment is not None and (tuple(augment.shape) != shape or augment.dtype != torch.float32
+                                    or augment.device.type != self.device.type):
+            raise ValueError(f"{type(self).__name__}.step: augment must be a float32 tensor of shape {shape} on {self.device}, "
+                             f"got {tuple(augment.shape)} {augment.dtype} on {augment.device}")
+        return (*given, augment)
+
+    def _augmented(self, x, augment, k):
+        """``x`` as the discriminator sees it: through parameter set ``k`` of ``augment``, or as it is without the option."""
+        if self._augment is None:
+            return x
+        return F.diff_augment(x, augment[k], self._augment[1], self._augment[2])
 
     def _zero(self, net, flat, opt=None, grad_hook=None, update_ema=True):
         """A phase's zeroing.  ``opt``: the optimizer whose `step` ends the phase -- the big Linear weights the coming
@@ -1246,11 +1322,11 @@ class _GraphedSteps:
             p.requires_grad_(not frozen)
 
     def _iteration(self, data, latents, labels, grad_hook, prepack, acc):
-        """The iteration itself: ``latents`` in `_latents` order, ``labels`` = (real, fake, global batch) -- floats, or
-        the device scalars of a capture -- or None without `_has_labels`; ``grad_hook(phase, net)`` (tests) is called
-        right before each optimizer step; ``prepack``: see `_run_with_pack_plan`; ``acc``: the open
-        `F.accumulate_param_grads`, or None without `_accumulate`.  Counts `iteration`; returns the losses as device
-        scalars (no synchronisation)."""
+        """The iteration itself: ``latents`` in `_drawn` order (the uniforms of ``diff_augment`` last), ``labels`` = (real,
+        fake, global batch) -- floats, or the device scalars of a capture -- or None without `_has_labels`;
+        ``grad_hook(phase, net)`` (tests) is called right before each optimizer step; ``prepack``: see
+        `_run_with_pack_plan`; ``acc``: the open `F.accumulate_param_grads`, or None without `_accumulate`.  Counts
+        `iteration`; returns the losses as device scalars (no synchronisation)."""
         raise NotImplementedError
 
     def _eager(self, data, latents, labels, grad_hook=None):
@@ -1277,11 +1353,12 @@ class _GraphedSteps:
                              *(() if self._word is None else (self._word,))),
                 ops.CONV_ARITH, tuple(o.state_generation for o in opts), self._host_state_key())
 
-    def _drive(self, data, given, real_label=None, fake_label=None, global_batch=None, grad_hook=None):
+    def _drive(self, data, given, real_label=None, fake_label=None, global_batch=None, grad_hook=None, augment=None):
         """One iteration from `_begin_step` to `_end_step`.  ``given``: the caller's latents in `_latents` order, None
         where the trainer is to draw.  Eager -- or, `_graph_usable`: the first GRAPH_WARM_STEPS iterations of a capture
         key eager (workspaces, packs, GEMM plans exist then), the next one captured and replayed, later ones replayed;
         and eager for good after a failed capture."""
+        given = self._with_augment(given, augment, data.size(0))
         self._begin_step()
         batch, labels = data.size(0), None
         if self._has_labels:
@@ -1303,13 +1380,14 @@ class _GraphedSteps:
             self._shape_steps[key] = self._shape_steps.get(key, 0) + 1
             return self._eager(data, self._draw(given, data.size(0)), labels)
         latents = self._draw(given, data.size(0), cap)
-        inputs = dict(data=data.contiguous(), **dict(zip(self._latents, latents)))
+        names = [d.name for d in self._drawn()]
+        inputs = dict(data=data.contiguous(), **dict(zip(names, latents)))
         if cap is None:
             if len(self._graphs) >= 4:               # each capture keeps its own memory pool: bound them
                 self._graphs.pop(next(iter(self._graphs)))
 
             def run(inp, real_dev, fake_dev):        # the iteration on the capture's static tensors
-                return self._eager(inp["data"], tuple(inp[n] for n in self._latents),
+                return self._eager(inp["data"], tuple(inp[n] for n in names),
                                    labels and (real_dev, fake_dev, labels[2]))
             bns = [m for net in self._nets() for m in net.modules() if hasattr(m, "_nbt_pending")]
             it0 = self.iteration
@@ -1412,12 +1490,26 @@ class BetaVAEGANTrainer(_GraphedSteps):
     value of the capture key, as beta is.  ``kld`` of the returned dict is the weighted loss that was backpropagated;
     ``kl``, ``kl_floored`` and ``dims_above`` (the number of dimensions above their floor) are added to it.  A callable
     capacity adds the ``iteration`` checkpoint key, a constant one no key; together with another objective it is a
-    ValueError.  Data parallel: the sums are those of this replica's batch -- replica-local, as those are."""
+    ValueError.  Data parallel: the sums are those of this replica's batch -- replica-local, as those are.
+
+    ``diff_augment=policy`` or ``(policy, p)`` (default: none -- then every launch, capture key, latent draw, checkpoint key
+    and bit is what it was): every image batch the discriminator sees goes through a random, differentiable transform
+    (Zhao et al. 2020; `functional.diff_augment`): ``policy`` is a comma-separated set of
+    ``"color"``, ``"translation"``, ``"cutout"``, an image is transformed with probability ``p`` (default 1, the published
+    method).  Four parameter sets per iteration, uniforms ``(4, B, 8)``: phase 1 set 0 on ``data`` and set 1 on
+    ``fake.detach()``; phase 2 set 2 on ``data`` AND on ``recon`` -- the pair Dis_l compares goes through the same transform
+    sample by sample, so the learned similarity still compares like with like -- and set 3 on ``fake``; phase 3 has no
+    discriminator, and the pixel MSE terms compare the images themselves.  The uniforms come from `augment_generator`, a
+    stream of the trainer's own seeded from (seed, rank), drawn after the iteration's latents -- the latent stream is bit
+    for bit what it is without the option -- and straight into a static input of the capture: a fresh draw every iteration
+    replays ONE graph.  `step(augment=)` takes them from the caller, `draw_augment` draws a set.  No checkpoint key.  Data
+    parallel: replica-local, each rank its own stream, as the latents are."""
 
     _parts = (_Part("netEG", VAE, "optimizerEG", "flat_eg", "eg", "encoder_decoder_optimizer"),              # :41, :49
               _Part("netD", Discriminator_celeba, "optimizerD", "flat_d", "d", "discriminator_optimizer"))    # :43, :50
     _latents = ("noise", "eps2", "eps3")
     _has_labels = _accumulate = True
+    _augment_sets = 4         # phase 1: data, fake.detach(); phase 2: data and recon (one set), fake
     _ema_names = ("netEG", "optimizerEG", "encoder_decoder_ema")
 
     def __init__(self, device="cuda", seed=999, beta=25.0, lr=1e-3, opt: Optional[ModelOpt] = None,
@@ -1426,28 +1518,34 @@ class BetaVAEGANTrainer(_GraphedSteps):
                  max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False,
                  lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0, decoupled_weight_decay: bool = False,
                  device_hyper: Optional[bool] = None, ema_decay=None, tc_decomposition=None,
-                 dataset_size: Optional[int] = None, dip_vae=None, mmd_vae=None, kl_control=None):
+                 dataset_size: Optional[int] = None, dip_vae=None, mmd_vae=None, kl_control=None, diff_augment=None):
         self.beta = float(beta)
         self._setup(device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
                     beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition,
-                    dataset_size, data_parallel, capturable, dip_vae, mmd_vae, kl_control)      # (lr: hard-coded 1e-3 at new_betavaegan.py:49-50)
+                    dataset_size, data_parallel, capturable, dip_vae, mmd_vae, kl_control,      # (lr: hard-coded 1e-3 at new_betavaegan.py:49-50)
+                    diff_augment)
         self._eg_params = [p for p in self.netEG.parameters() if p.dim() == 4]   # convolution filters
         self._d_params = [p for p in self.netD.parameters() if p.dim() == 4]
 
     # -- one iteration ------------------------------------------------------------
     def step(self, data, noise=None, eps2=None, eps3=None, real_label=0.9, fake_label=0.1,
-             global_batch: Optional[int] = None, grad_hook=None, prior=None) -> Dict[str, torch.Tensor]:
+             global_batch: Optional[int] = None, grad_hook=None, prior=None, augment=None) -> Dict[str, torch.Tensor]:
         """One iteration; returns the nine loss scalars as device tensors (no host sync).  From the third iteration of a
         batch shape on the iteration is a HIP-graph replay and the returned tensors are the capture's STATIC outputs: the
         next replay overwrites them -- ``.clone()`` (or ``float()``) what is kept across steps.
-        ``prior`` (with ``mmd_vae`` only): phase 3's draws from the prior, (B, n_hidden); None is drawn, after ``eps3``."""
-        return self._drive(data, self._with_prior((noise, eps2, eps3), prior), real_label, fake_label, global_batch, grad_hook)
+        ``prior`` (with ``mmd_vae`` only): phase 3's draws from the prior, (B, n_hidden); None is drawn, after ``eps3``.
+        ``augment`` (with ``diff_augment`` only): the iteration's four parameter sets, uniforms (4, B, 8); None is drawn,
+        after the latents, from the augmentation stream (`draw_augment`)."""
+        return self._drive(data, self._with_prior((noise, eps2, eps3), prior), real_label, fake_label, global_batch, grad_hook,
+                           augment)
 
     def _iteration(self, data, latents, labels, grad_hook, prepack, acc):
         """data (B,3,64,64) in [-1,1]; noise / eps2 / eps3 (B, n_hidden) ~ N(0,1) (new_betavaegan.py:111, model.py:534);
         the labels are the per-iteration scalars of :89-90."""
         netEG, netD = self.netEG, self.netD
+        *latents, aug = latents if self._augment is not None else (*latents, None)      # (the uniforms of diff_augment: last)
         noise, eps2, eps3, *prior = latents                  # (prior: one more draw with an objective that takes it, else nothing)
+        seen = self._augmented                               # what the discriminator sees of an image batch (DESIGN.md 4.31)
         real_label, fake_label, gb = labels
         prepack()
         out = {}
@@ -1459,7 +1557,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
             fake.register_hook(lambda g: self.probe("grad_wrt_fake", g))
         with F.deferred_wgrad():                             # D runs twice, one backward: big Linear weight gradient once
             # ... and its big Linear layer reads its weight once for both passes, forward and data gradient
-            f_real, f_fake = netD.features_grouped([data, fake.detach()])
+            f_real, f_fake = netD.features_grouped([seen(data, aug, 0), seen(fake.detach(), aug, 1)])
             p_real, _, err_real = netD.head_with_bce(f_real, real_label, gb)
             p_fake, _, err_fake = netD.head_with_bce(f_fake, fake_label, gb)
             _backward([err_real, err_fake])
@@ -1479,7 +1577,10 @@ class BetaVAEGANTrainer(_GraphedSteps):
         recon, mu, logvar = netEG(data, eps2)
         # D three times on frozen weights -- on data as under no_grad (D fwd #3: BN statistics still update), on fake and
         # on recon, in that order: the big Linear layer reads its weight once for the three
-        f_data, f_fake, f_rec = netD.features_grouped([data, fake, recon], no_grad=(True, False, False))
+        # (augmented: data and recon, the pair Dis_l compares, under ONE parameter set -- sample by sample the same transform;
+        # the pixel MSE below stays on the images themselves)
+        f_data, f_fake, f_rec = netD.features_grouped([seen(data, aug, 2), seen(fake, aug, 3), seen(recon, aug, 2)],
+                                                      no_grad=(True, False, False))
         sim_real = f_data.squeeze()
         _, _, err_g_fake = netD.head_with_bce(f_fake, real_label, gb)
         _, sim_rec, err_g_rec = netD.head_with_bce(f_rec, real_label, gb)
@@ -1778,7 +1879,8 @@ class VAETrainer(_GraphedSteps):
     the checkpoint key is ``VAE_model_ema``.  ``tc_decomposition`` / ``dataset_size``: as there, of the step's KL term
     (`train_epoch` fills a ``dataset_size`` that was not given); replica-local under data parallelism.  ``dip_vae``: as
     there -- the covariance is that of this replica's batch.  ``mmd_vae``: as there -- ``prior`` is drawn after ``eps``.
-    ``kl_control``: as there -- the per-dimension sums are those of this replica's batch."""
+    ``kl_control``: as there -- the per-dimension sums are those of this replica's batch.  There is no discriminator, so a
+    ``diff_augment`` is a TypeError."""
 
     _parts = (_Part("model", VAE, "optimizer", "flat", "vae", "optimizer"),)
     _latents = ("eps",)
@@ -1789,11 +1891,13 @@ class VAETrainer(_GraphedSteps):
                  nonfinite_guard: Optional[bool] = None, max_grad_norm: Optional[float] = None,
                  skip_nonfinite: bool = False, lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0,
                  decoupled_weight_decay: bool = False, device_hyper: Optional[bool] = None, ema_decay=None,
-                 tc_decomposition=None, dataset_size: Optional[int] = None, dip_vae=None, mmd_vae=None, kl_control=None):
+                 tc_decomposition=None, dataset_size: Optional[int] = None, dip_vae=None, mmd_vae=None, kl_control=None,
+                 diff_augment=None):
         self.beta = float(beta)
         self._setup(device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
                     beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition,
-                    dataset_size, capturable=capturable, dip_vae=dip_vae, mmd_vae=mmd_vae, kl_control=kl_control)
+                    dataset_size, capturable=capturable, dip_vae=dip_vae, mmd_vae=mmd_vae, kl_control=kl_control,
+                    diff_augment=diff_augment)
 
     def step(self, data, eps=None, grad_hook=None, prior=None):
         """``grad_hook(phase, net)`` (tests): called with ``("VAE", model)`` right before the optimizer step; such an
@@ -1844,12 +1948,15 @@ class GANTrainer(_GraphedSteps):
     BetaVAEGANTrainer; so are ``max_grad_norm``, ``skip_nonfinite`` and the schedule arguments (``lr_scheduler``,
     ``weight_decay``, ``decoupled_weight_decay``, ``device_hyper``; there is no KL term, so a ``beta_schedule``, a
     ``tc_decomposition``, a ``dip_vae``, an ``mmd_vae`` or a ``kl_control`` is a TypeError).  ``ema_decay``: as BetaVAEGANTrainer, of the generator -- `ema_model` shadows `netG`, the checkpoint key is
-    ``netG_ema``; the discriminator is not averaged."""
+    ``netG_ema``; the discriminator is not averaged.  ``diff_augment``: as BetaVAEGANTrainer, with three parameter sets,
+    uniforms ``(3, B, 8)``: set 0 on ``data`` and set 1 on ``fake.detach()`` in the discriminator phase, set 2 on ``fake`` in
+    the generator phase."""
 
     _parts = (_Part("netG", Generator_celeba, "optimizerG", "flat_g", "g", "G_trainer"),
               _Part("netD", Discriminator_celeba, "optimizerD", "flat_d", "d", "D_trainer"))
     _latents = ("noise",)
     _has_labels = _accumulate = True              # (D runs twice before its backward, as BetaVAEGANTrainer's)
+    _augment_sets = 3         # D phase: data, fake.detach(); G phase: fake
     _ema_names = ("netG", "optimizerG", "netG_ema")
 
     def __init__(self, device="cuda", seed=999, lr=3e-3, opt: Optional[ModelOpt] = None, fused_adam: bool = True,
@@ -1857,23 +1964,27 @@ class GANTrainer(_GraphedSteps):
                  nonfinite_guard: Optional[bool] = None, max_grad_norm: Optional[float] = None,
                  skip_nonfinite: bool = False, lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0,
                  decoupled_weight_decay: bool = False, device_hyper: Optional[bool] = None, ema_decay=None,
-                 tc_decomposition=None, dataset_size: Optional[int] = None, dip_vae=None, mmd_vae=None, kl_control=None):
+                 tc_decomposition=None, dataset_size: Optional[int] = None, dip_vae=None, mmd_vae=None, kl_control=None,
+                 diff_augment=None):
         self._setup(device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
                     beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition,
-                    dataset_size, data_parallel, dip_vae=dip_vae, mmd_vae=mmd_vae, kl_control=kl_control)
+                    dataset_size, data_parallel, dip_vae=dip_vae, mmd_vae=mmd_vae, kl_control=kl_control,
+                    diff_augment=diff_augment)
 
     def step(self, data, noise=None, real_label=0.9, fake_label=0.1, global_batch: Optional[int] = None,
-             grad_hook=None):
-        return self._drive(data, (noise,), real_label, fake_label, global_batch, grad_hook)
+             grad_hook=None, augment=None):
+        """``augment`` (with ``diff_augment`` only): the iteration's three parameter sets, uniforms (3, B, 8); None is drawn."""
+        return self._drive(data, (noise,), real_label, fake_label, global_batch, grad_hook, augment)
 
     def _iteration(self, data, latents, labels, grad_hook, prepack, acc):
-        noise, = latents
+        noise, *aug = latents                 # (aug: the uniforms of diff_augment, else nothing)
+        aug, seen = (aug[0] if aug else None), self._augmented
         real_label, fake_label, gb = labels
         prepack()
         self._zero(self.netD, self.flat_d, self.optimizerD, grad_hook)
         fake = self.netG(noise)
         with F.deferred_wgrad():                             # as BetaVAEGANTrainer's discriminator phase
-            f_real, f_fake = self.netD.features_grouped([data, fake.detach()])
+            f_real, f_fake = self.netD.features_grouped([seen(data, aug, 0), seen(fake.detach(), aug, 1)])
             p_real, _, err_real = self.netD.head_with_bce(f_real, real_label, gb)
             p_fake, _, err_fake = self.netD.head_with_bce(f_fake, fake_label, gb)
             _backward([err_real, err_fake])
@@ -1886,7 +1997,7 @@ class GANTrainer(_GraphedSteps):
         acc.reset()
         self._zero(self.netG, self.flat_g, self.optimizerG, grad_hook)
         self._set_frozen(self.netD, True)
-        _, _, err_g = self.netD.forward_with_bce(fake, real_label, gb)
+        _, _, err_g = self.netD.forward_with_bce(seen(fake, aug, 2), real_label, gb)
         _backward([err_g])
         self._set_frozen(self.netD, False)
         self._exchange(self.flat_g)

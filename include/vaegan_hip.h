@@ -52,7 +52,8 @@ extern "C" {
  * csrc/reparam_tc.hip; vg_linear_wgrad_adam, vg_linear_wgrad_adam_dev; the five vg_reparam_dip_* of
  * csrc/reparam_dip.hip; the three vg_agg_posterior_* of csrc/agg_posterior.hip; the five vg_reparam_mmd_* of
  * csrc/reparam_mmd.hip; the four vg_pair_* of csrc/pair_dist.hip; the two vg_recon_quality* of
- * csrc/recon_quality.hip; the five vg_reparam_klc_* of csrc/reparam_klc.hip) change
+ * csrc/recon_quality.hip; the five vg_reparam_klc_* of csrc/reparam_klc.hip; the three vg_diff_augment_* of
+ * csrc/diff_augment.hip) change
  * nothing an existing caller sees and keep the version: a binding that needs them and finds a library without them
  * fails at the symbol lookup, as loudly. */
 #define VG_ABI_VERSION 7
@@ -656,6 +657,42 @@ int vg_pair_hits(const float* a, const float* b, const float* thr, int* count, i
 size_t vg_recon_quality_workspace_bytes(int B, int C, int H, int W, int window);
 int vg_recon_quality(const float* x, const float* y, double* out, int B, int C, int H, int W, int window, double sigma,
                      double data_range, double k1, double k2, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- differentiable augmentation of the discriminator's inputs (Zhao et al. 2020, "Differentiable Augmentation for
+ * Data-Efficient GAN Training"; the reference trains without one; csrc/diff_augment.hip).
+ * x, y, gy, gx: contiguous fp32 [B,C,H,W], the output never the input; u: fp32 [B,8], uniforms in [0, 1), one row per
+ * image; `policy`: a bit set of VG_AUGMENT_*, 1..7; p in [0, 1].  Per image, in this order:
+ *   colour       b = u0 - 1/2, s = 2 u1, c = u2 + 1/2:  x1 = x + b;  x2 = (x1 - mean_C x1) s + mean_C x1;
+ *                x3 = (x2 - m) c + m,  m = mean_CHW x2 = mean_CHW x + b
+ *   translation  r_h = int(H/8 + 1/2), t_r = min(floor(u3 (2 r_h + 1)), 2 r_h) - r_h, t_c alike from u4 and W:
+ *                y[c][i][j] = x3[c][i + t_r][j + t_c] inside the image, 0 outside
+ *   cutout       k_h = int(H/2 + 1/2), n_h = H + 1 - (k_h mod 2), o_r = min(floor(u5 n_h), n_h - 1): rows
+ *                o_r - floor(k_h/2) .. o_r - floor(k_h/2) + k_h - 1 are cut, columns alike from u6 and W; a position whose
+ *                row AND column are cut is 0 (on the translated image)
+ *   gate         the image is transformed iff u7 < p; otherwise its output is a bit copy of its input.
+ * Each floor takes ONE fp32 product.  The backward is the transpose of the linear part and reads gy and u alone:
+ *   g3 = gy masked and shifted back;  g2 = c g3 + (1 - c) mean_CHW g3;  gx = s g2 + (1 - s) mean_C g2;
+ * a closed image's gx is a bit copy of its gy.  Without VG_AUGMENT_COLOR: ONE launch each way, the outputs are copies and
+ * zeros (exact), no workspace is read (it may be NULL).  With it: TWO launches each way -- per (image, chunk of
+ * VG_DIFF_AUGMENT_SUM_CHUNK elements of the image's C H W) the chunk's sum in fp64 into the workspace slot [image][chunk],
+ * then the apply pass, where every thread adds its image's slots in index order; the colour arithmetic is fp32 (error
+ * per element <= ~30 * 2^-24 (max|x| + 1/2) forward, of max|gy| backward).  Masks are selects: what is dropped is 0
+ * whatever it held.  No floating-point atomic; the same bits every run and wherever in the batch an image stands; no host
+ * read, no allocation: capturable.  No bound of max |y| is emitted: the 3-channel convolutions that consume y take none.
+ * VG_ERR_BAD_ARG before any launch: a NULL x / u / y, y == x, B < 1, C outside 1..VG_DIFF_AUGMENT_MAX_CHANNELS, H or
+ * W < 2, C H W or a grid past 2^31 - 1, policy outside 1..7, p outside [0, 1] or NaN, and with VG_AUGMENT_COLOR a NULL
+ * or not 8-byte aligned workspace; the workspace query returns 0 for the rejected sizes.  `workspace` (with
+ * VG_AUGMENT_COLOR): vg_diff_augment_workspace_bytes(...) bytes; a shorter one is VG_ERR_WORKSPACE. */
+#define VG_AUGMENT_COLOR 1
+#define VG_AUGMENT_TRANSLATION 2
+#define VG_AUGMENT_CUTOUT 4
+#define VG_DIFF_AUGMENT_MAX_CHANNELS 4
+#define VG_DIFF_AUGMENT_SUM_CHUNK 4096
+size_t vg_diff_augment_workspace_bytes(int B, int C, int H, int W);
+int vg_diff_augment_fwd(const float* x, const float* u, float* y, int B, int C, int H, int W, int policy, float p,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int vg_diff_augment_bwd(const float* gy, const float* u, float* gx, int B, int C, int H, int W, int policy, float p,
+                        void* workspace, size_t workspace_bytes, void* stream);
 
 /* out[i] = g[i] * s[0] with s a DEVICE scalar: applies the upstream gradient of a
  * loss scalar to a gradient precomputed by the fused loss kernels, without a

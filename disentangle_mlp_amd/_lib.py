@@ -119,6 +119,13 @@ SIGNATURES = {
     "vg_reparam_klc_bwd": (_I, [_P, _P, _P, _P, _P, _P, _F, _F, _F, _P, _P, _I, _I, _P, _Z, _P]),
     "vg_reparam_klc_fwd_dev": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _F, _P, _Z, _P]),
     "vg_reparam_klc_bwd_dev": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _I, _I, _P, _Z, _P]),
+    "vg_permute_dims": (_I, [_P, _P, _P, _I, _I, _P]),
+    "vg_factor_tc_workspace_bytes": (_Z, [_I, _I]),
+    "vg_factor_tc_fwd": (_I, [_P, _P, _P, _I, _F, _F, _P, _Z, _P]),
+    "vg_factor_tc_bwd": (_I, [_P, _F, _F, _P, _P, _I, _P, _Z, _P]),
+    "vg_factor_tc_fwd_dev": (_I, [_P, _P, _P, _I, _P, _P, _P, _Z, _P]),
+    "vg_factor_tc_bwd_dev": (_I, [_P, _P, _P, _P, _P, _I, _P, _Z, _P]),
+    "vg_factor_critic_loss": (_I, [_P, _P, _P, _P, _I, _F, _P]),
     "vg_agg_posterior_splits": (_I, [_I, _I, _I, _I]),
     "vg_agg_posterior_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "vg_agg_posterior_lse": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),

@@ -676,6 +676,55 @@ class SqDiffLossFn(Function):
         return ops.scale_by_scalar(ga, gout.contiguous()), None, None
 
 
+class FactorTCFn(Function):
+    """The encoder phase's FactorVAE loss (Kim & Mnih 2018) from the critic's logits on z and the
+    unweighted KL scalar: ``loss = beta*kl + gamma*sum_b(l0 - l1)``, one launch each way.  Returns ``loss`` and the
+    non-differentiable ``[3]`` tensor ``(kl, tc, rows with l0 > l1)``.  ``beta`` / ``gamma``: both floats or both device
+    words (kept as the words themselves, as `ReparamKLFn`'s beta).  Gradient: ``+-gamma*gloss`` per row to the logits,
+    ``beta*gloss`` to the KL; an absent ``gloss`` gives none."""
+
+    @staticmethod
+    def forward(ctx, logits, kl, beta, gamma):
+        out4 = ops.factor_tc_fwd(logits, kl, beta, gamma)
+        ctx.beta, ctx.gamma = beta, gamma
+        loss, parts = out4[0], out4[1:]
+        ctx.mark_non_differentiable(parts)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(logits)
+        return loss, parts
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gloss, _):
+        if gloss is None:
+            return None, None, None, None
+        (logits,) = ctx.saved_tensors
+        glogits, gkl = ops.factor_tc_bwd(logits, gloss.contiguous(), ctx.beta, ctx.gamma)
+        return glogits, gkl, None, None
+
+
+class FactorCriticLossFn(Function):
+    """The critic phase's cross-entropy on the logits of ``[z; z_perm]``, forward and gradient in one launch (as
+    `SqDiffLossFn` / `BCELossFn`); ``divisor``: what the sum of the 2B terms is divided by.  Returns ``(loss, acc)``; ``acc``,
+    the fraction of the rows on the right side of 0, takes no gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, divisor):
+        loss, glogits, acc = ops.factor_critic_loss(logits, divisor, want_grad=True)
+        ctx.save_for_backward(glogits)
+        ctx.mark_non_differentiable(acc)
+        ctx.set_materialize_grads(False)
+        return loss, acc
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout, _):
+        if gout is None:
+            return None, None
+        (glogits,) = ctx.saved_tensors
+        return ops.scale_by_scalar(glogits, gout.contiguous()), None
+
+
 class BCELossFn(Function):
     """nn.BCELoss() vs a constant label (new_betavaegan.py:53,97,101); ``divisor`` is the
     batch the mean runs over (the global batch under data parallelism)."""
@@ -850,6 +899,26 @@ def reparam_klc_dims(mu, logvar, eps, beta, capacity=0.0, free_bits=0.0):
 def reparam_klc(mu, logvar, eps, beta, capacity=0.0, free_bits=0.0):
     """`reparam_klc_dims` without ``kl_dim``: ``(z, loss, parts)``, as the other objectives."""
     return reparam_klc_dims(mu, logvar, eps, beta, capacity, free_bits)[:3]
+
+
+def permute_dims(z, u):
+    """FactorVAE's ``permute_dims`` (`ops.permute_dims`): every column of ``z`` permuted across the batch by the stable argsort
+    of the same column of the uniforms ``u``.  A sample of the product of the marginals: no gradient flows (``z`` is taken
+    detached)."""
+    return ops.permute_dims(z.detach().contiguous(), u.contiguous())
+
+
+def factor_tc(logits, kl, beta, gamma):
+    """`FactorTCFn`: ``(loss, parts)`` with ``loss = beta*kl + gamma*tc``, ``tc = sum_b (l0 - l1)`` and ``parts = (kl, tc, rows
+    with l0 > l1)``.  ``logits``: the critic's [B, 2] on z; ``kl``: the unweighted KL scalar (``reparam_kl(..., 1.0)``); ``beta``
+    / ``gamma``: both floats or both device words."""
+    return FactorTCFn.apply(logits.contiguous(), kl, _beta_arg(beta), _beta_arg(gamma))
+
+
+def factor_critic_loss(logits, divisor=None):
+    """`FactorCriticLossFn`: ``(loss, acc)`` of the critic on the logits [2B, 2] of ``[z; z_perm]``; ``divisor``: default the
+    2B rows (a mean), twice the global batch under data parallelism."""
+    return FactorCriticLossFn.apply(logits.contiguous(), divisor)
 
 
 def kld_loss(mu, logvar, beta):

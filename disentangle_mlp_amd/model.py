@@ -187,6 +187,34 @@ class HipLinear(nn.Linear):
         return tF.linear(x, self.weight, self.bias)
 
 
+class LatentCritic(nn.Sequential):
+    """FactorVAE's critic on the latent code (Kim & Mnih 2018, their discriminator): ``depth`` blocks
+    of `HipLinear` + LeakyReLU(0.2), then ``HipLinear(width, 2)`` -- logit 0: "drawn from q(z)", logit 1: "dimensions permuted
+    across the batch".  The layers are small: their GEMMs stay on the vendor route, as every small Linear here does.  A
+    plain ``nn.Sequential``: the state_dict keys are ``0.weight``, ``0.bias``, ``2.weight``, ...  ``generator``: the weights are
+    drawn from it -- torch's Linear default, U(+-1/sqrt(fan_in)) for weight and bias -- and the global CPU stream is left as
+    it was (a trainer adds a critic without moving the other networks' weights); None: torch's own initialisation."""
+
+    def __init__(self, n_hidden, width=1000, depth=6, generator=None):
+        n_hidden, width, depth = int(n_hidden), int(width), int(depth)
+        if n_hidden < 1 or width < 1 or depth < 1:
+            raise ValueError(f"LatentCritic: n_hidden, width and depth must be >= 1, got {n_hidden}, {width}, {depth}")
+        with (torch.random.fork_rng(devices=[]) if generator is not None else contextlib.nullcontext()):
+            layers, fin = [], n_hidden
+            for _ in range(depth):
+                layers += [HipLinear(fin, width), HipLeakyReLU()]
+                fin = width
+            super().__init__(*layers, HipLinear(fin, 2))
+        self.n_hidden, self.width, self.depth = n_hidden, width, depth
+        if generator is not None:
+            with torch.no_grad():
+                for m in self:
+                    if isinstance(m, HipLinear):
+                        bound = m.in_features ** -0.5
+                        m.weight.uniform_(-bound, bound, generator=generator)
+                        m.bias.uniform_(-bound, bound, generator=generator)
+
+
 def _link_bn(layer, bn):
     """Tell a ``bn_shadowed`` layer which BatchNorm its output feeds.  A tuple, not the module: nothing is registered
     (no child module, no state_dict key), and a deep copy of the network links the copies."""
@@ -595,3 +623,17 @@ class VAE(nn.Module, _DecoderMixin):
         kl_floored, dims_above)``.  ``beta`` / ``capacity``: both floats or both one-element fp32 device tensors."""
         return self._forward_with_objective(
             x, eps, lambda mu, logvar, eps: F.reparam_klc(mu, logvar, eps, beta, capacity, free_bits))
+
+    def forward_with_factor(self, x, eps, beta, gamma, critic):
+        """`forward_with_kl` with FactorVAE's total-correlation estimate added (functional.factor_tc):
+        returns ``recon, mu, logvar, loss, parts, z`` -- ``loss = beta*kl + gamma*sum_b(l0 - l1)`` with ``(l0, l1) =
+        critic(z_b)``, ``parts`` the ``[3]`` tensor ``(kl, tc, rows with l0 > l1)``, and ``z`` DETACHED: what the critic's own
+        phase permutes and classifies, from this same forward.  The gradient reaches the encoder through ``critic``; whether
+        the critic's weights take one is the caller's business (a trainer freezes them here).  ``beta`` / ``gamma``: both
+        floats or both one-element fp32 device tensors."""
+        mu, logvar = self.encode(x)
+        if eps is None:
+            eps = torch.randn_like(mu)
+        z, kl = F.reparam_kl(mu, logvar, eps, 1.0)      # unweighted: `factor_tc` weighs it, and reports it as it is
+        loss, parts = F.factor_tc(critic(z), kl, beta, gamma)
+        return self.decode(z), mu, logvar, loss, parts, z.detach()

@@ -1528,6 +1528,79 @@ def reparam_klc_bwd(gz, mu, logvar, eps, gate, gloss, beta, capacity, free_bits)
     return gmu, glv
 
 
+PERMUTE_MAX_BATCH = 2048      # VG_PERMUTE_MAX_BATCH: the rows of a 16-column strip of fp32 that fit the CU's LDS (128 of 160 KiB)
+
+
+def permute_dims(z, u):
+    """``z_perm[i, d] = z[pi_d[i], d]`` with ``pi_d`` the stable ascending argsort of ``u[:, d]`` (vg_permute_dims, DESIGN.md
+    section 4.32): every column of ``z`` [B, D] permuted across the batch on its own, as ``z.gather(0, torch.argsort(u, dim=0,
+    stable=True))`` -- in one launch, the same bits every run.  ``u``: [B, D] fp32, U[0, 1) draws.  ``ValueError`` for a batch
+    above `PERMUTE_MAX_BATCH`.  Forward only."""
+    lib = _lib.load()
+    _req(z, "z"), _req(u, "u")
+    if z.dim() != 2 or u.shape != z.shape or z.numel() == 0:
+        raise RuntimeError(f"permute_dims: z and u must be [B, D] tensors of one shape, got {tuple(z.shape)} and {tuple(u.shape)}")
+    B, D = z.shape
+    if B > PERMUTE_MAX_BATCH:
+        raise ValueError(f"permute_dims: a batch of {B} is above {PERMUTE_MAX_BATCH}, the rows of a 16-column strip that fit "
+                         "the LDS of one compute unit")
+    z_perm = torch.empty_like(z)
+    check(lib.vg_permute_dims(z.data_ptr(), u.data_ptr(), z_perm.data_ptr(), B, D, _stream()), "vg_permute_dims")
+    return z_perm
+
+
+def _req_logits(logits, name):
+    _req(logits, name)
+    if logits.dim() != 2 or logits.shape[1] != 2 or logits.shape[0] < 1:
+        raise RuntimeError(f"{name}: expected the critic's [rows, 2] logits, got {tuple(logits.shape)}")
+    return logits
+
+
+def factor_tc_fwd(logits, kl, beta, gamma):
+    """The encoder phase's FactorVAE loss (vg_factor_tc_fwd) from the critic's ``logits`` [B, 2] on z and
+    ``kl``, the 0-dim device tensor of the unweighted KL: ``out4 = [beta * kl + gamma * tc, kl, tc, rows with l0 > l1]``, ``tc =
+    sum_b (l0 - l1)``.  ``beta`` and ``gamma``: both floats, or both one-element fp32 device words read by the kernel."""
+    lib = _lib.load()
+    _req_logits(logits, "logits"), _req(kl, "kl")
+    if kl.numel() != 1:
+        raise RuntimeError("factor_tc: kl is the one-element tensor of the KL summed over the batch")
+    out4 = torch.empty(4, dtype=torch.float32, device=logits.device)
+    head = (logits.data_ptr(), kl.data_ptr(), out4.data_ptr(), logits.shape[0])
+    _objective_launch(lib.vg_factor_tc_workspace_bytes, lib.vg_factor_tc_fwd, lib.vg_factor_tc_fwd_dev, logits, head, beta, (),
+                      second=("gamma", gamma))
+    return out4
+
+
+def factor_tc_bwd(logits, gloss, beta, gamma):
+    """``(glogits, gkl)`` of `factor_tc_fwd`: the constant ``+-gamma * gloss`` per row and ``beta * gloss``.  ``logits`` gives the
+    shape; ``gloss``: 0-dim device tensor, the upstream gradient of ``out4[0]``."""
+    lib = _lib.load()
+    _req_logits(logits, "logits"), _req(gloss, "gloss")
+    glogits = torch.empty_like(logits)
+    gkl = torch.empty((), dtype=torch.float32, device=logits.device)
+    _objective_launch(lib.vg_factor_tc_workspace_bytes, lib.vg_factor_tc_bwd, lib.vg_factor_tc_bwd_dev, logits,
+                      (gloss.data_ptr(),), beta, (glogits.data_ptr(), gkl.data_ptr(), logits.shape[0]), second=("gamma", gamma))
+    return glogits, gkl
+
+
+def factor_critic_loss(logits, divisor=None, want_grad=True):
+    """The critic phase's cross-entropy (vg_factor_critic_loss) on ``logits`` [2B, 2] -- the first B rows
+    are z (class 0), the last B permuted (class 1): ``(loss, glogits, acc)`` with ``loss = sum softplus(other - own) / divisor``
+    (default: the 2B rows, a mean), its gradient (None without ``want_grad``) and the fraction of the rows on the right side
+    of 0 (a tie is wrong), in one launch."""
+    lib = _lib.load()
+    _req_logits(logits, "logits")
+    rows = logits.shape[0]
+    if rows % 2:
+        raise RuntimeError(f"factor_critic_loss: the rows are [z; z_perm], an even number, got {rows}")
+    loss = torch.empty((), dtype=torch.float32, device=logits.device)
+    acc = torch.empty((), dtype=torch.float32, device=logits.device)
+    glogits = torch.empty_like(logits) if want_grad else None
+    check(lib.vg_factor_critic_loss(logits.data_ptr(), loss.data_ptr(), _ptr(glogits), acc.data_ptr(), rows // 2,
+                                    float(divisor if divisor is not None else rows), _stream()), "vg_factor_critic_loss")
+    return loss, glogits, acc
+
+
 def sqdiff_loss(a, b, scale, gscale=1.0, want_grad=True):
     lib = _lib.load()
     _req(a, "a"), _req(b, "b")

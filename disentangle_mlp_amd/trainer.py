@@ -43,7 +43,7 @@ from . import functional as F
 from . import model as _model
 from . import ops
 from .optim import HipAdam, NONFINITE_GRAD, NONFINITE_PARAM, isfinite_bits
-from .model import VAE, Discriminator_celeba, Generator_celeba, weights_init, shadowed_bias_params
+from .model import VAE, Discriminator_celeba, Generator_celeba, LatentCritic, weights_init, shadowed_bias_params
 
 
 @dataclass
@@ -260,7 +260,7 @@ def _backward(losses):
 
 
 def _make_adam(params, lr, fused, capturable=False, nonfinite_guard=False, max_grad_norm=None, skip_nonfinite=False,
-               weight_decay=0.0, decoupled_weight_decay=False, device_hyper=False, ema=None):
+               weight_decay=0.0, decoupled_weight_decay=False, device_hyper=False, ema=None, betas=None):
     """Adam with the reference's defaults (new_betavaegan.py:49-50).  On the GPU the step runs on the
     hand-written kernel (optim.HipAdam, a torch.optim.Adam subclass: identical state_dict); ``capturable``:
     its scalars are formed on the device so that a whole iteration can be captured in a HIP graph;
@@ -270,8 +270,10 @@ def _make_adam(params, lr, fused, capturable=False, nonfinite_guard=False, max_g
     ``weight_decay`` / ``decoupled_weight_decay``: torch.optim.Adam's, inside the fused step on the GPU; ``device_hyper``:
     lr and weight decay in device words a captured step reads (optim.HipAdam).  ``ema``: ``(decay, targets)`` of the one
     optimizer whose step keeps the weight EMA (`_GraphedSteps._ema_setup`) -- a HipAdam with device scalars and the decay
-    in a device word, whether or not the iteration is captured."""
+    in a device word, whether or not the iteration is captured.  ``betas``: Adam's pair, None for torch's default."""
     decay = dict(weight_decay=weight_decay, decoupled_weight_decay=decoupled_weight_decay)
+    if betas is not None:
+        decay["betas"] = betas
     if ema is not None:
         return HipAdam(params, lr=lr, capturable=True, nonfinite_guard=nonfinite_guard, max_grad_norm=max_grad_norm,
                        skip_nonfinite=skip_nonfinite, device_hyper=device_hyper, ema_decay=ema[0], ema_targets=ema[1],
@@ -308,6 +310,23 @@ def _augment_generator(device, seed, rank):
     one is -- apart from it, so that the latents are bit for bit what they are without the option."""
     g = torch.Generator(device=device)
     g.manual_seed(int(seed) + (1 << 32) + int(rank))      # (far from every rank's latent seed, seed + 1 + rank)
+    return g
+
+
+def _permute_generator(device, seed, rank):
+    """Generator of the uniforms of ``factor_vae``'s ``permute_dims``: a third stream per replica, seeded from (seed, rank)
+    apart from the latent and the augmentation ones -- both are bit for bit what they are without the option."""
+    g = torch.Generator(device=device)
+    g.manual_seed(int(seed) + (2 << 32) + int(rank))
+    return g
+
+
+def _owned_generator(seed):
+    """CPU generator of the initial weights of a network an objective owns (``factor_vae``'s critic): seeded from ``seed``
+    alone, so every rank draws the same weights, and not the global CPU stream, so the trainer's other networks -- built
+    right behind ``torch.manual_seed(seed)`` -- are what they are without the option."""
+    g = torch.Generator()
+    g.manual_seed(int(seed) + (3 << 32))
     return g
 
 
@@ -528,6 +547,20 @@ class _Objective(NamedTuple):
     word: Optional[str] = None            # its OWN scheduled value: the name it goes by.  `parse` returns it FIRST (a float, or a
     #                                       callable iteration -> float); it is no frozen argument -- `forward` gets it first among
     #                                       ``args`` as a float, or under ``device_hyper`` as a device word beside beta's
+    owns: Optional["_Owned"] = None       # a network of its own with an optimizer, inputs and a phase:
+    #                                       `forward` gets the network LAST among ``args`` and may return more than five values --
+    #                                       what is behind ``parts`` is carried to the phase
+
+
+class _Owned(NamedTuple):
+    """The network an objective owns, and all a trainer needs to carry it: one more `_Part` (present only with the keyword),
+    its construction, its optimizer's own arguments, the inputs its phase draws and the phase itself."""
+    part: _Part               # network, optimizer, exchange, pack-plan name, checkpoint key of the optimizer
+    ckpt: str                 # checkpoint key of the network's state_dict
+    build: Callable           # (ModelOpt, the frozen arguments, a CPU generator) -> the network, on the CPU
+    adam: Callable            # the frozen arguments -> dict(lr=, betas=) of its optimizer
+    drawn: tuple              # the `_Drawn` inputs of its phase, last in draw order (behind ``augment``)
+    phase: Callable           # (trainer, what `forward` carried, the drawn tensors, global batch, grad_hook) -> loss outputs
 
 
 def _parse_tc(tc_decomposition, opt):
@@ -598,6 +631,70 @@ def _parse_klc(kl_control, opt):
     return capacity, _nonneg("kl_control: free_bits", free_bits)
 
 
+FACTOR_CRITIC_DEFAULTS = dict(width=1000, depth=6, lr=1e-4, betas=(0.5, 0.9))      # Kim & Mnih 2018, their discriminator
+
+
+def _parse_factor(factor_vae, opt):
+    """``factor_vae=gamma`` or ``(gamma, dict(width=, depth=, lr=, betas=))``: the weight of the total-correlation estimate -- a
+    float or a callable iteration -> float --, and the critic and its Adam (`FACTOR_CRITIC_DEFAULTS`)."""
+    gamma, given = factor_vae, {}
+    if isinstance(factor_vae, (tuple, list)):
+        try:
+            gamma, given = factor_vae
+        except ValueError:
+            raise TypeError(f"factor_vae must be gamma or a pair (gamma, dict of critic options), got {factor_vae!r}") from None
+    if not isinstance(given, dict) or set(given) - set(FACTOR_CRITIC_DEFAULTS):
+        raise TypeError(f"factor_vae: the critic's options are a dict with keys among {sorted(FACTOR_CRITIC_DEFAULTS)}, got "
+                        f"{given!r}")
+    if not callable(gamma):
+        gamma = _nonneg("factor_vae: gamma", gamma)
+    cfg = {**FACTOR_CRITIC_DEFAULTS, **given}
+    sizes = []
+    for name in ("width", "depth"):
+        v = cfg[name]
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"factor_vae: {name} must be an integer, got {v!r}")
+        if v < 1:
+            raise ValueError(f"factor_vae: {name} must be >= 1, got {v!r}")
+        sizes.append(int(v))
+    try:
+        lr = float(cfg["lr"])
+        b1, b2 = (float(b) for b in cfg["betas"])
+    except (TypeError, ValueError):
+        raise TypeError(f"factor_vae: lr must be a number and betas a pair of numbers, got {cfg['lr']!r} and {cfg['betas']!r}") from None
+    if not (np.isfinite(lr) and lr > 0.0):
+        raise ValueError(f"factor_vae: lr must be finite and > 0, got {cfg['lr']!r}")
+    if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):      # (NaN fails the comparisons)
+        raise ValueError(f"factor_vae: betas must lie in [0, 1), got {cfg['betas']!r}")
+    return gamma, sizes[0], sizes[1], lr, (b1, b2)
+
+
+def _factor_critic_phase(trainer, carried, drawn, global_batch, grad_hook):
+    """FactorVAE's critic phase, last in the iteration (Kim & Mnih 2018, algorithm 2): ``carried`` is
+    the encoder phase's z, detached -- no second encode --, ``drawn`` the uniforms of ``permute_dims``.  One critic forward on
+    the 2B rows ``[z; z_perm]``, the cross-entropy as a mean over 2 x the global batch, full backward, exchange, Adam step."""
+    (z,), (u,) = carried, drawn
+    o = trainer._objective[0].owns.part
+    critic, opt, flat = (getattr(trainer, a) for a in (o.net, o.opt, o.flat))
+    trainer._zero(critic, flat, None, grad_hook)      # (no weight of it is updated inside the backward: its layers are small)
+    logits = critic(torch.cat([z, F.permute_dims(z, u)]))
+    loss, acc = F.factor_critic_loss(logits, 2 * global_batch)
+    _backward([loss])
+    trainer._exchange(flat)
+    if grad_hook:
+        grad_hook("critic", critic)
+    opt.step()
+    return dict(critic_loss=loss.detach(), critic_acc=acc)
+
+
+_FACTOR_CRITIC = _Owned(
+    _Part("critic", LatentCritic, "optimizer_critic", "flat_critic", "critic", "latent_critic_optimizer"), "latent_critic",
+    build=lambda opt, args, generator: LatentCritic(opt.n_hidden, args[0], args[1], generator=generator),
+    adam=lambda args: dict(lr=args[2], betas=args[3]),
+    drawn=(_Drawn("permute", "uniform", "permute_generator"),),
+    phase=_factor_critic_phase)
+
+
 # The table: the methods are looked up on the network when called (a test may replace one).
 _OBJECTIVES = (
     _Objective("tc_decomposition", _parse_tc,       # args: (alpha, gamma, dataset_size); `beta` weighs the total correlation
@@ -612,6 +709,9 @@ _OBJECTIVES = (
     _Objective("kl_control", _parse_klc,            # args: (capacity: its word, free_bits); `beta` weighs |kl_floored - B capacity|
                lambda net, data, eps, beta, args, prior: net.forward_with_klc(data, eps, beta, *args),
                ("kl", "kl_floored", "dims_above"), word="capacity"),
+    _Objective("factor_vae", _parse_factor,         # args: (gamma: its word, width, depth, lr, betas, the critic); `beta` weighs the KL
+               lambda net, data, eps, beta, args, prior: net.forward_with_factor(data, eps, beta, args[0], args[-1]),
+               ("kl", "tc"), word="gamma", owns=_FACTOR_CRITIC),
 )
 
 
@@ -638,7 +738,8 @@ class _GraphedSteps:
 
     def _setup(self, device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
                beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition, dataset_size,
-               data_parallel=None, capturable=None, dip_vae=None, mmd_vae=None, kl_control=None, diff_augment=None):
+               data_parallel=None, capturable=None, dip_vae=None, mmd_vae=None, kl_control=None, diff_augment=None,
+               factor_vae=None):
         """The constructor body of every trainer (new_betavaegan.py:36-53, new_vae.py:33-37, new_gan.py:47-61).  A trainer
         with a KL term has set `beta` before."""
         has_beta = hasattr(self, "beta")
@@ -647,8 +748,8 @@ class _GraphedSteps:
         self._single_use = {}     # (id(network), DEFER_WGRAD) -> its weights that may be updated inside the backward
         on_gpu = self.device.type == "cuda"
         _use_tuned_gemms(self.device)
-        self._select_objective(dict(tc_decomposition=tc_decomposition, dip_vae=dip_vae, mmd_vae=mmd_vae, kl_control=kl_control),
-                               dataset_size, has_beta)
+        self._select_objective(dict(tc_decomposition=tc_decomposition, dip_vae=dip_vae, mmd_vae=mmd_vae, kl_control=kl_control,
+                                    factor_vae=factor_vae), dataset_size, has_beta)
         if diff_augment is not None:
             if not self._augment_sets:
                 raise TypeError(f"{type(self).__name__} has no discriminator: diff_augment does not apply")
@@ -678,17 +779,84 @@ class _GraphedSteps:
             setattr(self, p.opt, _make_adam(getattr(self, p.net).parameters(), lr, fused, capturable, self.nonfinite_guard,
                                             ema=ema if p.opt == self._ema_names[1] else None, **adam))
         self._make_schedulers()
+        self._own_network(seed, fused, capturable, adam)          # (behind the schedulers: its optimizer has none)
         for p in self._parts:         # in table order on every rank: creating the communicator is collective
             net = getattr(self, p.net)
             setattr(self, p.flat, FlatGrads(net.parameters(), silent=shadowed_bias_params(net)) if self.dp else None)
         self.latent_generator = _latent_generator(self.device, seed, self.rank)
         if self._augment is not None:
             self.augment_generator = _augment_generator(self.device, seed, self.rank)
+        if self._owned is not None and self._owned.drawn:
+            self.permute_generator = _permute_generator(self.device, seed, self.rank)
         if self._has_labels:
             self.label_rng = _shared_label_rng(seed)      # used by train_epoch when world > 1: one draw per GLOBAL batch
         for net in self._nets():
             net.train()
         self.iteration = 0
+
+    # ---- a network the selected objective owns (`_Owned`) ----------------------------------------
+    @property
+    def _owned(self):
+        return self._objective[0].owns if self._objective is not None else None
+
+    def _own_network(self, seed, fused, capturable, adam):
+        """`_setup`: build the network the objective owns from a generator of the trainer's own (the global CPU stream, and
+        with it every other network's weights, stays what it is without the keyword), give it its optimizer -- the same
+        guard, clipping, skipping and device words as the others; its own lr and betas; no scheduler, weight decay or EMA --
+        and append its `_Part` to this trainer's table: from here on everything that lists networks, optimizers or
+        exchanges finds it."""
+        owned = self._owned
+        if owned is None:
+            return
+        args = self._objective[1]
+        net = owned.build(self.opt, args, _owned_generator(seed))
+        setattr(self, owned.part.net, net.to(self.device))
+        own = dict(adam, weight_decay=0.0, decoupled_weight_decay=False, **owned.adam(args))
+        setattr(self, owned.part.opt, _make_adam(net.parameters(), own.pop("lr"), fused, capturable, self.nonfinite_guard, **own))
+        self._parts = (*type(self)._parts, owned.part)
+
+    def _owned_checkpoint(self):
+        """The additional checkpoint keys -- present only with an objective that owns a network: its weights, its optimizer."""
+        owned = self._owned
+        if owned is None:
+            return {}
+        return {owned.ckpt: getattr(self, owned.part.net).state_dict(), owned.part.ckpt: getattr(self, owned.part.opt).state_dict()}
+
+    @torch.no_grad()
+    def _owned_restore(self, ck, in_place=False):
+        """After the trainer's own networks were loaded: the owned network and its optimizer from their checkpoint keys -- a
+        checkpoint without them (one written without the keyword) leaves both as they are, as a missing EMA key does.
+        ``in_place``: copied into the existing tensors (`load_in_place`)."""
+        owned = self._owned
+        if owned is None or owned.ckpt not in ck or owned.part.ckpt not in ck:
+            return
+        net, opt = getattr(self, owned.part.net), getattr(self, owned.part.opt)
+        if not in_place:
+            net.load_state_dict(ck[owned.ckpt])
+            opt.load_state_dict(ck[owned.part.ckpt])
+            return
+        for k, v in net.state_dict().items():
+            v.copy_(ck[owned.ckpt][k])
+        if isinstance(opt, HipAdam):
+            opt.load_state_in_place(ck[owned.part.ckpt])
+            opt.refresh_weight_bounds()
+        else:
+            opt.load_state_dict(ck[owned.part.ckpt])
+
+    def _split_owned(self, latents):
+        """`_iteration`: its inputs without those of the owned network's phase (last in `_drawn` order), and those."""
+        n = len(self._owned.drawn) if self._owned is not None else 0
+        return (latents[:len(latents) - n], tuple(latents[len(latents) - n:])) if n else (latents, ())
+
+    def _owned_phase(self, drawn, batch, global_batch, grad_hook):
+        """The phase of the owned network, behind the encoder phase's optimizer step: its loss outputs ({} without one).
+        ``global_batch``: what `step` was given, else this replica's batch times the world size."""
+        owned = self._owned
+        if owned is None:
+            return {}
+        carried, self._carried = self._carried, ()
+        gb = global_batch if global_batch is not None else batch * self.world
+        return owned.phase(self, carried, drawn, gb, grad_hook)
 
     # ---- the table of parts, read ------------------------------------------------------------------------------------
     def _nets(self):
@@ -895,6 +1063,7 @@ class _GraphedSteps:
     _word_schedule = None     # callable iteration -> that value, or None (a constant, or set by hand)
     _word_dev = None          # with device_hyper: the persistent fp32 word the objective's kernels read
     _word_written = None
+    _carried = ()             # what the objective's forward returned behind ``parts``: for the owned network's phase
 
     def _select_objective(self, given, dataset_size, has_beta=True):
         """A trainer's constructor: ``given`` maps every keyword of the table to its value; at most one is not None.  The
@@ -947,7 +1116,19 @@ class _GraphedSteps:
         args = self._objective_key()[1]
         if self._word is not None:
             args = (self._word_dev if self._word_dev is not None else self._word, *args)
-        return self._objective[0].forward(net, data, eps, self._kl_beta(), args, prior)
+        owned = self._owned
+        if owned is None:
+            return self._objective[0].forward(net, data, eps, self._kl_beta(), args, prior)
+        # the owned network only relays gradients here, as the discriminator in the decoder phase: no weight gradients are
+        # formed for it (what requires a gradient is decided when the forward builds its graph)
+        own = getattr(self, owned.part.net)
+        self._set_frozen(own, True)
+        try:
+            out = self._objective[0].forward(net, data, eps, self._kl_beta(), (*args, own), prior)
+        finally:
+            self._set_frozen(own, False)
+        self._carried = tuple(out[5:])
+        return out[:5]
 
     def _with_prior(self, given, prior):
         """`step`'s latents in `_latents` order: behind the trainer's own, the prior's draw (or None: drawn) of an objective
@@ -1003,6 +1184,25 @@ class _GraphedSteps:
         """``(capacity, free_bits)`` as they are now (read-only); None when the option is off."""
         return None if self.capacity is None else (self._word, *self._objective[1])
 
+    @property
+    def gamma(self):
+        """The weight of ``factor_vae``'s total-correlation estimate this step runs (ran) with; None without the option."""
+        return self._word if self._objective and self._objective[0].word == "gamma" else None
+
+    def set_gamma(self, value):
+        """Set that weight by hand (a schedule, if any, overwrites it at the start of the next step).  With ``device_hyper``
+        the next step picks it up without a new capture."""
+        if self.gamma is None:
+            raise TypeError(f"{type(self).__name__}: construct with factor_vae=... to have a total-correlation weight")
+        self._word = self._word_checked(value)
+
+    @property
+    def factor_vae(self):
+        """``(gamma, dict(width=, depth=, lr=, betas=))`` as they are now (read-only); None when the option is off."""
+        if self.gamma is None:
+            return None
+        return self._word, dict(zip(FACTOR_CRITIC_DEFAULTS, self._objective[1]))
+
     def _begin_step(self):
         if self._dataset_size_missing():
             raise ValueError(f"{type(self).__name__}: {self._objective[0].keyword} needs dataset_size (the number of training "
@@ -1027,8 +1227,9 @@ class _GraphedSteps:
         opts = self._optimizers()
         if which is not None and which not in opts:
             raise KeyError(f"no optimizer {which!r}: {sorted(opts)}")
+        owned = self._owned.part.opt if self._owned is not None else None      # (its own lr: set only when named)
         for name, opt in opts.items():
-            if which is None or name == which:
+            if (which is None and name != owned) or name == which:
                 for group in opt.param_groups:
                     group["lr"] = float(value)
 
@@ -1059,6 +1260,8 @@ class _GraphedSteps:
                 self.lr_schedulers[name].load_state_dict(sd)
         if in_place and "lr_schedulers" in ck:
             for name, key in self._checkpoint_optimizer_keys.items():
+                if self._owned is not None and name == self._owned.part.opt:      # (no scheduler; its key may be absent)
+                    continue
                 for group, saved in zip(getattr(self, name).param_groups, ck[key]["param_groups"]):
                     group["lr"] = saved["lr"]
         if self.beta_schedule is not None and "iteration" in ck:
@@ -1259,6 +1462,8 @@ class _GraphedSteps:
         drawn = [_Drawn(name, "normal", "latent_generator") for name in self._latents]
         if self._augment is not None:
             drawn.append(_Drawn("augment", "uniform", "augment_generator"))
+        if self._owned is not None:      # (``factor_vae``: ``permute``, U[0,1) of shape (batch, n_hidden) from the permutation stream)
+            drawn.extend(self._owned.drawn)
         return drawn
 
     def _draw(self, given, batch, cap=None):
@@ -1268,7 +1473,7 @@ class _GraphedSteps:
         out = []
         for d, t in zip(self._drawn(), given):
             if t is None and cap is None:
-                t = self.draw_latents(batch) if d.dist == "normal" else self.draw_augment(batch)
+                t = self.draw_latents(batch) if d.dist == "normal" else getattr(self, f"draw_{d.name}")(batch)
             elif t is None:
                 g = getattr(self, d.generator)
                 t = cap.inputs[d.name].normal_(generator=g) if d.dist == "normal" else cap.inputs[d.name].uniform_(generator=g)
@@ -1287,6 +1492,26 @@ class _GraphedSteps:
             raise ValueError(f"{type(self).__name__}.step: augment must be a float32 tensor of shape {shape} on {self.device}, "
                              f"got {tuple(augment.shape)} {augment.dtype} on {augment.device}")
         return (*given, augment)
+
+    def draw_permute(self, batch):
+        """One iteration's uniforms of ``factor_vae``'s ``permute_dims``, [batch, n_hidden], from this replica's permutation
+        stream."""
+        if self.gamma is None:
+            raise TypeError(f"{type(self).__name__}: construct with factor_vae=... to draw its uniforms")
+        return torch.rand(batch, self.opt.n_hidden, device=self.device, generator=self.permute_generator)
+
+    def _with_permute(self, given, permute, batch):
+        """`step`'s random inputs in `_drawn` order: behind ``augment``, the caller's ``permute`` (or None: drawn)."""
+        if self.gamma is None:
+            if permute is not None:
+                raise TypeError(f"{type(self).__name__}.step: permute= belongs to factor_vae, which is off")
+            return given
+        shape = (batch, self.opt.n_hidden)
+        if permute is not None and (tuple(permute.shape) != shape or permute.dtype != torch.float32
+                                    or permute.device.type != self.device.type):
+            raise ValueError(f"{type(self).__name__}.step: permute must be a float32 tensor of shape {shape} on {self.device}, "
+                             f"got {tuple(permute.shape)} {permute.dtype} on {permute.device}")
+        return (*given, permute)
 
     def _augmented(self, x, augment, k):
         """``x`` as the discriminator sees it: through parameter set ``k`` of ``augment``, or as it is without the option."""
@@ -1353,12 +1578,13 @@ class _GraphedSteps:
                              *(() if self._word is None else (self._word,))),
                 ops.CONV_ARITH, tuple(o.state_generation for o in opts), self._host_state_key())
 
-    def _drive(self, data, given, real_label=None, fake_label=None, global_batch=None, grad_hook=None, augment=None):
+    def _drive(self, data, given, real_label=None, fake_label=None, global_batch=None, grad_hook=None, augment=None,
+               permute=None):
         """One iteration from `_begin_step` to `_end_step`.  ``given``: the caller's latents in `_latents` order, None
         where the trainer is to draw.  Eager -- or, `_graph_usable`: the first GRAPH_WARM_STEPS iterations of a capture
         key eager (workspaces, packs, GEMM plans exist then), the next one captured and replayed, later ones replayed;
         and eager for good after a failed capture."""
-        given = self._with_augment(given, augment, data.size(0))
+        given = self._with_permute(self._with_augment(given, augment, data.size(0)), permute, data.size(0))
         self._begin_step()
         batch, labels = data.size(0), None
         if self._has_labels:
@@ -1503,7 +1729,27 @@ class BetaVAEGANTrainer(_GraphedSteps):
     stream of the trainer's own seeded from (seed, rank), drawn after the iteration's latents -- the latent stream is bit
     for bit what it is without the option -- and straight into a static input of the capture: a fresh draw every iteration
     replays ONE graph.  `step(augment=)` takes them from the caller, `draw_augment` draws a set.  No checkpoint key.  Data
-    parallel: replica-local, each rank its own stream, as the latents are."""
+    parallel: replica-local, each rank its own stream, as the latents are.
+
+    ``factor_vae=gamma`` or ``(gamma, dict(width=1000, depth=6, lr=1e-4, betas=(0.5, 0.9)))`` (default: none -- then every
+    launch, capture key, checkpoint key, latent draw, initial weight and bit is what it was): FactorVAE (Kim & Mnih 2018,
+    disentanglement_lib's form).  The trainer owns one more network, `critic`
+    (`model.LatentCritic`: two logits per code, "drawn from q(z)" / "dimensions permuted across the batch"), with its own
+    `optimizer_critic`.  Phase 3 minimises ``beta * kl + gamma * sum_b (l0(z_b) - l1(z_b))`` (`VAE.forward_with_factor`); the
+    critic only relays gradients there.  A fourth phase, last in the iteration, trains the critic on ``z.detach()`` of that
+    same forward and on ``permute_dims(z, u)``: one forward on the 2B rows, the cross-entropy as a mean over 2 x the global
+    batch, full backward, exchange, Adam step.  ``gamma``: a float >= 0 or a callable ``iteration -> float``; `gamma` reads
+    it, `set_gamma` sets it by hand; with ``device_hyper`` -- on by default also when gamma is a callable -- it lives in a
+    device word beside beta's, so an annealed gamma still replays ONE graph.  `beta` stays the trainer's own.  The critic's
+    initial weights come from a generator of the trainer's own seeded from ``seed`` (alike on every rank; the global CPU
+    stream and the other networks' weights are untouched); its optimizer gets the same guard, clipping and device words as
+    the others, its own ``lr`` / ``betas``, and no scheduler, weight decay or EMA (`set_lr` leaves it alone unless named).
+    The uniforms ``(B, n_hidden)`` of the permutation come from `permute_generator`, a third stream per replica, drawn last,
+    straight into a static input of the capture; `step(permute=)` takes them from the caller, `draw_permute` draws a set; B
+    <= 2048.  ``kld`` of the returned dict is the weighted loss; ``kl``, ``tc`` (unweighted), ``critic_loss`` and
+    ``critic_acc`` are added.  Checkpoints gain ``latent_critic`` and ``latent_critic_optimizer``; one without them loads
+    and leaves a fresh critic.  Together with another objective keyword it is a ValueError.  Data parallel: the critic's
+    gradients are exchanged through a `FlatGrads` of its own; the permutation is across this replica's batch."""
 
     _parts = (_Part("netEG", VAE, "optimizerEG", "flat_eg", "eg", "encoder_decoder_optimizer"),              # :41, :49
               _Part("netD", Discriminator_celeba, "optimizerD", "flat_d", "d", "discriminator_optimizer"))    # :43, :50
@@ -1518,31 +1764,35 @@ class BetaVAEGANTrainer(_GraphedSteps):
                  max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False,
                  lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0, decoupled_weight_decay: bool = False,
                  device_hyper: Optional[bool] = None, ema_decay=None, tc_decomposition=None,
-                 dataset_size: Optional[int] = None, dip_vae=None, mmd_vae=None, kl_control=None, diff_augment=None):
+                 dataset_size: Optional[int] = None, dip_vae=None, mmd_vae=None, kl_control=None, diff_augment=None,
+                 factor_vae=None):
         self.beta = float(beta)
         self._setup(device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
                     beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition,
                     dataset_size, data_parallel, capturable, dip_vae, mmd_vae, kl_control,      # (lr: hard-coded 1e-3 at new_betavaegan.py:49-50)
-                    diff_augment)
+                    diff_augment, factor_vae)
         self._eg_params = [p for p in self.netEG.parameters() if p.dim() == 4]   # convolution filters
         self._d_params = [p for p in self.netD.parameters() if p.dim() == 4]
 
     # -- one iteration ------------------------------------------------------------
     def step(self, data, noise=None, eps2=None, eps3=None, real_label=0.9, fake_label=0.1,
-             global_batch: Optional[int] = None, grad_hook=None, prior=None, augment=None) -> Dict[str, torch.Tensor]:
+             global_batch: Optional[int] = None, grad_hook=None, prior=None, augment=None,
+             permute=None) -> Dict[str, torch.Tensor]:
         """One iteration; returns the nine loss scalars as device tensors (no host sync).  From the third iteration of a
         batch shape on the iteration is a HIP-graph replay and the returned tensors are the capture's STATIC outputs: the
         next replay overwrites them -- ``.clone()`` (or ``float()``) what is kept across steps.
         ``prior`` (with ``mmd_vae`` only): phase 3's draws from the prior, (B, n_hidden); None is drawn, after ``eps3``.
         ``augment`` (with ``diff_augment`` only): the iteration's four parameter sets, uniforms (4, B, 8); None is drawn,
-        after the latents, from the augmentation stream (`draw_augment`)."""
+        after the latents, from the augmentation stream (`draw_augment`).  ``permute`` (with ``factor_vae`` only): the uniforms
+        of ``permute_dims``, (B, n_hidden); None is drawn, last, from the permutation stream (`draw_permute`)."""
         return self._drive(data, self._with_prior((noise, eps2, eps3), prior), real_label, fake_label, global_batch, grad_hook,
-                           augment)
+                           augment, permute)
 
     def _iteration(self, data, latents, labels, grad_hook, prepack, acc):
         """data (B,3,64,64) in [-1,1]; noise / eps2 / eps3 (B, n_hidden) ~ N(0,1) (new_betavaegan.py:111, model.py:534);
         the labels are the per-iteration scalars of :89-90."""
         netEG, netD = self.netEG, self.netD
+        latents, own = self._split_owned(latents)            # (the inputs of an owned network's phase: behind everything else)
         *latents, aug = latents if self._augment is not None else (*latents, None)      # (the uniforms of diff_augment: last)
         noise, eps2, eps3, *prior = latents                  # (prior: one more draw with an objective that takes it, else nothing)
         seen = self._augmented                               # what the discriminator sees of an image batch (DESIGN.md 4.31)
@@ -1612,6 +1862,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
         self.optimizerEG.step()
         ops.invalidate_packed_filters(self._eg_params)
         out.update(kld=kld.detach(), mse_enc=mse3.detach(), **self._kl_part_outputs(parts))
+        out.update(self._owned_phase(own, data.size(0), gb, grad_hook))      # (``factor_vae``: the critic's phase; else nothing)
         self.iteration += 1
         return out
 
@@ -1820,6 +2071,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
             "discriminator_optimizer": self.optimizerD.state_dict(),
             **self._schedule_checkpoint(),       # (additional keys, only when a schedule exists)
             **self._ema_checkpoint(),            # (encoder_decoder_ema, only with an average)
+            **self._owned_checkpoint(),          # (latent_critic, latent_critic_optimizer: only with factor_vae)
         }
 
     def save(self, path, epoch, legacy_format=False):
@@ -1838,6 +2090,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
         self.optimizerD.load_state_dict(ck["discriminator_optimizer"])
         self._schedule_restore(ck)
         self._ema_restore(ck)
+        self._owned_restore(ck)
         self.clear_nonfinite()                               # a good checkpoint is the way back from a NonFiniteError
         return ck["epoch"]
 
@@ -1868,6 +2121,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
                 opt.refresh_weight_bounds()
         self._schedule_restore(ck, in_place=True)
         self._ema_restore(ck)
+        self._owned_restore(ck, in_place=True)
         self.clear_nonfinite()
         return ck["epoch"]
 
@@ -1879,8 +2133,9 @@ class VAETrainer(_GraphedSteps):
     the checkpoint key is ``VAE_model_ema``.  ``tc_decomposition`` / ``dataset_size``: as there, of the step's KL term
     (`train_epoch` fills a ``dataset_size`` that was not given); replica-local under data parallelism.  ``dip_vae``: as
     there -- the covariance is that of this replica's batch.  ``mmd_vae``: as there -- ``prior`` is drawn after ``eps``.
-    ``kl_control``: as there -- the per-dimension sums are those of this replica's batch.  There is no discriminator, so a
-    ``diff_augment`` is a TypeError."""
+    ``kl_control``: as there -- the per-dimension sums are those of this replica's batch.  ``factor_vae``: as there -- the
+    critic's phase follows the one optimizer step, ``permute`` is drawn last, and the cross-entropy's divisor is 2 x (this
+    replica's batch x the world size).  There is no discriminator, so a ``diff_augment`` is a TypeError."""
 
     _parts = (_Part("model", VAE, "optimizer", "flat", "vae", "optimizer"),)
     _latents = ("eps",)
@@ -1892,20 +2147,23 @@ class VAETrainer(_GraphedSteps):
                  skip_nonfinite: bool = False, lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0,
                  decoupled_weight_decay: bool = False, device_hyper: Optional[bool] = None, ema_decay=None,
                  tc_decomposition=None, dataset_size: Optional[int] = None, dip_vae=None, mmd_vae=None, kl_control=None,
-                 diff_augment=None):
+                 diff_augment=None, factor_vae=None):
         self.beta = float(beta)
         self._setup(device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
                     beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition,
                     dataset_size, capturable=capturable, dip_vae=dip_vae, mmd_vae=mmd_vae, kl_control=kl_control,
-                    diff_augment=diff_augment)
+                    diff_augment=diff_augment, factor_vae=factor_vae)
 
-    def step(self, data, eps=None, grad_hook=None, prior=None):
-        """``grad_hook(phase, net)`` (tests): called with ``("VAE", model)`` right before the optimizer step; such an
-        iteration is eager, as BetaVAEGANTrainer's.  ``prior`` (with ``mmd_vae`` only): the draws from the prior, (B,
-        n_hidden); None is drawn, after ``eps``."""
-        return self._drive(data, self._with_prior((eps,), prior), grad_hook=grad_hook)
+    def step(self, data, eps=None, grad_hook=None, prior=None, permute=None):
+        """``grad_hook(phase, net)`` (tests): called with ``("VAE", model)`` right before the optimizer step -- and, with
+        ``factor_vae``, with ``("critic", critic)`` right before the critic's; such an iteration is eager, as
+        BetaVAEGANTrainer's.  ``prior`` (with ``mmd_vae`` only): the draws from the prior, (B, n_hidden); None is drawn,
+        after ``eps``.  ``permute`` (with ``factor_vae`` only): the uniforms of ``permute_dims``, (B, n_hidden); None is
+        drawn, last, from the permutation stream."""
+        return self._drive(data, self._with_prior((eps,), prior), grad_hook=grad_hook, permute=permute)
 
     def _iteration(self, data, latents, labels, grad_hook, prepack, acc):
+        latents, own = self._split_owned(latents)      # (the inputs of an owned network's phase: behind everything else)
         eps, *prior = latents                 # (prior: one more draw with an objective that takes it, else nothing)
         prepack()                             # the filters the previous optimizer step changed: one pack launch
         self._zero(self.model, self.flat, self.optimizer, grad_hook)
@@ -1916,8 +2174,10 @@ class VAETrainer(_GraphedSteps):
         if grad_hook:
             grad_hook("VAE", self.model)
         self.optimizer.step()
+        out = dict(mse=mse.detach(), kld=kld.detach(), **self._kl_part_outputs(parts))
+        out.update(self._owned_phase(own, data.size(0), None, grad_hook))      # (``factor_vae``: the critic's phase; else nothing)
         self.iteration += 1
-        return dict(mse=mse.detach(), kld=kld.detach(), **self._kl_part_outputs(parts))
+        return out
 
     def train_epoch(self, loader, max_iterations=None):
         """``train(epoch)`` of new_vae.py:48-68: returns ``avg_loss`` = sum over the epoch of
@@ -1938,7 +2198,7 @@ class VAETrainer(_GraphedSteps):
 
     def checkpoint(self, epoch):
         return {"epoch": epoch, "VAE_model": self.model.state_dict(), "optimizer": self.optimizer.state_dict(),
-                **self._schedule_checkpoint(), **self._ema_checkpoint()}
+                **self._schedule_checkpoint(), **self._ema_checkpoint(), **self._owned_checkpoint()}
 
 
 class GANTrainer(_GraphedSteps):
@@ -1947,7 +2207,7 @@ class GANTrainer(_GraphedSteps):
     gradient exchange (SUM) per optimizer step, BCE divided by the global batch.  ``graph``: as
     BetaVAEGANTrainer; so are ``max_grad_norm``, ``skip_nonfinite`` and the schedule arguments (``lr_scheduler``,
     ``weight_decay``, ``decoupled_weight_decay``, ``device_hyper``; there is no KL term, so a ``beta_schedule``, a
-    ``tc_decomposition``, a ``dip_vae``, an ``mmd_vae`` or a ``kl_control`` is a TypeError).  ``ema_decay``: as BetaVAEGANTrainer, of the generator -- `ema_model` shadows `netG`, the checkpoint key is
+    ``tc_decomposition``, a ``dip_vae``, an ``mmd_vae``, a ``kl_control`` or a ``factor_vae`` is a TypeError).  ``ema_decay``: as BetaVAEGANTrainer, of the generator -- `ema_model` shadows `netG`, the checkpoint key is
     ``netG_ema``; the discriminator is not averaged.  ``diff_augment``: as BetaVAEGANTrainer, with three parameter sets,
     uniforms ``(3, B, 8)``: set 0 on ``data`` and set 1 on ``fake.detach()`` in the discriminator phase, set 2 on ``fake`` in
     the generator phase."""
@@ -1965,11 +2225,11 @@ class GANTrainer(_GraphedSteps):
                  skip_nonfinite: bool = False, lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0,
                  decoupled_weight_decay: bool = False, device_hyper: Optional[bool] = None, ema_decay=None,
                  tc_decomposition=None, dataset_size: Optional[int] = None, dip_vae=None, mmd_vae=None, kl_control=None,
-                 diff_augment=None):
+                 diff_augment=None, factor_vae=None):
         self._setup(device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
                     beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition,
                     dataset_size, data_parallel, dip_vae=dip_vae, mmd_vae=mmd_vae, kl_control=kl_control,
-                    diff_augment=diff_augment)
+                    diff_augment=diff_augment, factor_vae=factor_vae)
 
     def step(self, data, noise=None, real_label=0.9, fake_label=0.1, global_batch: Optional[int] = None,
              grad_hook=None, augment=None):

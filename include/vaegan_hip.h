@@ -53,7 +53,7 @@ extern "C" {
  * csrc/reparam_dip.hip; the three vg_agg_posterior_* of csrc/agg_posterior.hip; the five vg_reparam_mmd_* of
  * csrc/reparam_mmd.hip; the four vg_pair_* of csrc/pair_dist.hip; the two vg_recon_quality* of
  * csrc/recon_quality.hip; the five vg_reparam_klc_* of csrc/reparam_klc.hip; the three vg_diff_augment_* of
- * csrc/diff_augment.hip) change
+ * csrc/diff_augment.hip; the seven of csrc/factor_vae.hip) change
  * nothing an existing caller sees and keep the version: a binding that needs them and finds a library without them
  * fails at the symbol lookup, as loudly. */
 #define VG_ABI_VERSION 7
@@ -573,6 +573,48 @@ int vg_reparam_klc_bwd_dev(const float* gz, const float* mu, const float* logvar
                            const float* gloss, const float* beta_dev, const float* capacity_dev, float free_bits,
                            float* gmu, float* glogvar, int B, int D, void* workspace, size_t workspace_bytes,
                            void* stream);
+
+/* ---- FactorVAE (Kim & Mnih 2018; disentanglement_lib's form): the pieces around the latent critic; DESIGN.md section
+ * 4.32; csrc/factor_vae.hip.  The critic maps a code to two logits (l0: "drawn from q(z)", l1: "dimensions permuted
+ * across the batch"); its GEMMs are not part of this library.
+ *
+ * vg_permute_dims: z_perm[i,d] = z[pi_d[i], d] with pi_d the STABLE ascending argsort of column d of u (ties by row index;
+ * torch.sort's order: -0 == +0, NaN last), z, u, z_perm row-major fp32 [B,D].  Rank by counting: a workgroup stages 16
+ * columns of u, all B rows, in LDS and every thread counts the rows that sort before its own; every element of z_perm is
+ * written exactly once, no atomic, one launch, the same bits every run.  Forward only.  D >= 1; 1 <= B <=
+ * VG_PERMUTE_MAX_BATCH: 16 columns x 2048 rows x 4 bytes are 128 KiB of the CU's 160 KiB of LDS (the next power of two
+ * does not fit; B <= 256 and B <= 1024 take 16 and 64 KiB).  VG_ERR_BAD_ARG: a NULL pointer, z_perm aliasing z or u, B or D
+ * outside that range.
+ *
+ * vg_factor_tc_fwd: the encoder phase's loss from logits [B,2] of the critic on z and kl, the DEVICE scalar of the
+ * UNWEIGHTED KL summed over the batch (vg_reparam_kl_fwd with beta = 1):
+ *   tc = sum_b (l0 - l1)  (fp64, fixed order)      out4 = {beta*kl + gamma*tc, kl, tc, #{b : l0 > l1}}
+ * vg_factor_tc_bwd: glogits[b] = {+gamma*gloss, -gamma*gloss}, gkl = beta*gloss (gloss: DEVICE scalar, upstream of
+ * out4[0]).  One launch each.  `workspace` is not used (vg_factor_tc_workspace_bytes returns 0; the arguments keep the
+ * shape of the other objectives' entry points).  The `_dev` twins read beta AND gamma from device words (fp32): a gamma
+ * annealed every iteration replays one captured graph; the same fp32 values give the same bits.  VG_ERR_BAD_ARG: a NULL
+ * pointer (workspace excepted), B < 1.  The weights' values are not checked.
+ *
+ * vg_factor_critic_loss: the critic phase's cross-entropy on logits [2B,2] -- rows [0,B) are z (class 0), rows [B,2B)
+ * permuted (class 1) --, its gradient and the accuracy, in one launch:
+ *   x_b = l1 - l0 (b < B), l0 - l1 (b >= B)      loss = sum_b softplus(x_b) / divisor  (fp64 sum, fixed order)
+ *   glogits[b] = -+sigmoid(x_b) / divisor on the row's own class, +- on the other      acc = #{b : x_b < 0} / (2B)
+ * softplus and sigmoid in their overflow-safe forms (|x| = 1e4 gives x or 0, and exactly 1 or 0); a NaN logit is a NaN
+ * loss; a tie x_b == 0 counts as wrong.  glogits and acc may be NULL.  VG_ERR_BAD_ARG: logits or loss NULL, glogits
+ * aliasing logits, B < 1, a divisor that is not finite and > 0. */
+#define VG_PERMUTE_MAX_BATCH 2048
+int vg_permute_dims(const float* z, const float* u, float* z_perm, int B, int D, void* stream);
+size_t vg_factor_tc_workspace_bytes(int B, int D);
+int vg_factor_tc_fwd(const float* logits, const float* kl, float* out4, int B, float beta, float gamma, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int vg_factor_tc_bwd(const float* gloss, float beta, float gamma, float* glogits, float* gkl, int B, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int vg_factor_tc_fwd_dev(const float* logits, const float* kl, float* out4, int B, const float* beta_dev,
+                         const float* gamma_dev, void* workspace, size_t workspace_bytes, void* stream);
+int vg_factor_tc_bwd_dev(const float* gloss, const float* beta_dev, const float* gamma_dev, float* glogits, float* gkl,
+                         int B, void* workspace, size_t workspace_bytes, void* stream);
+int vg_factor_critic_loss(const float* logits, float* loss, float* glogits, float* acc, int B, float divisor,
+                          void* stream);
 
 /* ---- log-density under the aggregate posterior, at evaluation scale (the ELBO decomposition over a dataset and MIG:
  * Chen et al. 2018, section 4 and appendix C; csrc/agg_posterior.hip).  Forward only.  With

@@ -166,6 +166,8 @@ TUNING_SIGNATURES = {
     "vg_debug_ring_route": (_I, [_I, _I, _I, _I, _I, _I, _I, _P]),
     "vg_debug_set_bn_team": (_I, [_I, _I]),
     "vg_debug_bn_bwd_plan": (_I, [_I, _I, _I, _P, _P, _P, _P]),
+    "vg_debug_set_conv_general_tile": (_I, [_I, _I]),
+    "vg_debug_conv_general_tile": (_I, [_I, ctypes.c_long, _I, _P]),
 }
 
 _lib = None          # the library ops.py calls: the product one unless a test / script switched to the tuning build

@@ -248,13 +248,31 @@ bool cg_filter_ok(int Cout, int Cin, int KH, int KW) {
 
 // Tile of a launch: 128 output channels unless padding Cout to 128 wastes more than a fifth over padding it to 64; 128
 // pixels unless that leaves fewer workgroups than CUs.
+VG_KNOB(int, g_cg_tm, 0);   // tuning build only: forced tile (64 / 128; 0: the heuristic), vg_debug_set_conv_general_tile
+VG_KNOB(int, g_cg_tn, 0);
 void cg_tile(int Cout, int npix, int* tm, int* tn) {
   const int p64 = cdiv(Cout, 64) * 64, p128 = cdiv(Cout, 128) * 128;
-  *tm = (5 * p128 <= 6 * p64) ? 128 : 64;
-  *tn = ((long)cdiv(Cout, *tm) * cdiv(npix, 128) >= CG_CUS) ? 128 : 64;
+  *tm = g_cg_tm ? g_cg_tm : (5 * p128 <= 6 * p64) ? 128 : 64;
+  *tn = g_cg_tn ? g_cg_tn : ((long)cdiv(Cout, *tm) * cdiv(npix, 128) >= CG_CUS) ? 128 : 64;
 }
 
 }  // namespace
+
+#ifdef VG_TUNING
+extern "C" int vg_debug_set_conv_general_tile(int tm, int tn) {
+  if ((tm != 0 && tm != 64 && tm != 128) || (tn != 0 && tn != 64 && tn != 128)) return VG_ERR_BAD_ARG;
+  g_cg_tm = tm;
+  g_cg_tn = tn;
+  return 0;
+}
+
+extern "C" int vg_debug_conv_general_tile(int Cout, long npix, int pad, int* out) {
+  if (!out || Cout <= 0 || npix <= 0 || npix > 0x7fffffffL - 128) return VG_ERR_BAD_ARG;
+  cg_tile(Cout, (int)npix, &out[0], &out[1]);
+  out[2] = pad ? 1 : 0;
+  return 0;
+}
+#endif
 
 extern "C" size_t vg_conv_general_packed_bytes(int Cout, int Cin, int KH, int KW) {
   if (!cg_filter_ok(Cout, Cin, KH, KW)) return 0;

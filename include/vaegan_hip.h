@@ -1052,6 +1052,13 @@ int vg_debug_set_bn_team(int nv, int max_wgs);
  *   out[5]: path (0 BatchNorm1d, 1 one pass <2>, 2 one pass <8>, 3 two passes, 4 team), nv, T (members per channel),
  *           teams, rounds; nv = T = teams = rounds = 0 off the team path. */
 int vg_debug_bn_bwd_plan(int B, int C, int HW, const void* gy, const void* x, const void* gx, int* out);
+/* General forward convolution (conv_general.hip): force the tile of every later vg_conv_general_fwd -- tm output channels
+ * x tn output pixels, each 64 or 128, 0 = that side by the heuristic; anything else: VG_ERR_BAD_ARG, knobs unchanged. */
+int vg_debug_set_conv_general_tile(int tm, int tn);
+/* The instantiation vg_conv_general_fwd would launch for Cout output channels and npix = B OH OW output pixels under
+ * the current knobs (host only, nothing runs) -- from the launch's own cg_tile.  pad: pad_h || pad_w of the launch.
+ *   out[3]: tm, tn, pad (conv_general_kernel<tm, tn, pad>). */
+int vg_debug_conv_general_tile(int Cout, long npix, int pad, int* out);
 #endif
 
 #ifdef __cplusplus

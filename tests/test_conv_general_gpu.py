@@ -1,7 +1,8 @@
 """MI355X: the general fp16x3 forward convolution (csrc/conv_general.hip, ops.conv2d_bias_act) on every distinct
 convolution of the FID Inception network, against relu(F.conv2d) in fp64 on the CPU.  Tolerance: relative L2 <= 3e-6,
 the project's figure for every fp16x3 convolution; the fp32 CPU convolution itself stays at
-0.7e-7 ... 2.5e-7 on these shapes, so the fp64 reference is far inside it."""
+0.7e-7 ... 2.5e-7 on these shapes, so the fp64 reference is far inside it.
+The kernel's edges -- every forced tile, tails, borders, non-finite inputs, per element -- are tests/test_conv_general_elem_gpu.py's."""
 import functools
 
 import pytest

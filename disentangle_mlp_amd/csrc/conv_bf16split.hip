@@ -399,60 +399,76 @@ __global__ __launch_bounds__(XNT, 2) void conv5x5_bf16split_quad_kernel(XArgs A)
   bf16split_body<C, 0, 0, true>(A, lds, blockIdx.x, 0);
 }
 
-struct XSplit {
-  int k;          // 1: no split
-  float* slabs;   // k partial outputs
-  const float* in_amax;   // fp16 planes only
-};
+// What a launch does, decided once (x_plan).  ksplit 1: none (forward only); slab_bytes: of the ksplit partial outputs.
+struct XPlan { int var, ksplit; Tile tile; TileCounts n; long grid; size_t slab_bytes; };
 
-template <class C, bool QUAD = false>
-int launch_x(const float* x, const bf16x8* w, const float* bias, float* y, int B, int Cin, int XH, int XW, int Cout,
-             XSplit xs, hipStream_t st) {
+// Launches what the plan says; decides nothing.
+template <class C, bool QUAD>
+int launch_x(const XPlan& p, const float* x, const bf16x8* w, const float* bias, float* y, int B, int Cin, int XH, int XW,
+             int Cout, float* slabs, const float* in_amax, hipStream_t st) {
+  if (!same_tile(p.tile, tile_of<C>()) || !grid_ok(p.grid)) return VG_ERR_BAD_ARG;
   XArgs A;
-  const int ksplit = (C::MODE == CONV_FWD) ? xs.k : 1;
-  const long per_cls = fill_split<C>(A, x, w, bias, y, B, Cin, XH, XW, Cout, ksplit, xs.slabs, xs.in_amax);
-  const long grid = per_cls * (QUAD ? 1 : C::NCLS) * ksplit;
-  if (!grid_ok(grid)) return VG_ERR_BAD_ARG;
+  fill_split<C>(A, x, w, bias, y, B, Cin, XH, XW, Cout, p.ksplit, slabs, in_amax, p.n);
   if constexpr (QUAD)
-    hipLaunchKernelGGL(conv5x5_bf16split_quad_kernel<C>, dim3((unsigned)grid), dim3(XNT), 0, st, A);
+    hipLaunchKernelGGL(conv5x5_bf16split_quad_kernel<C>, dim3((unsigned)p.grid), dim3(XNT), 0, st, A);
   else
-    hipLaunchKernelGGL(conv5x5_bf16split_kernel<C>, dim3((unsigned)grid), dim3(XNT), 0, st, A);
+    hipLaunchKernelGGL(conv5x5_bf16split_kernel<C>, dim3((unsigned)p.grid), dim3(XNT), 0, st, A);
   VG_CHECK_LAUNCH();
-  return reduce_slabs(A, xs.slabs, y, ksplit, st);
+  return reduce_slabs(A, slabs, y, p.ksplit, st);
 }
 
 // diagnostics: 0 = 128 cout x 128 px, 1 = 64 x 128, 2 = 64 x 64, 3 = 32 cout x 128 px, 4 = 32 x 256 (transposed, one workgroup
 // per parity class), 5 = 128 x 128 along cout, 6 = 32 x 256 quad (transposed, stride 2, 2 planes: all four classes per workgroup)
 VG_KNOB(int, g_x_tile_override, -1);
 
-template <int MODE, int S, int WC, int FC, int FP, int NP, bool F16>
-int dispatch_geom(const float* x, const bf16x8* w, const float* bias, float* y, int B, int Cin, int XH, int XW,
-                  int Cout, XSplit xs, hipStream_t st) {
-  const int tsw = tile_extent(MODE, S, XW);
-  constexpr int TM = 32 * (4 / WC) * FP;
-  if constexpr (TM == 128) {
-    if (tsw >= 32) return launch_x<XCfg<MODE, S, 1, 4, 32, WC, FC, FP, NP, F16>>(x, w, bias, y, B, Cin, XH, XW, Cout, xs, st);
-    if (tsw >= 16) return launch_x<XCfg<MODE, S, 1, 8, 16, WC, FC, FP, NP, F16>>(x, w, bias, y, B, Cin, XH, XW, Cout, xs, st);
-    return launch_x<XCfg<MODE, S, 2, 8, 8, WC, FC, FP, NP, F16>>(x, w, bias, y, B, Cin, XH, XW, Cout, xs, st);
-  } else if constexpr (TM == 256) {
-    if (tsw >= 32) return launch_x<XCfg<MODE, S, 1, 8, 32, WC, FC, FP, NP, F16>>(x, w, bias, y, B, Cin, XH, XW, Cout, xs, st);
-    if (tsw >= 16) return launch_x<XCfg<MODE, S, 1, 16, 16, WC, FC, FP, NP, F16>>(x, w, bias, y, B, Cin, XH, XW, Cout, xs, st);
-    return launch_x<XCfg<MODE, S, 4, 8, 8, WC, FC, FP, NP, F16>>(x, w, bias, y, B, Cin, XH, XW, Cout, xs, st);
-  } else {
-    if (tsw >= 32) return launch_x<XCfg<MODE, S, 1, 2, 32, WC, FC, FP, NP, F16>>(x, w, bias, y, B, Cin, XH, XW, Cout, xs, st);
-    if (tsw >= 16) return launch_x<XCfg<MODE, S, 1, 4, 16, WC, FC, FP, NP, F16>>(x, w, bias, y, B, Cin, XH, XW, Cout, xs, st);
-    return launch_x<XCfg<MODE, S, 1, 8, 8, WC, FC, FP, NP, F16>>(x, w, bias, y, B, Cin, XH, XW, Cout, xs, st);
+// the quad form has one geometry: the 8 x 32 tile, whatever the image (narrower ones are masked)
+constexpr bool x_has_quad(int mode, int S, int NP) { return mode == CONV_TR && S == 2 && NP == 2; }
+template <int MODE, int S, int NP, bool F16>
+using XQuadCfg = XCfg<MODE, S, 1, 8, 32, 1, 1, 2, NP, F16>;
+
+// (variant, width of the tile space) -> f(XCfg{}, IntC<quad form>{}).  The pixel tile of TM = 64 / 128 / 256 pixels by the
+// width -- rows of 32 or 16 pixels of one image (TM / 32, TM / 16 of them), or 8 x 8 pixels of TM / 64 images -- of the
+// variant's WC, FC, FP
+template <int MODE, int S, int WC, int FC, int FP, int NP, bool F16, class F>
+int x_with_geom(int tsw, F&& f) {
+  auto width = [&](auto tw) {
+    constexpr int TW = decltype(tw)::value, TM = 32 * (4 / WC) * FP, NB = (TW == 8) ? TM / 64 : 1;
+    return f(XCfg<MODE, S, NB, TM / (NB * TW), TW, WC, FC, FP, NP, F16>{}, IntC<0>{});
+  };
+  return tsw >= 32 ? width(IntC<32>{}) : (tsw >= 16 ? width(IntC<16>{}) : width(IntC<8>{}));
+}
+template <int MODE, int S, int NP, bool F16, class F>
+int x_for_cfg(int var, int tsw, F&& f) {
+  if (var == 0) return x_with_geom<MODE, S, 2, 2, 2, NP, F16>(tsw, f);
+  if (var == 1) return x_with_geom<MODE, S, 2, 1, 2, NP, F16>(tsw, f);
+  if (var == 3) return x_with_geom<MODE, S, 1, 1, 1, NP, F16>(tsw, f);
+  if (var == 5) return x_with_geom<MODE, S, 4, 1, 4, NP, F16>(tsw, f);   // 4 wavefronts along cout
+  if constexpr (MODE == CONV_TR) {
+    if (var == 4) return x_with_geom<MODE, S, 1, 1, 2, NP, F16>(tsw, f);
   }
+  if constexpr (x_has_quad(MODE, S, NP)) {
+    if (var == 6) return f(XQuadCfg<MODE, S, NP, F16>{}, IntC<1>{});
+  }
+  return x_with_geom<MODE, S, 2, 1, 1, NP, F16>(tsw, f);
+}
+
+// Forward, deep K on a small grid (the 8 x 8-pixel layers): the 128 x 128 tile with the channel chunks split
+// over k workgroups, partial outputs summed in a fixed order.  1 = no split.  wgs: workgroups of that tile.
+int fwd_ksplit(long wgs, int nchunks, int Cout) {
+  if (g_x_tile_override >= 0 || Cout <= 64 || wgs >= 512 || nchunks < 8) return 1;
+  int k = 2;     // every split must own at least one chunk: (k - 1) * ceil(nchunks / k) < nchunks
+  while (wgs * k < 512 && k < 8 && nchunks / (2 * k) >= 2 && (2 * k - 1) * cdiv(nchunks, 2 * k) < nchunks) k *= 2;
+  return k;
 }
 
 // Biggest tile that still gives every CU two workgroups (256 CUs): 128 cout x 128 px, else 64 cout x
 // 128 px, else 64 x 64; 32 cout x 128 px (4 wavefronts along the pixels) for thin outputs.
-template <int MODE, int S, int NP, bool F16 = false>
-int dispatch_x(const float* x, const bf16x8* w, const float* bias, float* y, int B, int Cin, int XH, int XW, int Cout,
-               XSplit xs, hipStream_t st) {
-  const int tsw = tile_extent(MODE, S, XW), tsh = tile_extent(MODE, S, XH);
-  const int ncls = (MODE == CONV_TR) ? S * S : 1;
-  const long px128 = (long)cdiv(B * cdiv(tsh, 8) * cdiv(tsw, 8) * 64, 128) * ncls;
+template <int MODE, int S, int NP, bool F16>
+XPlan x_plan(int B, int Cin, int XH, int XW, int Cout) {
+  const int tsw = tile_extent(MODE, S, XW), ncls = (MODE == CONV_TR) ? S * S : 1;
+  const long px128 = px_tiles(MODE, S, B, XH, XW, 128) * ncls;
+  XPlan p;
+  p.ksplit = (MODE == CONV_FWD) ? fwd_ksplit(px128 * cdiv(Cout, 128), Cin / 16, Cout) : 1;
   int var = 2;
   if (Cout <= 32) var = (MODE == CONV_TR && px128 >= 1024) ? 4 : 3;      // transposed, large grid: 256 pixels per workgroup
   else if (MODE == CONV_FWD && Cout > 64 && px128 * cdiv(Cout, 128) >= 512) var = 0;   // transposed: 64 x 128 measured faster
@@ -463,23 +479,30 @@ int dispatch_x(const float* x, const bf16x8* w, const float* bias, float* y, int
   // stride 2, 2 planes, images at least one 8 x 32 tile wide: the quad form of that tile (bit-identical to variant 4),
   // once its grid -- a quarter of the per-class one -- has a workgroup for every CU.  Measured (profiles/r08_convT_quad.json):
   // 0.56 - 0.89 of the per-class time at 256 and 512 workgroups, 1.0 - 1.5 of it at 128.
-  constexpr bool HAS_QUAD = MODE == CONV_TR && S == 2 && NP == 2;
-  if (HAS_QUAD && var == 4 && tsw >= 32 && (long)B * cdiv(tsh, 8) * cdiv(tsw, 32) >= 256) var = 6;
-  if (MODE == CONV_FWD && xs.k > 1) var = 0;             // split-K is sized for the 128 x 128 tile
+  constexpr bool HAS_QUAD = x_has_quad(MODE, S, NP);
+  if constexpr (HAS_QUAD)
+    if (var == 4 && tsw >= 32 && tile_counts(tile_of<XQuadCfg<MODE, S, NP, F16>>(), B, XH, XW, Cout).per_cls >= 256) var = 6;
+  if (p.ksplit > 1) var = 0;             // split-K is sized for the 128 x 128 tile
   else if (g_x_tile_override >= 0 && g_x_tile_override <= 6 && !(g_x_tile_override == 4 && MODE == CONV_FWD) &&
            !(g_x_tile_override == 6 && !HAS_QUAD))
     var = g_x_tile_override;
-  if (var == 0) return dispatch_geom<MODE, S, 2, 2, 2, NP, F16>(x, w, bias, y, B, Cin, XH, XW, Cout, xs, st);
-  if (var == 1) return dispatch_geom<MODE, S, 2, 1, 2, NP, F16>(x, w, bias, y, B, Cin, XH, XW, Cout, xs, st);
-  if (var == 3) return dispatch_geom<MODE, S, 1, 1, 1, NP, F16>(x, w, bias, y, B, Cin, XH, XW, Cout, xs, st);
-  if (var == 5) return dispatch_geom<MODE, S, 4, 1, 4, NP, F16>(x, w, bias, y, B, Cin, XH, XW, Cout, xs, st);   // 4 wavefronts along cout
-  if constexpr (MODE == CONV_TR) {
-    if (var == 4) return dispatch_geom<MODE, S, 1, 1, 2, NP, F16>(x, w, bias, y, B, Cin, XH, XW, Cout, xs, st);
-  }
-  if constexpr (HAS_QUAD) {     // one geometry: the 8 x 32 tile, whatever the image (narrower ones are masked)
-    if (var == 6) return launch_x<XCfg<MODE, S, 1, 8, 32, 1, 1, 2, NP, F16>, true>(x, w, bias, y, B, Cin, XH, XW, Cout, xs, st);
-  }
-  return dispatch_geom<MODE, S, 2, 1, 1, NP, F16>(x, w, bias, y, B, Cin, XH, XW, Cout, xs, st);
+  p.var = var;
+  x_for_cfg<MODE, S, NP, F16>(var, tsw, [&](auto c, auto) { p.tile = tile_of<decltype(c)>(); return 0; });
+  p.n = tile_counts(p.tile, B, XH, XW, Cout);
+  p.grid = p.n.per_cls * (var == 6 ? 1 : ncls) * p.ksplit;
+  p.slab_bytes = slab_bytes(MODE, S, B, XH, XW, Cout, p.ksplit);
+  return p;
+}
+
+template <int MODE, int S, int NP, bool F16>
+int dispatch_x(const float* x, const bf16x8* w, const float* bias, float* y, int B, int Cin, int XH, int XW, int Cout,
+               void* workspace, size_t workspace_bytes, const float* in_amax, hipStream_t st) {
+  const XPlan p = x_plan<MODE, S, NP, F16>(B, Cin, XH, XW, Cout);
+  if (p.ksplit > 1 && (!workspace || workspace_bytes < p.slab_bytes)) return VG_ERR_WORKSPACE;
+  if (F16 && !in_amax) return VG_ERR_BAD_ARG;
+  return x_for_cfg<MODE, S, NP, F16>(p.var, tile_extent(MODE, S, XW), [&](auto c, auto quad) {
+    return launch_x<decltype(c), decltype(quad)::value != 0>(p, x, w, bias, y, B, Cin, XH, XW, Cout, (float*)workspace, in_amax, st);
+  });
 }
 
 // packed[class][chunk][step][plane][k-block][CoutP] x 8 bf16 (+ VG_PACK_SPARE zero steps at the end: the ring
@@ -605,18 +628,6 @@ __global__ __launch_bounds__(256) void pack_bf16split_multi_kernel(PackBatch P, 
                       P.w_amax[t], b % nbx, b / nbx);
 }
 
-// Forward, deep K on a small grid (the 8 x 8-pixel layers): the 128 x 128 tile with the channel chunks split
-// over k workgroups, partial outputs summed in a fixed order.  1 = no split.
-int fwd_ksplit(int B, int Cin, int H, int W, int Cout, int S) {
-  if (g_x_tile_override >= 0) return 1;
-  const int tsw = tile_extent(CONV_FWD, S, W), tsh = tile_extent(CONV_FWD, S, H), nchunks = Cin / 16;
-  const long wgs = (long)cdiv(B * cdiv(tsh, 8) * cdiv(tsw, 8) * 64, 128) * cdiv(Cout, 128);
-  if (Cout <= 64 || wgs >= 512 || nchunks < 8) return 1;
-  int k = 2;     // every split must own at least one chunk: (k - 1) * ceil(nchunks / k) < nchunks
-  while (wgs * k < 512 && k < 8 && nchunks / (2 * k) >= 2 && (2 * k - 1) * cdiv(nchunks, 2 * k) < nchunks) k *= 2;
-  return k;
-}
-
 // the shape every entry point of the split arithmetics takes
 bool shape_ok(int B, int Cin, int H, int W, int Cout, int stride, int planes) {
   return conv_shape_ok(B, Cin, H, W, Cout, stride) && Cin % 16 == 0 && planes_ok(planes);
@@ -636,13 +647,11 @@ bool fuse_empty(const vg_conv_fusion* f) { return !f || (!f->in_scale && !f->in_
 // (planes, stride) -> dispatch_x<MODE, S, NP, F16>
 template <int MODE>
 int dispatch_planes(const float* x, const void* packed, const float* bias, float* y, int B, int Cin, int H, int W, int Cout,
-                    int stride, int planes, int ksplit, void* workspace, const vg_conv_fusion* fuse, hipStream_t st) {
-  const XSplit xs = {ksplit, (float*)workspace, fuse ? fuse->in_amax : nullptr};
-  if ((planes & VG_PLANES_F16_FLAG) && !xs.in_amax) return VG_ERR_BAD_ARG;
+                    int stride, int planes, void* workspace, size_t workspace_bytes, const vg_conv_fusion* fuse, hipStream_t st) {
   return for_planes(planes, [&](auto np, auto f16) {
     auto run = [&](auto s) {
       return dispatch_x<MODE, decltype(s)::value, decltype(np)::value, decltype(f16)::value != 0>(
-          x, (const bf16x8*)packed, bias, y, B, Cin, H, W, Cout, xs, st);
+          x, (const bf16x8*)packed, bias, y, B, Cin, H, W, Cout, workspace, workspace_bytes, fuse ? fuse->in_amax : nullptr, st);
     };
     if constexpr (MODE == CONV_FWD) return run(IntC<1>{});
     else return for_stride(stride, run);
@@ -712,9 +721,7 @@ extern "C" int vg_conv5x5_pack_bf16split_multi(const VgPackEntry* entries, int c
 extern "C" size_t vg_conv5x5_fwd_bf16split_workspace_bytes(int B, int Cin, int H, int W, int Cout, int stride, int planes) {
   if (!shape_ok(B, Cin, H, W, Cout, stride, planes)) return 0;
   if (stride == 2) return vg_internal_ring_workspace_bytes(CONV_FWD, B, Cin, H, W, Cout, planes);
-  const int k = fwd_ksplit(B, Cin, H, W, Cout, stride);
-  if (k <= 1) return 0;
-  return (size_t)k * B * Cout * out_extent(CONV_FWD, stride, H) * out_extent(CONV_FWD, stride, W) * sizeof(float);
+  return x_plan<CONV_FWD, 1, 2, false>(B, Cin, H, W, Cout).slab_bytes;      // (the K split does not look at the planes)
 }
 
 extern "C" int vg_conv5x5_bf16split_fusable(int transposed, int Cin, int Cout, int stride) {
@@ -740,10 +747,7 @@ extern "C" int vg_conv5x5_fwd_bf16split(const float* x, const void* packed, cons
   if (on_ring(CONV_FWD, Cout, stride))
     return vg_internal_ring_conv(CONV_FWD, x, packed, bias, y, B, Cin, H, W, Cout, planes, workspace, workspace_bytes, fuse, st);
   if (!fuse_empty(fuse)) return VG_ERR_BAD_ARG;
-  const int k = fwd_ksplit(B, Cin, H, W, Cout, stride);
-  if (k > 1 && (!workspace || workspace_bytes < vg_conv5x5_fwd_bf16split_workspace_bytes(B, Cin, H, W, Cout, stride, planes)))
-    return VG_ERR_WORKSPACE;
-  return dispatch_planes<CONV_FWD>(x, packed, bias, y, B, Cin, H, W, Cout, stride, planes, k, workspace, fuse, st);
+  return dispatch_planes<CONV_FWD>(x, packed, bias, y, B, Cin, H, W, Cout, stride, planes, workspace, workspace_bytes, fuse, st);
 }
 
 extern "C" size_t vg_convT5x5_fwd_bf16split_workspace_bytes(int B, int Cin, int H, int W, int Cout, int stride, int planes) {
@@ -759,5 +763,5 @@ extern "C" int vg_convT5x5_fwd_bf16split(const float* x, const void* packed, con
   if (on_ring(CONV_TR, Cout, stride))
     return vg_internal_ring_conv(CONV_TR, x, packed, bias, y, B, Cin, H, W, Cout, planes, workspace, workspace_bytes, fuse, st);
   if (!fuse_empty(fuse)) return VG_ERR_BAD_ARG;
-  return dispatch_planes<CONV_TR>(x, packed, bias, y, B, Cin, H, W, Cout, stride, planes, 1, nullptr, fuse, st);
+  return dispatch_planes<CONV_TR>(x, packed, bias, y, B, Cin, H, W, Cout, stride, planes, workspace, workspace_bytes, fuse, st);
 }

@@ -30,7 +30,6 @@
 
 namespace {
 
-
 template <int MODE_, int S_, int NB_, int TH_, int TW_, int TN_, int WC_, int WP_, int CK_, int MINW_ = 2, int KS_ = 1,
           bool PK_ = false>
 struct Cfg {
@@ -352,35 +351,22 @@ __global__ __launch_bounds__(C::NT, C::MINW) void conv5x5_igemm_kernel(Args A) {
   }
 }
 
-// statistics request of a launch: `need` != NULL: only report the floats the chosen tile variant would write
-struct IgStats {
-  float* ptr;
-  size_t cap;
-  size_t* need;
-};
+// What a launch does, decided once (ig_plan, below the variant table): the Pick row, its tile's counts and grid, the floats
+// the tile writes when statistics are asked for (forward only, else 0)
+struct IgPlan { int width, var; Tile tile; TileCounts n; long grid; size_t stats_floats; };
 
+// Launches what the plan says; decides nothing.
 template <class C>
-int launch(const float* x, const float* w, const float* bias, float* y, int B, int Cin, int XH, int XW,
-           int Cout, hipStream_t st, const IgStats* sx = nullptr) {
+int launch(const IgPlan& p, const float* x, const float* w, const float* bias, float* y, int B, int Cin, int XH, int XW,
+           int Cout, hipStream_t st, float* stats, size_t stats_cap) {
+  if (!same_tile(p.tile, tile_of<C>()) || !grid_ok(p.grid)) return VG_ERR_BAD_ARG;
   Args A;
-  const long per_cls = fill_geom<C>(A, x, bias, y, B, Cin, XH, XW, Cout);
+  fill_geom<C>(A, x, bias, y, B, Cin, XH, XW, Cout, p.n);
   A.w = w;
-  A.stats = nullptr;
   A.CinP = packed_cin(Cin); A.CoutP = packed_cout(Cout);
-  const long grid = per_cls * C::NCLS;
-  if (!grid_ok(grid)) return VG_ERR_BAD_ARG;
-  if (sx) {
-    const size_t floats = (C::MODE == CONV_FWD) ? (size_t)(per_cls / A.ntiles_n) * C::WP * Cout * 2 : 0;
-    if (sx->need) {
-      *sx->need = floats;
-      return 0;
-    }
-    if (sx->ptr) {
-      if (!floats || sx->cap < floats) return VG_ERR_BAD_ARG;
-      A.stats = sx->ptr;
-    }
-  }
-  hipLaunchKernelGGL(conv5x5_igemm_kernel<C>, dim3((unsigned)grid), dim3(C::NT), 0, st, A);
+  if (stats && (!p.stats_floats || stats_cap < p.stats_floats)) return VG_ERR_BAD_ARG;
+  A.stats = stats;
+  hipLaunchKernelGGL(conv5x5_igemm_kernel<C>, dim3((unsigned)p.grid), dim3(C::NT), 0, st, A);
   VG_CHECK_LAUNCH();
   return 0;
 }
@@ -434,33 +420,31 @@ int g_tile_override[2] = {-1, -1};  // tuning build only (vg_debug_set_conv_tile
 constexpr int g_tile_override[2] = {-1, -1};
 #endif
 
-template <int MODE, int S, int WIDTH, bool PK>
-int launch_var(int var, const float* x, const float* w, const float* bias, float* y, int B, int Cin, int XH,
-               int XW, int Cout, hipStream_t st, const IgStats* sx = nullptr) {
-  switch (var) {
-    case 0: return launch<typename Pick<MODE, S, WIDTH, 0, PK>::type>(x, w, bias, y, B, Cin, XH, XW, Cout, st, sx);
-    case 1: return launch<typename Pick<MODE, S, WIDTH, 1, PK>::type>(x, w, bias, y, B, Cin, XH, XW, Cout, st, sx);
-    case 2: return launch<typename Pick<MODE, S, WIDTH, 2, PK>::type>(x, w, bias, y, B, Cin, XH, XW, Cout, st, sx);
-    case 3: return launch<typename Pick<MODE, S, WIDTH, 3, PK>::type>(x, w, bias, y, B, Cin, XH, XW, Cout, st, sx);
-    case 4: return launch<typename Pick<MODE, S, WIDTH, 4, PK>::type>(x, w, bias, y, B, Cin, XH, XW, Cout, st, sx);
-    case 5: return launch<typename Pick<MODE, S, WIDTH, 5, PK>::type>(x, w, bias, y, B, Cin, XH, XW, Cout, st, sx);
-    case 6: return launch<typename Pick<MODE, S, WIDTH, 6, PK>::type>(x, w, bias, y, B, Cin, XH, XW, Cout, st, sx);
-    default: return launch<typename Pick<MODE, S, WIDTH, 7, PK>::type>(x, w, bias, y, B, Cin, XH, XW, Cout, st, sx);
+// (width, variant) -> f(Cfg{}) of the Pick table
+template <int MODE, int S, int WIDTH, bool PK, int V = 0, class F>
+int for_var(int var, F&& f) {
+  if constexpr (V < NVAR - 1) {
+    if (var != V) return for_var<MODE, S, WIDTH, PK, V + 1>(var, f);
   }
+  return f(typename Pick<MODE, S, WIDTH, V, PK>::type{});
+}
+template <int MODE, int S, bool PK, class F>
+int for_cfg(int width, int var, F&& f) {
+  if (width == 32) return for_var<MODE, S, 32, PK>(var, f);
+  if (width == 16) return for_var<MODE, S, 16, PK>(var, f);
+  return for_var<MODE, S, 8, PK>(var, f);
 }
 
 // Tile choice: widest pixel row the tile space supports; cout tile to fit Cout; smaller tiles
 // when the big ones would leave CUs idle (256 CUs x 2 resident workgroups).
 template <int MODE, int S, bool PK>
-int dispatch(const float* x, const float* w, const float* bias, float* y, int B, int Cin, int XH, int XW,
-             int Cout, hipStream_t st, const IgStats* sx = nullptr) {
-  const int tsw = tile_extent(MODE, S, XW), tsh = tile_extent(MODE, S, XH);
-  const int width = tsw >= 32 ? 32 : (tsw >= 16 ? 16 : 8);
+IgPlan ig_plan(int B, int XH, int XW, int Cout) {
+  const int tsw = tile_extent(MODE, S, XW);
   // Measured on MI355X at B=128 (scripts/tune_conv.py).  Staging (global loads -> LDS) is the
   // cost next to the MFMAs, so the biggest pixel tile that still fills the chip wins: 256 px x
   // 128 / 64 cout (8 waves) on the large grids, 128 px x 64 cout otherwise -- with 8 waves
   // (in-workgroup split of the K chunk) where 4 waves would leave SIMDs with a single wave.
-  const long px256 = (long)cdiv(B * cdiv(tsh, 8) * cdiv(tsw, 8) * 64, 256);
+  const long px256 = px_tiles(MODE, S, B, XH, XW, 256);
   const int ncls = (MODE == CONV_TR) ? S * S : 1;
   int var;
   if (Cout <= 32) {
@@ -479,10 +463,23 @@ int dispatch(const float* x, const float* w, const float* bias, float* y, int B,
     else var = (2 * px256 * cdiv(Cout, 64) * ncls < 768) ? 2 : 3;
   }
   const int ov = g_tile_override[MODE];
-  const int use = (ov >= 0 && ov < NVAR) ? ov : var;
-  if (width == 32) return launch_var<MODE, S, 32, PK>(use, x, w, bias, y, B, Cin, XH, XW, Cout, st, sx);
-  if (width == 16) return launch_var<MODE, S, 16, PK>(use, x, w, bias, y, B, Cin, XH, XW, Cout, st, sx);
-  return launch_var<MODE, S, 8, PK>(use, x, w, bias, y, B, Cin, XH, XW, Cout, st, sx);
+  IgPlan p;
+  p.width = tsw >= 32 ? 32 : (tsw >= 16 ? 16 : 8);
+  p.var = (ov >= 0 && ov < NVAR) ? ov : var;
+  for_cfg<MODE, S, PK>(p.width, p.var, [&](auto c) { p.tile = tile_of<decltype(c)>(); return 0; });
+  p.n = tile_counts(p.tile, B, XH, XW, Cout);
+  p.grid = p.n.per_cls * ncls;
+  p.stats_floats = (MODE == CONV_FWD) ? tile_stats_floats(p.tile, p.n, Cout) : 0;
+  return p;
+}
+
+template <int MODE, int S, bool PK>
+int dispatch(const float* x, const float* w, const float* bias, float* y, int B, int Cin, int XH, int XW,
+             int Cout, hipStream_t st, float* stats = nullptr, size_t stats_cap = 0) {
+  const IgPlan p = ig_plan<MODE, S, PK>(B, XH, XW, Cout);
+  return for_cfg<MODE, S, PK>(p.width, p.var, [&](auto c) {
+    return launch<decltype(c)>(p, x, w, bias, y, B, Cin, XH, XW, Cout, st, stats, stats_cap);
+  });
 }
 
 // ---- filter pre-pack: [class][ci][tap][CoutP], zero padded to CinP x CoutP.  One workgroup
@@ -568,11 +565,8 @@ extern "C" int vg_conv5x5_fwd_packed(const float* x, const float* packed, const 
 
 extern "C" size_t vg_conv5x5_fwd_packed_stats_floats(int B, int Cin, int H, int W, int Cout, int stride) {
   if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2)) return 0;
-  size_t need = 0;
-  const IgStats sx = {nullptr, 0, &need};
-  const int rc = (stride == 2) ? dispatch<CONV_FWD, 2, true>(nullptr, nullptr, nullptr, nullptr, B, Cin, H, W, Cout, nullptr, &sx)
-                               : dispatch<CONV_FWD, 1, true>(nullptr, nullptr, nullptr, nullptr, B, Cin, H, W, Cout, nullptr, &sx);
-  return rc == 0 ? need : 0;
+  const IgPlan p = (stride == 2) ? ig_plan<CONV_FWD, 2, true>(B, H, W, Cout) : ig_plan<CONV_FWD, 1, true>(B, H, W, Cout);
+  return grid_ok(p.grid) ? p.stats_floats : 0;
 }
 
 extern "C" int vg_conv5x5_fwd_packed_stats(const float* x, const float* packed, const float* bias, float* y, int B,
@@ -581,9 +575,8 @@ extern "C" int vg_conv5x5_fwd_packed_stats(const float* x, const float* packed, 
   if (!conv_args_ok(x, packed, y, B, Cin, H, W, Cout, stride) || ((uintptr_t)packed & 15) != 0 || !stats)
     return VG_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
-  const IgStats sx = {stats, stats_floats, nullptr};
-  if (stride == 2) return dispatch<CONV_FWD, 2, true>(x, packed, bias, y, B, Cin, H, W, Cout, st, &sx);
-  return dispatch<CONV_FWD, 1, true>(x, packed, bias, y, B, Cin, H, W, Cout, st, &sx);
+  if (stride == 2) return dispatch<CONV_FWD, 2, true>(x, packed, bias, y, B, Cin, H, W, Cout, st, stats, stats_floats);
+  return dispatch<CONV_FWD, 1, true>(x, packed, bias, y, B, Cin, H, W, Cout, st, stats, stats_floats);
 }
 
 extern "C" int vg_convT5x5_fwd(const float* x, const float* w, const float* bias, float* y, int B, int Cin,

@@ -605,132 +605,121 @@ __global__ __launch_bounds__(RNT, 2) void conv5x5_ring_kernel(RArgs A) {
   }
 }
 
-// transposed: two classes per workgroup when that still gives every CU a workgroup (and the XCD arithmetic holds)
-template <class C>
-constexpr bool ring_paired(long per_cls, int ksplit) {
-  return C::NCLS == 4 && C::F16 && per_cls * ksplit * 2 >= 256 && per_cls % 8 == 0;
+// ---- host side: every decision of a launch is taken once, in ring_plan ----------------------------------------------------
+// Tile variants, WC x 8 / WC wavefronts of FC x FP fragments.  0: 256 cout x 128 px (4 x 2 wavefronts of 64 x 64); 1: 128
+// cout x 128 px (2 x 4 wavefronts of 64 cout x 32 px); 2: 128 cout x 128 px (4 x 2 wavefronts of 32 cout x 64 px); 3: 128
+// cout x 256 px (2 x 4 wavefronts of 64 x 64).
+struct RingVariant { int WC, FC, FP; };
+constexpr RingVariant RING_VARIANTS[4] = {{4, 2, 2}, {2, 2, 1}, {4, 1, 2}, {2, 2, 2}};
+constexpr int ring_wp(int v) { return 8 / RING_VARIANTS[v].WC; }
+constexpr int ring_tn(int v) { return 32 * RING_VARIANTS[v].WC * RING_VARIANTS[v].FC; }
+constexpr int ring_tm(int v) { return 32 * ring_wp(v) * RING_VARIANTS[v].FP; }
+// pixel-tile geometry by the width of the tiled image (forward: output, transposed: input); TM = 128 or 256 pixels
+struct RingGeom { int NB, TH, TW; };
+constexpr RingGeom ring_geom(int TM, int tsw) {
+  return TM == 256 ? RingGeom{1, 16, 16} : (tsw > 8 ? RingGeom{1, 8, 16} : RingGeom{2, 8, 8});
+}
+// Does variant v exist for this mode and these planes on a tile space of tsh x tsw?  The plan's fall-backs and the
+// instantiations of ring_for_cfg both ask here; RCfg's static_assert on LDSU checks the answers that are about LDS.
+//   3: whole 16 x 16 tiles only; forward only with fp16 planes (89.6 KB patch + 24 KB ring; three bf16 planes: 170 KB)
+//   0: transposed, 8-wide images, three planes: ring + the two 2 x 10 x 10 patches (24 units per row) exceed the LDS
+constexpr bool ring_fits(int v, int mode, int np, bool f16, int tsh, int tsw) {
+  if (v == 3) return (mode == CONV_TR || f16) && tsw % 16 == 0 && tsh % 16 == 0;
+  if (v == 0) return !(mode == CONV_TR && tsw <= 8 && np == 3);
+  return v == 1 || v == 2;
 }
 
-VG_KNOB(int*, g_ring_route_out, nullptr);   // tuning build only: vg_debug_ring_route's out[6]; the launch reports, runs nothing
+VG_KNOB(int, g_ring_variant, -1);   // tuning build only: forced tile variant (0 .. 3)
 
-// fu: the caller's fusion (never NULL here; stats only without a K split: the host says so)
-template <class C>
-int launch_ring(const float* x, const bf16x8* w, const float* bias, float* y, int B, int Cin, int XH, int XW, int Cout,
-                int ksplit, float* slabs, const vg_conv_fusion& fu, hipStream_t st) {
-  RArgs A;
-  const long per_cls = fill_split<C>(A, x, w, bias, y, B, Cin, XH, XW, Cout, ksplit, slabs, fu.in_amax);
-  A.in_scale = fu.in_scale; A.in_shift = fu.in_shift; A.in_act = fu.in_act;
-  A.stats = (ksplit == 1) ? fu.stats : nullptr;
-  A.paired = ring_paired<C>(per_cls, ksplit) ? 1 : 0;
-  const long grid = per_cls * (A.paired ? 2 : C::NCLS) * ksplit;
-  if (!grid_ok(grid)) return VG_ERR_BAD_ARG;
-  if (g_ring_route_out) {     // (a constant NULL in the product library)
-    const int route[6] = {-1, ksplit, C::NB, C::TH, C::TW, A.paired};
-    for (int i = 1; i < 6; ++i) g_ring_route_out[i] = route[i];
-    return 0;
-  }
-  if (A.in_scale) hipLaunchKernelGGL((conv5x5_ring_kernel<C, true>), dim3((unsigned)grid), dim3(RNT), 0, st, A);
-  else hipLaunchKernelGGL((conv5x5_ring_kernel<C, false>), dim3((unsigned)grid), dim3(RNT), 0, st, A);
-  VG_CHECK_LAUNCH();
-  return reduce_slabs(A, slabs, y, ksplit, st);
-}
-
-// pixel-tile geometry by the width of the tiled image (forward: output, transposed: input)
-template <int MODE, int WC, int FC, int FP, int NP, bool F16>
-int ring_geom(const float* x, const bf16x8* w, const float* bias, float* y, int B, int Cin, int XH, int XW, int Cout,
-              int ksplit, float* slabs, const vg_conv_fusion& fu, hipStream_t st) {
-  const int tsw = tile_extent(MODE, 2, XW);
-  constexpr int TM = 32 * (8 / WC) * FP;
-  static_assert(TM == 128 || TM == 256, "pixel tile");
-  if constexpr (TM == 128) {
-    if (tsw > 8) return launch_ring<RCfg<MODE, 1, 8, 16, WC, FC, FP, NP, F16>>(x, w, bias, y, B, Cin, XH, XW, Cout, ksplit, slabs, fu, st);
-    // transposed, 8-wide images, 256 cout, three planes: ring + the two 2 x 10 x 10 patches (24 units per row) exceed
-    // the LDS; the plan sends those layers to the 128-cout tiles
-    if constexpr (MODE == CONV_TR && WC * FC * 32 == 256 && NP == 3) return VG_ERR_BAD_ARG;
-    else return launch_ring<RCfg<MODE, 2, 8, 8, WC, FC, FP, NP, F16>>(x, w, bias, y, B, Cin, XH, XW, Cout, ksplit, slabs, fu, st);
-  } else {   // 256 pixels: whole 16 x 16 tiles only (the plan never picks it for narrower images)
-    return launch_ring<RCfg<MODE, 1, 16, 16, WC, FC, FP, NP, F16>>(x, w, bias, y, B, Cin, XH, XW, Cout, ksplit, slabs, fu, st);
-  }
-}
-
-VG_KNOB(int, g_ring_variant, -1);   // tuning build only: forced tile variant
-
-}  // namespace
-
-// Tile variants.  0: 256 cout x 128 px (4 x 2 wavefronts of 64 x 64); 1: 128 cout x 128 px (2 x 4 wavefronts of
-// 64 cout x 32 px); 2: 128 cout x 128 px (4 x 2 wavefronts of 32 cout x 64 px); 3 (transposed only, small patch):
-// 128 cout x 256 px (2 x 4 wavefronts of 64 x 64).
-template <int MODE, int NP, bool F16>
-static int ring_dispatch(int variant, const float* x, const bf16x8* w, const float* bias, float* y, int B, int Cin, int XH,
-                         int XW, int Cout, int ksplit, float* slabs, const vg_conv_fusion& fu, hipStream_t st) {
-  switch (variant) {
-    case 0: return ring_geom<MODE, 4, 2, 2, NP, F16>(x, w, bias, y, B, Cin, XH, XW, Cout, ksplit, slabs, fu, st);
-    case 1: return ring_geom<MODE, 2, 2, 1, NP, F16>(x, w, bias, y, B, Cin, XH, XW, Cout, ksplit, slabs, fu, st);
-    case 2: return ring_geom<MODE, 4, 1, 2, NP, F16>(x, w, bias, y, B, Cin, XH, XW, Cout, ksplit, slabs, fu, st);
-    default:      // forward: with fp16 planes only (its patch does not fit beside the ring otherwise)
-      if constexpr (MODE == CONV_TR || F16) return ring_geom<MODE, 2, 2, 2, NP, F16>(x, w, bias, y, B, Cin, XH, XW, Cout, ksplit, slabs, fu, st);
-      return VG_ERR_BAD_ARG;
-  }
-}
-
-// ---- decisions shared with conv_bf16split.hip ------------------------------------------------------------------
 // K split (channel chunks over workgroups, partial outputs summed in a fixed order) for layers whose tile grid
 // leaves CUs idle: the smallest power of two that gives >= 192 workgroups, every split owning >= 2 chunks.
-static int ring_ksplit(long wgs, int nchunks) {
+int ring_ksplit(long wgs, int nchunks) {
   int k = 1;
   while (wgs * k < 192 && k < 8 && nchunks / (2 * k) >= 2 && (2 * k - 1) * cdiv(nchunks, 2 * k) < nchunks) k *= 2;
   return k;
 }
 
-struct RingPlan {
-  int variant, ksplit;
-};
+// variant: after the fall-backs; tile: ring_geom's NB, TH, TW, the variant's TN, WP; stats_floats: 0 when the layer runs
+// K-split (its partial outputs never meet in one workgroup: statistics come from a pass over y); workspace_bytes: the slabs
+struct RingPlan { int variant, ksplit; Tile tile; TileCounts n; int paired; long grid; size_t stats_floats, workspace_bytes; };
 
-static RingPlan ring_plan(int mode, int B, int Cin, int XH, int XW, int Cout, int planes) {
+RingPlan ring_plan(int mode, int B, int Cin, int XH, int XW, int Cout, int planes) {
   const bool f16 = (planes & VG_PLANES_F16_FLAG) != 0;      // two fp16 planes: smaller ring slots and patches, more tiles fit
-  const int tsw = tile_extent(mode, 2, XW), tsh = tile_extent(mode, 2, XH);
-  const int ncls = (mode == CONV_TR) ? 4 : 1;
-  // pixel tiles of 128 (geometry 8 x 16 per image, or 2 images x 8 x 8)
-  const long pt128 = (tsw > 8) ? (long)B * cdiv(tsh, 8) * cdiv(tsw, 16) : (long)cdiv(B, 2) * cdiv(tsh, 8) * cdiv(tsw, 8);
+  const int np = planes & 0xff, tsw = tile_extent(mode, 2, XW), tsh = tile_extent(mode, 2, XH);
+  auto tile_of_variant = [&](int v) {
+    const RingGeom g = ring_geom(ring_tm(v), tsw);
+    return Tile{mode, 2, g.NB, g.TH, g.TW, ring_tn(v), ring_wp(v)};
+  };
   RingPlan p;
   // measured at B = 128 (scripts/time_ring.py): 256-cout tiles for wide layers; for <= 128 output channels the
   // 4 x 2 wavefront arrangement (32 cout x 64 px per wavefront), and for the transposed form -- small patch -- the
   // 256-pixel tile when the image has whole 16 x 16 tiles
-  if (Cout > 128) p.variant = 0;
-  else p.variant = (mode == CONV_TR && tsw >= 16 && tsh >= 16) ? 3 : 2;
-  // fp16 planes, forward: the 128 cout x 256 px tile fits too (89.6 KB patch + 24 KB ring; with three bf16 planes 170 KB)
-  // -- half the workgroups, half the filter DMA per MFMA -- where whole 16 x 16 tiles still give every CU a workgroup
-  if (f16 && mode == CONV_FWD && Cout <= 128 && tsw >= 16 && tsh >= 16 && tsw % 16 == 0 && tsh % 16 == 0 &&
-      (long)B * (tsh / 16) * (tsw / 16) * cdiv(Cout, 128) >= 256)
+  p.variant = (Cout > 128) ? 0 : ((mode == CONV_TR && tsw >= 16 && tsh >= 16) ? 3 : 2);
+  // fp16 planes, forward: the 128 cout x 256 px tile fits too -- half the workgroups, half the filter DMA per MFMA --
+  // where whole 16 x 16 tiles still give every CU a workgroup
+  if (f16 && mode == CONV_FWD && Cout <= 128 && ring_fits(3, mode, np, f16, tsh, tsw) &&
+      tile_counts(tile_of_variant(3), B, XH, XW, Cout).per_cls >= 256)
     p.variant = 3;
-  if (g_ring_variant >= 0) p.variant = g_ring_variant;
-  if (p.variant == 3 && ((mode == CONV_FWD && !f16) || tsw <= 8 || tsw % 16 || tsh % 16)) p.variant = 1;
-  // transposed, 8-wide images: the 256-cout tile's ring + two 2 x 10 x 10 patches exceed the LDS with three planes
-  if (p.variant == 0 && mode == CONV_TR && tsw <= 8 && !f16) p.variant = 2;
-  const int tn = (p.variant == 0) ? 256 : 128;
-  const long wgs = ((p.variant == 3) ? (pt128 + 1) / 2 : pt128) * cdiv(Cout, tn) * ncls;
-  p.ksplit = ring_ksplit(wgs, Cin / 16);
+  if (g_ring_variant >= 0 && g_ring_variant <= 3) p.variant = g_ring_variant;
+  if (p.variant == 3 && !ring_fits(3, mode, np, f16, tsh, tsw)) p.variant = 1;
+  // 8-wide transposed images, bf16 planes: the 128-cout tiles -- with three planes the 256-cout one does not fit; with two
+  // it would, but these layers have always run on the 128-cout tiles and the routes stay as they are
+  if (p.variant == 0 && (!ring_fits(0, mode, np, f16, tsh, tsw) || (mode == CONV_TR && tsw <= 8 && !f16))) p.variant = 2;
+  p.tile = tile_of_variant(p.variant);
+  p.n = tile_counts(p.tile, B, XH, XW, Cout);
+  const int ncls = (mode == CONV_TR) ? 4 : 1;
+  p.ksplit = ring_ksplit(p.n.per_cls * ncls, Cin / 16);
+  // transposed: two classes per workgroup when that still gives every CU a workgroup (and the XCD arithmetic holds);
+  // fp16-plane launches only (with three planes two accumulator sets spill)
+  p.paired = (ncls == 4 && f16 && p.n.per_cls * p.ksplit * 2 >= 256 && p.n.per_cls % 8 == 0) ? 1 : 0;
+  p.grid = p.n.per_cls * (p.paired ? 2 : ncls) * p.ksplit;
+  p.stats_floats = (p.ksplit > 1) ? 0 : tile_stats_floats(p.tile, p.n, Cout);
+  p.workspace_bytes = slab_bytes(mode, 2, B, XH, XW, Cout, p.ksplit);
   return p;
 }
 
-size_t vg_internal_ring_workspace_bytes(int mode, int B, int Cin, int H, int W, int Cout, int planes) {
-  const RingPlan p = ring_plan(mode, B, Cin, H, W, Cout, planes);
-  if (p.ksplit <= 1) return 0;
-  const size_t yh = out_extent(mode, 2, H), yw = out_extent(mode, 2, W);
-  return (size_t)p.ksplit * B * Cout * yh * yw * sizeof(float);
+// The plan's variant and geometry -> f(RCfg{}); VG_ERR_BAD_ARG for a combination ring_fits says does not exist.
+template <int MODE, int NP, bool F16, int V, int TSW, class F>
+int ring_with_cfg(F&& f) {
+  constexpr RingVariant T = RING_VARIANTS[V];
+  constexpr RingGeom G = ring_geom(ring_tm(V), TSW);      // (a tile-wide image is the smallest one of the geometry)
+  if constexpr (ring_fits(V, MODE, NP, F16, G.TH, G.TW)) return f(RCfg<MODE, G.NB, G.TH, G.TW, T.WC, T.FC, T.FP, NP, F16>{});
+  else return VG_ERR_BAD_ARG;
+}
+template <int MODE, int NP, bool F16, class F>
+int ring_for_cfg(const RingPlan& p, F&& f) {
+  auto geom = [&](auto v) {
+    constexpr int V = decltype(v)::value;
+    return p.tile.TW == 8 ? ring_with_cfg<MODE, NP, F16, V, 8>(f) : ring_with_cfg<MODE, NP, F16, V, 16>(f);
+  };
+  const int v = p.variant;
+  return v == 0 ? geom(IntC<0>{}) : (v == 1 ? geom(IntC<1>{}) : (v == 2 ? geom(IntC<2>{}) : geom(IntC<3>{})));
 }
 
-// Floats of the output-statistics buffer ([slot][Cout][2]; one slot per (class, pixel tile, wavefront row)); 0 when
-// the layer runs K-split (its partial outputs never meet in one workgroup: statistics come from a pass over y).
+// Launches what the plan says; decides nothing.  fu: the caller's fusion (never NULL here).
+template <class C>
+int launch_ring(const RingPlan& p, const float* x, const bf16x8* w, const float* bias, float* y, int B, int Cin, int XH,
+                int XW, int Cout, float* slabs, const vg_conv_fusion& fu, hipStream_t st) {
+  if (!same_tile(p.tile, tile_of<C>()) || !grid_ok(p.grid)) return VG_ERR_BAD_ARG;
+  RArgs A;
+  fill_split<C>(A, x, w, bias, y, B, Cin, XH, XW, Cout, p.ksplit, slabs, fu.in_amax, p.n);
+  A.in_scale = fu.in_scale; A.in_shift = fu.in_shift; A.in_act = fu.in_act;
+  A.stats = (p.ksplit == 1) ? fu.stats : nullptr;
+  A.paired = p.paired;
+  if (A.in_scale) hipLaunchKernelGGL((conv5x5_ring_kernel<C, true>), dim3((unsigned)p.grid), dim3(RNT), 0, st, A);
+  else hipLaunchKernelGGL((conv5x5_ring_kernel<C, false>), dim3((unsigned)p.grid), dim3(RNT), 0, st, A);
+  VG_CHECK_LAUNCH();
+  return reduce_slabs(A, slabs, y, p.ksplit, st);
+}
+
+}  // namespace
+
+size_t vg_internal_ring_workspace_bytes(int mode, int B, int Cin, int H, int W, int Cout, int planes) {
+  return ring_plan(mode, B, Cin, H, W, Cout, planes).workspace_bytes;
+}
+
 size_t vg_internal_ring_stats_floats(int mode, int B, int Cin, int H, int W, int Cout, int planes) {
-  const RingPlan p = ring_plan(mode, B, Cin, H, W, Cout, planes);
-  if (p.ksplit > 1) return 0;
-  const int tsw = tile_extent(mode, 2, W), tsh = tile_extent(mode, 2, H);
-  long tiles;
-  if (p.variant == 3) tiles = (long)B * cdiv(tsh, 16) * cdiv(tsw, 16);
-  else tiles = (tsw > 8) ? (long)B * cdiv(tsh, 8) * cdiv(tsw, 16) : (long)cdiv(B, 2) * cdiv(tsh, 8) * cdiv(tsw, 8);
-  const int wp = (p.variant == 0 || p.variant == 2) ? 2 : 4;
-  return (size_t)tiles * wp * ((mode == CONV_TR) ? 4 : 1) * Cout * 2;
+  return ring_plan(mode, B, Cin, H, W, Cout, planes).stats_floats;
 }
 
 int vg_internal_ring_conv(int mode, const float* x, const void* packed, const float* bias, float* y, int B, int Cin, int H,
@@ -739,37 +728,31 @@ int vg_internal_ring_conv(int mode, const float* x, const void* packed, const fl
   const vg_conv_fusion none = {};
   const vg_conv_fusion& fu = fuse ? *fuse : none;
   const RingPlan p = ring_plan(mode, B, Cin, H, W, Cout, planes);
-  if (p.ksplit > 1 && (!workspace || workspace_bytes < vg_internal_ring_workspace_bytes(mode, B, Cin, H, W, Cout, planes)))
-    return VG_ERR_WORKSPACE;
+  if (p.ksplit > 1 && (!workspace || workspace_bytes < p.workspace_bytes)) return VG_ERR_WORKSPACE;
   if (affine_on_load_slope(fu.in_scale, fu.in_shift, fu.in_act) < 0.f) return VG_ERR_BAD_ARG;      // (the kernel derives the slope from in_act)
-  if (fu.stats && (p.ksplit > 1 || fu.stats_floats < vg_internal_ring_stats_floats(mode, B, Cin, H, W, Cout, planes))) return VG_ERR_BAD_ARG;
+  if (fu.stats && (p.ksplit > 1 || fu.stats_floats < p.stats_floats)) return VG_ERR_BAD_ARG;
   if ((planes & VG_PLANES_F16_FLAG) && ((planes & 0xff) != 2 || !fu.in_amax)) return VG_ERR_BAD_ARG;
   return for_planes(planes, [&](auto np, auto f16) {
-    constexpr int NP = decltype(np)::value;
-    constexpr bool F16 = decltype(f16)::value != 0;
-    const bf16x8* w = (const bf16x8*)packed;
-    float* slabs = (float*)workspace;
-    if (mode == CONV_FWD) return ring_dispatch<CONV_FWD, NP, F16>(p.variant, x, w, bias, y, B, Cin, H, W, Cout, p.ksplit, slabs, fu, st);
-    return ring_dispatch<CONV_TR, NP, F16>(p.variant, x, w, bias, y, B, Cin, H, W, Cout, p.ksplit, slabs, fu, st);
+    auto run = [&](auto m) {
+      return ring_for_cfg<decltype(m)::value, decltype(np)::value, decltype(f16)::value != 0>(p, [&](auto c) {
+        return launch_ring<decltype(c)>(p, x, (const bf16x8*)packed, bias, y, B, Cin, H, W, Cout, (float*)workspace, fu, st);
+      });
+    };
+    return mode == CONV_FWD ? run(IntC<CONV_FWD>{}) : run(IntC<CONV_TR>{});
   });
 }
 
 #ifdef VG_TUNING
 void vg_internal_ring_set_variant(int v) { g_ring_variant = v; }
 
-// Host only: the shape goes down the launch's own path (ring_plan, ring_dispatch, ring_geom, launch_ring), which reports
-// instead of launching while g_ring_route_out is set.  No pointer is dereferenced on the way.
+// Host only: the launch's own plan, read out.
 extern "C" int vg_debug_ring_route(int mode, int B, int Cin, int H, int W, int Cout, int planes, int* out) {
   if (!out || (mode != CONV_FWD && mode != CONV_TR) || !conv_shape_ok(B, Cin, H, W, Cout, 2) || Cin % 16 || !planes_ok(planes))
     return VG_ERR_BAD_ARG;
   const RingPlan p = ring_plan(mode, B, Cin, H, W, Cout, planes);
-  alignas(16) static float word[4];
-  vg_conv_fusion fu = {};
-  fu.in_amax = word;
   out[0] = p.variant;
-  g_ring_route_out = out;
-  const int rc = vg_internal_ring_conv(mode, word, word, nullptr, word, B, Cin, H, W, Cout, planes, word, (size_t)-1, &fu, nullptr);
-  g_ring_route_out = nullptr;
-  return rc;
+  if (!grid_ok(p.grid)) return VG_ERR_BAD_ARG;
+  out[1] = p.ksplit; out[2] = p.tile.NB; out[3] = p.tile.TH; out[4] = p.tile.TW; out[5] = p.paired;
+  return 0;
 }
 #endif

@@ -171,18 +171,39 @@ inline float affine_on_load_slope(const float* scale, const float* shift, int ac
   return (!scale || act == VG_ACT_NONE) ? 1.f : (act == VG_ACT_RELU ? 0.f : 0.2f);
 }
 
-// Fills the shared fields for tile configuration C; returns the workgroups per class (and per K split).
+// A tile configuration C at run time, and THE tile-count formula: every plan of the three files (ring_plan, ig_plan,
+// x_plan) and, through the plan, every kernel argument block, statistics size and grid counts its tiles here.
+struct Tile { int mode, S, NB, TH, TW, TN, WP; };
 template <class C>
-long fill_geom(ConvGeom& A, const float* x, const float* bias, float* y, int B, int Cin, int XH, int XW, int Cout) {
+constexpr Tile tile_of() { return {C::MODE, C::S, C::NB, C::TH, C::TW, C::TN, C::WP}; }
+constexpr bool same_tile(const Tile& a, const Tile& b) {
+  return a.mode == b.mode && a.S == b.S && a.NB == b.NB && a.TH == b.TH && a.TW == b.TW && a.TN == b.TN && a.WP == b.WP;
+}
+struct TileCounts { int tiles_w, tiles_hw, ntiles_n; long per_cls; };      // per_cls: workgroups per class (and per K split)
+constexpr TileCounts tile_counts(const Tile& t, int B, int XH, int XW, int Cout) {
+  const int tiles_w = cdiv(tile_extent(t.mode, t.S, XW), t.TW);
+  const int tiles_hw = cdiv(tile_extent(t.mode, t.S, XH), t.TH) * tiles_w, ntiles_n = cdiv(Cout, t.TN);
+  return {tiles_w, tiles_hw, ntiles_n, (long)ntiles_n * tiles_hw * cdiv(B, t.NB)};
+}
+// floats of a statistics buffer [slot][Cout][2]: one slot per (class, pixel tile, wavefront row)
+constexpr size_t tile_stats_floats(const Tile& t, const TileCounts& n, int Cout) {
+  return (size_t)(n.per_cls / n.ntiles_n) * t.WP * ((t.mode == CONV_FWD) ? 1 : t.S * t.S) * Cout * 2;
+}
+// the size measure of the tile heuristics (not a tile count): pixel tiles of `px` pixels, the images in whole 8 x 8 blocks
+inline long px_tiles(int mode, int S, int B, int XH, int XW, int px) {
+  return (long)cdiv(B * cdiv(tile_extent(mode, S, XH), 8) * cdiv(tile_extent(mode, S, XW), 8) * 64, px);
+}
+inline size_t slab_bytes(int mode, int S, int B, int XH, int XW, int Cout, int ksplit) {      // the partial outputs of a K split
+  return ksplit <= 1 ? 0 : (size_t)ksplit * B * Cout * out_extent(mode, S, XH) * out_extent(mode, S, XW) * sizeof(float);
+}
+
+// Fills the shared fields for tile configuration C from the counts of the launch's plan (tile_counts of tile_of<C>()).
+template <class C>
+void fill_geom(ConvGeom& A, const float* x, const float* bias, float* y, int B, int Cin, int XH, int XW, int Cout, const TileCounts& n) {
   A.x = x; A.bias = bias; A.y = y;
   A.B = B; A.Cin = Cin; A.XH = XH; A.XW = XW; A.Cout = Cout;
   A.YH = out_extent(C::MODE, C::S, XH); A.YW = out_extent(C::MODE, C::S, XW);
-  A.tiles_w = cdiv(tile_extent(C::MODE, C::S, XW), C::TW);
-  A.tiles_hw = cdiv(tile_extent(C::MODE, C::S, XH), C::TH) * A.tiles_w;
-  A.ntiles_n = cdiv(Cout, C::TN);
-  const long per_cls = (long)A.ntiles_n * A.tiles_hw * cdiv(B, C::NB);
-  A.blocks_per_cls = (int)per_cls;
-  return per_cls;
+  A.tiles_w = n.tiles_w; A.tiles_hw = n.tiles_hw; A.ntiles_n = n.ntiles_n; A.blocks_per_cls = (int)n.per_cls;
 }
 inline bool grid_ok(long grid) { return grid > 0 && grid <= 0x7fffffffL; }
 
@@ -198,16 +219,15 @@ struct SplitGeom : ConvGeom {
   const float* w_unscale;
 };
 template <class C>
-long fill_split(SplitGeom& A, const float* x, const bf16x8* w, const float* bias, float* y, int B, int Cin, int XH, int XW,
-                int Cout, int ksplit, float* slabs, const float* in_amax) {
-  const long per_cls = fill_geom<C>(A, x, bias, ksplit > 1 ? slabs : y, B, Cin, XH, XW, Cout);
+void fill_split(SplitGeom& A, const float* x, const bf16x8* w, const float* bias, float* y, int B, int Cin, int XH, int XW,
+                int Cout, int ksplit, float* slabs, const float* in_amax, const TileCounts& n) {
+  fill_geom<C>(A, x, bias, ksplit > 1 ? slabs : y, B, Cin, XH, XW, Cout, n);
   A.w = w;
   A.CoutP = packed_cout(Cout);
   A.cps = cdiv(Cin / 16, ksplit);
   A.ysplit = (size_t)B * Cout * A.YH * A.YW;
   A.in_amax = in_amax;
   A.w_unscale = (const float*)(w + vg_pack_trailer_units(Cin / 16 * 25, C::NP, A.CoutP));
-  return per_cls;
 }
 // conv_ring.hip, called by the entry points of conv_bf16split.hip: stride-2 convolution (mode CONV_FWD) / transposed
 // convolution (CONV_TR) on the 8-wave ring kernel.  planes may carry VG_PLANES_F16 (then fuse->in_amax is required);

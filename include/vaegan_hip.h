@@ -1036,7 +1036,7 @@ int vg_debug_set_conv_bf16split_tile(int variant);
  * 3 = 128 x 256 (transposed), -1 = heuristic */
 int vg_debug_set_conv_ring_tile(int variant);
 /* What the ring kernel would launch for a stride-2 shape (mode 0 forward, 1 transposed) under the current knob (host
- * only, nothing runs) -- from the same planning and dispatch code as the launch.
+ * only, nothing runs) -- the launch's own plan (ring_plan, conv_ring.hip), read out.
  *   out[6]: tile variant, K splits, then the pixel tile: images, rows, columns (of the output forward, of the input
  *           transposed); paired (transposed: 1 = a workgroup runs two parity classes).
  * VG_ERR_BAD_ARG: the kernel does not take the shape. */

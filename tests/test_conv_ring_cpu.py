@@ -11,7 +11,8 @@ csrc/conv_bf16split.hip) -- no GPU, no kernel; the library is asked host-only qu
 3. Every mutation of R.MUTATIONS applied to the restatement is rejected by that check, on the smallest case that can
    show it.
 4. The routes the case table claims are the library's (vg_debug_ring_route: the launch's own code), and agree with the
-   public workspace and statistics queries.
+   public workspace and statistics queries -- for the table's cases and, test_one_plan_sizes_what_it_routes, over a sweep
+   of shapes, planes and forced variants: the sizes are the formulas on the route's own tile and split.
 """
 import ctypes
 import math
@@ -174,6 +175,47 @@ def test_claimed_ring_routes_are_the_librarys(tuning_lib, case):
     wp = 2 if variant in (0, 2) else 4                                    # wavefront rows of a tile: one slot each
     assert st == (0 if ksplit > 1 else tiles * wp * (4 if case.mode == R.TR else 1) * case.Cout * 2)
     assert not (paired and case.mode == R.FWD)
+
+
+def test_one_plan_sizes_what_it_routes(tuning_lib):
+    """The statistics and workspace sizes are those of the route's own tile and split (one host plan per launch), over 640
+    ring shapes: every forced variant and the heuristic, both modes, fp16 and three bf16 planes, tile-ragged and whole
+    images, one and 128 images.  Every expected value is the formula on the route's words."""
+    lib, cdiv = tuning_lib, lambda a, b: -(-a // b)
+    seen, out = set(), (ctypes.c_int * 6)()
+    try:
+        for force in (-1, 0, 1, 2, 3):
+            lib.vg_debug_set_conv_ring_tile(force)
+            for tr in (0, 1):
+                name = "convT5x5" if tr else "conv5x5"
+                for planes in (PLANES, 3):
+                    for B in (3, 128):
+                        for Cin in (32, 256):
+                            for H, W in ((8, 8), (16, 16), (17, 9), (32, 64)):
+                                for Cout in (65, 257):
+                                    shape = (B, Cin, H, W, Cout)
+                                    assert lib.vg_conv5x5_bf16split_fusable(tr, Cin, Cout, 2) == 1
+                                    assert lib.vg_debug_ring_route(tr, *shape, planes, out) == 0, (force, tr, planes, shape)
+                                    variant, ksplit, NB, TH, TW, paired = out
+                                    ws = getattr(lib, f"vg_{name}_fwd_bf16split_workspace_bytes")(*shape, 2, planes)
+                                    st = getattr(lib, f"vg_{name}_fwd_bf16split_stats_floats")(*shape, 2, planes)
+                                    tsh, tsw = (H, W) if tr else ((H - 1) // 2 + 1, (W - 1) // 2 + 1)      # the tile space
+                                    YH, YW = (2 * H, 2 * W) if tr else (tsh, tsw)
+                                    wp = 2 if variant in (0, 2) else 4
+                                    slots = cdiv(B, NB) * cdiv(tsh, TH) * cdiv(tsw, TW) * wp * (4 if tr else 1)
+                                    assert variant in (0, 1, 2, 3) and ksplit in (1, 2, 4, 8)
+                                    assert st == (0 if ksplit > 1 else slots * Cout * 2), (force, tr, planes, shape, tuple(out), st)
+                                    assert ws == (0 if ksplit == 1 else ksplit * B * Cout * YH * YW * 4), (force, tr, planes, shape, tuple(out), ws)
+                                    assert not paired or (tr and planes == PLANES), (force, tr, planes, shape, tuple(out))
+                                    seen.add((tr, planes, variant, ksplit > 1, paired))
+    finally:
+        lib.vg_debug_set_conv_ring_tile(-1)
+    for tr in (0, 1):
+        for planes in (PLANES, 3):
+            got = {s[2] for s in seen if s[:2] == (tr, planes)}
+            assert got == ({0, 1, 2} if (not tr and planes == 3) else {0, 1, 2, 3}), (tr, planes, got)      # (3: no forward tile with bf16 planes)
+            assert any(s[3] for s in seen if s[:2] == (tr, planes)), "no K-split case"
+    assert any(s[4] for s in seen), "no paired case"
 
 
 def test_ring_route_refuses_what_the_kernel_does_not_take(tuning_lib):

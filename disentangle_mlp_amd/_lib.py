@@ -142,6 +142,9 @@ SIGNATURES = {
     "vg_dot_sigmoid_bce_workspace_bytes": (_Z, [_I]),
     "vg_dot_sigmoid_bce_fwd": (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _I, _I, _F, _P, _Z, _P]),
     "vg_dot_sigmoid_bce_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "vg_dot_gan_loss_workspace_bytes": (_Z, [_I]),
+    "vg_dot_gan_loss_fwd": (_I, [_P, _P, _P, _I, _F, _P, _P, _P, _P, _P, _I, _I, _F, _P, _Z, _P]),
+    "vg_gan_loss": (_I, [_P, _I, _F, _P, _P, _P, _P, _I, _F, _F, _P]),
     "vg_u8_gather_normalize": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _F, _P]),
     "vg_minmax_workspace_bytes": (_Z, [_Z]),
     "vg_minmax": (_I, [_P, _Z, _P, _P, _Z, _P]),

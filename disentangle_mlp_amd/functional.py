@@ -788,6 +788,83 @@ class DotSigmoidBCEFn(Function):
         return (gfeat,) + slot.hand_over((gw, gb)) + (None, None)
 
 
+# Adversarial losses on the logit: (name, role) -> the kernel's kind.  role: which term of the
+# iteration the call is -- "real" / "fake": the discriminator's two (phase 1), "gen": every generator-side term.
+GAN_LOSS_NAMES = ("logistic", "hinge", "lsgan")
+GAN_ROLES = ("real", "fake", "gen")
+GAN_LOSSES = {
+    ("logistic", "real"): ops.GAN_LOGISTIC, ("logistic", "fake"): ops.GAN_LOGISTIC, ("logistic", "gen"): ops.GAN_LOGISTIC,
+    ("lsgan", "real"): ops.GAN_LSGAN, ("lsgan", "fake"): ops.GAN_LSGAN, ("lsgan", "gen"): ops.GAN_LSGAN,
+    ("hinge", "real"): ops.GAN_HINGE_REAL, ("hinge", "fake"): ops.GAN_HINGE_FAKE, ("hinge", "gen"): ops.GAN_HINGE_GEN,
+}
+
+
+def gan_loss_name(name):
+    """``name`` if it is one of `GAN_LOSS_NAMES`; a ValueError that lists them otherwise."""
+    if name not in GAN_LOSS_NAMES:
+        raise ValueError(f"gan_loss: unknown loss {name!r}; one of " + ", ".join(repr(n) for n in GAN_LOSS_NAMES))
+    return name
+
+
+def gan_loss_kind(name, role):
+    """The kernel's kind for loss ``name`` in ``role``; ``name`` may already be a kind (an int)."""
+    if isinstance(name, int) and not isinstance(name, bool):
+        return name
+    gan_loss_name(name)
+    if role not in GAN_ROLES:
+        raise ValueError(f"gan_loss: unknown role {role!r}; one of " + ", ".join(repr(r) for r in GAN_ROLES))
+    return GAN_LOSSES[(name, role)]
+
+
+class GanLossFn(Function):
+    """A GAN loss of a logit vector against a constant label (ops.gan_loss), forward and gradient in one launch as
+    `BCELossFn`.  Returns (p = sigmoid(logit), loss); p is for logging and takes no gradient."""
+
+    @staticmethod
+    def forward(ctx, logit, kind, target, divisor):
+        p, loss, glogit = ops.gan_loss(logit, kind, target, divisor, 1.0, want_grad=True)
+        ctx.save_for_backward(glogit)
+        ctx.mark_non_differentiable(p)
+        ctx.set_materialize_grads(False)
+        return p, loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, _gp, gout):
+        if gout is None:
+            return None, None, None, None
+        (glogit,) = ctx.saved_tensors
+        return ops.scale_by_scalar(glogit, gout.contiguous()), None, None, None
+
+
+class DotGanLossFn(Function):
+    """Linear(K -> 1) + a GAN loss of its logit against a constant label in one launch each way, as `DotSigmoidBCEFn`
+    (whose backward kernel this one uses: it takes any dlogit).  Returns (logit (B,), p = sigmoid(logit), loss); logit and
+    p are not differentiable here (the iteration only reads them)."""
+
+    @staticmethod
+    def forward(ctx, feat, w, bias, kind, target, divisor):
+        logit, p, loss, dlogit = ops.dot_gan_loss_fwd(feat, w, bias, kind, target, divisor, want_grad=True)
+        ctx.save_for_backward(feat, w, dlogit)
+        ctx.acc = _acc_ctx()
+        ctx.has_bias = bias is not None
+        ctx.mark_non_differentiable(logit, p)
+        ctx.set_materialize_grads(False)
+        return logit, p, loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, _glogit, _gp, gloss):
+        if gloss is None:
+            return None, None, None, None, None, None
+        feat, w, dlogit = ctx.saved_tensors
+        need_w, need_b = ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+        slot = _grad_slot(ctx.acc if (need_w and need_b) else None, id(w))
+        gfeat, gw, gb = ops.dot_sigmoid_bce_bwd(dlogit, gloss.contiguous(), feat, w, ctx.needs_input_grad[0], need_w, need_b,
+                                                accumulate_into=slot.prev)
+        return (gfeat,) + slot.hand_over((gw, gb)) + (None, None, None)
+
+
 # ------------------------------------------------------------ functional API
 def conv5x5(x, w, bias, stride, bias_grad=BIAS_GRAD_COMPUTE):
     return ConvFn.apply(x, w, bias, stride, False, bias_grad)
@@ -951,6 +1028,21 @@ def dot_sigmoid_bce(feat, w, bias, label_value, divisor=None):
     if not isinstance(label_value, torch.Tensor):
         label_value = float(label_value)
     return DotSigmoidBCEFn.apply(feat.contiguous(), w, bias, label_value, divisor)
+
+
+def gan_loss(logit, kind, label_value, divisor=None):
+    """(p, loss) of a logit vector: see GanLossFn.  ``kind``: an ops.GAN_* code (`gan_loss_kind(name, role)`);
+    ``label_value`` as in `bce_loss` -- the hinge kinds ignore it."""
+    if not isinstance(label_value, torch.Tensor):
+        label_value = float(label_value)
+    return GanLossFn.apply(logit.contiguous(), kind, label_value, divisor)
+
+
+def dot_gan_loss(feat, w, bias, kind, label_value, divisor=None):
+    """(logit, p, loss): see DotGanLossFn.  ``w`` (1, K) or (K,), ``bias`` (1,)."""
+    if not isinstance(label_value, torch.Tensor):
+        label_value = float(label_value)
+    return DotGanLossFn.apply(feat.contiguous(), w, bias, kind, label_value, divisor)
 
 
 

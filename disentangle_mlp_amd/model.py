@@ -543,6 +543,27 @@ class Discriminator_celeba(nn.Module):
         loss in ONE kernel each way.  Returns (p, features, bce)."""
         return self.head_with_bce(self.lth_features(self._features_of(x)), label, divisor)
 
+    def head_with_loss(self, feat, loss, role, label, divisor=None):
+        """The head under an adversarial loss of the LOGIT on features already computed:
+        ``loss`` in "logistic" / "hinge" / "lsgan", ``role`` in "real" / "fake" / "gen" (functional.GAN_LOSSES), ``label`` as
+        in `head_with_bce` (the hinge terms ignore it).  Returns (p, logit, features, loss); p = sigmoid(logit) is for
+        logging only -- the Sigmoid module is not on this path, and nothing is differentiated through p or logit.
+        Routes as `head_with_bce`: one kernel each way, or -- FUSE_HEAD_BCE off, a hooked head Linear -- the Linear
+        module followed by the loss kernel.  (A hook on the Sigmoid does not count here: that module is on neither
+        route of this path, so it would never fire.)"""
+        kind = F.gan_loss_kind(loss, role)
+        lin = self.sigmoid_output[0]
+        if not FUSE_HEAD_BCE or lin._forward_hooks or lin._forward_pre_hooks:
+            logit = lin(feat).squeeze(-1)
+            p, val = F.gan_loss(logit, kind, label, divisor)
+            return p, logit.detach(), feat.squeeze(), val
+        logit, p, val = F.dot_gan_loss(feat, lin.weight, lin.bias, kind, label, divisor)
+        return p, logit, feat.squeeze(), val
+
+    def forward_with_loss(self, x, loss, role, label, divisor=None):
+        """`forward_with_bce` under an adversarial loss of the logit: (p, logit, features, loss) of `head_with_loss`."""
+        return self.head_with_loss(self.lth_features(self._features_of(x)), loss, role, label, divisor)
+
 
 class VAE(nn.Module, _DecoderMixin):
     """model.py:419-571.  ``forward(x, eps=None)``: eps may be injected for reproducible

@@ -1673,6 +1673,66 @@ def dot_sigmoid_bce_bwd(dlogit, gloss, feat, w, need_feat=True, need_w=True, nee
     return gfeat, gw, gb
 
 
+# adversarial losses on the logit (VG_GAN_* of include/vaegan_hip.h)
+GAN_LOGISTIC, GAN_LSGAN, GAN_HINGE_REAL, GAN_HINGE_FAKE, GAN_HINGE_GEN = range(5)
+
+
+def _gan_kind(kind, name):
+    if isinstance(kind, bool) or not isinstance(kind, int) or not GAN_LOGISTIC <= kind <= GAN_HINGE_GEN:
+        raise RuntimeError(f"{name}: kind is one of the five GAN_* codes, got {kind!r}")
+    return kind
+
+
+def _gan_label(target, name):
+    """(host value, device pointer) of a label: a Python float, or a one-element fp32 DEVICE tensor (bce_loss)."""
+    if isinstance(target, torch.Tensor):
+        _req(target, "target")
+        if target.numel() != 1:
+            raise RuntimeError(f"{name}: a device label is one fp32 value")
+        return 0.0, target.data_ptr()
+    return float(target), None
+
+
+def gan_loss(logit, kind, target, divisor=None, gscale=1.0, want_grad=True):
+    """A GAN loss of the logit vector ``logit`` (B,) against ``target`` (as in `bce_loss`; the hinge kinds ignore it):
+    (p = sigmoid(logit), loss, gscale * d loss / d logit)."""
+    lib = _lib.load()
+    _req(logit, "logit")
+    kind = _gan_kind(kind, "gan_loss")
+    B = logit.numel()
+    p = torch.empty(B, dtype=torch.float32, device=logit.device)
+    loss = torch.empty((), dtype=torch.float32, device=logit.device)
+    glogit = torch.empty_like(logit) if want_grad else None
+    host, dev = _gan_label(target, "gan_loss")
+    check(lib.vg_gan_loss(logit.data_ptr(), kind, host, dev, p.data_ptr(), loss.data_ptr(), _ptr(glogit), B,
+                          float(divisor if divisor is not None else B), float(gscale), _stream()), "vg_gan_loss")
+    return p, loss, glogit
+
+
+def dot_gan_loss_fwd(feat, w, bias, kind, target, divisor=None, want_grad=True):
+    """The discriminator's head + a GAN loss of its logit in one launch: logit = feat @ w + bias (B,), p = sigmoid(logit)
+    (for logging), the loss of ``kind`` against ``target`` (float or one-element device tensor) summed over the rows and
+    divided by ``divisor``, and dlogit = d loss / d logit -- what `dot_sigmoid_bce_bwd` takes."""
+    lib = _lib.load()
+    _req(feat, "feat"), _req(w, "w")
+    kind = _gan_kind(kind, "dot_gan_loss")
+    B, K = feat.shape
+    if w.numel() != K:
+        raise RuntimeError("dot_gan_loss: weight does not match the features")
+    if bias is not None:
+        _req(bias, "bias")
+    logit = torch.empty(B, dtype=torch.float32, device=feat.device)
+    p = torch.empty(B, dtype=torch.float32, device=feat.device)
+    loss = torch.empty((), dtype=torch.float32, device=feat.device)
+    dlogit = torch.empty(B, dtype=torch.float32, device=feat.device) if want_grad else None
+    host, dev = _gan_label(target, "dot_gan_loss")
+    ws = workspace(lib.vg_dot_gan_loss_workspace_bytes(B), feat.device)
+    check(lib.vg_dot_gan_loss_fwd(feat.data_ptr(), w.data_ptr(), _ptr(bias), kind, host, dev, logit.data_ptr(), p.data_ptr(),
+                                  loss.data_ptr(), _ptr(dlogit), B, K, float(divisor if divisor is not None else B),
+                                  ws.data_ptr(), ws.numel(), _stream()), "vg_dot_gan_loss_fwd")
+    return logit, p, loss, dlogit
+
+
 # ---------------------------------------------------------------- image I/O (SURVEY 8f N2 / N3)
 def u8_gather_normalize(images_u8, index, mean=0.5, std=0.5):
     """images_u8 [N,H,W,C] uint8 (device), index int64 (device) -> fp32 [B,C,H,W] =

@@ -735,11 +735,12 @@ class _GraphedSteps:
     _accumulate = False       # layers applied twice before one backward add their second parameter gradient in-kernel
     _augment_sets = 0         # parameter sets of ``diff_augment`` an iteration uses (0: the trainer has no discriminator)
     _augment = None           # (policy names, bit set, p) of ``diff_augment``, None when off
+    _gan_loss = None          # name of the adversarial loss on the logit (``gan_loss``), None: the reference's BCE on p
 
     def _setup(self, device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
                beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition, dataset_size,
                data_parallel=None, capturable=None, dip_vae=None, mmd_vae=None, kl_control=None, diff_augment=None,
-               factor_vae=None):
+               factor_vae=None, gan_loss=None):
         """The constructor body of every trainer (new_betavaegan.py:36-53, new_vae.py:33-37, new_gan.py:47-61).  A trainer
         with a KL term has set `beta` before."""
         has_beta = hasattr(self, "beta")
@@ -754,6 +755,10 @@ class _GraphedSteps:
             if not self._augment_sets:
                 raise TypeError(f"{type(self).__name__} has no discriminator: diff_augment does not apply")
             self._augment = _parse_diff_augment(diff_augment)
+        if gan_loss is not None:
+            if not self._augment_sets:
+                raise TypeError(f"{type(self).__name__} has no discriminator: gan_loss does not apply")
+            self._gan_loss = F.gan_loss_name(gan_loss)
         self.max_grad_norm, self.skip_nonfinite = max_grad_norm, bool(skip_nonfinite)
         self._skipped = {}
         self.world, self.rank = _dist_world(), _dist_rank()
@@ -1442,7 +1447,16 @@ class _GraphedSteps:
                 self._objective_key(),       # (which objective, and its frozen kernel arguments)
                 tuple(net.training for net in self._nets()),
                 tuple(p.requires_grad for net in self._nets() for p in net.parameters()),
-                *(() if self._augment is None else (self._augment,)))      # (the augmentation's launches: policy and p)
+                *(() if self._augment is None else (self._augment,)),      # (the augmentation's launches: policy and p)
+                *(() if self._gan_loss is None else (("gan_loss", self._gan_loss),)))      # (the head's loss kernels)
+
+    def _head(self, netD, feat, role, label, gb):
+        """The discriminator's head and its loss on features ``feat`` -> (p, logit, features, loss): the reference's BCE on
+        p (``logit`` is None then), or -- ``gan_loss`` -- that loss of the logit in ``role``."""
+        if self._gan_loss is None:
+            p, f, err = netD.head_with_bce(feat, label, gb)
+            return p, None, f, err
+        return netD.head_with_loss(feat, self._gan_loss, role, label, gb)
 
     # ---- one iteration: the path every `step` takes ----------------------------------------------------------------------
     def draw_latents(self, batch):
@@ -1749,7 +1763,22 @@ class BetaVAEGANTrainer(_GraphedSteps):
     <= 2048.  ``kld`` of the returned dict is the weighted loss; ``kl``, ``tc`` (unweighted), ``critic_loss`` and
     ``critic_acc`` are added.  Checkpoints gain ``latent_critic`` and ``latent_critic_optimizer``; one without them loads
     and leaves a fresh critic.  Together with another objective keyword it is a ValueError.  Data parallel: the critic's
-    gradients are exchanged through a `FlatGrads` of its own; the permutation is across this replica's batch."""
+    gradients are exchanged through a `FlatGrads` of its own; the permutation is across this replica's batch.
+
+    ``gan_loss="logistic" | "hinge" | "lsgan"`` (default: none -- then every launch, capture key, draw, checkpoint key and
+    bit is what it was): the adversarial terms become that loss of the discriminator's LOGIT instead of nn.BCELoss on
+    ``sigmoid(logit)`` (`Discriminator_celeba.head_with_loss`).  The reference's BCE, evaluated in
+    fp32 on p, has a gradient of exactly 0 once p rounds to 1 and loses it as p underflows; a loss of the logit cannot.
+    ``"logistic"`` is the same objective as the default (BCE-with-logits, soft labels included), ``"lsgan"`` is
+    ``(logit - label)^2 / 2``, ``"hinge"`` is ``max(0, 1 - s)`` on real, ``max(0, 1 + s)`` on fake and ``-s`` for the
+    generator.  Phase 1 real: role "real" with ``real_label``; phase 1 fake: role "fake" with ``fake_label``; every
+    generator-side term (``errG_fake``, ``errG_recon``): role "gen" with ``real_label``; the divisor stays the global
+    batch.  Dis_l, the pixel MSE terms and the feature path are untouched.  The labels stay the capture's device words, so
+    the per-iteration label flips still replay ONE graph.  The hinge terms IGNORE the labels; `train_epoch` still draws
+    them, so every random stream is what it is without the keyword.  The returned dict keeps its keys -- ``D_x_sum`` stays
+    the sum of ``sigmoid(logit_real)`` -- and gains ``D_logit_real_sum`` and ``D_logit_fake_sum``, the sums of the phase-1
+    logits.  No checkpoint key; data parallel: nothing new (replica-local head, SUM exchange, global divisor).  An
+    unknown name is a ValueError.  Composes with every other keyword: none of them touches the head."""
 
     _parts = (_Part("netEG", VAE, "optimizerEG", "flat_eg", "eg", "encoder_decoder_optimizer"),              # :41, :49
               _Part("netD", Discriminator_celeba, "optimizerD", "flat_d", "d", "discriminator_optimizer"))    # :43, :50
@@ -1765,12 +1794,12 @@ class BetaVAEGANTrainer(_GraphedSteps):
                  lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0, decoupled_weight_decay: bool = False,
                  device_hyper: Optional[bool] = None, ema_decay=None, tc_decomposition=None,
                  dataset_size: Optional[int] = None, dip_vae=None, mmd_vae=None, kl_control=None, diff_augment=None,
-                 factor_vae=None):
+                 factor_vae=None, gan_loss=None):
         self.beta = float(beta)
         self._setup(device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
                     beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition,
                     dataset_size, data_parallel, capturable, dip_vae, mmd_vae, kl_control,      # (lr: hard-coded 1e-3 at new_betavaegan.py:49-50)
-                    diff_augment, factor_vae)
+                    diff_augment, factor_vae, gan_loss)
         self._eg_params = [p for p in self.netEG.parameters() if p.dim() == 4]   # convolution filters
         self._d_params = [p for p in self.netD.parameters() if p.dim() == 4]
 
@@ -1808,8 +1837,8 @@ class BetaVAEGANTrainer(_GraphedSteps):
         with F.deferred_wgrad():                             # D runs twice, one backward: big Linear weight gradient once
             # ... and its big Linear layer reads its weight once for both passes, forward and data gradient
             f_real, f_fake = netD.features_grouped([seen(data, aug, 0), seen(fake.detach(), aug, 1)])
-            p_real, _, err_real = netD.head_with_bce(f_real, real_label, gb)
-            p_fake, _, err_fake = netD.head_with_bce(f_fake, fake_label, gb)
+            p_real, s_real, _, err_real = self._head(netD, f_real, "real", real_label, gb)
+            p_fake, s_fake, _, err_fake = self._head(netD, f_fake, "fake", fake_label, gb)
             _backward([err_real, err_fake])
         self._exchange(self.flat_d)
         if grad_hook:
@@ -1820,6 +1849,8 @@ class BetaVAEGANTrainer(_GraphedSteps):
         acc.reset()
         out["errD_real"], out["errD_fake"] = err_real.detach(), err_fake.detach()
         out["D_x_sum"] = p_real.detach().sum()
+        if s_real is not None:
+            out["D_logit_real_sum"], out["D_logit_fake_sum"] = s_real.detach().sum(), s_fake.detach().sum()
 
         # ---- phase 2: "decoder" -- every EG parameter moves (:127-164)
         self._zero(netEG, self.flat_eg, self.optimizerEG, grad_hook, update_ema=False)      # (phase 2 never averages)
@@ -1832,8 +1863,8 @@ class BetaVAEGANTrainer(_GraphedSteps):
         f_data, f_fake, f_rec = netD.features_grouped([seen(data, aug, 2), seen(fake, aug, 3), seen(recon, aug, 2)],
                                                       no_grad=(True, False, False))
         sim_real = f_data.squeeze()
-        _, _, err_g_fake = netD.head_with_bce(f_fake, real_label, gb)
-        _, sim_rec, err_g_rec = netD.head_with_bce(f_rec, real_label, gb)
+        _, _, _, err_g_fake = self._head(netD, f_fake, "gen", real_label, gb)
+        _, _, sim_rec, err_g_rec = self._head(netD, f_rec, "gen", real_label, gb)
         sim = F.sim_loss(sim_rec, sim_real)
         mse2 = F.reconstruction_loss(recon, data)
         _backward([err_g_fake, err_g_rec, sim, mse2])
@@ -2135,7 +2166,7 @@ class VAETrainer(_GraphedSteps):
     there -- the covariance is that of this replica's batch.  ``mmd_vae``: as there -- ``prior`` is drawn after ``eps``.
     ``kl_control``: as there -- the per-dimension sums are those of this replica's batch.  ``factor_vae``: as there -- the
     critic's phase follows the one optimizer step, ``permute`` is drawn last, and the cross-entropy's divisor is 2 x (this
-    replica's batch x the world size).  There is no discriminator, so a ``diff_augment`` is a TypeError."""
+    replica's batch x the world size).  There is no discriminator, so a ``diff_augment`` or a ``gan_loss`` is a TypeError."""
 
     _parts = (_Part("model", VAE, "optimizer", "flat", "vae", "optimizer"),)
     _latents = ("eps",)
@@ -2147,12 +2178,12 @@ class VAETrainer(_GraphedSteps):
                  skip_nonfinite: bool = False, lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0,
                  decoupled_weight_decay: bool = False, device_hyper: Optional[bool] = None, ema_decay=None,
                  tc_decomposition=None, dataset_size: Optional[int] = None, dip_vae=None, mmd_vae=None, kl_control=None,
-                 diff_augment=None, factor_vae=None):
+                 diff_augment=None, factor_vae=None, gan_loss=None):
         self.beta = float(beta)
         self._setup(device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
                     beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition,
                     dataset_size, capturable=capturable, dip_vae=dip_vae, mmd_vae=mmd_vae, kl_control=kl_control,
-                    diff_augment=diff_augment, factor_vae=factor_vae)
+                    diff_augment=diff_augment, factor_vae=factor_vae, gan_loss=gan_loss)
 
     def step(self, data, eps=None, grad_hook=None, prior=None, permute=None):
         """``grad_hook(phase, net)`` (tests): called with ``("VAE", model)`` right before the optimizer step -- and, with
@@ -2210,7 +2241,8 @@ class GANTrainer(_GraphedSteps):
     ``tc_decomposition``, a ``dip_vae``, an ``mmd_vae``, a ``kl_control`` or a ``factor_vae`` is a TypeError).  ``ema_decay``: as BetaVAEGANTrainer, of the generator -- `ema_model` shadows `netG`, the checkpoint key is
     ``netG_ema``; the discriminator is not averaged.  ``diff_augment``: as BetaVAEGANTrainer, with three parameter sets,
     uniforms ``(3, B, 8)``: set 0 on ``data`` and set 1 on ``fake.detach()`` in the discriminator phase, set 2 on ``fake`` in
-    the generator phase."""
+    the generator phase.  ``gan_loss``: as BetaVAEGANTrainer -- roles "real" and "fake" in the discriminator phase, "gen"
+    with ``real_label`` for ``errG``; the dict gains ``D_logit_real_sum`` and ``D_logit_fake_sum``."""
 
     _parts = (_Part("netG", Generator_celeba, "optimizerG", "flat_g", "g", "G_trainer"),
               _Part("netD", Discriminator_celeba, "optimizerD", "flat_d", "d", "D_trainer"))
@@ -2225,11 +2257,11 @@ class GANTrainer(_GraphedSteps):
                  skip_nonfinite: bool = False, lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0,
                  decoupled_weight_decay: bool = False, device_hyper: Optional[bool] = None, ema_decay=None,
                  tc_decomposition=None, dataset_size: Optional[int] = None, dip_vae=None, mmd_vae=None, kl_control=None,
-                 diff_augment=None, factor_vae=None):
+                 diff_augment=None, factor_vae=None, gan_loss=None):
         self._setup(device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
                     beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition,
                     dataset_size, data_parallel, dip_vae=dip_vae, mmd_vae=mmd_vae, kl_control=kl_control,
-                    diff_augment=diff_augment, factor_vae=factor_vae)
+                    diff_augment=diff_augment, factor_vae=factor_vae, gan_loss=gan_loss)
 
     def step(self, data, noise=None, real_label=0.9, fake_label=0.1, global_batch: Optional[int] = None,
              grad_hook=None, augment=None):
@@ -2245,8 +2277,8 @@ class GANTrainer(_GraphedSteps):
         fake = self.netG(noise)
         with F.deferred_wgrad():                             # as BetaVAEGANTrainer's discriminator phase
             f_real, f_fake = self.netD.features_grouped([seen(data, aug, 0), seen(fake.detach(), aug, 1)])
-            p_real, _, err_real = self.netD.head_with_bce(f_real, real_label, gb)
-            p_fake, _, err_fake = self.netD.head_with_bce(f_fake, fake_label, gb)
+            p_real, s_real, _, err_real = self._head(self.netD, f_real, "real", real_label, gb)
+            p_fake, s_fake, _, err_fake = self._head(self.netD, f_fake, "fake", fake_label, gb)
             _backward([err_real, err_fake])
         self._exchange(self.flat_d)
         if grad_hook:
@@ -2257,7 +2289,10 @@ class GANTrainer(_GraphedSteps):
         acc.reset()
         self._zero(self.netG, self.flat_g, self.optimizerG, grad_hook)
         self._set_frozen(self.netD, True)
-        _, _, err_g = self.netD.forward_with_bce(seen(fake, aug, 2), real_label, gb)
+        if self._gan_loss is None:
+            _, _, err_g = self.netD.forward_with_bce(seen(fake, aug, 2), real_label, gb)
+        else:
+            _, _, _, err_g = self.netD.forward_with_loss(seen(fake, aug, 2), self._gan_loss, "gen", real_label, gb)
         _backward([err_g])
         self._set_frozen(self.netD, False)
         self._exchange(self.flat_g)
@@ -2265,8 +2300,11 @@ class GANTrainer(_GraphedSteps):
             grad_hook("G", self.netG)
         self.optimizerG.step()
         self.iteration += 1
-        return dict(errD_real=err_real.detach(), errD_fake=err_fake.detach(), errG=err_g.detach(),
-                    D_x_sum=p_real.detach().sum())
+        out = dict(errD_real=err_real.detach(), errD_fake=err_fake.detach(), errG=err_g.detach(),
+                   D_x_sum=p_real.detach().sum())
+        if s_real is not None:
+            out.update(D_logit_real_sum=s_real.detach().sum(), D_logit_fake_sum=s_fake.detach().sum())
+        return out
 
     def train_epoch(self, loader, label_rng=None, max_iterations=None):
         """``train()`` of new_gan.py:66-141: label draw per iteration (:68-69), returns the reference's

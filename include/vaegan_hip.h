@@ -53,7 +53,7 @@ extern "C" {
  * csrc/reparam_dip.hip; the three vg_agg_posterior_* of csrc/agg_posterior.hip; the five vg_reparam_mmd_* of
  * csrc/reparam_mmd.hip; the four vg_pair_* of csrc/pair_dist.hip; the two vg_recon_quality* of
  * csrc/recon_quality.hip; the five vg_reparam_klc_* of csrc/reparam_klc.hip; the three vg_diff_augment_* of
- * csrc/diff_augment.hip; the seven of csrc/factor_vae.hip) change
+ * csrc/diff_augment.hip; the seven of csrc/factor_vae.hip; the three of csrc/gan_loss.hip) change
  * nothing an existing caller sees and keep the version: a binding that needs them and finds a library without them
  * fails at the symbol lookup, as loudly. */
 #define VG_ABI_VERSION 7
@@ -772,6 +772,35 @@ int vg_dot_sigmoid_bce_fwd(const float* feat, const float* w, const float* bias,
                            void* workspace, size_t workspace_bytes, void* stream);
 int vg_dot_sigmoid_bce_bwd(const float* dlogit, const float* gloss, const float* feat, const float* w, float* gfeat,
                            float* gw, float* gb, int B, int K, int accumulate_param_grads /* gw, gb += */, void* stream);
+
+/* Adversarial losses on the LOGIT s (csrc/gan_loss.hip).  Per row, with label t:
+ *   VG_GAN_LOGISTIC    l = (1-t) s + softplus(-s)     dl/ds = sigmoid(s) - t      (BCE-with-logits: nn.BCELoss's objective)
+ *   VG_GAN_LSGAN       l = (s-t)^2 / 2                dl/ds = s - t
+ *   VG_GAN_HINGE_REAL  l = max(0, 1-s)                dl/ds = -1 where 1-s > 0, else 0 (an exact tie: 0)
+ *   VG_GAN_HINGE_FAKE  l = max(0, 1+s)                dl/ds = +1 where 1+s > 0, else 0
+ *   VG_GAN_HINGE_GEN   l = -s                         dl/ds = -1
+ * (the hinge kinds ignore t).  softplus(-s) = max(-s, 0) + log1p(exp(-|s|)) and sigmoid(s) from exp(-|s|): neither
+ * overflows, and the gradient is never lost to the rounding of a probability.  A NaN logit gives a NaN loss and a NaN
+ * gradient for every kind; +-inf give what the formulas give in IEEE arithmetic.
+ *   vg_dot_gan_loss_fwd: logit[b] = <feat[b,:], w> + bias[0] (bias may be NULL);  p[b] = sigmoid(logit[b]) (for logging,
+ *     any kind);  loss[0] = (1/divisor) sum_b l(logit[b]), the row terms added in double in index order (workspace);
+ *     dlogit[b] = (1/divisor) dl/ds (may be NULL).  The label is `target`, or target_dev[0] when target_dev != NULL.
+ *     16-byte loads when K % 4 == 0 and feat, w are 16-byte aligned, element loads otherwise.  Its backward is
+ *     vg_dot_sigmoid_bce_bwd, which takes any dlogit.
+ *   vg_gan_loss: the same on a logit vector (B,): p (may be NULL), loss[0] (may be NULL),
+ *     glogit[b] = gscale/divisor dl/ds (may be NULL).
+ * No atomics: the same bits every run. */
+#define VG_GAN_LOGISTIC 0
+#define VG_GAN_LSGAN 1
+#define VG_GAN_HINGE_REAL 2
+#define VG_GAN_HINGE_FAKE 3
+#define VG_GAN_HINGE_GEN 4
+size_t vg_dot_gan_loss_workspace_bytes(int B);
+int vg_dot_gan_loss_fwd(const float* feat, const float* w, const float* bias, int kind, float target,
+                        const float* target_dev, float* logit, float* p, float* loss, float* dlogit, int B, int K,
+                        float divisor, void* workspace, size_t workspace_bytes, void* stream);
+int vg_gan_loss(const float* logit, int kind, float target, const float* target_dev, float* p, float* loss,
+                float* glogit, int B, float divisor, float gscale, void* stream);
 
 /* ---- Adam (experiments/new_betavaegan.py:49-50: optim.Adam defaults, stepped 3x per iteration)
  * For each tensor: m += (1-beta1)(g-m); v = beta2 v + (1-beta2) g^2;

@@ -138,6 +138,9 @@ SIGNATURES = {
     "vg_diff_augment_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "vg_diff_augment_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _Z, _P]),
     "vg_diff_augment_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _Z, _P]),
+    "vg_diff_augment_fwd_dev": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _Z, _P]),
+    "vg_diff_augment_bwd_dev": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _Z, _P]),
+    "vg_ada_update": (_I, [_P, _I, _F, _F, _F, _I, _P, _P]),
     "vg_bce_loss_dev": (_I, [_P, _P, _P, _P, _I, _F, _F, _P]),
     "vg_dot_sigmoid_bce_workspace_bytes": (_Z, [_I]),
     "vg_dot_sigmoid_bce_fwd": (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _I, _I, _F, _P, _Z, _P]),

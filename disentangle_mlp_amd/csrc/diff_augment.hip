@@ -7,7 +7,8 @@
 //                x3 = (x2 - m) c + m  with m = mean_CHW x2 = mean_CHW x + b (saturation keeps a pixel's channel mean);
 //   translation  y[c][i][j] = x3[c][i + t_r][j + t_c] inside the image, 0 outside;
 //   cutout       0 where the row AND the column are cut -- on the translated image;
-//   gate         u7 < p, else the output is a copy of the input.
+//   gate         u7 < p, else the output is a copy of the input.  p: a launch argument, or (the _dev entry points) a device
+//                word the kernels read when they run -- the one vg_ada_update, the controller at the end of this file, moves.
 // Given u the map is affine in x.  The backward is the transpose of its linear part and reads gy and u alone:
 //   g3 = gy masked and shifted back;  g2 = c g3 + (1 - c) mean_CHW g3;  gx = s g2 + (1 - s) mean_C g2.
 //
@@ -95,6 +96,9 @@ __device__ __forceinline__ Xf decode(const float* __restrict__ u, int policy, fl
   return t;
 }
 
+// the gate's p: the launch's value, or -- the _dev entry points -- the device word as it is when the kernel runs
+__device__ __forceinline__ float gate_p(float p, const float* __restrict__ p_dev) { return p_dev ? p_dev[0] : p; }
+
 // whether output position (i, j) takes a source pixel (it is not cut and its source lies inside the image)
 __device__ __forceinline__ bool kept(const Xf& t, int i, int j, int H, int W) {
   const bool cut = i >= t.r0 && i <= t.r1 && j >= t.c0 && j <= t.c1;
@@ -106,11 +110,11 @@ __device__ __forceinline__ bool kept(const Xf& t, int i, int j, int H, int W) {
 template <bool BWD>
 __global__ __launch_bounds__(NT) void sum_kernel(const float* __restrict__ v, const float* __restrict__ u,
                                                  double* __restrict__ slots, int H, int W, int hw, int chw, int chunks,
-                                                 int policy, float p) {
+                                                 int policy, float p, const float* __restrict__ p_dev) {
   __shared__ double red[NT / 64];
   const int tid = threadIdx.x;
   const int b = blockIdx.x / chunks, chunk = blockIdx.x - b * chunks;
-  const Xf t = decode(u + (size_t)b * 8, policy, p, H, W);
+  const Xf t = decode(u + (size_t)b * 8, policy, gate_p(p, p_dev), H, W);
   double s = 0.0;
   if (t.open) {                                         // (uniform over the workgroup; a closed image's slots are unread)
     const float* img = v + (size_t)b * chw;
@@ -156,9 +160,10 @@ __device__ __forceinline__ double image_sum(const double* __restrict__ slots, in
 template <int C>
 __global__ __launch_bounds__(NT) void fwd_kernel(const float* __restrict__ x, const float* __restrict__ u,
                                                  float* __restrict__ y, const double* __restrict__ slots, int H, int W,
-                                                 int hw, int chunks, int tiles, int policy, float p) {
+                                                 int hw, int chunks, int tiles, int policy, float p,
+                                                 const float* __restrict__ p_dev) {
   const int b = blockIdx.x / tiles, tile = blockIdx.x - b * tiles;
-  const Xf t = decode(u + (size_t)b * 8, policy, p, H, W);
+  const Xf t = decode(u + (size_t)b * 8, policy, gate_p(p, p_dev), H, W);
   const size_t base = (size_t)b * C * hw;
   const bool colour = (policy & VG_AUGMENT_COLOR) != 0;
   float m = 0.f;
@@ -205,9 +210,10 @@ __global__ __launch_bounds__(NT) void fwd_kernel(const float* __restrict__ x, co
 template <int C>
 __global__ __launch_bounds__(NT) void bwd_kernel(const float* __restrict__ gy, const float* __restrict__ u,
                                                  float* __restrict__ gx, const double* __restrict__ slots, int H, int W,
-                                                 int hw, int chunks, int tiles, int policy, float p) {
+                                                 int hw, int chunks, int tiles, int policy, float p,
+                                                 const float* __restrict__ p_dev) {
   const int b = blockIdx.x / tiles, tile = blockIdx.x - b * tiles;
-  const Xf t = decode(u + (size_t)b * 8, policy, p, H, W);
+  const Xf t = decode(u + (size_t)b * 8, policy, gate_p(p, p_dev), H, W);
   const size_t base = (size_t)b * C * hw;
   const bool colour = (policy & VG_AUGMENT_COLOR) != 0;
   float rest = 0.f;                                     // (1 - c) mean_CHW g3: what every element of g2 gets
@@ -249,11 +255,12 @@ __global__ __launch_bounds__(NT) void bwd_kernel(const float* __restrict__ gy, c
 }
 
 template <bool BWD>
-int run(const float* in, const float* u, float* out, int B, int C, int H, int W, int policy, float p, void* workspace,
-        size_t workspace_bytes, hipStream_t st) {
+int run(const float* in, const float* u, float* out, int B, int C, int H, int W, int policy, float p, const float* p_dev,
+        void* workspace, size_t workspace_bytes, hipStream_t st) {
   Plan pl;
   if (!in || !u || !out || in == out || !dims_ok(B, C, H, W) || !make_plan(B, C, H, W, pl)) return VG_ERR_BAD_ARG;
-  if (policy < 1 || policy > 7 || !(p >= 0.f && p <= 1.f)) return VG_ERR_BAD_ARG;      // (a NaN p fails the comparison)
+  // (a NaN p fails the comparison; with the word the host knows no p: whatever the word holds is compared with u7)
+  if (policy < 1 || policy > 7 || (!p_dev && !(p >= 0.f && p <= 1.f))) return VG_ERR_BAD_ARG;
   const bool colour = (policy & VG_AUGMENT_COLOR) != 0;
   double* slots = nullptr;
   if (colour) {
@@ -261,17 +268,17 @@ int run(const float* in, const float* u, float* out, int B, int C, int H, int W,
     if (workspace_bytes < pl.bytes) return VG_ERR_WORKSPACE;
     slots = (double*)workspace;
     hipLaunchKernelGGL(sum_kernel<BWD>, dim3((unsigned)pl.sum_blocks), dim3(NT), 0, st, in, u, slots, H, W, pl.hw,
-                       (int)pl.chw, pl.chunks, policy, p);
+                       (int)pl.chw, pl.chunks, policy, p, p_dev);
     VG_CHECK_LAUNCH();
   }
   auto apply = [&](auto cc) {
     constexpr int CC = decltype(cc)::value;
     if constexpr (BWD)
       hipLaunchKernelGGL(bwd_kernel<CC>, dim3((unsigned)pl.apply_blocks), dim3(NT), 0, st, in, u, out, (const double*)slots,
-                         H, W, pl.hw, pl.chunks, pl.tiles, policy, p);
+                         H, W, pl.hw, pl.chunks, pl.tiles, policy, p, p_dev);
     else
       hipLaunchKernelGGL(fwd_kernel<CC>, dim3((unsigned)pl.apply_blocks), dim3(NT), 0, st, in, u, out, (const double*)slots,
-                         H, W, pl.hw, pl.chunks, pl.tiles, policy, p);
+                         H, W, pl.hw, pl.chunks, pl.tiles, policy, p, p_dev);
   };
   switch (C) {
     case 1: apply(IntC<1>{}); break;
@@ -283,6 +290,41 @@ int run(const float* in, const float* u, float* out, int B, int C, int H, int W,
   return 0;
 }
 
+// ---- the controller of p (Karras et al. 2020, section 3): ONE workgroup -------------------------
+// The sign statistic is an integer: a thread's elements, the wavefront by shuffles, the four wavefronts through LDS --
+// exact, so no order can show.  Thread 0 then owns the eight words: plain loads and stores, nobody else touches them.
+static_assert(sizeof(vg_ada_state) == 32, "eight device words");
+
+__global__ __launch_bounds__(NT) void ada_kernel(const float* __restrict__ d, int B, float threshold, float target,
+                                                 float rate, int interval, vg_ada_state* __restrict__ st) {
+  __shared__ int red[NT / 64];
+  int s = 0;
+  for (int i = threadIdx.x; i < B; i += NT) {
+    const float v = d[i];
+    s += (int)(v > threshold) - (int)(v < threshold);   // (a NaN or a tie: both comparisons fail -- 0, and counted)
+  }
+  const int tot = block_sum<NT>(s, red);
+  if (threadIdx.x != 0) return;
+  float p = st->p;
+  int sign_sum = st->sign_sum + tot, count = st->count + B, calls = st->calls + 1;
+  if (calls >= interval) {                              // (>=, not ==: a state restored under a larger interval still adjusts)
+    const float rt = (float)sign_sum / (float)count;
+    const int dir = (int)(rt > target) - (int)(rt < target);
+    // one rounded product, one rounded sum, never an FMA: three fp32 operations anyone can restate
+    const float step = __fmul_rn((float)count, rate);
+    if (dir != 0) p = __fadd_rn(p, dir > 0 ? step : -step);
+    p = p < 0.f ? 0.f : (p > 1.f ? 1.f : p);            // (a NaN p stays a NaN: it closes every image and shows in the word)
+    st->rt = rt;
+    st->adjustments += 1;
+    sign_sum = count = calls = 0;
+  }
+  st->p = p;
+  st->sign_sum = sign_sum;
+  st->count = count;
+  st->calls = calls;
+  st->reserved[0] = st->reserved[1] = 0;
+}
+
 }  // namespace
 
 extern "C" size_t vg_diff_augment_workspace_bytes(int B, int C, int H, int W) {
@@ -292,10 +334,32 @@ extern "C" size_t vg_diff_augment_workspace_bytes(int B, int C, int H, int W) {
 
 extern "C" int vg_diff_augment_fwd(const float* x, const float* u, float* y, int B, int C, int H, int W, int policy, float p,
                                    void* workspace, size_t workspace_bytes, void* stream) {
-  return run<false>(x, u, y, B, C, H, W, policy, p, workspace, workspace_bytes, (hipStream_t)stream);
+  return run<false>(x, u, y, B, C, H, W, policy, p, nullptr, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int vg_diff_augment_bwd(const float* gy, const float* u, float* gx, int B, int C, int H, int W, int policy, float p,
                                    void* workspace, size_t workspace_bytes, void* stream) {
-  return run<true>(gy, u, gx, B, C, H, W, policy, p, workspace, workspace_bytes, (hipStream_t)stream);
+  return run<true>(gy, u, gx, B, C, H, W, policy, p, nullptr, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" int vg_diff_augment_fwd_dev(const float* x, const float* u, float* y, int B, int C, int H, int W, int policy,
+                                       const float* p_dev, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!p_dev) return VG_ERR_BAD_ARG;
+  return run<false>(x, u, y, B, C, H, W, policy, 0.f, p_dev, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" int vg_diff_augment_bwd_dev(const float* gy, const float* u, float* gx, int B, int C, int H, int W, int policy,
+                                       const float* p_dev, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!p_dev) return VG_ERR_BAD_ARG;
+  return run<true>(gy, u, gx, B, C, H, W, policy, 0.f, p_dev, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" int vg_ada_update(const float* d_real, int B, float threshold, float target, float rate, int interval, void* state,
+                             void* stream) {
+  if (!d_real || !state || ((uintptr_t)state & 3u) != 0 || B < 1 || interval < 1) return VG_ERR_BAD_ARG;
+  if (!isfinite(target) || !isfinite(rate) || rate < 0.f || threshold != threshold) return VG_ERR_BAD_ARG;
+  hipLaunchKernelGGL(ada_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, d_real, B, threshold, target, rate, interval,
+                     (vg_ada_state*)state);
+  VG_CHECK_LAUNCH();
+  return 0;
 }

@@ -745,7 +745,9 @@ class BCELossFn(Function):
 class DiffAugmentFn(Function):
     """Differentiable augmentation of an image batch (ops.diff_augment_fwd).  Given ``u`` the map is
     affine in ``x``: the backward is the transpose of its linear part, from ``gy`` and ``u`` alone -- ``u`` is all that is
-    saved.  ``policy``: the bit set; ``u`` gets no gradient."""
+    saved.  ``policy``: the bit set; ``u`` gets no gradient.  ``p``: a float, or the device word (a one-element fp32 tensor,
+    DESIGN.md section 4.35), which is held by reference and read again when the backward runs: it must not change in
+    between."""
 
     @staticmethod
     def forward(ctx, x, u, policy, p):
@@ -1049,8 +1051,11 @@ def dot_gan_loss(feat, w, bias, kind, label_value, divisor=None):
 def diff_augment(x, u, policy="color,translation,cutout", p=1.0):
     """Differentiable augmentation (Zhao et al. 2020) of ``x`` [B, C, H, W] under ``u`` [B, 8] (`diff_augment_uniforms`):
     ``policy`` names the transforms (any order; applied as colour, translation, cutout), an image is transformed iff
-    ``u[:, 7] < p``.  Differentiable in ``x``; see DiffAugmentFn."""
-    return DiffAugmentFn.apply(x.contiguous(), u, ops.augment_policy(policy), ops.augment_probability(p))
+    ``u[:, 7] < p``.  ``p``: a float in [0, 1], or a one-element fp32 device tensor the kernels read when they run (the word
+    `ops.ada_update` moves).  Differentiable in ``x``; see DiffAugmentFn."""
+    if not isinstance(p, torch.Tensor):
+        p = ops.augment_probability(p)
+    return DiffAugmentFn.apply(x.contiguous(), u, ops.augment_policy(policy), p)
 
 
 def diff_augment_uniforms(batch, device, generator=None, sets=None):

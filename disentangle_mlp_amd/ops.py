@@ -1295,8 +1295,18 @@ def augment_probability(p):
     return v
 
 
+def _augment_word(p, device):
+    """``p`` given as a tensor: the device word of the _dev entry points -- one fp32 element on ``device``."""
+    if p.dtype != torch.float32 or p.numel() != 1 or not p.is_cuda or p.device != device:
+        raise RuntimeError(f"diff_augment: p as a tensor is ONE float32 word on the images' device, got "
+                           f"{tuple(p.shape)} {p.dtype} on {p.device}")
+    return p
+
+
 def _diff_augment(symbol, v, u, policy, p):
-    bits, p = augment_policy(policy), augment_probability(p)
+    bits, word = augment_policy(policy), isinstance(p, torch.Tensor)
+    if not word:
+        p = augment_probability(p)
     _req(v, symbol), _req(u, "u")
     if v.dim() != 4 or u.shape != (v.shape[0], AUGMENT_UNIFORMS) or u.device != v.device:
         raise RuntimeError(f"{symbol}: a [B, C, H, W] tensor and u [B, {AUGMENT_UNIFORMS}] on one device, got "
@@ -1306,6 +1316,8 @@ def _diff_augment(symbol, v, u, policy, p):
     nbytes = lib.vg_diff_augment_workspace_bytes(B, C, H, W)
     if nbytes == 0:
         raise RuntimeError(f"{symbol}: needs B >= 1, 1 <= C <= 4, H, W >= 2 and an image below 2^31 elements, got {tuple(v.shape)}")
+    if word:                                            # (the kernels read it when they run: no host read here)
+        symbol, p = symbol + "_dev", _augment_word(p, v.device).data_ptr()
     out = torch.empty_like(v)
     ws = workspace(nbytes, v.device) if bits & AUGMENT_BITS["color"] else None      # (the image sums: the colour step alone)
     check(getattr(lib, symbol)(v.data_ptr(), u.data_ptr(), out.data_ptr(), B, C, H, W, bits, p, _ptr(ws),
@@ -1317,13 +1329,66 @@ def diff_augment_fwd(x, u, policy, p=1.0):
     """The augmented batch of ``x`` [B, C, H, W] under the rows of ``u`` [B, 8], uniforms in [0, 1): colour, translation,
     cutout in that order, each if ``policy`` names it, on the images with ``u[:, 7] < p``; the others are copied
     (vg_diff_augment_fwd).  Two launches with the colour step, one without; no bound of the output
-    is emitted -- its consumers, the 3-channel convolutions, ask for none."""
+    is emitted -- its consumers, the 3-channel convolutions, ask for none.  ``p``: a float in [0, 1], a launch argument --
+    or a one-element fp32 DEVICE tensor the kernels read when they run (vg_diff_augment_fwd_dev):
+    for the same p the same bits, and a p that moves between replays of a capture."""
     return _diff_augment("vg_diff_augment_fwd", x, u, policy, p)
 
 
 def diff_augment_bwd(gy, u, policy, p=1.0):
-    """The transpose of `diff_augment_fwd`'s linear part applied to ``gy``: it reads ``gy`` and ``u`` alone."""
+    """The transpose of `diff_augment_fwd`'s linear part applied to ``gy``: it reads ``gy`` and ``u`` alone.  ``p`` as
+    there; a device word is read when the backward runs, so it must not change between a forward and its backward."""
     return _diff_augment("vg_diff_augment_bwd", gy, u, policy, p)
+
+
+# ---- adaptive discriminator augmentation: the controller of p (vg_ada_update, DESIGN.md section 4.35) --------------------
+ADA_WORDS = ("p", "sign_sum", "count", "calls", "rt", "adjustments")      # vg_ada_state, words 0..5; 6 and 7 are reserved
+ADA_FLOAT_WORDS = (0, 4)
+
+
+def ada_state(device, p0=0.0):
+    """The controller's eight words (vg_ada_state) as an int32 tensor on ``device``: word 0 holds the bits of ``p0``, the
+    others 0.  ``ada_state(...)[0:1].view(torch.float32)`` is the word `diff_augment_fwd` / `_bwd` take for ``p``."""
+    state = torch.zeros(8, dtype=torch.int32)
+    state[0:1].view(torch.float32)[0] = augment_probability(p0)
+    return state.to(device)
+
+
+def _ada_state_arg(state):
+    if (not isinstance(state, torch.Tensor) or state.dtype != torch.int32 or state.shape != (8,)
+            or not state.is_contiguous()):
+        raise RuntimeError("ada: state is the contiguous int32 tensor of 8 words that ada_state returns")
+    return state
+
+
+def ada_update(d_real, state, threshold=0.0, target=0.6, rate=2e-6, interval=4):
+    """One call of the controller on ``d_real`` (B,), the discriminator's outputs on the real batch: the signs of
+    ``d_real - threshold`` are added to ``state``; the ``interval``-th call since the last adjustment forms ``r_t = sign sum /
+    count`` and moves p by ``count * rate`` towards ``r_t == target``, clamped to [0, 1] (one launch, one workgroup, no host
+    read: capturable).  ``threshold``: 0 for logits, 0.5 for probabilities.  Returns ``state``."""
+    _ada_state_arg(state)
+    interval, threshold, target, rate = int(interval), float(threshold), float(target), float(rate)
+    if interval < 1:
+        raise ValueError(f"ada_update: interval must be >= 1, got {interval}")
+    if math.isnan(threshold) or not math.isfinite(target) or not (math.isfinite(rate) and rate >= 0.0):
+        raise ValueError(f"ada_update: threshold must be a number, target finite, rate finite and >= 0, got "
+                         f"{threshold}, {target}, {rate}")
+    B = d_real.numel() if isinstance(d_real, torch.Tensor) else 0
+    if interval * B >= 1 << 31:
+        raise ValueError(f"ada_update: interval * B must stay below 2^31 (the count is an int32), got {interval} * {B}")
+    _req(d_real, "d_real")
+    if d_real.dim() != 1 or B < 1 or state.device != d_real.device:
+        raise RuntimeError(f"ada_update: d_real is a non-empty vector (B,) on the state's device, got {tuple(d_real.shape)}")
+    check(_lib.load().vg_ada_update(d_real.data_ptr(), B, threshold, target, rate, interval, state.data_ptr(), _stream()),
+          "vg_ada_update")
+    return state
+
+
+def ada_read(state):
+    """``{"p", "sign_sum", "count", "calls", "rt", "adjustments"}`` of ``state`` as Python numbers: ONE host read."""
+    host = _ada_state_arg(state).cpu()
+    floats = host.view(torch.float32)
+    return {name: (float(floats[i]) if i in ADA_FLOAT_WORDS else int(host[i])) for i, name in enumerate(ADA_WORDS)}
 
 
 def reparam_tc_bwd(gz, mu, logvar, eps, z, lse_joint, lse_dim, gloss, beta, alpha, gamma):

@@ -27,6 +27,7 @@ sums, BCE is divided by the *global* batch), which reproduces the global-batch
 gradient.
 """
 import copy
+import math
 import os
 import warnings
 import weakref
@@ -340,6 +341,39 @@ def _parse_diff_augment(diff_augment):
         raise TypeError(f"diff_augment: the policy is a string of names, got {policy!r}")
     bits, p = ops.augment_policy(policy), ops.augment_probability(p)
     return ",".join(n for n, b in ops.AUGMENT_BITS.items() if bits & b), bits, p
+
+
+ADA_DEFAULTS = dict(target=0.6, kimg=500.0, interval=4)      # Karras et al. 2020: r_t held at 0.6, p from 0 to 1 in 500 kimg
+
+
+def _parse_ada(ada):
+    """``ada=True`` or ``dict(target=, kimg=, interval=)`` -> (target, rate, interval) of `ops.ada_update`, with ``rate =
+    1 / (kimg * 1000)``: p moves by (images seen) * rate per adjustment; None for None / False."""
+    if ada is None or ada is False:
+        return None
+    if ada is True:
+        ada = {}
+    if not isinstance(ada, dict):
+        raise TypeError(f"ada must be None, True or a dict(target=, kimg=, interval=), got {ada!r}")
+    unknown = sorted(set(ada) - set(ADA_DEFAULTS))
+    if unknown:
+        raise TypeError(f"ada: unknown key {unknown[0]!r} (known: {', '.join(ADA_DEFAULTS)})")
+    args = dict(ADA_DEFAULTS, **ada)
+    try:
+        target, kimg = float(args["target"]), float(args["kimg"])
+        interval = args["interval"]
+        if isinstance(interval, bool) or int(interval) != interval:
+            raise TypeError
+        interval = int(interval)
+    except (TypeError, ValueError):
+        raise TypeError(f"ada: target and kimg are numbers, interval is an integer, got {args!r}") from None
+    if not (math.isfinite(target) and -1.0 < target < 1.0):
+        raise ValueError(f"ada: target must lie inside (-1, 1), the range of r_t, got {target!r}")
+    if not (math.isfinite(kimg) and kimg > 0.0 and math.isfinite(1.0 / (kimg * 1000.0))):
+        raise ValueError(f"ada: kimg must be finite and > 0, got {kimg!r}")
+    if interval < 1:
+        raise ValueError(f"ada: interval must be >= 1, got {interval!r}")
+    return target, 1.0 / (kimg * 1000.0), interval
 
 
 def sample_labels(rng=None):
@@ -736,11 +770,14 @@ class _GraphedSteps:
     _augment_sets = 0         # parameter sets of ``diff_augment`` an iteration uses (0: the trainer has no discriminator)
     _augment = None           # (policy names, bit set, p) of ``diff_augment``, None when off
     _gan_loss = None          # name of the adversarial loss on the logit (``gan_loss``), None: the reference's BCE on p
+    _ada = None               # (target, rate, interval) of ``ada``, the controller of the augmentation's p; None when off
+    _ada_state = None         # with ``ada``: the controller's eight device words (`ops.ada_state`), never replaced
+    augment_p = None          # with ``ada``: word 0 of them as a one-element fp32 device view -- the p the kernels read
 
     def _setup(self, device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
                beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition, dataset_size,
                data_parallel=None, capturable=None, dip_vae=None, mmd_vae=None, kl_control=None, diff_augment=None,
-               factor_vae=None, gan_loss=None):
+               factor_vae=None, gan_loss=None, ada=None):
         """The constructor body of every trainer (new_betavaegan.py:36-53, new_vae.py:33-37, new_gan.py:47-61).  A trainer
         with a KL term has set `beta` before."""
         has_beta = hasattr(self, "beta")
@@ -755,6 +792,16 @@ class _GraphedSteps:
             if not self._augment_sets:
                 raise TypeError(f"{type(self).__name__} has no discriminator: diff_augment does not apply")
             self._augment = _parse_diff_augment(diff_augment)
+        if ada is not None and ada is not False:
+            if not self._augment_sets:
+                raise TypeError(f"{type(self).__name__} has no discriminator: ada does not apply")
+            self._ada = _parse_ada(ada)
+            if self._augment is None:
+                raise ValueError("ada adapts the probability of diff_augment: pass diff_augment=policy or (policy, p0) with it")
+            if isinstance(diff_augment, str):            # (a bare policy: Karras's start, p = 0 -- not the fixed-p default 1)
+                self._augment = (*self._augment[:2], 0.0)
+            self._ada_state = ops.ada_state(self.device, self._augment[2])
+            self.augment_p = self._ada_state[0:1].view(torch.float32)
         if gan_loss is not None:
             if not self._augment_sets:
                 raise TypeError(f"{type(self).__name__} has no discriminator: gan_loss does not apply")
@@ -1447,7 +1494,10 @@ class _GraphedSteps:
                 self._objective_key(),       # (which objective, and its frozen kernel arguments)
                 tuple(net.training for net in self._nets()),
                 tuple(p.requires_grad for net in self._nets() for p in net.parameters()),
-                *(() if self._augment is None else (self._augment,)),      # (the augmentation's launches: policy and p)
+                # (the augmentation's launches: policy and p -- or, ``ada``: p is a device word, and the controller's frozen
+                # arguments stand in its place)
+                *(() if self._augment is None else (self._augment,) if self._ada is None
+                  else (self._augment[:2], ("ada", *self._ada))),
                 *(() if self._gan_loss is None else (("gan_loss", self._gan_loss),)))      # (the head's loss kernels)
 
     def _head(self, netD, feat, role, label, gb):
@@ -1531,7 +1581,47 @@ class _GraphedSteps:
         """``x`` as the discriminator sees it: through parameter set ``k`` of ``augment``, or as it is without the option."""
         if self._augment is None:
             return x
-        return F.diff_augment(x, augment[k], self._augment[1], self._augment[2])
+        return F.diff_augment(x, augment[k], self._augment[1], self._augment[2] if self._ada is None else self.augment_p)
+
+    # ---- ``ada``: the controller of the augmentation's p (DESIGN.md section 4.35) -----------------------------------------
+    @property
+    def ada(self):
+        """``dict(target=, rate=, interval=)`` of the controller (``rate = 1 / (kimg * 1000)``); None when the option is off."""
+        return None if self._ada is None else dict(zip(("target", "rate", "interval"), self._ada))
+
+    def ada_report(self):
+        """The controller's words as Python numbers (`ops.ada_read`: p, sign_sum, count, calls, rt, adjustments) -- ONE
+        host read, a synchronisation: for logging every now and then, not for every step."""
+        if self._ada is None:
+            raise TypeError(f"{type(self).__name__}: construct with ada=... to read its controller")
+        return ops.ada_read(self._ada_state)
+
+    def _ada_update(self, p_real, s_real):
+        """The LAST launch of an iteration: the controller on the phase-1 real head's output of this iteration -- the logits
+        (threshold 0) under ``gan_loss``, else the probabilities (threshold 0.5).  Every augmentation launch of the
+        iteration, forward and backward, ran before it and read the p the previous iteration left.  Returns the two
+        outputs it adds: clones of words 0 and 4 taken behind the update ({} without the option)."""
+        if self._ada is None:
+            return {}
+        d, threshold = (p_real, 0.5) if s_real is None else (s_real, 0.0)
+        ops.ada_update(d.detach().reshape(-1), self._ada_state, threshold, *self._ada)
+        words = self._ada_state.view(torch.float32)
+        return dict(augment_p=words[0].clone(), ada_rt=words[4].clone())
+
+    def _ada_checkpoint(self):
+        """The additional checkpoint key -- present only with ``ada``: the eight words as a CPU tensor (one host read)."""
+        return {} if self._ada is None else {"ada_state": self._ada_state.to("cpu", copy=True)}
+
+    @torch.no_grad()
+    def _ada_restore(self, ck):
+        """The controller's words from their checkpoint key, copied into the existing buffer -- a captured iteration reads
+        and writes it; a checkpoint without the key leaves them as they are."""
+        sd = ck.get("ada_state") if self._ada is not None else None
+        if sd is None:
+            return
+        if not isinstance(sd, torch.Tensor) or sd.dtype != torch.int32 or tuple(sd.shape) != (8,):
+            raise ValueError("ada_state: the checkpoint's key is not the controller's eight int32 words")
+        self._ada_state.copy_(sd)
 
     def _zero(self, net, flat, opt=None, grad_hook=None, update_ema=True):
         """A phase's zeroing.  ``opt``: the optimizer whose `step` ends the phase -- the big Linear weights the coming
@@ -1778,7 +1868,27 @@ class BetaVAEGANTrainer(_GraphedSteps):
     them, so every random stream is what it is without the keyword.  The returned dict keeps its keys -- ``D_x_sum`` stays
     the sum of ``sigmoid(logit_real)`` -- and gains ``D_logit_real_sum`` and ``D_logit_fake_sum``, the sums of the phase-1
     logits.  No checkpoint key; data parallel: nothing new (replica-local head, SUM exchange, global divisor).  An
-    unknown name is a ValueError.  Composes with every other keyword: none of them touches the head."""
+    unknown name is a ValueError.  Composes with every other keyword: none of them touches the head.
+
+    ``ada=True`` or ``dict(target=0.6, kimg=500, interval=4)`` (default: none -- then every launch, capture key, draw,
+    checkpoint key and bit is what it was): adaptive discriminator augmentation (Karras et al. 2020, section 3; DESIGN.md
+    section 4.35).  It needs ``diff_augment`` (a ValueError without) and takes its probability over: p lives in a device
+    word, `augment_p`, that every augmentation kernel reads when it runs, and a controller (`ops.ada_update`, one
+    single-workgroup launch) moves it.  Per iteration the controller adds the signs of the phase-1 REAL head's outputs --
+    the logits against 0 under ``gan_loss``, else the probabilities against 1/2 -- to two integer words; every ``interval``
+    iterations it forms the overfitting heuristic ``r_t = E[sign(D(real))]`` of those iterations and moves p by
+    ``(images seen) / (kimg * 1000)`` towards ``r_t == target``, clamped to [0, 1]: ``kimg`` thousand images take p from 0 to
+    1.  With the keyword a bare policy string starts at ``p = 0`` (Karras), ``(policy, p0)`` at ``p0``.  The controller is the
+    LAST launch of the iteration, behind an owned network's phase: every augmentation launch of iteration t, forward and
+    backward, reads the p that iteration t - 1 left, so no backward ever sees another gate than its forward.  It is inside
+    the capture, and the capture key carries ``("ada", target, rate, interval)`` in place of p: a p that moves replays ONE
+    graph.  The returned dict gains ``augment_p`` and ``ada_rt``, device scalars cloned from the words behind the update
+    (``ada_rt`` is 0 before the first adjustment); `ada_report` reads all the words in one host read; `ada` reads the
+    arguments.  Checkpoints gain ``ada_state``, the eight words as a CPU tensor; `load` / `load_in_place` copy it into the
+    existing buffer, and a checkpoint without it leaves the state as it is.  Data parallel: replica-local, as every other
+    option here -- each rank counts the signs of ITS batch and moves ITS word, nothing is exchanged, so the ranks' p may
+    drift apart by a few steps.  Composes with ``gan_loss``, ``factor_vae``, the EMA, clipping and the schedules: none of them
+    touches the word.  Whether it holds ``D_x`` off 1 on a small set has not been measured here."""
 
     _parts = (_Part("netEG", VAE, "optimizerEG", "flat_eg", "eg", "encoder_decoder_optimizer"),              # :41, :49
               _Part("netD", Discriminator_celeba, "optimizerD", "flat_d", "d", "discriminator_optimizer"))    # :43, :50
@@ -1794,12 +1904,12 @@ class BetaVAEGANTrainer(_GraphedSteps):
                  lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0, decoupled_weight_decay: bool = False,
                  device_hyper: Optional[bool] = None, ema_decay=None, tc_decomposition=None,
                  dataset_size: Optional[int] = None, dip_vae=None, mmd_vae=None, kl_control=None, diff_augment=None,
-                 factor_vae=None, gan_loss=None):
+                 factor_vae=None, gan_loss=None, ada=None):
         self.beta = float(beta)
         self._setup(device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
                     beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition,
                     dataset_size, data_parallel, capturable, dip_vae, mmd_vae, kl_control,      # (lr: hard-coded 1e-3 at new_betavaegan.py:49-50)
-                    diff_augment, factor_vae, gan_loss)
+                    diff_augment, factor_vae, gan_loss, ada)
         self._eg_params = [p for p in self.netEG.parameters() if p.dim() == 4]   # convolution filters
         self._d_params = [p for p in self.netD.parameters() if p.dim() == 4]
 
@@ -1894,6 +2004,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
         ops.invalidate_packed_filters(self._eg_params)
         out.update(kld=kld.detach(), mse_enc=mse3.detach(), **self._kl_part_outputs(parts))
         out.update(self._owned_phase(own, data.size(0), gb, grad_hook))      # (``factor_vae``: the critic's phase; else nothing)
+        out.update(self._ada_update(p_real, s_real))          # (``ada``: the controller, the iteration's last launch; else nothing)
         self.iteration += 1
         return out
 
@@ -2103,6 +2214,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
             **self._schedule_checkpoint(),       # (additional keys, only when a schedule exists)
             **self._ema_checkpoint(),            # (encoder_decoder_ema, only with an average)
             **self._owned_checkpoint(),          # (latent_critic, latent_critic_optimizer: only with factor_vae)
+            **self._ada_checkpoint(),            # (ada_state: only with ada)
         }
 
     def save(self, path, epoch, legacy_format=False):
@@ -2122,6 +2234,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
         self._schedule_restore(ck)
         self._ema_restore(ck)
         self._owned_restore(ck)
+        self._ada_restore(ck)
         self.clear_nonfinite()                               # a good checkpoint is the way back from a NonFiniteError
         return ck["epoch"]
 
@@ -2153,6 +2266,7 @@ class BetaVAEGANTrainer(_GraphedSteps):
         self._schedule_restore(ck, in_place=True)
         self._ema_restore(ck)
         self._owned_restore(ck, in_place=True)
+        self._ada_restore(ck)
         self.clear_nonfinite()
         return ck["epoch"]
 
@@ -2166,7 +2280,8 @@ class VAETrainer(_GraphedSteps):
     there -- the covariance is that of this replica's batch.  ``mmd_vae``: as there -- ``prior`` is drawn after ``eps``.
     ``kl_control``: as there -- the per-dimension sums are those of this replica's batch.  ``factor_vae``: as there -- the
     critic's phase follows the one optimizer step, ``permute`` is drawn last, and the cross-entropy's divisor is 2 x (this
-    replica's batch x the world size).  There is no discriminator, so a ``diff_augment`` or a ``gan_loss`` is a TypeError."""
+    replica's batch x the world size).  There is no discriminator, so a ``diff_augment``, a ``gan_loss`` or an ``ada`` is a
+    TypeError."""
 
     _parts = (_Part("model", VAE, "optimizer", "flat", "vae", "optimizer"),)
     _latents = ("eps",)
@@ -2178,12 +2293,12 @@ class VAETrainer(_GraphedSteps):
                  skip_nonfinite: bool = False, lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0,
                  decoupled_weight_decay: bool = False, device_hyper: Optional[bool] = None, ema_decay=None,
                  tc_decomposition=None, dataset_size: Optional[int] = None, dip_vae=None, mmd_vae=None, kl_control=None,
-                 diff_augment=None, factor_vae=None, gan_loss=None):
+                 diff_augment=None, factor_vae=None, gan_loss=None, ada=None):
         self.beta = float(beta)
         self._setup(device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
                     beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition,
                     dataset_size, capturable=capturable, dip_vae=dip_vae, mmd_vae=mmd_vae, kl_control=kl_control,
-                    diff_augment=diff_augment, factor_vae=factor_vae, gan_loss=gan_loss)
+                    diff_augment=diff_augment, factor_vae=factor_vae, gan_loss=gan_loss, ada=ada)
 
     def step(self, data, eps=None, grad_hook=None, prior=None, permute=None):
         """``grad_hook(phase, net)`` (tests): called with ``("VAE", model)`` right before the optimizer step -- and, with
@@ -2242,7 +2357,10 @@ class GANTrainer(_GraphedSteps):
     ``netG_ema``; the discriminator is not averaged.  ``diff_augment``: as BetaVAEGANTrainer, with three parameter sets,
     uniforms ``(3, B, 8)``: set 0 on ``data`` and set 1 on ``fake.detach()`` in the discriminator phase, set 2 on ``fake`` in
     the generator phase.  ``gan_loss``: as BetaVAEGANTrainer -- roles "real" and "fake" in the discriminator phase, "gen"
-    with ``real_label`` for ``errG``; the dict gains ``D_logit_real_sum`` and ``D_logit_fake_sum``."""
+    with ``real_label`` for ``errG``; the dict gains ``D_logit_real_sum`` and ``D_logit_fake_sum``.  ``ada``: as
+    BetaVAEGANTrainer -- the controller reads the discriminator phase's real head and is the iteration's last launch, behind
+    the generator's optimizer step; replica-local under data parallelism; the checkpoint gains ``ada_state``, and `load`
+    restores it with everything else `checkpoint` wrote (there is no `load_in_place` here)."""
 
     _parts = (_Part("netG", Generator_celeba, "optimizerG", "flat_g", "g", "G_trainer"),
               _Part("netD", Discriminator_celeba, "optimizerD", "flat_d", "d", "D_trainer"))
@@ -2257,11 +2375,11 @@ class GANTrainer(_GraphedSteps):
                  skip_nonfinite: bool = False, lr_scheduler=None, beta_schedule=None, weight_decay: float = 0.0,
                  decoupled_weight_decay: bool = False, device_hyper: Optional[bool] = None, ema_decay=None,
                  tc_decomposition=None, dataset_size: Optional[int] = None, dip_vae=None, mmd_vae=None, kl_control=None,
-                 diff_augment=None, factor_vae=None, gan_loss=None):
+                 diff_augment=None, factor_vae=None, gan_loss=None, ada=None):
         self._setup(device, seed, lr, opt, fused_adam, graph, nonfinite_guard, max_grad_norm, skip_nonfinite, lr_scheduler,
                     beta_schedule, weight_decay, decoupled_weight_decay, device_hyper, ema_decay, tc_decomposition,
                     dataset_size, data_parallel, dip_vae=dip_vae, mmd_vae=mmd_vae, kl_control=kl_control,
-                    diff_augment=diff_augment, factor_vae=factor_vae, gan_loss=gan_loss)
+                    diff_augment=diff_augment, factor_vae=factor_vae, gan_loss=gan_loss, ada=ada)
 
     def step(self, data, noise=None, real_label=0.9, fake_label=0.1, global_batch: Optional[int] = None,
              grad_hook=None, augment=None):
@@ -2304,6 +2422,7 @@ class GANTrainer(_GraphedSteps):
                    D_x_sum=p_real.detach().sum())
         if s_real is not None:
             out.update(D_logit_real_sum=s_real.detach().sum(), D_logit_fake_sum=s_fake.detach().sum())
+        out.update(self._ada_update(p_real, s_real))          # (``ada``: the controller, the iteration's last launch; else nothing)
         return out
 
     def train_epoch(self, loader, label_rng=None, max_iterations=None):
@@ -2336,4 +2455,19 @@ class GANTrainer(_GraphedSteps):
     def checkpoint(self, epoch):
         return {"epoch": epoch, "netG": self.netG.state_dict(), "netD": self.netD.state_dict(),
                 "G_trainer": self.optimizerG.state_dict(), "D_trainer": self.optimizerD.state_dict(),
-                **self._schedule_checkpoint(), **self._ema_checkpoint()}
+                **self._schedule_checkpoint(), **self._ema_checkpoint(), **self._ada_checkpoint()}
+
+    def load(self, path_or_dict):
+        """The way back from `checkpoint`: both networks, both optimizers, and what the options added -- the schedules, the
+        averaged generator, the controller's words of ``ada`` (copied into the existing buffer; a checkpoint without the
+        key keeps the current state).  Returns the epoch."""
+        ck = path_or_dict if isinstance(path_or_dict, dict) else torch.load(path_or_dict, map_location=self.device)
+        self.netG.load_state_dict(ck["netG"])
+        self.netD.load_state_dict(ck["netD"])
+        self.optimizerG.load_state_dict(ck["G_trainer"])
+        self.optimizerD.load_state_dict(ck["D_trainer"])
+        self._schedule_restore(ck)
+        self._ema_restore(ck)
+        self._ada_restore(ck)
+        self.clear_nonfinite()
+        return ck["epoch"]

@@ -53,7 +53,8 @@ extern "C" {
  * csrc/reparam_dip.hip; the three vg_agg_posterior_* of csrc/agg_posterior.hip; the five vg_reparam_mmd_* of
  * csrc/reparam_mmd.hip; the four vg_pair_* of csrc/pair_dist.hip; the two vg_recon_quality* of
  * csrc/recon_quality.hip; the five vg_reparam_klc_* of csrc/reparam_klc.hip; the three vg_diff_augment_* of
- * csrc/diff_augment.hip; the seven of csrc/factor_vae.hip; the three of csrc/gan_loss.hip) change
+ * csrc/diff_augment.hip; the seven of csrc/factor_vae.hip; the three of csrc/gan_loss.hip;
+ * vg_diff_augment_fwd_dev, vg_diff_augment_bwd_dev, vg_ada_update) change
  * nothing an existing caller sees and keep the version: a binding that needs them and finds a library without them
  * fails at the symbol lookup, as loudly. */
 #define VG_ABI_VERSION 7
@@ -735,6 +736,45 @@ int vg_diff_augment_fwd(const float* x, const float* u, float* y, int B, int C, 
                         void* workspace, size_t workspace_bytes, void* stream);
 int vg_diff_augment_bwd(const float* gy, const float* u, float* gx, int B, int C, int H, int W, int policy, float p,
                         void* workspace, size_t workspace_bytes, void* stream);
+/* The same two with p read from DEVICE memory (p_dev[0], fp32) by the kernels when they run: a p that changes between
+ * replays of an iteration captured in a HIP graph (vg_ada_update below writes one).  The same kernels, the same launches
+ * and, for the same p, the value entry points' bits element for element.  The host knows no p, so none is range-checked:
+ * an image is transformed iff u7 < p_dev[0] whatever the word holds -- a word <= 0 closes every image, one > u7's largest
+ * value opens every image, a NaN closes every image (u7 < NaN is false).  The backward reads the word when IT runs: the
+ * word must not change between a forward and its backward, or the transpose is that of another gate.  A NULL p_dev is
+ * VG_ERR_BAD_ARG; everything else as above. */
+int vg_diff_augment_fwd_dev(const float* x, const float* u, float* y, int B, int C, int H, int W, int policy,
+                            const float* p_dev, void* workspace, size_t workspace_bytes, void* stream);
+int vg_diff_augment_bwd_dev(const float* gy, const float* u, float* gx, int B, int C, int H, int W, int policy,
+                            const float* p_dev, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Adaptive discriminator augmentation (Karras et al. 2020, "Training GANs with Limited Data", section 3; DESIGN.md section
+ * 4.35): the controller of the p above.  `state`: eight device words (32 bytes, 4-byte aligned) -- word 0 is the p_dev of
+ * the _dev entry points.  One call per iteration on d_real[B], the discriminator's outputs on the real batch (logits with
+ * threshold 0, probabilities with threshold 0.5):
+ *   sign_sum += sum_b ((d[b] > threshold) - (d[b] < threshold))     integers: exact, no order shows; a NaN or a tie adds 0
+ *   count += B;  calls += 1                                          (and is counted)
+ * and once calls reaches `interval`:
+ *   r_t = (float)sign_sum / (float)count                             one fp32 division
+ *   s = (r_t > target) - (r_t < target)
+ *   p = clamp(p + s * ((float)count * rate), 0, 1)                   ONE rounded fp32 product, ONE rounded fp32 sum, no FMA;
+ *                                                                    s = 0 leaves p as it is; a NaN p stays a NaN
+ *   rt = r_t;  adjustments += 1;  sign_sum = count = calls = 0.
+ * With rate = 1 / (kimg * 1000) the step is Karras's batch * interval / (kimg * 1000), exact for a ragged last batch.
+ * One workgroup, no floating-point atomic, plain stores, no host read: capturable.  The caller keeps interval * B below
+ * 2^31.  VG_ERR_BAD_ARG before the launch: a NULL d_real or state, a state off a 4-byte boundary, B < 1, interval < 1, a
+ * NaN threshold, a non-finite target or rate, rate < 0. */
+typedef struct vg_ada_state {
+  float p;           /* [0] the augmentation probability */
+  int sign_sum;      /* [1] sum of the signs since the last adjustment */
+  int count;         /* [2] outputs seen since the last adjustment */
+  int calls;         /* [3] calls since the last adjustment */
+  float rt;          /* [4] r_t of the last adjustment (0 before the first) */
+  int adjustments;   /* [5] adjustments made */
+  int reserved[2];   /* [6], [7] written 0 */
+} vg_ada_state;
+int vg_ada_update(const float* d_real, int B, float threshold, float target, float rate, int interval, void* state,
+                  void* stream);
 
 /* out[i] = g[i] * s[0] with s a DEVICE scalar: applies the upstream gradient of a
  * loss scalar to a gradient precomputed by the fused loss kernels, without a

@@ -26,6 +26,27 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
     if (e__ != hipSuccess) return (int)e__;       \
   } while (0)
 
+// ---- a scheduled scalar -----------------------------------------------------------------------
+// A hyperparameter that may change between the replays of a captured iteration -- beta, the KL capacity, FactorVAE's
+// gamma, the augmentation's p, the GAN label -- reaches its kernel as ONE argument: a host float, or one fp32 word on the
+// device that the kernel reads as it is when it runs.  An entry point and its `_dev` twin differ only in how they build
+// it; the kernel reads it once, at the top, and the same fp32 value gives the same bits either way.
+struct Word {
+  float v;
+  bool dev;            // built by word_at: `p` is what counts, NULL included (the host's view; the kernel looks at p alone)
+  const float* p;
+};
+inline Word word(float v) { return {v, false, nullptr}; }
+inline Word word_at(const float* p) { return {0.f, true, p}; }
+// an entry that takes both in one signature (`target, target_dev`): the word where there is one
+inline Word word_or(float v, const float* p) { return p ? word_at(p) : word(v); }
+// what is checked of a float alone (a range, finiteness) asks this first: of a word the host knows no value
+inline bool is_float(Word w) { return !w.dev; }
+// a `_dev` entry given NULL for a word: every launcher refuses it (VG_ERR_BAD_ARG) before any launch, through this
+template <class... W>
+inline bool words_ok(W... w) { return ((!w.dev || w.p) && ...); }
+__device__ __forceinline__ float read_word(Word w) { return w.p ? w.p[0] : w.v; }
+
 // D(32x32) += A(32x2) * B(2x32).  Lane l supplies A[i=l&31][k=l>>5] and
 // B[k=l>>5][j=l&31]; D register r of lane l is D[i=(r&3)+8*(r>>2)+4*(l>>5)][j=l&31].
 __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {

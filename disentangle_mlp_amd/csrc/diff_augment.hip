@@ -96,9 +96,6 @@ __device__ __forceinline__ Xf decode(const float* __restrict__ u, int policy, fl
   return t;
 }
 
-// the gate's p: the launch's value, or -- the _dev entry points -- the device word as it is when the kernel runs
-__device__ __forceinline__ float gate_p(float p, const float* __restrict__ p_dev) { return p_dev ? p_dev[0] : p; }
-
 // whether output position (i, j) takes a source pixel (it is not cut and its source lies inside the image)
 __device__ __forceinline__ bool kept(const Xf& t, int i, int j, int H, int W) {
   const bool cut = i >= t.r0 && i <= t.r1 && j >= t.c0 && j <= t.c1;
@@ -110,11 +107,11 @@ __device__ __forceinline__ bool kept(const Xf& t, int i, int j, int H, int W) {
 template <bool BWD>
 __global__ __launch_bounds__(NT) void sum_kernel(const float* __restrict__ v, const float* __restrict__ u,
                                                  double* __restrict__ slots, int H, int W, int hw, int chw, int chunks,
-                                                 int policy, float p, const float* __restrict__ p_dev) {
+                                                 int policy, Word p) {
   __shared__ double red[NT / 64];
   const int tid = threadIdx.x;
   const int b = blockIdx.x / chunks, chunk = blockIdx.x - b * chunks;
-  const Xf t = decode(u + (size_t)b * 8, policy, gate_p(p, p_dev), H, W);
+  const Xf t = decode(u + (size_t)b * 8, policy, read_word(p), H, W);
   double s = 0.0;
   if (t.open) {                                         // (uniform over the workgroup; a closed image's slots are unread)
     const float* img = v + (size_t)b * chw;
@@ -160,10 +157,9 @@ __device__ __forceinline__ double image_sum(const double* __restrict__ slots, in
 template <int C>
 __global__ __launch_bounds__(NT) void fwd_kernel(const float* __restrict__ x, const float* __restrict__ u,
                                                  float* __restrict__ y, const double* __restrict__ slots, int H, int W,
-                                                 int hw, int chunks, int tiles, int policy, float p,
-                                                 const float* __restrict__ p_dev) {
+                                                 int hw, int chunks, int tiles, int policy, Word p) {
   const int b = blockIdx.x / tiles, tile = blockIdx.x - b * tiles;
-  const Xf t = decode(u + (size_t)b * 8, policy, gate_p(p, p_dev), H, W);
+  const Xf t = decode(u + (size_t)b * 8, policy, read_word(p), H, W);
   const size_t base = (size_t)b * C * hw;
   const bool colour = (policy & VG_AUGMENT_COLOR) != 0;
   float m = 0.f;
@@ -210,10 +206,9 @@ __global__ __launch_bounds__(NT) void fwd_kernel(const float* __restrict__ x, co
 template <int C>
 __global__ __launch_bounds__(NT) void bwd_kernel(const float* __restrict__ gy, const float* __restrict__ u,
                                                  float* __restrict__ gx, const double* __restrict__ slots, int H, int W,
-                                                 int hw, int chunks, int tiles, int policy, float p,
-                                                 const float* __restrict__ p_dev) {
+                                                 int hw, int chunks, int tiles, int policy, Word p) {
   const int b = blockIdx.x / tiles, tile = blockIdx.x - b * tiles;
-  const Xf t = decode(u + (size_t)b * 8, policy, gate_p(p, p_dev), H, W);
+  const Xf t = decode(u + (size_t)b * 8, policy, read_word(p), H, W);
   const size_t base = (size_t)b * C * hw;
   const bool colour = (policy & VG_AUGMENT_COLOR) != 0;
   float rest = 0.f;                                     // (1 - c) mean_CHW g3: what every element of g2 gets
@@ -255,12 +250,12 @@ __global__ __launch_bounds__(NT) void bwd_kernel(const float* __restrict__ gy, c
 }
 
 template <bool BWD>
-int run(const float* in, const float* u, float* out, int B, int C, int H, int W, int policy, float p, const float* p_dev,
-        void* workspace, size_t workspace_bytes, hipStream_t st) {
+int run(const float* in, const float* u, float* out, int B, int C, int H, int W, int policy, Word p, void* workspace,
+        size_t workspace_bytes, hipStream_t st) {
   Plan pl;
   if (!in || !u || !out || in == out || !dims_ok(B, C, H, W) || !make_plan(B, C, H, W, pl)) return VG_ERR_BAD_ARG;
   // (a NaN p fails the comparison; with the word the host knows no p: whatever the word holds is compared with u7)
-  if (policy < 1 || policy > 7 || (!p_dev && !(p >= 0.f && p <= 1.f))) return VG_ERR_BAD_ARG;
+  if (policy < 1 || policy > 7 || !words_ok(p) || (is_float(p) && !(p.v >= 0.f && p.v <= 1.f))) return VG_ERR_BAD_ARG;
   const bool colour = (policy & VG_AUGMENT_COLOR) != 0;
   double* slots = nullptr;
   if (colour) {
@@ -268,17 +263,17 @@ int run(const float* in, const float* u, float* out, int B, int C, int H, int W,
     if (workspace_bytes < pl.bytes) return VG_ERR_WORKSPACE;
     slots = (double*)workspace;
     hipLaunchKernelGGL(sum_kernel<BWD>, dim3((unsigned)pl.sum_blocks), dim3(NT), 0, st, in, u, slots, H, W, pl.hw,
-                       (int)pl.chw, pl.chunks, policy, p, p_dev);
+                       (int)pl.chw, pl.chunks, policy, p);
     VG_CHECK_LAUNCH();
   }
   auto apply = [&](auto cc) {
     constexpr int CC = decltype(cc)::value;
     if constexpr (BWD)
       hipLaunchKernelGGL(bwd_kernel<CC>, dim3((unsigned)pl.apply_blocks), dim3(NT), 0, st, in, u, out, (const double*)slots,
-                         H, W, pl.hw, pl.chunks, pl.tiles, policy, p, p_dev);
+                         H, W, pl.hw, pl.chunks, pl.tiles, policy, p);
     else
       hipLaunchKernelGGL(fwd_kernel<CC>, dim3((unsigned)pl.apply_blocks), dim3(NT), 0, st, in, u, out, (const double*)slots,
-                         H, W, pl.hw, pl.chunks, pl.tiles, policy, p, p_dev);
+                         H, W, pl.hw, pl.chunks, pl.tiles, policy, p);
   };
   switch (C) {
     case 1: apply(IntC<1>{}); break;
@@ -334,24 +329,22 @@ extern "C" size_t vg_diff_augment_workspace_bytes(int B, int C, int H, int W) {
 
 extern "C" int vg_diff_augment_fwd(const float* x, const float* u, float* y, int B, int C, int H, int W, int policy, float p,
                                    void* workspace, size_t workspace_bytes, void* stream) {
-  return run<false>(x, u, y, B, C, H, W, policy, p, nullptr, workspace, workspace_bytes, (hipStream_t)stream);
+  return run<false>(x, u, y, B, C, H, W, policy, word(p), workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int vg_diff_augment_bwd(const float* gy, const float* u, float* gx, int B, int C, int H, int W, int policy, float p,
                                    void* workspace, size_t workspace_bytes, void* stream) {
-  return run<true>(gy, u, gx, B, C, H, W, policy, p, nullptr, workspace, workspace_bytes, (hipStream_t)stream);
+  return run<true>(gy, u, gx, B, C, H, W, policy, word(p), workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int vg_diff_augment_fwd_dev(const float* x, const float* u, float* y, int B, int C, int H, int W, int policy,
                                        const float* p_dev, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!p_dev) return VG_ERR_BAD_ARG;
-  return run<false>(x, u, y, B, C, H, W, policy, 0.f, p_dev, workspace, workspace_bytes, (hipStream_t)stream);
+  return run<false>(x, u, y, B, C, H, W, policy, word_at(p_dev), workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int vg_diff_augment_bwd_dev(const float* gy, const float* u, float* gx, int B, int C, int H, int W, int policy,
                                        const float* p_dev, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!p_dev) return VG_ERR_BAD_ARG;
-  return run<true>(gy, u, gx, B, C, H, W, policy, 0.f, p_dev, workspace, workspace_bytes, (hipStream_t)stream);
+  return run<true>(gy, u, gx, B, C, H, W, policy, word_at(p_dev), workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int vg_ada_update(const float* d_real, int B, float threshold, float target, float rate, int interval, void* state,

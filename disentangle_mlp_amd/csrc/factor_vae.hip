@@ -74,15 +74,9 @@ int permute_launch(const float* z, const float* u, float* z_perm, int B, int D, 
 }
 
 // ---- the encoder phase's loss ---------------------------------------------------------------------------------------------------
-template <bool DEV>
 __global__ __launch_bounds__(NT) void factor_tc_fwd_kernel(const float* __restrict__ logits, const float* __restrict__ kl,
-                                                           float* __restrict__ out4, int B, float beta,
-                                                           const float* __restrict__ beta_dev, float gamma,
-                                                           const float* __restrict__ gamma_dev) {
-  if constexpr (DEV) {
-    beta = beta_dev[0];
-    gamma = gamma_dev[0];
-  }
+                                                           float* __restrict__ out4, int B, Word beta_w, Word gamma_w) {
+  const float beta = read_word(beta_w), gamma = read_word(gamma_w);
   __shared__ double red[NT / 64];
   double s = 0.0, n = 0.0;
   for (int b = threadIdx.x; b < B; b += NT) {
@@ -100,15 +94,9 @@ __global__ __launch_bounds__(NT) void factor_tc_fwd_kernel(const float* __restri
   out4[3] = (float)q;
 }
 
-template <bool DEV>
-__global__ __launch_bounds__(NT) void factor_tc_bwd_kernel(const float* __restrict__ gloss, float beta,
-                                                           const float* __restrict__ beta_dev, float gamma,
-                                                           const float* __restrict__ gamma_dev, float* __restrict__ glogits,
-                                                           float* __restrict__ gkl, int B) {
-  if constexpr (DEV) {
-    beta = beta_dev[0];
-    gamma = gamma_dev[0];
-  }
+__global__ __launch_bounds__(NT) void factor_tc_bwd_kernel(const float* __restrict__ gloss, Word beta_w, Word gamma_w,
+                                                           float* __restrict__ glogits, float* __restrict__ gkl, int B) {
+  const float beta = read_word(beta_w), gamma = read_word(gamma_w);
   const float gl = gloss[0];
   const float g = gamma * gl;
   const int b = blockIdx.x * NT + threadIdx.x;
@@ -156,21 +144,16 @@ __global__ __launch_bounds__(NT) void factor_critic_loss_kernel(const float* __r
 
 constexpr int MAX_ROWS = 1 << 28;      // logits of 2 * MAX_ROWS rows are indexed in int
 
-template <bool DEV>
-int tc_fwd(const float* logits, const float* kl, float* out4, int B, float beta, const float* beta_dev, float gamma,
-           const float* gamma_dev, hipStream_t st) {
-  if (!logits || !kl || !out4 || B < 1 || B > MAX_ROWS || (DEV && (!beta_dev || !gamma_dev))) return VG_ERR_BAD_ARG;
-  hipLaunchKernelGGL(factor_tc_fwd_kernel<DEV>, dim3(1), dim3(NT), 0, st, logits, kl, out4, B, beta, beta_dev, gamma, gamma_dev);
+int tc_fwd(const float* logits, const float* kl, float* out4, int B, Word beta, Word gamma, hipStream_t st) {
+  if (!logits || !kl || !out4 || B < 1 || B > MAX_ROWS || !words_ok(beta, gamma)) return VG_ERR_BAD_ARG;
+  hipLaunchKernelGGL(factor_tc_fwd_kernel, dim3(1), dim3(NT), 0, st, logits, kl, out4, B, beta, gamma);
   VG_CHECK_LAUNCH();
   return 0;
 }
 
-template <bool DEV>
-int tc_bwd(const float* gloss, float beta, const float* beta_dev, float gamma, const float* gamma_dev, float* glogits,
-           float* gkl, int B, hipStream_t st) {
-  if (!gloss || !glogits || !gkl || B < 1 || B > MAX_ROWS || (DEV && (!beta_dev || !gamma_dev))) return VG_ERR_BAD_ARG;
-  hipLaunchKernelGGL(factor_tc_bwd_kernel<DEV>, dim3(cdiv(B, NT)), dim3(NT), 0, st, gloss, beta, beta_dev, gamma, gamma_dev,
-                     glogits, gkl, B);
+int tc_bwd(const float* gloss, Word beta, Word gamma, float* glogits, float* gkl, int B, hipStream_t st) {
+  if (!gloss || !glogits || !gkl || B < 1 || B > MAX_ROWS || !words_ok(beta, gamma)) return VG_ERR_BAD_ARG;
+  hipLaunchKernelGGL(factor_tc_bwd_kernel, dim3(cdiv(B, NT)), dim3(NT), 0, st, gloss, beta, gamma, glogits, gkl, B);
   VG_CHECK_LAUNCH();
   return 0;
 }
@@ -195,25 +178,25 @@ extern "C" size_t vg_factor_tc_workspace_bytes(int B, int D) {
 extern "C" int vg_factor_tc_fwd(const float* logits, const float* kl, float* out4, int B, float beta, float gamma,
                                 void* workspace, size_t workspace_bytes, void* stream) {
   (void)workspace, (void)workspace_bytes;
-  return tc_fwd<false>(logits, kl, out4, B, beta, nullptr, gamma, nullptr, (hipStream_t)stream);
+  return tc_fwd(logits, kl, out4, B, word(beta), word(gamma), (hipStream_t)stream);
 }
 
 extern "C" int vg_factor_tc_fwd_dev(const float* logits, const float* kl, float* out4, int B, const float* beta_dev,
                                     const float* gamma_dev, void* workspace, size_t workspace_bytes, void* stream) {
   (void)workspace, (void)workspace_bytes;
-  return tc_fwd<true>(logits, kl, out4, B, 0.f, beta_dev, 0.f, gamma_dev, (hipStream_t)stream);
+  return tc_fwd(logits, kl, out4, B, word_at(beta_dev), word_at(gamma_dev), (hipStream_t)stream);
 }
 
 extern "C" int vg_factor_tc_bwd(const float* gloss, float beta, float gamma, float* glogits, float* gkl, int B, void* workspace,
                                 size_t workspace_bytes, void* stream) {
   (void)workspace, (void)workspace_bytes;
-  return tc_bwd<false>(gloss, beta, nullptr, gamma, nullptr, glogits, gkl, B, (hipStream_t)stream);
+  return tc_bwd(gloss, word(beta), word(gamma), glogits, gkl, B, (hipStream_t)stream);
 }
 
 extern "C" int vg_factor_tc_bwd_dev(const float* gloss, const float* beta_dev, const float* gamma_dev, float* glogits,
                                     float* gkl, int B, void* workspace, size_t workspace_bytes, void* stream) {
   (void)workspace, (void)workspace_bytes;
-  return tc_bwd<true>(gloss, 0.f, beta_dev, 0.f, gamma_dev, glogits, gkl, B, (hipStream_t)stream);
+  return tc_bwd(gloss, word_at(beta_dev), word_at(gamma_dev), glogits, gkl, B, (hipStream_t)stream);
 }
 
 extern "C" int vg_factor_critic_loss(const float* logits, float* loss, float* glogits, float* acc, int B, float divisor,

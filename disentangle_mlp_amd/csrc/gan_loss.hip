@@ -49,13 +49,12 @@ __device__ __forceinline__ GanTerm gan_term(float s, float t, int kind) {
 // a wavefront owns a row (16-byte loads when `vec`, one 64-lane shuffle sum), 16 rows per workgroup; lane 0 evaluates
 // the loss; the row terms go to the workspace in double and the sum kernel below adds them in index order.  No atomic.
 __global__ __launch_bounds__(1024) void dot_gan_loss_fwd_kernel(const float* __restrict__ feat, const float* __restrict__ w,
-                                                                const float* __restrict__ bias, int kind, float target,
-                                                                const float* __restrict__ target_dev,
+                                                                const float* __restrict__ bias, int kind, Word target_w,
                                                                 float* __restrict__ logit_out, float* __restrict__ p_out,
                                                                 double* __restrict__ terms, float* __restrict__ dlogit,
                                                                 int B, int K, float inv_div, int vec) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (target_dev) target = target_dev[0];
+  const float target = read_word(target_w);
   const float b0 = bias ? bias[0] : 0.f;
   const int b = blockIdx.x * 16 + wid;                 // one row per wavefront, 16 rows per workgroup
   if (b >= B) return;
@@ -95,12 +94,11 @@ __global__ __launch_bounds__(NT) void gan_sum_finalize_kernel(const double* __re
 }
 
 // The same losses on a logit vector (the unfused route: a hooked head), as bce_kernel serves nn.BCELoss.
-__global__ __launch_bounds__(NT) void gan_loss_kernel(const float* __restrict__ logit, int kind, float target,
-                                                      const float* __restrict__ target_dev, float* __restrict__ p_out,
-                                                      float* __restrict__ loss, float* __restrict__ glogit, int B,
-                                                      float inv_div, float gscale) {
+__global__ __launch_bounds__(NT) void gan_loss_kernel(const float* __restrict__ logit, int kind, Word target_w,
+                                                      float* __restrict__ p_out, float* __restrict__ loss,
+                                                      float* __restrict__ glogit, int B, float inv_div, float gscale) {
   __shared__ double red[NT / 64];
-  if (target_dev) target = target_dev[0];
+  const float target = read_word(target_w);
   double s = 0.0;
   for (int i = threadIdx.x; i < B; i += NT) {
     const GanTerm r = gan_term(logit[i], target, kind);
@@ -127,7 +125,7 @@ extern "C" int vg_dot_gan_loss_fwd(const float* feat, const float* w, const floa
   const int vec = ((K & 3) == 0 && ((((uintptr_t)feat | (uintptr_t)w) & 15) == 0)) ? 1 : 0;
   double* terms = (double*)workspace;
   hipLaunchKernelGGL(dot_gan_loss_fwd_kernel, dim3(cdiv(B, 16)), dim3(1024), 0, (hipStream_t)stream, feat, w, bias, kind,
-                     target, target_dev, logit, p, terms, dlogit, B, K, 1.f / divisor, vec);
+                     word_or(target, target_dev), logit, p, terms, dlogit, B, K, 1.f / divisor, vec);
   VG_CHECK_LAUNCH();
   hipLaunchKernelGGL(gan_sum_finalize_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, (const double*)terms, B, loss,
                      1.f / divisor);
@@ -138,8 +136,8 @@ extern "C" int vg_dot_gan_loss_fwd(const float* feat, const float* w, const floa
 extern "C" int vg_gan_loss(const float* logit, int kind, float target, const float* target_dev, float* p, float* loss,
                            float* glogit, int B, float divisor, float gscale, void* stream) {
   if (!logit || !kind_ok(kind) || B <= 0 || !(divisor > 0.f)) return VG_ERR_BAD_ARG;
-  hipLaunchKernelGGL(gan_loss_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, logit, kind, target, target_dev, p, loss,
-                     glogit, B, 1.f / divisor, gscale);
+  hipLaunchKernelGGL(gan_loss_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, logit, kind, word_or(target, target_dev), p,
+                     loss, glogit, B, 1.f / divisor, gscale);
   VG_CHECK_LAUNCH();
   return 0;
 }

@@ -82,16 +82,14 @@ __global__ __launch_bounds__(NT) void act_bwd_kernel(const float* __restrict__ g
 // One workgroup of 1024 threads (16 wavefronts); a wavefront owns a row at a time,
 // so the per-sample KL is one 64-lane shuffle reduction and the total is summed in a
 // fixed order.
-// BETA_DEV: beta is read from DEVICE memory (beta_dev[0]) -- a KL weight that changes between the replays of a captured
+// beta is a Word (common.hpp): a float, or a KL weight in DEVICE memory that changes between the replays of a captured
 // iteration; the expressions it enters are the same, so the same fp32 beta gives the same bits.
-template <bool BETA_DEV>
 __global__ __launch_bounds__(1024) void reparam_kl_fwd_kernel(const float* __restrict__ mu,
                                                               const float* __restrict__ lv,
                                                               const float* __restrict__ eps, float* __restrict__ z,
                                                               float* __restrict__ kl, float* __restrict__ kl_rows,
-                                                              int B, int D, float beta,
-                                                              const float* __restrict__ beta_dev) {
-  if constexpr (BETA_DEV) beta = beta_dev[0];
+                                                              int B, int D, Word beta_w) {
+  const float beta = read_word(beta_w);
   __shared__ double red[16];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   double wave_total = 0.0;
@@ -117,14 +115,12 @@ __global__ __launch_bounds__(1024) void reparam_kl_fwd_kernel(const float* __res
   }
 }
 
-template <bool BETA_DEV>
 __global__ __launch_bounds__(NT) void reparam_kl_bwd_kernel(const float* __restrict__ gz, const float* __restrict__ mu,
                                                             const float* __restrict__ lv,
-                                                            const float* __restrict__ eps, const float* __restrict__ gkl, float beta,
-                                                            const float* __restrict__ beta_dev,
+                                                            const float* __restrict__ eps, const float* __restrict__ gkl, Word beta_w,
                                                             float* __restrict__ gmu, float* __restrict__ glv,
                                                             size_t n) {
-  if constexpr (BETA_DEV) beta = beta_dev[0];
+  const float beta = read_word(beta_w);
   const size_t stride = (size_t)gridDim.x * NT;
   const float kb = (gkl ? gkl[0] : 0.f) * beta;
   // An absent upstream gradient takes its whole term out, as autograd does: every factor of that term is 0, not only
@@ -171,11 +167,10 @@ __global__ __launch_bounds__(NT) void sum_finalize_kernel(const double* __restri
   if (threadIdx.x == 0) out[0] = (float)(scale * t);
 }
 
-__global__ __launch_bounds__(NT) void bce_kernel(const float* __restrict__ p, float target,
-                                                 const float* __restrict__ target_dev, float* __restrict__ loss,
+__global__ __launch_bounds__(NT) void bce_kernel(const float* __restrict__ p, Word target_w, float* __restrict__ loss,
                                                  float* __restrict__ gp, int B, float inv_div, float gscale) {
   __shared__ double red[NT / 64];
-  if (target_dev) target = target_dev[0];       // a label that changes between replays of a captured iteration
+  const float target = read_word(target_w);     // (a word: a label that changes between replays of a captured iteration)
   double s = 0.0;
   for (int i = threadIdx.x; i < B; i += NT) {
     const float v = p[i];
@@ -196,12 +191,11 @@ __global__ __launch_bounds__(NT) void bce_kernel(const float* __restrict__ p, fl
 // expressions, in the same fp32 operations, as bias_act (sigmoid), bce_kernel and act_bwd: p, the loss, and
 // dlogit = dBCE/dp * p (1 - p).
 __global__ __launch_bounds__(1024) void dot_sigmoid_bce_fwd_kernel(const float* __restrict__ feat, const float* __restrict__ w,
-                                                                   const float* __restrict__ bias, float target,
-                                                                   const float* __restrict__ target_dev,
+                                                                   const float* __restrict__ bias, Word target_w,
                                                                    float* __restrict__ p_out, double* __restrict__ terms,
                                                                    float* __restrict__ dlogit, int B, int K, float inv_div) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (target_dev) target = target_dev[0];
+  const float target = read_word(target_w);
   const float b0 = bias ? bias[0] : 0.f;
   const int b = blockIdx.x * 16 + wid;                 // one row per wavefront, 16 rows per workgroup
   if (b >= B) return;
@@ -296,6 +290,31 @@ int flat_grid(size_t n) {
   const size_t blocks = (n / 4 + NT - 1) / NT;
   return (int)(blocks > 2048 ? 2048 : (blocks < 1 ? 1 : blocks));
 }
+
+int reparam_kl_fwd(const float* mu, const float* logvar, const float* eps, float* z, float* kl, float* kl_rows, int B, int D,
+                   Word beta, hipStream_t st) {
+  if (!mu || !logvar || B <= 0 || D <= 0 || (z && !eps) || !words_ok(beta)) return VG_ERR_BAD_ARG;
+  hipLaunchKernelGGL(reparam_kl_fwd_kernel, dim3(1), dim3(1024), 0, st, mu, logvar, eps, z, kl, kl_rows, B, D, beta);
+  VG_CHECK_LAUNCH();
+  return 0;
+}
+
+int reparam_kl_bwd(const float* gz, const float* mu, const float* logvar, const float* eps, const float* gkl, Word beta,
+                   float* gmu, float* glogvar, int B, int D, hipStream_t st) {
+  if (!mu || !logvar || !eps || !gmu || !glogvar || B <= 0 || D <= 0 || !words_ok(beta)) return VG_ERR_BAD_ARG;
+  const size_t n = (size_t)B * D;
+  hipLaunchKernelGGL(reparam_kl_bwd_kernel, dim3(flat_grid(n * 4)), dim3(NT), 0, st, gz, mu, logvar, eps, gkl, beta, gmu,
+                     glogvar, n);
+  VG_CHECK_LAUNCH();
+  return 0;
+}
+
+int bce_loss(const float* p, Word target, float* loss, float* gp, int B, float divisor, float gscale, hipStream_t st) {
+  if (!p || !words_ok(target) || B <= 0 || !(divisor > 0.f)) return VG_ERR_BAD_ARG;
+  hipLaunchKernelGGL(bce_kernel, dim3(1), dim3(NT), 0, st, p, target, loss, gp, B, 1.f / divisor, gscale);
+  VG_CHECK_LAUNCH();
+  return 0;
+}
 constexpr int SQ_PARTS = 1024;
 // the 16-byte loops need every pointer they cast on a 16-byte boundary: a contiguous view at an offset of 1-3 floats
 // is a legal argument and takes the scalar loop
@@ -328,41 +347,23 @@ extern "C" int vg_act_bwd(const float* gy, const float* y, float* gx, size_t n, 
 
 extern "C" int vg_reparam_kl_fwd(const float* mu, const float* logvar, const float* eps, float* z, float* kl,
                                  float* kl_rows, int B, int D, float beta, void* stream) {
-  if (!mu || !logvar || B <= 0 || D <= 0 || (z && !eps)) return VG_ERR_BAD_ARG;
-  hipLaunchKernelGGL(reparam_kl_fwd_kernel<false>, dim3(1), dim3(1024), 0, (hipStream_t)stream, mu, logvar, eps, z, kl,
-                     kl_rows, B, D, beta, (const float*)nullptr);
-  VG_CHECK_LAUNCH();
-  return 0;
+  return reparam_kl_fwd(mu, logvar, eps, z, kl, kl_rows, B, D, word(beta), (hipStream_t)stream);
 }
 
 extern "C" int vg_reparam_kl_fwd_dev(const float* mu, const float* logvar, const float* eps, float* z, float* kl,
                                      float* kl_rows, int B, int D, const float* beta_dev, void* stream) {
-  if (!mu || !logvar || B <= 0 || D <= 0 || (z && !eps) || !beta_dev) return VG_ERR_BAD_ARG;
-  hipLaunchKernelGGL(reparam_kl_fwd_kernel<true>, dim3(1), dim3(1024), 0, (hipStream_t)stream, mu, logvar, eps, z, kl,
-                     kl_rows, B, D, 0.f, beta_dev);
-  VG_CHECK_LAUNCH();
-  return 0;
+  return reparam_kl_fwd(mu, logvar, eps, z, kl, kl_rows, B, D, word_at(beta_dev), (hipStream_t)stream);
 }
 
 extern "C" int vg_reparam_kl_bwd(const float* gz, const float* mu, const float* logvar, const float* eps,
                                  const float* gkl, float beta, float* gmu, float* glogvar, int B, int D, void* stream) {
-  if (!mu || !logvar || !eps || !gmu || !glogvar || B <= 0 || D <= 0) return VG_ERR_BAD_ARG;
-  const size_t n = (size_t)B * D;
-  hipLaunchKernelGGL(reparam_kl_bwd_kernel<false>, dim3(flat_grid(n * 4)), dim3(NT), 0, (hipStream_t)stream, gz, mu,
-                     logvar, eps, gkl, beta, (const float*)nullptr, gmu, glogvar, n);
-  VG_CHECK_LAUNCH();
-  return 0;
+  return reparam_kl_bwd(gz, mu, logvar, eps, gkl, word(beta), gmu, glogvar, B, D, (hipStream_t)stream);
 }
 
 extern "C" int vg_reparam_kl_bwd_dev(const float* gz, const float* mu, const float* logvar, const float* eps,
                                      const float* gkl, const float* beta_dev, float* gmu, float* glogvar, int B, int D,
                                      void* stream) {
-  if (!mu || !logvar || !eps || !gmu || !glogvar || B <= 0 || D <= 0 || !beta_dev) return VG_ERR_BAD_ARG;
-  const size_t n = (size_t)B * D;
-  hipLaunchKernelGGL(reparam_kl_bwd_kernel<true>, dim3(flat_grid(n * 4)), dim3(NT), 0, (hipStream_t)stream, gz, mu,
-                     logvar, eps, gkl, 0.f, beta_dev, gmu, glogvar, n);
-  VG_CHECK_LAUNCH();
-  return 0;
+  return reparam_kl_bwd(gz, mu, logvar, eps, gkl, word_at(beta_dev), gmu, glogvar, B, D, (hipStream_t)stream);
 }
 
 extern "C" int vg_scale_by_scalar(const float* g, const float* s, float* out, size_t n, void* stream) {
@@ -392,11 +393,7 @@ extern "C" int vg_sqdiff_loss(const float* a, const float* b, float* loss, float
 
 extern "C" int vg_bce_loss(const float* p, float target, float* loss, float* gp, int B, float divisor, float gscale,
                            void* stream) {
-  if (!p || B <= 0 || !(divisor > 0.f)) return VG_ERR_BAD_ARG;
-  hipLaunchKernelGGL(bce_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, p, target, (const float*)nullptr, loss, gp, B,
-                     1.f / divisor, gscale);
-  VG_CHECK_LAUNCH();
-  return 0;
+  return bce_loss(p, word(target), loss, gp, B, divisor, gscale, (hipStream_t)stream);
 }
 
 extern "C" size_t vg_dot_sigmoid_bce_workspace_bytes(int B) { return B > 0 ? (size_t)B * sizeof(double) : 0; }
@@ -408,8 +405,8 @@ extern "C" int vg_dot_sigmoid_bce_fwd(const float* feat, const float* w, const f
   if ((K & 3) == 0 && ((((uintptr_t)feat | (uintptr_t)w) & 15) != 0)) return VG_ERR_BAD_ARG;
   if (!workspace || workspace_bytes < vg_dot_sigmoid_bce_workspace_bytes(B)) return VG_ERR_WORKSPACE;
   double* terms = (double*)workspace;
-  hipLaunchKernelGGL(dot_sigmoid_bce_fwd_kernel, dim3(cdiv(B, 16)), dim3(1024), 0, (hipStream_t)stream, feat, w, bias, target,
-                     target_dev, p, terms, dlogit, B, K, 1.f / divisor);
+  hipLaunchKernelGGL(dot_sigmoid_bce_fwd_kernel, dim3(cdiv(B, 16)), dim3(1024), 0, (hipStream_t)stream, feat, w, bias,
+                     word_or(target, target_dev), p, terms, dlogit, B, K, 1.f / divisor);
   VG_CHECK_LAUNCH();
   hipLaunchKernelGGL(sum_finalize_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, (const double*)terms, B, loss,
                      1.f / divisor);
@@ -429,9 +426,5 @@ extern "C" int vg_dot_sigmoid_bce_bwd(const float* dlogit, const float* gloss, c
 
 extern "C" int vg_bce_loss_dev(const float* p, const float* target_dev, float* loss, float* gp, int B, float divisor,
                                float gscale, void* stream) {
-  if (!p || !target_dev || B <= 0 || !(divisor > 0.f)) return VG_ERR_BAD_ARG;
-  hipLaunchKernelGGL(bce_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, p, 0.f, target_dev, loss, gp, B, 1.f / divisor,
-                     gscale);
-  VG_CHECK_LAUNCH();
-  return 0;
+  return bce_loss(p, word_at(target_dev), loss, gp, B, divisor, gscale, (hipStream_t)stream);
 }

@@ -1,9 +1,15 @@
 // What the reparameterisation kernels fused with an objective of the KL phase -- reparam_tc.hip, reparam_dip.hip,
 // reparam_mmd.hip, reparam_klc.hip -- have in common to the letter: DESIGN.md section 4.24.  Only that: a kernel whose
 // inner loop differs between two of them (chain lengths, staging layout) stays in its file, and nothing here asks who
-// calls it.  All four files use MAX_DIM, the per-element expressions and the gz-only backward; the tile geometry, the
-// tile decode and the slot sums belong to reparam_dip.hip and reparam_mmd.hip alone (reparam_klc.hip takes the strip's
-// width and the workgroup size from it).  Everything has internal linkage: each file compiles its own copy.
+// calls it.  What it holds:
+//   all four files   MAX_DIM and dims_ok, weight_ok (a float weight: finite and >= 0), the per-element expressions
+//                    (reparam_z, kl_term) and the gz-only backward;
+//   klc and dip      reparam_bwd_store, the end of their elementwise backward (mmd and tc keep their own stores: each
+//                    says why where it stands);
+//   dip and mmd      the tile geometry, the tile decode and the slot sums (reparam_klc.hip takes the strip's width and
+//                    the workgroup size from it).
+// A scheduled value -- beta, the capacity -- is a `Word` (common.hpp).  Everything has internal linkage: each file compiles
+// its own copy.
 #pragma once
 #include "common.hpp"
 
@@ -12,6 +18,10 @@
 namespace {
 
 constexpr int MAX_DIM = 1024;      // B and D
+inline bool dims_ok(int B, int D, int min_b = 1) { return B >= min_b && B <= MAX_DIM && D >= 1 && D <= MAX_DIM; }
+// a weight given as a float (lambda, free bits, a capacity): finite and >= 0.  Written as two comparisons, which a NaN
+// fails both: the same floats pass as with isfinite(v) && v >= 0.f, and no classification call is needed.
+inline bool weight_ok(float v) { return v >= 0.f && v <= 3.402823466e38f; }
 
 // ---- the geometry reparam_dip.hip and reparam_mmd.hip share (their own comments say what a row and a column are) -------
 constexpr int STRIP = 64;          // columns of a strip workgroup (z and the KL partial): one per lane
@@ -69,6 +79,16 @@ __device__ __forceinline__ float reparam_z(float mu, float lv, float eps) { retu
 // the element's term of -2 KL, in fp64
 __device__ __forceinline__ double kl_term(float mu, float lv) {
   return 1.0 + (double)lv - (double)mu * (double)mu - (double)expf(lv);
+}
+
+// The end of an elementwise backward: element o gets gl times the loss term's partials (pmu, plv) plus the decoder's
+// gradient through z; l = lv[o].  An absent gz takes its whole term out, every factor of it, as in reparam_kl_bwd_kernel.
+__device__ __forceinline__ void reparam_bwd_store(const float* __restrict__ gz, const float* __restrict__ eps, float l, float gl,
+                                                  float pmu, float plv, float* __restrict__ gmu, float* __restrict__ glv,
+                                                  size_t o) {
+  const float g = gz ? gz[o] : 0.f, e = gz ? eps[o] : 0.f, h = gz ? expf(0.5f * l) : 0.f;
+  gmu[o] = fmaf(gl, pmu, g);
+  glv[o] = fmaf(gl, plv, g * e * 0.5f * h);
 }
 
 // ---- backward with gloss absent ---------------------------------------------------------------------------------------------

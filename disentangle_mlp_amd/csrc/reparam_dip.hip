@@ -124,12 +124,10 @@ __global__ __launch_bounds__(CNT) void dip_cov_kernel(const float* __restrict__ 
 }
 
 // ---- forward 3: one wavefront, the partials in slot order ---------------------------------------------------------------
-template <bool BETA_DEV>
 __global__ __launch_bounds__(64) void dip_sum_kernel(const double* __restrict__ klp, int nstrips,
-                                                     const double* __restrict__ covp, int ntiles, int B, float beta,
-                                                     const float* __restrict__ beta_dev, float lambda_od, float lambda_d,
-                                                     float* __restrict__ out4) {
-  if constexpr (BETA_DEV) beta = beta_dev[0];
+                                                     const double* __restrict__ covp, int ntiles, int B, Word beta_w,
+                                                     float lambda_od, float lambda_d, float* __restrict__ out4) {
+  const float beta = read_word(beta_w);
   double kl = 0.0, od = 0.0, dg = 0.0;
   for (int i = threadIdx.x; i < nstrips; i += 64) kl += klp[i];
   for (int i = threadIdx.x; i < ntiles; i += 64) {
@@ -149,14 +147,13 @@ __global__ __launch_bounds__(64) void dip_sum_kernel(const double* __restrict__ 
 
 // ---- backward: rows [RB blockIdx.y, +RB) x columns [64 blockIdx.x, +64) --------------------------------------------------
 // G_id = 2 lambda_od C_id (i != d), 2 lambda_d (C_dd - 1) on the diagonal; Gmu[b, d] = 2 sum_i c[b, i] G[i, d].
-template <bool BETA_DEV>
 __global__ __launch_bounds__(CNT) void dip_bwd_kernel(const float* __restrict__ gz, const float* __restrict__ mu,
                                                       const float* __restrict__ lv, const float* __restrict__ eps,
                                                       const float* __restrict__ cov, const double* __restrict__ mean,
-                                                      const float* __restrict__ gloss, int variant, float beta,
-                                                      const float* __restrict__ beta_dev, float lambda_od, float lambda_d,
-                                                      float* __restrict__ gmu, float* __restrict__ glv, int B, int D) {
-  if constexpr (BETA_DEV) beta = beta_dev[0];
+                                                      const float* __restrict__ gloss, int variant, Word beta_w,
+                                                      float lambda_od, float lambda_d, float* __restrict__ gmu,
+                                                      float* __restrict__ glv, int B, int D) {
+  const float beta = read_word(beta_w);
   __shared__ float sc[RB][BK];
   const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
   const int d = blockIdx.x * 64 + lane, r0 = blockIdx.y * RB;
@@ -193,26 +190,20 @@ __global__ __launch_bounds__(CNT) void dip_bwd_kernel(const float* __restrict__ 
     if (b < B) {
       const size_t o = (size_t)b * D + d;
       const float l = lv[o], el = expf(l);
-      // an absent gz takes its whole term out, as in reparam_kl_bwd_kernel
-      const float g = gz ? gz[o] : 0.f, e = gz ? eps[o] : 0.f, h = gz ? expf(0.5f * l) : 0.f;
       const float pmu = fmaf(beta, mu[o], (float)(2.0 * tot[q]));
       const float plv = fmaf(beta * 0.5f, el - 1.f, gdd * el);
-      gmu[o] = fmaf(gl, pmu, g);
-      glv[o] = fmaf(gl, plv, g * e * 0.5f * h);
+      reparam_bwd_store(gz, eps, l, gl, pmu, plv, gmu, glv, o);
     }
   }
 }
 
-bool dims_ok(int B, int D) { return B >= 1 && B <= MAX_DIM && D >= 1 && D <= MAX_DIM; }
 bool variant_ok(int v) { return v == 1 || v == 2; }
 
-template <bool BETA_DEV>
 int dip_fwd(const float* mu, const float* lv, const float* eps, float* z, float* out4, float* cov, double* mean, int B, int D,
-            int variant, float beta, const float* beta_dev, float lambda_od, float lambda_d, void* workspace,
-            size_t workspace_bytes, hipStream_t st) {
+            int variant, Word beta, float lambda_od, float lambda_d, void* workspace, size_t workspace_bytes, hipStream_t st) {
   if (!mu || !lv || !eps || !z || !out4 || !cov || !mean || !workspace || !dims_ok(B, D) || !variant_ok(variant))
     return VG_ERR_BAD_ARG;
-  if (BETA_DEV && !beta_dev) return VG_ERR_BAD_ARG;
+  if (!words_ok(beta)) return VG_ERR_BAD_ARG;
   if (workspace_bytes < vg_reparam_dip_workspace_bytes(B, D)) return VG_ERR_WORKSPACE;
   double* klp = (double*)workspace;      // [KL_SLOTS], then evar [D], then {od, dg} per tile
   double* evar = klp + KL_SLOTS;
@@ -223,23 +214,22 @@ int dip_fwd(const float* mu, const float* lv, const float* eps, float* z, float*
   hipLaunchKernelGGL(dip_cov_kernel, dim3(ntiles), dim3(CNT), 0, st, mu, (const double*)mean, (const double*)evar, cov, covp,
                      B, D, variant);
   VG_CHECK_LAUNCH();
-  hipLaunchKernelGGL(dip_sum_kernel<BETA_DEV>, dim3(1), dim3(64), 0, st, (const double*)klp, nstrips, (const double*)covp,
-                     ntiles, B, beta, beta_dev, lambda_od, lambda_d, out4);
+  hipLaunchKernelGGL(dip_sum_kernel, dim3(1), dim3(64), 0, st, (const double*)klp, nstrips, (const double*)covp, ntiles, B, beta,
+                     lambda_od, lambda_d, out4);
   VG_CHECK_LAUNCH();
   return 0;
 }
 
-template <bool BETA_DEV>
 int dip_bwd(const float* gz, const float* mu, const float* lv, const float* eps, const float* cov, const double* mean,
-            const float* gloss, int variant, float beta, const float* beta_dev, float lambda_od, float lambda_d, float* gmu,
-            float* glv, int B, int D, void* workspace, size_t workspace_bytes, hipStream_t st) {
+            const float* gloss, int variant, Word beta, float lambda_od, float lambda_d, float* gmu, float* glv, int B, int D,
+            void* workspace, size_t workspace_bytes, hipStream_t st) {
   if (!mu || !lv || !eps || !cov || !mean || !gmu || !glv || !workspace || !dims_ok(B, D) || !variant_ok(variant))
     return VG_ERR_BAD_ARG;
-  if (BETA_DEV && !beta_dev) return VG_ERR_BAD_ARG;
+  if (!words_ok(beta)) return VG_ERR_BAD_ARG;
   if (workspace_bytes < vg_reparam_dip_workspace_bytes(B, D)) return VG_ERR_WORKSPACE;
   if (!gloss) return reparam_bwd_gz_only(gz, lv, eps, gmu, glv, B, D, st);
-  hipLaunchKernelGGL(dip_bwd_kernel<BETA_DEV>, dim3(cdiv(D, 64), cdiv(B, RB)), dim3(CNT), 0, st, gz, mu, lv, eps, cov, mean,
-                     gloss, variant, beta, beta_dev, lambda_od, lambda_d, gmu, glv, B, D);
+  hipLaunchKernelGGL(dip_bwd_kernel, dim3(cdiv(D, 64), cdiv(B, RB)), dim3(CNT), 0, st, gz, mu, lv, eps, cov, mean, gloss,
+                     variant, beta, lambda_od, lambda_d, gmu, glv, B, D);
   VG_CHECK_LAUNCH();
   return 0;
 }
@@ -254,30 +244,30 @@ extern "C" size_t vg_reparam_dip_workspace_bytes(int B, int D) {
 extern "C" int vg_reparam_dip_fwd(const float* mu, const float* logvar, const float* eps, float* z, float* out4, float* cov,
                                   double* mean, int B, int D, int variant, float beta, float lambda_od, float lambda_d,
                                   void* workspace, size_t workspace_bytes, void* stream) {
-  return dip_fwd<false>(mu, logvar, eps, z, out4, cov, mean, B, D, variant, beta, nullptr, lambda_od, lambda_d, workspace,
-                        workspace_bytes, (hipStream_t)stream);
+  return dip_fwd(mu, logvar, eps, z, out4, cov, mean, B, D, variant, word(beta), lambda_od, lambda_d, workspace, workspace_bytes,
+                 (hipStream_t)stream);
 }
 
 extern "C" int vg_reparam_dip_fwd_dev(const float* mu, const float* logvar, const float* eps, float* z, float* out4,
                                       float* cov, double* mean, int B, int D, int variant, const float* beta_dev,
                                       float lambda_od, float lambda_d, void* workspace, size_t workspace_bytes,
                                       void* stream) {
-  return dip_fwd<true>(mu, logvar, eps, z, out4, cov, mean, B, D, variant, 0.f, beta_dev, lambda_od, lambda_d, workspace,
-                       workspace_bytes, (hipStream_t)stream);
+  return dip_fwd(mu, logvar, eps, z, out4, cov, mean, B, D, variant, word_at(beta_dev), lambda_od, lambda_d, workspace,
+                 workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int vg_reparam_dip_bwd(const float* gz, const float* mu, const float* logvar, const float* eps, const float* cov,
                                   const double* mean, const float* gloss, int variant, float beta, float lambda_od,
                                   float lambda_d, float* gmu, float* glogvar, int B, int D, void* workspace,
                                   size_t workspace_bytes, void* stream) {
-  return dip_bwd<false>(gz, mu, logvar, eps, cov, mean, gloss, variant, beta, nullptr, lambda_od, lambda_d, gmu, glogvar, B, D,
-                        workspace, workspace_bytes, (hipStream_t)stream);
+  return dip_bwd(gz, mu, logvar, eps, cov, mean, gloss, variant, word(beta), lambda_od, lambda_d, gmu, glogvar, B, D, workspace,
+                 workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int vg_reparam_dip_bwd_dev(const float* gz, const float* mu, const float* logvar, const float* eps,
                                       const float* cov, const double* mean, const float* gloss, int variant,
                                       const float* beta_dev, float lambda_od, float lambda_d, float* gmu, float* glogvar,
                                       int B, int D, void* workspace, size_t workspace_bytes, void* stream) {
-  return dip_bwd<true>(gz, mu, logvar, eps, cov, mean, gloss, variant, 0.f, beta_dev, lambda_od, lambda_d, gmu, glogvar, B, D,
-                       workspace, workspace_bytes, (hipStream_t)stream);
+  return dip_bwd(gz, mu, logvar, eps, cov, mean, gloss, variant, word_at(beta_dev), lambda_od, lambda_d, gmu, glogvar, B, D,
+                 workspace, workspace_bytes, (hipStream_t)stream);
 }

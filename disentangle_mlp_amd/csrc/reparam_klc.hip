@@ -45,16 +45,11 @@ __global__ __launch_bounds__(CNT) void klc_cols_kernel(const float* __restrict__
 }
 
 // ---- forward 2: one workgroup, thread d owns dimension d ------------------------------------------------------------------
-template <bool DEV>
-__global__ __launch_bounds__(MAX_DIM) void klc_finish_kernel(const double* __restrict__ slot, int nrb, int B, int D, float beta,
-                                                             const float* __restrict__ beta_dev, float capacity,
-                                                             const float* __restrict__ capacity_dev, float free_bits,
+__global__ __launch_bounds__(MAX_DIM) void klc_finish_kernel(const double* __restrict__ slot, int nrb, int B, int D,
+                                                             Word beta_w, Word capacity_w, float free_bits,
                                                              float* __restrict__ out4, float* __restrict__ gate,
                                                              float* __restrict__ kl_dim) {
-  if constexpr (DEV) {
-    beta = beta_dev[0];
-    capacity = capacity_dev[0];
-  }
+  const float beta = read_word(beta_w), capacity = read_word(capacity_w);
   __shared__ double sk[MAX_DIM], sf[MAX_DIM];
   __shared__ double excess;      // T - B C
   const int d = threadIdx.x;
@@ -92,66 +87,54 @@ __global__ __launch_bounds__(MAX_DIM) void klc_finish_kernel(const double* __res
 }
 
 // ---- backward: elementwise, the loss term through gate ----------------------------------------------------------------------
-template <bool DEV>
 __global__ __launch_bounds__(256) void klc_bwd_kernel(const float* __restrict__ gz, const float* __restrict__ mu,
                                                       const float* __restrict__ lv, const float* __restrict__ eps,
                                                       const float* __restrict__ gate, const float* __restrict__ gloss,
-                                                      float beta, const float* __restrict__ beta_dev, float* __restrict__ gmu,
-                                                      float* __restrict__ glv, int D, size_t n) {
-  if constexpr (DEV) beta = beta_dev[0];
+                                                      Word beta_w, float* __restrict__ gmu, float* __restrict__ glv, int D,
+                                                      size_t n) {
+  const float beta = read_word(beta_w);
   const float gl = gloss[0];
   const size_t stride = (size_t)gridDim.x * 256;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
     const float bg = beta * gate[i % (size_t)D];
     const float l = lv[i], el = expf(l);
-    // an absent gz takes its whole term out, as in reparam_kl_bwd_kernel
-    const float g = gz ? gz[i] : 0.f, e = gz ? eps[i] : 0.f, h = gz ? expf(0.5f * l) : 0.f;
     const float pmu = bg * mu[i];
     const float plv = bg * 0.5f * (el - 1.f);
-    gmu[i] = fmaf(gl, pmu, g);
-    glv[i] = fmaf(gl, plv, g * e * 0.5f * h);
+    reparam_bwd_store(gz, eps, l, gl, pmu, plv, gmu, glv, i);
   }
 }
 
-bool dims_ok(int B, int D) { return B >= 1 && B <= MAX_DIM && D >= 1 && D <= MAX_DIM; }
-bool weight_ok(float v) { return v >= 0.f && v <= 3.402823466e38f; }      // finite and >= 0 (a NaN fails both)
-
 size_t slots_bytes(int B, int D) { return (size_t)cdiv(B, KROWS) * D * sizeof(double); }
 
-// what both directions refuse before any launch
-template <bool DEV>
-bool args_ok(int B, int D, float capacity, float free_bits, const float* beta_dev, const float* capacity_dev, const void* workspace,
-             size_t workspace_bytes) {
+// what both directions refuse before any launch (a capacity given as a float is a weight; of a word the host knows no value)
+bool args_ok(int B, int D, Word beta, Word capacity, float free_bits, const void* workspace, size_t workspace_bytes) {
   if (!workspace || !dims_ok(B, D) || !weight_ok(free_bits) || workspace_bytes < slots_bytes(B, D)) return false;
-  return DEV ? (beta_dev && capacity_dev) : weight_ok(capacity);
+  return words_ok(beta, capacity) && (!is_float(capacity) || weight_ok(capacity.v));
 }
 
-template <bool DEV>
 int klc_fwd(const float* mu, const float* lv, const float* eps, float* z, float* out4, float* gate, float* kl_dim, int B, int D,
-            float beta, const float* beta_dev, float capacity, const float* capacity_dev, float free_bits, void* workspace,
-            size_t workspace_bytes, hipStream_t st) {
+            Word beta, Word capacity, float free_bits, void* workspace, size_t workspace_bytes, hipStream_t st) {
   if (!mu || !lv || !eps || !z || !out4 || !gate || !kl_dim) return VG_ERR_BAD_ARG;
-  if (!args_ok<DEV>(B, D, capacity, free_bits, beta_dev, capacity_dev, workspace, workspace_bytes)) return VG_ERR_BAD_ARG;
+  if (!args_ok(B, D, beta, capacity, free_bits, workspace, workspace_bytes)) return VG_ERR_BAD_ARG;
   double* slot = (double*)workspace;      // [row blocks][D]
   const int nrb = cdiv(B, KROWS);
   hipLaunchKernelGGL(klc_cols_kernel, dim3(cdiv(D, STRIP), nrb), dim3(CNT), 0, st, mu, lv, eps, z, slot, B, D);
   VG_CHECK_LAUNCH();
-  hipLaunchKernelGGL(klc_finish_kernel<DEV>, dim3(1), dim3(cdiv(D, 64) * 64), 0, st, (const double*)slot, nrb, B, D, beta, beta_dev,
-                     capacity, capacity_dev, free_bits, out4, gate, kl_dim);
+  hipLaunchKernelGGL(klc_finish_kernel, dim3(1), dim3(cdiv(D, 64) * 64), 0, st, (const double*)slot, nrb, B, D, beta, capacity,
+                     free_bits, out4, gate, kl_dim);
   VG_CHECK_LAUNCH();
   return 0;
 }
 
-template <bool DEV>
 int klc_bwd(const float* gz, const float* mu, const float* lv, const float* eps, const float* gate, const float* gloss,
-            float beta, const float* beta_dev, float capacity, const float* capacity_dev, float free_bits, float* gmu,
-            float* glv, int B, int D, void* workspace, size_t workspace_bytes, hipStream_t st) {
+            Word beta, Word capacity, float free_bits, float* gmu, float* glv, int B, int D, void* workspace,
+            size_t workspace_bytes, hipStream_t st) {
   if (!mu || !lv || !eps || !gate || !gmu || !glv) return VG_ERR_BAD_ARG;
-  if (!args_ok<DEV>(B, D, capacity, free_bits, beta_dev, capacity_dev, workspace, workspace_bytes)) return VG_ERR_BAD_ARG;
+  if (!args_ok(B, D, beta, capacity, free_bits, workspace, workspace_bytes)) return VG_ERR_BAD_ARG;
   if (!gloss) return reparam_bwd_gz_only(gz, lv, eps, gmu, glv, B, D, st);
   const size_t n = (size_t)B * D;
-  hipLaunchKernelGGL(klc_bwd_kernel<DEV>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, gz, mu, lv, eps, gate, gloss,
-                     beta, beta_dev, gmu, glv, D, n);
+  hipLaunchKernelGGL(klc_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, gz, mu, lv, eps, gate, gloss, beta,
+                     gmu, glv, D, n);
   VG_CHECK_LAUNCH();
   return 0;
 }
@@ -164,29 +147,29 @@ extern "C" size_t vg_reparam_klc_workspace_bytes(int B, int D) { return dims_ok(
 extern "C" int vg_reparam_klc_fwd(const float* mu, const float* logvar, const float* eps, float* z, float* out4, float* gate,
                                   float* kl_dim, int B, int D, float beta, float capacity, float free_bits, void* workspace,
                                   size_t workspace_bytes, void* stream) {
-  return klc_fwd<false>(mu, logvar, eps, z, out4, gate, kl_dim, B, D, beta, nullptr, capacity, nullptr, free_bits, workspace,
-                        workspace_bytes, (hipStream_t)stream);
+  return klc_fwd(mu, logvar, eps, z, out4, gate, kl_dim, B, D, word(beta), word(capacity), free_bits, workspace,
+                 workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int vg_reparam_klc_fwd_dev(const float* mu, const float* logvar, const float* eps, float* z, float* out4,
                                       float* gate, float* kl_dim, int B, int D, const float* beta_dev,
                                       const float* capacity_dev, float free_bits, void* workspace, size_t workspace_bytes,
                                       void* stream) {
-  return klc_fwd<true>(mu, logvar, eps, z, out4, gate, kl_dim, B, D, 0.f, beta_dev, 0.f, capacity_dev, free_bits, workspace,
-                       workspace_bytes, (hipStream_t)stream);
+  return klc_fwd(mu, logvar, eps, z, out4, gate, kl_dim, B, D, word_at(beta_dev), word_at(capacity_dev), free_bits, workspace,
+                 workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int vg_reparam_klc_bwd(const float* gz, const float* mu, const float* logvar, const float* eps, const float* gate,
                                   const float* gloss, float beta, float capacity, float free_bits, float* gmu, float* glogvar,
                                   int B, int D, void* workspace, size_t workspace_bytes, void* stream) {
-  return klc_bwd<false>(gz, mu, logvar, eps, gate, gloss, beta, nullptr, capacity, nullptr, free_bits, gmu, glogvar, B, D,
-                        workspace, workspace_bytes, (hipStream_t)stream);
+  return klc_bwd(gz, mu, logvar, eps, gate, gloss, word(beta), word(capacity), free_bits, gmu, glogvar, B, D, workspace,
+                 workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int vg_reparam_klc_bwd_dev(const float* gz, const float* mu, const float* logvar, const float* eps,
                                       const float* gate, const float* gloss, const float* beta_dev, const float* capacity_dev,
                                       float free_bits, float* gmu, float* glogvar, int B, int D, void* workspace,
                                       size_t workspace_bytes, void* stream) {
-  return klc_bwd<true>(gz, mu, logvar, eps, gate, gloss, 0.f, beta_dev, 0.f, capacity_dev, free_bits, gmu, glogvar, B, D,
-                       workspace, workspace_bytes, (hipStream_t)stream);
+  return klc_bwd(gz, mu, logvar, eps, gate, gloss, word_at(beta_dev), word_at(capacity_dev), free_bits, gmu, glogvar, B, D,
+                 workspace, workspace_bytes, (hipStream_t)stream);
 }

@@ -167,6 +167,9 @@ __global__ __launch_bounds__(CNT) void mmd_pairs_kernel(const float* __restrict_
 }
 
 // ---- forward 3: one wavefront, the partials in slot order -------------------------------------------------------------------
+// BETA_DEV (this kernel and the backward): beta read from the device word.  The other objectives take a `Word` (common.hpp);
+// as a Word this file's captured forward + backward at (256, 128) measured 0.78 us above the parent's median with a spread
+// of 0.66 us (profiles/scheduled_word.json), so its two kernels keep the compile-time twin.
 template <bool BETA_DEV>
 __global__ __launch_bounds__(64) void mmd_sum_kernel(const double* __restrict__ klp, int nstrips,
                                                      const double* __restrict__ pairp, int B, float beta,
@@ -258,22 +261,22 @@ __global__ __launch_bounds__(CNT) void mmd_bwd_kernel(const float* __restrict__ 
       const float Gz = (float)(scale * tot[q]);
       const float pmu = fmaf(beta, mu[o], Gz);
       const float plv = fmaf(beta * 0.5f, el - 1.f, Gz * s);
-      // an absent gz takes its whole term out, as in reparam_kl_bwd_kernel
+      // an absent gz takes its whole term out, as in reparam_kl_bwd_kernel.  Not reparam_bwd_store: that adds a zero term,
+      // fmaf(gl, pmu, 0.f), and this a bare product -- the two differ in the sign of a zero product
       gmu[o] = gz ? fmaf(gl, pmu, gz[o]) : gl * pmu;
       glv[o] = gz ? fmaf(gl, plv, gz[o] * s) : gl * plv;
     }
   }
 }
 
-bool dims_ok(int B, int D) { return B >= 2 && B <= MAX_DIM && D >= 1 && D <= MAX_DIM; }
-bool lambda_ok(float l) { return isfinite(l) && l >= 0.f; }
+constexpr int MIN_B = 2;           // the U-statistic divides by B - 1
 
 template <bool BETA_DEV>
 int mmd_fwd(const float* mu, const float* lv, const float* eps, const float* zp, float* z, float* out4, float* w, int B, int D,
             int kind, float beta, const float* beta_dev, float lambda_mmd, const float* bandwidths, int n_bandwidths,
             void* workspace, size_t workspace_bytes, hipStream_t st) {
-  if (!mu || !lv || !eps || !zp || !z || !out4 || !w || !bandwidths || !workspace || !dims_ok(B, D)) return VG_ERR_BAD_ARG;
-  if ((kind != KIND_RBF && kind != KIND_IMQ) || n_bandwidths < 1 || n_bandwidths > MAX_BW || !lambda_ok(lambda_mmd))
+  if (!mu || !lv || !eps || !zp || !z || !out4 || !w || !bandwidths || !workspace || !dims_ok(B, D, MIN_B)) return VG_ERR_BAD_ARG;
+  if ((kind != KIND_RBF && kind != KIND_IMQ) || n_bandwidths < 1 || n_bandwidths > MAX_BW || !weight_ok(lambda_mmd))
     return VG_ERR_BAD_ARG;
   if (BETA_DEV && !beta_dev) return VG_ERR_BAD_ARG;
   if (workspace_bytes < vg_reparam_mmd_workspace_bytes(B, D)) return VG_ERR_BAD_ARG;
@@ -303,7 +306,7 @@ template <bool BETA_DEV>
 int mmd_bwd(const float* gz, const float* mu, const float* lv, const float* eps, const float* z, const float* zp,
             const float* w, const float* gloss, float beta, const float* beta_dev, float lambda_mmd, float* gmu, float* glv,
             int B, int D, void* workspace, size_t workspace_bytes, hipStream_t st) {
-  if (!mu || !lv || !eps || !z || !zp || !w || !gmu || !glv || !workspace || !dims_ok(B, D) || !lambda_ok(lambda_mmd))
+  if (!mu || !lv || !eps || !z || !zp || !w || !gmu || !glv || !workspace || !dims_ok(B, D, MIN_B) || !weight_ok(lambda_mmd))
     return VG_ERR_BAD_ARG;
   if (BETA_DEV && !beta_dev) return VG_ERR_BAD_ARG;
   if (workspace_bytes < vg_reparam_mmd_workspace_bytes(B, D)) return VG_ERR_BAD_ARG;
@@ -318,7 +321,7 @@ int mmd_bwd(const float* gz, const float* mu, const float* lv, const float* eps,
 
 // KL partials per strip, then the sum of k per pair tile (zz, pp, zp): all fp64
 extern "C" size_t vg_reparam_mmd_workspace_bytes(int B, int D) {
-  return dims_ok(B, D) ? (size_t)(KL_SLOTS + pair_tiles(B)) * sizeof(double) : 0;
+  return dims_ok(B, D, MIN_B) ? (size_t)(KL_SLOTS + pair_tiles(B)) * sizeof(double) : 0;
 }
 
 extern "C" int vg_reparam_mmd_fwd(const float* mu, const float* logvar, const float* eps, const float* zp, float* z,

@@ -160,11 +160,9 @@ __global__ __launch_bounds__(NT) void tc_fwd_kernel(const float* __restrict__ mu
 }
 
 // One wavefront: the per-sample parts summed in a fixed order, and the weighted loss.
-template <bool BETA_DEV>
-__global__ __launch_bounds__(64) void tc_sum_kernel(const double* __restrict__ parts, int B, float alpha, float beta,
-                                                    const float* __restrict__ beta_dev, float gamma,
-                                                    float* __restrict__ out4) {
-  if constexpr (BETA_DEV) beta = beta_dev[0];
+__global__ __launch_bounds__(64) void tc_sum_kernel(const double* __restrict__ parts, int B, float alpha, Word beta_w,
+                                                    float gamma, float* __restrict__ out4) {
+  const float beta = read_word(beta_w);
   double mi = 0.0, tc = 0.0, dw = 0.0;
   for (int i = threadIdx.x; i < B; i += 64) {
     mi += parts[3 * i + 0];
@@ -189,14 +187,13 @@ __device__ __forceinline__ float c_row(double rs, double lse_joint_i, bool diag,
 }
 
 // ---- backward, sums over j: workgroup i writes Gz[i,:] ---------------------------------------------------------------
-template <int KMAX, bool BETA_DEV>
+template <int KMAX>
 __global__ __launch_bounds__(NT) void tc_bwd_z_kernel(const float* __restrict__ mu, const float* __restrict__ lv,
                                                       const float* __restrict__ eps, const float* __restrict__ z,
                                                       const double* __restrict__ lse_joint,
-                                                      const float* __restrict__ lse_dim, float alpha, float beta,
-                                                      const float* __restrict__ beta_dev, float gamma,
-                                                      float* __restrict__ Gz, int B, int D) {
-  if constexpr (BETA_DEV) beta = beta_dev[0];
+                                                      const float* __restrict__ lse_dim, float alpha, Word beta_w,
+                                                      float gamma, float* __restrict__ Gz, int B, int D) {
+  const float beta = read_word(beta_w);
   extern __shared__ float red[];      // [NW][D]
   const int i = blockIdx.x, lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const size_t row_i = (size_t)i * D;
@@ -238,15 +235,14 @@ __global__ __launch_bounds__(NT) void tc_bwd_z_kernel(const float* __restrict__ 
 }
 
 // ---- backward, sums over i: workgroup j writes gmu[j,:], glogvar[j,:] ------------------------------------------------
-template <int KMAX, bool BETA_DEV>
+template <int KMAX>
 __global__ __launch_bounds__(NT) void tc_bwd_q_kernel(const float* __restrict__ gz, const float* __restrict__ mu,
                                                       const float* __restrict__ lv, const float* __restrict__ eps,
                                                       const double* __restrict__ lse_joint,
                                                       const float* __restrict__ lse_dim, const float* __restrict__ gloss,
-                                                      float alpha, float beta, const float* __restrict__ beta_dev,
-                                                      float gamma, const float* __restrict__ Gz, float* __restrict__ gmu,
-                                                      float* __restrict__ glv, int B, int D) {
-  if constexpr (BETA_DEV) beta = beta_dev[0];
+                                                      float alpha, Word beta_w, float gamma, const float* __restrict__ Gz,
+                                                      float* __restrict__ gmu, float* __restrict__ glv, int B, int D) {
+  const float beta = read_word(beta_w);
   extern __shared__ float red[];      // [NW][D], used for Gmu and then for Glv
   const int j = blockIdx.x, lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const size_t row_j = (size_t)j * D;
@@ -306,6 +302,7 @@ __global__ __launch_bounds__(NT) void tc_bwd_q_kernel(const float* __restrict__ 
       float slv = red[d];
       for (int w = 1; w < NW; ++w) slv += red[w * D + d];
       const float gzd = Gz[row_j + d];
+      // not reparam_bwd_store: the loss has a gradient through z too (gzd), `eh` serves both and rounds unlike g * e * 0.5f * h
       const float g = gz ? gz[row_j + d] : 0.f;
       const float eh = 0.5f * (eps[row_j + d] * expf(0.5f * lv[row_j + d]));      // d z / d logvar = eps * 0.5 * exp(logvar / 2)
       gmu[row_j + d] = fmaf(gl, smu[k] + gzd, g);
@@ -314,15 +311,13 @@ __global__ __launch_bounds__(NT) void tc_bwd_q_kernel(const float* __restrict__ 
   }
 }
 
-bool dims_ok(int B, int D) { return B >= 1 && B <= MAX_DIM && D >= 1 && D <= MAX_DIM; }
 size_t parts_bytes(int B) { return (size_t)B * 3 * sizeof(double); }
 
-template <bool BETA_DEV>
 int tc_fwd(const float* mu, const float* lv, const float* eps, float* z, float* out4, double* lse_joint, float* lse_dim,
-           int B, int D, float alpha, float beta, const float* beta_dev, float gamma, float log_bn, void* workspace,
-           size_t workspace_bytes, hipStream_t st) {
+           int B, int D, float alpha, Word beta, float gamma, float log_bn, void* workspace, size_t workspace_bytes,
+           hipStream_t st) {
   if (!mu || !lv || !eps || !z || !out4 || !lse_joint || !lse_dim || !workspace || !dims_ok(B, D)) return VG_ERR_BAD_ARG;
-  if (BETA_DEV && !beta_dev) return VG_ERR_BAD_ARG;
+  if (!words_ok(beta)) return VG_ERR_BAD_ARG;
   if (workspace_bytes < vg_reparam_tc_workspace_bytes(B, D)) return VG_ERR_WORKSPACE;
   double* parts = (double*)workspace;
   const size_t lds = (size_t)NW * D * sizeof(float);
@@ -331,34 +326,32 @@ int tc_fwd(const float* mu, const float* lv, const float* eps, float* z, float* 
   else
     hipLaunchKernelGGL(tc_fwd_kernel<16>, dim3(B), dim3(NT), lds, st, mu, lv, eps, z, lse_joint, lse_dim, parts, B, D, log_bn);
   VG_CHECK_LAUNCH();
-  hipLaunchKernelGGL(tc_sum_kernel<BETA_DEV>, dim3(1), dim3(64), 0, st, (const double*)parts, B, alpha, beta, beta_dev,
-                     gamma, out4);
+  hipLaunchKernelGGL(tc_sum_kernel, dim3(1), dim3(64), 0, st, (const double*)parts, B, alpha, beta, gamma, out4);
   VG_CHECK_LAUNCH();
   return 0;
 }
 
-template <bool BETA_DEV>
 int tc_bwd(const float* gz, const float* mu, const float* lv, const float* eps, const float* z, const double* lse_joint,
-           const float* lse_dim, const float* gloss, float alpha, float beta, const float* beta_dev, float gamma, float* gmu,
-           float* glv, int B, int D, void* workspace, size_t workspace_bytes, hipStream_t st) {
+           const float* lse_dim, const float* gloss, float alpha, Word beta, float gamma, float* gmu, float* glv, int B, int D,
+           void* workspace, size_t workspace_bytes, hipStream_t st) {
   if (!mu || !lv || !eps || !z || !lse_joint || !lse_dim || !gmu || !glv || !workspace || !dims_ok(B, D)) return VG_ERR_BAD_ARG;
-  if (BETA_DEV && !beta_dev) return VG_ERR_BAD_ARG;
+  if (!words_ok(beta)) return VG_ERR_BAD_ARG;
   if (workspace_bytes < vg_reparam_tc_workspace_bytes(B, D)) return VG_ERR_WORKSPACE;
   if (!gloss) return reparam_bwd_gz_only(gz, lv, eps, gmu, glv, B, D, st);
   float* Gz = (float*)((char*)workspace + parts_bytes(B));
   const size_t lds = (size_t)NW * D * sizeof(float);
   if (D <= 128) {
-    hipLaunchKernelGGL((tc_bwd_z_kernel<2, BETA_DEV>), dim3(B), dim3(NT), lds, st, mu, lv, eps, z, lse_joint, lse_dim, alpha,
-                       beta, beta_dev, gamma, Gz, B, D);
+    hipLaunchKernelGGL(tc_bwd_z_kernel<2>, dim3(B), dim3(NT), lds, st, mu, lv, eps, z, lse_joint, lse_dim, alpha, beta, gamma,
+                       Gz, B, D);
     VG_CHECK_LAUNCH();
-    hipLaunchKernelGGL((tc_bwd_q_kernel<2, BETA_DEV>), dim3(B), dim3(NT), lds, st, gz, mu, lv, eps, lse_joint, lse_dim,
-                       gloss, alpha, beta, beta_dev, gamma, (const float*)Gz, gmu, glv, B, D);
+    hipLaunchKernelGGL(tc_bwd_q_kernel<2>, dim3(B), dim3(NT), lds, st, gz, mu, lv, eps, lse_joint, lse_dim, gloss, alpha, beta,
+                       gamma, (const float*)Gz, gmu, glv, B, D);
   } else {
-    hipLaunchKernelGGL((tc_bwd_z_kernel<16, BETA_DEV>), dim3(B), dim3(NT), lds, st, mu, lv, eps, z, lse_joint, lse_dim, alpha,
-                       beta, beta_dev, gamma, Gz, B, D);
+    hipLaunchKernelGGL(tc_bwd_z_kernel<16>, dim3(B), dim3(NT), lds, st, mu, lv, eps, z, lse_joint, lse_dim, alpha, beta, gamma,
+                       Gz, B, D);
     VG_CHECK_LAUNCH();
-    hipLaunchKernelGGL((tc_bwd_q_kernel<16, BETA_DEV>), dim3(B), dim3(NT), lds, st, gz, mu, lv, eps, lse_joint, lse_dim,
-                       gloss, alpha, beta, beta_dev, gamma, (const float*)Gz, gmu, glv, B, D);
+    hipLaunchKernelGGL(tc_bwd_q_kernel<16>, dim3(B), dim3(NT), lds, st, gz, mu, lv, eps, lse_joint, lse_dim, gloss, alpha, beta,
+                       gamma, (const float*)Gz, gmu, glv, B, D);
   }
   VG_CHECK_LAUNCH();
   return 0;
@@ -374,29 +367,29 @@ extern "C" size_t vg_reparam_tc_workspace_bytes(int B, int D) {
 extern "C" int vg_reparam_tc_fwd(const float* mu, const float* logvar, const float* eps, float* z, float* out4,
                                  double* lse_joint, float* lse_dim, int B, int D, float alpha, float beta, float gamma,
                                  float log_bn, void* workspace, size_t workspace_bytes, void* stream) {
-  return tc_fwd<false>(mu, logvar, eps, z, out4, lse_joint, lse_dim, B, D, alpha, beta, nullptr, gamma, log_bn, workspace,
-                       workspace_bytes, (hipStream_t)stream);
+  return tc_fwd(mu, logvar, eps, z, out4, lse_joint, lse_dim, B, D, alpha, word(beta), gamma, log_bn, workspace, workspace_bytes,
+                (hipStream_t)stream);
 }
 
 extern "C" int vg_reparam_tc_fwd_dev(const float* mu, const float* logvar, const float* eps, float* z, float* out4,
                                      double* lse_joint, float* lse_dim, int B, int D, float alpha, const float* beta_dev,
                                      float gamma, float log_bn, void* workspace, size_t workspace_bytes, void* stream) {
-  return tc_fwd<true>(mu, logvar, eps, z, out4, lse_joint, lse_dim, B, D, alpha, 0.f, beta_dev, gamma, log_bn, workspace,
-                      workspace_bytes, (hipStream_t)stream);
+  return tc_fwd(mu, logvar, eps, z, out4, lse_joint, lse_dim, B, D, alpha, word_at(beta_dev), gamma, log_bn, workspace,
+                workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int vg_reparam_tc_bwd(const float* gz, const float* mu, const float* logvar, const float* eps, const float* z,
                                  const double* lse_joint, const float* lse_dim, const float* gloss, float alpha, float beta,
                                  float gamma, float* gmu, float* glogvar, int B, int D, void* workspace,
                                  size_t workspace_bytes, void* stream) {
-  return tc_bwd<false>(gz, mu, logvar, eps, z, lse_joint, lse_dim, gloss, alpha, beta, nullptr, gamma, gmu, glogvar, B, D,
-                       workspace, workspace_bytes, (hipStream_t)stream);
+  return tc_bwd(gz, mu, logvar, eps, z, lse_joint, lse_dim, gloss, alpha, word(beta), gamma, gmu, glogvar, B, D, workspace,
+                workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int vg_reparam_tc_bwd_dev(const float* gz, const float* mu, const float* logvar, const float* eps,
                                      const float* z, const double* lse_joint, const float* lse_dim, const float* gloss,
                                      float alpha, const float* beta_dev, float gamma, float* gmu, float* glogvar, int B, int D,
                                      void* workspace, size_t workspace_bytes, void* stream) {
-  return tc_bwd<true>(gz, mu, logvar, eps, z, lse_joint, lse_dim, gloss, alpha, 0.f, beta_dev, gamma, gmu, glogvar, B, D,
-                      workspace, workspace_bytes, (hipStream_t)stream);
+  return tc_bwd(gz, mu, logvar, eps, z, lse_joint, lse_dim, gloss, alpha, word_at(beta_dev), gamma, gmu, glogvar, B, D, workspace,
+                workspace_bytes, (hipStream_t)stream);
 }

@@ -1,15 +1,18 @@
-"""SHA-256 of everything the KL-phase objectives compute (beta-TCVAE, DIP-VAE I / II, InfoVAE / WAE-MMD), from seeded inputs:
-what a change that must not move a bit is compared by.  A few seconds on the GPU.
+"""SHA-256 of everything the KL-phase objectives compute (beta-TCVAE, DIP-VAE I / II, InfoVAE / WAE-MMD, the KL capacity, the
+plain KL term, FactorVAE's encoder loss), from seeded inputs: what a change that must not move a bit is compared by.  A few
+seconds on the GPU.
 
   ops       `ops.reparam_<tc|dip|mmd>_fwd` / `_bwd` at (B, D) = (2, 1), (3, 5), (33, 65), (64, 128), (130, 129) -- the smallest
             legal batch, ragged strips and tiles, one full tile pair with a mirrored tile, TC's D > 128 instantiation -- with
             ``beta`` a float and the device word, DIP variants i and ii, MMD rbf with the default bandwidth and imq with 8
             bandwidths: z, out4 and the saved tensors of the forward; gmu and glv of the backward with ``gz`` and ``gloss``
-            each present and absent.
+            each present and absent.  `reparam_klc` at the same shapes with beta AND the capacity floats or words, free
+            bits 0 and 0.05, the capacity at half and at twice the floored total (`KLC_CASES`); `reparam_kl` with its row
+            sums; `factor_tc` forward and backward at `FACTOR_ROWS` rows -- 1, one below and one above the workgroup's 256.
   function  the same cases through `functional.reparam_*` and autograd: z, loss, parts and the two ``.grad``s (the loss and
             z both backpropagated).
   trainer   four iterations of `VAETrainer` at B = 8, graph on (two eager, the capture's first replay, one more replay),
-            with each objective and with none: every value of every returned loss dict and the final weights.
+            with each objective (the KL capacity constant and annealed, FactorVAE with its critic) and with none: every value of every returned loss dict and the final weights.
 
     objective_bits.py [--tree DIR] [--out out.json]
 
@@ -28,9 +31,15 @@ CASES = {      # name -> (objective, what follows ``beta`` in the forward op, wh
     "mmd_imq8": ("mmd", lambda B: (100.0, "imq", (0.5, 1.0, 2.0, 4.0, 8.0, 16.0, 32.0, 64.0)),
                  (100.0, "imq", (0.5, 1.0, 2.0, 4.0, 8.0, 16.0, 32.0, 64.0))),
 }
+KLC_CASES = {f"klc_f{f}_fb{fb}": (f, fb) for f in (0.5, 2.0) for fb in (0.0, 0.05)}      # name -> (capacity / floored total, free bits)
+FACTOR_ROWS = (1, 255, 257)
+GAMMA = 35.0
 TRAINER_CASES = {"none": {}, "tc": dict(tc_decomposition=(1.0, 0.5), dataset_size=1000), "dip_i": dict(dip_vae=("i", 10.0, 100.0)),
                  "dip_ii": dict(dip_vae=("ii", 10.0, 5.0)), "mmd_rbf": dict(mmd_vae=("rbf", 1000.0)),
-                 "mmd_imq8": dict(mmd_vae=("imq", 100.0, (0.5, 1.0, 2.0, 4.0, 8.0, 16.0, 32.0, 64.0)))}
+                 "mmd_imq8": dict(mmd_vae=("imq", 100.0, (0.5, 1.0, 2.0, 4.0, 8.0, 16.0, 32.0, 64.0))),
+                 "klc_constant": dict(kl_control=(5.0, 0.05)),
+                 "klc_annealed": dict(kl_control=(lambda it: 25.0 * min(it, 3) / 3.0, 0.0)),
+                 "factor": dict(factor_vae=GAMMA)}
 
 
 def sha(t):
@@ -46,8 +55,86 @@ def inputs(torch, B, D):
     return {k: v.cuda() for k, v in i.items()}
 
 
-def run_ops(torch, ops):
+def word_or_float(torch, kind, v):
+    return v if kind == "float" else torch.full((1,), v, device="cuda")
+
+
+def klc_capacity(i, f, free_bits):
+    """f times the floored total of the KL per sample, from the inputs in fp64 on the CPU, rounded to fp32"""
+    import numpy as np
+    mu, lv = i["mu"].double().cpu(), i["lv"].double().cpu()
+    K = (-0.5 * (1.0 + lv - mu ** 2 - lv.exp())).sum(0)
+    return float(np.float32(f * float(K.clamp(min=mu.shape[0] * free_bits).sum()) / mu.shape[0]))
+
+
+def grads_of(bwd, i):
+    """the backward with ``gz`` and ``gloss`` each present and absent: bwd(gz, gloss) -> (gmu, glv)"""
+    d = {}
+    for gz in (i["gz"], None):
+        for gloss in (i["gloss"], None):
+            gmu, glv = bwd(gz, gloss)
+            tag = f"gz{int(gz is not None)}_gloss{int(gloss is not None)}"
+            d[f"gmu_{tag}"], d[f"glv_{tag}"] = sha(gmu), sha(glv)
+    return d
+
+
+def run_ops_words(torch, ops):
+    """The kernels whose scheduled words do not fit `CASES`: two words (klc, factor_tc), or no objective (reparam_kl)."""
     out = {}
+    for B, D in SHAPES:
+        i = inputs(torch, B, D)
+        for kind in ("float", "word"):
+            beta = word_or_float(torch, kind, BETA)
+            z, kl, rows = ops.reparam_kl_fwd(i["mu"], i["lv"], i["eps"], beta, want_rows=True)
+            out[f"{B}x{D}/kl/beta_{kind}"] = {"z": sha(z), "kl": sha(kl), "rows": sha(rows), **grads_of(
+                lambda gz, gkl: ops.reparam_kl_bwd(gz, i["mu"], i["lv"], i["eps"], gkl, beta), i)}
+            for name, (f, fb) in KLC_CASES.items():
+                cap = word_or_float(torch, kind, klc_capacity(i, f, fb))
+                z, out4, gate, kl_dim = ops.reparam_klc_fwd(i["mu"], i["lv"], i["eps"], beta, cap, fb)
+                out[f"{B}x{D}/{name}/words_{kind}"] = {"z": sha(z), "out4": sha(out4), "gate": sha(gate), "kl_dim": sha(kl_dim), **grads_of(
+                    lambda gz, gloss: ops.reparam_klc_bwd(gz, i["mu"], i["lv"], i["eps"], gate, gloss, beta, cap, fb), i)}
+    for rows in FACTOR_ROWS:
+        g = torch.Generator().manual_seed(rows)
+        logits, kl, gloss = torch.randn(rows, 2, generator=g).cuda(), torch.tensor(3.25).cuda(), torch.tensor(0.75).cuda()
+        for kind in ("float", "word"):
+            beta, gamma = word_or_float(torch, kind, BETA), word_or_float(torch, kind, GAMMA)
+            glogits, gkl = ops.factor_tc_bwd(logits, gloss, beta, gamma)
+            out[f"{rows}/factor_tc/words_{kind}"] = {"out4": sha(ops.factor_tc_fwd(logits, kl, beta, gamma)), "glogits": sha(glogits),
+                                                     "gkl": sha(gkl)}
+    return out
+
+
+def run_function_words(torch, F):
+    out = {}
+    for B, D in SHAPES:
+        i = inputs(torch, B, D)
+        i["mu"].requires_grad_(True), i["lv"].requires_grad_(True)
+        for kind in ("float", "word"):
+            beta = word_or_float(torch, kind, BETA)
+            calls = {"kl": lambda: F.reparam_kl(i["mu"], i["lv"], i["eps"], beta)}
+            for name, (f, fb) in KLC_CASES.items():
+                cap = word_or_float(torch, kind, klc_capacity(i, f, fb))
+                calls[name] = lambda cap=cap, fb=fb: F.reparam_klc_dims(i["mu"], i["lv"], i["eps"], beta, cap, fb)
+            for name, fn in calls.items():
+                i["mu"].grad = i["lv"].grad = None
+                z, loss, *rest = fn()
+                torch.autograd.backward([loss, z], grad_tensors=[i["gloss"], i["gz"]])
+                out[f"{B}x{D}/{name}/words_{kind}"] = {"z": sha(z), "loss": sha(loss), **{f"rest{n}": sha(t) for n, t in enumerate(rest)},
+                                                      "mu.grad": sha(i["mu"].grad), "lv.grad": sha(i["lv"].grad)}
+    for rows in FACTOR_ROWS:
+        g = torch.Generator().manual_seed(rows)
+        logits, kl = torch.randn(rows, 2, generator=g).cuda().requires_grad_(True), torch.tensor(3.25).cuda().requires_grad_(True)
+        for kind in ("float", "word"):
+            logits.grad = kl.grad = None
+            loss, parts = F.factor_tc(logits, kl, word_or_float(torch, kind, BETA), word_or_float(torch, kind, GAMMA))
+            loss.backward(torch.tensor(0.75).cuda())
+            out[f"{rows}/factor_tc/words_{kind}"] = {"loss": sha(loss), "parts": sha(parts), "logits.grad": sha(logits.grad),
+                                                     "kl.grad": sha(kl.grad)}
+    return out
+
+
+def run_ops(torch, ops):
+    out = run_ops_words(torch, ops)
     for B, D in SHAPES:
         i = inputs(torch, B, D)
         for name, (obj, fwd_args, bwd_args) in CASES.items():
@@ -73,7 +160,7 @@ def run_function(torch, F):
             "dip_ii": lambda i, beta: F.reparam_dip(i["mu"], i["lv"], i["eps"], beta, 10.0, 5.0, "ii"),
             "mmd_rbf": lambda i, beta: F.reparam_mmd(i["mu"], i["lv"], i["eps"], i["zp"], beta, 1000.0, "rbf"),
             "mmd_imq8": lambda i, beta: F.reparam_mmd(i["mu"], i["lv"], i["eps"], i["zp"], beta, 100.0, "imq", CASES["mmd_imq8"][2][2])}
-    out = {}
+    out = run_function_words(torch, F)
     for B, D in SHAPES:
         i = inputs(torch, B, D)
         i["mu"].requires_grad_(True), i["lv"].requires_grad_(True)

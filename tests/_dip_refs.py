@@ -5,22 +5,12 @@ same inputs).  `closed_form_grads` is the hand-derived gradient the kernels impl
 CPU."""
 import torch
 
-from _tc_refs import bound, rel_err  # noqa: F401  (the project's convention, shared with the beta-TCVAE tests)
+from _reparam_refs import bound, expected_grads, gz_grads, make_inputs, rel_err  # noqa: F401  (shared by the four objectives)
 
 BETA = 6.0
 CASES = [("i", 10.0, 100.0), ("ii", 10.0, 10.0), ("ii", 0.5, 4.0)]      # (variant, lambda_od, lambda_d)
 SHAPES = [(1, 1), (2, 3), (5, 7), (17, 65), (64, 128), (128, 128), (130, 200), (256, 128), (3, 600)]
 COMPARED = ("z", "loss", "kl", "od", "dg", "cov", "gmu_loss", "glv_loss")
-
-
-def make_inputs(B, D, seed=0):
-    """mu ~ N(0,1); logvar ~ N(-1, 1.5^2) clamped to [-6, 2]; eps ~ N(0,1); gz ~ N(0,1) (a decoder's gradient); fp32."""
-    g = torch.Generator().manual_seed(1000 * B + D + seed)
-    mu = torch.randn(B, D, generator=g)
-    lv = (torch.randn(B, D, generator=g) * 1.5 - 1.0).clamp_(-6.0, 2.0)
-    eps = torch.randn(B, D, generator=g)
-    gz = torch.randn(B, D, generator=g)
-    return dict(mu=mu, lv=lv, eps=eps, gz=gz)
 
 
 def covariance(mu, lv, variant):
@@ -68,24 +58,6 @@ def reparam_dip(mu, lv, eps, beta, variant, lambda_od, lambda_d, dtype=torch.flo
     gmu, glv = torch.autograd.grad(o["loss"], (mu, lv), allow_unused=True)
     glv = torch.zeros_like(lv) if glv is None else glv
     return dict(z=z.detach(), gmu_loss=gmu, glv_loss=glv, **{k: v.detach() for k, v in o.items()})
-
-
-def gz_grads(lv, eps, gz, dtype=torch.float64):
-    """The decoder's gradient through z = mu + eps exp(lv / 2): (gmu, glv)."""
-    lv, eps, gz = (t.detach().to(dtype) for t in (lv, eps, gz))
-    return gz, gz * eps * 0.5 * torch.exp(0.5 * lv)
-
-
-def expected_grads(ref, lv, eps, gz=None, gloss=None, dtype=torch.float64):
-    """What vg_reparam_dip_bwd writes for the upstream pair (gz or None, gloss as a float or None)."""
-    gmu = torch.zeros_like(ref["gmu_loss"])
-    glv = torch.zeros_like(ref["glv_loss"])
-    if gloss is not None:
-        gmu, glv = gmu + gloss * ref["gmu_loss"], glv + gloss * ref["glv_loss"]
-    if gz is not None:
-        a, b = gz_grads(lv, eps, gz, dtype)
-        gmu, glv = gmu + a, glv + b
-    return gmu, glv
 
 
 def closed_form_grads(mu, lv, beta, variant, lambda_od, lambda_d, dtype=torch.float64):

@@ -6,7 +6,7 @@ kernels implement -- the gate formula -- checked against autograd on the CPU."""
 import torch
 
 from _dip_refs import SHAPES  # noqa: F401  (the same shapes as the DIP-VAE tests)
-from _tc_refs import bound, rel_err  # noqa: F401  (the project's convention, shared with the beta-TCVAE tests)
+from _reparam_refs import bound, expected_grads, gz_grads, rel_err  # noqa: F401  (shared by the four objectives)
 
 BETA = 6.0
 # (f, lambda): the capacity is C = f * T64 / B with T64 the fp64 floored total of that input -- below, at (f = 0: far
@@ -75,24 +75,6 @@ def reparam_klc(mu, lv, eps, beta, capacity, free_bits, dtype=torch.float64):
     glv = torch.zeros_like(lv) if glv is None else glv
     return dict(z=z.detach(), gmu_loss=gmu, glv_loss=glv, gate=gate(mu.detach(), lv.detach(), capacity, free_bits),
                 **{k: v.detach() for k, v in o.items()})
-
-
-def gz_grads(lv, eps, gz, dtype=torch.float64):
-    """The decoder's gradient through z = mu + eps exp(lv / 2): (gmu, glv)."""
-    lv, eps, gz = (t.detach().to(dtype) for t in (lv, eps, gz))
-    return gz, gz * eps * 0.5 * torch.exp(0.5 * lv)
-
-
-def expected_grads(ref, lv, eps, gz=None, gloss=None, dtype=torch.float64):
-    """What vg_reparam_klc_bwd writes for the upstream pair (gz or None, gloss as a float or None)."""
-    gmu = torch.zeros_like(ref["gmu_loss"])
-    glv = torch.zeros_like(ref["glv_loss"])
-    if gloss is not None:
-        gmu, glv = gmu + gloss * ref["gmu_loss"], glv + gloss * ref["glv_loss"]
-    if gz is not None:
-        a, b = gz_grads(lv, eps, gz, dtype)
-        gmu, glv = gmu + a, glv + b
-    return gmu, glv
 
 
 def gate(mu, lv, capacity, free_bits):

@@ -8,7 +8,7 @@ gradient the kernels implement, checked against autograd on the CPU.
 terms (`mmd_terms` / `loss_terms`), not over the value: at (64, 128), imq, mmd is 0.12 against terms of 12.4."""
 import torch
 
-from _tc_refs import bound, rel_err  # noqa: F401  (the project's convention, shared with the beta-TCVAE tests)
+from _reparam_refs import bound, expected_grads, gz_grads, rel_err  # noqa: F401  (shared by the four objectives)
 
 LAMBDA = 1000.0
 CASES = [("rbf", None, LAMBDA, 6.0), ("imq", None, LAMBDA, 6.0), ("imq", None, LAMBDA, 0.0)]   # (kernel, bandwidths, lambda, beta)
@@ -97,24 +97,6 @@ def scalar_err(got, ref, scale):
 def scalar_bound(r32, r64, name):
     """The project's convention for ``mmd`` and ``loss``, errors over the reference's ``<name>_terms``."""
     return max(1e-6, 5.0 * scalar_err(r32[name], r64[name], r64[name + "_terms"]))
-
-
-def gz_grads(lv, eps, gz, dtype=torch.float64):
-    """The decoder's gradient through z = mu + eps exp(lv / 2): (gmu, glv)."""
-    lv, eps, gz = (t.detach().to(dtype) for t in (lv, eps, gz))
-    return gz, gz * eps * 0.5 * torch.exp(0.5 * lv)
-
-
-def expected_grads(ref, lv, eps, gz=None, gloss=None, dtype=torch.float64):
-    """What vg_reparam_mmd_bwd writes for the upstream pair (gz or None, gloss as a float or None)."""
-    gmu = torch.zeros_like(ref["gmu_loss"])
-    glv = torch.zeros_like(ref["glv_loss"])
-    if gloss is not None:
-        gmu, glv = gmu + gloss * ref["gmu_loss"], glv + gloss * ref["glv_loss"]
-    if gz is not None:
-        a, b = gz_grads(lv, eps, gz, dtype)
-        gmu, glv = gmu + a, glv + b
-    return gmu, glv
 
 
 def closed_form_grads(mu, lv, eps, zp, beta, kernel, lambda_mmd, bandwidths=None, dtype=torch.float64):

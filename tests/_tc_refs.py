@@ -7,20 +7,12 @@ import math
 
 import torch
 
+from _reparam_refs import bound, expected_grads, gz_grads, make_inputs, rel_err  # noqa: F401  (shared by the four objectives)
+
 LOG_2PI = math.log(2.0 * math.pi)
 DATASET_SIZE = 162770                  # the N of the tests (CelebA's training split)
 WEIGHTS = [(1.0, 6.0, 1.0), (0.5, 4.0, 2.0)]      # (alpha, beta, gamma)
 SHAPES = [(1, 1), (2, 3), (5, 7), (17, 65), (64, 128), (128, 128), (130, 200), (256, 128)]
-
-
-def make_inputs(B, D, seed=0):
-    """mu ~ N(0,1); logvar ~ N(-1, 1.5^2) clamped to [-6, 2]; eps ~ N(0,1); gz ~ N(0,1) (a decoder's gradient); fp32."""
-    g = torch.Generator().manual_seed(1000 * B + D + seed)
-    mu = torch.randn(B, D, generator=g)
-    lv = (torch.randn(B, D, generator=g) * 1.5 - 1.0).clamp_(-6.0, 2.0)
-    eps = torch.randn(B, D, generator=g)
-    gz = torch.randn(B, D, generator=g)
-    return dict(mu=mu, lv=lv, eps=eps, gz=gz)
 
 
 def pair_terms(z, mu, lv):
@@ -62,24 +54,6 @@ def reparam_tc(mu, lv, eps, alpha, beta, gamma, dataset_size=DATASET_SIZE, dtype
                 glv_loss=glv)
 
 
-def gz_grads(lv, eps, gz, dtype=torch.float64):
-    """The decoder's gradient through z = mu + eps exp(lv / 2): (gmu, glv)."""
-    lv, eps, gz = (t.detach().to(dtype) for t in (lv, eps, gz))
-    return gz, gz * eps * 0.5 * torch.exp(0.5 * lv)
-
-
-def expected_grads(ref, lv, eps, gz=None, gloss=None, dtype=torch.float64):
-    """What vg_reparam_tc_bwd writes for the upstream pair (gz or None, gloss as a float or None)."""
-    gmu = torch.zeros_like(ref["gmu_loss"])
-    glv = torch.zeros_like(ref["glv_loss"])
-    if gloss is not None:
-        gmu, glv = gmu + gloss * ref["gmu_loss"], glv + gloss * ref["glv_loss"]
-    if gz is not None:
-        a, b = gz_grads(lv, eps, gz, dtype)
-        gmu, glv = gmu + a, glv + b
-    return gmu, glv
-
-
 def closed_form_grads(mu, lv, eps, alpha, beta, gamma, dtype=torch.float64):
     """The gradient as the kernels form it (gloss = 1, no gz): softmax weights w, v -> Gz, Gmu, Glv -> (gmu, glv)."""
     mu, lv, eps = (t.detach().to(dtype) for t in (mu, lv, eps))
@@ -96,14 +70,3 @@ def closed_form_grads(mu, lv, eps, alpha, beta, gamma, dtype=torch.float64):
     Gmu = (c * r).sum(0)
     Glv = (c * (-0.5 + 0.5 * r * diff)).sum(0)
     return Gmu + Gz, Glv + Gz * eps * 0.5 * h
-
-
-def rel_err(got, ref):
-    """max |got - ref| over the reference's largest magnitude."""
-    got, ref = torch.as_tensor(got).double().cpu(), torch.as_tensor(ref).double().cpu()
-    return float((got - ref).abs().max()) / max(float(ref.abs().max()), 1e-30)
-
-
-def bound(ref32, ref64):
-    """The project's convention (conftest.check_state, SURVEY KAT-0): max(1e-6, 5 x the fp32 restatement's own error)."""
-    return max(1e-6, 5.0 * rel_err(ref32, ref64))
